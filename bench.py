@@ -30,6 +30,9 @@ other keys, so everything a reader of that record needs is inside those three; f
   multi_gpu_programs - N>1 only, rank 0, after the timed region: the pure-C++ multi-process programs for configs[3] and configs[4]
                  (token-sharded transformer block) over the same GPUs, each checked against its world-size-1 / plaintext answer.
 
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last one returned (the reduced ciphertext, and a seeded sample of 32 of
+the shard's products) as float64 .npy files under DIR, so that two builds run with the same arguments can be compared output for output.
+
 `--dry-run` (CPU, gloo): walks every collective, barrier and rank-0 report of the N>1 path with the kernels stood in by host
 arithmetic - `python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --dry-run` (tests/test_bench_dry_run.py).
 """
@@ -354,7 +357,14 @@ def main():
                     help="form of the fused multiply: auto = measured on this box (library probe + three timed steps per form), or forced")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not profile the multiply's HBM traffic with rocprofv3 after the timed region (roofline.traffic then quotes the committed profile)")
     ap.add_argument("--dry-run", action="store_true", help="CPU + gloo: walk the multi-rank host path (collectives, barriers, report) without kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned, as float64 .npy: DIR/total.npy = the reduced ciphertext [3][L][N], "
+                         "DIR/products.npy = the products of 32 pairs of its shard drawn with numpy seed 0, sorted [32][3][L][N] (13 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the kernels: the dry run computes stand-ins")
     if args.dry_run:
         return dry_run(args)
 
@@ -953,6 +963,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # --dump-outputs: what a caller of the timed step receives from its last step, so that two builds can be compared output for output.  Taken
+    # here, before anything below reuses the step's buffers.  The inputs are seeded (1000 + rank), so the same arguments give the same words.
+    # Residues are < 2^60: float64 keeps their top 53 bits.
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        sampled = np.sort(np.random.default_rng(0).choice(B, size=min(B, 32), replace=False))
+        arrays = {"total": totals[last], "products": out[torch.from_numpy(sampled).to(dev)]}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t_ in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), to_host(t_).astype(np.float64))
+        dumped = {"dir": args.dump_outputs, "arrays": {name: list(t_.shape) for name, t_ in arrays.items()}, "products_pairs": sampled.tolist()}
+
     # SURVEY.md section 8(e)'s alternative exchange, measured next to the timed one whenever there is more than one rank (after the timed region: `value`
     # is the all-gather step's): the SAME step with a 64-bit sum all-reduce of the partials + one mod-q pass instead of all-gather + local sum.
     collective_ab = None
@@ -1100,6 +1122,8 @@ def main():
         result["collective_ab"] = collective_ab
     rates = [B * args.steps / e for e in per_rank_elapsed]
     result["per_rank_ct_mul_per_s"] = {"min": min(rates), "max": max(rates), "ranks": len(rates)}
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     detail = {}
     if ntt_result is not None:
         # BASELINE.json metric, second half ("NTT HBM GB/s vs peak"), where the driver's record keeps it: configs[1] in place, the

@@ -56,6 +56,13 @@ def test_bench_refuses_a_world_size_mismatch():
     assert run.returncode != 0 and "torch.distributed.run" in (run.stdout + run.stderr)
 
 
+@pytest.mark.parametrize("args", [["--steps", "0"], ["--warmup", "-1"], ["--dump-outputs", "out", "--dry-run"]])
+def test_bench_refuses_arguments_it_cannot_honour(args, tmp_path):
+    """--steps is the number of timed steps (at least one: the reported outputs are the last step's); the dry run has no outputs to dump."""
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    assert run.returncode == 2 and "error:" in run.stderr and not os.path.exists(tmp_path / "out")
+
+
 def test_run_program_kills_the_whole_process_group_on_timeout(tmp_path):
     """bench.run_program: the C++ multi-GPU programs fork one process per GPU; a timeout has to take the children down with the parent."""
     import time

@@ -716,6 +716,35 @@ def test_bench_distributed_path_world_size_one():
     assert d["reduce_consistent"] is True and "dpfhe_comm_allgather" in d["config"]["collective"]
 
 
+def test_bench_dump_outputs_are_the_oracles_words_for_the_seeded_inputs(tmp_path):
+    """bench.py --dump-outputs: the last timed step's total and its sampled products, as float64, equal the oracle's for the bench's seeded inputs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, out_dir = 64, tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-per-gpu", str(B), "--no-cpu-baseline",
+           "--skip-other", "--no-live-traffic", "--sustained-seconds", "0", "--dump-outputs", str(out_dir)]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    d = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
+    pairs = d["dumped_outputs"]["products_pairs"]
+    assert d["steps"] == 2 and len(pairs) == 32 and pairs == sorted(set(pairs)) and 0 <= pairs[0] and pairs[-1] < B
+    total, products = np.load(out_dir / "total.npy"), np.load(out_dir / "products.npy")
+    assert total.dtype == products.dtype == np.float64 and sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 << 20
+    # the bench's inputs, regenerated (seed 1000 + rank)
+    p = FheParams.n4096_l4()
+    L, n = p.n_limbs, p.n
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(1000)
+    q = torch.tensor(p.moduli, dtype=torch.int64, device=dev).view(1, 1, L, 1)
+    ah = to_host(torch.randint(0, 2**62, (B, 2, L, n), generator=g, dtype=torch.int64, device=dev) % q)
+    bh = to_host(torch.randint(0, 2**62, (B, 2, L, n), generator=g, dtype=torch.int64, device=dev) % q)
+    orc = Oracle.from_params(p)
+    want = orc.ct_mul(ah, bh, threads=0)
+    assert np.array_equal(products, want[pairs].astype(np.float64))
+    assert np.array_equal(total, orc.reduce_sum(want, 3).astype(np.float64))
+
+
 def test_config3_full_size_matvec_linearity_and_whole_buffer_oracle(rigs):
     """BASELINE configs[2]: hidden = 768 rows, 64 input ciphertexts, N=4096, L=4 (6 GiB of plaintext weights)."""
     r = rigs("n4096")
