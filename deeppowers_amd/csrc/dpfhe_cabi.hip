@@ -21,6 +21,7 @@
 
 #include "../../include/dpfhe.h"
 #include "base_ext.h"
+#include "expand.h"
 #include "kernels_large.h"
 #include "kernels_misc.h"
 #include "launch.h"
@@ -1623,6 +1624,43 @@ extern "C" int dpfhe_copy(dpfhe_ctx* c, uint64_t* d_dst, const uint64_t* d_src, 
         hipLaunchKernelGGL(copy_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), reinterpret_cast<U64x2*>(d_dst),
                            reinterpret_cast<const U64x2*>(d_src), n_vec);
     return check_launch("copy kernel launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// seeded uniform polynomials (expand.h, k_expand.hip): component `component` of items 0 .. batch-1 = expand(seed, first_item + b, limb, component)
+static int expand_args(const char* what, const void* buf, size_t components, uint32_t component, const uint8_t* seed, uint64_t first_item, size_t batch,
+                       ExpandKey& key) {
+    if (!buf || !seed) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or seed");
+    if (component >= components) return fail(DPFHE_INVALID_ARGUMENT, what, "component must be < components");
+    if (first_item > ((uint64_t)1 << 32) || batch > ((uint64_t)1 << 32) - first_item) return fail(DPFHE_INVALID_ARGUMENT, what, "first_item + batch must be <= 2^32");
+    std::memcpy(key.w, seed, 32);   // little-endian words (x86-64 and gfx950 hosts)
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_expand_uniform(dpfhe_ctx* c, uint64_t* d_buf, size_t batch, size_t components, uint32_t component, const uint8_t seed[32],
+                                    uint64_t first_item, void* stream) {
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "null context");
+    ExpandKey key;
+    if (int rc = expand_args("dpfhe_expand_uniform", d_buf, components, component, seed, first_item, batch, key)) return rc;
+    if (misaligned(d_buf)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "misaligned buffer");
+    if (batch == 0) return DPFHE_SUCCESS;
+    DPFHE_ON_DEVICE(c, "dpfhe_expand_uniform");
+    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;   // q and floor(2^128 / q) of every limb, whatever its class
+    if (launch_expand_uniform((int)c->log2n, d_buf, batch, components, component, c->n_limbs, lc, key, (uint32_t)first_item, static_cast<hipStream_t>(stream)))
+        return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "batch too large for one launch");
+    return check_launch("expand_uniform kernel launch");
+}
+
+extern "C" int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t components,
+                                         uint32_t component, const uint8_t seed[32], uint64_t first_item) {
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "null moduli");
+    ExpandKey key;
+    if (int rc = expand_args("dpfhe_expand_uniform_host", out, components, component, seed, first_item, batch, key)) return rc;
+    if (n_limbs == 0 || log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "n_limbs >= 1 and log2_n in [8, 16]");
+    for (uint32_t l = 0; l < n_limbs; ++l)
+        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "moduli must be odd, >= 3 and < 2^60");
+    expand_uniform_host((int)log2_n, moduli, n_limbs, out, batch, components, component, key, (uint32_t)first_item);
+    return DPFHE_SUCCESS;
 }
 
 // ------------------------------------------------------------------------------------------------

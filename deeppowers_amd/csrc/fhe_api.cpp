@@ -218,6 +218,82 @@ void PolyBuffer::load(std::istream& is) {
     impl_->ntt = h.is_ntt != 0;
 }
 
+namespace {
+const char kSeededMagic[8] = {'D', 'P', 'F', 'H', 'E', 's', '1', 0};
+struct SeededHeader {   // DPFHEs1 (wire.py _SHDR): all little-endian
+    char magic[8];
+    uint32_t log2_n, n_limbs;
+    uint64_t batch, components;
+    uint32_t is_ntt, expanded_component;
+    uint64_t first_item;
+    uint8_t seed[32];
+};
+static_assert(sizeof(SeededHeader) == 80, "the DPFHEs1 header is 80 bytes");
+}  // namespace
+
+void PolyBuffer::save_seeded(std::ostream& os, const Seed& seed, uint32_t component, uint64_t first_item) const {
+    const FheParams& p = impl_->ctx->params();
+    const size_t batch = impl_->batch, comps = impl_->comps, poly = p.n_limbs() * p.n();
+    if (component >= comps) throw Exception(ErrorCode::INVALID_ARGUMENT, "save_seeded: component must be < components");
+    // re-expand and compare: a buffer that was overwritten or transformed since it was expanded must not go out under its seed
+    PolyBuffer ref(*impl_->ctx, batch, comps, impl_->ntt);
+    check(dpfhe_expand_uniform(static_cast<dpfhe_ctx*>(impl_->ctx->handle()), ref.data(), batch, comps, component, seed.bytes, first_item, nullptr),
+          "dpfhe_expand_uniform");
+    std::vector<uint64_t> host(impl_->words), want(impl_->words);
+    ref.copy_to_host(want.data());
+    copy_to_host(host.data());
+    for (size_t b = 0; b < batch; ++b) {
+        const size_t off = (b * comps + component) * poly;
+        if (std::memcmp(host.data() + off, want.data() + off, poly * sizeof(uint64_t)) != 0)
+            throw Exception(ErrorCode::INVALID_STATE, "save_seeded: the buffer's component no longer matches its seed (overwritten or transformed)");
+    }
+    SeededHeader h{};
+    std::memcpy(h.magic, kSeededMagic, 8);
+    h.log2_n = p.log2_n; h.n_limbs = (uint32_t)p.n_limbs(); h.batch = batch; h.components = comps;
+    h.is_ntt = impl_->ntt ? 1u : 0u; h.expanded_component = component; h.first_item = first_item;
+    std::memcpy(h.seed, seed.bytes, 32);
+    os.write(reinterpret_cast<const char*>(&h), sizeof h);
+    os.write(reinterpret_cast<const char*>(p.moduli.data()), (std::streamsize)(p.n_limbs() * sizeof(uint64_t)));
+    for (size_t b = 0; b < batch; ++b)
+        for (size_t c = 0; c < comps; ++c)
+            if (c != component) os.write(reinterpret_cast<const char*>(host.data() + (b * comps + c) * poly), (std::streamsize)(poly * sizeof(uint64_t)));
+    if (!os) throw Exception(ErrorCode::RUNTIME_ERROR, "save_seeded: stream write failed");
+}
+
+void PolyBuffer::load_seeded(std::istream& is, Stream* stream) {
+    const FheParams& p = impl_->ctx->params();
+    SeededHeader h{};
+    is.read(reinterpret_cast<char*>(&h), sizeof h);
+    if (!is || std::memcmp(h.magic, kSeededMagic, 8) != 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: not a DPFHEs1 stream");
+    if (h.log2_n != p.log2_n || h.n_limbs != p.n_limbs() || h.batch != impl_->batch || h.components != impl_->comps)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: header does not match this buffer (log2_n / limbs / batch / components)");
+    if (h.expanded_component >= h.components) throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: expanded_component must be < components");
+    if (h.first_item > ((uint64_t)1 << 32) || h.batch > ((uint64_t)1 << 32) - h.first_item)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: first_item + batch must be <= 2^32");
+    std::vector<uint64_t> moduli(h.n_limbs);
+    is.read(reinterpret_cast<char*>(moduli.data()), (std::streamsize)(moduli.size() * sizeof(uint64_t)));
+    if (!is || moduli != p.moduli) throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: moduli differ from this context");
+    const size_t n = p.n(), L = p.n_limbs(), poly = L * n, comps = impl_->comps, kept = comps - 1, comp = h.expanded_component;
+    std::vector<uint64_t> host(impl_->batch * kept * poly);
+    is.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(host.size() * sizeof(uint64_t)));
+    if (!is) throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: truncated stream");
+    for (size_t i = 0; i < host.size(); ++i)
+        if (host[i] >= p.moduli[(i / n) % L]) throw Exception(ErrorCode::INVALID_ARGUMENT, "load_seeded: non-canonical residue in the payload");
+    hip_check(hipSetDevice(impl_->device_id), "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the stored components of every item: the run before the expanded one and the run after it, one strided copy each
+    const size_t row = comps * poly * sizeof(uint64_t), src_row = kept * poly * sizeof(uint64_t);
+    if (comp > 0)
+        hip_check(hipMemcpy2DAsync(impl_->d, row, host.data(), src_row, comp * poly * sizeof(uint64_t), impl_->batch, hipMemcpyHostToDevice, s), "hipMemcpy2DAsync");
+    if (comp + 1 < comps)
+        hip_check(hipMemcpy2DAsync(impl_->d + (comp + 1) * poly, row, host.data() + comp * poly, src_row, (comps - 1 - comp) * poly * sizeof(uint64_t),
+                                   impl_->batch, hipMemcpyHostToDevice, s), "hipMemcpy2DAsync");
+    check(dpfhe_expand_uniform(static_cast<dpfhe_ctx*>(impl_->ctx->handle()), impl_->d, impl_->batch, comps, (uint32_t)comp, h.seed, h.first_item, stream),
+          "dpfhe_expand_uniform");
+    hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");   // `host` is released on return
+    impl_->ntt = h.is_ntt != 0;
+}
+
 Ciphertext::Ciphertext(const Context& ctx, size_t size, size_t batch, bool is_ntt) : PolyBuffer(ctx, batch, size, is_ntt) {
     if (size != 2 && size != 3) throw Exception(ErrorCode::INVALID_ARGUMENT, "Ciphertext: size must be 2 or 3");
 }
@@ -685,14 +761,15 @@ void make_switch_key(const Context& ctx, const SecretKey& sk, Rng& rng, const ui
                      size_t n_digits = 0 /* 0 = all limbs */, const uint64_t* d_target_scaled_ntt = nullptr);
 }  // namespace
 
-void KeyGenerator::create_galois_keys(GaloisKeys& out) {
-    const Context& ctx = *impl_->ctx;
+namespace {
+// NTT(sigma_g(s)): the target of the switching key for Galois element g
+PolyBuffer galois_target_ntt(const Context& ctx, const SecretKey& sk, uint32_t galois_elt) {
     const FheParams& p = ctx.params();
     const size_t n = p.n(), L = p.n_limbs();
-    const std::vector<int8_t>& s = impl_->sk->coefficients();
+    const std::vector<int8_t>& s = sk.coefficients();
     std::vector<int64_t> sg(n, 0);
     for (size_t i = 0; i < n; ++i) {   // sigma_g(s): coefficient i -> index i g mod 2N, negated past N
-        const size_t idx = (i * (size_t)out.galois_elt()) & (2 * n - 1);
+        const size_t idx = (i * (size_t)galois_elt) & (2 * n - 1);
         if (idx < n) sg[idx] = s[i]; else sg[idx - n] = -s[i];
     }
     std::vector<uint64_t> host(L * n);
@@ -703,7 +780,79 @@ void KeyGenerator::create_galois_keys(GaloisKeys& out) {
     Evaluator ev(ctx);
     ev.transform_to_ntt_inplace(target);
     ctx.synchronize();
-    make_switch_key(ctx, *impl_->sk, impl_->rng, target.data(), out);
+    return target;
+}
+
+// 32 bytes from the generator (the OS CSPRNG, or the deterministic TestSeed stream)
+void draw_seed(Sampler& rng, Seed& out) {
+    for (int i = 0; i < 4; ++i) {
+        const uint64_t v = rng.next();
+        std::memcpy(out.bytes + 8 * i, &v, 8);
+    }
+}
+
+// seeded key_j = (-(a_j s) + e_j + g_j * target, a_j), a_j = expand(seed, j, ., 1) written straight into the key's NTT-domain component
+void make_switch_key_seeded(const Context& ctx, const SecretKey& sk, Sampler& rng, const uint64_t* d_target_ntt, PolyBuffer& out, Seed& seed_out) {
+    const FheParams& p = ctx.params();
+    const size_t n = p.n(), L = p.n_limbs(), poly = L * n;
+    dpfhe_ctx* h = static_cast<dpfhe_ctx*>(ctx.handle());
+    if (out.batch() != L || out.size() != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "seeded switching key: [L][2][L][N] expected");
+    draw_seed(rng, seed_out);
+    check(dpfhe_expand_uniform(h, out.data(), L, 2, 1, seed_out.bytes, 0, nullptr), "dpfhe_expand_uniform");
+    PolyBuffer e(ctx, 1, 1, false), t(ctx, 1, 1, true);
+    std::vector<uint64_t> he(poly);
+    for (size_t j = 0; j < L; ++j) {
+        for (size_t k = 0; k < n; ++k) {
+            const int64_t ev = rng.error();
+            for (size_t l = 0; l < L; ++l) he[l * n + k] = lift_signed(ev, p.moduli[l]);
+        }
+        e.copy_from_host(he.data());
+        uint64_t* b = out.data() + (j * 2 + 0) * poly;
+        const uint64_t* a = out.data() + (j * 2 + 1) * poly;
+        check(dpfhe_ntt_fwd(h, e.data(), 1, nullptr), "dpfhe_ntt_fwd");                       // NTT(e_j)
+        check(dpfhe_dyadic_mul(h, t.data(), a, sk.ntt(), 1, nullptr), "dpfhe_dyadic_mul");      // a_j s
+        check(dpfhe_sub(h, b, e.data(), t.data(), 1, nullptr), "dpfhe_sub");                   // e_j - a_j s
+        check(dpfhe_add(h, t.data(), b, d_target_ntt, 1, nullptr), "dpfhe_add");              // + g_j * target: limb j only
+        hip_check(hipMemcpyAsync(b + j * n, t.data() + j * n, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr), "hipMemcpyAsync");
+        ctx.synchronize();
+    }
+    out.set_ntt(true);
+}
+}  // namespace
+
+void KeyGenerator::create_galois_keys(GaloisKeys& out) {
+    PolyBuffer target = galois_target_ntt(*impl_->ctx, *impl_->sk, out.galois_elt());
+    make_switch_key(*impl_->ctx, *impl_->sk, impl_->rng, target.data(), out);
+}
+
+void KeyGenerator::create_galois_keys_seeded(GaloisKeys& out, Seed& seed_out) {
+    PolyBuffer target = galois_target_ntt(*impl_->ctx, *impl_->sk, out.galois_elt());
+    make_switch_key_seeded(*impl_->ctx, *impl_->sk, impl_->rng, target.data(), out, seed_out);
+}
+
+void KeyGenerator::create_relin_keys_seeded(RelinKeys& out, Seed& seed_out) {
+    make_switch_key_seeded(*impl_->ctx, *impl_->sk, impl_->rng, impl_->sk->ntt_squared(), out, seed_out);
+}
+
+void KeyGenerator::create_public_key_seeded(PublicKey& out, Seed& seed_out) {
+    const Context& ctx = *impl_->ctx;
+    const FheParams& p = ctx.params();
+    const size_t n = p.n(), L = p.n_limbs(), poly = L * n;
+    dpfhe_ctx* h = static_cast<dpfhe_ctx*>(ctx.handle());
+    draw_seed(impl_->rng, seed_out);
+    check(dpfhe_expand_uniform(h, out.data(), 1, 2, 1, seed_out.bytes, 0, nullptr), "dpfhe_expand_uniform");   // a: uniform, any domain
+    std::vector<uint64_t> he(poly);
+    for (size_t k = 0; k < n; ++k) {
+        const int64_t ev = impl_->rng.error();
+        for (size_t l = 0; l < L; ++l) he[l * n + k] = lift_signed(ev, p.moduli[l]);
+    }
+    PolyBuffer e(ctx, 1, 1, false), t(ctx, 1, 1, true);
+    e.copy_from_host(he.data());
+    check(dpfhe_ntt_fwd(h, e.data(), 1, nullptr), "dpfhe_ntt_fwd");
+    check(dpfhe_dyadic_mul(h, t.data(), out.data() + poly, impl_->sk->ntt(), 1, nullptr), "dpfhe_dyadic_mul");   // a s
+    check(dpfhe_sub(h, out.data(), e.data(), t.data(), 1, nullptr), "dpfhe_sub");                               // pk0 = e - a s
+    ctx.synchronize();
+    out.set_ntt(true);
 }
 
 void KeyGenerator::create_public_key(PublicKey& out) {
@@ -827,6 +976,37 @@ void encrypt_scaled(const Context& ctx, const SecretKey& sk, Rng& rng, const int
     }
     out.set_ntt(false);
 }
+// the same with every c1 of the batch expanded on the device from ONE fresh seed (item b: expand(seed, b, ., 1))
+void encrypt_scaled_seeded(const Context& ctx, const SecretKey& sk, Sampler& rng, const int64_t* messages, const std::vector<uint64_t>& scale, Ciphertext& out,
+                           Seed& seed_out) {
+    const FheParams& p = ctx.params();
+    const size_t n = p.n(), L = p.n_limbs(), poly = L * n;
+    dpfhe_ctx* h = static_cast<dpfhe_ctx*>(ctx.handle());
+    draw_seed(rng, seed_out);
+    check(dpfhe_expand_uniform(h, out.data(), out.batch(), 2, 1, seed_out.bytes, 0, nullptr), "dpfhe_expand_uniform");   // c1 (coefficient domain)
+    PolyBuffer a(ctx, 1, 1, false), t(ctx, 1, 1, false);
+    std::vector<uint64_t> hm(poly);
+    for (size_t item = 0; item < out.batch(); ++item) {
+        for (size_t l = 0; l < L; ++l) {
+            const uint64_t q = p.moduli[l];
+            for (size_t k = 0; k < n; ++k) hm[l * n + k] = (uint64_t)((u128)lift_signed(messages[item * n + k], q) * scale[l] % q);
+        }
+        for (size_t k = 0; k < n; ++k) {   // + e, the same small integer in every limb
+            const int64_t ev = rng.error();
+            for (size_t l = 0; l < L; ++l) { const uint64_t q = p.moduli[l]; uint64_t v = hm[l * n + k] + lift_signed(ev, q); hm[l * n + k] = v >= q ? v - q : v; }
+        }
+        uint64_t* c0 = out.data() + (item * 2 + 0) * poly;
+        const uint64_t* c1 = out.data() + (item * 2 + 1) * poly;
+        t.copy_from_host(hm.data());                       // e + scale m
+        hip_check(hipMemcpyAsync(a.data(), c1, poly * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr), "hipMemcpyAsync");
+        check(dpfhe_ntt_fwd(h, a.data(), 1, nullptr), "dpfhe_ntt_fwd");
+        check(dpfhe_dyadic_mul(h, a.data(), a.data(), sk.ntt(), 1, nullptr), "dpfhe_dyadic_mul");
+        check(dpfhe_ntt_inv(h, a.data(), 1, nullptr), "dpfhe_ntt_inv");          // c1 s
+        check(dpfhe_sub(h, c0, t.data(), a.data(), 1, nullptr), "dpfhe_sub");     // c0 = e + scale m - c1 s
+        ctx.synchronize();
+    }
+    out.set_ntt(false);
+}
 // (c0, c1) = (u pk0 + e1 + scale m, u pk1 + e2), u ternary, e1 / e2 uniform in [-8, 8]
 template <class Rng>
 void encrypt_scaled_pk(const Context& ctx, const PublicKey& pk, Rng& rng, const int64_t* messages, const std::vector<uint64_t>& scale, Ciphertext& out) {
@@ -887,6 +1067,30 @@ void Encryptor::encrypt_exact(const int64_t* messages, uint64_t t, Ciphertext& o
     for (size_t l = 0; l < p.n_limbs(); ++l) scale[l] = big_mod_small(delta, p.moduli[l]);
     if (impl_->pk) encrypt_scaled_pk(*impl_->ctx, *impl_->pk, impl_->rng, messages, scale, out);
     else encrypt_scaled(*impl_->ctx, *impl_->sk, impl_->rng, messages, scale, out);
+}
+
+void Encryptor::encrypt_seeded(const int64_t* messages, unsigned log2_scale, Ciphertext& out, Seed& seed_out) {
+    if (impl_->pk) throw Exception(ErrorCode::INVALID_STATE, "encrypt_seeded: a public-key encryption's c1 = u pk1 + e2 cannot be seeded");
+    if (!messages) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_seeded: null messages");
+    if (out.size() != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_seeded: output must be a 2-component ciphertext");
+    if (log2_scale > 200) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_seeded: log2_scale too large");
+    const FheParams& p = impl_->ctx->params();
+    std::vector<uint64_t> scale(p.n_limbs());
+    for (size_t l = 0; l < p.n_limbs(); ++l) scale[l] = powmod(2, log2_scale, p.moduli[l]);
+    encrypt_scaled_seeded(*impl_->ctx, *impl_->sk, impl_->rng, messages, scale, out, seed_out);
+}
+
+void Encryptor::encrypt_exact_seeded(const int64_t* messages, uint64_t t, Ciphertext& out, Seed& seed_out) {
+    if (impl_->pk) throw Exception(ErrorCode::INVALID_STATE, "encrypt_exact_seeded: a public-key encryption's c1 = u pk1 + e2 cannot be seeded");
+    if (!messages) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_exact_seeded: null messages");
+    if (out.size() != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_exact_seeded: output must be a 2-component ciphertext");
+    if (t < 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "encrypt_exact_seeded: plaintext modulus must be >= 2");
+    const FheParams& p = impl_->ctx->params();
+    Big delta = modulus_product(p);
+    big_divmod_small(delta, t);   // floor(Q / t)
+    std::vector<uint64_t> scale(p.n_limbs());
+    for (size_t l = 0; l < p.n_limbs(); ++l) scale[l] = big_mod_small(delta, p.moduli[l]);
+    encrypt_scaled_seeded(*impl_->ctx, *impl_->sk, impl_->rng, messages, scale, out, seed_out);
 }
 
 // ---- Decryptor --------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,55 @@
+// k_expand.hip - seeded uniform polynomials (expand.h): the device kernel, its launcher and the host twin.
+//
+// One lane per ChaCha20 block: a lane produces 4 coefficients (32 contiguous bytes, two 16-byte stores) and consecutive lanes write
+// consecutive blocks, so the stores coalesce without LDS.  A workgroup covers one (item, limb) range of blocks, so the limb's
+// constants are workgroup-uniform scalar loads; the seed's key words are kernel arguments (SGPRs).  No loads from memory besides
+// the LimbConst: the kernel is VALU-bound (20 ChaCha rounds + four exact 128-bit reductions per lane).
+#include "expand.h"
+
+namespace dpfhe {
+
+typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
+
+// block b = ((item * L + limb) << log2_chunks) + chunk;  lane t of the chunk computes ChaCha block j = chunk * blockDim.x + t
+__global__ __launch_bounds__(256) void expand_uniform_kernel(u64* __restrict__ buf, const ExpandKey key, const LimbConst* __restrict__ lc, u32 first_item,
+                                                             u32 comp, u32 comps, u32 n_limbs, u32 log2n, u32 log2_chunks) {
+    const u32 blk = blockIdx.x;
+    const u32 chunk = blk & ((1u << log2_chunks) - 1u);
+    const u32 item_limb = blk >> log2_chunks;
+    const u32 limb = item_limb % n_limbs, b = item_limb / n_limbs;
+    const u32 j = chunk * blockDim.x + threadIdx.x;
+    const u64 q = lc[limb].q, br_hi = lc[limb].br_hi, br_lo = lc[limb].br_lo;
+    u64 v[4];
+    expand_block(key, j, first_item + b, limb, comp, q, br_hi, br_lo, v);
+    u64* p = buf + ((((size_t)b * comps + comp) * n_limbs + limb) << log2n) + 4 * (size_t)j;
+    reinterpret_cast<u64x2_t*>(p)[0] = u64x2_t{v[0], v[1]};
+    reinterpret_cast<u64x2_t*>(p)[1] = u64x2_t{v[2], v[3]};
+}
+
+int launch_expand_uniform(int log2n, u64* buf, size_t batch, size_t comps, u32 comp, u32 n_limbs, const LimbConst* lc, const ExpandKey& key, u32 first_item,
+                          hipStream_t s) {
+    const u32 blocks_per_poly = 1u << (log2n - 2);                  // ChaCha blocks of one residue polynomial (log2n >= 8: at least one wave)
+    const u32 threads = blocks_per_poly < 256u ? blocks_per_poly : 256u;
+    u32 log2_chunks = 0;
+    while ((threads << log2_chunks) < blocks_per_poly) ++log2_chunks;
+    const size_t grid = (batch * n_limbs) << log2_chunks;
+    if (grid == 0 || grid > 0x7fffffffu || batch > 0xffffffffu) return -1;
+    hipLaunchKernelGGL(expand_uniform_kernel, dim3((unsigned)grid), dim3(threads), 0, s, buf, key, lc, first_item, comp, (u32)comps, n_limbs, (u32)log2n,
+                       log2_chunks);
+    return 0;
+}
+
+void expand_uniform_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, size_t batch, size_t comps, u32 comp, const ExpandKey& key, u32 first_item) {
+    const size_t n = (size_t)1 << log2n;
+    for (u32 l = 0; l < n_limbs; ++l) {
+        const u64 q = moduli[l];
+        const unsigned __int128 br = (~(unsigned __int128)0) / q;   // floor(2^128 / q): q is odd, never a power of two
+        const u64 br_hi = (u64)(br >> 64), br_lo = (u64)br;
+        for (size_t b = 0; b < batch; ++b) {
+            u64* p = out + ((b * comps + comp) * n_limbs + l) * n;
+            for (u32 j = 0; j < (u32)(n / 4); ++j) expand_block(key, j, first_item + (u32)b, l, comp, q, br_hi, br_lo, p + 4 * (size_t)j);
+        }
+    }
+}
+
+}  // namespace dpfhe

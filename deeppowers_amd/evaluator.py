@@ -411,6 +411,20 @@ class Evaluator:
         _cabi.check(self._lib.dpfhe_copy(self.ctx.handle, dst.data_ptr(), src.data_ptr(), src.numel(), self._sp(stream)), "dpfhe_copy")
         return dst
 
+    # ---- seeded uniform polynomials (include/dpfhe.h dpfhe_expand_uniform; wire.py DPFHEs1) ---------------------------------------
+    def expand_uniform_(self, t: torch.Tensor, seed: bytes, component: int, first_item: int = 0, stream=None) -> torch.Tensor:
+        """in place: component `component` of every item of t [batch...][components][L][N] = expand(seed, first_item + b, limb, component), the
+        PRF expansion a seeded stream stands for; every other word is left as it is.  The seed is public; never reuse one under one secret key."""
+        self._chk(t)
+        seed = bytes(seed)
+        if len(seed) != 32 or t.dim() < 3 or component < 0 or first_item < 0:
+            raise _cabi.DpfheError(2000, "expand_uniform_: a 32-byte seed, a [batch...][components][L][N] tensor, component and first_item >= 0")
+        comps = t.shape[-3]
+        batch = t.numel() // (comps * self.ctx.params.words_per_rns_poly())
+        _cabi.check(self._lib.dpfhe_expand_uniform(self.ctx.handle, t.data_ptr(), batch, comps, int(component), seed, int(first_item), self._sp(stream)),
+                    "dpfhe_expand_uniform")
+        return t
+
     # ---- N3, round 3: baby-step / giant-step with the division by P deferred (include/dpfhe.h) ---------------------------
     def rotate_hoisted_qp(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> torch.Tensor:
         """[T][2][L-1][N] coefficient-domain inputs on the extended context -> [1 + k][T][2][L][N], NTT domain over Q P:

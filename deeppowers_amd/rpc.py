@@ -2,9 +2,10 @@
 
 The reference serves text (`/root/reference/src/core/api/deeppowers.proto:6-32`, handler
 `/root/reference/src/core/api/grpc_server.cpp:163-226`: build a request, run the model, fill the response, record the
-latency, map exceptions to `INTERNAL`).  This is the encrypted twin: the request carries DPFHEv1 ciphertext streams
-(`wire.py`), the server runs a registered *encrypted model* - a callable built from `Evaluator` operations, i.e. HIP
-kernels through the C ABI - and answers with a ciphertext stream.  The service never holds a secret key.
+latency, map exceptions to `INTERNAL`).  This is the encrypted twin: the request carries DPFHEv1 ciphertext streams or seeded
+DPFHEs1 streams whose uniform component the server re-expands from a 32-byte seed (`wire.py`), the server runs a registered
+*encrypted model* - a callable built from `Evaluator` operations, i.e. HIP kernels through the C ABI - and answers with a
+ciphertext stream.  The service never holds a secret key.
 
 Messages are declared in `dpfhe_rpc.proto` (next to this file).  The image has grpcio and protobuf but no protoc plugin,
 so the descriptors are built here at run time; tests/test_rpc.py keeps the two in step.
@@ -196,8 +197,29 @@ class EncryptedInferenceServer:
         self.models[name] = model
 
     # -- handlers ----------------------------------------------------------------------------------------------
+    def _host_words(self, blob):
+        """-> (words [batch][components][L][N], is_ntt) of a DPFHEv1 or DPFHEs1 stream, the latter re-expanded by the host twin"""
+        if bytes(blob[:8]) == wire.SEEDED_MAGIC:
+            stored, is_ntt, seed, comp, first = wire.loads_seeded(blob, self.params)
+            if stored.shape[0] > self.max_batch:
+                raise ValueError(f"batch of {stored.shape[0]} ciphertexts exceeds this server's limit of {self.max_batch}")
+            return wire.inflate_seeded(stored, self.params, seed, comp, first), is_ntt
+        return wire.loads(blob, self.params)
+
     def _to_device(self, blob):
         from .evaluator import Ciphertext, to_device
+        if bytes(blob[:8]) == wire.SEEDED_MAGIC:   # upload the stored components, expand the seeded one on the device
+            stored, is_ntt, seed, comp, first = wire.loads_seeded(blob, self.params)
+            if stored.shape[0] > self.max_batch:
+                raise ValueError(f"batch of {stored.shape[0]} ciphertexts exceeds this server's limit of {self.max_batch}")
+            batch, kept = stored.shape[:2]
+            t = self.ctx.empty(batch, components=kept + 1)
+            if kept:
+                dev = to_device(stored, self.ctx.device)
+                t[:, :comp].copy_(dev[:, :comp])
+                t[:, comp + 1:].copy_(dev[:, comp:])
+            self.ev.expand_uniform_(t, seed, comp, first)
+            return Ciphertext(t, is_ntt)
         words, is_ntt = wire.loads(blob, self.params)
         if words.shape[0] > self.max_batch:
             raise ValueError(f"batch of {words.shape[0]} ciphertexts exceeds this server's limit of {self.max_batch}")
@@ -220,7 +242,7 @@ class EncryptedInferenceServer:
             return grpc.StatusCode.NOT_FOUND, f"no model named '{request.model}'"
         try:
             if getattr(model, "host_only", False):
-                words, is_ntt = wire.loads(request.ciphertext, self.params)
+                words, is_ntt = self._host_words(request.ciphertext)
                 out_blob, n_ct, dev_ms = wire.dumps(words, self.params, is_ntt), words.shape[0], 0.0
             else:
                 if self.ctx is None:
@@ -254,7 +276,9 @@ class EncryptedInferenceServer:
 
     def _register_keys(self, request, context):
         try:
-            words, is_ntt = wire.loads(request.relin_keys, self.params)
+            # a seeded key stream is expanded by the host twin here: the digest below covers the FULL key words, so a seeded and a plain
+            # registration of the same keys are the same keys, and the check still runs before any device copy
+            words, is_ntt = self._host_words(request.relin_keys)
             L = self.params.n_limbs
             if words.shape[:2] != (L, 2) or not is_ntt:
                 raise ValueError("relin_keys: batch = n_limbs, 2 components, NTT domain")
@@ -335,15 +359,22 @@ class EncryptedClient:
                        for name, req, resp in METHODS}
         self.last_response = None
 
-    def register_relin_keys(self, evk_ntt: np.ndarray, timeout: float = 60.0) -> bool:
-        blob = wire.dumps(np.asarray(evk_ntt, dtype=np.uint64), self.params, True)
+    def register_relin_keys(self, evk_ntt: np.ndarray, timeout: float = 60.0, seed: bytes | None = None) -> bool:
+        """`seed`: the keys' a_j are expand(seed, j, ., 1) (KeyGenerator::create_relin_keys_seeded) - only their other half is sent"""
+        evk = np.asarray(evk_ntt, dtype=np.uint64)
+        blob = wire.dumps(evk, self.params, True) if seed is None else wire.dumps_seeded(evk, self.params, True, seed)
         return self._calls["RegisterKeys"](pb["RegisterKeysRequest"](session_id=self.session_id, relin_keys=blob), timeout=timeout).ok
 
-    def generate(self, model: str, a: np.ndarray, b: np.ndarray | None = None, is_ntt: bool = False, timeout: float = 120.0):
-        """-> (words [batch][components][L][N], is_ntt)"""
+    def generate(self, model: str, a: np.ndarray, b: np.ndarray | None = None, is_ntt: bool = False, timeout: float = 120.0,
+                 seed_a: bytes | None = None, seed_b: bytes | None = None):
+        """-> (words [batch][components][L][N], is_ntt).  seed_a / seed_b: the operand's c1 is expand(seed, item, ., 1) (Encryptor::encrypt_seeded),
+        so it travels as a seeded stream of half the size"""
+        def blob(x, seed):
+            if x is None:
+                return b""
+            return wire.dumps(x, self.params, is_ntt) if seed is None else wire.dumps_seeded(x, self.params, is_ntt, seed)
         req = pb["EncryptedGenerateRequest"](request_id=uuid.uuid4().hex, model=model, session_id=self.session_id,
-                                             ciphertext=wire.dumps(a, self.params, is_ntt),
-                                             ciphertext_b=wire.dumps(b, self.params, is_ntt) if b is not None else b"")
+                                             ciphertext=blob(a, seed_a), ciphertext_b=blob(b, seed_b))
         resp = self._calls["EncryptedGenerate"](req, timeout=timeout)
         if resp.request_id != req.request_id:
             raise RuntimeError("response does not belong to this request")

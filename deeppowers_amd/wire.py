@@ -1,6 +1,12 @@
 """Ciphertext wire format - the Python twin of PolyBuffer::save/load in
 include/deeppowers/fhe.hpp.  Little-endian: b"DPFHEv1\0", u32 log2_n, u32 n_limbs, u64 batch, u64 components,
-u32 is_ntt, u32 reserved, u64 moduli[n_limbs], then the u64 words [batch][component][limb][N]."""
+u32 is_ntt, u32 reserved, u64 moduli[n_limbs], then the u64 words [batch][component][limb][N].
+
+Seeded streams (DPFHEs1, the twin of PolyBuffer::save_seeded / load_seeded): one component - the uniform c1 of a fresh symmetric
+ciphertext, the a_j of a key - is not sent but re-expanded from a public 32-byte seed (include/dpfhe.h dpfhe_expand_uniform).
+Header, 80 bytes, little-endian: b"DPFHEs1\0", u32 log2_n, u32 n_limbs, u64 batch, u64 components, u32 is_ntt,
+u32 expanded_component, u64 first_item, u8 seed[32]; then u64 moduli[n_limbs]; then the words of every OTHER component,
+[batch][components - 1][L][N].  Size = 80 + 8 L + 8 batch (components - 1) L N.  A seed must never be reused under one secret key."""
 from __future__ import annotations
 
 import struct
@@ -46,3 +52,95 @@ def loads(blob: bytes, params: FheParams):
     if (words >= np.array(params.moduli, dtype=np.uint64)[None, None, :, None]).any():
         raise ValueError("non-canonical residue")
     return words, bool(is_ntt)
+
+
+SEEDED_MAGIC = b"DPFHEs1\0"
+_SHDR = struct.Struct("<8sIIQQIIQ32s")
+
+
+def expand_host(params: FheParams, batch: int, components: int, component: int, seed: bytes, first_item: int = 0,
+                out: np.ndarray | None = None) -> np.ndarray:
+    """Host twin of dpfhe_expand_uniform: component `component` of items 0 .. batch-1 of `out` ([batch][components][L][N] uint64, zeros when
+    None) = expand(seed, first_item + b, limb, component); the other words are left as they are."""
+    import ctypes as C
+
+    from . import _cabi
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    if not (0 <= component < components) or first_item < 0 or first_item + batch > 1 << 32:
+        raise ValueError("component must be < components and first_item + batch <= 2^32")
+    if out is None:
+        out = np.zeros((batch, components, params.n_limbs, params.n), dtype=np.uint64)
+    if out.dtype != np.uint64 or not out.flags.c_contiguous or out.shape != (batch, components, params.n_limbs, params.n):
+        raise ValueError("out must be a contiguous uint64 array [batch][components][L][N]")
+    lib = _cabi.load()
+    m = (C.c_uint64 * params.n_limbs)(*params.moduli)
+    _cabi.check(lib.dpfhe_expand_uniform_host(m, params.n_limbs, params.log2_n, out.ctypes.data, batch, components, component, seed, first_item),
+                "dpfhe_expand_uniform_host")
+    return out
+
+
+def dumps_seeded(words: np.ndarray, params: FheParams, is_ntt: bool, seed: bytes, component: int = 1, first_item: int = 0,
+                 verify: bool = True) -> bytes:
+    """words: uint64 [batch][components][L][N] whose component `component` is expand(seed, first_item + b, ., component).  That component is
+    left out of the stream; with verify=True it is checked against the host twin first (a stale seed raises ValueError)."""
+    a = np.ascontiguousarray(words, dtype="<u8")
+    if a.ndim != 4 or a.shape[2] != params.n_limbs or a.shape[3] != params.n:
+        raise ValueError("words must be [batch][components][L][N]")
+    batch, comps = a.shape[:2]
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    if not (0 <= component < comps) or first_item < 0 or first_item + batch > 1 << 32:
+        raise ValueError("component must be < components and first_item + batch <= 2^32")
+    q = np.array(params.moduli, dtype=np.uint64)[None, None, :, None]
+    if (a >= q).any():
+        raise ValueError("non-canonical residue")
+    if verify:
+        exp = np.zeros((batch, comps, params.n_limbs, params.n), dtype=np.uint64)
+        expand_host(params, batch, comps, component, seed, first_item, out=exp)
+        if not np.array_equal(exp[:, component], a[:, component]):
+            raise ValueError("component does not match its seed (overwritten, transformed or another seed)")
+    stored = np.ascontiguousarray(np.delete(a, component, axis=1), dtype="<u8")
+    hdr = _SHDR.pack(SEEDED_MAGIC, params.log2_n, params.n_limbs, batch, comps, 1 if is_ntt else 0, component, first_item, seed)
+    return hdr + np.array(params.moduli, dtype="<u8").tobytes() + stored.tobytes()
+
+
+def loads_seeded(blob: bytes, params: FheParams):
+    """-> (stored words [batch][components - 1][L][N] uint64, is_ntt, seed, component, first_item).  Raises ValueError on any mismatch."""
+    if len(blob) < _SHDR.size:
+        raise ValueError("truncated header")
+    magic, log2_n, n_limbs, batch, comps, is_ntt, component, first_item, seed = _SHDR.unpack_from(blob, 0)
+    if magic != SEEDED_MAGIC:
+        raise ValueError("not a DPFHEs1 stream")
+    if log2_n != params.log2_n or n_limbs != params.n_limbs:
+        raise ValueError("header does not match the parameters")
+    if component >= comps:
+        raise ValueError("expanded_component must be < components")
+    if first_item + batch > 1 << 32:
+        raise ValueError("first_item + batch must be <= 2^32")
+    off = _SHDR.size
+    if len(blob) < off + 8 * n_limbs:
+        raise ValueError("truncated moduli")
+    moduli = np.frombuffer(blob, dtype="<u8", count=n_limbs, offset=off)
+    if tuple(int(m) for m in moduli) != tuple(params.moduli):
+        raise ValueError("moduli differ")
+    off += 8 * n_limbs
+    count = batch * (comps - 1) * n_limbs * params.n
+    if len(blob) != off + 8 * count:
+        raise ValueError("payload size does not match the header")
+    words = np.frombuffer(blob, dtype="<u8", count=count, offset=off).reshape(batch, comps - 1, n_limbs, params.n).astype(np.uint64)
+    if (words >= np.array(params.moduli, dtype=np.uint64)[None, None, :, None]).any():
+        raise ValueError("non-canonical residue")
+    return words, bool(is_ntt), bytes(seed), int(component), int(first_item)
+
+
+def inflate_seeded(stored: np.ndarray, params: FheParams, seed: bytes, component: int, first_item: int = 0) -> np.ndarray:
+    """stored words [batch][components - 1][L][N] (loads_seeded) -> the full words [batch][components][L][N], the missing component
+    expanded by the host twin (clients without a GPU, host-only servers)."""
+    batch, kept = stored.shape[:2]
+    full = np.empty((batch, kept + 1, params.n_limbs, params.n), dtype=np.uint64)
+    full[:, :component] = stored[:, :component]
+    full[:, component + 1:] = stored[:, component:]
+    return expand_host(params, batch, kept + 1, component, seed, first_item, out=full)

@@ -40,6 +40,14 @@ private:
 
 using Stream = void;  // a hipStream_t; nullptr = the null stream
 
+// Seed of a seeded ciphertext or key: its uniform component (c1 of a fresh symmetric ciphertext, a_j of a key) is expand(seed, item, limb, component)
+// (include/dpfhe.h dpfhe_expand_uniform) and travels as these 32 bytes instead of L N words per item.  The seed is PUBLIC - it stands for a public
+// uniform polynomial; security rests on ChaCha20 as a PRG with a public seed.  It must never be reused under one secret key: equal c1 would make
+// c0 - c0' = scale (m - m') + e - e' public.  Every *_seeded call below draws a fresh one (and the item index is part of the nonce).
+struct Seed {
+    uint8_t bytes[32];
+};
+
 struct FheParams {
     uint32_t log2_n = 0;
     std::vector<uint64_t> moduli;  // primes < 2^60, q = 1 (mod 2N)
@@ -113,6 +121,13 @@ public:
     // header matches this buffer's context and shape (throws INVALID_ARGUMENT otherwise) and sets the domain flag.
     void save(std::ostream& os) const;
     void load(std::istream& is);
+    // Seeded stream "DPFHEs1\0": component `component` of items 0 .. batch-1 must be expand(seed, first_item + b, ., component); it is left out.
+    // 80-byte header (little-endian): magic, u32 log2_n, u32 n_limbs, u64 batch, u64 components, u32 is_ntt, u32 expanded_component, u64 first_item,
+    // u8 seed[32]; then u64 moduli[n_limbs]; then the other components' words [batch][components-1][L][N].  save_seeded re-expands and compares
+    // first: a buffer that no longer matches its seed (overwritten, transformed) throws INVALID_STATE, so no stale seed is ever written.
+    // load_seeded checks the header as load() does, uploads the stored components and expands the missing one on the device (on `stream`).
+    void save_seeded(std::ostream& os, const Seed& seed, uint32_t component = 1, uint64_t first_item = 0) const;
+    void load_seeded(std::istream& is, Stream* stream = nullptr);
 
 private:
     class Impl;
@@ -302,6 +317,11 @@ public:
     void create_relin_keys(RelinKeys& out);  // evk_j = (-(a_j s) + e_j + g_j s^2, a_j), NTT domain
     void create_galois_keys(GaloisKeys& out);  // key_j = (-(a_j s) + e_j + g_j sigma_g(s), a_j) for out.galois_elt()
     void create_public_key(PublicKey& out);    // (-(a s) + e, a), NTT domain
+    // the same with the uniform half expanded from a fresh seed drawn from this generator's randomness: a_j = expand(seed, j, ., 1)
+    // (PolyBuffer::save_seeded(os, seed) then ships half of the words)
+    void create_relin_keys_seeded(RelinKeys& out, Seed& seed_out);
+    void create_galois_keys_seeded(GaloisKeys& out, Seed& seed_out);
+    void create_public_key_seeded(PublicKey& out, Seed& seed_out);
 
 private:
     class Impl;
@@ -322,6 +342,10 @@ public:
     void encrypt(const int64_t* messages, unsigned log2_scale, Ciphertext& out);
     // exact integer arithmetic mod a plaintext modulus t (BFV-style scaling): c0 = -(a s) + e + floor(Q/t) * m
     void encrypt_exact(const int64_t* messages, uint64_t plain_modulus, Ciphertext& out);
+    // Seeded symmetric encryption: one fresh seed per call (from this encryptor's randomness), c1 of item b = expand(seed, b, ., 1) expanded on the
+    // device, c0 = -(c1 s) + e + scale m as above.  A public-key Encryptor throws INVALID_STATE (its c1 = u pk1 + e2 is not a PRF output).
+    void encrypt_seeded(const int64_t* messages, unsigned log2_scale, Ciphertext& out, Seed& seed_out);
+    void encrypt_exact_seeded(const int64_t* messages, uint64_t plain_modulus, Ciphertext& out, Seed& seed_out);
 
 private:
     class Impl;

@@ -298,6 +298,20 @@ int dpfhe_comm_allgather(dpfhe_comm* comm, uint64_t* d_recv, const uint64_t* d_s
 int dpfhe_comm_allreduce_sum(dpfhe_comm* comm, dpfhe_ctx* ctx, uint64_t* d_io, size_t n_rns_polys, void* stream);
 int dpfhe_canonicalize_sum(dpfhe_ctx* ctx, uint64_t* d_io, size_t n_rns_polys, void* stream);
 
+/* -- seeded uniform polynomials: the uniform half of a fresh symmetric ciphertext (c1) or of a key (a_j) travels as a 32-byte seed.
+ * expand(seed, item, limb, component) has N coefficients mod q_limb: ChaCha20 block function of RFC 8439 section 2.3 with key = seed (8 little-endian
+ * words), 32-bit block counter = k / 4 and nonce = (item, limb, component) as u32 words; coefficient k is output words 4 (k mod 4) .. +3 read as one
+ * 128-bit little-endian integer X, reduced exactly: X mod q_limb.  `limb` is the limb's index in the context (a context of the first m moduli expands the
+ * first m limbs of the full one).  The words are the same whatever the limb's arithmetic class and whichever domain the buffer is in.
+ * The seed is public: security rests on ChaCha20 as a PRG with a public seed.  Never reuse a seed under one secret key (equal c1 leak c0 - c0').
+ * dpfhe_expand_uniform: writes component `component` of items 0 .. batch-1 of d_buf [batch][components][L][N] as expand(seed, first_item + b, l, component)
+ *   and leaves every other word untouched.  DPFHE_INVALID_ARGUMENT on null pointers, component >= components, first_item + batch > 2^32.
+ * dpfhe_expand_uniform_host: the same on the host (no device, no context); moduli odd, >= 3 and < 2^60, log2_n in [8, 16]. */
+int dpfhe_expand_uniform(dpfhe_ctx* ctx, uint64_t* d_buf, size_t batch, size_t components, uint32_t component, const uint8_t seed[32],
+                         uint64_t first_item, void* stream);
+int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t components,
+                              uint32_t component, const uint8_t seed[32], uint64_t first_item);
+
 const char* dpfhe_strerror(int code);
 /* text of the last HIP/RCCL failure on the calling thread ("" if none) */
 const char* dpfhe_last_error(void);

@@ -1,0 +1,185 @@
+"""-m gpu: seeded uniform polynomials on the device (include/dpfhe.h dpfhe_expand_uniform, csrc/k_expand.hip).
+
+The kernel must give the host twin's words (tests/test_seeded_cpu.py holds the host twin to a restatement of the definition) on every
+ring degree and limb class, write nothing but its component, and split into item ranges with first_item.  Through the C++ facade
+(tests/cpp/test_seeded_api.cpp): seeded encryption, keys and streams.  Over RPC: seeded operands and keys give the plain request's words."""
+import os
+import subprocess
+
+import grpc
+import numpy as np
+import pytest
+
+from deeppowers_amd import _cabi, rpc, wire
+from deeppowers_amd.params import FheParams, ntt_primes
+from test_rlwe_semantics import negacyclic_int, phase, small_params
+from test_seeded_cpu import SEED, SENTINEL, mixed_params, pinned60, primes31
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+pytestmark = pytest.mark.gpu
+
+
+def _device_vs_twin(p, batch, comps, comp, first_item, seed=SEED):
+    import torch
+    from deeppowers_amd.evaluator import Context, Evaluator, to_host
+    ctx = Context(p, 0)
+    try:
+        ev = Evaluator(ctx)
+        t = torch.full((batch, comps, p.n_limbs, p.n), int(SENTINEL.view(np.int64)), dtype=torch.int64, device=ctx.device)
+        ev.expand_uniform_(t, seed, comp, first_item)
+        torch.cuda.synchronize()
+        got = to_host(t)
+        want = wire.expand_host(p, batch, comps, comp, seed, first_item, out=np.full(got.shape, SENTINEL, dtype=np.uint64))
+        assert np.array_equal(got, want), (p.log2_n, p.moduli, comps, comp, first_item)
+        assert (got[:, [c for c in range(comps) if c != comp]] == SENTINEL).all()
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("log2n", range(8, 17))
+def test_device_matches_host_twin_every_ring_degree(log2n):
+    p = ntt_primes(log2n, 3 if log2n <= 14 else 2, 60)
+    _device_vs_twin(p, 3, 2, 1, 0)
+    _device_vs_twin(p, 2, 3, 0 if log2n % 2 else 2, (1 << 31) + 5)
+
+
+@pytest.mark.parametrize("name", ["pinned60", "primes31", "mixed", "config1"])
+def test_device_matches_host_twin_limb_classes(name):
+    p = {"pinned60": pinned60, "primes31": primes31, "mixed": mixed_params, "config1": FheParams.config1}[name]()
+    for comps, comp, first in ((2, 1, 0), (3, 0, (1 << 31) + 5), (3, 2, 7)):
+        _device_vs_twin(p, 5, comps, comp, first)
+
+
+def test_full_size_split_launches_and_host_twin():
+    """8192 items x N = 4096 x L = 4: one launch == two launches over item ranges (first_item 0 and 4096); the first 1024 items == host twin"""
+    import torch
+    from deeppowers_amd.evaluator import Context, Evaluator, to_host
+    p = pinned60()
+    ctx = Context(p, 0)
+    try:
+        ev = Evaluator(ctx)
+        one = torch.zeros((8192, 2, p.n_limbs, p.n), dtype=torch.int64, device=ctx.device)
+        two = torch.zeros_like(one)
+        ev.expand_uniform_(one, SEED, 1)
+        ev.expand_uniform_(two[:4096], SEED, 1, first_item=0)
+        ev.expand_uniform_(two[4096:], SEED, 1, first_item=4096)
+        torch.cuda.synchronize()
+        assert torch.equal(one, two)
+        assert int(one[:, 0].abs().sum()) == 0                      # component 0 untouched
+        got = to_host(one[:1024])
+        assert np.array_equal(got, wire.expand_host(p, 1024, 2, 1, SEED))
+        del one, two
+    finally:
+        ctx.close()
+
+
+def test_device_entry_rejects_bad_arguments():
+    import torch
+    from deeppowers_amd.evaluator import Context, Evaluator
+    p = pinned60()
+    ctx = Context(p, 0)
+    try:
+        ev = Evaluator(ctx)
+        t = torch.zeros((2, 2, p.n_limbs, p.n), dtype=torch.int64, device=ctx.device)
+        lib = ctx._lib
+        assert lib.dpfhe_expand_uniform(ctx.handle, None, 2, 2, 1, SEED, 0, None) == 2000
+        assert lib.dpfhe_expand_uniform(ctx.handle, t.data_ptr(), 2, 2, 1, None, 0, None) == 2000
+        assert lib.dpfhe_expand_uniform(ctx.handle, t.data_ptr(), 2, 2, 2, SEED, 0, None) == 2000
+        assert lib.dpfhe_expand_uniform(ctx.handle, t.data_ptr(), 2, 2, 1, SEED, (1 << 32) - 1, None) == 2000
+        with pytest.raises(_cabi.DpfheError):
+            ev.expand_uniform_(t, SEED[:16], 1)
+        torch.cuda.synchronize()
+        assert int(t.abs().sum()) == 0
+        ev.expand_uniform_(t, SEED, 1, first_item=(1 << 32) - 2)     # the last legal range
+        torch.cuda.synchronize()
+        assert int(t[:, 0].abs().sum()) == 0 and int(t[:, 1].abs().sum()) != 0
+    finally:
+        ctx.close()
+
+
+def test_cpp_seeded_facade(tmp_path):
+    exe = str(tmp_path / "test_seeded_api")
+    lib = os.path.join(ROOT, "deeppowers_amd")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_seeded_api.cpp"), "-o", exe,
+                           "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "seeded C++ facade OK" in out.stdout, out.stdout + out.stderr
+
+
+# ---- RPC --------------------------------------------------------------------------------------------------------------------------------
+def _encrypt_seeded(rng, p, s, msgs, delta, seed):
+    """symmetric encryption whose c1 of item b is expand(seed, b, ., 1): c0 = -(c1 s) + e + delta m"""
+    from oracle import pyoracle as po
+    batch, n = len(msgs), p.n
+    ct = wire.expand_host(p, batch, 2, 1, seed)
+    for b in range(batch):
+        e = rng.integers(-8, 9, n)
+        for l, q in enumerate(p.moduli):
+            a_s = po.negacyclic_schoolbook([int(v) for v in ct[b, 1, l]], [int(v) % q for v in s], q)
+            ct[b, 0, l] = [(-a_s[k] + int(e[k]) + delta * int(msgs[b][k])) % q for k in range(n)]
+    return ct
+
+
+def _relin_keys_seeded(rng, p, s, seed):
+    """evk_j = (-(a_j s) + e_j + g_j s^2, a_j) in the NTT domain with a_j = expand(seed, j, ., 1) taken as NTT-domain words"""
+    from oracle import pyoracle as po
+    from oracle.cbind import Oracle
+    n, L = p.n, p.n_limbs
+    orc = Oracle.from_params(p)
+    evk = wire.expand_host(p, L, 2, 1, seed)
+    s_res = np.array([[int(v) % q for v in s] for q in p.moduli], dtype=np.uint64)[None]
+    s_ntt = orc.ntt_fwd(s_res.copy()).reshape(L, n)
+    for j in range(L):
+        e = rng.integers(-8, 9, n)
+        b = np.zeros((1, L, n), np.uint64)
+        for i, q in enumerate(p.moduli):
+            sq = [int(v) % q for v in s]
+            s2 = po.negacyclic_schoolbook(sq, sq, q) if i == j else [0] * n
+            b[0, i] = [(int(e[k]) + s2[k]) % q for k in range(n)]
+        b_ntt = orc.ntt_fwd(b).reshape(L, n)
+        for i, q in enumerate(p.moduli):
+            evk[j, 0, i] = [(int(b_ntt[i, k]) - int(evk[j, 1, i, k]) * int(s_ntt[i, k])) % q for k in range(n)]
+    return evk
+
+
+def test_multiply_relinearize_over_rpc_with_seeded_operands_and_keys():
+    from deeppowers_amd.evaluator import Context
+    from oracle.cbind import Oracle
+    p = small_params()
+    rng = np.random.default_rng(21)
+    s = rng.integers(-1, 2, p.n)
+    delta = 1 << 40
+    seed_a, seed_b, seed_k = bytes([1] * 32), bytes([2] * 32), bytes([3] * 32)
+    m1, m2 = rng.integers(0, 1000, (2, p.n)), rng.integers(0, 1000, (2, p.n))
+    a = _encrypt_seeded(rng, p, s, m1, delta, seed_a)
+    b = _encrypt_seeded(rng, p, s, m2, delta, seed_b)
+    evk = _relin_keys_seeded(rng, p, s, seed_k)
+    ctx = Context(p, 0)
+    server = rpc.EncryptedInferenceServer(ctx)
+    server.register_model("multiply", rpc.MultiplyRelinearize())
+    port = server.start("127.0.0.1:0")
+    seeded = rpc.EncryptedClient(f"127.0.0.1:{port}", p)
+    plain = rpc.EncryptedClient(f"127.0.0.1:{port}", p)
+    try:
+        assert seeded.register_relin_keys(evk, seed=seed_k)
+        assert seeded.register_relin_keys(evk)                      # the same keys, plain: idempotent (digest over the expanded words)
+        other = evk.copy(); other[0, 0, 0, 0] = (other[0, 0, 0, 0] + np.uint64(1)) % np.uint64(p.moduli[0])
+        with pytest.raises(grpc.RpcError) as e:
+            seeded.register_relin_keys(other)
+        assert e.value.code() == grpc.StatusCode.ALREADY_EXISTS
+        assert plain.register_relin_keys(evk)
+        y_seeded, is_ntt = seeded.generate("multiply", a, b, seed_a=seed_a, seed_b=seed_b)
+        y_plain, _ = plain.generate("multiply", a, b)
+        assert not is_ntt and np.array_equal(y_seeded, y_plain)
+        orc = Oracle.from_params(p)
+        assert np.array_equal(y_seeded, orc.relinearize(orc.ct_mul(a, b), evk))
+        for i in range(2):
+            ph, Q = phase(p, y_seeded[i], s)
+            dec = [((v if v < Q // 2 else v - Q) + (delta * delta) // 2) // (delta * delta) for v in ph]
+            assert dec == [v if v < Q // 2 else v - Q for v in negacyclic_int([int(v) for v in m1[i]], [int(v) for v in m2[i]], Q)]
+    finally:
+        seeded.close()
+        plain.close()
+        server.stop()
+        ctx.close()
