@@ -64,6 +64,9 @@ SYMBOLS = {
     "dpfhe_canonicalize_sum": ([C.c_void_p, _U64P, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_expand_uniform": ([C.c_void_p, _U64P, C.c_size_t, C.c_size_t, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p], C.c_int),
     "dpfhe_expand_uniform_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_char_p, C.c_uint64], C.c_int),
+    "dpfhe_add_plain_scaled": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_int, C.c_void_p], C.c_int),
+    "dpfhe_add_plain_scaled_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                     C.c_uint64, C.c_int], C.c_int),
     "dpfhe_strerror": ([C.c_int], C.c_char_p),
     "dpfhe_last_error": ([], C.c_char_p),
 }

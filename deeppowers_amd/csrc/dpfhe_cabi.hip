@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +23,7 @@
 #include "../../include/dpfhe.h"
 #include "base_ext.h"
 #include "expand.h"
+#include "plain_add.h"
 #include "kernels_large.h"
 #include "kernels_misc.h"
 #include "launch.h"
@@ -1661,6 +1663,98 @@ extern "C" int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limb
         if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "moduli must be odd, >= 3 and < 2^60");
     expand_uniform_host((int)log2_n, moduli, n_limbs, out, batch, components, component, key, (uint32_t)first_item);
     return DPFHE_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact plaintext addition (plain_add.h, k_plain_add.hip): c0 += round(Q b / t) (or -=), one item of `plain` per batch / plain_items ciphertexts
+// t^-1 mod q by the extended Euclidean algorithm; false when gcd(t, q) != 1
+static bool inverse_mod(uint64_t t, uint64_t q, uint64_t& inv) {
+    int64_t r0 = (int64_t)q, r1 = (int64_t)(t % q), s0 = 0, s1 = 1;   // q < 2^60: every remainder and coefficient fits int64
+    while (r1) {
+        const int64_t k = r0 / r1, r2 = r0 - k * r1, s2 = s0 - k * s1;
+        r0 = r1; r1 = r2; s0 = s1; s1 = s2;
+    }
+    if (r0 != 1) return false;
+    inv = s0 < 0 ? (uint64_t)(s0 + (int64_t)q) : (uint64_t)s0;
+    return true;
+}
+
+// validates the shape and t, then fills the launch-independent constants and every limb's (q, t^-1, floor(t^-1 2^64 / q))
+static int plain_add_args(const char* what, const uint64_t* out, const uint64_t* in, const uint64_t* plain, size_t batch, size_t comps, size_t plain_items,
+                          uint64_t t, int negate, const uint64_t* moduli, uint32_t n_limbs, PlainAddArgs& a, std::vector<PlainAddLimb>& limbs) {
+    if (!out || !in || !plain) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer");
+    if (comps != 2 && comps != 3) return fail(DPFHE_INVALID_ARGUMENT, what, "ciphertexts have 2 or 3 components");
+    if (plain_items == 0 || batch % plain_items) return fail(DPFHE_INVALID_ARGUMENT, what, "batch must be a multiple of plain_items");
+    if (t < 3 || (t >> 32) || !(t & 1)) return fail(DPFHE_INVALID_ARGUMENT, what, "plain modulus t must be odd, >= 3 and < 2^32");
+    uint64_t q_mod_t = 1 % t;
+    limbs.resize(n_limbs);
+    for (uint32_t l = 0; l < n_limbs; ++l) {
+        const uint64_t q = moduli[l];
+        uint64_t inv = 0;
+        if (!inverse_mod(t, q, inv)) return fail(DPFHE_INVALID_ARGUMENT, what, "t must be coprime to every modulus");
+        limbs[l] = PlainAddLimb{q, inv, (uint64_t)(((unsigned __int128)inv << 64) / q)};
+        q_mod_t = (uint64_t)((unsigned __int128)q_mod_t * (q % t) % t);
+    }
+    a = PlainAddArgs{};
+    a.t = t;
+    a.t_mu = ~(uint64_t)0 / t;   // = floor(2^64 / t): t is odd, never a power of two
+    a.m = negate ? q_mod_t : (t - q_mod_t) % t;
+    a.half = (t - 1) / 2;
+    return DPFHE_SUCCESS;
+}
+
+// the limbs in launches of at most kPlainAddLimbs (their constants are a kernel argument)
+template <class F>
+static int for_limb_groups(PlainAddArgs& a, const std::vector<PlainAddLimb>& limbs, F f) {
+    for (uint32_t l0 = 0; l0 < (uint32_t)limbs.size(); l0 += kPlainAddLimbs) {
+        a.l0 = l0;
+        a.n_limbs = std::min<uint32_t>(kPlainAddLimbs, (uint32_t)limbs.size() - l0);
+        std::copy(limbs.begin() + l0, limbs.begin() + l0 + a.n_limbs, a.limb);
+        if (int rc = f(a)) return rc;
+    }
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_add_plain_scaled(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in, const uint64_t* d_plain, size_t batch, size_t comps,
+                                      size_t plain_items, uint64_t t, int negate, void* stream) {
+    static const char* what = "dpfhe_add_plain_scaled";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    PlainAddArgs a;
+    std::vector<PlainAddLimb> limbs;
+    if (int rc = plain_add_args(what, d_out, d_in, d_plain, batch, comps, plain_items, t, negate, c->moduli.data(), c->n_limbs, a, limbs)) return rc;
+    if (misaligned(d_out) || misaligned(d_in) || misaligned(d_plain)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    const size_t words = batch * comps * ((size_t)c->n_limbs << c->log2n);
+    if (d_out != d_in && overlaps(d_out, words, d_in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap without being the same buffer");
+    if (batch == 0) return DPFHE_SUCCESS;
+    DPFHE_ON_DEVICE(c, what);
+    const size_t group = batch / plain_items;
+    return for_limb_groups(a, limbs, [&](const PlainAddArgs& g) {
+        if (launch_add_plain_scaled((int)c->log2n, d_out, d_in, d_plain, batch, (u32)comps, c->n_limbs, group, g, static_cast<hipStream_t>(stream)))
+            return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+        return check_launch("add_plain_scaled kernel launch");
+    });
+}
+
+extern "C" int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
+                                           size_t batch, size_t comps, size_t plain_items, uint64_t t, int negate) {
+    static const char* what = "dpfhe_add_plain_scaled_host";
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, what, "null moduli");
+    if (n_limbs == 0 || log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, what, "n_limbs >= 1 and log2_n in [8, 16]");
+    for (uint32_t l = 0; l < n_limbs; ++l)
+        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be odd, >= 3 and < 2^60");
+    PlainAddArgs a;
+    std::vector<PlainAddLimb> limbs;
+    if (int rc = plain_add_args(what, out, in, plain, batch, comps, plain_items, t, negate, moduli, n_limbs, a, limbs)) return rc;
+    const size_t n = (size_t)1 << log2_n, words = batch * comps * n_limbs * n;
+    if (out != in && overlaps(out, words, in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap without being the same buffer");
+    for (size_t i = 0; i < plain_items * n; ++i)
+        if (plain[i] >> 32) return fail(DPFHE_INVALID_ARGUMENT, what, "plaintext words must be < 2^32");
+    if (batch == 0) return DPFHE_SUCCESS;
+    const size_t group = batch / plain_items;
+    return for_limb_groups(a, limbs, [&](const PlainAddArgs& g) {
+        add_plain_scaled_host((int)log2_n, out, in, plain, batch, (u32)comps, n_limbs, group, g);
+        return (int)DPFHE_SUCCESS;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

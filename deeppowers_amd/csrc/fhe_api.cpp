@@ -334,6 +334,54 @@ void ScalarMatrix::set(const int64_t* w) {
     hip_check(hipMemcpy(impl_->d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
 }
 
+// ---- ExactPlaintext ---------------------------------------------------------------------------------------------------------
+class ExactPlaintext::Impl {
+public:
+    const Context* ctx = nullptr;
+    uint64_t t = 0;
+    size_t items = 0, n = 0;
+    uint64_t* d = nullptr;
+    ~Impl() {
+        if (d) (void)hipFree(d);
+    }
+    void upload(const int64_t* coeffs) {   // items * n values, reduced mod t
+        std::vector<uint64_t> host(items * n);
+        for (size_t i = 0; i < host.size(); ++i) {
+            const int64_t r = coeffs[i] % (int64_t)t;
+            host[i] = (uint64_t)(r < 0 ? r + (int64_t)t : r);
+        }
+        hip_check(hipMemcpy(d, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+};
+ExactPlaintext::ExactPlaintext(const Context& ctx, uint64_t t, size_t items) : impl_(new Impl) {
+    if (t < 3 || (t >> 32) || !(t & 1)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext: plaintext modulus must be odd, >= 3 and < 2^32");
+    if (items == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext: items must be > 0");
+    impl_->ctx = &ctx; impl_->t = t; impl_->items = items; impl_->n = ctx.params().n();
+    hip_check(hipSetDevice(ctx.device_id()), "hipSetDevice");
+    void* p = nullptr;
+    hip_check(hipMalloc(&p, items * impl_->n * sizeof(uint64_t)), "hipMalloc");
+    impl_->d = static_cast<uint64_t*>(p);
+    hip_check(hipMemset(p, 0, items * impl_->n * sizeof(uint64_t)), "hipMemset");
+}
+ExactPlaintext::~ExactPlaintext() = default;
+size_t ExactPlaintext::items() const { return impl_->items; }
+uint64_t ExactPlaintext::plain_modulus() const { return impl_->t; }
+size_t ExactPlaintext::ring_degree() const { return impl_->n; }
+const uint64_t* ExactPlaintext::data() const { return impl_->d; }
+void ExactPlaintext::set_coefficients(const int64_t* coeffs) {
+    if (!coeffs) throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext::set_coefficients: null coefficients");
+    impl_->upload(coeffs);
+}
+void ExactPlaintext::set_slots(const BatchEncoder& enc, const uint64_t* slots) {
+    if (!slots) throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext::set_slots: null slots");
+    if (enc.plain_modulus() != impl_->t || enc.slot_count() != impl_->n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext::set_slots: the encoder's plaintext modulus or ring degree differs");
+    const size_t n = impl_->n;
+    std::vector<int64_t> coeffs(impl_->items * n);
+    for (size_t i = 0; i < impl_->items; ++i) enc.encode(slots + i * n, coeffs.data() + i * n);
+    impl_->upload(coeffs.data());
+}
+
 RelinKeys::RelinKeys(const Context& ctx) : PolyBuffer(ctx, ctx.params().n_limbs(), 2, /*is_ntt=*/true) {}
 GaloisKeys::GaloisKeys(const Context& ctx, uint32_t galois_elt) : PolyBuffer(ctx, ctx.params().n_limbs(), 2, /*is_ntt=*/true), galois_elt_(galois_elt) {
     if (!(galois_elt & 1u) || galois_elt >= 2 * ctx.params().n()) throw Exception(ErrorCode::INVALID_ARGUMENT, "GaloisKeys: galois_elt must be odd and < 2N");
@@ -414,6 +462,28 @@ void Evaluator::rescale(const Ciphertext& in, Ciphertext& out, Stream* s) const 
         throw Exception(ErrorCode::INVALID_ARGUMENT, "rescale: output must live on the next-level context (L-1 limbs), same size and batch");
     check(dpfhe_rescale(impl_->h(), out.data(), in.data(), in.batch() * in.size(), s), "dpfhe_rescale");
     out.set_ntt(false);
+}
+namespace {
+void add_plain_exact_impl(const Context& ctx, const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, bool negate, Stream* s, const char* what) {
+    const FheParams& fp = ctx.params();
+    if (in.is_ntt()) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": input must be in the coefficient domain");
+    if ((in.size() != 2 && in.size() != 3) || in.words() != in.batch() * in.size() * fp.n_limbs() * fp.n())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": input must be a 2- or 3-component ciphertext of this context");
+    if (out.size() != in.size() || out.batch() != in.batch() || out.words() != in.words())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output shape differs");
+    if (p.ring_degree() != fp.n() || in.batch() % p.items())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": plaintext of another ring degree, or a batch that is not a multiple of its items");
+    check(dpfhe_add_plain_scaled(static_cast<dpfhe_ctx*>(ctx.handle()), out.data(), in.data(), p.data(), in.batch(), in.size(), p.items(), p.plain_modulus(),
+                                 negate ? 1 : 0, s),
+          "dpfhe_add_plain_scaled");
+    out.set_ntt(false);
+}
+}  // namespace
+void Evaluator::add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* s) const {
+    add_plain_exact_impl(*impl_->ctx, in, p, out, false, s, "add_plain_exact");
+}
+void Evaluator::sub_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* s) const {
+    add_plain_exact_impl(*impl_->ctx, in, p, out, true, s, "sub_plain_exact");
 }
 // ---- ExactMultiplier ------------------------------------------------------------------------------------------------------------
 class ExactMultiplier::Impl {
@@ -1553,6 +1623,7 @@ public:
     bool replicate = false;   // one block: every window computes it (the output is again a periodic vector)
     size_t n1 = 0, n2 = 0;
     std::unique_ptr<Plaintext> diag;   // [passes][n2][n1] pre-rotated diagonals, NTT domain
+    std::unique_ptr<ExactPlaintext> bias;   // [passes][N]: bias[R] on every slot that holds output row R, or null
     std::vector<uint32_t> baby_elts, giant_elts, fold_elts;
     // per-layer scratch, reused by every apply() (one caller at a time).  Terms over Q P live on the key switcher's extended context.
     std::unique_ptr<PolyBuffer> babies_qp, inner_qp, terms_qp, ksum_qp;
@@ -1589,6 +1660,10 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
 }
 
 PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext)
+    : PackedLinear(ctx, enc, ks, W, out_dim, in_dim, tokens_per_ciphertext, nullptr) {}
+
+PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext,
+                           const uint64_t* bias)
     : impl_(new Impl) {
     if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: one or two tokens per ciphertext");
     const FheParams& p = ctx.params();
@@ -1625,6 +1700,9 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
     for (uint32_t g : I.fold_elts) ks.add_galois_element(g);
     for (size_t i = 0; i < out_dim * in_dim; ++i)
         if (W[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: weight >= plaintext modulus");
+    if (bias)
+        for (size_t i = 0; i < out_dim; ++i)
+            if (bias[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: bias >= plaintext modulus");
 
     // Pre-rotated diagonals.  The product of giant step i lands on output slot r = r' - i n1 (row rotation), so position r' of
     // diagonal (i, j) carries the weight of the output row that slot r holds and of input index (r + k) mod n, k = i n1 + j.
@@ -1661,9 +1739,21 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
         I.inner_elts.push_back(1u);
         I.inner_elts.insert(I.inner_elts.end(), I.giant_elts.begin(), I.giant_elts.end());
     }
+    // the bias: one slot vector per output ciphertext, in the layout the output itself has (row_of_slot - so also the replicated, folded and two-token ones)
+    if (bias) {
+        std::vector<uint64_t> bslots(I.passes * N);
+        for (size_t pass = 0; pass < I.passes; ++pass)
+            for (size_t sl = 0; sl < N; ++sl) {
+                const size_t R = I.row_of_slot(pass, sl);
+                bslots[pass * N + sl] = R != (size_t)-1 ? bias[R] : 0;
+            }
+        I.bias.reset(new ExactPlaintext(ctx, t, I.passes));
+        I.bias->set_slots(enc, bslots.data());
+    }
     I.ensure_tokens(1);
     ext.synchronize();
 }
+bool PackedLinear::has_bias() const { return impl_->bias != nullptr; }
 PackedLinear::~PackedLinear() = default;
 size_t PackedLinear::dim() const { return impl_->m; }
 size_t PackedLinear::in_dim() const { return impl_->in_dim; }
@@ -1762,6 +1852,9 @@ void PackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
             check(dpfhe_add(h, last ? y.data() : f.data(), f.data(), f.data() + T * ct_words, 2 * T, s), "dpfhe_add");
         }
     }
+    // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
+    if (I.bias)
+        check(dpfhe_add_plain_scaled(h, y.data(), y.data(), I.bias->data(), I.passes * T, 2, I.passes, I.bias->plain_modulus(), 0, s), "dpfhe_add_plain_scaled");
     y.set_ntt(false);
     // enqueue only: the scratch belongs to the layer, the caller synchronises (Context::synchronize) before reading y
 }
@@ -1872,14 +1965,20 @@ public:
 };
 
 PackedTransformerBlock::PackedTransformerBlock(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
-                                               const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h) : impl_(new Impl) {
+                                               const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h)
+    : PackedTransformerBlock(ctx, enc, ks, W_qkv, W_o, W_up, W_down, d, h, nullptr, nullptr, nullptr, nullptr) {}
+
+PackedTransformerBlock::PackedTransformerBlock(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
+                                               const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h, const uint64_t* b_qkv, const uint64_t* b_o,
+                                               const uint64_t* b_up, const uint64_t* b_down) : impl_(new Impl) {
     if (!W_qkv || !W_o || !W_up || !W_down || d == 0 || h == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedTransformerBlock: null or empty matrix");
     Impl& I = *impl_;
     I.ctx = &ctx; I.ks = &ks; I.d = d; I.h = h;
-    I.qkv.reset(new PackedLinear(ctx, enc, ks, W_qkv, 3 * d, d));
-    I.proj.reset(new PackedLinear(ctx, enc, ks, W_o, d, d));
-    I.up.reset(new PackedLinear(ctx, enc, ks, W_up, h, d));
-    I.down.reset(new PackedLinear(ctx, enc, ks, W_down, d, h));
+    // the biases ride on the layers: b_v reaches `a` through the PackedSelect of the v third, b_up enters W_down's input with W_up h1
+    I.qkv.reset(new PackedLinear(ctx, enc, ks, W_qkv, 3 * d, d, 1, b_qkv));
+    I.proj.reset(new PackedLinear(ctx, enc, ks, W_o, d, d, 1, b_o));
+    I.up.reset(new PackedLinear(ctx, enc, ks, W_up, h, d, 1, b_up));
+    I.down.reset(new PackedLinear(ctx, enc, ks, W_down, d, h, 1, b_down));
     const size_t row = ctx.params().n() / 2;
     // the hand-overs below rely on: one output ciphertext per layer, outputs of the wide layers at slot r of row 0 (out >= period),
     // and W_down consuming a vector that fills a whole slot row

@@ -425,6 +425,19 @@ class Evaluator:
                     "dpfhe_expand_uniform")
         return t
 
+    # ---- exact plaintext addition (include/dpfhe.h dpfhe_add_plain_scaled) ----------------------------------------------------------
+    def add_plain_scaled_(self, ct: torch.Tensor, plain: torch.Tensor, t: int, negate: bool = False, stream=None) -> torch.Tensor:
+        """in place: ct [batch][comps][L][N] (comps 2 or 3, exact BFV-style, coefficient domain) gets c0 += round(Q b / t) mod q_l (-= with negate)
+        for b = plain [P][N] words in [0, 2^32); item i takes plaintext item i / (batch / P).  Decrypts to (m +- b) mod t."""
+        self._chk(ct)
+        p = self.ctx.params
+        if ct.dim() != 4 or plain.dim() != 2 or plain.shape[-1] != p.n or plain.dtype != torch.int64 or not plain.is_contiguous() \
+                or plain.device != ct.device:
+            raise _cabi.DpfheError(2000, "add_plain_scaled_: a [batch][comps][L][N] ciphertext tensor and a contiguous int64 [P][N] plaintext on its device")
+        _cabi.check(self._lib.dpfhe_add_plain_scaled(self.ctx.handle, ct.data_ptr(), ct.data_ptr(), plain.data_ptr(), ct.shape[0], ct.shape[1],
+                                                     plain.shape[0], int(t), 1 if negate else 0, self._sp(stream)), "dpfhe_add_plain_scaled")
+        return ct
+
     # ---- N3, round 3: baby-step / giant-step with the division by P deferred (include/dpfhe.h) ---------------------------
     def rotate_hoisted_qp(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> torch.Tensor:
         """[T][2][L-1][N] coefficient-domain inputs on the extended context -> [1 + k][T][2][L][N], NTT domain over Q P:

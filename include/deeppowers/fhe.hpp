@@ -144,6 +144,29 @@ public:
     explicit Ciphertext(const Context& ctx, size_t size = 2, size_t batch = 1, bool is_ntt = false);
 };
 
+class BatchEncoder;
+// Device plaintext over Z_t for EXACT (BFV-style) ciphertexts - the bias of an encrypted layer: `items` polynomials of N coefficients in [0, t)
+// ([items][N] u64 words, include/dpfhe.h dpfhe_add_plain_scaled).  Evaluator::add_plain_exact adds round(Q b / t) to c0, so the ciphertext decrypts to
+// (m + b) mod t; item i of a ciphertext batch takes plaintext item i / (batch / items).
+class ExactPlaintext {
+public:
+    // t odd, 3 <= t < 2^32 (coprime to the moduli: checked when it is added); all coefficients start at 0
+    ExactPlaintext(const Context& ctx, uint64_t plain_modulus, size_t items = 1);
+    ~ExactPlaintext();
+    ExactPlaintext(const ExactPlaintext&) = delete;
+    ExactPlaintext& operator=(const ExactPlaintext&) = delete;
+    void set_coefficients(const int64_t* coeffs);   // items * N values, centred or non-negative: reduced mod t
+    void set_slots(const BatchEncoder& enc, const uint64_t* slots);   // items * N slot values < t, encoded on the host with enc (same t)
+    size_t items() const;
+    uint64_t plain_modulus() const;
+    size_t ring_degree() const;     // N
+    const uint64_t* data() const;   // device, [items][N]
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
 // Plaintext scalar weights of a linear layer: rows x cols integers, stored as one residue per limb ([rows][cols][L]).
 class ScalarMatrix {
 public:
@@ -215,6 +238,10 @@ public:
     void matvec_scalar(const ScalarMatrix& W, const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
     // A8: modular sum over the batch -> one item
     void reduce_sum(const PolyBuffer& in, PolyBuffer& out, Stream* stream = nullptr) const;
+    // exact plaintext addition / subtraction: out = in with c0 +- round(Q b / t) (dpfhe_add_plain_scaled), so it decrypts to (m +- b) mod t.  in: 2 or 3
+    // components (an ExactMultiplier product before relinearisation too), coefficient domain, batch a multiple of p.items(); out: same shape (may be in).
+    void add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
+    void sub_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
 
 private:
     class Impl;
@@ -480,6 +507,11 @@ public:
     PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext = 1);
     // square d x d (d a power of two dividing N/2)
     PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t d);
+    // y = W x + bias: `bias` holds out_dim values < t (null: exactly the constructor above).  Every slot that holds output row R gets bias[R] (0 where no
+    // row is), encoded once per output ciphertext and kept on the device; apply() ends with one exact plaintext addition on its stream.
+    PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim,
+                 size_t tokens_per_ciphertext, const uint64_t* bias);
+    bool has_bias() const;
     ~PackedLinear();
     PackedLinear(const PackedLinear&) = delete;
     PackedLinear& operator=(const PackedLinear&) = delete;
@@ -548,6 +580,11 @@ public:
     // row-major weights with entries < t: W_qkv (3 d x d, rows [q | k | v]), W_o (d x d), W_up (h x d), W_down (d x h)
     PackedTransformerBlock(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
                            const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h);
+    // with the biases of the four dense sites (each may be null; values < t): b_qkv (3 d, [q | k | v]), b_o (d), b_up (h), b_down (d):
+    //     qkv = W_qkv x + b_qkv,  a = v + b_v,  h1 = x + W_o a + b_o,  h2 = h1 + W_down (W_up h1 + b_up) + b_down   (stage() reports the biased values)
+    PackedTransformerBlock(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
+                           const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h, const uint64_t* b_qkv, const uint64_t* b_o,
+                           const uint64_t* b_up, const uint64_t* b_down);
     ~PackedTransformerBlock();
     PackedTransformerBlock(const PackedTransformerBlock&) = delete;
     PackedTransformerBlock& operator=(const PackedTransformerBlock&) = delete;

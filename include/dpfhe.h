@@ -312,6 +312,19 @@ int dpfhe_expand_uniform(dpfhe_ctx* ctx, uint64_t* d_buf, size_t batch, size_t c
 int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t components,
                               uint32_t component, const uint8_t seed[32], uint64_t first_item);
 
+/* -- exact plaintext addition: a plaintext b over Z_t added to (or, negate != 0, subtracted from) exact BFV-style ciphertexts - the bias of an encrypted
+ * linear layer.  d_in, d_out: [batch][comps][L][N] coefficient-domain ciphertexts (comps 2 or 3: also an unrelinearised product); d_plain: [plain_items][N]
+ * words b in [0, 2^32) (BatchEncoder::decode's input convention); ciphertext item i uses plaintext item i / (batch / plain_items).
+ * Component 0 becomes c0 +- round(Q b / t) mod q_l, Q = prod q_l; the other components are copied when d_out != d_in (in place is allowed).
+ * t odd, 3 <= t < 2^32, coprime to every q_l.  DPFHE_INVALID_ARGUMENT, before touching the device, on a null pointer, comps not 2 or 3, batch not a
+ * multiple of plain_items, such a t, or out and in overlapping without being the same buffer.
+ * dpfhe_add_plain_scaled_host: the same words on the host (no device, no context; moduli odd, >= 3 and < 2^60, log2_n in [8, 16]; plaintext words
+ * >= 2^32 are rejected there, on the device they are a caller error). */
+int dpfhe_add_plain_scaled(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_in, const uint64_t* d_plain, size_t batch, size_t comps, size_t plain_items,
+                           uint64_t t, int negate, void* stream);
+int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
+                                size_t batch, size_t comps, size_t plain_items, uint64_t t, int negate);
+
 const char* dpfhe_strerror(int code);
 /* text of the last HIP/RCCL failure on the calling thread ("" if none) */
 const char* dpfhe_last_error(void);
