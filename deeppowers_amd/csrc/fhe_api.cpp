@@ -382,6 +382,86 @@ void ExactPlaintext::set_slots(const BatchEncoder& enc, const uint64_t* slots) {
     impl_->upload(coeffs.data());
 }
 
+// ---- CompactCiphertext ------------------------------------------------------------------------------------------------------
+class CompactCiphertext::Impl {
+public:
+    const Context* ctx = nullptr;
+    size_t batch = 0, bytes = 0;
+    unsigned bits[2] = {0, 0};
+    uint8_t* d = nullptr;
+    ~Impl() {
+        if (d) (void)hipFree(d);
+    }
+};
+CompactCiphertext::CompactCiphertext(const Context& ctx, size_t batch, unsigned bits0, unsigned bits1) : impl_(new Impl) {
+    if (batch == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext: batch must be > 0");
+    if (bits0 < 8 || bits0 > 60 || bits1 < 8 || bits1 > 60) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext: widths must lie in [8, 60]");
+    impl_->ctx = &ctx; impl_->batch = batch; impl_->bits[0] = bits0; impl_->bits[1] = bits1;
+    impl_->bytes = batch * (ctx.params().n() * (bits0 + bits1) / 8);
+    hip_check(hipSetDevice(ctx.device_id()), "hipSetDevice");
+    void* p = nullptr;
+    hip_check(hipMalloc(&p, impl_->bytes), "hipMalloc");
+    impl_->d = static_cast<uint8_t*>(p);
+}
+CompactCiphertext::~CompactCiphertext() = default;
+size_t CompactCiphertext::batch() const { return impl_->batch; }
+unsigned CompactCiphertext::bits(unsigned c) const {
+    if (c > 1) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::bits: component 0 or 1");
+    return impl_->bits[c];
+}
+size_t CompactCiphertext::ring_degree() const { return impl_->ctx->params().n(); }
+size_t CompactCiphertext::bytes() const { return impl_->bytes; }
+uint8_t* CompactCiphertext::data() { return impl_->d; }
+const uint8_t* CompactCiphertext::data() const { return impl_->d; }
+void CompactCiphertext::copy_to_host(uint8_t* dst) const {
+    if (!dst) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::copy_to_host: null destination");
+    hip_check(hipMemcpy(dst, impl_->d, impl_->bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+}
+void CompactCiphertext::copy_from_host(const uint8_t* src) {
+    if (!src) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::copy_from_host: null source");
+    hip_check(hipMemcpy(impl_->d, src, impl_->bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
+}
+
+namespace {
+const char kCompactMagic[8] = {'D', 'P', 'F', 'H', 'E', 'c', '1', 0};
+struct CompactHeader {   // DPFHEc1 (wire.py _CHDR): all little-endian
+    char magic[8];
+    uint32_t log2_n, bits0, bits1, reserved;
+    uint64_t batch;
+};
+static_assert(sizeof(CompactHeader) == 32, "the DPFHEc1 header is 32 bytes");
+}  // namespace
+
+void CompactCiphertext::save(std::ostream& os) const {
+    CompactHeader h{};
+    std::memcpy(h.magic, kCompactMagic, 8);
+    h.log2_n = impl_->ctx->params().log2_n; h.bits0 = impl_->bits[0]; h.bits1 = impl_->bits[1]; h.reserved = 0; h.batch = impl_->batch;
+    std::vector<uint8_t> host(impl_->bytes);
+    copy_to_host(host.data());
+    os.write(reinterpret_cast<const char*>(&h), sizeof h);
+    os.write(reinterpret_cast<const char*>(host.data()), (std::streamsize)host.size());
+    if (!os) throw Exception(ErrorCode::RUNTIME_ERROR, "CompactCiphertext::save: stream write failed");
+}
+void CompactCiphertext::load(std::istream& is) {
+    CompactHeader h{};
+    is.read(reinterpret_cast<char*>(&h), sizeof h);
+    if (!is || std::memcmp(h.magic, kCompactMagic, 8) != 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::load: not a DPFHEc1 stream");
+    if (h.log2_n != impl_->ctx->params().log2_n || h.bits0 != impl_->bits[0] || h.bits1 != impl_->bits[1] || h.reserved != 0 || h.batch != impl_->batch)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::load: header does not match this object (log2_n / widths / batch)");
+    std::vector<uint8_t> host(impl_->bytes);
+    is.read(reinterpret_cast<char*>(host.data()), (std::streamsize)host.size());
+    if (!is) throw Exception(ErrorCode::INVALID_ARGUMENT, "CompactCiphertext::load: truncated stream");
+    copy_from_host(host.data());
+}
+std::pair<unsigned, unsigned> CompactCiphertext::recommended_bits(unsigned log2_n, uint64_t t) {
+    if (log2_n < 8 || log2_n > 16 || t < 2 || (t >> 32)) throw Exception(ErrorCode::INVALID_ARGUMENT, "recommended_bits: log2_n in [8, 16], t in [2, 2^32)");
+    const double lt = std::log2((double)t);
+    const unsigned k0 = std::max(8u, (unsigned)std::ceil(lt) + 2);
+    const unsigned k1 = std::max(8u, (unsigned)std::ceil(lt + 3 + std::log2(std::sqrt((double)(1u << log2_n) * std::log(std::pow(2.0, 65)) / 2))));
+    if (k1 > 60) throw Exception(ErrorCode::INVALID_ARGUMENT, "recommended_bits: width above 60 bits");
+    return {k0, k1};
+}
+
 RelinKeys::RelinKeys(const Context& ctx) : PolyBuffer(ctx, ctx.params().n_limbs(), 2, /*is_ntt=*/true) {}
 GaloisKeys::GaloisKeys(const Context& ctx, uint32_t galois_elt) : PolyBuffer(ctx, ctx.params().n_limbs(), 2, /*is_ntt=*/true), galois_elt_(galois_elt) {
     if (!(galois_elt & 1u) || galois_elt >= 2 * ctx.params().n()) throw Exception(ErrorCode::INVALID_ARGUMENT, "GaloisKeys: galois_elt must be odd and < 2N");
@@ -484,6 +564,14 @@ void Evaluator::add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, C
 }
 void Evaluator::sub_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* s) const {
     add_plain_exact_impl(*impl_->ctx, in, p, out, true, s, "sub_plain_exact");
+}
+void Evaluator::compact(const Ciphertext& in, CompactCiphertext& out, Stream* s) const {
+    const FheParams& fp = impl_->ctx->params();
+    if (in.is_ntt()) throw Exception(ErrorCode::INVALID_STATE, "compact: input must be in the coefficient domain");
+    if (in.size() != 2 || in.words() != in.batch() * 2 * fp.n_limbs() * fp.n())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "compact: input must be a 2-component ciphertext of this context");
+    if (out.batch() != in.batch() || out.ring_degree() != fp.n()) throw Exception(ErrorCode::INVALID_ARGUMENT, "compact: batch or ring degree differs");
+    check(dpfhe_compact(impl_->h(), out.data(), in.data(), in.batch(), out.bits(0), out.bits(1), s), "dpfhe_compact");
 }
 // ---- ExactMultiplier ------------------------------------------------------------------------------------------------------------
 class ExactMultiplier::Impl {
@@ -1289,6 +1377,68 @@ double Decryptor::noise_budget_bits(const Ciphertext& ct, uint64_t t) {
         if (b > worst) worst = b;
     });
     return bits(impl_->Q) - 1.0 - worst;
+}
+
+namespace {
+// per coefficient of every item of a compact ciphertext: (K, phase in [0, 2^K)), phase = c0 2^(K - k0) + (c1 * s) 2^(K - k1) mod 2^K
+template <class F>
+void for_each_compact_phase(const CompactCiphertext& ct, const std::vector<int8_t>& s, F f) {
+    const size_t n = ct.ring_degree();
+    const unsigned k0 = ct.bits(0), k1 = ct.bits(1), K = std::max(k0, k1);
+    const size_t rec = n * (k0 + k1) / 8;
+    std::vector<uint8_t> host(ct.bytes());
+    ct.copy_to_host(host.data());
+    auto value = [](const uint8_t* bytes, size_t j, unsigned k) {   // bits [j k, (j + 1) k) of a little-endian bit string
+        uint64_t v = 0;
+        for (unsigned b = 0; b < k; ++b) {
+            const size_t bit = j * k + b;
+            v |= (uint64_t)((bytes[bit / 8] >> (bit % 8)) & 1u) << b;
+        }
+        return v;
+    };
+    std::vector<uint64_t> c0(n), c1(n), acc(n);
+    const uint64_t mask = K == 64 ? ~0ull : (1ull << K) - 1;
+    for (size_t item = 0; item < ct.batch(); ++item) {
+        const uint8_t* r = host.data() + item * rec;
+        for (size_t j = 0; j < n; ++j) { c0[j] = value(r, j, k0); c1[j] = value(r + n * k0 / 8, j, k1); }
+        std::fill(acc.begin(), acc.end(), 0);
+        for (size_t j = 0; j < n; ++j) {   // c1 * s in Z_2^64[X]/(X^N + 1): s_j c1 X^j
+            if (!s[j]) continue;
+            const uint64_t sj = (uint64_t)(int64_t)s[j];   // +-1 in wrapping arithmetic
+            for (size_t i = 0; i + j < n; ++i) acc[i + j] += sj * c1[i];
+            for (size_t i = n - j; i < n; ++i) acc[i + j - n] -= sj * c1[i];   // X^N = -1
+        }
+        for (size_t k = 0; k < n; ++k) f(item, k, K, ((c0[k] << (K - k0)) + (acc[k] << (K - k1))) & mask);
+    }
+}
+}  // namespace
+
+void Decryptor::decrypt_exact(const CompactCiphertext& ct, uint64_t t, uint64_t* out) {
+    if (!out) throw Exception(ErrorCode::INVALID_ARGUMENT, "decrypt_exact: null output");
+    if (t < 2 || t >> 32) throw Exception(ErrorCode::INVALID_ARGUMENT, "decrypt_exact: plaintext modulus must be in [2, 2^32)");
+    if (ct.ring_degree() != impl_->ctx->params().n()) throw Exception(ErrorCode::INVALID_ARGUMENT, "decrypt_exact: ring degree differs");
+    const size_t n = ct.ring_degree();
+    for_each_compact_phase(ct, impl_->sk->coefficients(), [&](size_t item, size_t k, unsigned K, uint64_t phase) {
+        const u128 m = ((u128)t * phase + ((u128)1 << (K - 1))) >> K;   // round(t phase / 2^K), in [0, t]
+        out[item * n + k] = (uint64_t)(m % t);
+    });
+}
+
+double Decryptor::noise_budget_bits(const CompactCiphertext& ct, uint64_t t) {
+    if (t < 2 || t >> 32) throw Exception(ErrorCode::INVALID_ARGUMENT, "noise_budget_bits: plaintext modulus must be in [2, 2^32)");
+    if (ct.ring_degree() != impl_->ctx->params().n()) throw Exception(ErrorCode::INVALID_ARGUMENT, "noise_budget_bits: ring degree differs");
+    double worst = 0.0;   // most noise bits seen
+    unsigned K = 0;
+    for_each_compact_phase(ct, impl_->sk->coefficients(), [&](size_t, size_t, unsigned k, uint64_t phase) {
+        K = k;
+        // e = t phase - m 2^K with m = round(t phase / 2^K): |e| <= 2^(K-1), exact in 128 bits (t phase < 2^92)
+        const u128 tp = (u128)t * phase, m = (tp + ((u128)1 << (K - 1))) >> K, mq = m << K;
+        const u128 e = tp >= mq ? tp - mq : mq - tp;
+        const uint64_t hi = (uint64_t)(e >> 64), lo = (uint64_t)e;
+        const double b = hi ? 128.0 - __builtin_clzll(hi) : (lo ? 64.0 - __builtin_clzll(lo) : 0.0);
+        if (b > worst) worst = b;
+    });
+    return (double)(K + 1) - 1.0 - worst;   // bits(2^K) - 1 - worst, as for Q above
 }
 
 // ---- HybridKeySwitcher ---------------------------------------------------------------------------------------------------

@@ -1,0 +1,100 @@
+// k_compact.hip - compact result ciphertexts (compact.h): the device kernel, its launcher and the host twin.
+//
+// One lane per pair of coefficients: for each component it reads its pair of every limb row (16-byte loads, each row contiguous across the wave),
+// computes the two switched values in registers and parks them in LDS.  After one barrier the block's bit strings are gathered from LDS into
+// 16-byte chunks: the block's 2 T values of component c are 2 T k_c bits = T k_c / 64 chunks (T >= 128 lanes, so every chunk is whole and
+// starts on a 32-byte boundary of the record), and every global store is one full 16-byte contiguous store.
+#include "compact.h"
+
+namespace dpfhe {
+
+typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
+
+constexpr u32 kCompactThreads = 256;
+
+// lane `tid`'s two values of component C, parked in LDS
+template <int NL, int C>
+__device__ __forceinline__ void compact_pair(u64* vals, const u64* __restrict__ in, const CompactArgs& a, size_t item, size_t poly, size_t k, u32 tid) {
+    const u64* src = in + (item * 2 + C) * NL * poly + k;
+    u64 x0[NL], x1[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const u64x2_t w = *reinterpret_cast<const u64x2_t*>(src + l * poly);
+        x0[l] = w.x;
+        x1[l] = w.y;
+    }
+    vals[2 * tid] = compact_value<NL>(x0, C, a);
+    vals[2 * tid + 1] = compact_value<NL>(x1, C, a);
+}
+
+// block b = (item << log2_chunks) + chunk;  lane t of the chunk owns coefficients 2 j, 2 j + 1, j = chunk * blockDim.x + t
+template <int NL>
+__global__ __launch_bounds__(kCompactThreads) void compact_kernel(uint8_t* __restrict__ out, const u64* __restrict__ in, const CompactArgs a, u32 log2n,
+                                                                  u32 log2_chunks) {
+    __shared__ u64 vals[2][2 * kCompactThreads];
+    const u32 tid = threadIdx.x, T = blockDim.x;
+    const u32 chunk = blockIdx.x & ((1u << log2_chunks) - 1u);
+    const size_t item = blockIdx.x >> log2_chunks;
+    const size_t poly = (size_t)1 << log2n;
+    const size_t k = 2 * ((size_t)chunk * T + tid);
+    compact_pair<NL, 0>(vals[0], in, a, item, poly, k, tid);
+    compact_pair<NL, 1>(vals[1], in, a, item, poly, k, tid);
+    __syncthreads();
+    const u32 ch0 = T * a.bits[0] / 64, ch1 = T * a.bits[1] / 64;   // 16-byte chunks of the block's bit string per component
+    uint8_t* rec = out + item * compact_record_bytes(log2n, a);
+    for (u32 m = tid; m < ch0 + ch1; m += T) {
+        const u32 c = m >= ch0 ? 1u : 0u, mm = c ? m - ch0 : m, kb = a.bits[c];
+        const u32 b0 = 128 * mm;                                          // chunk mm holds bits [b0, b0 + 128) of the block's string
+        u64 lo = 0, hi = 0;
+        for (u32 j = b0 / kb; j <= (b0 + 127) / kb; ++j) {               // the <= 17 values that overlap it
+            const u64 v = vals[c][j];
+            const int p = (int)(j * kb) - (int)b0;
+            if (p < 0) lo |= v >> -p;
+            else if (p == 0) lo |= v;
+            else if (p < 64) { lo |= v << p; hi |= v >> (64 - p); }
+            else hi |= v << (p - 64);
+        }
+        const size_t off = (c ? ((size_t)a.bits[0] << log2n) / 8 : 0) + (size_t)chunk * T * kb / 4 + 16 * (size_t)mm;
+        *reinterpret_cast<u64x2_t*>(rec + off) = u64x2_t{lo, hi};
+    }
+}
+
+int launch_compact(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a, hipStream_t s) {
+    const u32 pairs = 1u << (log2n - 1);                       // lanes per residue polynomial (log2n >= 8: at least two waves)
+    const u32 threads = pairs < kCompactThreads ? pairs : kCompactThreads;
+    u32 log2_chunks = 0;
+    while ((threads << log2_chunks) < pairs) ++log2_chunks;
+    const size_t grid = batch << log2_chunks;
+    if (grid == 0 || grid > 0x7fffffffu || (grid >> log2_chunks) != batch) return -1;
+    const bool ok = compact_with_limbs(a.n_limbs, [&](auto nl) {
+        hipLaunchKernelGGL(compact_kernel<decltype(nl)::value>, dim3((unsigned)grid), dim3(threads), 0, s, out, in, a, (u32)log2n, log2_chunks);
+    });
+    return ok ? 0 : -1;
+}
+
+void compact_host(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a) {
+    const size_t n = (size_t)1 << log2n, rec = compact_record_bytes(log2n, a);
+    compact_with_limbs(a.n_limbs, [&](auto nl) {
+        constexpr int NL = decltype(nl)::value;
+        for (size_t i = 0; i < batch; ++i) {
+            uint8_t* dst = out + i * rec;
+            for (int c = 0; c < 2; ++c) {
+                const u64* src = in + (i * 2 + c) * NL * n;
+                const u32 kb = a.bits[c];
+                for (size_t b = 0; b < (n * kb) / 8; ++b) dst[b] = 0;
+                for (size_t j = 0; j < n; ++j) {
+                    u64 x[NL];
+                    for (int l = 0; l < NL; ++l) x[l] = src[l * n + j];
+                    const u64 v = compact_value<NL>(x, c, a);
+                    for (u32 b = 0; b < kb; ++b) {
+                        const size_t bit = j * kb + b;
+                        dst[bit / 8] |= (uint8_t)(((v >> b) & 1u) << (bit % 8));
+                    }
+                }
+                dst += (n * kb) / 8;
+            }
+        }
+    });
+}
+
+}  // namespace dpfhe

@@ -438,6 +438,23 @@ class Evaluator:
                                                      plain.shape[0], int(t), 1 if negate else 0, self._sp(stream)), "dpfhe_add_plain_scaled")
         return ct
 
+    # ---- compact result ciphertexts (include/dpfhe.h dpfhe_compact) ------------------------------------------------------------------
+    def compact(self, ct: torch.Tensor, bits0: int, bits1: int, stream=None) -> torch.Tensor:
+        """ct [batch][2][L][N] (coefficient domain) -> a new uint8 tensor [batch][N (bits0 + bits1) / 8]: each component switched from Q to
+        2^bits (round(2^k X / Q) mod 2^k) and bit-packed, the DPFHEc1 records (wire.dumps_compact).  Widths from wire.compact_bits."""
+        self._chk(ct)
+        p = self.ctx.params
+        if ct.dim() != 4 or ct.shape[1] != 2 or ct.shape[0] == 0:
+            raise _cabi.DpfheError(2000, "compact: a [batch][2][L][N] ciphertext tensor, batch >= 1")
+        if not (8 <= int(bits0) <= 60 and 8 <= int(bits1) <= 60):
+            raise _cabi.DpfheError(2000, "compact: widths must lie in [8, 60]")
+        rec = ((int(bits0) + int(bits1)) << p.log2_n) // 8
+        with self._on(stream):
+            out = torch.empty((ct.shape[0], rec), dtype=torch.uint8, device=self.ctx.device)
+        _cabi.check(self._lib.dpfhe_compact(self.ctx.handle, out.data_ptr(), ct.data_ptr(), ct.shape[0], int(bits0), int(bits1), self._sp(stream)),
+                    "dpfhe_compact")
+        return out
+
     # ---- N3, round 3: baby-step / giant-step with the division by P deferred (include/dpfhe.h) ---------------------------
     def rotate_hoisted_qp(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> torch.Tensor:
         """[T][2][L-1][N] coefficient-domain inputs on the extended context -> [1 + k][T][2][L][N], NTT domain over Q P:

@@ -6,7 +6,11 @@ Seeded streams (DPFHEs1, the twin of PolyBuffer::save_seeded / load_seeded): one
 ciphertext, the a_j of a key - is not sent but re-expanded from a public 32-byte seed (include/dpfhe.h dpfhe_expand_uniform).
 Header, 80 bytes, little-endian: b"DPFHEs1\0", u32 log2_n, u32 n_limbs, u64 batch, u64 components, u32 is_ntt,
 u32 expanded_component, u64 first_item, u8 seed[32]; then u64 moduli[n_limbs]; then the words of every OTHER component,
-[batch][components - 1][L][N].  Size = 80 + 8 L + 8 batch (components - 1) L N.  A seed must never be reused under one secret key."""
+[batch][components - 1][L][N].  Size = 80 + 8 L + 8 batch (components - 1) L N.  A seed must never be reused under one secret key.
+
+Compact result streams (DPFHEc1, the twin of CompactCiphertext::save / load): 2-component results switched from Q to 2^k_c and bit-packed
+(include/dpfhe.h dpfhe_compact).  32-byte header: b"DPFHEc1\0", u32 log2_n, u32 bits0, u32 bits1, u32 reserved = 0, u64 batch; then the records,
+N (bits0 + bits1) / 8 bytes each.  loads / loads_seeded reject them (another magic)."""
 from __future__ import annotations
 
 import struct
@@ -144,3 +148,68 @@ def inflate_seeded(stored: np.ndarray, params: FheParams, seed: bytes, component
     full[:, :component] = stored[:, :component]
     full[:, component + 1:] = stored[:, component:]
     return expand_host(params, batch, kept + 1, component, seed, first_item, out=full)
+
+
+COMPACT_MAGIC = b"DPFHEc1\0"
+_CHDR = struct.Struct("<8sIIIIQ")
+
+
+def compact_bits(log2_n: int, t: int) -> tuple[int, int]:
+    """Recommended widths (k_0, k_1) of a compact result (Evaluator.compact, DPFHEc1) for plaintext modulus t at N = 2^log2_n:
+    k_0 = ceil(log2 t) + 2, k_1 = ceil(log2 t + 3 + log2 sqrt(N ln(2^65) / 2)).  The c0 rounding costs at most 1/8 of the decryption tolerance, the
+    c1 rounding times the ternary secret at most 1/8 with probability >= 1 - 2^-64 per coefficient (Hoeffding over <= N terms), so any ciphertext
+    with a noise budget of at least 2 bits still decrypts.  Both widths are at least 8; ValueError if one would exceed 60."""
+    import math
+    if not (8 <= log2_n <= 16) or not (2 <= t < 1 << 32):
+        raise ValueError("log2_n in [8, 16] and t in [2, 2^32)")
+    lt = math.log2(t)
+    k0 = max(8, math.ceil(lt) + 2)
+    k1 = max(8, math.ceil(lt + 3 + math.log2(math.sqrt((1 << log2_n) * math.log(2.0 ** 65) / 2))))
+    if k1 > 60:
+        raise ValueError("width above 60 bits")
+    return k0, k1
+
+
+def compact_record_bytes(log2_n: int, bits0: int, bits1: int) -> int:
+    return ((bits0 + bits1) << log2_n) // 8
+
+
+def dumps_compact(records: np.ndarray, log2_n: int, bits0: int, bits1: int) -> bytes:
+    """records: uint8 [batch][N (bits0 + bits1) / 8] (Evaluator.compact, dpfhe_compact_host).  32-byte little-endian header: b"DPFHEc1\\0",
+    u32 log2_n, u32 bits0, u32 bits1, u32 reserved = 0, u64 batch; then the records.  Size = 32 + batch N (bits0 + bits1) / 8."""
+    a = np.ascontiguousarray(records, dtype=np.uint8)
+    if not (8 <= log2_n <= 16) or not (8 <= bits0 <= 60) or not (8 <= bits1 <= 60):
+        raise ValueError("log2_n in [8, 16] and widths in [8, 60]")
+    if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] != compact_record_bytes(log2_n, bits0, bits1):
+        raise ValueError("records must be [batch][N (bits0 + bits1) / 8] with batch >= 1")
+    return _CHDR.pack(COMPACT_MAGIC, log2_n, bits0, bits1, 0, a.shape[0]) + a.tobytes()
+
+
+def loads_compact(blob: bytes):
+    """-> (records uint8 [batch][N (bits0 + bits1) / 8], log2_n, bits0, bits1).  Raises ValueError on a bad header or a wrong size."""
+    if len(blob) < _CHDR.size:
+        raise ValueError("truncated header")
+    magic, log2_n, bits0, bits1, reserved, batch = _CHDR.unpack_from(blob, 0)
+    if magic != COMPACT_MAGIC:
+        raise ValueError("not a DPFHEc1 stream")
+    if reserved != 0 or not (8 <= log2_n <= 16) or not (8 <= bits0 <= 60) or not (8 <= bits1 <= 60) or batch == 0:
+        raise ValueError("bad header")
+    rec = compact_record_bytes(log2_n, bits0, bits1)
+    if len(blob) != _CHDR.size + batch * rec:
+        raise ValueError("payload size does not match the header")
+    return np.frombuffer(blob, dtype=np.uint8, offset=_CHDR.size).reshape(batch, rec).copy(), int(log2_n), int(bits0), int(bits1)
+
+
+def compact_host(params: FheParams, words: np.ndarray, bits0: int, bits1: int) -> np.ndarray:
+    """Host twin of Evaluator.compact / dpfhe_compact: words uint64 [batch][2][L][N] -> records uint8 [batch][N (bits0 + bits1) / 8]."""
+    import ctypes as C
+
+    from . import _cabi
+    a = np.ascontiguousarray(words, dtype=np.uint64)
+    if a.ndim != 4 or a.shape[1] != 2 or a.shape[2] != params.n_limbs or a.shape[3] != params.n:
+        raise ValueError("words must be [batch][2][L][N]")
+    out = np.empty((a.shape[0], compact_record_bytes(params.log2_n, bits0, bits1)), dtype=np.uint8)
+    lib = _cabi.load()
+    m = (C.c_uint64 * params.n_limbs)(*params.moduli)
+    _cabi.check(lib.dpfhe_compact_host(m, params.n_limbs, params.log2_n, out.ctypes.data, a.ctypes.data, a.shape[0], bits0, bits1), "dpfhe_compact_host")
+    return out

@@ -167,6 +167,39 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// Compact result ciphertext (stream "DPFHEc1\0"): a 2-component exact ciphertext switched from Q to 2^k_c per component and bit-packed on the device
+// (include/dpfhe.h dpfhe_compact), N (bits0 + bits1) / 8 bytes per item instead of 16 L N.  Device-resident: batch records, item i's record at byte
+// i N (bits0 + bits1) / 8, component 0 first, value j of a component at bits [j k, (j + 1) k) of its little-endian bit string.  Only the holder of the
+// secret key reads it back (Decryptor::decrypt_exact / noise_budget_bits overloads).  The switch is public: security rests on the secret, as for rescale.
+class CompactCiphertext {
+public:
+    // widths in [8, 60] (recommended_bits); throws INVALID_ARGUMENT otherwise or for batch 0
+    CompactCiphertext(const Context& ctx, size_t batch, unsigned bits0, unsigned bits1);
+    ~CompactCiphertext();
+    CompactCiphertext(const CompactCiphertext&) = delete;
+    CompactCiphertext& operator=(const CompactCiphertext&) = delete;
+    size_t batch() const;
+    unsigned bits(unsigned component) const;
+    size_t ring_degree() const;   // N
+    size_t bytes() const;         // batch * N (bits0 + bits1) / 8
+    uint8_t* data();              // device
+    const uint8_t* data() const;
+    void copy_to_host(uint8_t* dst) const;        // bytes() bytes
+    void copy_from_host(const uint8_t* src);
+    // 32-byte little-endian header: magic, u32 log2_n, u32 bits0, u32 bits1, u32 reserved = 0, u64 batch; then the records (32 + bytes() in all).
+    // load() checks the header against this object (throws INVALID_ARGUMENT on any difference or a truncated stream).
+    void save(std::ostream& os) const;
+    void load(std::istream& is);
+    // widths for plaintext modulus t at N = 2^log2_n: k0 = ceil(log2 t) + 2, k1 = ceil(log2 t + 3 + log2 sqrt(N ln(2^65) / 2)) (both at least 8).
+    // Any ciphertext with a noise budget of at least 2 bits decrypts from them (c0 rounding <= 1/8 of the tolerance, c1 rounding times s <= 1/8 with
+    // probability >= 1 - 2^-64 per coefficient).  t = 65537: (19, 27) at N = 2^11, (19, 28) at 2^12 and 2^13, (19, 29) at 2^14.
+    static std::pair<unsigned, unsigned> recommended_bits(unsigned log2_n, uint64_t plain_modulus);
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
 // Plaintext scalar weights of a linear layer: rows x cols integers, stored as one residue per limb ([rows][cols][L]).
 class ScalarMatrix {
 public:
@@ -242,6 +275,9 @@ public:
     // components (an ExactMultiplier product before relinearisation too), coefficient domain, batch a multiple of p.items(); out: same shape (may be in).
     void add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
     void sub_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
+    // compact result: out = in switched to 2^k_c and bit-packed (dpfhe_compact; enqueue only).  in: 2 components, coefficient domain, in.batch() items
+    // (INVALID_STATE for an NTT-domain input, INVALID_ARGUMENT for 3 components, a batch or ring-degree mismatch, or more than 10 limbs: rescale first).
+    void compact(const Ciphertext& in, CompactCiphertext& out, Stream* stream = nullptr) const;
 
 private:
     class Impl;
@@ -394,6 +430,10 @@ public:
     // log2(Q / 2) - log2 |t * phase - Q * round(t * phase / Q)|, exact big-integer arithmetic.  Decryption is correct while it is > 0;
     // a fresh ciphertext at N = 8192 with five 60-bit limbs and t = 65537 has ~ 270 bits.  Host-side (whoever holds the secret key).
     double noise_budget_bits(const Ciphertext& ct, uint64_t plain_modulus);
+    // the same from compact form, exact on the host: K = max(bits), phase = c0 2^(K - bits0) + (c1 * s) 2^(K - bits1) mod 2^K (negacyclic product in
+    // wrapping 64-bit arithmetic), m = round(t phase / 2^K) mod t; the budget is the expression above with 2^K in place of Q.
+    void decrypt_exact(const CompactCiphertext& ct, uint64_t plain_modulus, uint64_t* messages_out);
+    double noise_budget_bits(const CompactCiphertext& ct, uint64_t plain_modulus);
 
 private:
     class Impl;

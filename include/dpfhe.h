@@ -325,6 +325,19 @@ int dpfhe_add_plain_scaled(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_in
 int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
                                 size_t batch, size_t comps, size_t plain_items, uint64_t t, int negate);
 
+/* -- compact result ciphertexts (stream DPFHEc1): a public modulus switch of 2-component ciphertexts from Q = prod q_l to 2^k, then bit-packing.
+ * d_in: [batch][2][L][N] coefficient-domain canonical residues, X in [0, Q) a coefficient's CRT value; component c becomes, with k = bits_c,
+ *   round(2^k X / Q) mod 2^k  (Q is odd: no tie).  d_out: batch records of N (bits0 + bits1) / 8 bytes; item i's record starts at byte i N (bits0 + bits1) / 8,
+ *   component 0 (N bits0 / 8 bytes) first; value j holds bits [j k, (j + 1) k) of its component's little-endian bit string (bit b: bit b % 8 of byte b / 8).
+ * Decryption (client): K = max(bits), phase = c0 2^(K - bits0) + (c1 * s) 2^(K - bits1) mod 2^K, m = round(t phase / 2^K) mod t.
+ * dpfhe_compact enqueues only (no allocation, no synchronise).  DPFHE_INVALID_ARGUMENT on a null pointer, batch 0, a width outside [8, 60],
+ *   more than 10 limbs (rescale first), in or out not 16-byte aligned, in and out overlapping, or a grid too large for one launch.
+ * dpfhe_compact_host: the same bytes on the host (no device, no context); also rejects log2_n outside [8, 16] and moduli that are even, < 3, >= 2^60
+ *   or not pairwise coprime. */
+int dpfhe_compact(dpfhe_ctx* ctx, uint8_t* d_out, const uint64_t* d_in, size_t batch, uint32_t bits0, uint32_t bits1, void* stream);
+int dpfhe_compact_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint8_t* out, const uint64_t* in, size_t batch,
+                       uint32_t bits0, uint32_t bits1);
+
 const char* dpfhe_strerror(int code);
 /* text of the last HIP/RCCL failure on the calling thread ("" if none) */
 const char* dpfhe_last_error(void);
