@@ -7,6 +7,11 @@ A "step" = one pass of the hot path over this rank's shard of synthetic cipherte
 Weak scaling: --batch-per-gpu ciphertext pairs per GPU (default 8192 = BASELINE configs[3] per-GPU
 share of 65536), inputs resident in HBM before the timed region.  `value` = ct-muls by all ranks / time.
 
+A plain run does only what `value` needs: set-up, the sustained windows (run unreported: without them the chip is in another power regime and
+the step reads 2-3 % lower, MEASUREMENTS.md section 5), the choice of the multiply's form, the warm-up and the timed steps, `--dump-outputs`, and
+the line with the figures of those steps.  `--full` adds every block below that takes runs of its own (NTT, other configurations, live ALU
+ceiling and traffic, box regime, CPU baseline, the consistency checks, and at N>1 the all-reduce A/B and the C++ multi-GPU programs).
+
 Extra objects on the JSON line (the driver's stored record keeps `config`, `roofline` and `cpu_baseline` whole and only the NAMES of
 other keys, so everything a reader of that record needs is inside those three; full detail also goes to gpurun_out/bench_detail.json):
   roofline     - the dominant kernel of the timed region (the fused multiply, in the form config.autotune names): algorithmic bytes
@@ -266,12 +271,6 @@ def dry_run(args):
         per_rank = [float(v) for v in every.tolist()]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    want = msum(product(i) for i in range(world * B))   # world-size-1 recomputation of the same global batch
-    assert shard_bounds(world * B, world, rank) == (lo, lo + B)
-    ar_total = step_allreduce()
-    ok = torch.tensor([int(np.array_equal(total, want) and gathered.shape[0] == world and np.array_equal(ar_total, want))])
-    if dist.is_initialized():
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
     rates = [B * args.steps / e for e in per_rank]
     gather_us.sort()
     result = {"metric": "ciphertext-mul/s (N=4096, 4 RNS limbs)", "value": world * B * args.steps / elapsed, "unit": "ct-mul/s", "n_gpus": world, "steps": args.steps,
@@ -281,9 +280,17 @@ def dry_run(args):
                          "batch_per_gpu": B, "global_batch": B * world, "parallelism": f"batch-sharded x{world}, one process per rank", "collective": "torch.distributed all_gather_into_tensor (gloo)"},
               "per_rank_ct_mul_per_s": {"min": min(rates), "max": max(rates), "ranks": len(rates)},
               "allgather_us": {"median": gather_us[len(gather_us) // 2], "min": gather_us[0], "max": gather_us[-1]},
-              "reduce_consistent": bool(ok.item()), "global_sum_matches_world1": bool(ok.item()), "native_comm_id_shipped": id_ok,
-              "collective_ab": {"allreduce_total_equals_allgather_total": bool(ok.item()), "what": "all-gather + local sum against sum all-reduce + one mod-q pass (gloo)"}}
-    if dist.is_initialized() and world > 1:   # the rank-0 programs of the N>1 report, stood in by canned output; the host-side wait is real
+              "native_comm_id_shipped": id_ok}
+    if args.full:   # the checks and the all-reduce A/B of a --full run
+        want = msum(product(i) for i in range(world * B))   # world-size-1 recomputation of the same global batch
+        assert shard_bounds(world * B, world, rank) == (lo, lo + B)
+        ar_total = step_allreduce()
+        ok = torch.tensor([int(np.array_equal(total, want) and gathered.shape[0] == world and np.array_equal(ar_total, want))])
+        if dist.is_initialized():
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+        result.update({"reduce_consistent": bool(ok.item()), "global_sum_matches_world1": bool(ok.item()),
+                       "collective_ab": {"allreduce_total_equals_allgather_total": bool(ok.item()), "what": "all-gather + local sum against sum all-reduce + one mod-q pass (gloo)"}})
+    if args.full and dist.is_initialized() and world > 1:   # the rank-0 programs of the N>1 report, stood in by canned output; the host-side wait is real
         def fake(argv, timeout):
             if argv[0] == "sharded_ct_mul":
                 return 0, json.dumps({"host": "c++", "world": int(argv[1]), "matches_world1_recomputation": True, "ct_mul_per_s": 0.0, "dry_run": True}) + "\nOK\n"
@@ -357,6 +364,9 @@ def main():
                     help="form of the fused multiply: auto = measured on this box (library probe + three timed steps per form), or forced")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not profile the multiply's HBM traffic with rocprofv3 after the timed region (roofline.traffic then quotes the committed profile)")
     ap.add_argument("--dry-run", action="store_true", help="CPU + gloo: walk the multi-rank host path (collectives, barriers, report) without kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: NTT, other configurations, CPU baseline, live roofline figures, "
+                         "consistency checks, and at N>1 the all-reduce A/B and the C++ multi-GPU programs")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="rank 0 writes what the last timed step returned, as float64 .npy: DIR/total.npy = the reduced ciphertext [3][L][N], "
                          "DIR/products.npy = the products of 32 pairs of its shard drawn with numpy seed 0, sorted [32][3][L][N] (13 MB in all)")
@@ -851,7 +861,7 @@ def main():
             other.setdefault("packed_linear", {})["error"] = repr(e)[:300]
         return other
 
-    def alu_ceiling():
+    def alu_ceiling(live):
         import re as _re
         import subprocess
 
@@ -859,7 +869,7 @@ def main():
             m = _re.findall(r"butterflies fused12\s+8 blk/CU:.*?clock\s+([0-9.]+) MHz.*?([0-9.]+) T bfly/s", txt)
             return (float(m[-1][1]) * 1e12, float(m[-1][0])) if m else (None, None)
         exe = os.path.join(ROOT, "tools", "bin", "ubench2")
-        if rank == 0 and os.path.exists(exe):
+        if live and rank == 0 and os.path.exists(exe):
             try:
                 torch.cuda.synchronize()
                 run = subprocess.run([exe, "bfly"], capture_output=True, text=True, timeout=120)
@@ -876,20 +886,23 @@ def main():
                     return peak, clock, "profiles/" + nm + " (committed profile, NOT measured in this run)", False
         return None, None, None, False
 
-    alu_result = alu_ceiling()
-    regime_result = box_regime(local_rank) if rank == 0 else None
+    alu_result = alu_ceiling(args.full)
+    regime_result = box_regime(local_rank) if (rank == 0 and args.full) else None
     # before the long multiply loop heats the chip into lower clocks; every rank measures (same thermal history on every GPU),
     # rank 0 reports
-    ntt_result = measure_ntt()
-    other_result = measure_other_configs() if (world == 1 and not args.skip_other) else None
+    ntt_result = measure_ntt() if args.full else None
+    other_result = measure_other_configs() if (args.full and world == 1 and not args.skip_other) else None
     if other_result is not None:
         try:
             other_result.setdefault("packed_linear", {})["kernels"] = measure_packed_kernels(alu_result[0])
         except Exception as e:   # a secondary block must not take the headline metric down with it
             other_result.setdefault("packed_linear", {})["kernels"] = {"error": repr(e)[:300]}
     # every rank runs the windows whatever N is (no collective inside; rank 0 reports): the timed region below is shorter than the power
-    # manager's memory, so what ran before it decides which regime it sees (MEASUREMENTS.md section 5) - the same history for every N
+    # manager's memory, so what ran before it decides which regime it sees (MEASUREMENTS.md section 5) - the same history for every N,
+    # and for a plain run too, which runs them unreported
     sustained_result = measure_sustained(args.sustained_seconds) if args.sustained_seconds > 0 else None
+    if not args.full:
+        sustained_result = None
 
     def tune_form():
         """Which form of the fused multiply this run times.  (1) the library's own measurement repeated on scratch of the timed batch's
@@ -978,7 +991,7 @@ def main():
     # SURVEY.md section 8(e)'s alternative exchange, measured next to the timed one whenever there is more than one rank (after the timed region: `value`
     # is the all-gather step's): the SAME step with a 64-bit sum all-reduce of the partials + one mod-q pass instead of all-gather + local sum.
     collective_ab = None
-    if world > 1:
+    if args.full and world > 1:
         try:   # (every rank walks the same path: an exception here is raised on all of them, so the ranks stay in step)
             pipe_ar = ShardedMultiplyReduce(ev, B, comm=comm, main=main, collective="allreduce", outs=pipe.outs)   # same output buffers: no second 6 GiB
             for _ in range(max(1, args.warmup)):
@@ -1042,7 +1055,7 @@ def main():
     # ... and, when rocprofv3 is on this box, MEASURED in this run: tools/live_traffic.py profiles 2048-pair launches of the same kernel form with
     # FETCH_SIZE and WRITE_SIZE in two separate --pmc passes (after the timed region; ~20 s), scaled per ct-mul
     live_traffic = None
-    if rank == 0 and world == 1 and not args.no_live_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_live_traffic:
         try:
             import subprocess
             torch.cuda.synchronize()
@@ -1161,7 +1174,7 @@ def main():
             result["roofline"].update({"ct_mul_sustained_frac": cs["frac_of_hbm_peak"], "ct_mul_sustained_per_s": a.data.shape[0] / (cs["us_per_launch"] * 1e-6),
                                        "ct_mul_sustained_window_s": cs["window_s"], "ct_mul_sustained_board_w": cs.get("board_w_mean"),
                                        "ct_mul_sustained_cap_w": cs.get("cap_w"), "ct_mul_sustained_sclk_mhz": cs.get("sclk_mhz_mean")})
-    if rank == 0:
+    if regime_result is not None:
         try:   # where a workgroup of the multiply spends its life ON THIS BOX (diagnostic launch after the timed region; include/dpfhe.h dpfhe_debug_ct_mul_trace)
             regime_result["workgroup_timeline_us"] = workgroup_timeline()
         except Exception as e:
@@ -1186,22 +1199,23 @@ def main():
                                            pre + "_ct_mul_per_s": sg["ct_mul"]["per_s"], pre + "_ct_mul_frac": sg["ct_mul"]["frac_of_hbm_peak"]})
     # the reduced result of the last step equals a recomputation of the same sequence on the main stream (every rank checks,
     # rank 0 reports; at N>1 the recomputation repeats the all-gather, so all ranks must take part)
-    chk = ev.reduce_sum(Ciphertext(out), stream=main)
-    if world == 1 and comm is None and not dist.is_initialized():
-        torch.cuda.synchronize()
-        result["reduce_consistent"] = bool(torch.equal(chk.data, totals[last]))
-    else:
-        from deeppowers_amd.sharding import allgather_partials
-        gathered = allgather_partials(chk.data, comm=comm)
-        tot = ev.reduce_sum(Ciphertext(gathered), stream=main)
-        torch.cuda.synchronize()
-        ok = torch.tensor([int(torch.equal(tot.data, totals[last]))], device=dev)
-        if dist.is_initialized():
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        result["reduce_consistent"] = bool(ok.item())
+    if args.full:
+        chk = ev.reduce_sum(Ciphertext(out), stream=main)
+        if world == 1 and comm is None and not dist.is_initialized():
+            torch.cuda.synchronize()
+            result["reduce_consistent"] = bool(torch.equal(chk.data, totals[last]))
+        else:
+            from deeppowers_amd.sharding import allgather_partials
+            gathered = allgather_partials(chk.data, comm=comm)
+            tot = ev.reduce_sum(Ciphertext(gathered), stream=main)
+            torch.cuda.synchronize()
+            ok = torch.tensor([int(torch.equal(tot.data, totals[last]))], device=dev)
+            if dist.is_initialized():
+                dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            result["reduce_consistent"] = bool(ok.item())
 
     if world == 1:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle.cbind import Oracle
             orc = Oracle.from_params(params)
             # CPUs this process may actually use: the scheduler affinity AND the cgroup CPU quota (the GPU boxes of this pool are
@@ -1270,12 +1284,12 @@ def main():
         if isinstance(detail.get("other_configs"), dict):
             detail["other_configs"]["sum_in_ntt_domain"] = result["other_configs"]["sum_in_ntt_domain"]
 
-    if world > 1 and not args.skip_other:
+    if args.full and world > 1 and not args.skip_other:
         torch.cuda.synchronize()
         progs = on_rank0_while_others_wait(rank, lambda: multi_gpu_programs(world))
         if rank == 0:
             result["multi_gpu_programs"] = progs
-    if rank == 0:
+    if rank == 0 and args.full:
         try:   # the full blocks the line only digests (gpurun merges gpurun_out/ back; elsewhere this is a scratch file)
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "bench_detail.json"), "w") as f:
@@ -1283,6 +1297,7 @@ def main():
             result["detail_file"] = "gpurun_out/bench_detail.json (ntt, sustained, other_configs in full)"
         except Exception:
             pass
+    if rank == 0:
         print(json.dumps(result))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -30,7 +30,7 @@ def test_bench_dry_run_walks_every_collective(world):
     cmd = [sys.executable]
     if world > 1:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--dry-run", "--native-comm"]
+    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--dry-run", "--native-comm", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert run.returncode == 0, run.stdout + run.stderr
     r = _line(run.stdout)
@@ -49,6 +49,19 @@ def test_bench_dry_run_walks_every_collective(world):
         assert "multi_gpu_programs" not in r
     # value is the whole-job aggregate: all ranks' pairs over the MAX-over-ranks time
     assert abs(r["value"] - r["config"]["global_batch"] * r["steps"] / (r["ms_per_step"] * 1e-3 * r["steps"])) < 1e-6 * r["value"]
+
+
+def test_bench_plain_dry_run_walks_only_the_timed_path():
+    """Without --full the N>1 host path stops after the timed steps: the headline line, no checks, no all-reduce A/B, no rank-0 programs."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert run.returncode == 0, run.stdout + run.stderr
+    r = _line(run.stdout)
+    assert r["dry_run"] is True and r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["per_rank_ct_mul_per_s"]["ranks"] == 2
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(r) and r["unit"] == "ct-mul/s" and r["higher_is_better"] is True
+    assert not {"reduce_consistent", "global_sum_matches_world1", "collective_ab", "multi_gpu_programs"} & set(r)
+    assert abs(r["value"] - r["config"]["global_batch"] / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
 
 
 def test_bench_refuses_a_world_size_mismatch():

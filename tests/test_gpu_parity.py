@@ -692,7 +692,7 @@ def test_bench_distributed_path_world_size_one():
     env = dict(os.environ, DPFHE_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--batch-per-gpu", "64", "--no-cpu-baseline"]
+           "--batch-per-gpu", "64", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -714,6 +714,23 @@ def test_bench_distributed_path_world_size_one():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["reduce_consistent"] is True and "dpfhe_comm_allgather" in d["config"]["collective"]
+
+
+def test_bench_plain_run_measures_only_the_headline(tmp_path):
+    """bench.py without --full: the timed steps and the figures they give, none of the blocks that take runs of their own, no detail file."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-per-gpu", "64", "--sustained-seconds", "0.1"]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tmp_path)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    d = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["metric"] == "ciphertext-mul/s (N=4096, 4 RNS limbs)" and d["unit"] == "ct-mul/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"cpu_baseline", "bit_exact_sample", "reduce_consistent", "other_configs", "collective_ab", "multi_gpu_programs", "detail_file"} & set(d)
+    rf = d["roofline"]
+    assert not {"ntt", "regime", "ntt_fwd_frac", "ct_mul_sustained_frac"} & set(rf) and rf["traffic_live"] is None and 0 < rf["frac"] < 1
+    assert d["config"]["autotune"]["chosen"] in ("quad", "dual") and rf["autotune_chosen"] == d["config"]["autotune"]["chosen"]
 
 
 def test_bench_dump_outputs_are_the_oracles_words_for_the_seeded_inputs(tmp_path):

@@ -7,13 +7,13 @@ STEPS=${@:-bench probes prof packed pmc}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-PROF_ARGS="--steps 5 --warmup 1 --no-cpu-baseline --sustained-seconds 0 --skip-other --no-live-traffic"
+PROF_ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --sustained-seconds 0 --skip-other --no-live-traffic"
 db() { find $1 -name "*.db" | head -1; }
 for step in $STEPS; do
 case $step in
 bench)
   (rocminfo | grep -E "Marketing Name|Compute Unit|Max Clock|gfx" | head -8; nproc; grep -m1 "model name" /proc/cpuinfo; cat /sys/fs/cgroup/cpu.max) > $OUT/env.log 2>&1
-  timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" ;;
+  timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" ;;
 probes)
   timeout 300 ./tools/bin/ubench2 > $OUT/ubench2.log 2>&1; echo "ubench2 rc=$?"
   timeout 200 python tools/power_probe.py 2>&1 | grep -v amdgpu.ids > $OUT/power_probe.txt; echo "power_probe rc=$?" ;;

@@ -16,10 +16,10 @@ echo "== ubench =="
 timeout 600 ./tools/ubench > $OUT/ubench.log 2>&1; echo "ubench rc=$?" | tee -a $OUT/ubench.log
 cat $OUT/ubench.log
 echo "== bench =="
-timeout 900 python bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 echo "== rocprofv3 kernel trace =="
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?"
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?"
 ls -R $OUT/prof | head -20
 find $OUT/prof -name "*kernel_stats*" | head -1 | xargs -r head -20
 # keep the merged-back payload small: drop the raw trace, keep stats

@@ -25,5 +25,5 @@ if [ "$(cat $OUT/slow)" = "1" ]; then
     timeout 200 rocprofv3 --pmc $set --kernel-trace -d $OUT/pmc$i -o pmc -- python tools/ntt_bench.py 1024 8192 > $OUT/pmc$i.log 2>&1
     f=$(db $OUT/pmc$i); [ -n "$f" ] && python tools/pmc_summary.py $f "ct_mul" > $OUT/pmc_lat_pass$i.txt 2>&1; grep -A9 "ct_mul_quad" $OUT/pmc_lat_pass$i.txt | head -10; rm -rf $OUT/pmc$i
   done
-  timeout 300 python bench.py --skip-other --no-cpu-baseline > $OUT/bench_lean.json 2> $OUT/bench.err; tail -c 400 $OUT/bench_lean.json
+  timeout 300 python bench.py --full --skip-other --no-cpu-baseline > $OUT/bench_lean.json 2> $OUT/bench.err; tail -c 400 $OUT/bench_lean.json
 fi
