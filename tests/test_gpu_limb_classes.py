@@ -7,6 +7,7 @@ schoolbook, a different algorithm from all four)."""
 import numpy as np
 import pytest
 
+from class_edges import expected_class, worst_case   # (the one statement of the class rule and of the stripes, shared with test_gpu_class_edges.py)
 from deeppowers_amd.params import FheParams, PRIMES_60, ntt_primes
 from oracle import pyoracle as po
 from oracle.cbind import Oracle
@@ -30,19 +31,6 @@ def primes_of(log2n, widths):
     return FheParams(log2n, tuple(qs), tuple(ps))
 
 
-def expected_class(q):
-    if q < (1 << 60) and (1 << 60) - q < (1 << 24):
-        return "fold"
-    if q < (1 << 47):
-        return "f64"
-    k = q.bit_length()
-    if 48 <= k <= 59 and (((1 << k) - q) << (60 - k)) < (1 << 24):
-        return "fold_scaled"
-    if q < (1 << 50):
-        return "f64_wide"
-    return "shoup"
-
-
 def shoup_class_primes(log2n, bits, count):
     """`count` primes = 1 mod 2N of `bits` (51 ... 59) bits that NO fast class takes: too wide for the doubles, too far below 2^bits for the scaled fold"""
     from deeppowers_amd.params import is_prime, min_primitive_2n_root
@@ -53,15 +41,6 @@ def shoup_class_primes(log2n, bits, count):
             qs.append(q)
         q -= 2 * n
     return qs, [min_primitive_2n_root(n, v) for v in qs]
-
-
-def worst_case(x, qcol, n):
-    """stripes of extreme residues in the first item: q - 1 everywhere in one stretch, alternating q - 1 / 0 in another, the half point in a third"""
-    x[0, ..., : n // 8] = qcol - np.uint64(1)
-    x[0, ..., n // 8: n // 4: 2] = qcol - np.uint64(1)
-    x[0, ..., n // 8 + 1: n // 4: 2] = 0
-    x[0, ..., n // 4: n // 4 + n // 8] = qcol // np.uint64(2)
-    return x
 
 
 CASES = [
