@@ -67,11 +67,13 @@ struct DeviceGuard {
     DeviceGuard _guard((ctx)->device);                                                                         \
     if (_guard.err != hipSuccess) return fail(DPFHE_DEVICE_ERROR, what, hipGetErrorString(_guard.err))
 
-// half-open word ranges [a, a + na) and [b, b + nb) intersect
-static inline bool overlaps(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) {
+// half-open byte ranges [a, a + na) and [b, b + nb) intersect
+static inline bool overlaps_bytes(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb * 8 && b0 < a0 + na * 8;
+    return a0 < b0 + nb && b0 < a0 + na;
 }
+// the same for word ranges
+static inline bool overlaps(const uint64_t* a, size_t na, const uint64_t* b, size_t nb) { return overlaps_bytes(a, na * 8, b, nb * 8); }
 
 static inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 static const size_t kMaxGrid = 0x7fffffff;
@@ -83,9 +85,10 @@ struct dpfhe_ctx {
     int n_cu = 256;          // compute units of the device (launch-size caps of the streaming kernels)
     std::vector<uint64_t> moduli;   // host copy (constants of dpfhe_base_extend / dpfhe_scale_round)
     uint64_t p_special = 0;  // the LAST modulus (the special prime of hybrid key switching when this is an extended context)
-    void* d_blob = nullptr;  // one allocation: LimbConst[L] | fwd | inv | last | RescaleConst[L]  (both arithmetic layouts share it)
+    void* d_blob = nullptr;  // one allocation: LimbConst[L] | fwd | inv | last | RescaleConst[L]  (both arithmetic layouts share it: ctx_layout)
+    const LimbConst* lc = nullptr;   // the limb constants at the head of d_blob: what the one-pass kernels read, whichever table set below is filled
     const RescaleConst* d_rescale = nullptr;
-    DevTables<ShoupArith> shoup{};
+    DevTables<ShoupArith> shoup{};   // the table set of the context-wide arithmetic (with_ctx_arith): the one that matches `fold` is filled
     DevTables<FoldArith> foldt{};
     // Round 6 - per-limb arithmetic classes.  A context whose limbs are not ALL of the pinned 2^60 - d shape used to run every limb on the
     // generic (Harvey / Shoup) kernels.  Now each limb gets the fastest policy its prime admits (tables.h limb_class) for the batched transforms and
@@ -308,6 +311,66 @@ static DevTables<Arith> mixed_view(const unsigned char* b, const MixedLayout& m,
     return tb;
 }
 
+// Tables of the context-wide arithmetic (FoldArith or ShoupArith, every limb): ONE blob of 256-byte aligned sections.  One twiddle table pair per kernel
+// geometry in use: slot 0 = the fused kernels' LOGE 4 layout, slot 1 = the batched NTT kernels' layout when that differs.  Split transforms (N > 16384)
+// store, per limb, n_sub tables of N2 points (sub-trees of the full table) plus the top-stage twiddles.  FoldArith at N = 8192 / 16384 adds the "halves" /
+// "quarters" tables next to the one-piece ones (ntt_halves.h / ntt_quarters.h; the fused kernels keep the one-piece layout); elsewhere their offsets are
+// the end of the blob and their pointers stay null.
+struct CtxLayout {
+    int log_n1, log_n2, loge_ntt;
+    size_t n_sub, n2, tw_sz;
+    bool split, two_geo, halves, quarters;
+    size_t o_lc, o_fwd4, o_inv4, o_fwd, o_inv, o_last, o_top_fwd, o_top_inv, o_top_last, o_resc, o_hfwd, o_hinv, o_htop_fwd, o_htop_last,
+           o_qfwd, o_qinv, o_qtop_fwd, o_qtop_inv, o_qtop_last, total;
+};
+static CtxLayout ctx_layout(int log2n, size_t L, bool fold) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    CtxLayout m;
+    m.tw_sz = fold ? sizeof(TwFold) : sizeof(TwShoup);
+    m.log_n1 = split_log_n1(log2n); m.log_n2 = log2n - m.log_n1;
+    m.n_sub = (size_t)1 << m.log_n1; m.n2 = (size_t)1 << m.log_n2;
+    m.loge_ntt = ntt_loge(m.log_n2);
+    m.split = m.log_n1 > 0; m.two_geo = !m.split && m.loge_ntt != kFusedLoge;
+    m.halves = log2n == 13 && fold;     // the halves tables (launch.h): large batched transforms at N = 8192
+    m.quarters = log2n == 14 && fold;   // four sub-tree tables per limb + the column stages' twiddles
+    const size_t tw_sz = m.tw_sz, n_sub = m.n_sub, tab = L * ((size_t)1 << log2n) * tw_sz;
+    m.o_lc = 0; m.o_fwd4 = up(m.o_lc + L * sizeof(LimbConst)); m.o_inv4 = up(m.o_fwd4 + tab);
+    m.o_fwd = m.two_geo ? up(m.o_inv4 + tab) : m.o_fwd4; m.o_inv = m.two_geo ? up(m.o_fwd + tab) : m.o_inv4;
+    m.o_last = up(m.o_inv + tab); m.o_top_fwd = up(m.o_last + L * n_sub * 2 * tw_sz); m.o_top_inv = up(m.o_top_fwd + L * n_sub * tw_sz);
+    m.o_top_last = up(m.o_top_inv + L * n_sub * tw_sz); m.o_resc = up(m.o_top_last + L * 2 * tw_sz);
+    const bool h = m.halves, qu = m.quarters;
+    m.o_hfwd = up(m.o_resc + L * sizeof(RescaleConst)); m.o_hinv = h ? up(m.o_hfwd + tab) : m.o_hfwd; m.o_htop_fwd = h ? up(m.o_hinv + tab) : m.o_hfwd;
+    m.o_htop_last = h ? up(m.o_htop_fwd + L * tw_sz) : m.o_hfwd;
+    const size_t o_q0 = h ? up(m.o_htop_last + L * 2 * tw_sz) : m.o_hfwd;
+    m.o_qfwd = o_q0; m.o_qinv = qu ? up(m.o_qfwd + tab) : o_q0; m.o_qtop_fwd = qu ? up(m.o_qinv + tab) : o_q0;
+    m.o_qtop_inv = qu ? up(m.o_qtop_fwd + L * sizeof(QuartersTop)) : o_q0; m.o_qtop_last = qu ? up(m.o_qtop_inv + L * 2 * tw_sz) : o_q0;
+    m.total = qu ? up(m.o_qtop_last + L * 2 * tw_sz) : o_q0;
+    return m;
+}
+template <class Arith>
+static DevTables<Arith> ctx_view(const unsigned char* d, const CtxLayout& m, size_t L) {
+    typedef typename Arith::Tw Tw;
+    DevTables<Arith> tb{};
+    tb.lc = reinterpret_cast<const LimbConst*>(d + m.o_lc);
+    tb.fwd = reinterpret_cast<const Tw*>(d + m.o_fwd); tb.inv = reinterpret_cast<const Tw*>(d + m.o_inv);
+    tb.fwd4 = reinterpret_cast<const Tw*>(d + m.o_fwd4); tb.inv4 = reinterpret_cast<const Tw*>(d + m.o_inv4);
+    tb.last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_last);
+    tb.top_fwd = reinterpret_cast<const Tw*>(d + m.o_top_fwd); tb.top_inv = reinterpret_cast<const Tw*>(d + m.o_top_inv);
+    tb.top_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_top_last);
+    tb.n_sub = (int)m.n_sub;
+    tb.n_limbs = (int)L;
+    if (m.quarters) {
+        tb.qfwd = reinterpret_cast<const Tw*>(d + m.o_qfwd); tb.qinv = reinterpret_cast<const Tw*>(d + m.o_qinv);
+        tb.qtop_fwd = reinterpret_cast<const QuartersTop*>(d + m.o_qtop_fwd); tb.qtop_inv = reinterpret_cast<const Tw*>(d + m.o_qtop_inv);
+        tb.qtop_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_qtop_last);
+    }
+    if (m.halves) {
+        tb.hfwd = reinterpret_cast<const Tw*>(d + m.o_hfwd); tb.hinv = reinterpret_cast<const Tw*>(d + m.o_hinv);
+        tb.htop_fwd = reinterpret_cast<const Tw*>(d + m.o_htop_fwd); tb.htop_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_htop_last);
+    }
+    return tb;
+}
+
 extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_limbs, const uint64_t* moduli,
                                 const uint64_t* psi, int device_id) {
     if (!out || !moduli || !psi) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_create", "null argument");
@@ -337,30 +400,9 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
     c->moduli.assign(moduli, moduli + L);
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->n_cu = cus; }
 
-    // blob layout (all 256-byte aligned sections).  One twiddle table pair per kernel geometry in use: slot 0 = the
-    // fused kernels' LOGE 4 layout, slot 1 = the batched NTT kernels' layout when that differs.  Split transforms
-    // (N > 16384) store, per limb, n_sub tables of N2 points (sub-trees of the full table) plus the top-stage twiddles.
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t tw_sz = fold ? sizeof(TwFold) : sizeof(TwShoup);
-    const int log_n1 = split_log_n1((int)log2_n), log_n2 = (int)log2_n - log_n1;
-    const size_t n_sub = (size_t)1 << log_n1, n2 = (size_t)1 << log_n2;
-    const int loge_ntt = ntt_loge(log_n2);
-    const bool split = log_n1 > 0, two_geo = !split && loge_ntt != kFusedLoge;
-    const size_t tab = L * n * tw_sz;
-    const size_t o_lc = 0, o_fwd4 = up(o_lc + L * sizeof(LimbConst)), o_inv4 = up(o_fwd4 + tab),
-                 o_fwd = two_geo ? up(o_inv4 + tab) : o_fwd4, o_inv = two_geo ? up(o_fwd + tab) : o_inv4,
-                 o_last = up(o_inv + tab), o_top_fwd = up(o_last + L * n_sub * 2 * tw_sz), o_top_inv = up(o_top_fwd + L * n_sub * tw_sz),
-                 o_top_last = up(o_top_inv + L * n_sub * tw_sz), o_resc = up(o_top_last + L * 2 * tw_sz);
-    // N = 8192: the "halves" tables next to the one-piece ones (ntt_halves.h; the fused kernels keep the one-piece layout)
-    const bool halves = log2_n == 13 && fold;   // the halves tables (launch.h): large batched transforms at N = 8192
-    const size_t o_hfwd = up(o_resc + L * sizeof(RescaleConst)), o_hinv = halves ? up(o_hfwd + tab) : o_hfwd, o_htop_fwd = halves ? up(o_hinv + tab) : o_hfwd,
-                 o_htop_last = halves ? up(o_htop_fwd + L * tw_sz) : o_hfwd, o_q0 = halves ? up(o_htop_last + L * 2 * tw_sz) : o_hfwd;
-    // N = 16384, FoldArith: the "quarters" tables next to the one-piece ones (ntt_quarters.h: four sub-tree tables per limb + the column stages' twiddles)
-    const bool quarters = log2_n == 14 && fold;
-    const size_t o_qfwd = o_q0, o_qinv = quarters ? up(o_qfwd + tab) : o_q0, o_qtop_fwd = quarters ? up(o_qinv + tab) : o_q0,
-                 o_qtop_inv = quarters ? up(o_qtop_fwd + L * sizeof(QuartersTop)) : o_q0, o_qtop_last = quarters ? up(o_qtop_inv + L * 2 * tw_sz) : o_q0,
-                 total = quarters ? up(o_qtop_last + L * 2 * tw_sz) : o_q0;
-    std::vector<unsigned char> blob(total, 0);
+    const CtxLayout lay = ctx_layout((int)log2_n, L, fold);
+    const size_t tw_sz = lay.tw_sz, n_sub = lay.n_sub, n2 = lay.n2;
+    std::vector<unsigned char> blob(lay.total, 0);
     auto fill = [&](auto tw_tag) {
         typedef decltype(tw_tag) Tw;
         for (size_t l = 0; l < L; ++l) {
@@ -371,112 +413,79 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
                 permute_window0(t, logn_tab, loge, geo_perm_stages(logn_tab, loge));
                 std::memcpy(&blob[off], t.data(), t.size() * sizeof(Tw));
             };
-            InvLast<Tw>* lasts = reinterpret_cast<InvLast<Tw>*>(&blob[o_last]);
-            if (!split) {
-                for (int geo = 0; geo < (two_geo ? 2 : 1); ++geo) {
-                    const int loge = geo ? loge_ntt : kFusedLoge;
-                    pack(ht[l].rp, (int)log2_n, loge, (geo ? o_fwd : o_fwd4) + l * n * tw_sz);
-                    pack(ht[l].irp, (int)log2_n, loge, (geo ? o_inv : o_inv4) + l * n * tw_sz);
+            InvLast<Tw>* lasts = reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_last]);
+            if (!lay.split) {
+                for (int geo = 0; geo < (lay.two_geo ? 2 : 1); ++geo) {
+                    const int loge = geo ? lay.loge_ntt : kFusedLoge;
+                    pack(ht[l].rp, (int)log2_n, loge, (geo ? lay.o_fwd : lay.o_fwd4) + l * n * tw_sz);
+                    pack(ht[l].irp, (int)log2_n, loge, (geo ? lay.o_inv : lay.o_inv4) + l * n * tw_sz);
                 }
                 lasts[l] = InvLast<Tw>{h_make_tw<Tw>(ht[l].w_last, q), h_make_tw<Tw>(ht[l].lc.ninv, q)};
                 if constexpr (std::is_same<Tw, TwFold>::value) {
-                    if (quarters) {
+                    if (lay.quarters) {
                         for (size_t r = 0; r < 4; ++r) {
-                            pack(subtree_table(ht[l].rp, 14, 2, r), 12, 4, o_qfwd + (l * 4 + r) * (n / 4) * tw_sz);
-                            pack(subtree_table(ht[l].irp, 14, 2, r), 12, 4, o_qinv + (l * 4 + r) * (n / 4) * tw_sz);
+                            pack(subtree_table(ht[l].rp, 14, 2, r), 12, 4, lay.o_qfwd + (l * 4 + r) * (n / 4) * tw_sz);
+                            pack(subtree_table(ht[l].irp, 14, 2, r), 12, 4, lay.o_qinv + (l * 4 + r) * (n / 4) * tw_sz);
                         }
-                        reinterpret_cast<QuartersTop*>(&blob[o_qtop_fwd])[l] = QuartersTop{h_tw_fold(ht[l].rp[1], q), h_tw_fold(ht[l].rp[2], q), h_tw_fold(ht[l].rp[3], q)};
-                        reinterpret_cast<TwFold*>(&blob[o_qtop_inv])[2 * l] = h_tw_fold(ht[l].irp[2], q);
-                        reinterpret_cast<TwFold*>(&blob[o_qtop_inv])[2 * l + 1] = h_tw_fold(ht[l].irp[3], q);
-                        reinterpret_cast<InvLast<TwFold>*>(&blob[o_qtop_last])[l] = InvLast<TwFold>{h_tw_fold(ht[l].w_last, q), h_tw_fold(ht[l].lc.ninv, q)};
+                        reinterpret_cast<QuartersTop*>(&blob[lay.o_qtop_fwd])[l] = QuartersTop{h_tw_fold(ht[l].rp[1], q), h_tw_fold(ht[l].rp[2], q), h_tw_fold(ht[l].rp[3], q)};
+                        reinterpret_cast<TwFold*>(&blob[lay.o_qtop_inv])[2 * l] = h_tw_fold(ht[l].irp[2], q);
+                        reinterpret_cast<TwFold*>(&blob[lay.o_qtop_inv])[2 * l + 1] = h_tw_fold(ht[l].irp[3], q);
+                        reinterpret_cast<InvLast<TwFold>*>(&blob[lay.o_qtop_last])[l] = InvLast<TwFold>{h_tw_fold(ht[l].w_last, q), h_tw_fold(ht[l].lc.ninv, q)};
                     }
                 }
-                if (halves) {
+                if (lay.halves) {
                     for (size_t r = 0; r < 2; ++r) {
-                        pack(subtree_table(ht[l].rp, 13, 1, r), 12, 4, o_hfwd + (l * 2 + r) * (n / 2) * tw_sz);
-                        pack(subtree_table(ht[l].irp, 13, 1, r), 12, 4, o_hinv + (l * 2 + r) * (n / 2) * tw_sz);
+                        pack(subtree_table(ht[l].rp, 13, 1, r), 12, 4, lay.o_hfwd + (l * 2 + r) * (n / 2) * tw_sz);
+                        pack(subtree_table(ht[l].irp, 13, 1, r), 12, 4, lay.o_hinv + (l * 2 + r) * (n / 2) * tw_sz);
                     }
-                    reinterpret_cast<Tw*>(&blob[o_htop_fwd])[l] = h_make_tw<Tw>(ht[l].rp[1], q);
-                    reinterpret_cast<InvLast<Tw>*>(&blob[o_htop_last])[l] = lasts[l];   // the column stage IS the one-piece transform's last stage
+                    reinterpret_cast<Tw*>(&blob[lay.o_htop_fwd])[l] = h_make_tw<Tw>(ht[l].rp[1], q);
+                    reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_htop_last])[l] = lasts[l];   // the column stage IS the one-piece transform's last stage
                 }
             } else {
                 for (size_t r = 0; r < n_sub; ++r) {
-                    const std::vector<u64> f = subtree_table(ht[l].rp, (int)log2_n, log_n1, r), v = subtree_table(ht[l].irp, (int)log2_n, log_n1, r);
-                    pack(f, log_n2, loge_ntt, o_fwd + (l * n_sub + r) * n2 * tw_sz);
-                    pack(v, log_n2, loge_ntt, o_inv + (l * n_sub + r) * n2 * tw_sz);
+                    const std::vector<u64> f = subtree_table(ht[l].rp, (int)log2_n, lay.log_n1, r), v = subtree_table(ht[l].irp, (int)log2_n, lay.log_n1, r);
+                    pack(f, lay.log_n2, lay.loge_ntt, lay.o_fwd + (l * n_sub + r) * n2 * tw_sz);
+                    pack(v, lay.log_n2, lay.loge_ntt, lay.o_inv + (l * n_sub + r) * n2 * tw_sz);
                     // generic primes: no N^-1 inside a block.  FoldArith: the block's last stage divides its sums by N2 exactly (FoldArith::mul_ninv),
                     // so its differences carry N2^-1 in their twiddle; the column stage then multiplies by N1^-1 (top_last below)
                     const u64 n2inv = std::is_same<Tw, TwFold>::value ? h_powmod((u64)n2 % q, q - 2, q) : 1;
                     lasts[l * n_sub + r] = InvLast<Tw>{h_make_tw<Tw>(h_mulmod(v[1], n2inv, q), q), h_make_tw<Tw>(1, q)};
                 }
-                Tw* tf = reinterpret_cast<Tw*>(&blob[o_top_fwd]) + l * n_sub;
-                Tw* tv = reinterpret_cast<Tw*>(&blob[o_top_inv]) + l * n_sub;
+                Tw* tf = reinterpret_cast<Tw*>(&blob[lay.o_top_fwd]) + l * n_sub;
+                Tw* tv = reinterpret_cast<Tw*>(&blob[lay.o_top_inv]) + l * n_sub;
                 for (size_t i = 1; i < n_sub; ++i) { tf[i] = h_make_tw<Tw>(ht[l].rp[i], q); tv[i] = h_make_tw<Tw>(ht[l].irp[i], q); }
                 // FoldArith sub-transforms divide by their own length N2 in their last stage (ntt_core.h: FoldArith::mul_ninv, exact division), so the
                 // column stage multiplies by N1^-1 = N^-1 N2 only; generic-prime sub-transforms multiply by 1 there and the column stage by N^-1
                 const u64 up = std::is_same<Tw, TwFold>::value ? (u64)n2 % q : 1;
-                reinterpret_cast<InvLast<Tw>*>(&blob[o_top_last])[l] = InvLast<Tw>{h_make_tw<Tw>(h_mulmod(ht[l].w_last, up, q), q), h_make_tw<Tw>(h_mulmod(ht[l].lc.ninv, up, q), q)};
+                reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_top_last])[l] = InvLast<Tw>{h_make_tw<Tw>(h_mulmod(ht[l].w_last, up, q), q), h_make_tw<Tw>(h_mulmod(ht[l].lc.ninv, up, q), q)};
             }
         }
     };
-    for (size_t l = 0; l < L; ++l) std::memcpy(&blob[o_lc + l * sizeof(LimbConst)], &ht[l].lc, sizeof(LimbConst));
+    for (size_t l = 0; l < L; ++l) std::memcpy(&blob[lay.o_lc + l * sizeof(LimbConst)], &ht[l].lc, sizeof(LimbConst));
     if (fold) fill(TwFold{}); else fill(TwShoup{});
     {   // rescale constants relative to the LAST prime (used only when L >= 2)
         const u64 ql = moduli[L - 1], hh = ql / 2;
-        RescaleConst* r = reinterpret_cast<RescaleConst*>(&blob[o_resc]);
+        RescaleConst* r = reinterpret_cast<RescaleConst*>(&blob[lay.o_resc]);
         for (size_t l = 0; l + 1 < L; ++l) {
             const u64 q = moduli[l];
             r[l].h_mod = hh % q; r[l].inv = h_powmod(ql % q, q - 2, q); r[l].q_last = ql; r[l].h = hh;
         }
     }
-    hipError_t e = hipMalloc(&c->d_blob, total);
-    if (e == hipSuccess) e = hipMemcpy(c->d_blob, blob.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (c->d_blob) (void)hipFree(c->d_blob);
-        delete c;
+    // both table uploads; a failed one frees what exists, restores the caller's device and reports `stage`
+    auto upload = [&](void*& dst, const std::vector<unsigned char>& host, const char* stage) -> int {
+        hipError_t e = hipMalloc(&dst, host.size());
+        if (e == hipSuccess) e = hipMemcpy(dst, host.data(), host.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) return DPFHE_SUCCESS;
+        (void)dpfhe_ctx_destroy(c);
         (void)hipSetDevice(prev);
-        return fail(e == hipErrorOutOfMemory ? DPFHE_OUT_OF_MEMORY : DPFHE_DEVICE_ERROR, "dpfhe_ctx_create: table upload", hipGetErrorString(e));
-    }
-    unsigned char* d = static_cast<unsigned char*>(c->d_blob);
-    c->d_rescale = reinterpret_cast<const RescaleConst*>(d + o_resc);
-    if (fold) {
-        c->foldt.lc = reinterpret_cast<const LimbConst*>(d + o_lc);
-        c->foldt.fwd = reinterpret_cast<const TwFold*>(d + o_fwd);
-        c->foldt.inv = reinterpret_cast<const TwFold*>(d + o_inv);
-        c->foldt.fwd4 = reinterpret_cast<const TwFold*>(d + o_fwd4);
-        c->foldt.inv4 = reinterpret_cast<const TwFold*>(d + o_inv4);
-        c->foldt.last = reinterpret_cast<const InvLast<TwFold>*>(d + o_last);
-        c->foldt.top_fwd = reinterpret_cast<const TwFold*>(d + o_top_fwd);
-        c->foldt.top_inv = reinterpret_cast<const TwFold*>(d + o_top_inv);
-        c->foldt.top_last = reinterpret_cast<const InvLast<TwFold>*>(d + o_top_last);
-        c->foldt.n_sub = (int)n_sub;
-        c->foldt.n_limbs = (int)n_limbs;
-        if (quarters) {
-            c->foldt.qfwd = reinterpret_cast<const TwFold*>(d + o_qfwd); c->foldt.qinv = reinterpret_cast<const TwFold*>(d + o_qinv);
-            c->foldt.qtop_fwd = reinterpret_cast<const QuartersTop*>(d + o_qtop_fwd); c->foldt.qtop_inv = reinterpret_cast<const TwFold*>(d + o_qtop_inv);
-            c->foldt.qtop_last = reinterpret_cast<const InvLast<TwFold>*>(d + o_qtop_last);
-        }
-        if (halves) {
-            c->foldt.hfwd = reinterpret_cast<const TwFold*>(d + o_hfwd); c->foldt.hinv = reinterpret_cast<const TwFold*>(d + o_hinv);
-            c->foldt.htop_fwd = reinterpret_cast<const TwFold*>(d + o_htop_fwd); c->foldt.htop_last = reinterpret_cast<const InvLast<TwFold>*>(d + o_htop_last);
-        }
-    } else {
-        c->shoup.lc = reinterpret_cast<const LimbConst*>(d + o_lc);
-        c->shoup.fwd = reinterpret_cast<const TwShoup*>(d + o_fwd);
-        c->shoup.inv = reinterpret_cast<const TwShoup*>(d + o_inv);
-        c->shoup.fwd4 = reinterpret_cast<const TwShoup*>(d + o_fwd4);
-        c->shoup.inv4 = reinterpret_cast<const TwShoup*>(d + o_inv4);
-        c->shoup.last = reinterpret_cast<const InvLast<TwShoup>*>(d + o_last);
-        c->shoup.top_fwd = reinterpret_cast<const TwShoup*>(d + o_top_fwd);
-        c->shoup.top_inv = reinterpret_cast<const TwShoup*>(d + o_top_inv);
-        c->shoup.top_last = reinterpret_cast<const InvLast<TwShoup>*>(d + o_top_last);
-        c->shoup.n_sub = (int)n_sub;
-        c->shoup.n_limbs = (int)n_limbs;
-        if (halves) {
-            c->shoup.hfwd = reinterpret_cast<const TwShoup*>(d + o_hfwd); c->shoup.hinv = reinterpret_cast<const TwShoup*>(d + o_hinv);
-            c->shoup.htop_fwd = reinterpret_cast<const TwShoup*>(d + o_htop_fwd); c->shoup.htop_last = reinterpret_cast<const InvLast<TwShoup>*>(d + o_htop_last);
-        }
-    }
+        return fail(e == hipErrorOutOfMemory ? DPFHE_OUT_OF_MEMORY : DPFHE_DEVICE_ERROR, stage, hipGetErrorString(e));
+    };
+    if (int rc = upload(c->d_blob, blob, "dpfhe_ctx_create: table upload")) return rc;
+    const unsigned char* d = static_cast<const unsigned char*>(c->d_blob);
+    c->lc = reinterpret_cast<const LimbConst*>(d + lay.o_lc);
+    c->d_rescale = reinterpret_cast<const RescaleConst*>(d + lay.o_resc);
+    if (fold) c->foldt = ctx_view<FoldArith>(d, lay, L);
+    else c->shoup = ctx_view<ShoupArith>(d, lay, L);
     // per-limb arithmetic classes of a non-uniform context (see dpfhe_ctx::classes)
     if (!fold && L <= 16 && log2_n >= 8 && log2_n <= 14) {
         bool any_fast = false;
@@ -492,15 +501,7 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
                 else if (k == kClassFoldScaled) fill_mixed_limb<TwFold>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_tw_fold_scaled(w, q, fold_scaled_shift(q)); });
                 else fill_mixed_limb<TwShoup>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_make_tw<TwShoup>(w, q); });
             }
-            hipError_t ce = hipMalloc(&c->class_blob, m.total);
-            if (ce == hipSuccess) ce = hipMemcpy(c->class_blob, mb.data(), m.total, hipMemcpyHostToDevice);
-            if (ce != hipSuccess) {
-                if (c->class_blob) (void)hipFree(c->class_blob);
-                (void)hipFree(c->d_blob);
-                delete c;
-                (void)hipSetDevice(prev);
-                return fail(ce == hipErrorOutOfMemory ? DPFHE_OUT_OF_MEMORY : DPFHE_DEVICE_ERROR, "dpfhe_ctx_create: class table upload", hipGetErrorString(ce));
-            }
+            if (int rc = upload(c->class_blob, mb, "dpfhe_ctx_create: class table upload")) return rc;
             const unsigned char* b = static_cast<const unsigned char*>(c->class_blob);
             c->cls_fold = mixed_view<FoldArith>(b, m, L);
             c->cls_f64 = mixed_view<F64Arith>(b, m, L);
@@ -560,12 +561,30 @@ static int check_launch(const char* what) {
     return DPFHE_SUCCESS;
 }
 
+// hybrid key switching: the last limb is the special prime P, the others are the data limbs
+static int check_extended(const dpfhe_ctx* c, const char* what) {
+    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    return DPFHE_SUCCESS;
+}
+static int check_galois_elts(const dpfhe_ctx* c, const uint32_t* elts, size_t n, const char* what) {
+    const unsigned two_n = 2u << c->log2n;
+    for (size_t i = 0; i < n; ++i)
+        if (!(elts[i] & 1u) || elts[i] >= two_n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois elements must be odd and < 2N");
+    return DPFHE_SUCCESS;
+}
+
 template <class Arith>
 static const DevTables<Arith>& tables_of(const dpfhe_ctx* c);
 template <>
 const DevTables<ShoupArith>& tables_of<ShoupArith>(const dpfhe_ctx* c) { return c->shoup; }
 template <>
 const DevTables<FoldArith>& tables_of<FoldArith>(const dpfhe_ctx* c) { return c->foldt; }
+
+// The arithmetic of the one-pass (streaming) kernels and of the other context-wide launches: FoldArith when every limb is a pinned 2^60 - d prime, ShoupArith
+// otherwise; fn(FoldArith{} or ShoupArith{}) launches.  It deliberately ignores the per-limb classes (running these kernels per class is DESIGN.md
+// section 8, item 2), and it is not with_policy below, which picks the key-switching kernels' tables per class.
+template <class Fn>
+static auto with_ctx_arith(const dpfhe_ctx* c, Fn fn) { return c->fold ? fn(FoldArith{}) : fn(ShoupArith{}); }
 
 // the widest grid a batched transform of `npolys` residue polynomials launches fits one launch
 static bool ntt_grid_fits(const dpfhe_ctx* c, size_t npolys) {
@@ -646,12 +665,11 @@ static int ntt_launch_items(dpfhe_ctx* c, bool inverse, uint64_t* out, const uin
         }
         if (rc == 1)                                                                   // (one class, or a geometry without the merged kernel)
             rc = for_each_class(c, Lu, [&](const auto& tb) { return launch_ntt((int)c->log2n, inverse, out, in, items * (size_t)tb.n_active, tb, s); });
-    } else if (c->fold) {
-        DevTables<FoldArith> td = c->foldt; td.n_limbs = (int)Lu;
-        rc = launch_ntt<FoldArith>((int)c->log2n, inverse, out, in, items * Lu, td, s);
     } else {
-        DevTables<ShoupArith> td = c->shoup; td.n_limbs = (int)Lu;
-        rc = launch_ntt<ShoupArith>((int)c->log2n, inverse, out, in, items * Lu, td, s);
+        rc = with_ctx_arith(c, [&](auto arith) {
+            DevTables<decltype(arith)> td = tables_of<decltype(arith)>(c); td.n_limbs = (int)Lu;
+            return launch_ntt((int)c->log2n, inverse, out, in, items * Lu, td, s);
+        });
     }
     if (rc) return fail(DPFHE_INVALID_STATE, "ntt", "no kernel geometry for this log2_n");
     return check_launch("ntt kernel launch");
@@ -676,15 +694,16 @@ extern "C" int dpfhe_ntt_fwd_oop(dpfhe_ctx* c, uint64_t* o, const uint64_t* i, s
 extern "C" int dpfhe_ntt_inv_oop(dpfhe_ctx* c, uint64_t* o, const uint64_t* i, size_t n, void* s) { return ntt_entry(c, true, o, i, n, s); }
 
 // ------------------------------------------------------------------------------------------------
-template <class Arith, int OP>
-static void launch_dy(dpfhe_ctx* c, u64* out, const u64* a, const u64* b, size_t npolys, hipStream_t s, int b_period = 0) {
+template <int OP>
+static void launch_dy(const dpfhe_ctx* c, u64* out, const u64* a, const u64* b, size_t npolys, hipStream_t s, int b_period) {
     // distinct streams of the launch: a, b (unless broadcast or the same buffer), the result (unless in place; read as well by mul_add)
     const int streams = 1 + ((OP != DY_NEG && !b_period && b != a) ? 1 : 0) + ((out != a && out != b) ? 1 : 0);
     const bool nt = (npolys << c->log2n) * sizeof(u64) * (size_t)streams > ((size_t)256 << 20);   // cannot stay in the Infinity Cache
-    if (nt) hipLaunchKernelGGL((dyadic_kernel<Arith, OP, true>), dim3((unsigned)npolys), dim3(256), 0, s, out, a, b, tables_of<Arith>(c).lc,
-                               (int)c->n_limbs, 1 << c->log2n, b_period);
-    else hipLaunchKernelGGL((dyadic_kernel<Arith, OP, false>), dim3((unsigned)npolys), dim3(256), 0, s, out, a, b, tables_of<Arith>(c).lc,
-                            (int)c->n_limbs, 1 << c->log2n, b_period);
+    with_ctx_arith(c, [&](auto arith) {
+        typedef decltype(arith) Arith;
+        if (nt) hipLaunchKernelGGL((dyadic_kernel<Arith, OP, true>), dim3((unsigned)npolys), dim3(256), 0, s, out, a, b, c->lc, (int)c->n_limbs, 1 << c->log2n, b_period);
+        else hipLaunchKernelGGL((dyadic_kernel<Arith, OP, false>), dim3((unsigned)npolys), dim3(256), 0, s, out, a, b, c->lc, (int)c->n_limbs, 1 << c->log2n, b_period);
+    });
 }
 
 static int dyadic_entry(dpfhe_ctx* c, int op, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t n_rns_polys, void* stream, bool broadcast_b = false) {
@@ -698,16 +717,14 @@ static int dyadic_entry(dpfhe_ctx* c, int op, uint64_t* out, const uint64_t* a, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (op == DY_NEG) b = a;
     const int b_period = broadcast_b ? (int)c->n_limbs : 0;
-#define DY_CASE(OP)                                                             \
-    case OP:                                                                    \
-        if (c->fold) launch_dy<FoldArith, OP>(c, out, a, b, npolys, s, b_period); \
-        else launch_dy<ShoupArith, OP>(c, out, a, b, npolys, s, b_period);      \
-        break
     switch (op) {
-        DY_CASE(DY_MUL); DY_CASE(DY_MUL_ADD); DY_CASE(DY_ADD); DY_CASE(DY_SUB); DY_CASE(DY_NEG);
+        case DY_MUL: launch_dy<DY_MUL>(c, out, a, b, npolys, s, b_period); break;
+        case DY_MUL_ADD: launch_dy<DY_MUL_ADD>(c, out, a, b, npolys, s, b_period); break;
+        case DY_ADD: launch_dy<DY_ADD>(c, out, a, b, npolys, s, b_period); break;
+        case DY_SUB: launch_dy<DY_SUB>(c, out, a, b, npolys, s, b_period); break;
+        case DY_NEG: launch_dy<DY_NEG>(c, out, a, b, npolys, s, b_period); break;
         default: return fail(DPFHE_INVALID_ARGUMENT, "dyadic", "bad op");
     }
-#undef DY_CASE
     return check_launch("dyadic kernel launch");
 }
 
@@ -816,9 +833,7 @@ static int ct_mul_composed_slice(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t*
         pa = ws.p;
         pb = square ? ws.p : ws.p + 2 * batch * poly;
     }
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
-    if (c->fold) hipLaunchKernelGGL((tensor3_kernel<FoldArith>), dim3((unsigned)grid), dim3(256), 0, s, d_out3, pa, pb, lc, (int)L, (int)n, chunks);
-    else hipLaunchKernelGGL((tensor3_kernel<ShoupArith>), dim3((unsigned)grid), dim3(256), 0, s, d_out3, pa, pb, lc, (int)L, (int)n, chunks);
+    with_ctx_arith(c, [&](auto arith) { hipLaunchKernelGGL((tensor3_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, s, d_out3, pa, pb, c->lc, (int)L, (int)n, chunks); });
     if (int rc = check_launch("tensor product kernel launch")) return rc;
     if (!(flags & DPFHE_OUT_NTT)) return ntt_launch(c, true, d_out3, d_out3, batch * 3 * L, s);
     return DPFHE_SUCCESS;
@@ -833,17 +848,16 @@ static int key_switch_composed_slice(dpfhe_ctx* c, uint64_t* d_out2, const uint6
     if (lift_grid > kMaxGrid || 2 * batch * L * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, batch * L * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     StreamScratch ws(c, s);
     if (int rc = ws.alloc(batch * L * L * n, what)) return rc;
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
-    if (c->fold) hipLaunchKernelGGL((lift_rns_digits_kernel<FoldArith>), dim3((unsigned)lift_grid), dim3(256), 0, s, ws.p, d_in, in_comps, in_comps - 1, lc, (int)L, (int)n, chunks);
-    else hipLaunchKernelGGL((lift_rns_digits_kernel<ShoupArith>), dim3((unsigned)lift_grid), dim3(256), 0, s, ws.p, d_in, in_comps, in_comps - 1, lc, (int)L, (int)n, chunks);
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((lift_rns_digits_kernel<decltype(arith)>), dim3((unsigned)lift_grid), dim3(256), 0, s, ws.p, d_in, in_comps, in_comps - 1, c->lc, (int)L, (int)n, chunks);
+    });
     if (int rc = check_launch("digit lift kernel launch")) return rc;
     if (int rc = ntt_launch(c, false, ws.p, ws.p, batch * L * L, s)) return rc;
     const unsigned grid = (unsigned)(batch * L * (size_t)chunks);
-    if (c->fold) hipLaunchKernelGGL((key_inner_product_kernel<FoldArith>), dim3(grid), dim3(256), 0, s, d_out2, ws.p, d_evk, lc, (int)L, (int)L, (int)n, chunks);
-    else hipLaunchKernelGGL((key_inner_product_kernel<ShoupArith>), dim3(grid), dim3(256), 0, s, d_out2, ws.p, d_evk, lc, (int)L, (int)L, (int)n, chunks);
+    with_ctx_arith(c, [&](auto arith) { hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3(grid), dim3(256), 0, s, d_out2, ws.p, d_evk, c->lc, (int)L, (int)L, (int)n, chunks); });
     if (int rc = check_launch("key inner product kernel launch")) return rc;
     if (int rc = ntt_launch(c, true, d_out2, d_out2, batch * 2 * L, s)) return rc;
-    hipLaunchKernelGGL(add_back_kernel, dim3(2 * grid), dim3(256), 0, s, d_out2, d_in, in_comps, add_mask, lc, (int)L, (int)n, chunks);
+    hipLaunchKernelGGL(add_back_kernel, dim3(2 * grid), dim3(256), 0, s, d_out2, d_in, in_comps, add_mask, c->lc, (int)L, (int)n, chunks);
     return check_launch("add-back kernel launch");
 }
 
@@ -900,8 +914,7 @@ extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2
         const size_t pairs = blocks / c->n_limbs;
         rc = for_each_class(c, c->n_limbs, [&](const auto& tb) { return launch_ct_mul((int)c->log2n, flags, d_out3, d_a2, d_b2, pairs * (size_t)tb.n_active, tb, s); });
     } else {
-        rc = c->fold ? launch_ct_mul<FoldArith>((int)c->log2n, flags, d_out3, d_a2, d_b2, blocks, c->foldt, s)
-                     : launch_ct_mul<ShoupArith>((int)c->log2n, flags, d_out3, d_a2, d_b2, blocks, c->shoup, s);
+        rc = with_ctx_arith(c, [&](auto arith) { return launch_ct_mul((int)c->log2n, flags, d_out3, d_a2, d_b2, blocks, tables_of<decltype(arith)>(c), s); });
     }
     if (rc) return fail(DPFHE_INVALID_STATE, "dpfhe_ct_mul", "no kernel geometry for this log2_n");
     return check_launch("ct_mul kernel launch");
@@ -956,6 +969,14 @@ extern "C" int dpfhe_switch_key(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* 
     return check_launch("switch_key kernel launch");
 }
 
+// rescale_kernel over `blocks` (polynomial, kept limb, 512-word chunk) workgroups; `add` (add_comps components per item, null: none) as add_mask selects
+static void launch_rescale(const dpfhe_ctx* c, size_t blocks, hipStream_t s, u64* out, const u64* in, const u64* add, int add_comps, int add_mask) {
+    const int n = 1 << c->log2n, chunks = (n + 511) / 512;
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((rescale_kernel<decltype(arith)>), dim3((unsigned)blocks), dim3(256), 0, s, out, in, add, add_comps, add_mask, c->lc, c->d_rescale, (int)c->n_limbs, n, chunks);
+    });
+}
+
 extern "C" int dpfhe_rescale(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t n_rns_polys, void* stream) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_rescale", "null context");
     if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, "dpfhe_rescale", "no limb left to drop");
@@ -967,9 +988,15 @@ extern "C" int dpfhe_rescale(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_rescale", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_rescale");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->fold) hipLaunchKernelGGL((rescale_kernel<FoldArith>), dim3((unsigned)blocks), dim3(256), 0, s, d_out, d_in, (const u64*)nullptr, 0, 0, c->foldt.lc, c->d_rescale, (int)c->n_limbs, n, chunks);
-    else hipLaunchKernelGGL((rescale_kernel<ShoupArith>), dim3((unsigned)blocks), dim3(256), 0, s, d_out, d_in, (const u64*)nullptr, 0, 0, c->shoup.lc, c->d_rescale, (int)c->n_limbs, n, chunks);
+    launch_rescale(c, blocks, s, d_out, d_in, nullptr, 0, 0);
     return check_launch("rescale kernel launch");
+}
+
+// lift_digits_kernel over `grid` (digit, limb, chunk) workgroups: the Ld digits of the component at `comp` (items `item_stride` words apart) into `digits`
+static void launch_lift_digits(const dpfhe_ctx* c, size_t grid, hipStream_t s, u64* digits, const u64* comp, size_t item_stride, int chunks) {
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((lift_digits_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, s, digits, comp, item_stride, c->lc, (int)c->n_limbs, 1 << c->log2n, chunks);
+    });
 }
 
 // Above N = 8192 (no fused key-switch kernel): out[item][2][L][N] (NTT domain over Q P) = sum_j NTT(lift(digit_j of item)) (.) key_j, the digits being the Ld
@@ -980,7 +1007,6 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
                                  size_t batch, hipStream_t s, const char* what) {
     const size_t L = c->n_limbs, Ld = L - 1;
     const int n = 1 << c->log2n, ch = n / 512;
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
     const size_t per = slice_items(c, batch, Ld * L * (size_t)n);
     for (size_t i0 = 0; i0 < batch; i0 += per) {
         const size_t m = batch - i0 < per ? batch - i0 : per;
@@ -989,14 +1015,14 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
         StreamScratch ws(c, s);
         if (int rc = ws.alloc(m * Ld * L * n, what)) return rc;
         const u64* comp = comp0 + i0 * item_stride;
-        if (c->fold) hipLaunchKernelGGL((lift_digits_kernel<FoldArith>), dim3((unsigned)lift_grid), dim3(256), 0, s, ws.p, comp, item_stride, lc, (int)L, n, ch);
-        else hipLaunchKernelGGL((lift_digits_kernel<ShoupArith>), dim3((unsigned)lift_grid), dim3(256), 0, s, ws.p, comp, item_stride, lc, (int)L, n, ch);
+        launch_lift_digits(c, lift_grid, s, ws.p, comp, item_stride, ch);
         if (int rc = check_launch("digit lift kernel launch")) return rc;
         if (int rc = ntt_launch(c, false, ws.p, ws.p, m * Ld * L, s)) return rc;
         const unsigned grid = (unsigned)(m * L * (size_t)ch);
         u64* o = d_out_qp + i0 * 2 * L * n;
-        if (c->fold) hipLaunchKernelGGL((key_inner_product_kernel<FoldArith>), dim3(grid), dim3(256), 0, s, o, ws.p, d_keys, lc, (int)Ld, (int)L, n, ch, key_stride, key_group, (unsigned)i0);
-        else hipLaunchKernelGGL((key_inner_product_kernel<ShoupArith>), dim3(grid), dim3(256), 0, s, o, ws.p, d_keys, lc, (int)Ld, (int)L, n, ch, key_stride, key_group, (unsigned)i0);
+        with_ctx_arith(c, [&](auto arith) {
+            hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3(grid), dim3(256), 0, s, o, ws.p, d_keys, c->lc, (int)Ld, (int)L, n, ch, key_stride, key_group, (unsigned)i0);
+        });
         if (int rc = check_launch("key inner product kernel launch")) return rc;
     }
     return DPFHE_SUCCESS;
@@ -1006,7 +1032,7 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
 static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_out2, const uint64_t* d_in, const uint64_t* d_key,
                         uint64_t* d_work, size_t batch, void* stream, size_t key_stride = 0, unsigned key_group = 1) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    if (int rc = check_extended(c, what)) return rc;
     if (batch == 0) return DPFHE_SUCCESS;
     if (!d_out2 || !d_in || !d_key || !d_work || misaligned(d_out2) || misaligned(d_in) || misaligned(d_key) || misaligned(d_work))
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
@@ -1040,9 +1066,7 @@ static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* 
     const int chunks = (n + 511) / 512;
     const size_t rblocks = batch * 2 * Ld * (size_t)chunks;
     if (rblocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-    const int add_mask = in_comps == 3 ? 3 : 1;
-    if (c->fold) hipLaunchKernelGGL((rescale_kernel<FoldArith>), dim3((unsigned)rblocks), dim3(256), 0, s, d_out2, d_work, d_in, in_comps, add_mask, c->foldt.lc, c->d_rescale, (int)L, n, chunks);
-    else hipLaunchKernelGGL((rescale_kernel<ShoupArith>), dim3((unsigned)rblocks), dim3(256), 0, s, d_out2, d_work, d_in, in_comps, add_mask, c->shoup.lc, c->d_rescale, (int)L, n, chunks);
+    launch_rescale(c, rblocks, s, d_out2, d_work, d_in, in_comps, in_comps == 3 ? 3 : 1);
     return check_launch("hybrid rescale launch");
 }
 
@@ -1075,7 +1099,7 @@ static unsigned galois_inverse(unsigned g, unsigned two_n) {  // g^-1 mod 2N by 
 static int rotate_batch_impl(dpfhe_ctx* c, const char* what, uint64_t* d_out2, const uint64_t* d_in2, size_t n_in, const uint32_t* galois_elts, size_t n_elts,
                              size_t group, const uint64_t* d_keys, uint64_t* d_work, uint64_t* d_rotated, size_t batch, void* stream) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    if (int rc = check_extended(c, what)) return rc;
     if (batch == 0) return DPFHE_SUCCESS;
     if (n_in != 1 && n_in != batch) return fail(DPFHE_INVALID_ARGUMENT, what, "n_in must be 1 (one input, many rotations) or equal to batch");
     if (group == 0 || n_elts * group != batch) return fail(DPFHE_INVALID_ARGUMENT, what, "batch must be n_elts * group");
@@ -1085,11 +1109,9 @@ static int rotate_batch_impl(dpfhe_ctx* c, const char* what, uint64_t* d_out2, c
     const size_t L = c->n_limbs, Ld = L - 1;
     const int n = 1 << c->log2n;
     const unsigned two_n = 2u << c->log2n;
-    for (size_t i = 0; i < n_elts; ++i)
-        if (!(galois_elts[i] & 1u) || galois_elts[i] >= two_n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois elements must be odd and < 2N");
+    if (int rc = check_galois_elts(c, galois_elts, n_elts, what)) return rc;
     const size_t ct_words = 2 * Ld * (size_t)n, key_words = Ld * 2 * L * (size_t)n;
     if (n_in == batch && overlaps(d_rotated, batch * ct_words, d_in2, batch * ct_words)) return fail(DPFHE_INVALID_ARGUMENT, what, "d_rotated overlaps the input");
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DPFHE_ON_DEVICE(c, what);
     for (size_t first = 0; first < batch; first += kMaxGaloisBatch) {   // the elements travel as kernel arguments, 64 at a time
@@ -1097,7 +1119,7 @@ static int rotate_batch_impl(dpfhe_ctx* c, const char* what, uint64_t* d_out2, c
         GaloisInvs inv{};
         for (size_t i = 0; i < cnt; ++i) inv.v[i] = galois_inverse(galois_elts[(first + i) / group], two_n);
         const uint64_t* src = d_in2 + (n_in == 1 ? 0 : first * ct_words);
-        launch_galois_multi(s, (unsigned)(cnt * 2 * Ld), d_rotated + first * ct_words, src, n_in == 1 ? (size_t)0 : ct_words, lc, (int)Ld, n, (int)(2 * Ld), inv, 0u, 0u);
+        launch_galois_multi(s, (unsigned)(cnt * 2 * Ld), d_rotated + first * ct_words, src, n_in == 1 ? (size_t)0 : ct_words, c->lc, (int)Ld, n, (int)(2 * Ld), inv, 0u, 0u);
         int e = check_launch("galois kernel launch");
         if (e) return e;
     }
@@ -1123,7 +1145,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
                                            uint64_t* d_work, uint64_t* d_rotated0, uint64_t* d_digits, size_t batch, void* stream) {
     const char* what = "dpfhe_rotate_hybrid_hoisted";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    if (int rc = check_extended(c, what)) return rc;
     if (c->log2n > 14) return fail(DPFHE_INVALID_STATE, what, "available up to N = 16384");
     if (batch == 0 || n_items == 0) return DPFHE_SUCCESS;
     const bool composed = c->log2n > (uint32_t)kMaxFusedLog2N;   // N = 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
@@ -1133,8 +1155,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
     const size_t L = c->n_limbs, Ld = L - 1, T = n_items, total = batch * T;
     const int n = 1 << c->log2n;
     const unsigned two_n = 2u << c->log2n;
-    for (size_t i = 0; i < batch; ++i)
-        if (!(galois_elts[i] & 1u) || galois_elts[i] >= two_n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois elements must be odd and < 2N");
+    if (int rc = check_galois_elts(c, galois_elts, batch, what)) return rc;
     const size_t in_words = T * 2 * Ld * (size_t)n, out_words = total * 2 * Ld * n, work_words = d_work ? total * 2 * L * n : 0, rot_words = d_rotated0 ? total * Ld * n : 0,
                  dig_words = T * Ld * L * (size_t)n;
     if (overlaps(d_out2, out_words, d_in2, in_words) || overlaps(d_out2, out_words, d_work, work_words) || overlaps(d_out2, out_words, d_rotated0, rot_words) ||
@@ -1161,10 +1182,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
             if (int rc = rotate_hoisted_qp_impl(c, qp, d_in2, T, galois_elts + r0, d_keys + r0 * key_words, in_ntt, d_digits, m, stream, r0 != 0)) return rc;
             hipStream_t s = static_cast<hipStream_t>(stream);
             if (int rc = ntt_launch(c, true, qp + item_qp, qp + item_qp, m * T * 2 * L, s)) return rc;
-            const size_t rblocks = m * T * 2 * Ld * (size_t)chunks;
-            u64* o = d_out2 + r0 * T * 2 * Ld * n;
-            if (c->fold) hipLaunchKernelGGL((rescale_kernel<FoldArith>), dim3((unsigned)rblocks), dim3(256), 0, s, o, qp + item_qp, (const u64*)nullptr, 0, 0, c->foldt.lc, c->d_rescale, (int)L, n, chunks);
-            else hipLaunchKernelGGL((rescale_kernel<ShoupArith>), dim3((unsigned)rblocks), dim3(256), 0, s, o, qp + item_qp, (const u64*)nullptr, 0, 0, c->shoup.lc, c->d_rescale, (int)L, n, chunks);
+            launch_rescale(c, m * T * 2 * Ld * (size_t)chunks, s, d_out2 + r0 * T * 2 * Ld * n, qp + item_qp, nullptr, 0, 0);
             if (int rc = check_launch("hoisted rescale launch")) return rc;
         }
         return DPFHE_SUCCESS;
@@ -1172,13 +1190,10 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
     // (the key-switch launch pads its (rotation, limb[, component]) tiles to a multiple of 8 per token: launch_impl.h launch_hoisted_ks)
     if (total * 2 * Ld * (size_t)chunks > kMaxGrid || (total * L * 2 + 8 * T) > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid)
         return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DPFHE_ON_DEVICE(c, what);
     // 1. digits of every item's c1, lifted to every limb, then transformed (T * Ld RNS polynomials on the extended context)
-    const unsigned lift_grid = (unsigned)(T * Ld * L * (size_t)chunks);
-    if (c->fold) hipLaunchKernelGGL((lift_digits_kernel<FoldArith>), dim3(lift_grid), dim3(256), 0, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, lc, (int)L, n, chunks);
-    else hipLaunchKernelGGL((lift_digits_kernel<ShoupArith>), dim3(lift_grid), dim3(256), 0, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, lc, (int)L, n, chunks);
+    launch_lift_digits(c, T * Ld * L * (size_t)chunks, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, chunks);
     if (int e = check_launch("lift_digits kernel launch")) return e;
     if (int e = ntt_launch_items(c, false, d_digits, d_digits, T * Ld, 0, s)) return e;   // (per limb class where the context has them)
     // 2. sigma_g(c0) of every (rotation, item) for the final addition: [batch][T][Ld][N]; 64 output items per launch
@@ -1186,7 +1201,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
         const size_t cnt = total - first < (size_t)kMaxGaloisBatch ? total - first : (size_t)kMaxGaloisBatch;
         GaloisInvs inv{};
         for (size_t i = 0; i < cnt; ++i) inv.v[i] = galois_inverse(galois_elts[(first + i) / T], two_n);
-        launch_galois_multi(s, (unsigned)(cnt * Ld), d_rotated0 + first * Ld * n, d_in2, 2 * Ld * (size_t)n, lc, (int)Ld, n, (int)Ld, inv, (unsigned)T, (unsigned)(first % T));
+        launch_galois_multi(s, (unsigned)(cnt * Ld), d_rotated0 + first * Ld * n, d_in2, 2 * Ld * (size_t)n, c->lc, (int)Ld, n, (int)Ld, inv, (unsigned)T, (unsigned)(first % T));
         if (int e = check_launch("galois kernel launch")) return e;
     }
     // 3. permuted digits (.) keys, one inverse transform per (rotation, limb, key component, item); 64 rotations per launch
@@ -1199,9 +1214,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
         if (int e = check_launch("hoisted key-switch kernel launch")) return e;
     }
     // 4. divide by P with rounding; component 0 gets sigma_g(c0) added ([total][1][Ld][N] addend)
-    const size_t rblocks = total * 2 * Ld * (size_t)chunks;
-    if (c->fold) hipLaunchKernelGGL((rescale_kernel<FoldArith>), dim3((unsigned)rblocks), dim3(256), 0, s, d_out2, d_work, d_rotated0, 1, 1, c->foldt.lc, c->d_rescale, (int)L, n, chunks);
-    else hipLaunchKernelGGL((rescale_kernel<ShoupArith>), dim3((unsigned)rblocks), dim3(256), 0, s, d_out2, d_work, d_rotated0, 1, 1, c->shoup.lc, c->d_rescale, (int)L, n, chunks);
+    launch_rescale(c, total * 2 * Ld * (size_t)chunks, s, d_out2, d_work, d_rotated0, 1, 1);
     return check_launch("hoisted rescale launch");
 }
 
@@ -1213,7 +1226,7 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
                                   uint64_t* d_in_ntt, uint64_t* d_digits, size_t batch, void* stream, bool prepared) {
     const char* what = "dpfhe_rotate_hoisted_qp";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    if (int rc = check_extended(c, what)) return rc;
     if (c->log2n > 14) return fail(DPFHE_INVALID_STATE, what, "available up to N = 16384 (the stream kernels and the single-kernel transforms)");
     if (n_items == 0) return DPFHE_SUCCESS;
     if (!d_out_qp || !d_in2 || (batch && (!galois_elts || !d_keys)) || !d_in_ntt || !d_digits || misaligned(d_out_qp) || misaligned(d_in2) || misaligned(d_keys) ||
@@ -1221,9 +1234,7 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
     const size_t L = c->n_limbs, Ld = L - 1, T = n_items;
     const int n = 1 << c->log2n;
-    const unsigned two_n = 2u << c->log2n;
-    for (size_t i = 0; i < batch; ++i)
-        if (!(galois_elts[i] & 1u) || galois_elts[i] >= two_n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois elements must be odd and < 2N");
+    if (int rc = check_galois_elts(c, galois_elts, batch, what)) return rc;
     const size_t in_words = T * 2 * Ld * (size_t)n, out_words = (batch + 1) * T * 2 * L * n, dig_words = T * Ld * L * (size_t)n;
     if (overlaps(d_out_qp, out_words, d_in2, in_words) || overlaps(d_out_qp, out_words, d_in_ntt, in_words) || overlaps(d_out_qp, out_words, d_digits, dig_words) ||
         overlaps(d_digits, dig_words, d_in2, in_words) || overlaps(d_digits, dig_words, d_in_ntt, in_words) || overlaps(d_in_ntt, in_words, d_in2, in_words))
@@ -1232,7 +1243,6 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
     const int chunks = (n + 511) / 512;
     if ((batch + 1) * T * L * 8 > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid || T * 2 * L * (size_t)chunks > kMaxGrid)
         return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
     const u64 p_special = c->p_special;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DPFHE_ON_DEVICE(c, what);
@@ -1240,15 +1250,12 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
         // 1. NTT of the inputs on the data limbs (the same tables, seen as an Ld-limb context)
         if (int e = ntt_launch_items(c, false, d_in_ntt, d_in2, T * 2, Ld, s)) return e;
         // 2. digits of every item's c1, lifted to every limb and transformed
-        const unsigned lift_grid = (unsigned)(T * Ld * L * (size_t)chunks);
-        if (c->fold) hipLaunchKernelGGL((lift_digits_kernel<FoldArith>), dim3(lift_grid), dim3(256), 0, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, lc, (int)L, n, chunks);
-        else hipLaunchKernelGGL((lift_digits_kernel<ShoupArith>), dim3(lift_grid), dim3(256), 0, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, lc, (int)L, n, chunks);
+        launch_lift_digits(c, T * Ld * L * (size_t)chunks, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, chunks);
         if (int e = check_launch("lift_digits kernel launch")) return e;
         if (int e = ntt_launch_items(c, false, d_digits, d_digits, T * Ld, 0, s)) return e;   // (per limb class where the context has them)
         // 3. item block 0: the inputs themselves as P * ct over the extended basis
         const unsigned idg = (unsigned)(T * 2 * L * (size_t)chunks);
-        if (c->fold) hipLaunchKernelGGL((lift_qp_kernel<FoldArith>), dim3(idg), dim3(256), 0, s, d_out_qp, d_in_ntt, lc, p_special, (int)L, n, chunks);
-        else hipLaunchKernelGGL((lift_qp_kernel<ShoupArith>), dim3(idg), dim3(256), 0, s, d_out_qp, d_in_ntt, lc, p_special, (int)L, n, chunks);
+        with_ctx_arith(c, [&](auto arith) { hipLaunchKernelGGL((lift_qp_kernel<decltype(arith)>), dim3(idg), dim3(256), 0, s, d_out_qp, d_in_ntt, c->lc, p_special, (int)L, n, chunks); });
         if (int e = check_launch("lift_qp kernel launch")) return e;
     }
     // 4. the rotations: permuted digit segments x key segments as a stream (kernels_misc.h hoisted_qp_stream_kernel), 64 rotations per launch
@@ -1263,7 +1270,7 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
                 const size_t grid1 = qp_stream_grid((int)c->log2n, (int)L, cnt, T, 1);
                 if (grid1 > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
 #define QPU(LD) case LD: hipLaunchKernelGGL((hoisted_qp_upfront_kernel<LD>), dim3((unsigned)grid1), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge, \
-                                            (unsigned)cnt, (unsigned)T, p_special, lc, (int)c->log2n); break
+                                            (unsigned)cnt, (unsigned)T, p_special, c->lc, (int)c->log2n); break
                 switch (Ld) { QPU(1); QPU(2); QPU(3); QPU(4); QPU(5); QPU(6); }
 #undef QPU
                 if (int e = check_launch("hoisted_qp kernel launch")) return e;
@@ -1271,10 +1278,10 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
             }
             const size_t grid = qp_stream_grid((int)c->log2n, (int)L, cnt, T);
             if (grid > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-            if (c->fold) hipLaunchKernelGGL((hoisted_qp_stream_kernel<FoldArith, kQpPairs>), dim3((unsigned)grid), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge,
-                                            (unsigned)cnt, (unsigned)T, p_special, lc, (int)L, (int)c->log2n);
-            else hipLaunchKernelGGL((hoisted_qp_stream_kernel<ShoupArith, kQpPairs>), dim3((unsigned)grid), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge,
-                                    (unsigned)cnt, (unsigned)T, p_special, lc, (int)L, (int)c->log2n);
+            with_ctx_arith(c, [&](auto arith) {
+                hipLaunchKernelGGL((hoisted_qp_stream_kernel<decltype(arith), kQpPairs>), dim3((unsigned)grid), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge,
+                                   (unsigned)cnt, (unsigned)T, p_special, c->lc, (int)L, (int)c->log2n);
+            });
         }
         if (int e = check_launch("hoisted_qp kernel launch")) return e;
     }
@@ -1291,9 +1298,7 @@ extern "C" int dpfhe_ntt_inv_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
     if (n_elts == 0 || rns_polys_per_elt == 0) return DPFHE_SUCCESS;
     if (!d_out || !d_in || !galois_elts || misaligned(d_out) || misaligned(d_in)) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
-    const unsigned two_n = 2u << c->log2n;
-    for (size_t i = 0; i < n_elts; ++i)
-        if (!(galois_elts[i] & 1u) || galois_elts[i] >= two_n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois elements must be odd and < 2N");
+    if (int rc = check_galois_elts(c, galois_elts, n_elts, what)) return rc;
     const size_t per_elt = rns_polys_per_elt * c->n_limbs, words = n_elts * per_elt << c->log2n;
     if (d_out != d_in && overlaps(d_out, words, d_in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "output must be the input buffer or disjoint from it");
     if (per_elt * (n_elts < (size_t)kMaxGaloisBatch ? n_elts : (size_t)kMaxGaloisBatch) > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
@@ -1312,7 +1317,7 @@ extern "C" int dpfhe_ntt_inv_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_
 extern "C" int dpfhe_switch_key_qp(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* d_in2, const uint64_t* d_keys, size_t n_keys, size_t group, void* stream) {
     const char* what = "dpfhe_switch_key_qp";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (c->n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended context needs at least one data limb and the special prime");
+    if (int rc = check_extended(c, what)) return rc;
     const size_t batch = n_keys * group;
     if (batch == 0) return DPFHE_SUCCESS;
     if (!d_out_qp || !d_in2 || !d_keys || misaligned(d_out_qp) || misaligned(d_in2) || misaligned(d_keys)) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
@@ -1347,8 +1352,9 @@ extern "C" int dpfhe_rescale_bsgs(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->fold) hipLaunchKernelGGL((rescale_bsgs_kernel<FoldArith>), dim3((unsigned)blocks), dim3(256), 0, s, d_out2, d_in_qp, d_addends, n_add, batch, c->foldt.lc, c->d_rescale, (int)L, n, chunks);
-    else hipLaunchKernelGGL((rescale_bsgs_kernel<ShoupArith>), dim3((unsigned)blocks), dim3(256), 0, s, d_out2, d_in_qp, d_addends, n_add, batch, c->shoup.lc, c->d_rescale, (int)L, n, chunks);
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((rescale_bsgs_kernel<decltype(arith)>), dim3((unsigned)blocks), dim3(256), 0, s, d_out2, d_in_qp, d_addends, n_add, batch, c->lc, c->d_rescale, (int)L, n, chunks);
+    });
     return check_launch("rescale_bsgs kernel launch");
 }
 
@@ -1364,8 +1370,7 @@ extern "C" int dpfhe_apply_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_t*
     if (npolys > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_apply_galois", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_apply_galois");
     const unsigned inv = galois_inverse(galois_elt, two_n);
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
-    hipLaunchKernelGGL(galois_kernel, dim3((unsigned)npolys), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_in, lc, (int)c->n_limbs,
+    hipLaunchKernelGGL(galois_kernel, dim3((unsigned)npolys), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_in, c->lc, (int)c->n_limbs,
                        1 << c->log2n, inv);
     return check_launch("galois kernel launch");
 }
@@ -1392,9 +1397,9 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
         const bool ntw = rows * cols * ((size_t)c->n_limbs << c->log2n) * sizeof(u64) > ((size_t)256 << 20);
         // (the branch-free FULL form of the kernel, which the multi-right-hand-side product takes, measured SLOWER here: 1412 against 1258 us on configs[2] -
         // this launch streams 6 GiB of W from HBM with two right-hand-side polynomials per workgroup and lives on memory-level parallelism, not on issue slots)
-        if (ntw) hipLaunchKernelGGL((matvec_fold_kernel<RT, 2, WPT, true>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->foldt.lc, (int)c->n_limbs, n, chunks, rows,
+        if (ntw) hipLaunchKernelGGL((matvec_fold_kernel<RT, 2, WPT, true>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->lc, (int)c->n_limbs, n, chunks, rows,
                                     cols, (size_t)2, 1u, (unsigned)(rtiles * slabs));
-        else hipLaunchKernelGGL((matvec_fold_kernel<RT, 2, WPT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->foldt.lc, (int)c->n_limbs, n, chunks, rows, cols,
+        else hipLaunchKernelGGL((matvec_fold_kernel<RT, 2, WPT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->lc, (int)c->n_limbs, n, chunks, rows, cols,
                                 (size_t)2, 1u, (unsigned)(rtiles * slabs));
         return check_launch("matvec kernel launch");
     }
@@ -1402,8 +1407,30 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
     const size_t slabs = c->n_limbs * (size_t)chunks;
     const size_t blocks = ((slabs + 7) / 8) * 8 * ((rows + RT - 1) / RT);   // block ids laid out per XCD: kernels_misc.h matvec_kernel
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_plain", "too many rows for one launch");
-    hipLaunchKernelGGL((matvec_kernel<ShoupArith, RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->shoup.lc, (int)c->n_limbs, n, chunks, rows, cols);
+    hipLaunchKernelGGL((matvec_kernel<ShoupArith, RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->lc, (int)c->n_limbs, n, chunks, rows, cols);
     return check_launch("matvec kernel launch");
+}
+
+// One launch of the multi-right-hand-side product: `groups` groups of C / 2 right-hand sides (x / y at xs / ys, the full [n_rhs][2] stride), RT rows and
+// 256 WPT words per workgroup, block ids laid out per XCD (kernels_misc.h).  FOLD: matvec_fold_kernel's split-at-bit-30 column accumulators; otherwise
+// the generic matvec_multi_kernel (2 words per thread).
+template <bool FOLD, int RT, int C, int WPT = 2>
+static int matvec_multi_launch(const dpfhe_ctx* c, const char* what, u64* ys, const u64* d_W, const u64* xs, size_t rows, size_t cols, size_t n_rhs, size_t groups,
+                               hipStream_t s) {
+    const int n = 1 << c->log2n, chunks = (n + 256 * WPT - 1) / (256 * WPT);
+    const size_t slabs = c->n_limbs * (size_t)chunks, rtiles = (rows + RT - 1) / RT, tiles = rtiles * slabs;
+    const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles * groups;
+    if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "too many rows for one launch");
+    if constexpr (!FOLD)
+        hipLaunchKernelGGL((matvec_multi_kernel<ShoupArith, RT, C>), dim3((unsigned)blocks), dim3(256), 0, s, ys, d_W, xs, c->lc, (int)c->n_limbs, n, chunks, rows, cols,
+                           n_rhs * 2, (unsigned)groups, (unsigned)tiles);
+    else if (rows % RT == 0 && cols % FoldArith::kDot30Period == 0)   // whole row tiles and whole periods (a packed layer's products): the branch-free form
+        hipLaunchKernelGGL((matvec_fold_kernel<RT, C, WPT, false, kMatvecWd, true>), dim3((unsigned)blocks), dim3(256), 0, s, ys, d_W, xs, c->lc, (int)c->n_limbs, n, chunks,
+                           rows, cols, n_rhs * 2, (unsigned)groups, (unsigned)tiles);
+    else
+        hipLaunchKernelGGL((matvec_fold_kernel<RT, C, WPT, false, kMatvecWd>), dim3((unsigned)blocks), dim3(256), 0, s, ys, d_W, xs, c->lc, (int)c->n_limbs, n, chunks,
+                           rows, cols, n_rhs * 2, (unsigned)groups, (unsigned)tiles);
+    return check_launch("matvec_multi kernel launch");
 }
 
 extern "C" int dpfhe_matvec_plain_multi(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d_W, const uint64_t* d_x, size_t rows, size_t cols, size_t n_rhs,
@@ -1414,8 +1441,6 @@ extern "C" int dpfhe_matvec_plain_multi(dpfhe_ctx* c, uint64_t* d_y, const uint6
     if (cols == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "cols must be > 0");
     if (!d_y || !d_W || !d_x || misaligned(d_y) || misaligned(d_W) || misaligned(d_x)) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
     if (n_rhs == 1) return dpfhe_matvec_plain(c, d_y, d_W, d_x, rows, cols, stream);
-    const int n = 1 << c->log2n;
-    const int chunks = (n + 511) / 512;
     const size_t poly = (size_t)c->n_limbs << c->log2n;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DPFHE_ON_DEVICE(c, what);
@@ -1425,54 +1450,17 @@ extern "C" int dpfhe_matvec_plain_multi(dpfhe_ctx* c, uint64_t* d_y, const uint6
     // 1024-diagonal matvec of a packed GPT-2 layer, per token: 86 us single; 8 tokens: 75 us with one launch per group (W re-read from
     // HBM by every group), see MEASUREMENTS.md for the XCD-grouped launch.
     const size_t pairs = n_rhs / 2;
+    const uint64_t* x_last = d_x + (n_rhs - 1) * 2 * poly;   // an odd last right-hand side
+    uint64_t* y_last = d_y + (n_rhs - 1) * 2 * poly;
+    int rc = DPFHE_SUCCESS;
     if (c->fold) {   // split-at-bit-30 column accumulators (kernels_misc.h matvec_fold_kernel), same grouping and block-id layout
-#define MVF_LAUNCH(RT, C, WPT, GROUPS, XS, YS)                                                                                                          \
-    {                                                                                                                                                    \
-        const int chunks = (n + 256 * (WPT) - 1) / (256 * (WPT));                                                                                        \
-        const size_t slabs = c->n_limbs * (size_t)chunks, rtiles = (rows + RT - 1) / RT, tiles = rtiles * slabs;                                         \
-        const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles * (GROUPS);                                                                                 \
-        if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "too many rows for one launch");                                             \
-        /* whole row tiles and whole periods (a packed layer's products): the branch-free form, see kernels_misc.h */                                    \
-        if (rows % (RT) == 0 && cols % FoldArith::kDot30Period == 0)                                                                \
-            hipLaunchKernelGGL((matvec_fold_kernel<RT, C, WPT, false, kMatvecWd, true>), dim3((unsigned)blocks), dim3(256), 0, s, YS, d_W, XS, c->foldt.lc, (int)c->n_limbs, n, chunks, rows, \
-                               cols, n_rhs * 2, (unsigned)(GROUPS), (unsigned)tiles);                                                                    \
-        else                                                                                                                                             \
-            hipLaunchKernelGGL((matvec_fold_kernel<RT, C, WPT, false, kMatvecWd>), dim3((unsigned)blocks), dim3(256), 0, s, YS, d_W, XS, c->foldt.lc, (int)c->n_limbs, n, chunks, rows, cols, \
-                               n_rhs * 2, (unsigned)(GROUPS), (unsigned)tiles);                                                                          \
+        if (pairs) rc = matvec_multi_launch<true, kMatvecRt4, 4, kMatvecWpt4>(c, what, d_y, d_W, d_x, rows, cols, n_rhs, pairs, s);
+        if (!rc && (n_rhs & 1)) rc = matvec_multi_launch<true, 4, 2, kMatvecWpt2>(c, what, y_last, d_W, x_last, rows, cols, n_rhs, 1, s);
+    } else {
+        if (pairs) rc = matvec_multi_launch<false, 4, 4>(c, what, d_y, d_W, d_x, rows, cols, n_rhs, pairs, s);
+        if (!rc && (n_rhs & 1)) rc = matvec_multi_launch<false, 4, 2>(c, what, y_last, d_W, x_last, rows, cols, n_rhs, 1, s);
     }
-        if (pairs) {
-            MVF_LAUNCH(kMatvecRt4, 4, kMatvecWpt4, pairs, d_x, d_y)
-            if (int e = check_launch("matvec_multi kernel launch")) return e;
-        }
-        if (n_rhs & 1) {
-            const uint64_t* xs = d_x + (n_rhs - 1) * 2 * poly;
-            uint64_t* ys = d_y + (n_rhs - 1) * 2 * poly;
-            MVF_LAUNCH(4, 2, kMatvecWpt2, 1, xs, ys)
-            if (int e = check_launch("matvec_multi kernel launch")) return e;
-        }
-#undef MVF_LAUNCH
-        return DPFHE_SUCCESS;
-    }
-#define MV_LAUNCH(ARITH, RT, C, LC, GROUPS, XS, YS)                                                                                                      \
-    {                                                                                                                                                    \
-        const size_t slabs = c->n_limbs * (size_t)chunks, rtiles = (rows + RT - 1) / RT, tiles = rtiles * slabs;                                         \
-        const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles * (GROUPS);                                                                                 \
-        if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "too many rows for one launch");                                             \
-        hipLaunchKernelGGL((matvec_multi_kernel<ARITH, RT, C>), dim3((unsigned)blocks), dim3(256), 0, s, YS, d_W, XS, LC, (int)c->n_limbs, n, chunks, rows, cols, \
-                           n_rhs * 2, (unsigned)(GROUPS), (unsigned)tiles);                                                                              \
-    }
-    if (pairs) {
-        MV_LAUNCH(ShoupArith, 4, 4, c->shoup.lc, pairs, d_x, d_y)
-        if (int e = check_launch("matvec_multi kernel launch")) return e;
-    }
-    if (n_rhs & 1) {
-        const uint64_t* xs = d_x + (n_rhs - 1) * 2 * poly;
-        uint64_t* ys = d_y + (n_rhs - 1) * 2 * poly;
-        MV_LAUNCH(ShoupArith, 4, 2, c->shoup.lc, 1, xs, ys)
-        if (int e = check_launch("matvec_multi kernel launch")) return e;
-    }
-#undef MV_LAUNCH
-    return DPFHE_SUCCESS;
+    return rc;
 }
 
 extern "C" int dpfhe_matvec_scalar(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d_w, const uint64_t* d_x, size_t rows, size_t cols,
@@ -1489,8 +1477,9 @@ extern "C" int dpfhe_matvec_scalar(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* 
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_scalar", "too many rows for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_matvec_scalar");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->fold) hipLaunchKernelGGL((matvec_scalar_kernel<FoldArith, RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_w, d_x, c->foldt.lc, (int)c->n_limbs, n, chunks, rows, cols);
-    else hipLaunchKernelGGL((matvec_scalar_kernel<ShoupArith, RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_w, d_x, c->shoup.lc, (int)c->n_limbs, n, chunks, rows, cols);
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((matvec_scalar_kernel<decltype(arith), RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_w, d_x, c->lc, (int)c->n_limbs, n, chunks, rows, cols);
+    });
     return check_launch("matvec_scalar kernel launch");
 }
 
@@ -1502,7 +1491,6 @@ extern "C" int dpfhe_reduce_sum(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_reduce_sum", "too many components");
     DPFHE_ON_DEVICE(c, "dpfhe_reduce_sum");
     const int n = 1 << c->log2n;
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
     const int chunks = (n + 511) / 512;
     const size_t words_per_item = components * c->n_limbs * (size_t)n;
     // batch splits (their partial sums are combined with atomics): 15 for the large batches of the sharded multiply; a short batch (the
@@ -1517,10 +1505,10 @@ extern "C" int dpfhe_reduce_sum(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d
     // components at N=4096) and 2 % faster for the multiply it overlaps with in bench.py
     unsigned grid = poly_chunks * splits;
     if (count > 512 && grid > 2u * (unsigned)c->n_cu) grid = 2u * (unsigned)c->n_cu;   // short batches are latency-bound: no cap
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(grid), dim3(256), 0, s, d_out, d_in, lc, (int)c->n_limbs, n, chunks, count, words_per_item,
+    hipLaunchKernelGGL(reduce_partial_kernel, dim3(grid), dim3(256), 0, s, d_out, d_in, c->lc, (int)c->n_limbs, n, chunks, count, words_per_item,
                        poly_chunks, splits);
     if (int e = check_launch("reduce_sum partial kernel launch")) return e;
-    hipLaunchKernelGGL(reduce_final_kernel, dim3((unsigned)(blocks * chunks)), dim3(256), 0, s, d_out, lc, (int)c->n_limbs, n, chunks);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3((unsigned)(blocks * chunks)), dim3(256), 0, s, d_out, c->lc, (int)c->n_limbs, n, chunks);
     return check_launch("reduce_sum kernel launch");
 }
 
@@ -1533,7 +1521,7 @@ extern "C" int dpfhe_canonicalize_sum(dpfhe_ctx* c, uint64_t* d_io, size_t n_rns
     const size_t blocks = n_rns_polys * c->n_limbs * (size_t)chunks;
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_canonicalize_sum", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_canonicalize_sum");
-    hipLaunchKernelGGL(reduce_final_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_io, c->fold ? c->foldt.lc : c->shoup.lc, (int)c->n_limbs, n, chunks);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_io, c->lc, (int)c->n_limbs, n, chunks);
     return check_launch("canonicalize_sum kernel launch");
 }
 
@@ -1591,9 +1579,9 @@ static int base_extend_common(dpfhe_ctx* c, int mode, uint64_t* d_out, size_t ou
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(n_polys * (size_t)chunks);
     const size_t in_dst_off = mode == 1 ? ((size_t)dst0 - (size_t)src0) * n : 0;   // d_in points at the first DROPPED limb of item 0 (may wrap below it: size_t arithmetic, same pointer sum)
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;
-    const int rc = c->fold ? launch_base_extend<FoldArith>(mode, d_out, out_stride_limbs * n, d_in, in_stride_limbs * n, in_dst_off, a, lc, (int)n, chunks, grid, s)
-                           : launch_base_extend<ShoupArith>(mode, d_out, out_stride_limbs * n, d_in, in_stride_limbs * n, in_dst_off, a, lc, (int)n, chunks, grid, s);
+    const int rc = with_ctx_arith(c, [&](auto arith) {
+        return launch_base_extend<decltype(arith)>(mode, d_out, out_stride_limbs * n, d_in, in_stride_limbs * n, in_dst_off, a, c->lc, (int)n, chunks, grid, s);
+    });
     if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel for this number of source limbs");
     return check_launch("base_extend kernel launch");
 }
@@ -1640,6 +1628,14 @@ static int expand_args(const char* what, const void* buf, size_t components, uin
     return DPFHE_SUCCESS;
 }
 
+// the ring of a host twin (no context to take it from): at least one limb, 8 <= log2 N <= 16, odd moduli in [3, 2^60)
+static int check_host_ring(const char* what, const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n) {
+    if (n_limbs == 0 || log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, what, "n_limbs >= 1 and log2_n in [8, 16]");
+    for (uint32_t l = 0; l < n_limbs; ++l)
+        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be odd, >= 3 and < 2^60");
+    return DPFHE_SUCCESS;
+}
+
 extern "C" int dpfhe_expand_uniform(dpfhe_ctx* c, uint64_t* d_buf, size_t batch, size_t components, uint32_t component, const uint8_t seed[32],
                                     uint64_t first_item, void* stream) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "null context");
@@ -1648,8 +1644,8 @@ extern "C" int dpfhe_expand_uniform(dpfhe_ctx* c, uint64_t* d_buf, size_t batch,
     if (misaligned(d_buf)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "misaligned buffer");
     if (batch == 0) return DPFHE_SUCCESS;
     DPFHE_ON_DEVICE(c, "dpfhe_expand_uniform");
-    const LimbConst* lc = c->fold ? c->foldt.lc : c->shoup.lc;   // q and floor(2^128 / q) of every limb, whatever its class
-    if (launch_expand_uniform((int)c->log2n, d_buf, batch, components, component, c->n_limbs, lc, key, (uint32_t)first_item, static_cast<hipStream_t>(stream)))
+    // c->lc holds q and floor(2^128 / q) of every limb, whatever its class
+    if (launch_expand_uniform((int)c->log2n, d_buf, batch, components, component, c->n_limbs, c->lc, key, (uint32_t)first_item, static_cast<hipStream_t>(stream)))
         return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "batch too large for one launch");
     return check_launch("expand_uniform kernel launch");
 }
@@ -1659,9 +1655,7 @@ extern "C" int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limb
     if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "null moduli");
     ExpandKey key;
     if (int rc = expand_args("dpfhe_expand_uniform_host", out, components, component, seed, first_item, batch, key)) return rc;
-    if (n_limbs == 0 || log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "n_limbs >= 1 and log2_n in [8, 16]");
-    for (uint32_t l = 0; l < n_limbs; ++l)
-        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "moduli must be odd, >= 3 and < 2^60");
+    if (int rc = check_host_ring("dpfhe_expand_uniform_host", moduli, n_limbs, log2_n)) return rc;
     expand_uniform_host((int)log2_n, moduli, n_limbs, out, batch, components, component, key, (uint32_t)first_item);
     return DPFHE_SUCCESS;
 }
@@ -1740,9 +1734,7 @@ extern "C" int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_li
                                            size_t batch, size_t comps, size_t plain_items, uint64_t t, int negate) {
     static const char* what = "dpfhe_add_plain_scaled_host";
     if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, what, "null moduli");
-    if (n_limbs == 0 || log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, what, "n_limbs >= 1 and log2_n in [8, 16]");
-    for (uint32_t l = 0; l < n_limbs; ++l)
-        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be odd, >= 3 and < 2^60");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
     PlainAddArgs a;
     std::vector<PlainAddLimb> limbs;
     if (int rc = plain_add_args(what, out, in, plain, batch, comps, plain_items, t, negate, moduli, n_limbs, a, limbs)) return rc;
@@ -1798,12 +1790,6 @@ static int compact_args(const char* what, uint32_t bits0, uint32_t bits1, const 
     return DPFHE_SUCCESS;
 }
 
-// half-open byte ranges [a, a + na) and [b, b + nb) intersect
-static inline bool overlaps_bytes(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 extern "C" int dpfhe_compact(dpfhe_ctx* c, uint8_t* d_out, const uint64_t* d_in, size_t batch, uint32_t bits0, uint32_t bits1, void* stream) {
     static const char* what = "dpfhe_compact";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
@@ -1825,8 +1811,7 @@ extern "C" int dpfhe_compact_host(const uint64_t* moduli, uint32_t n_limbs, uint
     if (!moduli || !out || !in || batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or batch 0");
     if (log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, what, "log2_n in [8, 16]");
     if (n_limbs == 0 || n_limbs > kCompactMaxLimbs) return fail(DPFHE_INVALID_ARGUMENT, what, "1 to 10 limbs (rescale first)");
-    for (uint32_t l = 0; l < n_limbs; ++l)
-        if (moduli[l] < 3 || (moduli[l] >> 60) || !(moduli[l] & 1)) return fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be odd, >= 3 and < 2^60");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;   // (after this twin's own shape messages: only the moduli can fail here)
     CompactArgs a;
     if (int rc = compact_args(what, bits0, bits1, moduli, n_limbs, a)) return rc;
     const size_t words = batch * 2 * ((size_t)n_limbs << log2_n), bytes = batch * compact_record_bytes(log2_n, a);
