@@ -69,11 +69,17 @@ SYMBOLS = {
                                      C.c_uint64, C.c_int], C.c_int),
     "dpfhe_compact": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_compact_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32], C.c_int),
+    "dpfhe_encoder_create": ([C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64], C.c_int),
+    "dpfhe_encoder_destroy": ([C.c_void_p], C.c_int),
+    "dpfhe_encoder_root": ([C.c_void_p], C.c_uint64),
+    "dpfhe_encode_slots": ([C.c_void_p, _U64P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p], C.c_int),
+    "dpfhe_encode_slots_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32], C.c_int),
     "dpfhe_strerror": ([C.c_int], C.c_char_p),
     "dpfhe_last_error": ([], C.c_char_p),
 }
 
 IN_NTT, OUT_NTT = 1, 2
+ENCODE_PLAIN, ENCODE_NTT = 1, 2   # dpfhe_encode_slots flags
 
 
 class TuneInfo(C.Structure):

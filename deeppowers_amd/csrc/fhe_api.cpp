@@ -7,12 +7,14 @@
 #include <sys/random.h>
 
 #include <cerrno>
+#include <chrono>
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
 #include <istream>
+#include <mutex>
 #include <ostream>
 
 #include "deeppowers/fhe.hpp"
@@ -165,6 +167,7 @@ size_t PolyBuffer::size() const { return impl_->comps; }
 size_t PolyBuffer::words() const { return impl_->words; }
 bool PolyBuffer::is_ntt() const { return impl_->ntt; }
 void PolyBuffer::set_ntt(bool v) { impl_->ntt = v; }
+const Context& PolyBuffer::context() const { return *impl_->ctx; }
 void PolyBuffer::copy_from_host(const uint64_t* src) {
     if (!src) throw Exception(ErrorCode::INVALID_ARGUMENT, "copy_from_host: null source");
     hip_check(hipMemcpy(impl_->d, src, impl_->words * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
@@ -380,6 +383,11 @@ void ExactPlaintext::set_slots(const BatchEncoder& enc, const uint64_t* slots) {
     std::vector<int64_t> coeffs(impl_->items * n);
     for (size_t i = 0; i < impl_->items; ++i) enc.encode(slots + i * n, coeffs.data() + i * n);
     impl_->upload(coeffs.data());
+}
+void ExactPlaintext::set_slots_device(const BatchEncoder& enc, const uint32_t* slots, Stream* s) {
+    if (enc.plain_modulus() != impl_->t || enc.slot_count() != impl_->n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "ExactPlaintext::set_slots_device: the encoder's plaintext modulus or ring degree differs");
+    enc.encode_device_words(*impl_->ctx, slots, impl_->items, impl_->d, DPFHE_ENCODE_PLAIN, s);
 }
 
 // ---- CompactCiphertext ------------------------------------------------------------------------------------------------------
@@ -1667,7 +1675,34 @@ public:
     uint64_t t = 0;
     size_t n = 0;
     int logn = 0;
-    uint64_t n_inv = 0;
+    uint64_t n_inv = 0, zeta = 0;
+    // device encoders (include/dpfhe.h dpfhe_encoder), one per context this encoder has been asked to encode for: a dpfhe_encoder is bound to one context's
+    // limbs.  An entry remembers the moduli it was made for: a context that died and another that took its handle's address never share one.
+    struct DeviceEncoder { void* handle; std::vector<uint64_t> moduli; dpfhe_encoder* enc; };
+    mutable std::mutex enc_mutex;
+    mutable std::vector<DeviceEncoder> encoders;
+    ~Impl() {
+        for (auto& e : encoders) (void)dpfhe_encoder_destroy(e.enc);
+    }
+    dpfhe_encoder* encoder_for(const Context& c) const {
+        if (c.params().n() != n) throw Exception(ErrorCode::INVALID_ARGUMENT, "BatchEncoder::encode_device: the target's context has another ring degree");
+        std::lock_guard<std::mutex> lock(enc_mutex);
+        for (size_t i = 0; i < encoders.size(); ++i) {
+            if (encoders[i].handle != c.handle()) continue;
+            if (encoders[i].moduli == c.params().moduli) return encoders[i].enc;
+            (void)dpfhe_encoder_destroy(encoders[i].enc);   // (frees its own tables only: the context it was bound to is gone)
+            encoders.erase(encoders.begin() + i);
+            break;
+        }
+        dpfhe_encoder* e = nullptr;
+        check(dpfhe_encoder_create(&e, static_cast<dpfhe_ctx*>(c.handle()), t), "dpfhe_encoder_create");
+        if (dpfhe_encoder_root(e) != zeta) {
+            (void)dpfhe_encoder_destroy(e);
+            throw Exception(ErrorCode::INVALID_STATE, "BatchEncoder::encode_device: host and device encoders disagree on the root of unity");
+        }
+        encoders.push_back(DeviceEncoder{c.handle(), c.params().moduli, e});
+        return e;
+    }
     std::vector<uint64_t> rp, irp;       // zeta^brv(i), zeta^-brv(i) mod t  (the library's NTT convention, over Z_t)
     std::vector<uint32_t> idx;           // slot -> NTT index: row 0 slots, then row 1 slots
 
@@ -1709,6 +1744,7 @@ BatchEncoder::BatchEncoder(const Context& ctx, uint64_t t) : impl_(new Impl) {
     }
     if (!zeta) throw Exception(ErrorCode::INVALID_ARGUMENT, "BatchEncoder: no primitive 2N-th root of unity mod t (t not prime?)");
     const uint64_t izeta = powmod(zeta, t - 2, t);
+    impl_->zeta = zeta;
     impl_->rp.assign(n, 0); impl_->irp.assign(n, 0);
     uint64_t pw = 1, ipw = 1;
     for (size_t i = 0; i < n; ++i) {
@@ -1749,6 +1785,34 @@ void BatchEncoder::decode(const uint64_t* coeffs, uint64_t* slots) const {
     impl_->ntt_fwd(a);
     for (size_t i = 0; i < n; ++i) slots[i] = a[impl_->idx[i]];
 }
+uint64_t BatchEncoder::root() const { return impl_->zeta; }
+void BatchEncoder::encode_device_words(const Context& ctx, const uint32_t* slots, size_t items, uint64_t* d_out, uint32_t flags, Stream* s) const {
+    if (!slots || !d_out || items == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "BatchEncoder::encode_device: null argument or no items");
+    dpfhe_encoder* e = impl_->encoder_for(ctx);
+    hipPointerAttribute_t attr{};
+    const bool on_device = hipPointerGetAttributes(&attr, slots) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    if (on_device) {
+        check(dpfhe_encode_slots(e, d_out, slots, items, flags, s), "dpfhe_encode_slots");
+        return;
+    }
+    (void)hipGetLastError();   // (an unregistered host pointer is reported as an error by some runtimes)
+    hip_check(hipSetDevice(ctx.device_id()), "hipSetDevice");
+    void* stage = nullptr;
+    const size_t bytes = items * impl_->n * sizeof(uint32_t);
+    hip_check(hipMalloc(&stage, bytes), "hipMalloc");
+    hipError_t err = hipMemcpyAsync(stage, slots, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(s));
+    int rc = DPFHE_SUCCESS;
+    if (err == hipSuccess) rc = dpfhe_encode_slots(e, d_out, static_cast<const uint32_t*>(stage), items, flags, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(static_cast<hipStream_t>(s));
+    (void)hipFree(stage);
+    hip_check(err, "BatchEncoder::encode_device staging");
+    check(rc, "dpfhe_encode_slots");
+}
+void BatchEncoder::encode_device(const uint32_t* slots, size_t items, Plaintext& out, bool to_ntt, Stream* s) const {
+    if (out.batch() != items) throw Exception(ErrorCode::INVALID_ARGUMENT, "BatchEncoder::encode_device: the plaintext must hold `items` polynomials");
+    encode_device_words(out.context(), slots, items, out.data(), to_ntt ? DPFHE_ENCODE_NTT : 0u, s);
+    out.set_ntt(to_ntt);
+}
 uint32_t BatchEncoder::galois_element(int left_rotation) const {
     const long long row = (long long)impl_->n / 2;
     const uint64_t s = (uint64_t)(((left_rotation % row) + row) % row);
@@ -1774,6 +1838,7 @@ public:
     size_t n1 = 0, n2 = 0;
     std::unique_ptr<Plaintext> diag;   // [passes][n2][n1] pre-rotated diagonals, NTT domain
     std::unique_ptr<ExactPlaintext> bias;   // [passes][N]: bias[R] on every slot that holds output row R, or null
+    double encode_s = 0;                    // wall time the constructor spent building and encoding the diagonals and the bias (device work included)
     std::vector<uint32_t> baby_elts, giant_elts, fold_elts;
     // per-layer scratch, reused by every apply() (one caller at a time).  Terms over Q P live on the key switcher's extended context.
     std::unique_ptr<PolyBuffer> babies_qp, inner_qp, terms_qp, ksum_qp;
@@ -1864,46 +1929,59 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
         throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: the key switcher was built for another context");
     const size_t Le = L + 1;
     I.diag.reset(new Plaintext(ext, I.passes * I.n2 * n1, /*is_ntt=*/false));
-    std::vector<uint64_t> slots(N), host(n1 * Le * N);
-    std::vector<int64_t> coeffs(N);
-    for (size_t pass = 0; pass < I.passes; ++pass) {
-        for (size_t i = 0; i < I.n2; ++i) {
-            for (size_t j = 0; j < n1; ++j) {
-                const size_t k = i * n1 + j;
-                for (size_t rho = 0; rho < 2; ++rho)
-                    for (size_t rp = 0; rp < row; ++rp) {
-                        const size_t r = (rp + row - (i * n1) % row) % row;
-                        const size_t R = I.row_of_slot(pass, rho * row + r), col = (r + k) % I.n;
-                        slots[rho * row + rp] = (R != (size_t)-1 && col < in_dim) ? W[R * in_dim + col] : 0;
-                    }
-                enc.encode(slots.data(), coeffs.data());
-                for (size_t l = 0; l < Le; ++l)
-                    for (size_t c = 0; c < N; ++c) host[(j * Le + l) * N + c] = lift_signed(coeffs[c], pe.moduli[l]);
+    // the slot vectors are built here as 32-bit values and encoded on the device: inverse transform over Z_t, lift to the Le limbs and the forward
+    // transform, one call per giant step's n1 diagonals (the words BatchEncoder::encode + lift_signed + transform_to_ntt gave)
+    const auto encode_t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> slots(n1 * N);
+    void* stage = nullptr;
+    hip_check(hipSetDevice(ext.device_id()), "hipSetDevice");
+    hip_check(hipMalloc(&stage, slots.size() * sizeof(uint32_t)), "hipMalloc");
+    try {
+        for (size_t pass = 0; pass < I.passes; ++pass) {
+            for (size_t i = 0; i < I.n2; ++i) {
+                for (size_t j = 0; j < n1; ++j) {
+                    const size_t k = i * n1 + j;
+                    for (size_t rho = 0; rho < 2; ++rho)
+                        for (size_t rp = 0; rp < row; ++rp) {
+                            const size_t r = (rp + row - (i * n1) % row) % row;
+                            const size_t R = I.row_of_slot(pass, rho * row + r), col = (r + k) % I.n;
+                            slots[j * N + rho * row + rp] = (R != (size_t)-1 && col < in_dim) ? (uint32_t)W[R * in_dim + col] : 0u;
+                        }
+                }
+                // the copy is ordered behind the previous encode on the null stream; the host builds the next vectors while the device encodes these
+                uint32_t* d_slots = static_cast<uint32_t*>(stage);
+                hip_check(hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+                enc.encode_device_words(ext, d_slots, n1, I.diag->data() + ((pass * I.n2 + i) * n1) * Le * N, DPFHE_ENCODE_NTT, nullptr);
             }
-            hip_check(hipMemcpy(I.diag->data() + ((pass * I.n2 + i) * n1) * Le * N, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
         }
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    } catch (...) {
+        (void)hipFree(stage);
+        throw;
     }
-    Evaluator ev(ext);
-    ev.transform_to_ntt_inplace(*I.diag);
+    (void)hipFree(stage);
+    I.diag->set_ntt(true);
     for (size_t pass = 0; pass < I.passes; ++pass) {
         I.inner_elts.push_back(1u);
         I.inner_elts.insert(I.inner_elts.end(), I.giant_elts.begin(), I.giant_elts.end());
     }
     // the bias: one slot vector per output ciphertext, in the layout the output itself has (row_of_slot - so also the replicated, folded and two-token ones)
     if (bias) {
-        std::vector<uint64_t> bslots(I.passes * N);
+        std::vector<uint32_t> bslots(I.passes * N);
         for (size_t pass = 0; pass < I.passes; ++pass)
             for (size_t sl = 0; sl < N; ++sl) {
                 const size_t R = I.row_of_slot(pass, sl);
-                bslots[pass * N + sl] = R != (size_t)-1 ? bias[R] : 0;
+                bslots[pass * N + sl] = R != (size_t)-1 ? (uint32_t)bias[R] : 0u;
             }
         I.bias.reset(new ExactPlaintext(ctx, t, I.passes));
-        I.bias->set_slots(enc, bslots.data());
+        I.bias->set_slots_device(enc, bslots.data());
     }
+    I.encode_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - encode_t0).count();
     I.ensure_tokens(1);
     ext.synchronize();
 }
 bool PackedLinear::has_bias() const { return impl_->bias != nullptr; }
+double PackedLinear::encode_seconds() const { return impl_->encode_s; }
 PackedLinear::~PackedLinear() = default;
 size_t PackedLinear::dim() const { return impl_->m; }
 size_t PackedLinear::in_dim() const { return impl_->in_dim; }
@@ -2040,16 +2118,10 @@ PackedSelect::PackedSelect(const Context& ctx, const BatchEncoder& enc, HybridKe
     for (size_t sft = period; sft < row; sft <<= 1) { I.spread_elts.push_back(enc.galois_element(-(int)sft)); ks.add_galois_element(I.spread_elts.back()); }
     I.swap_elt = (uint32_t)(2 * N - 1);
     if (I.tpc == 1) ks.add_galois_element(I.swap_elt);
-    std::vector<uint64_t> slots(N, 0), host(L * N);
-    std::vector<int64_t> coeffs(N);
+    std::vector<uint32_t> slots(N, 0);
     for (size_t i = 0; i < length; ++i) { slots[i] = 1; if (I.tpc == 2) slots[row + i] = 1; }   // (two tokens: the same slice of row 1)
-    enc.encode(slots.data(), coeffs.data());
-    for (size_t l = 0; l < L; ++l)
-        for (size_t c = 0; c < N; ++c) host[l * N + c] = lift_signed(coeffs[c], p.moduli[l]);
     I.mask.reset(new Plaintext(ctx, 1, false));
-    I.mask->copy_from_host(host.data());
-    Evaluator ev(ctx);
-    ev.transform_to_ntt_inplace(*I.mask);
+    enc.encode_device(slots.data(), 1, *I.mask, /*to_ntt=*/true);
     I.ensure(1);
     ctx.synchronize();
 }

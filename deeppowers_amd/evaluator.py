@@ -108,8 +108,20 @@ class Context:
         """Slice size (MiB of scratch) of the composed large-ring operations (log2_n >= 14); a set-up call."""
         _cabi.check(self._lib.dpfhe_ctx_set_scratch_limit(self._h, int(mib)), "dpfhe_ctx_set_scratch_limit")
 
+    def encoder(self, t: int):
+        """the device slot encoder (include/dpfhe.h dpfhe_encoder) of this context for the plaintext modulus t: created at first use (a set-up call:
+        one allocation and copy), kept until close()"""
+        cache = self.__dict__.setdefault("_encoders", {})
+        if int(t) not in cache:
+            h = C.c_void_p()
+            _cabi.check(self._lib.dpfhe_encoder_create(C.byref(h), self._h, int(t)), "dpfhe_encoder_create")
+            cache[int(t)] = h
+        return cache[int(t)]
+
     def close(self):
         if getattr(self, "_h", None):
+            for h in self.__dict__.pop("_encoders", {}).values():
+                self._lib.dpfhe_encoder_destroy(h)
             self._lib.dpfhe_ctx_destroy(self._h)
             self._h = None
 
@@ -437,6 +449,25 @@ class Evaluator:
         _cabi.check(self._lib.dpfhe_add_plain_scaled(self.ctx.handle, ct.data_ptr(), ct.data_ptr(), plain.data_ptr(), ct.shape[0], ct.shape[1],
                                                      plain.shape[0], int(t), 1 if negate else 0, self._sp(stream)), "dpfhe_add_plain_scaled")
         return ct
+
+    # ---- slot encoding on the device (include/dpfhe.h dpfhe_encode_slots) ------------------------------------------------------------
+    def encode_slots(self, slots: torch.Tensor, t: int, plain: bool = False, to_ntt: bool = False, stream=None) -> torch.Tensor:
+        """slots: contiguous [items][N] tensor of slot values < t on the context's device, int32 (read as unsigned 32-bit words, so a value >= 2^31
+        is its two's-complement int32) or int64 (converted here) -> a new int64 tensor: [items][N] coefficients in [0, t) (plain: the operand of
+        add_plain_scaled_) or [items][L][N] residues of the centred polynomial (to_ntt: transformed, the operand of multiply_plain).  The encoder of
+        (context, t) is cached on the context; a request-time operand never visits the host."""
+        p = self.ctx.params
+        if slots.dim() != 2 or slots.shape[0] == 0 or slots.shape[1] != p.n or slots.device != self.ctx.device or slots.dtype not in (torch.int32, torch.int64):
+            raise _cabi.DpfheError(2000, "encode_slots: a non-empty [items][N] int32 or int64 tensor on the context's device")
+        if plain and to_ntt:
+            raise _cabi.DpfheError(2000, "encode_slots: the plain form has no transform")
+        enc = self.ctx.encoder(t)
+        with self._on(stream):
+            words = slots.to(torch.int32).contiguous()   # (int64 -> int32 keeps the low 32 bits)
+            out = torch.empty((slots.shape[0], p.n) if plain else (slots.shape[0], p.n_limbs, p.n), dtype=torch.int64, device=self.ctx.device)
+        flags = _cabi.ENCODE_PLAIN if plain else (_cabi.ENCODE_NTT if to_ntt else 0)
+        _cabi.check(self._lib.dpfhe_encode_slots(enc, out.data_ptr(), words.data_ptr(), slots.shape[0], flags, self._sp(stream)), "dpfhe_encode_slots")
+        return out
 
     # ---- compact result ciphertexts (include/dpfhe.h dpfhe_compact) ------------------------------------------------------------------
     def compact(self, ct: torch.Tensor, bits0: int, bits1: int, stream=None) -> torch.Tensor:

@@ -114,6 +114,7 @@ public:
     size_t words() const;  // batch * size * L * N
     bool is_ntt() const;
     void set_ntt(bool v);
+    const Context& context() const;   // the context the buffer was made for
     void copy_from_host(const uint64_t* src);  // words() canonical residues
     void copy_to_host(uint64_t* dst) const;
     // N4: wire format.  Little-endian: "DPFHEv1\0", u32 log2_n, u32 n_limbs, u64 batch, u64 components,
@@ -157,6 +158,9 @@ public:
     ExactPlaintext& operator=(const ExactPlaintext&) = delete;
     void set_coefficients(const int64_t* coeffs);   // items * N values, centred or non-negative: reduced mod t
     void set_slots(const BatchEncoder& enc, const uint64_t* slots);   // items * N slot values < t, encoded on the host with enc (same t)
+    // the same coefficients, encoded on the device (include/dpfhe.h dpfhe_encode_slots, DPFHE_ENCODE_PLAIN): items * N 32-bit slot values, a HOST or a
+    // DEVICE pointer as for BatchEncoder::encode_device
+    void set_slots_device(const BatchEncoder& enc, const uint32_t* slots, Stream* stream = nullptr);
     size_t items() const;
     uint64_t plain_modulus() const;
     size_t ring_degree() const;     // N
@@ -512,6 +516,16 @@ public:
     void encode(const uint64_t* slots /* N values < t: row 0 then row 1 */, int64_t* coeffs_out /* N, centred mod t */) const;
     void decode(const uint64_t* coeffs_mod_t /* N */, uint64_t* slots_out /* N */) const;
     uint32_t galois_element(int left_rotation) const;   // 3^s mod 2N (negative s rotates right)
+    uint64_t root() const;                              // zeta (include/dpfhe.h dpfhe_encoder_root gives the same number)
+    // Encoding ON THE DEVICE (include/dpfhe.h dpfhe_encode_slots): `items` slot vectors of N 32-bit values < t -> the `items` polynomials of `out`, the
+    // words encode() + a lift to every limb + an upload would give (to_ntt: transformed as well; out's domain flag is set either way).  `out` may belong to
+    // the encoder's context or to ANY context of the same ring degree on the same device (the extended Q P context of a key switcher): the encoder keeps
+    // one set of device tables per context it has encoded for.  `slots` is a device pointer (16-byte aligned: the call only enqueues on `stream`, no
+    // allocation, no synchronisation - a request-time operand never visits the host) or a host pointer (staged through a temporary device buffer; the
+    // call then synchronises `stream`).  Thread-safe.
+    void encode_device(const uint32_t* slots, size_t items, Plaintext& out, bool to_ntt = false, Stream* stream = nullptr) const;
+    // the building block of the above and of ExactPlaintext::set_slots_device: d_out on ctx's device, flags as for dpfhe_encode_slots
+    void encode_device_words(const Context& ctx, const uint32_t* slots, size_t items, uint64_t* d_out, uint32_t flags, Stream* stream = nullptr) const;
 
 private:
     class Impl;
@@ -552,6 +566,7 @@ public:
     PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim,
                  size_t tokens_per_ciphertext, const uint64_t* bias);
     bool has_bias() const;
+    double encode_seconds() const;   // wall time the constructor spent building and encoding the diagonals and the bias (the rest of it generates keys)
     ~PackedLinear();
     PackedLinear(const PackedLinear&) = delete;
     PackedLinear& operator=(const PackedLinear&) = delete;

@@ -338,6 +338,34 @@ int dpfhe_compact(dpfhe_ctx* ctx, uint8_t* d_out, const uint64_t* d_in, size_t b
 int dpfhe_compact_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint8_t* out, const uint64_t* in, size_t batch,
                        uint32_t bits0, uint32_t bits1);
 
+/* -- slot encoding over Z_t: slot vectors -> message polynomials on the device (what BatchEncoder::encode + lift_signed + an upload did on the host).
+ * Definition.  N = 2^log2_n; t prime, t < 2^32, t = 1 mod 2N.  zeta = g^((t-1)/2N) mod t for the smallest g >= 2 with zeta^N = -1 mod t (dpfhe_encoder_root).
+ *   The N slots are 2 rows of N/2.  The message polynomial m (degree < N, coefficients mod t) is the one with
+ *       m(zeta^(3^i)) = slots[i],   m(zeta^(-3^i)) = slots[N/2 + i],   0 <= i < N/2, exponents mod 2N
+ *   (N values fix a polynomial of degree < N; X -> X^(3^s) rotates both rows left by s slots, X -> X^(2N-1) swaps them).
+ *   DPFHE_ENCODE_PLAIN: out is [items][N], word k = coefficient a_k of m in [0, t) - the operand of dpfhe_add_plain_scaled.
+ *   default (flags 0):  out is [items][L][N], word [item][l][k] = c_k mod q_l in [0, q_l), c_k = a_k - t if a_k > floor(t/2), else a_k (the centred
+ *       coefficient), for every limb l of the context.  A limb may be smaller than t, and t need not be coprime to the q_l: the residue is exact either way.
+ *   DPFHE_ENCODE_NTT:   the residue output, then the context's forward transform of it in place (the words dpfhe_ntt_fwd makes of the default output);
+ *       invalid together with DPFHE_ENCODE_PLAIN.
+ * dpfhe_encoder_create is a set-up call (one allocation, one copy: the powers of zeta^-1 with their quotients, the slot -> position table, the limb
+ *   constants).  The encoder is bound to `ctx` (its N and limbs), which must outlive it; it is immutable afterwards and may be shared between threads.
+ *   DPFHE_INVALID_ARGUMENT, before touching the device, on a null pointer, t >= 2^32, t not prime, t != 1 mod 2N.  Destroying null is safe.
+ * dpfhe_encode_slots enqueues only (no allocation, no synchronise): d_slots is [items][N] 32-bit slot values, 16-byte aligned like d_out.  A slot value
+ *   >= t is a caller error; the device REDUCES it mod t (it never faults).  DPFHE_INVALID_ARGUMENT on a null pointer, items 0, an unknown flag bit, PLAIN
+ *   with NTT, a misaligned buffer, out and slots overlapping, or more than (2^31 - 1) / N items (one launch).  At log2_n >= 15 the transform is two kernels
+ *   and parks its intermediate words in d_out itself.
+ * dpfhe_encode_slots_host: the same words on the host (no device, no context; moduli odd, >= 3 and < 2^60, log2_n in [8, 16]); rejects a slot value
+ *   >= t and DPFHE_ENCODE_NTT as well. */
+typedef struct dpfhe_encoder dpfhe_encoder;
+enum { DPFHE_ENCODE_PLAIN = 1u, DPFHE_ENCODE_NTT = 2u };
+int dpfhe_encoder_create(dpfhe_encoder** out, dpfhe_ctx* ctx, uint64_t t);
+int dpfhe_encoder_destroy(dpfhe_encoder* enc);
+uint64_t dpfhe_encoder_root(const dpfhe_encoder* enc);
+int dpfhe_encode_slots(dpfhe_encoder* enc, uint64_t* d_out, const uint32_t* d_slots, size_t items, uint32_t flags, void* stream);
+int dpfhe_encode_slots_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t t, uint64_t* out, const uint32_t* slots, size_t items,
+                            uint32_t flags);
+
 const char* dpfhe_strerror(int code);
 /* text of the last HIP/RCCL failure on the calling thread ("" if none) */
 const char* dpfhe_last_error(void);
