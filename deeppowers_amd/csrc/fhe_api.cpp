@@ -1449,6 +1449,61 @@ double Decryptor::noise_budget_bits(const CompactCiphertext& ct, uint64_t t) {
     return (double)(K + 1) - 1.0 - worst;   // bits(2^K) - 1 - worst, as for Q above
 }
 
+// ---- Rerandomizer -------------------------------------------------------------------------------------------------------
+class Rerandomizer::Impl {
+public:
+    const Context* ctx = nullptr;
+    const PublicKey* pk = nullptr;
+    Sampler rng;
+    std::unique_ptr<PolyBuffer> work;   // 3 L N words per item: u | the two products (dpfhe_rerandomize)
+    unsigned log2_q = 0;                // floor(log2 Q), exact
+    void init(const Context& c, const PublicKey& k) {
+        if (!k.is_ntt() || k.size() != 2 || k.batch() != 1) throw Exception(ErrorCode::INVALID_ARGUMENT, "Rerandomizer: public key must be one 2-component NTT-domain item");
+        if (&k.context() != &c) throw Exception(ErrorCode::INVALID_ARGUMENT, "Rerandomizer: the public key belongs to another context");
+        ctx = &c; pk = &k;
+        std::vector<uint64_t> w(1, 1);   // Q in 64-bit words
+        for (uint64_t q : c.params().moduli) {
+            uint64_t carry = 0;
+            for (uint64_t& x : w) { const u128 t = (u128)x * q + carry; x = (uint64_t)t; carry = (uint64_t)(t >> 64); }
+            if (carry) w.push_back(carry);
+        }
+        log2_q = (unsigned)(64 * (w.size() - 1) + (63 - __builtin_clzll(w.back())));
+    }
+};
+Rerandomizer::Rerandomizer(const Context& ctx, const PublicKey& pk) : impl_(new Impl) { impl_->init(ctx, pk); }
+Rerandomizer::Rerandomizer(const Context& ctx, const PublicKey& pk, TestSeed seed) : impl_(new Impl) {
+    impl_->init(ctx, pk);
+    impl_->rng = Sampler(seed);
+}
+Rerandomizer::~Rerandomizer() = default;
+unsigned Rerandomizer::flood_bits_for(double noise_bits, unsigned log2_n, unsigned lambda) {
+    const double b = std::ceil(noise_bits < 0 ? 0.0 : noise_bits);
+    return (unsigned)b + lambda + log2_n;
+}
+unsigned Rerandomizer::max_flood_bits(uint64_t t) const {
+    unsigned ceil_log2_t = 0;
+    while (ceil_log2_t < 64 && ((uint64_t)1 << ceil_log2_t) < t) ++ceil_log2_t;
+    const unsigned need = ceil_log2_t + 4;
+    const unsigned cap = impl_->log2_q > need ? impl_->log2_q - need : 0;
+    return cap < 250 ? cap : 250;
+}
+void Rerandomizer::rerandomize(Ciphertext& ct, uint64_t t, unsigned flood_bits, Stream* s) {
+    Impl& I = *impl_;
+    const FheParams& fp = I.ctx->params();
+    if (ct.is_ntt() || ct.size() != 2 || ct.batch() == 0 || &ct.context() != I.ctx || ct.words() != ct.batch() * 2 * fp.n_limbs() * fp.n())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "rerandomize: a 2-component coefficient-domain ciphertext of this context (relinearise a product first)");
+    if (t < 2 || t >> 32) throw Exception(ErrorCode::INVALID_ARGUMENT, "rerandomize: plaintext modulus must be in [2, 2^32)");
+    if (flood_bits < 1 || flood_bits > max_flood_bits(t))
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "rerandomize: flood_bits must lie in [1, floor(log2 Q) - ceil(log2 t) - 4] (and at most 250): less than about two bits of budget would remain");
+    if (!I.work || I.work->batch() < ct.batch()) I.work.reset(new PolyBuffer(*I.ctx, ct.batch(), 3, false));   // grown, never shrunk
+    Seed seed;   // fresh for every call, never stored
+    draw_seed(I.rng, seed);
+    const int rc = dpfhe_rerandomize(static_cast<dpfhe_ctx*>(I.ctx->handle()), ct.data(), I.pk->data(), ct.batch(), flood_bits, seed.bytes, 0, I.work->data(), s);
+    volatile uint8_t* wipe = seed.bytes;
+    for (size_t i = 0; i < sizeof(seed.bytes); ++i) wipe[i] = 0;
+    check(rc, "dpfhe_rerandomize");
+}
+
 // ---- HybridKeySwitcher ---------------------------------------------------------------------------------------------------
 class HybridKeySwitcher::Impl {
 public:

@@ -437,6 +437,36 @@ class Evaluator:
                     "dpfhe_expand_uniform")
         return t
 
+    # ---- noise polynomials and re-randomisation (include/dpfhe.h dpfhe_sample_noise, dpfhe_rerandomize) ------------------------------
+    def sample_noise_(self, t: torch.Tensor, kind: int, param: int, stream_id: int, seed: bytes, component: int, first_item: int = 0, add: bool = False,
+                      stream=None) -> torch.Tensor:
+        """in place: component `component` of every item of t [batch...][components][L][N] = noise(seed, first_item + b, stream_id, kind, param) (+= it
+        mod q with add); every other word is left as it is.  kind: _cabi.NOISE_TERNARY / NOISE_CBD21 / NOISE_FLOOD (param = bits).  The seed is SECRET
+        and serves one call only."""
+        self._chk(t)
+        seed = bytes(seed)
+        if len(seed) != 32 or t.dim() < 3 or component < 0 or first_item < 0 or not (0 <= stream_id < 1 << 32) or kind < 0 or param < 0:
+            raise _cabi.DpfheError(2000, "sample_noise_: a 32-byte seed, a [batch...][components][L][N] tensor, component, first_item, kind and param >= 0")
+        comps = t.shape[-3]
+        batch = t.numel() // (comps * self.ctx.params.words_per_rns_poly())
+        _cabi.check(self._lib.dpfhe_sample_noise(self.ctx.handle, t.data_ptr(), batch, comps, int(component), int(kind), int(param), int(stream_id), seed,
+                                                 int(first_item), _cabi.NOISE_ADD if add else 0, self._sp(stream)), "dpfhe_sample_noise")
+        return t
+
+    def rerandomize_(self, ct: torch.Tensor, pk: torch.Tensor, flood_bits: int, seed: bytes, first_item: int = 0, stream=None) -> torch.Tensor:
+        """in place: ct [batch][2][L][N] (coefficient domain) += a fresh encryption of zero under pk [2][L][N] (NTT domain) whose c0 error is uniform
+        on [-2^flood_bits, 2^flood_bits) (dpfhe_rerandomize).  Allocates its 3 batch L N words of scratch from torch's caching allocator.  The
+        seed is SECRET and serves one call only; flood_bits from the caller's public noise bound."""
+        self._chk(ct, pk)
+        p = self.ctx.params
+        seed = bytes(seed)
+        if len(seed) != 32 or ct.dim() != 4 or ct.shape[1] != 2 or ct.shape[0] == 0 or tuple(pk.shape) != (2, p.n_limbs, p.n) or first_item < 0 or flood_bits < 0:
+            raise _cabi.DpfheError(2000, "rerandomize_: a 32-byte seed, a [batch][2][L][N] ciphertext tensor (batch >= 1) and a [2][L][N] public key")
+        work = self._empty((ct.shape[0], 3, p.n_limbs, p.n), stream)
+        _cabi.check(self._lib.dpfhe_rerandomize(self.ctx.handle, ct.data_ptr(), pk.data_ptr(), ct.shape[0], int(flood_bits), seed, int(first_item),
+                                                work.data_ptr(), self._sp(stream)), "dpfhe_rerandomize")
+        return ct
+
     # ---- exact plaintext addition (include/dpfhe.h dpfhe_add_plain_scaled) ----------------------------------------------------------
     def add_plain_scaled_(self, ct: torch.Tensor, plain: torch.Tensor, t: int, negate: bool = False, stream=None) -> torch.Tensor:
         """in place: ct [batch][comps][L][N] (comps 2 or 3, exact BFV-style, coefficient domain) gets c0 += round(Q b / t) mod q_l (-= with negate)

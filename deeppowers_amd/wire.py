@@ -85,6 +85,32 @@ def expand_host(params: FheParams, batch: int, components: int, component: int, 
     return out
 
 
+def noise_host(params: FheParams, batch: int, components: int, component: int, kind: int, param: int, stream_id: int, seed: bytes,
+               first_item: int = 0, add: bool = False, out: np.ndarray | None = None) -> np.ndarray:
+    """Host twin of dpfhe_sample_noise (include/dpfhe.h): component `component` of items 0 .. batch-1 of `out` ([batch][components][L][N] uint64,
+    zeros when None) = noise(seed, first_item + b, stream_id, kind, param), or += it mod q with add; the other words are left as they are.
+    kind 0 ternary, 1 centred binomial (eta = 21), 2 flood on [-2^param, 2^param).  The seed is SECRET and serves one call only."""
+    import ctypes as C
+
+    from . import _cabi
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    if not (0 <= component < components) or batch < 1 or first_item < 0 or first_item + batch > 1 << 32 or not (0 <= stream_id < 1 << 32):
+        raise ValueError("component must be < components, batch >= 1, first_item + batch <= 2^32, stream_id a u32")
+    if kind not in (0, 1, 2) or (kind == 2 and not (1 <= param <= 250)):
+        raise ValueError("kind 0, 1 or 2; flood bits in [1, 250]")
+    if out is None:
+        out = np.zeros((batch, components, params.n_limbs, params.n), dtype=np.uint64)
+    if out.dtype != np.uint64 or not out.flags.c_contiguous or out.shape != (batch, components, params.n_limbs, params.n):
+        raise ValueError("out must be a contiguous uint64 array [batch][components][L][N]")
+    lib = _cabi.load()
+    m = (C.c_uint64 * params.n_limbs)(*params.moduli)
+    _cabi.check(lib.dpfhe_sample_noise_host(m, params.n_limbs, params.log2_n, out.ctypes.data, batch, components, component, kind, int(param) if kind == 2 else 0,
+                                            stream_id, seed, first_item, _cabi.NOISE_ADD if add else 0), "dpfhe_sample_noise_host")
+    return out
+
+
 def dumps_seeded(words: np.ndarray, params: FheParams, is_ntt: bool, seed: bytes, component: int = 1, first_item: int = 0,
                  verify: bool = True) -> bytes:
     """words: uint64 [batch][components][L][N] whose component `component` is expand(seed, first_item + b, ., component).  That component is

@@ -444,6 +444,36 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// Re-randomised results (include/dpfhe.h dpfhe_rerandomize): before a result leaves the server, add a fresh public-key
+// encryption of zero  (u pk0 + e0, u pk1 + e1)  whose c0 error e0 is uniform on [-2^flood_bits, 2^flood_bits): it drowns the noise the circuit left,
+// which is a function of the server's weights and the client - who holds the secret key - could otherwise read.  Order: evaluate -> rerandomize ->
+// Evaluator::compact.  The noise comes from ChaCha20 on the device under a SECRET 32-byte seed drawn fresh for every call (OS CSPRNG) and never stored.
+// What is claimed is the usual flooding argument against a client that follows the protocol, given a correct PUBLIC noise bound; nothing is claimed
+// against malformed input ciphertexts, and timing and sizes still show the circuit's shape.
+class Rerandomizer {
+public:
+    // pk: the client's public key on ctx (KeyGenerator::create_public_key); ctx and pk must outlive the object
+    Rerandomizer(const Context& ctx, const PublicKey& pk);
+    Rerandomizer(const Context& ctx, const PublicKey& pk, TestSeed seed);   // deterministic seeds - tests only
+    ~Rerandomizer();
+    Rerandomizer(const Rerandomizer&) = delete;
+    Rerandomizer& operator=(const Rerandomizer&) = delete;
+    // in place on ct (2 components, coefficient domain, encrypt_exact-style with plaintext modulus t); enqueues on `stream`.  The work buffer belongs to
+    // the object: grown when a larger batch arrives, never shrunk, so steady-state calls allocate nothing (one rerandomize() at a time per object).
+    // INVALID_ARGUMENT for a 3-component or NTT-domain ciphertext, a ciphertext of another context, or flood_bits outside [1, max_flood_bits(t)].
+    void rerandomize(Ciphertext& ct, uint64_t plain_modulus, unsigned flood_bits, Stream* stream = nullptr);
+    // floor(log2 Q) - ceil(log2 t) - 4 (at most 250): beyond it less than about two bits of budget would remain, which is what compact needs
+    unsigned max_flood_bits(uint64_t plain_modulus) const;
+    // ceil(noise_bits) + lambda + log2_n: a shift by |v_old| <= 2^B moves a uniform value on [-2^f, 2^f) by statistical distance 2^(B - f - 1) per
+    // coefficient; over N coefficients that is at most 2^-lambda.  noise_bits is the caller's PUBLIC bound B for the circuit (log2 Q - 1 - log2 t minus
+    // the budget its noise model guarantees): the library does not and cannot measure noise on the server.
+    static unsigned flood_bits_for(double noise_bits, unsigned log2_n, unsigned lambda = 40);
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
 // Hybrid key switching with one special prime P (SURVEY.md 8f N1 "base extension"): keys live on the extended
 // context (data moduli + P) and the switching noise drops from ~ L N q sigma to ~ L N q sigma / P.
 class HybridKeySwitcher {

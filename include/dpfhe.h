@@ -366,6 +366,42 @@ int dpfhe_encode_slots(dpfhe_encoder* enc, uint64_t* d_out, const uint32_t* d_sl
 int dpfhe_encode_slots_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t t, uint64_t* out, const uint32_t* slots, size_t items,
                             uint32_t flags);
 
+/* -- re-randomised results: noise polynomials from a SECRET seed, and a fresh public-key encryption of zero with a flooding error added to result
+ * ciphertexts before they leave the server (order: evaluate -> dpfhe_rerandomize -> dpfhe_compact).
+ * Definition.  noise(seed, item, stream_id, kind, param) is a polynomial of N SIGNED INTEGERS v_k; every limb of the output holds the same integer as its
+ *   canonical residue v_k mod q_limb in [0, q_limb).  Coefficient k takes the ChaCha20 block (RFC 8439 section 2.3) with key = the 32-byte seed (8
+ *   little-endian words), 32-bit block counter k >> 1 and nonce = (u32 item, u32 stream_id, u32 0x6b73616d), and of that block the output words
+ *   8 (k & 1) .. 8 (k & 1) + 7 read as ONE 256-bit little-endian integer X.  (The third nonce word keeps these streams apart from expand(seed, item, limb,
+ *   component), component < 3, even if a caller misuses one seed for both.)
+ *     DPFHE_NOISE_TERNARY:  v = floor(3 (X mod 2^64) / 2^64) - 1                                   bias at most 2^-63 per coefficient, no rejection
+ *     DPFHE_NOISE_CBD21:    v = popcount(X & 0x1fffff) - popcount((X >> 21) & 0x1fffff)             centred binomial, eta = 21: sigma = 3.24, |v| <= 21
+ *     DPFHE_NOISE_FLOOD:    v = (X mod 2^(f + 1)) - 2^f,  f = param, 1 <= f <= 250                  exactly uniform on [-2^f, 2^f)
+ *   The words do not depend on the limbs' arithmetic classes.  The seed is SECRET: it is a kernel argument and is never written to memory or to a
+ *   stream.  One seed must never serve two calls: equal masks would make the difference of two results equal the difference of their inputs.
+ * dpfhe_sample_noise: component `comp` of items 0 .. batch-1 of d_out [batch][comps][L][N] = noise(seed, first_item + b, stream_id, kind, param), or
+ *   += noise mod q_limb with DPFHE_NOISE_ADD; every other word is untouched.  Enqueues only (no allocation, no synchronise).  DPFHE_INVALID_ARGUMENT,
+ *   nothing written, on a null pointer, batch 0, a misaligned buffer, kind > 2, f outside [1, 250], comp >= comps, an unknown flag bit,
+ *   first_item + batch > 2^32, or a batch too large for one launch.  param is ignored for the other two kinds.
+ * dpfhe_sample_noise_host: the same words on the host (no device, no context; moduli odd, >= 3 and < 2^60, log2_n in [8, 16]).
+ * dpfhe_rerandomize: in place on `batch` 2-component coefficient-domain ciphertexts d_ct2 [batch][2][L][N]; d_pk = [2][L][N], NTT domain (a public key
+ *   (-(a s) + e, a)); d_work: 3 batch L N words of scratch.  Word for word, with item = first_item + b:
+ *       u  = noise(seed, item, 0, TERNARY)           u^ = NTT(u)
+ *       e0 = noise(seed, item, 2, FLOOD, flood_bits)
+ *       e1 = noise(seed, item, 1, CBD21)
+ *       c0 += INTT(pk0 (.) u^) + e0                   c1 += INTT(pk1 (.) u^) + e1            (mod every q_limb)
+ *   Enqueues only (no allocation, no synchronise), every log2_n and limb class.  DPFHE_INVALID_ARGUMENT, nothing written, on a null pointer, batch 0,
+ *   a misaligned buffer, d_work / d_ct2 / d_pk overlapping, first_item + batch > 2^32, or flood_bits outside [1, min(250, floor(log2 Q) - 3)] (the mask
+ *   alone would wrap; the entry does not know the plaintext modulus - Rerandomizer in fhe.hpp applies the bound that leaves a decryptable result).
+ *   Three-component inputs are out of scope: relinearise first.  Nothing is claimed against malformed input ciphertexts. */
+enum { DPFHE_NOISE_TERNARY = 0u, DPFHE_NOISE_CBD21 = 1u, DPFHE_NOISE_FLOOD = 2u };
+enum { DPFHE_NOISE_ADD = 1u };
+int dpfhe_sample_noise(dpfhe_ctx* ctx, uint64_t* d_out, size_t batch, size_t comps, uint32_t comp, uint32_t kind, uint32_t param, uint32_t stream_id,
+                       const uint8_t seed[32], uint32_t first_item, uint32_t flags, void* stream);
+int dpfhe_sample_noise_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t comps, uint32_t comp,
+                            uint32_t kind, uint32_t param, uint32_t stream_id, const uint8_t seed[32], uint32_t first_item, uint32_t flags);
+int dpfhe_rerandomize(dpfhe_ctx* ctx, uint64_t* d_ct2, const uint64_t* d_pk, size_t batch, uint32_t flood_bits, const uint8_t seed[32],
+                      uint32_t first_item, uint64_t* d_work, void* stream);
+
 const char* dpfhe_strerror(int code);
 /* text of the last HIP/RCCL failure on the calling thread ("" if none) */
 const char* dpfhe_last_error(void);
