@@ -1503,12 +1503,26 @@ extern "C" int dpfhe_reduce_sum(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d
     if (blocks * (size_t)chunks * splits > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_reduce_sum", "too many components for one launch");
     HIP_TRY(hipMemsetAsync(d_out, 0, words_per_item * sizeof(u64), s));   // after every validation: a rejected call leaves d_out untouched
     const unsigned poly_chunks = (unsigned)(blocks * chunks);
-    // two workgroups per CU walk the work items: as fast as an uncapped launch when alone (537 vs 551 us for 8192 x 3
-    // components at N=4096) and 2 % faster for the multiply it overlaps with in bench.py
-    unsigned grid = poly_chunks * splits;
-    if (count > 512 && grid > 2u * (unsigned)c->n_cu) grid = 2u * (unsigned)c->n_cu;   // short batches are latency-bound: no cap
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(grid), dim3(256), 0, s, d_out, d_in, c->lc, (int)c->n_limbs, n, chunks, count, words_per_item,
-                       poly_chunks, splits);
+    const unsigned items = poly_chunks * splits;
+    // The ONE place that picks the partial-sum kernel.  The large batches of the sharded multiply on all-fold limbs: reduce_thin_kernel, one workgroup
+    // per CU - the only placement that leaves both multiply workgroups of a CU resident while the reduce of the previous step runs beside them
+    // (kernels_misc.h; a second thin workgroup on a CU would not fit the registers either).  Everything else - short batches (latency-bound: no cap),
+    // the 32 rotated terms of a packed layer, limbs of another class: reduce_partial_kernel, as before.
+    if (c->fold && count > 512) {
+        const unsigned grid = items < (unsigned)c->n_cu ? items : (unsigned)c->n_cu;
+        const unsigned threads = n / 2 < 256 ? (unsigned)n / 2 : 256u;   // N = 256: half a chunk
+        unsigned log2_chunks = 0;
+        while ((1 << log2_chunks) < chunks) ++log2_chunks;
+        hipLaunchKernelGGL(reduce_thin_kernel, dim3(grid), dim3(threads), 0, s, d_out, d_in, c->lc, (unsigned)c->n_limbs, (unsigned)n, log2_chunks,
+                           count / splits, (unsigned)(count % splits), words_per_item, poly_chunks, splits);
+    } else {
+        // two workgroups per CU walk the work items: as fast as an uncapped launch when alone (537 vs 551 us for 8192 x 3
+        // components at N=4096) and 2 % faster for the multiply it overlaps with in bench.py
+        unsigned grid = items;
+        if (count > 512 && grid > 2u * (unsigned)c->n_cu) grid = 2u * (unsigned)c->n_cu;
+        hipLaunchKernelGGL(reduce_partial_kernel, dim3(grid), dim3(256), 0, s, d_out, d_in, c->lc, (int)c->n_limbs, n, chunks, count, words_per_item,
+                           poly_chunks, splits);
+    }
     if (int e = check_launch("reduce_sum partial kernel launch")) return e;
     hipLaunchKernelGGL(reduce_final_kernel, dim3((unsigned)(blocks * chunks)), dim3(256), 0, s, d_out, c->lc, (int)c->n_limbs, n, chunks);
     return check_launch("reduce_sum kernel launch");

@@ -5,6 +5,7 @@
 
 #include "launch.h"
 #include "modarith.h"
+#include "reduce_thin.h"
 
 namespace dpfhe {
 
@@ -136,6 +137,42 @@ __global__ __launch_bounds__(256) void reduce_partial_kernel(u64* out, const u64
             atomicAdd(reinterpret_cast<unsigned long long*>(out + p * n + w), (unsigned long long)s0);
             atomicAdd(reinterpret_cast<unsigned long long*>(out + p * n + w + 1), (unsigned long long)s1);
         }
+    }
+}
+
+// The same partial sums for the sharded multiply's batches (FoldArith limbs, count > 512), built to run BESIDE the fused multiply
+// instead of in its place: ct_mul_quad_kernel holds 2 x 240 of a SIMD lane's 512 registers, so a kernel of at most 32 registers, no
+// LDS and ONE workgroup per CU (the launcher's grid) is the only shape whose waves fit next to both multiply workgroups of a CU
+// (tests/test_reduce_thin_budget.py holds both budgets).  The lazy sums of reduce_thin.h are what make
+// 32 registers enough: five 16-byte loads in flight, two accumulators, one lane offset; everything else is wave-uniform.
+// Same work items, same atomics into the zeroed `out`, same reduce_final_kernel behind it.
+__global__ __launch_bounds__(256) void reduce_thin_kernel(u64* __restrict__ out, const u64* __restrict__ in, const LimbConst* __restrict__ lcs, unsigned n_limbs,
+                                                          unsigned n, unsigned log2_chunks, size_t per, unsigned rem, size_t words_per_item, unsigned poly_chunks,
+                                                          unsigned nsplit) {
+    // launched with min(256, N / 2) threads: no thread is out of range, so every branch and every address part below is wave-uniform but this one
+    const unsigned lane = threadIdx.x * 16u;   // byte offset of the thread's two words inside a 512-word chunk
+    // split `s` sums items [s per + min(s, rem), (s + 1) per + min(s + 1, rem)); the workgroup walks (chunk, split) with stride gridDim.x, without a division
+    unsigned pc = blockIdx.x % poly_chunks, split = blockIdx.x / poly_chunks;
+    while (split < nsplit) {
+        const unsigned p = pc >> log2_chunks, w0 = (pc & ((1u << log2_chunks) - 1u)) * 512u;
+        const LimbConst lc = lcs[p % n_limbs];
+        const size_t lo = split * per + (split < rem ? split : rem), hi = (split + 1) * per + (split + 1 < rem ? split + 1 : rem);
+        const u64* src = in + (size_t)p * n + w0;
+        // (uniform base in scalar registers) + (the lane's 32-bit offset): a raw buffer load takes exactly that - as pointer arithmetic hipcc builds a 64-bit
+        // vector address per load (two registers and a v_lshl_add_u64 each: 48 registers instead of 32)
+        const U64x2 sum = thin_sum([&](size_t it) {
+            typedef unsigned v4u __attribute__((ext_vector_type(4)));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u64*>(src + it * words_per_item), 0, 0x7fffffff, 0x00020000);
+            const v4u t = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lane, 0, 0);
+            return U64x2{((u64)t.y << 32) | t.x, ((u64)t.w << 32) | t.z};
+        }, lo, hi, lc);
+        if (hi > lo) {
+            u64* o = reinterpret_cast<u64*>(reinterpret_cast<char*>(out + (size_t)p * n + w0) + lane);
+            atomicAdd(reinterpret_cast<unsigned long long*>(o), (unsigned long long)sum.a);
+            atomicAdd(reinterpret_cast<unsigned long long*>(o + 1), (unsigned long long)sum.b);
+        }
+        pc += gridDim.x;
+        while (pc >= poly_chunks) { pc -= poly_chunks; ++split; }
     }
 }
 
