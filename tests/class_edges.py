@@ -17,7 +17,8 @@ import functools
 
 import numpy as np
 
-from deeppowers_amd.params import is_prime, min_primitive_2n_root
+from deeppowers_amd.params import FheParams, is_prime, min_primitive_2n_root
+from oracle.cbind import Oracle
 
 FSCALED_KS = tuple(range(48, 60))
 SHOUP_ABOVE_KS = (50, 59)
@@ -114,3 +115,120 @@ def entry_class(name):
     if name.startswith("shoup"):
         return "shoup"
     return {"fold_edge": "fold", "fold_near": "fold", "f64_edge": "f64", "f64_wide_low": "f64_wide", "f64_wide_edge": "f64_wide", "smallest": "f64"}[name]
+
+
+# ---- the edge contexts of the GPU tests (tests/test_gpu_class_edges.py, tests/test_gpu_packed_stage_edges.py) and of their CPU counterparts --------------------
+CLASSES = ("fold", "f64", "fold_scaled", "f64_wide", "shoup")
+FSCALED_ORDER = (59, 56, 50, 58, 57, 55, 54, 53, 52, 51, 49, 48)   # edge primes of several shifts, the widest scaling first
+
+# the deployable hybrid shapes: kind -> (the data limbs, the catalogue entry whose first prime is the special prime P, the context's last limb)
+MIXED_P = {
+    "f64_under_fold": (lambda cat, first: list(cat["f64_edge"][:3]), "fold_edge"),
+    "fold_scaled_under_shoup": (lambda cat, first: [e for k in FSCALED_ORDER for e in first(f"fscaled_edge_{k}")][:3], "shoup60"),
+    "f64_wide_under_fold_scaled": (lambda cat, first: list(cat["f64_wide_edge"][:2]), "fscaled_edge_59"),
+    "shoup_under_f64": (lambda cat, first: list(cat["shoup60"][:2]), "f64_edge"),            # P narrower than the data
+    "fold_under_smallest": (lambda cat, first: list(cat["fold_edge"][:3]), "smallest"),      # fold data limbs that are not an all-fold context
+}
+MIXED_P_CLASSES = {
+    "f64_under_fold": ("f64",) * 3 + ("fold",),
+    "fold_scaled_under_shoup": ("fold_scaled",) * 3 + ("shoup",),
+    "f64_wide_under_fold_scaled": ("f64_wide",) * 2 + ("fold_scaled",),
+    "shoup_under_f64": ("shoup",) * 2 + ("f64",),
+    "fold_under_smallest": ("fold",) * 3 + ("f64",),
+}
+
+
+def edge_moduli(kind, log2n):
+    """the primes of an edge context: a uniform context of one class (2 - 4 primes nearest its bound), 'mixed' (one edge prime of every class plus
+    shoup60, fscaled_out_50 and the smallest prime), 'shoup60' (the matvec context: the widest generic-path primes), a MIXED_P kind (the deployable
+    hybrid shape: data limbs of one class under a special prime of another), or 'fold_scaled6' (five fold_scaled digits and a fold_scaled P)"""
+    cat = catalogue(log2n)
+    first = lambda name, i=0: [cat[name][i]] if name in cat and len(cat[name]) > i else []
+    if kind == "fold":
+        ps = list(cat["fold_edge"][:4])
+    elif kind == "f64":
+        ps = list(cat["f64_edge"][:3]) + first("smallest")
+    elif kind == "fold_scaled":
+        ps = [e for k in FSCALED_ORDER for e in first(f"fscaled_edge_{k}")][:4]
+    elif kind == "f64_wide":
+        ps = list(cat["f64_wide_edge"][:2]) + list(cat["f64_wide_low"][:2])
+    elif kind == "shoup":
+        ps = list(cat["shoup60"][:2]) + first("shoup_above_59") + first("shoup_above_50")
+    elif kind == "shoup60":
+        ps = list(cat["shoup60"][:2])
+    elif kind == "fold2":
+        ps = list(cat["fold_edge"][:2])
+    elif kind == "mixed":
+        ps = (first("fold_edge") + first("f64_edge") + first("fscaled_edge_59") + first("smallest") + first("shoup_above_50") + first("fscaled_out_50")
+              + first("shoup60") + first("f64_wide_low"))
+    elif kind in MIXED_P:
+        data, special = MIXED_P[kind]
+        ps = data(cat, first) + first(special)
+    elif kind == "smallest":      # q far below 2^32, below a large plaintext modulus and any flood value (the host-twinned device operations); without
+        ps = [e for e in cat["smallest"] if e[0] != 65537][:3]   # 65537 = 1 mod 2N itself: the packed layers' plaintext modulus must stay coprime to Q
+    elif kind == "fold_scaled6":
+        ps = [e for k in FSCALED_ORDER for e in first(f"fscaled_edge_{k}")][:4] + first("fscaled_edge_59", 1) + first("fscaled_edge_58", 1)
+    else:
+        raise ValueError(kind)
+    assert len(ps) >= 2 and len({q for q, _ in ps}) == len(ps), (kind, log2n)   # (fscaled_out_50 is f64_wide_edge's first prime: the mixture takes f64_wide_low)
+    return FheParams(log2n, tuple(q for q, _ in ps), tuple(w for _, w in ps))
+
+
+def reported_classes(p):
+    """what dpfhe_ctx_limb_class reports: the catalogue's class per limb where the context has per-limb classes (8 <= log2 N <= 14, L <= 16), the
+    context-wide policy otherwise (fold when every limb is 2^60 - d, shoup else)"""
+    want = tuple(expected_class(q) for q in p.moduli)
+    if all(c == "fold" for c in want):
+        return want
+    if p.log2_n > 14 or p.n_limbs > 16:
+        return ("shoup",) * p.n_limbs
+    return want
+
+
+class Rig:
+    def __init__(self, kind, log2n):
+        from deeppowers_amd.evaluator import Context, Evaluator
+        self.kind, self.p = kind, edge_moduli(kind, log2n)
+        self.L, self.n = self.p.n_limbs, self.p.n
+        self.orc = Oracle.from_params(self.p)
+        self.ctx = Context(self.p, 0)
+        self.ev = Evaluator(self.ctx)
+        self.qcol = np.array(self.p.moduli, np.uint64)[:, None]
+        assert self.ctx.limb_classes == reported_classes(self.p), (kind, log2n, self.ctx.limb_classes, [hex(q) for q in self.p.moduli])
+        if kind in CLASSES and log2n <= 14:
+            assert set(self.ctx.limb_classes) == {kind}
+        if kind == "mixed":
+            assert set(self.ctx.limb_classes) == set(CLASSES)
+        if kind in MIXED_P:
+            assert self.ctx.limb_classes == MIXED_P_CLASSES[kind], (kind, log2n, self.ctx.limb_classes)
+        if kind == "fold_scaled6":
+            assert self.ctx.limb_classes == ("fold_scaled",) * 6, (kind, log2n, self.ctx.limb_classes)
+
+    def dev(self, a):
+        from deeppowers_amd.evaluator import to_device
+        return to_device(np.ascontiguousarray(a), self.ctx.device)
+
+    def words(self, orc, lead, seed):
+        """orc.fill words shaped [*lead][L][N] with worst_case stripes in item 0 and q - 1 everywhere in item 1"""
+        count = int(np.prod(lead))
+        x = orc.fill(count, seed).reshape(tuple(lead) + (orc.L, orc.n))
+        qcol = np.array(orc.moduli, np.uint64)[:, None]
+        worst_case(x, qcol, orc.n)
+        if lead[0] > 1:
+            x[1] = qcol - np.uint64(1)
+        return x
+
+    def close(self):
+        self.ctx.close()
+
+
+def rescale_bsgs_reference(orc, data, t_qp, addends):
+    """dpfhe_rescale_bsgs from the oracle's parts (orc: the extended context, data: its first L - 1 limbs): round(t_qp / P), plus component 0 of every
+    addend, plus component 1 of addend 0.  t_qp [batch][2][L][N], addends [n_add][batch][2][L-1][N] -> [batch][2][L-1][N]"""
+    want = orc.rescale(t_qp)
+    for t in range(t_qp.shape[0]):
+        for a in range(addends.shape[0]):
+            want[t, 0] = data.dyadic("add", want[t, 0][None].copy(), addends[a, t, 0][None].copy())[0]
+        if addends.shape[0]:
+            want[t, 1] = data.dyadic("add", want[t, 1][None].copy(), addends[0, t, 1][None].copy())[0]
+    return want

@@ -17,6 +17,14 @@ def smallest_t(log2n):
     return t
 
 
+def largest_t(log2n):
+    """the largest prime below 2^32 that is 1 mod 2N"""
+    t = (1 << 32) - ((1 << 32) - 1) % (2 << log2n)
+    while not is_prime(t):
+        t -= 2 << log2n
+    return t
+
+
 def zeta_of(log2n, t):
     """g^((t-1)/2N) for the smallest g >= 2 for which it has order exactly 2N"""
     n = 1 << log2n
@@ -100,6 +108,15 @@ def slot_vectors(rng, n, t):
     v[5, n // 2 + int(rng.integers(0, n // 2))] = int(rng.integers(1, t))
     v[6] = int(rng.integers(1, t))
     return v
+
+
+def extreme_slot_vectors(rng, n, t):
+    """slot_vectors with the extreme values planted: 0, t - 1, (t - 1) / 2 and (t + 1) / 2 side by side in a random vector, and a vector of each of
+    the two half points in every slot"""
+    v = slot_vectors(rng, n, t)
+    edges = np.array([0, t - 1, (t - 1) // 2, (t + 1) // 2], dtype=np.uint32)
+    v[0, :4], v[0, n // 2: n // 2 + 4], v[1, -4:] = edges, edges[::-1], edges
+    return np.concatenate([v, np.full((1, n), (t - 1) // 2, np.uint32), np.full((1, n), (t + 1) // 2, np.uint32)])
 
 
 def t_values(log2n, big):

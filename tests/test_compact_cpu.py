@@ -105,6 +105,21 @@ def test_host_twin_matches_big_integer_definition(cls, L):
             assert np.array_equal(twin(p, words, bits0, bits1), reference(p, words, bits0, bits1)), (cls, L, log2n, bits0, bits1)
 
 
+def test_host_twin_matches_big_integer_definition_on_the_smallest_primes():
+    """every limb a smallest prime = 1 mod 2N (class_edges 'smallest': q below 2^18, Q below 2^52 - narrower than the widest record width): what
+    tests/test_gpu_compact.py's comparison at the catalogue's extremes rests on"""
+    from class_edges import edge_moduli
+    rng = np.random.default_rng(77)
+    for log2n in (8, 12):
+        p = edge_moduli("smallest", log2n)
+        assert max(p.moduli) < 1 << 18
+        for bits0, bits1 in WIDTHS:
+            words = random_words(rng, p, 2)
+            plant_edges(p, words, bits0, bits1)
+            words[1] = np.array(p.moduli, dtype=np.uint64)[None, :, None] - np.uint64(1)      # X = Q - 1 in every coefficient
+            assert np.array_equal(twin(p, words, bits0, bits1), reference(p, words, bits0, bits1)), (log2n, bits0, bits1)
+
+
 def test_host_twin_largest_ring():
     p = ntt_primes(16, 3, 60)
     rng = np.random.default_rng(16)

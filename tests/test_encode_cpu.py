@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from deeppowers_amd import _cabi
-from encode_ref import residues, slot_vectors, slots_by_evaluation, slots_by_transform, t_values, twin, zeta_of
+from encode_ref import (extreme_slot_vectors, largest_t, residues, slot_vectors, slots_by_evaluation, slots_by_transform, t_values, twin,
+                        zeta_of)
 from test_plain_add_cpu import PARAMS, big_prime_t
 from test_seeded_cpu import SENTINEL
 
@@ -73,6 +74,25 @@ def test_residue_output_is_the_centred_polynomial_mod_each_limb(name, items):
         got = twin(moduli, log2n, t, slots)
         assert np.array_equal(got, residues(plain, moduli, t)), (name, t)
         assert all(int(got[:, l].max()) < q for l, q in enumerate(moduli))
+
+
+def test_residue_output_on_the_smallest_primes_with_the_largest_t():
+    """every limb a smallest prime = 1 mod 2N (class_edges 'smallest': q far below t), t the largest prime below 2^32 that is 1 mod 2N, slots at 0,
+    t - 1, (t - 1) / 2 and (t + 1) / 2: the polynomial decodes to the slots, its residues are centred(m) mod q_l - what tests/test_gpu_encode.py's
+    comparison at the catalogue's extremes rests on"""
+    from class_edges import edge_moduli
+    for log2n in (8, 12):
+        p = edge_moduli("smallest", log2n)
+        t = largest_t(log2n)
+        assert max(p.moduli) < 1 << 18 and t > (1 << 32) - (1 << 20)
+        slots = extreme_slot_vectors(np.random.default_rng(log2n), p.n, t)
+        plain = twin(p.moduli, log2n, t, slots, plain=True)
+        zeta = zeta_of(log2n, t)
+        for i in range(slots.shape[0]):
+            assert np.array_equal(slots_by_evaluation(plain[i], log2n, t, zeta), slots[i].astype(np.uint64)), (log2n, i)
+        got = twin(p.moduli, log2n, t, slots)
+        assert np.array_equal(got, residues(plain, p.moduli, t)), log2n
+        assert all(int(got[:, l].max()) < q for l, q in enumerate(p.moduli))
 
 
 def test_host_twin_rejects_bad_arguments():

@@ -1,18 +1,31 @@
 """GPU: the baby-step / giant-step stages with the division by P deferred (include/dpfhe.h "N3, round 3") against the oracle's
-definition-form restatements - automorphisms in the coefficient domain, transforms afterwards - bit for bit, on FoldArith and on
-generic (Shoup) primes, with more than one 64-element launch group and several tokens."""
+definition-form restatements - automorphisms in the coefficient domain, transforms afterwards - bit for bit, on the pinned fold primes and
+on one context of fold_scaled and f64 primes, with more than one 64-element launch group and several tokens.  (The other classes, the class
+edges and data limbs under a special prime of another class: tests/test_gpu_packed_stage_edges.py.)"""
 import numpy as np
 import pytest
 
+from class_edges import expected_class
 from deeppowers_amd.params import FheParams, PRIMES_60, ntt_primes
 from oracle import pyoracle as po
 from oracle.cbind import Oracle
 
 pytestmark = pytest.mark.gpu
 
+MIXED_CLASSES = ("fold_scaled", "fold_scaled", "f64", "fold_scaled")   # what _params("mixed") runs on: no f64_wide and no shoup limb
+
+
+def _context(name, pe):
+    from deeppowers_amd.evaluator import Context
+    ctx = Context(pe, 0)
+    if name == "mixed":
+        assert ctx.limb_classes == MIXED_CLASSES
+    return ctx
+
 
 def _params(name):
-    if name == "mixed":   # generic primes: the Shoup kernels
+    if name == "mixed":   # not fold primes: the largest primes below 2^59, 2^50 and 2^58 are fold_scaled, the one below 2^33 is f64 (MIXED_CLASSES) -
+        # the key-switching kernels launch once per class, the one-pass kernels run the generic arithmetic on every limb
         n = 1024
 
         def gp(bits):
@@ -21,6 +34,7 @@ def _params(name):
                 q -= 2 * n
             return q
         qs = (gp(59), gp(50), gp(33), gp(58))
+        assert tuple(expected_class(q) for q in qs) == MIXED_CLASSES
         return FheParams(10, qs, tuple(po.min_primitive_2n_root(n, q) for q in qs))
     if name == "n4096":
         return FheParams(12, tuple(x[0] for x in PRIMES_60[:3]), tuple(x[1] for x in PRIMES_60[:3]))     # 2 data limbs + P
@@ -41,7 +55,7 @@ def test_rotate_hoisted_qp_bit_exact(name):
     orc = Oracle.from_params(pe)
     L, Ld, n = pe.n_limbs, pe.n_limbs - 1, pe.n
     data = Oracle(pe.log2_n, pe.moduli[:-1], pe.psi[:-1])
-    ctx = Context(pe, 0)
+    ctx = _context(name, pe)
     ev = Evaluator(ctx)
     for k, T in ((5, 1), (70, 3), (0, 2)):
         elts = [pow(3, i + 1, 2 * n) for i in range(k)]
@@ -69,7 +83,7 @@ def test_ntt_inverse_galois_bit_exact(name):
     pe = _params(name)
     orc = Oracle.from_params(pe)
     L, n = pe.n_limbs, pe.n
-    ctx = Context(pe, 0)
+    ctx = _context(name, pe)
     ev = Evaluator(ctx)
     for k, per in ((1, 1), (70, 3)):
         elts = [pow(3, 5 * i, 2 * n) for i in range(k)]     # includes g = 1 (the identity)
@@ -92,7 +106,7 @@ def test_switch_key_qp_bit_exact(name):
     orc = Oracle.from_params(pe)
     L, Ld, n = pe.n_limbs, pe.n_limbs - 1, pe.n
     data = Oracle(pe.log2_n, pe.moduli[:-1], pe.psi[:-1])
-    ctx = Context(pe, 0)
+    ctx = _context(name, pe)
     ev = Evaluator(ctx)
     for k, group in ((1, 3), (5, 1), (9, 4)):
         keys = orc.fill(k * Ld * 2, 821).reshape(k, Ld, 2, L, n)
@@ -115,7 +129,7 @@ def test_rescale_bsgs_and_the_whole_deferred_sum(name):
     orc = Oracle.from_params(pe)
     L, Ld, n = pe.n_limbs, pe.n_limbs - 1, pe.n
     data = Oracle(pe.log2_n, pe.moduli[:-1], pe.psi[:-1])
-    ctx = Context(pe, 0)
+    ctx = _context(name, pe)
     ev = Evaluator(ctx)
     n2, T = 6, 3
     rot = data.fill(n2 * T * 2, 831).reshape(n2, T, 2, Ld, n)

@@ -9,87 +9,10 @@ another class unseen."""
 import numpy as np
 import pytest
 
-from class_edges import catalogue, expected_class, worst_case
-from deeppowers_amd.params import FheParams
+from class_edges import CLASSES, Rig
 from oracle.cbind import Oracle
 
 pytestmark = pytest.mark.gpu
-
-CLASSES = ("fold", "f64", "fold_scaled", "f64_wide", "shoup")
-FSCALED_ORDER = (59, 56, 50, 58, 57, 55, 54, 53, 52, 51, 49, 48)   # edge primes of several shifts, the widest scaling first
-
-
-def edge_moduli(kind, log2n):
-    """the primes of an edge context: a uniform context of one class (2 - 4 primes nearest its bound), 'mixed' (one edge prime of every class plus
-    shoup60, fscaled_out_50 and the smallest prime), or 'shoup60' (the matvec context: the widest generic-path primes)"""
-    cat = catalogue(log2n)
-    first = lambda name, i=0: [cat[name][i]] if name in cat and len(cat[name]) > i else []
-    if kind == "fold":
-        ps = list(cat["fold_edge"][:4])
-    elif kind == "f64":
-        ps = list(cat["f64_edge"][:3]) + first("smallest")
-    elif kind == "fold_scaled":
-        ps = [e for k in FSCALED_ORDER for e in first(f"fscaled_edge_{k}")][:4]
-    elif kind == "f64_wide":
-        ps = list(cat["f64_wide_edge"][:2]) + list(cat["f64_wide_low"][:2])
-    elif kind == "shoup":
-        ps = list(cat["shoup60"][:2]) + first("shoup_above_59") + first("shoup_above_50")
-    elif kind == "shoup60":
-        ps = list(cat["shoup60"][:2])
-    elif kind == "fold2":
-        ps = list(cat["fold_edge"][:2])
-    elif kind == "mixed":
-        ps = (first("fold_edge") + first("f64_edge") + first("fscaled_edge_59") + first("smallest") + first("shoup_above_50") + first("fscaled_out_50")
-              + first("shoup60") + first("f64_wide_low"))
-    else:
-        raise ValueError(kind)
-    assert len(ps) >= 2 and len({q for q, _ in ps}) == len(ps), (kind, log2n)   # (fscaled_out_50 is f64_wide_edge's first prime: the mixture takes f64_wide_low)
-    return FheParams(log2n, tuple(q for q, _ in ps), tuple(w for _, w in ps))
-
-
-def reported_classes(p):
-    """what dpfhe_ctx_limb_class reports: the catalogue's class per limb where the context has per-limb classes (8 <= log2 N <= 14, L <= 16), the
-    context-wide policy otherwise (fold when every limb is 2^60 - d, shoup else)"""
-    want = tuple(expected_class(q) for q in p.moduli)
-    if all(c == "fold" for c in want):
-        return want
-    if p.log2_n > 14 or p.n_limbs > 16:
-        return ("shoup",) * p.n_limbs
-    return want
-
-
-class Rig:
-    def __init__(self, kind, log2n):
-        from deeppowers_amd.evaluator import Context, Evaluator
-        self.kind, self.p = kind, edge_moduli(kind, log2n)
-        self.L, self.n = self.p.n_limbs, self.p.n
-        self.orc = Oracle.from_params(self.p)
-        self.ctx = Context(self.p, 0)
-        self.ev = Evaluator(self.ctx)
-        self.qcol = np.array(self.p.moduli, np.uint64)[:, None]
-        assert self.ctx.limb_classes == reported_classes(self.p), (kind, log2n, self.ctx.limb_classes, [hex(q) for q in self.p.moduli])
-        if kind in CLASSES and log2n <= 14:
-            assert set(self.ctx.limb_classes) == {kind}
-        if kind == "mixed":
-            assert set(self.ctx.limb_classes) == set(CLASSES)
-
-    def dev(self, a):
-        from deeppowers_amd.evaluator import to_device
-        return to_device(np.ascontiguousarray(a), self.ctx.device)
-
-    def words(self, orc, lead, seed):
-        """orc.fill words shaped [*lead][L][N] with worst_case stripes in item 0 and q - 1 everywhere in item 1"""
-        count = int(np.prod(lead))
-        x = orc.fill(count, seed).reshape(tuple(lead) + (orc.L, orc.n))
-        qcol = np.array(orc.moduli, np.uint64)[:, None]
-        worst_case(x, qcol, orc.n)
-        if lead[0] > 1:
-            x[1] = qcol - np.uint64(1)
-        return x
-
-    def close(self):
-        self.ctx.close()
-
 
 @pytest.fixture
 def rig(request):

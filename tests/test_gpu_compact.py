@@ -69,6 +69,16 @@ def test_device_matches_host_twin_limb_classes(name):
         _device_vs_twin(p, 3, b0, b1, seed=20 + i)
 
 
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_device_matches_host_twin_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py: one edge prime of every class and the smallest prime) and a context of smallest primes only
+    (Q below 2^52, narrower than the widest record), with the rounding boundaries planted"""
+    from class_edges import edge_moduli
+    p = edge_moduli(kind, log2n)
+    for i, (b0, b1) in enumerate(WIDTHS):
+        _device_vs_twin(p, 3, b0, b1, seed=40 + i)
+
+
 def test_device_entry_rejects_bad_arguments():
     import torch
     from deeppowers_amd.evaluator import Context, Evaluator

@@ -14,7 +14,7 @@ import pytest
 
 from deeppowers_amd import _cabi
 from deeppowers_amd.params import FheParams, min_primitive_2n_root, ntt_primes
-from encode_ref import slot_vectors, t_values, twin, zeta_of
+from encode_ref import extreme_slot_vectors, largest_t, slot_vectors, t_values, twin, zeta_of
 from test_plain_add_cpu import PARAMS, big_prime_t
 from test_seeded_cpu import SENTINEL
 
@@ -29,10 +29,12 @@ def _to_dev32(slots, device):
     return torch.from_numpy(np.ascontiguousarray(slots, dtype=np.uint32).view(np.int32)).to(device)
 
 
-def _device_vs_twin(p: FheParams, t, seed):
+def _device_vs_twin(p: FheParams, t, seed, slots=None, orc=None):
+    """slots: the vectors to encode (default: slot_vectors); orc: also hold the transformed output to this oracle's forward transform of the residues"""
     import torch
     from deeppowers_amd.evaluator import Context, Evaluator, to_host
-    slots = slot_vectors(np.random.default_rng(seed), p.n, t)
+    if slots is None:
+        slots = slot_vectors(np.random.default_rng(seed), p.n, t)
     want_plain, want_res = twin(p.moduli, p.log2_n, t, slots, plain=True), twin(p.moduli, p.log2_n, t, slots)
     ctx = Context(p, 0)
     try:
@@ -50,6 +52,8 @@ def _device_vs_twin(p: FheParams, t, seed):
         assert np.array_equal(to_host(got_res), want_res), (p.log2_n, t, "residues")
         assert np.array_equal(to_host(from_i64), want_res)
         assert torch.equal(got_ntt, fwd), (p.log2_n, t, "ntt")
+        if orc is not None:
+            assert np.array_equal(to_host(got_ntt), orc.ntt_fwd(want_res, threads=0)), (p.log2_n, t, "ntt against the oracle")
         assert np.array_equal(to_host(d_slots).view(np.uint32).reshape(slots.shape), slots)      # the input is untouched
     finally:
         ctx.close()
@@ -72,6 +76,19 @@ def test_device_matches_host_twin_limb_classes(name):
         ts = (65537, T_BIG)
     for i, t in enumerate(ts):
         _device_vs_twin(p, t, seed=7 + i)
+
+
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_device_matches_host_twin_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py) and a context of smallest primes only (every q far below t), t the largest prime below 2^32
+    that is 1 mod 2N, slots at 0, t - 1, (t - 1) / 2 and (t + 1) / 2 (the sign change of the centred lift): plain, residue and transformed output, the
+    last also against the oracle's forward transform of the twin's residues"""
+    from class_edges import edge_moduli
+    from oracle.cbind import Oracle
+    p = edge_moduli(kind, log2n)
+    t = largest_t(log2n)
+    assert t > (1 << 32) - (1 << 20) and (t - 1) % (2 * p.n) == 0
+    _device_vs_twin(p, t, seed=log2n, slots=extreme_slot_vectors(np.random.default_rng(log2n), p.n, t), orc=Oracle.from_params(p))
 
 
 def test_full_size_layer_and_second_stream():

@@ -61,6 +61,42 @@ def test_device_matches_host_twin_limb_classes(name):
         _device_vs_twin(p, 6, 2 + i % 2, (1, 6, 3)[i], t, bool(i % 2), seed=10 + i)
 
 
+def _device_and_twin_refuse(p: FheParams, t):
+    """t shares a factor with a modulus: the host twin and the device entry both refuse (DPFHE_INVALID_ARGUMENT) and the ciphertext keeps its words"""
+    from deeppowers_amd.evaluator import Context, Evaluator, to_device, to_host
+    rng = np.random.default_rng(t)
+    ct, plain = random_ct(rng, p, 2, 2), random_plain(rng, 1, p.n, t)
+    with pytest.raises(_cabi.DpfheError) as e:
+        twin(p, ct, plain, t)
+    assert e.value.code == 2000
+    ctx = Context(p, 0)
+    try:
+        d_ct, d_plain = to_device(ct, ctx.device), to_device(plain, ctx.device)
+        assert ctx._lib.dpfhe_add_plain_scaled(ctx.handle, d_ct.data_ptr(), d_ct.data_ptr(), d_plain.data_ptr(), 2, 2, 1, t, 0, None) == 2000
+        with pytest.raises(_cabi.DpfheError):
+            Evaluator(ctx).add_plain_scaled_(d_ct, d_plain, t)
+        assert np.array_equal(to_host(d_ct), ct)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_device_matches_host_twin_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py) and a context of smallest primes only (every q far below 2^32), with t just below 2^32 and
+    t = 65537.  At N = 8192 the smallest prime = 1 mod 2N is 65537 itself and the mixture holds it as a limb: there t = 65537 must be refused by the
+    twin and by the device, and the neighbouring 65539 is added instead."""
+    from class_edges import edge_moduli
+    p = edge_moduli(kind, log2n)
+    assert (65537 in p.moduli) == (kind == "mixed" and log2n == 13)
+    for i, t in enumerate((T_PRIME_BIG, 65537)):
+        assert t > (1 << 32) - (1 << 20) or t == 65537
+        if t in p.moduli:
+            _device_and_twin_refuse(p, t)
+            t = 65539
+        assert all(t % q for q in p.moduli)
+        _device_vs_twin(p, 4, 2 + i, (1, 2)[i], t, bool(i), seed=30 + i)
+
+
 def test_full_size_in_place():
     """8192 items x N = 4096 x L = 4, broadcast plaintext, in place: the first and last 64 items and three zero items in between == host twin"""
     import torch

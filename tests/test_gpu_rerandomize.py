@@ -91,6 +91,21 @@ def test_device_matches_host_twin_limb_classes(name):
     _with_ctx(p, lambda ctx: _device_vs_twin(ctx, p, _all_kinds(3, 0)))
 
 
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_device_matches_host_twin_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py) and a context of smallest primes only (every q below 2^18, far below a flood value): ternary,
+    centred binomial, and flood at 1, 64 and 250 bits, set and added (q - 1 in every word of the last item)"""
+    from class_edges import edge_moduli
+    p = edge_moduli(kind, log2n)
+    cases = []
+    for add in (False, True):
+        cases.append((3, 2, 1, TERNARY, 0, 0, 5, add))
+        cases.append((3, 3, 0, CBD21, 0, 1, 5, add))
+        for i, f in enumerate((1, 64, 250)):
+            cases.append((3, 2 + i % 2, i % 2, FLOOD, f, 2, 5, add))
+    _with_ctx(p, lambda ctx: _device_vs_twin(ctx, p, cases))
+
+
 def test_more_limbs_than_one_launch_group():
     p = ntt_primes(8, 19, 60)
     _with_ctx(p, lambda ctx: _device_vs_twin(ctx, p, [(3, 2, 1, FLOOD, 200, 2, 3, False), (3, 2, 0, CBD21, 0, 1, 0, True), (1, 1, 0, TERNARY, 0, 0, 9, False)]))
@@ -118,14 +133,32 @@ def _rerandomize_ref(p: FheParams, ct, pk, flood_bits, seed, first_item):
 @pytest.mark.parametrize("log2n", [8, 12, 13, 14, 16])
 @pytest.mark.parametrize("name", ["pinned60", "mixed", "primes31"])
 def test_rerandomize_equals_its_definition(name, log2n):
+    p = {"pinned60": lambda: ntt_primes(log2n, 4, 60), "mixed": lambda: mixed_params(log2n), "primes31": lambda: ntt_primes(log2n, 3, 31)}[name]()
+    _rerandomize_vs_definition(p, {"pinned60": 200, "mixed": 130, "primes31": 64}[name], (name, log2n))
+
+
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_rerandomize_equals_its_definition_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py) with the widest flood, 250 bits, and a context of smallest primes only with the widest flood
+    its Q admits (floor(log2 Q) - 3 bits, far above every q): the ciphertext and the key carry q - 1 in every word of one item / component"""
+    import math
+    from class_edges import edge_moduli
+    p = edge_moduli(kind, log2n)
+    flood_bits = min(250, math.prod(p.moduli).bit_length() - 1 - 3)
+    assert flood_bits == 250 or (kind == "smallest" and flood_bits > 40)
+    _rerandomize_vs_definition(p, flood_bits, (kind, log2n), extreme=True)
+
+
+def _rerandomize_vs_definition(p, flood_bits, what, extreme=False):
     import torch
     from deeppowers_amd.evaluator import Evaluator, to_device, to_host
-    p = {"pinned60": lambda: ntt_primes(log2n, 4, 60), "mixed": lambda: mixed_params(log2n), "primes31": lambda: ntt_primes(log2n, 3, 31)}[name]()
+    name, log2n = what
     batch, first_item = 3, 11
-    flood_bits = {"pinned60": 200, "mixed": 130, "primes31": 64}[name]
     rng = np.random.default_rng(log2n)
     ct = _random_words(rng, p, batch, 2)
     pk = _random_words(rng, p, 1, 2)[0]
+    if extreme:
+        ct[1] = pk[1] = (np.array(p.moduli, dtype=np.uint64) - np.uint64(1))[:, None]
     want = _rerandomize_ref(p, ct, pk, flood_bits, SEED, first_item)
 
     def run(ctx):

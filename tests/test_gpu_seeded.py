@@ -51,6 +51,17 @@ def test_device_matches_host_twin_limb_classes(name):
         _device_vs_twin(p, 5, comps, comp, first)
 
 
+@pytest.mark.parametrize("kind,log2n", [(k, ln) for k in ("mixed", "smallest") for ln in (12, 13)])
+def test_device_matches_host_twin_at_the_catalogue_extremes(kind, log2n):
+    """the all-class edge mixture (tests/class_edges.py: its fourth limb is the smallest prime = 1 mod 2N) and a context of smallest primes only: a
+    128-bit X reduced into a q below 2^18 next to 2^60 - d"""
+    from class_edges import edge_moduli
+    p = edge_moduli(kind, log2n)
+    assert min(p.moduli) < 1 << 18
+    for comps, comp, first in ((2, 1, 0), (3, 0, (1 << 31) + 5), (3, 2, 7)):
+        _device_vs_twin(p, 5, comps, comp, first)
+
+
 def test_full_size_split_launches_and_host_twin():
     """8192 items x N = 4096 x L = 4: one launch == two launches over item ranges (first_item 0 and 4096); the first 1024 items == host twin"""
     import torch

@@ -94,6 +94,24 @@ def test_twin_matches_definition(name, t):
         assert np.array_equal(got[:, 1:], ct[:, 1:])                          # components >= 1 untouched
 
 
+@pytest.mark.parametrize("t", (65537, T_PRIME_BIG))
+def test_twin_matches_definition_on_the_smallest_primes(t):
+    """every limb a smallest prime = 1 mod 2N (class_edges 'smallest'): q far below 2^32 and, for the large t, far below t, so
+    round(Q b / t) wraps each limb many times over - what tests/test_gpu_plain_add.py's comparison at the catalogue's extremes rests on"""
+    from class_edges import edge_moduli
+    for log2n in (8, 12):
+        p = edge_moduli("smallest", log2n)
+        assert min(p.moduli) < t and max(p.moduli) < 1 << 18 and all(t % q for q in p.moduli)
+        rng = np.random.default_rng(t % 1000 + log2n)
+        for batch, comps, items, negate in ((2, 2, 1, False), (4, 3, 2, True)):
+            ct = random_ct(rng, p, batch, comps)
+            ct[-1] = np.array(p.moduli, dtype=np.uint64)[None, :, None] - np.uint64(1)
+            plain = random_plain(rng, items, p.n, t)
+            got = twin(p, ct, plain, t, negate)
+            assert np.array_equal(got, reference(p, ct, plain, t, negate)), (log2n, t, batch, comps, items, negate)
+            assert np.array_equal(got[:, 1:], ct[:, 1:])
+
+
 def test_twin_in_place_out_of_place_and_sentinel():
     p = PARAMS["mixed"]()
     rng = np.random.default_rng(5)

@@ -92,6 +92,20 @@ def test_host_twin_matches_restatement_parameter_sets(name):
             _check(p, 1, 2, 0, FLOOD, f, 2, first)
 
 
+def test_host_twin_matches_restatement_on_the_smallest_primes():
+    """every limb a smallest prime = 1 mod 2N (class_edges 'smallest'): q below 2^18, so a flood value of 64 or 250 bits is reduced from far above q -
+    what tests/test_gpu_rerandomize.py's comparison at the catalogue's extremes rests on"""
+    from class_edges import edge_moduli
+    for log2n in (8, 12):
+        p = edge_moduli("smallest", log2n)
+        assert max(p.moduli) < 1 << 18
+        first = FIRST_ITEMS[log2n % 2]
+        _check(p, 2, 2, 1, TERNARY, 0, 0, first)
+        _check(p, 2, 3, 0, CBD21, 0, 1, first)
+        for f in (1, 64, 250):
+            _check(p, 1, 2, 0, FLOOD, f, 2, first)
+
+
 def test_more_limbs_than_one_launch_group():
     p = ntt_primes(8, 19, 60)                                              # the limb constants travel 16 limbs at a time
     _check(p, 2, 2, 1, FLOOD, 200, 2, 3)

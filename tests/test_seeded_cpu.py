@@ -168,6 +168,17 @@ def test_host_twin_matches_restatement_limb_classes(name):
         _check(p, 2, comps, comp, first)
 
 
+def test_host_twin_matches_restatement_on_the_smallest_primes():
+    """every limb a smallest prime = 1 mod 2N (class_edges 'smallest'): a 128-bit X reduced into a q below 2^18 - what tests/test_gpu_seeded.py's
+    comparison at the catalogue's extremes rests on"""
+    from class_edges import edge_moduli
+    for log2n in (8, 12):
+        p = edge_moduli("smallest", log2n)
+        assert max(p.moduli) < 1 << 18
+        for comps, comp, first in ((2, 1, 0), (3, 0, (1 << 31) + 5)):
+            _check(p, 2, comps, comp, first)
+
+
 def test_prefix_property_on_a_dropped_limb_level():
     full = ntt_primes(12, 4, 60)
     lower = full.drop_last_limb()
