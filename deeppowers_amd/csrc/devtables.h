@@ -1,10 +1,25 @@
-// devtables.h - device-side table handles passed to the kernels by value.
+// devtables.h - device-side table handles passed to the kernels by value, and the constants that shape the tables.
+// No HIP: the host-side builder (ctx_tables.h) and tools/emulate.cpp read it as plain C++.
 #pragma once
 #include "modarith.h"
 
 namespace dpfhe {
 
 struct QuartersTop;   // ntt_quarters.h
+
+// ---- the geometry constants that shape the tables (the launchers read them through launch.h) ----
+// words-per-thread exponent of the batched NTT kernels (launch_impl.h DPFHE_GEO_SWITCH); the fused kernels use 4.
+// ctx_tables.h builds a second table layout whenever the two differ.
+// (N = 8192 was measured with 32 words per thread / 3 phases and with 16 / 4 phases: same time, the kernels are VALU-bound;
+// 16 everywhere keeps one twiddle layout per context)
+// N = 16384 (128 KiB of LDS per polynomial): 1024 threads, one workgroup per CU (16 words per thread measured 5 % faster
+// than 32 on the forward transform); the fused kernels stop at N = 8192.
+constexpr int ntt_loge(int /*log2n*/) { return 4; }   // (32 words per thread at N = 4096 measured equal to slower - round 4 A/B, closed)
+constexpr int kMaxLog2N = 16;
+// N > 16384: split transform - log2(N1) top stages in ntt_top_kernel, then N1 transforms of N2 = 4096 points each
+constexpr int kSplitLog2N2 = 12;
+constexpr int split_log_n1(int log2n) { return log2n > 14 ? log2n - kSplitLog2N2 : 0; }
+constexpr int kFusedLoge = 4;   // words-per-thread exponent of the fused kernels (8 per thread measured slower - round 3 A/B, closed)
 
 template <class Tw>
 struct InvLast {  // per limb: last inverse stage twiddles with N^-1 folded in
@@ -13,7 +28,7 @@ struct InvLast {  // per limb: last inverse stage twiddles with N^-1 folded in
 };
 
 // Twiddle tables are stored in the layout of the kernel geometry that reads them (tables.h permute_window0):
-// fwd/inv for the batched NTT kernels (launch.h ntt_loge), fwd4/inv4 for the fused kernels, which always run 16
+// fwd/inv for the batched NTT kernels (ntt_loge above), fwd4/inv4 for the fused kernels, which always run 16
 // words per thread.  The two coincide unless the NTT geometry is not LOGE = 4 (N = 8192).
 template <class Arith>
 struct DevTables {
@@ -66,7 +81,7 @@ DPF_HD void block_item_limb(const TB& tb, size_t blk, size_t& item, int& limb) {
     }
 }
 
-// the batched transforms' view of a context with per-limb arithmetic classes (kernels.h ntt_classes_kernel, dpfhe_cabi.hip mixed_layout)
+// the batched transforms' view of a context with per-limb arithmetic classes (kernels.h ntt_classes_kernel, ctx_tables.h mixed_layout)
 struct MixedTables {
     const void* fwd;            // [L][N] twiddles, slot l in limb l's format, kernel layout of the batched transforms
     const void* inv;
@@ -74,6 +89,14 @@ struct MixedTables {
     const LimbConst* lc;        // [L], each as its class reads it (tables.h limb_const_of_class)
     int n_limbs;
     unsigned long long cls_map; // 4 bits per limb: tables.h LimbClass
+};
+
+// per limb below the last: the constants of the rescale / modulus switch to the next level (kernels_misc.h rescale_kernel), relative to the LAST prime
+struct RescaleConst {
+    u64 h_mod;     // floor(q_last / 2) mod q_i
+    u64 inv;       // q_last^-1 mod q_i
+    u64 q_last;
+    u64 h;         // floor(q_last / 2)
 };
 
 }  // namespace dpfhe

@@ -17,12 +17,12 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/dpfhe.h"
 #include "base_ext.h"
 #include "compact.h"
+#include "ctx_tables.h"
 #include "encode.h"
 #include "expand.h"
 #include "noise.h"
@@ -30,8 +30,6 @@
 #include "kernels_large.h"
 #include "kernels_misc.h"
 #include "launch.h"
-#include "ntt_core.h"
-#include "ntt_quarters.h"
 #include "tables.h"
 
 using namespace dpfhe;
@@ -262,123 +260,13 @@ extern "C" const char* dpfhe_ct_mul_variant_name(int variant) {
     return variant >= 0 && variant < kCtMulVariants ? kCtMulVariantNames[variant] : "";
 }
 
-// ------------------------------------------------------------------------------------------------
-// Tables of a context with per-limb arithmetic classes (round 6): ONE blob, LimbConst[L] | fwd4 | inv4 | (fwd | inv when the batched transforms use another
-// layout) | last[L] | last2[L], every per-limb slot in the format of that limb's class (all twiddle types are 16 bytes: the strides agree).  The classes'
-// DevTables are typed views of the same blob, each with its own active-limb map.  Single-kernel transforms only (log2 N <= 14).
-static_assert(sizeof(TwShoup) == 16 && sizeof(TwFold) == 16 && sizeof(TwF64) == 16, "the per-limb slots of the mixed tables share one stride");
-struct MixedLayout { size_t o_lc, o_fwd4, o_inv4, o_fwd, o_inv, o_last, o_last2, total; };
-static MixedLayout mixed_layout(int log2n, size_t L) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t n = (size_t)1 << log2n, tab = L * n * 16;
-    const bool two_geo = ntt_loge(log2n) != kFusedLoge;
-    MixedLayout m;
-    m.o_lc = 0; m.o_fwd4 = up(L * sizeof(LimbConst)); m.o_inv4 = up(m.o_fwd4 + tab);
-    m.o_fwd = two_geo ? up(m.o_inv4 + tab) : m.o_fwd4; m.o_inv = two_geo ? up(m.o_fwd + tab) : m.o_inv4;
-    m.o_last = up(m.o_inv + tab); m.o_last2 = up(m.o_last + L * 32); m.total = up(m.o_last2 + L * 32);
-    return m;
-}
-template <class Tw, class MakeTw>
-static void fill_mixed_limb(std::vector<unsigned char>& blob, const MixedLayout& m, int log2n, size_t l, const HostLimbTables& t, LimbClass cls, MakeTw make_tw) {
-    static_assert(sizeof(Tw) == 16 && sizeof(InvLast<Tw>) == 32, "slot sizes");
-    const size_t n = (size_t)1 << log2n;
-    const u64 q = t.lc.q;
-    const LimbConst lc = limb_const_of_class(t.lc, cls);
-    std::memcpy(&blob[m.o_lc + l * sizeof(LimbConst)], &lc, sizeof(LimbConst));
-    auto pack = [&](const std::vector<u64>& words, int loge, size_t off) {
-        std::vector<Tw> tw(words.size());
-        for (size_t i = 0; i < words.size(); ++i) tw[i] = make_tw(words[i], q);
-        permute_window0(tw, log2n, loge, geo_perm_stages(log2n, loge));
-        std::memcpy(&blob[off], tw.data(), tw.size() * sizeof(Tw));
-    };
-    pack(t.rp, kFusedLoge, m.o_fwd4 + l * n * 16);
-    pack(t.irp, kFusedLoge, m.o_inv4 + l * n * 16);
-    if (m.o_fwd != m.o_fwd4) { pack(t.rp, ntt_loge(log2n), m.o_fwd + l * n * 16); pack(t.irp, ntt_loge(log2n), m.o_inv + l * n * 16); }
-    reinterpret_cast<InvLast<Tw>*>(&blob[m.o_last])[l] = InvLast<Tw>{make_tw(t.w_last, q), make_tw(t.lc.ninv, q)};
-    // products of two scaled words carry s = 2^(60-k) twice: their inverse transform ends on twiddles with s^-1 folded in (DevTables::last2)
-    const u64 sinv = cls == kClassFoldScaled ? h_powmod((1ull << fold_scaled_shift(q)) % q, q - 2, q) : 1;
-    reinterpret_cast<InvLast<Tw>*>(&blob[m.o_last2])[l] = InvLast<Tw>{make_tw(h_mulmod(t.w_last, sinv, q), q), make_tw(h_mulmod(t.lc.ninv, sinv, q), q)};
-}
-template <class Arith>
-static DevTables<Arith> mixed_view(const unsigned char* b, const MixedLayout& m, size_t L) {
-    typedef typename Arith::Tw Tw;
-    DevTables<Arith> tb{};
-    tb.lc = reinterpret_cast<const LimbConst*>(b + m.o_lc);
-    tb.fwd = reinterpret_cast<const Tw*>(b + m.o_fwd); tb.inv = reinterpret_cast<const Tw*>(b + m.o_inv);
-    tb.fwd4 = reinterpret_cast<const Tw*>(b + m.o_fwd4); tb.inv4 = reinterpret_cast<const Tw*>(b + m.o_inv4);
-    tb.last = reinterpret_cast<const InvLast<Tw>*>(b + m.o_last);
-    tb.last2 = reinterpret_cast<const InvLast<Tw>*>(b + m.o_last2);
-    tb.n_sub = 1;
-    tb.n_limbs = (int)L;
-    return tb;
-}
-
-// Tables of the context-wide arithmetic (FoldArith or ShoupArith, every limb): ONE blob of 256-byte aligned sections.  One twiddle table pair per kernel
-// geometry in use: slot 0 = the fused kernels' LOGE 4 layout, slot 1 = the batched NTT kernels' layout when that differs.  Split transforms (N > 16384)
-// store, per limb, n_sub tables of N2 points (sub-trees of the full table) plus the top-stage twiddles.  FoldArith at N = 8192 / 16384 adds the "halves" /
-// "quarters" tables next to the one-piece ones (ntt_halves.h / ntt_quarters.h; the fused kernels keep the one-piece layout); elsewhere their offsets are
-// the end of the blob and their pointers stay null.
-struct CtxLayout {
-    int log_n1, log_n2, loge_ntt;
-    size_t n_sub, n2, tw_sz;
-    bool split, two_geo, halves, quarters;
-    size_t o_lc, o_fwd4, o_inv4, o_fwd, o_inv, o_last, o_top_fwd, o_top_inv, o_top_last, o_resc, o_hfwd, o_hinv, o_htop_fwd, o_htop_last,
-           o_qfwd, o_qinv, o_qtop_fwd, o_qtop_inv, o_qtop_last, total;
-};
-static CtxLayout ctx_layout(int log2n, size_t L, bool fold) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    CtxLayout m;
-    m.tw_sz = fold ? sizeof(TwFold) : sizeof(TwShoup);
-    m.log_n1 = split_log_n1(log2n); m.log_n2 = log2n - m.log_n1;
-    m.n_sub = (size_t)1 << m.log_n1; m.n2 = (size_t)1 << m.log_n2;
-    m.loge_ntt = ntt_loge(m.log_n2);
-    m.split = m.log_n1 > 0; m.two_geo = !m.split && m.loge_ntt != kFusedLoge;
-    m.halves = log2n == 13 && fold;     // the halves tables (launch.h): large batched transforms at N = 8192
-    m.quarters = log2n == 14 && fold;   // four sub-tree tables per limb + the column stages' twiddles
-    const size_t tw_sz = m.tw_sz, n_sub = m.n_sub, tab = L * ((size_t)1 << log2n) * tw_sz;
-    m.o_lc = 0; m.o_fwd4 = up(m.o_lc + L * sizeof(LimbConst)); m.o_inv4 = up(m.o_fwd4 + tab);
-    m.o_fwd = m.two_geo ? up(m.o_inv4 + tab) : m.o_fwd4; m.o_inv = m.two_geo ? up(m.o_fwd + tab) : m.o_inv4;
-    m.o_last = up(m.o_inv + tab); m.o_top_fwd = up(m.o_last + L * n_sub * 2 * tw_sz); m.o_top_inv = up(m.o_top_fwd + L * n_sub * tw_sz);
-    m.o_top_last = up(m.o_top_inv + L * n_sub * tw_sz); m.o_resc = up(m.o_top_last + L * 2 * tw_sz);
-    const bool h = m.halves, qu = m.quarters;
-    m.o_hfwd = up(m.o_resc + L * sizeof(RescaleConst)); m.o_hinv = h ? up(m.o_hfwd + tab) : m.o_hfwd; m.o_htop_fwd = h ? up(m.o_hinv + tab) : m.o_hfwd;
-    m.o_htop_last = h ? up(m.o_htop_fwd + L * tw_sz) : m.o_hfwd;
-    const size_t o_q0 = h ? up(m.o_htop_last + L * 2 * tw_sz) : m.o_hfwd;
-    m.o_qfwd = o_q0; m.o_qinv = qu ? up(m.o_qfwd + tab) : o_q0; m.o_qtop_fwd = qu ? up(m.o_qinv + tab) : o_q0;
-    m.o_qtop_inv = qu ? up(m.o_qtop_fwd + L * sizeof(QuartersTop)) : o_q0; m.o_qtop_last = qu ? up(m.o_qtop_inv + L * 2 * tw_sz) : o_q0;
-    m.total = qu ? up(m.o_qtop_last + L * 2 * tw_sz) : o_q0;
-    return m;
-}
-template <class Arith>
-static DevTables<Arith> ctx_view(const unsigned char* d, const CtxLayout& m, size_t L) {
-    typedef typename Arith::Tw Tw;
-    DevTables<Arith> tb{};
-    tb.lc = reinterpret_cast<const LimbConst*>(d + m.o_lc);
-    tb.fwd = reinterpret_cast<const Tw*>(d + m.o_fwd); tb.inv = reinterpret_cast<const Tw*>(d + m.o_inv);
-    tb.fwd4 = reinterpret_cast<const Tw*>(d + m.o_fwd4); tb.inv4 = reinterpret_cast<const Tw*>(d + m.o_inv4);
-    tb.last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_last);
-    tb.top_fwd = reinterpret_cast<const Tw*>(d + m.o_top_fwd); tb.top_inv = reinterpret_cast<const Tw*>(d + m.o_top_inv);
-    tb.top_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_top_last);
-    tb.n_sub = (int)m.n_sub;
-    tb.n_limbs = (int)L;
-    if (m.quarters) {
-        tb.qfwd = reinterpret_cast<const Tw*>(d + m.o_qfwd); tb.qinv = reinterpret_cast<const Tw*>(d + m.o_qinv);
-        tb.qtop_fwd = reinterpret_cast<const QuartersTop*>(d + m.o_qtop_fwd); tb.qtop_inv = reinterpret_cast<const Tw*>(d + m.o_qtop_inv);
-        tb.qtop_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_qtop_last);
-    }
-    if (m.halves) {
-        tb.hfwd = reinterpret_cast<const Tw*>(d + m.o_hfwd); tb.hinv = reinterpret_cast<const Tw*>(d + m.o_hinv);
-        tb.htop_fwd = reinterpret_cast<const Tw*>(d + m.o_htop_fwd); tb.htop_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_htop_last);
-    }
-    return tb;
-}
-
+// the tables of a context: built on the host by ctx_tables.h (layouts, blobs, typed views), uploaded and viewed on the device here
 extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_limbs, const uint64_t* moduli,
                                 const uint64_t* psi, int device_id) {
     if (!out || !moduli || !psi) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_create", "null argument");
     if (log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_create", "log2_n must be in [8, 16]");
     if (n_limbs == 0 || n_limbs > 1024) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_create", "n_limbs must be in [1, 1024]");
-    const size_t n = (size_t)1 << log2_n, L = n_limbs;
+    const size_t L = n_limbs;
     std::vector<HostLimbTables> ht(L);
     bool fold = true;
     for (size_t l = 0; l < L; ++l) {
@@ -403,76 +291,7 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->n_cu = cus; }
 
     const CtxLayout lay = ctx_layout((int)log2_n, L, fold);
-    const size_t tw_sz = lay.tw_sz, n_sub = lay.n_sub, n2 = lay.n2;
-    std::vector<unsigned char> blob(lay.total, 0);
-    auto fill = [&](auto tw_tag) {
-        typedef decltype(tw_tag) Tw;
-        for (size_t l = 0; l < L; ++l) {
-            const u64 q = moduli[l];
-            auto pack = [&](const std::vector<u64>& words, int logn_tab, int loge, size_t off) {   // one N-point table in kernel layout
-                std::vector<Tw> t(words.size());
-                for (size_t i = 0; i < words.size(); ++i) t[i] = h_make_tw<Tw>(words[i], q);
-                permute_window0(t, logn_tab, loge, geo_perm_stages(logn_tab, loge));
-                std::memcpy(&blob[off], t.data(), t.size() * sizeof(Tw));
-            };
-            InvLast<Tw>* lasts = reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_last]);
-            if (!lay.split) {
-                for (int geo = 0; geo < (lay.two_geo ? 2 : 1); ++geo) {
-                    const int loge = geo ? lay.loge_ntt : kFusedLoge;
-                    pack(ht[l].rp, (int)log2_n, loge, (geo ? lay.o_fwd : lay.o_fwd4) + l * n * tw_sz);
-                    pack(ht[l].irp, (int)log2_n, loge, (geo ? lay.o_inv : lay.o_inv4) + l * n * tw_sz);
-                }
-                lasts[l] = InvLast<Tw>{h_make_tw<Tw>(ht[l].w_last, q), h_make_tw<Tw>(ht[l].lc.ninv, q)};
-                if constexpr (std::is_same<Tw, TwFold>::value) {
-                    if (lay.quarters) {
-                        for (size_t r = 0; r < 4; ++r) {
-                            pack(subtree_table(ht[l].rp, 14, 2, r), 12, 4, lay.o_qfwd + (l * 4 + r) * (n / 4) * tw_sz);
-                            pack(subtree_table(ht[l].irp, 14, 2, r), 12, 4, lay.o_qinv + (l * 4 + r) * (n / 4) * tw_sz);
-                        }
-                        reinterpret_cast<QuartersTop*>(&blob[lay.o_qtop_fwd])[l] = QuartersTop{h_tw_fold(ht[l].rp[1], q), h_tw_fold(ht[l].rp[2], q), h_tw_fold(ht[l].rp[3], q)};
-                        reinterpret_cast<TwFold*>(&blob[lay.o_qtop_inv])[2 * l] = h_tw_fold(ht[l].irp[2], q);
-                        reinterpret_cast<TwFold*>(&blob[lay.o_qtop_inv])[2 * l + 1] = h_tw_fold(ht[l].irp[3], q);
-                        reinterpret_cast<InvLast<TwFold>*>(&blob[lay.o_qtop_last])[l] = InvLast<TwFold>{h_tw_fold(ht[l].w_last, q), h_tw_fold(ht[l].lc.ninv, q)};
-                    }
-                }
-                if (lay.halves) {
-                    for (size_t r = 0; r < 2; ++r) {
-                        pack(subtree_table(ht[l].rp, 13, 1, r), 12, 4, lay.o_hfwd + (l * 2 + r) * (n / 2) * tw_sz);
-                        pack(subtree_table(ht[l].irp, 13, 1, r), 12, 4, lay.o_hinv + (l * 2 + r) * (n / 2) * tw_sz);
-                    }
-                    reinterpret_cast<Tw*>(&blob[lay.o_htop_fwd])[l] = h_make_tw<Tw>(ht[l].rp[1], q);
-                    reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_htop_last])[l] = lasts[l];   // the column stage IS the one-piece transform's last stage
-                }
-            } else {
-                for (size_t r = 0; r < n_sub; ++r) {
-                    const std::vector<u64> f = subtree_table(ht[l].rp, (int)log2_n, lay.log_n1, r), v = subtree_table(ht[l].irp, (int)log2_n, lay.log_n1, r);
-                    pack(f, lay.log_n2, lay.loge_ntt, lay.o_fwd + (l * n_sub + r) * n2 * tw_sz);
-                    pack(v, lay.log_n2, lay.loge_ntt, lay.o_inv + (l * n_sub + r) * n2 * tw_sz);
-                    // generic primes: no N^-1 inside a block.  FoldArith: the block's last stage divides its sums by N2 exactly (FoldArith::mul_ninv),
-                    // so its differences carry N2^-1 in their twiddle; the column stage then multiplies by N1^-1 (top_last below)
-                    const u64 n2inv = std::is_same<Tw, TwFold>::value ? h_powmod((u64)n2 % q, q - 2, q) : 1;
-                    lasts[l * n_sub + r] = InvLast<Tw>{h_make_tw<Tw>(h_mulmod(v[1], n2inv, q), q), h_make_tw<Tw>(1, q)};
-                }
-                Tw* tf = reinterpret_cast<Tw*>(&blob[lay.o_top_fwd]) + l * n_sub;
-                Tw* tv = reinterpret_cast<Tw*>(&blob[lay.o_top_inv]) + l * n_sub;
-                for (size_t i = 1; i < n_sub; ++i) { tf[i] = h_make_tw<Tw>(ht[l].rp[i], q); tv[i] = h_make_tw<Tw>(ht[l].irp[i], q); }
-                // FoldArith sub-transforms divide by their own length N2 in their last stage (ntt_core.h: FoldArith::mul_ninv, exact division), so the
-                // column stage multiplies by N1^-1 = N^-1 N2 only; generic-prime sub-transforms multiply by 1 there and the column stage by N^-1
-                const u64 up = std::is_same<Tw, TwFold>::value ? (u64)n2 % q : 1;
-                reinterpret_cast<InvLast<Tw>*>(&blob[lay.o_top_last])[l] = InvLast<Tw>{h_make_tw<Tw>(h_mulmod(ht[l].w_last, up, q), q), h_make_tw<Tw>(h_mulmod(ht[l].lc.ninv, up, q), q)};
-            }
-        }
-    };
-    for (size_t l = 0; l < L; ++l) std::memcpy(&blob[lay.o_lc + l * sizeof(LimbConst)], &ht[l].lc, sizeof(LimbConst));
-    if (fold) fill(TwFold{}); else fill(TwShoup{});
-    {   // rescale constants relative to the LAST prime (used only when L >= 2)
-        const u64 ql = moduli[L - 1], hh = ql / 2;
-        RescaleConst* r = reinterpret_cast<RescaleConst*>(&blob[lay.o_resc]);
-        for (size_t l = 0; l + 1 < L; ++l) {
-            const u64 q = moduli[l];
-            r[l].h_mod = hh % q; r[l].inv = h_powmod(ql % q, q - 2, q); r[l].q_last = ql; r[l].h = hh;
-        }
-    }
+    const std::vector<unsigned char> blob = build_ctx_blob((int)log2_n, ht, fold);
     // both table uploads; a failed one frees what exists, restores the caller's device and reports `stage`
     auto upload = [&](void*& dst, const std::vector<unsigned char>& host, const char* stage) -> int {
         hipError_t e = hipMalloc(&dst, host.size());
@@ -489,36 +308,25 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
     if (fold) c->foldt = ctx_view<FoldArith>(d, lay, L);
     else c->shoup = ctx_view<ShoupArith>(d, lay, L);
     // per-limb arithmetic classes of a non-uniform context (see dpfhe_ctx::classes)
-    if (!fold && L <= 16 && log2_n >= 8 && log2_n <= 14) {
-        bool any_fast = false;
-        for (size_t l = 0; l < L; ++l) { c->limb_cls[l] = (unsigned char)limb_class(moduli[l]); any_fast = any_fast || c->limb_cls[l] != kClassShoup; }
-        if (any_fast) {
-            const MixedLayout m = mixed_layout((int)log2_n, L);
-            std::vector<unsigned char> mb(m.total, 0);
-            for (size_t l = 0; l < L; ++l) {
-                const LimbClass k = (LimbClass)c->limb_cls[l];
-                c->cls_map |= (unsigned long long)k << (4 * l);
-                if (k == kClassFold) fill_mixed_limb<TwFold>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_tw_fold(w, q); });
-                else if (k == kClassF64 || k == kClassF64Wide) fill_mixed_limb<TwF64>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_make_tw<TwF64>(w, q); });
-                else if (k == kClassFoldScaled) fill_mixed_limb<TwFold>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_tw_fold_scaled(w, q, fold_scaled_shift(q)); });
-                else fill_mixed_limb<TwShoup>(mb, m, (int)log2_n, l, ht[l], k, [](u64 w, u64 q) { return h_make_tw<TwShoup>(w, q); });
-            }
-            if (int rc = upload(c->class_blob, mb, "dpfhe_ctx_create: class table upload")) return rc;
-            const unsigned char* b = static_cast<const unsigned char*>(c->class_blob);
-            c->cls_fold = mixed_view<FoldArith>(b, m, L);
-            c->cls_f64 = mixed_view<F64Arith>(b, m, L);
-            c->cls_fscaled = mixed_view<FoldScaledArith>(b, m, L);
-            c->cls_f64w = mixed_view<F64WideArith>(b, m, L);
-            c->cls_shoup = mixed_view<ShoupArith>(b, m, L);
-            c->mixed.fwd = b + m.o_fwd; c->mixed.inv = b + m.o_inv; c->mixed.last = b + m.o_last;
-            c->mixed.lc = reinterpret_cast<const LimbConst*>(b + m.o_lc);
-            c->mixed.n_limbs = (int)L;
-            c->mixed.cls_map = c->cls_map;
-            c->classes = true;
-            bool same = true;
-            for (size_t l = 1; l < L; ++l) same = same && c->limb_cls[l] == c->limb_cls[0];
-            if (same) c->uniform_cls = c->limb_cls[0];
-        }
+    if (ctx_limb_classes((int)log2_n, ht, fold, c->limb_cls)) {
+        const MixedLayout m = mixed_layout((int)log2_n, L);
+        const std::vector<unsigned char> mb = build_class_blob((int)log2_n, ht, c->limb_cls);
+        for (size_t l = 0; l < L; ++l) c->cls_map |= (unsigned long long)c->limb_cls[l] << (4 * l);
+        if (int rc = upload(c->class_blob, mb, "dpfhe_ctx_create: class table upload")) return rc;
+        const unsigned char* b = static_cast<const unsigned char*>(c->class_blob);
+        c->cls_fold = mixed_view<FoldArith>(b, m, L);
+        c->cls_f64 = mixed_view<F64Arith>(b, m, L);
+        c->cls_fscaled = mixed_view<FoldScaledArith>(b, m, L);
+        c->cls_f64w = mixed_view<F64WideArith>(b, m, L);
+        c->cls_shoup = mixed_view<ShoupArith>(b, m, L);
+        c->mixed.fwd = b + m.o_fwd; c->mixed.inv = b + m.o_inv; c->mixed.last = b + m.o_last;
+        c->mixed.lc = reinterpret_cast<const LimbConst*>(b + m.o_lc);
+        c->mixed.n_limbs = (int)L;
+        c->mixed.cls_map = c->cls_map;
+        c->classes = true;
+        bool same = true;
+        for (size_t l = 1; l < L; ++l) same = same && c->limb_cls[l] == c->limb_cls[0];
+        if (same) c->uniform_cls = c->limb_cls[0];
     }
     tune_at_create(c);   // default form of the fused multiply, or a cached explicit probe of this shape: no device work
     (void)hipSetDevice(prev);

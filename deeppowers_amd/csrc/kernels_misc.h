@@ -618,12 +618,7 @@ __global__ __launch_bounds__(256) void matvec_scalar_kernel(u64* y, const u64* w
 // N1 (second half): rescale / modulus switch to the next level, coefficient domain.
 //   out_i = ((in_i + h) - ((in_last + h) mod q_last)) * q_last^-1   (mod q_i),  h = floor(q_last / 2),  i < L-1
 // i.e. round(x / q_last) of the CRT-composed value, limb by limb (no big integers).  HBM-bound.
-struct RescaleConst {
-    u64 h_mod;     // floor(q_last / 2) mod q_i
-    u64 inv;       // q_last^-1 mod q_i
-    u64 q_last;
-    u64 h;         // floor(q_last / 2)
-};
+// (RescaleConst: devtables.h)
 
 // `addend` (optional) is the last step of hybrid key switching: polynomial p = 2*b + comp of the rescaled pair gets
 // component comp of ciphertext b of `addend` ([batch][add_in_comps][L-1][N]) added when bit comp of add_mask is set.

@@ -7,18 +7,8 @@
 
 namespace dpfhe {
 
-// words-per-thread exponent of the batched NTT kernels (launch_impl.h DPFHE_GEO_SWITCH); the fused kernels use 4.
-// dpfhe_ctx_create builds a second table layout whenever the two differ.
-// (N = 8192 was measured with 32 words per thread / 3 phases and with 16 / 4 phases: same time, the kernels are VALU-bound;
-// 16 everywhere keeps one twiddle layout per context)
-// N = 16384 (128 KiB of LDS per polynomial): 1024 threads, one workgroup per CU (16 words per thread measured 5 % faster
-// than 32 on the forward transform); the fused kernels stop at N = 8192.
-constexpr int ntt_loge(int /*log2n*/) { return 4; }   // (32 words per thread at N = 4096 measured equal to slower - round 4 A/B, closed)
-constexpr int kMaxLog2N = 16, kMaxFusedLog2N = 13;
-// N > 16384: split transform - log2(N1) top stages in ntt_top_kernel, then N1 transforms of N2 = 4096 points each
-constexpr int kSplitLog2N2 = 12;
-constexpr int split_log_n1(int log2n) { return log2n > 14 ? log2n - kSplitLog2N2 : 0; }
-constexpr int kFusedLoge = 4;   // words-per-thread exponent of the fused kernels (8 per thread measured slower - round 3 A/B, closed)
+// (ntt_loge, kFusedLoge, kMaxLog2N, kSplitLog2N2, split_log_n1 - the constants that also shape the tables - are in devtables.h)
+constexpr int kMaxFusedLog2N = 13;
 // N = 8192 on the N = 4096 body ("halves": ntt_halves.h, kernels_halves.h - a register column stage + two 4096-point sub-transforms through one LDS
 // buffer, 256-thread workgroups, three to a CU).  Round 5, measured (profiles/r05_ntt13_batch_sweep.txt, r05_ntt_workgroup_timelines.txt, r05_halves_*.txt):
 //  * batched transforms: 2.5-9 % FASTER than the 512-thread kernels from 384 RNS polynomials (2304 workgroups) up - the 512-thread kernel keeps only 1.7 of

@@ -3,12 +3,15 @@ thread-by-thread emulator (tools/emulate.cpp) and checks it bit for bit against 
 Covers every geometry the C-ABI dispatches, both arithmetic policies, both directions, extreme
 inputs, and counts 64-bit wrap-arounds of the lazy (uncorrected) arithmetic - must be zero."""
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import class_edges
 from deeppowers_amd.params import PRIMES_60, PRIME_30, PSI_30_N1024, ntt_primes
 from oracle import pyoracle as po
 from oracle.cbind import Oracle
@@ -21,7 +24,7 @@ U = C.POINTER(C.c_uint64)
 def emu():
     so = os.path.join(ROOT, "tools", "libemu.so")
     src = os.path.join(ROOT, "tools", "emulate.cpp")
-    deps = [src] + [os.path.join(ROOT, "deeppowers_amd", "csrc", f) for f in ("ntt_core.h", "ntt_top.h", "ntt_halves.h", "ntt_quarters.h", "modarith.h", "tables.h")]
+    deps = [src] + [os.path.join(ROOT, "deeppowers_amd", "csrc", f) for f in ("ntt_core.h", "ntt_top.h", "ntt_halves.h", "ntt_quarters.h", "modarith.h", "tables.h", "ctx_tables.h", "devtables.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src])   # (F64Arith: nothing fused behind the explicit fma calls)
     lib = C.CDLL(so)
@@ -299,3 +302,88 @@ def test_emulated_fold_products_through_the_twiddle_chain(emu):
                 for add in adds:
                     assert emu.emu_fold_ptw(d, y, b, add) == (add + y * b) % q, (d, y, b, add)
     assert emu.emu_overflows() == before, "the chain wrapped around 2^64"
+
+
+# ---- whole contexts: the tables dpfhe_ctx_create uploads (csrc/ctx_tables.h), every limb ------------------------------------------------------------------------
+ONE_PIECE, HALVES, QUARTERS, GENERIC = 0, 1, 2, 3   # tools/emulate.cpp emu_ctx_ntt's `form`
+
+
+def _pinned(ln, limbs):
+    n = 1 << ln
+    qs = [PRIMES_60[i][0] for i in limbs]
+    return qs, [pow(PRIMES_60[i][2], 8192 // n, q) if ln <= 13 else po.min_primitive_2n_root(n, q) for i, q in zip(limbs, qs)]
+
+
+def _fold_primes_n32768():
+    """two fold primes = 1 mod 2^16, found as test_emulated_split_transform_matches_oracle finds its one"""
+    n = 1 << 15
+    qs = [c for c in ((1 << 60) - (k * 2 * n - 1) for k in range(1, 1 << (24 - 15 - 1))) if c % (2 * n) == 1 and po.is_prime(c)][:2]
+    return qs, [po.min_primitive_2n_root(n, q) for q in qs]
+
+
+def _params(p, count=None):
+    return list(p.moduli[:count]), list(p.psi[:count])
+
+
+CTX_CASES = {
+    "fold_n4096": (12, lambda: _pinned(12, (0, 3, 5)), (ONE_PIECE,)),
+    "fold_n8192": (13, lambda: _pinned(13, (0, 2, 5)), (ONE_PIECE, HALVES)),
+    "fold_n16384": (14, lambda: _pinned(14, (1, 2, 4)), (ONE_PIECE, QUARTERS)),
+    "fold_n32768": (15, _fold_primes_n32768, (ONE_PIECE, GENERIC)),          # (the split transform; GENERIC: the same two on ShoupArith tables)
+    "mixed_n4096": (12, lambda: _params(class_edges.edge_moduli("mixed", 12)), (ONE_PIECE,)),
+    "f64_n4096": (12, lambda: _params(ntt_primes(12, 3, 40)), (ONE_PIECE,)),
+    "fold_scaled_n4096": (12, lambda: _params(class_edges.edge_moduli("fold_scaled", 12), 3), (ONE_PIECE,)),
+}
+CTX_CLASSES = {"fold_n4096": {"fold"}, "fold_n8192": {"fold"}, "fold_n16384": {"fold"}, "fold_n32768": {"fold"}, "mixed_n4096": set(class_edges.CLASSES),
+               "f64_n4096": {"f64"}, "fold_scaled_n4096": {"fold_scaled"}}
+
+
+@pytest.mark.parametrize("name", list(CTX_CASES))
+def test_emulated_context_transforms_match_oracle_on_every_limb(emu, name):
+    """The transforms of a context of SEVERAL limbs, each limb on the tables csrc/ctx_tables.h builds for it - the bytes dpfhe_ctx_create uploads - read
+    with the kernels' own indexing: a wrong per-limb stride, sub-tree root, last-stage record or limb constant shows here, on the CPU.  Every limb, both
+    directions, a random polynomial and the all-(q - 1) one, against the oracle's single-limb transform; no 64-bit wrap of the lazy arithmetic."""
+    ln, primes, forms = CTX_CASES[name]
+    qs, psis = primes()
+    n, L = 1 << ln, len(qs)
+    assert L >= 2 and {class_edges.expected_class(q) for q in qs} == CTX_CLASSES[name]
+    emu.emu_ctx_ntt.argtypes = [C.c_int, C.c_int, U, U, C.c_int, C.c_int, C.c_int, U, U]
+    emu.emu_ctx_ntt.restype = C.c_int
+    m, w = np.array(qs, np.uint64), np.array(psis, np.uint64)
+    before = emu.emu_overflows()
+    for limb, (q, psi) in enumerate(zip(qs, psis)):
+        orc = Oracle(ln, [q], [psi])
+        for a in (orc.fill(1, 300 + limb).ravel().copy(), np.full(n, q - 1, np.uint64)):
+            a = np.ascontiguousarray(a, dtype=np.uint64)
+            want = (orc.ntt_fwd(a), orc.ntt_inv(a))
+            for form in forms:
+                for inv in (0, 1):
+                    out = np.zeros_like(a)
+                    rc = emu.emu_ctx_ntt(ln, L, m.ctypes.data_as(U), w.ctypes.data_as(U), limb, form, inv, a.ctypes.data_as(U), out.ctypes.data_as(U))
+                    assert rc == 0 and np.array_equal(out, want[inv]), (limb, form, inv)
+    assert emu.emu_overflows() == before, "lazy arithmetic wrapped around 2^64"
+
+
+with open(os.path.join(ROOT, "tests", "golden", "ctx_table_digests.json")) as _f:
+    CTX_DIGESTS = json.load(_f)
+
+
+@pytest.mark.parametrize("rec", CTX_DIGESTS, ids=[r["name"] for r in CTX_DIGESTS])
+def test_context_table_blobs_keep_their_bytes(emu, rec):
+    """Every byte a context uploads is pinned: size and SHA-256 of the context-wide blob and of the class blob, and the class chosen per limb, for
+    contexts that reach every branch of the two layouts (tests/golden/ctx_table_digests.json, recorded from the construction code as it stood inside
+    dpfhe_ctx_create before it moved to csrc/ctx_tables.h)."""
+    B = C.POINTER(C.c_ubyte)
+    emu.emu_ctx_blob.argtypes = [C.c_int, C.c_int, U, U, C.c_int, B, C.c_size_t, B]
+    emu.emu_ctx_blob.restype = C.c_long
+    m, w = np.array(rec["moduli"], np.uint64), np.array(rec["psi"], np.uint64)
+    L = len(rec["moduli"])
+    for which, key in ((0, "ctx_blob"), (1, "class_blob")):
+        cls = np.zeros(16, np.uint8)
+        size = emu.emu_ctx_blob(rec["log2n"], L, m.ctypes.data_as(U), w.ctypes.data_as(U), which, None, 0, cls.ctypes.data_as(B))
+        assert size == (rec[key]["bytes"] if rec[key] else 0), key
+        assert [int(v) for v in cls[:L]] == rec["limb_cls"]
+        if rec[key]:
+            buf = np.zeros(size, np.uint8)
+            assert emu.emu_ctx_blob(rec["log2n"], L, m.ctypes.data_as(U), w.ctypes.data_as(U), which, buf.ctypes.data_as(B), size, cls.ctypes.data_as(B)) == size
+            assert hashlib.sha256(buf.tobytes()).hexdigest() == rec[key]["sha256"], key

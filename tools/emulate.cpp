@@ -8,63 +8,96 @@
 #include <cstring>
 #include <vector>
 
-#include "../deeppowers_amd/csrc/ntt_core.h"
+#include "../deeppowers_amd/csrc/ctx_tables.h"
 #include "../deeppowers_amd/csrc/ntt_halves.h"
-#include "../deeppowers_amd/csrc/ntt_quarters.h"
 #include "../deeppowers_amd/csrc/ntt_top.h"
-#include "../deeppowers_amd/csrc/tables.h"
 
 namespace dpfhe { long g_emu_overflows = 0; }
 using namespace dpfhe;
 extern "C" long emu_overflows() { return g_emu_overflows; }
 
-template <class Arith> struct TwTab;
-template <> struct TwTab<ShoupArith> {
-    static std::vector<TwShoup> make(const std::vector<u64>& w, const std::vector<u64>& sh, u64) {
-        std::vector<TwShoup> v(w.size());
-        for (size_t i = 0; i < w.size(); ++i) v[i] = TwShoup{w[i], sh[i]};
-        return v;
-    }
-    static TwShoup one(u64 w, u64 sh, u64) { return TwShoup{w, sh}; }
-};
-template <> struct TwTab<FoldArith> {
-    static std::vector<TwFold> make(const std::vector<u64>& w, const std::vector<u64>&, u64 q) {
-        std::vector<TwFold> v(w.size());
-        for (size_t i = 0; i < w.size(); ++i) v[i] = h_tw_fold(w[i], q);
-        return v;
-    }
-    static TwFold one(u64 w, u64, u64 q) { return h_tw_fold(w, q); }
-};
-
-// round 6: the per-limb classes' policies (tables.h limb_class).  class_lc() = the LimbConst their transform kernels read.
-template <> struct TwTab<F64Arith> {
-    static std::vector<TwF64> make(const std::vector<u64>& w, const std::vector<u64>&, u64 q) {
-        std::vector<TwF64> v(w.size());
-        for (size_t i = 0; i < w.size(); ++i) v[i] = h_make_tw<TwF64>(w[i], q);
-        return v;
-    }
-    static TwF64 one(u64 w, u64, u64 q) { return h_make_tw<TwF64>(w, q); }
-};
-template <> struct TwTab<F64WideArith> : TwTab<F64Arith> {};
-template <> struct TwTab<FoldScaledArith> {
-    static std::vector<TwFold> make(const std::vector<u64>& w, const std::vector<u64>&, u64 q) {
-        std::vector<TwFold> v(w.size());
-        for (size_t i = 0; i < w.size(); ++i) v[i] = h_tw_fold_scaled(w[i], q, fold_scaled_shift(q));
-        return v;
-    }
-    static TwFold one(u64 w, u64, u64 q) { return h_tw_fold_scaled(w, q, fold_scaled_shift(q)); }
-};
+// ---- the tables the emulated kernels read ----------------------------------------------------------------------------
+// Built by ctx_tables.h, the code dpfhe_ctx_create uploads from, and read through the same DevTables views with the kernels' own indexing
+// (limb and sub-tree strides included); the single-prime entry points below are the n_limbs = 1 case.
 template <class Arith> static bool class_ok(u64 q) {
     if (Arith::kFold) return fold_eligible(q);
     if constexpr (Arith::kF64) return q < (1ull << Arith::kMaxBits);
     if (Arith::kFoldCore) return fold_scaled_shift(q) != 0;
     return true;
 }
-template <class Arith> static LimbConst class_lc(const LimbConst& lc) {
-    return limb_const_of_class(lc, Arith::kFold ? kClassFold : Arith::kF64 ? kClassF64 : Arith::kFoldCore ? kClassFoldScaled : kClassShoup);   // (F64Wide reads F64's record)
+template <class Arith> static constexpr LimbClass class_of() {
+    if constexpr (Arith::kF64) return Arith::kMaxBits == F64Arith::kMaxBits ? kClassF64 : kClassF64Wide;
+    else return Arith::kFold ? kClassFold : Arith::kFoldCore ? kClassFoldScaled : kClassShoup;
+}
+// fn(Arith{}) on the policy of class `arith` (tables.h LimbClass)
+template <class Fn> static int with_arith(int arith, Fn fn) {
+    switch (arith) {
+        case kClassShoup: return fn(ShoupArith{});
+        case kClassFold: return fn(FoldArith{});
+        case kClassF64: return fn(F64Arith{});
+        case kClassFoldScaled: return fn(FoldScaledArith{});
+        case kClassF64Wide: return fn(F64WideArith{});
+        default: return -1;
+    }
 }
 
-template <class B> static constexpr int E_of() { return B::E; }
+template <class Arith> struct Tables {
+    std::vector<unsigned char> blob;   // the bytes a context would upload
+    DevTables<Arith> tb{};             // the kernels' view of them, over this host copy
+};
+static int limb_tables(int log2n, int n_limbs, const u64* moduli, const u64* psi, std::vector<HostLimbTables>& ht) {
+    ht.resize((size_t)n_limbs);
+    for (int l = 0; l < n_limbs; ++l) if (int rc = build_limb_tables(log2n, moduli[l], psi[l], ht[(size_t)l])) return rc;
+    return 0;
+}
+// the class blob with limb l on class limb_cls[l], seen as Arith's (DevTables of a context with per-limb classes: dpfhe_ctx::cls_*)
+template <class Arith>
+static void class_tables(int log2n, const std::vector<HostLimbTables>& ht, const unsigned char* limb_cls, Tables<Arith>& t) {
+    t.blob = build_class_blob(log2n, ht, limb_cls);
+    t.tb = mixed_view<Arith>(t.blob.data(), mixed_layout(log2n, ht.size()), ht.size());
+}
+// The tables of a context that runs EVERY limb on Arith - the policy under test, whatever tables.h limb_class would choose: the context-wide blob for
+// FoldArith / ShoupArith, the class blob for the other classes.  2000: a prime the policy does not take.
+template <class Arith>
+static int policy_tables(int log2n, const std::vector<HostLimbTables>& ht, Tables<Arith>& t) {
+    for (const HostLimbTables& h : ht) if (!class_ok<Arith>(h.lc.q)) return 2000;
+    if constexpr (class_of<Arith>() == kClassFold || class_of<Arith>() == kClassShoup) {
+        t.blob = build_ctx_blob(log2n, ht, Arith::kFold);
+        t.tb = ctx_view<Arith>(t.blob.data(), ctx_layout(log2n, ht.size(), Arith::kFold), ht.size());
+    } else class_tables<Arith>(log2n, ht, std::vector<unsigned char>(ht.size(), (unsigned char)class_of<Arith>()).data(), t);
+    return 0;
+}
+template <class Arith>
+static int policy_tables(int log2n, u64 q, u64 psi, Tables<Arith>& t) {
+    std::vector<HostLimbTables> ht;
+    if (int rc = limb_tables(log2n, 1, &q, &psi, ht)) return rc;
+    return policy_tables<Arith>(log2n, ht, t);
+}
+// Forms the library does not ship - a geometry other than LOGE = 4, a ring below N = 256, the halves form on ShoupArith: one limb's tables through the
+// shared packing routines (ctx_tables.h pack_table / pack_subtrees), in the sections a context would have.  log_n1 = 1: the halves tables.
+template <class Arith>
+static int unshipped_tables(int log2n, int loge, int log_n1, u64 q, u64 psi, Tables<Arith>& t) {
+    typedef typename Arith::Tw Tw;
+    HostLimbTables h;
+    if (int rc = build_limb_tables(log2n, q, psi, h)) return rc;
+    if (!class_ok<Arith>(q)) return 2000;
+    const LimbClass k = class_of<Arith>();
+    struct Rest { TwBytes top; InvLast<TwBytes> last; LimbConst lc; };   // what follows the two tables: htop_fwd, last = htop_last, the limb constants
+    const size_t tab = ((size_t)1 << log2n) * sizeof(TwBytes);
+    t.blob.assign(2 * tab + sizeof(Rest), 0);
+    unsigned char* b = t.blob.data();
+    if (log_n1) { pack_subtrees(b, h.rp, k, q, log2n, log_n1, loge); pack_subtrees(b + tab, h.irp, k, q, log2n, log_n1, loge); }
+    else { pack_table(b, h.rp, k, q, log2n, loge); pack_table(b + tab, h.irp, k, q, log2n, loge); }
+    Rest* r = reinterpret_cast<Rest*>(b + 2 * tab);
+    *r = Rest{class_tw(k, h.rp[1], q), class_last(k, h.w_last, h.lc.ninv, q), limb_const_of_class(h.lc, k)};
+    t.tb.fwd = t.tb.hfwd = reinterpret_cast<const Tw*>(b); t.tb.inv = t.tb.hinv = reinterpret_cast<const Tw*>(b + tab);
+    t.tb.htop_fwd = reinterpret_cast<const Tw*>(&r->top);
+    t.tb.last = t.tb.htop_last = reinterpret_cast<const InvLast<Tw>*>(&r->last);
+    t.tb.lc = &r->lc;
+    t.tb.n_sub = t.tb.n_limbs = 1;
+    return 0;
+}
+
 // Exchanges are run the way the kernels synchronise them: the all-to-all exchange as "all threads write, barrier, all
 // threads read"; a wave-local exchange (Geo::exch_wave_local) one WAVE at a time - write then read - in DESCENDING wave
 // order, with no barrier, so a word that had to cross waves, or a region that another wave's exchange clobbers, shows up
@@ -164,360 +197,300 @@ static int check_geo() {
         // the kLdsIO rows of a wave lie in its region
         for (int tid = 0; tid < B::T; ++tid) {
             const int r = B::G::lds_row(tid), w = tid / 64;
-            if (r < w * B::G::kWaveStride || r + E_of<B>() + 2 > (w + 1) * B::G::kWaveStride) return -5;
+            if (r < w * B::G::kWaveStride || r + B::E + 2 > (w + 1) * B::G::kWaveStride) return -5;
         }
         return check_exchanges<B, 0>();
     }
     return 0;
 }
 
+// ---- one workgroup's transforms --------------------------------------------------------------------------------------
+template <class B> static u64 (&regs_of(std::vector<u64>& r, int tid))[B::E] { return *reinterpret_cast<u64(*)[B::E]>(&r[(size_t)tid * B::E]); }
+// forward chain of body B on table `tw` from coefficients `in` (in == out is fine: every word is loaded before the first store)
+template <class B>
+static void block_fwd(const typename B::Tw* tw, const LimbConst& lc, const u64* in, u64* out) {
+    std::vector<u64> regs((size_t)B::T * B::E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
+    for (int tid = 0; tid < B::T; ++tid) B::load_top(tid, regs_of<B>(regs, tid), in);
+    FwdSteps<B, 0>::run(regs, lds, tw, lc);
+    for (int tid = 0; tid < B::T; ++tid) { B::fwd_canon(regs_of<B>(regs, tid), lc); B::store_bot(tid, regs_of<B>(regs, tid), out); }
+}
+template <class B>
+static void block_inv(const typename B::Tw* tw, const InvLast<typename B::Tw>& last, const LimbConst& lc, const u64* in, u64* out) {
+    std::vector<u64> regs((size_t)B::T * B::E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
+    for (int tid = 0; tid < B::T; ++tid) B::load_bot(tid, regs_of<B>(regs, tid), in);
+    InvSteps<B, B::NPH - 1, kUnit>::run(regs, lds, tw, last.w_last, last.w_ninv, lc);
+    for (int tid = 0; tid < B::T; ++tid) { B::inv_canon(regs_of<B>(regs, tid), lc); B::store_top(tid, regs_of<B>(regs, tid), out); }
+}
+// kernels.h ntt_fwd_kernel / ntt_inv_kernel for block `sub` of a polynomial of limb `limb`
 template <class Arith, int LOGN, int LOGE>
-static int emu(int inverse, u64 q, u64 psi, const u64* in, u64* out) {
+static void emu_ntt_block(const DevTables<Arith>& tb, int limb, int sub, int inverse, const u64* in, u64* out) {
     typedef NttBody<Arith, LOGN, LOGE> B;
-    HostLimbTables t;
-    int rc = build_limb_tables(LOGN, q, psi, t);
-    if (rc) return rc;
-    if (!class_ok<Arith>(q)) return 2000;
-    const u64 ninv = t.lc.ninv;     // (F64Arith's LimbConst reuses the field)
-    t.lc = class_lc<Arith>(t.lc);
-    constexpr int E = B::E, T = B::T;
-    std::vector<u64> regs((size_t)T * E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
-    auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-    if (!inverse) {
-        auto tw = TwTab<Arith>::make(t.rp, t.rp_sh, q);
-        permute_window0(tw, LOGN, LOGE, B::G::kPermStages);
-        for (int tid = 0; tid < T; ++tid) B::load_top(tid, X(tid), in);
-        FwdSteps<B, 0>::run(regs, lds, tw.data(), t.lc);
-        for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(tid), t.lc); B::store_bot(tid, X(tid), out); }
-    } else {
-        auto tw = TwTab<Arith>::make(t.irp, t.irp_sh, q);
-        permute_window0(tw, LOGN, LOGE, B::G::kPermStages);
-        auto wl = TwTab<Arith>::one(t.w_last, t.w_last_sh, q), wn = TwTab<Arith>::one(ninv, h_shoup(ninv, q), q);
-        for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(tid), in);
-        InvSteps<B, B::NPH - 1, kUnit>::run(regs, lds, tw.data(), wl, wn, t.lc);
-        for (int tid = 0; tid < T; ++tid) { B::inv_canon(X(tid), t.lc); B::store_top(tid, X(tid), out); }
-    }
-    return 0;
+    const size_t slot = (size_t)limb * tb.n_sub + sub;
+    if (!inverse) block_fwd<B>(tb.fwd + slot * B::G::N, tb.lc[limb], in, out);
+    else block_inv<B>(tb.inv + slot * B::G::N, tb.last[slot], tb.lc[limb], in, out);
 }
 
-// arith: 0 Shoup, 1 Fold, 2 F64, 3 FoldScaled, 4 F64Wide (tables.h LimbClass).  `in`/`out` must be 16-byte aligned.  returns 0, 2000 bad args, -1 unsupported geometry
-extern "C" int emu_ntt(int arith, int log2n, int loge, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-#define CASE(LN, LE)                                                                     \
-    if (log2n == LN && loge == LE) {                                                     \
-        if (arith == 2) return emu<F64Arith, LN, LE>(inverse, q, psi, in, out);          \
-        if (arith == 4) return emu<F64WideArith, LN, LE>(inverse, q, psi, in, out);      \
-        if (arith == 3) return emu<FoldScaledArith, LN, LE>(inverse, q, psi, in, out);   \
-        return arith ? emu<FoldArith, LN, LE>(inverse, q, psi, in, out) : emu<ShoupArith, LN, LE>(inverse, q, psi, in, out); \
-    }
-    CASE(8, 4) CASE(10, 4) CASE(11, 4) CASE(12, 4) CASE(13, 5) CASE(14, 5) CASE(14, 4) CASE(12, 3) CASE(12, 5) CASE(13, 4) CASE(6, 3)
+// Split transform (N = 2^15, 2^16) as launch_impl.h launch_ntt_split runs it: ntt_top.h column stages (ntt_top_kernel) + N1 4096-point kernels on the
+// context's sub-tree tables.
+template <class Arith, int LOG_N1>
+static void emu_split(const DevTables<Arith>& tb, int limb, int inverse, const u64* in, u64* out) {
+    constexpr int LN2 = kSplitLog2N2, N1 = 1 << LOG_N1, N2 = 1 << LN2;
+    const LimbConst lc = tb.lc[limb];
+    auto columns = [&](const u64* src) {
+        for (size_t c = 0; c < (size_t)N2; ++c) {
+            u64 x[N1];
+            for (int r = 0; r < N1; ++r) x[r] = src[(size_t)r * N2 + c];
+            if (!inverse) top_forward<Arith, LOG_N1>(x, tb.top_fwd + (size_t)limb * N1, lc);
+            else top_inverse<Arith, LOG_N1>(x, tb.top_inv + (size_t)limb * N1, tb.top_last[limb], lc);
+            for (int r = 0; r < N1; ++r) out[(size_t)r * N2 + c] = x[r];
+        }
+    };
+    auto blocks = [&](const u64* src) { for (int r = 0; r < N1; ++r) emu_ntt_block<Arith, LN2, 4>(tb, limb, r, inverse, src + (size_t)r * N2, out + (size_t)r * N2); };
+    if (!inverse) { columns(in); blocks(out); } else { blocks(in); columns(out); }
+}
+
+// launch.h launch_ntt for a small batch: the one-piece kernel of the ring degree, the split transform from N = 2^15 (FoldArith / ShoupArith)
+template <class Arith>
+static int emu_launch_ntt(int log2n, const DevTables<Arith>& tb, int limb, int inverse, const u64* in, u64* out) {
+#define CASE(LN) if (log2n == LN) { emu_ntt_block<Arith, LN, 4>(tb, limb, 0, inverse, in, out); return 0; }
+    CASE(8) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
 #undef CASE
+    if constexpr (class_of<Arith>() == kClassFold || class_of<Arith>() == kClassShoup) {
+        if (log2n == 15) { emu_split<Arith, 3>(tb, limb, inverse, in, out); return 0; }
+        if (log2n == 16) { emu_split<Arith, 4>(tb, limb, inverse, in, out); return 0; }
+    }
     return -1;
 }
 
-// The GENERIC fused multiply's data path (kernels.h ct_mul_kernel, policies without lazy products): four forward transforms to canonical
-// words, Arith::mul_var products, three inverse transforms - for the round-6 policies, whose conversions (Arith::enter / leave) sit inside.
-template <class Arith, int LOGN, int LOGE>
-static int emu_ct_mul_generic(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-    typedef NttBody<Arith, LOGN, LOGE> B;
-    HostLimbTables t;
-    int rc = build_limb_tables(LOGN, q, psi, t);
-    if (rc) return rc;
-    if (!class_ok<Arith>(q)) return 2000;
-    const u64 ninv = t.lc.ninv;
-    const LimbConst lc = class_lc<Arith>(t.lc);
-    constexpr int E = B::E, T = B::T, N = B::G::N;
-    auto twf = TwTab<Arith>::make(t.rp, t.rp_sh, q), twi = TwTab<Arith>::make(t.irp, t.irp_sh, q);
-    permute_window0(twf, LOGN, LOGE, B::G::kPermStages);
-    permute_window0(twi, LOGN, LOGE, B::G::kPermStages);
-    const auto wl = TwTab<Arith>::one(t.w_last, t.w_last_sh, q), wn = TwTab<Arith>::one(ninv, h_shoup(ninv, q), q);
-    std::vector<u64> lds(B::G::lds_words());
-    auto fwd = [&](const u64* src) {
-        std::vector<u64> regs((size_t)T * E);
-        auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-        for (int tid = 0; tid < T; ++tid) B::load_top(tid, X(tid), src);
-        FwdSteps<B, 0>::run(regs, lds, twf.data(), lc);
-        for (int tid = 0; tid < T; ++tid) B::fwd_canon(X(tid), lc);
-        return regs;
-    };
-    auto inv = [&](std::vector<u64> regs, u64* dst) {
-        auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-        InvSteps<B, B::NPH - 1, kUnit>::run(regs, lds, twi.data(), wl, wn, lc);
-        for (int tid = 0; tid < T; ++tid) { B::inv_canon(X(tid), lc); B::store_top(tid, X(tid), dst); }
-    };
-    std::vector<u64> S0 = fwd(a0), S1 = fwd(b0), S2 = fwd(b1), S3 = fwd(a1), x((size_t)N);
-    for (int i = 0; i < N; ++i) x[i] = Arith::mul_var(S0[i], S1[i], lc);
-    inv(x, out3);
-    for (int i = 0; i < N; ++i) x[i] = add_mod(Arith::mul_var(S0[i], S2[i], lc), Arith::mul_var(S3[i], S1[i], lc), lc.q);
-    inv(x, out3 + N);
-    for (int i = 0; i < N; ++i) x[i] = Arith::mul_var(S3[i], S2[i], lc);
-    inv(x, out3 + 2 * N);
+// N = 8192 as a column stage in registers + two 4096-point sub-transforms through ONE LDS buffer (ntt_halves.h; kernels_halves.h runs exactly these steps
+// on the device): 256 emulated threads hold lo / hi, the sub-transforms run on the context's halves tables (sub-trees rooted at nodes 2 and 3).
+template <class Arith>
+static void emu_halves(const DevTables<Arith>& tb, int limb, int inverse, const u64* in, u64* out) {
+    typedef Halves13<Arith> H;
+    typedef typename H::B B;
+    constexpr int T = B::T, N = H::N, N2 = H::N2;
+    const LimbConst lc = tb.lc[limb];
+    std::vector<u64> r[2], lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);   // lo, hi
+    for (auto& v : r) v.assign((size_t)T * B::E, 0);
+    auto X = [](std::vector<u64>& v, int tid) -> u64(&)[B::E] { return regs_of<B>(v, tid); };
+    if (!inverse) {
+        const typename B::Tw* tw = tb.hfwd + (size_t)limb * N;     // [limb][half][N2]
+        const typename B::Tw wtop = tb.htop_fwd[limb];
+        for (int tid = 0; tid < T; ++tid) { B::load_top(tid, X(r[0], tid), in); B::load_top(tid, X(r[1], tid), in + N2); H::fwd_column(X(r[0], tid), X(r[1], tid), wtop, lc); }
+        for (int i = 0; i < 2; ++i) {
+            FwdSteps<B, 0>::run(r[i], lds, tw + (size_t)i * N2, lc);
+            for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(r[i], tid), lc); B::store_bot(tid, X(r[i], tid), out + (size_t)i * N2); }
+        }
+    } else {
+        const typename B::Tw* tw = tb.hinv + (size_t)limb * N;
+        const InvLast<typename B::Tw> last = tb.htop_last[limb];
+        for (int i = 0; i < 2; ++i) {
+            for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(r[i], tid), in + (size_t)i * N2);
+            InvSteps<B, B::NPH - 1, kUnit>::run(r[i], lds, tw + (size_t)i * N2, last.w_last, last.w_ninv, lc);
+        }
+        for (int tid = 0; tid < T; ++tid) {
+            H::inv_column(X(r[0], tid), X(r[1], tid), last, lc);
+            for (int i = 0; i < 2; ++i) { B::inv_canon(X(r[i], tid), lc); B::store_top(tid, X(r[i], tid), out + (size_t)i * N2); }
+        }
+    }
+}
+// N = 16384 as two column stages in registers + four 4096-point sub-transforms through ONE LDS buffer (ntt_quarters.h; kernels_quarters.h runs exactly these
+// steps on the device): 256 emulated threads hold q0..q3, the sub-transforms run on the context's quarters tables (sub-trees rooted at nodes 4..7).  FoldArith.
+static void emu_quarters(const DevTables<FoldArith>& tb, int limb, int inverse, const u64* in, u64* out) {
+    typedef Quarters14 Q;
+    typedef Q::B B;
+    constexpr int T = B::T, N = Q::N, N2 = Q::N2;
+    const LimbConst lc = tb.lc[limb];
+    std::vector<u64> r[4], lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
+    for (auto& v : r) v.assign((size_t)T * B::E, 0);
+    auto X = [](std::vector<u64>& v, int tid) -> u64(&)[B::E] { return regs_of<B>(v, tid); };
+    if (!inverse) {
+        const TwFold* tw = tb.qfwd + (size_t)limb * N;     // [limb][quarter][N2]
+        const QuartersTop top = tb.qtop_fwd[limb];
+        for (int tid = 0; tid < T; ++tid) {
+            for (int i = 0; i < 4; ++i) B::load_top(tid, X(r[i], tid), in + (size_t)i * N2);
+            Q::fwd_columns(X(r[0], tid), X(r[1], tid), X(r[2], tid), X(r[3], tid), top, lc);
+        }
+        for (int i = 0; i < 4; ++i) {
+            FwdSteps<B, 0>::run(r[i], lds, tw + (size_t)i * N2, lc);
+            for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(r[i], tid), lc); B::store_bot(tid, X(r[i], tid), out + (size_t)i * N2); }
+        }
+    } else {
+        const TwFold* tw = tb.qinv + (size_t)limb * N;
+        const InvLast<TwFold> last = tb.qtop_last[limb];
+        const TwFold wi2 = tb.qtop_inv[2 * limb], wi3 = tb.qtop_inv[2 * limb + 1];
+        for (int i = 0; i < 4; ++i) {
+            for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(r[i], tid), in + (size_t)i * N2);
+            InvSteps<B, B::NPH - 1, kUnit>::run(r[i], lds, tw + (size_t)i * N2, last.w_last, last.w_ninv, lc);
+        }
+        for (int tid = 0; tid < T; ++tid) {
+            Q::inv_columns(X(r[0], tid), X(r[1], tid), X(r[2], tid), X(r[3], tid), wi2, wi3, last, lc);
+            for (int i = 0; i < 4; ++i) { B::inv_canon(X(r[i], tid), lc); B::store_top(tid, X(r[i], tid), out + (size_t)i * N2); }
+        }
+    }
+}
+
+// ---- a whole context ---------------------------------------------------------------------------------------------------
+// What dpfhe_ctx_create decides for (log2n, moduli, psi) - fold or generic, per-limb classes or not - through the calls it makes.
+struct CtxChoice { std::vector<HostLimbTables> ht; bool fold = true, classes = false; unsigned char limb_cls[16] = {}; };
+static int ctx_choice(int log2n, int n_limbs, const u64* moduli, const u64* psi, CtxChoice& c) {
+    if (log2n < 8 || log2n > kMaxLog2N || n_limbs < 1 || n_limbs > 1024) return 2000;
+    if (int rc = limb_tables(log2n, n_limbs, moduli, psi, c.ht)) return rc;
+    for (int l = 0; l < n_limbs; ++l) { if (!h_is_prime(moduli[l])) return 2000; c.fold = c.fold && fold_eligible(moduli[l]); }
+    c.classes = ctx_limb_classes(log2n, c.ht, c.fold, c.limb_cls);
     return 0;
 }
-extern "C" int emu_ct_mul_class(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-#define CASE(LN)                                                                                                              \
-    if (log2n == LN) {                                                                                                        \
-        if (arith == 2) return emu_ct_mul_generic<F64Arith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                             \
-        if (arith == 4) return emu_ct_mul_generic<F64WideArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                         \
-        if (arith == 3) return emu_ct_mul_generic<FoldScaledArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                      \
-        if (arith == 0) return emu_ct_mul_generic<ShoupArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                           \
-        return -1;                                                                                                            \
+// One polynomial of limb `limb` through a transform of a context of n_limbs limbs.  form 0: what the library launches for a small batch (one-piece, or
+// split from N = 2^15; on the limb's own class when the context has classes); 1: the halves form; 2: the quarters form (2000 where the context has no such
+// tables); 3: form 0 on the GENERIC context-wide tables, as a context with one non-fold limb holds them for every limb.
+enum { kFormLaunch = 0, kFormHalves = 1, kFormQuarters = 2, kFormGeneric = 3 };
+extern "C" int emu_ctx_ntt(int log2n, int n_limbs, const u64* moduli, const u64* psi, int limb, int form, int inverse, const u64* in, u64* out) {
+    CtxChoice c;
+    if (int rc = ctx_choice(log2n, n_limbs, moduli, psi, c)) return rc;
+    if (limb < 0 || limb >= n_limbs || form < kFormLaunch || form > kFormGeneric) return 2000;
+    if (form == kFormLaunch && c.classes)
+        return with_arith(c.limb_cls[limb], [&](auto a) {
+            Tables<decltype(a)> t;
+            class_tables(log2n, c.ht, c.limb_cls, t);
+            return emu_launch_ntt(log2n, t.tb, limb, inverse, in, out);
+        });
+    if (form == kFormGeneric || (form == kFormLaunch && !c.fold)) {
+        Tables<ShoupArith> t;
+        if (int rc = policy_tables(log2n, c.ht, t)) return rc;
+        return emu_launch_ntt(log2n, t.tb, limb, inverse, in, out);
     }
+    Tables<FoldArith> t;
+    if (int rc = policy_tables(log2n, c.ht, t)) return rc;   // (2000: halves / quarters of a context that is not all-fold)
+    if (form == kFormLaunch) return emu_launch_ntt(log2n, t.tb, limb, inverse, in, out);
+    if (form == kFormHalves ? !t.tb.hfwd : !t.tb.qfwd) return 2000;
+    if (form == kFormHalves) emu_halves(t.tb, limb, inverse, in, out); else emu_quarters(t.tb, limb, inverse, in, out);
+    return 0;
+}
+// The bytes dpfhe_ctx_create would upload: which = 0 the context-wide blob, 1 the class blob.  Returns the size (0: the context has no class blob), or
+// -2000 for parameters a context rejects; copies the bytes when out holds at least that many, and the LimbClass per limb into limb_cls (n_limbs <= 16).
+extern "C" long emu_ctx_blob(int log2n, int n_limbs, const u64* moduli, const u64* psi, int which, unsigned char* out, size_t cap, unsigned char* limb_cls) {
+    CtxChoice c;
+    if (ctx_choice(log2n, n_limbs, moduli, psi, c)) return -2000;
+    std::vector<unsigned char> blob;
+    if (!which) blob = build_ctx_blob(log2n, c.ht, c.fold);
+    else if (c.classes) blob = build_class_blob(log2n, c.ht, c.limb_cls);
+    if (limb_cls && n_limbs <= 16) std::memcpy(limb_cls, c.limb_cls, (size_t)n_limbs);
+    if (out && cap >= blob.size()) std::memcpy(out, blob.data(), blob.size());
+    return (long)blob.size();
+}
+
+// ---- the single-prime entry points: a context of one limb, on the policy the caller names ----------------------------------
+// arith: 0 Shoup, 1 Fold, 2 F64, 3 FoldScaled, 4 F64Wide (tables.h LimbClass).  `in`/`out` must be 16-byte aligned.  returns 0, 2000 bad args, -1 unsupported geometry
+extern "C" int emu_ntt(int arith, int log2n, int loge, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
+    return with_arith(arith, [&](auto a) {
+        typedef decltype(a) Arith;
+        Tables<Arith> t;
+        if (log2n >= 8 && log2n <= 14 && log2n != 9 && loge == ntt_loge(log2n)) {
+            if (int rc = policy_tables<Arith>(log2n, q, psi, t)) return rc;
+            return emu_launch_ntt<Arith>(log2n, t.tb, 0, inverse, in, out);
+        }
+#define CASE(LN, LE)                                                                 \
+        if (log2n == LN && loge == LE) {                                             \
+            if (int rc = unshipped_tables<Arith>(LN, LE, 0, q, psi, t)) return rc;   \
+            emu_ntt_block<Arith, LN, LE>(t.tb, 0, 0, inverse, in, out);              \
+            return 0;                                                                \
+        }
+        CASE(13, 5) CASE(14, 5) CASE(12, 3) CASE(12, 5) CASE(6, 3)
+#undef CASE
+        return -1;
+    });
+}
+// (a fold prime alone is an all-fold context; arith = 0 runs it on the generic tables)
+extern "C" int emu_ntt_split(int arith, int log2n, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
+    if (log2n != 15 && log2n != 16) return -1;
+    if (arith && !fold_eligible(q)) return 2000;
+    return emu_ctx_ntt(log2n, 1, &q, &psi, 0, arith ? kFormLaunch : kFormGeneric, inverse, in, out);
+}
+// the halves form ships for FoldArith contexts only: ShoupArith runs it on tables packed here
+extern "C" int emu_ntt_halves(int arith, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
+    if (arith) return emu_ctx_ntt(13, 1, &q, &psi, 0, kFormHalves, inverse, in, out);
+    Tables<ShoupArith> t;
+    if (int rc = unshipped_tables(13, 4, 1, q, psi, t)) return rc;
+    emu_halves(t.tb, 0, inverse, in, out);
+    return 0;
+}
+extern "C" int emu_ntt_quarters(int inverse, u64 q, u64 psi, const u64* in, u64* out) { return emu_ctx_ntt(14, 1, &q, &psi, 0, kFormQuarters, inverse, in, out); }
+
+// Forward transform of words that are only known to be below 2^60 (the digits of a key switch are canonical for ANOTHER limb): NttBody's
+// FWD_IN = kRedB plans, which relin_kernel / relin_shared_kernel rely on to skip the canonicalisation.  FoldArith only.
+extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* out) {
+    Tables<FoldArith> t;
+    if (int rc = policy_tables(log2n, q, psi, t)) return rc;
+#define CASE(LN) if (log2n == LN) { block_fwd<NttBody<FoldArith, LN, kFusedLoge, 0, kRedB>>(t.tb.fwd4, t.tb.lc[0], in, out); return 0; }
     CASE(8) CASE(10) CASE(12) CASE(13)
 #undef CASE
     return -1;
 }
 
-// Split transform (N = 2^15, 2^16): ntt_top.h column stages + N1 emulated 4096-point kernels on sub-tree tables, the way
-// launch_impl.h launch_ntt_split and dpfhe_ctx_create arrange them.
-template <class Arith, int LOG_N1>
-static int emu_split(int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-    constexpr int LN2 = 12, LE = 4, N1 = 1 << LOG_N1, LOGN = LN2 + LOG_N1;
-    typedef NttBody<Arith, LN2, LE> B;
-    typedef typename Arith::Tw Tw;
-    HostLimbTables t;
-    int rc = build_limb_tables(LOGN, q, psi, t);
-    if (rc) return rc;
-    if (Arith::kFold && !fold_eligible(q)) return 2000;
-    constexpr int E = B::E, T = B::T, N2 = B::G::N;
-    const size_t n = (size_t)1 << LOGN;
-    std::vector<Tw> top_f(N1), top_i(N1);
-    for (int i = 1; i < N1; ++i) { top_f[i] = h_make_tw<Tw>(t.rp[i], q); top_i[i] = h_make_tw<Tw>(t.irp[i], q); }
-    // (dpfhe_cabi.hip: FoldArith sub-transforms divide by their own length in their last stage, so the column stage carries N1^-1 only)
-    const u64 up = Arith::kFold ? ((u64)N2 % q) : 1;
-    const InvLast<Tw> top_last{h_make_tw<Tw>(h_mulmod(t.w_last, up, q), q), h_make_tw<Tw>(h_mulmod(t.lc.ninv, up, q), q)};
-    std::vector<u64> buf(in, in + n), lds(B::G::lds_words());
-    auto columns = [&](bool fwd) {
-        for (size_t c = 0; c < (size_t)N2; ++c) {
-            u64 x[N1];
-            for (int r = 0; r < N1; ++r) x[r] = buf[(size_t)r * N2 + c];
-            if (fwd) top_forward<Arith, LOG_N1>(x, top_f.data(), t.lc); else top_inverse<Arith, LOG_N1>(x, top_i.data(), top_last, t.lc);
-            for (int r = 0; r < N1; ++r) buf[(size_t)r * N2 + c] = x[r];
-        }
-    };
-    auto blocks = [&](bool fwd) {
-        for (size_t r = 0; r < (size_t)N1; ++r) {
-            const std::vector<u64> words = subtree_table(fwd ? t.rp : t.irp, LOGN, LOG_N1, r);
-            std::vector<Tw> tw(words.size());
-            for (size_t i = 0; i < words.size(); ++i) tw[i] = h_make_tw<Tw>(words[i], q);
-            permute_window0(tw, LN2, LE, B::G::kPermStages);
-            std::vector<u64> regs((size_t)T * E), blk(buf.begin() + r * N2, buf.begin() + (r + 1) * N2), res(N2);
-            auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-            if (fwd) {
-                for (int tid = 0; tid < T; ++tid) B::load_top(tid, X(tid), blk.data());
-                FwdSteps<B, 0>::run(regs, lds, tw.data(), t.lc);
-                for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(tid), t.lc); B::store_bot(tid, X(tid), res.data()); }
-            } else {
-                // generic primes: no N^-1 inside a block; FoldArith: sums are divided by N2 exactly, differences carry N2^-1 in their twiddle (dpfhe_cabi.hip)
-                const u64 n2inv = Arith::kFold ? h_powmod((u64)N2 % q, q - 2, q) : 1;
-                const Tw wl = h_make_tw<Tw>(h_mulmod(words[1], n2inv, q), q), wn = h_make_tw<Tw>(1, q);
-                for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(tid), blk.data());
-                InvSteps<B, B::NPH - 1, kUnit>::run(regs, lds, tw.data(), wl, wn, t.lc);
-                for (int tid = 0; tid < T; ++tid) { B::inv_canon(X(tid), t.lc); B::store_top(tid, X(tid), res.data()); }
-            }
-            std::copy(res.begin(), res.end(), buf.begin() + r * N2);
-        }
-    };
-    if (!inverse) { columns(true); blocks(true); } else { blocks(false); columns(false); }
-    std::copy(buf.begin(), buf.end(), out);
-    return 0;
-}
-
-extern "C" int emu_ntt_split(int arith, int log2n, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-    if (log2n == 15) return arith ? emu_split<FoldArith, 3>(inverse, q, psi, in, out) : emu_split<ShoupArith, 3>(inverse, q, psi, in, out);
-    if (log2n == 16) return arith ? emu_split<FoldArith, 4>(inverse, q, psi, in, out) : emu_split<ShoupArith, 4>(inverse, q, psi, in, out);
-    return -1;
-}
-
-// Forward transform of words that are only known to be below 2^60 (the digits of a key switch are canonical for ANOTHER limb): NttBody's
-// FWD_IN = kRedB plans, which relin_kernel / relin_shared_kernel rely on to skip the canonicalisation.  FoldArith only.
-template <int LOGN, int LOGE>
-static int emu_fwd_any60(u64 q, u64 psi, const u64* in, u64* out) {
-    typedef NttBody<FoldArith, LOGN, LOGE, 0, kRedB> B;
-    HostLimbTables t;
-    int rc = build_limb_tables(LOGN, q, psi, t);
-    if (rc) return rc;
-    if (!fold_eligible(q)) return 2000;
-    constexpr int E = B::E, T = B::T;
-    std::vector<u64> regs((size_t)T * E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
-    auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-    auto tw = TwTab<FoldArith>::make(t.rp, t.rp_sh, q);
-    permute_window0(tw, LOGN, LOGE, B::G::kPermStages);
-    for (int tid = 0; tid < T; ++tid) B::load_top(tid, X(tid), in);
-    FwdSteps<B, 0>::run(regs, lds, tw.data(), t.lc);
-    for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(tid), t.lc); B::store_bot(tid, X(tid), out); }
-    return 0;
-}
-extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* out) {
-    if (log2n == 8) return emu_fwd_any60<8, 4>(q, psi, in, out);
-    if (log2n == 10) return emu_fwd_any60<10, 4>(q, psi, in, out);
-    if (log2n == 12) return emu_fwd_any60<12, 4>(q, psi, in, out);
-    if (log2n == 13) return emu_fwd_any60<13, 4>(q, psi, in, out);
-    return -1;
-}
-
-// N = 8192 as a column stage in registers + two 4096-point sub-transforms through ONE LDS buffer (ntt_halves.h; kernels_halves.h runs
-// exactly these steps on the device): 256 emulated threads hold lo / hi, the sub-transforms run on the tables dpfhe_ctx_create builds
-// for them (tables.h subtree_table, roots 2 and 3 of the N = 8192 table).
-template <class Arith>
-static int emu_halves(int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-    typedef Halves13<Arith> H;
-    typedef typename H::B B;
-    typedef typename Arith::Tw Tw;
-    HostLimbTables t;
-    int rc = build_limb_tables(H::LOGN, q, psi, t);
-    if (rc) return rc;
-    if (Arith::kFold && !fold_eligible(q)) return 2000;
-    constexpr int E = B::E, T = B::T, N2 = H::N2;
-    std::vector<u64> lo((size_t)T * E), hi((size_t)T * E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
-    auto X = [&](std::vector<u64>& r, int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&r[(size_t)tid * E]); };
-    std::vector<Tw> tw[2];
-    for (size_t r = 0; r < 2; ++r) {
-        const std::vector<u64> words = subtree_table(inverse ? t.irp : t.rp, H::LOGN, 1, r);
-        tw[r].resize(words.size());
-        for (size_t i = 0; i < words.size(); ++i) tw[r][i] = h_make_tw<Tw>(words[i], q);
-        permute_window0(tw[r], H::LOGN2, H::LOGE, B::G::kPermStages);
-    }
-    if (!inverse) {
-        const Tw wtop = h_make_tw<Tw>(t.rp[1], q);
-        for (int tid = 0; tid < T; ++tid) { B::load_top(tid, X(lo, tid), in); B::load_top(tid, X(hi, tid), in + N2); H::fwd_column(X(lo, tid), X(hi, tid), wtop, t.lc); }
-        FwdSteps<B, 0>::run(lo, lds, tw[0].data(), t.lc);
-        for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(lo, tid), t.lc); B::store_bot(tid, X(lo, tid), out); }
-        FwdSteps<B, 0>::run(hi, lds, tw[1].data(), t.lc);
-        for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(hi, tid), t.lc); B::store_bot(tid, X(hi, tid), out + N2); }
-    } else {
-        const InvLast<Tw> last{h_make_tw<Tw>(t.w_last, q), h_make_tw<Tw>(t.lc.ninv, q)};
-        const Tw unused = h_make_tw<Tw>(1, q);
-        for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(lo, tid), in);
-        InvSteps<B, B::NPH - 1, kUnit>::run(lo, lds, tw[0].data(), unused, unused, t.lc);
-        for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(hi, tid), in + N2);
-        InvSteps<B, B::NPH - 1, kUnit>::run(hi, lds, tw[1].data(), unused, unused, t.lc);
-        for (int tid = 0; tid < T; ++tid) {
-            H::inv_column(X(lo, tid), X(hi, tid), last, t.lc);
-            B::inv_canon(X(lo, tid), t.lc); B::inv_canon(X(hi, tid), t.lc);
-            B::store_top(tid, X(lo, tid), out); B::store_top(tid, X(hi, tid), out + N2);
-        }
-    }
-    return 0;
-}
-// N = 16384 as two column stages in registers + four 4096-point sub-transforms through ONE LDS buffer (ntt_quarters.h; kernels_quarters.h runs exactly these
-// steps on the device): 256 emulated threads hold q0..q3, the sub-transforms run on the sub-tree tables rooted at nodes 4..7.  FoldArith.
-extern "C" int emu_ntt_quarters(int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-    typedef Quarters14 Q;
-    typedef Q::B B;
-    HostLimbTables t;
-    int rc = build_limb_tables(Q::LOGN, q, psi, t);
-    if (rc) return rc;
-    if (!fold_eligible(q)) return 2000;
-    constexpr int E = B::E, T = B::T, N2 = Q::N2;
-    std::vector<u64> r[4], lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
-    for (auto& v : r) v.assign((size_t)T * E, 0);
-    auto X = [&](std::vector<u64>& v, int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&v[(size_t)tid * E]); };
-    std::vector<TwFold> tw[4];
-    for (size_t i = 0; i < 4; ++i) {
-        const std::vector<u64> words = subtree_table(inverse ? t.irp : t.rp, Q::LOGN, 2, i);
-        tw[i].resize(words.size());
-        for (size_t j = 0; j < words.size(); ++j) tw[i][j] = h_tw_fold(words[j], q);
-        permute_window0(tw[i], Q::LOGN2, Q::LOGE, B::G::kPermStages);
-    }
-    if (!inverse) {
-        const QuartersTop top{h_tw_fold(t.rp[1], q), h_tw_fold(t.rp[2], q), h_tw_fold(t.rp[3], q)};
-        for (int tid = 0; tid < T; ++tid) {
-            for (int i = 0; i < 4; ++i) B::load_top(tid, X(r[i], tid), in + (size_t)i * N2);
-            Q::fwd_columns(X(r[0], tid), X(r[1], tid), X(r[2], tid), X(r[3], tid), top, t.lc);
-        }
-        for (int i = 0; i < 4; ++i) {
-            FwdSteps<B, 0>::run(r[i], lds, tw[i].data(), t.lc);
-            for (int tid = 0; tid < T; ++tid) { B::fwd_canon(X(r[i], tid), t.lc); B::store_bot(tid, X(r[i], tid), out + (size_t)i * N2); }
-        }
-    } else {
-        const InvLast<TwFold> last{h_tw_fold(t.w_last, q), h_tw_fold(t.lc.ninv, q)};
-        const TwFold wi2 = h_tw_fold(t.irp[2], q), wi3 = h_tw_fold(t.irp[3], q), unused = h_tw_fold(1, q);
-        for (int i = 0; i < 4; ++i) {
-            for (int tid = 0; tid < T; ++tid) B::load_bot(tid, X(r[i], tid), in + (size_t)i * N2);
-            InvSteps<B, B::NPH - 1, kUnit>::run(r[i], lds, tw[i].data(), unused, unused, t.lc);
-        }
-        for (int tid = 0; tid < T; ++tid) {
-            Q::inv_columns(X(r[0], tid), X(r[1], tid), X(r[2], tid), X(r[3], tid), wi2, wi3, last, t.lc);
-            for (int i = 0; i < 4; ++i) { B::inv_canon(X(r[i], tid), t.lc); B::store_top(tid, X(r[i], tid), out + (size_t)i * N2); }
-        }
-    }
-    return 0;
-}
-
-extern "C" int emu_ntt_halves(int arith, int inverse, u64 q, u64 psi, const u64* in, u64* out) {
-    return arith ? emu_halves<FoldArith>(inverse, q, psi, in, out) : emu_halves<ShoupArith>(inverse, q, psi, in, out);
-}
-
-// The fused ct x ct kernels' lazy FoldArith data path (kernels.h ct_mul_kernel / ct_mul_dual_kernel - the paired kernel computes
-// the same values from the same operands, only two transforms at a time -, coefficient domain in and out), run with
-// the same per-thread transform code and the same dyadic sequence, so that the bound plans and the relaxed mul60
-// precondition (lazy forward outputs < 14 q times partially reduced b-side factors) are checked on the CPU with the
-// wrap-around / precondition counters armed.  out3 = (c0, c1, c2) of one limb.
-template <class Arith, int LOGN, int LOGE>
-static int emu_ct_mul_lazy(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-    typedef NttBody<Arith, LOGN, LOGE> B;
-    typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, true> BI;   // inverse of register-resident products (kernels.h ct_mul_quad_kernel / ct_mul_dual_kernel)
-    HostLimbTables t;
-    int rc = build_limb_tables(LOGN, q, psi, t);
-    if (rc) return rc;
-    if (!class_ok<Arith>(q)) return 2000;
-    constexpr int E = B::E, T = B::T, N = B::G::N;
-    static_assert(!Arith::kFoldCore || B::kFwdOutBound <= kLimitPartner, "lazy forward outputs must satisfy mul60's bound");
-    auto twf = TwTab<Arith>::make(t.rp, t.rp_sh, q), twi = TwTab<Arith>::make(t.irp, t.irp_sh, q);
-    permute_window0(twf, LOGN, LOGE, B::G::kPermStages);
-    permute_window0(twi, LOGN, LOGE, B::G::kPermStages);
-    // FoldScaledArith: the products carry the scale twice; the inverse's last stage folds one s^-1 in (DevTables::last2)
-    const u64 sinv = (Arith::kFoldCore && !Arith::kFold) ? h_powmod((1ull << fold_scaled_shift(q)) % q, q - 2, q) : 1;
-    const u64 wlv = h_mulmod(t.w_last, sinv, q), wnv = h_mulmod(t.lc.ninv, sinv, q);
-    const auto wl = TwTab<Arith>::one(wlv, h_shoup(wlv, q), q), wn = TwTab<Arith>::one(wnv, h_shoup(wnv, q), q);
-    const LimbConst lc = class_lc<Arith>(t.lc);
+// ---- the fused multiply -------------------------------------------------------------------------------------------------
+// One limb's (c0, c1, c2) through the fused ct x ct kernels' data paths (coefficient domain in and out), with the same per-thread transform code and the
+// same dyadic sequence, on the context's fused-layout tables (DevTables::fwd4 / inv4).
+//   LAZY (kernels.h ct_mul_quad_kernel / ct_mul_dual_kernel - the paired kernel computes the same values, two transforms at a time): lazy forward outputs,
+//     NttBody::tensor (fold policies turn b0, b1 into twiddles on the fly), the inverse of register-resident products - so the bound plans and the relaxed
+//     mul60 precondition (lazy forward outputs < 14 q times partially reduced b-side factors) are checked with the wrap-around / precondition counters armed;
+//   otherwise (ct_mul_kernel, any policy): four forward transforms to canonical words, Arith::mul_var products, three inverse transforms.
+template <class Arith, int LOGN, bool LAZY>
+static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    typedef NttBody<Arith, LOGN, kFusedLoge> B;
+    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, LAZY> BI;
+    Tables<Arith> t;
+    if (int rc = policy_tables(LOGN, q, psi, t)) return rc;
+    constexpr int T = B::T, N = B::G::N, limb = 0;
+    static_assert(!LAZY || !Arith::kFoldCore || B::kFwdOutBound <= kLimitPartner, "lazy forward outputs must satisfy mul60's bound");
+    // FoldScaledArith: lazy products carry the scale twice; the inverse's last stage folds one s^-1 in (DevTables::last2)
+    constexpr bool kScaledProducts = LAZY && Arith::kFoldCore && !Arith::kFold;
+    const LimbConst lc = t.tb.lc[limb];
+    const InvLast<typename B::Tw> last = kScaledProducts ? t.tb.last2[limb] : t.tb.last[limb];
+    const typename B::Tw *twf = t.tb.fwd4 + (size_t)limb * N, *twi = t.tb.inv4 + (size_t)limb * N;
     std::vector<u64> lds(B::G::lds_words());
     auto fwd = [&](const u64* src, bool partner) {
-        std::vector<u64> regs((size_t)T * E);
-        auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-        for (int tid = 0; tid < T; ++tid) B::load_top(tid, X(tid), src);
-        FwdSteps<B, 0>::run(regs, lds, twf.data(), lc);
-        if (partner) for (int tid = 0; tid < T; ++tid) B::prod_partner(X(tid), lc);
+        std::vector<u64> regs((size_t)T * B::E);
+        for (int tid = 0; tid < T; ++tid) B::load_top(tid, regs_of<B>(regs, tid), src);
+        FwdSteps<B, 0>::run(regs, lds, twf, lc);
+        for (int tid = 0; tid < T; ++tid) {
+            if constexpr (!LAZY) B::fwd_canon(regs_of<B>(regs, tid), lc);
+            else if (partner) B::prod_partner(regs_of<B>(regs, tid), lc);
+        }
         return regs;
     };
     auto inv = [&](std::vector<u64> regs, u64* dst) {
-        auto X = [&](int tid) -> u64(&)[E] { return *reinterpret_cast<u64(*)[E]>(&regs[(size_t)tid * E]); };
-        InvSteps<BI, B::NPH - 1, B::kProdInvIn>::run(regs, lds, twi.data(), wl, wn, lc);
-        for (int tid = 0; tid < T; ++tid) { B::inv_canon(X(tid), lc); B::store_top(tid, X(tid), dst); }
+        InvSteps<BI, B::NPH - 1, LAZY ? B::kProdInvIn : kUnit>::run(regs, lds, twi, last.w_last, last.w_ninv, lc);
+        for (int tid = 0; tid < T; ++tid) { B::inv_canon(regs_of<B>(regs, tid), lc); B::store_top(tid, regs_of<B>(regs, tid), dst); }
     };
-    // the tensor step as ct_mul_quad_kernel / ct_mul_dual_kernel run it (NttBody::tensor: fold policies turn b0, b1 into twiddles on the fly)
     std::vector<u64> S0 = fwd(a0, false), S1 = fwd(b0, true), S2 = fwd(b1, true), S3 = fwd(a1, false), c0((size_t)N), c1((size_t)N), c2((size_t)N);
-    for (int i = 0; i < N; ++i) B::tensor(S0[i], S3[i], S1[i], S2[i], c0[i], c1[i], c2[i], lc);
+    for (int i = 0; i < N; ++i) {
+        if constexpr (LAZY) B::tensor(S0[i], S3[i], S1[i], S2[i], c0[i], c1[i], c2[i], lc);
+        else { c0[i] = Arith::mul_var(S0[i], S1[i], lc); c1[i] = add_mod(Arith::mul_var(S0[i], S2[i], lc), Arith::mul_var(S3[i], S1[i], lc), lc.q); c2[i] = Arith::mul_var(S3[i], S2[i], lc); }
+    }
     inv(c0, out3);
     inv(c1, out3 + N);
     inv(c2, out3 + 2 * N);
     return 0;
 }
-template <int LOGN, int LOGE>
-static int emu_ct_mul_fold(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-    return emu_ct_mul_lazy<FoldArith, LOGN, LOGE>(q, psi, a0, a1, b0, b1, out3);
-}
-// the lazy-product path of the round-6 classes (arith 2 F64, 3 FoldScaled; 1 Fold)
-extern "C" int emu_ct_mul_lazy_class(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-#define CASE(LN)                                                                                                           \
-    if (log2n == LN) {                                                                                                     \
-        if (arith == 1) return emu_ct_mul_lazy<FoldArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                            \
-        if (arith == 2) return emu_ct_mul_lazy<F64Arith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                             \
-        if (arith == 4) return emu_ct_mul_lazy<F64WideArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                         \
-        if (arith == 3) return emu_ct_mul_lazy<FoldScaledArith, LN, 4>(q, psi, a0, a1, b0, b1, out3);                      \
-        return -1;                                                                                                         \
-    }
-    CASE(8) CASE(10) CASE(12) CASE(13)
+template <bool LAZY>
+static int emu_ct_mul_any(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    return with_arith(arith, [&](auto a) {
+        typedef decltype(a) Arith;
+#define CASE(LN) if (log2n == LN) return emu_ct_mul_path<Arith, LN, LAZY>(q, psi, a0, a1, b0, b1, out3);
+        if constexpr (LAZY ? Arith::kFoldCore || Arith::kF64 : !Arith::kFold) { CASE(8) CASE(10) CASE(12) CASE(13) }   // (ShoupArith has no lazy products; FoldArith always uses them)
 #undef CASE
-    return -1;
+        return -1;
+    });
 }
-
+// the generic path of the classes (arith 0 Shoup, 2 F64, 3 FoldScaled, 4 F64Wide), their lazy-product path (1 Fold, 2, 3, 4), and the pinned primes' multiply
+extern "C" int emu_ct_mul_class(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    return emu_ct_mul_any<false>(arith, log2n, q, psi, a0, a1, b0, b1, out3);
+}
+extern "C" int emu_ct_mul_lazy_class(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    return emu_ct_mul_any<true>(arith, log2n, q, psi, a0, a1, b0, b1, out3);
+}
 extern "C" int emu_ct_mul(int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-    if (log2n == 8) return emu_ct_mul_fold<8, 4>(q, psi, a0, a1, b0, b1, out3);
-    if (log2n == 10) return emu_ct_mul_fold<10, 4>(q, psi, a0, a1, b0, b1, out3);
-    if (log2n == 12) return emu_ct_mul_fold<12, 4>(q, psi, a0, a1, b0, b1, out3);
-    if (log2n == 13) return emu_ct_mul_fold<13, 4>(q, psi, a0, a1, b0, b1, out3);
-    return -1;
+    return emu_ct_mul_any<true>(kClassFold, log2n, q, psi, a0, a1, b0, b1, out3);
 }
 
 extern "C" int emu_check_lds_regions(int log2n, int loge) {
