@@ -174,6 +174,109 @@ def edge_moduli(kind, log2n):
     return FheParams(log2n, tuple(q for q, _ in ps), tuple(w for _, w in ps))
 
 
+# ---- digit ladders: contexts of any limb count (tests/test_gpu_digit_ladder.py, tests/test_digit_ladder_cpu.py) -----------------------------------------
+CHAIN_KINDS = ("fold", "shoup", "f64", "fold_scaled", "f64_wide")
+MIXED_CHAIN_ORDER = ("fold", "f64", "fold_scaled", "f64_wide", "shoup")     # limb i of mixed16 / mixed17 has class i mod 5: limb 15 is a fold limb
+
+
+@functools.lru_cache(maxsize=None)
+def chain_moduli(kind, log2n, count):
+    """the `count` primes = 1 mod 2N of class `kind` nearest the class bound, in the catalogue's order (the first PER_ENTRY are the catalogue's own)"""
+    two_n = 2 << log2n
+    if kind == "fold":          # fold_edge: from the bound 2^60 - 2^24 upward
+        qs = _walk(_first_at_or_above((1 << 60) - (1 << 24) + 1, two_n), 1 << 60, +1, two_n, count=count)
+    elif kind == "shoup":       # shoup60: from just outside fold downward
+        qs = _walk(_first_at_or_below((1 << 60) - (1 << 24), two_n), 1 << 59, -1, two_n, "shoup", count=count)
+    elif kind == "f64":         # f64_edge
+        qs = _walk(_first_at_or_below((1 << 47) - 1, two_n), 1 << 46, -1, two_n, count=count)
+    elif kind == "f64_wide":    # f64_wide_edge
+        qs = _walk(_first_at_or_below((1 << 50) - 1, two_n), 1 << 49, -1, two_n, "f64_wide", count=count)
+    elif kind == "fold_scaled":  # fscaled_edge_k, four per shift: the edge prime of every shift (the widest scaling first), then the second of every shift, ...
+        per = {k: _walk(_first_at_or_above((1 << k) - (1 << (k - 36)) + 1, two_n), 1 << k, +1, two_n, count=PER_ENTRY) for k in FSCALED_ORDER}
+        qs = [per[k][i] for i in range(PER_ENTRY) for k in FSCALED_ORDER if len(per[k]) > i][:count]
+    else:
+        raise ValueError(kind)
+    assert len(qs) == count and len(set(qs)) == count, (kind, log2n, count, len(qs))
+    return tuple(qs)
+
+
+def edge_chain(kind, log2n, count=None):
+    """a context of `count` limbs at the edge of one class (CHAIN_KINDS), or 'mixed16' / 'mixed17': 16 / 17 limbs that cycle the five classes
+    (MIXED_CHAIN_ORDER), each class's limbs its edge primes in order - limb 15, the top nibble of the active-limb map, is a fold limb"""
+    if kind in ("mixed16", "mixed17"):
+        total = int(kind[5:])
+        assert count in (None, total)
+        per = {c: chain_moduli(c, log2n, -(-total // len(MIXED_CHAIN_ORDER))) for c in MIXED_CHAIN_ORDER}
+        qs = tuple(per[MIXED_CHAIN_ORDER[i % 5]][i // 5] for i in range(total))
+        assert expected_class(qs[15]) != "shoup"
+    else:
+        qs = chain_moduli(kind, log2n, count)
+    assert len(set(qs)) == len(qs)
+    return FheParams(log2n, qs, tuple(min_primitive_2n_root(1 << log2n, q) for q in qs))
+
+
+def chain_classes(kind, count):
+    """the class of every limb of edge_chain(kind, log2n, count), by construction"""
+    if kind in ("mixed16", "mixed17"):
+        return tuple(MIXED_CHAIN_ORDER[i % 5] for i in range(int(kind[5:])))
+    return (kind,) * count
+
+
+# the rungs of tests/test_gpu_digit_ladder.py: (kind, log2 N, context limbs L).  RNS-digit keys give L digits, a special prime L - 1.
+#   fold, N = 256: every L to 18 (relin_kernel reduces its lazy sums first at the 14th digit), then both sides of the reductions at digits 26 and 38
+#   fold, N = 1024 / 4096: both sides of relin_shared_kernel's 4..7 digits, for L digits and for L - 1
+#   fold, N = 8192: the LDS key tiles, hoisted_qp_upfront_kernel<6> / hoisted_qp_stream_kernel from 7, the Dot30 fold every 8 terms, 14+ digits, 17 limbs, 40
+#   every other class, uniform: 8 digits, and 16 / 17 limbs (per-limb classes / the context-wide policy)
+#   mixed16 / mixed17: every class in one context on both sides of that switch
+LADDER = ([("fold", 8, L) for L in tuple(range(1, 19)) + (26, 27, 40)]
+          + [("fold", ln, L) for ln in (10, 12) for L in (3, 4, 5, 7, 8, 9)]
+          + [("fold", 13, L) for L in (7, 8, 9, 10, 14, 15, 17, 40)]
+          + [(k, ln, L) for k in CHAIN_KINDS[1:] for ln in (8, 12) for L in (8, 16, 17)]
+          + [("mixed16", 12, 16), ("mixed17", 12, 17)])
+
+
+def _pow_words(orc, base, exponents):
+    """base [1][L][N] ** exponents[l] mod q_l, word by word, by the oracle's modular multiply (square and multiply, the exponent's bits per limb)"""
+    result = np.ones_like(base)
+    e = np.array(exponents, dtype=object)
+    for bit in range(max(int(v).bit_length() for v in exponents)):
+        take = np.array([(int(v) >> bit) & 1 for v in e], bool)[None, :, None]
+        result = np.where(take, orc.dyadic("mul", result, base), result)
+        base = orc.dyadic("mul", base, base)
+    return result
+
+
+def inverse_words(orc, x):
+    """x [m][L][N], no word zero -> x^-1 mod q_l word by word: one Fermat inversion of the product over m (Montgomery's trick), by the oracle's multiply"""
+    m = x.shape[0]
+    pref = np.empty_like(x)
+    pref[0] = x[0]
+    for j in range(1, m):
+        pref[j] = orc.dyadic("mul", pref[j - 1][None], x[j][None], threads=0)[0]
+    inv = _pow_words(orc, np.ascontiguousarray(pref[m - 1][None]), [q - 2 for q in orc.moduli])
+    out = np.empty_like(x)
+    for j in range(m - 1, 0, -1):
+        out[j] = orc.dyadic("mul", inv, pref[j - 1][None], threads=0)[0]
+        inv = orc.dyadic("mul", inv, x[j][None], threads=0)
+    out[0] = inv[0]
+    return out
+
+
+def adversarial_key(orc, digits, seed):
+    """A key-switching key under which every lazily added product of one item is q - 1, the largest canonical word.
+
+    digits [nd][N]: the digit polynomials of that item (limb j of its last component, words below q_j); orc: the context the key lives on (L limbs).
+    x[j][i] = NTT_i(digits[j] mod q_i) is what a key-switching kernel multiplies with key word [j][comp][i]; both components get
+    e = (q_i - 1) x^-1 mod q_i, so x e = q_i - 1 in every word and the sum over the digits is the constant -nd mod q_i.  Where x = 0 the word stays random.
+    -> (key [nd][2][L][N], x [nd][L][N], the number of words with x = 0)"""
+    qcol = np.array(orc.moduli, np.uint64)[:, None]
+    x = orc.ntt_fwd(np.ascontiguousarray(digits[:, None, :] % qcol[None]), threads=0)
+    zero = x == 0
+    inv = inverse_words(orc, np.where(zero, np.uint64(1), x))
+    e = np.where(zero, orc.fill(x.shape[0], seed), orc.dyadic("negate", inv))
+    return np.ascontiguousarray(np.stack([e, e], axis=1)), x, int(zero.sum())
+
+
 def reported_classes(p):
     """what dpfhe_ctx_limb_class reports: the catalogue's class per limb where the context has per-limb classes (8 <= log2 N <= 14, L <= 16), the
     context-wide policy otherwise (fold when every limb is 2^60 - d, shoup else)"""
@@ -186,9 +289,14 @@ def reported_classes(p):
 
 
 class Rig:
-    def __init__(self, kind, log2n):
+    def __init__(self, kind, log2n=None):
+        """an edge context by name (edge_moduli(kind, log2n)), or ready FheParams (the digit ladders' edge_chain contexts)"""
         from deeppowers_amd.evaluator import Context, Evaluator
-        self.kind, self.p = kind, edge_moduli(kind, log2n)
+        if isinstance(kind, FheParams):
+            kind, log2n, self.p = None, kind.log2_n, kind
+        else:
+            self.p = edge_moduli(kind, log2n)
+        self.kind = kind
         self.L, self.n = self.p.n_limbs, self.p.n
         self.orc = Oracle.from_params(self.p)
         self.ctx = Context(self.p, 0)

@@ -105,6 +105,41 @@ def test_deep_level_limb_counts_bit_exact(log2n):
     ctx.close()
 
 
+@pytest.mark.parametrize("kind,log2n,counts", [("fold", 10, (8, 9)), ("shoup", 9, (5, 6, 7, 8))], ids=["fold_edge_n1024", "shoup60_n512"])
+def test_every_instantiated_source_limb_count_at_the_edge_primes(kind, log2n, counts):
+    """base_extend_kernel is instantiated once per source-limb count (kernels_bx.h): 1 to 10 on fold primes, 1 to 8 on generic ones, 9 or more refused
+    there.  The tests above reach 1 - 7 and 10 (fold) and 1 - 4 (generic); here the rest, on the primes nearest the class bound (class_edges.edge_chain:
+    the fold primes with the largest d, the widest words the generic path takes), both entries: the extension and the scale-and-round."""
+    from class_edges import edge_chain
+    p = edge_chain(kind, log2n, 12)
+    orc, ctx = Oracle.from_params(p), Context(p, 0)
+    ev = Evaluator(ctx)
+    assert ctx.limb_classes == (kind,) * 12 and ctx.uses_fold == (kind == "fold")
+    rng = np.random.default_rng(31)
+    L, n = p.n_limbs, p.n
+    for ns in counts:
+        for src0, dst0, nd in ((0, 0, L), (L - ns, 0, L - ns)):
+            src = p.moduli[src0:src0 + ns]
+            x = np.stack([rng.integers(0, q, (3, n), dtype=np.uint64) for q in src], axis=1)           # [3][ns][N]
+            x[0, :, : n // 2] = np.array(src, np.uint64)[:, None] - np.uint64(1)                       # X = -1: the sign path of every lane
+            Qs = int(np.prod([int(q) for q in src], dtype=object))
+            for k, val in enumerate((Qs // 2, Qs // 2 + 1, Qs // 2 - 1, 0)):
+                x[1, :, k] = [val % q for q in src]
+            got = to_host(ev.base_extend(to_device(x, ctx.device), src0, dst0, nd))
+            assert np.array_equal(got, orc.base_extend(x, src0, dst0, nd)), (ns, src0, dst0, nd)
+        y = np.stack([rng.integers(0, q, (2, n), dtype=np.uint64) for q in p.moduli], axis=1)          # any residues: the integer is what they represent
+        y[0, :, : n // 2] = np.array(p.moduli, np.uint64)[:, None] - np.uint64(1)
+        for drop0, keep0, nkeep, mul in ((0, ns, L - ns, 65537), (L - ns, 0, L - ns, 1)):
+            got = to_host(ev.scale_round(to_device(y, ctx.device), drop0, ns, keep0, nkeep, mul))
+            assert np.array_equal(got, orc.scale_round(y, drop0, ns, keep0, nkeep, mul)), (drop0, ns, keep0, nkeep, mul)
+    if kind == "shoup":
+        with pytest.raises(_cabi.DpfheError):
+            ev.base_extend(to_device(np.zeros((1, 9, n), np.uint64), ctx.device), 0, 0, L)             # nine generic source limbs
+        with pytest.raises(_cabi.DpfheError):
+            ev.scale_round(to_device(np.zeros((1, L, n), np.uint64), ctx.device), 0, 9, 9, L - 9, 1)
+    ctx.close()
+
+
 def test_multiply_exact_at_n16384_equals_the_oracle_pipeline():
     """Round 5: the exact multiply at N = 16384 (five primes = 1 mod 2^15, ciphertexts at the two-limb level: examples/encrypted_gpt2_block_act ... 14),
     where the tensor product is composed from the batched transforms: base extension, multiply, scale-and-round and the extension back, each and
