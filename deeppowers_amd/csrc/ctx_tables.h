@@ -98,6 +98,49 @@ inline bool ctx_limb_classes(int log2n, const std::vector<HostLimbTables>& ht, b
     return any_fast;
 }
 
+// ---- the lazy-multiply blob ----------------------------------------------------------------------------------------
+// Round 11: the fused multiply of the pinned primes at N = 4096 runs its transforms on twiddles split at bit 29 (FoldArith::mul_tw29_add, NttBody's
+// LAZY29 plans).  Those tables live in a blob of their own - fwd29 | inv29 | last29, fused layout only, [L] slots with only the fold limbs' filled - next
+// to the context-wide blob and the class blob, which stay byte for byte what they were.  Built for every context at log2 N = 12 in which a limb runs on
+// FoldArith: the all-fold contexts, and the fold limbs of a context with per-limb classes (they launch the same kernel).
+constexpr int kLazy29Log2N = 12;
+struct Lazy29Layout { size_t o_fwd, o_inv, o_last, total; };
+inline Lazy29Layout lazy29_layout(size_t L) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t tab = L * ((size_t)1 << kLazy29Log2N) * kTwSize;
+    Lazy29Layout m;
+    m.o_fwd = 0; m.o_inv = up(tab); m.o_last = up(m.o_inv + tab); m.total = up(m.o_last + L * 2 * kTwSize);
+    return m;
+}
+// fold_limb[l]: limb l runs on FoldArith.  Returns an empty blob when the context has no use for one.
+inline std::vector<unsigned char> build_lazy29_blob(int log2n, const std::vector<HostLimbTables>& ht, const std::vector<bool>& fold_limb) {
+    bool any = false;
+    for (size_t l = 0; l < ht.size(); ++l) any = any || fold_limb[l];
+    if (log2n != kLazy29Log2N || !any) return {};
+    const size_t L = ht.size(), n = (size_t)1 << log2n;
+    const Lazy29Layout m = lazy29_layout(L);
+    std::vector<unsigned char> blob(m.total, 0);
+    auto pack29 = [&](size_t off, const std::vector<u64>& words, u64 q) {
+        std::vector<TwBytes> t(words.size());
+        for (size_t i = 0; i < words.size(); ++i) t[i] = tw_bytes(h_tw_fold29(words[i], q));
+        permute_window0(t, log2n, kFusedLoge, geo_perm_stages(log2n, kFusedLoge));
+        std::memcpy(&blob[off], t.data(), t.size() * kTwSize);
+    };
+    for (size_t l = 0; l < L; ++l) {
+        if (!fold_limb[l]) continue;
+        const HostLimbTables& t = ht[l];
+        const u64 q = t.lc.q;
+        pack29(m.o_fwd + l * n * kTwSize, t.rp, q);
+        pack29(m.o_inv + l * n * kTwSize, t.irp, q);
+        reinterpret_cast<InvLast<TwBytes>*>(&blob[m.o_last])[l] = InvLast<TwBytes>{tw_bytes(h_tw_fold29(t.w_last, q)), tw_bytes(h_tw_fold29(t.lc.ninv, q))};
+    }
+    return blob;
+}
+inline void lazy29_view(DevTables<FoldArith>& tb, const unsigned char* d, const Lazy29Layout& m) {
+    tb.fwd29 = reinterpret_cast<const TwFold*>(d + m.o_fwd); tb.inv29 = reinterpret_cast<const TwFold*>(d + m.o_inv);
+    tb.last29 = reinterpret_cast<const InvLast<TwFold>*>(d + m.o_last);
+}
+
 // ---- the context-wide blob -----------------------------------------------------------------------------------------
 // Tables of the context-wide arithmetic (FoldArith or ShoupArith, every limb): ONE blob of 256-byte aligned sections.  One twiddle table pair per kernel
 // geometry in use: slot 0 = the fused kernels' LOGE 4 layout, slot 1 = the batched NTT kernels' layout when that differs.  Split transforms (N > 16384)

@@ -59,6 +59,11 @@ struct DevTables {
     // FoldScaledArith class only: the same with s^-1 = 2^-(60-k) folded in - the last stage of an inverse transform whose input is a PRODUCT of two
     // scaled words (the fused multiply's lazy tensor step).  Null elsewhere.
     const InvLast<typename Arith::Tw>* last2;  // [L]
+    // FoldArith at N = 4096 only (null elsewhere): the fused-layout tables and the last stage once more, every twiddle split at bit 29
+    // (FoldArith::mul_tw29_add) - what ct_mul_quad_kernel's lazy transforms read.  A separate blob (ctx_tables.h build_lazy29_blob).
+    const typename Arith::Tw* fwd29;        // [L][N]
+    const typename Arith::Tw* inv29;        // [L][N]
+    const InvLast<typename Arith::Tw>* last29;  // [L]
     const LimbConst* lc;                    // [L]
     int n_limbs;
     // Per-limb arithmetic classes (round 6, dpfhe_cabi.hip): a launch may cover only SOME limbs of the context - those whose primes this policy

@@ -100,6 +100,7 @@ struct dpfhe_ctx {
                                                       // kernels the context runs (with_policy below); a mixture keeps the generic ones, on the complete generic tables
     unsigned char limb_cls[16] = {};                  // LimbClass of limb i
     unsigned long long cls_map = 0;                   // the same, 4 bits per limb
+    void* lazy29_blob = nullptr;                      // the fused multiply's bit-29 twiddles (ctx_tables.h build_lazy29_blob): log2 N = 12 with a FoldArith limb, null elsewhere
     void* class_blob = nullptr;                       // ONE blob of tables whose per-limb slots are in their limb's class format (mixed_layout)
     DevTables<FoldArith> cls_fold{};                  // typed views of it; the active-limb maps are set per launch (for_each_class)
     DevTables<F64Arith> cls_f64{};
@@ -328,6 +329,15 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
         for (size_t l = 1; l < L; ++l) same = same && c->limb_cls[l] == c->limb_cls[0];
         if (same) c->uniform_cls = c->limb_cls[0];
     }
+    {   // the fused multiply's lazy tables: seen through whichever FoldArith view launches ct_mul_quad_kernel at N = 4096
+        std::vector<bool> fold_limb(L);
+        for (size_t l = 0; l < L; ++l) fold_limb[l] = fold || (c->classes && c->limb_cls[l] == kClassFold);
+        const std::vector<unsigned char> lb = build_lazy29_blob((int)log2_n, ht, fold_limb);
+        if (!lb.empty()) {
+            if (int rc = upload(c->lazy29_blob, lb, "dpfhe_ctx_create: lazy table upload")) return rc;
+            lazy29_view(fold ? c->foldt : c->cls_fold, static_cast<const unsigned char*>(c->lazy29_blob), lazy29_layout(L));
+        }
+    }
     tune_at_create(c);   // default form of the fused multiply, or a cached explicit probe of this shape: no device work
     (void)hipSetDevice(prev);
     *out = c;
@@ -338,6 +348,7 @@ extern "C" int dpfhe_ctx_destroy(dpfhe_ctx* c) {
     if (!c) return DPFHE_SUCCESS;
     if (c->d_blob) (void)hipFree(c->d_blob);
     if (c->class_blob) (void)hipFree(c->class_blob);
+    if (c->lazy29_blob) (void)hipFree(c->lazy29_blob);
     for (auto& a : c->scratch_arenas) if (a.p) (void)hipFree(a.p);
     delete c;
     return DPFHE_SUCCESS;

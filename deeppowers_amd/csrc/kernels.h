@@ -646,13 +646,15 @@ __device__ __forceinline__ u64 trace_stamp(u64 dep) {
 template <class Arith, int LOGN, int LOGE, bool TRACE = false, bool OUT_NTT = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64* __restrict__ out3, const u64* __restrict__ a2,
                                                                          const u64* __restrict__ b2, DevTables<Arith> tb, u64* __restrict__ trace = nullptr) {
-    typedef NttBody<Arith, LOGN, LOGE> B;
+    // the pinned primes at N = 4096 (round 11): unreduced butterfly products on the twiddles split at bit 29 (NttBody LAZY29, DevTables::fwd29 / inv29 / last29)
+    constexpr bool kLazy29 = Arith::kFold && LOGN == 12;
+    typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, false, kLazy29> B;
     static_assert(B::kLazyProducts && LOGE == kFusedLoge, "a policy with lazy products (ntt_core.h prod), fused twiddle layout");
-    typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, true> BI;   // the inverse transforms' body: their input is the register-resident products
+    typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, true, kLazy29> BI;   // the inverse transforms' body: their input is the register-resident products
     constexpr bool kScaledProducts = Arith::kFoldCore && !Arith::kFold;   // FoldScaledArith: the products carry the scale twice
     constexpr int E = B::E, N = B::G::N, W = B::G::lds_words();
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
     const u64 ts0 = trace_stamp<TRACE>((u64)tid);
     const size_t L = (size_t)tb.n_limbs;
     size_t bi;
@@ -663,8 +665,12 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
     const u64* src_b = b2 + ((bi * 2) * L + limb) * N;
     u64* dst = out3 + ((bi * 3) * L + limb) * N;
     const size_t cstride = L * N;
-    const InvLast<typename B::Tw> last = kScaledProducts ? tb.last2[limb] : tb.last[limb];
+    const InvLast<typename B::Tw> last = kLazy29 ? tb.last29[limb] : kScaledProducts ? tb.last2[limb] : tb.last[limb];
+    const typename B::Tw* const tw_fwd = (kLazy29 ? tb.fwd29 : tb.fwd4) + (size_t)limb * N;
+    const typename B::Tw* const tw_inv = (kLazy29 ? tb.inv29 : tb.inv4) + (size_t)limb * N;
     constexpr int kInvIn = B::kProdInvIn;
+    // reductions per transform and thread (96 butterflies each), visible at compile time; a b-side forward transform adds prod_partner's 16
+    static_assert(!kLazy29 || (B::template lazy_fwd_reductions<>() == 40 && BI::template lazy_inv_reductions<kInvIn>() == 55), "lazy plans of the N = 4096 geometry");
     u64 x[E], y[E], z[E], w[E];
     const u64 ts_p = trace_stamp<TRACE>((u64)(uintptr_t)src_a ^ (u64)lc.q);   // prologue done: kernel arguments and limb constants are in registers
     B::template load_top<true>(tid, x, src_a);
@@ -675,7 +681,10 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
     const u64 ts_i = trace_stamp<TRACE>((u64)tid);                              // all 64 loads are issued
     const u64 ts1 = trace_stamp<TRACE>(x[0]);
     const u64 ts_xl = trace_stamp<TRACE>(x[E - 1]);                             // the whole first operand has arrived
-    FwdChain4<B, 0>::run(tid, x, y, z, w, lds, lds + W, tb.fwd4 + (size_t)limb * N, lc);
+    // opaque from here on (its range restated): hipcc otherwise derives the LDS addresses of every exchange from tid up front and carries them, and tid itself
+    // through the first phase - 256 registers instead of 223 (the thin reduce needs the multiply at 240 or less: kernels_misc.h)
+    if constexpr (kLazy29) { asm volatile("" : "+v"(tid)); __builtin_assume(tid >= 0 && tid < B::T); }
+    FwdChain4<B, 0>::run(tid, x, y, z, w, lds, lds + W, tw_fwd, lc);
     B::prod_partner(y, lc);     // of every product below exactly one factor is reduced: b0, b1
     B::prod_partner(w, lc);
     const u64 ts2 = trace_stamp<TRACE>(w[E - 1]);
@@ -697,7 +706,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
         return;
     }
     constexpr bool kNtStore = true;   // the 3 GiB of products are written once and read by another kernel much later: around the Infinity Cache (-2.4 %)
-    InvChain3<BI, B::NPH - 1, kInvIn>::run(tid, x, y, z, lds, lds + W, tb.inv4 + (size_t)limb * N, last, lc);
+    InvChain3<BI, B::NPH - 1, kInvIn>::run(tid, x, y, z, lds, lds + W, tw_inv, last, lc);
     const u64 ts4 = trace_stamp<TRACE>(z[E - 1]);
     B::inv_canon(x, lc);
     B::template store_top<kNtStore>(tid, x, dst);

@@ -209,6 +209,37 @@ struct FoldArith {
         const u64 R = mad32((u32)(H >> 32), 4 * (u32)c.d, L);
         return reduce(R, c);
     }
+    // ---- the same twiddle split at bit 29: UNREDUCED products (round 11) ----------------------------------------------------------
+    // Packing (tables.h h_tw_fold29; the type stays TwFold):  w = a + b 2^29,  w 2^32 mod q = a' + b' 2^29  with a, a' < 2^29 and b, b' < 2^31
+    // (w, w 2^32 mod q < q < 2^60);  t.w = a | b << 32,  t.ws = a' | b' << 32.
+    //   H = y0 b + y1 b'                             < 2^64   (both products < 2^63)
+    //   L = H.lo 2^29 + y0 a + y1 a' + addend                  (H.lo 2^29 < 2 * 2^60,  y0 a < 2 * 2^60,  y1 a' < y / 8)
+    //   R = L + H.hi 2d                                        (2^61 == 2d mod q;  H.hi 2d < 2^57 = 2^60 / 8)
+    // so R == addend + y w (mod q) and R < 4.125 * 2^60 + y / 8 + addend: for ANY 64-bit y nothing wraps while addend + y / 8 < 11.875 * 2^60.
+    // Six multiply-adds and NO reduce: the split at bit 30 leaves R < 8 * 2^60 + y / 4 + addend, which a butterfly cannot carry to its next stage.
+    // A Cooley-Tukey butterfly takes x' = R as it is and y' = 2a + K q - x' with K q >= 4.125 * 2^60 + y / 8 (ntt_core.h make_ctf29_plan tracks
+    // the bounds and places the reductions of the addends, about every other stage).
+    static DPF_HD u64 mul_tw29_add(u64 y, const Tw& t, const LimbConst& c, u64 addend) {
+        const u32 y0 = (u32)y, y1 = (u32)(y >> 32);
+        const u32 a = (u32)t.w, b = (u32)(t.w >> 32), as = (u32)t.ws, bs = (u32)(t.ws >> 32);
+        DPFHE_EMU_ASSERT(((a | as) >> 29) == 0 && ((b | bs) >> 31) == 0);
+        DPFHE_EMU_ASSERT(tw29_fits(y0, y1, a, b, as, bs, addend, (u32)c.d));
+        const u64 H = mad32(y1, bs, mad32(y0, b, 0));
+        u32 two29 = 1u << 29;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("s_mov_b32 %0, 0x20000000" : "=s"(two29));  // opaque: H.lo * 2^29 + addend stays one v_mad_u64_u32 (as two30 in mul_tw)
+#endif
+        const u64 L = mad32(y1, as, mad32(y0, a, mad32((u32)H, two29, addend)));
+        return mad32((u32)(H >> 32), 2 * (u32)c.d, L);
+    }
+    static DPF_HD u64 mul_tw29(u64 y, const Tw& t, const LimbConst& c) { return mul_tw29_add(y, t, c, 0); }
+    // (emulator only) the chain above in exact arithmetic: none of H, L, R leaves 64 bits
+    static DPF_HD bool tw29_fits(u32 y0, u32 y1, u32 a, u32 b, u32 as, u32 bs, u64 addend, u32 d) {
+        typedef unsigned __int128 u128;
+        const u128 H = (u128)y0 * b + (u128)y1 * bs;
+        const u128 L = (u128)((u32)(u64)H) * (1u << 29) + (u128)y0 * a + (u128)y1 * as + addend;
+        return (H >> 64) == 0 && (L >> 64) == 0 && ((L + (u128)(u32)((u64)H >> 32) * (2 * d)) >> 64) == 0;
+    }
     // ---- variable x variable products through the twiddle chain (round 6) ------------------------------------------------------
     // One factor b (reduced: b < 2^60 + 2^29) is turned into a twiddle on the fly, then every product with it costs mul_tw's 9 instructions
     // instead of mul60's ~25 (hipcc builds mul60's {hi, 0} addends and fold124's shifted words with v_mov / v_alignbit), and a sum of two

@@ -36,7 +36,13 @@ inline u64 chk_shl1_add_sub(u64 a, u64 c, u64 s) {  // 2a + c - s must stay in [
     if (v < 0 || (v >> 64) || ((unsigned __int128)2 * a + c) >> 64) ++g_emu_overflows;
     return shl1_add(a, c) - s;
 }
+inline u64 chk_lazy_diff(u64 a, u64 c, u64 s) {  // 2a + c - s must END in [0, 2^64); 2a + c alone may pass 2^64 (arithmetic modulo 2^64)
+    __int128 v = 2 * (__int128)a + (__int128)c - (__int128)s;
+    if (v < 0 || (v >> 64)) ++g_emu_overflows;
+    return shl1_add(a, c) - s;
+}
 #else
+DPF_HD u64 chk_lazy_diff(u64 a, u64 c, u64 s) { return shl1_add(a, c) - s; }
 DPF_HD u64 chk_shl1_add_sub(u64 a, u64 c, u64 s) { return shl1_add(a, c) - s; }
 DPF_HD u64 chk_add(u64 a, u64 b) { return a + b; }
 DPF_HD u64 chk_sub_add(u64 a, u64 b, u64 off) { return a - b + off; }
@@ -268,6 +274,101 @@ constexpr CtfPlan<LOGE> make_ctf_plan(int lb_top, int r, int in_bound, int out_c
 }
 
 // ------------------------------------------------------------------------------------------------
+// lazy bound plans (round 11; FoldArith::mul_tw29_add on twiddles split at bit 29): a product leaves its multiply-add chain UNREDUCED,
+//     R < 4.125 * 2^60 + y / 8 + addend,          in plan units  kLazy29B + ceil(Y / 8) + A     (2^60 = q + d and 4.125 d < q / 1024: the + 1 in kLazy29B)
+// and takes ANY 64-bit y, so multiplied words are never reduced; only addends (forward) and sum inputs (inverse) are, where a bound would pass 16 q.
+// Forward butterfly: x' = a + w y unreduced (6 instructions), y' = 2a + K q - x' with K = ceil(kLazy29B + Y / 8) (3 instructions; K q >= the product part
+// of x', so 0 <= y' < a + K q: bound A + K 1024.  2a + K q may pass 2^64 on the way - the arithmetic is modulo 2^64 and the RESULT fits).
+// `a` is reduced first (3 instructions) when x' or y' would not fit a word, or when that saves reductions at the phase hand-over.
+// Inverse butterfly: x' = a + b, y' = (a - b + off q) w unreduced; the larger of a, b is reduced first when the sum or the difference would not fit, then
+// the other if it still does not.  The transform's last stage reduces its products (inv_canon's input bound) and divides its sums by N (mul_ninv).
+// Every plan counts its reductions (n_red): the transform's cost is 9 VALU per forward butterfly, 10 per inverse one, plus 3 per reduction.
+// ------------------------------------------------------------------------------------------------
+constexpr int kLazy29B = 4 * kUnit + kUnit / 8 + 1;
+constexpr int kCtf29Mid = 14 * kUnit;             // forward hand-over cap: above every word the N = 4096 geometry hands over (13 q) - no reduction at an exchange
+constexpr int kGs29Mid = 6 * kUnit + kUnit / 4;   // inverse hand-over cap: lets a phase's lazy products (5.7 q) and four-stage sums of reduced words pass
+
+template <int LOGE>
+struct Ctf29Plan {
+    bool red_a[LOGE][1 << LOGE];   // reduce the addend a of the butterfly with lower-index element k before stage u
+    int K[LOGE][1 << LOGE];        // y' = 2a + K q - x'
+    bool red_end[1 << LOGE];       // reduce element k after the last stage (above out_cap)
+    int out[1 << LOGE];            // bound of element k when the phase ends
+    int out_bound;                 // max of out[]
+    int n_red;                     // reductions in this phase
+};
+template <int LOGE>
+constexpr Ctf29Plan<LOGE> make_ctf29_plan(int lb_top, int r, int in_bound, int out_cap) {
+    Ctf29Plan<LOGE> p{};
+    constexpr int E = 1 << LOGE;
+    int bnd[E] = {};
+    for (int k = 0; k < E; ++k) bnd[k] = in_bound;
+    for (int u = 0; u < r; ++u) {
+        const int bit = 1 << (lb_top - u);
+        for (int k = 0; k < E; ++k) {
+            if (k & bit) continue;
+            int A = bnd[k];
+            const int P = kLazy29B + (bnd[k | bit] + 7) / 8;   // the product part of x'
+            const int K = (P + kUnit - 1) / kUnit;
+            bool red = P + A > kWord || A + K * kUnit > kWord;
+            // the phase's last stage: one reduction in front instead of one or two behind, where that brings both outputs under the cap
+            if (!red && u == r - 1 && A > kRedB && (P + A > out_cap || A + K * kUnit > out_cap) && P + kRedB <= out_cap && kRedB + K * kUnit <= out_cap) red = true;
+            if (red) { p.red_a[u][k] = true; A = kRedB; ++p.n_red; }
+            p.K[u][k] = K;
+            bnd[k] = P + A;
+            bnd[k | bit] = A + K * kUnit;
+        }
+    }
+    for (int k = 0; k < E; ++k) {
+        if (bnd[k] > out_cap) { p.red_end[k] = true; bnd[k] = kRedB; ++p.n_red; }
+        p.out[k] = bnd[k];
+        if (bnd[k] > p.out_bound) p.out_bound = bnd[k];
+    }
+    return p;
+}
+
+template <int LOGE>
+struct Gs29Plan {
+    bool red[LOGE][1 << LOGE];     // reduce element k before stage u
+    int off[LOGE][1 << LOGE];      // y' = (x - y + off q) w
+    bool red_end[1 << LOGE];       // reduce element k after the last stage (above out_cap)
+    int out_bound;
+    int n_red;                     // reductions in this phase, the reduced products of the transform's last stage included
+};
+// last: the phase ends with the transform's last stage (sums divided by 2^ninv_shift exactly, products reduced)
+template <int LOGE>
+constexpr Gs29Plan<LOGE> make_gs29_plan(int lb0, int r, int in_bound, int out_cap, bool last, int ninv_shift) {
+    Gs29Plan<LOGE> p{};
+    constexpr int E = 1 << LOGE;
+    int bnd[E] = {};
+    for (int k = 0; k < E; ++k) bnd[k] = in_bound;
+    for (int u = 0; u < r; ++u) {
+        const int bit = 1 << (lb0 + u);
+        const bool fin = last && u == r - 1;
+        const int sum_cap = fin ? kWord - kUnit / 8 : kWord;   // (FoldArith::mul_ninv needs a little headroom below 2^64)
+        for (int k = 0; k < E; ++k) {
+            if (k & bit) continue;
+            int bx = bnd[k], by = bnd[k | bit];
+            for (int pass = 0; pass < 2; ++pass) {
+                if (bx + by <= sum_cap && bx + (by + kUnit - 1) / kUnit * kUnit <= kWord) break;
+                if (bx >= by && bx > kRedB) { p.red[u][k] = true; bx = kRedB; ++p.n_red; }
+                else { p.red[u][k | bit] = true; by = kRedB; ++p.n_red; }
+            }
+            const int offq = (by + kUnit - 1) / kUnit;
+            p.off[u][k] = offq;
+            bnd[k] = fin ? kUnit + ((bx + by) >> ninv_shift) + 2 : bx + by;
+            bnd[k | bit] = fin ? kRedB : kLazy29B + (bx + offq * kUnit + 7) / 8;
+            if (fin) ++p.n_red;
+        }
+    }
+    for (int k = 0; k < E; ++k) {
+        if (bnd[k] > out_cap) { p.red_end[k] = true; bnd[k] = kRedB; ++p.n_red; }
+        if (bnd[k] > p.out_bound) p.out_bound = bnd[k];
+    }
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------
 // static bound plans (F64ArithT).  Bounds are on |x|, in units of q/1024.  A product's multiplied word must stay below cap = kCap q (<= 2^51); sums of
 // two words below 4 cap (exact additions: < 2^53).  A reduction leaves |x| <= q/2 + 1, a product |x| <= q.  With kCap = 16 (primes below 2^47) the forward
 // plan of every compiled ring degree is empty; with kCap = 2 (primes below 2^50) most multiplied words are reduced first.
@@ -346,12 +447,15 @@ constexpr int kSubInvOut = 7 * kUnit;   // lo + hi < 14 q: the column stage's su
 // canonical for ANOTHER limb of a FoldArith context - the digits of a key switch: the first stage's fused multiply-add reduces it for free).
 // RAW_INV: the INVERSE transform's input is already in the policy's internal form (register-resident products of forward outputs in the fused
 // multiply: doubles for F64Arith, scaled words for FoldScaledArith) - no Arith::enter in front of its first stage.
-template <class Arith, int LOGN, int LOGE, int SUB = 0, int FWD_IN = (SUB ? kCtfMid : kUnit), bool RAW_INV = false>
+// LAZY29: the transforms run the lazy plans above on twiddle tables split at bit 29 (ctx_tables.h build_lazy29_blob; the pinned primes' fused multiply at
+// N = 4096).  Forward outputs are then plain 64-bit words (kFwdOutBound up to kWord): for the tensor step's twiddle chain, not for mul60.
+template <class Arith, int LOGN, int LOGE, int SUB = 0, int FWD_IN = (SUB ? kCtfMid : kUnit), bool RAW_INV = false, bool LAZY29 = false>
 struct NttBody {
     typedef Geo<LOGN, LOGE> G;
     typedef typename Arith::Tw Tw;
     static constexpr int E = G::E, T = G::T, NPH = G::NPH;
     static_assert(FWD_IN >= kUnit && FWD_IN <= kCtfMid && (!SUB || FWD_IN == kCtfMid), "forward input bound: canonical ... the phase hand-over bound");
+    static_assert(!LAZY29 || (Arith::kFold && !SUB), "the lazy plans are the pinned primes', one-piece transforms only");
 
     // ---------------- global <-> registers ----------------
     // window-top mapping (forward input / inverse output): word j = k*T + tid, 8 B per lane, coalesced
@@ -670,9 +774,29 @@ struct NttBody {
         }
         return make_ctf_plan<LOGE>(ph.b - ph.c + ph.r - 1, ph.r, in, (P == NPH - 1) ? kWord : kCtfMid);
     }
+    // the lazy plan of forward phase P: kCtf29Mid at every exchange, nothing capped after the last
+    template <int P>
+    static constexpr Ctf29Plan<LOGE> ctf29_plan() {
+        constexpr Phase ph = G::phase(P);
+        int in = FWD_IN;
+        for (int i = 0; i < P; ++i) {
+            const Phase pi = G::phase(i);
+            in = make_ctf29_plan<LOGE>(pi.b - pi.c + pi.r - 1, pi.r, in, kCtf29Mid).out_bound;
+        }
+        return make_ctf29_plan<LOGE>(ph.b - ph.c + ph.r - 1, ph.r, in, (P == NPH - 1) ? kWord : kCtf29Mid);
+    }
+    template <int P, int IN>
+    static constexpr Gs29Plan<LOGE> gs29_plan() {
+        constexpr Phase ph = G::phase(P);
+        return make_gs29_plan<LOGE>(ph.b - ph.c, ph.r, (P == NPH - 1) ? IN : kGs29Mid, (P == 0) ? 3 * kUnit / 2 : kGs29Mid, P == 0, LOGN);
+    }
+    // reductions per transform and thread under the lazy plans (E / 2 * LOGN butterflies)
+    template <int P = 0> static constexpr int lazy_fwd_reductions() { if constexpr (P < NPH) return ctf29_plan<P>().n_red + lazy_fwd_reductions<P + 1>(); else return 0; }
+    template <int IN, int P = 0> static constexpr int lazy_inv_reductions() { if constexpr (P < NPH) return gs29_plan<P, IN>().n_red + lazy_inv_reductions<IN, P + 1>(); else return 0; }
+    template <bool L = LAZY29> static constexpr int fwd_out_bound_fold() { if constexpr (L) return ctf29_plan<NPH - 1>().out_bound; else return ctf_plan<NPH - 1>().out_bound; }
     // bound of every word a forward transform hands to a dyadic product when its output is left lazy
-    static constexpr int kFwdOutBound = Arith::kFoldCore ? ctf_plan<NPH - 1>().out_bound : Arith::kF64 ? f64_ct_plan<NPH - 1>().out_bound : 4 * kUnit;
-    static_assert(!Arith::kFoldCore || kFwdOutBound <= kLimitPartner, "lazy forward outputs must satisfy mul60's bound");
+    static constexpr int kFwdOutBound = Arith::kFoldCore ? fwd_out_bound_fold<>() : Arith::kF64 ? f64_ct_plan<NPH - 1>().out_bound : 4 * kUnit;
+    static_assert(!Arith::kFoldCore || kFwdOutBound <= (LAZY29 ? kWord : kLimitPartner), "lazy forward outputs must satisfy mul60's bound (LAZY29: fit a word)");
 
     // generic policies (FoldScaledArith, F64Arith) convert a canonical word when it enters a transform and back when it leaves (Arith::enter /
     // Arith::leave); the pinned-prime and Harvey policies work on the words as they are
@@ -713,6 +837,25 @@ struct NttBody {
 #pragma clang loop unroll(full)
             for (int k = 0; k < E; ++k)
                 if (plan.red_end[k]) x[k] = Arith::b(Arith::reduce(Arith::f(x[k]), q, qi));
+        } else if constexpr (LAZY29) {
+            constexpr Ctf29Plan<LOGE> plan = ctf29_plan<P>();
+#pragma clang loop unroll(full)
+            for (int u = 0; u < ph.r; ++u) {
+                const int lb = ph.b + ph.r - 1 - u - ph.c;
+#pragma clang loop unroll(full)
+                for (int k = 0; k < E; ++k) {
+                    if (k & (1 << lb)) continue;
+                    const int kk = k | (1 << lb);
+                    u64 a = x[k];
+                    if (plan.red_a[u][k]) a = FoldArith::reduce(a, lc);
+                    const u64 s = FoldArith::mul_tw29_add(x[kk], twr[u][k >> (lb + 1)], lc, a);
+                    x[k] = s;                                                        // a + w y, unreduced
+                    x[kk] = chk_lazy_diff(a, (u64)plan.K[u][k] * lc.q, s);           // a - w y = 2a + K q - x'
+                }
+            }
+#pragma clang loop unroll(full)
+            for (int k = 0; k < E; ++k)
+                if (plan.red_end[k]) x[k] = FoldArith::reduce(x[k], lc);
         } else if constexpr (Arith::kFoldCore) {
             constexpr CtfPlan<LOGE> plan = ctf_plan<P>();
 #pragma clang loop unroll(full)
@@ -759,6 +902,9 @@ struct NttBody {
         if constexpr (Arith::kF64) {
 #pragma clang loop unroll(full)
             for (int k = 0; k < E; ++k) x[k] = Arith::leave(x[k], lc);
+        } else if constexpr (LAZY29) {
+#pragma clang loop unroll(full)
+            for (int k = 0; k < E; ++k) x[k] = FoldArith::canon(x[k], lc);
         } else if constexpr (Arith::kFoldCore) {
             constexpr CtfPlan<LOGE> plan = ctf_plan<NPH - 1>();   // sums leave the last stage reduced: 4 instructions instead of 7
 #pragma clang loop unroll(full)
@@ -777,10 +923,17 @@ struct NttBody {
     static DPF_HD void fwd_reduce_partner(u64 (&x)[E], const LimbConst& lc_in) {
         static_assert(Arith::kFoldCore, "fold policies only");
         const auto& lc = Arith::ntt_lc(lc_in);
-        constexpr CtfPlan<LOGE> plan = ctf_plan<NPH - 1>();
+        if constexpr (LAZY29) {   // every word leaves the lazy plan's last stage unreduced
+            constexpr Ctf29Plan<LOGE> plan = ctf29_plan<NPH - 1>();
 #pragma clang loop unroll(full)
-        for (int k = 0; k < E; ++k)
-            if (plan.out[k] > kRedB) x[k] = FoldArith::reduce(x[k], lc);
+            for (int k = 0; k < E; ++k)
+                if (plan.out[k] > kRedB) x[k] = FoldArith::reduce(x[k], lc);
+        } else {
+            constexpr CtfPlan<LOGE> plan = ctf_plan<NPH - 1>();
+#pragma clang loop unroll(full)
+            for (int k = 0; k < E; ++k)
+                if (plan.out[k] > kRedB) x[k] = FoldArith::reduce(x[k], lc);
+        }
     }
 
     // ---------------- lazy products of forward outputs (the fused multiply's tensor step, in registers) ----------------
@@ -872,6 +1025,35 @@ struct NttBody {
 #pragma clang loop unroll(full)
             for (int k = 0; k < E; ++k)
                 if (plan.red_end[k]) x[k] = Arith::b(Arith::reduce(Arith::f(x[k]), q, qi));
+        } else if constexpr (LAZY29) {
+            constexpr Gs29Plan<LOGE> plan = gs29_plan<P, IN>();
+            const u64 q = lc.q;
+#pragma clang loop unroll(full)
+            for (int u = 0; u < ph.r; ++u) {
+                const int pos = ph.b + u;
+                const int lb = pos - ph.c;
+                const bool last = (pos == LOGN - 1);
+#pragma clang loop unroll(full)
+                for (int k = 0; k < E; ++k) {
+                    if (k & (1 << lb)) continue;
+                    const int kk = k | (1 << lb);
+                    u64 a = x[k], b = x[kk];
+                    if (plan.red[u][k]) a = FoldArith::reduce(a, lc);
+                    if (plan.red[u][kk]) b = FoldArith::reduce(b, lc);
+                    const u64 s = chk_add(a, b);
+                    const u64 dlt = chk_sub_add(a, b, (u64)plan.off[u][k] * q);
+                    if (last) {  // the sums are divided by N exactly, the products reduced: what inv_canon takes
+                        x[k] = FoldArith::mul_ninv(s, lc, LOGN);
+                        x[kk] = FoldArith::reduce(FoldArith::mul_tw29(dlt, w_last, lc), lc);
+                    } else {
+                        x[k] = s;
+                        x[kk] = FoldArith::mul_tw29(dlt, twr[u][k >> (lb + 1)], lc);   // unreduced: < 4.125 * 2^60 + dlt / 8
+                    }
+                }
+            }
+#pragma clang loop unroll(full)
+            for (int k = 0; k < E; ++k)
+                if (plan.red_end[k]) x[k] = FoldArith::reduce(x[k], lc);
         } else {
             constexpr GsPlan<LOGE> plan = gs_plan<P, IN>();
             const u64 q = lc.q, two_q = 2 * lc.q;

@@ -55,6 +55,12 @@ inline TwFold h_tw_fold(u64 w, u64 q) {
     return TwFold{(w & m30) | ((w >> 30) << 32), (ws & m30) | ((ws >> 30) << 32)};
 }
 
+// the same twiddle split at bit 29 (modarith.h FoldArith::mul_tw29_add): low halves < 2^29, high halves < 2^31
+inline TwFold h_tw_fold29(u64 w, u64 q) {
+    const u64 ws = (u64)(((u128)w << 32) % q), m29 = (1ull << 29) - 1;
+    return TwFold{(w & m29) | ((w >> 29) << 32), (ws & m29) | ((ws >> 29) << 32)};
+}
+
 template <class Tw> inline Tw h_make_tw(u64 w, u64 q);
 template <> inline TwFold h_make_tw<TwFold>(u64 w, u64 q) { return h_tw_fold(w, q); }
 template <> inline TwShoup h_make_tw<TwShoup>(u64 w, u64 q) { return TwShoup{w, (u64)(((u128)w << 64) / q)}; }

@@ -366,14 +366,19 @@ extern "C" int emu_ctx_ntt(int log2n, int n_limbs, const u64* moduli, const u64*
     if (form == kFormHalves) emu_halves(t.tb, limb, inverse, in, out); else emu_quarters(t.tb, limb, inverse, in, out);
     return 0;
 }
-// The bytes dpfhe_ctx_create would upload: which = 0 the context-wide blob, 1 the class blob.  Returns the size (0: the context has no class blob), or
+// The bytes dpfhe_ctx_create would upload: which = 0 the context-wide blob, 1 the class blob, 2 the lazy-multiply blob (log2 N = 12 with a fold limb).  Returns the size (0: the context has no class blob), or
 // -2000 for parameters a context rejects; copies the bytes when out holds at least that many, and the LimbClass per limb into limb_cls (n_limbs <= 16).
 extern "C" long emu_ctx_blob(int log2n, int n_limbs, const u64* moduli, const u64* psi, int which, unsigned char* out, size_t cap, unsigned char* limb_cls) {
     CtxChoice c;
     if (ctx_choice(log2n, n_limbs, moduli, psi, c)) return -2000;
     std::vector<unsigned char> blob;
     if (!which) blob = build_ctx_blob(log2n, c.ht, c.fold);
-    else if (c.classes) blob = build_class_blob(log2n, c.ht, c.limb_cls);
+    else if (which == 1) { if (c.classes) blob = build_class_blob(log2n, c.ht, c.limb_cls); }
+    else {   // 2: the lazy-multiply blob, as dpfhe_ctx_create calls for it
+        std::vector<bool> fold_limb((size_t)n_limbs);
+        for (int l = 0; l < n_limbs; ++l) fold_limb[(size_t)l] = c.fold || (c.classes && c.limb_cls[l] == kClassFold);
+        blob = build_lazy29_blob(log2n, c.ht, fold_limb);
+    }
     if (limb_cls && n_limbs <= 16) std::memcpy(limb_cls, c.limb_cls, (size_t)n_limbs);
     if (out && cap >= blob.size()) std::memcpy(out, blob.data(), blob.size());
     return (long)blob.size();
@@ -434,19 +439,29 @@ extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* 
 //     NttBody::tensor (fold policies turn b0, b1 into twiddles on the fly), the inverse of register-resident products - so the bound plans and the relaxed
 //     mul60 precondition (lazy forward outputs < 14 q times partially reduced b-side factors) are checked with the wrap-around / precondition counters armed;
 //   otherwise (ct_mul_kernel, any policy): four forward transforms to canonical words, Arith::mul_var products, three inverse transforms.
-template <class Arith, int LOGN, bool LAZY>
-static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
-    typedef NttBody<Arith, LOGN, kFusedLoge> B;
-    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, LAZY> BI;
+//   LAZY29 (ct_mul_quad_kernel at N = 4096 on the pinned primes): the same with NttBody's LAZY29 plans on the context's bit-29 tables (ctx_tables.h
+//     build_lazy29_blob); out_ntt: the products as DPFHE_OUT_NTT stores them (canonical, forward-output order), no inverse transforms.
+template <class Arith, int LOGN, bool LAZY, bool LAZY29 = false>
+static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3, bool out_ntt = false) {
+    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, false, LAZY29> B;
+    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, LAZY, LAZY29> BI;
     Tables<Arith> t;
     if (int rc = policy_tables(LOGN, q, psi, t)) return rc;
     constexpr int T = B::T, N = B::G::N, limb = 0;
-    static_assert(!LAZY || !Arith::kFoldCore || B::kFwdOutBound <= kLimitPartner, "lazy forward outputs must satisfy mul60's bound");
+    static_assert(!LAZY || !Arith::kFoldCore || B::kFwdOutBound <= (LAZY29 ? kWord : kLimitPartner), "lazy forward outputs must satisfy mul60's bound");
     // FoldScaledArith: lazy products carry the scale twice; the inverse's last stage folds one s^-1 in (DevTables::last2)
     constexpr bool kScaledProducts = LAZY && Arith::kFoldCore && !Arith::kFold;
     const LimbConst lc = t.tb.lc[limb];
-    const InvLast<typename B::Tw> last = kScaledProducts ? t.tb.last2[limb] : t.tb.last[limb];
-    const typename B::Tw *twf = t.tb.fwd4 + (size_t)limb * N, *twi = t.tb.inv4 + (size_t)limb * N;
+    std::vector<unsigned char> blob29;
+    if constexpr (LAZY29) {
+        std::vector<HostLimbTables> ht;
+        if (int rc = limb_tables(LOGN, 1, &q, &psi, ht)) return rc;
+        blob29 = build_lazy29_blob(LOGN, ht, std::vector<bool>(1, true));
+        if (blob29.empty()) return -1;
+        lazy29_view(t.tb, blob29.data(), lazy29_layout(1));
+    }
+    const InvLast<typename B::Tw> last = LAZY29 ? t.tb.last29[limb] : kScaledProducts ? t.tb.last2[limb] : t.tb.last[limb];
+    const typename B::Tw *twf = (LAZY29 ? t.tb.fwd29 : t.tb.fwd4) + (size_t)limb * N, *twi = (LAZY29 ? t.tb.inv29 : t.tb.inv4) + (size_t)limb * N;
     std::vector<u64> lds(B::G::lds_words());
     auto fwd = [&](const u64* src, bool partner) {
         std::vector<u64> regs((size_t)T * B::E);
@@ -467,10 +482,61 @@ static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u
         if constexpr (LAZY) B::tensor(S0[i], S3[i], S1[i], S2[i], c0[i], c1[i], c2[i], lc);
         else { c0[i] = Arith::mul_var(S0[i], S1[i], lc); c1[i] = add_mod(Arith::mul_var(S0[i], S2[i], lc), Arith::mul_var(S3[i], S1[i], lc), lc.q); c2[i] = Arith::mul_var(S3[i], S2[i], lc); }
     }
+    if (out_ntt) {
+        if constexpr (LAZY && Arith::kFold) {
+            std::vector<u64>* c[3] = {&c0, &c1, &c2};
+            for (int j = 0; j < 3; ++j)
+                for (int tid = 0; tid < T; ++tid) {
+                    u64(&r)[B::E] = regs_of<B>(*c[j], tid);
+                    for (int k = 0; k < B::E; ++k) r[k] = FoldArith::canon_small(r[k], lc);
+                    B::store_bot(tid, r, out3 + (size_t)j * N);
+                }
+            return 0;
+        }
+        return -1;
+    }
     inv(c0, out3);
     inv(c1, out3 + N);
     inv(c2, out3 + 2 * N);
     return 0;
+}
+// ct_mul_quad_kernel<FoldArith, 12, 4> as shipped: the lazy body on the bit-29 blob, coefficient-domain or NTT-domain output
+extern "C" int emu_ct_mul_lazy29(u64 q, u64 psi, int out_ntt, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    if (!fold_eligible(q)) return 2000;
+    return emu_ct_mul_path<FoldArith, 12, true, true>(q, psi, a0, a1, b0, b1, out3, out_ntt != 0);
+}
+// FoldArith::mul_tw29_add on the twiddle tables.h makes of w: the UNREDUCED word, through the very code the kernels run
+extern "C" u64 emu_fold_tw29(u64 d, u64 y, u64 w, u64 addend) {
+    LimbConst lc{};
+    lc.q = (1ull << 60) - d; lc.d = d;
+    return FoldArith::mul_tw29_add(y, h_tw_fold29(w, lc.q), lc, addend);
+}
+// The lazy plans of the N = 4096 geometry, one phase at a time (forward: phase p of the chain; inverse: phase p of the walk back, inputs below in_bound).
+// Forward rows [u][k]: red_a, K; inverse rows [u][k]: red, off.  tail[0 .. 16) = red_end, tail[16] = out_bound, tail[17] = n_red, tail[18 .. 34) = out (forward).
+extern "C" int emu_lazy29_plan(int inverse, int phase, int in_bound, int* flags, int* consts, int* tail) {
+    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, true, true> B;
+    if (phase < 0 || phase >= B::NPH) return 2000;
+    const Phase ph = B::G::phase(phase);
+    if (!inverse) {
+        const Ctf29Plan<4> p = make_ctf29_plan<4>(ph.b - ph.c + ph.r - 1, ph.r, in_bound, phase == B::NPH - 1 ? kWord : kCtf29Mid);
+        for (int u = 0; u < 4; ++u) for (int k = 0; k < 16; ++k) { flags[u * 16 + k] = p.red_a[u][k]; consts[u * 16 + k] = p.K[u][k]; }
+        for (int k = 0; k < 16; ++k) { tail[k] = p.red_end[k]; tail[18 + k] = p.out[k]; }
+        tail[16] = p.out_bound; tail[17] = p.n_red;
+    } else {
+        const Gs29Plan<4> p = make_gs29_plan<4>(ph.b - ph.c, ph.r, in_bound, phase == 0 ? 3 * kUnit / 2 : kGs29Mid, phase == 0, 12);
+        for (int u = 0; u < 4; ++u) for (int k = 0; k < 16; ++k) { flags[u * 16 + k] = p.red[u][k]; consts[u * 16 + k] = p.off[u][k]; }
+        for (int k = 0; k < 16; ++k) tail[k] = p.red_end[k];
+        tail[16] = p.out_bound; tail[17] = p.n_red;
+    }
+    return 0;
+}
+// what the shipped body compiles in: reductions per transform and thread, forward and inverse, and the hand-over bounds the phases were planned with
+extern "C" void emu_lazy29_totals(int* out) {
+    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, false, true> B;
+    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, true, true> BI;
+    out[0] = B::lazy_fwd_reductions<>(); out[1] = BI::lazy_inv_reductions<B::kProdInvIn>();
+    out[2] = B::ctf29_plan<0>().out_bound; out[3] = B::ctf29_plan<1>().out_bound; out[4] = B::ctf29_plan<2>().out_bound;
+    out[5] = kCtf29Mid; out[6] = kGs29Mid; out[7] = B::kProdInvIn;
 }
 template <bool LAZY>
 static int emu_ct_mul_any(int arith, int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
@@ -490,6 +556,7 @@ extern "C" int emu_ct_mul_lazy_class(int arith, int log2n, u64 q, u64 psi, const
     return emu_ct_mul_any<true>(arith, log2n, q, psi, a0, a1, b0, b1, out3);
 }
 extern "C" int emu_ct_mul(int log2n, u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3) {
+    if (log2n == 12) return fold_eligible(q) ? emu_ct_mul_path<FoldArith, 12, true, true>(q, psi, a0, a1, b0, b1, out3) : 2000;   // the quad form's lazy body (emu_ct_mul_lazy_class runs the paired form's)
     return emu_ct_mul_any<true>(kClassFold, log2n, q, psi, a0, a1, b0, b1, out3);
 }
 
