@@ -967,9 +967,8 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
     const char* what = "dpfhe_rotate_hybrid_hoisted";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
     if (int rc = check_extended(c, what)) return rc;
-    if (c->log2n > 14) return fail(DPFHE_INVALID_STATE, what, "available up to N = 16384");
     if (batch == 0 || n_items == 0) return DPFHE_SUCCESS;
-    const bool composed = c->log2n > (uint32_t)kMaxFusedLog2N;   // N = 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
+    const bool composed = c->log2n > (uint32_t)kMaxFusedLog2N;   // N >= 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
     if (!d_out2 || !d_in2 || !galois_elts || !d_keys || (!composed && (!d_work || !d_rotated0)) || !d_digits || misaligned(d_out2) || misaligned(d_in2) || misaligned(d_keys) ||
         misaligned(d_work) || misaligned(d_rotated0) || misaligned(d_digits))
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
@@ -987,7 +986,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
     const int chunks = (n + 511) / 512;
     if (composed) {
         DPFHE_ON_DEVICE(c, what);
-        // N = 16384 (round 5): no fused hoisted kernel - the deferred-division pipeline instead: dpfhe_rotate_hoisted_qp gives, per rotation and item,
+        // N >= 16384 (round 5; N = 32768, 65536 on the split transforms): no fused hoisted kernel - the deferred-division pipeline instead: dpfhe_rotate_hoisted_qp gives, per rotation and item,
         // P sigma_g(ct) + its key-switching term in the NTT domain over Q P; one inverse transform and the division by P per term finish it (the same words:
         // tests/test_rlwe_semantics.py).  Scratch (the Q P terms + the transformed inputs) from the stream's arena, rotations in slices under the scratch limit;
         // d_work / d_rotated0 are not used on this path.
@@ -1042,13 +1041,13 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
 // ------------------------------------------------------------------------------------------------
 // N3, round 3: baby-step / giant-step sums with the division by P DEFERRED (the rotated terms stay in the NTT domain over Q P)
 // ------------------------------------------------------------------------------------------------
-// (prepared = true: d_in_ntt, d_digits and item block 0 already hold what steps 1-3 write - a later slice of dpfhe_rotate_hybrid_hoisted at N = 16384)
+// (prepared = true: d_in_ntt, d_digits and item block 0 already hold what steps 1-3 write - a later slice of dpfhe_rotate_hybrid_hoisted at N >= 16384)
+// Every ring degree: the stream kernels take log2 N at run time (32-bit segment arithmetic modulo 2N <= 2^17), the transforms are ntt_launch_items'.
 static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
                                   uint64_t* d_in_ntt, uint64_t* d_digits, size_t batch, void* stream, bool prepared) {
     const char* what = "dpfhe_rotate_hoisted_qp";
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
     if (int rc = check_extended(c, what)) return rc;
-    if (c->log2n > 14) return fail(DPFHE_INVALID_STATE, what, "available up to N = 16384 (the stream kernels and the single-kernel transforms)");
     if (n_items == 0) return DPFHE_SUCCESS;
     if (!d_out_qp || !d_in2 || (batch && (!galois_elts || !d_keys)) || !d_in_ntt || !d_digits || misaligned(d_out_qp) || misaligned(d_in2) || misaligned(d_keys) ||
         misaligned(d_in_ntt) || misaligned(d_digits))
@@ -1062,7 +1061,7 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
         return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
     const size_t key_words = Ld * 2 * L * (size_t)n;
     const int chunks = (n + 511) / 512;
-    if ((batch + 1) * T * L * 8 > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid || T * 2 * L * (size_t)chunks > kMaxGrid)
+    if ((batch + 1) * T * L * 8 > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid || T * 2 * L * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, T * Ld * L))
         return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     const u64 p_special = c->p_special;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1122,9 +1121,27 @@ extern "C" int dpfhe_ntt_inv_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_
     if (int rc = check_galois_elts(c, galois_elts, n_elts, what)) return rc;
     const size_t per_elt = rns_polys_per_elt * c->n_limbs, words = n_elts * per_elt << c->log2n;
     if (d_out != d_in && overlaps(d_out, words, d_in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "output must be the input buffer or disjoint from it");
-    if (per_elt * (n_elts < (size_t)kMaxGaloisBatch ? n_elts : (size_t)kMaxGaloisBatch) > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    const bool split = split_log_n1((int)c->log2n) != 0;
+    // N > 16384: the sub-transforms of block b read block b' (ntt_core.h galois_sub_block) - in place, their output is staged in the stream's arena, elements in
+    // slices under the scratch limit (each slice: in -> scratch -> out, the same 4 N words of traffic per polynomial as the plain split inverse)
+    const size_t group = split && d_out == d_in ? slice_items(c, n_elts < (size_t)kMaxGaloisBatch ? n_elts : (size_t)kMaxGaloisBatch, per_elt << c->log2n) : (size_t)kMaxGaloisBatch;
+    if (!ntt_grid_fits(c, per_elt * (n_elts < group ? n_elts : group))) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (split) {
+        StreamScratch ws(c, s);
+        if (d_out == d_in) if (int rc = ws.alloc((n_elts < group ? n_elts : group) * per_elt << c->log2n, what)) return rc;
+        for (size_t first = 0; first < n_elts; first += group) {
+            const size_t cnt = n_elts - first < group ? n_elts - first : group;
+            const size_t off = first * per_elt << c->log2n;
+            u64* mid = d_out == d_in ? ws.p : d_out + off;
+            const int rc = c->fold ? launch_ntt_inv_galois_split((int)c->log2n, d_out + off, mid, d_in + off, galois_elts + first, cnt, per_elt, c->foldt, s)
+                                   : launch_ntt_inv_galois_split((int)c->log2n, d_out + off, mid, d_in + off, galois_elts + first, cnt, per_elt, c->shoup, s);
+            if (rc) return fail(DPFHE_INVALID_STATE, what, "no split transform for this context");
+            if (int e = check_launch("ntt_inv_galois kernel launch")) return e;
+        }
+        return DPFHE_SUCCESS;
+    }
     for (size_t first = 0; first < n_elts; first += kMaxGaloisBatch) {
         const size_t cnt = n_elts - first < (size_t)kMaxGaloisBatch ? n_elts - first : (size_t)kMaxGaloisBatch;
         const size_t off = first * per_elt << c->log2n;

@@ -56,6 +56,15 @@ const uint64_t kPrimes60N14[kChainPrimes14][2] = {
     {1152921504606748673ull, 62213374832584ull}, {1152921504606683137ull, 212089012217363ull}, {1152921504606584833ull, 92166579128688ull},
     {1152921504605962241ull, 74756755228070ull}, {1152921504604979201ull, 52069629205452ull}, {1152921504600260609ull, 27543819356734ull},
     {1152921504599080961ull, 92056553354496ull}, {1152921504598720513ull, 89492317149395ull}};
+// the 14 largest primes below 2^60 that are 1 mod 2^16 (deeppowers_amd/params.py ntt_primes(15, 14)): {q, smallest primitive 65536-th root}; the first 8 are
+// 2^60 - d with d < 2^24 (fold primes)
+constexpr size_t kChainPrimes15 = 14;
+const uint64_t kPrimes60N15[kChainPrimes15][2] = {
+    {1152921504606584833ull, 4443670208963ull}, {1152921504598720513ull, 100545759574150ull}, {1152921504597016577ull, 31693996050849ull},
+    {1152921504595968001ull, 88651361085495ull}, {1152921504595640321ull, 9679305630873ull}, {1152921504593412097ull, 24428769072221ull},
+    {1152921504592822273ull, 18776242964106ull}, {1152921504592429057ull, 5821397352863ull}, {1152921504589938689ull, 33888991361320ull},
+    {1152921504586530817ull, 74969624337902ull}, {1152921504585547777ull, 64462945958447ull}, {1152921504583647233ull, 6656235313685ull},
+    {1152921504581877761ull, 18584577086900ull}, {1152921504581419009ull, 34653674914762ull}};
 }  // namespace
 
 FheParams FheParams::drop_last_limb() const {
@@ -82,6 +91,13 @@ FheParams FheParams::n16384(size_t n_limbs) {
     if (n_limbs == 0 || n_limbs > kChainPrimes14) throw Exception(ErrorCode::INVALID_ARGUMENT, "FheParams::n16384: 1..8 limbs");
     FheParams p{14, {}, {}};
     for (size_t i = 0; i < n_limbs; ++i) { p.moduli.push_back(kPrimes60N14[i][0]); p.psi.push_back(kPrimes60N14[i][1]); }
+    return p;
+}
+
+FheParams FheParams::n32768(size_t n_limbs) {
+    if (n_limbs == 0 || n_limbs > kChainPrimes15) throw Exception(ErrorCode::INVALID_ARGUMENT, "FheParams::n32768: 1..14 limbs");
+    FheParams p{15, {}, {}};
+    for (size_t i = 0; i < n_limbs; ++i) { p.moduli.push_back(kPrimes60N15[i][0]); p.psi.push_back(kPrimes60N15[i][1]); }
     return p;
 }
 

@@ -2,6 +2,7 @@
 namespace dpfhe {
 template int launch_ntt<FoldArith>(int, bool, u64*, const u64*, size_t, const DevTables<FoldArith>&, hipStream_t);
 template int launch_ntt_inv_galois<FoldArith>(int, u64*, const u64*, const unsigned*, size_t, size_t, const DevTables<FoldArith>&, hipStream_t);
+template int launch_ntt_inv_galois_split<FoldArith>(int, u64*, u64*, const u64*, const unsigned*, size_t, size_t, const DevTables<FoldArith>&, hipStream_t);
 }
 #ifdef DPFHE_DIAGNOSTICS   // diagnostic builds only: 8 words per workgroup of the last traced forward transform (kernels_trace.h)
 extern "C" int dpfhe_debug_ntt_trace_read(unsigned long long* host, size_t max_blocks) {

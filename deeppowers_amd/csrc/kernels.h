@@ -415,7 +415,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_galois_kernel(u64*
     u64 x[E];
     if constexpr (B::kLdsIO) {   // coalesced 16-byte loads of the wave's source region, permuted through its LDS rows (ntt_core.h stage_gather)
         unsigned addr[E];
-        const long shift = B::gather_plan(tid, g, addr);
+        const long shift = B::gather_plan(tid, g, (g - 1u) >> 1, addr);
         u64 v[E];
         B::stage_load(tid, v, src + shift);
         B::stage_gather(tid, x, v, lds, addr);
@@ -432,6 +432,40 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_galois_kernel(u64*
     InvChain<B, B::NPH - 1, kUnit>::run_with(tid, x, lds, tw, last, lc, tw_first);
     B::inv_canon(x, lc);
     B::store_top(tid, x, out + p * N);
+}
+
+// The same at N > 16384, where the inverse transform is split (ntt_top.h): this kernel runs the N1 sub-transforms of a polynomial, the unchanged
+// ntt_top_kernel follows.  Sub-block b of NTT(sigma_g a) is a permutation of ONE sub-block b' of NTT(a) (ntt_core.h galois_sub_block), read with the same
+// coalesced loads and LDS gather as above - only the affine map's offset depends on the sub-block.  b' != b in general, so `out` must not be `in`: an in-place
+// caller stages this kernel's output in scratch (dpfhe_cabi.hip dpfhe_ntt_inv_galois).  One workgroup per (polynomial, sub-block); uniform contexts only.
+template <class Arith, int LOG_N1>
+__global__ __launch_bounds__(1 << (kSplitLog2N2 - 4)) void ntt_inv_galois_sub_kernel(u64* __restrict__ out, const u64* __restrict__ in, GaloisElts elts,
+                                                                                      unsigned polys_per_elt, DevTables<Arith> tb) {
+    typedef NttBody<Arith, kSplitLog2N2, 4> B;
+    constexpr int E = B::E, N2 = B::G::N;
+    static_assert(B::kLdsIO, "the sub-transforms gather through the wave's LDS rows");
+    __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
+    const int tid = threadIdx.x;
+    const size_t poly = blockIdx.x >> LOG_N1;
+    const unsigned b = blockIdx.x & ((1u << LOG_N1) - 1u);
+    const int limb = (int)(poly % (size_t)tb.n_limbs);
+    const unsigned g = elts.v[poly / polys_per_elt];
+    const GaloisSub gs = galois_sub_block<LOG_N1>(g, b, kSplitLog2N2);
+    const LimbConst lc = tb.lc[limb];
+    const size_t slot = ((size_t)limb << LOG_N1) + b;
+    const typename B::Tw* tw = tb.inv + slot * N2;
+    const InvLast<typename B::Tw> last = tb.last[slot];
+    typename B::TwRegs tw_first;
+    B::template load_tw<B::NPH - 1, false>(tid, tw, tw_first);
+    const u64* src = in + ((poly << LOG_N1) + gs.block) * N2;
+    u64 x[E], v[E];
+    unsigned addr[E];
+    const long shift = B::gather_plan(tid, g, gs.h, addr);
+    B::stage_load(tid, v, src + shift);
+    B::stage_gather(tid, x, v, lds, addr);
+    InvChain<B, B::NPH - 1, kUnit>::run_with(tid, x, lds, tw, last, lc, tw_first);
+    B::inv_canon(x, lc);
+    B::store_top(tid, x, out + (size_t)blockIdx.x * N2);
 }
 
 // ------------------------------------------------------------------------------------------------

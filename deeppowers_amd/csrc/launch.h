@@ -52,5 +52,8 @@ int launch_hoisted_ks(int log2n, u64* work, const u64* digits, const u64* keys, 
 // out = sigma_g(INTT(in)), the automorphism applied as a gather in the NTT domain; `polys_per_elt` residue polynomials per element (<= 64 elements)
 template <class Arith>
 int launch_ntt_inv_galois(int log2n, u64* out, const u64* in, const unsigned* elts, size_t n_elts, size_t polys_per_elt, const DevTables<Arith>& tb, hipStream_t s);
+// the same on the split transforms of N = 2^15, 2^16 (FoldArith / ShoupArith, uniform contexts): sub-transforms in -> mid, column stages mid -> out; mid != in
+template <class Arith>
+int launch_ntt_inv_galois_split(int log2n, u64* out, u64* mid, const u64* in, const unsigned* elts, size_t n_elts, size_t polys_per_elt, const DevTables<Arith>& tb, hipStream_t s);
 
 }  // namespace dpfhe

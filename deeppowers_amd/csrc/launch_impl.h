@@ -276,7 +276,7 @@ int launch_hoisted_ks(int log2n, u64* work, const u64* digits, const u64* keys, 
 
 template <class Arith>
 int launch_ntt_inv_galois(int log2n, u64* out, const u64* in, const unsigned* elts, size_t n_elts, size_t polys_per_elt, const DevTables<Arith>& tb, hipStream_t s) {
-    if (tb.n_sub != 1 || n_elts > (size_t)kMaxGaloisBatch) return -1;   // split transforms (N > 16384) have no gather form; callers chunk by kMaxGaloisBatch
+    if (tb.n_sub != 1 || n_elts > (size_t)kMaxGaloisBatch) return -1;   // split transforms (N > 16384): launch_ntt_inv_galois_split; callers chunk by kMaxGaloisBatch
     GaloisElts ge{};
     for (size_t i = 0; i < n_elts; ++i) ge.v[i] = elts[i];
     // polys_per_elt counts residue polynomials over ALL limbs; a class launch covers n_active of every n_limbs of them
@@ -286,6 +286,24 @@ int launch_ntt_inv_galois(int log2n, u64* out, const u64* in, const unsigned* el
     hipLaunchKernelGGL((ntt_inv_galois_kernel<Arith, LN, LE>), dim3(grid), dim3(Geo<LN, LE>::T), 0, s, out, in, ge, (unsigned)polys_per_elt, tb)
     DPFHE_NTT_GEO_SWITCH(log2n, NG_CASE)
 #undef NG_CASE
+    return 0;
+}
+
+// N = 2^15, 2^16: the sub-transforms gather `in` into `mid`, the column stages go from `mid` to `out` (mid == out, or scratch when out == in)
+template <class Arith>
+int launch_ntt_inv_galois_split(int log2n, u64* out, u64* mid, const u64* in, const unsigned* elts, size_t n_elts, size_t polys_per_elt, const DevTables<Arith>& tb, hipStream_t s) {
+    if (tb.n_active || tb.n_sub != (1 << split_log_n1(log2n)) || n_elts > (size_t)kMaxGaloisBatch || mid == in) return -1;
+    GaloisElts ge{};
+    for (size_t i = 0; i < n_elts; ++i) ge.v[i] = elts[i];
+    const size_t npolys = n_elts * polys_per_elt;
+    const unsigned top_grid = (unsigned)(npolys << (kSplitLog2N2 - 8));
+#define NGS_CASE(LOG_N1)                                                                                                                                              \
+    hipLaunchKernelGGL((ntt_inv_galois_sub_kernel<Arith, LOG_N1>), dim3((unsigned)(npolys << LOG_N1)), dim3(Geo<kSplitLog2N2, 4>::T), 0, s, mid, in, ge, (unsigned)polys_per_elt, tb); \
+    hipLaunchKernelGGL((ntt_top_kernel<Arith, LOG_N1, false>), dim3(top_grid), dim3(256), 0, s, out, mid, tb, kSplitLog2N2)
+    if (log2n == 15) { NGS_CASE(3); }
+    else if (log2n == 16) { NGS_CASE(4); }
+    else return -1;
+#undef NGS_CASE
     return 0;
 }
 

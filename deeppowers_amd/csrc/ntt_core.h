@@ -48,6 +48,29 @@ DPF_HD u64 chk_add(u64 a, u64 b) { return a + b; }
 DPF_HD u64 chk_sub_add(u64 a, u64 b, u64 off) { return a - b + off; }
 #endif
 
+// 32-bit bit reversal (v_bfrev_b32 on the device)
+DPF_HD unsigned brev32(unsigned x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __brev(x);
+#else
+    x = (x >> 16) | (x << 16);
+    x = ((x & 0xff00ff00u) >> 8) | ((x & 0x00ff00ffu) << 8);
+    x = ((x & 0xf0f0f0f0u) >> 4) | ((x & 0x0f0f0f0fu) << 4);
+    x = ((x & 0xccccccccu) >> 2) | ((x & 0x33333333u) << 2);
+    return ((x & 0xaaaaaaaau) >> 1) | ((x & 0x55555555u) << 1);
+#endif
+}
+// Sub-block b of a split transform (N = N1 N2, ntt_top.h) under sigma_g.  Position k = b N2 + k_low of the forward output holds exponent
+// e = 2 brv_N(k) + 1 = 2 N1 r + c with r = brv_N2(k_low) and c = 2 brv_N1(b) + 1, so g e = 2 N1 (g r + floor(g c / 2 N1)) + (g c mod 2 N1): every word
+// of sub-block b comes from ONE source sub-block (that of g c mod 2 N1), at r' = (g r + h) mod N2 - NttBody::gather_plan's map with this h.
+struct GaloisSub { unsigned block, h; };
+template <int LOG_N1>
+DPF_HD GaloisSub galois_sub_block(unsigned g, unsigned b, int log2_n2) {
+    const unsigned c = 2u * (brev32(b) >> (32 - LOG_N1)) + 1u, gc = g * c;   // g < 2N <= 2^17, c < 2 N1 <= 32
+    const unsigned c2 = gc & ((2u << LOG_N1) - 1u);
+    return GaloisSub{brev32((c2 - 1u) >> 1) >> (32 - LOG_N1), (gc >> (LOG_N1 + 1)) & ((1u << log2_n2) - 1u)};
+}
+
 // ------------------------------------------------------------------------------------------------
 // geometry
 // ------------------------------------------------------------------------------------------------
@@ -551,6 +574,7 @@ struct NttBody {
         const unsigned t = wave_thread0 + (((unsigned)r << kLow) | (lane & ((1u << kLow) - 1u)));
         return t * PC + (lane >> kLow);
     }
+#endif
     // The same transposition through LDS instead of registers: no VALU work at all (the kernels are VALU-bound, the LDS
     // pipe is ~10 % busy).  Each thread's E words live in its own padded row (E + 2 words: conflict-free 16-byte accesses);
     // a wave only ever touches the rows of its own 64 threads, which are also exactly what it read in the last forward
@@ -560,12 +584,13 @@ struct NttBody {
     // Both results are a per-thread base (slice 0) plus a compile-time multiple of r - written that way so that ONE address register
     // and immediate offsets serve all eight slices (left as lds_row(thread of slice r) the compiler rebuilds every address with
     // bit-field arithmetic: ~30 VALU instructions per transform).
-    static __device__ __forceinline__ void lds_slice(int tid, int r, unsigned& lds_word, unsigned& piece) {
+    static DPF_HD void lds_slice(int tid, int r, unsigned& lds_word, unsigned& piece) {
         const unsigned lane = (unsigned)tid & 63u, wave_thread0 = (unsigned)tid & ~63u, i = lane & 7u, pc = ((lane >> 3) + i) & 7u;
         const unsigned base_w = (unsigned)G::lds_row((int)(wave_thread0 + i)) + pc * 2, base_p = (wave_thread0 + i) * PC + pc;   // thread 8 r + i of the wave, r = 0
         lds_word = base_w + (unsigned)r * (8u * (E + 2));
         piece = base_p + (unsigned)r * (8u * PC);
     }
+#if defined(__HIP_DEVICE_COMPILE__)
     template <bool NT = false>
     static __device__ __forceinline__ void load_bot_lds(int tid, u64 (&x)[E], const u64* g, u64* lds) {
         const V2* p = reinterpret_cast<const V2*>(g);
@@ -582,6 +607,7 @@ struct NttBody {
 #pragma clang loop unroll(full)
         for (int k = 0; k < PC; ++k) { V2 t = row[k]; x[2 * k] = t.a; x[2 * k + 1] = t.b; }
     }
+#endif
     // The same staging in two halves, for callers that want the global loads in flight while they compute: stage_load requests the
     // wave's 64 E-word region (lane-contiguous 16-byte pieces), stage_rows / stage_gather put it through the wave's LDS rows.
     // stage_gather reads word k of the thread from LDS word addr[k] instead of its own row: the Galois permutation in the NTT domain
@@ -589,15 +615,16 @@ struct NttBody {
     // so a thread's E source words sit in ONE row and a wave's sources in ONE 64 E-word region - `g` is then the polynomial shifted
     // by (source region - own region) * 64 E words, and no 8-byte global gather is left.  Rows are wave-private: wavefront-scope
     // ordering only (the LDS runs one wave's DS instructions in order); the caller fences before reusing the rows.
-    static __device__ __forceinline__ void stage_load(int tid, u64 (&v)[E], const u64* g) {   // plain words: struct arrays carried around a loop stay in scratch
+    static DPF_HD void stage_load(int tid, u64 (&v)[E], const u64* g) {   // plain words: struct arrays carried around a loop stay in scratch
         const V2* p = reinterpret_cast<const V2*>(g);
 #pragma clang loop unroll(full)
         for (int r = 0; r < PC; ++r) { unsigned w, pc; lds_slice(tid, r, w, pc); const V2 t = p[pc]; v[2 * r] = t.a; v[2 * r + 1] = t.b; }
     }
-    static __device__ __forceinline__ void stage_write(int tid, const u64 (&v)[E], u64* lds) {
+    static DPF_HD void stage_write(int tid, const u64 (&v)[E], u64* lds) {
 #pragma clang loop unroll(full)
         for (int r = 0; r < PC; ++r) { unsigned w, pc; lds_slice(tid, r, w, pc); *reinterpret_cast<V2*>(lds + w) = V2{v[2 * r], v[2 * r + 1]}; }
     }
+#if defined(__HIP_DEVICE_COMPILE__)
     static __device__ __forceinline__ void stage_rows(int tid, u64 (&x)[E], const u64 (&v)[E], u64* lds) {
         stage_write(tid, v, lds);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -608,34 +635,47 @@ struct NttBody {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+#endif
+    // the read half of stage_gather, on its own for tools/emulate.cpp (which runs a wave's writes, then its reads)
+    static DPF_HD void gather_read(u64 (&x)[E], const u64* lds, const unsigned (&addr)[E]) {
+#pragma clang loop unroll(full)
+        for (int k = 0; k < E; ++k) x[k] = lds[addr[k]];
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
     static __device__ __forceinline__ void stage_gather(int tid, u64 (&x)[E], const u64 (&v)[E], u64* lds, const unsigned (&addr)[E]) {
         stage_write(tid, v, lds);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-#pragma clang loop unroll(full)
-        for (int k = 0; k < E; ++k) x[k] = lds[addr[k]];
+        gather_read(x, lds, addr);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+#endif
     // source addressing of stage_gather for the thread's E output positions tid E + k under sigma_g: LDS word addresses of the
-    // source words, and the region shift (in words) to add to the polynomial's base
-    static __device__ __forceinline__ long gather_plan(int tid, unsigned g, unsigned (&addr)[E]) {
+    // source words, and the region shift (in words) to add to the polynomial's base.  With r = brv(position) the source has
+    // r' = (g r + h) mod N: h = (g - 1) / 2 in a one-piece transform (2 r' + 1 = g (2 r + 1) mod 2N); in sub-block b of a split
+    // transform the sub-block's own offset (galois_sub_block below).  The map is affine in r, so the block property above holds for any h.
+    static DPF_HD long gather_plan(int tid, unsigned g, unsigned h, unsigned (&addr)[E]) {
         unsigned src0 = 0;
 #pragma clang loop unroll(full)
         for (int k = 0; k < E; ++k) {
             const unsigned p = (unsigned)tid * E + k;
-            const unsigned e = 2u * (__brev(p) >> (32 - LOGN)) + 1u;
-            const unsigned e2 = (g * e) & (2u * G::N - 1u);
-            const unsigned sp = __brev((e2 - 1u) >> 1) >> (32 - LOGN);
+            const unsigned r = brev32(p) >> (32 - LOGN);
+            const unsigned sp = brev32((g * r + h) & (unsigned)(G::N - 1)) >> (32 - LOGN);
             if (k == 0) src0 = sp;
             addr[k] = sp & (E - 1);
         }
         const unsigned row = (unsigned)G::lds_row((int)(((unsigned)tid & ~63u) + ((src0 >> LOGE) & 63u)));
 #pragma clang loop unroll(full)
         for (int k = 0; k < E; ++k) addr[k] += row;
+#if defined(__HIP_DEVICE_COMPILE__)
         const int region = __builtin_amdgcn_readfirstlane((int)(src0 >> (6 + LOGE)));     // wave-uniform
+#else
+        const int region = (int)(src0 >> (6 + LOGE));
+#endif
         return ((long)region - (long)(tid >> 6)) * (long)(64 * E);
     }
+#if defined(__HIP_DEVICE_COMPILE__)
     template <bool NT = false>
     static __device__ __forceinline__ void store_bot_lds(int tid, const u64 (&x)[E], u64* g, u64* lds) {
         V2* row = reinterpret_cast<V2*>(lds + (unsigned)G::lds_row(tid));
@@ -652,10 +692,8 @@ struct NttBody {
     }
 #endif
 #if !defined(__HIP_DEVICE_COMPILE__)
-    static void stage_load(int, u64 (&)[E], const u64*) {}
     static void stage_rows(int, u64 (&)[E], const u64 (&)[E], u64*) {}
     static void stage_gather(int, u64 (&)[E], const u64 (&)[E], u64*, const unsigned (&)[E]) {}
-    static long gather_plan(int, unsigned, unsigned (&)[E]) { return 0; }
     template <bool NT = false> static DPF_HD void load_bot_lds(int, u64 (&)[E], const u64*, u64*) {}   // device-only paths: never called on the host
     template <bool NT = false> static DPF_HD void store_bot_lds(int, const u64 (&)[E], u64*, u64*) {}
 #endif

@@ -538,7 +538,8 @@ class Evaluator:
         return out
 
     def ntt_inverse_galois(self, t: torch.Tensor, galois_elts, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
-        """t: [len(elts)][...][L][N] NTT domain -> sigma_{g_e}(INTT(t[e])) (the automorphism as a gather in the NTT domain)."""
+        """t: [len(elts)][...][L][N] NTT domain -> sigma_{g_e}(INTT(t[e])) (the automorphism as a gather in the NTT domain).  out may be t itself;
+        at log2_n >= 15 an in-place call stages through the context's scratch arena (Context.scratch_bytes)."""
         self._chk(t)
         k = len(galois_elts)
         if t.shape[0] != k:

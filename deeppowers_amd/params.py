@@ -92,6 +92,14 @@ class FheParams:
         exact multiplies at higher levels (include/deeppowers/fhe.hpp FheParams::n8192 tabulates the first 20)."""
         return ntt_primes(13, n_limbs)
 
+    @staticmethod
+    def n32768(n_limbs: int) -> "FheParams":
+        """N=32768 on the first n_limbs (1..14) primes of ntt_primes(15, .) (include/deeppowers/fhe.hpp FheParams::n32768 tabulates them): the ring
+        whose 128-bit budget (881 bits) holds two or three activated blocks.  The first 8 primes are fold primes (2^60 - d, d < 2^24: 480 bits on the
+        fast arithmetic); a context that holds any of primes 9..14 runs the context-wide generic arithmetic on every limb."""
+        if not 1 <= n_limbs <= 14:
+            raise ValueError("FheParams.n32768: 1..14 limbs")
+        return ntt_primes(15, n_limbs)
 
     @staticmethod
     def generic_n4096_l4() -> "FheParams":

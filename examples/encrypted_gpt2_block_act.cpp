@@ -6,14 +6,15 @@
 // to two limbs, the activation is an EXACT ciphertext x ciphertext multiply (ExactMultiplier: the fused tensor-product kernel, i.e. the
 // metric op, inside the forward) + relinearisation, and W_down and the residual run on two limbs.  Every stage is decrypted and compared
 // with the plaintext computation; the noise budget is reported after every stage (six levels: qkv, the v mask, W_o, W_up, the square, W_down).
-//   usage: encrypted_gpt2_block_act [tokens = 4] [reps = 2] [json | text] [ladder | flat] [log2_n = 13 | 14] [tokens_per_ciphertext = 1 | 2]
+//   usage: encrypted_gpt2_block_act [tokens = 4] [reps = 2] [json | text] [ladder | flat] [log2_n = 13 | 14 | 15] [tokens_per_ciphertext = 1 | 2]
 // tokens_per_ciphertext = 2 (round 6): the two slot rows of a ciphertext carry two tokens (PackedLinear's two-token packing): the same kernels, half the
 // ciphertexts - every stage is still decrypted and compared for BOTH rows.
 // STAND-INS (what this is not): x^2 for GELU, no LayerNorm, attention = v (exact at one position only), ONE of the reference's 12 blocks, no LM head.
 // SECURITY: at N = 8192 the 360-bit modulus under key switching is far beyond the 218 bits the Homomorphic Encryption Standard allows at 128-bit security
 // (ternary secret, sigma = 3.2): that ring is BASELINE configs[4]'s, a performance shape, not a deployable parameter set.  log2_n = 14 runs the same block
 // on six primes = 1 mod 2^15 at N = 16384, where 360 bits are inside the 438-bit budget of 128-bit security (the key switches and the multiply are then
-// composed from the batched transforms: slower per token, but a parameter set with a margin).
+// composed from the batched transforms: slower per token, but a parameter set with a margin).  log2_n = 15: the same block on FheParams::n32768(6) at
+// N = 32768 - 360 of the 881 bits that ring allows, the room encrypted_gpt2_stack uses for further blocks.
 // `ladder`: the modulus falls WITH the noise budget inside the block: qkv on 5 limbs, the v hand-over and W_o on 4, W_up on 3, the square and W_down on 2.
 #include <chrono>
 #include <cstdio>
@@ -50,13 +51,13 @@ int main(int argc, char** argv) {
     // cost goes with digits x limbs: 30 / 20 / 12 / 6 instead of 30 / 30 / 30 / 6); default: the attention half and W_up all on 5 limbs
     const bool ladder = argc > 4 && !std::strcmp(argv[4], "ladder");
     const int log2n = argc > 5 ? std::atoi(argv[5]) : 13;
-    if (log2n != 13 && log2n != 14) { std::fprintf(stderr, "log2_n must be 13 or 14\n"); return 1; }
+    if (log2n < 13 || log2n > 15) { std::fprintf(stderr, "log2_n must be 13, 14 or 15\n"); return 1; }
     const size_t tpc = argc > 6 ? (size_t)std::atol(argv[6]) : 1;
     if ((tpc != 1 && tpc != 2) || T % tpc) { std::fprintf(stderr, "tokens_per_ciphertext must be 1 or 2 and divide the token count\n"); return 1; }
     const size_t C = T / tpc;   // ciphertexts per application
     const int lv_attn = ladder ? 4 : 5, lv_up = ladder ? 3 : 5;
     try {
-        FheParams p5 = log2n == 14 ? FheParams::n16384(6) : FheParams::n8192_l6();
+        FheParams p5 = log2n == 15 ? FheParams::n32768(6) : log2n == 14 ? FheParams::n16384(6) : FheParams::n8192_l6();
         const uint64_t special = p5.moduli.back(), special_psi = p5.psi.back();
         p5.moduli.pop_back(); p5.psi.pop_back();
         FheParams pl[6];
@@ -147,7 +148,7 @@ int main(int argc, char** argv) {
             } else {
                 packed = &cu; spare = &cur;                                // two tokens per ciphertext: every row already holds ITS token's W_up outputs
             }
-            for (uint32_t e : spread) {                                    // (N = 16384 only: the period-4096 copies inside a slot row)
+            for (uint32_t e : spread) {                                    // (N >= 16384 only: the period-4096 copies inside a slot row)
                 hks[lv_up]->apply_galois_many(*packed, std::vector<uint32_t>(C, e), cus);
                 ev[lv_up]->add(*packed, cus, *spare);
                 std::swap(packed, spare);
@@ -205,7 +206,7 @@ int main(int argc, char** argv) {
             std::printf("{\"block\": \"transformer_block_square_activation\", \"hidden\": %zu, \"inner\": %zu, \"log2_n\": %d, \"modulus_bits_under_key_switching\": 360, \"he_standard_128bit_budget_bits\": %d, \"levels\": \"%s\", "
                         "\"plain_modulus\": %llu, \"tokens\": %zu, \"tokens_per_ciphertext\": %zu, \"key_switches_per_token\": %zu, \"ct_ct_multiplies_per_token\": 1, \"setup_s\": %.2f, \"ms_per_token\": %.3f, "
                         "\"budget_bits\": [%.0f, %.0f, %.0f, %.0f, %.0f, %.0f, %.0f, %.0f], \"correct\": %s}\n",
-                        D, H, log2n, log2n == 14 ? 438 : 218, levels, (unsigned long long)TM, T, tpc, ks, setup_s, ms_per_token, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], ok ? "true" : "false");
+                        D, H, log2n, log2n == 15 ? 881 : log2n == 14 ? 438 : 218, levels, (unsigned long long)TM, T, tpc, ks, setup_s, ms_per_token, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], ok ? "true" : "false");
         else
             std::printf("transformer block with a square activation (%s), %zu token(s) per application, %zu key switches + one ct x ct multiply per token; setup %.2f s, %.3f ms per token\n"
                         "  noise budget (bits): fresh %.0f -> qkv %.0f -> v hand-over %.0f -> h1 %.0f -> W_up hand-over %.0f -> 2 limbs %.0f -> squared %.0f -> h2 %.0f\n"

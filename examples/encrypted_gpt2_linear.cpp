@@ -3,12 +3,14 @@
 // Z_65537 by the diagonal method with baby-step / giant-step rotations (deeppowers::fhe::PackedLinear).
 // The layer shapes are the reference's matmul sites (/root/reference/src/core/execution/models/gpt_model.cpp:793 QKV 768 -> 2304,
 // :848 FFN 768 -> 3072 -> 768, :883 logits 768 -> 50257; hidden_size 768, vocab 50257 at execution/model.hpp:47-50).
-//   usage: encrypted_gpt2_linear [layer = all | square | qkv | ffn_up | ffn_down | lm_head | <out>x<in>] [reps = 2] [json | text] [tokens = 1] [log2_n = 13 | 14] [tokens_per_ciphertext = 1 | 2]
+//   usage: encrypted_gpt2_linear [layer = all | square | qkv | ffn_up | ffn_down | lm_head | <out>x<in>] [reps = 2] [json | text] [tokens = 1] [log2_n = 13 | 14 | 15] [tokens_per_ciphertext = 1 | 2]
 // tokens_per_ciphertext = 2 (round 6): the two slot rows of a ciphertext carry two tokens (PackedLinear's two-token packing) - the same kernels on half the ciphertexts.
 // WHAT THIS IS: single dense layers (matrix x encrypted vector over Z_65537), nothing else of the model.  SECURITY: at the default N = 8192 the 360-bit modulus
 // under key switching is beyond the 218 bits of 128-bit security at that ring (Homomorphic Encryption Standard): a performance shape (BASELINE configs[4]).
 // log2_n = 14: the same layer at N = 16384 on six primes that are 1 mod 2^15 (round 5: the packed pipeline's rotations above N = 8192 are composed
 // from the batched transforms; a 360-bit modulus under key switching at N = 16384 is inside the 128-bit-security budget of 438 bits).
+// log2_n = 15: N = 32768 on FheParams::n32768(6) - the same 360 bits under key switching against the 881-bit budget of that ring, the one with room for
+// several activated blocks (encrypted_gpt2_stack); the Galois inverse and the hoisted rotations run on the split transforms there.
 // Prints one line per layer; with a third argument "json" the lines are JSON objects (bench.py other_configs.packed_linear).
 // tokens > 1: that many encrypted hidden states go through the layer in ONE application (keys and diagonals read once).
 #include <chrono>
@@ -30,7 +32,7 @@ int main(int argc, char** argv) {
     const bool json = argc > 3 && !std::strcmp(argv[3], "json");
     const size_t T = argc > 4 ? (size_t)std::atol(argv[4]) : 1;
     const int log2n = argc > 5 ? std::atoi(argv[5]) : 13;
-    if (log2n != 13 && log2n != 14) { std::fprintf(stderr, "log2_n must be 13 or 14\n"); return 1; }
+    if (log2n < 13 || log2n > 15) { std::fprintf(stderr, "log2_n must be 13, 14 or 15\n"); return 1; }
     const size_t tpc = argc > 6 ? (size_t)std::atol(argv[6]) : 1;
     if ((tpc != 1 && tpc != 2) || T % tpc) { std::fprintf(stderr, "tokens_per_ciphertext must be 1 or 2 and divide the token count\n"); return 1; }
     const size_t C = T / tpc;   // ciphertexts per application
@@ -44,7 +46,7 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown layer '%s'\n", which.c_str()); return 1; }
     }
     try {
-        FheParams p = log2n == 14 ? FheParams::n16384(6) : FheParams::n8192_l6();
+        FheParams p = log2n == 15 ? FheParams::n32768(6) : log2n == 14 ? FheParams::n16384(6) : FheParams::n8192_l6();
         const uint64_t special = p.moduli.back(), special_psi = p.psi.back();
         p.moduli.pop_back(); p.psi.pop_back();
         const size_t n = p.n();

@@ -9,11 +9,14 @@
 // ciphertext x ciphertext multiply (ExactMultiplier around the fused tensor-product kernel, the metric op) at whatever level the chain is on
 // at that point (five limbs in the first of two blocks: an eleven-limb workspace).  Every block's output is decrypted and compared with the
 // plaintext forward; the budget is read after every level.
-//   usage: encrypted_gpt2_stack [tokens = 4] [reps = 1] [json | text] [data_limbs = 7] [blocks = 0: as many as the budget model allows]
+//   usage: encrypted_gpt2_stack [tokens = 4] [reps = 1] [json | text] [data_limbs = 7] [blocks = 0: as many as the budget model allows] [tokens_per_ciphertext = 1 | 2] [log2_n = 13 | 15]
+// log2_n = 15: the same stack at N = 32768 on FheParams::n32768 - the ring such a chain needs: 7 data limbs + P (two blocks) are 480 bits and 10 + P (three) 660 bits
+// under key switching, inside the 881 bits the Homomorphic Encryption Standard allows there at 128-bit security.  7 + P is the chain's all-fold head; a context
+// that reaches past its 8 fold primes - 10 + P, and the 2 l + 1 limb workspace of a square at l >= 4 limbs - runs the generic arithmetic on every limb.
 // STAND-INS: x^2 for GELU, no LayerNorm, attention = v (exact at one position only), at most 3 of the reference's 12 blocks, no LM head.
 // SECURITY: NONE TO SPEAK OF - N = 8192 with 7 ... 20 data primes + special prime is 480 ... 1260 bits under key switching against the 218 bits of 128-bit security
 // at that ring (Homomorphic Encryption Standard).  This program demonstrates the budget arithmetic of a deep chain (limb count per level planned from a noise model,
-// exact multiplies at several levels), not a deployable forward pass; a chain this long needs N >= 32768.
+// exact multiplies at several levels), not a deployable forward pass; a chain this long needs N >= 32768: log2_n = 15.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -43,9 +46,15 @@ void matvec(const std::vector<uint64_t>& W, size_t rows, size_t cols, const uint
 }
 // the budget model the level schedule is planned with (a server has no secret key to measure with): bits a level consumes, and what is
 // left right after a switch to l limbs at the most (60 l minus log2 t, the rounding noise of the switch and its key-switch floor)
-const double kCost[6] = {27, 25, 26, 27, 30, 28};   // qkv, v mask, W_o, W_up, square, W_down  (measured 26 / 23 / 25 / 25 / 29 / 27)
+const double kCost13[6] = {27, 25, 26, 27, 30, 28};   // qkv, v mask, W_o, W_up, square, W_down  (measured 26 / 23 / 25 / 25 / 29 / 27)
+// N = 32768, measured with Decryptor::noise_budget_bits by this program (`encrypted_gpt2_stack 4 1 text 7 2 1 15`, profiles/r12_large_ring_pipeline.txt): 26 / 26 / 27 /
+// 29 / 29 / 28 where the level starts below its cap; qkv right after a switch to 4 limbs reads 29 below cap_bits(4) (27 at N = 8192, its constant there), and W_up
+// now carries the two rotations that copy W_down's input along the longer slot row
+const double kCost15[6] = {29, 27, 28, 30, 30, 29};
+const double* kCost = kCost13;
 double cap_bits(int limbs) { return 60.0 * limbs - 27.0; }
-const double kBlockCost = 27 + 25 + 26 + 27 + 30 + 28, kMargin = 12, kWaste = 8;
+double kBlockCost = 27 + 25 + 26 + 27 + 30 + 28;
+const double kMargin = 12, kWaste = 8;
 enum { QKV = 0, MASK, WO, WUP, SQUARE, WDOWN };
 }  // namespace
 
@@ -60,8 +69,14 @@ int main(int argc, char** argv) {
     const size_t tpc = argc > 6 ? (size_t)std::atol(argv[6]) : 1;
     if ((tpc != 1 && tpc != 2) || T % tpc) { std::printf("tokens_per_ciphertext must be 1 or 2 and divide the token count\n"); return 2; }
     const size_t C = T / tpc;   // ciphertexts per application
+    const int log2n = argc > 7 ? std::atoi(argv[7]) : 13;
+    if (log2n != 13 && log2n != 15) { std::printf("log2_n must be 13 or 15\n"); return 2; }
+    if (log2n == 15) { kCost = kCost15; kBlockCost = 0; for (int i = 0; i < 6; ++i) kBlockCost += kCost15[i]; }
+    // the chain a level's context and a square's workspace are taken from: 20 primes at N = 8192, 14 at N = 32768
+    auto params = [&](size_t limbs) { return log2n == 15 ? FheParams::n32768(limbs) : FheParams::n8192(limbs); };
+    const int max_square_limbs = log2n == 15 ? 6 : 9;     // a multiply's workspace is 2 l + 1 limbs of that chain
     try {
-        const FheParams chain = FheParams::n8192(20);
+        const FheParams chain = params(log2n == 15 ? 14 : 20);
         // the special prime of the hybrid key switches: the first prime of the chain that is not a data limb
         const uint64_t special = chain.moduli[LD], special_psi = chain.psi[LD];
         const size_t n = chain.n();
@@ -80,7 +95,7 @@ int main(int argc, char** argv) {
         std::vector<Level> lv(LD + 1);
         std::unique_ptr<KeyGenerator> kg;
         for (int l = LD; l >= 2; --l) {
-            lv[l].ctx.reset(new Context(FheParams::n8192((size_t)l), 0));
+            lv[l].ctx.reset(new Context(params((size_t)l), 0));
             lv[l].ev.reset(new Evaluator(*lv[l].ctx));
             if (l == LD) kg.reset(new KeyGenerator(*lv[l].ctx));
             else lv[l].sk.reset(new SecretKey(*lv[l].ctx, kg->secret_key().coefficients()));   // the same secret, seen at that level
@@ -109,6 +124,10 @@ int main(int argc, char** argv) {
             return *lv[l].lin[kind];
         };
         const uint32_t row_swap = (uint32_t)(2 * n - 1);
+        size_t down_period = 1;                            // W_down's input period: 2^ceil(log2 H)
+        while (down_period < H) down_period <<= 1;
+        size_t spread_steps = 0;
+        for (size_t sft = down_period; sft < n / 2; sft <<= 1) ++spread_steps;
 
         // every buffer of the forward is created on first use (the first, untimed pass) and reused afterwards
         std::map<std::string, std::unique_ptr<Ciphertext>> pool;
@@ -182,21 +201,31 @@ int main(int argc, char** argv) {
                 const Ciphertext& h1_l4 = down(ch1, l3, l4, B + "h1d");
                 Ciphertext &cu = buf(B + "u", l4), &cus = buf(B + "us", l4), &cur2 = buf(B + "ur", l4);
                 layer(WUP, l4).apply(h1_l4, cu);                                              // gpt_model.cpp:848
-                const Ciphertext* w_in = &cur2;
+                Ciphertext *packed = &cur2, *spare = &cu;
                 if (tpc == 1) {
                     hks(l4).add_galois_element(row_swap);
                     hks(l4).apply_galois_many(cu, swaps, cus);
                     lv[l4].ev->add(cu, cus, cur2);
                 } else {
-                    w_in = &cu;   // two tokens per ciphertext: every row already holds ITS token's W_up outputs (a row of 4096 slots is W_down's whole input window)
+                    packed = &cu; spare = &cur2;   // two tokens per ciphertext: every row already holds ITS token's W_up outputs
                 }
+                // W_down reads its input replicated with period 4096 along a slot row: at N = 8192 a row IS one such window; a longer row (N = 32768: 16384
+                // slots) also needs the copies inside the row, one more rotation per doubling
+                for (size_t sft = down_period; sft < n / 2; sft <<= 1) {
+                    const uint32_t e = lv[l4].be->galois_element(-(int)sft);
+                    hks(l4).add_galois_element(e);
+                    hks(l4).apply_galois_many(*packed, std::vector<uint32_t>(C, e), cus);
+                    lv[l4].ev->add(*packed, cus, *spare);
+                    std::swap(packed, spare);
+                }
+                const Ciphertext* w_in = packed;
                 est = std::min(est, cap_bits(l4)) - kCost[WUP];
                 note("W_up", *w_in, l4);
                 // the activation: exact multiply at the level the chain is on + relinearisation
-                int l5 = std::min(choose(est, l4), 9);                                        // (a multiply's workspace is 2 l + 1 <= 19 limbs)
+                int l5 = std::min(choose(est, l4), max_square_limbs);                         // (a multiply's workspace is 2 l + 1 <= 19 limbs at N = 8192, 13 at N = 32768)
                 const Ciphertext& u_l5 = down(*w_in, l4, l5, B + "urd");
                 if (!lv[l5].mul) {
-                    lv[l5].work.reset(new Context(FheParams::n8192((size_t)(2 * l5 + 1)), 0));
+                    lv[l5].work.reset(new Context(params((size_t)(2 * l5 + 1)), 0));
                     lv[l5].mul.reset(new ExactMultiplier(*lv[l5].work, *lv[l5].ctx, TM));
                 }
                 Ciphertext &sq3 = buf(B + "sq3", l5, 3), &sq = buf(B + "sq", l5);
@@ -286,7 +315,7 @@ int main(int argc, char** argv) {
         for (int b = 0; b < blocks_done; ++b) {
             const int* L6 = &levels_used[b * 6];
             ks += layer(QKV, L6[0]).key_switches_per_apply() + lv[L6[1]].take_v->key_switches_per_apply() + layer(WO, L6[2]).key_switches_per_apply() +
-                  layer(WUP, L6[3]).key_switches_per_apply() + 1 + 1 + layer(WDOWN, L6[5]).key_switches_per_apply();
+                  layer(WUP, L6[3]).key_switches_per_apply() + 1 + 1 + spread_steps + layer(WDOWN, L6[5]).key_switches_per_apply();
         }
         std::string lev, bits, ests;
         for (size_t i = 0; i < levels_used.size(); ++i) lev += (i ? (i % 6 ? " " : " | ") : "") + std::to_string(levels_used[i]);
@@ -295,12 +324,14 @@ int main(int argc, char** argv) {
             std::snprintf(t, sizeof t, "%s%.0f", i ? ", " : "", trace[i].bits); bits += t;
             std::snprintf(t, sizeof t, "%s%.0f", i ? ", " : "", trace[i].est); ests += t;
         }
+        char security[96] = "";   // (N = 8192 keeps its line: that ring has no parameter set inside the budget to report)
+        if (log2n == 15) std::snprintf(security, sizeof security, "\"modulus_bits_under_key_switching\": %d, \"he_standard_128bit_budget_bits\": 881, ", 60 * (LD + 1));
         if (json)
-            std::printf("{\"stack\": \"transformer_blocks_square_activation\", \"hidden\": %zu, \"inner\": %zu, \"log2_n\": 13, \"data_limbs\": %d, \"blocks\": %d, "
+            std::printf("{\"stack\": \"transformer_blocks_square_activation\", \"hidden\": %zu, \"inner\": %zu, \"log2_n\": %d, %s\"data_limbs\": %d, \"blocks\": %d, "
                         "\"correct_blocks\": %d, \"limbs_per_level\": \"%s\", \"plain_modulus\": %llu, \"tokens\": %zu, \"tokens_per_ciphertext\": %zu, \"key_switches_per_token\": %zu, "
                         "\"ct_ct_multiplies_per_token\": %d, \"setup_s\": %.2f, \"first_pass_s\": %.2f, \"ms_per_token\": %.3f, \"ms_per_token_per_block\": %.3f, "
                         "\"fresh_budget_bits\": %.0f, \"budget_bits\": [%s], \"planned_bits\": [%s], \"correct\": %s}\n",
-                        D, H, LD, blocks_done, correct_blocks, lev.c_str(), (unsigned long long)TM, T, tpc, ks, blocks_done, setup_s, first_pass_s, ms_per_token,
+                        D, H, log2n, security, LD, blocks_done, correct_blocks, lev.c_str(), (unsigned long long)TM, T, tpc, ks, blocks_done, setup_s, first_pass_s, ms_per_token,
                         blocks_done ? ms_per_token / blocks_done : 0.0, fresh_bits, bits.c_str(), ests.c_str(), ok ? "true" : "false");
         else {
             std::printf("%d transformer block(s) with a square activation on %d data limbs, %zu token(s) per application: %zu key switches + %d ct x ct multiplies per token; "

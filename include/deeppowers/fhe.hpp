@@ -60,6 +60,10 @@ struct FheParams {
     static FheParams n8192_l6();    // N=8192, 6 x 60-bit limbs      (configs[4] sizes)
     static FheParams n16384(size_t n_limbs);  // N=16384, the first n_limbs (<= 8) primes below 2^60 that are 1 mod 2^15: a ring with room for a security margin
     static FheParams n8192(size_t n_limbs);   // N=8192, the first n_limbs (<= 20) primes of the same descending chain: deeper levels, multiply workspaces
+    // N=32768, the first n_limbs (<= 14) primes below 2^60 that are 1 mod 2^16 (deeppowers_amd/params.py ntt_primes(15, n)): the ring whose 128-bit budget (881
+    // bits) holds two or three activated blocks.  The first 8 are fold primes (2^60 - d, d < 2^24: 480 bits on the fast arithmetic); a context that holds any
+    // of primes 9..14 runs the context-wide generic arithmetic on every limb, as every mixed context above N = 16384 does.
+    static FheParams n32768(size_t n_limbs);
 };
 
 class PolyBuffer;

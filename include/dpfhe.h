@@ -65,9 +65,10 @@ enum { DPFHE_IN_NTT = 1u, DPFHE_OUT_NTT = 2u };
  * dpfhe_relinearize and dpfhe_switch_key compose the batched transforms with one-pass streaming kernels and take their scratch from the
  * context's scratch arena of the caller's stream (see "Conventions"; kept until dpfhe_ctx_destroy; large batches run in slices of at most
  * 1 GiB of scratch, or what dpfhe_ctx_set_scratch_limit said); so do the hybrid entries - dpfhe_relinearize_hybrid / dpfhe_switch_key_hybrid, and since round 5 the per-item-key ones:
- * dpfhe_rotate_hybrid_batch / dpfhe_rotate_hybrid_grouped and dpfhe_switch_key_qp; dpfhe_rotate_hoisted_qp and dpfhe_ntt_inv_galois run up to log2_n = 14
- * (the whole packed-layer pipeline at N = 16384), and so does dpfhe_rotate_hybrid_hoisted (there: the deferred-division pipeline + one inverse transform
- * and division by P per rotation, scratch from the arena)); n_limbs >= 1; moduli[i] prime < 2^60 with q = 1 (mod 2N); psi[i] a primitive
+ * dpfhe_rotate_hybrid_batch / dpfhe_rotate_hybrid_grouped and dpfhe_switch_key_qp; dpfhe_rotate_hoisted_qp and dpfhe_ntt_inv_galois run at every ring degree
+ * (the whole packed-layer pipeline at N = 16384, 32768 and 65536; above 16384 dpfhe_ntt_inv_galois is the Galois form of the split inverse and, in place,
+ * stages through the arena), and so does dpfhe_rotate_hybrid_hoisted (above N = 8192: the deferred-division pipeline + one inverse transform
+ * and division by P per rotation, scratch from the arena; d_work / d_rotated0 are not used there and may be NULL)); n_limbs >= 1; moduli[i] prime < 2^60 with q = 1 (mod 2N); psi[i] a primitive
  * 2N-th root of unity mod q_i (psi^N = -1).  Builds twiddle / Shoup / Barrett tables on device_id. */
 int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_limbs, const uint64_t* moduli,
                      const uint64_t* psi, int device_id);
@@ -196,7 +197,9 @@ int dpfhe_rotate_hybrid_batch(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64
  * rotation is then a permutation of those words in the NTT domain, its key inner product and two inverse transforms per limb
  * (instead of Ld + 2), followed by the divide-by-P pass.  Keys and d_work as for dpfhe_rotate_hybrid_batch; d_rotated0:
  * batch * Ld * N words of scratch (sigma_g(c0)).  The result is a valid key switch of sigma_g(ct) but NOT word-identical to
- * dpfhe_rotate_hybrid_batch: here the automorphism acts on the lifted digits (sigma_g after the lift), there on c1 before it. */
+ * dpfhe_rotate_hybrid_batch: here the automorphism acts on the lifted digits (sigma_g after the lift), there on c1 before it.
+ * log2_n >= 14 (up to 16): composed from dpfhe_rotate_hoisted_qp, one batched inverse transform and the division by P per rotation - the same words -, in
+ * slices of rotations under the scratch limit, scratch from the stream's arena; d_work and d_rotated0 are not touched and may be NULL. */
 int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts,
                                 const uint64_t* d_keys, uint64_t* d_work, uint64_t* d_rotated0, uint64_t* d_digits, size_t batch, void* stream);
 /*    n_items input ciphertexts (tokens) share the `batch` rotations and their keys: d_in2 is [n_items][2][Ld][N], the output is
@@ -218,8 +221,13 @@ int dpfhe_rotate_hybrid_grouped(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint
  *     ( sum_j NTT(sigma_g lift([c1]_{q_j})) (.) key_{g,j,0} + P NTT(sigma_g c0),  sum_j NTT(sigma_g lift([c1]_{q_j})) (.) key_{g,j,1} ),  g = galois_elts[r]
  *   (the P c0 term is 0 on the special limb).  Keys as for dpfhe_rotate_hybrid_hoisted.  Scratch: d_in_ntt n_items * 2 * Ld * N words,
  *   d_digits n_items * Ld * L * N words.  round(block / P) after an inverse transform equals dpfhe_rotate_hybrid_hoisted's output.
+ *   Every ring degree: the stream kernels take log2_n at run time; at log2_n = 15, 16 the transforms of the inputs and digits are the split ones.
  * dpfhe_ntt_inv_galois (any context): block e of rns_polys_per_elt RNS polynomials:  d_out = sigma_{galois_elts[e]}(INTT(d_in)), the
- *   automorphism applied as a gather in the NTT domain (no separate pass).  d_out == d_in allowed.  log2_n <= 14.
+ *   automorphism applied as a gather in the NTT domain (no separate pass).  d_out == d_in, or disjoint from it.  log2_n = 15, 16 (split transform,
+ *   uniform fold / generic contexts): sub-transform b of NTT(sigma_g a) gathers from ONE other sub-block of NTT(a), then the column stages run unchanged -
+ *   two kernels and the plain split inverse's 4 N words of traffic per polynomial.  There a call with d_out == d_in MAY TAKE ARENA SCRATCH: the
+ *   sub-transforms' output is staged in the stream's arena (one launch group of at most 64 elements at a time, fewer under dpfhe_ctx_set_scratch_limit);
+ *   no allocation and no synchronisation once the arena has that size.  Out of place it writes straight to d_out.
  * dpfhe_switch_key_qp: batch = n_keys * group coefficient-domain items d_in2 [batch][2][Ld][N], item i with key i / group ->
  *   d_out_qp [batch][2][L][N] = sum_j NTT(lift([c1]_{q_j})) (.) key_j, NTT domain, nothing added, no division: the giant steps'
  *   terms, to be summed (dpfhe_reduce_sum on ctx_ext), inverse-transformed once and finished by

@@ -1,0 +1,45 @@
+"""The C++ facade at N = 32768: FheParams::n32768 is the Python generator's chain (CPU), and a packed encrypted layer - PackedLinear::apply, which calls
+dpfhe_rotate_hoisted_qp and dpfhe_ntt_inv_galois in place - decrypts to W x mod t there, one and two tokens per ciphertext (GPU)."""
+import json
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_example(name):
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), name])
+    return os.path.join(ROOT, "examples", name)
+
+
+def test_cpp_n32768_chain_is_the_python_generators(tmp_path):
+    """CPU: FheParams::n32768(k) prints params.ntt_primes(15, k), k = 1 .. 14, and rejects 0 and 15"""
+    from deeppowers_amd.params import ntt_primes
+    src = tmp_path / "chain15.cpp"
+    src.write_text('#include <cstdio>\n#include <deeppowers/fhe.hpp>\nusing namespace deeppowers::fhe;\nint main() {\n'
+                   '  for (size_t k = 1; k <= 14; ++k) { auto p = FheParams::n32768(k); std::printf("%u %zu", p.log2_n, p.n_limbs());\n'
+                   '    for (size_t i = 0; i < p.n_limbs(); ++i) std::printf(" %llu %llu", (unsigned long long)p.moduli[i], (unsigned long long)p.psi[i]);\n'
+                   '    std::printf("\\n"); }\n'
+                   '  for (size_t k : {size_t(0), size_t(15)}) { try { FheParams::n32768(k); std::printf("accepted\\n"); } catch (const Exception&) { std::printf("rejected\\n"); } }\n}\n')
+    lib = os.path.join(ROOT, "deeppowers_amd")
+    exe = str(tmp_path / "chain15")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip",
+                           "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
+    chain = ntt_primes(15, 14)
+    assert len(lines) == 16 and lines[14:] == ["rejected", "rejected"]
+    for k in range(1, 15):
+        v = [int(w) for w in lines[k - 1].split()]
+        assert v[:2] == [15, k] and v[2::2] == list(chain.moduli[:k]) and v[3::2] == list(chain.psi[:k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tokens_per_ct", [1, 2])
+def test_example_encrypted_gpt2_layer_at_n32768(tokens_per_ct):
+    """a 64 x 64 layer (short key generation) on FheParams::n32768(6), two tokens: the program's own decrypt-and-compare"""
+    out = subprocess.run([build_example("encrypted_gpt2_linear"), "64x64", "1", "json", "2", "15", str(tokens_per_ct)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "OK" in out.stdout, out.stdout + out.stderr
+    rec = json.loads(next(l for l in out.stdout.splitlines() if l.startswith("{")))
+    assert rec["log2_n"] == 15 and rec["correct"] is True and rec["tokens_per_ciphertext"] == tokens_per_ct and rec["tokens_per_apply"] == 2

@@ -366,6 +366,65 @@ extern "C" int emu_ctx_ntt(int log2n, int n_limbs, const u64* moduli, const u64*
     if (form == kFormHalves) emu_halves(t.tb, limb, inverse, in, out); else emu_quarters(t.tb, limb, inverse, in, out);
     return 0;
 }
+// out = sigma_g(INTT(in)) at N = 2^15, 2^16 as launch_impl.h launch_ntt_inv_galois_split runs it: kernels.h ntt_inv_galois_sub_kernel's per-thread code for every
+// sub-block (galois_sub_block -> gather_plan -> stage_load / stage_write / gather_read through the wave's LDS rows, one wave at a time: the rows are
+// wave-private), then ntt_top.h's column stages.  -7: a staged load would leave the source sub-block, or a wave's threads disagree on their source region
+// (the kernel takes it from its first lane).
+template <class Arith, int LOG_N1>
+static int emu_split_inv_galois(const DevTables<Arith>& tb, int limb, unsigned g, const u64* in, u64* out) {
+    typedef NttBody<Arith, kSplitLog2N2, 4> B;
+    constexpr int N1 = 1 << LOG_N1, N2 = B::G::N, T = B::T, E = B::E;
+    static_assert(B::kLdsIO, "the kernel's gather path");
+    const LimbConst lc = tb.lc[limb];
+    std::vector<u64> mid((size_t)N1 * N2);
+    for (int b = 0; b < N1; ++b) {
+        const GaloisSub gs = galois_sub_block<LOG_N1>(g, (unsigned)b, kSplitLog2N2);
+        if (gs.block >= (unsigned)N1) return -7;
+        const size_t slot = (size_t)limb * N1 + (size_t)b;
+        const u64* src = in + (size_t)gs.block * N2;
+        std::vector<u64> regs((size_t)T * E), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
+        std::vector<unsigned> addr((size_t)T * E);
+        auto A = [&](int tid) -> unsigned(&)[E] { return *reinterpret_cast<unsigned(*)[E]>(&addr[(size_t)tid * E]); };
+        for (int w = T / 64 - 1; w >= 0; --w) {
+            long shift0 = 0;
+            for (int tid = w * 64; tid < (w + 1) * 64; ++tid) {
+                const long shift = B::gather_plan(tid, g, gs.h, A(tid));
+                if (tid == w * 64) shift0 = shift;
+                const long first = (long)w * 64 * E + shift;   // the wave's staged words: [first, first + 64 E) of the source sub-block
+                if (shift != shift0 || first < 0 || first + 64 * E > N2) return -7;
+                u64 v[E];
+                B::stage_load(tid, v, src + shift);
+                B::stage_write(tid, v, lds.data());
+            }
+            for (int tid = w * 64; tid < (w + 1) * 64; ++tid) B::gather_read(regs_of<B>(regs, tid), lds.data(), A(tid));
+        }
+        const InvLast<typename B::Tw> last = tb.last[slot];
+        InvSteps<B, B::NPH - 1, kUnit>::run(regs, lds, tb.inv + slot * N2, last.w_last, last.w_ninv, lc);
+        for (int tid = 0; tid < T; ++tid) { B::inv_canon(regs_of<B>(regs, tid), lc); B::store_top(tid, regs_of<B>(regs, tid), mid.data() + (size_t)b * N2); }
+    }
+    for (size_t c = 0; c < (size_t)N2; ++c) {
+        u64 x[N1];
+        for (int r = 0; r < N1; ++r) x[r] = mid[(size_t)r * N2 + c];
+        top_inverse<Arith, LOG_N1>(x, tb.top_inv + (size_t)limb * N1, tb.top_last[limb], lc);
+        for (int r = 0; r < N1; ++r) out[(size_t)r * N2 + c] = x[r];
+    }
+    return 0;
+}
+// One polynomial of limb `limb` of a context of n_limbs limbs through dpfhe_ntt_inv_galois at log2n = 15, 16.  form kFormLaunch: the context's own
+// tables (fold or generic); kFormGeneric: the generic tables whatever the primes.  g odd, < 2N.  in != out.
+extern "C" int emu_ctx_ntt_inv_galois(int log2n, int n_limbs, const u64* moduli, const u64* psi, int limb, int form, unsigned g, const u64* in, u64* out) {
+    CtxChoice c;
+    if (int rc = ctx_choice(log2n, n_limbs, moduli, psi, c)) return rc;
+    if (limb < 0 || limb >= n_limbs || (form != kFormLaunch && form != kFormGeneric) || !(g & 1u) || g >= (2u << log2n) || in == out) return 2000;
+    if (log2n != 15 && log2n != 16) return -1;
+    auto run = [&](auto a) {
+        Tables<decltype(a)> t;
+        if (int rc = policy_tables(log2n, c.ht, t)) return rc;
+        return log2n == 15 ? emu_split_inv_galois<decltype(a), 3>(t.tb, limb, g, in, out) : emu_split_inv_galois<decltype(a), 4>(t.tb, limb, g, in, out);
+    };
+    if (form == kFormGeneric || !c.fold) return run(ShoupArith{});
+    return run(FoldArith{});
+}
 // The bytes dpfhe_ctx_create would upload: which = 0 the context-wide blob, 1 the class blob, 2 the lazy-multiply blob (log2 N = 12 with a fold limb).  Returns the size (0: the context has no class blob), or
 // -2000 for parameters a context rejects; copies the bytes when out holds at least that many, and the LimbClass per limb into limb_cls (n_limbs <= 16).
 extern "C" long emu_ctx_blob(int log2n, int n_limbs, const u64* moduli, const u64* psi, int which, unsigned char* out, size_t cap, unsigned char* limb_cls) {
