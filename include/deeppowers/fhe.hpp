@@ -130,7 +130,8 @@ public:
     // 80-byte header (little-endian): magic, u32 log2_n, u32 n_limbs, u64 batch, u64 components, u32 is_ntt, u32 expanded_component, u64 first_item,
     // u8 seed[32]; then u64 moduli[n_limbs]; then the other components' words [batch][components-1][L][N].  save_seeded re-expands and compares
     // first: a buffer that no longer matches its seed (overwritten, transformed) throws INVALID_STATE, so no stale seed is ever written.
-    // load_seeded checks the header as load() does, uploads the stored components and expands the missing one on the device (on `stream`).
+    // load_seeded checks the header as load() does, uploads the stored components and expands the missing one on the device (on `stream`); it
+    // synchronises `stream` before returning (the host staging buffer is released).
     void save_seeded(std::ostream& os, const Seed& seed, uint32_t component = 1, uint64_t first_item = 0) const;
     void load_seeded(std::istream& is, Stream* stream = nullptr);
 
@@ -163,7 +164,7 @@ public:
     void set_coefficients(const int64_t* coeffs);   // items * N values, centred or non-negative: reduced mod t
     void set_slots(const BatchEncoder& enc, const uint64_t* slots);   // items * N slot values < t, encoded on the host with enc (same t)
     // the same coefficients, encoded on the device (include/dpfhe.h dpfhe_encode_slots, DPFHE_ENCODE_PLAIN): items * N 32-bit slot values, a HOST or a
-    // DEVICE pointer as for BatchEncoder::encode_device
+    // DEVICE pointer as for BatchEncoder::encode_device (a device pointer: enqueues on `stream` only; a host pointer: synchronises `stream`)
     void set_slots_device(const BatchEncoder& enc, const uint32_t* slots, Stream* stream = nullptr);
     size_t items() const;
     uint64_t plain_modulus() const;
@@ -249,6 +250,10 @@ public:
     Evaluator(const Evaluator&) = delete;
     Evaluator& operator=(const Evaluator&) = delete;
 
+    // The `stream` argument: every method below enqueues its work on `stream` and returns - no host synchronisation, no work on any other stream, and in
+    // steady state no allocation (include/dpfhe.h "Conventions": at log2_n >= 14 the composed operations grow the stream's arena only for a larger
+    // batch than before).  The one exception is apply_galois, which holds a temporary and synchronises `stream` before it returns.
+    // tests/cpp/test_stream_api.cpp holds every one of them to this.
     // A1 / A2 (in place; flips is_ntt)
     void transform_to_ntt_inplace(PolyBuffer& x, Stream* stream = nullptr) const;
     void transform_from_ntt_inplace(PolyBuffer& x, Stream* stream = nullptr) const;
@@ -265,7 +270,8 @@ public:
     // N1, second half: out = round(in / q_last) at the next level; `out` must have been created on a Context of
     // params().drop_last_limb() with the same size and batch (coefficient domain)
     void rescale(const Ciphertext& in, Ciphertext& out_next_level, Stream* stream = nullptr) const;
-    // N3: ciphertext of m(X) -> ciphertext of m(X^g) under the same key (automorphism + key switch), coefficient domain
+    // N3: ciphertext of m(X) -> ciphertext of m(X^g) under the same key (automorphism + key switch), coefficient domain.  Allocates a temporary and
+    // SYNCHRONISES `stream` before returning.
     void apply_galois(const Ciphertext& in2, const GaloisKeys& keys, Ciphertext& out2, Stream* stream = nullptr) const;
     // A7: ct (.) pt per component (NTT domain) and the matrix-vector product y_i = sum_j W_ij (.) x_j
     void multiply_plain(const Ciphertext& a, const Plaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
@@ -331,7 +337,7 @@ public:
     Communicator& operator=(const Communicator&) = delete;
     int rank() const;
     int world_size() const;
-    // recv.batch() == world_size * send.batch(), same components; the domain flag is copied
+    // recv.batch() == world_size * send.batch(), same components; the domain flag is copied.  Enqueues on `stream` and returns.
     void all_gather(const PolyBuffer& send, PolyBuffer& recv, Stream* stream = nullptr) const;
 
 private:
@@ -489,6 +495,10 @@ public:
     HybridKeySwitcher(const HybridKeySwitcher&) = delete;
     HybridKeySwitcher& operator=(const HybridKeySwitcher&) = delete;
     void add_galois_element(uint32_t galois_elt);  // generates and keeps the key for sigma_g
+    // The `stream` argument: relinearize and apply_galois allocate their temporaries per call and SYNCHRONISE `stream` before they
+    // return.  Every other method below enqueues on `stream` and returns without host synchronisation once its scratch has its size and the keys of its
+    // element list are packed: the FIRST call with a new element list packs the keys on `stream` and synchronises it, and a larger batch than ever
+    // before reallocates the scratch.
     // 3 -> 2 components, coefficient domain, on data_ctx
     void relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* stream = nullptr) const;
     // ciphertext of m(X) -> ciphertext of m(X^g); the element must have been added
@@ -558,7 +568,8 @@ public:
     // allocation, no synchronisation - a request-time operand never visits the host) or a host pointer (staged through a temporary device buffer; the
     // call then synchronises `stream`).  Thread-safe.
     void encode_device(const uint32_t* slots, size_t items, Plaintext& out, bool to_ntt = false, Stream* stream = nullptr) const;
-    // the building block of the above and of ExactPlaintext::set_slots_device: d_out on ctx's device, flags as for dpfhe_encode_slots
+    // the building block of the above and of ExactPlaintext::set_slots_device: d_out on ctx's device, flags as for dpfhe_encode_slots; the same rule for
+    // `stream` (device pointer: enqueue only; host pointer: synchronises `stream`)
     void encode_device_words(const Context& ctx, const uint32_t* slots, size_t items, uint64_t* d_out, uint32_t flags, Stream* stream = nullptr) const;
 
 private:
@@ -646,7 +657,8 @@ public:
     PackedSelect(const PackedSelect&) = delete;
     PackedSelect& operator=(const PackedSelect&) = delete;
     size_t key_switches_per_apply() const;
-    // x, y: T items, 2 components, coefficient domain; enqueues on `stream` (scratch belongs to the object: one apply() at a time)
+    // x, y: T items, 2 components, coefficient domain; enqueues on `stream` and returns, no host synchronisation (scratch belongs to the object and
+    // grows only for a larger T than before: one apply() at a time)
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:
@@ -683,7 +695,8 @@ public:
     void pack_input(const uint64_t* x /* d values */, uint64_t* slots /* N */) const;
     void unpack_output(const uint64_t* slots /* N */, uint64_t* y /* d values */) const;
     // x, y: T items (tokens), 2 components, coefficient domain, packed as pack_input packs; y is packed the same way (it can enter the
-    // next block as it is).  Enqueues on `stream`; one apply() at a time per object.
+    // next block as it is).  Enqueues on `stream` and returns (no host synchronisation; the stages and scratch grow only for a larger T than before);
+    // one apply() at a time per object.
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
     // intermediate results of the LAST apply() (T items each; valid until the next one): 0 = qkv (slot r of row 0 = output r), 1 = a = v in
     // the input packing, 2 = h1, 3 = W_up h1 in the input packing of W_down, 4 = h2 (= y)

@@ -29,6 +29,8 @@ Entry -> test (an entry of include/dpfhe.h that writes device memory and is not 
   dpfhe_comm_allgather / dpfhe_comm_allreduce_sum                      test_collectives_world_of_one
   dpfhe_expand_uniform / dpfhe_add_plain_scaled / dpfhe_compact / dpfhe_encode_slots / dpfhe_sample_noise / dpfhe_rerandomize
                                                                        their own sentinel tests (test_gpu_seeded / _plain_add / _compact / _encode / _rerandomize)
+The same table (dpfhe_ctx_autotune apart: a set-up call that synchronises) is held to the stream contract of the header - the caller's stream, enqueue
+only, no allocation in steady state - by tests/test_gpu_stream_contract.py, which runs these test bodies with Case.gate set (tests/stream_gate.py).
 Read-side overruns of inputs cannot be seen without a fault and are not looked for."""
 import ctypes as C
 
@@ -102,8 +104,22 @@ HUGE = [("fold", 16)]                                                        # t
 
 
 # ---- one call through the arena ------------------------------------------------------------------------------------------------------------------------------
+class At:
+    """the address callable a case's fn gets: at(name[, extra_words]) is a device address; at.stream is the stream argument of the call - None (the null
+    stream) in footprint mode, the gated stream's pointer in gated mode"""
+
+    def __init__(self, arena, base, stream=None):
+        self.arena, self.base, self.stream = arena, base, stream
+
+    def __call__(self, name, extra=0):
+        return self.arena.address(self.base, name, extra)
+
+
 class Case:
-    """the buffers of one call and what its outputs must hold; run(what, fn): fn(at) makes the call(s), at(name[, extra_words]) is a device address"""
+    """the buffers of one call and what its outputs must hold; run(what, fn): fn(at) makes the call(s), at(name[, extra_words]) is a device address and
+    at.stream the stream to pass.  tests/test_gpu_stream_contract.py sets Case.gate (a stream_gate.Gate) for the time of a test: run() is then
+    run_gated(), the same buffers and the same expected words held to the stream contract instead of the two fill patterns"""
+    gate = None
 
     def __init__(self, r):
         self.r, self.ar, self.want = r, Arena(), {}
@@ -123,13 +139,14 @@ class Case:
         self.want[name] = want
 
     def run(self, what, fn):
+        if Case.gate is not None:
+            return self.run_gated(what, fn, Case.gate)
         import torch
         dev = self.r.ctx.device
 
         def call(buf):
             t = torch.from_numpy(buf.view(np.int64)).to(dev)
-            base = t.data_ptr()
-            rc = fn(lambda name, extra=0: self.ar.address(base, name, extra))
+            rc = fn(At(self.ar, t.data_ptr()))
             _cabi.check(rc or 0, what)
             torch.cuda.synchronize(dev)
             return t.cpu().numpy().view(np.uint64)
@@ -137,6 +154,15 @@ class Case:
             return run_both_patterns(self.ar, call, self.want)
         except AssertionError as e:
             raise AssertionError(f"{what} on {self.r.kind} N = {self.r.n}: {e}") from e
+
+    def run_gated(self, what, fn, gate):
+        """the same call through stream_gate.run_gated: on the gate's stream, behind the gate, with the inputs arriving after it (one fill pattern)"""
+        from stream_gate import run_gated
+
+        def call(t, stream):
+            rc = fn(At(self.ar, t.data_ptr(), stream))
+            _cabi.check(rc or 0, what)
+        return run_gated(gate, self.ar, self.want, call, scratch_bytes=lambda: self.r.ctx.scratch_bytes, what=f"{what} on {self.r.kind} N = {self.r.n}")
 
 
 def data_oracle(r):
@@ -166,11 +192,11 @@ def test_transforms(rig, kind, log2n):
         for name, want in (("dpfhe_ntt_fwd", r.orc.ntt_fwd(x, threads=0)), ("dpfhe_ntt_inv", r.orc.ntt_inv(x, threads=0))):
             c = Case(r)
             c.inout("io", x, poly, want)
-            c.run(f"{name} x{count}", lambda at: getattr(lib, name)(h, at("io"), count, None))
+            c.run(f"{name} x{count}", lambda at: getattr(lib, name)(h, at("io"), count, at.stream))
             c = Case(r)
             c.inp("in", x, poly)
             c.out("out", x.size, poly, want)
-            c.run(f"{name}_oop x{count}", lambda at: getattr(lib, name + "_oop")(h, at("out"), at("in"), count, None))
+            c.run(f"{name}_oop x{count}", lambda at: getattr(lib, name + "_oop")(h, at("out"), at("in"), count, at.stream))
 
 
 # ---- streaming entries ---------------------------------------------------------------------------------------------------------------------------------------
@@ -197,61 +223,61 @@ def test_streaming_entries(rig, kind, log2n):
             c.inp("a", x, poly)
             c.inp("b", y, poly)
             c.out("out", x.size, poly, want)
-            c.run(f"{op} x{count}", lambda at: fn(h, at("out"), at("a"), at("b"), count, None))
+            c.run(f"{op} x{count}", lambda at: fn(h, at("out"), at("a"), at("b"), count, at.stream))
             c = Case(r)
             c.inout("a", x, poly, want)
             c.inp("b", y, poly)
-            c.run(f"{op} x{count}, out == a", lambda at: fn(h, at("a"), at("a"), at("b"), count, None))
+            c.run(f"{op} x{count}, out == a", lambda at: fn(h, at("a"), at("a"), at("b"), count, at.stream))
             c = Case(r)
             c.inp("a", x, poly)
             c.inout("b", y, poly, want)
-            c.run(f"{op} x{count}, out == b", lambda at: fn(h, at("b"), at("a"), at("b"), count, None))
+            c.run(f"{op} x{count}, out == b", lambda at: fn(h, at("b"), at("a"), at("b"), count, at.stream))
         c = Case(r)
         c.inout("acc", acc, poly, orc.dyadic("mul_add", x, y, acc=acc))
         c.inp("a", x, poly)
         c.inp("b", y, poly)
-        c.run(f"dpfhe_dyadic_mul_add x{count}", lambda at: lib.dpfhe_dyadic_mul_add(h, at("acc"), at("a"), at("b"), count, None))
+        c.run(f"dpfhe_dyadic_mul_add x{count}", lambda at: lib.dpfhe_dyadic_mul_add(h, at("acc"), at("a"), at("b"), count, at.stream))
         want = orc.dyadic("negate", x)
         c = Case(r)
         c.inp("a", x, poly)
         c.out("out", x.size, poly, want)
-        c.run(f"dpfhe_negate x{count}", lambda at: lib.dpfhe_negate(h, at("out"), at("a"), count, None))
+        c.run(f"dpfhe_negate x{count}", lambda at: lib.dpfhe_negate(h, at("out"), at("a"), count, at.stream))
         c = Case(r)
         c.inout("a", x, poly, want)
-        c.run(f"dpfhe_negate x{count}, out == a", lambda at: lib.dpfhe_negate(h, at("a"), at("a"), count, None))
+        c.run(f"dpfhe_negate x{count}, out == a", lambda at: lib.dpfhe_negate(h, at("a"), at("a"), count, at.stream))
         pt = r.words(orc, (2,), 430)[1]                                   # q - 1 in every word
         want = orc.dyadic("mul", x, np.ascontiguousarray(np.broadcast_to(pt, x.shape)))
         c = Case(r)
         c.inp("a", x, poly)
         c.inp("pt", pt, poly)
         c.out("out", x.size, poly, want)
-        c.run(f"dpfhe_multiply_plain x{count}", lambda at: lib.dpfhe_multiply_plain(h, at("out"), at("a"), at("pt"), count, None))
+        c.run(f"dpfhe_multiply_plain x{count}", lambda at: lib.dpfhe_multiply_plain(h, at("out"), at("a"), at("pt"), count, at.stream))
         c = Case(r)
         c.inout("a", x, poly, want)
         c.inp("pt", pt, poly)
-        c.run(f"dpfhe_multiply_plain x{count}, out == a", lambda at: lib.dpfhe_multiply_plain(h, at("a"), at("a"), at("pt"), count, None))
+        c.run(f"dpfhe_multiply_plain x{count}, out == a", lambda at: lib.dpfhe_multiply_plain(h, at("a"), at("a"), at("pt"), count, at.stream))
         for g in (5, 2 * n - 1):
             c = Case(r)
             c.inp("in", x, poly)
             c.out("out", x.size, poly, orc.apply_galois(x, g))
-            c.run(f"dpfhe_apply_galois x{count} g = {g}", lambda at: lib.dpfhe_apply_galois(h, at("out"), at("in"), count, g, None))
+            c.run(f"dpfhe_apply_galois x{count} g = {g}", lambda at: lib.dpfhe_apply_galois(h, at("out"), at("in"), count, g, at.stream))
         c = Case(r)
         c.inp("in", x, poly)
         c.out("out", count * (L - 1) * n, (L - 1) * n, orc.rescale(x))
-        c.run(f"dpfhe_rescale x{count}", lambda at: lib.dpfhe_rescale(h, at("out"), at("in"), count, None))
+        c.run(f"dpfhe_rescale x{count}", lambda at: lib.dpfhe_rescale(h, at("out"), at("in"), count, at.stream))
         # sums of up to 15 canonical residues (15 q < 2^64): the reference is the exact remainder
         terms = np.random.default_rng(count).integers(1, 16, x.shape, dtype=np.uint64)
         terms[0] = 15
         sums = x * terms
         c = Case(r)
         c.inout("io", sums, poly, sums % r.qcol)
-        c.run(f"dpfhe_canonicalize_sum x{count}", lambda at: lib.dpfhe_canonicalize_sum(h, at("io"), count, None))
+        c.run(f"dpfhe_canonicalize_sum x{count}", lambda at: lib.dpfhe_canonicalize_sum(h, at("io"), count, at.stream))
     src = np.random.default_rng(7).integers(0, 1 << 63, 1024 * 7 + 2, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
     for words in (2, 1022, 1024 * 7 + 2):
         c = Case(r)
         c.inp("src", src[:words], words)
         c.out("dst", words, words, src[:words])
-        c.run(f"dpfhe_copy {words} words", lambda at: lib.dpfhe_copy(h, at("dst"), at("src"), words, None))
+        c.run(f"dpfhe_copy {words} words", lambda at: lib.dpfhe_copy(h, at("dst"), at("src"), words, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", SMALL + HUGE, ids=ids(SMALL + HUGE))
@@ -268,7 +294,7 @@ def test_reduce_sum(rig, kind, log2n):
             c = Case(r)
             c.inp("in", cts, comps * L * n)
             c.out("out", comps * L * n, comps * L * n, orc.reduce_sum(cts.ravel(), comps))
-            c.run(f"dpfhe_reduce_sum {count} x {comps}", lambda at: lib.dpfhe_reduce_sum(h, at("out"), at("in"), count, comps, None))
+            c.run(f"dpfhe_reduce_sum {count} x {comps}", lambda at: lib.dpfhe_reduce_sum(h, at("out"), at("in"), count, comps, at.stream))
 
 
 # ---- the fused / composed multiply --------------------------------------------------------------------------------------------------------------------------
@@ -296,7 +322,7 @@ def run_ct_mul(r, label, a, b, flags, want):
     if b is not None:
         c.inp("b2", b, 2 * poly)
     c.out("out3", batch * 3 * poly, 3 * poly, want)
-    c.run(label, lambda at: lib.dpfhe_ct_mul(h, at("out3"), at("a2"), at("b2" if b is not None else "a2"), batch, flags, None))
+    c.run(label, lambda at: lib.dpfhe_ct_mul(h, at("out3"), at("a2"), at("b2" if b is not None else "a2"), batch, flags, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", SMALL + COMPOSED, ids=ids(SMALL + COMPOSED))
@@ -328,12 +354,12 @@ def test_diagnostic_and_tuning_entries(rig):
     c.inp("b2", b, 2 * poly)
     c.out("out3", batch * 3 * poly, 3 * poly, orc.ct_mul(a, b, threads=0))
     c.scratch("trace", batch * r.L * 12, 12)
-    c.run("dpfhe_debug_ct_mul_trace", lambda at: lib.dpfhe_debug_ct_mul_trace(h, at("out3"), at("a2"), at("b2"), batch, at("trace"), None))
+    c.run("dpfhe_debug_ct_mul_trace", lambda at: lib.dpfhe_debug_ct_mul_trace(h, at("out3"), at("a2"), at("b2"), batch, at("trace"), at.stream))
     words = 2 * 7 * poly                                                  # two synthetic ciphertext pairs with their products
     c = Case(r)
     c.scratch("work", words, 7 * poly)
     try:
-        c.run("dpfhe_ctx_autotune", lambda at: lib.dpfhe_ctx_autotune(h, at("work"), words, 2, None))
+        c.run("dpfhe_ctx_autotune", lambda at: lib.dpfhe_ctx_autotune(h, at("work"), words, 2, at.stream))
     finally:
         lib.dpfhe_tune_cache_clear()                                      # (the probe's result must not reach contexts that later tests create)
 
@@ -348,7 +374,7 @@ def run_relinearize(r, batch, seed=300):
     c.inp("in3", c3, 3 * poly)
     c.inp("evk", evk, 2 * poly)
     c.out("out2", batch * 2 * poly, 2 * poly, orc.relinearize(c3, evk, threads=0))
-    c.run(f"dpfhe_relinearize x{batch}", lambda at: lib.dpfhe_relinearize(h, at("out2"), at("in3"), at("evk"), batch, None))
+    c.run(f"dpfhe_relinearize x{batch}", lambda at: lib.dpfhe_relinearize(h, at("out2"), at("in3"), at("evk"), batch, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", SMALL + COMPOSED, ids=ids(SMALL + COMPOSED))
@@ -365,7 +391,7 @@ def test_key_switching(rig, kind, log2n):
         c.inp("in2", ct, 2 * poly)
         c.inp("key", key, 2 * poly)
         c.out("out2", batch * 2 * poly, 2 * poly, orc.switch_key(ct, key, threads=0))
-        c.run(f"dpfhe_switch_key x{batch}", lambda at: lib.dpfhe_switch_key(h, at("out2"), at("in2"), at("key"), batch, None))
+        c.run(f"dpfhe_switch_key x{batch}", lambda at: lib.dpfhe_switch_key(h, at("out2"), at("in2"), at("key"), batch, at.stream))
 
 
 EXTENDED = SMALL + HYBRID + COMPOSED
@@ -386,7 +412,7 @@ def test_hybrid_key_switching(rig, kind, log2n):
             c.inp("key", key, 2 * L * n)
             c.scratch("work", batch * 2 * L * n, 2 * L * n)
             c.out("out2", batch * 2 * Ld * n, 2 * Ld * n, orc.keyswitch_hybrid(ct, key, comps, threads=0))
-            c.run(f"{name} x{batch}", lambda at: getattr(lib, name)(h, at("out2"), at("in"), at("key"), at("work"), batch, None))
+            c.run(f"{name} x{batch}", lambda at: getattr(lib, name)(h, at("out2"), at("in"), at("key"), at("work"), batch, at.stream))
 
 
 def rotation_keys(r, k, seed):
@@ -412,7 +438,7 @@ def run_rotate_hoisted(r, k, T, seed=350):
     c.scratch("digits", T * Ld * L * n, Ld * L * n)
     c.out("out2", k * T * 2 * Ld * n, 2 * Ld * n, want)
     c.run(f"dpfhe_rotate_hybrid_hoisted {k} rotations of {T}",
-          lambda at: lib.dpfhe_rotate_hybrid_hoisted(h, at("out2"), at("in2"), T, u32(elts), at("keys"), at("work"), at("rotated0"), at("digits"), k, None))
+          lambda at: lib.dpfhe_rotate_hybrid_hoisted(h, at("out2"), at("in2"), T, u32(elts), at("keys"), at("work"), at("rotated0"), at("digits"), k, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", EXTENDED, ids=ids(EXTENDED))
@@ -435,7 +461,7 @@ def test_hybrid_rotations(rig, kind, log2n):
             c.scratch("rotated", k * ct_words, ct_words)
             c.out("out2", k * ct_words, ct_words, np.stack([rotated(cts[i if n_in > 1 else 0], elts[i], keys[i]) for i in range(k)]))
             c.run(f"dpfhe_rotate_hybrid_batch {k} rotations of {n_in}",
-                  lambda at: lib.dpfhe_rotate_hybrid_batch(h, at("out2"), at("in2"), n_in, u32(elts), at("keys"), at("work"), at("rotated"), k, None))
+                  lambda at: lib.dpfhe_rotate_hybrid_batch(h, at("out2"), at("in2"), n_in, u32(elts), at("keys"), at("work"), at("rotated"), k, at.stream))
         for group in (1, 3):
             items = r.words(data, (k * group, 2), 340 + group)
             c = Case(r)
@@ -445,7 +471,7 @@ def test_hybrid_rotations(rig, kind, log2n):
             c.scratch("rotated", k * group * ct_words, ct_words)
             c.out("out2", k * group * ct_words, ct_words, np.stack([rotated(items[i], elts[i // group], keys[i // group]) for i in range(k * group)]))
             c.run(f"dpfhe_rotate_hybrid_grouped {k} x {group}",
-                  lambda at: lib.dpfhe_rotate_hybrid_grouped(h, at("out2"), at("in2"), u32(elts), k, group, at("keys"), at("work"), at("rotated"), None))
+                  lambda at: lib.dpfhe_rotate_hybrid_grouped(h, at("out2"), at("in2"), u32(elts), k, group, at("keys"), at("work"), at("rotated"), at.stream))
         for T in (1, 3):
             run_rotate_hoisted(r, k, T)
 
@@ -465,7 +491,7 @@ def run_rotate_hoisted_qp(r, k, T, seed=700):
     c.scratch("digits", T * Ld * L * n, Ld * L * n)
     c.out("out_qp", (1 + k) * T * 2 * L * n, T * 2 * L * n, want)
     c.run(f"dpfhe_rotate_hoisted_qp {k} rotations of {T}",
-          lambda at: lib.dpfhe_rotate_hoisted_qp(h, at("out_qp"), at("in2"), T, u32(elts), at("keys") if k else None, at("in_ntt"), at("digits"), k, None))
+          lambda at: lib.dpfhe_rotate_hoisted_qp(h, at("out_qp"), at("in2"), T, u32(elts), at("keys") if k else None, at("in_ntt"), at("digits"), k, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", EXTENDED, ids=ids(EXTENDED))
@@ -486,7 +512,7 @@ def test_deferred_division_stages(rig, kind, log2n):
         c.inp("in2", items, 2 * Ld * n)
         c.inp("keys", keys, Ld * 2 * L * n)
         c.out("out_qp", k * group * 2 * L * n, 2 * L * n, want)
-        c.run(f"dpfhe_switch_key_qp {k} x {group}", lambda at: lib.dpfhe_switch_key_qp(h, at("out_qp"), at("in2"), at("keys"), k, group, None))
+        c.run(f"dpfhe_switch_key_qp {k} x {group}", lambda at: lib.dpfhe_switch_key_qp(h, at("out_qp"), at("in2"), at("keys"), k, group, at.stream))
     batch = 3
     rot = r.words(data, (6, batch, 2), 750)
     t_qp = r.words(orc, (batch, 2), 751)
@@ -497,7 +523,7 @@ def test_deferred_division_stages(rig, kind, log2n):
             c.inp("addends", rot[:n_add], 2 * Ld * n)
         c.out("out2", batch * 2 * Ld * n, 2 * Ld * n, rescale_bsgs_reference(orc, data, t_qp, rot[:n_add]))
         c.run(f"dpfhe_rescale_bsgs {n_add} addends",
-              lambda at: lib.dpfhe_rescale_bsgs(h, at("out2"), at("in_qp"), at("addends") if n_add else None, n_add, batch, None))
+              lambda at: lib.dpfhe_rescale_bsgs(h, at("out2"), at("in_qp"), at("addends") if n_add else None, n_add, batch, at.stream))
     for k, per in ((70, 3), (1, 1)):
         elts = [pow(3, 5 * i, 2 * n) for i in range(k)]
         if k > 2:
@@ -508,10 +534,10 @@ def test_deferred_division_stages(rig, kind, log2n):
         c = Case(r)
         c.inp("in", x, per * L * n)
         c.out("out", x.size, per * L * n, want)
-        c.run(f"dpfhe_ntt_inv_galois {k} x {per}", lambda at: lib.dpfhe_ntt_inv_galois(h, at("out"), at("in"), per, u32(elts), k, None))
+        c.run(f"dpfhe_ntt_inv_galois {k} x {per}", lambda at: lib.dpfhe_ntt_inv_galois(h, at("out"), at("in"), per, u32(elts), k, at.stream))
         c = Case(r)
         c.inout("io", x, per * L * n, want)
-        c.run(f"dpfhe_ntt_inv_galois {k} x {per}, d_out == d_in", lambda at: lib.dpfhe_ntt_inv_galois(h, at("io"), at("io"), per, u32(elts), k, None))
+        c.run(f"dpfhe_ntt_inv_galois {k} x {per}, d_out == d_in", lambda at: lib.dpfhe_ntt_inv_galois(h, at("io"), at("io"), per, u32(elts), k, at.stream))
 
 
 # ---- base extension and scale-and-round: the item strides ------------------------------------------------------------------------------------------------------
@@ -529,7 +555,7 @@ def run_base_extend(r, label, xs, src0, dst0, nd, in_stride, out_stride, want):
     words, seg = strided(items, out_stride, nd, n)
     c.out("out", words, out_stride * n, want, segments=seg)
     c.run(f"dpfhe_base_extend {label} strides {in_stride} -> {out_stride}",
-          lambda at: lib.dpfhe_base_extend(h, at("out"), out_stride, at("in"), in_stride, src0, ns, dst0, nd, items, None))
+          lambda at: lib.dpfhe_base_extend(h, at("out"), out_stride, at("in"), in_stride, src0, ns, dst0, nd, items, at.stream))
 
 
 def run_scale_round(r, label, w, drop0, ndrop, keep0, nkeep, mul, out_stride, want):
@@ -540,7 +566,7 @@ def run_scale_round(r, label, w, drop0, ndrop, keep0, nkeep, mul, out_stride, wa
     words, seg = strided(items, out_stride, nkeep, n)
     c.out("out", words, out_stride * n, want, segments=seg)
     c.run(f"dpfhe_scale_round {label} stride {out_stride}",
-          lambda at: lib.dpfhe_scale_round(h, at("out"), out_stride, at("in"), drop0, ndrop, keep0, nkeep, mul, items, None))
+          lambda at: lib.dpfhe_scale_round(h, at("out"), out_stride, at("in"), drop0, ndrop, keep0, nkeep, mul, items, at.stream))
 
 
 @pytest.mark.parametrize("kind,log2n", SMALL, ids=ids(SMALL))
@@ -594,7 +620,7 @@ def run_matvec(r, rows, cols):
     c.inp("W", W, poly)
     c.inp("x", x, 2 * poly)
     c.out("y", rows * 2 * poly, 2 * poly, orc.matvec_plain(W.ravel(), x.ravel(), rows, cols, threads=0))
-    c.run(f"dpfhe_matvec_plain {rows} x {cols}", lambda at: lib.dpfhe_matvec_plain(h, at("y"), at("W"), at("x"), rows, cols, None))
+    c.run(f"dpfhe_matvec_plain {rows} x {cols}", lambda at: lib.dpfhe_matvec_plain(h, at("y"), at("W"), at("x"), rows, cols, at.stream))
     q = np.array(r.p.moduli, np.uint64)
     w = np.random.default_rng(cols).integers(0, 1 << 62, (rows, cols, L), dtype=np.uint64) % q
     w[: rows - 1] = q - np.uint64(1)
@@ -602,7 +628,7 @@ def run_matvec(r, rows, cols):
     c.inp("w", w, L, align=8)                                             # d_w is documented as 8-byte aligned: an odd word offset
     c.inp("x", x, 2 * poly)
     c.out("y", rows * 2 * poly, 2 * poly, orc.matvec_scalar(w, x, rows, cols, threads=0))
-    c.run(f"dpfhe_matvec_scalar {rows} x {cols}", lambda at: lib.dpfhe_matvec_scalar(h, at("y"), at("w"), at("x"), rows, cols, None))
+    c.run(f"dpfhe_matvec_scalar {rows} x {cols}", lambda at: lib.dpfhe_matvec_scalar(h, at("y"), at("w"), at("x"), rows, cols, at.stream))
 
 
 def run_matvec_multi(r, rows, cols, n_rhs):
@@ -618,7 +644,7 @@ def run_matvec_multi(r, rows, cols, n_rhs):
     c.inp("W", W, poly)
     c.inp("x", x, 2 * poly)
     c.out("y", rows * n_rhs * 2 * poly, 2 * poly, want)
-    c.run(f"dpfhe_matvec_plain_multi {rows} x {cols} x {n_rhs}", lambda at: lib.dpfhe_matvec_plain_multi(h, at("y"), at("W"), at("x"), rows, cols, n_rhs, None))
+    c.run(f"dpfhe_matvec_plain_multi {rows} x {cols} x {n_rhs}", lambda at: lib.dpfhe_matvec_plain_multi(h, at("y"), at("W"), at("x"), rows, cols, n_rhs, at.stream))
 
 
 MULTI = ((8, 264, 2), (5, 257, 3), (4, 8, 1))                                # the full form, a ragged one, the smallest
@@ -703,9 +729,9 @@ def test_collectives_world_of_one(rig):
         c = Case(r)
         c.inp("send", x, poly)
         c.out("recv", x.size, poly, x)
-        c.run("dpfhe_comm_allgather", lambda at: lib.dpfhe_comm_allgather(comm, at("recv"), at("send"), x.size, None))
+        c.run("dpfhe_comm_allgather", lambda at: lib.dpfhe_comm_allgather(comm, at("recv"), at("send"), x.size, at.stream))
         c = Case(r)
         c.inout("io", x, poly, x)
-        c.run("dpfhe_comm_allreduce_sum", lambda at: lib.dpfhe_comm_allreduce_sum(comm, h, at("io"), 3, None))
+        c.run("dpfhe_comm_allreduce_sum", lambda at: lib.dpfhe_comm_allreduce_sum(comm, h, at("io"), 3, at.stream))
     finally:
         lib.dpfhe_comm_destroy(comm)

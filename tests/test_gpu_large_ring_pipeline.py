@@ -208,7 +208,7 @@ def test_footprints_at_n32768(rig, kind, ln):
         c = fp.Case(r)
         c.inp("in", x, per * L * n)
         c.out("out", x.size, per * L * n, want)
-        c.run(f"dpfhe_ntt_inv_galois {k} x {per}", lambda at: lib.dpfhe_ntt_inv_galois(h, at("out"), at("in"), per, fp.u32(elts), k, None))
+        c.run(f"dpfhe_ntt_inv_galois {k} x {per}", lambda at: lib.dpfhe_ntt_inv_galois(h, at("out"), at("in"), per, fp.u32(elts), k, at.stream))
         c = fp.Case(r)
         c.inout("io", x, per * L * n, want)
-        c.run(f"dpfhe_ntt_inv_galois {k} x {per}, d_out == d_in", lambda at: lib.dpfhe_ntt_inv_galois(h, at("io"), at("io"), per, fp.u32(elts), k, None))
+        c.run(f"dpfhe_ntt_inv_galois {k} x {per}, d_out == d_in", lambda at: lib.dpfhe_ntt_inv_galois(h, at("io"), at("io"), per, fp.u32(elts), k, at.stream))

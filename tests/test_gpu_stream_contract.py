@@ -1,0 +1,300 @@
+"""-m gpu: every stream-taking compute entry of include/dpfhe.h held to the header's promises about `stream` - the work runs on that stream, the call
+only enqueues and never synchronises, and in steady state it does not allocate - through the gate of tests/stream_gate.py (its protocol is described
+there; tests/test_gpu_stream_gate.py shows that the gate reports planted defects).
+
+The value tests pass None almost everywhere: the null stream, idle, compared after a full synchronisation.  One of several kernels launched on the wrong
+stream would still see finished inputs there.  Here every call runs on a NON-BLOCKING stream S behind a gate that holds S, with its true inputs arriving
+on S after the gate: a launch on any other stream runs too early and gives words that differ from the oracle's; a call that waits for S or the device
+returns after the gate; an allocation changes dpfhe_ctx_scratch_bytes.
+
+The 36 entries of tests/test_gpu_footprint.py's table run their own test bodies, contexts and shapes (Case.gate set: Case.run is Case.run_gated), one
+fill pattern; the three entries at N = 32768 those of tests/test_gpu_large_ring_pipeline.py.  dpfhe_ctx_autotune is a documented set-up call that
+synchronises and is left out.  The six entries with sentinel tests of their own get cases here, expected words from their host twins (dpfhe_*_host,
+which the CPU tests pin to Python integers):
+  dpfhe_expand_uniform      a middle component                                   dpfhe_add_plain_scaled   in place and apart, 2 and 3 components
+  dpfhe_compact             two widths                                           dpfhe_sample_noise       the three kinds, and DPFHE_NOISE_ADD
+  dpfhe_encode_slots        flags 0, PLAIN and NTT at N = 256 and N = 32768 (two kernels that park words in d_out)
+  dpfhe_rerandomize         on a `mixed` context, and at N = 16384
+The C++ facade's Stream* arguments: tests/cpp/test_stream_api.cpp, run from here."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import stream_gate as sg
+import test_gpu_footprint as fp
+import test_gpu_large_ring_pipeline as lr
+from class_edges import Rig
+from deeppowers_amd import _cabi, wire
+from deeppowers_amd.params import ntt_primes
+from test_seeded_cpu import SEED
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+rig = fp.rig
+
+
+@pytest.fixture
+def gated():
+    gate = sg.shared_gate("cuda:0")
+    fp.Case.gate = gate
+    yield gate
+    fp.Case.gate = None
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report():
+    yield
+    gate = sg._shared.get("gate")
+    if gate is not None:
+        print(f"\nstream contract: {gate.cases} gated calls passed; G = {gate.seconds * 1e3:.1f} ms (measured {gate.measured * 1e3:.3f} ms, probed stream "
+              f"{gate.probed_index}); slowest steady-state t_enqueue {gate.slowest[0] * 1e3:.3f} ms ({gate.slowest[1]})")
+
+
+# ---- the footprint table, gated ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,log2n", fp.SMALL + fp.COMPOSED + fp.HUGE, ids=fp.ids(fp.SMALL + fp.COMPOSED + fp.HUGE))
+def test_transforms(rig, gated, kind, log2n):
+    """with the halves / quarters threshold cases on the fold contexts at N = 8192 / 16384, and the two-kernel split transform at N = 65536"""
+    fp.test_transforms(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.STREAMING, ids=fp.ids(fp.STREAMING))
+def test_streaming_entries(rig, gated, kind, log2n):
+    fp.test_streaming_entries(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.SMALL + fp.HUGE, ids=fp.ids(fp.SMALL + fp.HUGE))
+def test_reduce_sum(rig, gated, kind, log2n):
+    """memset, partial and final kernels"""
+    fp.test_reduce_sum(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.SMALL + fp.COMPOSED, ids=fp.ids(fp.SMALL + fp.COMPOSED))
+def test_ct_mul(rig, gated, kind, log2n):
+    fp.test_ct_mul(rig, kind, log2n)
+
+
+def test_debug_ct_mul_trace(rig, gated):
+    """the first half of test_diagnostic_and_tuning_entries (dpfhe_ctx_autotune synchronises by its documentation and is left out)"""
+    r = rig("fold", 12)
+    lib, h, poly, orc = r.ctx._lib, r.ctx.handle, r.L * r.n, r.orc
+    batch = 3
+    a, b = r.words(orc, (batch, 2), 250), r.words(orc, (batch, 2), 251)
+    c = fp.Case(r)
+    c.inp("a2", a, 2 * poly)
+    c.inp("b2", b, 2 * poly)
+    c.out("out3", batch * 3 * poly, 3 * poly, orc.ct_mul(a, b, threads=0))
+    c.scratch("trace", batch * r.L * 12, 12)
+    c.run("dpfhe_debug_ct_mul_trace", lambda at: lib.dpfhe_debug_ct_mul_trace(h, at("out3"), at("a2"), at("b2"), batch, at("trace"), at.stream))
+
+
+@pytest.mark.parametrize("kind,log2n", fp.SMALL + fp.COMPOSED, ids=fp.ids(fp.SMALL + fp.COMPOSED))
+def test_key_switching(rig, gated, kind, log2n):
+    fp.test_key_switching(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.EXTENDED, ids=fp.ids(fp.EXTENDED))
+def test_hybrid_key_switching(rig, gated, kind, log2n):
+    fp.test_hybrid_key_switching(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.EXTENDED, ids=fp.ids(fp.EXTENDED))
+def test_hybrid_rotations(rig, gated, kind, log2n):
+    fp.test_hybrid_rotations(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.EXTENDED, ids=fp.ids(fp.EXTENDED))
+def test_deferred_division_stages(rig, gated, kind, log2n):
+    fp.test_deferred_division_stages(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind,log2n", fp.SMALL, ids=fp.ids(fp.SMALL))
+def test_base_extension_strides(rig, gated, kind, log2n):
+    fp.test_base_extension_strides(rig, kind, log2n)
+
+
+@pytest.mark.parametrize("kind", ["fold5", "shoup5"])
+def test_exact_multiplier_calls(rig, gated, kind):
+    fp.test_exact_multiplier_calls(rig, kind)
+
+
+@pytest.mark.parametrize("kind", ["fold", "mixed"])
+def test_matvec(rig, gated, kind):
+    fp.test_matvec(rig, kind)
+
+
+@pytest.mark.parametrize("kind", ["fold2", "shoup60"])
+def test_matvec_at_n4096(rig, gated, kind):
+    fp.test_matvec_at_n4096(rig, kind)
+
+
+@pytest.mark.parametrize("entry", list(fp.COMPOSED_CASES))
+@pytest.mark.parametrize("kind", ["fold", "shoup"])
+def test_composed_forms_and_their_slices(rig, gated, kind, entry):
+    """N = 16384: on a fresh context, on one whose arena of S a larger call of another entry has used, and in slices of one item under
+    set_scratch_limit(2) - every gated call after a warm-up that brought the arena of S to its size"""
+    fp.test_composed_forms_do_not_depend_on_the_scratch_arena(rig, kind, entry)
+
+
+def test_collectives_world_of_one(rig, gated):
+    fp.test_collectives_world_of_one(rig)
+
+
+@pytest.fixture
+def rig32k():
+    made = []
+
+    def make(kind, ln):
+        r = Rig(lr.params(kind, ln))
+        r.kind = f"{kind}{ln}"
+        made.append(r)
+        return r
+    yield make
+    for r in made:
+        r.close()
+
+
+@pytest.mark.parametrize("kind,ln", lr.N32768, ids=[f"{k}_n32768" for k, _ in lr.N32768])
+def test_n32768(rig32k, gated, kind, ln):
+    """dpfhe_rotate_hoisted_qp, dpfhe_rotate_hybrid_hoisted and dpfhe_ntt_inv_galois on the split transforms; the last also with d_out == d_in, staged
+    through the arena of S"""
+    lr.test_footprints_at_n32768(rig32k, kind, ln)
+
+
+# ---- the six entries with sentinel tests of their own --------------------------------------------------------------------------------------------------------
+def component_segments(batch, comps, comp, poly):
+    return [((b * comps + comp) * poly, poly) for b in range(batch)]
+
+
+@pytest.mark.parametrize("kind,log2n", [("mixed", 8), ("fold", 12)], ids=fp.ids([("mixed", 8), ("fold", 12)]))
+def test_expand_uniform(rig, gated, kind, log2n):
+    """component 1 of 3 in 2 items, first_item 5: the other components are stride gaps and must keep the fill pattern (an entry without inputs: a stray
+    launch's words are wiped by the copy behind the gate)"""
+    r = rig(kind, log2n)
+    lib, h, poly = r.ctx._lib, r.ctx.handle, r.L * r.n
+    batch, comps, comp = 2, 3, 1
+    want = wire.expand_host(r.p, batch, comps, comp, SEED, 5)[:, comp]
+    c = fp.Case(r)
+    c.out("buf", batch * comps * poly, comps * poly, want, segments=component_segments(batch, comps, comp, poly))
+    c.run("dpfhe_expand_uniform", lambda at: lib.dpfhe_expand_uniform(h, at("buf"), batch, comps, comp, SEED, 5, at.stream))
+
+
+@pytest.mark.parametrize("comps", [2, 3])
+def test_add_plain_scaled(rig, gated, comps):
+    from test_plain_add_cpu import random_ct, random_plain, twin
+    r = rig("mixed", 8)
+    lib, h, poly, t = r.ctx._lib, r.ctx.handle, r.L * r.n, 65537
+    batch, items = 2, 1
+    rng = np.random.default_rng(comps)
+    ct, plain = random_ct(rng, r.p, batch, comps), random_plain(rng, items, r.n, t) % np.uint64(1 << 32)
+    for negate in (0, 1):
+        want = twin(r.p, ct, plain, t, bool(negate))
+        c = fp.Case(r)
+        c.inout("ct", ct, comps * poly, want)
+        c.inp("plain", plain, r.n)
+        c.run(f"dpfhe_add_plain_scaled in place, {comps} components", lambda at: lib.dpfhe_add_plain_scaled(h, at("ct"), at("ct"), at("plain"), batch, comps, items, t, negate, at.stream))
+        c = fp.Case(r)
+        c.inp("in", ct, comps * poly)
+        c.inp("plain", plain, r.n)
+        c.out("out", ct.size, comps * poly, want)
+        c.run(f"dpfhe_add_plain_scaled apart, {comps} components", lambda at: lib.dpfhe_add_plain_scaled(h, at("out"), at("in"), at("plain"), batch, comps, items, t, negate, at.stream))
+
+
+@pytest.mark.parametrize("bits", [(19, 28), (60, 60)], ids=["19_28", "60_60"])
+def test_compact(rig, gated, bits):
+    from test_compact_cpu import plant_edges, random_words
+    r = rig("fold", 8)
+    lib, h, poly = r.ctx._lib, r.ctx.handle, r.L * r.n
+    batch = 3
+    words = random_words(np.random.default_rng(bits[0]), r.p, batch)
+    plant_edges(r.p, words, *bits)
+    want = wire.compact_host(r.p, words, *bits)
+    record_words = want.size // batch // 8
+    assert want.size == batch * record_words * 8
+    c = fp.Case(r)
+    c.inp("in", words, 2 * poly)
+    c.out("out", batch * record_words, record_words, np.ascontiguousarray(want).reshape(-1).view(np.uint64))
+    c.run(f"dpfhe_compact {bits}", lambda at: lib.dpfhe_compact(h, at("out"), at("in"), batch, bits[0], bits[1], at.stream))
+
+
+@pytest.mark.parametrize("log2n", [8, 15])
+def test_encode_slots(rig, rig32k, gated, log2n):
+    """flags 0, PLAIN and NTT, 3 slot vectors; at N = 32768 the transform over Z_t is two kernels that park their intermediate words in d_out"""
+    from encode_ref import slot_vectors, twin
+    r = rig("mixed", 8) if log2n == 8 else rig32k("fold", 15)
+    lib, n, L, t = r.ctx._lib, r.n, r.L, 65537
+    enc = r.ctx.encoder(t)
+    slots = slot_vectors(np.random.default_rng(log2n), n, t)[[0, 3, 5]]
+    res = twin(r.p.moduli, log2n, t, slots)
+    for flags, want, item in ((0, res, L * n), (_cabi.ENCODE_PLAIN, twin(r.p.moduli, log2n, t, slots, plain=True), n),
+                              (_cabi.ENCODE_NTT, r.orc.ntt_fwd(res, threads=0), L * n)):
+        c = fp.Case(r)
+        c.inp("slots", slots.view(np.uint64), n // 2)
+        c.out("out", want.size, item, want)
+        c.run(f"dpfhe_encode_slots flags {flags}", lambda at: lib.dpfhe_encode_slots(enc, at("out"), at("slots"), 3, flags, at.stream))
+
+
+def test_sample_noise(rig, gated):
+    """ternary, centred binomial and flood, each set (no input: the other components are gaps) and added with DPFHE_NOISE_ADD (the component in-out)"""
+    from test_rerandomize_cpu import CBD21, FLOOD, TERNARY
+    r = rig("mixed", 8)
+    lib, h, poly = r.ctx._lib, r.ctx.handle, r.L * r.n
+    batch, comps, first = 3, 2, 7
+    start = r.words(r.orc, (batch, comps), 900)
+    for kind, param, stream_id, comp in ((TERNARY, 0, 0, 1), (CBD21, 0, 1, 0), (FLOOD, 100, 2, 1)):
+        seg = component_segments(batch, comps, comp, poly)
+        want = wire.noise_host(r.p, batch, comps, comp, kind, param, stream_id, SEED, first)[:, comp]
+        c = fp.Case(r)
+        c.out("buf", batch * comps * poly, comps * poly, want, segments=seg)
+        c.run(f"dpfhe_sample_noise kind {kind}", lambda at: lib.dpfhe_sample_noise(h, at("buf"), batch, comps, comp, kind, param, stream_id, SEED, first, 0, at.stream))
+        want = wire.noise_host(r.p, batch, comps, comp, kind, param, stream_id, SEED, first, add=True, out=start.copy())[:, comp]
+        c = fp.Case(r)
+        c.ar.carve("buf", batch * comps * poly, "inout", comps * poly, data=np.ascontiguousarray(start[:, comp]), segments=seg)
+        c.want["buf"] = want
+        c.run(f"dpfhe_sample_noise kind {kind}, added",
+              lambda at: lib.dpfhe_sample_noise(h, at("buf"), batch, comps, comp, kind, param, stream_id, SEED, first, _cabi.NOISE_ADD, at.stream))
+
+
+@pytest.mark.parametrize("name,log2n,flood_bits", [("mixed", 12, 130), ("pinned60", 14, 200)], ids=["mixed_n4096", "pinned60_n16384"])
+def test_rerandomize(rig, gated, name, log2n, flood_bits):
+    """sample, transform, product, inverse and add: d_ct2 in-out, d_pk input, d_work scratch of exactly 3 batch L N words; the reference is the
+    definition composed from the host twin and the oracle (tests/test_gpu_rerandomize.py)"""
+    from test_gpu_rerandomize import _rerandomize_ref
+    if name == "mixed":
+        r = rig("mixed", log2n)
+    else:
+        r = fp.ParamsRig(name, ntt_primes(log2n, 4, 60))
+    try:
+        lib, h, poly = r.ctx._lib, r.ctx.handle, r.L * r.n
+        batch, first = 2, 11
+        ct, pk = r.words(r.orc, (batch, 2), 910), r.words(r.orc, (2,), 911)
+        c = fp.Case(r)
+        c.inout("ct", ct, 2 * poly, _rerandomize_ref(r.p, ct, pk, flood_bits, SEED, first))
+        c.inp("pk", pk, 2 * poly)
+        c.scratch("work", 3 * batch * poly, 3 * poly)
+        c.run("dpfhe_rerandomize", lambda at: lib.dpfhe_rerandomize(h, at("ct"), at("pk"), batch, flood_bits, SEED, first, at("work"), at.stream))
+    finally:
+        if name != "mixed":
+            r.close()
+
+
+# ---- the C++ facade's Stream* ----------------------------------------------------------------------------------------------------------------------------------
+def build_stream_api_test():
+    exe = os.path.join(ROOT, "tests", "cpp", "test_stream_api")
+    src = os.path.join(ROOT, "tests", "cpp", "test_stream_api.cpp")
+    lib, gate_dir = os.path.join(ROOT, "deeppowers_amd"), os.path.dirname(sg.build_library())
+    deps = [src, sg.LIB, os.path.join(ROOT, "include", "deeppowers", "fhe.hpp"), os.path.join(lib, "libdpfhe_api.so")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", src, "-o", exe,
+                               "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L" + gate_dir, "-lstream_gate", "-L/opt/rocm/lib", "-lamdhip64",
+                               f"-Wl,-rpath,{lib}", f"-Wl,-rpath,{gate_dir}", "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_cpp_facade_stream_arguments():
+    """tests/cpp/test_stream_api.cpp: the facade's Stream* methods behind the same gate on one non-blocking stream - results decrypt to the plaintext
+    computation, the enqueue-only methods return while the stream is held, the synchronising ones wait on S and not on the null stream"""
+    out = subprocess.run([build_stream_api_test(), str(sg.GATE_SECONDS)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout[-3000:] + out.stderr[-2000:]
