@@ -41,17 +41,15 @@ inline void pack_subtrees(unsigned char* dst, const std::vector<u64>& table, Lim
 }
 
 // ---- the class blob ------------------------------------------------------------------------------------------------
-// Tables of a context with per-limb arithmetic classes (round 6): ONE blob, LimbConst[L] | fwd4 | inv4 | (fwd | inv when the batched transforms use another
-// layout) | last[L] | last2[L], every per-limb slot in the format of that limb's class.  The classes' DevTables are typed views of the same blob, each with
-// its own active-limb map.  Single-kernel transforms only (log2 N <= 14).
-struct MixedLayout { size_t o_lc, o_fwd4, o_inv4, o_fwd, o_inv, o_last, o_last2, total; };
+// Tables of a context with per-limb arithmetic classes (round 6): ONE blob, LimbConst[L] | fwd | inv | last[L] | last2[L], every per-limb slot in the
+// format of that limb's class.  The classes' DevTables are typed views of the same blob, each with its own active-limb map.  Single-kernel transforms
+// only (log2 N <= 14).
+struct MixedLayout { size_t o_lc, o_fwd, o_inv, o_last, o_last2, total; };
 inline MixedLayout mixed_layout(int log2n, size_t L) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t n = (size_t)1 << log2n, tab = L * n * kTwSize;
-    const bool two_geo = ntt_loge(log2n) != kFusedLoge;
     MixedLayout m;
-    m.o_lc = 0; m.o_fwd4 = up(L * sizeof(LimbConst)); m.o_inv4 = up(m.o_fwd4 + tab);
-    m.o_fwd = two_geo ? up(m.o_inv4 + tab) : m.o_fwd4; m.o_inv = two_geo ? up(m.o_fwd + tab) : m.o_inv4;
+    m.o_lc = 0; m.o_fwd = up(L * sizeof(LimbConst)); m.o_inv = up(m.o_fwd + tab);
     m.o_last = up(m.o_inv + tab); m.o_last2 = up(m.o_last + L * 32); m.total = up(m.o_last2 + L * 32);
     return m;
 }
@@ -66,9 +64,8 @@ inline std::vector<unsigned char> build_class_blob(int log2n, const std::vector<
         const u64 q = t.lc.q;
         const LimbConst lc = limb_const_of_class(t.lc, cls);
         std::memcpy(&blob[m.o_lc + l * sizeof(LimbConst)], &lc, sizeof(LimbConst));
-        pack_table(&blob[m.o_fwd4 + l * slot], t.rp, cls, q, log2n, kFusedLoge);
-        pack_table(&blob[m.o_inv4 + l * slot], t.irp, cls, q, log2n, kFusedLoge);
-        if (m.o_fwd != m.o_fwd4) { pack_table(&blob[m.o_fwd + l * slot], t.rp, cls, q, log2n, ntt_loge(log2n)); pack_table(&blob[m.o_inv + l * slot], t.irp, cls, q, log2n, ntt_loge(log2n)); }
+        pack_table(&blob[m.o_fwd + l * slot], t.rp, cls, q, log2n, kLoge);
+        pack_table(&blob[m.o_inv + l * slot], t.irp, cls, q, log2n, kLoge);
         reinterpret_cast<InvLast<TwBytes>*>(&blob[m.o_last])[l] = class_last(cls, t.w_last, t.lc.ninv, q);
         // products of two scaled words carry s = 2^(60-k) twice: their inverse transform ends on twiddles with s^-1 folded in (DevTables::last2)
         const u64 sinv = cls == kClassFoldScaled ? h_powmod((1ull << fold_scaled_shift(q)) % q, q - 2, q) : 1;
@@ -82,7 +79,6 @@ inline DevTables<Arith> mixed_view(const unsigned char* b, const MixedLayout& m,
     DevTables<Arith> tb{};
     tb.lc = reinterpret_cast<const LimbConst*>(b + m.o_lc);
     tb.fwd = reinterpret_cast<const Tw*>(b + m.o_fwd); tb.inv = reinterpret_cast<const Tw*>(b + m.o_inv);
-    tb.fwd4 = reinterpret_cast<const Tw*>(b + m.o_fwd4); tb.inv4 = reinterpret_cast<const Tw*>(b + m.o_inv4);
     tb.last = reinterpret_cast<const InvLast<Tw>*>(b + m.o_last);
     tb.last2 = reinterpret_cast<const InvLast<Tw>*>(b + m.o_last2);
     tb.n_sub = 1;
@@ -100,7 +96,7 @@ inline bool ctx_limb_classes(int log2n, const std::vector<HostLimbTables>& ht, b
 
 // ---- the lazy-multiply blob ----------------------------------------------------------------------------------------
 // Round 11: the fused multiply of the pinned primes at N = 4096 runs its transforms on twiddles split at bit 29 (FoldArith::mul_tw29_add, NttBody's
-// LAZY29 plans).  Those tables live in a blob of their own - fwd29 | inv29 | last29, fused layout only, [L] slots with only the fold limbs' filled - next
+// LAZY29 plans).  Those tables live in a blob of their own - fwd29 | inv29 | last29, [L] slots with only the fold limbs' filled - next
 // to the context-wide blob and the class blob, which stay byte for byte what they were.  Built for every context at log2 N = 12 in which a limb runs on
 // FoldArith: the all-fold contexts, and the fold limbs of a context with per-limb classes (they launch the same kernel).
 constexpr int kLazy29Log2N = 12;
@@ -123,7 +119,7 @@ inline std::vector<unsigned char> build_lazy29_blob(int log2n, const std::vector
     auto pack29 = [&](size_t off, const std::vector<u64>& words, u64 q) {
         std::vector<TwBytes> t(words.size());
         for (size_t i = 0; i < words.size(); ++i) t[i] = tw_bytes(h_tw_fold29(words[i], q));
-        permute_window0(t, log2n, kFusedLoge, geo_perm_stages(log2n, kFusedLoge));
+        permute_window0(t, log2n, kLoge, geo_perm_stages(log2n, kLoge));
         std::memcpy(&blob[off], t.data(), t.size() * kTwSize);
     };
     for (size_t l = 0; l < L; ++l) {
@@ -142,16 +138,15 @@ inline void lazy29_view(DevTables<FoldArith>& tb, const unsigned char* d, const 
 }
 
 // ---- the context-wide blob -----------------------------------------------------------------------------------------
-// Tables of the context-wide arithmetic (FoldArith or ShoupArith, every limb): ONE blob of 256-byte aligned sections.  One twiddle table pair per kernel
-// geometry in use: slot 0 = the fused kernels' LOGE 4 layout, slot 1 = the batched NTT kernels' layout when that differs.  Split transforms (N > 16384)
-// store, per limb, n_sub tables of N2 points (sub-trees of the full table) plus the top-stage twiddles.  FoldArith at N = 8192 / 16384 adds the "halves" /
+// Tables of the context-wide arithmetic (FoldArith or ShoupArith, every limb): ONE blob of 256-byte aligned sections.  One twiddle table pair
+// (fwd | inv), in the layout every kernel reads (devtables.h kLoge).  Split transforms (N > 16384) store, per limb, n_sub tables of N2 points (sub-trees of the full table) plus the top-stage twiddles.  FoldArith at N = 8192 / 16384 adds the "halves" /
 // "quarters" tables next to the one-piece ones (ntt_halves.h / ntt_quarters.h; the fused kernels keep the one-piece layout); elsewhere their offsets are
 // the end of the blob and their pointers stay null.
 struct CtxLayout {
-    int log_n1, log_n2, loge_ntt;
+    int log_n1, log_n2;
     size_t n_sub, n2;
-    bool split, two_geo, halves, quarters;
-    size_t o_lc, o_fwd4, o_inv4, o_fwd, o_inv, o_last, o_top_fwd, o_top_inv, o_top_last, o_resc, o_hfwd, o_hinv, o_htop_fwd, o_htop_last,
+    bool split, halves, quarters;
+    size_t o_lc, o_fwd, o_inv, o_last, o_top_fwd, o_top_inv, o_top_last, o_resc, o_hfwd, o_hinv, o_htop_fwd, o_htop_last,
            o_qfwd, o_qinv, o_qtop_fwd, o_qtop_inv, o_qtop_last, total;
 };
 inline CtxLayout ctx_layout(int log2n, size_t L, bool fold) {
@@ -159,13 +154,11 @@ inline CtxLayout ctx_layout(int log2n, size_t L, bool fold) {
     CtxLayout m;
     m.log_n1 = split_log_n1(log2n); m.log_n2 = log2n - m.log_n1;
     m.n_sub = (size_t)1 << m.log_n1; m.n2 = (size_t)1 << m.log_n2;
-    m.loge_ntt = ntt_loge(m.log_n2);
-    m.split = m.log_n1 > 0; m.two_geo = !m.split && m.loge_ntt != kFusedLoge;
+    m.split = m.log_n1 > 0;
     m.halves = log2n == 13 && fold;     // the halves tables (launch.h): large batched transforms at N = 8192
     m.quarters = log2n == 14 && fold;   // four sub-tree tables per limb + the column stages' twiddles
     const size_t n_sub = m.n_sub, tab = L * ((size_t)1 << log2n) * kTwSize;
-    m.o_lc = 0; m.o_fwd4 = up(m.o_lc + L * sizeof(LimbConst)); m.o_inv4 = up(m.o_fwd4 + tab);
-    m.o_fwd = m.two_geo ? up(m.o_inv4 + tab) : m.o_fwd4; m.o_inv = m.two_geo ? up(m.o_fwd + tab) : m.o_inv4;
+    m.o_lc = 0; m.o_fwd = up(m.o_lc + L * sizeof(LimbConst)); m.o_inv = up(m.o_fwd + tab);
     m.o_last = up(m.o_inv + tab); m.o_top_fwd = up(m.o_last + L * n_sub * 2 * kTwSize); m.o_top_inv = up(m.o_top_fwd + L * n_sub * kTwSize);
     m.o_top_last = up(m.o_top_inv + L * n_sub * kTwSize); m.o_resc = up(m.o_top_last + L * 2 * kTwSize);
     const bool h = m.halves, qu = m.quarters;
@@ -191,11 +184,8 @@ inline std::vector<unsigned char> build_ctx_blob(int log2n, const std::vector<Ho
         const u64 q = t.lc.q;
         std::memcpy(&blob[lay.o_lc + l * sizeof(LimbConst)], &t.lc, sizeof(LimbConst));
         if (!lay.split) {
-            for (int geo = 0; geo < (lay.two_geo ? 2 : 1); ++geo) {
-                const int loge = geo ? lay.loge_ntt : kFusedLoge;
-                pack_table(&blob[(geo ? lay.o_fwd : lay.o_fwd4) + l * n * kTwSize], t.rp, k, q, log2n, loge);
-                pack_table(&blob[(geo ? lay.o_inv : lay.o_inv4) + l * n * kTwSize], t.irp, k, q, log2n, loge);
-            }
+            pack_table(&blob[lay.o_fwd + l * n * kTwSize], t.rp, k, q, log2n, kLoge);
+            pack_table(&blob[lay.o_inv + l * n * kTwSize], t.irp, k, q, log2n, kLoge);
             lasts(lay.o_last)[l] = class_last(k, t.w_last, t.lc.ninv, q);
             if (lay.quarters) {
                 pack_subtrees(&blob[lay.o_qfwd + l * n * kTwSize], t.rp, k, q, 14, 2, 4);
@@ -211,8 +201,8 @@ inline std::vector<unsigned char> build_ctx_blob(int log2n, const std::vector<Ho
                 lasts(lay.o_htop_last)[l] = lasts(lay.o_last)[l];   // the column stage IS the one-piece transform's last stage
             }
         } else {
-            pack_subtrees(&blob[lay.o_fwd + l * n * kTwSize], t.rp, k, q, log2n, lay.log_n1, lay.loge_ntt);
-            pack_subtrees(&blob[lay.o_inv + l * n * kTwSize], t.irp, k, q, log2n, lay.log_n1, lay.loge_ntt);
+            pack_subtrees(&blob[lay.o_fwd + l * n * kTwSize], t.rp, k, q, log2n, lay.log_n1, kLoge);
+            pack_subtrees(&blob[lay.o_inv + l * n * kTwSize], t.irp, k, q, log2n, lay.log_n1, kLoge);
             // generic primes: no N^-1 inside a block.  FoldArith: the block's last stage divides its sums by N2 exactly (FoldArith::mul_ninv),
             // so its differences carry N2^-1 in their twiddle; the column stage then multiplies by N1^-1 (top_last below)
             const u64 n2inv = fold ? h_powmod((u64)n2 % q, q - 2, q) : 1;
@@ -240,7 +230,6 @@ inline DevTables<Arith> ctx_view(const unsigned char* d, const CtxLayout& m, siz
     DevTables<Arith> tb{};
     tb.lc = reinterpret_cast<const LimbConst*>(d + m.o_lc);
     tb.fwd = reinterpret_cast<const Tw*>(d + m.o_fwd); tb.inv = reinterpret_cast<const Tw*>(d + m.o_inv);
-    tb.fwd4 = reinterpret_cast<const Tw*>(d + m.o_fwd4); tb.inv4 = reinterpret_cast<const Tw*>(d + m.o_inv4);
     tb.last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_last);
     tb.top_fwd = reinterpret_cast<const Tw*>(d + m.o_top_fwd); tb.top_inv = reinterpret_cast<const Tw*>(d + m.o_top_inv);
     tb.top_last = reinterpret_cast<const InvLast<Tw>*>(d + m.o_top_last);

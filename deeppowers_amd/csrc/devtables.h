@@ -8,18 +8,16 @@ namespace dpfhe {
 struct QuartersTop;   // ntt_quarters.h
 
 // ---- the geometry constants that shape the tables (the launchers read them through launch.h) ----
-// words-per-thread exponent of the batched NTT kernels (launch_impl.h DPFHE_GEO_SWITCH); the fused kernels use 4.
-// ctx_tables.h builds a second table layout whenever the two differ.
-// (N = 8192 was measured with 32 words per thread / 3 phases and with 16 / 4 phases: same time, the kernels are VALU-bound;
-// 16 everywhere keeps one twiddle layout per context)
-// N = 16384 (128 KiB of LDS per polynomial): 1024 threads, one workgroup per CU (16 words per thread measured 5 % faster
-// than 32 on the forward transform); the fused kernels stop at N = 8192.
-constexpr int ntt_loge(int /*log2n*/) { return 4; }   // (32 words per thread at N = 4096 measured equal to slower - round 4 A/B, closed)
+// words-per-thread exponent of every kernel that runs a transform: 16 words per thread at every ring degree, so a context has ONE twiddle layout.
+// Measured, closed: the fused kernels with 8 words per thread were slower (round 3 A/B); the batched transforms with 32 were equal at N = 8192 (3 phases
+// against 4: same time, the kernels are VALU-bound), equal to slower at N = 4096 and 5 % slower on the forward transform at N = 16384 (round 4 A/B).
+// (Geo / NttBody / pack_table keep their LOGE parameter: tests/test_emulated_kernels.py proves the address maps at other exponents too.)
+constexpr int kLoge = 4;
 constexpr int kMaxLog2N = 16;
+// N = 16384 (128 KiB of LDS per polynomial): 1024 threads, one workgroup per CU; the fused kernels stop at N = 8192 (launch.h kMaxFusedLog2N).
 // N > 16384: split transform - log2(N1) top stages in ntt_top_kernel, then N1 transforms of N2 = 4096 points each
 constexpr int kSplitLog2N2 = 12;
 constexpr int split_log_n1(int log2n) { return log2n > 14 ? log2n - kSplitLog2N2 : 0; }
-constexpr int kFusedLoge = 4;   // words-per-thread exponent of the fused kernels (8 per thread measured slower - round 3 A/B, closed)
 
 template <class Tw>
 struct InvLast {  // per limb: last inverse stage twiddles with N^-1 folded in
@@ -27,15 +25,12 @@ struct InvLast {  // per limb: last inverse stage twiddles with N^-1 folded in
     Tw w_ninv;    // N^-1
 };
 
-// Twiddle tables are stored in the layout of the kernel geometry that reads them (tables.h permute_window0):
-// fwd/inv for the batched NTT kernels (ntt_loge above), fwd4/inv4 for the fused kernels, which always run 16
-// words per thread.  The two coincide unless the NTT geometry is not LOGE = 4 (N = 8192).
+// Twiddle tables are stored in the layout of the kernel geometry that reads them (tables.h permute_window0): LOGE = kLoge above,
+// for the batched transforms and the fused kernels alike.
 template <class Arith>
 struct DevTables {
     const typename Arith::Tw* fwd;          // [L][N]  psi^brv(i)
     const typename Arith::Tw* inv;          // [L][N]  psi^-brv(i)
-    const typename Arith::Tw* fwd4;
-    const typename Arith::Tw* inv4;
     // split transform (N > 16384): fwd / inv / last then hold one N2-point table per (limb, block) - [L][n_sub][N2] and
     // [L][n_sub] - and the first log2(n_sub) stages run in ntt_top_kernel with these workgroup-uniform twiddles
     const typename Arith::Tw* top_fwd;      // [L][n_sub]  psi^brv(i), entry m + i of the full table, i < n_sub
@@ -59,7 +54,7 @@ struct DevTables {
     // FoldScaledArith class only: the same with s^-1 = 2^-(60-k) folded in - the last stage of an inverse transform whose input is a PRODUCT of two
     // scaled words (the fused multiply's lazy tensor step).  Null elsewhere.
     const InvLast<typename Arith::Tw>* last2;  // [L]
-    // FoldArith at N = 4096 only (null elsewhere): the fused-layout tables and the last stage once more, every twiddle split at bit 29
+    // FoldArith at N = 4096 only (null elsewhere): the same tables and the last stage once more, every twiddle split at bit 29
     // (FoldArith::mul_tw29_add) - what ct_mul_quad_kernel's lazy transforms read.  A separate blob (ctx_tables.h build_lazy29_blob).
     const typename Arith::Tw* fwd29;        // [L][N]
     const typename Arith::Tw* inv29;        // [L][N]

@@ -85,7 +85,7 @@ struct dpfhe_ctx {
     int n_cu = 256;          // compute units of the device (launch-size caps of the streaming kernels)
     std::vector<uint64_t> moduli;   // host copy (constants of dpfhe_base_extend / dpfhe_scale_round)
     uint64_t p_special = 0;  // the LAST modulus (the special prime of hybrid key switching when this is an extended context)
-    void* d_blob = nullptr;  // one allocation: LimbConst[L] | fwd | inv | last | RescaleConst[L]  (both arithmetic layouts share it: ctx_layout)
+    void* d_blob = nullptr;  // one allocation: LimbConst[L] | fwd | inv | last | RescaleConst[L]  (FoldArith's and ShoupArith's tables share the arrangement: ctx_layout)
     const LimbConst* lc = nullptr;   // the limb constants at the head of d_blob: what the one-pass kernels read, whichever table set below is filled
     const RescaleConst* d_rescale = nullptr;
     DevTables<ShoupArith> shoup{};   // the table set of the context-wide arithmetic (with_ctx_arith): the one that matches `fold` is filled
@@ -93,11 +93,11 @@ struct dpfhe_ctx {
     // Round 6 - per-limb arithmetic classes.  A context whose limbs are not ALL of the pinned 2^60 - d shape used to run every limb on the
     // generic (Harvey / Shoup) kernels.  Now each limb gets the fastest policy its prime admits (tables.h limb_class) for the batched transforms and
     // the fused multiply: one launch per class present, each over that class's limbs only (devtables.h DevTables::n_active / active_map).  The
-    // generic tables above stay complete (every limb), so the key-switching kernels of such a context run as before.
+    // generic tables above stay complete (every limb): the one-pass kernels read their limb constants whatever the classes are (with_ctx_arith).
     // `classes` is set when L <= 16, 8 <= log2 N <= 14 and at least one limb has a faster class than the context-wide policy.
     bool classes = false;
     int uniform_cls = kClassShoup;                    // the class ALL limbs share (kClassShoup when they differ, or when `classes` is off): which policy's KEY-SWITCHING
-                                                      // kernels the context runs (with_policy below); a mixture keeps the generic ones, on the complete generic tables
+                                                      // kernels the context runs (with_policy below); a mixture launches them once per class (class_mixture below)
     unsigned char limb_cls[16] = {};                  // LimbClass of limb i
     unsigned long long cls_map = 0;                   // the same, 4 bits per limb
     void* lazy29_blob = nullptr;                      // the fused multiply's bit-29 twiddles (ctx_tables.h build_lazy29_blob): log2 N = 12 with a FoldArith limb, null elsewhere
@@ -437,10 +437,14 @@ static int for_each_class(const dpfhe_ctx* c, size_t limbs_used, Fn fn) {
     return rc;
 }
 
-// The policy of the KEY-SWITCHING kernels (relin_kernel, hoisted_ks_kernel, ntt_inv_galois_kernel): fold for the pinned primes; the class's own for a
-// context whose limbs all share one class (round 6: the generic forms of those kernels with that class's transforms and products - an all-f64 context no
-// longer key-switches at the generic kernels' rate); the generic policy on the complete generic tables otherwise (a MIXTURE of classes does not come here for
-// its transform-bearing kernels: relin_launch / with_policy_or_classes below launch once per class).  fn(tables) launches.
+// A MIXTURE of classes: per-limb classes are on and the limbs do not all share one.  Its transform-bearing kernels launch once per class present
+// (for_each_class), each on that class's view of the class blob; uniform contexts launch once (with_policy).
+static bool class_mixture(const dpfhe_ctx* c) { return c->classes && c->uniform_cls == kClassShoup; }
+
+// The policy of the KEY-SWITCHING kernels (relin_kernel, hoisted_ks_kernel, ntt_inv_galois_kernel) of a context that is NOT a mixture: fold for the pinned
+// primes; the class's own for a context whose limbs all share one class (round 6: the generic forms of those kernels with that class's transforms and
+// products - an all-f64 context no longer key-switches at the generic kernels' rate); the generic policy on the generic tables otherwise.  A mixture does
+// not come here: relin_launch / with_policy_or_classes below launch it once per class, on the class blob.  fn(tables) launches.
 template <class Fn>
 static int with_policy(const dpfhe_ctx* c, Fn fn) {
     if (c->fold) return fn(c->foldt);
@@ -455,7 +459,7 @@ static int with_policy(const dpfhe_ctx* c, Fn fn) {
 // relin_kernel launches (`blocks` = items x L): on the context's policy, or - a MIXTURE of classes - one launch per class present, each over its own limbs
 // (relin_kernel maps its workgroups through DevTables::active_map: the digits of every limb still enter every limb's transforms)
 static int relin_launch(const dpfhe_ctx* c, int mode, u64* out, const u64* in, const u64* evk, size_t key_stride, unsigned key_group, size_t blocks, hipStream_t s) {
-    if (c->classes && c->uniform_cls == kClassShoup) {
+    if (class_mixture(c)) {
         const size_t items = blocks / c->n_limbs;
         return for_each_class(c, c->n_limbs, [&](const auto& tb) { return launch_relin((int)c->log2n, mode, out, in, evk, key_stride, key_group, items * (size_t)tb.n_active, tb, s); });
     }
@@ -465,7 +469,7 @@ static int relin_launch(const dpfhe_ctx* c, int mode, u64* out, const u64* in, c
 // the same choice for kernels whose workgroups map through DevTables::active_map (hoisted_ks_kernel, ntt_inv_galois_kernel): a mixture of classes launches once per class
 template <class Fn>
 static int with_policy_or_classes(const dpfhe_ctx* c, Fn fn) {
-    if (c->classes && c->uniform_cls == kClassShoup) return for_each_class(c, c->n_limbs, fn);
+    if (class_mixture(c)) return for_each_class(c, c->n_limbs, fn);
     return with_policy(c, fn);
 }
 
@@ -519,7 +523,7 @@ template <int OP>
 static void launch_dy(const dpfhe_ctx* c, u64* out, const u64* a, const u64* b, size_t npolys, hipStream_t s, int b_period) {
     // distinct streams of the launch: a, b (unless broadcast or the same buffer), the result (unless in place; read as well by mul_add)
     const int streams = 1 + ((OP != DY_NEG && !b_period && b != a) ? 1 : 0) + ((out != a && out != b) ? 1 : 0);
-    const bool nt = (npolys << c->log2n) * sizeof(u64) * (size_t)streams > ((size_t)256 << 20);   // cannot stay in the Infinity Cache
+    const bool nt = (npolys << c->log2n) * sizeof(u64) * (size_t)streams > kInfinityCacheBytes;   // cannot stay in the Infinity Cache
     with_ctx_arith(c, [&](auto arith) {
         typedef decltype(arith) Arith;
         if (nt) hipLaunchKernelGGL((dyadic_kernel<Arith, OP, true>), dim3((unsigned)npolys), dim3(256), 0, s, out, a, b, c->lc, (int)c->n_limbs, 1 << c->log2n, b_period);
@@ -560,7 +564,6 @@ extern "C" int dpfhe_multiply_plain(dpfhe_ctx* c, uint64_t* o, const uint64_t* a
 // ------------------------------------------------------------------------------------------------
 // ---- ring degrees above 8192: the fused kernels stop there (kernels_large.h); the same operations composed from the batched transforms
 // and one-pass streaming kernels.  Their scratch comes from per-stream arenas (StreamScratch below).
-static const uint32_t kFusedMaxLog2N = 13;
 
 // Scratch of the composed large-ring operations: one ARENA per (context, stream), a plain hipMalloc made the first time that stream runs a
 // composed operation and grown (hipStreamSynchronize of that stream + hipFree + hipMalloc) only when a larger slice than ever before arrives;
@@ -641,7 +644,7 @@ extern "C" size_t dpfhe_ctx_scratch_bytes(const dpfhe_ctx* c) {
 
 static int ct_mul_composed_slice(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch, uint32_t flags, hipStream_t s) {
     const size_t L = c->n_limbs, n = (size_t)1 << c->log2n, poly = L * n;
-    const int chunks = (int)(n / 512);
+    const int chunks = chunks_of(n);
     const size_t grid = batch * L * (size_t)chunks;
     if (grid > kMaxGrid || !ntt_grid_fits(c, batch * 3 * L)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "batch too large for one launch");
     StreamScratch ws(c, s);
@@ -664,7 +667,7 @@ static int ct_mul_composed_slice(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t*
 static int key_switch_composed_slice(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in, int in_comps, int add_mask, const uint64_t* d_evk, size_t batch,
                                      hipStream_t s, const char* what) {
     const size_t L = c->n_limbs, n = (size_t)1 << c->log2n;
-    const int chunks = (int)(n / 512);
+    const int chunks = chunks_of(n);
     const size_t lift_grid = batch * L * L * (size_t)chunks;
     if (lift_grid > kMaxGrid || 2 * batch * L * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, batch * L * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     StreamScratch ws(c, s);
@@ -722,7 +725,7 @@ extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_ct_mul");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->log2n > kFusedMaxLog2N) return ct_mul_composed(c, d_out3, d_a2, d_b2, batch, flags, s);
+    if (c->log2n > kMaxFusedLog2N) return ct_mul_composed(c, d_out3, d_a2, d_b2, batch, flags, s);
     if (flags == 0 && c->fold) {   // coefficient domain in and out: the form chosen for this box (bit-identical results)
         const int v = c->ct_mul_variant.load(std::memory_order_relaxed);
         if (v != ct_mul_default_variant((int)c->log2n) && ct_mul_variant_compiled(c, v)) {
@@ -731,7 +734,7 @@ extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2
         }
     }
     int rc;
-    if (c->classes && c->log2n <= kFusedMaxLog2N) {   // one launch per arithmetic class of the limbs (dpfhe_ctx::classes)
+    if (c->classes) {   // one launch per arithmetic class of the limbs (dpfhe_ctx::classes)
         const size_t pairs = blocks / c->n_limbs;
         rc = for_each_class(c, c->n_limbs, [&](const auto& tb) { return launch_ct_mul((int)c->log2n, flags, d_out3, d_a2, d_b2, pairs * (size_t)tb.n_active, tb, s); });
     } else {
@@ -768,7 +771,7 @@ extern "C" int dpfhe_relinearize(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t*
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_relinearize", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_relinearize");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->log2n > kFusedMaxLog2N) return key_switch_composed(c, d_out2, d_in3, 3, 3, d_evk, batch, s, "dpfhe_relinearize");
+    if (c->log2n > kMaxFusedLog2N) return key_switch_composed(c, d_out2, d_in3, 3, 3, d_evk, batch, s, "dpfhe_relinearize");
     const int rc = relin_launch(c, 0, d_out2, d_in3, d_evk, 0, 1, blocks, s);
     if (rc) return fail(DPFHE_INVALID_STATE, "dpfhe_relinearize", "no kernel geometry for this log2_n");
     return check_launch("relin kernel launch");
@@ -784,7 +787,7 @@ extern "C" int dpfhe_switch_key(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* 
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_switch_key", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_switch_key");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->log2n > kFusedMaxLog2N) return key_switch_composed(c, d_out2, d_in2, 2, 1, d_key, batch, s, "dpfhe_switch_key");
+    if (c->log2n > kMaxFusedLog2N) return key_switch_composed(c, d_out2, d_in2, 2, 1, d_key, batch, s, "dpfhe_switch_key");
     const int rc = relin_launch(c, 1, d_out2, d_in2, d_key, 0, 1, blocks, s);
     if (rc) return fail(DPFHE_INVALID_STATE, "dpfhe_switch_key", "no kernel geometry for this log2_n");
     return check_launch("switch_key kernel launch");
@@ -792,7 +795,7 @@ extern "C" int dpfhe_switch_key(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* 
 
 // rescale_kernel over `blocks` (polynomial, kept limb, 512-word chunk) workgroups; `add` (add_comps components per item, null: none) as add_mask selects
 static void launch_rescale(const dpfhe_ctx* c, size_t blocks, hipStream_t s, u64* out, const u64* in, const u64* add, int add_comps, int add_mask) {
-    const int n = 1 << c->log2n, chunks = (n + 511) / 512;
+    const int n = 1 << c->log2n, chunks = chunks_of(n);
     with_ctx_arith(c, [&](auto arith) {
         hipLaunchKernelGGL((rescale_kernel<decltype(arith)>), dim3((unsigned)blocks), dim3(256), 0, s, out, in, add, add_comps, add_mask, c->lc, c->d_rescale, (int)c->n_limbs, n, chunks);
     });
@@ -804,7 +807,7 @@ extern "C" int dpfhe_rescale(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in
     if (n_rns_polys == 0) return DPFHE_SUCCESS;
     if (!d_out || !d_in || misaligned(d_out) || misaligned(d_in)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_rescale", "null or misaligned buffer");
     const int n = 1 << c->log2n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     const size_t blocks = n_rns_polys * (c->n_limbs - 1) * (size_t)chunks;
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_rescale", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_rescale");
@@ -827,7 +830,7 @@ static void launch_lift_digits(const dpfhe_ctx* c, size_t grid, hipStream_t s, u
 static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* comp0, size_t item_stride, const uint64_t* d_keys, size_t key_stride, unsigned key_group,
                                  size_t batch, hipStream_t s, const char* what) {
     const size_t L = c->n_limbs, Ld = L - 1;
-    const int n = 1 << c->log2n, ch = n / 512;
+    const int n = 1 << c->log2n, ch = chunks_of(n);
     const size_t per = slice_items(c, batch, Ld * L * (size_t)n);
     for (size_t i0 = 0; i0 < batch; i0 += per) {
         const size_t m = batch - i0 < per ? batch - i0 : per;
@@ -871,7 +874,7 @@ static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* 
     DPFHE_ON_DEVICE(c, "hybrid key switch");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int mode = in_comps == 3 ? 2 : 3;
-    if (c->log2n > kFusedMaxLog2N) {
+    if (c->log2n > kMaxFusedLog2N) {
         // no fused kernel: digits lifted to Q P -> one batched transform -> inner products with the key(s) -> batched inverse into `work`;
         // in slices whose scratch (Ld L N words per item) stays below the context's limit
         if (int rc = key_products_composed(c, d_work, d_in + (size_t)(in_comps - 1) * Ld * n, (size_t)in_comps * Ld * n, d_key, key_stride, (unsigned)kg, batch, s, what)) return rc;
@@ -884,7 +887,7 @@ static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* 
         if (e) return e;
     }
     // divide by P with rounding and add c0 (and c1 for relinearisation): one pass over the 2*batch polynomials of `work`
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     const size_t rblocks = batch * 2 * Ld * (size_t)chunks;
     if (rblocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     launch_rescale(c, rblocks, s, d_out2, d_work, d_in, in_comps, in_comps == 3 ? 3 : 1);
@@ -968,7 +971,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
     if (int rc = check_extended(c, what)) return rc;
     if (batch == 0 || n_items == 0) return DPFHE_SUCCESS;
-    const bool composed = c->log2n > (uint32_t)kMaxFusedLog2N;   // N >= 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
+    const bool composed = c->log2n > kMaxFusedLog2N;   // N >= 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
     if (!d_out2 || !d_in2 || !galois_elts || !d_keys || (!composed && (!d_work || !d_rotated0)) || !d_digits || misaligned(d_out2) || misaligned(d_in2) || misaligned(d_keys) ||
         misaligned(d_work) || misaligned(d_rotated0) || misaligned(d_digits))
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
@@ -983,7 +986,7 @@ extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const
         overlaps(d_digits, dig_words, d_rotated0, rot_words) || overlaps(d_digits, dig_words, d_in2, in_words) || overlaps(d_rotated0, rot_words, d_in2, in_words))
         return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
     const size_t key_words = Ld * 2 * L * (size_t)n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     if (composed) {
         DPFHE_ON_DEVICE(c, what);
         // N >= 16384 (round 5; N = 32768, 65536 on the split transforms): no fused hoisted kernel - the deferred-division pipeline instead: dpfhe_rotate_hoisted_qp gives, per rotation and item,
@@ -1060,7 +1063,7 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
         overlaps(d_digits, dig_words, d_in2, in_words) || overlaps(d_digits, dig_words, d_in_ntt, in_words) || overlaps(d_in_ntt, in_words, d_in2, in_words))
         return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
     const size_t key_words = Ld * 2 * L * (size_t)n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     if ((batch + 1) * T * L * 8 > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid || T * 2 * L * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, T * Ld * L))
         return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     const u64 p_special = c->p_special;
@@ -1167,7 +1170,7 @@ extern "C" int dpfhe_switch_key_qp(dpfhe_ctx* c, uint64_t* d_out_qp, const uint6
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t key_words = Ld * 2 * L * (size_t)n;
-    if (c->log2n > kFusedMaxLog2N)   // composed from the batched transform (round 5): the digits of c1, lifted and transformed, times the group's key
+    if (c->log2n > kMaxFusedLog2N)   // composed from the batched transform (round 5): the digits of c1, lifted and transformed, times the group's key
         return key_products_composed(c, d_out_qp, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, d_keys, key_words, (unsigned)group, batch, s, what);
     const int rc = relin_launch(c, 4, d_out_qp, d_in2, d_keys, key_words, (unsigned)group, blocks, s);
     if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel geometry for this log2_n");
@@ -1183,7 +1186,7 @@ extern "C" int dpfhe_rescale_bsgs(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
     const size_t L = c->n_limbs, Ld = L - 1;
     const int n = 1 << c->log2n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     if (overlaps(d_out2, batch * 2 * Ld * n, d_in_qp, batch * 2 * L * n) || (n_add && overlaps(d_out2, batch * 2 * Ld * n, d_addends, n_add * batch * 2 * Ld * n)))
         return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
     const size_t blocks = batch * 2 * Ld * (size_t)chunks;
@@ -1232,7 +1235,7 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
         const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles;
         if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_plain", "too many rows for one launch");
         // a W beyond the 256 MiB Infinity Cache is a read-once stream (every tile goes to exactly one workgroup here): non-temporal loads
-        const bool ntw = rows * cols * ((size_t)c->n_limbs << c->log2n) * sizeof(u64) > ((size_t)256 << 20);
+        const bool ntw = rows * cols * ((size_t)c->n_limbs << c->log2n) * sizeof(u64) > kInfinityCacheBytes;
         // (the branch-free FULL form of the kernel, which the multi-right-hand-side product takes, measured SLOWER here: 1412 against 1258 us on configs[2] -
         // this launch streams 6 GiB of W from HBM with two right-hand-side polynomials per workgroup and lives on memory-level parallelism, not on issue slots)
         if (ntw) hipLaunchKernelGGL((matvec_fold_kernel<RT, 2, WPT, true>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->lc, (int)c->n_limbs, n, chunks, rows,
@@ -1241,7 +1244,7 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
                                 (size_t)2, 1u, (unsigned)(rtiles * slabs));
         return check_launch("matvec kernel launch");
     }
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     const size_t slabs = c->n_limbs * (size_t)chunks;
     const size_t blocks = ((slabs + 7) / 8) * 8 * ((rows + RT - 1) / RT);   // block ids laid out per XCD: kernels_misc.h matvec_kernel
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_plain", "too many rows for one launch");
@@ -1309,7 +1312,7 @@ extern "C" int dpfhe_matvec_scalar(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* 
     if (!d_y || !d_w || !d_x || misaligned(d_y) || misaligned(d_x) || (reinterpret_cast<uintptr_t>(d_w) & 7))
         return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_scalar", "null or misaligned buffer");
     const int n = 1 << c->log2n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     constexpr int RT = 8;
     const size_t blocks = ((rows + RT - 1) / RT) * c->n_limbs * (size_t)chunks;
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_scalar", "too many rows for one launch");
@@ -1329,7 +1332,7 @@ extern "C" int dpfhe_reduce_sum(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_reduce_sum", "too many components");
     DPFHE_ON_DEVICE(c, "dpfhe_reduce_sum");
     const int n = 1 << c->log2n;
-    const int chunks = (n + 511) / 512;
+    const int chunks = chunks_of(n);
     const size_t words_per_item = components * c->n_limbs * (size_t)n;
     // batch splits (their partial sums are combined with atomics): 15 for the large batches of the sharded multiply; a short batch (the
     // 32 rotated terms of a packed layer) keeps at least 8 items per split, so that every work item has 4 independent loads in flight
@@ -1369,7 +1372,7 @@ extern "C" int dpfhe_canonicalize_sum(dpfhe_ctx* c, uint64_t* d_io, size_t n_rns
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_canonicalize_sum", "null context");
     if (n_rns_polys == 0) return DPFHE_SUCCESS;
     if (!d_io || misaligned(d_io)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_canonicalize_sum", "null or misaligned buffer");
-    const int n = 1 << c->log2n, chunks = (n + 511) / 512;
+    const int n = 1 << c->log2n, chunks = chunks_of(n);
     const size_t blocks = n_rns_polys * c->n_limbs * (size_t)chunks;
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_canonicalize_sum", "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_canonicalize_sum");
@@ -1389,7 +1392,7 @@ static int base_extend_common(dpfhe_ctx* c, int mode, uint64_t* d_out, size_t ou
     if (mode == 1 && !(dst0 >= src0 + ns || dst0 + nd <= src0)) return fail(DPFHE_INVALID_ARGUMENT, what, "the dropped limbs and the kept limbs must be disjoint");
     if (!d_out || !d_in || misaligned(d_out) || misaligned(d_in) || out_stride_limbs < nd || in_stride_limbs < ns) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer, or an item stride shorter than its limbs");
     const size_t n = (size_t)1 << c->log2n;
-    const int chunks = (int)((n + 511) / 512);
+    const int chunks = chunks_of(n);
     if (n_polys * (size_t)chunks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     {   // mode 1: d_in points at the first dropped limb of item 0 inside a [n_polys][L][N] buffer that starts src0 limbs earlier
         const uint64_t* in_lo = mode == 1 ? d_in - (size_t)src0 * n : d_in;
@@ -1460,7 +1463,7 @@ extern "C" int dpfhe_copy(dpfhe_ctx* c, uint64_t* d_dst, const uint64_t* d_src, 
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_copy", "too many words for one launch");
     DPFHE_ON_DEVICE(c, "dpfhe_copy");
     // streams that cannot live in the 256 MiB Infinity Cache (source + destination) go around it
-    if (n_words * 16 > (size_t)256 << 20)
+    if (n_words * 16 > kInfinityCacheBytes)
         hipLaunchKernelGGL(copy_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), reinterpret_cast<U64x2*>(d_dst),
                            reinterpret_cast<const U64x2*>(d_src), n_vec);
     else

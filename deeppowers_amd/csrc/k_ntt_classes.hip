@@ -11,7 +11,7 @@ int launch_ntt_classes(int log2n, bool inverse, u64* out, const u64* in, size_t 
     if (inverse) hipLaunchKernelGGL((ntt_classes_kernel<LN, LE, false>), dim3((unsigned)npolys), dim3(Geo<LN, LE>::T), 0, s, out, in, tb); \
     else if constexpr (LN == 8 || LN == 14) return 1;                                                                                    \
     else hipLaunchKernelGGL((ntt_classes_kernel<LN, LE, true>), dim3((unsigned)npolys), dim3(Geo<LN, LE>::T), 0, s, out, in, tb)
-    DPFHE_NTT_GEO_SWITCH(log2n, NC_CASE)
+    DPFHE_GEO_SWITCH(log2n, 14, NC_CASE)
 #undef NC_CASE
     return 0;
 }

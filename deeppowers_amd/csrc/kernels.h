@@ -478,7 +478,7 @@ template <class Arith, int LOGN, int LOGE, bool IN_NTT, bool OUT_NTT>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), (LOGE <= 3 && LOGN - LOGE <= 9) ? 4 : kCtMulOcc) void ct_mul_kernel(u64* __restrict__ out3, const u64* __restrict__ a2,
                                                                         const u64* __restrict__ b2, DevTables<Arith> tb) {
     typedef NttBody<Arith, LOGN, LOGE> B;
-    static_assert(LOGE == kFusedLoge, "the fused kernels read the fused twiddle layout (DevTables::fwd4 / inv4)");
+    static_assert(LOGE == kLoge, "the tables are laid out for 16 words per thread (devtables.h kLoge)");
     constexpr int E = B::E, N = B::G::N;
     __shared__ __attribute__((aligned(16))) u64 lds[(IN_NTT && OUT_NTT) ? 16 : B::G::lds_words()];
     int tid = threadIdx.x;
@@ -503,8 +503,8 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (LOGE <= 3 && LOGN - LOGE <= 9)
     // A loop of three rounds holding two inlined instances of F and one of I (44 KiB of code).  (A loop of seven single
     // steps with one instance each was 2.5 % slower: hipcc copied all three kept polynomials at every loop latch.)
     u64 S0[E], S1[E], S2[E];
-    const typename B::Tw* const twf = tb.fwd4 + (size_t)limb * N;
-    const typename B::Tw* const twi = tb.inv4 + (size_t)limb * N;
+    const typename B::Tw* const twf = tb.fwd + (size_t)limb * N;
+    const typename B::Tw* const twi = tb.inv + (size_t)limb * N;
     auto forward = [&](u64 (&x)[E], const u64* src, bool reduce_out, bool first) {
         if (IN_NTT) { B::load_bot(tid, x, src); return; }
         B::template load_top<true>(tid, x, src);   // streamed once: non-temporal
@@ -586,7 +586,7 @@ template <class Arith, int LOGN, int LOGE, bool OUT_NTT>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_dual_kernel(u64* __restrict__ out3, const u64* __restrict__ a2,
                                                                          const u64* __restrict__ b2, DevTables<Arith> tb) {
     typedef NttBody<Arith, LOGN, LOGE> B;
-    static_assert(LOGE == kFusedLoge, "the fused kernels read the fused twiddle layout (DevTables::fwd4 / inv4)");
+    static_assert(LOGE == kLoge, "the tables are laid out for 16 words per thread (devtables.h kLoge)");
     constexpr int E = B::E, N = B::G::N, W = B::G::lds_words();
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
     int tid = threadIdx.x;
@@ -606,8 +606,8 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_dual_kernel(u64*
     constexpr bool kScaledProducts = kLazy && Arith::kFoldCore && !Arith::kFold;   // FoldScaledArith: the products carry the scale twice
     const InvLast<typename B::Tw> last = kScaledProducts ? tb.last2[limb] : tb.last[limb];
     constexpr int kInvIn = kLazy ? B::kProdInvIn : kUnit;
-    const typename B::Tw* const twf = tb.fwd4 + (size_t)limb * N;
-    const typename B::Tw* const twi = tb.inv4 + (size_t)limb * N;
+    const typename B::Tw* const twf = tb.fwd + (size_t)limb * N;
+    const typename B::Tw* const twi = tb.inv + (size_t)limb * N;
 
     u64 D0[E], D1[E], D2[E];
 #pragma unroll 1
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
     // the pinned primes at N = 4096 (round 11): unreduced butterfly products on the twiddles split at bit 29 (NttBody LAZY29, DevTables::fwd29 / inv29 / last29)
     constexpr bool kLazy29 = Arith::kFold && LOGN == 12;
     typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, false, kLazy29> B;
-    static_assert(B::kLazyProducts && LOGE == kFusedLoge, "a policy with lazy products (ntt_core.h prod), fused twiddle layout");
+    static_assert(B::kLazyProducts && LOGE == kLoge, "a policy with lazy products (ntt_core.h prod), tables laid out for kLoge");
     typedef NttBody<Arith, LOGN, LOGE, 0, kUnit, true, kLazy29> BI;   // the inverse transforms' body: their input is the register-resident products
     constexpr bool kScaledProducts = Arith::kFoldCore && !Arith::kFold;   // FoldScaledArith: the products carry the scale twice
     constexpr int E = B::E, N = B::G::N, W = B::G::lds_words();
@@ -700,8 +700,8 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
     u64* dst = out3 + ((bi * 3) * L + limb) * N;
     const size_t cstride = L * N;
     const InvLast<typename B::Tw> last = kLazy29 ? tb.last29[limb] : kScaledProducts ? tb.last2[limb] : tb.last[limb];
-    const typename B::Tw* const tw_fwd = (kLazy29 ? tb.fwd29 : tb.fwd4) + (size_t)limb * N;
-    const typename B::Tw* const tw_inv = (kLazy29 ? tb.inv29 : tb.inv4) + (size_t)limb * N;
+    const typename B::Tw* const tw_fwd = (kLazy29 ? tb.fwd29 : tb.fwd) + (size_t)limb * N;
+    const typename B::Tw* const tw_inv = (kLazy29 ? tb.inv29 : tb.inv) + (size_t)limb * N;
     constexpr int kInvIn = B::kProdInvIn;
     // reductions per transform and thread (96 butterflies each), visible at compile time; a b-side forward transform adds prod_partner's 16
     static_assert(!kLazy29 || (B::template lazy_fwd_reductions<>() == 40 && BI::template lazy_inv_reductions<kInvIn>() == 55), "lazy plans of the N = 4096 geometry");
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void re
     // the digits are residues of ANOTHER limb: any word below 2^60.  FoldArith's forward transform takes them as they are (NttBody FWD_IN = kRedB: the first
     // stage's fused multiply-add reduces its addend for free - 7 instructions per word less than canonicalising first); generic primes canonicalise.
     typedef NttBody<Arith, LOGN, LOGE, 0, Arith::kFold ? kRedB : kUnit> B;
-    static_assert(LOGE == kFusedLoge, "the fused kernels read the fused twiddle layout (DevTables::fwd4 / inv4)");
+    static_assert(LOGE == kLoge, "the tables are laid out for 16 words per thread (devtables.h kLoge)");
     constexpr int E = B::E, N = B::G::N;
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     int tid = threadIdx.x;
@@ -858,7 +858,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void re
         }
         const u64 tr1 = trace_stamp<TRACE>(tr_dep);
         if (j > 0) lds_barrier();
-        FwdChain<B, 0>::template run<false>(tid, x, lds, tb.fwd4 + (size_t)limb * N, lc);
+        FwdChain<B, 0>::template run<false>(tid, x, lds, tb.fwd + (size_t)limb * N, lc);
         if constexpr (TRACE) {
             tr_dep = 0;
 #pragma unroll
@@ -968,7 +968,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void re
         u64 orig[E];
         if (add_back && kPrefetch) B::load_top(tid, orig, in3 + ((bi * kInComps + c) * L + limb) * N);
         if (c > 0) lds_barrier();   // the first inverse follows wave-local work only; the second follows an all-to-all read
-        InvChain<B, B::NPH - 1, kInvIn>::run(tid, x, lds, tb.inv4 + (size_t)limb * N, last, lc);
+        InvChain<B, B::NPH - 1, kInvIn>::run(tid, x, lds, tb.inv + (size_t)limb * N, last, lc);
         if (add_back && !kPrefetch) B::load_top(tid, orig, in3 + ((bi * kInComps + c) * L + limb) * N);
         B::inv_canon(x, lc);
         if (add_back) {
@@ -988,7 +988,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void relin_shared_kernel(u64
                                                                            const u64* __restrict__ evk, size_t key_stride, unsigned key_group,
                                                                            unsigned n_outer, DevTables<Arith> tb) {
     typedef NttBody<Arith, LOGN, LOGE, 0, kRedB> B;   // digits enter the forward transforms as they are (< 2^60): relin_kernel
-    static_assert(Arith::kFold && LOGE == kFusedLoge, "FoldArith, fused twiddle layout");
+    static_assert(Arith::kFold && LOGE == kLoge, "FoldArith, tables laid out for kLoge");
     constexpr int E = B::E, N = B::G::N, W = B::G::lds_words();
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
     int tid = threadIdx.x;
@@ -1021,7 +1021,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void relin_shared_kernel(u64
     const int Ld = kHybrid ? L - 1 : L;
     const u64* c2 = in3 + ((bi * kInComps + (kInComps - 1)) * Ld) * N;
     evk += (bi / key_group) * key_stride;
-    const typename B::Tw* const twf = tb.fwd4 + (size_t)limb * N;
+    const typename B::Tw* const twf = tb.fwd + (size_t)limb * N;
     static_assert(7 * kMulB + kRedB <= kWord, "seven lazily added products must fit a 64-bit word");
     u64 acc0[E], acc1[E];
     auto digit = [&](u64 (&x)[E], int j) { B::load_top(tid, x, c2 + (size_t)j * N); };   // [c]_{q_j}: reduced mod q_i by the transform's first stage
@@ -1069,7 +1069,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void relin_shared_kernel(u64
         return;
     }
     asm volatile("" : "+v"(tid));
-    InvChain2<B, B::NPH - 1, 2 * kMulB>::run(tid, acc0, acc1, lds, lds + W, tb.inv4 + (size_t)limb * N, last, lc);
+    InvChain2<B, B::NPH - 1, 2 * kMulB>::run(tid, acc0, acc1, lds, lds + W, tb.inv + (size_t)limb * N, last, lc);
     B::inv_canon(acc0, lc);
     if (MODE == 0 || MODE == 1) {
         u64 orig[E];
@@ -1104,7 +1104,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void ho
                                                                                            const u64* __restrict__ keys, size_t key_stride, GaloisElts elts,
                                                                                            unsigned n_items, unsigned n_tiles, DevTables<Arith> tb) {
     typedef NttBody<Arith, LOGN, LOGE> B;
-    static_assert(LOGE == kFusedLoge, "the fused kernels read the fused twiddle layout (DevTables::fwd4 / inv4)");
+    static_assert(LOGE == kLoge, "the tables are laid out for 16 words per thread (devtables.h kLoge)");
     constexpr int E = B::E, N = B::G::N;
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     int tid = threadIdx.x;
@@ -1165,7 +1165,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void ho
         for (int k = 0; k < E; ++k) { e[k] = en[k]; x[k] = xn[k]; }
     }
     constexpr int kInvIn = Arith::kFold ? kRedB : kUnit;
-    InvChain<B, B::NPH - 1, kInvIn>::run(tid, acc, lds, tb.inv4 + (size_t)limb * N, last, lc);
+    InvChain<B, B::NPH - 1, kInvIn>::run(tid, acc, lds, tb.inv + (size_t)limb * N, last, lc);
     B::inv_canon(acc, lc);
     B::store_top(tid, acc, work + ((item * 2 + comp) * L + limb) * N);
 }
@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void hoisted_ks2_kernel(u64*
                                                                            const u64* __restrict__ keys, size_t key_stride, GaloisElts elts,
                                                                            unsigned n_items, unsigned n_tiles, DevTables<Arith> tb) {
     typedef NttBody<Arith, LOGN, LOGE> B;
-    static_assert(Arith::kFold && LOGE == kFusedLoge, "FoldArith, fused twiddle layout");
+    static_assert(Arith::kFold && LOGE == kLoge, "FoldArith, tables laid out for kLoge");
     constexpr int E = B::E, N = B::G::N, W = B::G::lds_words();
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
     const int tid = threadIdx.x;
@@ -1231,7 +1231,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void hoisted_ks2_kernel(u64*
 #pragma unroll
         for (int k = 0; k < E; ++k) x[k] = xn[k];
     }
-    InvChain2<B, B::NPH - 1, kRedB>::run(tid, acc0, acc1, lds, lds + W, tb.inv4 + (size_t)limb * N, last, lc);
+    InvChain2<B, B::NPH - 1, kRedB>::run(tid, acc0, acc1, lds, lds + W, tb.inv + (size_t)limb * N, last, lc);
     B::inv_canon(acc0, lc);
     B::store_top(tid, acc0, work + ((item * 2 + 0) * L + limb) * N);
     B::inv_canon(acc1, lc);

@@ -96,6 +96,10 @@ __global__ __launch_bounds__(256) void copy_kernel(U64x2* __restrict__ dst, cons
     }
 }
 
+// The streaming kernels below take their work in 512-word chunks of a residue polynomial: 256 threads x one 16-byte pair (the `chunks` argument of each;
+// a thread owns words chunk * 512 + 2 tid and the next).  Rings below N = 512 have one partial chunk, whose upper threads idle.
+constexpr int chunks_of(size_t n) { return (int)((n + 511) / 512); }
+
 // ------------------------------------------------------------------------------------------------
 // A8: out[c][l][:] = sum_i in[i][c][l][:]  (HBM-bound: one read per term).
 // grid (residue-poly chunks, splits): each workgroup reduces its share of the batch to a canonical partial

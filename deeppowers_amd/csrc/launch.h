@@ -7,8 +7,10 @@
 
 namespace dpfhe {
 
-// (ntt_loge, kFusedLoge, kMaxLog2N, kSplitLog2N2, split_log_n1 - the constants that also shape the tables - are in devtables.h)
-constexpr int kMaxFusedLog2N = 13;
+// (kLoge, kMaxLog2N, kSplitLog2N2, split_log_n1 - the constants that also shape the tables - are in devtables.h)
+constexpr int kMaxFusedLog2N = 13;   // the fused kernels (multiply, key switching, hoisted rotations) stop at N = 8192: above, the C ABI composes the same operations from the batched transforms
+// MI355X's Infinity Cache: a launch whose streams together exceed it takes the non-temporal form of its kernel, where one exists
+constexpr size_t kInfinityCacheBytes = (size_t)256 << 20;
 // N = 8192 on the N = 4096 body ("halves": ntt_halves.h, kernels_halves.h - a register column stage + two 4096-point sub-transforms through one LDS
 // buffer, 256-thread workgroups, three to a CU).  Round 5, measured (profiles/r05_ntt13_batch_sweep.txt, r05_ntt_workgroup_timelines.txt, r05_halves_*.txt):
 //  * batched transforms: 2.5-9 % FASTER than the 512-thread kernels from 384 RNS polynomials (2304 workgroups) up - the 512-thread kernel keeps only 1.7 of

@@ -17,37 +17,29 @@ namespace dpfhe {
 // has 64 KiB: this library does not build for it, by design - no dual paths).  A padding change that breaks the budget fails here,
 // not at launch time.
 constexpr size_t kLdsBytesPerCu = 160 * 1024;
-static_assert(2 * sizeof(u64) * Geo<13, kFusedLoge>::lds_words() <= kLdsBytesPerCu, "two LDS images of an N = 8192 polynomial must fit one CU's 160 KiB");
+static_assert(2 * sizeof(u64) * Geo<13, kLoge>::lds_words() <= kLdsBytesPerCu, "two LDS images of an N = 8192 polynomial must fit one CU's 160 KiB");
 // ... and today they fill it to the byte (2 x 81 920 B = 163 840 B: ct_mul_dual_kernel / hoisted_ks2_kernel at N = 8192 leave NO room for another
 // __shared__ word or a wider wave stride).  Pinned on purpose: whoever changes Geo's padding sees the exact figure change here, not a launch failure.
-static_assert(2 * sizeof(u64) * Geo<13, kFusedLoge>::lds_words() == 163840 && 2 * sizeof(u64) * Geo<12, kFusedLoge>::lds_words() == 77824,
+static_assert(2 * sizeof(u64) * Geo<13, kLoge>::lds_words() == 163840 && 2 * sizeof(u64) * Geo<12, kLoge>::lds_words() == 77824,
               "LDS footprint of the paired fused kernels changed: re-check the 160 KiB budget at N = 8192 (zero margin) and two workgroups per CU at N = 4096");
 static_assert(sizeof(u64) * Geo<14, 4>::lds_words() <= kLdsBytesPerCu, "the N = 16384 transform's LDS image must fit one CU's 160 KiB");
 
-// (log2n -> LOGE) pairs proven by tests/test_emulated_kernels.py
-#define DPFHE_GEO_SWITCH(log2n, MACRO) \
-    switch (log2n) {                   \
-        case 8: MACRO(8, 4); break;    \
-        case 9: MACRO(9, 4); break;    \
-        case 10: MACRO(10, 4); break;  \
-        case 11: MACRO(11, 4); break;  \
-        case 12: MACRO(12, 4); break;  \
-        case 13: MACRO(13, 4); break;  \
-        default: return -1;            \
+// every ring degree from N = 256 up to 2^MAXLN (13: the fused kernels, 14: the transforms and the Galois inverse), each at kLoge words per thread -
+// the pairs proven by tests/test_emulated_kernels.py.  MACRO(LN, LE) may `break` out of the switch.
+#define DPFHE_GEO_SWITCH(log2n, MAXLN, MACRO) \
+    switch (log2n) {                          \
+        case 8: MACRO(8, kLoge); break;       \
+        case 9: MACRO(9, kLoge); break;       \
+        case 10: MACRO(10, kLoge); break;     \
+        case 11: MACRO(11, kLoge); break;     \
+        case 12: MACRO(12, kLoge); break;     \
+        case 13: MACRO(13, kLoge); break;     \
+        DPFHE_GEO_CASE14_##MAXLN(MACRO)       \
+        default: return -1;                   \
     }
-// the batched NTT kernels additionally cover N = 16384
-#define DPFHE_NTT_GEO_SWITCH(log2n, MACRO)  \
-    switch (log2n) {                        \
-        case 8: MACRO(8, 4); break;         \
-        case 9: MACRO(9, 4); break;         \
-        case 10: MACRO(10, 4); break;       \
-        case 11: MACRO(11, 4); break;       \
-        case 12: MACRO(12, 4); break;       \
-        case 13: MACRO(13, 4); break;       \
-        case 14: MACRO(14, 4); break;       \
-        default: return -1;                 \
-    }
-static_assert(ntt_loge(12) == 4 && ntt_loge(13) == 4 && ntt_loge(8) == 4 && ntt_loge(14) == 4, "devtables.h ntt_loge must match DPFHE_NTT_GEO_SWITCH");
+#define DPFHE_GEO_CASE14_13(MACRO)
+#define DPFHE_GEO_CASE14_14(MACRO) case 14: MACRO(14, kLoge); break;
+static_assert(kMaxFusedLog2N == 13 && split_log_n1(14) == 0 && split_log_n1(15) > 0, "DPFHE_GEO_SWITCH's two MAXLN: the fused kernels' limit (launch.h) and the largest single-kernel transform (devtables.h)");
 
 template <class Arith, int LOG_N1>
 static void launch_ntt_split(bool inverse, u64* out, const u64* in, size_t npolys, const DevTables<Arith>& tb, hipStream_t s) {
@@ -71,7 +63,7 @@ int launch_ntt(int log2n, bool inverse, u64* out, const u64* in, size_t npolys, 
     }
     // batches whose input + output cannot stay in the 256 MiB Infinity Cache stream around it (FoldArith, the two production ring degrees)
     const size_t touched = (npolys << log2n) * sizeof(u64) * (out == in ? 1 : 2);
-    const bool nt = Arith::kFold && (log2n == 12 || log2n == 13) && touched > ((size_t)256 << 20);
+    const bool nt = Arith::kFold && (log2n == 12 || log2n == 13) && touched > kInfinityCacheBytes;
 #ifdef DPFHE_DIAGNOSTICS   // the forward transform at N = 4096 / 8192 with per-workgroup timestamps (kernels_trace.h, tools/ntt_trace.py)
     if constexpr (Arith::kFold) {
         if (!inverse && (log2n == 12 || log2n == 13) && npolys <= 65536 && !tb.n_active) {
@@ -87,7 +79,7 @@ int launch_ntt(int log2n, bool inverse, u64* out, const u64* in, size_t npolys, 
     // N = 16384, FoldArith: 256-thread workgroups on the N = 4096 body, two to a CU (ntt_quarters.h)
     if constexpr (Arith::kFold) {
         if (log2n == 14 && tb.qfwd && !tb.n_active && npolys >= kQuartersMinPolys) {
-            const bool nt14 = touched > ((size_t)256 << 20);
+            const bool nt14 = touched > kInfinityCacheBytes;
             if (inverse) {
                 if (nt14) hipLaunchKernelGGL((ntt_inv_quarters_kernel<true>), dim3((unsigned)npolys), dim3(256), 0, s, out, in, tb);
                 else hipLaunchKernelGGL((ntt_inv_quarters_kernel<false>), dim3((unsigned)npolys), dim3(256), 0, s, out, in, tb);
@@ -121,7 +113,7 @@ int launch_ntt(int log2n, bool inverse, u64* out, const u64* in, size_t npolys, 
     }                                                                                                                                 \
     if (inverse) hipLaunchKernelGGL((ntt_inv_kernel<Arith, LN, LE>), dim3((unsigned)npolys), dim3(Geo<LN, LE>::T), 0, s, out, in, tb); \
     else hipLaunchKernelGGL((ntt_fwd_kernel<Arith, LN, LE>), dim3((unsigned)npolys), dim3(Geo<LN, LE>::T), 0, s, out, in, tb)
-    DPFHE_NTT_GEO_SWITCH(log2n, NTT_CASE)
+    DPFHE_GEO_SWITCH(log2n, 14, NTT_CASE)
 #undef NTT_CASE
     return 0;
 }
@@ -132,17 +124,17 @@ static int launch_ct_mul_dom(int log2n, u64* out3, const u64* a2, const u64* b2,
     // Coefficient domain in and out, N <= 4096: all four forward and all three inverse transforms share their twiddle fetches
     // (ct_mul_quad_kernel); N = 8192 or NTT-domain output: transforms in pairs (ct_mul_dual_kernel; at N = 8192 the quad form
     // measured equal to slightly slower: one 8-wave workgroup per CU, three barriers per all-to-all exchange - profiles/r03_ab_quad13.txt)
-    constexpr int kQuadMaxLogN = 12, kDualMaxLogN = 13;
+    constexpr int kQuadMaxLogN = 12;
 #define CT_CASE(LN, LE)                                                                                                                              \
     if constexpr (Arith::kFoldCore && !IN_NTT && !OUT_NTT && LN <= kQuadMaxLogN)   /* (F64Arith's quad form spills: pairs) */                                           \
-        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kFusedLoge>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
+        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kLoge>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
     else if constexpr (Arith::kFold && !IN_NTT && OUT_NTT && LN <= kQuadMaxLogN)   /* round 6: four shared forward transforms + the lazy tensor step, products left in the NTT domain */ \
-        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kFusedLoge, false, true>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
-    else if constexpr ((Arith::kFoldCore || Arith::kF64) && !IN_NTT && LN <= kDualMaxLogN)                                                                                                     \
-        hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, LN, kFusedLoge, OUT_NTT>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb); \
+        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kLoge, false, true>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
+    else if constexpr ((Arith::kFoldCore || Arith::kF64) && !IN_NTT)                                                                                                     \
+        hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, LN, kLoge, OUT_NTT>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb); \
     else                                                                                                                                             \
-        hipLaunchKernelGGL((ct_mul_kernel<Arith, LN, kFusedLoge, IN_NTT, OUT_NTT>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb)
-    DPFHE_GEO_SWITCH(log2n, CT_CASE)
+        hipLaunchKernelGGL((ct_mul_kernel<Arith, LN, kLoge, IN_NTT, OUT_NTT>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb)
+    DPFHE_GEO_SWITCH(log2n, 13, CT_CASE)
 #undef CT_CASE
     return 0;
 }
@@ -166,8 +158,8 @@ int launch_ct_mul_variant(int log2n, int variant, u64* out3, const u64* a2, cons
     else {
 #define CTV_CASE(LN)                                                                                                                                  \
     case LN:                                                                                                                                          \
-        if (variant == kCtMulQuad) hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kFusedLoge>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
-        else if (variant == kCtMulDual) hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, LN, kFusedLoge, false>), dim3((unsigned)blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, out3, a2, b2, tb); \
+        if (variant == kCtMulQuad) hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kLoge>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
+        else if (variant == kCtMulDual) hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, LN, kLoge, false>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb); \
         else return -1;                                                                                                                               \
         return 0
         switch (log2n) {
@@ -184,7 +176,7 @@ int launch_ct_mul_trace(int log2n, u64* out3, const u64* a2, const u64* b2, size
     if constexpr (!Arith::kFold) return -1;
     else {
         if (log2n != 12) return -1;
-        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, 12, kFusedLoge, true>), dim3((unsigned)blocks), dim3(Geo<12, kFusedLoge>::T), 0, s, out3, a2, b2, tb, trace);
+        hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, 12, kLoge, true>), dim3((unsigned)blocks), dim3(Geo<12, kLoge>::T), 0, s, out3, a2, b2, tb, trace);
         return 0;
     }
 }
@@ -219,7 +211,7 @@ int launch_relin(int log2n, int mode, u64* out2, const u64* in3, const u64* evk,
         if (log2n == 13 && mode == 4) {
             if (!g_relin_trace) { if (hipMalloc(&g_relin_trace, sizeof(u64) * 8 * 65536) != hipSuccess) return -1; }
             g_relin_trace_blocks = grid;
-            hipLaunchKernelGGL((relin_kernel<Arith, 13, kFusedLoge, 4, true>), dim3(grid), dim3(Geo<13, kFusedLoge>::T), 0, s, out2, in3, evk, key_stride, kg, n_outer, tb, g_relin_trace);
+            hipLaunchKernelGGL((relin_kernel<Arith, 13, kLoge, 4, true>), dim3(grid), dim3(Geo<13, kLoge>::T), 0, s, out2, in3, evk, key_stride, kg, n_outer, tb, g_relin_trace);
             return 0;
         }
     }
@@ -227,19 +219,19 @@ int launch_relin(int log2n, int mode, u64* out2, const u64* in3, const u64* evk,
 #define RL_ONE(LN, M)                                                                                                                                    \
     if constexpr (Arith::kFold && LN >= 10 && LN <= 12) {                                                                          \
         if (n_digits >= 4 && n_digits <= 7 && !tb.n_active) {                                                                                                            \
-            hipLaunchKernelGGL((relin_shared_kernel<Arith, LN, kFusedLoge, M>), dim3(grid), dim3(Geo<LN, kFusedLoge>::T), 0, s, out2, in3, evk,          \
+            hipLaunchKernelGGL((relin_shared_kernel<Arith, LN, kLoge, M>), dim3(grid), dim3(Geo<LN, kLoge>::T), 0, s, out2, in3, evk,          \
                                key_stride, kg, n_outer, tb);                                                                                             \
             break;                                                                                                                                       \
         }                                                                                                                                                \
     }                                                                                                                                                    \
-    hipLaunchKernelGGL((relin_kernel<Arith, LN, kFusedLoge, M>), dim3(grid), dim3(Geo<LN, kFusedLoge>::T), 0, s, out2, in3, evk, key_stride, kg, n_outer, tb)
+    hipLaunchKernelGGL((relin_kernel<Arith, LN, kLoge, M>), dim3(grid), dim3(Geo<LN, kLoge>::T), 0, s, out2, in3, evk, key_stride, kg, n_outer, tb)
 #define RL_CASE(LN, LE)                \
     if (mode == 0) { RL_ONE(LN, 0); }      \
     else if (mode == 1) { RL_ONE(LN, 1); } \
     else if (mode == 2) { RL_ONE(LN, 2); } \
     else if (mode == 3) { RL_ONE(LN, 3); } \
     else { RL_ONE(LN, 4); }
-    DPFHE_GEO_SWITCH(log2n, RL_CASE)
+    DPFHE_GEO_SWITCH(log2n, 13, RL_CASE)
 #undef RL_CASE
 #undef RL_ONE
     return 0;
@@ -263,13 +255,13 @@ int launch_hoisted_ks(int log2n, u64* work, const u64* digits, const u64* keys, 
 #define HK_CASE(LN, LE)                                                                                                                                  \
     if constexpr (Arith::kFold) {                                                                                                                        \
         if (merged) {                                                                                                                                    \
-            hipLaunchKernelGGL((hoisted_ks2_kernel<Arith, LN, kFusedLoge>), dim3(blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, work, digits, keys, key_stride, ge, \
+            hipLaunchKernelGGL((hoisted_ks2_kernel<Arith, LN, kLoge>), dim3(blocks), dim3(Geo<LN, kLoge>::T), 0, s, work, digits, keys, key_stride, ge, \
                                (unsigned)n_items, tiles, tb);                                                                                            \
             break;                                                                                                                                       \
         }                                                                                                                                                \
     }                                                                                                                                                    \
-    hipLaunchKernelGGL((hoisted_ks_kernel<Arith, LN, kFusedLoge>), dim3(blocks), dim3(Geo<LN, kFusedLoge>::T), 0, s, work, digits, keys, key_stride, ge, (unsigned)n_items, tiles, tb)
-    DPFHE_GEO_SWITCH(log2n, HK_CASE)
+    hipLaunchKernelGGL((hoisted_ks_kernel<Arith, LN, kLoge>), dim3(blocks), dim3(Geo<LN, kLoge>::T), 0, s, work, digits, keys, key_stride, ge, (unsigned)n_items, tiles, tb)
+    DPFHE_GEO_SWITCH(log2n, 13, HK_CASE)
 #undef HK_CASE
     return 0;
 }
@@ -284,7 +276,7 @@ int launch_ntt_inv_galois(int log2n, u64* out, const u64* in, const unsigned* el
     const unsigned grid = (unsigned)(n_elts * polys_per_elt);
 #define NG_CASE(LN, LE) \
     hipLaunchKernelGGL((ntt_inv_galois_kernel<Arith, LN, LE>), dim3(grid), dim3(Geo<LN, LE>::T), 0, s, out, in, ge, (unsigned)polys_per_elt, tb)
-    DPFHE_NTT_GEO_SWITCH(log2n, NG_CASE)
+    DPFHE_GEO_SWITCH(log2n, 14, NG_CASE)
 #undef NG_CASE
     return 0;
 }

@@ -449,7 +449,7 @@ extern "C" int emu_ntt(int arith, int log2n, int loge, int inverse, u64 q, u64 p
     return with_arith(arith, [&](auto a) {
         typedef decltype(a) Arith;
         Tables<Arith> t;
-        if (log2n >= 8 && log2n <= 14 && log2n != 9 && loge == ntt_loge(log2n)) {
+        if (log2n >= 8 && log2n <= 14 && log2n != 9 && loge == kLoge) {
             if (int rc = policy_tables<Arith>(log2n, q, psi, t)) return rc;
             return emu_launch_ntt<Arith>(log2n, t.tb, 0, inverse, in, out);
         }
@@ -485,7 +485,7 @@ extern "C" int emu_ntt_quarters(int inverse, u64 q, u64 psi, const u64* in, u64*
 extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* out) {
     Tables<FoldArith> t;
     if (int rc = policy_tables(log2n, q, psi, t)) return rc;
-#define CASE(LN) if (log2n == LN) { block_fwd<NttBody<FoldArith, LN, kFusedLoge, 0, kRedB>>(t.tb.fwd4, t.tb.lc[0], in, out); return 0; }
+#define CASE(LN) if (log2n == LN) { block_fwd<NttBody<FoldArith, LN, kLoge, 0, kRedB>>(t.tb.fwd, t.tb.lc[0], in, out); return 0; }
     CASE(8) CASE(10) CASE(12) CASE(13)
 #undef CASE
     return -1;
@@ -493,7 +493,7 @@ extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* 
 
 // ---- the fused multiply -------------------------------------------------------------------------------------------------
 // One limb's (c0, c1, c2) through the fused ct x ct kernels' data paths (coefficient domain in and out), with the same per-thread transform code and the
-// same dyadic sequence, on the context's fused-layout tables (DevTables::fwd4 / inv4).
+// same dyadic sequence, on the context's tables (DevTables::fwd / inv).
 //   LAZY (kernels.h ct_mul_quad_kernel / ct_mul_dual_kernel - the paired kernel computes the same values, two transforms at a time): lazy forward outputs,
 //     NttBody::tensor (fold policies turn b0, b1 into twiddles on the fly), the inverse of register-resident products - so the bound plans and the relaxed
 //     mul60 precondition (lazy forward outputs < 14 q times partially reduced b-side factors) are checked with the wrap-around / precondition counters armed;
@@ -502,8 +502,8 @@ extern "C" int emu_ntt_fwd_any60(int log2n, u64 q, u64 psi, const u64* in, u64* 
 //     build_lazy29_blob); out_ntt: the products as DPFHE_OUT_NTT stores them (canonical, forward-output order), no inverse transforms.
 template <class Arith, int LOGN, bool LAZY, bool LAZY29 = false>
 static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u64* b0, const u64* b1, u64* out3, bool out_ntt = false) {
-    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, false, LAZY29> B;
-    typedef NttBody<Arith, LOGN, kFusedLoge, 0, kUnit, LAZY, LAZY29> BI;
+    typedef NttBody<Arith, LOGN, kLoge, 0, kUnit, false, LAZY29> B;
+    typedef NttBody<Arith, LOGN, kLoge, 0, kUnit, LAZY, LAZY29> BI;
     Tables<Arith> t;
     if (int rc = policy_tables(LOGN, q, psi, t)) return rc;
     constexpr int T = B::T, N = B::G::N, limb = 0;
@@ -520,7 +520,7 @@ static int emu_ct_mul_path(u64 q, u64 psi, const u64* a0, const u64* a1, const u
         lazy29_view(t.tb, blob29.data(), lazy29_layout(1));
     }
     const InvLast<typename B::Tw> last = LAZY29 ? t.tb.last29[limb] : kScaledProducts ? t.tb.last2[limb] : t.tb.last[limb];
-    const typename B::Tw *twf = (LAZY29 ? t.tb.fwd29 : t.tb.fwd4) + (size_t)limb * N, *twi = (LAZY29 ? t.tb.inv29 : t.tb.inv4) + (size_t)limb * N;
+    const typename B::Tw *twf = (LAZY29 ? t.tb.fwd29 : t.tb.fwd) + (size_t)limb * N, *twi = (LAZY29 ? t.tb.inv29 : t.tb.inv) + (size_t)limb * N;
     std::vector<u64> lds(B::G::lds_words());
     auto fwd = [&](const u64* src, bool partner) {
         std::vector<u64> regs((size_t)T * B::E);
@@ -573,7 +573,7 @@ extern "C" u64 emu_fold_tw29(u64 d, u64 y, u64 w, u64 addend) {
 // The lazy plans of the N = 4096 geometry, one phase at a time (forward: phase p of the chain; inverse: phase p of the walk back, inputs below in_bound).
 // Forward rows [u][k]: red_a, K; inverse rows [u][k]: red, off.  tail[0 .. 16) = red_end, tail[16] = out_bound, tail[17] = n_red, tail[18 .. 34) = out (forward).
 extern "C" int emu_lazy29_plan(int inverse, int phase, int in_bound, int* flags, int* consts, int* tail) {
-    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, true, true> B;
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, true, true> B;
     if (phase < 0 || phase >= B::NPH) return 2000;
     const Phase ph = B::G::phase(phase);
     if (!inverse) {
@@ -591,8 +591,8 @@ extern "C" int emu_lazy29_plan(int inverse, int phase, int in_bound, int* flags,
 }
 // what the shipped body compiles in: reductions per transform and thread, forward and inverse, and the hand-over bounds the phases were planned with
 extern "C" void emu_lazy29_totals(int* out) {
-    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, false, true> B;
-    typedef NttBody<FoldArith, 12, kFusedLoge, 0, kUnit, true, true> BI;
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, false, true> B;
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, true, true> BI;
     out[0] = B::lazy_fwd_reductions<>(); out[1] = BI::lazy_inv_reductions<B::kProdInvIn>();
     out[2] = B::ctf29_plan<0>().out_bound; out[3] = B::ctf29_plan<1>().out_bound; out[4] = B::ctf29_plan<2>().out_bound;
     out[5] = kCtf29Mid; out[6] = kGs29Mid; out[7] = B::kProdInvIn;
