@@ -74,6 +74,11 @@ SYMBOLS = {
     "dpfhe_encoder_root": ([C.c_void_p], C.c_uint64),
     "dpfhe_encode_slots": ([C.c_void_p, _U64P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_encode_slots_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32], C.c_int),
+    "dpfhe_cencoder_create": ([C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
+    "dpfhe_cencoder_destroy": ([C.c_void_p], C.c_int),
+    "dpfhe_encode_complex": ([C.c_void_p, _U64P, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_void_p], C.c_int),
+    "dpfhe_encode_complex_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32], C.c_int),
+    "dpfhe_decode_complex_host": ([C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32], C.c_int),
     "dpfhe_sample_noise": ([C.c_void_p, _U64P, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32,
                             C.c_void_p], C.c_int),
     "dpfhe_sample_noise_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -85,6 +90,7 @@ SYMBOLS = {
 
 IN_NTT, OUT_NTT = 1, 2
 ENCODE_PLAIN, ENCODE_NTT = 1, 2   # dpfhe_encode_slots flags
+ENCODE_REAL = 4                   # dpfhe_encode_complex: real slots
 NOISE_TERNARY, NOISE_CBD21, NOISE_FLOOD = 0, 1, 2   # dpfhe_sample_noise kinds
 NOISE_ADD = 1   # dpfhe_sample_noise flag
 

@@ -1890,6 +1890,75 @@ uint32_t BatchEncoder::galois_element(int left_rotation) const {
     return (uint32_t)powmod(3, s, 2 * impl_->n);
 }
 
+// ---- complex slot encoding (include/dpfhe.h dpfhe_encode_complex) ---------------------------------------------------------------------
+class ComplexEncoder::Impl {
+public:
+    size_t n = 0;
+    uint32_t logn = 0;
+    // one device encoder per context this encoder has been asked to encode for, as BatchEncoder::Impl keeps them
+    struct DeviceEncoder { void* handle; std::vector<uint64_t> moduli; dpfhe_cencoder* enc; };
+    mutable std::mutex enc_mutex;
+    mutable std::vector<DeviceEncoder> encoders;
+    ~Impl() {
+        for (auto& e : encoders) (void)dpfhe_cencoder_destroy(e.enc);
+    }
+    dpfhe_cencoder* encoder_for(const Context& c) const {
+        if (c.params().n() != n) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplexEncoder::encode_device: the target's context has another ring degree");
+        std::lock_guard<std::mutex> lock(enc_mutex);
+        for (size_t i = 0; i < encoders.size(); ++i) {
+            if (encoders[i].handle != c.handle()) continue;
+            if (encoders[i].moduli == c.params().moduli) return encoders[i].enc;
+            (void)dpfhe_cencoder_destroy(encoders[i].enc);   // (frees its own tables only: the context it was bound to is gone)
+            encoders.erase(encoders.begin() + i);
+            break;
+        }
+        dpfhe_cencoder* e = nullptr;
+        check(dpfhe_cencoder_create(&e, static_cast<dpfhe_ctx*>(c.handle())), "dpfhe_cencoder_create");
+        encoders.push_back(DeviceEncoder{c.handle(), c.params().moduli, e});
+        return e;
+    }
+};
+
+ComplexEncoder::ComplexEncoder(const Context& ctx) : impl_(new Impl) {
+    impl_->n = ctx.params().n();
+    impl_->logn = (uint32_t)ctx.params().log2_n;
+}
+ComplexEncoder::~ComplexEncoder() = default;
+size_t ComplexEncoder::slot_count() const { return impl_->n / 2; }
+uint32_t ComplexEncoder::galois_element(int steps) const {
+    const long long row = (long long)impl_->n / 2;
+    const uint64_t s = (uint64_t)(((steps % row) + row) % row);
+    return (uint32_t)powmod(3, s, 2 * impl_->n);
+}
+uint32_t ComplexEncoder::conjugation_element() const { return (uint32_t)(2 * impl_->n - 1); }
+
+void ComplexEncoder::encode(const std::complex<double>* slots, double scale, int64_t* coeffs) const {
+    if (!slots || !coeffs) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplexEncoder::encode: null argument");
+    const size_t n = impl_->n;
+    std::vector<double> in(n);       // (staged: the entry takes 16-byte aligned buffers, the caller's need not be)
+    std::vector<uint64_t> out(n);
+    for (size_t i = 0; i < n / 2; ++i) { in[2 * i] = slots[i].real(); in[2 * i + 1] = slots[i].imag(); }
+    const uint64_t any_modulus = 3;  // (the plain form has no limbs)
+    check(dpfhe_encode_complex_host(&any_modulus, 1, impl_->logn, out.data(), in.data(), 1, scale, DPFHE_ENCODE_PLAIN), "dpfhe_encode_complex_host");
+    for (size_t k = 0; k < n; ++k) coeffs[k] = (int64_t)out[k];
+}
+void ComplexEncoder::decode(const int64_t* coeffs, double scale, std::complex<double>* slots) const {
+    if (!slots || !coeffs) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplexEncoder::decode: null argument");
+    const size_t n = impl_->n;
+    std::vector<double> out(n);
+    check(dpfhe_decode_complex_host(impl_->logn, out.data(), coeffs, 1, scale, 0), "dpfhe_decode_complex_host");
+    for (size_t i = 0; i < n / 2; ++i) slots[i] = std::complex<double>(out[2 * i], out[2 * i + 1]);
+}
+void ComplexEncoder::encode_device_words(const Context& ctx, const double* d_slots, size_t items, double scale, uint64_t* d_out, uint32_t flags, Stream* s) const {
+    if (!d_slots || !d_out || items == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplexEncoder::encode_device: null argument or no items");
+    check(dpfhe_encode_complex(impl_->encoder_for(ctx), d_out, d_slots, items, scale, flags, s), "dpfhe_encode_complex");
+}
+void ComplexEncoder::encode_device(const double* d_slots, size_t items, double scale, Plaintext& out, bool to_ntt, bool real, Stream* s) const {
+    if (out.batch() != items) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplexEncoder::encode_device: the plaintext must hold `items` polynomials");
+    encode_device_words(out.context(), d_slots, items, scale, out.data(), (to_ntt ? DPFHE_ENCODE_NTT : 0u) | (real ? DPFHE_ENCODE_REAL : 0u), s);
+    out.set_ntt(to_ntt);
+}
+
 // ---- N3: packed matrix-vector product (diagonal method, baby-step / giant-step) -------------------------------------------
 constexpr int kBabyShiftDefault = 1;
 

@@ -118,10 +118,21 @@ class Context:
             cache[int(t)] = h
         return cache[int(t)]
 
+    def complex_encoder(self):
+        """the device complex-slot encoder (include/dpfhe.h dpfhe_cencoder) of this context: created at first use (a set-up call: one allocation and
+        copy), kept until close()"""
+        if self.__dict__.get("_cencoder") is None:
+            h = C.c_void_p()
+            _cabi.check(self._lib.dpfhe_cencoder_create(C.byref(h), self._h), "dpfhe_cencoder_create")
+            self._cencoder = h
+        return self._cencoder
+
     def close(self):
         if getattr(self, "_h", None):
             for h in self.__dict__.pop("_encoders", {}).values():
                 self._lib.dpfhe_encoder_destroy(h)
+            if self.__dict__.get("_cencoder") is not None:
+                self._lib.dpfhe_cencoder_destroy(self.__dict__.pop("_cencoder"))
             self._lib.dpfhe_ctx_destroy(self._h)
             self._h = None
 
@@ -497,6 +508,26 @@ class Evaluator:
             out = torch.empty((slots.shape[0], p.n) if plain else (slots.shape[0], p.n_limbs, p.n), dtype=torch.int64, device=self.ctx.device)
         flags = _cabi.ENCODE_PLAIN if plain else (_cabi.ENCODE_NTT if to_ntt else 0)
         _cabi.check(self._lib.dpfhe_encode_slots(enc, out.data_ptr(), words.data_ptr(), slots.shape[0], flags, self._sp(stream)), "dpfhe_encode_slots")
+        return out
+
+    # ---- complex slot encoding on the device (include/dpfhe.h dpfhe_encode_complex) ----------------------------------------------------
+    def encode_complex(self, slots: torch.Tensor, scale: float, to_ntt: bool = False, plain: bool = False, stream=None) -> torch.Tensor:
+        """slots: contiguous [items][N/2] tensor on the context's device, complex128 or float64 (real slots) -> a new int64 tensor holding
+        round(scale m): [items][N] two's-complement coefficients (plain: what a client encrypts) or [items][L][N] residues (to_ntt: transformed, the
+        operand of multiply_plain).  The encoder is cached on the context; the operand never visits the host."""
+        p = self.ctx.params
+        if (slots.dim() != 2 or slots.shape[0] == 0 or slots.shape[1] != p.n // 2 or slots.device != self.ctx.device
+                or slots.dtype not in (torch.complex128, torch.float64)):
+            raise _cabi.DpfheError(2000, "encode_complex: a non-empty [items][N/2] complex128 or float64 tensor on the context's device")
+        if plain and to_ntt:
+            raise _cabi.DpfheError(2000, "encode_complex: the plain form has no transform")
+        enc = self.ctx.complex_encoder()
+        flags = (_cabi.ENCODE_PLAIN if plain else (_cabi.ENCODE_NTT if to_ntt else 0)) | (_cabi.ENCODE_REAL if slots.dtype == torch.float64 else 0)
+        with self._on(stream):
+            words = slots.contiguous()
+            out = torch.empty((slots.shape[0], p.n) if plain else (slots.shape[0], p.n_limbs, p.n), dtype=torch.int64, device=self.ctx.device)
+        _cabi.check(self._lib.dpfhe_encode_complex(enc, out.data_ptr(), words.data_ptr(), slots.shape[0], float(scale), flags, self._sp(stream)),
+                    "dpfhe_encode_complex")
         return out
 
     # ---- compact result ciphertexts (include/dpfhe.h dpfhe_compact) ------------------------------------------------------------------

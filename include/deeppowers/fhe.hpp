@@ -14,6 +14,7 @@
 // (/root/reference/src/core/execution/models/gpt_model.cpp:793,848,883) is Evaluator::matvec_plain.
 #pragma once
 
+#include <complex>
 #include <cstddef>
 #include <cstdint>
 #include <iosfwd>
@@ -571,6 +572,36 @@ public:
     // the building block of the above and of ExactPlaintext::set_slots_device: d_out on ctx's device, flags as for dpfhe_encode_slots; the same rule for
     // `stream` (device pointer: enqueue only; host pointer: synchronises `stream`)
     void encode_device_words(const Context& ctx, const uint32_t* slots, size_t items, uint64_t* d_out, uint32_t flags, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ComplexEncoder: N/2 complex (or real) slots of the approximate (CKKS-style) family (include/dpfhe.h "complex slot encoding").  Slot i is the value of
+// the real message polynomial m at xi^(3^i), xi = exp(i pi / N), and conj(z_i) its value at xi^(-3^i); the encoding is round(scale m).  X -> X^(3^s)
+// rotates the slots LEFT by s (cyclically over N/2), X -> X^(2N-1) conjugates them.  The scale is the caller's to track: a product of encodings at
+// scales a and b is an encoding at a b, and rescale divides it by the dropped prime.
+class ComplexEncoder {
+public:
+    explicit ComplexEncoder(const Context& ctx);
+    ~ComplexEncoder();
+    ComplexEncoder(const ComplexEncoder&) = delete;
+    ComplexEncoder& operator=(const ComplexEncoder&) = delete;
+    size_t slot_count() const;                        // N / 2
+    uint32_t galois_element(int steps) const;         // 3^steps mod 2N (negative steps rotate right)
+    uint32_t conjugation_element() const;             // 2N - 1
+    // host (client) side: N/2 slots -> the N centred coefficients Encryptor::encrypt(coeffs, 0, ct) takes, and back from what Decryptor::decrypt(ct, 0, out)
+    // returns; the accuracy bounds are the header's E and D
+    void encode(const std::complex<double>* slots, double scale, int64_t* coeffs) const;
+    void decode(const int64_t* coeffs, double scale, std::complex<double>* slots) const;
+    // Encoding ON THE DEVICE (include/dpfhe.h dpfhe_encode_complex): `items` vectors of N/2 (re, im) pairs, or of N/2 doubles when `real`, -> the `items`
+    // polynomials of `out`, word for word what encode() + a lift to every limb + an upload would give (to_ntt: transformed as well; out's domain flag is
+    // set either way).  `out` may belong to ANY context of the encoder's ring degree on the same device.  `d_slots` is a DEVICE pointer, 16-byte aligned:
+    // the call only enqueues on `stream`, no allocation, no synchronisation.  Thread-safe.
+    void encode_device(const double* d_slots, size_t items, double scale, Plaintext& out, bool to_ntt = false, bool real = false, Stream* stream = nullptr) const;
+    // the building block of the above: d_out on ctx's device, flags as for dpfhe_encode_complex
+    void encode_device_words(const Context& ctx, const double* d_slots, size_t items, double scale, uint64_t* d_out, uint32_t flags, Stream* stream = nullptr) const;
 
 private:
     class Impl;

@@ -374,6 +374,50 @@ int dpfhe_encode_slots(dpfhe_encoder* enc, uint64_t* d_out, const uint32_t* d_sl
 int dpfhe_encode_slots_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t t, uint64_t* out, const uint32_t* slots, size_t items,
                             uint32_t flags);
 
+/* -- complex slot encoding: vectors of real or complex numbers -> the integer polynomials of the approximate (CKKS-style) family, on the device.
+ * Definition.  N = 2^log2_n, n = N/2, xi = exp(i pi / N), a primitive 2N-th root of unity in C.  A vector of n complex slots z_0 .. z_(n-1) fixes the
+ *   real polynomial m of degree < N with
+ *       m(xi^(3^i)) = z_i,   m(xi^(-3^i)) = conj(z_i),   0 <= i < n, exponents mod 2N
+ *   (the slot generator is 3, as for Z_t; X -> X^(3^s) rotates the slots left by s, cyclically over n, and X -> X^(2N-1) conjugates them).  Its
+ *   coefficients are m_k = (2/N) Re( sum_i z_i xi^(-3^i k) ).  With a scale Delta (a positive finite double) the encoding is c_k = round(Delta m_k).
+ * Accuracy.  The transform is FP64 and cannot be pinned word for word by a formula; it is pinned by a bound and by an identity.
+ *   Bound: |c_k - Delta m_k| <= 1/2 + E,  E = 8 log2(N) 2^-53 Delta max_i |z_i|   (no intermediate overflowing or subnormal).
+ *   Derivation (u = 2^-53).  The schedule is log2(N) - 1 levels of radix-2 butterflies (a + b, (a - b) w) on n complex words, then one multiplication of
+ *   every word by Delta / n (a power-of-two fraction of Delta: exact).  Per level a word takes one complex addition (relative error u), and on one branch
+ *   one complex product of 4 multiplications and 2 additions (sqrt(8) u) with a twiddle whose components are correctly rounded (u / sqrt(2)): at most
+ *   g = (1 + sqrt(8) + 1/sqrt(2)) u < 4.54 u of its modulus.  The exact word after l levels is a sum of 2^l slots times unit factors, at most 2^l max|z|,
+ *   and reaches an output through 2^(levels - l) unit factors, so each level adds at most g n max|z| to an output before the scaling, g Delta max|z|
+ *   after it; the scaling adds u.  First order total (4.54 (log2(N) - 1) + 1) u Delta max|z|; the second-order terms are below 2^-40 of that.  8 holds.
+ *   Identity: the device gives the words of dpfhe_encode_complex_host, bit for bit: both run the same IEEE additions, multiplications and rint in the
+ *   same order (no fused multiply-add, no division, no sincos on the device) on one twiddle table built on the host.
+ * Conversion.  y_k is the double the transform gives for Delta m_k: NaN -> 0; otherwise clamped to [-2^62, 2^62], then rint (ties to even).  Values outside
+ *   that range (or non-finite slots) are a caller error with this defined result; the entry never faults on any input.
+ * Output forms (the DPFHE_ENCODE_* flags above, and):
+ *   default (flags 0):  [items][L][N], word [item][l][k] = c_k mod q_l in [0, q_l) for every limb of the context (|c_k| may exceed q_l).
+ *   DPFHE_ENCODE_PLAIN: [items][N], c_k as two's-complement 64-bit words - what a client hands to Encryptor::encrypt(coeffs, 0, ct).
+ *   DPFHE_ENCODE_NTT:   the residues, then the context's forward transform in place; invalid together with PLAIN.
+ *   DPFHE_ENCODE_REAL:  the input is [items][n] doubles (imaginary parts zero) instead of [items][n] (re, im) pairs.
+ * dpfhe_cencoder_create is a set-up call (one allocation, one copy: n twiddles, the slot -> position table, the limb constants).  The encoder is bound to
+ *   `ctx`, which must outlive it; it is immutable afterwards and may be shared between threads.  Destroying null is safe.
+ * dpfhe_encode_complex enqueues only (no allocation, no synchronise).  DPFHE_INVALID_ARGUMENT, with nothing written, on a null pointer, items 0, an unknown
+ *   flag bit, PLAIN with NTT, a buffer not 16-byte aligned, out overlapping slots, a scale that is not finite and positive, or more than (2^31 - 1) / N
+ *   items (one launch).  At log2_n >= 15 the transform is two kernels and parks its n intermediate complex words in row 0 of each item of d_out itself.
+ * dpfhe_encode_complex_host: the same words on the host (no device, no context; moduli odd, >= 3 and < 2^60, log2_n in [8, 16]); rejects the same, and
+ *   DPFHE_ENCODE_NTT as well.
+ * dpfhe_decode_complex_host: z_i = m(xi^(3^i)) / scale for centred integer coefficients c_k [items][N] (what Decryptor::decrypt(ct, 0, out) returns), as
+ *   [items][n] (re, im) pairs, or with DPFHE_ENCODE_REAL [items][n] real parts.  Bound: |z_i - exact| <= D = 8 log2(N) 2^-53 N max_k |c_k| / scale: the same
+ *   levels run forwards on words c_j + i c_(j+n) of modulus <= sqrt(2) max|c|, a word after l levels being a sum of 2^l of them, so each level adds at most
+ *   g sqrt(2) n max|c| = g N max|c| / sqrt(2); the conversion of |c_k| >= 2^53 and the division add u each.  DPFHE_INVALID_ARGUMENT on a null pointer,
+ *   items 0, an unknown flag, log2_n outside [8, 16], overlapping buffers or a scale that is not finite and positive. */
+typedef struct dpfhe_cencoder dpfhe_cencoder;
+enum { DPFHE_ENCODE_REAL = 4u };
+int dpfhe_cencoder_create(dpfhe_cencoder** out, dpfhe_ctx* ctx);
+int dpfhe_cencoder_destroy(dpfhe_cencoder* enc);
+int dpfhe_encode_complex(dpfhe_cencoder* enc, uint64_t* d_out, const double* d_slots, size_t items, double scale, uint32_t flags, void* stream);
+int dpfhe_encode_complex_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const double* slots, size_t items, double scale,
+                              uint32_t flags);
+int dpfhe_decode_complex_host(uint32_t log2_n, double* slots_out, const int64_t* coeffs, size_t items, double scale, uint32_t flags);
+
 /* -- re-randomised results: noise polynomials from a SECRET seed, and a fresh public-key encryption of zero with a flooding error added to result
  * ciphertexts before they leave the server (order: evaluate -> dpfhe_rerandomize -> dpfhe_compact).
  * Definition.  noise(seed, item, stream_id, kind, param) is a polynomial of N SIGNED INTEGERS v_k; every limb of the output holds the same integer as its

@@ -1,0 +1,165 @@
+"""-m gpu: complex slot encoding on the device (include/dpfhe.h dpfhe_encode_complex, csrc/k_cencode.hip).
+
+The kernels must give the host twin's words bit for bit (tests/test_complex_encode_cpu.py holds the host twin to the definition and to the header's
+bound) at every ring degree, from complex and from real slots, in the plain, residue and transformed forms and on every limb class, on vectors that
+hold a clamped value, a NaN, an Inf and a denormal-sized slot; inside tests/footprint.py's arena at 16-byte alignment under both fill patterns, at
+N = 256 and at the smallest two-kernel ring (N = 32768, where row 0 of each item parks the intermediate words).  The same arena cases run behind
+tests/stream_gate.py's gate on a non-blocking stream in tests/test_gpu_stream_contract_complex_encode.py, which sorts after the test that makes the
+process's gate.  Through the C++ facade (tests/cpp/test_complex_encode_api.cpp): ComplexEncoder::encode_device equals encode + lift + upload
+word for word, and a device-encoded operand multiplies, rotates and rescales correctly under encryption."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from deeppowers_amd import _cabi
+from deeppowers_amd.params import FheParams, min_primitive_2n_root, ntt_primes
+from complex_encode_ref import special_vectors, twin
+from test_plain_add_cpu import PARAMS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits(t):
+    """a complex128 / float64 / int64 device tensor as host uint64 words"""
+    import torch
+    return (torch.view_as_real(t) if t.is_complex() else t).contiguous().cpu().numpy().view(np.uint64).reshape(-1)
+
+
+def _device_vs_twin(p: FheParams, seed):
+    import torch
+    from deeppowers_amd.evaluator import Context, Evaluator, to_host
+    z = special_vectors(np.random.default_rng(seed), p.log2_n)
+    x = z.real + z.imag
+    ctx = Context(p, 0)
+    try:
+        ev = Evaluator(ctx)
+        d_z, d_x = torch.from_numpy(z).to(ctx.device), torch.from_numpy(x).to(ctx.device)
+        for scale in (2.0 ** 40, 2.0 ** 60):                # at 2^60 the constant vector 8.0 clamps and every |c_k| is far beyond 2^53
+            want_plain, want_res = twin(p.moduli, p.log2_n, z, scale, plain=True), twin(p.moduli, p.log2_n, z, scale)
+            got_plain = ev.encode_complex(d_z, scale, plain=True)
+            got_res = ev.encode_complex(d_z, scale)
+            got_ntt = ev.encode_complex(d_z, scale, to_ntt=True)
+            got_real = ev.encode_complex(d_x, scale)
+            got_real_plain = ev.encode_complex(d_x, scale, plain=True)
+            fwd = got_res.clone()
+            _cabi.check(ctx._lib.dpfhe_ntt_fwd(ctx.handle, fwd.data_ptr(), fwd.shape[0], None), "dpfhe_ntt_fwd")
+            torch.cuda.synchronize()
+            assert np.array_equal(got_plain.cpu().numpy(), want_plain), (p.log2_n, scale, "plain")
+            assert np.array_equal(to_host(got_res), want_res), (p.log2_n, scale, "residues")
+            assert torch.equal(got_ntt, fwd), (p.log2_n, scale, "ntt")
+            assert np.array_equal(to_host(got_real), twin(p.moduli, p.log2_n, x, scale)), (p.log2_n, scale, "real")
+            assert np.array_equal(got_real_plain.cpu().numpy(), twin(p.moduli, p.log2_n, x, scale, plain=True)), (p.log2_n, scale, "real, plain")
+            if scale == 2.0 ** 60:
+                assert int(want_plain[1, 0]) == 1 << 62 and not want_plain[1, 1:].any()
+        assert np.array_equal(_bits(d_z), z.view(np.uint64).reshape(-1)) and np.array_equal(_bits(d_x), x.view(np.uint64).reshape(-1))      # the inputs are untouched
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("log2n", range(8, 17))
+def test_device_matches_host_twin_every_ring_degree(log2n):
+    _device_vs_twin(ntt_primes(log2n, 3 if log2n <= 14 else 2, 60), seed=100 * log2n)
+
+
+@pytest.mark.parametrize("name", list(PARAMS) + ["config1", "limbs40", "below_t"])
+def test_device_matches_host_twin_limb_classes(name):
+    """PARAMS holds contexts at N = 256 and N = 4096: every limb class, 31-bit limbs, 40 limbs, and a pair of 13-bit limbs"""
+    if name == "below_t":
+        p = FheParams(8, (7681, 12289), (min_primitive_2n_root(256, 7681), min_primitive_2n_root(256, 12289)))
+    else:
+        p = {"config1": FheParams.config1, "limbs40": lambda: ntt_primes(10, 40, 31)}.get(name, PARAMS.get(name))()
+    _device_vs_twin(p, seed=7)
+
+
+# ---- footprint; tests/test_gpu_stream_contract_complex_encode.py runs the same cases behind the gate --------------------------------------------------------
+import test_gpu_footprint as fp  # noqa: E402
+
+rig = fp.rig
+
+
+@pytest.fixture
+def rig32k():
+    import test_gpu_large_ring_pipeline as lr
+    from class_edges import Rig
+    made = []
+
+    def make(kind, ln):
+        r = Rig(lr.params(kind, ln))
+        r.kind = f"{kind}{ln}"
+        made.append(r)
+        return r
+    yield make
+    for r in made:
+        r.close()
+
+
+ARENA_SHAPES = [(8, 1), (15, 2)]      # one kernel, one item; the smallest two-kernel ring, two items
+
+
+def arena_cases(r, log2n, items):
+    """every form through fp.Case: the output and the slots carved out of one arena at 16-byte (not 32-byte) alignment between guard bands; at N = 32768
+    row 0 of each item (parked words) is part of the declared output and nothing outside it may move"""
+    lib, n, L = r.ctx._lib, r.n, r.L
+    enc = r.ctx.complex_encoder()
+    z = special_vectors(np.random.default_rng(log2n), log2n)[[0, 2][:items]]
+    x = np.ascontiguousarray(z.real + z.imag)
+    scale = 2.0 ** 45
+    res = twin(r.p.moduli, log2n, z, scale)
+    forms = ((0, z, res, L * n), (_cabi.ENCODE_PLAIN, z, twin(r.p.moduli, log2n, z, scale, plain=True), n),
+             (_cabi.ENCODE_NTT, z, r.orc.ntt_fwd(res, threads=0), L * n), (_cabi.ENCODE_REAL, x, twin(r.p.moduli, log2n, x, scale), L * n),
+             (_cabi.ENCODE_REAL | _cabi.ENCODE_PLAIN, x, twin(r.p.moduli, log2n, x, scale, plain=True), n))
+    for flags, src, want, item in forms:
+        c = fp.Case(r)
+        c.inp("slots", np.ascontiguousarray(src).view(np.uint64).reshape(-1), src[0].nbytes // 8)
+        c.out("out", want.size, item, want.view(np.uint64))
+        c.run(f"dpfhe_encode_complex flags {flags}", lambda at: lib.dpfhe_encode_complex(enc, at("out"), at("slots"), items, scale, flags, at.stream))
+
+
+@pytest.mark.parametrize("log2n,items", ARENA_SHAPES)
+def test_footprint(rig, rig32k, log2n, items):
+    assert fp.Case.gate is None
+    arena_cases(rig("mixed", 8) if log2n == 8 else rig32k("fold", 15), log2n, items)
+
+
+def test_device_entry_rejects_bad_arguments():
+    import torch
+    from deeppowers_amd.evaluator import Context, Evaluator
+    p = FheParams.n4096_l4()
+    ctx = Context(p, 0)
+    try:
+        lib = ctx._lib
+        e = ctx.complex_encoder()
+        assert ctx.complex_encoder() is e
+        out = torch.zeros((2, p.n_limbs, p.n), dtype=torch.int64, device=ctx.device)
+        sl = torch.ones((2, p.n // 2), dtype=torch.complex128, device=ctx.device)
+        o, s, d = out.data_ptr(), sl.data_ptr(), 2.0 ** 40
+        for args in ((None, o, s, 2, d, 0), (e, None, s, 2, d, 0), (e, o, None, 2, d, 0), (e, o, s, 0, d, 0), (e, o, s, 2, d, 3), (e, o, s, 2, d, 8),
+                     (e, o, s, 2, d, 7), (e, o + 8, s, 2, d, 0), (e, o, s + 8, 2, d, 0), (e, o, o, 2, d, 0), (e, o, s, 1 << 20, d, 0), (e, o, s, 2, 0.0, 0),
+                     (e, o, s, 2, -d, 0), (e, o, s, 2, float("inf"), 0), (e, o, s, 2, float("nan"), 0)):
+            assert lib.dpfhe_encode_complex(*args, None) == 2000, args
+        torch.cuda.synchronize()
+        assert int(out.abs().sum()) == 0
+        ev = Evaluator(ctx)
+        for bad in (sl[:, :16].contiguous(), sl.to(torch.complex64), sl.real.to(torch.float32)):
+            with pytest.raises(_cabi.DpfheError):
+                ev.encode_complex(bad, d)
+        with pytest.raises(_cabi.DpfheError):
+            ev.encode_complex(sl, d, to_ntt=True, plain=True)
+    finally:
+        ctx.close()
+
+
+def test_cpp_complex_encode_facade(tmp_path):
+    exe = str(tmp_path / "test_complex_encode_api")
+    lib = os.path.join(ROOT, "deeppowers_amd")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
+                           os.path.join(ROOT, "tests", "cpp", "test_complex_encode_api.cpp"), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib",
+                           "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    print(out.stdout)
+    assert out.returncode == 0 and "complex encode C++ facade OK" in out.stdout, out.stdout + out.stderr
