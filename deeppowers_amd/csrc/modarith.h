@@ -34,8 +34,32 @@ typedef uint32_t u32;
 #if defined(DPFHE_EMU_CHECK) && !defined(__HIPCC__)
 extern long g_emu_overflows;
 #define DPFHE_EMU_ASSERT(cond) do { if (!(cond)) ++g_emu_overflows; } while (0)
+// ... and DPFHE_EMU_NOTE(site, residue, q): per product / reduce primitive (EmuSite), which of the nine remainder-edge values
+// T(q) = {0, 1, 2, q - 2, q - 1, h - 1, h, h + 1, h + 2}, h = (q - 1) / 2, the residue class of the returned word has taken (bit i of g_emu_notes[site]:
+// the i-th of them in that order).  `residue` is the word as returned - lazy, signed (a double) or scaled by s = 2^(60-k) modulo s q (FoldScaledArith's
+// transforms: q arrives even and s is its lowest set bit) - and is brought to [0, q) here.  The fold primitives that read only c.d note modulo 2^60 - d:
+// a scaled limb's words reach some of them with the true prime in c.q.  tests/test_remainder_edges_cpu.py reads the masks.
+enum EmuSite { kSiteShoupMulTw, kSiteShoupMulVar, kSiteFoldMul60, kSiteFoldMul60Full, kSiteFoldReduce, kSiteFoldMulTw, kSiteFoldMulTwAdd, kSiteFoldMulTw29Add,
+               kSiteFoldMulPtwAdd, kSiteFoldMulNinv, kSiteFoldCanonSmall, kSiteFoldMulVar, kSiteFoldDot30Fold, kSiteFoldDot30Fold0, kSiteFoldScaledMulVar,
+               kSiteF64Mulmod, kSiteF64Reduce, kSiteF64Canon, kSiteF64MulVar, kSiteF64WideMulmod, kSiteF64WideReduce, kSiteF64WideCanon, kSiteF64WideMulVar,
+               kEmuSiteCount };
+inline unsigned g_emu_notes[kEmuSiteCount] = {};   // (an inline variable: every emulator source that arms DPFHE_EMU_CHECK gets it without defining it)
+inline void emu_note(int site, uint64_t x, uint64_t q) {
+    const uint64_t s = q & (~q + 1);                       // 1 for a prime; the scaling factor of a scaled modulus
+    q /= s;
+    const uint64_t r = (x / s) % q, h = (q - 1) / 2;
+    const uint64_t t[9] = {0, 1, 2, q - 2, q - 1, h - 1, h, h + 1, h + 2};
+    g_emu_notes[site] |= 1u << 31;                         // the site was reached
+    for (int i = 0; i < 9; ++i) if (r == t[i]) g_emu_notes[site] |= 1u << i;
+}
+inline void emu_note(int site, double x, double q) {      // an integer-valued double, |x| < 2^53
+    const long long m = (long long)q, v = (long long)x % m;
+    emu_note(site, (uint64_t)(v < 0 ? v + m : v), (uint64_t)m);
+}
+#define DPFHE_EMU_NOTE(site, residue, q) emu_note(site, residue, q)
 #else
 #define DPFHE_EMU_ASSERT(cond) do { } while (0)
+#define DPFHE_EMU_NOTE(site, residue, q) do { } while (0)
 #endif
 
 struct LimbConst {  // one per RNS limb, read through scalar loads (limb index is workgroup-uniform)
@@ -110,7 +134,9 @@ struct ShoupArith {
     // w*y mod q, result in [0, 2q), for ANY y < 2^64 (w < q, wsh = floor(w 2^64/q))
     static DPF_HD u64 mul_tw(u64 y, const Tw& t, const LimbConst& c) {
         u64 hi = mulhi64(y, t.wsh);
-        return y * t.w - hi * c.q;
+        const u64 r = y * t.w - hi * c.q;
+        DPFHE_EMU_NOTE(kSiteShoupMulTw, r, c.q);
+        return r;
     }
     // a*b mod q, canonical, a,b < 2^64 with a*b < 2^124 (generic 128-bit Barrett, ratio = floor(2^128/q))
     static DPF_HD u64 mul_var(u64 a, u64 b, const LimbConst& c) {
@@ -124,8 +150,9 @@ struct ShoupArith {
         t2hi += (s2 < t2lo);
         u64 qhat = z1 * c.br_hi + t1hi + t2hi;
         u64 r = z0 - qhat * c.q;
-        r = csub(r, 2 * c.q);
-        return csub(r, c.q);
+        r = csub(csub(r, 2 * c.q), c.q);
+        DPFHE_EMU_NOTE(kSiteShoupMulVar, r, c.q);
+        return r;
     }
 };
 
@@ -158,7 +185,9 @@ struct FoldArith {
 #endif
         u64 n = mad32(y1, w0, m);
         u64 r = mad32(y1, w1, n >> 32);
-        return fold124((u32)p, (u32)n, r, d);
+        const u64 f = fold124((u32)p, (u32)n, r, d);
+        DPFHE_EMU_NOTE(kSiteFoldMul60, f, (1ull << 60) - d);
+        return f;
     }
     // same for ANY y < 2^64 (one extra carry add)
     static DPF_HD u64 mul60_full(u64 y, u64 w, u32 d) {
@@ -167,11 +196,15 @@ struct FoldArith {
         u64 m = mad32(y0, w1, p >> 32);
         u64 n = mad32(y1, w0, (u32)m);
         u64 r = mad32(y1, w1, (n >> 32) + (m >> 32));
-        return fold124((u32)p, (u32)n, r, d);
+        const u64 f = fold124((u32)p, (u32)n, r, d);
+        DPFHE_EMU_NOTE(kSiteFoldMul60Full, f, (1ull << 60) - d);
+        return f;
     }
     // any x < 2^64  ->  x mod q representative < 2^60 + 16 d
     static DPF_HD u64 reduce(u64 x, const LimbConst& c) {
-        return mad32((u32)(x >> 60), (u32)c.d, x & 0x0fffffffffffffffull);
+        const u64 r = mad32((u32)(x >> 60), (u32)c.d, x & 0x0fffffffffffffffull);
+        DPFHE_EMU_NOTE(kSiteFoldReduce, r, (1ull << 60) - c.d);
+        return r;
     }
     // y*w mod q for ANY 64-bit y; result < 2^60 + 13 d.
     //   y w  ==  y0 w + y1 (w 2^32 mod q)  =  L + H 2^30     with  L = y0 a + y1 a',  H = y0 b + y1 b'  (< 2^63)
@@ -188,8 +221,9 @@ struct FoldArith {
         asm("s_mov_b32 %0, 0x40000000" : "=s"(two30));  // opaque: hipcc would turn H.lo * 2^30 into shift + zero-extend + add
 #endif
         const u64 L = mad32(y1, as, mad32(y0, a, mad32((u32)H, two30, 0)));
-        const u64 R = mad32((u32)(H >> 32), 4 * (u32)c.d, L);
-        return reduce(R, c);
+        const u64 R = reduce(mad32((u32)(H >> 32), 4 * (u32)c.d, L), c);
+        DPFHE_EMU_NOTE(kSiteFoldMulTw, R, (1ull << 60) - c.d);
+        return R;
     }
     // addend + y*w mod q in ONE fold: the first multiply-add of mul_tw's chain has a free 64-bit addend, so the butterfly
     // sum x' = a + y w costs nothing beyond the product and comes out already reduced (< 2^60 + 16 d).
@@ -207,7 +241,9 @@ struct FoldArith {
 #endif
         const u64 L = mad32(y1, as, mad32(y0, a, mad32((u32)H, two30, addend)));
         const u64 R = mad32((u32)(H >> 32), 4 * (u32)c.d, L);
-        return reduce(R, c);
+        const u64 out = reduce(R, c);
+        DPFHE_EMU_NOTE(kSiteFoldMulTwAdd, out, (1ull << 60) - c.d);
+        return out;
     }
     // ---- the same twiddle split at bit 29: UNREDUCED products (round 11) ----------------------------------------------------------
     // Packing (tables.h h_tw_fold29; the type stays TwFold):  w = a + b 2^29,  w 2^32 mod q = a' + b' 2^29  with a, a' < 2^29 and b, b' < 2^31
@@ -230,7 +266,9 @@ struct FoldArith {
         asm("s_mov_b32 %0, 0x20000000" : "=s"(two29));  // opaque: H.lo * 2^29 + addend stays one v_mad_u64_u32 (as two30 in mul_tw)
 #endif
         const u64 L = mad32(y1, as, mad32(y0, a, mad32((u32)H, two29, addend)));
-        return mad32((u32)(H >> 32), 2 * (u32)c.d, L);
+        const u64 R = mad32((u32)(H >> 32), 2 * (u32)c.d, L);
+        DPFHE_EMU_NOTE(kSiteFoldMulTw29Add, R, (1ull << 60) - c.d);
+        return R;
     }
     static DPF_HD u64 mul_tw29(u64 y, const Tw& t, const LimbConst& c) { return mul_tw29_add(y, t, c, 0); }
     // (emulator only) the chain above in exact arithmetic: none of H, L, R leaves 64 bits
@@ -287,7 +325,9 @@ struct FoldArith {
 #endif
         const u64 L = mad32(y1, as, mad32(y0, a, mad32((u32)H, two30, addend)));
         const u64 R = mad32((u32)(H >> 32), 4 * (u32)c.d, L);
-        return reduce(R, c);
+        const u64 out = reduce(R, c);
+        DPFHE_EMU_NOTE(kSiteFoldMulPtwAdd, out, (1ull << 60) - c.d);
+        return out;
     }
     static DPF_HD u64 mul_ptw(u64 y, const Tw& t, const LimbConst& c) { return mul_ptw_add(y, t, c, 0); }
     // acc + x e mod q for a key word e < 2^60 + 2^29 (canonical) and ANY 64-bit x (a lazy forward output), acc < 2^62 - 2^58: 17 instructions, result
@@ -303,18 +343,26 @@ struct FoldArith {
         DPFHE_EMU_ASSERT((unsigned __int128)x + (unsigned __int128)m * c.d < ((unsigned __int128)1 << 64));
         const u64 t = mad32(m, (u32)c.d, x);
         const u32 vhi = (u32)(c.q >> 32) - (m << (28 - n));
-        return (t >> n) + (((u64)vhi << 32) | (u32)c.q);
+        const u64 y = (t >> n) + (((u64)vhi << 32) | (u32)c.q);
+        DPFHE_EMU_NOTE(kSiteFoldMulNinv, y, c.q);
+        return y;
     }
     // r < 2^60 + 2^59  ->  r mod q in [0, q), without compare/select: r >= q  <=>  r + d >= 2^60, and then
     // r - q = (r + d) - 2^60.  4 instructions (add, shift, multiply-add, and) against 5 for csub.
     static DPF_HD u64 canon_small(u64 r, const LimbConst& c) {
         DPFHE_EMU_ASSERT(r < (3ull << 59));
         const u32 k = (u32)((r + c.d) >> 60);
-        return mad32(k, (u32)c.d, r) & 0x0fffffffffffffffull;
+        const u64 y = mad32(k, (u32)c.d, r) & 0x0fffffffffffffffull;
+        DPFHE_EMU_NOTE(kSiteFoldCanonSmall, y, (1ull << 60) - c.d);
+        return y;
     }
     static DPF_HD u64 canon(u64 x, const LimbConst& c) { return canon_small(reduce(x, c), c); }
     // a*b mod q, canonical; a < 2^64, b < 2^60
-    static DPF_HD u64 mul_var(u64 a, u64 b, const LimbConst& c) { return csub(mul60(a, b, (u32)c.d), c.q); }
+    static DPF_HD u64 mul_var(u64 a, u64 b, const LimbConst& c) {
+        const u64 r = csub(mul60(a, b, (u32)c.d), c.q);
+        DPFHE_EMU_NOTE(kSiteFoldMulVar, r, c.q);
+        return r;
+    }
 
     // ---- lazy dot products of CANONICAL residues (the plaintext matrix-vector products, kernels_misc.h) -------------------
     // Both factors are split at bit 30 (a = a0 + a1 2^30, all four halves < 2^30), so every partial product is < 2^60 and
@@ -358,7 +406,9 @@ struct FoldArith {
         u64 A = mad32((u32)U, d, V);                                            // < 3 * 2^60 + 2^57
         A = mad32((u32)(T >> 28), d, A);                                        // + < 2^52
         A = add_hi32(A, (u32)T & 0x0fffffffu);                                  // + (T mod 2^28) 2^32 < 2^60: A < 2^63, no carry out of the high word
-        return reduce(A, c);
+        const u64 out = reduce(A, c);
+        DPFHE_EMU_NOTE(kSiteFoldDot30Fold, out, (1ull << 60) - c.d);
+        return out;
     }
     // the same without a running word and WITHOUT the reduction of S0 in front, for columns whose S0 is known to be small: S0 < 12 * 2^60 (a period that
     // started from a folded word < 2^60 + 16 d and added at most 8 products, or up to 11 products from zero).  Then
@@ -376,7 +426,9 @@ struct FoldArith {
         A = mad32((u32)U, d, A);
         A = mad32((u32)(T >> 28), d, A);
         A = add_hi32(A, (u32)T & 0x0fffffffu);
-        return reduce(A, c);
+        const u64 out = reduce(A, c);
+        DPFHE_EMU_NOTE(kSiteFoldDot30Fold0, out, (1ull << 60) - c.d);
+        return out;
     }
 };
 
@@ -401,7 +453,9 @@ struct FoldScaledArith {
     static DPF_HD u64 leave(u64 x, const LimbConst& c) { return x >> c.pad1; }                       // canonical mod q' (a multiple of s)  ->  x
     static DPF_HD u64 mul_var(u64 a, u64 b, const LimbConst& c) {                                    // canonical a, b < q
         const u64 r = FoldArith::mul60(a << c.pad1, b, (u32)c.d);                                    // s a b mod q', < q' + 2^53
-        return csub(r, c.q << c.pad1) >> c.pad1;
+        const u64 out = csub(r, c.q << c.pad1) >> c.pad1;
+        DPFHE_EMU_NOTE(kSiteFoldScaledMulVar, out, c.q);
+        return out;
     }
 };
 
@@ -433,6 +487,7 @@ struct F64ArithT {
     static constexpr int kMaxBits = MAXBITS;
     static_assert(MAXBITS >= 20 && MAXBITS <= 50, "the error-free product needs q + ulp(y w) / 2 < 2^53 and a quotient estimate within 1");
     static constexpr int kCap = 1 << (51 - MAXBITS);   // |y| < kCap q  =>  |y| < 2^51
+    static constexpr int kSiteOffset = MAXBITS == 47 ? 0 : 4;   // (DPFHE_EMU_NOTE: the wide instantiation's sites follow the 47-bit one's)
     static DPF_HD const LimbConst& ntt_lc(const LimbConst& c) { return c; }
     static DPF_HD double f(u64 x) { return __builtin_bit_cast(double, x); }
     static DPF_HD u64 b(double x) { return __builtin_bit_cast(u64, x); }
@@ -449,13 +504,21 @@ struct F64ArithT {
         const double e = __builtin_fma(y, w, -p);
         const double h = rint_mul(y, wq);
         const double r = __builtin_fma(-h, q, p);
-        return r + e;
+        const double t = r + e;
+        DPFHE_EMU_NOTE(kSiteF64Mulmod + kSiteOffset, t, q);
+        return t;
     }
     // any |x| < 2^52  ->  x mod q in [-q/2 - 1, q/2 + 1]
-    static DPF_HD double reduce(double x, double q, double qi) { return __builtin_fma(-rint_mul(x, qi), q, x); }
+    static DPF_HD double reduce(double x, double q, double qi) {
+        const double r = __builtin_fma(-rint_mul(x, qi), q, x);
+        DPFHE_EMU_NOTE(kSiteF64Reduce + kSiteOffset, r, q);
+        return r;
+    }
     static DPF_HD double canon(double x, double q, double qi) {
         const double r = reduce(x, q, qi);
-        return r < 0.0 ? r + q : r;
+        const double y = r < 0.0 ? r + q : r;
+        DPFHE_EMU_NOTE(kSiteF64Canon + kSiteOffset, y, q);
+        return y;
     }
     static DPF_HD u64 enter(u64 x, const LimbConst&) { return b(to_f(x)); }
     static DPF_HD u64 leave(u64 x, const LimbConst& c) { return from_f(canon(f(x), qd(c), qinv(c))); }
@@ -466,7 +529,9 @@ struct F64ArithT {
         const double e = __builtin_fma(x, y, -p);
         const double h = rint_mul(p, qi);               // p / q < 2^47: the estimate is within 2^-5 of the quotient
         const double r = __builtin_fma(-h, q, p) + e;   // in [-q/2 - 1, q/2 + 1]
-        return from_f(r < 0.0 ? r + q : r);
+        const double out = r < 0.0 ? r + q : r;
+        DPFHE_EMU_NOTE(kSiteF64MulVar + kSiteOffset, out, q);
+        return from_f(out);
     }
 };
 typedef F64ArithT<47> F64Arith;

@@ -268,13 +268,14 @@ def adversarial_key(orc, digits, seed):
     digits [nd][N]: the digit polynomials of that item (limb j of its last component, words below q_j); orc: the context the key lives on (L limbs).
     x[j][i] = NTT_i(digits[j] mod q_i) is what a key-switching kernel multiplies with key word [j][comp][i]; both components get
     e = (q_i - 1) x^-1 mod q_i, so x e = q_i - 1 in every word and the sum over the digits is the constant -nd mod q_i.  Where x = 0 the word stays random.
+    The special case "every target q - 1" of tests/remainder_edges.py key_for_targets.
     -> (key [nd][2][L][N], x [nd][L][N], the number of words with x = 0)"""
-    qcol = np.array(orc.moduli, np.uint64)[:, None]
-    x = orc.ntt_fwd(np.ascontiguousarray(digits[:, None, :] % qcol[None]), threads=0)
-    zero = x == 0
-    inv = inverse_words(orc, np.where(zero, np.uint64(1), x))
-    e = np.where(zero, orc.fill(x.shape[0], seed), orc.dyadic("negate", inv))
-    return np.ascontiguousarray(np.stack([e, e], axis=1)), x, int(zero.sum())
+    import remainder_edges as re_
+    x = re_.digit_transforms(orc, digits)
+    rnd = orc.fill(x.shape[0], seed)
+    tgt = re_.constant(orc, (x.shape[0], 2), lambda q: q - 1)
+    key, zero = re_.key_for_targets(orc, x, tgt, np.stack([rnd, rnd], axis=1))
+    return key, x, int(zero.sum())
 
 
 def reported_classes(p):

@@ -15,6 +15,12 @@
 namespace dpfhe { long g_emu_overflows = 0; }
 using namespace dpfhe;
 extern "C" long emu_overflows() { return g_emu_overflows; }
+// modarith.h DPFHE_EMU_NOTE: per site (EmuSite, in declaration order) bit i = the i-th remainder-edge value has been returned, bit 31 = the site was reached
+extern "C" void emu_notes_reset() { std::memset(g_emu_notes, 0, sizeof g_emu_notes); }
+extern "C" int emu_notes_get(unsigned* out, int cap) {
+    for (int i = 0; i < kEmuSiteCount && i < cap; ++i) out[i] = g_emu_notes[i];
+    return kEmuSiteCount;
+}
 
 // ---- the tables the emulated kernels read ----------------------------------------------------------------------------
 // Built by ctx_tables.h, the code dpfhe_ctx_create uploads from, and read through the same DevTables views with the kernels' own indexing
