@@ -1,6 +1,8 @@
 // devtables.h - device-side table handles passed to the kernels by value, and the constants that shape the tables.
 // No HIP: the host-side builder (ctx_tables.h) and tools/emulate.cpp read it as plain C++.
 #pragma once
+#include <stddef.h>
+
 #include "modarith.h"
 
 namespace dpfhe {
@@ -79,6 +81,31 @@ DPF_HD void block_item_limb(const TB& tb, size_t blk, size_t& item, int& limb) {
         item = blk / (unsigned)tb.n_limbs;
         limb = (int)(blk % (unsigned)tb.n_limbs);
     }
+}
+
+// limb number of index i among the limbs a launch works on (all limbs, or one class through its active_map): what a work map's limb index means
+template <class TB>
+DPF_HD int launch_limb(const TB& tb, unsigned i) {
+    return tb.n_active ? (int)((tb.active_map >> (4u * i)) & 15u) : (int)i;
+}
+
+// (polynomial, limb, sub-block) of a workgroup of the batched transforms: block p transforms words [p N, (p + 1) N) - one polynomial, or one of its n_sub
+// blocks (SUB = false: kernels that only run with n_sub = 1) -, or, in a launch over one arithmetic class (n_active; n_sub = 1), the class's limb of its item
+struct TransformBlock {
+    size_t p, sub;
+    int limb;
+};
+template <bool SUB = true, class TB>
+DPF_HD TransformBlock transform_block(const TB& tb, size_t blk) {
+    size_t p = blk;
+    const size_t sub = SUB ? p % (size_t)tb.n_sub : 0;
+    int limb = (int)((SUB ? p / (size_t)tb.n_sub : p) % (size_t)tb.n_limbs);
+    if (tb.n_active) {
+        size_t item;
+        block_item_limb(tb, blk, item, limb);
+        p = item * (size_t)tb.n_limbs + (size_t)limb;
+    }
+    return TransformBlock{p, sub, limb};
 }
 
 // the batched transforms' view of a context with per-limb arithmetic classes (kernels.h ntt_classes_kernel, ctx_tables.h mixed_layout)

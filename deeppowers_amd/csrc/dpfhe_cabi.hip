@@ -688,26 +688,27 @@ static int key_switch_composed_slice(dpfhe_ctx* c, uint64_t* d_out2, const uint6
 
 // Large batches go through in slices whose scratch stays below the context's scratch limit (the slices run back to back on the caller's stream and reuse
 // the pool's block): the scratch of a composed operation is 4 (multiply) or L^2 / 2 (key switch) times its input.
+// fn(first, count) over [0, total) in slices of at most `per` (scratch-limited slices; kMaxGaloisBatch elements per launch); stops at the first non-zero result
+template <class Fn>
+static int for_slices(size_t total, size_t per, Fn fn) {
+    for (size_t first = 0; first < total; first += per)
+        if (int rc = fn(first, total - first < per ? total - first : per)) return rc;
+    return DPFHE_SUCCESS;
+}
 static size_t slice_items(const dpfhe_ctx* c, size_t batch, size_t scratch_words_per_item) {   // 1 GiB of scratch unless dpfhe_ctx_set_scratch_limit said otherwise
     const size_t fit = c->scratch_limit_words.load(std::memory_order_relaxed) / scratch_words_per_item;
     return fit == 0 ? 1 : (fit < batch ? fit : batch);
 }
 static int ct_mul_composed(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch, uint32_t flags, hipStream_t s) {
     const size_t poly = (size_t)c->n_limbs << c->log2n, per = slice_items(c, batch, 4 * poly);
-    for (size_t i = 0; i < batch; i += per) {
-        const size_t m = batch - i < per ? batch - i : per;
-        if (int rc = ct_mul_composed_slice(c, d_out3 + i * 3 * poly, d_a2 + i * 2 * poly, d_b2 + i * 2 * poly, m, flags, s)) return rc;
-    }
-    return DPFHE_SUCCESS;
+    return for_slices(batch, per, [&](size_t i, size_t m) { return ct_mul_composed_slice(c, d_out3 + i * 3 * poly, d_a2 + i * 2 * poly, d_b2 + i * 2 * poly, m, flags, s); });
 }
 static int key_switch_composed(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in, int in_comps, int add_mask, const uint64_t* d_evk, size_t batch,
                                hipStream_t s, const char* what) {
     const size_t poly = (size_t)c->n_limbs << c->log2n, per = slice_items(c, batch, c->n_limbs * poly);
-    for (size_t i = 0; i < batch; i += per) {
-        const size_t m = batch - i < per ? batch - i : per;
-        if (int rc = key_switch_composed_slice(c, d_out2 + i * 2 * poly, d_in + i * (size_t)in_comps * poly, in_comps, add_mask, d_evk, m, s, what)) return rc;
-    }
-    return DPFHE_SUCCESS;
+    return for_slices(batch, per, [&](size_t i, size_t m) {
+        return key_switch_composed_slice(c, d_out2 + i * 2 * poly, d_in + i * (size_t)in_comps * poly, in_comps, add_mask, d_evk, m, s, what);
+    });
 }
 
 extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch,
@@ -833,8 +834,7 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
     const size_t L = c->n_limbs, Ld = L - 1;
     const int n = 1 << c->log2n, ch = chunks_of(n);
     const size_t per = slice_items(c, batch, Ld * L * (size_t)n);
-    for (size_t i0 = 0; i0 < batch; i0 += per) {
-        const size_t m = batch - i0 < per ? batch - i0 : per;
+    return for_slices(batch, per, [&](size_t i0, size_t m) -> int {
         const size_t lift_grid = m * Ld * L * (size_t)ch;
         if (lift_grid > kMaxGrid || !ntt_grid_fits(c, m * Ld * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch (lower the scratch limit)");
         StreamScratch ws(c, s);
@@ -848,9 +848,8 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
         with_ctx_arith(c, [&](auto arith) {
             hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3(grid), dim3(256), 0, s, o, ws.p, d_keys, c->lc, (int)Ld, (int)L, n, ch, key_stride, key_group, (unsigned)i0);
         });
-        if (int rc = check_launch("key inner product kernel launch")) return rc;
-    }
-    return DPFHE_SUCCESS;
+        return check_launch("key inner product kernel launch");
+    });
 }
 
 // hybrid key switching = inner product over all L limbs (relin_kernel MODE 2/3) + divide by the special prime and add (c0, c1)
@@ -869,9 +868,9 @@ static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* 
             return fail(DPFHE_INVALID_ARGUMENT, what, "output, input and work buffers must not overlap");
     }
     const size_t blocks = batch * L;
-    // the grouped launch pads the grid to whole XCD rounds (launch_impl.h launch_relin): ceil(blocks / group / 8) * 8 * group workgroups
-    const size_t kg = key_group ? key_group : 1, padded = ((blocks / kg + 7) / 8) * 8 * kg;
-    if (blocks > kMaxGrid || padded > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    // the grouped and key-major launches pad the grid to whole XCD rounds: the launcher's own plan (a launch per limb class is no larger)
+    const size_t kg = key_group ? key_group : 1;
+    if (blocks > kMaxGrid || RelinMap::plan(blocks, (unsigned)L, key_stride, key_group).grid > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "hybrid key switch");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int mode = in_comps == 3 ? 2 : 3;
@@ -939,15 +938,14 @@ static int rotate_batch_impl(dpfhe_ctx* c, const char* what, uint64_t* d_out2, c
     if (n_in == batch && overlaps(d_rotated, batch * ct_words, d_in2, batch * ct_words)) return fail(DPFHE_INVALID_ARGUMENT, what, "d_rotated overlaps the input");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DPFHE_ON_DEVICE(c, what);
-    for (size_t first = 0; first < batch; first += kMaxGaloisBatch) {   // the elements travel as kernel arguments, 64 at a time
-        const size_t cnt = batch - first < (size_t)kMaxGaloisBatch ? batch - first : (size_t)kMaxGaloisBatch;
+    const int rc = for_slices(batch, kMaxGaloisBatch, [&](size_t first, size_t cnt) {   // the elements travel as kernel arguments, 64 at a time
         GaloisInvs inv{};
         for (size_t i = 0; i < cnt; ++i) inv.v[i] = galois_inverse(galois_elts[(first + i) / group], two_n);
         const uint64_t* src = d_in2 + (n_in == 1 ? 0 : first * ct_words);
         launch_galois_multi(s, (unsigned)(cnt * 2 * Ld), d_rotated + first * ct_words, src, n_in == 1 ? (size_t)0 : ct_words, c->lc, (int)Ld, n, (int)(2 * Ld), inv, 0u, 0u);
-        int e = check_launch("galois kernel launch");
-        if (e) return e;
-    }
+        return check_launch("galois kernel launch");
+    });
+    if (rc) return rc;
     return hybrid_entry(c, what, 2, d_out2, d_rotated, d_keys, d_work, batch, stream, key_words, (unsigned)group);
 }
 
@@ -959,87 +957,6 @@ extern "C" int dpfhe_rotate_hybrid_batch(dpfhe_ctx* c, uint64_t* d_out2, const u
 extern "C" int dpfhe_rotate_hybrid_grouped(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, const uint32_t* galois_elts, size_t n_elts, size_t group,
                                            const uint64_t* d_keys, uint64_t* d_work, uint64_t* d_rotated, void* stream) {
     return rotate_batch_impl(c, "dpfhe_rotate_hybrid_grouped", d_out2, d_in2, n_elts * group, galois_elts, n_elts, group, d_keys, d_work, d_rotated, n_elts * group, stream);
-}
-
-static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
-                                  uint64_t* d_in_ntt, uint64_t* d_digits, size_t batch, void* stream, bool prepared);
-
-// N3, hoisted: `batch` rotations of ONE ciphertext; the digit decomposition of c1 and its Ld*L forward transforms are done once
-// (d_digits), every rotation is a permutation of those words in the NTT domain + its key inner product + two inverse transforms
-extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
-                                           uint64_t* d_work, uint64_t* d_rotated0, uint64_t* d_digits, size_t batch, void* stream) {
-    const char* what = "dpfhe_rotate_hybrid_hoisted";
-    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (int rc = check_extended(c, what)) return rc;
-    if (batch == 0 || n_items == 0) return DPFHE_SUCCESS;
-    const bool composed = c->log2n > kMaxFusedLog2N;   // N >= 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
-    if (!d_out2 || !d_in2 || !galois_elts || !d_keys || (!composed && (!d_work || !d_rotated0)) || !d_digits || misaligned(d_out2) || misaligned(d_in2) || misaligned(d_keys) ||
-        misaligned(d_work) || misaligned(d_rotated0) || misaligned(d_digits))
-        return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
-    const size_t L = c->n_limbs, Ld = L - 1, T = n_items, total = batch * T;
-    const int n = 1 << c->log2n;
-    const unsigned two_n = 2u << c->log2n;
-    if (int rc = check_galois_elts(c, galois_elts, batch, what)) return rc;
-    const size_t in_words = T * 2 * Ld * (size_t)n, out_words = total * 2 * Ld * n, work_words = d_work ? total * 2 * L * n : 0, rot_words = d_rotated0 ? total * Ld * n : 0,
-                 dig_words = T * Ld * L * (size_t)n;
-    if (overlaps(d_out2, out_words, d_in2, in_words) || overlaps(d_out2, out_words, d_work, work_words) || overlaps(d_out2, out_words, d_rotated0, rot_words) ||
-        overlaps(d_work, work_words, d_rotated0, rot_words) || overlaps(d_digits, dig_words, d_work, work_words) || overlaps(d_digits, dig_words, d_out2, out_words) ||
-        overlaps(d_digits, dig_words, d_rotated0, rot_words) || overlaps(d_digits, dig_words, d_in2, in_words) || overlaps(d_rotated0, rot_words, d_in2, in_words))
-        return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
-    const size_t key_words = Ld * 2 * L * (size_t)n;
-    const int chunks = chunks_of(n);
-    if (composed) {
-        DPFHE_ON_DEVICE(c, what);
-        // N >= 16384 (round 5; N = 32768, 65536 on the split transforms): no fused hoisted kernel - the deferred-division pipeline instead: dpfhe_rotate_hoisted_qp gives, per rotation and item,
-        // P sigma_g(ct) + its key-switching term in the NTT domain over Q P; one inverse transform and the division by P per term finish it (the same words:
-        // tests/test_rlwe_semantics.py).  Scratch (the Q P terms + the transformed inputs) from the stream's arena, rotations in slices under the scratch limit;
-        // d_work / d_rotated0 are not used on this path.
-        const size_t item_qp = T * 2 * L * (size_t)n, fit = c->scratch_limit_words.load(std::memory_order_relaxed) / item_qp;
-        const size_t per = fit > 2 ? (fit - 2 < batch ? fit - 2 : batch) : 1;     // (+ block 0 and the transformed inputs)
-        if (per * T * 2 * Ld * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, per * T * 2 * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch (lower the scratch limit)");
-        StreamScratch ws(c, static_cast<hipStream_t>(stream));       // one arena for every slice: the transformed inputs and digits are prepared by the first slice only
-        if (int rc = ws.alloc((per + 1) * item_qp + in_words, what)) return rc;
-        u64* qp = ws.p;
-        u64* in_ntt = qp + (per + 1) * item_qp;
-        for (size_t r0 = 0; r0 < batch; r0 += per) {
-            const size_t m = batch - r0 < per ? batch - r0 : per;
-            if (int rc = rotate_hoisted_qp_impl(c, qp, d_in2, T, galois_elts + r0, d_keys + r0 * key_words, in_ntt, d_digits, m, stream, r0 != 0)) return rc;
-            hipStream_t s = static_cast<hipStream_t>(stream);
-            if (int rc = ntt_launch(c, true, qp + item_qp, qp + item_qp, m * T * 2 * L, s)) return rc;
-            launch_rescale(c, m * T * 2 * Ld * (size_t)chunks, s, d_out2 + r0 * T * 2 * Ld * n, qp + item_qp, nullptr, 0, 0);
-            if (int rc = check_launch("hoisted rescale launch")) return rc;
-        }
-        return DPFHE_SUCCESS;
-    }
-    // (the key-switch launch pads its (rotation, limb[, component]) tiles to a multiple of 8 per token: launch_impl.h launch_hoisted_ks)
-    if (total * 2 * Ld * (size_t)chunks > kMaxGrid || (total * L * 2 + 8 * T) > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid)
-        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DPFHE_ON_DEVICE(c, what);
-    // 1. digits of every item's c1, lifted to every limb, then transformed (T * Ld RNS polynomials on the extended context)
-    launch_lift_digits(c, T * Ld * L * (size_t)chunks, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, chunks);
-    if (int e = check_launch("lift_digits kernel launch")) return e;
-    if (int e = ntt_launch_items(c, false, d_digits, d_digits, T * Ld, 0, s)) return e;   // (per limb class where the context has them)
-    // 2. sigma_g(c0) of every (rotation, item) for the final addition: [batch][T][Ld][N]; 64 output items per launch
-    for (size_t first = 0; first < total; first += kMaxGaloisBatch) {
-        const size_t cnt = total - first < (size_t)kMaxGaloisBatch ? total - first : (size_t)kMaxGaloisBatch;
-        GaloisInvs inv{};
-        for (size_t i = 0; i < cnt; ++i) inv.v[i] = galois_inverse(galois_elts[(first + i) / T], two_n);
-        launch_galois_multi(s, (unsigned)(cnt * Ld), d_rotated0 + first * Ld * n, d_in2, 2 * Ld * (size_t)n, c->lc, (int)Ld, n, (int)Ld, inv, (unsigned)T, (unsigned)(first % T));
-        if (int e = check_launch("galois kernel launch")) return e;
-    }
-    // 3. permuted digits (.) keys, one inverse transform per (rotation, limb, key component, item); 64 rotations per launch
-    for (size_t first = 0; first < batch; first += kMaxGaloisBatch) {
-        const size_t cnt = batch - first < (size_t)kMaxGaloisBatch ? batch - first : (size_t)kMaxGaloisBatch;
-        const int rc = with_policy_or_classes(c, [&](const auto& tb) {
-            return launch_hoisted_ks((int)c->log2n, d_work + first * T * 2 * L * n, d_digits, d_keys + first * key_words, key_words, galois_elts + first, cnt, T, tb, s);
-        });
-        if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel geometry for this log2_n");
-        if (int e = check_launch("hoisted key-switch kernel launch")) return e;
-    }
-    // 4. divide by P with rounding; component 0 gets sigma_g(c0) added ([total][1][Ld][N] addend)
-    launch_rescale(c, total * 2 * Ld * (size_t)chunks, s, d_out2, d_work, d_rotated0, 1, 1);
-    return check_launch("hoisted rescale launch");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1083,38 +1000,109 @@ static int rotate_hoisted_qp_impl(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64
         if (int e = check_launch("lift_qp kernel launch")) return e;
     }
     // 4. the rotations: permuted digit segments x key segments as a stream (kernels_misc.h hoisted_qp_stream_kernel), 64 rotations per launch
-    for (size_t first = 0; first < batch; first += kMaxGaloisBatch) {
-        const size_t cnt = batch - first < (size_t)kMaxGaloisBatch ? batch - first : (size_t)kMaxGaloisBatch;
+    return for_slices(batch, kMaxGaloisBatch, [&](size_t first, size_t cnt) -> int {
         uint64_t* dst = d_out_qp + (1 + first) * T * 2 * L * n;
         {
             QpElts ge{};
             for (size_t i = 0; i < cnt; ++i) ge.v[i] = galois_elts[first + i];
             // (pairs per thread: 2 measured best at 8 tokens - 291 us against 300 with 1 and 329 with 4 -, 1 is 5 % ahead at one token: profiles/r04_ab_baby_steps.txt)
             if (c->fold && Ld >= 1 && Ld <= 6) {   // every segment of the workgroup requested up front (one pair of words per thread)
-                const size_t grid1 = qp_stream_grid((int)c->log2n, (int)L, cnt, T, 1);
+                const size_t grid1 = QpMap::grid((int)c->log2n, (int)L, cnt, T, 1);
                 if (grid1 > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
 #define QPU(LD) case LD: hipLaunchKernelGGL((hoisted_qp_upfront_kernel<LD>), dim3((unsigned)grid1), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge, \
                                             (unsigned)cnt, (unsigned)T, p_special, c->lc, (int)c->log2n); break
                 switch (Ld) { QPU(1); QPU(2); QPU(3); QPU(4); QPU(5); QPU(6); }
 #undef QPU
-                if (int e = check_launch("hoisted_qp kernel launch")) return e;
-                continue;
+                return check_launch("hoisted_qp kernel launch");
             }
-            const size_t grid = qp_stream_grid((int)c->log2n, (int)L, cnt, T);
+            const size_t grid = QpMap::grid((int)c->log2n, (int)L, cnt, T);
             if (grid > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
             with_ctx_arith(c, [&](auto arith) {
                 hipLaunchKernelGGL((hoisted_qp_stream_kernel<decltype(arith), kQpPairs>), dim3((unsigned)grid), dim3(256), 0, s, dst, d_digits, d_in_ntt, d_keys + first * key_words, key_words, ge,
                                    (unsigned)cnt, (unsigned)T, p_special, c->lc, (int)L, (int)c->log2n);
             });
         }
-        if (int e = check_launch("hoisted_qp kernel launch")) return e;
-    }
-    return DPFHE_SUCCESS;
+        return check_launch("hoisted_qp kernel launch");
+    });
 }
 
 extern "C" int dpfhe_rotate_hoisted_qp(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
                                        uint64_t* d_in_ntt, uint64_t* d_digits, size_t batch, void* stream) {
     return rotate_hoisted_qp_impl(c, d_out_qp, d_in2, n_items, galois_elts, d_keys, d_in_ntt, d_digits, batch, stream, false);
+}
+
+// N3, hoisted: `batch` rotations of ONE ciphertext; the digit decomposition of c1 and its Ld*L forward transforms are done once
+// (d_digits), every rotation is a permutation of those words in the NTT domain + its key inner product + two inverse transforms
+extern "C" int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
+                                           uint64_t* d_work, uint64_t* d_rotated0, uint64_t* d_digits, size_t batch, void* stream) {
+    const char* what = "dpfhe_rotate_hybrid_hoisted";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (int rc = check_extended(c, what)) return rc;
+    if (batch == 0 || n_items == 0) return DPFHE_SUCCESS;
+    const bool composed = c->log2n > kMaxFusedLog2N;   // N >= 16384: the deferred-division pipeline below never touches d_work / d_rotated0 - they may be NULL
+    if (!d_out2 || !d_in2 || !galois_elts || !d_keys || (!composed && (!d_work || !d_rotated0)) || !d_digits || misaligned(d_out2) || misaligned(d_in2) || misaligned(d_keys) ||
+        misaligned(d_work) || misaligned(d_rotated0) || misaligned(d_digits))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    const size_t L = c->n_limbs, Ld = L - 1, T = n_items, total = batch * T;
+    const int n = 1 << c->log2n;
+    const unsigned two_n = 2u << c->log2n;
+    if (int rc = check_galois_elts(c, galois_elts, batch, what)) return rc;
+    const size_t in_words = T * 2 * Ld * (size_t)n, out_words = total * 2 * Ld * n, work_words = d_work ? total * 2 * L * n : 0, rot_words = d_rotated0 ? total * Ld * n : 0,
+                 dig_words = T * Ld * L * (size_t)n;
+    if (overlaps(d_out2, out_words, d_in2, in_words) || overlaps(d_out2, out_words, d_work, work_words) || overlaps(d_out2, out_words, d_rotated0, rot_words) ||
+        overlaps(d_work, work_words, d_rotated0, rot_words) || overlaps(d_digits, dig_words, d_work, work_words) || overlaps(d_digits, dig_words, d_out2, out_words) ||
+        overlaps(d_digits, dig_words, d_rotated0, rot_words) || overlaps(d_digits, dig_words, d_in2, in_words) || overlaps(d_rotated0, rot_words, d_in2, in_words))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
+    const size_t key_words = Ld * 2 * L * (size_t)n;
+    const int chunks = chunks_of(n);
+    if (composed) {
+        DPFHE_ON_DEVICE(c, what);
+        // N >= 16384 (round 5; N = 32768, 65536 on the split transforms): no fused hoisted kernel - the deferred-division pipeline instead: dpfhe_rotate_hoisted_qp gives, per rotation and item,
+        // P sigma_g(ct) + its key-switching term in the NTT domain over Q P; one inverse transform and the division by P per term finish it (the same words:
+        // tests/test_rlwe_semantics.py).  Scratch (the Q P terms + the transformed inputs) from the stream's arena, rotations in slices under the scratch limit;
+        // d_work / d_rotated0 are not used on this path.
+        const size_t item_qp = T * 2 * L * (size_t)n, fit = c->scratch_limit_words.load(std::memory_order_relaxed) / item_qp;
+        const size_t per = fit > 2 ? (fit - 2 < batch ? fit - 2 : batch) : 1;     // (+ block 0 and the transformed inputs)
+        if (per * T * 2 * Ld * (size_t)chunks > kMaxGrid || !ntt_grid_fits(c, per * T * 2 * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch (lower the scratch limit)");
+        StreamScratch ws(c, static_cast<hipStream_t>(stream));       // one arena for every slice: the transformed inputs and digits are prepared by the first slice only
+        if (int rc = ws.alloc((per + 1) * item_qp + in_words, what)) return rc;
+        u64* qp = ws.p;
+        u64* in_ntt = qp + (per + 1) * item_qp;
+        return for_slices(batch, per, [&](size_t r0, size_t m) -> int {
+            if (int rc = rotate_hoisted_qp_impl(c, qp, d_in2, T, galois_elts + r0, d_keys + r0 * key_words, in_ntt, d_digits, m, stream, r0 != 0)) return rc;
+            hipStream_t s = static_cast<hipStream_t>(stream);
+            if (int rc = ntt_launch(c, true, qp + item_qp, qp + item_qp, m * T * 2 * L, s)) return rc;
+            launch_rescale(c, m * T * 2 * Ld * (size_t)chunks, s, d_out2 + r0 * T * 2 * Ld * n, qp + item_qp, nullptr, 0, 0);
+            return check_launch("hoisted rescale launch");
+        });
+    }
+    // (the key-switch launch pads its (rotation, limb[, component]) tiles to a multiple of 8 per token: launch_impl.h launch_hoisted_ks)
+    if (total * 2 * Ld * (size_t)chunks > kMaxGrid || (total * L * 2 + 8 * T) > kMaxGrid || T * Ld * L * (size_t)chunks > kMaxGrid)
+        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DPFHE_ON_DEVICE(c, what);
+    // 1. digits of every item's c1, lifted to every limb, then transformed (T * Ld RNS polynomials on the extended context)
+    launch_lift_digits(c, T * Ld * L * (size_t)chunks, s, d_digits, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, chunks);
+    if (int e = check_launch("lift_digits kernel launch")) return e;
+    if (int e = ntt_launch_items(c, false, d_digits, d_digits, T * Ld, 0, s)) return e;   // (per limb class where the context has them)
+    // 2. sigma_g(c0) of every (rotation, item) for the final addition: [batch][T][Ld][N]; 64 output items per launch
+    if (int e = for_slices(total, kMaxGaloisBatch, [&](size_t first, size_t cnt) {
+        GaloisInvs inv{};
+        for (size_t i = 0; i < cnt; ++i) inv.v[i] = galois_inverse(galois_elts[(first + i) / T], two_n);
+        launch_galois_multi(s, (unsigned)(cnt * Ld), d_rotated0 + first * Ld * n, d_in2, 2 * Ld * (size_t)n, c->lc, (int)Ld, n, (int)Ld, inv, (unsigned)T, (unsigned)(first % T));
+        return check_launch("galois kernel launch");
+    })) return e;
+    // 3. permuted digits (.) keys, one inverse transform per (rotation, limb, key component, item); 64 rotations per launch
+    if (int e = for_slices(batch, kMaxGaloisBatch, [&](size_t first, size_t cnt) -> int {
+        const int rc = with_policy_or_classes(c, [&](const auto& tb) {
+            return launch_hoisted_ks((int)c->log2n, d_work + first * T * 2 * L * n, d_digits, d_keys + first * key_words, key_words, galois_elts + first, cnt, T, tb, s);
+        });
+        if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel geometry for this log2_n");
+        return check_launch("hoisted key-switch kernel launch");
+    })) return e;
+    // 4. divide by P with rounding; component 0 gets sigma_g(c0) added ([total][1][Ld][N] addend)
+    launch_rescale(c, total * 2 * Ld * (size_t)chunks, s, d_out2, d_work, d_rotated0, 1, 1);
+    return check_launch("hoisted rescale launch");
 }
 
 extern "C" int dpfhe_ntt_inv_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t rns_polys_per_elt, const uint32_t* galois_elts, size_t n_elts, void* stream) {
@@ -1135,25 +1123,21 @@ extern "C" int dpfhe_ntt_inv_galois(dpfhe_ctx* c, uint64_t* d_out, const uint64_
     if (split) {
         StreamScratch ws(c, s);
         if (d_out == d_in) if (int rc = ws.alloc((n_elts < group ? n_elts : group) * per_elt << c->log2n, what)) return rc;
-        for (size_t first = 0; first < n_elts; first += group) {
-            const size_t cnt = n_elts - first < group ? n_elts - first : group;
+        return for_slices(n_elts, group, [&](size_t first, size_t cnt) -> int {
             const size_t off = first * per_elt << c->log2n;
             u64* mid = d_out == d_in ? ws.p : d_out + off;
             const int rc = c->fold ? launch_ntt_inv_galois_split((int)c->log2n, d_out + off, mid, d_in + off, galois_elts + first, cnt, per_elt, c->foldt, s)
                                    : launch_ntt_inv_galois_split((int)c->log2n, d_out + off, mid, d_in + off, galois_elts + first, cnt, per_elt, c->shoup, s);
             if (rc) return fail(DPFHE_INVALID_STATE, what, "no split transform for this context");
-            if (int e = check_launch("ntt_inv_galois kernel launch")) return e;
-        }
-        return DPFHE_SUCCESS;
+            return check_launch("ntt_inv_galois kernel launch");
+        });
     }
-    for (size_t first = 0; first < n_elts; first += kMaxGaloisBatch) {
-        const size_t cnt = n_elts - first < (size_t)kMaxGaloisBatch ? n_elts - first : (size_t)kMaxGaloisBatch;
+    return for_slices(n_elts, kMaxGaloisBatch, [&](size_t first, size_t cnt) -> int {
         const size_t off = first * per_elt << c->log2n;
         const int rc = with_policy_or_classes(c, [&](const auto& tb) { return launch_ntt_inv_galois((int)c->log2n, d_out + off, d_in + off, galois_elts + first, cnt, per_elt, tb, s); });
         if (rc) return fail(DPFHE_INVALID_STATE, what, "no single-kernel transform for this log2_n");
-        if (int e = check_launch("ntt_inv_galois kernel launch")) return e;
-    }
-    return DPFHE_SUCCESS;
+        return check_launch("ntt_inv_galois kernel launch");
+    });
 }
 
 extern "C" int dpfhe_switch_key_qp(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_t* d_in2, const uint64_t* d_keys, size_t n_keys, size_t group, void* stream) {
@@ -1167,10 +1151,10 @@ extern "C" int dpfhe_switch_key_qp(dpfhe_ctx* c, uint64_t* d_out_qp, const uint6
     const int n = 1 << c->log2n;
     if (overlaps(d_out_qp, batch * 2 * L * n, d_in2, batch * 2 * Ld * n)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps the input");
     const size_t blocks = batch * L;
-    if ((blocks / 8 + 1) * 8 + 8 * group > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    const size_t key_words = Ld * 2 * L * (size_t)n;
+    if (blocks > kMaxGrid || RelinMap::plan(blocks, (unsigned)L, key_words, (unsigned)group).grid > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t key_words = Ld * 2 * L * (size_t)n;
     if (c->log2n > kMaxFusedLog2N)   // composed from the batched transform (round 5): the digits of c1, lifted and transformed, times the group's key
         return key_products_composed(c, d_out_qp, d_in2 + Ld * (size_t)n, 2 * Ld * (size_t)n, d_keys, key_words, (unsigned)group, batch, s, what);
     const int rc = relin_launch(c, 4, d_out_qp, d_in2, d_keys, key_words, (unsigned)group, blocks, s);
@@ -1233,7 +1217,7 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
         constexpr int WPT = kMatvecWpt2;
         const int chunks = (n + 256 * WPT - 1) / (256 * WPT);
         const size_t slabs = c->n_limbs * (size_t)chunks, rtiles = (rows + RT - 1) / RT;
-        const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles;
+        const size_t blocks = MatvecMap::grid(c->n_limbs, chunks, rtiles, 1);
         if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_plain", "too many rows for one launch");
         // a W beyond the 256 MiB Infinity Cache is a read-once stream (every tile goes to exactly one workgroup here): non-temporal loads
         const bool ntw = rows * cols * ((size_t)c->n_limbs << c->log2n) * sizeof(u64) > kInfinityCacheBytes;
@@ -1246,8 +1230,7 @@ extern "C" int dpfhe_matvec_plain(dpfhe_ctx* c, uint64_t* d_y, const uint64_t* d
         return check_launch("matvec kernel launch");
     }
     const int chunks = chunks_of(n);
-    const size_t slabs = c->n_limbs * (size_t)chunks;
-    const size_t blocks = ((slabs + 7) / 8) * 8 * ((rows + RT - 1) / RT);   // block ids laid out per XCD: kernels_misc.h matvec_kernel
+    const size_t blocks = MatvecMap::grid(c->n_limbs, chunks, (rows + RT - 1) / RT, 1);   // block ids laid out per XCD: kernels_misc.h matvec_kernel
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_matvec_plain", "too many rows for one launch");
     hipLaunchKernelGGL((matvec_kernel<ShoupArith, RT>), dim3((unsigned)blocks), dim3(256), 0, s, d_y, d_W, d_x, c->lc, (int)c->n_limbs, n, chunks, rows, cols);
     return check_launch("matvec kernel launch");
@@ -1261,7 +1244,7 @@ static int matvec_multi_launch(const dpfhe_ctx* c, const char* what, u64* ys, co
                                hipStream_t s) {
     const int n = 1 << c->log2n, chunks = (n + 256 * WPT - 1) / (256 * WPT);
     const size_t slabs = c->n_limbs * (size_t)chunks, rtiles = (rows + RT - 1) / RT, tiles = rtiles * slabs;
-    const size_t blocks = ((slabs + 7) / 8) * 8 * rtiles * groups;
+    const size_t blocks = MatvecMap::grid(c->n_limbs, chunks, rtiles, groups);
     if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "too many rows for one launch");
     if constexpr (!FOLD)
         hipLaunchKernelGGL((matvec_multi_kernel<ShoupArith, RT, C>), dim3((unsigned)blocks), dim3(256), 0, s, ys, d_W, xs, c->lc, (int)c->n_limbs, n, chunks, rows, cols,

@@ -10,6 +10,7 @@
 #include "launch.h"
 #include "ntt_core.h"
 #include "ntt_top.h"
+#include "workmap.h"
 
 namespace dpfhe {
 
@@ -274,14 +275,9 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_fwd_kernel(u64* __rest
     typedef NttBody<Arith, LOGN, LOGE> B;
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     const int tid = threadIdx.x;
-    size_t p = blockIdx.x;                   // block p transforms words [p N, (p + 1) N): one polynomial, or one of its n_sub blocks
-    const size_t sub = p % (size_t)tb.n_sub;
-    int limb = (int)((p / (size_t)tb.n_sub) % (size_t)tb.n_limbs);
-    if (tb.n_active) {                       // a launch over one arithmetic class of the context's limbs (devtables.h; n_sub = 1)
-        size_t item;
-        block_item_limb(tb, blockIdx.x, item, limb);
-        p = item * (size_t)tb.n_limbs + (size_t)limb;
-    }
+    const TransformBlock blk = transform_block(tb, blockIdx.x);
+    const size_t p = blk.p, sub = blk.sub;
+    const int limb = blk.limb;
     const LimbConst lc = tb.lc[limb];
     const typename B::Tw* tw = tb.fwd + ((size_t)limb * tb.n_sub + sub) * B::G::N;
     u64 x[B::E];
@@ -298,14 +294,9 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_kernel(u64* __rest
     typedef NttBody<Arith, LOGN, LOGE> B;
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     const int tid = threadIdx.x;
-    size_t p = blockIdx.x;
-    const size_t sub = p % (size_t)tb.n_sub;
-    int limb = (int)((p / (size_t)tb.n_sub) % (size_t)tb.n_limbs);
-    if (tb.n_active) {
-        size_t item;
-        block_item_limb(tb, blockIdx.x, item, limb);
-        p = item * (size_t)tb.n_limbs + (size_t)limb;
-    }
+    const TransformBlock blk = transform_block(tb, blockIdx.x);
+    const size_t p = blk.p, sub = blk.sub;
+    const int limb = blk.limb;
     const LimbConst lc = tb.lc[limb];
     const typename B::Tw* tw = tb.inv + ((size_t)limb * tb.n_sub + sub) * B::G::N;
     const InvLast<typename B::Tw> last = tb.last[(size_t)limb * tb.n_sub + sub];
@@ -398,13 +389,9 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_galois_kernel(u64*
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     const int tid = threadIdx.x;
     // (a launch over one class of a mixed context: blockIdx.x counts (polynomial, class limb) pairs; polys_per_elt is then per class too)
-    size_t p = blockIdx.x;
-    int limb = (int)(p % (size_t)tb.n_limbs);
-    if (tb.n_active) {
-        size_t item;
-        block_item_limb(tb, blockIdx.x, item, limb);
-        p = item * (size_t)tb.n_limbs + (size_t)limb;
-    }
+    const TransformBlock blk = transform_block<false>(tb, blockIdx.x);   // (single-kernel transforms only: n_sub = 1)
+    const size_t p = blk.p;
+    const int limb = blk.limb;
     const unsigned g = elts.v[blockIdx.x / polys_per_elt];
     const LimbConst lc = tb.lc[limb];
     const typename B::Tw* tw = tb.inv + (size_t)limb * N;
@@ -421,12 +408,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_galois_kernel(u64*
         B::stage_gather(tid, x, v, lds, addr);
     } else {
 #pragma unroll
-        for (int kk = 0; kk < E; ++kk) {
-            const unsigned pos = (unsigned)tid * E + kk;
-            const unsigned e = 2u * (__brev(pos) >> (32 - LOGN)) + 1u;
-            const unsigned e2 = (g * e) & (2u * N - 1u);
-            x[kk] = src[__brev((e2 - 1u) >> 1) >> (32 - LOGN)];
-        }
+        for (int kk = 0; kk < E; ++kk) x[kk] = src[galois_src_pos<LOGN>(g, (unsigned)tid * E + kk)];
     }
     if constexpr (B::G::T <= 64) __syncthreads();   // single-wave geometries have no barrier inside the transform
     InvChain<B, B::NPH - 1, kUnit>::run_with(tid, x, lds, tw, last, lc, tw_first);
@@ -772,7 +754,6 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
 // multiply-accumulate with the two key polynomials (NTT domain, L2-resident: 2 L^2 N words in total); then two inverse
 // NTTs, add c0_i / c1_i, store.  L + 2 transforms per workgroup; HBM: L + 2 reads and 2 writes of a residue polynomial.
 // ------------------------------------------------------------------------------------------------
-constexpr unsigned kRelinRotMajor = 0x80000000u;   // flag in relin_kernel's n_outer: key-major workgroup ids (launch_impl.h launch_relin)
 template <class Arith>
 __device__ __forceinline__ u64 canon_any(u64 v, const LimbConst& lc) {  // any v < 2^64 -> [0, q)
     if (Arith::kFold) return FoldArith::canon(v, lc);
@@ -801,31 +782,13 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void re
     __shared__ __attribute__((aligned(16))) u64 lds[B::G::lds_words()];
     int tid = threadIdx.x;
     const int L = tb.n_limbs;
-    size_t bi;
-    int limb;
-    // La = the limbs THIS launch works on: all of them, or one arithmetic class of a mixed context (devtables.h n_active / active_map; `limb` below is then
-    // an index into the class and is mapped to the limb's number in the context right after)
+    // La = the limbs THIS launch works on: all of them, or one arithmetic class of a mixed context (devtables.h n_active / active_map; the map's limb
+    // index is then an index into the class and is mapped to the limb's number in the context right after)
     const unsigned La = tb.n_active ? (unsigned)tb.n_active : (unsigned)L;
-    if (n_outer & kRelinRotMajor) {
-        // round 4: ALL workgroups of a key (L limbs x key_group items) on ONE XCD, limb-major: the items' digits (read by every limb's
-        // workgroup) and the key tiles (read by every item's workgroup) both come from HBM once - the layout below fetched the digits L times
-        const unsigned n_keys = (n_outer & ~kRelinRotMajor) / La, per_key = La * key_group;
-        const unsigned q = blockIdx.x >> 3, w = q % per_key, key = (q / per_key) * 8u + (blockIdx.x & 7u);
-        if (key >= n_keys) return;
-        limb = (int)(w / key_group);
-        bi = (size_t)key * key_group + w % key_group;
-    } else if (n_outer) {
-        // `key_group` consecutive items share a key (the giant steps of several tokens): their workgroups for one limb get ids that are
-        // equal modulo 8 and adjacent above that, i.e. the same XCD at the same time - the key tiles come from HBM once per group
-        const unsigned q = blockIdx.x >> 3, inner = q % key_group, outer = (q / key_group) * 8u + (blockIdx.x & 7u);
-        if (outer >= n_outer) return;
-        limb = (int)(outer % La);
-        bi = (size_t)(outer / La) * key_group + inner;
-    } else {
-        bi = blockIdx.x / La;
-        limb = (int)(blockIdx.x % La);
-    }
-    if (tb.n_active) limb = (int)((tb.active_map >> (4u * (unsigned)limb)) & 15u);
+    const RelinWork wk = RelinMap::decode(blockIdx.x, n_outer, key_group, La);   // plain, grouped or key-major ids (workmap.h)
+    if (!wk.live) return;
+    const size_t bi = wk.item;
+    const int limb = launch_limb(tb, (unsigned)wk.limb_index);
     const LimbConst lc = tb.lc[limb];
     const InvLast<typename B::Tw> last = tb.last[limb];
     constexpr int kInComps = (MODE == 0 || MODE == 2) ? 3 : 2;
@@ -993,27 +956,10 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void relin_shared_kernel(u64
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
     int tid = threadIdx.x;
     const int L = tb.n_limbs;
-    size_t bi;
-    int limb;
-    if (n_outer & kRelinRotMajor) {
-        // round 4: ALL workgroups of a key (L limbs x key_group items) on ONE XCD, limb-major: the items' digits (read by every limb's
-        // workgroup) and the key tiles (read by every item's workgroup) both come from HBM once - the layout below fetched the digits L times
-        const unsigned n_keys = (n_outer & ~kRelinRotMajor) / (unsigned)L, per_key = (unsigned)L * key_group;
-        const unsigned q = blockIdx.x >> 3, w = q % per_key, key = (q / per_key) * 8u + (blockIdx.x & 7u);
-        if (key >= n_keys) return;
-        limb = (int)(w / key_group);
-        bi = (size_t)key * key_group + w % key_group;
-    } else if (n_outer) {
-        // `key_group` consecutive items share a key (the giant steps of several tokens): their workgroups for one limb get ids that are
-        // equal modulo 8 and adjacent above that, i.e. the same XCD at the same time - the key tiles come from HBM once per group
-        const unsigned q = blockIdx.x >> 3, inner = q % key_group, outer = (q / key_group) * 8u + (blockIdx.x & 7u);
-        if (outer >= n_outer) return;
-        limb = (int)(outer % (unsigned)L);
-        bi = (size_t)(outer / (unsigned)L) * key_group + inner;
-    } else {
-        bi = blockIdx.x / (unsigned)L;
-        limb = (int)(blockIdx.x % (unsigned)L);
-    }
+    const RelinWork wk = RelinMap::decode(blockIdx.x, n_outer, key_group, (unsigned)L);   // plain, grouped or key-major ids (workmap.h)
+    if (!wk.live) return;
+    const size_t bi = wk.item;
+    const int limb = wk.limb_index;
     const LimbConst lc = tb.lc[limb];
     const InvLast<typename B::Tw> last = tb.last[limb];
     constexpr int kInComps = (MODE == 0 || MODE == 2) ? 3 : 2;
@@ -1113,15 +1059,14 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void ho
     // chain each - the k rotations of one token would otherwise fill a fraction of the chip with long-running workgroups
     // Several input ciphertexts (tokens) share the rotations: block = ((rotation * L + limb) * 2 + comp) * n_items + token, so
     // that the workgroups reading one key tile are neighbours in time (the tile is fetched once into L2 / Infinity Cache).
-    // ... and on the same XCD: ids are dealt to the 8 XCDs round-robin, so id = ((tile / 8) * n_items + token) * 8 + tile % 8 keeps the
-    // n_items workgroups of a tile on XCD tile % 8, adjacent in time - the key tile comes from HBM once, the other tokens hit that L2
-    const unsigned q = blockIdx.x >> 3, token = q % n_items, tile = (q / n_items) * 8u + (blockIdx.x & 7u);
-    if (tile >= n_tiles) return;
-    const int comp = (int)(tile & 1u);
+    // ... and on the same XCD (workmap.h HoistedMap): the key tile comes from HBM once, the other tokens hit that L2
     const unsigned La = tb.n_active ? (unsigned)tb.n_active : (unsigned)L;   // limbs this launch works on (one class of a mixed context, or all)
-    const size_t rot = (tile >> 1) / La;
-    int limb = (int)((tile >> 1) % La);
-    if (tb.n_active) limb = (int)((tb.active_map >> (4u * (unsigned)limb)) & 15u);
+    const HoistedWork wk = HoistedMap::decode<false>(blockIdx.x, n_items, n_tiles, La);
+    if (!wk.live) return;
+    const int comp = wk.comp;
+    const unsigned token = wk.token;
+    const size_t rot = wk.rot;
+    const int limb = launch_limb(tb, (unsigned)wk.limb_index);
     const size_t item = rot * n_items + token;        // output / work item
     digits += (size_t)token * (size_t)(L - 1) * L * N;
     const LimbConst lc = tb.lc[limb];
@@ -1131,12 +1076,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), (Arith::kFold ? 2 : 1)) void ho
     // source positions of this thread's E output positions p = tid E + kk
     unsigned src[E];
 #pragma unroll
-    for (int kk = 0; kk < E; ++kk) {
-        const unsigned p = (unsigned)tid * E + kk;
-        const unsigned e = 2u * (__brev(p) >> (32 - LOGN)) + 1u;
-        const unsigned e2 = (g * e) & (2u * N - 1u);
-        src[kk] = __brev((e2 - 1u) >> 1) >> (32 - LOGN);
-    }
+    for (int kk = 0; kk < E; ++kk) src[kk] = galois_src_pos<LOGN>(g, (unsigned)tid * E + kk);
     u64 acc[E], x[E], e[E];
 #pragma unroll
     for (int k = 0; k < E; ++k) acc[k] = 0;
@@ -1183,10 +1123,11 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void hoisted_ks2_kernel(u64*
     __shared__ __attribute__((aligned(16))) u64 lds[2 * W];
     const int tid = threadIdx.x;
     const int L = tb.n_limbs, Ld = L - 1;
-    const unsigned q = blockIdx.x >> 3, token = q % n_items, tile = (q / n_items) * 8u + (blockIdx.x & 7u);
-    if (tile >= n_tiles) return;
-    const size_t rot = tile / (unsigned)L;
-    const int limb = (int)(tile % (unsigned)L);
+    const HoistedWork wk = HoistedMap::decode<true>(blockIdx.x, n_items, n_tiles, (unsigned)L);
+    if (!wk.live) return;
+    const unsigned token = wk.token;
+    const size_t rot = wk.rot;
+    const int limb = wk.limb_index;
     const size_t item = rot * n_items + token;
     digits += (size_t)token * (size_t)(L - 1) * L * N;
     const LimbConst lc = tb.lc[limb];
@@ -1195,12 +1136,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void hoisted_ks2_kernel(u64*
     const u64* evk = keys + rot * key_stride;
     unsigned src[E];
 #pragma unroll
-    for (int kk = 0; kk < E; ++kk) {
-        const unsigned p = (unsigned)tid * E + kk;
-        const unsigned e = 2u * (__brev(p) >> (32 - LOGN)) + 1u;
-        const unsigned e2 = (g * e) & (2u * N - 1u);
-        src[kk] = __brev((e2 - 1u) >> 1) >> (32 - LOGN);
-    }
+    for (int kk = 0; kk < E; ++kk) src[kk] = galois_src_pos<LOGN>(g, (unsigned)tid * E + kk);
     u64 acc0[E], acc1[E], x[E], e[E];
 #pragma unroll
     for (int k = 0; k < E; ++k) acc0[k] = acc1[k] = 0;

@@ -1,6 +1,7 @@
 // kernels_bx.h - exact base extension / scale-and-round (include/dpfhe.h dpfhe_base_extend, dpfhe_scale_round); see base_ext.h for the argument block.
 #pragma once
 #include "base_ext.h"
+#include "workmap.h"
 
 namespace dpfhe {
 
@@ -17,8 +18,9 @@ __global__ __launch_bounds__(256) void base_extend_kernel(u64* __restrict__ out,
                                                           size_t in_dst_off /* MODE 1: word offset of the destination limbs inside an input item */,
                                                           BaseExtArgs a, const LimbConst* __restrict__ lcs, int n, int chunks) {
     static_assert(NS >= 1 && NS <= kBxMaxSrc, "source limbs");
-    const int chunk = (int)(blockIdx.x % chunks);
-    const size_t p = blockIdx.x / chunks;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, 1);   // (item, chunk): a workgroup reads all source limbs of its words
+    const int chunk = wk.chunk;
+    const size_t p = wk.poly;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const u64* src = in + p * in_stride + w0;

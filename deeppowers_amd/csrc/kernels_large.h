@@ -14,9 +14,9 @@ namespace dpfhe {
 template <class Arith>
 __global__ __launch_bounds__(256) void tensor3_kernel(u64* __restrict__ out3, const u64* __restrict__ a2, const u64* __restrict__ b2, const LimbConst* lcs,
                                                       int n_limbs, int n, int chunks) {
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % n_limbs);
-    const size_t pair = blockIdx.x / chunks / n_limbs;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t pair = wk.poly;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -38,9 +38,9 @@ __global__ __launch_bounds__(256) void tensor3_kernel(u64* __restrict__ out3, co
 template <class Arith>
 __global__ __launch_bounds__(256) void lift_rns_digits_kernel(u64* __restrict__ out, const u64* __restrict__ in, int in_comps, int comp, const LimbConst* lcs,
                                                               int n_limbs, int n, int chunks) {
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % n_limbs);
-    const size_t dg = blockIdx.x / chunks / n_limbs, item = dg / (unsigned)n_limbs, digit = dg % (unsigned)n_limbs;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);   // poly = (item, digit)
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t dg = wk.poly, item = dg / (unsigned)n_limbs, digit = dg % (unsigned)n_limbs;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -62,9 +62,9 @@ template <class Arith>
 __global__ __launch_bounds__(256) void key_inner_product_kernel(u64* __restrict__ acc, const u64* __restrict__ x, const u64* __restrict__ evk, const LimbConst* lcs,
                                                                 int n_digits, int n_limbs, int n, int chunks, size_t key_stride = 0, unsigned key_group = 1,
                                                                 unsigned item0 = 0) {
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % n_limbs);
-    const size_t item = blockIdx.x / chunks / n_limbs;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t item = wk.poly;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];

@@ -6,6 +6,7 @@
 #include "launch.h"
 #include "modarith.h"
 #include "reduce_thin.h"
+#include "workmap.h"
 
 namespace dpfhe {
 
@@ -96,9 +97,7 @@ __global__ __launch_bounds__(256) void copy_kernel(U64x2* __restrict__ dst, cons
     }
 }
 
-// The streaming kernels below take their work in 512-word chunks of a residue polynomial: 256 threads x one 16-byte pair (the `chunks` argument of each;
-// a thread owns words chunk * 512 + 2 tid and the next).  Rings below N = 512 have one partial chunk, whose upper threads idle.
-constexpr int chunks_of(size_t n) { return (int)((n + 511) / 512); }
+// (the streaming kernels below take their work in 512-word chunks of a residue polynomial: workmap.h chunks_of, chunk_work)
 
 // ------------------------------------------------------------------------------------------------
 // A8: out[c][l][:] = sum_i in[i][c][l][:]  (HBM-bound: one read per term).
@@ -224,14 +223,12 @@ template <class Arith, int RT>
 __global__ __launch_bounds__(256) void matvec_kernel(u64* y, const u64* W, const u64* x, const LimbConst* lcs, int n_limbs, int n,
                                                      int chunks, size_t rows, size_t cols) {
     const size_t L = (size_t)n_limbs;
-    // XCD-aware block ids (see matvec_multi_kernel): slab p = (limb, chunk) on XCD p mod 8, its row tiles adjacent there - the x tile of
+    // XCD-aware block ids (workmap.h MatvecMap): slab p = (limb, chunk) on XCD p mod 8, its row tiles adjacent there - the x tile of
     // a slab is fetched from HBM once and re-read from that XCD's L2 by the other row tiles
-    const unsigned n_slabs = (unsigned)L * (unsigned)chunks, R = (unsigned)((rows + RT - 1) / RT);
-    const unsigned id = blockIdx.x, q = id >> 3, slab = (q / R) * 8u + (id & 7u);
-    if (slab >= n_slabs) return;
-    const int chunk = (int)(slab % chunks);
-    const int limb = (int)(slab / chunks);
-    const size_t row0 = (size_t)(q % R) * RT;
+    const MatvecWork wk = MatvecMap::decode(blockIdx.x, (unsigned)L, (unsigned)chunks, (unsigned)((rows + RT - 1) / RT), 1u);
+    if (!wk.live) return;
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t row0 = (size_t)wk.row_tile * RT;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -287,18 +284,16 @@ template <class Arith, int RT, int C>
 __global__ __launch_bounds__(256) void matvec_multi_kernel(u64* y, const u64* W, const u64* x, const LimbConst* lcs, int n_limbs, int n,
                                                            int chunks, size_t rows, size_t cols, size_t polys_per_col /* >= C: the full [n_rhs][2] extent */,
                                                            unsigned n_groups, unsigned n_tiles) {
-    // `n_groups` groups of C / 2 right-hand sides and all row tiles in ONE launch, block ids laid out for the 8 XCDs (workgroups are
-    // dealt to them round-robin by id): slab p = (limb, chunk of 512 words) lives on XCD p mod 8, and its row tiles x groups are
-    // adjacent ids on that XCD - id = ((p / 8) * R * G + r * G + g) * 8 + p % 8.  The G workgroups of a row tile read the same W tile and
-    // the R workgroups of a group the same x tile at about the same time: each is fetched from HBM once, the rest are L2 hits.
+    // `n_groups` groups of C / 2 right-hand sides and all row tiles in ONE launch, block ids laid out for the 8 XCDs (workmap.h MatvecMap):
+    // slab p = (limb, chunk of 512 words) lives on XCD p mod 8, and its row tiles x groups are adjacent ids on that XCD.  The G workgroups of a
+    // row tile read the same W tile and the R workgroups of a group the same x tile at about the same time: each is fetched from HBM once.
     const size_t L = (size_t)n_limbs;
-    const unsigned n_slabs = (unsigned)L * (unsigned)chunks, R = n_tiles / n_slabs;   // n_tiles = row tiles * slabs
-    const unsigned id = blockIdx.x, lane = id & 7u, q = id >> 3;
-    const unsigned group = q % n_groups, rt = (q / n_groups) % R, slab = (q / (n_groups * R)) * 8u + lane;
-    if (slab >= n_slabs) return;
-    const int chunk = (int)(slab % chunks);
-    const int limb = (int)(slab / chunks);
-    const size_t row0 = (size_t)rt * RT;
+    const unsigned n_slabs = (unsigned)L * (unsigned)chunks;   // n_tiles = row tiles * slabs
+    const MatvecWork wk = MatvecMap::decode(blockIdx.x, (unsigned)L, (unsigned)chunks, n_tiles / n_slabs, n_groups);
+    if (!wk.live) return;
+    const unsigned group = wk.group;
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t row0 = (size_t)wk.row_tile * RT;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     x += (size_t)group * C * L * n;
@@ -399,13 +394,12 @@ __global__ __launch_bounds__(256) void matvec_fold_kernel(u64* y, const u64* W, 
     typedef FoldArith::Half30 H;
     constexpr int P = FoldArith::kDot30Period;
     const size_t L = (size_t)n_limbs;
-    const unsigned n_slabs = (unsigned)L * (unsigned)chunks, R = n_tiles / n_slabs;
-    const unsigned id = blockIdx.x, lane = id & 7u, q = id >> 3;
-    const unsigned group = q % n_groups, rt = (q / n_groups) % R, slab = (q / (n_groups * R)) * 8u + lane;
-    if (slab >= n_slabs) return;
-    const int chunk = (int)(slab % chunks);
-    const int limb = (int)(slab / chunks);
-    const size_t row0 = (size_t)rt * RT;
+    const unsigned n_slabs = (unsigned)L * (unsigned)chunks;
+    const MatvecWork wk = MatvecMap::decode(blockIdx.x, (unsigned)L, (unsigned)chunks, n_tiles / n_slabs, n_groups);
+    if (!wk.live) return;
+    const unsigned group = wk.group;
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t row0 = (size_t)wk.row_tile * RT;
     const unsigned w0 = (unsigned)(chunk * 256 * WPT + (int)threadIdx.x * WPT);   // the ONLY per-thread part of every address
     if ((int)w0 >= n) return;
     x += (size_t)group * C * L * n;
@@ -575,9 +569,9 @@ template <class Arith, int RT>
 __global__ __launch_bounds__(256) void matvec_scalar_kernel(u64* y, const u64* w, const u64* x, const LimbConst* lcs, int n_limbs, int n,
                                                             int chunks, size_t rows, size_t cols) {
     const size_t L = (size_t)n_limbs;
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % L);
-    const size_t row0 = (blockIdx.x / chunks / L) * RT;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, L);   // poly = row tile
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t row0 = wk.poly * RT;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -630,9 +624,9 @@ template <class Arith>
 __global__ __launch_bounds__(256) void rescale_kernel(u64* out, const u64* in, const u64* addend, int add_in_comps, int add_mask,
                                                       const LimbConst* lcs, const RescaleConst* rcs, int n_limbs, int n, int chunks) {
     const int Lo = n_limbs - 1;
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % Lo);
-    const size_t poly = blockIdx.x / chunks / Lo;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t poly = wk.poly;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -671,9 +665,9 @@ template <class Arith>
 __global__ __launch_bounds__(256) void rescale_bsgs_kernel(u64* out, const u64* in, const u64* addends, size_t n_add, size_t batch, const LimbConst* lcs,
                                                            const RescaleConst* rcs, int n_limbs, int n, int chunks) {
     const int Lo = n_limbs - 1;
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % Lo);
-    const size_t poly = blockIdx.x / chunks / Lo;   // = b * 2 + comp
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t poly = wk.poly;   // = b * 2 + comp
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     const LimbConst lc = lcs[limb];
@@ -713,9 +707,9 @@ __global__ __launch_bounds__(256) void rescale_bsgs_kernel(u64* out, const u64* 
 // data limbs, 0 on the special limb (P = 0 mod P).  in: [n_polys][Ld][N] -> out: [n_polys][L][N].  The un-rotated baby step.
 template <class Arith>
 __global__ __launch_bounds__(256) void lift_qp_kernel(u64* out, const u64* in, const LimbConst* lcs, u64 p_special, int n_limbs, int n, int chunks) {
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % n_limbs);
-    const size_t poly = blockIdx.x / chunks / n_limbs;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t poly = wk.poly;
     const int w0 = chunk * 512 + threadIdx.x * 2;
     if (w0 >= n) return;
     U64x2 r{0, 0};
@@ -745,44 +739,29 @@ __global__ __launch_bounds__(256) void lift_qp_kernel(u64* out, const u64* in, c
 // block of 16 rotations x n_items tokens at a time, all workgroups of one (limb, SOURCE segment): the block's workgroups are resident
 // together (5 per CU), every key segment is fetched from HBM once for its n_items tokens and every digit segment once for its 16 rotations.
 // ------------------------------------------------------------------------------------------------
-constexpr int kQpPairs = 2;          // 16-byte pairs per thread: segment = 512 pairs = 1024 words
-constexpr int kQpRotGroup = 16;      // rotations that share a digit segment in one XCD block
+// (kQpPairs, kQpRotGroup, the id layout and the pair map: workmap.h QpMap)
 struct QpElts { unsigned v[kMaxGaloisBatch]; };
-
-__device__ __forceinline__ unsigned qp_brev(unsigned x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
 
 template <class Arith, int PP>
 __global__ __launch_bounds__(256) void hoisted_qp_stream_kernel(u64* __restrict__ out, const u64* __restrict__ digits, const u64* __restrict__ xntt,
                                                                 const u64* __restrict__ keys, size_t key_stride, QpElts elts, unsigned n_rot, unsigned n_items,
                                                                 u64 p_special, const LimbConst* __restrict__ lcs, int n_limbs, int log2n) {
-    const int L = n_limbs, Ld = L - 1, n1 = log2n - 1;
-    const unsigned half = 1u << n1, n = 2u << n1, seg_pairs = 256u * PP;
-    const unsigned nseg = half > seg_pairs ? half / seg_pairs : 1u, tbits = 31u - (unsigned)__clz((int)nseg);
-    const unsigned combos = (unsigned)L * nseg, n_rg = (n_rot + kQpRotGroup - 1) / kQpRotGroup, bs = (unsigned)kQpRotGroup * n_items;
+    const int L = n_limbs, Ld = L - 1;
+    const QpGeo geo = QpMap::geo(log2n, PP);
     // id -> (XCD x, block of one (limb, source segment, rotation group), rotation in group, token)
-    const unsigned xcd = blockIdx.x & 7u, q = blockIdx.x >> 3, within = q % bs, t1 = q / bs, rg = t1 % n_rg, combo = (t1 / n_rg) * 8u + xcd;
-    const unsigned rot = rg * kQpRotGroup + within / n_items, token = within % n_items;
-    if (combo >= combos || rot >= n_rot) return;
-    const int limb = (int)(combo % (unsigned)L);
-    const unsigned sseg = combo / (unsigned)L;
+    const QpWork wk = QpMap::decode(blockIdx.x, geo, (unsigned)L, n_rot, n_items);
+    if (!wk.live) return;
+    const int limb = wk.limb;
+    const unsigned rot = wk.rot, token = wk.token;
     const unsigned g = elts.v[rot];
-    // output segment whose sources are segment sseg:  2 rev(oseg) + 1 = g^-1 (2 rev(sseg) + 1)  mod 2 nseg
-    unsigned ginv = g;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ginv *= 2u - g * ginv;                  // g^-1 mod 2^32
-    const unsigned uo = (ginv * (2u * qp_brev(sseg, (int)tbits) + 1u)) & (2u * nseg - 1u);
-    const unsigned oseg = qp_brev((uo - 1u) >> 1, (int)tbits);
     const LimbConst lc = lcs[limb];
-    const size_t N = n;
+    const size_t N = geo.n;
     unsigned ms[PP], mo[PP];
     bool sw[PP], ok[PP];
 #pragma unroll
     for (int c = 0; c < PP; ++c) {
-        mo[c] = oseg * seg_pairs + (unsigned)c * 256u + threadIdx.x;
-        ok[c] = mo[c] < half;
-        const unsigned cf = (g * (2u * qp_brev(mo[c], n1) + 1u)) & (2u * n - 1u);
-        sw[c] = cf >= n;
-        ms[c] = qp_brev(((cf & (n - 1u)) - 1u) >> 1, n1);
+        const QpPair pm = QpMap::pair_map(g, wk.sseg, (unsigned)c * 256u + threadIdx.x, geo);
+        mo[c] = pm.out; ms[c] = pm.src; sw[c] = pm.swap; ok[c] = pm.ok;
     }
     const size_t item = (size_t)rot * n_items + token;
     const u64* dig = digits + ((size_t)token * Ld * L + limb) * N;      // digit j at + j L N
@@ -925,28 +904,18 @@ __global__ __launch_bounds__(256) void hoisted_qp_upfront_kernel(u64* __restrict
                                                                  const u64* __restrict__ keys, size_t key_stride, QpElts elts, unsigned n_rot, unsigned n_items,
                                                                  u64 p_special, const LimbConst* __restrict__ lcs, int log2n) {
     constexpr int L = LD + 1;
-    const int n1 = log2n - 1;
-    const unsigned half = 1u << n1, n = 2u << n1, seg_pairs = 256u;
-    const unsigned nseg = half > seg_pairs ? half / seg_pairs : 1u, tbits = 31u - (unsigned)__clz((int)nseg);
-    const unsigned combos = (unsigned)L * nseg, n_rg = (n_rot + kQpRotGroup - 1) / kQpRotGroup, bs = (unsigned)kQpRotGroup * n_items;
-    const unsigned xcd = blockIdx.x & 7u, q = blockIdx.x >> 3, within = q % bs, t1 = q / bs, rg = t1 % n_rg, combo = (t1 / n_rg) * 8u + xcd;
-    const unsigned rot = rg * kQpRotGroup + within / n_items, token = within % n_items;
-    if (combo >= combos || rot >= n_rot) return;
-    const int limb = (int)(combo % (unsigned)L);
-    const unsigned sseg = combo / (unsigned)L;
+    const QpGeo geo = QpMap::geo(log2n, 1);
+    const QpWork wk = QpMap::decode(blockIdx.x, geo, (unsigned)L, n_rot, n_items);
+    if (!wk.live) return;
+    const int limb = wk.limb;
+    const unsigned rot = wk.rot, token = wk.token;
     const unsigned g = elts.v[rot];
-    unsigned ginv = g;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ginv *= 2u - g * ginv;
-    const unsigned uo = (ginv * (2u * qp_brev(sseg, (int)tbits) + 1u)) & (2u * nseg - 1u);
-    const unsigned oseg = qp_brev((uo - 1u) >> 1, (int)tbits);
     const LimbConst lc = lcs[limb];
-    const size_t N = n;
-    const unsigned mo = oseg * seg_pairs + threadIdx.x;
-    if (mo >= half) return;
-    const unsigned cf = (g * (2u * qp_brev(mo, n1) + 1u)) & (2u * n - 1u);
-    const bool sw = cf >= n;
-    const unsigned ms = qp_brev(((cf & (n - 1u)) - 1u) >> 1, n1);
+    const size_t N = geo.n;
+    const QpPair pm = QpMap::pair_map(g, wk.sseg, threadIdx.x, geo);
+    if (!pm.ok) return;
+    const unsigned mo = pm.out, ms = pm.src;
+    const bool sw = pm.swap;
     const size_t item = (size_t)rot * n_items + token;
     const U64x2* dig = reinterpret_cast<const U64x2*>(digits + ((size_t)token * LD * L + limb) * N) + ms;      // digit j at + j L N words
     const U64x2* evk = reinterpret_cast<const U64x2*>(keys + (size_t)rot * key_stride + (size_t)limb * N) + mo;  // key (j, comp) at + (j 2 + comp) L N words
@@ -982,13 +951,6 @@ __global__ __launch_bounds__(256) void hoisted_qp_upfront_kernel(u64* __restrict
     r1.a = FoldArith::canon_small(FoldArith::dot30_fold(s1[0], 0, lc), lc); r1.b = FoldArith::canon_small(FoldArith::dot30_fold(s1[1], 0, lc), lc);
     st_vec<true>(reinterpret_cast<U64x2*>(out + ((item * 2 + 0) * L + limb) * N) + mo, r0);
     st_vec<true>(reinterpret_cast<U64x2*>(out + ((item * 2 + 1) * L + limb) * N) + mo, r1);
-}
-
-// grid of the stream kernel (dpfhe_cabi.hip): 8 XCDs x blocks of (16 rotations x n_items) x rotation groups x ceil(L nseg / 8)
-inline size_t qp_stream_grid(int log2n, int n_limbs, size_t n_rot, size_t n_items, int pairs = kQpPairs) {
-    const size_t half = (size_t)1 << (log2n - 1), seg_pairs = 256 * (size_t)pairs, nseg = half > seg_pairs ? half / seg_pairs : 1;
-    const size_t combos = (size_t)n_limbs * nseg, n_rg = (n_rot + kQpRotGroup - 1) / kQpRotGroup;
-    return 8 * ((combos + 7) / 8) * n_rg * (size_t)kQpRotGroup * n_items;
 }
 
 // N3, hoisted rotations: digit j of the key-switched component (limb j of c1, coefficient domain, values < q_j) lifted to every

@@ -193,19 +193,10 @@ int launch_relin(int log2n, int mode, u64* out2, const u64* in3, const u64* evk,
     if (mode < 0 || mode > 4) return -1;
     const unsigned La = tb.n_active ? (unsigned)tb.n_active : (unsigned)tb.n_limbs;   // limbs this launch works on (one class of a mixed context, or all): blocks = items x La
     const int n_digits = mode >= 2 ? tb.n_limbs - 1 : tb.n_limbs;
-    // items that share a key (key_group > 1) are laid out per XCD: kernels.h relin_kernel
+    // plain ids, or - items that share a key, or have one each - ids laid out per XCD (workmap.h RelinMap, decoded by the kernels)
     const unsigned kg = key_group ? key_group : 1u;
-    // (round 6: items with a key each and NO sharing - one token's rotations - take the key-major order too: all limbs of an item on one XCD, so that its
-    //  digits cross the fabric once, not once per XCD - profiles/r06_giant_traffic.txt, shape (15, 1).  Items that share ONE key (key_stride 0) keep the plain
-    //  order, in which an XCD only ever touches the key tiles of its own limbs.)
-    unsigned n_outer = ((kg > 1 || key_stride != 0) && blocks % ((size_t)kg * La) == 0) ? (unsigned)(blocks / kg) : 0u;   // whole groups only
-    unsigned grid = n_outer ? ((n_outer + 7u) / 8u) * 8u * kg : (unsigned)blocks;
-    // eight keys or more: one key (all its limbs and items) per XCD at a time, so that the items' digits are fetched once, not once per limb
-    if (n_outer && n_outer / La >= 8u) {
-        const unsigned n_keys = n_outer / La;
-        grid = ((n_keys + 7u) / 8u) * 8u * La * kg;
-        n_outer |= kRelinRotMajor;
-    }
+    const RelinPlan plan = RelinMap::plan(blocks, La, key_stride, key_group);
+    const unsigned n_outer = plan.n_outer, grid = (unsigned)plan.grid;
 #ifdef DPFHE_DIAGNOSTICS   // (tools/relin_trace.py reads the buffer back)
     if constexpr (Arith::kFold) {
         if (log2n == 13 && mode == 4) {
@@ -248,10 +239,9 @@ int launch_hoisted_ks(int log2n, u64* work, const u64* digits, const u64* keys, 
     // transforms share their twiddles (kernels.h hoisted_ks2_kernel)
     constexpr size_t kHoistedMergeMin = 512;
     const unsigned La = tb.n_active ? (unsigned)tb.n_active : (unsigned)tb.n_limbs;  // limbs this launch works on (one class of a mixed context, or all)
-    const unsigned tiles1 = (unsigned)(count * (size_t)La);                         // (rotation, limb)
-    const bool merged = Arith::kFold && !tb.n_active && tb.n_limbs - 1 <= 7 && (size_t)tiles1 * n_items >= kHoistedMergeMin;
-    const unsigned tiles = merged ? tiles1 : tiles1 * 2u;                           // ... x key component when split
-    const unsigned blocks = ((tiles + 7u) / 8u) * 8u * (unsigned)n_items;           // x token, ids laid out per XCD (kernels.h)
+    const bool merged = Arith::kFold && !tb.n_active && tb.n_limbs - 1 <= 7 && count * (size_t)La * n_items >= kHoistedMergeMin;
+    const HoistedPlan plan = HoistedMap::plan(count, La, n_items, merged);          // (rotation, limb[, key component when split]) tiles x token, ids laid out per XCD
+    const unsigned tiles = plan.tiles, blocks = plan.blocks;
 #define HK_CASE(LN, LE)                                                                                                                                  \
     if constexpr (Arith::kFold) {                                                                                                                        \
         if (merged) {                                                                                                                                    \

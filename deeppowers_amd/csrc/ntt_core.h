@@ -60,6 +60,14 @@ DPF_HD unsigned brev32(unsigned x) {
     return ((x & 0xaaaaaaaau) >> 1) | ((x & 0x55555555u) << 1);
 #endif
 }
+// sigma_g: a(X) -> a(X^g) in forward-output order, where position p carries the evaluation at psi^(2 brv(p) + 1): NTT(sigma_g a)[p] = NTT(a)[p'] with
+// 2 brv(p') + 1 = g (2 brv(p) + 1) mod 2N.  Returns p' (brv over LOGN bits; g odd, < 2N).
+template <int LOGN>
+DPF_HD unsigned galois_src_pos(unsigned g, unsigned p) {
+    const unsigned e = 2u * (brev32(p) >> (32 - LOGN)) + 1u;
+    const unsigned e2 = (g * e) & ((2u << LOGN) - 1u);
+    return brev32((e2 - 1u) >> 1) >> (32 - LOGN);
+}
 // Sub-block b of a split transform (N = N1 N2, ntt_top.h) under sigma_g.  Position k = b N2 + k_low of the forward output holds exponent
 // e = 2 brv_N(k) + 1 = 2 N1 r + c with r = brv_N2(k_low) and c = 2 brv_N1(b) + 1, so g e = 2 N1 (g r + floor(g c / 2 N1)) + (g c mod 2 N1): every word
 // of sub-block b comes from ONE source sub-block (that of g c mod 2 N1), at r' = (g r + h) mod N2 - NttBody::gather_plan's map with this h.

@@ -1,0 +1,105 @@
+// emulate_workmap.cpp - the work maps of deeppowers_amd/csrc/workmap.h on the CPU (TEST INFRASTRUCTURE, like emulate.cpp and emulate_reduce.cpp).
+// Per map: "decode ids [0, n_ids)" with the very functions the kernels call, and "the grid for these parameters" with the very functions the launchers
+// call.  Rows of `out` are int64.  Built by tests/test_work_maps_cpu.py (g++), never shipped.
+#include "../deeppowers_amd/csrc/devtables.h"
+#include "../deeppowers_amd/csrc/workmap.h"
+
+using namespace dpfhe;
+typedef long long i64;
+
+namespace {
+struct Tables {   // what the limb helpers of devtables.h read of a DevTables
+    int n_sub, n_limbs, n_active;
+    unsigned long long active_map;
+};
+}  // namespace
+
+extern "C" {
+
+// key switching: plan -> grid (n_outer through the pointer); rows (item, limb, live) - limb through the launch's active_map when n_active != 0
+u64 wm_relin_plan(size_t blocks, unsigned La, size_t key_stride, unsigned key_group, unsigned* n_outer) {
+    const RelinPlan p = RelinMap::plan(blocks, La, key_stride, key_group);
+    *n_outer = p.n_outer;
+    return p.grid;
+}
+void wm_relin_decode(unsigned n_ids, unsigned n_outer, unsigned key_group, unsigned La, int n_limbs, int n_active, unsigned long long active_map, i64* out) {
+    const Tables tb{1, n_limbs, n_active, active_map};
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const RelinWork w = RelinMap::decode(id, n_outer, key_group, La);
+        out[3 * id] = (i64)w.item; out[3 * id + 1] = launch_limb(tb, (unsigned)w.limb_index); out[3 * id + 2] = w.live;
+    }
+}
+
+// hoisted rotations: rows (rotation, limb index, component, token, live)
+void wm_hoisted_plan(size_t count, unsigned La, size_t n_items, int merged, unsigned* tiles, unsigned* blocks) {
+    const HoistedPlan p = HoistedMap::plan(count, La, n_items, merged != 0);
+    *tiles = p.tiles;
+    *blocks = p.blocks;
+}
+void wm_hoisted_decode(unsigned n_ids, unsigned n_items, unsigned n_tiles, unsigned La, int merged, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const HoistedWork w = merged ? HoistedMap::decode<true>(id, n_items, n_tiles, La) : HoistedMap::decode<false>(id, n_items, n_tiles, La);
+        i64* o = out + 5 * (size_t)id;
+        o[0] = (i64)w.rot; o[1] = w.limb_index; o[2] = w.comp; o[3] = w.token; o[4] = w.live;
+    }
+}
+
+// matrix-vector products: rows (limb, chunk, row tile, group, live)
+u64 wm_matvec_grid(size_t n_limbs, size_t chunks, size_t row_tiles, size_t n_groups) { return MatvecMap::grid(n_limbs, chunks, row_tiles, n_groups); }
+void wm_matvec_decode(unsigned n_ids, unsigned n_limbs, unsigned chunks, unsigned row_tiles, unsigned n_groups, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const MatvecWork w = MatvecMap::decode(id, n_limbs, chunks, row_tiles, n_groups);
+        i64* o = out + 5 * (size_t)id;
+        o[0] = w.limb; o[1] = w.chunk; o[2] = w.row_tile; o[3] = w.group; o[4] = w.live;
+    }
+}
+
+// baby steps: rows (limb, source segment, rotation, token, live); pair map of one (g, source segment): rows (out, src, swap, ok) per lane
+u64 wm_qp_grid(int log2n, size_t n_limbs, size_t n_rot, size_t n_items, unsigned pairs) { return QpMap::grid(log2n, n_limbs, n_rot, n_items, pairs); }
+unsigned wm_qp_segments(int log2n, unsigned pairs) { return QpMap::geo(log2n, pairs).nseg; }
+void wm_qp_decode(unsigned n_ids, int log2n, unsigned pairs, unsigned n_limbs, unsigned n_rot, unsigned n_items, i64* out) {
+    const QpGeo geo = QpMap::geo(log2n, pairs);
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const QpWork w = QpMap::decode(id, geo, n_limbs, n_rot, n_items);
+        i64* o = out + 5 * (size_t)id;
+        o[0] = w.limb; o[1] = w.sseg; o[2] = w.rot; o[3] = w.token; o[4] = w.live;
+    }
+}
+void wm_qp_pair_map(int log2n, unsigned pairs, unsigned g, unsigned sseg, i64* out) {
+    const QpGeo geo = QpMap::geo(log2n, pairs);
+    for (unsigned lane = 0; lane < geo.seg_pairs; ++lane) {
+        const QpPair p = QpMap::pair_map(g, sseg, lane, geo);
+        i64* o = out + 4 * (size_t)lane;
+        o[0] = p.out; o[1] = p.src; o[2] = p.swap; o[3] = p.ok;
+    }
+}
+
+// streaming kernels: rows (chunk, limb, polynomial)
+int wm_chunks_of(size_t n) { return chunks_of(n); }
+void wm_chunk_decode(unsigned n_ids, int chunks, int n_limbs, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const ChunkWork w = chunk_work(id, chunks, n_limbs);
+        out[3 * id] = w.chunk; out[3 * id + 1] = w.limb; out[3 * id + 2] = (i64)w.poly;
+    }
+}
+
+// batched transforms: rows (first word / N, limb, sub-block)
+void wm_transform_decode(unsigned n_ids, int n_sub, int n_limbs, int n_active, unsigned long long active_map, i64* out) {
+    const Tables tb{n_sub, n_limbs, n_active, active_map};
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const TransformBlock b = transform_block(tb, id);
+        out[3 * id] = (i64)b.p; out[3 * id + 1] = b.limb; out[3 * id + 2] = (i64)b.sub;
+    }
+}
+
+// Galois source positions of all N output positions; 0, or -1 for a ring degree not compiled here
+int wm_galois_src_pos(int log2n, unsigned g, i64* out) {
+    for (unsigned p = 0; p < (1u << log2n); ++p) {
+        if (log2n == 8) out[p] = galois_src_pos<8>(g, p);
+        else if (log2n == 10) out[p] = galois_src_pos<10>(g, p);
+        else return -1;
+    }
+    return 0;
+}
+
+}  // extern "C"
