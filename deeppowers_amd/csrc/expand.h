@@ -1,6 +1,6 @@
 // expand.h - the uniform half of seeded ciphertexts and keys: expand(seed, item, limb, component), a wire format.
 //
-//   ChaCha20 block function exactly as in RFC 8439 section 2.3: constants | key = the 32-byte seed as 8 little-endian words |
+//   ChaCha20 block function exactly as in RFC 8439 section 2.3 (chacha20.h): constants | key = the 32-byte seed as 8 little-endian words |
 //   word 12 = 32-bit block counter | words 13..15 = nonce, here (item, limb, component).  Coefficient k of the polynomial takes
 //   block k / 4, output words 4 (k mod 4) .. 4 (k mod 4) + 3, read as ONE 128-bit little-endian integer X, and is X mod q_limb.
 //   The statistical distance from uniform is at most q / 2^128 < 2^-68 per coefficient; there is no rejection step.
@@ -14,40 +14,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "chacha20.h"
 #include "modarith.h"
 
 namespace dpfhe {
-
-struct ExpandKey {   // the seed as 8 little-endian words: a kernel argument, so the key words live in SGPRs
-    u32 w[8];
-};
-
-DPF_HD u32 rotl32(u32 v, int c) { return __builtin_rotateleft32(v, (u32)c); }   // one v_alignbit_b32 (v_perm_b32 for 8 / 16)
-
-#define DPFHE_CHACHA_QR(a, b, c, d)            \
-    a += b; d = rotl32(d ^ a, 16);             \
-    c += d; b = rotl32(b ^ c, 12);             \
-    a += b; d = rotl32(d ^ a, 8);              \
-    c += d; b = rotl32(b ^ c, 7)
-
-// RFC 8439 section 2.3: the 16 output words of the block (counter, nonce n0 n1 n2) under key k
-DPF_HD void chacha20_block(const ExpandKey& k, u32 counter, u32 n0, u32 n1, u32 n2, u32 out[16]) {
-    u32 x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;   // "expand 32-byte k"
-    u32 x4 = k.w[0], x5 = k.w[1], x6 = k.w[2], x7 = k.w[3], x8 = k.w[4], x9 = k.w[5], x10 = k.w[6], x11 = k.w[7];
-    u32 x12 = counter, x13 = n0, x14 = n1, x15 = n2;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int i = 0; i < 10; ++i) {
-        DPFHE_CHACHA_QR(x0, x4, x8, x12); DPFHE_CHACHA_QR(x1, x5, x9, x13); DPFHE_CHACHA_QR(x2, x6, x10, x14); DPFHE_CHACHA_QR(x3, x7, x11, x15);
-        DPFHE_CHACHA_QR(x0, x5, x10, x15); DPFHE_CHACHA_QR(x1, x6, x11, x12); DPFHE_CHACHA_QR(x2, x7, x8, x13); DPFHE_CHACHA_QR(x3, x4, x9, x14);
-    }
-    out[0] = x0 + 0x61707865u; out[1] = x1 + 0x3320646eu; out[2] = x2 + 0x79622d32u; out[3] = x3 + 0x6b206574u;
-    out[4] = x4 + k.w[0]; out[5] = x5 + k.w[1]; out[6] = x6 + k.w[2]; out[7] = x7 + k.w[3];
-    out[8] = x8 + k.w[4]; out[9] = x9 + k.w[5]; out[10] = x10 + k.w[6]; out[11] = x11 + k.w[7];
-    out[12] = x12 + counter; out[13] = x13 + n0; out[14] = x14 + n1; out[15] = x15 + n2;
-}
-#undef DPFHE_CHACHA_QR
 
 // X = hi 2^64 + lo  ->  X mod q, exact for ANY X < 2^128 (q < 2^60; br = floor(2^128 / q) = br_hi 2^64 + br_lo, LimbConst).
 // Barrett: floor(X br / 2^128) >= floor(X / q) - 1 since br > 2^128 / q - 1 and X < 2^128.  The estimate below is

@@ -1,0 +1,218 @@
+// fhe_keyswitch.cpp - the facade's hybrid key switcher (one special prime P): relinearisation and Galois keys on the extended context Q P and the
+// rotations built on them.  Part of libdpfhe_api.so (fhe_api.cpp names the other units); its keys are made by fhe_keys.cpp's make_switch_key.
+#include "fhe_internal.h"
+#include "fhe_sampler.h"
+
+namespace deeppowers {
+namespace fhe {
+
+using namespace detail;
+
+// ---- HybridKeySwitcher ---------------------------------------------------------------------------------------------------
+class __attribute__((visibility("hidden"))) HybridKeySwitcher::Impl {   // (hidden like the Sampler it holds)
+public:
+    const Context* data_ctx = nullptr;
+    std::unique_ptr<Context> ext;
+    std::unique_ptr<SecretKey> sk_ext;
+    std::unique_ptr<PolyBuffer> relin;                       // [Ld][2][L][N]
+    std::vector<std::pair<uint32_t, std::unique_ptr<PolyBuffer>>> galois;
+    std::vector<std::pair<std::vector<uint32_t>, std::unique_ptr<PolyBuffer>>> packed;   // element list -> its keys back to back
+    std::unique_ptr<PolyBuffer> scratch_work;      // batched rotations: reused across calls (one caller at a time per switcher)
+    std::unique_ptr<Ciphertext> scratch_rotated;
+    std::unique_ptr<PolyBuffer> scratch_digits;    // hoisted rotations: NTT of the lifted digits, [Ld][L][N]
+    std::unique_ptr<Ciphertext> scratch_in_ntt;    // rotate_hoisted_qp: NTT of the inputs on the data limbs
+    void init(const Context& data, const SecretKey& sk, uint64_t special_prime, uint64_t special_psi) {
+        data_ctx = &data;
+        FheParams pe = data.params();
+        pe.moduli.push_back(special_prime);
+        pe.psi.push_back(special_psi);
+        ext.reset(new Context(pe, data.device_id()));
+        sk_ext.reset(new SecretKey(*ext, sk.coefficients()));
+        p_special = special_prime;
+        relin.reset(new PolyBuffer(*ext, pe.n_limbs() - 1, 2, true));
+        make_key(sk_ext->ntt_squared(), *relin);
+    }
+    const PolyBuffer* find_key(uint32_t g) const {   // null: the element was never added
+        for (auto& kv : galois) if (kv.first == g) return kv.second.get();
+        return nullptr;
+    }
+    // the keys of an element list, packed back to back once and cached
+    const PolyBuffer* packed_keys(const std::vector<uint32_t>& elts, Stream* s = nullptr) {
+        for (auto& kv : packed) if (kv.first == elts) return kv.second.get();
+        const FheParams& pe = ext->params();
+        const size_t L = pe.n_limbs(), Ld = L - 1, key_words = Ld * 2 * L * pe.n();
+        std::unique_ptr<PolyBuffer> buf(new PolyBuffer(*ext, elts.size() * Ld, 2, true));
+        for (size_t i = 0; i < elts.size(); ++i) {
+            const PolyBuffer* key = find_key(elts[i]);
+            if (!key) throw Exception(ErrorCode::INVALID_STATE, "HybridKeySwitcher: no key for an element (add_galois_element first)");
+            // on the caller's stream: a blocking null-stream copy would not order against work on a non-blocking stream
+            hip_check(hipMemcpyAsync(buf->data() + i * key_words, key->data(), key_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)),
+                      "hipMemcpyAsync D2D");
+        }
+        // The pack is cached and handed to LATER callers on ANY stream: it happens once per element list, so the copies are simply waited for
+        // here - nothing orders another stream's kernels against an asynchronous copy they never saw being enqueued.
+        hip_check(hipStreamSynchronize(static_cast<hipStream_t>(s)), "hipStreamSynchronize (key pack)");
+        packed.emplace_back(elts, std::move(buf));
+        return packed.back().second.get();
+    }
+    void ensure_scratch(size_t k) {
+        grow_scratch(scratch_work, k, [&](size_t b) { return new PolyBuffer(*ext, b, 2, false); });
+        grow_scratch(scratch_rotated, k, [&](size_t b) { return new Ciphertext(*data_ctx, 2, b); });
+    }
+    void ensure_digits(size_t polys) { grow_scratch(scratch_digits, polys, [&](size_t b) { return new PolyBuffer(*ext, b, 1, true); }); }
+    Sampler rng;
+    uint64_t p_special = 0;
+
+    // target (NTT domain on ext, all limbs) scaled by P limb-wise: P mod q_i for data limbs, 0 for the P limb
+    void make_key(const uint64_t* d_target_ntt_ext, PolyBuffer& out) {
+        const FheParams& pe = ext->params();
+        const size_t n = pe.n(), L = pe.n_limbs();
+        std::vector<uint64_t> host(L * n);
+        hip_check(hipMemcpy(host.data(), d_target_ntt_ext, L * n * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        for (size_t l = 0; l < L; ++l) {
+            const uint64_t q = pe.moduli[l], f = p_special % q;   // 0 on the special limb itself
+            for (size_t k = 0; k < n; ++k) host[l * n + k] = (uint64_t)((u128)host[l * n + k] * f % q);
+        }
+        PolyBuffer scaled(*ext, 1, 1, true);
+        scaled.copy_from_host(host.data());
+        make_switch_key(*ext, *sk_ext, rng, scaled.data(), out, L - 1, nullptr);
+    }
+};
+
+HybridKeySwitcher::HybridKeySwitcher(const Context& data_ctx, const SecretKey& sk, uint64_t special_prime, uint64_t special_psi) : impl_(new Impl) {
+    impl_->init(data_ctx, sk, special_prime, special_psi);
+}
+HybridKeySwitcher::HybridKeySwitcher(const Context& data_ctx, const SecretKey& sk, uint64_t special_prime, uint64_t special_psi, TestSeed seed) : impl_(new Impl) {
+    impl_->rng = Sampler(seed);
+    impl_->init(data_ctx, sk, special_prime, special_psi);
+}
+HybridKeySwitcher::~HybridKeySwitcher() = default;
+
+void HybridKeySwitcher::add_galois_element(uint32_t g) {
+    const FheParams& pe = impl_->ext->params();
+    const size_t n = pe.n(), L = pe.n_limbs();
+    if (!(g & 1u) || g >= 2 * n) throw Exception(ErrorCode::INVALID_ARGUMENT, "add_galois_element: element must be odd and < 2N");
+    if (impl_->find_key(g)) return;
+    PolyBuffer target = galois_target_ntt(*impl_->ext, impl_->sk_ext->coefficients(), g);
+    std::unique_ptr<PolyBuffer> key(new PolyBuffer(*impl_->ext, L - 1, 2, true));
+    impl_->make_key(target.data(), *key);
+    impl_->galois.emplace_back(g, std::move(key));
+}
+
+void HybridKeySwitcher::relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* s) const {
+    if (in3.is_ntt() || in3.size() != 3 || out2.size() != 2 || out2.batch() != in3.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::relinearize: 3-component coefficient-domain input, 2-component output");
+    PolyBuffer work(*impl_->ext, in3.batch(), 2, false);
+    check(dpfhe_relinearize_hybrid(handle_of(*impl_->ext), out2.data(), in3.data(), impl_->relin->data(), work.data(), in3.batch(), s),
+          "dpfhe_relinearize_hybrid");
+    hip_check(hipStreamSynchronize(static_cast<hipStream_t>(s)), "hipStreamSynchronize");   // `work` is freed on return
+    out2.set_ntt(false);
+}
+
+void HybridKeySwitcher::apply_galois(const Ciphertext& in2, uint32_t g, Ciphertext& out2, Stream* s) const {
+    if (in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || out2.batch() != in2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::apply_galois: 2-component coefficient-domain input and output");
+    const PolyBuffer* key = impl_->find_key(g);
+    if (!key) throw Exception(ErrorCode::INVALID_STATE, "HybridKeySwitcher::apply_galois: no key for this element (add_galois_element first)");
+    Ciphertext rotated(*impl_->data_ctx, 2, in2.batch());
+    PolyBuffer work(*impl_->ext, in2.batch(), 2, false);
+    check(dpfhe_apply_galois(handle_of(*impl_->data_ctx), rotated.data(), in2.data(), in2.batch() * 2, g, s), "dpfhe_apply_galois");
+    check(dpfhe_switch_key_hybrid(handle_of(*impl_->ext), out2.data(), rotated.data(), key->data(), work.data(), in2.batch(), s),
+          "dpfhe_switch_key_hybrid");
+    hip_check(hipStreamSynchronize(static_cast<hipStream_t>(s)), "hipStreamSynchronize");
+    out2.set_ntt(false);
+}
+
+void HybridKeySwitcher::apply_galois_many(const Ciphertext& in2, const std::vector<uint32_t>& elts, Ciphertext& out2, size_t out_first, Stream* s) const {
+    if (in2.batch() != 1 && in2.batch() != elts.size())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::apply_galois_many: input of 1 or k items, output with room for k items");
+    apply_galois_range(in2, 0, in2.batch() == 1 && elts.size() != 1, elts, out2, out_first, s);
+}
+
+void HybridKeySwitcher::apply_galois_range(const Ciphertext& in2, size_t in_first, bool broadcast, const std::vector<uint32_t>& elts, Ciphertext& out2,
+                                           size_t out_first, Stream* s) const {
+    const size_t k = elts.size();
+    if (k == 0) return;
+    if (in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in_first + (broadcast ? 1 : k) > in2.batch() || out_first + k > out2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::apply_galois_range: input range of 1 (broadcast) or k items, output with room for k items");
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), Ld = L - 1, n = pe.n(), ct_words = 2 * Ld * n;
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    impl_->ensure_scratch(k);   // kept for the next call: no allocation and no host synchronisation on the steady path
+    check(dpfhe_rotate_hybrid_batch(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words,
+                                    broadcast ? 1 : k, elts.data(), keys->data(), impl_->scratch_work->data(), impl_->scratch_rotated->data(), k, s),
+          "dpfhe_rotate_hybrid_batch");
+    out2.set_ntt(false);
+}
+
+void HybridKeySwitcher::apply_galois_hoisted(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& elts, Ciphertext& out2,
+                                             size_t out_first, Stream* s) const {
+    const size_t k = elts.size();
+    if (k == 0 || n_items == 0) return;
+    if (in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in_first + n_items > in2.batch() || out_first + k * n_items > out2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::apply_galois_hoisted: n_items input items, output with room for k * n_items items");
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), Ld = L - 1, n = pe.n(), ct_words = 2 * Ld * n;
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    impl_->ensure_scratch(k * n_items);
+    impl_->ensure_digits(n_items * Ld);
+    check(dpfhe_rotate_hybrid_hoisted(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words, n_items,
+                                      elts.data(), keys->data(), impl_->scratch_work->data(), impl_->scratch_rotated->data(), impl_->scratch_digits->data(), k, s),
+          "dpfhe_rotate_hybrid_hoisted");
+    out2.set_ntt(false);
+}
+
+void HybridKeySwitcher::apply_galois_grouped(const Ciphertext& in2, size_t in_first, const std::vector<uint32_t>& elts, size_t group, Ciphertext& out2,
+                                             size_t out_first, Stream* s) const {
+    const size_t k = elts.size(), batch = k * group;
+    if (batch == 0) return;
+    if (in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in_first + batch > in2.batch() || out_first + batch > out2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::apply_galois_grouped: k * group items in and out");
+    const FheParams& pe = impl_->ext->params();
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), ct_words = 2 * Ld * n;
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    impl_->ensure_scratch(batch);
+    check(dpfhe_rotate_hybrid_grouped(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words, elts.data(), k,
+                                      group, keys->data(), impl_->scratch_work->data(), impl_->scratch_rotated->data(), s),
+          "dpfhe_rotate_hybrid_grouped");
+    out2.set_ntt(false);
+}
+
+const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
+
+void HybridKeySwitcher::rotate_hoisted_qp(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& elts, PolyBuffer& out_qp,
+                                          size_t out_first, Stream* s) const {
+    const size_t k = elts.size();
+    if (n_items == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), Ld = L - 1, n = pe.n();
+    if (in2.is_ntt() || in2.size() != 2 || out_qp.size() != 2 || in_first + n_items > in2.batch() || out_first + (k + 1) * n_items > out_qp.batch() ||
+        out_qp.words() != out_qp.batch() * 2 * L * n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::rotate_hoisted_qp: n_items coefficient-domain inputs, (k + 1) * n_items items on the extended context out");
+    const PolyBuffer* keys = k ? impl_->packed_keys(elts, s) : nullptr;
+    impl_->ensure_digits(n_items * Ld);
+    grow_scratch(impl_->scratch_in_ntt, n_items, [&](size_t b) { return new Ciphertext(*impl_->data_ctx, 2, b, true); });
+    check(dpfhe_rotate_hoisted_qp(handle_of(*impl_->ext), out_qp.data() + out_first * 2 * L * n, in2.data() + in_first * 2 * Ld * n, n_items,
+                                  elts.data(), keys ? keys->data() : nullptr, impl_->scratch_in_ntt->data(), impl_->scratch_digits->data(), k, s),
+          "dpfhe_rotate_hoisted_qp");
+    out_qp.set_ntt(true);
+}
+
+void HybridKeySwitcher::switch_key_qp(const Ciphertext& in2, size_t in_first, const std::vector<uint32_t>& elts, size_t group, PolyBuffer& out_qp,
+                                      size_t out_first, Stream* s) const {
+    const size_t k = elts.size(), batch = k * group;
+    if (batch == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), Ld = L - 1, n = pe.n();
+    if (in2.is_ntt() || in2.size() != 2 || out_qp.size() != 2 || in_first + batch > in2.batch() || out_first + batch > out_qp.batch() ||
+        out_qp.words() != out_qp.batch() * 2 * L * n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::switch_key_qp: k * group coefficient-domain items in, as many items on the extended context out");
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    check(dpfhe_switch_key_qp(handle_of(*impl_->ext), out_qp.data() + out_first * 2 * L * n, in2.data() + in_first * 2 * Ld * n, keys->data(), k,
+                              group, s),
+          "dpfhe_switch_key_qp");
+    out_qp.set_ntt(true);
+}
+
+}  // namespace fhe
+}  // namespace deeppowers

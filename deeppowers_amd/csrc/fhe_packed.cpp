@@ -1,0 +1,446 @@
+// fhe_packed.cpp - the facade's packed encrypted layers over the slot encoding and the hybrid key switcher: PackedLinear, PackedSelect,
+// PackedTransformerBlock.  Part of libdpfhe_api.so (fhe_api.cpp names the other units).
+#include <chrono>
+
+#include "fhe_internal.h"
+
+namespace deeppowers {
+namespace fhe {
+
+using namespace detail;
+
+// ---- N3: packed matrix-vector product (diagonal method, baby-step / giant-step) -------------------------------------------
+constexpr int kBabyShiftDefault = 1;
+
+class PackedLinear::Impl {
+public:
+    const Context* ctx = nullptr;
+    const BatchEncoder* enc = nullptr;
+    HybridKeySwitcher* ks = nullptr;
+    size_t out_dim = 0, in_dim = 0;
+    size_t n = 0;        // input period: the input vector repeats every n slots of a row (power of two >= in_dim)
+    size_t m = 0;        // diagonals per pass = output period (n, or the padded out_dim of a wide-input layer)
+    size_t tpc = 1;      // tokens per ciphertext: 2 = the two slot rows carry two tokens (the windows of ONE row share the output blocks)
+    size_t copies = 0;   // independent n-slot windows that share the output blocks = N / n (tpc = 2: of one row, N / 2 / n)
+    size_t blocks = 0;   // output row blocks of m rows
+    size_t passes = 0;   // output ciphertexts
+    bool replicate = false;   // one block: every window computes it (the output is again a periodic vector)
+    size_t n1 = 0, n2 = 0;
+    std::unique_ptr<Plaintext> diag;   // [passes][n2][n1] pre-rotated diagonals, NTT domain
+    std::unique_ptr<ExactPlaintext> bias;   // [passes][N]: bias[R] on every slot that holds output row R, or null
+    double encode_s = 0;                    // wall time the constructor spent building and encoding the diagonals and the bias (device work included)
+    std::vector<uint32_t> baby_elts, giant_elts, fold_elts;
+    // per-layer scratch, reused by every apply() (one caller at a time).  Terms over Q P live on the key switcher's extended context.
+    std::unique_ptr<PolyBuffer> babies_qp, inner_qp, terms_qp, ksum_qp;
+    std::unique_ptr<Ciphertext> rot, fold;
+    std::vector<uint32_t> inner_elts;                            // element of inner sum (pass, i): 1 for i = 0, the giant step's otherwise
+    size_t tokens = 0;                                           // scratch capacity in tokens
+    void ensure_tokens(size_t T) {
+        if (T <= tokens) return;
+        const Context& ext = ks->extended_context();
+        babies_qp.reset(new PolyBuffer(ext, n1 * T, 2, true));                      // [n1][T]: P rot_j(x_t) + key-switching terms, NTT domain
+        inner_qp.reset(new PolyBuffer(ext, passes * n2 * T, 2, true));              // [passes * n2][T]
+        rot.reset(new Ciphertext(*ctx, 2, passes * n2 * T));                        // the inner sums, rotated by their giant step, divided by P
+        if (n2 > 1) {
+            terms_qp.reset(new PolyBuffer(ext, (n2 - 1) * T, 2, true));             // key inner products of one output ciphertext's giant steps
+            ksum_qp.reset(new PolyBuffer(ext, T, 2, true));
+        }
+        if (!fold_elts.empty()) fold.reset(new Ciphertext(*ctx, 2, 2 * T));         // [2][T]: running sums | their rotation
+        tokens = T;
+    }
+
+    // which output row a slot of pass `pass` holds (or npos)
+    size_t row_of_slot(size_t pass, size_t slot) const {
+        const size_t row = enc->row_size(), r = slot % row, rho = slot / row;
+        const size_t c = r / n + (tpc == 2 ? 0 : rho * (row / n));
+        const size_t b = replicate || m < n ? 0 : pass * copies + c;
+        const size_t R = b * m + r % m;
+        return R < out_dim ? R : (size_t)-1;
+    }
+};
+
+PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t d)
+    : PackedLinear(ctx, enc, ks, W, d, d) {
+    if (d < 2 || (d & (d - 1))) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: d must be a power of two dividing N/2");
+}
+
+PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext)
+    : PackedLinear(ctx, enc, ks, W, out_dim, in_dim, tokens_per_ciphertext, nullptr) {}
+
+PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext,
+                           const uint64_t* bias)
+    : impl_(new Impl) {
+    if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: one or two tokens per ciphertext");
+    const FheParams& p = ctx.params();
+    const size_t N = p.n(), L = p.n_limbs(), row = N / 2;
+    if (!W || out_dim == 0 || in_dim == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: empty matrix");
+    if (enc.slot_count() != N) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: encoder and context disagree on N");
+    auto pow2 = [](size_t v) { size_t x = 1; while (x < v) x <<= 1; return x; };
+    Impl& I = *impl_;
+    I.ctx = &ctx; I.enc = &enc; I.ks = &ks; I.out_dim = out_dim; I.in_dim = in_dim;
+    I.n = pow2(in_dim) < 2 ? 2 : pow2(in_dim);
+    if (I.n > row) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: in_dim (padded to a power of two) must be <= N/2");
+    I.tpc = tokens_per_ciphertext;
+    I.copies = (I.tpc == 2 ? row : N) / I.n;
+    const size_t mo = pow2(out_dim) < 2 ? 2 : pow2(out_dim);
+    I.m = mo < I.n ? mo : I.n;                                  // wide-input layer: only m wrapped diagonals, folded afterwards
+    I.blocks = (out_dim + I.m - 1) / I.m;
+    I.replicate = I.blocks == 1;
+    I.passes = I.replicate ? 1 : (I.blocks + I.copies - 1) / I.copies;
+    size_t n1 = 1;
+    while (n1 * n1 < I.m) n1 <<= 1;
+    // A hoisted baby step (gathers + key inner products, no transform) costs about a third of a giant step (Ld transforms per limb + its
+    // share of the inverse transform and the division by P), so the split leans towards baby steps: n1 = 2 sqrt(m) when m allows.
+    int shift = kBabyShiftDefault;
+    // (the split sweep behind this default: profiles/r03_bsgs_split_sweep.txt)
+    for (; shift > 0 && n1 * 2 < I.m; --shift) n1 <<= 1;
+    for (; shift < 0 && n1 > 2; ++shift) n1 >>= 1;
+    I.n1 = n1; I.n2 = I.m / n1;
+    const uint64_t t = enc.plain_modulus();
+    for (size_t j = 1; j < I.n1; ++j) I.baby_elts.push_back(enc.galois_element((int)j));
+    for (size_t i = 1; i < I.n2; ++i) I.giant_elts.push_back(enc.galois_element((int)(i * n1)));
+    for (size_t sft = I.m; sft < I.n; sft <<= 1) I.fold_elts.push_back(enc.galois_element((int)sft));
+    for (uint32_t g : I.baby_elts) ks.add_galois_element(g);
+    for (uint32_t g : I.giant_elts) ks.add_galois_element(g);
+    for (uint32_t g : I.fold_elts) ks.add_galois_element(g);
+    for (size_t i = 0; i < out_dim * in_dim; ++i)
+        if (W[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: weight >= plaintext modulus");
+    if (bias)
+        for (size_t i = 0; i < out_dim; ++i)
+            if (bias[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: bias >= plaintext modulus");
+
+    // Pre-rotated diagonals.  The product of giant step i lands on output slot r = r' - i n1 (row rotation), so position r' of
+    // diagonal (i, j) carries the weight of the output row that slot r holds and of input index (r + k) mod n, k = i n1 + j.
+    // They are multiplied with terms over Q P (the division by P comes after the sum), so they are encoded over all limbs of the
+    // key switcher's extended context.
+    const Context& ext = ks.extended_context();
+    const FheParams& pe = ext.params();
+    if (pe.log2_n != p.log2_n || pe.n_limbs() != L + 1 || !std::equal(p.moduli.begin(), p.moduli.end(), pe.moduli.begin()))
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: the key switcher was built for another context");
+    const size_t Le = L + 1;
+    I.diag.reset(new Plaintext(ext, I.passes * I.n2 * n1, /*is_ntt=*/false));
+    // the slot vectors are built here as 32-bit values and encoded on the device: inverse transform over Z_t, lift to the Le limbs and the forward
+    // transform, one call per giant step's n1 diagonals (the words BatchEncoder::encode + lift_signed + transform_to_ntt gave)
+    const auto encode_t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> slots(n1 * N);
+    void* stage = nullptr;
+    hip_check(hipSetDevice(ext.device_id()), "hipSetDevice");
+    hip_check(hipMalloc(&stage, slots.size() * sizeof(uint32_t)), "hipMalloc");
+    try {
+        for (size_t pass = 0; pass < I.passes; ++pass) {
+            for (size_t i = 0; i < I.n2; ++i) {
+                for (size_t j = 0; j < n1; ++j) {
+                    const size_t k = i * n1 + j;
+                    for (size_t rho = 0; rho < 2; ++rho)
+                        for (size_t rp = 0; rp < row; ++rp) {
+                            const size_t r = (rp + row - (i * n1) % row) % row;
+                            const size_t R = I.row_of_slot(pass, rho * row + r), col = (r + k) % I.n;
+                            slots[j * N + rho * row + rp] = (R != (size_t)-1 && col < in_dim) ? (uint32_t)W[R * in_dim + col] : 0u;
+                        }
+                }
+                // the copy is ordered behind the previous encode on the null stream; the host builds the next vectors while the device encodes these
+                uint32_t* d_slots = static_cast<uint32_t*>(stage);
+                hip_check(hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+                enc.encode_device_words(ext, d_slots, n1, I.diag->data() + ((pass * I.n2 + i) * n1) * Le * N, DPFHE_ENCODE_NTT, nullptr);
+            }
+        }
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    } catch (...) {
+        (void)hipFree(stage);
+        throw;
+    }
+    (void)hipFree(stage);
+    I.diag->set_ntt(true);
+    for (size_t pass = 0; pass < I.passes; ++pass) {
+        I.inner_elts.push_back(1u);
+        I.inner_elts.insert(I.inner_elts.end(), I.giant_elts.begin(), I.giant_elts.end());
+    }
+    // the bias: one slot vector per output ciphertext, in the layout the output itself has (row_of_slot - so also the replicated, folded and two-token ones)
+    if (bias) {
+        std::vector<uint32_t> bslots(I.passes * N);
+        for (size_t pass = 0; pass < I.passes; ++pass)
+            for (size_t sl = 0; sl < N; ++sl) {
+                const size_t R = I.row_of_slot(pass, sl);
+                bslots[pass * N + sl] = R != (size_t)-1 ? (uint32_t)bias[R] : 0u;
+            }
+        I.bias.reset(new ExactPlaintext(ctx, t, I.passes));
+        I.bias->set_slots_device(enc, bslots.data());
+    }
+    I.encode_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - encode_t0).count();
+    I.ensure_tokens(1);
+    ext.synchronize();
+}
+bool PackedLinear::has_bias() const { return impl_->bias != nullptr; }
+double PackedLinear::encode_seconds() const { return impl_->encode_s; }
+PackedLinear::~PackedLinear() = default;
+size_t PackedLinear::dim() const { return impl_->m; }
+size_t PackedLinear::in_dim() const { return impl_->in_dim; }
+size_t PackedLinear::out_dim() const { return impl_->out_dim; }
+size_t PackedLinear::input_period() const { return impl_->n; }
+size_t PackedLinear::output_ciphertexts() const { return impl_->passes; }
+size_t PackedLinear::baby_steps() const { return impl_->n1; }
+size_t PackedLinear::giant_steps() const { return impl_->n2; }
+size_t PackedLinear::key_switches_per_apply() const {
+    return impl_->baby_elts.size() + impl_->passes * impl_->giant_elts.size() + impl_->fold_elts.size();
+}
+
+void PackedLinear::pack_input(const uint64_t* x, uint64_t* slots) const {
+    const size_t N = impl_->enc->slot_count();
+    for (size_t s = 0; s < N; ++s) {
+        const size_t c = (s % (N / 2)) % impl_->n;
+        slots[s] = c < impl_->in_dim ? x[c] : 0;
+    }
+}
+size_t PackedLinear::tokens_per_ciphertext() const { return impl_->tpc; }
+void PackedLinear::pack_input_rows(const uint64_t* x0, const uint64_t* x1, uint64_t* slots) const {
+    const size_t N = impl_->enc->slot_count(), row = N / 2;
+    for (size_t s = 0; s < N; ++s) {
+        const size_t c = (s % row) % impl_->n;
+        slots[s] = c < impl_->in_dim ? (s < row ? x0[c] : x1[c]) : 0;
+    }
+}
+void PackedLinear::unpack_output_rows(const uint64_t* slots, uint64_t* y0, uint64_t* y1) const {
+    const size_t N = impl_->enc->slot_count(), row = N / 2;
+    for (size_t rho = 0; rho < 2; ++rho) {
+        std::vector<char> seen(impl_->out_dim, 0);
+        uint64_t* y = rho ? y1 : y0;
+        for (size_t pass = 0; pass < impl_->passes; ++pass)
+            for (size_t s = rho * row; s < (rho + 1) * row; ++s) {
+                const size_t R = impl_->row_of_slot(pass, s);
+                if (R != (size_t)-1 && !seen[R]) { y[R] = slots[pass * N + s]; seen[R] = 1; }
+            }
+    }
+}
+void PackedLinear::unpack_output(const uint64_t* slots, uint64_t* y) const {
+    const size_t N = impl_->enc->slot_count();
+    std::vector<char> seen(impl_->out_dim, 0);
+    for (size_t pass = 0; pass < impl_->passes; ++pass)
+        for (size_t s = 0; s < N; ++s) {
+            const size_t R = impl_->row_of_slot(pass, s);
+            if (R != (size_t)-1 && !seen[R]) { y[R] = slots[pass * N + s]; seen[R] = 1; }
+        }
+}
+
+void PackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
+    Impl& I = *impl_;
+    const size_t T = x.batch();
+    if (x.is_ntt() || x.size() != 2 || T == 0 || y.size() != 2 || y.batch() != I.passes * T)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear::apply: T 2-component coefficient-domain ciphertexts in, output_ciphertexts() * T out");
+    I.ensure_tokens(T);   // (re)allocates only when a larger batch than ever before arrives
+    const Context& ctx = *I.ctx;
+    const FheParams& p = ctx.params();
+    const size_t ct_words = 2 * p.n_limbs() * p.n(), n1 = I.n1, n2 = I.n2;
+    hipStream_t hs = static_cast<hipStream_t>(s);
+    dpfhe_ctx* h = handle_of(ctx);
+    dpfhe_ctx* he = handle_of(I.ks->extended_context());
+    // Layout of every intermediate: [rotation or diagonal index][token][component] - the token index sits where the plaintext
+    // matvec sees "more components", so keys and diagonals are read once for all tokens.
+    // baby steps: P rot_j(x_t) + key-switching term, j < n1, all tokens, ONE hoisted pass; they stay in the NTT domain over Q P
+    I.ks->rotate_hoisted_qp(x, 0, T, I.baby_elts, *I.babies_qp, 0, s);
+    // inner sums of all giant steps of all output ciphertexts of all tokens: ONE matrix-vector product over the pre-rotated diagonals
+    check(dpfhe_matvec_plain_multi(he, I.inner_qp->data(), I.diag->data(), I.babies_qp->data(), I.passes * n2, n1, T, s), "dpfhe_matvec_plain_multi");
+    // back to the coefficient domain, the giant step's automorphism applied by the transform's loads; then the ONE division by P
+    // the baby steps and the plaintext products share
+    check(dpfhe_ntt_inv_galois(he, I.inner_qp->data(), I.inner_qp->data(), T * 2, I.inner_elts.data(), I.passes * n2, s), "dpfhe_ntt_inv_galois");
+    Ciphertext& rot = *I.rot;
+    check(dpfhe_rescale(he, rot.data(), I.inner_qp->data(), I.passes * n2 * T * 2, s), "dpfhe_rescale");
+    rot.set_ntt(false);
+    // giant steps: key inner products of the rotated inner sums (i >= 1), summed over Q P; one inverse transform and one
+    // division by P per output ciphertext, which also adds the c0 parts and the un-rotated inner sum
+    uint64_t* sums = I.fold_elts.empty() ? y.data() : I.fold->data();   // wide-input layer: the block sum is folded below before it becomes y
+    if (n2 > 1) {
+        for (size_t pass = 0; pass < I.passes; ++pass) {
+            const size_t base = pass * n2 * T;
+            I.ks->switch_key_qp(rot, base + T, I.giant_elts, T, *I.terms_qp, 0, s);
+            check(dpfhe_reduce_sum(he, I.ksum_qp->data(), I.terms_qp->data(), n2 - 1, 2 * T, s), "dpfhe_reduce_sum");
+            check(dpfhe_ntt_inv(he, I.ksum_qp->data(), T * 2, s), "dpfhe_ntt_inv");
+            check(dpfhe_rescale_bsgs(he, sums + pass * T * ct_words, I.ksum_qp->data(), rot.data() + base * ct_words, n2, T, s), "dpfhe_rescale_bsgs");
+        }
+    } else {
+        hip_check(hipMemcpyAsync(sums, rot.data(), I.passes * T * ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, hs), "hipMemcpyAsync");
+    }
+    // wide input (m < n): slot r holds the partial sum over input indices congruent to r + k; fold the n/m windows together
+    if (!I.fold_elts.empty()) {
+        Ciphertext& f = *I.fold;   // items [0, T): running sums, [T, 2T): their rotation
+        f.set_ntt(false);
+        for (size_t e = 0; e < I.fold_elts.size(); ++e) {
+            const std::vector<uint32_t> one(1, I.fold_elts[e]);
+            I.ks->apply_galois_grouped(f, 0, one, T, f, T, s);
+            const bool last = e + 1 == I.fold_elts.size();
+            check(dpfhe_add(h, last ? y.data() : f.data(), f.data(), f.data() + T * ct_words, 2 * T, s), "dpfhe_add");
+        }
+    }
+    // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
+    if (I.bias)
+        check(dpfhe_add_plain_scaled(h, y.data(), y.data(), I.bias->data(), I.passes * T, 2, I.passes, I.bias->plain_modulus(), 0, s), "dpfhe_add_plain_scaled");
+    y.set_ntt(false);
+    // enqueue only: the scratch belongs to the layer, the caller synchronises (Context::synchronize) before reading y
+}
+
+// ---- N3: hand-over between packed layers and the transformer block's linear skeleton ------------------------------------------
+class PackedSelect::Impl {
+public:
+    const Context* ctx = nullptr;
+    HybridKeySwitcher* ks = nullptr;
+    size_t offset = 0, tpc = 1;
+    uint32_t shift_elt = 0, swap_elt = 0;
+    std::vector<uint32_t> spread_elts;          // right rotations by period, 2 period, ... up to half a slot row
+    std::unique_ptr<Plaintext> mask;            // NTT domain: 1 on slots [0, length) of row 0, 0 elsewhere
+    std::unique_ptr<Ciphertext> a, b;           // scratch, T items each
+    size_t tokens = 0;
+    void ensure(size_t T) {
+        if (T <= tokens) return;
+        a.reset(new Ciphertext(*ctx, 2, T));
+        b.reset(new Ciphertext(*ctx, 2, T));
+        tokens = T;
+    }
+};
+
+PackedSelect::PackedSelect(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, size_t offset, size_t length, size_t period, size_t tokens_per_ciphertext) : impl_(new Impl) {
+    if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedSelect: one or two tokens per ciphertext");
+    const FheParams& p = ctx.params();
+    const size_t N = p.n(), row = N / 2, L = p.n_limbs();
+    if (enc.slot_count() != N || length == 0 || period < length || (period & (period - 1)) || period > row || offset + length > row)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedSelect: slice of slot row 0, period a power of two in [length, N/2]");
+    Impl& I = *impl_;
+    I.ctx = &ctx; I.ks = &ks; I.offset = offset; I.tpc = tokens_per_ciphertext;
+    if (offset) { I.shift_elt = enc.galois_element((int)offset); ks.add_galois_element(I.shift_elt); }
+    for (size_t sft = period; sft < row; sft <<= 1) { I.spread_elts.push_back(enc.galois_element(-(int)sft)); ks.add_galois_element(I.spread_elts.back()); }
+    I.swap_elt = (uint32_t)(2 * N - 1);
+    if (I.tpc == 1) ks.add_galois_element(I.swap_elt);
+    std::vector<uint32_t> slots(N, 0);
+    for (size_t i = 0; i < length; ++i) { slots[i] = 1; if (I.tpc == 2) slots[row + i] = 1; }   // (two tokens: the same slice of row 1)
+    I.mask.reset(new Plaintext(ctx, 1, false));
+    enc.encode_device(slots.data(), 1, *I.mask, /*to_ntt=*/true);
+    I.ensure(1);
+    ctx.synchronize();
+}
+PackedSelect::~PackedSelect() = default;
+size_t PackedSelect::key_switches_per_apply() const { return (impl_->offset ? 1 : 0) + impl_->spread_elts.size() + (impl_->tpc == 1 ? 1 : 0); }
+
+void PackedSelect::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
+    Impl& I = *impl_;
+    const size_t T = x.batch();
+    if (x.is_ntt() || x.size() != 2 || y.size() != 2 || y.batch() != T || T == 0)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedSelect::apply: T 2-component coefficient-domain ciphertexts in and out");
+    I.ensure(T);
+    dpfhe_ctx* h = handle_of(*I.ctx);
+    Ciphertext &a = *I.a, &b = *I.b;
+    const Ciphertext* cur = &x;
+    if (I.offset) {   // slot offset + i -> slot i
+        I.ks->apply_galois_grouped(x, 0, std::vector<uint32_t>(1, I.shift_elt), T, a, 0, s);
+        cur = &a;
+    }
+    // mask: NTT, every polynomial times the (broadcast) mask in one launch, back
+    check(dpfhe_ntt_fwd_oop(h, b.data(), cur->data(), T * 2, s), "dpfhe_ntt_fwd_oop");
+    check(dpfhe_multiply_plain(h, b.data(), b.data(), I.mask->data(), T * 2, s), "dpfhe_multiply_plain");
+    check(dpfhe_ntt_inv(h, b.data(), T * 2, s), "dpfhe_ntt_inv");
+    b.set_ntt(false);
+    // spread along the row: b += rot(b, -period), then -2 period, ...; then the other row
+    Ciphertext* have = &b;
+    Ciphertext* tmp = &a;
+    auto rotate_add = [&](uint32_t g, Ciphertext& out) {
+        I.ks->apply_galois_grouped(*have, 0, std::vector<uint32_t>(1, g), T, *tmp, 0, s);
+        check(dpfhe_add(h, out.data(), have->data(), tmp->data(), T * 2, s), "dpfhe_add");
+        out.set_ntt(false);
+    };
+    if (I.tpc == 1) {
+        for (uint32_t g : I.spread_elts) rotate_add(g, *have);
+        rotate_add(I.swap_elt, y);
+    } else {   // two tokens per ciphertext: every row keeps its own token - spread inside the rows only, the last step writes y
+        const FheParams& p = I.ctx->params();
+        if (I.spread_elts.empty()) {
+            hip_check(hipMemcpyAsync(y.data(), have->data(), T * 2 * p.n_limbs() * p.n() * sizeof(uint64_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)), "hipMemcpyAsync");
+            y.set_ntt(false);
+        } else {
+            for (size_t i = 0; i + 1 < I.spread_elts.size(); ++i) rotate_add(I.spread_elts[i], *have);
+            rotate_add(I.spread_elts.back(), y);
+        }
+    }
+}
+
+class PackedTransformerBlock::Impl {
+public:
+    const Context* ctx = nullptr;
+    HybridKeySwitcher* ks = nullptr;
+    size_t d = 0, h = 0;
+    std::unique_ptr<PackedLinear> qkv, proj, up, down;
+    std::unique_ptr<PackedSelect> take_v;
+    std::unique_ptr<Ciphertext> st[5], o, u, us, dn;   // stages + scratch, T items each
+    size_t tokens = 0;
+    void ensure(size_t T) {
+        if (T <= tokens) return;
+        for (auto& c : st) c.reset(new Ciphertext(*ctx, 2, T));
+        o.reset(new Ciphertext(*ctx, 2, T)); u.reset(new Ciphertext(*ctx, 2, T)); us.reset(new Ciphertext(*ctx, 2, T)); dn.reset(new Ciphertext(*ctx, 2, T));
+        tokens = T;
+    }
+};
+
+PackedTransformerBlock::PackedTransformerBlock(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
+                                               const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h)
+    : PackedTransformerBlock(ctx, enc, ks, W_qkv, W_o, W_up, W_down, d, h, nullptr, nullptr, nullptr, nullptr) {}
+
+PackedTransformerBlock::PackedTransformerBlock(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W_qkv, const uint64_t* W_o,
+                                               const uint64_t* W_up, const uint64_t* W_down, size_t d, size_t h, const uint64_t* b_qkv, const uint64_t* b_o,
+                                               const uint64_t* b_up, const uint64_t* b_down) : impl_(new Impl) {
+    if (!W_qkv || !W_o || !W_up || !W_down || d == 0 || h == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedTransformerBlock: null or empty matrix");
+    Impl& I = *impl_;
+    I.ctx = &ctx; I.ks = &ks; I.d = d; I.h = h;
+    // the biases ride on the layers: b_v reaches `a` through the PackedSelect of the v third, b_up enters W_down's input with W_up h1
+    I.qkv.reset(new PackedLinear(ctx, enc, ks, W_qkv, 3 * d, d, 1, b_qkv));
+    I.proj.reset(new PackedLinear(ctx, enc, ks, W_o, d, d, 1, b_o));
+    I.up.reset(new PackedLinear(ctx, enc, ks, W_up, h, d, 1, b_up));
+    I.down.reset(new PackedLinear(ctx, enc, ks, W_down, d, h, 1, b_down));
+    const size_t row = ctx.params().n() / 2;
+    // the hand-overs below rely on: one output ciphertext per layer, outputs of the wide layers at slot r of row 0 (out >= period),
+    // and W_down consuming a vector that fills a whole slot row
+    if (I.qkv->output_ciphertexts() != 1 || I.up->output_ciphertexts() != 1 || I.down->output_ciphertexts() != 1 || I.proj->output_ciphertexts() != 1 ||
+        3 * d < I.qkv->input_period() || 3 * d > row || h < I.up->input_period() || I.down->input_period() != row || I.proj->input_period() != I.qkv->input_period())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedTransformerBlock: needs 3 d <= N/2, h >= the padded d and the padded h = N/2 (GPT-2 small at N = 8192: d = 768, h = 3072)");
+    I.take_v.reset(new PackedSelect(ctx, enc, ks, 2 * d, d, I.proj->input_period()));
+    ks.add_galois_element((uint32_t)(2 * ctx.params().n() - 1));
+    I.ensure(1);
+}
+PackedTransformerBlock::~PackedTransformerBlock() = default;
+size_t PackedTransformerBlock::hidden() const { return impl_->d; }
+size_t PackedTransformerBlock::inner() const { return impl_->h; }
+size_t PackedTransformerBlock::key_switches_per_token() const {
+    const Impl& I = *impl_;
+    return I.qkv->key_switches_per_apply() + I.take_v->key_switches_per_apply() + I.proj->key_switches_per_apply() + I.up->key_switches_per_apply() + 1 +
+           I.down->key_switches_per_apply();
+}
+void PackedTransformerBlock::pack_input(const uint64_t* x, uint64_t* slots) const { impl_->qkv->pack_input(x, slots); }
+void PackedTransformerBlock::unpack_output(const uint64_t* slots, uint64_t* y) const { impl_->down->unpack_output(slots, y); }
+const Ciphertext& PackedTransformerBlock::stage(int index) const {
+    if (index < 0 || index > 4 || !impl_->st[index]) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedTransformerBlock::stage: index in [0, 4]");
+    return *impl_->st[index];
+}
+
+void PackedTransformerBlock::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
+    Impl& I = *impl_;
+    const size_t T = x.batch();
+    if (x.is_ntt() || x.size() != 2 || y.size() != 2 || y.batch() != T || T == 0)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedTransformerBlock::apply: T 2-component coefficient-domain ciphertexts in and out");
+    I.ensure(T);
+    dpfhe_ctx* h = handle_of(*I.ctx);
+    const FheParams& p = I.ctx->params();
+    const size_t words = T * 2 * p.n_limbs() * p.n();
+    Ciphertext &qkv = *I.st[0], &a = *I.st[1], &h1 = *I.st[2], &u2 = *I.st[3], &h2 = *I.st[4];
+    I.qkv->apply(x, qkv, s);                                   // q | k | v at slots 0 .. 3d-1 of row 0 (gpt_model.cpp:793)
+    I.take_v->apply(qkv, a, s);                                // attention over one position: the output is v; re-packed as a layer input
+    I.proj->apply(a, *I.o, s);                                 // attention-output projection
+    check(dpfhe_add(h, h1.data(), x.data(), I.o->data(), T * 2, s), "dpfhe_add");   // residual
+    h1.set_ntt(false);
+    I.up->apply(h1, *I.u, s);                                  // FFN up (gpt_model.cpp:848): outputs at slot r of row 0
+    I.ks->apply_galois_grouped(*I.u, 0, std::vector<uint32_t>(1, (uint32_t)(2 * p.n() - 1)), T, *I.us, 0, s);   // row swap
+    check(dpfhe_add(h, u2.data(), I.u->data(), I.us->data(), T * 2, s), "dpfhe_add");                          // both rows: W_down's input packing
+    u2.set_ntt(false);
+    I.down->apply(u2, *I.dn, s);                               // FFN down
+    check(dpfhe_add(h, h2.data(), h1.data(), I.dn->data(), T * 2, s), "dpfhe_add");   // residual
+    h2.set_ntt(false);
+    hip_check(hipMemcpyAsync(y.data(), h2.data(), words * sizeof(uint64_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(s)), "hipMemcpyAsync");
+    y.set_ntt(false);
+}
+
+}  // namespace fhe
+}  // namespace deeppowers

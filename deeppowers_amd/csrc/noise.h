@@ -1,7 +1,7 @@
 // noise.h - secret-seeded noise polynomials for re-randomising result ciphertexts: noise(seed, item, stream_id, kind, param).
 //
 //   A polynomial of N SIGNED INTEGERS v_k; every limb holds the same integer as its canonical residue v_k mod q_limb in [0, q_limb).
-//   Coefficient k takes the ChaCha20 block (RFC 8439 section 2.3, chacha20_block of expand.h) with key = the 32-byte seed, block counter k >> 1 and
+//   Coefficient k takes the ChaCha20 block (RFC 8439 section 2.3, chacha20_block of chacha20.h) with key = the 32-byte seed, block counter k >> 1 and
 //   nonce (item, stream_id, 0x6b73616d), and of it the output words 8 (k & 1) .. 8 (k & 1) + 7 read as ONE 256-bit little-endian integer X.
 //   The third nonce word keeps these streams apart from expand(seed, item, limb, component) (component < 3) even under a misused common seed.
 //     kind 0, ternary:            v = floor(3 (X mod 2^64) / 2^64) - 1           (bias at most 2^-63 per coefficient, no rejection)
