@@ -32,6 +32,12 @@
  *     state they neither allocate nor synchronise.  dpfhe_ctx_create (uploads the tables: one allocation, one copy, no kernel), dpfhe_ctx_autotune
  *     (times kernels on caller scratch) and dpfhe_comm_create are set-up calls: they may allocate and synchronise.  After set-up a dpfhe_ctx is immutable: concurrent calls from different host threads on
  *     different streams are allowed.
+ *   - digits: wherever a formula below writes [c]_{q_j} (key switching, relinearisation, the hoisted rotations), it means limb j of c taken as it
+ *     is stored - every word read as the integer in [0, q_j), NOT centred on zero - and that integer polynomial reduced modulo each limb of the
+ *     context it is then multiplied on ("lift").  A centred digit would differ by q_j in the words above q_j / 2 and give other output words.
+ *   - rounding: every round(x / D) below divides by a product D of odd primes, so x / D is never a half-integer and no tie rule is involved:
+ *     round(x / D) = floor((2 x + D) / (2 D)).  Where the result is only kept modulo limbs that divide Q / D (dpfhe_rescale, the hybrid entries'
+ *     division by P, dpfhe_scale_round) it does not depend on whether x is read centred or in [0, Q): the two readings differ by a multiple of Q / D.
  *   - No C++ types and no exceptions cross this boundary.
  */
 #ifndef DPFHE_H
