@@ -67,6 +67,9 @@ SYMBOLS = {
     "dpfhe_add_plain_scaled": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_int, C.c_void_p], C.c_int),
     "dpfhe_add_plain_scaled_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                      C.c_uint64, C.c_int], C.c_int),
+    "dpfhe_add_plain": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p], C.c_int),
+    "dpfhe_add_plain_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                              C.c_int], C.c_int),
     "dpfhe_compact": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_compact_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32], C.c_int),
     "dpfhe_encoder_create": ([C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64], C.c_int),

@@ -1589,6 +1589,47 @@ extern "C" int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_li
     });
 }
 
+// plaintext addition on residues (plain_add.h, k_plain_add.hip): c0 +- p mod q_l, p [plain_items][L][N] canonical words of the ciphertext's domain
+// the shape checks the device entry and the host twin share; `limbs` and `log2n` are the ring's
+static int add_plain_args(const char* what, const uint64_t* out, const uint64_t* in, const uint64_t* plain, size_t batch, size_t comps, size_t plain_items,
+                          uint32_t limbs, uint32_t log2n) {
+    if (!out || !in || !plain) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer");
+    if (comps != 2 && comps != 3) return fail(DPFHE_INVALID_ARGUMENT, what, "ciphertexts have 2 or 3 components");
+    if (batch == 0 || plain_items == 0 || batch % plain_items) return fail(DPFHE_INVALID_ARGUMENT, what, "batch must be a positive multiple of plain_items");
+    if (batch > (kMaxGrid >> (log2n > 9 ? log2n - 9 : 0))) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    const size_t poly = (size_t)limbs << log2n, words = batch * comps * poly;
+    if (out != in && overlaps(out, words, in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap without being the same buffer");
+    if (overlaps(out, words, plain, plain_items * poly)) return fail(DPFHE_INVALID_ARGUMENT, what, "out overlaps the plaintext");
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_add_plain(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in, const uint64_t* d_plain, size_t batch, size_t comps, size_t plain_items,
+                               int negate, void* stream) {
+    static const char* what = "dpfhe_add_plain";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (int rc = add_plain_args(what, d_out, d_in, d_plain, batch, comps, plain_items, c->n_limbs, c->log2n)) return rc;
+    if (misaligned(d_out) || misaligned(d_in) || misaligned(d_plain)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    DPFHE_ON_DEVICE(c, what);
+    if (launch_add_plain((int)c->log2n, d_out, d_in, d_plain, batch, (u32)comps, c->n_limbs, batch / plain_items, negate != 0, c->lc,
+                         static_cast<hipStream_t>(stream)))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    return check_launch("add_plain kernel launch");
+}
+
+extern "C" int dpfhe_add_plain_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
+                                    size_t batch, size_t comps, size_t plain_items, int negate) {
+    static const char* what = "dpfhe_add_plain_host";
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, what, "null moduli");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (int rc = add_plain_args(what, out, in, plain, batch, comps, plain_items, n_limbs, log2_n)) return rc;
+    const size_t n = (size_t)1 << log2_n;
+    for (size_t i = 0; i < plain_items * n_limbs; ++i)
+        for (size_t k = 0; k < n; ++k)
+            if (plain[i * n + k] >= moduli[i % n_limbs]) return fail(DPFHE_INVALID_ARGUMENT, what, "plaintext words must be canonical residues");
+    add_plain_host((int)log2_n, moduli, n_limbs, out, in, plain, batch, (u32)comps, batch / plain_items, negate != 0);
+    return DPFHE_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------------
 // compact result ciphertexts (compact.h, k_compact.hip): round(2^k X / Q) mod 2^k per component, bit-packed
 // validates the widths and limb count, then fills every constant; the moduli must be pairwise coprime (their inverses exist)

@@ -538,7 +538,26 @@ void add_plain_exact_impl(const Context& ctx, const Ciphertext& in, const ExactP
           "dpfhe_add_plain_scaled");
     out.set_ntt(false);
 }
+void add_plain_impl(const Context& ctx, const Ciphertext& in, const Plaintext& p, Ciphertext& out, bool negate, Stream* s, const char* what) {
+    const FheParams& fp = ctx.params();
+    const size_t poly = fp.n_limbs() * fp.n();
+    if ((in.size() != 2 && in.size() != 3) || in.batch() == 0 || in.words() != in.batch() * in.size() * poly)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": input must be a 2- or 3-component ciphertext of this context");
+    if (out.size() != in.size() || out.batch() != in.batch() || out.words() != in.words())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output shape differs");
+    if (p.batch() == 0 || p.words() != p.batch() * poly || in.batch() % p.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": plaintext of another context, or a batch that is not a multiple of its items");
+    if (in.is_ntt() != p.is_ntt()) throw Exception(ErrorCode::INVALID_STATE, std::string(what) + ": ciphertext and plaintext are in different domains");
+    check(dpfhe_add_plain(handle_of(ctx), out.data(), in.data(), p.data(), in.batch(), in.size(), p.batch(), negate ? 1 : 0, s), "dpfhe_add_plain");
+    out.set_ntt(in.is_ntt());
+}
 }  // namespace
+void Evaluator::add_plain(const Ciphertext& in, const Plaintext& p, Ciphertext& out, Stream* s) const {
+    add_plain_impl(*impl_->ctx, in, p, out, false, s, "add_plain");
+}
+void Evaluator::sub_plain(const Ciphertext& in, const Plaintext& p, Ciphertext& out, Stream* s) const {
+    add_plain_impl(*impl_->ctx, in, p, out, true, s, "sub_plain");
+}
 void Evaluator::add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* s) const {
     add_plain_exact_impl(*impl_->ctx, in, p, out, false, s, "add_plain_exact");
 }

@@ -1,6 +1,8 @@
-// fhe_packed.cpp - the facade's packed encrypted layers over the slot encoding and the hybrid key switcher: PackedLinear, PackedSelect,
-// PackedTransformerBlock.  Part of libdpfhe_api.so (fhe_api.cpp names the other units).
+// fhe_packed.cpp - the facade's packed encrypted layers over the slot encodings and the hybrid key switcher: PackedLinear, ApproxPackedLinear,
+// PackedSelect, PackedTransformerBlock.  Part of libdpfhe_api.so (fhe_api.cpp names the other units).
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 
 #include "fhe_internal.h"
 
@@ -12,29 +14,78 @@ using namespace detail;
 // ---- N3: packed matrix-vector product (diagonal method, baby-step / giant-step) -------------------------------------------
 constexpr int kBabyShiftDefault = 1;
 
-class PackedLinear::Impl {
-public:
+namespace {
+
+// What the exact and the approximate layer share: the geometry of the diagonal method on slot rows of N / 2 slots, its rotation keys, the per-layer
+// scratch and the body of apply() up to the level-L result - nothing in it depends on the plaintext space; only the encoding of the diagonals and of
+// the bias does, and that stays with the two classes.
+struct PackedCore {
     const Context* ctx = nullptr;
-    const BatchEncoder* enc = nullptr;
     HybridKeySwitcher* ks = nullptr;
     size_t out_dim = 0, in_dim = 0;
+    size_t row = 0;      // slots per slot row, N / 2
+    size_t rows = 2;     // slot rows of the encoding: 2 over Z_t, 1 for complex slots
     size_t n = 0;        // input period: the input vector repeats every n slots of a row (power of two >= in_dim)
     size_t m = 0;        // diagonals per pass = output period (n, or the padded out_dim of a wide-input layer)
-    size_t tpc = 1;      // tokens per ciphertext: 2 = the two slot rows carry two tokens (the windows of ONE row share the output blocks)
-    size_t copies = 0;   // independent n-slot windows that share the output blocks = N / n (tpc = 2: of one row, N / 2 / n)
+    size_t tpc = 1;      // tokens per ciphertext: 2 = the two slot rows (complex slots: the real and imaginary parts) carry two tokens
+    size_t copies = 0;   // independent n-slot windows that share the output blocks: rows * N / 2 / n, or those of ONE row when each row has its own token
     size_t blocks = 0;   // output row blocks of m rows
     size_t passes = 0;   // output ciphertexts
     bool replicate = false;   // one block: every window computes it (the output is again a periodic vector)
     size_t n1 = 0, n2 = 0;
     std::unique_ptr<Plaintext> diag;   // [passes][n2][n1] pre-rotated diagonals, NTT domain
-    std::unique_ptr<ExactPlaintext> bias;   // [passes][N]: bias[R] on every slot that holds output row R, or null
-    double encode_s = 0;                    // wall time the constructor spent building and encoding the diagonals and the bias (device work included)
     std::vector<uint32_t> baby_elts, giant_elts, fold_elts;
     // per-layer scratch, reused by every apply() (one caller at a time).  Terms over Q P live on the key switcher's extended context.
     std::unique_ptr<PolyBuffer> babies_qp, inner_qp, terms_qp, ksum_qp;
     std::unique_ptr<Ciphertext> rot, fold;
     std::vector<uint32_t> inner_elts;                            // element of inner sum (pass, i): 1 for i = 0, the giant step's otherwise
     size_t tokens = 0;                                           // scratch capacity in tokens
+
+    // the split, the Galois elements (added to `ks` in the order baby, giant, fold) and the check that `ks` extends `ctx`; `galois(s)` = 3^s mod 2N
+    template <class Galois>
+    void plan(const char* who, const Context& c, HybridKeySwitcher& k, size_t out_d, size_t in_d, size_t slot_rows, size_t tokens_per_ciphertext, Galois galois) {
+        const std::string name(who);
+        if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, name + ": one or two tokens per ciphertext");
+        if (out_d == 0 || in_d == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, name + ": empty matrix");
+        auto pow2 = [](size_t v) { size_t x = 1; while (x < v) x <<= 1; return x; };
+        ctx = &c; ks = &k; out_dim = out_d; in_dim = in_d;
+        row = c.params().n() / 2; rows = slot_rows;
+        n = pow2(in_dim) < 2 ? 2 : pow2(in_dim);
+        if (n > row) throw Exception(ErrorCode::INVALID_ARGUMENT, name + ": in_dim (padded to a power of two) must be <= N/2");
+        tpc = tokens_per_ciphertext;
+        copies = (tpc == 2 ? row : rows * row) / n;
+        const size_t mo = pow2(out_dim) < 2 ? 2 : pow2(out_dim);
+        m = mo < n ? mo : n;                                    // wide-input layer: only m wrapped diagonals, folded afterwards
+        blocks = (out_dim + m - 1) / m;
+        replicate = blocks == 1;
+        passes = replicate ? 1 : (blocks + copies - 1) / copies;
+        size_t b = 1;
+        while (b * b < m) b <<= 1;
+        // A hoisted baby step (gathers + key inner products, no transform) costs about a third of a giant step (Ld transforms per limb + its
+        // share of the inverse transform and the division by P), so the split leans towards baby steps: n1 = 2 sqrt(m) when m allows.
+        int shift = kBabyShiftDefault;
+        // (the split sweep behind this default: profiles/r03_bsgs_split_sweep.txt)
+        for (; shift > 0 && b * 2 < m; --shift) b <<= 1;
+        for (; shift < 0 && b > 2; ++shift) b >>= 1;
+        n1 = b; n2 = m / n1;
+        for (size_t j = 1; j < n1; ++j) baby_elts.push_back(galois((int)j));
+        for (size_t i = 1; i < n2; ++i) giant_elts.push_back(galois((int)(i * n1)));
+        for (size_t sft = m; sft < n; sft <<= 1) fold_elts.push_back(galois((int)sft));
+        for (uint32_t g : baby_elts) k.add_galois_element(g);
+        for (uint32_t g : giant_elts) k.add_galois_element(g);
+        for (uint32_t g : fold_elts) k.add_galois_element(g);
+        const FheParams &p = c.params(), &pe = k.extended_context().params();
+        if (pe.log2_n != p.log2_n || pe.n_limbs() != p.n_limbs() + 1 || !std::equal(p.moduli.begin(), p.moduli.end(), pe.moduli.begin()))
+            throw Exception(ErrorCode::INVALID_ARGUMENT, name + ": the key switcher was built for another context");
+    }
+    // after the diagonals: the inner sums' elements
+    void finish_plan() {
+        for (size_t pass = 0; pass < passes; ++pass) {
+            inner_elts.push_back(1u);
+            inner_elts.insert(inner_elts.end(), giant_elts.begin(), giant_elts.end());
+        }
+    }
+
     void ensure_tokens(size_t T) {
         if (T <= tokens) return;
         const Context& ext = ks->extended_context();
@@ -49,14 +100,79 @@ public:
         tokens = T;
     }
 
-    // which output row a slot of pass `pass` holds (or npos)
+    // which output row a slot of pass `pass` holds (or npos); slot < rows * N / 2
     size_t row_of_slot(size_t pass, size_t slot) const {
-        const size_t row = enc->row_size(), r = slot % row, rho = slot / row;
+        const size_t r = slot % row, rho = slot / row;
         const size_t c = r / n + (tpc == 2 ? 0 : rho * (row / n));
         const size_t b = replicate || m < n ? 0 : pass * copies + c;
         const size_t R = b * m + r % m;
         return R < out_dim ? R : (size_t)-1;
     }
+    // Pre-rotated diagonals.  The product of giant step i lands on output slot r = r' - i n1 (row rotation), so position r' of
+    // diagonal (i, j) carries the weight of the output row that slot r holds and of input index (r + k) mod n, k = i n1 + j.
+    // -> the index into W of what slot `slot` (position r' of its row) of that diagonal holds, or npos for a zero
+    size_t diag_weight(size_t pass, size_t i, size_t j, size_t slot) const {
+        const size_t rho = slot / row, rp = slot % row, k = i * n1 + j;
+        const size_t r = (rp + row - (i * n1) % row) % row;
+        const size_t R = row_of_slot(pass, rho * row + r), col = (r + k) % n;
+        return (R != (size_t)-1 && col < in_dim) ? R * in_dim + col : (size_t)-1;
+    }
+
+    // x: T items on ctx -> sums: passes * T items on ctx (output ciphertext o of token t at item o * T + t), 2 components, coefficient domain, L limbs
+    void run(const Ciphertext& x, uint64_t* y, Stream* s) {
+        const size_t T = x.batch();
+        const FheParams& p = ctx->params();
+        const size_t ct_words = 2 * p.n_limbs() * p.n();
+        hipStream_t hs = static_cast<hipStream_t>(s);
+        dpfhe_ctx* h = handle_of(*ctx);
+        dpfhe_ctx* he = handle_of(ks->extended_context());
+        // Layout of every intermediate: [rotation or diagonal index][token][component] - the token index sits where the plaintext
+        // matvec sees "more components", so keys and diagonals are read once for all tokens.
+        // baby steps: P rot_j(x_t) + key-switching term, j < n1, all tokens, ONE hoisted pass; they stay in the NTT domain over Q P
+        ks->rotate_hoisted_qp(x, 0, T, baby_elts, *babies_qp, 0, s);
+        // inner sums of all giant steps of all output ciphertexts of all tokens: ONE matrix-vector product over the pre-rotated diagonals
+        check(dpfhe_matvec_plain_multi(he, inner_qp->data(), diag->data(), babies_qp->data(), passes * n2, n1, T, s), "dpfhe_matvec_plain_multi");
+        // back to the coefficient domain, the giant step's automorphism applied by the transform's loads; then the ONE division by P
+        // the baby steps and the plaintext products share
+        check(dpfhe_ntt_inv_galois(he, inner_qp->data(), inner_qp->data(), T * 2, inner_elts.data(), passes * n2, s), "dpfhe_ntt_inv_galois");
+        Ciphertext& rt = *rot;
+        check(dpfhe_rescale(he, rt.data(), inner_qp->data(), passes * n2 * T * 2, s), "dpfhe_rescale");
+        rt.set_ntt(false);
+        // giant steps: key inner products of the rotated inner sums (i >= 1), summed over Q P; one inverse transform and one
+        // division by P per output ciphertext, which also adds the c0 parts and the un-rotated inner sum
+        uint64_t* sums = fold_elts.empty() ? y : fold->data();   // wide-input layer: the block sum is folded below before it becomes y
+        if (n2 > 1) {
+            for (size_t pass = 0; pass < passes; ++pass) {
+                const size_t base = pass * n2 * T;
+                ks->switch_key_qp(rt, base + T, giant_elts, T, *terms_qp, 0, s);
+                check(dpfhe_reduce_sum(he, ksum_qp->data(), terms_qp->data(), n2 - 1, 2 * T, s), "dpfhe_reduce_sum");
+                check(dpfhe_ntt_inv(he, ksum_qp->data(), T * 2, s), "dpfhe_ntt_inv");
+                check(dpfhe_rescale_bsgs(he, sums + pass * T * ct_words, ksum_qp->data(), rt.data() + base * ct_words, n2, T, s), "dpfhe_rescale_bsgs");
+            }
+        } else {
+            hip_check(hipMemcpyAsync(sums, rt.data(), passes * T * ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, hs), "hipMemcpyAsync");
+        }
+        // wide input (m < n): slot r holds the partial sum over input indices congruent to r + k; fold the n/m windows together
+        if (!fold_elts.empty()) {
+            Ciphertext& f = *fold;   // items [0, T): running sums, [T, 2T): their rotation
+            f.set_ntt(false);
+            for (size_t e = 0; e < fold_elts.size(); ++e) {
+                const std::vector<uint32_t> one(1, fold_elts[e]);
+                ks->apply_galois_grouped(f, 0, one, T, f, T, s);
+                const bool last = e + 1 == fold_elts.size();
+                check(dpfhe_add(h, last ? y : f.data(), f.data(), f.data() + T * ct_words, 2 * T, s), "dpfhe_add");
+            }
+        }
+    }
+};
+
+}  // namespace
+
+class PackedLinear::Impl : public PackedCore {
+public:
+    const BatchEncoder* enc = nullptr;
+    std::unique_ptr<ExactPlaintext> bias;   // [passes][N]: bias[R] on every slot that holds output row R, or null
+    double encode_s = 0;                    // wall time the constructor spent building and encoding the diagonals and the bias (device work included)
 };
 
 PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t d)
@@ -70,53 +186,26 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
 PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext,
                            const uint64_t* bias)
     : impl_(new Impl) {
-    if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: one or two tokens per ciphertext");
     const FheParams& p = ctx.params();
-    const size_t N = p.n(), L = p.n_limbs(), row = N / 2;
-    if (!W || out_dim == 0 || in_dim == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: empty matrix");
+    const size_t N = p.n(), L = p.n_limbs();
+    if (!W) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: empty matrix");
+    if (tokens_per_ciphertext != 1 && tokens_per_ciphertext != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: one or two tokens per ciphertext");
     if (enc.slot_count() != N) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: encoder and context disagree on N");
-    auto pow2 = [](size_t v) { size_t x = 1; while (x < v) x <<= 1; return x; };
     Impl& I = *impl_;
-    I.ctx = &ctx; I.enc = &enc; I.ks = &ks; I.out_dim = out_dim; I.in_dim = in_dim;
-    I.n = pow2(in_dim) < 2 ? 2 : pow2(in_dim);
-    if (I.n > row) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: in_dim (padded to a power of two) must be <= N/2");
-    I.tpc = tokens_per_ciphertext;
-    I.copies = (I.tpc == 2 ? row : N) / I.n;
-    const size_t mo = pow2(out_dim) < 2 ? 2 : pow2(out_dim);
-    I.m = mo < I.n ? mo : I.n;                                  // wide-input layer: only m wrapped diagonals, folded afterwards
-    I.blocks = (out_dim + I.m - 1) / I.m;
-    I.replicate = I.blocks == 1;
-    I.passes = I.replicate ? 1 : (I.blocks + I.copies - 1) / I.copies;
-    size_t n1 = 1;
-    while (n1 * n1 < I.m) n1 <<= 1;
-    // A hoisted baby step (gathers + key inner products, no transform) costs about a third of a giant step (Ld transforms per limb + its
-    // share of the inverse transform and the division by P), so the split leans towards baby steps: n1 = 2 sqrt(m) when m allows.
-    int shift = kBabyShiftDefault;
-    // (the split sweep behind this default: profiles/r03_bsgs_split_sweep.txt)
-    for (; shift > 0 && n1 * 2 < I.m; --shift) n1 <<= 1;
-    for (; shift < 0 && n1 > 2; ++shift) n1 >>= 1;
-    I.n1 = n1; I.n2 = I.m / n1;
+    I.enc = &enc;
     const uint64_t t = enc.plain_modulus();
-    for (size_t j = 1; j < I.n1; ++j) I.baby_elts.push_back(enc.galois_element((int)j));
-    for (size_t i = 1; i < I.n2; ++i) I.giant_elts.push_back(enc.galois_element((int)(i * n1)));
-    for (size_t sft = I.m; sft < I.n; sft <<= 1) I.fold_elts.push_back(enc.galois_element((int)sft));
-    for (uint32_t g : I.baby_elts) ks.add_galois_element(g);
-    for (uint32_t g : I.giant_elts) ks.add_galois_element(g);
-    for (uint32_t g : I.fold_elts) ks.add_galois_element(g);
+    // (the weights are looked at only after the keys exist, as before: a refused matrix leaves the key switcher with the layer's elements)
+    I.plan("PackedLinear", ctx, ks, out_dim, in_dim, 2, tokens_per_ciphertext, [&](int s) { return enc.galois_element(s); });
+    const size_t n1 = I.n1;
     for (size_t i = 0; i < out_dim * in_dim; ++i)
         if (W[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: weight >= plaintext modulus");
     if (bias)
         for (size_t i = 0; i < out_dim; ++i)
             if (bias[i] >= t) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: bias >= plaintext modulus");
 
-    // Pre-rotated diagonals.  The product of giant step i lands on output slot r = r' - i n1 (row rotation), so position r' of
-    // diagonal (i, j) carries the weight of the output row that slot r holds and of input index (r + k) mod n, k = i n1 + j.
-    // They are multiplied with terms over Q P (the division by P comes after the sum), so they are encoded over all limbs of the
-    // key switcher's extended context.
+    // The diagonals (PackedCore::diag_weight) are multiplied with terms over Q P (the division by P comes after the sum), so they are encoded over
+    // all limbs of the key switcher's extended context.
     const Context& ext = ks.extended_context();
-    const FheParams& pe = ext.params();
-    if (pe.log2_n != p.log2_n || pe.n_limbs() != L + 1 || !std::equal(p.moduli.begin(), p.moduli.end(), pe.moduli.begin()))
-        throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: the key switcher was built for another context");
     const size_t Le = L + 1;
     I.diag.reset(new Plaintext(ext, I.passes * I.n2 * n1, /*is_ntt=*/false));
     // the slot vectors are built here as 32-bit values and encoded on the device: inverse transform over Z_t, lift to the Le limbs and the forward
@@ -129,15 +218,11 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
     try {
         for (size_t pass = 0; pass < I.passes; ++pass) {
             for (size_t i = 0; i < I.n2; ++i) {
-                for (size_t j = 0; j < n1; ++j) {
-                    const size_t k = i * n1 + j;
-                    for (size_t rho = 0; rho < 2; ++rho)
-                        for (size_t rp = 0; rp < row; ++rp) {
-                            const size_t r = (rp + row - (i * n1) % row) % row;
-                            const size_t R = I.row_of_slot(pass, rho * row + r), col = (r + k) % I.n;
-                            slots[j * N + rho * row + rp] = (R != (size_t)-1 && col < in_dim) ? (uint32_t)W[R * in_dim + col] : 0u;
-                        }
-                }
+                for (size_t j = 0; j < n1; ++j)
+                    for (size_t sl = 0; sl < N; ++sl) {
+                        const size_t w = I.diag_weight(pass, i, j, sl);
+                        slots[j * N + sl] = w != (size_t)-1 ? (uint32_t)W[w] : 0u;
+                    }
                 // the copy is ordered behind the previous encode on the null stream; the host builds the next vectors while the device encodes these
                 uint32_t* d_slots = static_cast<uint32_t*>(stage);
                 hip_check(hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
@@ -151,10 +236,7 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
     }
     (void)hipFree(stage);
     I.diag->set_ntt(true);
-    for (size_t pass = 0; pass < I.passes; ++pass) {
-        I.inner_elts.push_back(1u);
-        I.inner_elts.insert(I.inner_elts.end(), I.giant_elts.begin(), I.giant_elts.end());
-    }
+    I.finish_plan();
     // the bias: one slot vector per output ciphertext, in the layout the output itself has (row_of_slot - so also the replicated, folded and two-token ones)
     if (bias) {
         std::vector<uint32_t> bslots(I.passes * N);
@@ -227,52 +309,192 @@ void PackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
     if (x.is_ntt() || x.size() != 2 || T == 0 || y.size() != 2 || y.batch() != I.passes * T)
         throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear::apply: T 2-component coefficient-domain ciphertexts in, output_ciphertexts() * T out");
     I.ensure_tokens(T);   // (re)allocates only when a larger batch than ever before arrives
-    const Context& ctx = *I.ctx;
-    const FheParams& p = ctx.params();
-    const size_t ct_words = 2 * p.n_limbs() * p.n(), n1 = I.n1, n2 = I.n2;
-    hipStream_t hs = static_cast<hipStream_t>(s);
-    dpfhe_ctx* h = handle_of(ctx);
-    dpfhe_ctx* he = handle_of(I.ks->extended_context());
-    // Layout of every intermediate: [rotation or diagonal index][token][component] - the token index sits where the plaintext
-    // matvec sees "more components", so keys and diagonals are read once for all tokens.
-    // baby steps: P rot_j(x_t) + key-switching term, j < n1, all tokens, ONE hoisted pass; they stay in the NTT domain over Q P
-    I.ks->rotate_hoisted_qp(x, 0, T, I.baby_elts, *I.babies_qp, 0, s);
-    // inner sums of all giant steps of all output ciphertexts of all tokens: ONE matrix-vector product over the pre-rotated diagonals
-    check(dpfhe_matvec_plain_multi(he, I.inner_qp->data(), I.diag->data(), I.babies_qp->data(), I.passes * n2, n1, T, s), "dpfhe_matvec_plain_multi");
-    // back to the coefficient domain, the giant step's automorphism applied by the transform's loads; then the ONE division by P
-    // the baby steps and the plaintext products share
-    check(dpfhe_ntt_inv_galois(he, I.inner_qp->data(), I.inner_qp->data(), T * 2, I.inner_elts.data(), I.passes * n2, s), "dpfhe_ntt_inv_galois");
-    Ciphertext& rot = *I.rot;
-    check(dpfhe_rescale(he, rot.data(), I.inner_qp->data(), I.passes * n2 * T * 2, s), "dpfhe_rescale");
-    rot.set_ntt(false);
-    // giant steps: key inner products of the rotated inner sums (i >= 1), summed over Q P; one inverse transform and one
-    // division by P per output ciphertext, which also adds the c0 parts and the un-rotated inner sum
-    uint64_t* sums = I.fold_elts.empty() ? y.data() : I.fold->data();   // wide-input layer: the block sum is folded below before it becomes y
-    if (n2 > 1) {
-        for (size_t pass = 0; pass < I.passes; ++pass) {
-            const size_t base = pass * n2 * T;
-            I.ks->switch_key_qp(rot, base + T, I.giant_elts, T, *I.terms_qp, 0, s);
-            check(dpfhe_reduce_sum(he, I.ksum_qp->data(), I.terms_qp->data(), n2 - 1, 2 * T, s), "dpfhe_reduce_sum");
-            check(dpfhe_ntt_inv(he, I.ksum_qp->data(), T * 2, s), "dpfhe_ntt_inv");
-            check(dpfhe_rescale_bsgs(he, sums + pass * T * ct_words, I.ksum_qp->data(), rot.data() + base * ct_words, n2, T, s), "dpfhe_rescale_bsgs");
-        }
-    } else {
-        hip_check(hipMemcpyAsync(sums, rot.data(), I.passes * T * ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, hs), "hipMemcpyAsync");
-    }
-    // wide input (m < n): slot r holds the partial sum over input indices congruent to r + k; fold the n/m windows together
-    if (!I.fold_elts.empty()) {
-        Ciphertext& f = *I.fold;   // items [0, T): running sums, [T, 2T): their rotation
-        f.set_ntt(false);
-        for (size_t e = 0; e < I.fold_elts.size(); ++e) {
-            const std::vector<uint32_t> one(1, I.fold_elts[e]);
-            I.ks->apply_galois_grouped(f, 0, one, T, f, T, s);
-            const bool last = e + 1 == I.fold_elts.size();
-            check(dpfhe_add(h, last ? y.data() : f.data(), f.data(), f.data() + T * ct_words, 2 * T, s), "dpfhe_add");
-        }
-    }
+    I.run(x, y.data(), s);
+    dpfhe_ctx* h = handle_of(*I.ctx);
     // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
     if (I.bias)
         check(dpfhe_add_plain_scaled(h, y.data(), y.data(), I.bias->data(), I.passes * T, 2, I.passes, I.bias->plain_modulus(), 0, s), "dpfhe_add_plain_scaled");
+    y.set_ntt(false);
+    // enqueue only: the scratch belongs to the layer, the caller synchronises (Context::synchronize) before reading y
+}
+
+// ---- the approximate (CKKS-style) layer: real weights on the one row of N / 2 complex slots, rescale, plaintext add ---------------------------
+class ApproxPackedLinear::Impl : public PackedCore {
+public:
+    const Context* next = nullptr;
+    const ComplexEncoder* enc = nullptr;
+    double w_scale = 0, x_scale = 0, q_last = 0;
+    double rho = 0;          // max_j q_j / P over the data limbs
+    double w_max = 0;        // max |W_ij|
+    double w_row1 = 0;       // max_R ||W_R||_1
+    double b_max = 0;        // max |bias_R| (0 without a bias)
+    std::unique_ptr<Plaintext> bias;    // on `next`: [passes] polynomials at output_scale(), coefficient domain, or null
+    std::unique_ptr<Ciphertext> full;   // the level-L result before the rescale: passes * T items
+    double encode_s = 0;
+    void ensure(size_t T) {
+        grow_scratch(full, passes * T, [&](size_t b) { return new Ciphertext(*ctx, 2, b); });
+        ensure_tokens(T);
+    }
+};
+
+ApproxPackedLinear::ApproxPackedLinear(const Context& ctx, const Context& next_ctx, const ComplexEncoder& enc, HybridKeySwitcher& ks, const double* W, size_t out_dim,
+                                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext, const double* bias)
+    : impl_(new Impl) {
+    const FheParams& p = ctx.params();
+    const size_t N = p.n(), L = p.n_limbs(), row = N / 2;
+    if (!W || out_dim == 0 || in_dim == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: empty matrix");
+    if (enc.slot_count() != row) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: encoder and context disagree on N");
+    if (!(weight_scale > 0) || !(input_scale > 0) || !std::isfinite(weight_scale) || !std::isfinite(input_scale))
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: the scales must be finite and positive");
+    if (L < 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: no limb to rescale by");
+    const FheParams pn = p.drop_last_limb();
+    if (next_ctx.params().log2_n != pn.log2_n || next_ctx.params().moduli != pn.moduli || next_ctx.params().psi != pn.psi || next_ctx.device_id() != ctx.device_id())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: next_ctx must be a context on data_ctx.params().drop_last_limb(), on the same device");
+    Impl& I = *impl_;
+    I.next = &next_ctx; I.enc = &enc; I.w_scale = weight_scale; I.x_scale = input_scale; I.q_last = (double)p.moduli.back();
+    const double out_scale = input_scale * weight_scale / I.q_last, clamp = std::ldexp(1.0, 62);
+    for (size_t R = 0; R < out_dim; ++R) {
+        double sum = 0;
+        for (size_t c = 0; c < in_dim; ++c) {
+            const double w = W[R * in_dim + c];
+            if (!std::isfinite(w)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: a weight is not finite");
+            sum += std::fabs(w);
+            I.w_max = std::max(I.w_max, std::fabs(w));
+        }
+        I.w_row1 = std::max(I.w_row1, sum);
+    }
+    if (weight_scale * I.w_max >= clamp) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: weight_scale * max|W| must stay below 2^62 (the encoder's clamp)");
+    if (bias) {
+        for (size_t R = 0; R < out_dim; ++R) {
+            if (!std::isfinite(bias[R])) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: a bias value is not finite");
+            I.b_max = std::max(I.b_max, std::fabs(bias[R]));
+        }
+        if (out_scale * I.b_max * 2 >= clamp) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: output_scale() * max|bias| must stay below 2^61");
+    }
+    // the geometry of PackedLinear on the ONE slot row: 3^s rotates it as it rotates the rows over Z_t, so both families share keys on one key switcher
+    I.plan("ApproxPackedLinear", ctx, ks, out_dim, in_dim, 1, tokens_per_ciphertext, [&](int s) { return enc.galois_element(s); });
+    const FheParams& pe = ks.extended_context().params();
+    for (size_t l = 0; l < L; ++l) I.rho = std::max(I.rho, (double)p.moduli[l] / (double)pe.moduli.back());
+
+    // the diagonals are real slot vectors at weight_scale, encoded over all limbs of the extended context, n1 per call
+    const Context& ext = ks.extended_context();
+    const size_t Le = L + 1, n1 = I.n1;
+    I.diag.reset(new Plaintext(ext, I.passes * I.n2 * n1, /*is_ntt=*/false));
+    const auto encode_t0 = std::chrono::steady_clock::now();
+    std::vector<double> slots(std::max(n1 * row, bias ? I.passes * N : (size_t)0));
+    double* stage = device_alloc<double>(ext.device_id(), slots.size());
+    try {
+        for (size_t pass = 0; pass < I.passes; ++pass)
+            for (size_t i = 0; i < I.n2; ++i) {
+                for (size_t j = 0; j < n1; ++j)
+                    for (size_t sl = 0; sl < row; ++sl) {
+                        const size_t w = I.diag_weight(pass, i, j, sl);
+                        slots[j * row + sl] = w != (size_t)-1 ? W[w] : 0.0;
+                    }
+                // the copy is ordered behind the previous encode on the null stream; the host builds the next vectors while the device encodes these
+                hip_check(hipMemcpy(stage, slots.data(), n1 * row * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy H2D");
+                enc.encode_device_words(ext, stage, n1, weight_scale, I.diag->data() + ((pass * I.n2 + i) * n1) * Le * N, DPFHE_ENCODE_NTT | DPFHE_ENCODE_REAL, nullptr);
+            }
+        I.diag->set_ntt(true);
+        I.finish_plan();
+        // the bias: one vector of (re, im) slots per output ciphertext at output_scale(), in the layout the output has (row_of_slot); two tokens: b (1 + i)
+        if (bias) {
+            for (size_t pass = 0; pass < I.passes; ++pass)
+                for (size_t sl = 0; sl < row; ++sl) {
+                    const size_t R = I.row_of_slot(pass, sl);
+                    const double b = R != (size_t)-1 ? bias[R] : 0.0;
+                    slots[(pass * row + sl) * 2] = b;
+                    slots[(pass * row + sl) * 2 + 1] = I.tpc == 2 ? b : 0.0;
+                }
+            hip_check(hipMemcpy(stage, slots.data(), I.passes * N * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy H2D");
+            I.bias.reset(new Plaintext(next_ctx, I.passes, false));
+            enc.encode_device(stage, I.passes, out_scale, *I.bias, /*to_ntt=*/false, /*real=*/false, nullptr);
+        }
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    } catch (...) {
+        (void)hipFree(stage);
+        throw;
+    }
+    (void)hipFree(stage);
+    I.encode_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - encode_t0).count();
+    I.ensure(1);
+    ext.synchronize();
+}
+ApproxPackedLinear::~ApproxPackedLinear() = default;
+bool ApproxPackedLinear::has_bias() const { return impl_->bias != nullptr; }
+double ApproxPackedLinear::encode_seconds() const { return impl_->encode_s; }
+double ApproxPackedLinear::output_scale() const { return impl_->x_scale * impl_->w_scale / impl_->q_last; }
+size_t ApproxPackedLinear::dim() const { return impl_->m; }
+size_t ApproxPackedLinear::in_dim() const { return impl_->in_dim; }
+size_t ApproxPackedLinear::out_dim() const { return impl_->out_dim; }
+size_t ApproxPackedLinear::input_period() const { return impl_->n; }
+size_t ApproxPackedLinear::output_ciphertexts() const { return impl_->passes; }
+size_t ApproxPackedLinear::baby_steps() const { return impl_->n1; }
+size_t ApproxPackedLinear::giant_steps() const { return impl_->n2; }
+size_t ApproxPackedLinear::tokens_per_ciphertext() const { return impl_->tpc; }
+size_t ApproxPackedLinear::key_switches_per_apply() const {
+    return impl_->baby_elts.size() + impl_->passes * impl_->giant_elts.size() + impl_->fold_elts.size();
+}
+
+void ApproxPackedLinear::pack_input_pair(const double* xa, const double* xb, std::complex<double>* slots) const {
+    for (size_t s = 0; s < impl_->row; ++s) {
+        const size_t c = s % impl_->n;
+        slots[s] = c < impl_->in_dim ? std::complex<double>(xa[c], xb ? xb[c] : 0.0) : std::complex<double>(0.0, 0.0);
+    }
+}
+void ApproxPackedLinear::pack_input(const double* x, std::complex<double>* slots) const { pack_input_pair(x, nullptr, slots); }
+void ApproxPackedLinear::unpack_output_pair(const std::complex<double>* slots, double* ya, double* yb) const {
+    std::vector<char> seen(impl_->out_dim, 0);
+    for (size_t pass = 0; pass < impl_->passes; ++pass)
+        for (size_t s = 0; s < impl_->row; ++s) {
+            const size_t R = impl_->row_of_slot(pass, s);
+            if (R == (size_t)-1 || seen[R]) continue;
+            ya[R] = slots[pass * impl_->row + s].real();
+            if (yb) yb[R] = slots[pass * impl_->row + s].imag();
+            seen[R] = 1;
+        }
+}
+void ApproxPackedLinear::unpack_output(const std::complex<double>* slots, double* y) const { unpack_output_pair(slots, y, nullptr); }
+size_t ApproxPackedLinear::row_of_slot(size_t output_ciphertext, size_t slot) const {
+    if (output_ciphertext >= impl_->passes || slot >= impl_->row) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear::row_of_slot: index out of range");
+    return impl_->row_of_slot(output_ciphertext, slot);
+}
+
+// the bound of include/deeppowers/fhe.hpp, term by term in that order
+double ApproxPackedLinear::error_bound(double max_abs_input, double input_noise_bound) const {
+    const Impl& I = *impl_;
+    const FheParams& p = I.ctx->params();
+    const double N = (double)p.n(), Ld = (double)p.n_limbs(), two = I.tpc == 2 ? std::sqrt(2.0) : 1.0;
+    const double u8 = 8.0 * (double)p.log2_n * std::ldexp(1.0, -53);
+    const double Dx = I.x_scale, Dw = I.w_scale, Do = output_scale();
+    const double K = 21.0 * Ld * N * I.rho, H = (N + 1) / 2;
+    const double X = max_abs_input * two, B = I.b_max * two, n = (double)I.n, n2 = (double)I.n2;
+    const double G = N * (0.5 + u8 * Dw * I.w_max);                 // a diagonal's slot, off its weight
+    const double S = N * input_noise_bound + N * K;                 // a baby step's slot, off Dx x
+    const double products = Dw * I.w_row1 * S + Dx * X * n * G + n * G * S;
+    const double e0 = n2 * H + (I.n2 > 1 ? (n2 - 1) * K + H : 0.0);
+    const double windows = n / (double)I.m;                         // 2^F
+    const double eF = windows * e0 + (windows - 1) * (K + H);
+    double pre = (products + N * eF) / (Dx * Dw) + N * H / Do;
+    if (I.bias) pre += N * (0.5 + u8 * Do * B) / Do;
+    const double Z = I.w_row1 * X + B;
+    return pre + u8 * N * (Z + pre);
+}
+
+void ApproxPackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
+    Impl& I = *impl_;
+    const size_t T = x.batch();
+    const FheParams& p = I.ctx->params();
+    const size_t poly = p.n_limbs() * p.n();
+    if (x.is_ntt() || x.size() != 2 || T == 0 || x.words() != T * 2 * poly || y.size() != 2 || y.batch() != I.passes * T ||
+        y.words() != I.passes * T * 2 * (poly - p.n()))
+        throw Exception(ErrorCode::INVALID_ARGUMENT,
+                        "ApproxPackedLinear::apply: T 2-component coefficient-domain ciphertexts on data_ctx in, output_ciphertexts() * T on next_ctx out");
+    I.ensure(T);   // (re)allocates only when a larger batch than ever before arrives
+    I.run(x, I.full->data(), s);                                   // level L, scale input_scale * weight_scale
+    check(dpfhe_rescale(handle_of(*I.ctx), y.data(), I.full->data(), I.passes * T * 2, s), "dpfhe_rescale");
+    // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
+    if (I.bias) check(dpfhe_add_plain(handle_of(*I.next), y.data(), y.data(), I.bias->data(), I.passes * T, 2, I.passes, 0, s), "dpfhe_add_plain");
     y.set_ntt(false);
     // enqueue only: the scratch belongs to the layer, the caller synchronises (Context::synchronize) before reading y
 }

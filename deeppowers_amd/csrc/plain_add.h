@@ -53,4 +53,16 @@ int launch_add_plain_scaled(int log2n, u64* out, const u64* in, const u64* plain
 // host twin of the same
 void add_plain_scaled_host(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 ctx_limbs, size_t group, const PlainAddArgs& a);
 
+// ---- plaintext addition on residues (dpfhe_add_plain): the plaintext is an RNS polynomial of the ciphertext's own limbs and domain (an encoder's
+// residue or NTT output), so c0 +- p needs no scaling - the approximate family's bias add, and a plain add in the exact family's NTT domain.
+// x, p canonical: x + p, or x + (q - p), lies in [0, 2q) - one conditional subtraction (p = 0 subtracted: x + q - q = x)
+DPF_HD u64 add_plain_word(u64 x, u64 p, u64 q, u32 negate) { return csub(x + (negate ? q - p : p), q); }
+
+// device: out[i][0] = in[i][0] +- plain[i / group] on every limb, out[i][k >= 1] = in[i][k] when out != in; q_l from lc[l].q.
+// 0, or -1 if the grid is too large for one launch.
+int launch_add_plain(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 n_limbs, size_t group, bool negate,
+                     const LimbConst* lc, hipStream_t s);
+// host twin of the same
+void add_plain_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, size_t group, bool negate);
+
 }  // namespace dpfhe

@@ -491,6 +491,19 @@ class Evaluator:
                                                      plain.shape[0], int(t), 1 if negate else 0, self._sp(stream)), "dpfhe_add_plain_scaled")
         return ct
 
+    # ---- plaintext addition on residues (include/dpfhe.h dpfhe_add_plain) -------------------------------------------------------------
+    def add_plain_(self, ct: torch.Tensor, plain: torch.Tensor, negate: bool = False, stream=None) -> torch.Tensor:
+        """in place: ct [batch][comps][L][N] (comps 2 or 3) gets c0 += p mod q_l (-= with negate) for p = plain [P][L][N] canonical residues of the
+        SAME domain as ct (encode_complex / encode_slots output, or their to_ntt form); item i takes plaintext item i / (batch / P)."""
+        self._chk(ct)
+        p = self.ctx.params
+        if ct.dim() != 4 or plain.dim() != 3 or tuple(plain.shape[1:]) != (p.n_limbs, p.n) or plain.dtype != torch.int64 or not plain.is_contiguous() \
+                or plain.device != ct.device:
+            raise _cabi.DpfheError(2000, "add_plain_: a [batch][comps][L][N] ciphertext tensor and a contiguous int64 [P][L][N] plaintext on its device")
+        _cabi.check(self._lib.dpfhe_add_plain(self.ctx.handle, ct.data_ptr(), ct.data_ptr(), plain.data_ptr(), ct.shape[0], ct.shape[1], plain.shape[0],
+                                              1 if negate else 0, self._sp(stream)), "dpfhe_add_plain")
+        return ct
+
     # ---- slot encoding on the device (include/dpfhe.h dpfhe_encode_slots) ------------------------------------------------------------
     def encode_slots(self, slots: torch.Tensor, t: int, plain: bool = False, to_ntt: bool = False, stream=None) -> torch.Tensor:
         """slots: contiguous [items][N] tensor of slot values < t on the context's device, int32 (read as unsigned 32-bit words, so a value >= 2^31

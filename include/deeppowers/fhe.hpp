@@ -290,6 +290,12 @@ public:
     // components (an ExactMultiplier product before relinearisation too), coefficient domain, batch a multiple of p.items(); out: same shape (may be in).
     void add_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
     void sub_plain_exact(const Ciphertext& in, const ExactPlaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
+    // plaintext addition / subtraction on residues: out = in with c0 +- p mod q_l (dpfhe_add_plain) - p an encoding at the ciphertext's own scale (the
+    // approximate family: ComplexEncoder::encode_device), or any plaintext whose residues are to be added as they are.  in: 2 or 3 components, batch a
+    // multiple of p.batch() (item i takes plaintext item i / (in.batch() / p.batch())); out: same shape (may be in); either domain, INVALID_STATE when the
+    // domain flags of in and p differ.  out takes in's domain flag.
+    void add_plain(const Ciphertext& in, const Plaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
+    void sub_plain(const Ciphertext& in, const Plaintext& p, Ciphertext& out, Stream* stream = nullptr) const;
     // compact result: out = in switched to 2^k_c and bit-packed (dpfhe_compact; enqueue only).  in: 2 components, coefficient domain, in.batch() items
     // (INVALID_STATE for an NTT-domain input, INVALID_ARGUMENT for 3 components, a batch or ring-degree mismatch, or more than 10 limbs: rescale first).
     void compact(const Ciphertext& in, CompactCiphertext& out, Stream* stream = nullptr) const;
@@ -668,6 +674,76 @@ public:
     // Enqueues on `stream` and returns (no host synchronisation).  Scratch: the layer's own buffers (they grow only when a larger T
     // than ever before arrives) AND the key switcher's (digit images, packed keys) - so one apply() at a time per LAYER, and all layers
     // built on one HybridKeySwitcher share ONE stream at a time; synchronise before reading y on the host.
+    void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxPackedLinear: encrypted y = W x + b for REAL weights in the approximate (CKKS-style) family - PackedLinear's geometry (n, m, blocks, passes,
+// replication, n1 / n2, fold rotations, pre-rotated diagonals) laid on the ONE row of N/2 complex slots of a ComplexEncoder, where PackedLinear has two
+// rows over Z_t: copies = (N/2) / n.  The pipeline is PackedLinear's, kernel for kernel (it does not depend on the plaintext space); the diagonals are
+// real slot vectors encoded at weight_scale, the input arrives at input_scale, and apply() ends with the family's fixed-point truncation: one rescale by
+// q_last to next_ctx, then - with a bias - one plaintext addition (dpfhe_add_plain) of the bias encoded at output_scale().  3^s is the rotation by s of
+// both encoders, so an exact and an approximate layer on one HybridKeySwitcher share keys.
+//
+// Error bound.  Notation: Dx = input_scale, Dw = weight_scale, Do = output_scale() = Dx Dw / q_last; Ld the data limbs, P the special prime,
+//   rho = max_j q_j / P; u8 = 8 log2(N) 2^-53 (the E and D of include/dpfhe.h); w1 = max_R ||W_R||_1; X = max|x_i|, B = max|b_R| (both times sqrt 2 with
+//   two tokens per ciphertext: a slot is x_A + i x_B); Bin = the infinity norm of the input phase's error in coefficients (21 + 1/2 + E_x for a fresh
+//   symmetric ciphertext of an encoding at Dx: fhe_sampler.h gives |e| <= 21, E_x = u8 Dx X).
+//   Tools.  (T1) an integer polynomial with |e_k| <= b has every slot <= N b in modulus.  (T2) slots multiply slot-wise and an automorphism permutes
+//   slots and keeps the coefficient norm.  (T3) a division of both components by a prime with rounding adds r0 + r1 s, |r0|, |r1| <= 1/2, s ternary:
+//   at most H = (N + 1) / 2 per coefficient.  (T4) a key switch with digits in [0, q_j) and key errors |e| <= 21 adds, over Q P, at most
+//   21 Ld N max_j q_j per coefficient: K = 21 Ld N rho after the division by P (whose rounding is counted by T3).
+//   The products.  A diagonal's encoding has slot Dw w + eps, |eps| <= G = N (1/2 + u8 Dw max|W|) (E at weight_scale, T1).  A baby step, divided by P,
+//   has slot Dx x + delta, |delta| <= S = N Bin + N K (the input's own error; the baby-step key switch, T4 + T1).  An output slot of row R sums the n
+//   (diagonal, window) pairs whose weights are the row's entries - m diagonals, then n / m windows folded -, so, at scale Dx Dw, it is off
+//   Dx Dw (W x)_R by at most   Dw ||W_R||_1 S + Dx X n G + n G S.   The first term holds the dominant one, ||W_R||_1 21 Ld N^2 rho / Dx after scaling.
+//   The additive terms, in coefficients at scale Dx Dw: the n2 inner sums' division by P, n2 H; with giant steps (n2 > 1) their n2 - 1 key switches and
+//   rescale_bsgs's rounding, (n2 - 1) K + H: together e0.  A fold step adds the running sum to its rotation, 2 e + K + H: after the log2(n / m) steps
+//   eF = (n / m) e0 + (n / m - 1) (K + H).  In slots (T1): N eF.
+//   After the rescale by q_last everything above is divided by Dx Dw in units of the output; its rounding adds N H / Do (T3, T1), the bias's encoding
+//   N (1/2 + u8 Do B) / Do.  Their sum is `pre`, and it bounds every slot (a slot that holds no row has ||W_R||_1 = 0), so the decrypted coefficients
+//   obey max|c_k| <= max slot <= Do (w1 X + B + pre) and the client's decode adds D = u8 N (w1 X + B + pre).
+//   error_bound(X, Bin) = pre + D with w1 for ||W_R||_1: a bound on |decoded output row R - (W x + b)_R| for every row, token and output slot of the row.
+//   (Worst case throughout: the measured error sits orders of magnitude below it - key-switch errors add like a random walk, not in absolute value.)
+class ApproxPackedLinear {
+public:
+    // W: out_dim * in_dim finite doubles, row-major, weight_scale * max|W| < 2^62 (the encoder's clamp); bias: out_dim doubles or null (null: the words of
+    // a layer built without one).  next_ctx: a context on data_ctx.params().drop_last_limb() on the same device (INVALID_ARGUMENT otherwise).  `enc` may be
+    // bound to any context of the ring degree.  tokens_per_ciphertext = 2: token A in the real parts, token B in the imaginary parts of the slots - the
+    // diagonals are real, so W (x_A + i x_B) = W x_A + i W x_B with the same kernels at half the cost per token; the bias slots are b (1 + i).
+    ApproxPackedLinear(const Context& data_ctx, const Context& next_ctx, const ComplexEncoder& enc, HybridKeySwitcher& ks, const double* W, size_t out_dim,
+                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext = 1, const double* bias = nullptr);
+    ~ApproxPackedLinear();
+    ApproxPackedLinear(const ApproxPackedLinear&) = delete;
+    ApproxPackedLinear& operator=(const ApproxPackedLinear&) = delete;
+    bool has_bias() const;
+    double encode_seconds() const;      // wall time the constructor spent building and encoding the diagonals and the bias
+    double output_scale() const;        // input_scale * weight_scale / q_last
+    size_t dim() const;                 // m: diagonals per output ciphertext
+    size_t in_dim() const;
+    size_t out_dim() const;
+    size_t input_period() const;        // n
+    size_t output_ciphertexts() const;  // batch of y per token
+    size_t baby_steps() const;
+    size_t giant_steps() const;
+    size_t key_switches_per_apply() const;
+    size_t tokens_per_ciphertext() const;
+    // which output row slot `slot` (< N/2) of output ciphertext `output_ciphertext` holds, or (size_t)-1
+    size_t row_of_slot(size_t output_ciphertext, size_t slot) const;
+    // slot vectors (N/2 complex values each) <-> plain vectors: x (in_dim values) -> the slots to encode at input_scale and encrypt;
+    // output_ciphertexts() * N/2 decoded slots (decode at output_scale()) -> y (out_dim values).  _pair: two tokens, real and imaginary parts.
+    void pack_input(const double* x, std::complex<double>* slots) const;
+    void pack_input_pair(const double* x_a, const double* x_b, std::complex<double>* slots) const;
+    void unpack_output(const std::complex<double>* slots, double* y) const;
+    void unpack_output_pair(const std::complex<double>* slots, double* y_a, double* y_b) const;
+    // the bound derived above: max_abs_input = the largest |x_i|, input_noise_bound = Bin
+    double error_bound(double max_abs_input, double input_noise_bound) const;
+    // x: T items on data_ctx (coefficient domain, 2 components, scale input_scale); y: output_ciphertexts() * T items on next_ctx, output ciphertext o of
+    // token t at item o * T + t, coefficient domain, scale output_scale().  The stream contract of PackedLinear::apply: enqueues only; the scratch grows
+    // only for a larger T than before; one apply() at a time per layer and per key switcher.
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:

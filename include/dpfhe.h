@@ -339,6 +339,22 @@ int dpfhe_add_plain_scaled(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_in
 int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
                                 size_t batch, size_t comps, size_t plain_items, uint64_t t, int negate);
 
+/* -- plaintext addition on residues: a plaintext polynomial p, given as residues over the ciphertext's own limbs, added to (or, negate != 0, subtracted
+ * from) component 0 - the bias of an approximate (CKKS-style) layer at the ciphertext's scale, or any plaintext add where no scaling by Q / t applies.
+ * d_in, d_out: [batch][comps][L][N] canonical residues (comps 2 or 3); d_plain: [plain_items][L][N] canonical residues, word [item][l][k] in [0, q_l) -
+ *   the default output of dpfhe_encode_complex or dpfhe_encode_slots, or their DPFHE_ENCODE_NTT output.  The entry works in either domain (addition
+ *   commutes with the transform): the caller passes operands of the SAME domain.  Ciphertext item i uses plaintext item i / (batch / plain_items).
+ * Component 0 becomes c0 +- p mod q_l, canonical; the other components are copied when d_out != d_in (in place is allowed).
+ * dpfhe_add_plain enqueues only (no allocation, no synchronise) on every log2_n and every limb class.  DPFHE_INVALID_ARGUMENT, before touching the
+ *   device, on a null pointer, comps not 2 or 3, batch 0, batch not a multiple of plain_items, a buffer not 16-byte aligned, out and in overlapping
+ *   without being the same buffer, out overlapping the plaintext, or a grid too large for one launch (batch max(N / 512, 1) > 2^31 - 1).
+ * dpfhe_add_plain_host: the same words on the host (no device, no context; moduli odd, >= 3 and < 2^60, log2_n in [8, 16]; no alignment rule; a
+ *   plaintext word >= q_l is rejected there, on the device it is a caller error). */
+int dpfhe_add_plain(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_in, const uint64_t* d_plain, size_t batch, size_t comps, size_t plain_items,
+                    int negate, void* stream);
+int dpfhe_add_plain_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* in, const uint64_t* plain,
+                         size_t batch, size_t comps, size_t plain_items, int negate);
+
 /* -- compact result ciphertexts (stream DPFHEc1): a public modulus switch of 2-component ciphertexts from Q = prod q_l to 2^k, then bit-packing.
  * d_in: [batch][2][L][N] coefficient-domain canonical residues, X in [0, Q) a coefficient's CRT value; component c becomes, with k = bits_c,
  *   round(2^k X / Q) mod 2^k  (Q is odd: no tie).  d_out: batch records of N (bits0 + bits1) / 8 bytes; item i's record starts at byte i N (bits0 + bits1) / 8,
