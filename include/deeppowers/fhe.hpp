@@ -708,6 +708,13 @@ private:
 //   obey max|c_k| <= max slot <= Do (w1 X + B + pre) and the client's decode adds D = u8 N (w1 X + B + pre).
 //   error_bound(X, Bin) = pre + D with w1 for ||W_R||_1: a bound on |decoded output row R - (W x + b)_R| for every row, token and output slot of the row.
 //   (Worst case throughout: the measured error sits orders of magnitude below it - key-switch errors add like a random walk, not in absolute value.)
+//
+// Exact on a transparent input.  On a ciphertext with c1 = 0 every key-switch digit is zero, so every key inner product is zero and every division by P
+//   divides P (...) exactly: with c0 the residues of an integer polynomial mu, sigma_g a(X) = a(X^g) in Z[X] / (X^N + 1), p[o][i][j] the encoding of
+//   pre-rotated diagonal i n1 + j of output ciphertext o at weight_scale and bias_o the bias's at output_scale(), apply() gives c1_o = 0 and
+//     S_i = sum_{j < n1} p[o][i][j] sigma_{3^j}(mu),   M_o = sum_{i < n2} sigma_{3^(i n1)}(S_i),   M_o += sigma_{3^s}(M_o) for s = m, 2m, ... < n,
+//     c0_o = round(M_o / q_last) + bias_o  mod q_l, l < L - 1,
+//   word for word (tests/approx_layer_model.py states it on Python integers, tests/test_gpu_approx_layer_words.py holds the device to it).
 class ApproxPackedLinear {
 public:
     // W: out_dim * in_dim finite doubles, row-major, weight_scale * max|W| < 2^62 (the encoder's clamp); bias: out_dim doubles or null (null: the words of
