@@ -89,6 +89,8 @@ struct dpfhe_ctx {
     void* d_blob = nullptr;  // one allocation: LimbConst[L] | fwd | inv | last | RescaleConst[L]  (FoldArith's and ShoupArith's tables share the arrangement: ctx_layout)
     const LimbConst* lc = nullptr;   // the limb constants at the head of d_blob: what the one-pass kernels read, whichever table set below is filled
     const RescaleConst* d_rescale = nullptr;
+    void* rescale2_blob = nullptr;                   // a table of its own (the blob above is pinned by digest): RescaleConst[L-2] of the first L-2 limbs relative to
+    const RescaleConst* d_rescale2 = nullptr;        // limb L-2 - on an extended context the division by the last DATA prime (relin_rescale_kernel); null when L < 3
     DevTables<ShoupArith> shoup{};   // the table set of the context-wide arithmetic (with_ctx_arith): the one that matches `fold` is filled
     DevTables<FoldArith> foldt{};
     // Round 6 - per-limb arithmetic classes.  A context whose limbs are not ALL of the pinned 2^60 - d shape used to run every limb on the
@@ -339,6 +341,12 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
             lazy29_view(fold ? c->foldt : c->cls_fold, static_cast<const unsigned char*>(c->lazy29_blob), lazy29_layout(L));
         }
     }
+    if (L >= 3) {   // the second division of dpfhe_relinearize_rescale_hybrid
+        std::vector<unsigned char> rb((L - 2) * sizeof(RescaleConst));
+        fill_rescale_consts(reinterpret_cast<RescaleConst*>(rb.data()), moduli, L - 2, [](u64 a, u64 q) { return h_powmod(a, q - 2, q); });
+        if (int rc = upload(c->rescale2_blob, rb, "dpfhe_ctx_create: second rescale table upload")) return rc;
+        c->d_rescale2 = static_cast<const RescaleConst*>(c->rescale2_blob);
+    }
     tune_at_create(c);   // default form of the fused multiply, or a cached explicit probe of this shape: no device work
     (void)hipSetDevice(prev);
     *out = c;
@@ -350,6 +358,7 @@ extern "C" int dpfhe_ctx_destroy(dpfhe_ctx* c) {
     if (c->d_blob) (void)hipFree(c->d_blob);
     if (c->class_blob) (void)hipFree(c->class_blob);
     if (c->lazy29_blob) (void)hipFree(c->lazy29_blob);
+    if (c->rescale2_blob) (void)hipFree(c->rescale2_blob);
     for (auto& a : c->scratch_arenas) if (a.p) (void)hipFree(a.p);
     delete c;
     return DPFHE_SUCCESS;
@@ -852,18 +861,20 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
     });
 }
 
-// hybrid key switching = inner product over all L limbs (relin_kernel MODE 2/3) + divide by the special prime and add (c0, c1)
+// hybrid key switching = inner product over all L limbs (relin_kernel MODE 2/3) + divide by the special prime and add (c0, c1);
+// drop_last (relinearisation only): the last pass also divides by the last data prime, d_out2 is [batch][2][Ld-1][N] (relin_rescale_kernel)
 static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_out2, const uint64_t* d_in, const uint64_t* d_key,
-                        uint64_t* d_work, size_t batch, void* stream, size_t key_stride = 0, unsigned key_group = 1) {
+                        uint64_t* d_work, size_t batch, void* stream, size_t key_stride = 0, unsigned key_group = 1, bool drop_last = false) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
     if (int rc = check_extended(c, what)) return rc;
+    if (drop_last && c->n_limbs < 3) return fail(DPFHE_INVALID_STATE, what, "no data limb left to drop (Ld < 2)");
     if (batch == 0) return DPFHE_SUCCESS;
     if (!d_out2 || !d_in || !d_key || !d_work || misaligned(d_out2) || misaligned(d_in) || misaligned(d_key) || misaligned(d_work))
         return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
     const size_t L = c->n_limbs, Ld = L - 1;
     const int n = 1 << c->log2n;
     {   // the rescale-add pass reads (c0, c1) of the input while it writes the output; the work buffer is written by pass 1
-        const size_t in_words = batch * (size_t)in_comps * Ld * n, out_words = batch * 2 * Ld * n, work_words = batch * 2 * L * n;
+        const size_t in_words = batch * (size_t)in_comps * Ld * n, out_words = batch * 2 * (drop_last ? Ld - 1 : Ld) * n, work_words = batch * 2 * L * n;
         if (overlaps(d_out2, out_words, d_in, in_words) || overlaps(d_work, work_words, d_in, in_words) || overlaps(d_work, work_words, d_out2, out_words))
             return fail(DPFHE_INVALID_ARGUMENT, what, "output, input and work buffers must not overlap");
     }
@@ -890,6 +901,13 @@ static int hybrid_entry(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* 
     const int chunks = chunks_of(n);
     const size_t rblocks = batch * 2 * Ld * (size_t)chunks;
     if (rblocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (drop_last) {   // ... and by the last data prime in the same pass
+        with_ctx_arith(c, [&](auto arith) {
+            hipLaunchKernelGGL((relin_rescale_kernel<decltype(arith)>), dim3((unsigned)(batch * 2 * (Ld - 1) * (size_t)chunks)), dim3(256), 0, s, d_out2, d_work, d_in, c->lc,
+                               c->d_rescale, c->d_rescale2, (int)L, n, chunks);
+        });
+        return check_launch("hybrid rescale-twice launch");
+    }
     launch_rescale(c, rblocks, s, d_out2, d_work, d_in, in_comps, in_comps == 3 ? 3 : 1);
     return check_launch("hybrid rescale launch");
 }
@@ -901,6 +919,10 @@ extern "C" int dpfhe_relinearize_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const ui
 extern "C" int dpfhe_switch_key_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, const uint64_t* d_key, uint64_t* d_work, size_t batch,
                                        void* stream) {
     return hybrid_entry(c, "dpfhe_switch_key_hybrid", 2, d_out2, d_in2, d_key, d_work, batch, stream);
+}
+extern "C" int dpfhe_relinearize_rescale_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in3, const uint64_t* d_key, uint64_t* d_work, size_t batch,
+                                                void* stream) {
+    return hybrid_entry(c, "dpfhe_relinearize_rescale_hybrid", 3, d_out2, d_in3, d_key, d_work, batch, stream, 0, 1, true);
 }
 
 // automorphism launch: polynomials up to 64 KiB are staged through LDS, larger ones gathered from global memory
@@ -1627,6 +1649,106 @@ extern "C" int dpfhe_add_plain_host(const uint64_t* moduli, uint32_t n_limbs, ui
         for (size_t k = 0; k < n; ++k)
             if (plain[i * n + k] >= moduli[i % n_limbs]) return fail(DPFHE_INVALID_ARGUMENT, what, "plaintext words must be canonical residues");
     add_plain_host((int)log2_n, moduli, n_limbs, out, in, plain, batch, (u32)comps, batch / plain_items, negate != 0);
+    return DPFHE_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fused rescales of the approximate family's activations (fused_rescale.h; kernels in kernels_misc.h)
+// what a host twin has no context to take from: every limb's constants and the rescale constants of limbs [0, last) relative to limb `last`
+static void host_limb_consts(const uint64_t* moduli, uint32_t n_limbs, std::vector<LimbConst>& lc, bool& fold) {
+    lc.assign(n_limbs, LimbConst{});
+    fold = true;
+    for (uint32_t l = 0; l < n_limbs; ++l) {
+        const u64 q = moduli[l];
+        const unsigned __int128 ratio = (~(unsigned __int128)0) / q;
+        lc[l].q = q;
+        lc[l].d = fold_eligible(q) ? (1ull << 60) - q : 0;
+        lc[l].br_hi = (u64)(ratio >> 64); lc[l].br_lo = (u64)ratio;
+        lc[l].two64 = (u64)((((unsigned __int128)1) << 64) % q);
+        fold = fold && fold_eligible(q);
+    }
+}
+static int host_rescale_consts(const char* what, const uint64_t* moduli, size_t last, std::vector<RescaleConst>& rc) {
+    rc.assign(last, RescaleConst{});
+    bool coprime = true;
+    fill_rescale_consts(rc.data(), moduli, last, [&](u64 a, u64 q) { uint64_t inv = 0; coprime = inverse_mod(a, q, inv) && coprime; return inv; });
+    return coprime ? (int)DPFHE_SUCCESS : fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be pairwise coprime");
+}
+
+extern "C" int dpfhe_relinearize_rescale_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp,
+                                                   const uint64_t* in3, size_t batch) {
+    static const char* what = "dpfhe_relinearize_rescale_pass_host";
+    if (!moduli || !out || !work_qp || !in3) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (n_limbs < 3) return fail(DPFHE_INVALID_STATE, what, "no data limb left to drop (Ld < 2)");
+    const size_t n = (size_t)1 << log2_n, L = n_limbs, Ld = L - 1;
+    if (overlaps(out, batch * 2 * (Ld - 1) * n, work_qp, batch * 2 * L * n) || overlaps(out, batch * 2 * (Ld - 1) * n, in3, batch * 3 * Ld * n))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    for (size_t p = 0; p < 2 * batch; ++p)
+        for (size_t l = 0; l < L; ++l)
+            for (size_t k = 0; k < n; ++k) {
+                if (work_qp[(p * L + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+                if (l < Ld && in3[(((p >> 1) * 3 + (p & 1)) * Ld + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+            }
+    std::vector<LimbConst> lc;
+    std::vector<RescaleConst> rcp, rcq;
+    bool fold;
+    host_limb_consts(moduli, n_limbs, lc, fold);
+    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
+    if (int rc = host_rescale_consts(what, moduli, L - 2, rcq)) return rc;
+    if (fold) relin_rescale_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
+    else relin_rescale_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
+    return DPFHE_SUCCESS;
+}
+
+// the shape checks the device entry and the host twin of the linear combination share
+static int lincomb_args(const char* what, const uint64_t* out, const uint64_t* x, const uint64_t* w, size_t n_terms, size_t batch, uint32_t limbs, uint32_t log2n) {
+    if (!out || !x || !w) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer");
+    if (limbs < 2) return fail(DPFHE_INVALID_STATE, what, "no limb left to drop");
+    if (n_terms == 0 || n_terms > kLincombMaxTerms) return fail(DPFHE_INVALID_ARGUMENT, what, "1 to 16 terms");
+    if (batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "batch must be positive");
+    const size_t n = (size_t)1 << log2n;
+    if (batch > kMaxGrid / (2 * (size_t)(limbs - 1) * (size_t)chunks_of(n))) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    const size_t out_words = batch * 2 * (limbs - 1) * n;
+    if (overlaps(out, out_words, x, n_terms * batch * 2 * limbs * n) || overlaps(out, out_words, w, (n_terms + 1) * limbs))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_lincomb_rescale(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_x, const uint64_t* d_w, size_t n_terms, size_t batch, void* stream) {
+    static const char* what = "dpfhe_lincomb_rescale";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (int rc = lincomb_args(what, d_out, d_x, d_w, n_terms, batch, c->n_limbs, c->log2n)) return rc;
+    if (misaligned(d_out) || misaligned(d_x) || misaligned(d_w)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    DPFHE_ON_DEVICE(c, what);
+    const int n = 1 << c->log2n, chunks = chunks_of(n);
+    const size_t blocks = batch * 2 * (c->n_limbs - 1) * (size_t)chunks;
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((lincomb_rescale_kernel<decltype(arith)>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_x, d_w, c->lc,
+                           c->d_rescale, (int)c->n_limbs, n, chunks, (int)n_terms, batch);
+    });
+    return check_launch("lincomb_rescale kernel launch");
+}
+
+extern "C" int dpfhe_lincomb_rescale_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* x, const uint64_t* w,
+                                          size_t n_terms, size_t batch) {
+    static const char* what = "dpfhe_lincomb_rescale_host";
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, what, "null moduli");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (int rc = lincomb_args(what, out, x, w, n_terms, batch, n_limbs, log2_n)) return rc;
+    const size_t n = (size_t)1 << log2_n, L = n_limbs;
+    for (size_t i = 0; i < n_terms * batch * 2 * L; ++i)
+        for (size_t k = 0; k < n; ++k)
+            if (x[i * n + k] >= moduli[i % L]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+    for (size_t i = 0; i < (n_terms + 1) * L; ++i)
+        if (w[i] >= moduli[i % L]) return fail(DPFHE_INVALID_ARGUMENT, what, "weights must be canonical residues");
+    std::vector<LimbConst> lc;
+    std::vector<RescaleConst> rc;
+    bool fold;
+    host_limb_consts(moduli, n_limbs, lc, fold);
+    if (int e = host_rescale_consts(what, moduli, L - 1, rc)) return e;
+    if (fold) lincomb_rescale_host<FoldArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
+    else lincomb_rescale_host<ShoupArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
     return DPFHE_SUCCESS;
 }
 

@@ -21,6 +21,7 @@ public:
     std::unique_ptr<Ciphertext> scratch_rotated;
     std::unique_ptr<PolyBuffer> scratch_digits;    // hoisted rotations: NTT of the lifted digits, [Ld][L][N]
     std::unique_ptr<Ciphertext> scratch_in_ntt;    // rotate_hoisted_qp: NTT of the inputs on the data limbs
+    std::unique_ptr<Ciphertext> scratch_product;   // multiply_rescale: the 3-component product on the data limbs
     void init(const Context& data, const SecretKey& sk, uint64_t special_prime, uint64_t special_psi) {
         data_ctx = &data;
         FheParams pe = data.params();
@@ -178,7 +179,36 @@ void HybridKeySwitcher::apply_galois_grouped(const Ciphertext& in2, size_t in_fi
     out2.set_ntt(false);
 }
 
+void HybridKeySwitcher::multiply_rescale(const Ciphertext& a, const Ciphertext& b, Ciphertext& out_next_level, Stream* s) const {
+    if (b.batch() != a.batch() || out_next_level.batch() != a.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: operands and output of one batch");
+    multiply_rescale_range(a, 0, b, 0, a.batch(), out_next_level, 0, s);
+}
+
+void HybridKeySwitcher::multiply_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, Ciphertext& out,
+                                               size_t out_first, Stream* s) const {
+    const FheParams& pe = impl_->ext->params();
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), in_words = 2 * Ld * n;
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, "HybridKeySwitcher::multiply_rescale: no data limb left to drop");
+    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+        a_first + count > a.batch() || b_first + count > b.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: 2-component coefficient-domain ciphertexts on the data context, ranges inside them");
+    const size_t out_words = 2 * (Ld - 1) * n;
+    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + count > out.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: output must live on the next-level context (Ld - 1 limbs), 2 components, with room for the range");
+    if (count == 0) return;
+    grow_scratch(impl_->scratch_product, count, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
+    grow_scratch(impl_->scratch_work, count, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, count, 0, s),
+          "dpfhe_ct_mul");
+    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                           impl_->scratch_work->data(), count, s),
+          "dpfhe_relinearize_rescale_hybrid");
+    out.set_ntt(false);
+}
+
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
+const Context& HybridKeySwitcher::data_context() const { return *impl_->data_ctx; }
 
 void HybridKeySwitcher::rotate_hoisted_qp(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& elts, PolyBuffer& out_qp,
                                           size_t out_first, Stream* s) const {

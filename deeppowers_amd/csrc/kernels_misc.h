@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fused_rescale.h"
 #include "launch.h"
 #include "modarith.h"
 #include "reduce_thin.h"
@@ -701,6 +702,78 @@ __global__ __launch_bounds__(256) void rescale_bsgs_kernel(u64* out, const u64* 
         r.a = add_mod(r.a, v.a, lc.q); r.b = add_mod(r.b, v.b, lc.q);
     }
     *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) = r;
+}
+
+// The last pass of a relinearised product that is rescaled at once (fused_rescale.h (a)): divide the key-switched sums by P, add (c0, c1), divide by the
+// last data prime.  work: [batch][2][L][N] over Q P, in3: [batch][3][Ld][N] (components 0 and 1 are read), out: [batch][2][Ld-1][N].  Per (polynomial,
+// kept limb, chunk): five 16-byte loads per lane (the rows of limb Ld-1 and of P are shared by the Ld-1 workgroups of a polynomial's chunk: re-read
+// from cache) and one store.  lcs / rcp: the extended context's limb and rescale constants (relative to P), rcq: [Ld-1] relative to q_{Ld-1}.
+template <class Arith>
+__global__ __launch_bounds__(256) void relin_rescale_kernel(u64* out, const u64* __restrict__ work, const u64* __restrict__ in3, const LimbConst* lcs,
+                                                            const RescaleConst* rcp, const RescaleConst* rcq, int n_limbs, int n, int chunks) {
+    const int Ld = n_limbs - 1, Lo = Ld - 1;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
+    const int limb = wk.limb;
+    const size_t poly = wk.poly;   // = b * 2 + comp
+    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const RelinRescaleConsts k{lcs[limb], lcs[Lo], rcp[limb], rcp[Lo], rcq[limb]};
+    const u64* wp = work + poly * n_limbs * (size_t)n + w0;
+    const u64* cp = in3 + ((poly >> 1) * 3 + (poly & 1)) * Ld * (size_t)n + w0;
+    const U64x2 wi = *reinterpret_cast<const U64x2*>(wp + (size_t)limb * n);
+    const U64x2 wl = *reinterpret_cast<const U64x2*>(wp + (size_t)Lo * n);
+    const U64x2 wP = *reinterpret_cast<const U64x2*>(wp + (size_t)Ld * n);
+    const U64x2 ci = *reinterpret_cast<const U64x2*>(cp + (size_t)limb * n);
+    const U64x2 cl = *reinterpret_cast<const U64x2*>(cp + (size_t)Lo * n);
+    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) =
+        U64x2{relin_rescale_word<Arith>(wi.a, wl.a, wP.a, ci.a, cl.a, k), relin_rescale_word<Arith>(wi.b, wl.b, wP.b, ci.b, cl.b, k)};
+}
+
+// Scalar linear combination of K ciphertexts per item, a constant on X^0 of component 0, and the rescale (fused_rescale.h (b)):
+//   out[t][c] = round((sum_{k<K} w_k x[k][t][c] + [c = 0] w_K) / q_{L-1}).   x: [K][batch][2][L][N], w: [K + 1][L], out: [batch][2][L-1][N].
+// Per (polynomial, kept limb, chunk): 2 K 16-byte loads per lane (limb i and the last limb of every term, four terms in flight) and one store; the
+// weights are workgroup-uniform (scalar loads).
+template <class Arith>
+__global__ __launch_bounds__(256) void lincomb_rescale_kernel(u64* out, const u64* __restrict__ x, const u64* __restrict__ w, const LimbConst* lcs,
+                                                              const RescaleConst* rcs, int n_limbs, int n, int chunks, int n_terms, size_t batch) {
+    const int Lo = n_limbs - 1;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
+    const int limb = wk.limb;
+    const size_t poly = wk.poly;   // = t * 2 + c
+    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const LimbConst lc = lcs[limb], lcl = lcs[Lo];
+    const size_t term = batch * 2 * n_limbs * (size_t)n;
+    const u64* xi = x + (poly * n_limbs + limb) * n + w0;
+    const u64* xl = x + (poly * n_limbs + Lo) * n + w0;
+    LazySum si[2] = {{0, 0}, {0, 0}}, sl[2] = {{0, 0}, {0, 0}};
+    int k = 0;
+    for (; k + 4 <= n_terms; k += 4) {
+        U64x2 vi[4], vl[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            vi[u] = *reinterpret_cast<const U64x2*>(xi + (k + u) * term);
+            vl[u] = *reinterpret_cast<const U64x2*>(xl + (k + u) * term);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const u64 wi = w[(k + u) * n_limbs + limb], wl = w[(k + u) * n_limbs + Lo];
+            lazy_mac(si[0], wi, vi[u].a); lazy_mac(si[1], wi, vi[u].b);
+            lazy_mac(sl[0], wl, vl[u].a); lazy_mac(sl[1], wl, vl[u].b);
+        }
+    }
+    for (; k < n_terms; ++k) {
+        const U64x2 vi = *reinterpret_cast<const U64x2*>(xi + k * term);
+        const U64x2 vl = *reinterpret_cast<const U64x2*>(xl + k * term);
+        const u64 wi = w[k * n_limbs + limb], wl = w[k * n_limbs + Lo];
+        lazy_mac(si[0], wi, vi.a); lazy_mac(si[1], wi, vi.b);
+        lazy_mac(sl[0], wl, vl.a); lazy_mac(sl[1], wl, vl.b);
+    }
+    if (!(poly & 1) && w0 == 0) { lazy_add(si[0], w[n_terms * n_limbs + limb]); lazy_add(sl[0], w[n_terms * n_limbs + Lo]); }
+    const RescaleConst rc = rcs[limb];
+    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) =
+        U64x2{rescale_word<Arith>(lazy_reduce<Arith>(si[0], lc), lazy_reduce<Arith>(sl[0], lcl), lc, rc),
+              rescale_word<Arith>(lazy_reduce<Arith>(si[1], lc), lazy_reduce<Arith>(sl[1], lcl), lc, rc)};
 }
 
 // N3 (round 3): a ciphertext in the NTT domain on the data limbs, lifted to the extended basis as P * ct: word * (P mod q_i) on the

@@ -367,6 +367,25 @@ class Evaluator:
         _cabi.check(fn(self.ctx.handle, out.data_ptr(), d.data_ptr(), key.data_ptr(), work.data_ptr(), batch, self._sp(stream)), "dpfhe_*_hybrid")
         return Ciphertext(out, False)
 
+    def relinearize_rescale_hybrid(self, ct3: Ciphertext, key: torch.Tensor, stream=None) -> Ciphertext:
+        """A relinearised product at the next level (dpfhe_relinearize_rescale_hybrid): the words of rescale(keyswitch_hybrid(ct3, key)) with one
+        rounding pass.  THIS evaluator's context is the extended one; ct3: [batch][3][L-1][N], key as for keyswitch_hybrid -> [batch][2][L-2][N]."""
+        p = self.ctx.params
+        L, Ld, n = p.n_limbs, p.n_limbs - 1, p.n
+        d = ct3.data
+        if ct3.is_ntt or ct3.size != 3 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "relinearize_rescale_hybrid: coefficient-domain [batch][3][L-1][N] ciphertexts on the extended context")
+        if tuple(key.shape) != (Ld, 2, L, n):
+            raise _cabi.DpfheError(2000, "key must be [L-1][2][L][N]")
+        if Ld < 2:
+            raise _cabi.DpfheError(2002, "relinearize_rescale_hybrid: no data limb left to drop")
+        batch = d.shape[0]
+        out = self._empty((batch, 2, Ld - 1, n), stream)
+        work = self._empty((batch, 2, L, n), stream)
+        _cabi.check(self._lib.dpfhe_relinearize_rescale_hybrid(self.ctx.handle, out.data_ptr(), d.data_ptr(), key.data_ptr(), work.data_ptr(), batch,
+                                                               self._sp(stream)), "dpfhe_relinearize_rescale_hybrid")
+        return Ciphertext(out, False)
+
     def rotate_hybrid_batch(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> Ciphertext:
         """N3, batched rotations on the extended context: output item i = key-switched sigma_{galois_elts[i]} of input item
         i, or of THE input item when ct holds one.  keys: [len(elts)][L-1][2][L][N] (key i switches sigma_{g_i}(s) -> s)."""
@@ -631,6 +650,19 @@ class Evaluator:
         out = self._empty((rows, n_rhs, 2, self.ctx.params.n_limbs, self.ctx.params.n), stream)
         _cabi.check(self._lib.dpfhe_matvec_plain_multi(self.ctx.handle, out.data_ptr(), W.data.data_ptr(), x.data_ptr(), rows, cols, n_rhs, self._sp(stream)),
                     "dpfhe_matvec_plain_multi")
+        return out
+
+    def lincomb_rescale(self, x: torch.Tensor, w: torch.Tensor, stream=None) -> torch.Tensor:
+        """x: [K][batch][2][L][N] (coefficient domain), w: [K + 1][L] residues on the device (row K: the constant on X^0 of component 0) ->
+        [batch][2][L-1][N] = round((sum_k w_k x[k] + constant) / q_last)  (dpfhe_lincomb_rescale; 1 <= K <= 16)."""
+        self._chk(x)
+        p = self.ctx.params
+        if (x.dim() != 5 or x.shape[2] != 2 or w.dtype != torch.int64 or not w.is_cuda or not w.is_contiguous() or w.device != self.ctx.device
+                or tuple(w.shape) != (x.shape[0] + 1, p.n_limbs)):
+            raise _cabi.DpfheError(2000, "lincomb_rescale: x [K][batch][2][L][N], w [K + 1][L] int64 cuda")
+        K, batch = x.shape[0], x.shape[1]
+        out = self._empty((batch, 2, p.n_limbs - 1, p.n), stream)
+        _cabi.check(self._lib.dpfhe_lincomb_rescale(self.ctx.handle, out.data_ptr(), x.data_ptr(), w.data_ptr(), K, batch, self._sp(stream)), "dpfhe_lincomb_rescale")
         return out
 
     def rescale_words(self, t: torch.Tensor, stream=None) -> torch.Tensor:

@@ -510,6 +510,15 @@ public:
     void relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* stream = nullptr) const;
     // ciphertext of m(X) -> ciphertext of m(X^g); the element must have been added
     void apply_galois(const Ciphertext& in2, uint32_t galois_elt, Ciphertext& out2, Stream* stream = nullptr) const;
+    // The approximate family's ciphertext x ciphertext step: out = round(relinearize(a * b) / q_last) at the next level - Evaluator::multiply on data_ctx,
+    // then dpfhe_relinearize_rescale_hybrid (the division by P and by the last data prime in one pass; the words of relinearize + Evaluator::rescale).
+    // a, b: 2 components, coefficient domain, one batch, on data_ctx (they may be the same object: a square); out_next_level: 2 components, same batch, on a
+    // Context of data_ctx.params().drop_last_limb().  At scales s_a, s_b the result has scale s_a s_b / q_last.  Enqueues only: the product and the Q P
+    // sums live in scratch the object owns, grown only for a larger batch than ever before.  INVALID_STATE when data_ctx has one limb.
+    void multiply_rescale(const Ciphertext& a, const Ciphertext& b, Ciphertext& out_next_level, Stream* stream = nullptr) const;
+    // the same on item ranges: out item out_first + i = items a_first + i of a times b_first + i of b, i < count (a and b may be one buffer, also one range)
+    void multiply_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, Ciphertext& out_next_level,
+                                size_t out_first, Stream* stream = nullptr) const;
     // many rotations in one pass (dpfhe_rotate_hybrid_batch): out item out_first + i = sigma_{elts[i]} of in item i, or of THE
     // item of `in` when it holds one.  All elements must have been added; the keys of a given element list are packed
     // back to back once and cached.
@@ -533,6 +542,7 @@ public:
     // ---- division by P deferred ("double hoisting"; include/dpfhe.h "N3, round 3") -------------------------------------
     // The context of the data moduli + the special prime: buffers holding terms over Q P live on it.
     const Context& extended_context() const;
+    const Context& data_context() const;   // the level the ciphertexts live on (the constructor's data_ctx)
     // n_items inputs (in2 items in_first ...) -> out_qp items out_first + r * n_items + t, r = 0 .. elts.size(): r = 0 is P * ct_t, r >= 1 is
     // P * sigma_{elts[r-1]}(ct_t) + its key-switching term; NTT domain over Q P, NOT divided by P (dpfhe_rotate_hoisted_qp).
     // `out_qp`: 2-component buffer on extended_context().
@@ -751,6 +761,67 @@ public:
     // x: T items on data_ctx (coefficient domain, 2 components, scale input_scale); y: output_ciphertexts() * T items on next_ctx, output ciphertext o of
     // token t at item o * T + t, coefficient domain, scale output_scale().  The stream contract of PackedLinear::apply: enqueues only; the scratch grows
     // only for a larger T than before; one apply() at a time per layer and per key switcher.
+    void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxPolynomial: slot-wise y = p(x) = sum_{k=0..d} a_k x^k, 2 <= d <= 15, power basis, in the approximate (CKKS-style) family - the non-linearity
+// between two ApproxPackedLinear layers.  It needs relinearisation keys only (no Galois keys): one HybridKeySwitcher per level at which a product happens.
+//
+// Levels.  Depth 0 is the input's context; a product at level r (1 <= r <= r* = ceil(log2 d)) takes operands of depth r - 1, runs on levels[r - 1] (whose
+//   data context IS depth r - 1) and leaves its result at depth r, one limb lower.  sum_ctx is depth r*, out_ctx depth r* + 1: depth() = r* + 1 limbs go.
+// Schedule.  x^k for k in (2^(r-1), 2^r] is x^(2^(r-1)) * x^(k - 2^(r-1)) at level r; all products of a level are ONE batched
+//   HybridKeySwitcher::multiply_rescale_range over (powers x tokens).  An operand of lower depth is first dropped to depth r - 1 by keeping its first limbs
+//   (a strided device copy on the stream; the ciphertext and its scale do not change).  All powers are dropped to depth r*, and one dpfhe_lincomb_rescale
+//   takes sum_k c_k x^k + c_0 and the rescale by q* (the last prime of sum_ctx) for all tokens.
+// Scales, in exactly these double operations (tests/approx_poly_model.py mirrors them):  s_1 = input_scale;  s_k = (s_i * s_j) / (double)q  with
+//   i = 2^(ceil(log2 k) - 1), j = k - i and q the prime that product drops (the last prime of depth ceil(log2 k) - 1);  with S = output_scale:
+//   c_k = llround(a_k * ((S * (double)q*) / s_k)) for k >= 1, and the constant  c_0 = llround(a_0 * S) q*  as an exact integer product (a_0 S q* itself is
+//   far above 2^63 for any useful S under a 60-bit q*; the rescale gives llround(a_0 S) back exactly).  The residues of c_k are the weights; |c_k| >= 2^62
+//   (k >= 1) or |llround(a_0 S)| >= 2^62 is INVALID_ARGUMENT.  The output's scale is exactly S.  (Scales near the primes keep s_k near s_1: with
+//   s_1 = 2^50 under 60-bit primes s_2 is 2^40.)
+//
+// Error bound.  ApproxPackedLinear's notation and tools T1 - T4; u = 2^-53, X = max|x|, Bin the input phase's coefficient error; per level r: L_r its data
+//   limbs, q_r the prime it drops, rho_r = max_j q_j / P_r, K_r = 21 L_r N rho_r (T4), H = (N + 1) / 2 (T3).  The phase of power k has slot s_k x^k + d_k,
+//   |d_k| <= D_k.  D_1 = N Bin (T1).  A tensor product multiplies phases, so slots multiply (T2): (s_i x^i + d_i)(s_j x^j + d_j); the relinearisation
+//   adds K_r + H per coefficient after its division by P, the division by q_r divides all of it and adds H, and s_k as a double is off the real
+//   s_i s_j / q_r by at most 4 u s_k (two roundings and the conversion of q_r):
+//     D_k = (s_i X^i D_j + s_j X^j D_i + D_i D_j + N (K_r + H)) / q_r + N H + 4 u s_k X^k.
+//   The weights: c_k = a_k S q* / s_k + r_k with |r_k| <= R_k = 1/2 + 4 u |a_k| S q* / s_k (llround; four roundings in the double expression), and
+//   c_0 = a_0 S q* + r_0 with |r_0| <= R_0 = q* (1/2 + 2 u |a_0| S).  A scalar multiple multiplies the phase, the constant is c_0 in every slot, so the sum's slot is S q* p(x) off by at most
+//     sum_{k>=1} (R_k s_k X^k + |a_k| (S q* / s_k) D_k + R_k D_k) + R_0;   after the rescale, in units of the output:  pre = that / (S q*) + N H / S  (T3, T1).
+//   The decrypted coefficients obey max|c| <= max slot <= S (A + pre), A = sum_k |a_k| X^k, so the client's decode adds D = u8 N (A + pre), u8 = 8 log2(N) u.
+//   error_bound(X, Bin) = pre + D bounds |decoded slot - p(x)| for every slot and token, PROVIDED no phase wraps (the caller's choice of limbs: the largest
+//   phase, at sum_ctx, is about S q* A).  Worst case throughout; the roundings' N H dominates (2^23 at N = 4096, against scales near 2^60).
+//
+// Exact on a transparent input (c1 = 0: every relinearisation digit is zero): with mu_1 the input's integer polynomial and (*) the product in
+//   Z[X] / (X^N + 1),  mu_k = round(mu_i (*) mu_j / q_r),  M = sum_k c_k mu_k + c_0 X^0,  c0_out = round(M / q*) mod q_l,  c1_out = 0, word for word.
+class ApproxPolynomial {
+public:
+    // levels: ceil(log2 d) key switchers, input level first, levels[r] on the context of the input's limbs without the last r (same ring, same device, same
+    // secret); sum_ctx: levels.back()'s data context without its last limb; out_ctx: sum_ctx without its last limb.  coeffs: a_0 .. a_d, finite, d + 1 of
+    // them.  INVALID_ARGUMENT for a degree outside [2, 15], a wrong number of levels, contexts that do not form that chain, scales that are not finite and
+    // positive, a coefficient that is not finite or a |c_k| >= 2^62.  Everything referenced must outlive the object.
+    ApproxPolynomial(const std::vector<HybridKeySwitcher*>& levels, const Context& sum_ctx, const Context& out_ctx, const std::vector<double>& coeffs,
+                     double input_scale, double output_scale);
+    ~ApproxPolynomial();
+    ApproxPolynomial(const ApproxPolynomial&) = delete;
+    ApproxPolynomial& operator=(const ApproxPolynomial&) = delete;
+    size_t degree() const;                // d
+    size_t depth() const;                 // ceil(log2 d) + 1: the limbs between x and y
+    double output_scale() const;          // S, exactly
+    double power_scale(size_t k) const;   // s_k, 1 <= k <= d
+    int64_t weight(size_t k) const;       // c_k, 1 <= k <= d; weight(0) = llround(a_0 S), the constant at the output scale (c_0 = weight(0) q*)
+    // the bound derived above; the static form needs no device: data_moduli are the input level's limbs, special_primes one P per level
+    double error_bound(double max_abs_input, double input_noise_bound) const;
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, const std::vector<uint64_t>& special_primes,
+                              const std::vector<double>& coeffs, double input_scale, double output_scale, double max_abs_input, double input_noise_bound);
+    // x: T items on levels[0]'s data context (2 components, coefficient domain, scale input_scale); y: T items on out_ctx, scale output_scale().  Enqueues
+    // only; the scratch (powers, operands) belongs to the object and grows only for a larger T than before; one apply() at a time per object and per key
+    // switcher.
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:

@@ -190,6 +190,36 @@ int dpfhe_relinearize_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_
 int dpfhe_switch_key_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, const uint64_t* d_key, uint64_t* d_work,
                             size_t batch, void* stream);
 
+/* -- a relinearised product at the next level in one call (the approximate family's ciphertext x ciphertext step): dpfhe_relinearize_hybrid and the
+ * dpfhe_rescale that follows it, with ONE rounding pass instead of two.  ctx_ext, d_in3, d_key, d_work (batch * 2 * L * N words) and the overlap rules are
+ * dpfhe_relinearize_hybrid's; d_out2 is [batch][2][Ld-1][N], coefficient domain, on the data context's first Ld - 1 limbs:
+ *   d_out2 = round( ((c0, c1) + round(sum_j [c2]_{q_j} key_j / P)) / q_{Ld-1} )
+ * word for word what dpfhe_rescale on the Ld data limbs makes of dpfhe_relinearize_hybrid's output: the last pass reads the Q P sums on limbs i, Ld-1 and P
+ * and (c0, c1) on limbs i and Ld-1, and applies both divisions to the coefficient in registers (each is modular and local to the coefficient).  Every ring
+ * degree (above N = 8192 the sums are composed as for dpfhe_relinearize_hybrid, scratch from the stream's arena).  Enqueues only; at log2_n <= 13 it
+ * never allocates.  DPFHE_INVALID_STATE when Ld < 2 (no data limb left to drop).
+ * dpfhe_relinearize_rescale_pass_host: the host twin of that last pass alone (no device, no context): moduli are the n_limbs = Ld + 1 >= 3 limbs of the
+ *   extended basis (odd, >= 3, < 2^60, pairwise coprime), work_qp [batch][2][L][N] the sums over Q P in the coefficient domain, in3 [batch][3][Ld][N]
+ *   (components 0 and 1 are read), out [batch][2][Ld-1][N].  Words that are not canonical residues are rejected. */
+int dpfhe_relinearize_rescale_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in3, const uint64_t* d_key, uint64_t* d_work,
+                                     size_t batch, void* stream);
+int dpfhe_relinearize_rescale_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp,
+                                        const uint64_t* in3, size_t batch);
+
+/* -- scalar linear combination + constant + rescale (the final sum of a polynomial in a ciphertext): per item t and component c, coefficient domain,
+ *   d_out[t][c] = round( (sum_{k < n_terms} w_k * x[k][t][c]  +  [c = 0] w_K X^0) / q_{L-1} ),   K = n_terms, 1 <= n_terms <= 16
+ * d_x: [n_terms][batch][2][L][N] canonical residues (term-major: term k of every item, then term k + 1); d_w: [n_terms + 1][L] canonical residues ON THE
+ * DEVICE, word [k][l] = w_k mod q_l, the last row the constant (added to coefficient 0 of component 0 only; a row of zeros for none); d_out:
+ * [batch][2][L-1][N].  The rounding is dpfhe_rescale's; the words are those of the sum taken mod every q_l and then rescaled, however the sum is taken.
+ * One launch for all items, one pass: 2 n_terms reads and one write per output word.  Enqueues only (no allocation, no synchronise), every log2_n and limb
+ * class.  DPFHE_INVALID_STATE when L < 2; DPFHE_INVALID_ARGUMENT, before touching the device, on a null pointer, n_terms outside [1, 16], batch 0, a buffer
+ * not 16-byte aligned, d_out overlapping d_x or d_w, or a grid too large for one launch.
+ * dpfhe_lincomb_rescale_host: the same words on the host (no device, no context; moduli odd, >= 3, < 2^60 and pairwise coprime, log2_n in [8, 16]; no
+ *   alignment rule; words that are not canonical residues are rejected there, on the device they are a caller error). */
+int dpfhe_lincomb_rescale(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_x, const uint64_t* d_w, size_t n_terms, size_t batch, void* stream);
+int dpfhe_lincomb_rescale_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* x, const uint64_t* w,
+                               size_t n_terms, size_t batch);
+
 /* -- N3, batched rotations (the baby / giant steps of a packed matrix-vector product): item i of the output is the
  * hybrid-key-switched sigma_{galois_elts[i]} of input item i (n_in == batch) or of THE input item (n_in == 1).
  * galois_elts: HOST array of `batch` odd elements < 2N.  d_keys: `batch` keys back to back, each [Ld][2][L][N] as for
