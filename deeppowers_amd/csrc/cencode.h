@@ -237,10 +237,7 @@ inline void cenc_host_tables(u32 log2_n, const u64* moduli, u32 n_limbs, Cencode
 }
 
 #if defined(__HIPCC__)
-// device: out = the encoding of d_slots ([items][n] (re, im) pairs, or [items][n] doubles when real) at scale Delta = scale_over_n n; plain: [items][N]
-// two's-complement words, else [items][L][N] residues.  0, or -1 if the grid is too large.
-int launch_encode_complex(u64* out, const double* slots, size_t items, double scale_over_n, bool real, bool plain, const CencodeTables& tb, hipStream_t s);
-// host twin of the same (tables in host memory)
+// host twin of the device launch (k_cencode.hip launch_encode_complex), tables in host memory
 void encode_complex_host(u64* out, const double* slots, size_t items, double scale_over_n, bool real, bool plain, const CencodeTables& tb);
 // z_i = m(xi^(3^i)) / scale from centred coefficients ([items][N]); real: the real parts only
 void decode_complex_host(double* slots_out, const int64_t* coeffs, size_t items, double scale, bool real, u32 log2_n);

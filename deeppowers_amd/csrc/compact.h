@@ -88,9 +88,7 @@ static_assert(kCompactMaxLimbs == 10, "one case per limb count above");
 // bytes of one item's record
 DPF_HD size_t compact_record_bytes(u32 log2n, const CompactArgs& a) { return ((size_t)(a.bits[0] + a.bits[1]) << log2n) / 8; }
 
-// device: out = the records of in [batch][2][L][N] (log2n >= 8; out and in 16-byte aligned).  0, or -1 if the grid is too large for one launch.
-int launch_compact(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a, hipStream_t s);
-// host twin of the same
+// host twin of the device launch (k_compact.hip launch_compact)
 void compact_host(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a);
 
 }  // namespace dpfhe

@@ -1,5 +1,5 @@
 // ctx_tables.h - host-side construction of the table blobs of a context: every byte the kernels read through
-// DevTables / MixedTables (devtables.h).  Plain C++17, no HIP: dpfhe_ctx_create (dpfhe_cabi.hip) uploads these blobs
+// DevTables / MixedTables (devtables.h).  Plain C++17, no HIP: dpfhe_ctx_create (cabi_ctx.hip) uploads these blobs
 // and tools/emulate.cpp runs the kernels' per-thread code on them, so the CPU proofs cover the shipped arrangement.
 #pragma once
 #include <cstring>

@@ -63,7 +63,7 @@ struct DevTables {
     const InvLast<typename Arith::Tw>* last29;  // [L]
     const LimbConst* lc;                    // [L]
     int n_limbs;
-    // Per-limb arithmetic classes (round 6, dpfhe_cabi.hip): a launch may cover only SOME limbs of the context - those whose primes this policy
+    // Per-limb arithmetic classes (round 6, cabi.h dpfhe_ctx::classes): a launch may cover only SOME limbs of the context - those whose primes this policy
     // serves.  n_active = 0: all n_limbs limbs (the uniform contexts; block b works on limb b mod n_limbs).  Otherwise block b works on item
     // b / n_active and limb (active_map >> 4 (b mod n_active)) & 15; tables and data stay indexed by the limb's number in the context
     // (n_limbs = the stride), so a class's tables simply leave the other limbs' slots unused.  Contexts of more than 16 limbs are uniform.

@@ -215,9 +215,7 @@ inline bool enc_host_tables(u32 log2_n, u64 t, const u64* moduli, u32 n_limbs, E
 }
 
 #if defined(__HIPCC__)
-// device: out = the encoding of d_slots [items][N]; plain: [items][N] words in [0, t), else [items][L][N] residues.  0, or -1 if the grid is too large.
-int launch_encode_slots(u64* out, const u32* slots, size_t items, bool plain, const EncodeTables& tb, hipStream_t s);
-// host twin of the same (tables in host memory)
+// host twin of the device launch (k_encode.hip launch_encode_slots), tables in host memory
 void encode_slots_host(u64* out, const u32* slots, size_t items, bool plain, const EncodeTables& tb);
 #endif
 

@@ -46,10 +46,7 @@ DPF_HD void expand_block(const ExpandKey& k, u32 j, u32 item, u32 limb, u32 comp
     }
 }
 
-// device: component `comp` of items [0, batch) of buf [batch][comps][L][N] = expand(seed, first_item + b, limb, comp); 0, or -1 if the grid is too large
-int launch_expand_uniform(int log2n, u64* buf, size_t batch, size_t comps, u32 comp, u32 n_limbs, const LimbConst* lc, const ExpandKey& key, u32 first_item,
-                          hipStream_t s);
-// host twin of the same (every other word untouched)
+// host twin of the device launch (k_expand.hip launch_expand_uniform): every other word untouched
 void expand_uniform_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, size_t batch, size_t comps, u32 comp, const ExpandKey& key, u32 first_item);
 
 }  // namespace dpfhe

@@ -13,7 +13,7 @@
 //       Canonical words are below 2^60, so K + 1 <= 17 products sum below 17 2^120 < 2^125: one 128-bit lazy sum per word, reduced once.
 //
 // All results are canonical residues, so the words do not depend on how a policy reduces: Arith::kFold picks FoldArith's folds, anything else the
-// generic 128-bit Barrett products, as in every other streaming kernel (dpfhe_cabi.hip with_ctx_arith).
+// generic 128-bit Barrett products, as in every other streaming kernel (cabi.h with_ctx_arith).
 //
 // Shared by the device kernels (kernels_misc.h relin_rescale_kernel, lincomb_rescale_kernel) and the host twins below (dpfhe_relinearize_rescale_pass_host,
 // dpfhe_lincomb_rescale_host): one statement of the arithmetic.  No HIP in here.

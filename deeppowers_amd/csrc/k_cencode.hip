@@ -1,4 +1,4 @@
-// k_cencode.hip - complex slot encoding (cencode.h): the device kernels, their launcher, the host twin and the host decoder.
+// k_cencode.hip - complex slot encoding (cencode.h): the device kernels, their launcher, the host twin, the host decoder and the entries of include/dpfhe.h.
 //
 // N <= 16384: one workgroup of up to 512 lanes per slot vector.  It gathers the n = N / 2 complex slots in transform order (the slot -> position table
 // and the conjugation fused into the load) and keeps them in LDS (16 n = 8 N bytes: dynamic up to 64 KiB, a static 128 KiB array at N = 16384), runs the
@@ -8,6 +8,10 @@
 // N = 32768, 65536: the first 12 levels run per 4096-word chunk as above and park their words in row 0 of the item's own output (real parts in the
 // low half of the row, imaginary parts in the high half: exactly N doubles); a second kernel takes, per lane, the 4 or 8 complex words 4096 apart of a
 // pair of columns through the remaining levels in registers and writes all rows of exactly the positions it read - no scratch and no hazard.
+#include <cstring>
+#include <new>
+
+#include "cabi.h"
 #include "cencode.h"
 
 namespace dpfhe {
@@ -51,7 +55,9 @@ __global__ __launch_bounds__(kCencThreads) void cencode_tail_kernel(u64* __restr
     cenc_lane_tail<R>(out + item * ((plain ? (size_t)1 : (size_t)tb.n_limbs) << tb.log2n), k, kCencChunkLog, scale, plain != 0, tb);
 }
 
-int launch_encode_complex(u64* out, const double* slots, size_t items, double scale, bool real, bool plain, const CencodeTables& tb, hipStream_t s) {
+// device: out = the encoding of d_slots ([items][n] (re, im) pairs, or [items][n] doubles when real) at scale Delta = scale_over_n n; plain: [items][N]
+// two's-complement words, else [items][L][N] residues.  0, or -1 if the grid is too large.
+static int launch_encode_complex(u64* out, const double* slots, size_t items, double scale, bool real, bool plain, const CencodeTables& tb, hipStream_t s) {
     const u32 log2h = tb.log2n - 1;
     const bool whole = log2h <= kCencMaxLdsLog;
     const u32 log2c = whole ? log2h : kCencChunkLog;
@@ -137,3 +143,111 @@ void decode_complex_host(double* slots_out, const int64_t* coeffs, size_t items,
 }
 
 }  // namespace dpfhe
+
+// ------------------------------------------------------------------------------------------------
+// complex slot encoding (cencode.h, k_cencode.hip): vectors of n = N / 2 complex (or real) slots -> round(Delta m), plain or as residues on every limb
+struct dpfhe_cencoder {
+    dpfhe_ctx* ctx = nullptr;
+    void* d_blob = nullptr;   // one allocation: cenc_f64x2 tw[n] | CencLimb[L] | u32 src[n]
+    CencodeTables tb{};
+};
+
+static const uint32_t kCencodeFlags = DPFHE_ENCODE_PLAIN | DPFHE_ENCODE_NTT | DPFHE_ENCODE_REAL;
+
+// Delta / n, the factor the last level carries (n a power of two: exact unless it underflows); false unless Delta is finite and positive
+static bool cencode_scale(double scale, uint32_t log2_n, double& scale_over_n) {
+    if (!(scale > 0.0) || !std::isfinite(scale)) return false;
+    scale_over_n = std::ldexp(scale, -(int)(log2_n - 1));
+    return true;
+}
+
+extern "C" int dpfhe_cencoder_create(dpfhe_cencoder** out, dpfhe_ctx* c) {
+    static const char* what = "dpfhe_cencoder_create";
+    if (!out || !c) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument");
+    CencodeHostTables h;
+    cenc_host_tables(c->log2n, c->moduli.data(), c->n_limbs, h);
+    const size_t half = (size_t)1 << (c->log2n - 1);
+    const size_t tw_bytes = half * sizeof(cenc_f64x2), limb_bytes = c->n_limbs * sizeof(CencLimb), src_bytes = half * sizeof(u32);
+    std::vector<unsigned char> blob(tw_bytes + limb_bytes + src_bytes);
+    std::memcpy(blob.data(), h.tw.data(), tw_bytes);
+    std::memcpy(blob.data() + tw_bytes, h.limb.data(), limb_bytes);
+    std::memcpy(blob.data() + tw_bytes + limb_bytes, h.src.data(), src_bytes);
+    DPFHE_ON_DEVICE(c, what);
+    dpfhe_cencoder* e = new (std::nothrow) dpfhe_cencoder;
+    if (!e) return fail(DPFHE_OUT_OF_MEMORY, what, "host allocation");
+    if (int rc = upload_blob(&e->d_blob, blob, what)) {
+        delete e;
+        return rc;
+    }
+    const unsigned char* d = static_cast<const unsigned char*>(e->d_blob);
+    e->ctx = c;
+    e->tb.tw = reinterpret_cast<const cenc_f64x2*>(d);
+    e->tb.limb = reinterpret_cast<const CencLimb*>(d + tw_bytes);
+    e->tb.src = reinterpret_cast<const u32*>(d + tw_bytes + limb_bytes);
+    e->tb.log2n = c->log2n;
+    e->tb.n_limbs = c->n_limbs;
+    *out = e;
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_cencoder_destroy(dpfhe_cencoder* e) {
+    if (!e) return DPFHE_SUCCESS;
+    if (e->d_blob) (void)hipFree(e->d_blob);
+    delete e;
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_encode_complex(dpfhe_cencoder* e, uint64_t* d_out, const double* d_slots, size_t items, double scale, uint32_t flags, void* stream) {
+    static const char* what = "dpfhe_encode_complex";
+    if (!e || !d_out || !d_slots || items == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument or items 0");
+    if ((flags & ~kCencodeFlags) || (flags & (DPFHE_ENCODE_PLAIN | DPFHE_ENCODE_NTT)) == (DPFHE_ENCODE_PLAIN | DPFHE_ENCODE_NTT))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag, or PLAIN together with NTT");
+    if (misaligned(d_out) || misaligned(d_slots)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    dpfhe_ctx* c = e->ctx;
+    double scale_over_n = 0.0;
+    if (!cencode_scale(scale, c->log2n, scale_over_n)) return fail(DPFHE_INVALID_ARGUMENT, what, "scale must be finite and positive");
+    const bool plain = (flags & DPFHE_ENCODE_PLAIN) != 0, real = (flags & DPFHE_ENCODE_REAL) != 0;
+    const size_t n = (size_t)1 << c->log2n;
+    if (items > kMaxGrid / n) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");   // (also keeps every size below in range)
+    if (overlaps_bytes(d_out, items * (plain ? 1 : c->n_limbs) * n * 8, d_slots, items * (real ? n / 2 : n) * 8))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "out and slots overlap");
+    if ((flags & DPFHE_ENCODE_NTT) && !ntt_grid_fits(c, items * c->n_limbs)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");
+    DPFHE_ON_DEVICE(c, what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (launch_encode_complex(d_out, d_slots, items, scale_over_n, real, plain, e->tb, s)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");
+    if (int rc = check_launch("encode_complex kernel launch")) return rc;
+    if (flags & DPFHE_ENCODE_NTT) return ntt_launch_items(c, false, d_out, d_out, items, 0, s);
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_encode_complex_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const double* slots, size_t items, double scale,
+                                         uint32_t flags) {
+    static const char* what = "dpfhe_encode_complex_host";
+    if (!moduli || !out || !slots || items == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument or items 0");
+    if (flags & ~(uint32_t)(DPFHE_ENCODE_PLAIN | DPFHE_ENCODE_REAL)) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag (the host twin has no transform over the q_l)");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (misaligned(out) || misaligned(slots)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    double scale_over_n = 0.0;
+    if (!cencode_scale(scale, log2_n, scale_over_n)) return fail(DPFHE_INVALID_ARGUMENT, what, "scale must be finite and positive");
+    const size_t n = (size_t)1 << log2_n;
+    const bool plain = (flags & DPFHE_ENCODE_PLAIN) != 0, real = (flags & DPFHE_ENCODE_REAL) != 0;
+    if (items > ~(size_t)0 / (8 * n * n_limbs)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items");
+    if (overlaps_bytes(out, items * (plain ? 1 : n_limbs) * n * 8, slots, items * (real ? n / 2 : n) * 8)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and slots overlap");
+    CencodeHostTables h;
+    cenc_host_tables(log2_n, moduli, n_limbs, h);
+    encode_complex_host(out, slots, items, scale_over_n, real, plain, h.view(log2_n));
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_decode_complex_host(uint32_t log2_n, double* slots_out, const int64_t* coeffs, size_t items, double scale, uint32_t flags) {
+    static const char* what = "dpfhe_decode_complex_host";
+    if (!slots_out || !coeffs || items == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument or items 0");
+    if (flags & ~(uint32_t)DPFHE_ENCODE_REAL) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag");
+    if (log2_n < 8 || log2_n > 16) return fail(DPFHE_INVALID_ARGUMENT, what, "log2_n must lie in [8, 16]");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(DPFHE_INVALID_ARGUMENT, what, "scale must be finite and positive");
+    const size_t n = (size_t)1 << log2_n;
+    if (items > ~(size_t)0 / (8 * n)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items");
+    if (overlaps_bytes(slots_out, items * ((flags & DPFHE_ENCODE_REAL) ? n / 2 : n) * 8, coeffs, items * n * 8)) return fail(DPFHE_INVALID_ARGUMENT, what, "slots and coefficients overlap");
+    decode_complex_host(slots_out, coeffs, items, scale, (flags & DPFHE_ENCODE_REAL) != 0, log2_n);
+    return DPFHE_SUCCESS;
+}

@@ -1,9 +1,10 @@
-// k_compact.hip - compact result ciphertexts (compact.h): the device kernel, its launcher and the host twin.
+// k_compact.hip - compact result ciphertexts (compact.h): the device kernel, its launcher, the host twin and the entries of include/dpfhe.h.
 //
 // One lane per pair of coefficients: for each component it reads its pair of every limb row (16-byte loads, each row contiguous across the wave),
 // computes the two switched values in registers and parks them in LDS.  After one barrier the block's bit strings are gathered from LDS into
 // 16-byte chunks: the block's 2 T values of component c are 2 T k_c bits = T k_c / 64 chunks (T >= 128 lanes, so every chunk is whole and
 // starts on a 32-byte boundary of the record), and every global store is one full 16-byte contiguous store.
+#include "cabi.h"
 #include "compact.h"
 
 namespace dpfhe {
@@ -59,7 +60,8 @@ __global__ __launch_bounds__(kCompactThreads) void compact_kernel(uint8_t* __res
     }
 }
 
-int launch_compact(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a, hipStream_t s) {
+// device: out = the records of in [batch][2][L][N] (log2n >= 8; out and in 16-byte aligned).  0, or -1 if the grid is too large for one launch.
+static int launch_compact(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a, hipStream_t s) {
     const u32 pairs = 1u << (log2n - 1);                       // lanes per residue polynomial (log2n >= 8: at least two waves)
     const u32 threads = pairs < kCompactThreads ? pairs : kCompactThreads;
     u32 log2_chunks = 0;
@@ -98,3 +100,73 @@ void compact_host(int log2n, uint8_t* out, const u64* in, size_t batch, const Co
 }
 
 }  // namespace dpfhe
+
+// ------------------------------------------------------------------------------------------------
+// compact result ciphertexts (compact.h, k_compact.hip): round(2^k X / Q) mod 2^k per component, bit-packed
+// validates the widths and limb count, then fills every constant; the moduli must be pairwise coprime (their inverses exist)
+static int compact_args(const char* what, uint32_t bits0, uint32_t bits1, const uint64_t* moduli, uint32_t n_limbs, CompactArgs& a) {
+    if (bits0 < kCompactMinBits || bits0 > kCompactMaxBits || bits1 < kCompactMinBits || bits1 > kCompactMaxBits)
+        return fail(DPFHE_INVALID_ARGUMENT, what, "widths must lie in [8, 60]");
+    if (n_limbs == 0 || n_limbs > kCompactMaxLimbs) return fail(DPFHE_INVALID_ARGUMENT, what, "1 to 10 limbs (rescale first)");
+    a = CompactArgs{};
+    a.n_limbs = n_limbs;
+    a.bits[0] = bits0; a.bits[1] = bits1;
+    a.q64 = 1;
+    for (uint32_t k = 0; k < n_limbs; ++k) {
+        const uint64_t q = moduli[k];
+        a.q[k] = q;
+        a.lift[k] = q * ((((uint64_t)1 << 60) + q - 1) / q);   // < 2^60 + q
+        for (uint32_t i = 0; i < k; ++i) {
+            if (!inverse_mod(moduli[i], q, a.inv[k][i])) return fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be pairwise coprime");
+            a.inv_sh[k][i] = (uint64_t)(((unsigned __int128)a.inv[k][i] << 64) / q);
+        }
+        for (int c = 0; c < 2; ++c) {
+            a.pow2[c][k] = (uint64_t)(((unsigned __int128)1 << a.bits[c]) % q);
+            a.pow2_sh[c][k] = (uint64_t)(((unsigned __int128)a.pow2[c][k] << 64) / q);
+        }
+        a.q64 *= q;
+    }
+    uint64_t inv = a.q64;   // Q odd: Q Q = 1 mod 8, and each Newton step doubles the correct low bits
+    for (int s = 0; s < 5; ++s) inv *= 2 - a.q64 * inv;
+    a.qinv64 = inv;
+    // floor(Q / 2) = (Q - 1) / 2 has the residues (q_i - 1) / 2 (Q = 0 and 2^-1 = (q_i + 1) / 2 mod q_i); its digits as the kernel computes them
+    for (uint32_t i = 0; i < n_limbs; ++i) a.half[i] = (moduli[i] - 1) / 2;
+    compact_with_limbs(n_limbs, [&](auto nl) {
+        constexpr int NL = decltype(nl)::value;
+        u64 v[NL];
+        for (int i = 0; i < NL; ++i) v[i] = a.half[i];
+        compact_digits<NL>(v, a);
+        for (int i = 0; i < NL; ++i) a.half[i] = v[i];
+    });
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_compact(dpfhe_ctx* c, uint8_t* d_out, const uint64_t* d_in, size_t batch, uint32_t bits0, uint32_t bits1, void* stream) {
+    static const char* what = "dpfhe_compact";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (!d_out || !d_in || batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or batch 0");
+    CompactArgs a;
+    if (int rc = compact_args(what, bits0, bits1, c->moduli.data(), c->n_limbs, a)) return rc;
+    if (misaligned(d_out) || misaligned(d_in)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    const size_t words = batch * 2 * ((size_t)c->n_limbs << c->log2n), bytes = batch * compact_record_bytes(c->log2n, a);
+    if (overlaps_bytes(d_out, bytes, d_in, words * 8)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap");
+    DPFHE_ON_DEVICE(c, what);
+    if (launch_compact((int)c->log2n, d_out, d_in, batch, a, static_cast<hipStream_t>(stream)))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    return check_launch("compact kernel launch");
+}
+
+extern "C" int dpfhe_compact_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint8_t* out, const uint64_t* in, size_t batch, uint32_t bits0,
+                                  uint32_t bits1) {
+    static const char* what = "dpfhe_compact_host";
+    if (!moduli || !out || !in || batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or batch 0");
+    if (log2_n < 8 || log2_n > (uint32_t)kMaxLog2N) return fail(DPFHE_INVALID_ARGUMENT, what, "log2_n in [8, 16]");
+    if (n_limbs == 0 || n_limbs > kCompactMaxLimbs) return fail(DPFHE_INVALID_ARGUMENT, what, "1 to 10 limbs (rescale first)");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;   // (after this twin's own shape messages: only the moduli can fail here)
+    CompactArgs a;
+    if (int rc = compact_args(what, bits0, bits1, moduli, n_limbs, a)) return rc;
+    const size_t words = batch * 2 * ((size_t)n_limbs << log2_n), bytes = batch * compact_record_bytes(log2_n, a);
+    if (overlaps_bytes(out, bytes, in, words * 8)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap");
+    compact_host((int)log2_n, out, in, batch, a);
+    return DPFHE_SUCCESS;
+}

@@ -1,9 +1,12 @@
-// k_expand.hip - seeded uniform polynomials (expand.h): the device kernel, its launcher and the host twin.
+// k_expand.hip - seeded uniform polynomials (expand.h): the device kernel, its launcher, the host twin and the entries of include/dpfhe.h.
 //
 // One lane per ChaCha20 block: a lane produces 4 coefficients (32 contiguous bytes, two 16-byte stores) and consecutive lanes write
 // consecutive blocks, so the stores coalesce without LDS.  A workgroup covers one (item, limb) range of blocks, so the limb's
 // constants are workgroup-uniform scalar loads; the seed's key words are kernel arguments (SGPRs).  No loads from memory besides
 // the LimbConst: the kernel is VALU-bound (20 ChaCha rounds + four exact 128-bit reductions per lane).
+#include <cstring>
+
+#include "cabi.h"
 #include "expand.h"
 
 namespace dpfhe {
@@ -26,7 +29,8 @@ __global__ __launch_bounds__(256) void expand_uniform_kernel(u64* __restrict__ b
     reinterpret_cast<u64x2_t*>(p)[1] = u64x2_t{v[2], v[3]};
 }
 
-int launch_expand_uniform(int log2n, u64* buf, size_t batch, size_t comps, u32 comp, u32 n_limbs, const LimbConst* lc, const ExpandKey& key, u32 first_item,
+// device: component `comp` of items [0, batch) of buf [batch][comps][L][N] = expand(seed, first_item + b, limb, comp); 0, or -1 if the grid is too large
+static int launch_expand_uniform(int log2n, u64* buf, size_t batch, size_t comps, u32 comp, u32 n_limbs, const LimbConst* lc, const ExpandKey& key, u32 first_item,
                           hipStream_t s) {
     const u32 blocks_per_poly = 1u << (log2n - 2);                  // ChaCha blocks of one residue polynomial (log2n >= 8: at least one wave)
     const u32 threads = blocks_per_poly < 256u ? blocks_per_poly : 256u;
@@ -53,3 +57,38 @@ void expand_uniform_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, si
 }
 
 }  // namespace dpfhe
+
+// ------------------------------------------------------------------------------------------------
+// seeded uniform polynomials (expand.h, k_expand.hip): component `component` of items 0 .. batch-1 = expand(seed, first_item + b, limb, component)
+static int expand_args(const char* what, const void* buf, size_t components, uint32_t component, const uint8_t* seed, uint64_t first_item, size_t batch,
+                       ExpandKey& key) {
+    if (!buf || !seed) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or seed");
+    if (component >= components) return fail(DPFHE_INVALID_ARGUMENT, what, "component must be < components");
+    if (first_item > ((uint64_t)1 << 32) || batch > ((uint64_t)1 << 32) - first_item) return fail(DPFHE_INVALID_ARGUMENT, what, "first_item + batch must be <= 2^32");
+    std::memcpy(key.w, seed, 32);   // little-endian words (x86-64 and gfx950 hosts)
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_expand_uniform(dpfhe_ctx* c, uint64_t* d_buf, size_t batch, size_t components, uint32_t component, const uint8_t seed[32],
+                                    uint64_t first_item, void* stream) {
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "null context");
+    ExpandKey key;
+    if (int rc = expand_args("dpfhe_expand_uniform", d_buf, components, component, seed, first_item, batch, key)) return rc;
+    if (misaligned(d_buf)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "misaligned buffer");
+    if (batch == 0) return DPFHE_SUCCESS;
+    DPFHE_ON_DEVICE(c, "dpfhe_expand_uniform");
+    // c->lc holds q and floor(2^128 / q) of every limb, whatever its class
+    if (launch_expand_uniform((int)c->log2n, d_buf, batch, components, component, c->n_limbs, c->lc, key, (uint32_t)first_item, static_cast<hipStream_t>(stream)))
+        return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform", "batch too large for one launch");
+    return check_launch("expand_uniform kernel launch");
+}
+
+extern "C" int dpfhe_expand_uniform_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t components,
+                                         uint32_t component, const uint8_t seed[32], uint64_t first_item) {
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_expand_uniform_host", "null moduli");
+    ExpandKey key;
+    if (int rc = expand_args("dpfhe_expand_uniform_host", out, components, component, seed, first_item, batch, key)) return rc;
+    if (int rc = check_host_ring("dpfhe_expand_uniform_host", moduli, n_limbs, log2_n)) return rc;
+    expand_uniform_host((int)log2_n, moduli, n_limbs, out, batch, components, component, key, (uint32_t)first_item);
+    return DPFHE_SUCCESS;
+}

@@ -1,10 +1,14 @@
-// k_noise.hip - noise polynomials for re-randomisation (noise.h): the device kernel, its launcher, the host twin, and the accumulate pass of
-// dpfhe_rerandomize.
+// k_noise.hip - noise polynomials for re-randomisation (noise.h): the device kernel, its launcher, the host twin, the accumulate pass of
+// dpfhe_rerandomize, and the entries of include/dpfhe.h.
 //
 // One lane per ChaCha20 block: the block gives two adjacent coefficients, and since the key stream does not depend on the limb the lane decodes them
 // once and walks the limbs, writing one 16-byte store per limb row; consecutive lanes write consecutive 16-byte words, so every wave store covers 1 KiB
 // of one row without LDS.  The limb constants and the seed's key words are kernel arguments (scalar loads, SGPRs).  Without `add` the kernel loads
 // nothing from memory; with it, one 16-byte load per store.
+#include <algorithm>
+#include <cstring>
+
+#include "cabi.h"
 #include "noise.h"
 
 namespace dpfhe {
@@ -41,7 +45,9 @@ static void launch_kind(u64* buf, const NoiseArgs& a, unsigned grid, unsigned th
     else hipLaunchKernelGGL((sample_noise_kernel<KIND, false>), dim3(grid), dim3(threads), 0, s, buf, a, log2_chunks);
 }
 
-int launch_sample_noise(u64* buf, size_t batch, const NoiseArgs& a, hipStream_t s) {
+// device: component a.comp of items [0, batch) of buf [batch][comps][ctx_limbs][N], limbs [a.l0, a.l0 + a.n_limbs): = noise, or += noise mod q with a.add;
+// 0, or -1 if the grid is too large
+static int launch_sample_noise(u64* buf, size_t batch, const NoiseArgs& a, hipStream_t s) {
     const u32 pairs = 1u << (a.log2n - 1);                     // ChaCha blocks of one polynomial (log2n >= 8: at least two waves)
     const u32 threads = pairs < 256u ? pairs : 256u;
     u32 log2_chunks = 0;
@@ -97,7 +103,8 @@ __global__ __launch_bounds__(256) void add_products_kernel(u64* __restrict__ ct,
     }
 }
 
-int launch_add_products(u64* ct, const u64* prod, size_t batch, u32 n_limbs, int log2n, const LimbConst* lc, hipStream_t s) {
+// device: ct [batch][2][L][N] += prod [2][batch][L][N] mod q, word by word (the last step of dpfhe_rerandomize); 0, or -1 if the grid is too large
+static int launch_add_products(u64* ct, const u64* prod, size_t batch, u32 n_limbs, int log2n, const LimbConst* lc, hipStream_t s) {
     const size_t grid = batch * 2 * n_limbs;
     if (grid == 0 || grid > 0x7fffffffu) return -1;
     hipLaunchKernelGGL(add_products_kernel, dim3((unsigned)grid), dim3(256), 0, s, ct, prod, lc, (u32)batch, n_limbs, (u32)log2n);
@@ -105,3 +112,119 @@ int launch_add_products(u64* ct, const u64* prod, size_t batch, u32 n_limbs, int
 }
 
 }  // namespace dpfhe
+
+// ------------------------------------------------------------------------------------------------
+// noise polynomials and re-randomisation (noise.h, k_noise.hip): noise(seed, item, stream_id, kind, param) into one component of a batch
+static int noise_args(const char* what, const void* out, size_t batch, size_t comps, uint32_t comp, uint32_t kind, uint32_t param, uint32_t stream_id,
+                      const uint8_t* seed, uint32_t first_item, uint32_t flags, uint32_t ctx_limbs, uint32_t log2_n, NoiseArgs& a) {
+    if (!out || !seed || batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or seed, or batch 0");
+    if (kind > kNoiseFlood) return fail(DPFHE_INVALID_ARGUMENT, what, "kind must be 0 (ternary), 1 (centred binomial) or 2 (flood)");
+    if (kind == kNoiseFlood && (param < 1 || param > kNoiseMaxFlood)) return fail(DPFHE_INVALID_ARGUMENT, what, "flood bits must lie in [1, 250]");
+    if (comp >= comps || comps > 0xffffffffu) return fail(DPFHE_INVALID_ARGUMENT, what, "component must be < components");
+    if (flags & ~(uint32_t)DPFHE_NOISE_ADD) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag");
+    if (batch > ((uint64_t)1 << 32) - first_item) return fail(DPFHE_INVALID_ARGUMENT, what, "first_item + batch must be <= 2^32");
+    a = NoiseArgs{};
+    std::memcpy(a.key.w, seed, 32);   // little-endian words (x86-64 and gfx950 hosts)
+    a.first_item = first_item; a.stream_id = stream_id; a.kind = kind; a.param = kind == kNoiseFlood ? param : 0;
+    a.comp = comp; a.comps = (uint32_t)comps; a.ctx_limbs = ctx_limbs; a.log2n = log2_n;
+    a.add = flags & DPFHE_NOISE_ADD ? 1u : 0u;
+    return DPFHE_SUCCESS;
+}
+
+// the limbs in launches of at most kNoiseLimbs (their constants are a kernel argument)
+template <class F>
+static int for_noise_groups(NoiseArgs& a, const uint64_t* moduli, uint32_t n_limbs, F f) {
+    for (uint32_t l0 = 0; l0 < n_limbs; l0 += kNoiseLimbs) {
+        a.l0 = l0;
+        a.n_limbs = std::min<uint32_t>(kNoiseLimbs, n_limbs - l0);
+        for (uint32_t l = 0; l < a.n_limbs; ++l) a.limb[l] = noise_limb(moduli[l0 + l], a.kind, a.param);
+        if (int rc = f(a)) return rc;
+    }
+    return DPFHE_SUCCESS;
+}
+
+// arguments validated, device selected by the caller
+static int noise_launch(const char* what, dpfhe_ctx* c, uint64_t* d_out, size_t batch, NoiseArgs& a, hipStream_t s) {
+    return for_noise_groups(a, c->moduli.data(), c->n_limbs, [&](const NoiseArgs& g) {
+        if (launch_sample_noise(d_out, batch, g, s)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+        return check_launch("sample_noise kernel launch");
+    });
+}
+
+extern "C" int dpfhe_sample_noise(dpfhe_ctx* c, uint64_t* d_out, size_t batch, size_t comps, uint32_t comp, uint32_t kind, uint32_t param, uint32_t stream_id,
+                                  const uint8_t seed[32], uint32_t first_item, uint32_t flags, void* stream) {
+    static const char* what = "dpfhe_sample_noise";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    NoiseArgs a;
+    if (int rc = noise_args(what, d_out, batch, comps, comp, kind, param, stream_id, seed, first_item, flags, c->n_limbs, c->log2n, a)) return rc;
+    if (misaligned(d_out)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    if ((batch << (c->log2n - 1)) > kMaxGrid * (size_t)256) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    DPFHE_ON_DEVICE(c, what);
+    return noise_launch(what, c, d_out, batch, a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int dpfhe_sample_noise_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, size_t batch, size_t comps, uint32_t comp,
+                                       uint32_t kind, uint32_t param, uint32_t stream_id, const uint8_t seed[32], uint32_t first_item, uint32_t flags) {
+    static const char* what = "dpfhe_sample_noise_host";
+    if (!moduli) return fail(DPFHE_INVALID_ARGUMENT, what, "null moduli");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    NoiseArgs a;
+    if (int rc = noise_args(what, out, batch, comps, comp, kind, param, stream_id, seed, first_item, flags, n_limbs, log2_n, a)) return rc;
+    return for_noise_groups(a, moduli, n_limbs, [&](const NoiseArgs& g) {
+        sample_noise_host(out, batch, g);
+        return (int)DPFHE_SUCCESS;
+    });
+}
+
+// floor(log2 of the product of the moduli), exactly (the product in 64-bit words)
+static uint32_t floor_log2_product(const std::vector<uint64_t>& moduli) {
+    std::vector<uint64_t> w(1, 1);
+    for (uint64_t q : moduli) {
+        uint64_t carry = 0;
+        for (uint64_t& x : w) {
+            const unsigned __int128 t = (unsigned __int128)x * q + carry;
+            x = (uint64_t)t;
+            carry = (uint64_t)(t >> 64);
+        }
+        if (carry) w.push_back(carry);
+    }
+    return (uint32_t)(64 * (w.size() - 1) + (63 - __builtin_clzll(w.back())));
+}
+
+// u = ternary, e0 = flood, e1 = centred binomial:  (c0, c1) += (INTT(pk0 (.) NTT(u)) + e0, INTT(pk1 (.) NTT(u)) + e1).
+// d_work: u [batch][L][N] | products [2][batch][L][N]
+extern "C" int dpfhe_rerandomize(dpfhe_ctx* c, uint64_t* d_ct2, const uint64_t* d_pk, size_t batch, uint32_t flood_bits, const uint8_t seed[32],
+                                 uint32_t first_item, uint64_t* d_work, void* stream) {
+    static const char* what = "dpfhe_rerandomize";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (!d_ct2 || !d_pk || !d_work || !seed || batch == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer or seed, or batch 0");
+    if (misaligned(d_ct2) || misaligned(d_pk) || misaligned(d_work)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
+    const uint32_t log2_q = floor_log2_product(c->moduli);
+    if (flood_bits < 1 || flood_bits > kNoiseMaxFlood || flood_bits + 3 > log2_q)
+        return fail(DPFHE_INVALID_ARGUMENT, what, "flood_bits must lie in [1, min(250, floor(log2 Q) - 3)]");
+    if (batch > ((uint64_t)1 << 32) - first_item) return fail(DPFHE_INVALID_ARGUMENT, what, "first_item + batch must be <= 2^32");
+    const size_t poly = (size_t)c->n_limbs << c->log2n, npolys = batch * c->n_limbs;
+    if (!ntt_grid_fits(c, 2 * npolys) || (batch << (c->log2n - 1)) > kMaxGrid * (size_t)256)
+        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (overlaps(d_work, 3 * batch * poly, d_ct2, 2 * batch * poly) || overlaps(d_work, 3 * batch * poly, d_pk, 2 * poly) ||
+        overlaps(d_ct2, 2 * batch * poly, d_pk, 2 * poly))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "the work buffer, the ciphertexts and the public key must not overlap");
+    DPFHE_ON_DEVICE(c, what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t* u = d_work;
+    uint64_t* prod = d_work + batch * poly;
+    NoiseArgs a;
+    if (int rc = noise_args(what, u, batch, 1, 0, kNoiseTernary, 0, 0, seed, first_item, 0, c->n_limbs, c->log2n, a)) return rc;
+    if (int rc = noise_launch(what, c, u, batch, a, s)) return rc;
+    if (int rc = ntt_launch(c, false, u, u, npolys, s)) return rc;
+    (void)launch_dyadic(c, DY_MUL, prod, u, d_pk, npolys, s, (int)c->n_limbs);
+    (void)launch_dyadic(c, DY_MUL, prod + batch * poly, u, d_pk + poly, npolys, s, (int)c->n_limbs);
+    if (int rc = check_launch("dyadic kernel launch")) return rc;
+    if (int rc = ntt_launch(c, true, prod, prod, 2 * npolys, s)) return rc;
+    if (launch_add_products(d_ct2, prod, batch, c->n_limbs, (int)c->log2n, c->lc, s)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (int rc = check_launch("add_products kernel launch")) return rc;
+    if (int rc = noise_args(what, d_ct2, batch, 2, 0, kNoiseFlood, flood_bits, 2, seed, first_item, DPFHE_NOISE_ADD, c->n_limbs, c->log2n, a)) return rc;
+    if (int rc = noise_launch(what, c, d_ct2, batch, a, s)) return rc;
+    if (int rc = noise_args(what, d_ct2, batch, 2, 1, kNoiseCbd21, 0, 1, seed, first_item, DPFHE_NOISE_ADD, c->n_limbs, c->log2n, a)) return rc;
+    return noise_launch(what, c, d_ct2, batch, a, s);
+}

@@ -1,4 +1,5 @@
-// kernels.h - the gfx950 kernels of the FHE hot path (device code; included by dpfhe_cabi.hip only).
+// kernels.h - the gfx950 kernels of the FHE hot path (device code; included through launch_impl.h by the per-policy units k_*.hip, each of which
+// instantiates the kernels of its own policy).
 //
 // A1/A2 batched NTT, A3 dyadic ops, A6 fused ct x ct multiply, A7 ct x pt
 // matvec, A8 shard-local reduce.  No reference counterpart (section 0).  Integer modular arithmetic:
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_kernel(u64* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Round 6: the batched transforms of a context whose limbs run on DIFFERENT arithmetic classes (dpfhe_cabi.hip dpfhe_ctx::classes) in ONE launch.
+// Round 6: the batched transforms of a context whose limbs run on DIFFERENT arithmetic classes (cabi.h dpfhe_ctx::classes) in ONE launch.
 // The tables of such a context live in one blob whose per-limb slots are each in their limb's own format (all twiddle types are 16 bytes, so the
 // strides agree); the limb's class is workgroup-uniform, so the kernel branches once, on a scalar, into that class's transform - the same per-thread
 // code as ntt_fwd_kernel / ntt_inv_kernel.  Four arms - Shoup, fold, f64, scaled fold; a fifth (F64WideArith) spills a few registers at N = 2048 / 4096, so contexts

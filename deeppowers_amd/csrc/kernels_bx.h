@@ -10,7 +10,7 @@ __device__ __forceinline__ u64 bx_canon(u64 v, const LimbConst& lc) {   // any w
     if constexpr (Arith::kFold) return FoldArith::canon(v, lc);
     else return ShoupArith::mul_var(v, 1, lc);
 }
-// The number of source limbs is a TEMPLATE parameter (one kernel per count, dpfhe_cabi.hip dispatches): every index into the digit array v
+// The number of source limbs is a TEMPLATE parameter (one kernel per count, cabi_bx.hip dispatches): every index into the digit array v
 // is a compile-time constant - a run-time one, which is what the unroller leaves behind once 10 x 10 x 2 bodies exceed its budget, puts the
 // array in scratch memory.  The argument block is read in place (never through a reference: that would copy its 3 KiB to scratch as well).
 template <class Arith, int MODE, int NS>

@@ -23,6 +23,7 @@ constexpr size_t kHalvesMinPolys = 2304;   // residue polynomials per launch fro
 // slower below (a workgroup lives four sub-transforms long: 28.7 against 21.4 us at 192).  launch_ntt picks the form by batch size, FoldArith contexts.
 constexpr size_t kQuartersMinPolys = 768;
 constexpr int kMaxGaloisBatch = 64;   // Galois elements travel as kernel arguments, this many per launch
+enum DyOp { DY_MUL = 0, DY_MUL_ADD = 1, DY_ADD = 2, DY_SUB = 3, DY_NEG = 4 };   // the coefficient-wise operations (kernels_poly.h dyadic_kernel)
 
 // return 0, or -1 when log2n has no compiled geometry.  Launch errors are left in hipGetLastError().
 template <class Arith>

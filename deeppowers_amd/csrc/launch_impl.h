@@ -152,22 +152,21 @@ int launch_ct_mul(int log2n, unsigned flags, u64* out3, const u64* a2, const u64
 // The fused multiply in a NAMED form (coefficient domain in and out, FoldArith, N = 4096 / 8192): what dpfhe_ctx_autotune probes and
 // what a context then launches.  kCtMulQuad / kCtMulDual differ in how many transforms share twiddle fetches and LDS
 // buffers (kernels.h), not in results (bit-identical) or HBM traffic (7 residue polynomials per limb).  -1: not compiled for this ring.
+// The default form of a ring degree IS the kernel launch_ct_mul(flags = 0) runs (launch_ct_mul_dom above: same kernel, same arguments), built in the
+// policy's own unit: it is forwarded there, so the tuner times the very object production launches and no kernel is built twice.
 template <class Arith>
 int launch_ct_mul_variant(int log2n, int variant, u64* out3, const u64* a2, const u64* b2, size_t blocks, const DevTables<Arith>& tb, hipStream_t s) {
     if constexpr (!Arith::kFold) return -1;
     else {
-#define CTV_CASE(LN)                                                                                                                                  \
-    case LN:                                                                                                                                          \
-        if (variant == kCtMulQuad) hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, LN, kLoge>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr); \
-        else if (variant == kCtMulDual) hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, LN, kLoge, false>), dim3((unsigned)blocks), dim3(Geo<LN, kLoge>::T), 0, s, out3, a2, b2, tb); \
-        else return -1;                                                                                                                               \
-        return 0
-        switch (log2n) {
-            CTV_CASE(12);
-            CTV_CASE(13);
-            default: return -1;
-        }
-#undef CTV_CASE
+        static_assert(ct_mul_default_variant(12) == kCtMulQuad && ct_mul_default_variant(13) == kCtMulDual, "the non-default forms below");
+        if (log2n != 12 && log2n != 13) return -1;
+        if (variant == ct_mul_default_variant(log2n)) return launch_ct_mul<Arith>(log2n, 0u, out3, a2, b2, blocks, tb, s);
+        if (log2n == 12 && variant == kCtMulDual)
+            hipLaunchKernelGGL((ct_mul_dual_kernel<Arith, 12, kLoge, false>), dim3((unsigned)blocks), dim3(Geo<12, kLoge>::T), 0, s, out3, a2, b2, tb);
+        else if (log2n == 13 && variant == kCtMulQuad)
+            hipLaunchKernelGGL((ct_mul_quad_kernel<Arith, 13, kLoge>), dim3((unsigned)blocks), dim3(Geo<13, kLoge>::T), 0, s, out3, a2, b2, tb, (u64*)nullptr);
+        else return -1;
+        return 0;
     }
 }
 // diagnostics: the quad form with per-workgroup timestamps (kernels.h trace_stamp); N = 4096 only

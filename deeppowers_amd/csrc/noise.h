@@ -123,12 +123,7 @@ inline NoiseLimb noise_limb(u64 q, u32 kind, u32 f) {
     return c;
 }
 
-// device: component a.comp of items [0, batch) of buf [batch][comps][ctx_limbs][N], limbs [a.l0, a.l0 + a.n_limbs): = noise, or += noise mod q with a.add;
-// 0, or -1 if the grid is too large
-int launch_sample_noise(u64* buf, size_t batch, const NoiseArgs& a, hipStream_t s);
-// host twin of the same (every other word untouched)
+// host twin of the device launch (k_noise.hip launch_sample_noise): every other word untouched
 void sample_noise_host(u64* out, size_t batch, const NoiseArgs& a);
-// device: ct [batch][2][L][N] += prod [2][batch][L][N] mod q, word by word (the last step of dpfhe_rerandomize); 0, or -1 if the grid is too large
-int launch_add_products(u64* ct, const u64* prod, size_t batch, u32 n_limbs, int log2n, const LimbConst* lc, hipStream_t s);
 
 }  // namespace dpfhe

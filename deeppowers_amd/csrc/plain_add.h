@@ -46,11 +46,7 @@ DPF_HD u64 plain_add_limb(u64 x, u64 y, const PlainAddLimb& c, bool hi) {
     return csub(x + v, c.q);
 }
 
-// device: out[i][0][l0 .. l0 + n_limbs) = in[i][0] + round(Q plain[i / group] / t), out[i][k >= 1] = in[i][k] of those limbs when out != in.
-// 0, or -1 if the grid is too large for one launch.
-int launch_add_plain_scaled(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 ctx_limbs, size_t group, const PlainAddArgs& a,
-                            hipStream_t s);
-// host twin of the same
+// host twin of the device launch (k_plain_add.hip launch_add_plain_scaled)
 void add_plain_scaled_host(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 ctx_limbs, size_t group, const PlainAddArgs& a);
 
 // ---- plaintext addition on residues (dpfhe_add_plain): the plaintext is an RNS polynomial of the ciphertext's own limbs and domain (an encoder's
@@ -58,11 +54,7 @@ void add_plain_scaled_host(int log2n, u64* out, const u64* in, const u64* plain,
 // x, p canonical: x + p, or x + (q - p), lies in [0, 2q) - one conditional subtraction (p = 0 subtracted: x + q - q = x)
 DPF_HD u64 add_plain_word(u64 x, u64 p, u64 q, u32 negate) { return csub(x + (negate ? q - p : p), q); }
 
-// device: out[i][0] = in[i][0] +- plain[i / group] on every limb, out[i][k >= 1] = in[i][k] when out != in; q_l from lc[l].q.
-// 0, or -1 if the grid is too large for one launch.
-int launch_add_plain(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 n_limbs, size_t group, bool negate,
-                     const LimbConst* lc, hipStream_t s);
-// host twin of the same
+// host twin of the device launch (k_plain_add.hip launch_add_plain)
 void add_plain_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, size_t group, bool negate);
 
 }  // namespace dpfhe

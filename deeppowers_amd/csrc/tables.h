@@ -1,5 +1,5 @@
 // tables.h - host-side construction of the per-limb constants and twiddle tables (A0 of SURVEY.md
-// section 8a).  Plain C++17, no HIP: shared by the C-ABI (dpfhe_cabi.hip, through ctx_tables.h) and tools/emulate.cpp.
+// section 8a).  Plain C++17, no HIP: shared by the C-ABI (cabi_ctx.hip, through ctx_tables.h) and tools/emulate.cpp.
 #pragma once
 #include <vector>
 

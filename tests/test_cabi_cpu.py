@@ -134,6 +134,23 @@ def test_no_kernel_spills_to_scratch(lib):
     assert not bad, f"kernels with scratch: {bad[:5]}"
 
 
+def test_every_kernel_is_built_in_exactly_one_object(lib):
+    """Each kernel has ONE object: a kernel header included from two translation units, or a template instantiated from two, compiles the kernel
+    twice - and then the copy that is probed or profiled need not be the copy that production launches (csrc/cabi.h states the rule).  Across the
+    per-object build logs every `Function Name:` occurs in exactly one log."""
+    import glob
+    logs = glob.glob(os.path.join(ROOT, "deeppowers_amd", "csrc", "build", "*.log"))
+    if not logs:
+        pytest.skip("no build logs (library was not built in this checkout)")
+    where = {}
+    for path in logs:
+        for block in open(path).read().split("Function Name: ")[1:]:
+            where.setdefault(block.split("\n")[0].strip(), set()).add(os.path.basename(path))
+    assert len(where) > 50, "resource-usage remarks missing from the build logs"
+    twice = {name: sorted(w) for name, w in where.items() if len(w) > 1}
+    assert not twice, f"kernels built in more than one object: {twice}"
+
+
 def test_library_sources_read_no_environment_variable():
     """A library's behaviour does not depend on its environment: no getenv anywhere in the product sources (round 6 removed the last one, the split-sweep switch)."""
     import glob

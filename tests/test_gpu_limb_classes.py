@@ -213,7 +213,7 @@ def test_sympy_fixture_replayed_on_the_device(golden_dir):
 @pytest.mark.parametrize("name,log2n,widths", [("f64", 12, (30, 31, 40, 46)), ("f64_n8192", 13, (45, 46, 33)), ("f64_wide", 12, (49, 49, 48)), ("fold_scaled", 12, (59, 58, 59)),
                                                ("fold_scaled_n8192", 13, (59, 58, 57)), ("f64_n1024", 10, (30, 30))], ids=lambda v: v if isinstance(v, str) else None)
 def test_key_switching_runs_on_the_class_of_a_uniform_context(name, log2n, widths):
-    """a context whose limbs all share ONE class key-switches on that class's kernels (dpfhe_cabi.hip with_policy: the generic forms of relin_kernel /
+    """a context whose limbs all share ONE class key-switches on that class's kernels (cabi.h with_policy: the generic forms of relin_kernel /
     hoisted_ks_kernel / ntt_inv_galois_kernel instantiated for the class): relinearisation, the plain key switch behind an automorphism, hybrid key switching
     with 2- and 3-component inputs, hoisted rotations - every word against the oracle"""
     from deeppowers_amd.evaluator import Ciphertext, Context, Evaluator, to_device, to_host

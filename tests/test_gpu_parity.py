@@ -213,7 +213,7 @@ def test_dyadic_ops_vs_oracle(rigs, name):
 
 @pytest.mark.parametrize("name", ["n4096", "shoup12"])
 def test_dyadic_ops_beyond_the_infinity_cache_take_the_non_temporal_path(rigs, name):
-    """A launch that touches more than the 256 MiB Infinity Cache holds runs the non-temporal variant of the dyadic kernel (dpfhe_cabi.hip
+    """A launch that touches more than the 256 MiB Infinity Cache holds runs the non-temporal variant of the dyadic kernel (cabi_poly.hip
     launch_dy): same words.  768 x L residue polynomials of 32 KiB per operand = 96 MiB (72 with three limbs) per stream."""
     r = rigs(name)
     L, n = r.p.n_limbs, r.p.n

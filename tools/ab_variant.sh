@@ -5,7 +5,7 @@ set -e
 TAG=$1; shift
 cd "$(dirname "$0")/../deeppowers_amd/csrc"
 D=build/ab_$TAG; mkdir -p $D
-for src in dpfhe_cabi.hip k_*.hip; do
+for src in *.hip; do
   f=${src%.hip}
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Rpass-analysis=kernel-resource-usage "$@" -c -o $D/$f.o $f.hip 2> $D/$f.log &
 done

@@ -1,5 +1,5 @@
 """Relinearisation throughput per limb class at N = 4096, L = 4 (tool): 2048 three-component ciphertexts, RNS-digit keys - the key switch that follows the
-metric op - on contexts whose limbs all share one class (the class's own key-switching kernels, dpfhe_cabi.hip with_policy) and on the generic class."""
+metric op - on contexts whose limbs all share one class (the class's own key-switching kernels, cabi.h with_policy) and on the generic class."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deeppowers_amd.evaluator import Ciphertext, Context, Evaluator
