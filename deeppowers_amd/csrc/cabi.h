@@ -2,7 +2,10 @@
 // arithmetic policies and limb classes, and the few launch functions one family borrows from another.  The units of include/dpfhe.h:
 //   cabi_ctx.hip        contexts, their tables, the fused multiply's tuner, the scratch arenas, dpfhe_strerror / dpfhe_last_error
 //   cabi_poly.hip       transforms, coefficient-wise operations, copy                                  (kernels_poly.h)
-//   dpfhe_cabi.hip      multiply, key switching, rescaling; rotations; matrix-vector products, shard-local sums  (kernels_misc.h, kernels_large.h)
+//   cabi_mul.hip        ciphertext multiply and its traced form                                        (kernels_mul.h)
+//   cabi_keyswitch.hip  key switching (RNS-digit and hybrid keys), rescales, host twins of the fused rescales  (kernels_keyswitch.h)
+//   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations                            (kernels_rotate.h)
+//   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)
 //   cabi_bx.hip         base extension, scale-and-round                                                (base_ext.h; kernels in k_bx_*.hip)
 //   cabi_comm.hip       the RCCL communicator
 //   k_expand / k_plain_add / k_compact / k_noise / k_encode / k_cencode.hip   each newer family whole: kernel, launcher, host twin, entries
@@ -192,7 +195,7 @@ inline bool class_mixture(const dpfhe_ctx* c) { return c->classes && c->uniform_
 // The policy of the KEY-SWITCHING kernels (relin_kernel, hoisted_ks_kernel, ntt_inv_galois_kernel) of a context that is NOT a mixture: fold for the pinned
 // primes; the class's own for a context whose limbs all share one class (round 6: the generic forms of those kernels with that class's transforms and
 // products - an all-f64 context no longer key-switches at the generic kernels' rate); the generic policy on the generic tables otherwise.  A mixture does
-// not come here: relin_launch (dpfhe_cabi.hip) / with_policy_or_classes below launch it once per class, on the class blob.  fn(tables) launches.
+// not come here: relin_launch (cabi_keyswitch.hip) / with_policy_or_classes below launch it once per class, on the class blob.  fn(tables) launches.
 template <class Fn>
 static int with_policy(const dpfhe_ctx* c, Fn fn) {
     if (c->fold) return fn(c->foldt);
@@ -273,3 +276,9 @@ inline int ntt_launch(dpfhe_ctx* c, bool inverse, uint64_t* out, const uint64_t*
 }
 // dyadic_kernel<op> over `npolys` residue polynomials (DyOp; b_period as in kernels_poly.h); -1: no such op                                  // cabi_poly.hip
 int launch_dyadic(const dpfhe_ctx* c, int op, u64* out, const u64* a, const u64* b, size_t npolys, hipStream_t s, int b_period);
+// what the rotations borrow from key switching (cabi_keyswitch.hip, which describes each at its definition): the division by P, the digit lift, and the
+// hybrid key switch itself with every check of its entries (`what` names the caller in its reports)
+void launch_rescale(const dpfhe_ctx* c, size_t blocks, hipStream_t s, u64* out, const u64* in, const u64* add, int add_comps, int add_mask);
+void launch_lift_digits(const dpfhe_ctx* c, size_t grid, hipStream_t s, u64* digits, const u64* comp, size_t item_stride, int chunks);
+int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_out2, const uint64_t* d_in, const uint64_t* d_key, uint64_t* d_work, size_t batch,
+                      void* stream, size_t key_stride = 0, unsigned key_group = 1, bool drop_last = false);

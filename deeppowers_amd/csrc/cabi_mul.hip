@@ -1,0 +1,83 @@
+// cabi_mul.hip - the C ABI's ciphertext multiply: dpfhe_ct_mul on the fused kernels of kernels.h (launch.h), composed above N = 8192 over
+// kernels_mul.h, and its traced diagnostic form.  cabi.h lists the other units and states the ABI's conventions.
+#include "cabi.h"
+#include "kernels_mul.h"
+
+// ---- ring degrees above 8192: the fused kernels stop there (kernels_mul.h); the same operation composed from the batched transforms
+// and a one-pass streaming kernel.  Its scratch comes from per-stream arenas (cabi.h StreamScratch).
+
+static int ct_mul_composed_slice(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch, uint32_t flags, hipStream_t s) {
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n, poly = L * n;
+    const int chunks = chunks_of(n);
+    const size_t grid = batch * L * (size_t)chunks;
+    if (grid > kMaxGrid || !ntt_grid_fits(c, batch * 3 * L)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "batch too large for one launch");
+    StreamScratch ws(c, s);
+    const u64 *pa = d_a2, *pb = d_b2;
+    if (!(flags & DPFHE_IN_NTT)) {   // transformed copies of the operands: [a | b], 2 * batch * 2 * L residue polynomials
+        const bool square = d_a2 == d_b2;
+        if (int rc = ws.alloc((square ? 2 : 4) * batch * poly, "dpfhe_ct_mul (scratch for the transformed operands)")) return rc;
+        if (int rc = ntt_launch(c, false, ws.p, d_a2, batch * 2 * L, s)) return rc;
+        if (!square) if (int rc = ntt_launch(c, false, ws.p + 2 * batch * poly, d_b2, batch * 2 * L, s)) return rc;
+        pa = ws.p;
+        pb = square ? ws.p : ws.p + 2 * batch * poly;
+    }
+    with_ctx_arith(c, [&](auto arith) { hipLaunchKernelGGL((tensor3_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, s, d_out3, pa, pb, c->lc, (int)L, (int)n, chunks); });
+    if (int rc = check_launch("tensor product kernel launch")) return rc;
+    if (!(flags & DPFHE_OUT_NTT)) return ntt_launch(c, true, d_out3, d_out3, batch * 3 * L, s);
+    return DPFHE_SUCCESS;
+}
+
+static int ct_mul_composed(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch, uint32_t flags, hipStream_t s) {
+    const size_t poly = (size_t)c->n_limbs << c->log2n, per = slice_items(c, batch, 4 * poly);
+    return for_slices(batch, per, [&](size_t i, size_t m) { return ct_mul_composed_slice(c, d_out3 + i * 3 * poly, d_a2 + i * 2 * poly, d_b2 + i * 2 * poly, m, flags, s); });
+}
+
+// output items are 3 L N words apart, input items 2 L N: a workgroup would overwrite operands another one has not read yet
+static bool ct_mul_output_overlaps(const dpfhe_ctx* c, const uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch) {
+    const size_t poly = (size_t)c->n_limbs << c->log2n;
+    return overlaps(d_out3, batch * 3 * poly, d_a2, batch * 2 * poly) || overlaps(d_out3, batch * 3 * poly, d_b2, batch * 2 * poly);
+}
+
+extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch,
+                            uint32_t flags, void* stream) {
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "null context");
+    if (flags & ~(DPFHE_IN_NTT | DPFHE_OUT_NTT)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "unknown flag");
+    if (batch == 0) return DPFHE_SUCCESS;
+    if (!d_out3 || !d_a2 || !d_b2 || misaligned(d_out3) || misaligned(d_a2) || misaligned(d_b2))
+        return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "null or misaligned buffer");
+    if (ct_mul_output_overlaps(c, d_out3, d_a2, d_b2, batch)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "output overlaps an operand");
+    const size_t blocks = batch * c->n_limbs;
+    if (blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ct_mul", "batch too large for one launch");
+    DPFHE_ON_DEVICE(c, "dpfhe_ct_mul");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->log2n > kMaxFusedLog2N) return ct_mul_composed(c, d_out3, d_a2, d_b2, batch, flags, s);
+    if (flags == 0 && c->fold) {   // coefficient domain in and out: the form chosen for this box (bit-identical results)
+        const int v = c->ct_mul_variant.load(std::memory_order_relaxed);
+        if (v != ct_mul_default_variant((int)c->log2n) && ct_mul_variant_compiled(c, v)) {
+            if (launch_ct_mul_variant<FoldArith>((int)c->log2n, v, d_out3, d_a2, d_b2, blocks, c->foldt, s)) return fail(DPFHE_INVALID_STATE, "dpfhe_ct_mul", "variant not compiled");
+            return check_launch("ct_mul kernel launch");
+        }
+    }
+    int rc;
+    if (c->classes) {   // one launch per arithmetic class of the limbs (dpfhe_ctx::classes)
+        const size_t pairs = blocks / c->n_limbs;
+        rc = for_each_class(c, c->n_limbs, [&](const auto& tb) { return launch_ct_mul((int)c->log2n, flags, d_out3, d_a2, d_b2, pairs * (size_t)tb.n_active, tb, s); });
+    } else {
+        rc = with_ctx_arith(c, [&](auto arith) { return launch_ct_mul((int)c->log2n, flags, d_out3, d_a2, d_b2, blocks, tables_of<decltype(arith)>(c), s); });
+    }
+    if (rc) return fail(DPFHE_INVALID_STATE, "dpfhe_ct_mul", "no kernel geometry for this log2_n");
+    return check_launch("ct_mul kernel launch");
+}
+
+// diagnostics: the quad form with per-workgroup timestamps (kernels.h ct_mul_quad_kernel<..., TRACE>); FoldArith contexts at N = 4096
+extern "C" int dpfhe_debug_ct_mul_trace(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch, uint64_t* d_trace, void* stream) {
+    if (!c || !d_out3 || !d_a2 || !d_b2 || !d_trace) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_debug_ct_mul_trace", "null argument");
+    if (!c->fold || c->log2n != 12) return fail(DPFHE_INVALID_STATE, "dpfhe_debug_ct_mul_trace", "FoldArith contexts at N = 4096 only");
+    const size_t blocks = batch * c->n_limbs;
+    if (batch == 0 || blocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_debug_ct_mul_trace", "bad batch");
+    if (ct_mul_output_overlaps(c, d_out3, d_a2, d_b2, batch)) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_debug_ct_mul_trace", "output overlaps an operand");
+    DPFHE_ON_DEVICE(c, "dpfhe_debug_ct_mul_trace");
+    if (launch_ct_mul_trace<FoldArith>((int)c->log2n, d_out3, d_a2, d_b2, blocks, c->foldt, d_trace, static_cast<hipStream_t>(stream)))
+        return fail(DPFHE_INVALID_STATE, "dpfhe_debug_ct_mul_trace", "not compiled");
+    return check_launch("traced ct_mul kernel launch");
+}

@@ -118,7 +118,7 @@ struct MixedTables {
     unsigned long long cls_map; // 4 bits per limb: tables.h LimbClass
 };
 
-// per limb below the last: the constants of the rescale / modulus switch to the next level (kernels_misc.h rescale_kernel), relative to the LAST prime
+// per limb below the last: the constants of the rescale / modulus switch to the next level (kernels_keyswitch.h rescale_kernel), relative to the LAST prime
 struct RescaleConst {
     u64 h_mod;     // floor(q_last / 2) mod q_i
     u64 inv;       // q_last^-1 mod q_i

@@ -1,7 +1,7 @@
 // fused_rescale.h - the two one-pass rescales of the approximate (CKKS-style) family's activations: a relinearised product that drops P and the last
 // data prime together, and a scalar linear combination of ciphertexts with a constant that drops the last prime.
 //
-//   rescale step (kernels_misc.h rescale_kernel):  R(x, last; q_last)_i = ((x_i + h) - ((last + h) mod q_last)) q_last^-1  mod q_i,  h = floor(q_last / 2)
+//   rescale step (kernels_keyswitch.h rescale_kernel):  R(x, last; q_last)_i = ((x_i + h) - ((last + h) mod q_last)) q_last^-1  mod q_i,  h = floor(q_last / 2)
 //   = round(X / q_last) mod q_i of the value X the limbs hold.  Every step is modular and local to the coefficient, so two of them chain without a
 //   round trip through memory as long as the intermediate word of the NEXT divisor's limb is carried along:
 //
@@ -15,7 +15,7 @@
 // All results are canonical residues, so the words do not depend on how a policy reduces: Arith::kFold picks FoldArith's folds, anything else the
 // generic 128-bit Barrett products, as in every other streaming kernel (cabi.h with_ctx_arith).
 //
-// Shared by the device kernels (kernels_misc.h relin_rescale_kernel, lincomb_rescale_kernel) and the host twins below (dpfhe_relinearize_rescale_pass_host,
+// Shared by the device kernels (kernels_keyswitch.h relin_rescale_kernel, lincomb_rescale_kernel) and the host twins below (dpfhe_relinearize_rescale_pass_host,
 // dpfhe_lincomb_rescale_host): one statement of the arithmetic.  No HIP in here.
 #pragma once
 #include <stddef.h>

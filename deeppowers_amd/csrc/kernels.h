@@ -420,7 +420,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void ntt_inv_galois_kernel(u64*
 // The same at N > 16384, where the inverse transform is split (ntt_top.h): this kernel runs the N1 sub-transforms of a polynomial, the unchanged
 // ntt_top_kernel follows.  Sub-block b of NTT(sigma_g a) is a permutation of ONE sub-block b' of NTT(a) (ntt_core.h galois_sub_block), read with the same
 // coalesced loads and LDS gather as above - only the affine map's offset depends on the sub-block.  b' != b in general, so `out` must not be `in`: an in-place
-// caller stages this kernel's output in scratch (dpfhe_cabi.hip dpfhe_ntt_inv_galois).  One workgroup per (polynomial, sub-block); uniform contexts only.
+// caller stages this kernel's output in scratch (cabi_rotate.hip dpfhe_ntt_inv_galois).  One workgroup per (polynomial, sub-block); uniform contexts only.
 template <class Arith, int LOG_N1>
 __global__ __launch_bounds__(1 << (kSplitLog2N2 - 4)) void ntt_inv_galois_sub_kernel(u64* __restrict__ out, const u64* __restrict__ in, GaloisElts elts,
                                                                                       unsigned polys_per_elt, DevTables<Arith> tb) {
@@ -699,7 +699,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void ct_mul_quad_kernel(u64*
     const u64 ts1 = trace_stamp<TRACE>(x[0]);
     const u64 ts_xl = trace_stamp<TRACE>(x[E - 1]);                             // the whole first operand has arrived
     // opaque from here on (its range restated): hipcc otherwise derives the LDS addresses of every exchange from tid up front and carries them, and tid itself
-    // through the first phase - 256 registers instead of 223 (the thin reduce needs the multiply at 240 or less: kernels_misc.h)
+    // through the first phase - 256 registers instead of 223 (the thin reduce needs the multiply at 240 or less: kernels_linalg.h)
     if constexpr (kLazy29) { asm volatile("" : "+v"(tid)); __builtin_assume(tid >= 0 && tid < B::T); }
     FwdChain4<B, 0>::run(tid, x, y, z, w, lds, lds + W, tw_fwd, lc);
     B::prod_partner(y, lc);     // of every product below exactly one factor is reduced: b0, b1
@@ -1176,6 +1176,6 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), 2) void hoisted_ks2_kernel(u64*
 }
 
 // (N3, round 3's hoisted_qp_kernel - one workgroup per (rotation, limb, token) on the transform geometry - lived here; round 4 replaced it by
-// kernels_misc.h hoisted_qp_stream_kernel: no transform in that pass, so no transform geometry, and 0.99 x instead of 2.3 x its algorithmic bytes.)
+// kernels_rotate.h hoisted_qp_stream_kernel: no transform in that pass, so no transform geometry, and 0.99 x instead of 2.3 x its algorithmic bytes.)
 
 }  // namespace dpfhe

@@ -1,13 +1,10 @@
-// kernels_misc.h - streaming (HBM-bound) kernels: A7 ct x pt matvec, A8 shard-local reduce, rescales, Galois and hoisted rotations (A3: kernels_poly.h).
-// Included by dpfhe_cabi.hip only.  No reference counterpart.
+// kernels_linalg.h - streaming (HBM-bound) kernels of the linear algebra: A7 ct x pt matvec, A8 shard-local reduce.
+// Included by cabi_linalg.hip only.  No reference counterpart.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "fused_rescale.h"
-#include "launch.h"
 #include "modarith.h"
 #include "reduce_thin.h"
-#include "stream_access.h"
 #include "workmap.h"
 
 namespace dpfhe {
@@ -525,485 +522,6 @@ __global__ __launch_bounds__(256) void matvec_scalar_kernel(u64* y, const u64* w
         u64* yp = y + (((row0 + r) * 2) * L + limb) * n + w0;
         *reinterpret_cast<U64x2*>(yp) = U64x2{acc_reduce<Arith>(acc[r][0][0], lc, two64), acc_reduce<Arith>(acc[r][0][1], lc, two64)};
         *reinterpret_cast<U64x2*>(yp + L * n) = U64x2{acc_reduce<Arith>(acc[r][1][0], lc, two64), acc_reduce<Arith>(acc[r][1][1], lc, two64)};
-    }
-}
-
-// N1 (second half): rescale / modulus switch to the next level, coefficient domain.
-//   out_i = ((in_i + h) - ((in_last + h) mod q_last)) * q_last^-1   (mod q_i),  h = floor(q_last / 2),  i < L-1
-// i.e. round(x / q_last) of the CRT-composed value, limb by limb (no big integers).  HBM-bound.
-// (RescaleConst: devtables.h)
-
-// `addend` (optional) is the last step of hybrid key switching: polynomial p = 2*b + comp of the rescaled pair gets
-// component comp of ciphertext b of `addend` ([batch][add_in_comps][L-1][N]) added when bit comp of add_mask is set.
-template <class Arith>
-__global__ __launch_bounds__(256) void rescale_kernel(u64* out, const u64* in, const u64* addend, int add_in_comps, int add_mask,
-                                                      const LimbConst* lcs, const RescaleConst* rcs, int n_limbs, int n, int chunks) {
-    const int Lo = n_limbs - 1;
-    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
-    const int chunk = wk.chunk, limb = wk.limb;
-    const size_t poly = wk.poly;
-    const int w0 = chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    const LimbConst lc = lcs[limb];
-    const RescaleConst rc = rcs[limb];
-    const U64x2 x = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + limb) * n + w0);
-    const U64x2 last = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + Lo) * n + w0);
-    U64x2 r;
-    {
-        const u64 t = csub(last.a + rc.h, rc.q_last);             // (in_last + h) mod q_last
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);   // ... mod q_i
-        const u64 d = sub_mod(add_mod(x.a, rc.h_mod, lc.q), tm, lc.q);
-        r.a = Arith::mul_var(d, rc.inv, lc);
-    }
-    {
-        const u64 t = csub(last.b + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        const u64 d = sub_mod(add_mod(x.b, rc.h_mod, lc.q), tm, lc.q);
-        r.b = Arith::mul_var(d, rc.inv, lc);
-    }
-    if (addend && ((add_mask >> (poly & 1)) & 1)) {
-        const size_t ap = (poly >> 1) * (size_t)add_in_comps + (poly & 1);
-        const U64x2 ad = *reinterpret_cast<const U64x2*>(addend + (ap * Lo + limb) * n + w0);
-        r.a = add_mod(r.a, ad.a, lc.q);
-        r.b = add_mod(r.b, ad.b, lc.q);
-    }
-    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) = r;
-}
-
-// N3 (round 3, deferred divide-by-P): the last step of a baby-step / giant-step sum whose key-switched terms were summed over Q P.
-//   out[b][comp][i] = round(in[b][comp] / P)_i  +  sum_{a < n_add} addends[a][b][0][i]   (comp 0)
-//                                               +  addends[0][b][1][i]                    (comp 1)
-// in: [batch][2][L][N] (coefficient domain, Q P), addends: [n_add][batch][2][Ld][N] (the rotated inner sums: item 0 is the
-// un-rotated one and keeps both components, of the others only c0 survives - their c1 went through the key switch), out:
-// [batch][2][Ld][N].  One pass; the rounding is orc_rescale's.
-template <class Arith>
-__global__ __launch_bounds__(256) void rescale_bsgs_kernel(u64* out, const u64* in, const u64* addends, size_t n_add, size_t batch, const LimbConst* lcs,
-                                                           const RescaleConst* rcs, int n_limbs, int n, int chunks) {
-    const int Lo = n_limbs - 1;
-    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
-    const int chunk = wk.chunk, limb = wk.limb;
-    const size_t poly = wk.poly;   // = b * 2 + comp
-    const int w0 = chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    const LimbConst lc = lcs[limb];
-    const RescaleConst rc = rcs[limb];
-    const U64x2 x = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + limb) * n + w0);
-    const U64x2 last = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + Lo) * n + w0);
-    U64x2 r;
-    {
-        const u64 t = csub(last.a + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        r.a = Arith::mul_var(sub_mod(add_mod(x.a, rc.h_mod, lc.q), tm, lc.q), rc.inv, lc);
-    }
-    {
-        const u64 t = csub(last.b + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        r.b = Arith::mul_var(sub_mod(add_mod(x.b, rc.h_mod, lc.q), tm, lc.q), rc.inv, lc);
-    }
-    const size_t terms = (poly & 1) ? (n_add ? 1 : 0) : n_add;
-    const u64* ap = addends + (poly * Lo + limb) * n + w0;
-    const size_t astride = batch * 2 * Lo * (size_t)n;
-    size_t a = 0;
-    for (; a + 4 <= terms; a += 4) {
-        U64x2 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const U64x2*>(ap + (a + u) * astride);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { r.a = add_mod(r.a, v[u].a, lc.q); r.b = add_mod(r.b, v[u].b, lc.q); }
-    }
-    for (; a < terms; ++a) {
-        const U64x2 v = *reinterpret_cast<const U64x2*>(ap + a * astride);
-        r.a = add_mod(r.a, v.a, lc.q); r.b = add_mod(r.b, v.b, lc.q);
-    }
-    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) = r;
-}
-
-// The last pass of a relinearised product that is rescaled at once (fused_rescale.h (a)): divide the key-switched sums by P, add (c0, c1), divide by the
-// last data prime.  work: [batch][2][L][N] over Q P, in3: [batch][3][Ld][N] (components 0 and 1 are read), out: [batch][2][Ld-1][N].  Per (polynomial,
-// kept limb, chunk): five 16-byte loads per lane (the rows of limb Ld-1 and of P are shared by the Ld-1 workgroups of a polynomial's chunk: re-read
-// from cache) and one store.  lcs / rcp: the extended context's limb and rescale constants (relative to P), rcq: [Ld-1] relative to q_{Ld-1}.
-template <class Arith>
-__global__ __launch_bounds__(256) void relin_rescale_kernel(u64* out, const u64* __restrict__ work, const u64* __restrict__ in3, const LimbConst* lcs,
-                                                            const RescaleConst* rcp, const RescaleConst* rcq, int n_limbs, int n, int chunks) {
-    const int Ld = n_limbs - 1, Lo = Ld - 1;
-    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
-    const int limb = wk.limb;
-    const size_t poly = wk.poly;   // = b * 2 + comp
-    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    const RelinRescaleConsts k{lcs[limb], lcs[Lo], rcp[limb], rcp[Lo], rcq[limb]};
-    const u64* wp = work + poly * n_limbs * (size_t)n + w0;
-    const u64* cp = in3 + ((poly >> 1) * 3 + (poly & 1)) * Ld * (size_t)n + w0;
-    const U64x2 wi = *reinterpret_cast<const U64x2*>(wp + (size_t)limb * n);
-    const U64x2 wl = *reinterpret_cast<const U64x2*>(wp + (size_t)Lo * n);
-    const U64x2 wP = *reinterpret_cast<const U64x2*>(wp + (size_t)Ld * n);
-    const U64x2 ci = *reinterpret_cast<const U64x2*>(cp + (size_t)limb * n);
-    const U64x2 cl = *reinterpret_cast<const U64x2*>(cp + (size_t)Lo * n);
-    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) =
-        U64x2{relin_rescale_word<Arith>(wi.a, wl.a, wP.a, ci.a, cl.a, k), relin_rescale_word<Arith>(wi.b, wl.b, wP.b, ci.b, cl.b, k)};
-}
-
-// Scalar linear combination of K ciphertexts per item, a constant on X^0 of component 0, and the rescale (fused_rescale.h (b)):
-//   out[t][c] = round((sum_{k<K} w_k x[k][t][c] + [c = 0] w_K) / q_{L-1}).   x: [K][batch][2][L][N], w: [K + 1][L], out: [batch][2][L-1][N].
-// Per (polynomial, kept limb, chunk): 2 K 16-byte loads per lane (limb i and the last limb of every term, four terms in flight) and one store; the
-// weights are workgroup-uniform (scalar loads).
-template <class Arith>
-__global__ __launch_bounds__(256) void lincomb_rescale_kernel(u64* out, const u64* __restrict__ x, const u64* __restrict__ w, const LimbConst* lcs,
-                                                              const RescaleConst* rcs, int n_limbs, int n, int chunks, int n_terms, size_t batch) {
-    const int Lo = n_limbs - 1;
-    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
-    const int limb = wk.limb;
-    const size_t poly = wk.poly;   // = t * 2 + c
-    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    const LimbConst lc = lcs[limb], lcl = lcs[Lo];
-    const size_t term = batch * 2 * n_limbs * (size_t)n;
-    const u64* xi = x + (poly * n_limbs + limb) * n + w0;
-    const u64* xl = x + (poly * n_limbs + Lo) * n + w0;
-    LazySum si[2] = {{0, 0}, {0, 0}}, sl[2] = {{0, 0}, {0, 0}};
-    int k = 0;
-    for (; k + 4 <= n_terms; k += 4) {
-        U64x2 vi[4], vl[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            vi[u] = *reinterpret_cast<const U64x2*>(xi + (k + u) * term);
-            vl[u] = *reinterpret_cast<const U64x2*>(xl + (k + u) * term);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const u64 wi = w[(k + u) * n_limbs + limb], wl = w[(k + u) * n_limbs + Lo];
-            lazy_mac(si[0], wi, vi[u].a); lazy_mac(si[1], wi, vi[u].b);
-            lazy_mac(sl[0], wl, vl[u].a); lazy_mac(sl[1], wl, vl[u].b);
-        }
-    }
-    for (; k < n_terms; ++k) {
-        const U64x2 vi = *reinterpret_cast<const U64x2*>(xi + k * term);
-        const U64x2 vl = *reinterpret_cast<const U64x2*>(xl + k * term);
-        const u64 wi = w[k * n_limbs + limb], wl = w[k * n_limbs + Lo];
-        lazy_mac(si[0], wi, vi.a); lazy_mac(si[1], wi, vi.b);
-        lazy_mac(sl[0], wl, vl.a); lazy_mac(sl[1], wl, vl.b);
-    }
-    if (!(poly & 1) && w0 == 0) { lazy_add(si[0], w[n_terms * n_limbs + limb]); lazy_add(sl[0], w[n_terms * n_limbs + Lo]); }
-    const RescaleConst rc = rcs[limb];
-    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) =
-        U64x2{rescale_word<Arith>(lazy_reduce<Arith>(si[0], lc), lazy_reduce<Arith>(sl[0], lcl), lc, rc),
-              rescale_word<Arith>(lazy_reduce<Arith>(si[1], lc), lazy_reduce<Arith>(sl[1], lcl), lc, rc)};
-}
-
-// N3 (round 3): a ciphertext in the NTT domain on the data limbs, lifted to the extended basis as P * ct: word * (P mod q_i) on the
-// data limbs, 0 on the special limb (P = 0 mod P).  in: [n_polys][Ld][N] -> out: [n_polys][L][N].  The un-rotated baby step.
-template <class Arith>
-__global__ __launch_bounds__(256) void lift_qp_kernel(u64* out, const u64* in, const LimbConst* lcs, u64 p_special, int n_limbs, int n, int chunks) {
-    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
-    const int chunk = wk.chunk, limb = wk.limb;
-    const size_t poly = wk.poly;
-    const int w0 = chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    U64x2 r{0, 0};
-    if (limb < n_limbs - 1) {
-        const LimbConst lc = lcs[limb];
-        const u64 pmod = Arith::kFold ? FoldArith::canon(p_special, lc) : ShoupArith::mul_var(p_special, 1, lc);
-        const U64x2 v = *reinterpret_cast<const U64x2*>(in + (poly * (n_limbs - 1) + limb) * n + w0);
-        r.a = Arith::mul_var(v.a, pmod, lc);
-        r.b = Arith::mul_var(v.b, pmod, lc);
-    }
-    *reinterpret_cast<U64x2*>(out + (poly * n_limbs + limb) * n + w0) = r;
-}
-
-// (the exact base extension / scale-and-round kernels live in kernels_bx.h: one kernel per source-limb count, compiled in their own
-// translation units k_bx_fold.hip / k_bx_shoup.hip)
-
-// ------------------------------------------------------------------------------------------------
-// N3, round 4: the baby-step pass of the double-hoisted packed products as a STREAM (replaces kernels.h hoisted_qp_kernel, whose one
-// workgroup per (rotation, limb, token) re-read the digit images once per rotation: 2.3 x its algorithmic bytes in L2 misses).
-//   out[(r, t)] = ( sum_j perm_g(digit_{t,j}) (.) key_{r,j,0} + P perm_g(NTT(c0_t)),  sum_j perm_g(digit_{t,j}) (.) key_{r,j,1} )   over all L limbs.
-// No transform, so no NTT geometry: a workgroup is 256 threads x PP 16-byte pairs = one SEGMENT of 512 PP words of one (rotation, limb, token).
-// Keys and results are read / written in natural (forward-output) order, lane-contiguous; only the digit words are permuted, and sigma_g
-// in forward-output order maps every aligned pair ONTO an aligned pair (swapped or not) and every aligned segment onto an aligned segment:
-//   pair m -> pair m' = brv((c - 1) / 2),  c = g (2 brv(m) + 1) mod 2N reduced mod N,  words swapped iff that product is >= N
-// (brv over log2 N - 1 bits) - one 16-byte gather per pair inside ONE source segment, indices computed once per thread and reused for
-// all digits.  What makes the traffic algorithmic is WHERE workgroups run: ids are dealt to the 8 XCDs round-robin, and XCD x gets, one
-// block of 16 rotations x n_items tokens at a time, all workgroups of one (limb, SOURCE segment): the block's workgroups are resident
-// together (5 per CU), every key segment is fetched from HBM once for its n_items tokens and every digit segment once for its 16 rotations.
-// ------------------------------------------------------------------------------------------------
-// (kQpPairs, kQpRotGroup, the id layout and the pair map: workmap.h QpMap)
-struct QpElts { unsigned v[kMaxGaloisBatch]; };
-
-template <class Arith, int PP>
-__global__ __launch_bounds__(256) void hoisted_qp_stream_kernel(u64* __restrict__ out, const u64* __restrict__ digits, const u64* __restrict__ xntt,
-                                                                const u64* __restrict__ keys, size_t key_stride, QpElts elts, unsigned n_rot, unsigned n_items,
-                                                                u64 p_special, const LimbConst* __restrict__ lcs, int n_limbs, int log2n) {
-    const int L = n_limbs, Ld = L - 1;
-    const QpGeo geo = QpMap::geo(log2n, PP);
-    // id -> (XCD x, block of one (limb, source segment, rotation group), rotation in group, token)
-    const QpWork wk = QpMap::decode(blockIdx.x, geo, (unsigned)L, n_rot, n_items);
-    if (!wk.live) return;
-    const int limb = wk.limb;
-    const unsigned rot = wk.rot, token = wk.token;
-    const unsigned g = elts.v[rot];
-    const LimbConst lc = lcs[limb];
-    const size_t N = geo.n;
-    unsigned ms[PP], mo[PP];
-    bool sw[PP], ok[PP];
-#pragma unroll
-    for (int c = 0; c < PP; ++c) {
-        const QpPair pm = QpMap::pair_map(g, wk.sseg, (unsigned)c * 256u + threadIdx.x, geo);
-        mo[c] = pm.out; ms[c] = pm.src; sw[c] = pm.swap; ok[c] = pm.ok;
-    }
-    const size_t item = (size_t)rot * n_items + token;
-    const u64* dig = digits + ((size_t)token * Ld * L + limb) * N;      // digit j at + j L N
-    const u64* evk = keys + (size_t)rot * key_stride + (size_t)limb * N; // key (j, comp) at + (j 2 + comp) L N
-    auto gather = [&](U64x2 (&x)[PP], const u64* tile) {
-#pragma unroll
-        for (int c = 0; c < PP; ++c)
-            if (ok[c]) x[c] = reinterpret_cast<const U64x2*>(tile)[ms[c]];
-    };
-    auto unswap = [&](U64x2 (&x)[PP]) {
-#pragma unroll
-        for (int c = 0; c < PP; ++c) { const u64 a = x[c].a, b = x[c].b; x[c].a = sw[c] ? b : a; x[c].b = sw[c] ? a : b; }
-    };
-    auto stream = [&](U64x2 (&e)[PP], const u64* tile) {
-#pragma unroll
-        for (int c = 0; c < PP; ++c)
-            if (ok[c]) e[c] = reinterpret_cast<const U64x2*>(tile)[mo[c]];
-    };
-    u64* o0 = out + ((item * 2 + 0) * L + limb) * N;
-    u64* o1 = out + ((item * 2 + 1) * L + limb) * N;
-    U64x2 x[PP], e0[PP], e1[PP];
-#pragma unroll
-    for (int c = 0; c < PP; ++c) { x[c] = U64x2{0, 0}; e0[c] = U64x2{0, 0}; e1[c] = U64x2{0, 0}; }
-    if constexpr (Arith::kFold) {
-        // Lazy inner products on 30-bit halves (modarith.h Dot30: FOUR multiply-adds per term, the split of a digit word shared by both key
-        // components, one fold per kDot30Period terms) instead of one mul60 (15 instructions) per product: the pass is VALU-bound once its
-        // traffic is algorithmic.  All operands are canonical residues (< 2^60), which is what split30 needs.
-        typedef FoldArith::Dot30 Dot;
-        typedef FoldArith::Half30 Half;
-        Dot s0[PP][2], s1[PP][2];
-        u64 r0[PP][2], r1[PP][2];
-#pragma unroll
-        for (int c = 0; c < PP; ++c)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { s0[c][h] = Dot{0, 0, 0}; s1[c][h] = Dot{0, 0, 0}; r0[c][h] = 0; r1[c][h] = 0; }
-        int terms = 0;
-        auto fold_all = [&]() {
-#pragma unroll
-            for (int c = 0; c < PP; ++c)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    r0[c][h] = FoldArith::dot30_fold(s0[c][h], r0[c][h], lc); s0[c][h] = Dot{0, 0, 0};
-                    r1[c][h] = FoldArith::dot30_fold(s1[c][h], r1[c][h], lc); s1[c][h] = Dot{0, 0, 0};
-                }
-            terms = 0;
-        };
-        if (limb < Ld) {   // component 0 starts with P perm_g(NTT(c0)) on the data limbs (P = 0 on the special limb)
-            U64x2 c0[PP];
-#pragma unroll
-            for (int c = 0; c < PP; ++c) c0[c] = U64x2{0, 0};
-            gather(c0, xntt + ((size_t)token * 2 * Ld + limb) * N);
-            gather(x, dig);
-            stream(e0, evk);
-            stream(e1, evk + (size_t)L * N);
-            unswap(c0);
-            const Half hp = FoldArith::split30(FoldArith::canon(p_special, lc));
-#pragma unroll
-            for (int c = 0; c < PP; ++c) {
-                FoldArith::dot30_mac(s0[c][0], FoldArith::split30(c0[c].a), hp);
-                FoldArith::dot30_mac(s0[c][1], FoldArith::split30(c0[c].b), hp);
-            }
-            terms = 1;
-        } else {
-            gather(x, dig);
-            stream(e0, evk);
-            stream(e1, evk + (size_t)L * N);
-        }
-#pragma unroll 1
-        for (int j = 0; j < Ld; ++j) {
-            U64x2 xn[PP], e0n[PP], e1n[PP];
-            const int jn = j + 1 < Ld ? j + 1 : j;   // the last iteration re-requests its own segments (cache hits) instead of branching
-#pragma unroll
-            for (int c = 0; c < PP; ++c) { xn[c] = x[c]; e0n[c] = e0[c]; e1n[c] = e1[c]; }
-            gather(xn, dig + (size_t)jn * L * N);
-            stream(e0n, evk + (size_t)(jn * 2) * L * N);
-            stream(e1n, evk + (size_t)(jn * 2 + 1) * L * N);
-            unswap(x);
-            if (terms == FoldArith::kDot30Period) fold_all();   // workgroup-uniform
-            ++terms;
-#pragma unroll
-            for (int c = 0; c < PP; ++c) {
-                const Half xa = FoldArith::split30(x[c].a), xb = FoldArith::split30(x[c].b);
-                FoldArith::dot30_mac(s0[c][0], xa, FoldArith::split30(e0[c].a));
-                FoldArith::dot30_mac(s0[c][1], xb, FoldArith::split30(e0[c].b));
-                FoldArith::dot30_mac(s1[c][0], xa, FoldArith::split30(e1[c].a));
-                FoldArith::dot30_mac(s1[c][1], xb, FoldArith::split30(e1[c].b));
-            }
-#pragma unroll
-            for (int c = 0; c < PP; ++c) { x[c] = xn[c]; e0[c] = e0n[c]; e1[c] = e1n[c]; }
-        }
-        fold_all();
-#pragma unroll
-        for (int c = 0; c < PP; ++c) {
-            if (!ok[c]) continue;
-            // written once, read by the next launch: around the caches the keys and digits live in
-            st_vec<true>(reinterpret_cast<U64x2*>(o0) + mo[c], U64x2{FoldArith::canon_small(r0[c][0], lc), FoldArith::canon_small(r0[c][1], lc)});
-            st_vec<true>(reinterpret_cast<U64x2*>(o1) + mo[c], U64x2{FoldArith::canon_small(r1[c][0], lc), FoldArith::canon_small(r1[c][1], lc)});
-        }
-    } else {
-        U64x2 acc0[PP], acc1[PP];
-#pragma unroll
-        for (int c = 0; c < PP; ++c) { acc0[c] = U64x2{0, 0}; acc1[c] = U64x2{0, 0}; }
-        auto accw = [&](u64 acc, u64 a, u64 b) -> u64 { return add_mod(acc, ShoupArith::mul_var(a, b, lc), lc.q); };
-        if (limb < Ld) {
-            U64x2 c0[PP];
-#pragma unroll
-            for (int c = 0; c < PP; ++c) c0[c] = U64x2{0, 0};
-            gather(c0, xntt + ((size_t)token * 2 * Ld + limb) * N);
-            unswap(c0);
-            const u64 pmod = ShoupArith::mul_var(p_special, 1, lc);
-#pragma unroll
-            for (int c = 0; c < PP; ++c) { acc0[c].a = ShoupArith::mul_var(c0[c].a, pmod, lc); acc0[c].b = ShoupArith::mul_var(c0[c].b, pmod, lc); }
-        }
-#pragma unroll 1
-        for (int j = 0; j < Ld; ++j) {
-            gather(x, dig + (size_t)j * L * N);
-            stream(e0, evk + (size_t)(j * 2) * L * N);
-            stream(e1, evk + (size_t)(j * 2 + 1) * L * N);
-            unswap(x);
-#pragma unroll
-            for (int c = 0; c < PP; ++c) {
-                acc0[c].a = accw(acc0[c].a, x[c].a, e0[c].a); acc0[c].b = accw(acc0[c].b, x[c].b, e0[c].b);
-                acc1[c].a = accw(acc1[c].a, x[c].a, e1[c].a); acc1[c].b = accw(acc1[c].b, x[c].b, e1[c].b);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < PP; ++c) {
-            if (!ok[c]) continue;
-            st_vec<true>(reinterpret_cast<U64x2*>(o0) + mo[c], acc0[c]);
-            st_vec<true>(reinterpret_cast<U64x2*>(o1) + mo[c], acc1[c]);
-        }
-    }
-}
-// The same pass with EVERY operand segment of the workgroup requested up front (round 4, after the workgroup timeline of the multiply put the
-// cost of a first HBM touch at ~3.6 us): the loop form above keeps one digit's segments in flight while it multiplies the previous one, i.e. it
-// pays that latency once per digit; here a thread owns ONE pair of words, the digit count LD is a template parameter, and the 3 LD + 1 loads of
-// the thread are all issued before the first product (straight-line code: hipcc counts vmcnt exactly).  FoldArith, LD <= 6.
-template <int LD>
-__global__ __launch_bounds__(256) void hoisted_qp_upfront_kernel(u64* __restrict__ out, const u64* __restrict__ digits, const u64* __restrict__ xntt,
-                                                                 const u64* __restrict__ keys, size_t key_stride, QpElts elts, unsigned n_rot, unsigned n_items,
-                                                                 u64 p_special, const LimbConst* __restrict__ lcs, int log2n) {
-    constexpr int L = LD + 1;
-    const QpGeo geo = QpMap::geo(log2n, 1);
-    const QpWork wk = QpMap::decode(blockIdx.x, geo, (unsigned)L, n_rot, n_items);
-    if (!wk.live) return;
-    const int limb = wk.limb;
-    const unsigned rot = wk.rot, token = wk.token;
-    const unsigned g = elts.v[rot];
-    const LimbConst lc = lcs[limb];
-    const size_t N = geo.n;
-    const QpPair pm = QpMap::pair_map(g, wk.sseg, threadIdx.x, geo);
-    if (!pm.ok) return;
-    const unsigned mo = pm.out, ms = pm.src;
-    const bool sw = pm.swap;
-    const size_t item = (size_t)rot * n_items + token;
-    const U64x2* dig = reinterpret_cast<const U64x2*>(digits + ((size_t)token * LD * L + limb) * N) + ms;      // digit j at + j L N words
-    const U64x2* evk = reinterpret_cast<const U64x2*>(keys + (size_t)rot * key_stride + (size_t)limb * N) + mo;  // key (j, comp) at + (j 2 + comp) L N words
-    const size_t tile = (size_t)L * N / 2;   // in 16-byte units
-    U64x2 x[LD], e0[LD], e1[LD], c0{0, 0};
-    const bool data_limb = limb < LD;
-    if (data_limb) c0 = (reinterpret_cast<const U64x2*>(xntt + ((size_t)token * 2 * LD + limb) * N))[ms];
-#pragma unroll
-    for (int j = 0; j < LD; ++j) {
-        x[j] = dig[(size_t)j * tile];
-        e0[j] = evk[(size_t)(2 * j) * tile];
-        e1[j] = evk[(size_t)(2 * j + 1) * tile];
-    }
-    typedef FoldArith::Dot30 Dot;
-    typedef FoldArith::Half30 Half;
-    static_assert(LD + 1 <= FoldArith::kDot30Period, "one fold per accumulator");
-    Dot s0[2] = {Dot{0, 0, 0}, Dot{0, 0, 0}}, s1[2] = {Dot{0, 0, 0}, Dot{0, 0, 0}};
-    if (data_limb) {   // P perm_g(NTT(c0)) on the data limbs
-        const Half hp = FoldArith::split30(FoldArith::canon(p_special, lc));
-        FoldArith::dot30_mac(s0[0], FoldArith::split30(sw ? c0.b : c0.a), hp);
-        FoldArith::dot30_mac(s0[1], FoldArith::split30(sw ? c0.a : c0.b), hp);
-    }
-#pragma unroll
-    for (int j = 0; j < LD; ++j) {
-        const Half xa = FoldArith::split30(sw ? x[j].b : x[j].a), xb = FoldArith::split30(sw ? x[j].a : x[j].b);
-        FoldArith::dot30_mac(s0[0], xa, FoldArith::split30(e0[j].a));
-        FoldArith::dot30_mac(s0[1], xb, FoldArith::split30(e0[j].b));
-        FoldArith::dot30_mac(s1[0], xa, FoldArith::split30(e1[j].a));
-        FoldArith::dot30_mac(s1[1], xb, FoldArith::split30(e1[j].b));
-    }
-    U64x2 r0, r1;
-    r0.a = FoldArith::canon_small(FoldArith::dot30_fold(s0[0], 0, lc), lc); r0.b = FoldArith::canon_small(FoldArith::dot30_fold(s0[1], 0, lc), lc);
-    r1.a = FoldArith::canon_small(FoldArith::dot30_fold(s1[0], 0, lc), lc); r1.b = FoldArith::canon_small(FoldArith::dot30_fold(s1[1], 0, lc), lc);
-    st_vec<true>(reinterpret_cast<U64x2*>(out + ((item * 2 + 0) * L + limb) * N) + mo, r0);
-    st_vec<true>(reinterpret_cast<U64x2*>(out + ((item * 2 + 1) * L + limb) * N) + mo, r1);
-}
-
-// N3, hoisted rotations: digit j of the key-switched component (limb j of c1, coefficient domain, values < q_j) lifted to every
-// limb i of the extended basis: out[j][i][k] = c1[j][k] mod q_i (canonical).  One workgroup per (digit, limb, 512-word chunk).
-template <class Arith>
-// Several input ciphertexts: item t reads c1 + t * in_item_stride and writes out + t * (n_limbs - 1) * n_limbs * n.
-__global__ __launch_bounds__(256) void lift_digits_kernel(u64* out, const u64* c1, size_t in_item_stride, const LimbConst* lcs, int n_limbs, int n, int chunks) {
-    const int chunk = (int)(blockIdx.x % chunks);
-    const int limb = (int)((blockIdx.x / chunks) % n_limbs);
-    const size_t dg = blockIdx.x / chunks / n_limbs, item = dg / (unsigned)(n_limbs - 1), digit = dg % (unsigned)(n_limbs - 1);
-    c1 += item * in_item_stride;
-    out += item * (size_t)(n_limbs - 1) * n_limbs * n;
-    const int w0 = chunk * 512 + threadIdx.x * 2;
-    if (w0 >= n) return;
-    const LimbConst lc = lcs[limb];
-    const U64x2 v = *reinterpret_cast<const U64x2*>(c1 + digit * n + w0);
-    U64x2 r;
-    r.a = Arith::kFold ? FoldArith::canon(v.a, lc) : ShoupArith::mul_var(v.a, 1, lc);
-    r.b = Arith::kFold ? FoldArith::canon(v.b, lc) : ShoupArith::mul_var(v.b, 1, lc);
-    *reinterpret_cast<U64x2*>(out + (digit * n_limbs + limb) * n + w0) = r;
-}
-
-// N3: Galois automorphism a(X) -> a(X^g), g odd, coefficient domain (a signed permutation; HBM-bound).
-// Gather form: out[k] = +in[j] if j = k g^-1 mod 2N < N, else -in[j - N]  (coalesced writes, scattered 8-byte reads).
-__global__ __launch_bounds__(256) void galois_kernel(u64* out, const u64* in, const LimbConst* lcs, int n_limbs, int n, unsigned g_inv) {
-    const size_t p = blockIdx.x;
-    const u64 q = lcs[p % (size_t)n_limbs].q;
-    const unsigned mask2n = 2u * (unsigned)n - 1u;
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const unsigned j = ((unsigned)k * g_inv) & mask2n;
-        const u64 v = in[p * n + (j & ((unsigned)n - 1u))];
-        out[p * n + k] = (j < (unsigned)n) ? v : neg_mod(v, q);
-    }
-}
-
-// batched rotations: item i applies its own element (g_inv.v[i]) to input item i (or to the single input item when
-// in_item_stride == 0); polys_per_item residue polynomials per item
-struct GaloisInvs { unsigned v[kMaxGaloisBatch]; };
-// in_mod > 0: output item i reads input item (item0 + i) % in_mod (several rotations of each of in_mod inputs: rotation-major order)
-// LDS_STAGE (N <= 8192: the polynomial fits 64 KiB of dynamic LDS): the source polynomial is read with coalesced 16-byte loads
-// into LDS and gathered from there - the odd multiplier g^-1 spreads consecutive k over distinct banks - instead of 8-byte
-// global gathers that touch a different cache line per lane (packed GPT-2 layer, 8 tokens per application: 0.278 -> 0.265 ms per token).
-template <bool LDS_STAGE>
-__global__ __launch_bounds__(256) void galois_multi_kernel(u64* out, const u64* in, size_t in_item_stride, const LimbConst* lcs, int n_limbs, int n,
-                                                           int polys_per_item, GaloisInvs g_inv, unsigned in_mod, unsigned item0) {
-    extern __shared__ __attribute__((aligned(16))) u64 stage[];
-    const size_t item = blockIdx.x / (unsigned)polys_per_item, p = blockIdx.x % (unsigned)polys_per_item;
-    const u64 q = lcs[p % (size_t)n_limbs].q;
-    const unsigned mask2n = 2u * (unsigned)n - 1u, gi = g_inv.v[item];
-    const size_t in_item = in_mod ? (item0 + item) % in_mod : item;
-    const u64* src = in + in_item * in_item_stride + p * n;
-    u64* dst = out + (item * polys_per_item + p) * n;
-    if (LDS_STAGE) {
-        for (int k = threadIdx.x * 2; k < n; k += 512) *reinterpret_cast<U64x2*>(stage + k) = *reinterpret_cast<const U64x2*>(src + k);
-        __syncthreads();
-        for (int k = threadIdx.x * 2; k < n; k += 512) {
-            const unsigned j0 = ((unsigned)k * gi) & mask2n, j1 = (j0 + gi) & mask2n;
-            const u64 v0 = stage[j0 & ((unsigned)n - 1u)], v1 = stage[j1 & ((unsigned)n - 1u)];
-            *reinterpret_cast<U64x2*>(dst + k) = U64x2{(j0 < (unsigned)n) ? v0 : neg_mod(v0, q), (j1 < (unsigned)n) ? v1 : neg_mod(v1, q)};
-        }
-        return;
-    }
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const unsigned j = ((unsigned)k * gi) & mask2n;
-        const u64 v = src[j & ((unsigned)n - 1u)];
-        dst[k] = (j < (unsigned)n) ? v : neg_mod(v, q);
     }
 }
 

@@ -1,7 +1,7 @@
 // kernels_quarters.h - the N = 16384 batched transforms on the N = 4096 body (device code; included by launch_impl.h; round 6).
 //
 // SURVEY.md section 8(a) A1/A2 at N = 16384, the ring of the parameter set with a security margin, where every operation is composed from the batched
-// transforms (kernels_large.h).  ntt_quarters.h has the arithmetic: two radix-2 column stages in registers, then the four independent 4096-point
+// transforms (kernels_mul.h, kernels_keyswitch.h).  ntt_quarters.h has the arithmetic: two radix-2 column stages in registers, then the four independent 4096-point
 // sub-transforms one after the other through ONE 38 KiB LDS buffer, 256 threads (4 waves) per workgroup, two workgroups per CU (64 words per thread stay in
 // registers) - where Geo<14, 4>'s 1024-thread workgroup owns its CU alone and nothing overlaps its load, exchange and store phases.  FoldArith contexts.
 #pragma once

@@ -364,7 +364,7 @@ struct FoldArith {
         return r;
     }
 
-    // ---- lazy dot products of CANONICAL residues (the plaintext matrix-vector products, kernels_misc.h) -------------------
+    // ---- lazy dot products of CANONICAL residues (the plaintext matrix-vector products, kernels_linalg.h) -------------------
     // Both factors are split at bit 30 (a = a0 + a1 2^30, all four halves < 2^30), so every partial product is < 2^60 and
     // the three columns  S0 = sum a0 b0,  S1 = sum (a0 b1 + a1 b0),  S2 = sum a1 b1  are plain 64-bit multiply-add chains:
     // FOUR v_mad_u64_u32 per multiply-accumulate and nothing else (the 128-bit accumulators this replaces cost 21 VALU

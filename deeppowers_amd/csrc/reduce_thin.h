@@ -1,4 +1,4 @@
-// reduce_thin.h - the per-thread sum of reduce_thin_kernel (kernels_misc.h), host + device: tools/emulate_reduce.cpp runs this very loop on
+// reduce_thin.h - the per-thread sum of reduce_thin_kernel (kernels_linalg.h), host + device: tools/emulate_reduce.cpp runs this very loop on
 // the CPU with the wrap-around counter armed (tests/test_reduce_thin_cpu.py).  FoldArith limbs only (q = 2^60 - d, d < 2^24).
 #pragma once
 #include <stddef.h>

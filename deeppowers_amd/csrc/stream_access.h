@@ -1,5 +1,5 @@
 // stream_access.h - 16-byte accesses that go around the Infinity Cache (device): what the dyadic kernels (kernels_poly.h) and the baby-step stream of
-// the deferred-division products (kernels_misc.h) share.
+// the deferred-division products (kernels_rotate.h) share.
 #pragma once
 #include <hip/hip_runtime.h>
 

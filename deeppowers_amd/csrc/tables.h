@@ -122,6 +122,18 @@ inline std::vector<u64> subtree_table(const std::vector<u64>& table, int log2n, 
 // q = 2^60 - d with d < 2^24: eligible for FoldArith
 inline bool fold_eligible(u64 q) { return q < (1ull << 60) && ((1ull << 60) - q) < (1ull << 24); }
 
+// the fields of a limb's constants that depend on the modulus alone (ninv / ninv_sh, which need the ring degree, stay 0: build_limb_tables fills them;
+// the host twins of the one-pass kernels, which have no ring to transform in, read none of them)
+inline LimbConst limb_const_of_modulus(u64 q) {
+    LimbConst c{};
+    c.q = q;
+    c.d = fold_eligible(q) ? (1ull << 60) - q : 0;
+    const u128 ratio = (~(u128)0) / q;
+    c.br_hi = (u64)(ratio >> 64); c.br_lo = (u64)ratio;
+    c.two64 = (u64)((((u128)1) << 64) % q);
+    return c;
+}
+
 // Device layout of a twiddle table for kernel geometry (log2n, loge): the sections of the window-0 stages
 // (bit positions < perm_stages = Geo::kPermStages) are transposed from [thread][entry] to [entry][thread] so that a
 // wave fetches lane-contiguous entries (ntt_core.h tw_index).  T = N >> loge threads.
@@ -159,14 +171,9 @@ inline int build_limb_tables(int log2n, u64 q, u64 psi, HostLimbTables& t) {
         pw = h_mulmod(pw, psi, q); ipw = h_mulmod(ipw, ipsi, q);
     }
     LimbConst& c = t.lc;
-    c.q = q;
-    c.d = fold_eligible(q) ? (1ull << 60) - q : 0;
+    c = limb_const_of_modulus(q);
     c.ninv = h_powmod(n % q, q - 2, q);
     c.ninv_sh = h_shoup(c.ninv, q);
-    const u128 ratio = (~(u128)0) / q;
-    c.br_hi = (u64)(ratio >> 64); c.br_lo = (u64)ratio;
-    c.two64 = (u64)((((u128)1) << 64) % q);
-    c.pad1 = 0;
     t.w_last = h_mulmod(t.irp[1], c.ninv, q);
     t.w_last_sh = h_shoup(t.w_last, q);
     return 0;

@@ -1,5 +1,5 @@
 // workmap.h - where a workgroup works: the decode of a workgroup id into its work item, and the grid that decode expects, once per kernel family.
-// No HIP: kernels, launchers (launch_impl.h, dpfhe_cabi.hip) and tools/emulate_workmap.cpp read the same text, so every layout is enumerated on the
+// No HIP: kernels, launchers (launch_impl.h, cabi_*.hip) and tools/emulate_workmap.cpp read the same text, so every layout is enumerated on the
 // CPU (tests/test_work_maps_cpu.py: coverage, dead ids, locality) before it runs on a GPU.  A layout change starts in that test.
 // Each decode keeps the arithmetic and the statement order its kernels had before it moved here (a dead id leaves early where they returned early, and
 // carries a flag where they computed everything first): hipcc's register counts follow that order - MEASUREMENTS.md, "One work map per kernel family".
@@ -104,7 +104,7 @@ struct HoistedMap {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Matrix-vector products (kernels_misc.h matvec_kernel, matvec_multi_kernel, matvec_fold_kernel): outer = slab = (limb, chunk of words), inner =
+// Matrix-vector products (kernels_linalg.h matvec_kernel, matvec_multi_kernel, matvec_fold_kernel): outer = slab = (limb, chunk of words), inner =
 // (row tile, group of right-hand sides), group fastest.  The G workgroups of a row tile read the same W tile and the R workgroups of a group the
 // same x tile at about the same time, on XCD slab % 8: each is fetched from HBM once.
 // ------------------------------------------------------------------------------------------------
@@ -123,7 +123,7 @@ struct MatvecMap {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Baby steps of the double-hoisted products (kernels_misc.h hoisted_qp_stream_kernel, hoisted_qp_upfront_kernel): a workgroup is 256 threads x
+// Baby steps of the double-hoisted products (kernels_rotate.h hoisted_qp_stream_kernel, hoisted_qp_upfront_kernel): a workgroup is 256 threads x
 // `pairs` 16-byte pairs = one segment of one (rotation, limb, token).  outer = combo = (limb, SOURCE segment), inner = (rotation group, rotation in
 // the group, token): XCD combo % 8 gets, one block of kQpRotGroup rotations x n_items tokens at a time, all workgroups of one combo - every key
 // segment is fetched from HBM once for its tokens and every digit segment once for its 16 rotations.

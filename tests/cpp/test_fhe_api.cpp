@@ -128,7 +128,7 @@ static void run(const FheParams& p, size_t batch) {
     orc_ctx_destroy(orc);
 }
 
-// N = 16384: no fused kernels - dpfhe_ct_mul / dpfhe_relinearize compose the batched transforms with streaming kernels (kernels_large.h)
+// N = 16384: no fused kernels - dpfhe_ct_mul / dpfhe_relinearize compose the batched transforms with streaming kernels (kernels_mul.h, kernels_keyswitch.h)
 static void large_ring() {
     FheParams p;
     p.log2_n = 14;

@@ -201,7 +201,7 @@ MATVEC_COLS = (127, 128, 129, 256, 257)
 def test_matvec_accumulation_periods_at_the_class_edges(rig, kind, cols):
     """matvec_plain and matvec_scalar with q - 1 in every word of W and of half of x, rows a multiple of the row tile (8) and not (5).
 
-    The generic matvec (kernels_misc.h matvec_kernel / matvec_scalar_kernel / matvec_multi_kernel) adds 128-bit products and folds its accumulators
+    The generic matvec (kernels_linalg.h matvec_kernel / matvec_scalar_kernel / matvec_multi_kernel) adds 128-bit products and folds its accumulators
     every 128 columns.  That 128 is conservative: with q < 2^60 - 2^24 (shoup60), 256 products of (q - 1)^2 next to a reduced value still stay below
     2^128, but 257 do not.  So this test guards the real limit - a fold period past 256 columns fails at cols = 257 - and does not pin the number 128:
     a period as wrong as 136 would not overflow here.  The fold matvec folds its split-at-bit-30 columns every FoldArith::kDot30Period = 8 terms; on

@@ -218,6 +218,21 @@ def test_rescale_bsgs(ctxs):
     x.no(w, "output overlaps an input", f(h, R[2], R[1], R[2], 1, 1, None))
 
 
+def test_lincomb_rescale(ctxs):
+    x, one = ctxs("n256_l3"), ctxs("n256_l1")
+    f, h, R, w = x.lib.dpfhe_lincomb_rescale, x.h, x.R, "dpfhe_lincomb_rescale"
+    call = lambda o, i, wt, n_terms=2, batch=1: f(h, o, i, wt, n_terms, batch, None)
+    ptrs = (R[0], R[1], R[2])
+    x.ok(w, call(*ptrs))
+    one.no(w, "no limb left to drop", f(one.h, one.R[0], one.R[1], one.R[2], 2, 1, None), STATE)
+    x.no(w, "1 to 16 terms", call(*ptrs, n_terms=0))
+    x.no(w, "1 to 16 terms", call(*ptrs, n_terms=17))
+    x.no(w, "batch must be positive", call(*ptrs, batch=0))
+    x.no(w, "output overlaps an input", call(R[1], R[1], R[2]))
+    x.no(w, "output overlaps an input", call(R[2], R[1], R[2]))
+    x.each_misaligned(w, "misaligned buffer", call, ptrs)             # (the last check: after the shapes and the overlaps)
+
+
 # ---- rotations -------------------------------------------------------------------------------------------------------------------------------------------
 def test_rotate_hybrid_batch_and_grouped(ctxs):
     x, one = ctxs("n256_l3"), ctxs("n256_l1")

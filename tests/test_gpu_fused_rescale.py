@@ -1,5 +1,5 @@
 """-m gpu: the fused rescales on the device (include/dpfhe.h dpfhe_relinearize_rescale_hybrid, dpfhe_lincomb_rescale; csrc/fused_rescale.h, the kernels in
-csrc/kernels_misc.h).
+csrc/kernels_keyswitch.h).
 
 dpfhe_relinearize_rescale_hybrid against the ORACLE, word for word: orc.rescale(orc.keyswitch_hybrid(ct3, key, 3)) - the fused path at N = 256 (one partial
 chunk) and N = 4096 on the pinned fold primes at Ld = 2 (one output limb) and Ld = 4 and on a mixed-class context, the composed path at N = 16384; batches

@@ -792,7 +792,7 @@ def test_config3_full_size_matvec_linearity_and_whole_buffer_oracle(rigs):
 @pytest.mark.parametrize("name", ["fold14", "shoup14", "fold15", "fold16"])
 def test_large_rings_multiply_and_key_switch_composed_behind_the_c_abi(rigs, name):
     """N > 8192 has no fused kernels: dpfhe_ct_mul / dpfhe_relinearize / dpfhe_switch_key compose the batched transforms with one-pass
-    streaming kernels (kernels_large.h; scratch from the stream-ordered allocator) and match the oracle in every domain combination,
+    streaming kernels (kernels_mul.h, kernels_keyswitch.h; scratch from the stream-ordered allocator) and match the oracle in every domain combination,
     also for a squaring (one transformed copy) and on a side stream."""
     r = rigs(name)
     L, n = r.p.n_limbs, r.p.n

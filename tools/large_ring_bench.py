@@ -35,7 +35,7 @@ for ln, polys in ((14, 6144), (15, 4096), (16, 2048)):
         ts = sorted(s.elapsed_time(e) * 1e3 for s, e in evs)
         print(f"{os.path.basename(os.environ.get('DPFHE_AB_LIB', 'HEAD')):14s} N={n:6d} {polys} residue polys ntt_{name}: median {ts[7]:8.1f} us  = {nbytes / ts[7] / 8e6 * 100:5.1f}% of 8 TB/s")
     del x, y
-    # the composed multiply / relinearisation (kernels_large.h): 4 + 3 transforms and one tensor pass; L (L + 2) transforms and three passes
+    # the composed multiply / relinearisation (kernels_mul.h, kernels_keyswitch.h): 4 + 3 transforms and one tensor pass; L (L + 2) transforms and three passes
     pairs = max(1, 256 >> (ln - 14))
     a = Ciphertext(torch.randint(0, 2**62, (pairs, 2, L, n), dtype=torch.int64, device=ctx.device) % q.view(1, 1, L, 1))
     b = Ciphertext(torch.randint(0, 2**62, (pairs, 2, L, n), dtype=torch.int64, device=ctx.device) % q.view(1, 1, L, 1))
