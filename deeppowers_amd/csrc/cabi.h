@@ -4,7 +4,7 @@
 //   cabi_poly.hip       transforms, coefficient-wise operations, copy                                  (kernels_poly.h)
 //   cabi_mul.hip        ciphertext multiply and its traced form                                        (kernels_mul.h)
 //   cabi_keyswitch.hip  key switching (RNS-digit and hybrid keys), rescales, host twins of the fused rescales  (kernels_keyswitch.h)
-//   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations                            (kernels_rotate.h)
+//   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations, the rotate-and-add ladder (kernels_rotate.h, rotate_add.h)
 //   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)
 //   cabi_bx.hip         base extension, scale-and-round                                                (base_ext.h; kernels in k_bx_*.hip)
 //   cabi_comm.hip       the RCCL communicator
@@ -282,3 +282,7 @@ void launch_rescale(const dpfhe_ctx* c, size_t blocks, hipStream_t s, u64* out, 
 void launch_lift_digits(const dpfhe_ctx* c, size_t grid, hipStream_t s, u64* digits, const u64* comp, size_t item_stride, int chunks);
 int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_out2, const uint64_t* d_in, const uint64_t* d_key, uint64_t* d_work, size_t batch,
                       void* stream, size_t key_stride = 0, unsigned key_group = 1, bool drop_last = false);
+// ... and its first pass alone, for a caller with a last pass of its own (the rotate-and-add ladder): the grid check, then the key products into d_work
+bool key_products_fit(const dpfhe_ctx* c, size_t batch, size_t key_stride, unsigned key_group);
+int key_products_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_work, const uint64_t* d_in, const uint64_t* d_key, size_t batch, hipStream_t s,
+                        size_t key_stride, unsigned key_group);

@@ -1,9 +1,10 @@
 // cabi_keyswitch.hip - the C ABI's key switching: RNS-digit and hybrid keys on the fused relin_kernel of kernels.h (launch.h), composed above
 // N = 8192 over kernels_keyswitch.h; the rescales, which are first of all key switching's division by P; the host twins of the fused rescales.
-// The rotations (cabi_rotate.hip) borrow launch_rescale, launch_lift_digits and key_switch_hybrid from here (cabi.h).
+// The rotations (cabi_rotate.hip) borrow launch_rescale, launch_lift_digits, key_switch_hybrid and its first pass key_products_hybrid from here (cabi.h).
 #include "cabi.h"
 #include "fused_rescale.h"
 #include "kernels_keyswitch.h"
+#include "rotate_add.h"
 
 // relin_kernel launches (`blocks` = items x L): on the context's policy, or - a MIXTURE of classes - one launch per class present, each over its own limbs
 // (relin_kernel maps its workgroups through DevTables::active_map: the digits of every limb still enter every limb's transforms)
@@ -155,25 +156,10 @@ int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_
         if (overlaps(d_out2, out_words, d_in, in_words) || overlaps(d_work, work_words, d_in, in_words) || overlaps(d_work, work_words, d_out2, out_words))
             return fail(DPFHE_INVALID_ARGUMENT, what, "output, input and work buffers must not overlap");
     }
-    const size_t blocks = batch * L;
-    // the grouped and key-major launches pad the grid to whole XCD rounds: the launcher's own plan (a launch per limb class is no larger)
-    const size_t kg = key_group ? key_group : 1;
-    if (blocks > kMaxGrid || RelinMap::plan(blocks, (unsigned)L, key_stride, key_group).grid > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (!key_products_fit(c, batch, key_stride, key_group)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, "hybrid key switch");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int mode = in_comps == 3 ? 2 : 3;
-    if (c->log2n > kMaxFusedLog2N) {
-        // no fused kernel: digits lifted to Q P -> one batched transform -> inner products with the key(s) -> batched inverse into `work`;
-        // in slices whose scratch (Ld L N words per item) stays below the context's limit
-        if (int rc = key_products_composed(c, d_work, d_in + (size_t)(in_comps - 1) * Ld * n, (size_t)in_comps * Ld * n, d_key, key_stride, (unsigned)kg, batch, s, what)) return rc;
-        if (!ntt_grid_fits(c, batch * 2 * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-        if (int rc = ntt_launch(c, true, d_work, d_work, batch * 2 * L, s)) return rc;
-    } else {
-        const int rc = relin_launch(c, mode, d_work, d_in, d_key, key_stride, key_group, blocks, s);
-        if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel geometry for this log2_n");
-        int e = check_launch("hybrid key-switch kernel launch");
-        if (e) return e;
-    }
+    if (int rc = key_products_hybrid(c, what, in_comps, d_work, d_in, d_key, batch, s, key_stride, key_group)) return rc;
     // divide by P with rounding and add c0 (and c1 for relinearisation): one pass over the 2*batch polynomials of `work`
     const int chunks = chunks_of(n);
     const size_t rblocks = batch * 2 * Ld * (size_t)chunks;
@@ -187,6 +173,34 @@ int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_
     }
     launch_rescale(c, rblocks, s, d_out2, d_work, d_in, in_comps, in_comps == 3 ? 3 : 1);
     return check_launch("hybrid rescale launch");
+}
+
+// the fused key-switch launch of `batch` items fits one grid (the grouped and key-major launches pad the grid to whole XCD rounds: the launcher's own
+// plan; a launch per limb class is no larger)
+bool key_products_fit(const dpfhe_ctx* c, size_t batch, size_t key_stride, unsigned key_group) {
+    const size_t blocks = batch * c->n_limbs;
+    return blocks <= kMaxGrid && RelinMap::plan(blocks, c->n_limbs, key_stride, key_group).grid <= kMaxGrid;
+}
+
+// The first pass of hybrid key switching alone: d_work [batch][2][L][N] (coefficient domain over Q P) = sum_j [last component of item]_{q_j} key_j, nothing
+// added, nothing divided.  d_in: [batch][in_comps][Ld][N].  Arguments validated (key_products_fit included), device selected by the caller.
+int key_products_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_work, const uint64_t* d_in, const uint64_t* d_key, size_t batch, hipStream_t s,
+                        size_t key_stride, unsigned key_group) {
+    const size_t L = c->n_limbs, Ld = L - 1, blocks = batch * L, kg = key_group ? key_group : 1;
+    const int n = 1 << c->log2n;
+    const int mode = in_comps == 3 ? 2 : 3;
+    if (c->log2n > kMaxFusedLog2N) {
+        // no fused kernel: digits lifted to Q P -> one batched transform -> inner products with the key(s) -> batched inverse into `work`;
+        // in slices whose scratch (Ld L N words per item) stays below the context's limit
+        if (int rc = key_products_composed(c, d_work, d_in + (size_t)(in_comps - 1) * Ld * n, (size_t)in_comps * Ld * n, d_key, key_stride, (unsigned)kg, batch, s, what)) return rc;
+        if (!ntt_grid_fits(c, batch * 2 * L)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+        if (int rc = ntt_launch(c, true, d_work, d_work, batch * 2 * L, s)) return rc;
+    } else {
+        const int rc = relin_launch(c, mode, d_work, d_in, d_key, key_stride, key_group, blocks, s);
+        if (rc) return fail(DPFHE_INVALID_STATE, what, "no kernel geometry for this log2_n");
+        return check_launch("hybrid key-switch kernel launch");
+    }
+    return DPFHE_SUCCESS;
 }
 
 extern "C" int dpfhe_relinearize_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in3, const uint64_t* d_key, uint64_t* d_work, size_t batch,
@@ -287,6 +301,36 @@ extern "C" int dpfhe_relinearize_rescale_pass_host(const uint64_t* moduli, uint3
     if (int rc = host_rescale_consts(what, moduli, L - 2, rcq)) return rc;
     if (fold) relin_rescale_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
     else relin_rescale_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
+    return DPFHE_SUCCESS;
+}
+
+// host twin of the last pass of a rotate-and-add step (rotate_add.h; the device pass is cabi_rotate.hip's): a division by P like the one above
+extern "C" int dpfhe_rotate_add_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp, const uint64_t* in2,
+                                          uint32_t galois_elt, size_t batch) {
+    static const char* what = "dpfhe_rotate_add_pass_host";
+    if (!moduli || !out || !work_qp || !in2) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (n_limbs < 2) return fail(DPFHE_INVALID_STATE, what, "the extended basis needs at least one data limb and the special prime");
+    const size_t n = (size_t)1 << log2_n, L = n_limbs, Ld = L - 1;
+    if (!(galois_elt & 1u) || galois_elt >= 2 * n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois_elt must be odd and < 2N");
+    if (overlaps(out, batch * 2 * Ld * n, work_qp, batch * 2 * L * n) || overlaps(out, batch * 2 * Ld * n, in2, batch * 2 * Ld * n))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    for (size_t p = 0; p < 2 * batch; ++p)
+        for (size_t l = 0; l < L; ++l)
+            for (size_t k = 0; k < n; ++k) {
+                if (work_qp[(p * L + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+                if (l < Ld && in2[(p * Ld + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+            }
+    std::vector<LimbConst> lc;
+    std::vector<RescaleConst> rcp;
+    bool fold;
+    host_limb_consts(moduli, n_limbs, lc, fold);
+    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
+    unsigned g_inv = 1;   // g^-1 mod 2N by Newton iteration (g odd)
+    for (int i = 0; i < 5; ++i) g_inv *= 2u - galois_elt * g_inv;
+    g_inv &= 2u * (unsigned)n - 1u;
+    if (fold) rotate_add_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), out, work_qp, in2, g_inv, batch);
+    else rotate_add_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), out, work_qp, in2, g_inv, batch);
     return DPFHE_SUCCESS;
 }
 

@@ -1,4 +1,4 @@
-// cabi_rotate.hip - the C ABI's rotations: Galois automorphisms, batched and hoisted rotations under hybrid keys (kernels_rotate.h; the fused
+// cabi_rotate.hip - the C ABI's rotations: Galois automorphisms, batched and hoisted rotations and the rotate-and-add ladder under hybrid keys (kernels_rotate.h; the fused
 // hoisted key switch and the inverse transform with a built-in automorphism are kernels.h's, through launch.h).  The key switch behind a rotation,
 // its digit lift and its division by P are cabi_keyswitch.hip's (cabi.h).  cabi.h lists the other units and states the ABI's conventions.
 #include "cabi.h"
@@ -6,11 +6,12 @@
 
 // automorphism launch: polynomials up to 64 KiB are staged through LDS, larger ones gathered from global memory
 static void launch_galois_multi(hipStream_t s, unsigned grid, u64* out, const u64* in, size_t in_item_stride, const LimbConst* lc, int n_limbs, int n,
-                                int polys_per_item, const GaloisInvs& inv, unsigned in_mod, unsigned item0) {
+                                int polys_per_item, const GaloisInvs& inv, unsigned in_mod, unsigned item0, size_t out_item_stride = 0) {
+    if (!out_item_stride) out_item_stride = (size_t)polys_per_item * n;   // output items back to back
     if (n <= 8192)
-        hipLaunchKernelGGL(galois_multi_kernel<true>, dim3(grid), dim3(256), (size_t)n * 8, s, out, in, in_item_stride, lc, n_limbs, n, polys_per_item, inv, in_mod, item0);
+        hipLaunchKernelGGL(galois_multi_kernel<true>, dim3(grid), dim3(256), (size_t)n * 8, s, out, in, in_item_stride, lc, n_limbs, n, polys_per_item, inv, in_mod, item0, out_item_stride);
     else
-        hipLaunchKernelGGL(galois_multi_kernel<false>, dim3(grid), dim3(256), 0, s, out, in, in_item_stride, lc, n_limbs, n, polys_per_item, inv, in_mod, item0);
+        hipLaunchKernelGGL(galois_multi_kernel<false>, dim3(grid), dim3(256), 0, s, out, in, in_item_stride, lc, n_limbs, n, polys_per_item, inv, in_mod, item0, out_item_stride);
 }
 
 static unsigned galois_inverse(unsigned g, unsigned two_n) {  // g^-1 mod 2N by Newton iteration (g odd): x <- x (2 - g x)
@@ -81,6 +82,64 @@ extern "C" int dpfhe_rotate_hybrid_batch(dpfhe_ctx* c, uint64_t* d_out2, const u
 extern "C" int dpfhe_rotate_hybrid_grouped(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, const uint32_t* galois_elts, size_t n_elts, size_t group,
                                            const uint64_t* d_keys, uint64_t* d_work, uint64_t* d_rotated, void* stream) {
     return rotate_batch_impl(c, "dpfhe_rotate_hybrid_grouped", d_out2, d_in2, n_elts * group, galois_elts, n_elts, group, d_keys, d_work, d_rotated, n_elts * group, stream);
+}
+
+// The rotate-and-add ladder: acc <- acc + rotate(acc, g_e) for e < n_steps, every item of a step under that step's element and key.  Three launches per step:
+//   1. sigma_g(c1) of every item - into the c1 slots of the step's OUTPUT buffer, which nothing reads until pass 3 overwrites it: there the fused key switch
+//      finds its digits at the two-component item stride it reads (kernels.h relin_kernel MODE 3), and no buffer of its own is needed;
+//   2. the key products of those words over Q P (cabi_keyswitch.hip key_products_hybrid: fused up to N = 8192, composed above);
+//   3. rotate_add_pass_kernel: / P, + the step's input, + sigma_g(c0) gathered in the pass.
+// The steps ping-pong between d_out2 and d_acc so that the last one lands in d_out2; step 0 reads d_in2.
+extern "C" int dpfhe_rotate_add_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in2, const uint32_t* galois_elts, const uint64_t* d_keys, uint64_t* d_work,
+                                       uint64_t* d_acc, size_t n_steps, size_t batch, void* stream) {
+    const char* what = "dpfhe_rotate_add_hybrid";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (int rc = check_extended(c, what)) return rc;
+    if (n_steps == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "n_steps must be positive");
+    if (batch == 0) return DPFHE_SUCCESS;
+    if (n_steps == 1) d_acc = nullptr;   // not used
+    if (!d_out2 || !d_in2 || !galois_elts || !d_keys || !d_work || (n_steps > 1 && !d_acc) || misaligned(d_out2) || misaligned(d_in2) || misaligned(d_keys) ||
+        misaligned(d_work) || misaligned(d_acc))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    if (int rc = check_galois_elts(c, galois_elts, n_steps, what)) return rc;
+    const size_t L = c->n_limbs, Ld = L - 1;
+    const int n = 1 << c->log2n;
+    const unsigned two_n = 2u << c->log2n;
+    const size_t ct_words = 2 * Ld * (size_t)n, key_words = Ld * 2 * L * (size_t)n, io_words = batch * ct_words, work_words = batch * 2 * L * n,
+                 acc_words = d_acc ? io_words : 0;
+    if (overlaps(d_out2, io_words, d_in2, io_words) || overlaps(d_work, work_words, d_in2, io_words) || overlaps(d_work, work_words, d_out2, io_words) ||
+        overlaps(d_acc, acc_words, d_in2, io_words) || overlaps(d_acc, acc_words, d_out2, io_words) || overlaps(d_acc, acc_words, d_work, work_words))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "buffers must not overlap");
+    const unsigned slices = RotateAddMap::slices((size_t)n);
+    const size_t pass_grid = RotateAddMap::grid(batch * Ld, slices);
+    if (batch * Ld > kMaxGrid || pass_grid > kMaxGrid || !key_products_fit(c, batch, key_words, (unsigned)batch) || batch > 0xffffffffu)
+        return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DPFHE_ON_DEVICE(c, what);
+    const uint64_t* cur = d_in2;
+    for (size_t e = 0; e < n_steps; ++e) {
+        uint64_t* dst = ((n_steps - 1 - e) & 1) ? d_acc : d_out2;
+        if (int rc = for_slices(batch, kMaxGaloisBatch, [&](size_t first, size_t cnt) {   // the elements travel as kernel arguments, 64 at a time
+                const GaloisInvs inv = galois_inverses(galois_elts + e, first, cnt, batch, two_n);
+                launch_galois_multi(s, (unsigned)(cnt * Ld), dst + first * ct_words + Ld * (size_t)n, cur + first * ct_words + Ld * (size_t)n, ct_words, c->lc, (int)Ld, n, (int)Ld,
+                                    inv, 0u, 0u, ct_words);
+                return check_launch("galois kernel launch");
+            }))
+            return rc;
+        if (int rc = key_products_hybrid(c, what, 2, d_work, dst, d_keys + e * key_words, batch, s, key_words, (unsigned)batch)) return rc;
+        const unsigned g_inv = galois_inverse(galois_elts[e], two_n);
+        with_ctx_arith(c, [&](auto arith) {
+            if (RotateAddMap::staged((size_t)n))
+                hipLaunchKernelGGL((rotate_add_pass_kernel<decltype(arith), true>), dim3((unsigned)pass_grid), dim3(256), (size_t)n * 8, s, dst, d_work, cur, c->lc, c->d_rescale,
+                                   (int)L, n, slices, batch * Ld, g_inv);
+            else
+                hipLaunchKernelGGL((rotate_add_pass_kernel<decltype(arith), false>), dim3((unsigned)pass_grid), dim3(256), 0, s, dst, d_work, cur, c->lc, c->d_rescale, (int)L, n,
+                                   slices, batch * Ld, g_inv);
+        });
+        if (int rc = check_launch("rotate-add pass launch")) return rc;
+        cur = dst;
+    }
+    return DPFHE_SUCCESS;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,8 @@
 // fhe_keyswitch.cpp - the facade's hybrid key switcher (one special prime P): relinearisation and Galois keys on the extended context Q P and the
 // rotations built on them.  Part of libdpfhe_api.so (fhe_api.cpp names the other units); its keys are made by fhe_keys.cpp's make_switch_key.
+#include <algorithm>
+#include <cmath>
+
 #include "fhe_internal.h"
 #include "fhe_sampler.h"
 
@@ -19,6 +22,7 @@ public:
     std::vector<std::pair<std::vector<uint32_t>, std::unique_ptr<PolyBuffer>>> packed;   // element list -> its keys back to back
     std::unique_ptr<PolyBuffer> scratch_work;      // batched rotations: reused across calls (one caller at a time per switcher)
     std::unique_ptr<Ciphertext> scratch_rotated;
+    std::unique_ptr<Ciphertext> scratch_acc;       // rotate-and-add ladders: the ping-pong partner of the output
     std::unique_ptr<PolyBuffer> scratch_digits;    // hoisted rotations: NTT of the lifted digits, [Ld][L][N]
     std::unique_ptr<Ciphertext> scratch_in_ntt;    // rotate_hoisted_qp: NTT of the inputs on the data limbs
     std::unique_ptr<Ciphertext> scratch_product;   // multiply_rescale: the 3-component product on the data limbs
@@ -100,6 +104,12 @@ void HybridKeySwitcher::add_galois_element(uint32_t g) {
     impl_->galois.emplace_back(g, std::move(key));
 }
 
+const PolyBuffer& HybridKeySwitcher::galois_key(uint32_t g) const {
+    const PolyBuffer* key = impl_->find_key(g);
+    if (!key) throw Exception(ErrorCode::INVALID_STATE, "HybridKeySwitcher::galois_key: no key for this element (add_galois_element first)");
+    return *key;
+}
+
 void HybridKeySwitcher::relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* s) const {
     if (in3.is_ntt() || in3.size() != 3 || out2.size() != 2 || out2.batch() != in3.batch())
         throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::relinearize: 3-component coefficient-domain input, 2-component output");
@@ -179,6 +189,23 @@ void HybridKeySwitcher::apply_galois_grouped(const Ciphertext& in2, size_t in_fi
     out2.set_ntt(false);
 }
 
+void HybridKeySwitcher::rotate_add_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& elts, Ciphertext& out2, size_t out_first,
+                                         Stream* s) const {
+    if (count == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), ct_words = 2 * Ld * n;
+    if (elts.empty() || in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in2.words() != in2.batch() * ct_words || out2.words() != out2.batch() * ct_words ||
+        in_first + count > in2.batch() || out_first + count > out2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::rotate_add_range: at least one element, count coefficient-domain items of the data context in and out");
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    grow_scratch(impl_->scratch_work, count, [&](size_t b) { return new PolyBuffer(*impl_->ext, b, 2, false); });
+    if (elts.size() > 1) grow_scratch(impl_->scratch_acc, count, [&](size_t b) { return new Ciphertext(*impl_->data_ctx, 2, b); });
+    check(dpfhe_rotate_add_hybrid(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words, elts.data(), keys->data(),
+                                  impl_->scratch_work->data(), elts.size() > 1 ? impl_->scratch_acc->data() : nullptr, elts.size(), count, s),
+          "dpfhe_rotate_add_hybrid");
+    out2.set_ntt(false);
+}
+
 void HybridKeySwitcher::multiply_rescale(const Ciphertext& a, const Ciphertext& b, Ciphertext& out_next_level, Stream* s) const {
     if (b.batch() != a.batch() || out_next_level.batch() != a.batch())
         throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: operands and output of one batch");
@@ -242,6 +269,59 @@ void HybridKeySwitcher::switch_key_qp(const Ciphertext& in2, size_t in_first, co
                               group, s),
           "dpfhe_switch_key_qp");
     out_qp.set_ntt(true);
+}
+
+// ---- SlotSum -------------------------------------------------------------------------------------------------------------
+class __attribute__((visibility("hidden"))) SlotSum::Impl {
+public:
+    HybridKeySwitcher* ks = nullptr;
+    size_t block = 0, stride = 0;
+    std::vector<uint32_t> elts;
+};
+
+SlotSum::SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride) : impl_(new Impl) {
+    const FheParams& p = ks.data_context().params();
+    const size_t n = p.n();
+    auto pow2 = [](size_t v) { return v && !(v & (v - 1)); };
+    if (!pow2(block) || !pow2(stride) || block < 2 || stride > n / 2 || block > n / 2 / stride)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum: block and stride must be powers of two with block >= 2 and block * stride <= N / 2");
+    impl_->ks = &ks;
+    impl_->block = block;
+    impl_->stride = stride;
+    uint64_t g = 3;   // 3^stride mod 2N by `log2(stride)` squarings, then one squaring per step
+    for (size_t v = stride; v > 1; v >>= 1) g = g * g % (2 * n);
+    for (size_t b = block; b > 1; b >>= 1) {
+        impl_->elts.push_back((uint32_t)g);
+        ks.add_galois_element((uint32_t)g);
+        g = g * g % (2 * n);
+    }
+}
+SlotSum::~SlotSum() = default;
+size_t SlotSum::block() const { return impl_->block; }
+size_t SlotSum::stride() const { return impl_->stride; }
+size_t SlotSum::steps() const { return impl_->elts.size(); }
+const std::vector<uint32_t>& SlotSum::galois_elements() const { return impl_->elts; }
+
+double SlotSum::error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double scale, double max_abs_input,
+                            double input_noise_bound) {
+    const double N = std::ldexp(1.0, (int)log2_n), Ld = (double)data_moduli.size(), B = (double)block;
+    uint64_t qmax = 0;
+    for (uint64_t q : data_moduli) qmax = std::max(qmax, q);
+    const double rho = (double)qmax / (double)special_prime;
+    const double u8 = 8.0 * (double)log2_n * std::ldexp(1.0, -53);
+    const double K = 21.0 * Ld * N * rho, H = (N + 1) / 2;
+    const double pre = N * (B * input_noise_bound + (B - 1) * (K + H)) / scale;
+    return pre + u8 * N * (B * max_abs_input + pre);
+}
+double SlotSum::error_bound(double scale, double max_abs_input, double input_noise_bound) const {
+    const FheParams& pe = impl_->ks->extended_context().params();
+    return error_bound(pe.log2_n, std::vector<uint64_t>(pe.moduli.begin(), pe.moduli.end() - 1), pe.moduli.back(), impl_->block, scale, max_abs_input,
+                       input_noise_bound);
+}
+
+void SlotSum::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
+    if (x.batch() == 0 || y.batch() != x.batch()) throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum::apply: T items in, T items out");
+    impl_->ks->rotate_add_range(x, 0, x.batch(), impl_->elts, y, 0, s);
 }
 
 }  // namespace fhe

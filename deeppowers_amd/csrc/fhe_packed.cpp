@@ -96,7 +96,7 @@ struct PackedCore {
             terms_qp.reset(new PolyBuffer(ext, (n2 - 1) * T, 2, true));             // key inner products of one output ciphertext's giant steps
             ksum_qp.reset(new PolyBuffer(ext, T, 2, true));
         }
-        if (!fold_elts.empty()) fold.reset(new Ciphertext(*ctx, 2, 2 * T));         // [2][T]: running sums | their rotation
+        if (!fold_elts.empty()) fold.reset(new Ciphertext(*ctx, 2, T));             // the block sums before the fold
         tokens = T;
     }
 
@@ -119,12 +119,12 @@ struct PackedCore {
     }
 
     // x: T items on ctx -> sums: passes * T items on ctx (output ciphertext o of token t at item o * T + t), 2 components, coefficient domain, L limbs
-    void run(const Ciphertext& x, uint64_t* y, Stream* s) {
+    void run(const Ciphertext& x, Ciphertext& y_ct, Stream* s) {
         const size_t T = x.batch();
+        uint64_t* y = y_ct.data();
         const FheParams& p = ctx->params();
         const size_t ct_words = 2 * p.n_limbs() * p.n();
         hipStream_t hs = static_cast<hipStream_t>(s);
-        dpfhe_ctx* h = handle_of(*ctx);
         dpfhe_ctx* he = handle_of(ks->extended_context());
         // Layout of every intermediate: [rotation or diagonal index][token][component] - the token index sits where the plaintext
         // matvec sees "more components", so keys and diagonals are read once for all tokens.
@@ -153,15 +153,10 @@ struct PackedCore {
             hip_check(hipMemcpyAsync(sums, rt.data(), passes * T * ct_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, hs), "hipMemcpyAsync");
         }
         // wide input (m < n): slot r holds the partial sum over input indices congruent to r + k; fold the n/m windows together
+        // (one rotate-and-add ladder: the words of a grouped rotation and an addition per step, dpfhe_rotate_add_hybrid)
         if (!fold_elts.empty()) {
-            Ciphertext& f = *fold;   // items [0, T): running sums, [T, 2T): their rotation
-            f.set_ntt(false);
-            for (size_t e = 0; e < fold_elts.size(); ++e) {
-                const std::vector<uint32_t> one(1, fold_elts[e]);
-                ks->apply_galois_grouped(f, 0, one, T, f, T, s);
-                const bool last = e + 1 == fold_elts.size();
-                check(dpfhe_add(h, last ? y : f.data(), f.data(), f.data() + T * ct_words, 2 * T, s), "dpfhe_add");
-            }
+            fold->set_ntt(false);
+            ks->rotate_add_range(*fold, 0, T, fold_elts, y_ct, 0, s);
         }
     }
 };
@@ -309,7 +304,7 @@ void PackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
     if (x.is_ntt() || x.size() != 2 || T == 0 || y.size() != 2 || y.batch() != I.passes * T)
         throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear::apply: T 2-component coefficient-domain ciphertexts in, output_ciphertexts() * T out");
     I.ensure_tokens(T);   // (re)allocates only when a larger batch than ever before arrives
-    I.run(x, y.data(), s);
+    I.run(x, y, s);
     dpfhe_ctx* h = handle_of(*I.ctx);
     // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
     if (I.bias)
@@ -491,7 +486,7 @@ void ApproxPackedLinear::apply(const Ciphertext& x, Ciphertext& y, Stream* s) co
         throw Exception(ErrorCode::INVALID_ARGUMENT,
                         "ApproxPackedLinear::apply: T 2-component coefficient-domain ciphertexts on data_ctx in, output_ciphertexts() * T on next_ctx out");
     I.ensure(T);   // (re)allocates only when a larger batch than ever before arrives
-    I.run(x, I.full->data(), s);                                   // level L, scale input_scale * weight_scale
+    I.run(x, *I.full, s);                                          // level L, scale input_scale * weight_scale
     check(dpfhe_rescale(handle_of(*I.ctx), y.data(), I.full->data(), I.passes * T * 2, s), "dpfhe_rescale");
     // + bias: output ciphertext o of every token (item o * T + t) takes bias item o
     if (I.bias) check(dpfhe_add_plain(handle_of(*I.next), y.data(), y.data(), I.bias->data(), I.passes * T, 2, I.passes, 0, s), "dpfhe_add_plain");

@@ -1,10 +1,11 @@
-// kernels_rotate.h - streaming (HBM-bound) kernels of the rotations: Galois automorphisms and the hoisted baby steps over Q P.
+// kernels_rotate.h - streaming (HBM-bound) kernels of the rotations: Galois automorphisms, the last pass of a rotate-and-add step and the hoisted baby steps over Q P.
 // Included by cabi_rotate.hip only.  No reference counterpart.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
 #include "modarith.h"
+#include "rotate_add.h"
 #include "stream_access.h"
 #include "workmap.h"
 
@@ -27,19 +28,20 @@ __global__ __launch_bounds__(256) void galois_kernel(u64* out, const u64* in, co
 // in_item_stride == 0); polys_per_item residue polynomials per item
 struct GaloisInvs { unsigned v[kMaxGaloisBatch]; };
 // in_mod > 0: output item i reads input item (item0 + i) % in_mod (several rotations of each of in_mod inputs: rotation-major order)
+// output items are out_item_stride words apart (polys_per_item * n: back to back)
 // LDS_STAGE (N <= 8192: the polynomial fits 64 KiB of dynamic LDS): the source polynomial is read with coalesced 16-byte loads
 // into LDS and gathered from there - the odd multiplier g^-1 spreads consecutive k over distinct banks - instead of 8-byte
 // global gathers that touch a different cache line per lane (packed GPT-2 layer, 8 tokens per application: 0.278 -> 0.265 ms per token).
 template <bool LDS_STAGE>
 __global__ __launch_bounds__(256) void galois_multi_kernel(u64* out, const u64* in, size_t in_item_stride, const LimbConst* lcs, int n_limbs, int n,
-                                                           int polys_per_item, GaloisInvs g_inv, unsigned in_mod, unsigned item0) {
+                                                           int polys_per_item, GaloisInvs g_inv, unsigned in_mod, unsigned item0, size_t out_item_stride) {
     extern __shared__ __attribute__((aligned(16))) u64 stage[];
     const size_t item = blockIdx.x / (unsigned)polys_per_item, p = blockIdx.x % (unsigned)polys_per_item;
     const u64 q = lcs[p % (size_t)n_limbs].q;
     const unsigned mask2n = 2u * (unsigned)n - 1u, gi = g_inv.v[item];
     const size_t in_item = in_mod ? (item0 + item) % in_mod : item;
     const u64* src = in + in_item * in_item_stride + p * n;
-    u64* dst = out + (item * polys_per_item + p) * n;
+    u64* dst = out + item * out_item_stride + p * n;
     if (LDS_STAGE) {
         for (int k = threadIdx.x * 2; k < n; k += 512) *reinterpret_cast<U64x2*>(stage + k) = *reinterpret_cast<const U64x2*>(src + k);
         __syncthreads();
@@ -54,6 +56,50 @@ __global__ __launch_bounds__(256) void galois_multi_kernel(u64* out, const u64* 
         const unsigned j = ((unsigned)k * gi) & mask2n;
         const u64 v = src[j & ((unsigned)n - 1u)];
         dst[k] = (j < (unsigned)n) ? v : neg_mod(v, q);
+    }
+}
+
+// The last pass of a rotate-and-add step (rotate_add.h): divide the key products of sigma_g(c1) by P, add the step's input and sigma_g(c0), which is gathered
+// here and never written.  work: [batch][2][L][N] over Q P, in2 / out: [batch][2][Ld][N].  One workgroup per (item, data limb, slice of the polynomial's
+// 512-word chunks - workmap.h RotateAddMap), both components of the slice.  LDS_STAGE (N <= 8192): the c0 polynomial is read once with 16-byte loads into LDS
+// and serves the direct addend and the gather (the odd multiplier g^-1 spreads consecutive k over the banks, as in galois_multi_kernel); otherwise the
+// gather goes to global memory, 8 bytes per word, from the L2 of the XCD that runs all slices of the polynomial.  Per slice word: the rows of limb i and
+// of P of both components of `work`, c1, and one store per component.
+template <class Arith, bool LDS_STAGE>
+__global__ __launch_bounds__(256) void rotate_add_pass_kernel(u64* __restrict__ out, const u64* __restrict__ work, const u64* __restrict__ in2, const LimbConst* lcs,
+                                                              const RescaleConst* rcs, int n_limbs, int n, unsigned slices, size_t n_polys, unsigned g_inv) {
+    extern __shared__ __attribute__((aligned(16))) u64 stage[];
+    const int Ld = n_limbs - 1;
+    const RotateAddWork wk = RotateAddMap::decode(blockIdx.x, slices, n_polys, (unsigned)Ld);
+    if (!wk.live) return;
+    const int limb = wk.limb;
+    const LimbConst lc = lcs[limb];
+    const RescaleConst rc = rcs[limb];
+    const u64* c0 = in2 + (wk.item * 2 * Ld + limb) * n;
+    const u64* c1 = c0 + (size_t)Ld * n;
+    const u64* w0 = work + (wk.item * 2 * n_limbs + limb) * n;
+    const u64* p0 = work + (wk.item * 2 * n_limbs + Ld) * n;
+    const u64 *w1 = w0 + (size_t)n_limbs * n, *p1 = p0 + (size_t)n_limbs * n;
+    u64* o0 = out + (wk.item * 2 * Ld + limb) * n;
+    u64* o1 = o0 + (size_t)Ld * n;
+    if (LDS_STAGE) {
+        for (int k = threadIdx.x * 2; k < n; k += 512) *reinterpret_cast<U64x2*>(stage + k) = *reinterpret_cast<const U64x2*>(c0 + k);
+        __syncthreads();
+    }
+    const u64* src = LDS_STAGE ? stage : c0;
+    const unsigned mask2n = 2u * (unsigned)n - 1u, maskn = (unsigned)n - 1u;
+    const int per = chunks_of(n) / (int)slices;
+    for (int ch = (int)wk.slice * per; ch < ((int)wk.slice + 1) * per; ++ch) {
+        const int k = ch * 512 + threadIdx.x * 2;
+        if (k >= n) break;   // (rings below 512 words: one partial chunk)
+        const U64x2 a0 = *reinterpret_cast<const U64x2*>(w0 + k), b0 = *reinterpret_cast<const U64x2*>(p0 + k);
+        const U64x2 a1 = *reinterpret_cast<const U64x2*>(w1 + k), b1 = *reinterpret_cast<const U64x2*>(p1 + k);
+        const U64x2 d1 = *reinterpret_cast<const U64x2*>(c1 + k);
+        const U64x2 d0 = *reinterpret_cast<const U64x2*>(src + k);
+        const unsigned j0 = ((unsigned)k * g_inv) & mask2n, j1 = (j0 + g_inv) & mask2n;
+        const u64 s0 = src[j0 & maskn], s1 = src[j1 & maskn];
+        *reinterpret_cast<U64x2*>(o0 + k) = U64x2{rotate_add_word0<Arith>(a0.a, b0.a, d0.a, s0, j0 > maskn, lc, rc), rotate_add_word0<Arith>(a0.b, b0.b, d0.b, s1, j1 > maskn, lc, rc)};
+        *reinterpret_cast<U64x2*>(o1 + k) = U64x2{rotate_add_word1<Arith>(a1.a, b1.a, d1.a, lc, rc), rotate_add_word1<Arith>(a1.b, b1.b, d1.b, lc, rc)};
     }
 }
 

@@ -199,4 +199,31 @@ DPF_HD ChunkWork chunk_work(unsigned id, int chunks, Limbs n_limbs) {
     return ChunkWork{(int)(id % chunks), (int)((id / chunks) % n_limbs), (size_t)(id / chunks / n_limbs)};
 }
 
+// ------------------------------------------------------------------------------------------------
+// The last pass of a rotate-and-add step (kernels_rotate.h rotate_add_pass_kernel): outer = (item, data limb), inner = slice of that residue polynomial's
+// chunks.  A workgroup writes its slice of BOTH components; component 0 gathers sigma_g(c0) from anywhere in the polynomial, so the `slices`
+// workgroups of a polynomial share ONE XCD: staged (the polynomial fits 64 KiB of LDS, N <= 8192) each of them reads all of c0 - from HBM once, L2 hits
+// for the rest -, at most 8 of them; unstaged the gathers of all chunks go to that XCD's L2.  slices divides chunks (powers of two).
+// ------------------------------------------------------------------------------------------------
+constexpr int kRotateAddStagedMaxN = 8192;
+struct RotateAddWork {
+    size_t item;
+    int limb;
+    unsigned slice;
+    bool live;
+};
+struct RotateAddMap {
+    static DPF_HD bool staged(size_t n) { return n <= (size_t)kRotateAddStagedMaxN; }
+    static DPF_HD unsigned slices(size_t n) {
+        const unsigned chunks = (unsigned)chunks_of(n);
+        return staged(n) && chunks > 8u ? 8u : chunks;
+    }
+    static DPF_HD RotateAddWork decode(unsigned id, unsigned slices, size_t n_polys, unsigned n_data_limbs) {
+        const XcdSlot s = xcd_deal::decode(id, slices);
+        if (s.outer >= n_polys) return RotateAddWork{0, 0, 0, false};
+        return RotateAddWork{(size_t)(s.outer / n_data_limbs), (int)(s.outer % n_data_limbs), s.inner, true};
+    }
+    static DPF_HD size_t grid(size_t n_polys, unsigned slices) { return xcd_deal::grid(n_polys, slices); }   // n_polys = items x data limbs
+};
+
 }  // namespace dpfhe

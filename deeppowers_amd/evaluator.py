@@ -446,6 +446,27 @@ class Evaluator:
                                                           rotated.data_ptr(), self._sp(stream)), "dpfhe_rotate_hybrid_grouped")
         return Ciphertext(out, False)
 
+    def rotate_add_hybrid(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> Ciphertext:
+        """N3, the rotate-and-add ladder: acc <- acc + rotate(acc, galois_elts[e]) for every e in order, all items of ct under the step's element and key
+        (sums across slots: elements 3^(stride 2^e) sum blocks of 2^len(elts) slots).  keys: [len(elts)][L-1][2][L][N].  The words are those of
+        rotate_hybrid_grouped(ct, [g], T, key) followed by add, step by step."""
+        p = self.ctx.params
+        L, Ld, n = p.n_limbs, p.n_limbs - 1, p.n
+        d = ct.data
+        k = len(galois_elts)
+        if ct.is_ntt or ct.size != 2 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "rotate_add_hybrid: coefficient-domain [T][2][L-1][N] ciphertexts on the extended context")
+        if tuple(keys.shape) != (k, Ld, 2, L, n) or keys.dtype != torch.int64 or not keys.is_contiguous():
+            raise _cabi.DpfheError(2000, "keys must be [k][L-1][2][L][N]")
+        T = d.shape[0]
+        out = self._empty((T, 2, Ld, n), stream)
+        work = self._empty((T, 2, L, n), stream)
+        acc = self._empty((T, 2, Ld, n), stream) if k > 1 else None
+        elts = (C.c_uint32 * k)(*[int(g) for g in galois_elts])
+        _cabi.check(self._lib.dpfhe_rotate_add_hybrid(self.ctx.handle, out.data_ptr(), d.data_ptr(), elts, keys.data_ptr(), work.data_ptr(),
+                                                      acc.data_ptr() if acc is not None else None, k, T, self._sp(stream)), "dpfhe_rotate_add_hybrid")
+        return Ciphertext(out, False)
+
     def device_copy(self, dst: torch.Tensor, src: torch.Tensor, stream=None) -> torch.Tensor:
         """Plain device-to-device copy through the library's streaming access shape (dpfhe_copy): the practical HBM ceiling."""
         if dst.numel() != src.numel() or dst.dtype != torch.int64 or src.dtype != torch.int64 or not dst.is_contiguous() or not src.is_contiguous():

@@ -502,6 +502,8 @@ public:
     HybridKeySwitcher(const HybridKeySwitcher&) = delete;
     HybridKeySwitcher& operator=(const HybridKeySwitcher&) = delete;
     void add_galois_element(uint32_t galois_elt);  // generates and keeps the key for sigma_g
+    // the key of an added element: [Ld][2][L][N] on extended_context(), NTT domain - what the C ABI's rotations take (INVALID_STATE: never added)
+    const PolyBuffer& galois_key(uint32_t galois_elt) const;
     // The `stream` argument: relinearize and apply_galois allocate their temporaries per call and SYNCHRONISE `stream` before they
     // return.  Every other method below enqueues on `stream` and returns without host synchronisation once its scratch has its size and the keys of its
     // element list are packed: the FIRST call with a new element list packs the keys on `stream` and synchronises it, and a larger batch than ever
@@ -538,6 +540,13 @@ public:
     // k * group items, item i rotated by galois_elts[i / group] (the giant steps of `group` tokens; keys read once per element)
     void apply_galois_grouped(const Ciphertext& in2, size_t in_first, const std::vector<uint32_t>& galois_elts, size_t group, Ciphertext& out2,
                               size_t out_first, Stream* stream = nullptr) const;
+
+    // The rotate-and-add ladder (dpfhe_rotate_add_hybrid): out item out_first + i = acc_k of in item in_first + i, i < count, where acc_0 is the item and
+    // acc_{e+1} = acc_e + sigma_{elts[e]}(acc_e) - the words of apply_galois_grouped with that one element followed by Evaluator::add, step by step, in three
+    // launches per step instead of four.  All elements must have been added; `in2` and `out2` may be the same buffer as long as the two ranges do not overlap.
+    // Enqueues only after the first call with a given element list; the scratch (the Q P products, the ladder's second accumulator) is the object's own.
+    void rotate_add_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& galois_elts, Ciphertext& out2, size_t out_first,
+                          Stream* stream = nullptr) const;
 
     // ---- division by P deferred ("double hoisting"; include/dpfhe.h "N3, round 3") -------------------------------------
     // The context of the data moduli + the special prime: buffers holding terms over Q P live on it.
@@ -618,6 +627,46 @@ public:
     void encode_device(const double* d_slots, size_t items, double scale, Plaintext& out, bool to_ntt = false, bool real = false, Stream* stream = nullptr) const;
     // the building block of the above: d_out on ctx's device, flags as for dpfhe_encode_complex
     void encode_device_words(const Context& ctx, const double* d_slots, size_t items, double scale, uint64_t* d_out, uint32_t flags, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// SlotSum: sums across the slots of one ciphertext - what LayerNorm's mean and variance, a softmax's denominator and an inner product of two encrypted
+// vectors need.  After apply(), slot i holds  sum_{j < block} x[(i + j stride) mod N/2]  (within each of BatchEncoder's two rows, over the one row of a
+// ComplexEncoder): log2(block) rotate-and-add steps by 3^(stride 2^e), e < log2(block), as ONE HybridKeySwitcher::rotate_add_range.  On an input of period
+// block * stride - what pack_input of the packed layers produces - every slot therefore holds the total of its residue class modulo stride.  Independent of
+// the family: both encoders rotate by 3^s.  Exact over Z_t (sums mod t); the approximate family's error:
+//
+// Error bound.  ApproxPackedLinear's notation and tools T1 - T4: Ld the data limbs, rho = max_j q_j / P, K = 21 Ld N rho (T4), H = (N + 1) / 2 (T3),
+//   u8 = 8 log2(N) 2^-53, D = the input's scale, X = max|x_i|, Bin the infinity norm of the input phase's error in coefficients.  A step adds the running sum
+//   to its rotation: the automorphism keeps the coefficient norm (T2), its key switch adds K and the division by P's rounding H, so an error e becomes
+//   e + (e + K + H) = 2 e + K + H.  After the log2(block) steps:  block Bin + (block - 1) (K + H)  per coefficient, N times that per slot (T1), in units of the
+//   values:  pre = N (block Bin + (block - 1) (K + H)) / D.  The scale does not change.  Every slot is at most block X + pre in modulus, so the decrypted
+//   coefficients obey max|c_k| <= D (block X + pre) and the client's decode adds u8 N (block X + pre).
+//   error_bound(D, X, Bin) = pre + u8 N (block X + pre): a bound on |decoded slot - the sum| for every slot and token, provided the phase does not wrap.
+//   (Worst case throughout, like the layers' bounds: key-switch errors add like a random walk, not in absolute value.)
+class SlotSum {
+public:
+    // block, stride: powers of two, block >= 2, block * stride <= N/2 (INVALID_ARGUMENT otherwise).  Adds the elements 3^(stride 2^e) mod 2N, e < log2(block),
+    // to `ks` in ascending order of e; `ks` must outlive the object.
+    SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride = 1);
+    ~SlotSum();
+    SlotSum(const SlotSum&) = delete;
+    SlotSum& operator=(const SlotSum&) = delete;
+    size_t block() const;
+    size_t stride() const;
+    size_t steps() const;                                    // log2(block): key switches per item
+    const std::vector<uint32_t>& galois_elements() const;    // the ladder's elements, in the order they are applied
+    // the bound derived above (the approximate family): scale = D, max_abs_input = X, input_noise_bound = Bin
+    double error_bound(double scale, double max_abs_input, double input_noise_bound) const;
+    // ... and without a device: data_moduli are the limbs of ks.data_context(), special_prime its P
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double scale, double max_abs_input,
+                              double input_noise_bound);
+    // x: T items on ks.data_context() (2 components, coefficient domain); y: T items on the same context, another buffer.  Level and scale do not change.
+    // The stream contract of HybridKeySwitcher::rotate_add_range: enqueues only after the first call; one apply() at a time per key switcher.
+    void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:
     class Impl;

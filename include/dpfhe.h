@@ -247,6 +247,28 @@ int dpfhe_rotate_hybrid_hoisted(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint
 int dpfhe_rotate_hybrid_grouped(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, const uint32_t* galois_elts, size_t n_elts, size_t group,
                                 const uint64_t* d_keys, uint64_t* d_work, uint64_t* d_rotated, void* stream);
 
+/* -- N3, the rotate-and-add ladder (sums across the slots of one ciphertext): acc_0 = d_in2, acc_{e+1} = acc_e + R_e mod q_l for e < n_steps, d_out2 = acc_{n_steps},
+ * where R_e is what dpfhe_rotate_hybrid_grouped(n_elts = 1, group = batch, element galois_elts[e], key e) makes of acc_e:
+ *   R_e = (sigma_g c0, 0) + round(sum_j [sigma_g c1]_{q_j} key_j / P),  the automorphism before the digit lift as in dpfhe_rotate_hybrid_batch
+ * - word for word that rotation followed by dpfhe_add.  All buffers [batch][2][Ld][N], coefficient domain, canonical residues; every item of a step shares the
+ * step's element and key.  galois_elts: HOST array of n_steps odd elements < 2N; d_keys: n_steps keys back to back, each [Ld][2][L][N] as for
+ * dpfhe_switch_key_hybrid.  Per step three launches instead of four: sigma_g(c1) alone is materialised (in the c1 slots of the step's output buffer, where
+ * the key switch reads it and the last pass overwrites it: no buffer of its own), the key products, and ONE last pass that divides by P, adds the un-rotated
+ * input and gathers sigma_g(c0) itself - 7 Ld + 4 L words of N per item and step instead of 14 Ld + 4 L.
+ * Scratch, exactly: d_work batch * 2 * L * N words; d_acc batch * 2 * Ld * N words, the ping-pong partner of d_out2 (the last step lands in d_out2; d_out2
+ * holds intermediate sums before that) - not read when n_steps == 1, where it may be NULL.  No buffer overlaps another or the input.
+ * Enqueues only, every log2_n (8 ... 16) and limb class; above N = 8192 the key products are composed and take arena scratch, exactly as in
+ * dpfhe_switch_key_hybrid.  DPFHE_INVALID_STATE on a context without a special prime; DPFHE_INVALID_ARGUMENT, before the device is touched, on n_steps == 0, a
+ * null or misaligned buffer, an even element or one >= 2N, overlapping buffers, or a grid too large for one launch.  batch == 0 returns success.
+ * dpfhe_rotate_add_pass_host: the host twin of the last pass of ONE step alone (no device, no context): moduli are the n_limbs = Ld + 1 >= 2 limbs of the
+ *   extended basis (odd, >= 3, < 2^60, P coprime to every data limb), work_qp [batch][2][L][N] the key products over Q P in the coefficient domain, in2 [batch][2][Ld][N] the
+ *   step's input, out [batch][2][Ld][N]:  out.c0 = round(work.c0 / P) + in.c0 + sigma_g(in.c0),  out.c1 = round(work.c1 / P) + in.c1.  Words that are not
+ *   canonical residues are rejected. */
+int dpfhe_rotate_add_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, const uint32_t* galois_elts, const uint64_t* d_keys, uint64_t* d_work,
+                            uint64_t* d_acc, size_t n_steps, size_t batch, void* stream);
+int dpfhe_rotate_add_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp, const uint64_t* in2,
+                               uint32_t galois_elt, size_t batch);
+
 /* -- N3, round 3: baby-step / giant-step sums with the division by P DEFERRED ("double hoisting", Bossuat-Mouchet-Troncoso-Pastoriza-
  * Hubaux 2021).  A rotated term is kept in the NTT domain over the extended basis Q P as  P sigma_g(ct) + key-switching noise;
  * plaintext products and sums are taken there, and one inverse transform + divide-by-P is paid per SUM, not per rotation.

@@ -83,6 +83,18 @@ void wm_chunk_decode(unsigned n_ids, int chunks, int n_limbs, i64* out) {
     }
 }
 
+// last pass of a rotate-and-add step: rows (item, limb, slice, live)
+unsigned wm_rotate_add_slices(size_t n) { return RotateAddMap::slices(n); }
+int wm_rotate_add_staged(size_t n) { return RotateAddMap::staged(n); }
+u64 wm_rotate_add_grid(size_t n_polys, unsigned slices) { return RotateAddMap::grid(n_polys, slices); }
+void wm_rotate_add_decode(unsigned n_ids, unsigned slices, size_t n_polys, unsigned n_data_limbs, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const RotateAddWork w = RotateAddMap::decode(id, slices, n_polys, n_data_limbs);
+        i64* o = out + 4 * (size_t)id;
+        o[0] = (i64)w.item; o[1] = w.limb; o[2] = w.slice; o[3] = w.live;
+    }
+}
+
 // batched transforms: rows (first word / N, limb, sub-block)
 void wm_transform_decode(unsigned n_ids, int n_sub, int n_limbs, int n_active, unsigned long long active_map, i64* out) {
     const Tables tb{n_sub, n_limbs, n_active, active_map};
