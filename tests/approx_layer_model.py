@@ -26,16 +26,14 @@ on oracle.cbind.Oracle (for N = 32768, where one big-integer product takes secon
 model A to the float64 W x + b; tests/test_gpu_approx_layer_words.py holds the device's words to them.
 """
 import math
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+import cpp_build
 from deeppowers_amd import ckks
 from deeppowers_amd.params import FheParams, ntt_primes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAGIC = 0x31574C5041      # "APLW1"
 NOISE = 21                # |e| of a fresh ciphertext (deeppowers_amd/csrc/fhe_sampler.h)
 
@@ -383,12 +381,4 @@ class Run:
 
 
 def build_words_program():
-    """tests/cpp/approx_layer_words, rebuilt only when the source, the header or a library changed"""
-    exe = os.path.join(ROOT, "tests", "cpp", "approx_layer_words")
-    src = exe + ".cpp"
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    deps = [src, os.path.join(ROOT, "include", "deeppowers", "fhe.hpp"), os.path.join(lib, "libdpfhe_api.so"), os.path.join(lib, "libdpfhe_hip.so")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), src, "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip",
-                               "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return cpp_build.build_program("approx_layer_words")

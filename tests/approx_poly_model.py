@@ -10,17 +10,15 @@ Every division is by an odd prime, so round(x / q) = floor((2 x + q) / (2 q)) ha
 tools it borrows; tests/test_approx_poly_model_cpu.py holds the model to the float64 p(x), tests/test_gpu_approx_poly_words.py holds the device to the model."""
 import functools
 import math
-import os
 import struct
-import subprocess
 
 import numpy as np
 
 import approx_layer_model as alm
+import cpp_build
 from deeppowers_amd import ckks
 from deeppowers_amd.params import ntt_primes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAGIC = int.from_bytes(b"APPW1", "little")
 INPUT_SCALE, OUTPUT_SCALE, X_MAX = 2.0 ** 59, 2.0 ** 50, 2.0
 
@@ -182,26 +180,9 @@ class Run:
             fh.write(np.ascontiguousarray(self.c0[:T], dtype="<u8").tobytes())
 
 
-def _build(name, extra=()):
-    """tests/cpp/<name>, rebuilt only when the source, the header or a library changed"""
-    exe = os.path.join(ROOT, "tests", "cpp", name)
-    src = exe + ".cpp"
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    deps = [src, os.path.join(ROOT, "include", "deeppowers", "fhe.hpp"), os.path.join(lib, "libdpfhe_api.so"), os.path.join(lib, "libdpfhe_hip.so")] + [e for e in extra if os.path.sep in e]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = []
-        for e in extra:
-            if os.path.sep in e:
-                flags += ["-L" + os.path.dirname(e), "-l" + os.path.basename(e)[3:-3], f"-Wl,-rpath,{os.path.dirname(e)}"]
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", src, "-o", exe,
-                               "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip"] + flags + ["-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def build_words_program():
-    return _build("approx_poly_words")
+    return cpp_build.build_program("approx_poly_words")
 
 
 def build_api_test():
-    import stream_gate as sg
-    return _build("test_approx_poly_api", extra=(sg.build_library(),))
+    return cpp_build.build_program("test_approx_poly_api", gate=True)

@@ -13,19 +13,13 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
 static std::string g_outdir;
-static const uint64_t T_MOD = 65537;
-static uint64_t g_lcg = 2024;
-static uint64_t rnd(uint64_t m) { g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull; return (g_lcg >> 33) % m; }
+static Lcg rnd{2024};
 
 static void dump(const char* name, const void* data, size_t bytes) {
     const std::string path = g_outdir + "/" + name + ".bin";
@@ -258,10 +252,5 @@ int main(int argc, char** argv) {
         std::printf("exception: %s\n", e.what());
         return 2;
     }
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("facade digests written\n");
-    return 0;
+    return finish("facade digests written");
 }

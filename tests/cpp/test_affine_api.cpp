@@ -7,58 +7,13 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-static uint64_t g_seed = 99;
-static uint64_t rnd(uint64_t m) { g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull; return (g_seed >> 33) % m; }
-static const uint64_t T_MOD = 65537;
-static uint64_t small8() { return (T_MOD + rnd(255) - 127) % T_MOD; }   // 8-bit quantised, centred
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
-
-// y = W x + b mod t
-static std::vector<uint64_t> affine(const std::vector<uint64_t>& W, const uint64_t* b, size_t rows, size_t cols, const uint64_t* x) {
-    std::vector<uint64_t> y(rows);
-    for (size_t r = 0; r < rows; ++r) {
-        unsigned __int128 acc = b ? b[r] : 0;
-        for (size_t c = 0; c < cols; ++c) acc += (unsigned __int128)W[r * cols + c] * x[c];
-        y[r] = (uint64_t)(acc % T_MOD);
-    }
-    return y;
-}
-
-// the chain primes of FheParams::n8192 seen at ring degree 2^log2n (psi raised to the power 8192 / N); the last one is returned as the special prime
-static FheParams ring(unsigned log2n, size_t data_limbs, uint64_t& special, uint64_t& special_psi) {
-    FheParams p = FheParams::n8192(data_limbs + 1);
-    const size_t n = (size_t)1 << log2n;
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
-    special = p.moduli.back(); special_psi = p.psi.back();
-    p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
-    return p;
-}
+static Lcg rnd{99};
+static uint64_t small8() { return rnd.small8(); }
 
 // ---- add / sub of a plaintext, budget, 3-component products ---------------------------------------------------------------------
 static void plain_add() {
@@ -194,8 +149,8 @@ static void packed_bias(const FheParams& p, uint64_t special, uint64_t special_p
         size_t bad = 0, bad_period = 0;
         for (size_t c = 0; c < C; ++c) {
             for (size_t o = 0; o < outs; ++o) be.decode(&dm[(o * C + c) * n], &got[o * n]);
-            const std::vector<uint64_t> w0 = affine(W, bias.data(), out, in, &x[tpc * c * in]);
-            const std::vector<uint64_t> w1 = tpc == 2 ? affine(W, bias.data(), out, in, &x[(2 * c + 1) * in]) : w0;
+            const std::vector<uint64_t> w0 = affine(W, bias.data(), out, in, &x[tpc * c * in], T_MOD);
+            const std::vector<uint64_t> w1 = tpc == 2 ? affine(W, bias.data(), out, in, &x[(2 * c + 1) * in], T_MOD) : w0;
             if (tpc == 1) lin.unpack_output(got.data(), y0.data());
             else lin.unpack_output_rows(got.data(), y0.data(), y1.data());
             bad += y0 != w0;
@@ -259,12 +214,12 @@ static void block_bias() {
         dec.decrypt_exact(blk.stage(st), T_MOD, dm.data());
         for (size_t tk = 0; tk < T; ++tk) {
             const uint64_t* xt = &x[tk * d];
-            const std::vector<uint64_t> qkv = affine(Wqkv, bqkv.data(), 3 * d, d, xt);
-            const std::vector<uint64_t> o = affine(Wo, bo.data(), d, d, &qkv[2 * d]);
+            const std::vector<uint64_t> qkv = affine(Wqkv, bqkv.data(), 3 * d, d, xt, T_MOD);
+            const std::vector<uint64_t> o = affine(Wo, bo.data(), d, d, &qkv[2 * d], T_MOD);
             std::vector<uint64_t> h1(d), h2(d);
             for (size_t i = 0; i < d; ++i) h1[i] = (xt[i] + o[i]) % T_MOD;
-            const std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, h1.data());
-            const std::vector<uint64_t> dn = affine(Wd, bd.data(), d, h, u.data());
+            const std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, h1.data(), T_MOD);
+            const std::vector<uint64_t> dn = affine(Wd, bd.data(), d, h, u.data(), T_MOD);
             for (size_t i = 0; i < d; ++i) h2[i] = (h1[i] + dn[i]) % T_MOD;
             be.decode(&dm[tk * n], got.data());
             for (size_t s = 0; s < n; ++s) {
@@ -334,9 +289,9 @@ static void ffn_act_bias() {
     dec2.decrypt_exact(cy, T_MOD, dm.data());
     size_t bad = 0;
     for (size_t tk = 0; tk < T; ++tk) {
-        std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, &x[tk * d]);
+        std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, &x[tk * d], T_MOD);
         for (auto& v : u) v = (uint64_t)((unsigned __int128)v * v % T_MOD);
-        const std::vector<uint64_t> want = affine(Wd, bd.data(), d, h, u.data());
+        const std::vector<uint64_t> want = affine(Wd, bd.data(), d, h, u.data(), T_MOD);
         be2.decode(&dm[tk * n], got.data());
         down.unpack_output(got.data(), y.data());
         bad += y != want;
@@ -369,10 +324,5 @@ int main() {
         std::printf("exception: %s\n", e.what());
         return 2;
     }
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("affine C++ facade OK\n");
-    return 0;
+    return finish("affine C++ facade OK");
 }

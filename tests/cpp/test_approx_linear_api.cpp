@@ -1,11 +1,9 @@
 // GPU test of the approximate packed layer in the C++ facade (ApproxPackedLinear, Evaluator::add_plain / sub_plain): every unpacked output of every shape
 // lies within ApproxPackedLinear::error_bound of the float64 W x + b, that bound is at most 2^-10 and the reference has max|y| >= 1 on every case (a
-// wrong diagonal, rotation, scale or level gives errors of order max|y|).  Built and run by tests/test_gpu_approx_linear.py (-m gpu).
+// wrong diagonal, rotation, scale or level gives errors of order max|y|); apply() returns while its stream is held (the gate of tests/cpp/facade_test.h) and
+// gives the same words there.  Built and run by tests/test_gpu_approx_linear.py (-m gpu).
 // `test_approx_linear_api ref` only draws the cases and prints max|y| of each (no device).  Exit code 0 = all checks passed.
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -15,59 +13,17 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
-
-extern "C" int stream_gate_enqueue(void* stream, uint64_t ticks, uint64_t max_iters);
-extern "C" int stream_gate_stream_create(void** out);
-extern "C" int stream_gate_stream_destroy(void* stream);
+#define FACADE_TEST_GATE
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
+using namespace facade_test;
 typedef std::complex<double> cplx;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-// SplitMix64 -> uniform on [-1, 1]
-static uint64_t g_state = 0;
-static double uni() {
-    uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * std::ldexp(1.0, -52) - 1.0;
-}
+static SplitMix64 g_rng;   // every case sets its state
+static double uni() { return g_rng.sym(); }
 static const uint64_t kSeed = 7;
 static const double kInputScale = std::ldexp(1.0, 50), kWeightScale = std::ldexp(1.0, 58);
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
-
-// the chain primes of FheParams::n8192 seen at ring degree 2^log2n (psi raised to the power 8192 / N); the last one is returned as the special prime
-static FheParams ring(unsigned log2n, size_t data_limbs, uint64_t& special, uint64_t& special_psi) {
-    FheParams p = FheParams::n8192(data_limbs + 1);
-    const size_t n = (size_t)1 << log2n;
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
-    special = p.moduli.back(); special_psi = p.psi.back();
-    p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
-    return p;
-}
 
 struct Shape { unsigned log2n; size_t out_dim, in_dim, T, tpc; const char* what; };
 static const Shape kShapes[] = {
@@ -82,7 +38,7 @@ struct Case {
     std::vector<double> W, b, x, y;   // x: [T * tpc][in_dim], y: [T * tpc][out_dim]
     double ymax = 0;
     Case(const Shape& s, size_t index, bool with_bias) {
-        g_state = kSeed * 1000 + index * 2 + (with_bias ? 1 : 0);
+        g_rng.state = kSeed * 1000 + index * 2 + (with_bias ? 1 : 0);
         const size_t tokens = s.T * s.tpc;
         W.resize(s.out_dim * s.in_dim); b.resize(s.out_dim); x.resize(tokens * s.in_dim); y.resize(tokens * s.out_dim);
         for (auto& v : W) v = uni();
@@ -185,7 +141,7 @@ static void run_shape(Rig& r, const Shape& s, size_t index, bool with_bias) {
 }
 
 // a null bias gives the words of the bias-less constructor; apply() behind the gate returns while the stream is held and gives the same words
-static void words_and_stream(Rig& r, void* S, double G) {
+static void words_and_stream(Rig& r, Gate& gate) {
     const Shape& s = kShapes[1];
     const Case c(s, 1, false);
     ApproxPackedLinear a(r.ctx, r.next, r.cenc, r.hks, c.W.data(), s.out_dim, s.in_dim, kWeightScale, kInputScale);
@@ -197,27 +153,13 @@ static void words_and_stream(Rig& r, void* S, double G) {
     b.apply(cx, yb);
     r.next.synchronize();
     CHECK(words(yb) == wa);
-    // the gate: warm-up on S (keys packed, scratch at its size), then the gate, an event, the call - which must come back with the event pending
-    hipStream_t hs = static_cast<hipStream_t>(S);
-    b.apply(cx, yb, S);
-    CHECK(hipStreamSynchronize(hs) == hipSuccess);
-    CHECK(hipMemset(yb.data(), 0xA5, yb.words() * 8) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    hipEvent_t E;
-    CHECK(hipEventCreateWithFlags(&E, hipEventDisableTiming) == hipSuccess);
-    const uint64_t ticks = (uint64_t)(G * 1e8);
-    CHECK(stream_gate_enqueue(S, ticks, 4 * ticks / 100) == 0);
-    CHECK(hipEventRecord(E, hs) == hipSuccess);
-    const auto t0 = std::chrono::steady_clock::now();
-    b.apply(cx, yb, S);
-    const double t_enqueue = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const hipError_t q = hipEventQuery(E);
-    if (q != hipErrorNotReady) { std::printf("FAIL ApproxPackedLinear::apply: synchronised - the gate had ended when the call returned (t_enqueue %.3f ms, G %.1f ms)\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    else if (t_enqueue > G / 4) { std::printf("FAIL ApproxPackedLinear::apply: inconclusive - t_enqueue %.3f ms > G / 4, G %.1f ms\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    (void)hipGetLastError();
-    CHECK(hipStreamSynchronize(hs) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    CHECK(hipEventDestroy(E) == hipSuccess);
+    // the gate, with the full protocol: the warm-up (keys packed, scratch at its size) and the gate on zero words in the input buffer, the encrypted tokens
+    // copied in on S behind the gate, the output wiped on S behind it; the call comes back with the event pending, within G / 4, with the same words
+    Ciphertext gx(r.ctx, 2, s.T), zero(r.ctx, 2, s.T);
+    HIP(hipMemset(zero.data(), 0, zero.words() * 8));
+    const double t_enqueue = gate.gated("ApproxPackedLinear::apply", {late(gx, zero, cx)}, {out_of(yb)}, [&](Stream* st) { b.apply(gx, yb, st); });
     CHECK(words(yb) == wa);
-    std::printf("ApproxPackedLinear::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, G * 1e3);
+    std::printf("ApproxPackedLinear::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, gate.G * 1e3);
 
     // Evaluator::add_plain / sub_plain on the layer's output: back to the input's words; both domains; the domain flags must agree
     Evaluator ev(r.next);
@@ -225,7 +167,7 @@ static void words_and_stream(Rig& r, void* S, double G) {
     for (size_t items : {(size_t)1, (size_t)s.T}) {
         Plaintext pt(r.next, items);
         std::vector<uint64_t> pw(items * poly);
-        g_state = 99 + items;
+        g_rng.state = 99 + items;
         for (size_t i = 0; i < pw.size(); ++i) {
             const uint64_t q = r.pn.moduli[(i / r.pn.n()) % r.pn.n_limbs()];
             pw[i] = (i % 5 == 0) ? q - 1 : (uint64_t)((uni() + 1.0) / 2.0 * (double)(q - 1));
@@ -302,25 +244,22 @@ int main(int argc, char** argv) {
     }
     const double G = argc > 1 ? std::atof(argv[1]) : 0.040;
     try {
-        void* S = nullptr;
-        if (stream_gate_stream_create(&S) != 0 || !S) { std::printf("no non-blocking stream\n"); return 2; }
+        Gate gate(G);
+        if (!gate.ok()) { std::printf("no non-blocking stream\n"); return 2; }
         {
             Rig r11(11);
             for (size_t i = 0; i < 3; ++i)
                 for (int bias = 0; bias < 2; ++bias) run_shape(r11, kShapes[i], i, bias != 0);
-            words_and_stream(r11, S, G);
+            words_and_stream(r11, gate);
             rejections(r11);
         }
         {
             Rig r10(10);
             for (int bias = 0; bias < 2; ++bias) run_shape(r10, kShapes[3], 3, bias != 0);
         }
-        stream_gate_stream_destroy(S);
     } catch (const std::exception& e) {
         std::printf("FAIL exception: %s\n", e.what());
         return 1;
     }
-    if (failures) { std::printf("%d failures\n", failures); return 1; }
-    std::printf("approximate packed layer C++ facade OK\n");
-    return 0;
+    return finish("approximate packed layer C++ facade OK");
 }

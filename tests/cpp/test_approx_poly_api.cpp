@@ -1,12 +1,9 @@
 // GPU test of the approximate family's activations in the C++ facade (HybridKeySwitcher::multiply_rescale, ApproxPolynomial): on ENCRYPTED inputs every
 // decoded slot of every token lies within the stated error bound of the float64 product / polynomial, the bound is at most 2^-10 of max|p(x)| >= 1 (a wrong
-// power, scale, weight or level gives errors of order max|p|); both calls return while their stream is held (the pattern of tests/cpp/test_stream_api.cpp)
+// power, scale, weight or level gives errors of order max|p|); both calls return while their stream is held (the gate of tests/cpp/facade_test.h)
 // and give the same words there; the constructor's and apply()'s rejections.  Built and run by tests/test_gpu_approx_poly.py (-m gpu).
 // `test_approx_poly_api ref` only draws the cases and prints max|p(x)| and ApproxPolynomial::error_bound of each (no device).  Exit code 0 = all passed.
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -16,40 +13,16 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
-
-extern "C" int stream_gate_enqueue(void* stream, uint64_t ticks, uint64_t max_iters);
-extern "C" int stream_gate_stream_create(void** out);
-extern "C" int stream_gate_stream_destroy(void* stream);
+#define FACADE_TEST_GATE
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
+using namespace facade_test;
 typedef std::complex<double> cplx;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
+static SplitMix64 g_rng;   // every case sets its state
+static double uni() { return g_rng.sym(); }
 
-// SplitMix64 -> uniform on [-1, 1]
-static uint64_t g_state = 0;
-static double uni() {
-    uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * std::ldexp(1.0, -52) - 1.0;
-}
 static const unsigned kLog2N = 12;
 static const size_t kDataLimbs = 5, kTokens = 3;
 static const double kInputScale = std::ldexp(1.0, 59), kOutputScale = std::ldexp(1.0, 50), kX = 2.0;
@@ -57,24 +30,13 @@ static const size_t kDegrees[] = {2, 3, 4, 7};
 
 static size_t ceil_log2(size_t k) { size_t r = 0; while (((size_t)1 << r) < k) ++r; return r; }
 
-// the chain primes of FheParams::n8192 seen at ring degree 2^log2n (psi raised to the power 8192 / N); the last one is returned as the special prime
-static FheParams ring(unsigned log2n, size_t data_limbs, uint64_t& special, uint64_t& special_psi) {
-    FheParams p = FheParams::n8192(data_limbs + 1);
-    const size_t n = (size_t)1 << log2n;
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
-    special = p.moduli.back(); special_psi = p.psi.back();
-    p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
-    return p;
-}
-
 // one case: a_0 = 2 and sum_{k >= 1} |a_k| X^k <= 0.9, so 1.1 <= p(x) <= 2.9 on [-X, X]; the tokens' slots uniform on [-X, X]; the float64 p(x)
 struct Case {
     size_t d;
     std::vector<double> a, x, y;   // x, y: [kTokens][N/2]
     double pmax = 0;
     explicit Case(size_t degree) : d(degree) {
-        g_state = 7000 + degree;
+        g_rng.state = 7000 + degree;
         const size_t row = ((size_t)1 << kLog2N) / 2;
         a.assign(d + 1, 2.0);
         for (size_t k = 1; k <= d; ++k) {
@@ -139,12 +101,6 @@ struct Rig {
     }
 };
 
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
-
 static void run_polynomial(Rig& r, size_t d) {
     const Case c(d);
     const size_t rstar = ceil_log2(d), row = r.params[0].n() / 2;
@@ -168,9 +124,9 @@ static void run_polynomial(Rig& r, size_t d) {
 }
 
 // a x b on encrypted inputs: the slot error of one product by the header's recurrence (D_2 with two different operands of modulus <= X), and the gate
-static void run_multiply_rescale(Rig& r, void* S, double G) {
+static void run_multiply_rescale(Rig& r, Gate& gate) {
     const size_t N = r.params[0].n(), row = N / 2, T = 2;
-    g_state = 4242;
+    g_rng.state = 4242;
     std::vector<double> xa(T * row), xb(T * row);
     for (auto& v : xa) v = kX * uni();
     for (auto& v : xb) v = kX * uni();
@@ -205,58 +161,29 @@ static void run_multiply_rescale(Rig& r, void* S, double G) {
     for (size_t i = 0; i < row; ++i) wp = std::max(wp, std::max(std::fabs(zp[row + i].real() - xa[row + i] * xb[i]), std::abs(zp[i])));
     CHECK(wp <= bound);
 
-    // the gate: warm-up on S, then the gate, an event, the call - which must come back with the event pending - and the same words
+    // the gate, with the full protocol: zero words in both operand buffers during the warm-up and the gate, the operands copied in on S behind it, the
+    // output wiped on S behind it; the call comes back with the event pending, within G / 4, and gives the words of the idle stream
     const std::vector<uint64_t> want = words(out);
-    hipStream_t hs = static_cast<hipStream_t>(S);
-    r.hks[0]->multiply_rescale(a, b, out, S);
-    CHECK(hipStreamSynchronize(hs) == hipSuccess);
-    CHECK(hipMemset(out.data(), 0xA5, out.words() * 8) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    hipEvent_t E;
-    CHECK(hipEventCreateWithFlags(&E, hipEventDisableTiming) == hipSuccess);
-    const uint64_t ticks = (uint64_t)(G * 1e8);
-    CHECK(stream_gate_enqueue(S, ticks, 4 * ticks / 100) == 0);
-    CHECK(hipEventRecord(E, hs) == hipSuccess);
-    const auto t0 = std::chrono::steady_clock::now();
-    r.hks[0]->multiply_rescale(a, b, out, S);
-    const double t_enqueue = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const hipError_t qy = hipEventQuery(E);
-    if (qy != hipErrorNotReady) { std::printf("FAIL multiply_rescale: synchronised - the gate had ended when the call returned (t_enqueue %.3f ms, G %.1f ms)\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    else if (t_enqueue > G / 4) { std::printf("FAIL multiply_rescale: inconclusive - t_enqueue %.3f ms > G / 4, G %.1f ms\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    (void)hipGetLastError();
-    CHECK(hipStreamSynchronize(hs) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    CHECK(hipEventDestroy(E) == hipSuccess);
+    Ciphertext ga(*r.ctx[0], 2, T), gb(*r.ctx[0], 2, T), zero(*r.ctx[0], 2, T);
+    HIP(hipMemset(zero.data(), 0, zero.words() * 8));
+    const double t_enqueue = gate.gated("HybridKeySwitcher::multiply_rescale", {late(ga, zero, a), late(gb, zero, b)}, {out_of(out)},
+                                        [&](Stream* s) { r.hks[0]->multiply_rescale(ga, gb, out, s); });
     CHECK(words(out) == want);
-    std::printf("HybridKeySwitcher::multiply_rescale behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, G * 1e3);
+    std::printf("HybridKeySwitcher::multiply_rescale behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, gate.G * 1e3);
 }
 
-static void polynomial_behind_the_gate(Rig& r, void* S, double G) {
+static void polynomial_behind_the_gate(Rig& r, Gate& gate) {
     const Case c(7);
     ApproxPolynomial poly(r.levels(3), *r.ctx[3], *r.ctx[4], c.a, kInputScale, kOutputScale);
-    Ciphertext x(*r.ctx[0], 2, kTokens), y(*r.ctx[4], 2, kTokens);
-    r.encrypt(c.x.data(), kTokens, x);
-    poly.apply(x, y);
+    Ciphertext x(*r.ctx[0], 2, kTokens), real(*r.ctx[0], 2, kTokens), zero(*r.ctx[0], 2, kTokens), y(*r.ctx[4], 2, kTokens);
+    r.encrypt(c.x.data(), kTokens, real);
+    HIP(hipMemset(zero.data(), 0, zero.words() * 8));
+    poly.apply(real, y);
     r.ctx[0]->synchronize();
     const std::vector<uint64_t> want = words(y);
-    hipStream_t hs = static_cast<hipStream_t>(S);
-    poly.apply(x, y, S);
-    CHECK(hipStreamSynchronize(hs) == hipSuccess);
-    CHECK(hipMemset(y.data(), 0xA5, y.words() * 8) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    hipEvent_t E;
-    CHECK(hipEventCreateWithFlags(&E, hipEventDisableTiming) == hipSuccess);
-    const uint64_t ticks = (uint64_t)(G * 1e8);
-    CHECK(stream_gate_enqueue(S, ticks, 4 * ticks / 100) == 0);
-    CHECK(hipEventRecord(E, hs) == hipSuccess);
-    const auto t0 = std::chrono::steady_clock::now();
-    poly.apply(x, y, S);
-    const double t_enqueue = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const hipError_t qy = hipEventQuery(E);
-    if (qy != hipErrorNotReady) { std::printf("FAIL ApproxPolynomial::apply: synchronised - the gate had ended when the call returned (t_enqueue %.3f ms, G %.1f ms)\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    else if (t_enqueue > G / 4) { std::printf("FAIL ApproxPolynomial::apply: inconclusive - t_enqueue %.3f ms > G / 4, G %.1f ms\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    (void)hipGetLastError();
-    CHECK(hipStreamSynchronize(hs) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    CHECK(hipEventDestroy(E) == hipSuccess);
+    const double t_enqueue = gate.gated("ApproxPolynomial::apply", {late(x, zero, real)}, {out_of(y)}, [&](Stream* s) { poly.apply(x, y, s); });
     CHECK(words(y) == want);
-    std::printf("ApproxPolynomial::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, G * 1e3);
+    std::printf("ApproxPolynomial::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, gate.G * 1e3);
 }
 
 static void rejections(Rig& r) {
@@ -313,21 +240,16 @@ int main(int argc, char** argv) {
     }
     const double G = argc > 1 ? std::atof(argv[1]) : 0.040;
     try {
-        void* S = nullptr;
-        if (stream_gate_stream_create(&S) != 0 || !S) { std::printf("no non-blocking stream\n"); return 2; }
-        {
-            Rig r;
-            for (size_t d : kDegrees) run_polynomial(r, d);
-            run_multiply_rescale(r, S, G);
-            polynomial_behind_the_gate(r, S, G);
-            rejections(r);
-        }
-        stream_gate_stream_destroy(S);
+        Gate gate(G);
+        if (!gate.ok()) { std::printf("no non-blocking stream\n"); return 2; }
+        Rig r;
+        for (size_t d : kDegrees) run_polynomial(r, d);
+        run_multiply_rescale(r, gate);
+        polynomial_behind_the_gate(r, gate);
+        rejections(r);
     } catch (const std::exception& e) {
         std::printf("FAIL exception: %s\n", e.what());
         return 1;
     }
-    if (failures) { std::printf("%d failures\n", failures); return 1; }
-    std::printf("approximate polynomial C++ facade OK\n");
-    return 0;
+    return finish("approximate polynomial C++ facade OK");
 }

@@ -6,41 +6,13 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-static uint64_t g_seed = 1234;
-static uint64_t rnd(uint64_t m) { g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull; return (g_seed >> 33) % m; }
-static const uint64_t T_MOD = 65537;
-static uint64_t small8() { return (T_MOD + rnd(255) - 127) % T_MOD; }
-
-// y = W x + b mod t
-static std::vector<uint64_t> affine(const std::vector<uint64_t>& W, const uint64_t* b, size_t rows, size_t cols, const uint64_t* x) {
-    std::vector<uint64_t> y(rows);
-    for (size_t r = 0; r < rows; ++r) {
-        unsigned __int128 acc = b ? b[r] : 0;
-        for (size_t c = 0; c < cols; ++c) acc += (unsigned __int128)W[r * cols + c] * x[c];
-        y[r] = (uint64_t)(acc % T_MOD);
-    }
-    return y;
-}
+static Lcg rnd{1234};
+static uint64_t small8() { return rnd.small8(); }
 
 // compact at the recommended widths, save, load into a fresh object, decrypt: the messages mod t, and the budget
 static std::vector<uint64_t> compact_round_trip(const Context& ctx, const Evaluator& ev, Decryptor& dec, const Ciphertext& ct, double& budget) {
@@ -155,7 +127,7 @@ static void linear768() {
     for (size_t tk = 0; tk < T; ++tk) {
         for (size_t o = 0; o < outs; ++o) be.decode(&dm[(o * T + tk) * n], &got[o * n]);
         lin.unpack_output(got.data(), y.data());
-        bad += y != affine(W, bias.data(), d, d, &x[tk * d]);
+        bad += y != affine(W, bias.data(), d, d, &x[tk * d], T_MOD);
     }
     CHECK(bad == 0);
     CHECK(budget >= 1);
@@ -212,11 +184,11 @@ static void ffn_act16384() {
     CHECK(dm == full);                                         // compact and full words decrypt alike
     size_t bad = 0;
     for (size_t tk = 0; tk < T; ++tk) {
-        std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, &x[tk * d]);
+        std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, &x[tk * d], T_MOD);
         for (auto& v : u) v = (uint64_t)((unsigned __int128)v * v % T_MOD);
         be2.decode(&dm[tk * n], got.data());
         down.unpack_output(got.data(), y.data());
-        bad += y != affine(Wd, bd.data(), d, h, u.data());
+        bad += y != affine(Wd, bd.data(), d, h, u.data(), T_MOD);
     }
     CHECK(bad == 0);
     CHECK(budget >= 1);
@@ -232,10 +204,5 @@ int main() {
         std::printf("exception: %s\n", e.what());
         return 2;
     }
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("compact C++ facade OK\n");
-    return 0;
+    return finish("compact C++ facade OK");
 }

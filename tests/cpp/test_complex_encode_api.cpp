@@ -9,39 +9,16 @@
 #include <cstdio>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 #include "dpfhe.h"
 
 using namespace deeppowers::fhe;
 typedef std::complex<double> cplx;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
+static Lcg g_lcg{2026};
+static double rnd_unit() { return (double)(int64_t)(g_lcg.step() >> 11) / 4503599627370496.0 - 1.0; }   // uniform in [-1, 1): the top 53 bits of the state
 
-static uint64_t g_seed = 2026;
-static double rnd_unit() {   // uniform in [-1, 1)
-    g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)(int64_t)(g_seed >> 11) / 4503599627370496.0 - 1.0;
-}
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
 static uint64_t lift(int64_t v, uint64_t q) {
     const int64_t r = (int64_t)((__int128)v % (__int128)q);
     return (uint64_t)(r < 0 ? r + (int64_t)q : r);
@@ -209,7 +186,5 @@ int main() {
         std::printf("FAIL exception: %s\n", e.what());
         return 1;
     }
-    if (failures) { std::printf("%d checks failed\n", failures); return 1; }
-    std::printf("complex encode C++ facade OK\n");
-    return 0;
+    return finish("complex encode C++ facade OK");
 }

@@ -7,35 +7,14 @@
 #include <cstdio>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 #include "dpfhe.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
+static Lcg rnd{2026};
 
-static uint64_t g_seed = 2026;
-static uint64_t rnd(uint64_t m) { g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull; return (g_seed >> 33) % m; }
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
 static uint64_t lift(int64_t v, uint64_t q) {
     const int64_t r = (int64_t)((__int128)v % (__int128)q);
     return (uint64_t)(r < 0 ? r + (int64_t)q : r);
@@ -165,7 +144,5 @@ int main() {
         std::printf("FAIL exception: %s\n", e.what());
         return 1;
     }
-    if (failures) { std::printf("%d checks failed\n", failures); return 1; }
-    std::printf("encode C++ facade OK\n");
-    return 0;
+    return finish("encode C++ facade OK");
 }

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 extern "C" {
 struct orc_ctx;
@@ -22,11 +22,7 @@ void orc_matvec_plain(const orc_ctx* c, uint64_t* y, const uint64_t* W, const ui
 }
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                         \
-    do {                                                                    \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; } \
-    } while (0)
+using namespace facade_test;
 
 static void run(const FheParams& p, size_t batch) {
     const size_t L = p.n_limbs(), n = p.n();
@@ -133,9 +129,8 @@ static void large_ring() {
     FheParams p;
     p.log2_n = 14;
     for (uint64_t q : {1152921504606748673ull, 1152921504606683137ull, 1152921504606584833ull}) {   // pinned primes = 1 mod 32768
-        auto pw = [q](uint64_t b, uint64_t e) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
         uint64_t psi = 0;
-        for (uint64_t g = 2; !psi; ++g) { const uint64_t z = pw(g, (q - 1) / 32768); if (pw(z, 16384) == q - 1) psi = z; }
+        for (uint64_t g = 2; !psi; ++g) { const uint64_t z = modpow(g, (q - 1) / 32768, q); if (modpow(z, 16384, q) == q - 1) psi = z; }
         p.moduli.push_back(q); p.psi.push_back(psi);
     }
     const size_t L = p.n_limbs(), n = p.n(), batch = 2;
@@ -182,8 +177,7 @@ static void packed_rect(unsigned log2n) {
     FheParams p = FheParams::n8192_l6();
     const size_t n = (size_t)1 << log2n;
     const uint64_t special = p.moduli.back();
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
+    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = modpow(p.psi[l], 8192 / n, p.moduli[l]);
     const uint64_t special_psi = p.psi.back();
     p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
     Context ctx(p, 0);
@@ -193,8 +187,8 @@ static void packed_rect(unsigned log2n) {
     BatchEncoder be(ctx, 65537);
     const uint64_t t = be.plain_modulus();
     HybridKeySwitcher hks(ctx, kg.secret_key(), special, special_psi, TestSeed{33});
-    uint64_t s = 17;
-    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (s >> 33) % t; };
+    Lcg lcg{17};
+    auto rnd = [&]() { return lcg(t); };
     // (out, in): blocks sharing one ciphertext | ragged sizes | more blocks than windows (2 outputs) | one block | wide input
     // with folding | wide input, ragged | single-row output
     const size_t shapes[][2] = {{96, 32}, {77, 24}, {n + 40, 16}, {20, 32}, {16, 128}, {12, 100}, {1, 64}, {n / 2, n / 2}};
@@ -307,8 +301,8 @@ static void end_to_end(const FheParams& p, size_t batch) {
     RelinKeys rk(ctx);
     kg.create_relin_keys(rk);
     std::vector<int64_t> m1(batch * n), m2(batch * n), out(batch * n), want(batch * n, 0);
-    uint64_t s = 99;
-    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (int64_t)((s >> 33) % 201) - 100; };
+    Lcg lcg{99};
+    auto rnd = [&]() { return (int64_t)lcg(201) - 100; };
     for (auto& v : m1) v = rnd();
     for (auto& v : m2) v = rnd();
     for (size_t b = 0; b < batch; ++b)
@@ -414,8 +408,7 @@ static void packed(unsigned log2n, size_t d) {
     FheParams p = FheParams::n8192_l6();          // six pinned primes = 1 mod 16384; psi_N = psi_8192^(8192/N)
     const size_t n = (size_t)1 << log2n, row = n / 2;
     const uint64_t special = p.moduli.back();
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
+    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = modpow(p.psi[l], 8192 / n, p.moduli[l]);
     const uint64_t special_psi = p.psi.back();
     p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();    // 5 data limbs + the 6th as the special prime
     Context ctx(p, 0);
@@ -424,8 +417,8 @@ static void packed(unsigned log2n, size_t d) {
     Decryptor dec(ctx, kg.secret_key());
     BatchEncoder be(ctx, 65537);
     const uint64_t t = be.plain_modulus();
-    uint64_t s = 7;
-    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (s >> 33) % t; };
+    Lcg lcg{7};
+    auto rnd = [&]() { return lcg(t); };
     // encoder round trip, and slot-wise product = polynomial product
     std::vector<uint64_t> va(n), vb(n), got(n);
     for (auto& v : va) v = rnd();
@@ -521,6 +514,5 @@ int main() {
         std::printf("unexpected exception: %s\n", e.what());
         return 2;
     }
-    std::printf(failures ? "FAILED (%d)\n" : "OK\n", failures);
-    return failures ? 1 : 0;
+    return finish("OK");
 }

@@ -8,41 +8,18 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-static uint64_t g_seed = 4321;
-static uint64_t rnd(uint64_t m) { g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull; return (g_seed >> 33) % m; }
-static const uint64_t T_MOD = 65537;
-static uint64_t small8() { return (T_MOD + rnd(255) - 127) % T_MOD; }
+static Lcg rnd{4321};
+static uint64_t small8() { return rnd.small8(); }
 
 static double log2_q(const FheParams& p) {
     double s = 0;
     for (uint64_t q : p.moduli) s += std::log2((double)q);
     return s;
-}
-
-static std::vector<uint64_t> words_of(const Ciphertext& ct) {
-    std::vector<uint64_t> w(ct.words());
-    ct.copy_to_host(w.data());
-    return w;
 }
 
 // ---- (a), (b), (d): a fresh exact ciphertext at N = 4096, four pinned limbs ------------------------------------------------------------
@@ -59,14 +36,14 @@ static void fresh() {
     for (auto& v : m) v = (int64_t)rnd(T_MOD);
     Ciphertext ct(ctx, 2, B);
     enc.encrypt_exact(m.data(), T_MOD, ct);
-    const std::vector<uint64_t> before = words_of(ct);
+    const std::vector<uint64_t> before = words(ct);
     const double fresh_budget = dec.noise_budget_bits(ct, T_MOD);
 
     // (a) flood_bits = 100 under a TestSeed
     Rerandomizer rr(ctx, pk, TestSeed{113});
     rr.rerandomize(ct, T_MOD, 100);
     ctx.synchronize();
-    const std::vector<uint64_t> after = words_of(ct);
+    const std::vector<uint64_t> after = words(ct);
     std::vector<uint64_t> got(B * n);
     dec.decrypt_exact(ct, T_MOD, got.data());
     size_t bad = 0, c1_changed = 0, c0_changed = 0;
@@ -101,7 +78,7 @@ static void fresh() {
     os_rr.rerandomize(x, T_MOD, 100);
     os_rr.rerandomize(y, T_MOD, 100);
     ctx.synchronize();
-    const std::vector<uint64_t> wx = words_of(x), wy = words_of(y);
+    const std::vector<uint64_t> wx = words(x), wy = words(y);
     size_t differ = 0;
     for (size_t i = 0; i < wx.size(); ++i) differ += wx[i] != wy[i];
     CHECK(2 * differ > wx.size());
@@ -138,17 +115,6 @@ static void fresh() {
     CHECK(Rerandomizer::flood_bits_for(82.0, 12, 64) == 82 + 64 + 12);
 }
 
-// y = W x + b mod t
-static std::vector<uint64_t> affine(const std::vector<uint64_t>& W, const uint64_t* b, size_t rows, size_t cols, const uint64_t* x) {
-    std::vector<uint64_t> y(rows);
-    for (size_t r = 0; r < rows; ++r) {
-        unsigned __int128 acc = b ? b[r] : 0;
-        for (size_t c = 0; c < cols; ++c) acc += (unsigned __int128)W[r * cols + c] * x[c];
-        y[r] = (uint64_t)(acc % T_MOD);
-    }
-    return y;
-}
-
 // ---- (c) a biased 768 x 768 PackedLinear at N = 8192, five data limbs: evaluate -> rerandomize -> compact -> decrypt ------------------------
 static void linear768() {
     FheParams p = FheParams::n8192(6);
@@ -182,12 +148,12 @@ static void linear768() {
     // the client reads the budget of this circuit once; the server uses the bound from then on
     const double b = dec.noise_budget_bits(cy, T_MOD), lq = log2_q(p), noise_bits = lq - 1 - std::log2((double)T_MOD) - b;
     const unsigned flood_bits = Rerandomizer::flood_bits_for(noise_bits, 13);
-    const std::vector<uint64_t> c_before = words_of(cy);
+    const std::vector<uint64_t> c_before = words(cy);
     Rerandomizer rr(ctx, pk, TestSeed{94});
     CHECK(flood_bits <= rr.max_flood_bits(T_MOD));
     rr.rerandomize(cy, T_MOD, flood_bits);
     ctx.synchronize();
-    const std::vector<uint64_t> c_after = words_of(cy);
+    const std::vector<uint64_t> c_after = words(cy);
     size_t changed = 0;
     for (size_t i = 0; i < c_after.size(); ++i) changed += c_after[i] != c_before[i];
     CHECK(2 * changed > c_after.size());
@@ -202,7 +168,7 @@ static void linear768() {
     for (size_t tk = 0; tk < T; ++tk) {
         for (size_t o = 0; o < outs; ++o) be.decode(&dm[(o * T + tk) * n], &got[o * n]);
         lin.unpack_output(got.data(), y.data());
-        bad += y != affine(W, bias.data(), d, d, &x[tk * d]);
+        bad += y != affine(W, bias.data(), d, d, &x[tk * d], T_MOD);
     }
     CHECK(bad == 0);
     CHECK(b_after >= 2);
@@ -220,10 +186,5 @@ int main() {
         std::printf("exception: %s\n", e.what());
         return 2;
     }
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("rerandomize C++ facade OK\n");
-    return 0;
+    return finish("rerandomize C++ facade OK");
 }

@@ -6,31 +6,11 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
+using namespace facade_test;
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
 
 static std::string save_v1(const PolyBuffer& b) { std::ostringstream os; b.save(os); return os.str(); }
 static std::string save_s1(const PolyBuffer& b, const Seed& s) { std::ostringstream os; b.save_seeded(os, s); return os.str(); }
@@ -62,8 +42,8 @@ static void approximate(const FheParams& p, size_t batch) {
     Encryptor enc(ctx, kg.secret_key(), TestSeed{42});
     Decryptor dec(ctx, kg.secret_key());
     std::vector<int64_t> m1(batch * n), m2(batch * n), out(batch * n);
-    uint64_t s = 5;
-    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (int64_t)((s >> 33) % 201) - 100; };
+    Lcg lcg{5};
+    auto rnd = [&]() { return (int64_t)lcg(201) - 100; };
     for (auto& v : m1) v = rnd();
     for (auto& v : m2) v = rnd();
     const unsigned scale = 45;
@@ -203,8 +183,8 @@ static void exact(size_t batch) {
     Seed ks{};
     kg.create_relin_keys_seeded(rk, ks);
     std::vector<int64_t> a(batch * n), b(batch * n);
-    uint64_t s = 17;
-    auto rnd = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (int64_t)((s >> 33) % t); };
+    Lcg lcg{17};
+    auto rnd = [&]() { return (int64_t)lcg(t); };
     for (auto& v : a) v = rnd();
     for (auto& v : b) v = rnd();
     Ciphertext ca(lctx, 2, batch), cb(lctx, 2, batch), c3(lctx, 3, batch), cr(lctx, 2, batch);
@@ -231,7 +211,5 @@ int main() {
     approximate(FheParams::n4096_l4(), 3);
     approximate(FheParams::n8192_l6(), 2);
     exact(2);
-    if (failures) { std::printf("%d FAILURES\n", failures); return 1; }
-    std::printf("seeded C++ facade OK\n");
-    return 0;
+    return finish("seeded C++ facade OK");
 }

@@ -2,13 +2,10 @@
 // family every decoded slot of every token lies within SlotSum::error_bound of the float64 sum  sum_{j < block} x[(i + j stride) mod N/2]  (blocks 2, 8 and
 // 2048 at stride 1, block 8 at stride 4; three tokens), the bound is at most 2^-10 of max|sum| >= 1 (a wrong element, step count or stride gives errors of
 // the order of the sums); in the exact family (block 8) the decrypted slots equal the sums mod t in both rows; apply() returns while its stream is held (the
-// pattern of tests/cpp/test_stream_api.cpp) and gives the same words there; the rejections.  Built and run by tests/test_gpu_slot_sum.py (-m gpu), which
+// gate of tests/cpp/facade_test.h) and gives the same words there; the rejections.  Built and run by tests/test_gpu_slot_sum.py (-m gpu), which
 // also compares the words this program dumps with the Python mirror's.
 // `test_slot_sum_api ref` only draws the cases and prints max|sum| and SlotSum::error_bound of each (no device).  Exit code 0 = all passed.
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -18,40 +15,14 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
-
-extern "C" int stream_gate_enqueue(void* stream, uint64_t ticks, uint64_t max_iters);
-extern "C" int stream_gate_stream_create(void** out);
-extern "C" int stream_gate_stream_destroy(void* stream);
+#define FACADE_TEST_GATE
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
+using namespace facade_test;
 typedef std::complex<double> cplx;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
 
-template <class F>
-static void expect_error(ErrorCode code, F f, const char* what) {
-    try {
-        f();
-        std::printf("FAIL %s: no exception\n", what);
-        ++failures;
-    } catch (const Exception& e) {
-        if (e.code() != code) { std::printf("FAIL %s: code %d (%s)\n", what, (int)e.code(), e.what()); ++failures; }
-    }
-}
-
-// SplitMix64 -> uniform on [0, 1)
-static uint64_t g_state = 0;
-static uint64_t next64() {
-    uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static double uni() { return (double)(next64() >> 11) * std::ldexp(1.0, -53); }
+static SplitMix64 g_rng;   // every case sets its state
 
 static const unsigned kLog2N = 12;
 static const size_t kDataLimbs = 4, kTokens = 3, kN = (size_t)1 << kLog2N, kRow = kN / 2;
@@ -59,26 +30,15 @@ static const double kScale = std::ldexp(1.0, 50), kX = 1.0;
 static const size_t kCases[][2] = {{2, 1}, {8, 1}, {2048, 1}, {8, 4}};   // (block, stride)
 static const uint64_t kT = 65537;
 
-// the chain primes of FheParams::n8192 seen at ring degree 2^log2n (psi raised to the power 8192 / N); the last one is returned as the special prime
-static FheParams ring(unsigned log2n, size_t data_limbs, uint64_t& special, uint64_t& special_psi) {
-    FheParams p = FheParams::n8192(data_limbs + 1);
-    const size_t n = (size_t)1 << log2n;
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
-    special = p.moduli.back(); special_psi = p.psi.back();
-    p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
-    return p;
-}
-
 // one case: the tokens' slots uniform on [0.5, 1] (no period: the general statement of the sum), the float64 sums
 struct Case {
     size_t block, stride;
     std::vector<double> x, y;   // [kTokens][N/2]
     double smax = 0;
     Case(size_t b, size_t s) : block(b), stride(s) {
-        g_state = 9000 + 17 * b + s;
+        g_rng.state = 9000 + 17 * b + s;
         x.resize(kTokens * kRow); y.resize(kTokens * kRow);
-        for (auto& v : x) v = 0.5 + 0.5 * uni();
+        for (auto& v : x) v = 0.5 + 0.5 * g_rng.unit();
         for (size_t t = 0; t < kTokens; ++t)
             for (size_t i = 0; i < kRow; ++i) {
                 double acc = 0;
@@ -127,12 +87,6 @@ struct Rig {
     }
 };
 
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
-
 static void run_approx(Rig& r, size_t block, size_t stride) {
     const Case c(block, stride);
     SlotSum sum(*r.ks, block, stride);
@@ -161,10 +115,10 @@ static void run_approx(Rig& r, size_t block, size_t stride) {
 static void run_exact(Rig& r) {
     const size_t block = 8, T = 2;
     SlotSum sum(*r.ks, block);
-    g_state = 515;
+    g_rng.state = 515;
     std::vector<uint64_t> slots(T * kN), got(T * kN), dec(T * kN);
     std::vector<int64_t> msg(T * kN);
-    for (auto& v : slots) v = next64() % kT;
+    for (auto& v : slots) v = g_rng.next() % kT;
     for (size_t t = 0; t < T; ++t) r.benc->encode(&slots[t * kN], &msg[t * kN]);
     Ciphertext x(*r.ctx, 2, T), y(*r.ctx, 2, T);
     r.enc->encrypt_exact(msg.data(), kT, x);
@@ -203,35 +157,20 @@ static void run_ranges(Rig& r) {
     CHECK(std::all_of(wp.begin(), wp.begin() + 2 * item, [](uint64_t v) { return v == 0; }));
 }
 
-// the gate: warm-up on S, then the gate, an event, the call - which must come back with the event pending - and the same words
-static void behind_the_gate(Rig& r, void* S, double G, const char* dump) {
+// the gate, with the full protocol: zero words in the input buffer during the warm-up and the gate, the encrypted tokens copied in on S behind it, the
+// output wiped on S behind it; the call comes back with the event pending, within G / 4, and gives the words of the idle stream
+static void behind_the_gate(Rig& r, Gate& gate, const char* dump) {
     const Case c(2048, 1);
     SlotSum sum(*r.ks, 2048);
-    Ciphertext x(*r.ctx, 2, kTokens), y(*r.ctx, 2, kTokens);
-    r.encrypt(c.x.data(), kTokens, x);
-    sum.apply(x, y);
+    Ciphertext x(*r.ctx, 2, kTokens), real(*r.ctx, 2, kTokens), zero(*r.ctx, 2, kTokens), y(*r.ctx, 2, kTokens);
+    r.encrypt(c.x.data(), kTokens, real);
+    HIP(hipMemset(zero.data(), 0, zero.words() * 8));
+    sum.apply(real, y);
     r.ctx->synchronize();
     const std::vector<uint64_t> want = words(y);
-    hipStream_t hs = static_cast<hipStream_t>(S);
-    sum.apply(x, y, S);
-    CHECK(hipStreamSynchronize(hs) == hipSuccess);
-    CHECK(hipMemset(y.data(), 0xA5, y.words() * 8) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    hipEvent_t E;
-    CHECK(hipEventCreateWithFlags(&E, hipEventDisableTiming) == hipSuccess);
-    const uint64_t ticks = (uint64_t)(G * 1e8);
-    CHECK(stream_gate_enqueue(S, ticks, 4 * ticks / 100) == 0);
-    CHECK(hipEventRecord(E, hs) == hipSuccess);
-    const auto t0 = std::chrono::steady_clock::now();
-    sum.apply(x, y, S);
-    const double t_enqueue = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const hipError_t qy = hipEventQuery(E);
-    if (qy != hipErrorNotReady) { std::printf("FAIL SlotSum::apply: synchronised - the gate had ended when the call returned (t_enqueue %.3f ms, G %.1f ms)\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    else if (t_enqueue > G / 4) { std::printf("FAIL SlotSum::apply: inconclusive - t_enqueue %.3f ms > G / 4, G %.1f ms\n", t_enqueue * 1e3, G * 1e3); ++failures; }
-    (void)hipGetLastError();
-    CHECK(hipStreamSynchronize(hs) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
-    CHECK(hipEventDestroy(E) == hipSuccess);
+    const double t_enqueue = gate.gated("SlotSum::apply", {late(x, zero, real)}, {out_of(y)}, [&](Stream* s) { sum.apply(x, y, s); });
     CHECK(words(y) == want);
-    std::printf("SlotSum::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, G * 1e3);
+    std::printf("SlotSum::apply behind the gate: t_enqueue %.3f ms, G %.1f ms\n", t_enqueue * 1e3, gate.G * 1e3);
     if (dump) {   // what the Python mirror is compared with: the context, the ladder's elements and packed keys, the input and output words of item 0 and 1
         const FheParams& pe = r.ks->extended_context().params();
         const size_t L = pe.n_limbs(), Ld = L - 1, steps = sum.steps(), T = 2;
@@ -292,22 +231,17 @@ int main(int argc, char** argv) {
     const double G = argc > 1 ? std::atof(argv[1]) : 0.040;
     const char* dump = argc > 2 ? argv[2] : nullptr;
     try {
-        void* S = nullptr;
-        if (stream_gate_stream_create(&S) != 0 || !S) { std::printf("no non-blocking stream\n"); return 2; }
-        {
-            Rig r;
-            for (const auto& bs : kCases) run_approx(r, bs[0], bs[1]);
-            run_exact(r);
-            run_ranges(r);
-            behind_the_gate(r, S, G, dump);
-            rejections(r);
-        }
-        stream_gate_stream_destroy(S);
+        Gate gate(G);
+        if (!gate.ok()) { std::printf("no non-blocking stream\n"); return 2; }
+        Rig r;
+        for (const auto& bs : kCases) run_approx(r, bs[0], bs[1]);
+        run_exact(r);
+        run_ranges(r);
+        behind_the_gate(r, gate, dump);
+        rejections(r);
     } catch (const std::exception& e) {
         std::printf("FAIL exception: %s\n", e.what());
         return 1;
     }
-    if (failures) { std::printf("%d failures\n", failures); return 1; }
-    std::printf("slot sum C++ facade OK\n");
-    return 0;
+    return finish("slot sum C++ facade OK");
 }

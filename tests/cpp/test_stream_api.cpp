@@ -1,16 +1,11 @@
 // GPU test of the Stream* argument of the C++ facade (include/deeppowers/fhe.hpp): every method that promises "enqueues on `stream`" is run on ONE
-// non-blocking stream S behind the gate of tests/cpp/stream_gate.hip, with the protocol of tests/stream_gate.py:
-//   warm-up on zero inputs (an encryption of zero in the input ciphertext buffer) on S, synchronise;  gate on S, event E, then the real inputs arrive by
-//   hipMemcpyAsync on S and every output buffer is wiped on S;  the call, timed on the host;  hipEventQuery(E) must still be hipErrorNotReady (the call
-//   waited for neither S nor the device) and the call must have taken at most G / 4;  synchronise S;  the result decrypts to the plaintext computation
-//   (or, for the word-level Evaluator methods, equals the words of the same call on the idle null stream) and differs from the warm-up's.
-// A launch or copy on another stream runs during the gate, on the zero inputs or on the warm-up's intermediates, or is wiped: the result is wrong.
+// non-blocking stream S behind the gate of tests/cpp/stream_gate.hip, with the protocol of Gate::gated (tests/cpp/facade_test.h): the warm-up and the gate
+// run on zero inputs (an encryption of zero in the input ciphertext buffer), the real inputs arrive and the outputs are wiped on S behind the gate, the call
+// must return with the gate's event pending and within G / 4.  Here, after S has run, the result decrypts to the plaintext computation (or, for the
+// word-level Evaluator methods, equals the words of the same call on the idle null stream).
 // The three methods that synchronise `stream` on purpose (Evaluator::apply_galois, HybridKeySwitcher::relinearize / apply_galois) are held to their
 // values, and to returning only after S has run (they waited for S).
 // Built and run by tests/test_gpu_stream_contract.py (-m gpu); argv[1] = G in seconds.  Exit code 0 = all checks passed.
-#include <hip/hip_runtime_api.h>
-
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,115 +13,14 @@
 #include <string>
 #include <vector>
 
-#include "deeppowers/fhe.hpp"
-
-extern "C" int stream_gate_enqueue(void* stream, uint64_t ticks, uint64_t max_iters);
-extern "C" int stream_gate_stream_create(void** out);
-extern "C" int stream_gate_stream_destroy(void* stream);
+#define FACADE_TEST_GATE
+#include "facade_test.h"
 
 using namespace deeppowers::fhe;
-static int failures = 0;
-#define CHECK(cond)                                                                                  \
-    do {                                                                                             \
-        if (!(cond)) { std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond); ++failures; }   \
-    } while (0)
-#define HIP(call)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess) { std::printf("FAIL %s:%d  %s: %s\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); ++failures; } \
-    } while (0)
+using namespace facade_test;
 
-static uint64_t g_seed = 2024;
-static uint64_t rnd(uint64_t m) { g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull; return (g_seed >> 33) % m; }
-static const uint64_t T_MOD = 65537;
-static uint64_t small8() { return (T_MOD + rnd(255) - 127) % T_MOD; }
-
-static void* S = nullptr;        // the non-blocking stream
-static double G = 0.040;         // the gate, seconds
-static double slowest = 0;
-static std::string slowest_what;
-static int gated_calls = 0;
-
-struct Late { void* dst; const void* zero; const void* real; size_t bytes; };   // an input buffer: zeros during the warm-up and the gate, the real words behind it
-struct Out { void* p; size_t bytes; };                                          // an output buffer: wiped behind the gate
-
-static std::vector<uint8_t> download(const std::vector<Out>& outs) {
-    size_t total = 0;
-    for (auto& o : outs) total += o.bytes;
-    std::vector<uint8_t> h(total);
-    size_t at = 0;
-    for (auto& o : outs) { HIP(hipMemcpy(h.data() + at, o.p, o.bytes, hipMemcpyDeviceToHost)); at += o.bytes; }
-    return h;
-}
-
-// enqueue_only: the protocol above.  Otherwise (a method documented to synchronise `stream`): the call must return only after S has run.
-static void gated(const char* what, const std::vector<Late>& ins, const std::vector<Out>& outs, const std::function<void(Stream*)>& call, bool enqueue_only = true) {
-    hipStream_t hs = static_cast<hipStream_t>(S);
-    for (auto& i : ins) HIP(hipMemcpy(i.dst, i.zero, i.bytes, hipMemcpyDeviceToDevice));
-    HIP(hipDeviceSynchronize());
-    call(S);
-    HIP(hipStreamSynchronize(hs));
-    const std::vector<uint8_t> warm = download(outs.empty() ? std::vector<Out>{{ins[0].dst, ins[0].bytes}} : outs);
-    for (auto& i : ins) HIP(hipMemcpy(i.dst, i.zero, i.bytes, hipMemcpyDeviceToDevice));   // (an in-place method changed its input)
-    HIP(hipDeviceSynchronize());
-    hipEvent_t E;
-    HIP(hipEventCreateWithFlags(&E, hipEventDisableTiming));
-    const uint64_t ticks = (uint64_t)(G * 1e8);
-    CHECK(stream_gate_enqueue(S, ticks, 4 * ticks / 100) == 0);
-    HIP(hipEventRecord(E, hs));
-    for (auto& i : ins) HIP(hipMemcpyAsync(i.dst, i.real, i.bytes, hipMemcpyDeviceToDevice, hs));
-    for (auto& o : outs) HIP(hipMemsetAsync(o.p, 0xA5, o.bytes, hs));
-    const auto t0 = std::chrono::steady_clock::now();
-    call(S);
-    const double t_enqueue = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const hipError_t q = hipEventQuery(E);
-    if (enqueue_only) {
-        if (q != hipErrorNotReady) { std::printf("FAIL %s: synchronised - the gate on S had ended when the call returned (t_enqueue %.3f ms, G %.1f ms)\n", what, t_enqueue * 1e3, G * 1e3); ++failures; }
-        else if (t_enqueue > G / 4) { std::printf("FAIL %s: inconclusive - t_enqueue %.3f ms > G / 4, G %.1f ms\n", what, t_enqueue * 1e3, G * 1e3); ++failures; }
-        else if (t_enqueue > slowest) { slowest = t_enqueue; slowest_what = what; }
-    } else if (q != hipSuccess) {
-        std::printf("FAIL %s: documented to synchronise `stream`, but S had not run when it returned\n", what);
-        ++failures;
-    }
-    (void)hipGetLastError();
-    HIP(hipStreamSynchronize(hs));
-    HIP(hipDeviceSynchronize());
-    HIP(hipEventDestroy(E));
-    if (!ins.empty() && download(outs.empty() ? std::vector<Out>{{ins[0].dst, ins[0].bytes}} : outs) == warm) {
-        std::printf("FAIL %s: the result equals the warm-up's on zero inputs: the case cannot see a launch that ran too early\n", what);
-        ++failures;
-    }
-    ++gated_calls;
-}
-
-static std::vector<uint64_t> words(const PolyBuffer& b) {
-    std::vector<uint64_t> h(b.words());
-    b.copy_to_host(h.data());
-    return h;
-}
-static Late late(PolyBuffer& dst, const PolyBuffer& zero, const PolyBuffer& real) { return Late{dst.data(), zero.data(), real.data(), dst.words() * 8}; }
-static Out out_of(PolyBuffer& b) { return Out{b.data(), b.words() * 8}; }
-
-static std::vector<uint64_t> affine(const std::vector<uint64_t>& W, const uint64_t* b, size_t rows, size_t cols, const uint64_t* x) {
-    std::vector<uint64_t> y(rows);
-    for (size_t r = 0; r < rows; ++r) {
-        unsigned __int128 acc = b ? b[r] : 0;
-        for (size_t c = 0; c < cols; ++c) acc += (unsigned __int128)W[r * cols + c] * x[c];
-        y[r] = (uint64_t)(acc % T_MOD);
-    }
-    return y;
-}
-
-// the chain primes of FheParams::n8192 seen at ring degree 2^log2n; the last one is returned as the special prime
-static FheParams ring(unsigned log2n, size_t data_limbs, uint64_t& special, uint64_t& special_psi) {
-    FheParams p = FheParams::n8192(data_limbs + 1);
-    const size_t n = (size_t)1 << log2n;
-    auto pw = [](uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; for (b %= q; e; e >>= 1) { if (e & 1) r = (uint64_t)((unsigned __int128)r * b % q); b = (uint64_t)((unsigned __int128)b * b % q); } return r; };
-    for (size_t l = 0; l < p.moduli.size(); ++l) p.psi[l] = pw(p.psi[l], 8192 / n, p.moduli[l]);
-    special = p.moduli.back(); special_psi = p.psi.back();
-    p.log2_n = log2n; p.moduli.pop_back(); p.psi.pop_back();
-    return p;
-}
+static Lcg rnd{2024};
+static uint64_t small8() { return rnd.small8(); }
 
 // everything at N = 1024 on five data limbs + a special prime (the small ring packed_rect(10) of test_fhe_api.cpp uses)
 struct Rig {
@@ -140,8 +34,9 @@ struct Rig {
     BatchEncoder be;
     HybridKeySwitcher hks;
     size_t n;
-    Rig() : p(ring(10, 5, special, special_psi)), ctx(p, 0), ev(ctx), kg(ctx, TestSeed{81}), enc(ctx, kg.secret_key(), TestSeed{82}), dec(ctx, kg.secret_key()),
-            be(ctx, T_MOD), hks(ctx, kg.secret_key(), special, special_psi, TestSeed{83}), n(p.n()) {}
+    Gate gate;   // the non-blocking stream S, the gate G and the tally of the gated calls
+    explicit Rig(double G) : p(ring(10, 5, special, special_psi)), ctx(p, 0), ev(ctx), kg(ctx, TestSeed{81}), enc(ctx, kg.secret_key(), TestSeed{82}), dec(ctx, kg.secret_key()),
+            be(ctx, T_MOD), hks(ctx, kg.secret_key(), special, special_psi, TestSeed{83}), n(p.n()), gate(G) {}
     // C ciphertexts of the given slot vectors, and C encryptions of zero
     void encrypt_slots(const std::vector<uint64_t>& slots, Ciphertext& real, Ciphertext& zero) {
         const size_t C = real.batch();
@@ -179,7 +74,7 @@ static void packed_linear(Rig& r) {
         r.encrypt_slots(slots, real, zero);
         char what[96];
         std::snprintf(what, sizeof what, "PackedLinear::apply %zu x %zu, %zu per ciphertext%s", out, in, tpc, sh[3] ? ", biased" : "");
-        gated(what, {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { lin.apply(cx, cy, s); });
+        r.gate.gated(what, {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { lin.apply(cx, cy, s); });
         const std::vector<uint64_t> got = r.decrypt_slots(cy);
         std::vector<uint64_t> tok(outs * n), y0(out), y1(out);
         size_t bad = 0;
@@ -187,8 +82,8 @@ static void packed_linear(Rig& r) {
             for (size_t o = 0; o < outs; ++o) std::memcpy(&tok[o * n], &got[(o * C + c) * n], n * 8);
             if (tpc == 1) lin.unpack_output(tok.data(), y0.data());
             else lin.unpack_output_rows(tok.data(), y0.data(), y1.data());
-            bad += y0 != affine(W, sh[3] ? bias.data() : nullptr, out, in, &x[tpc * c * in]);
-            if (tpc == 2) bad += y1 != affine(W, sh[3] ? bias.data() : nullptr, out, in, &x[(2 * c + 1) * in]);
+            bad += y0 != affine(W, sh[3] ? bias.data() : nullptr, out, in, &x[tpc * c * in], T_MOD);
+            if (tpc == 2) bad += y1 != affine(W, sh[3] ? bias.data() : nullptr, out, in, &x[(2 * c + 1) * in], T_MOD);
         }
         if (bad) std::printf("  %s: %zu wrong tokens\n", what, bad);
         CHECK(bad == 0);
@@ -204,7 +99,7 @@ static void packed_select(Rig& r) {
         for (auto& v : slots) v = 1 + rnd(T_MOD - 1);
         Ciphertext cx(r.ctx, 2, C), real(r.ctx, 2, C), zero(r.ctx, 2, C), cy(r.ctx, 2, C);
         r.encrypt_slots(slots, real, zero);
-        gated(tpc == 1 ? "PackedSelect::apply" : "PackedSelect::apply, two tokens per ciphertext", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { sel.apply(cx, cy, s); });
+        r.gate.gated(tpc == 1 ? "PackedSelect::apply" : "PackedSelect::apply, two tokens per ciphertext", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { sel.apply(cx, cy, s); });
         const std::vector<uint64_t> got = r.decrypt_slots(cy);
         size_t bad = 0;
         for (size_t c = 0; c < C; ++c)
@@ -229,15 +124,15 @@ static void block(Rig& r) {
     for (size_t tk = 0; tk < T; ++tk) blk.pack_input(&x[tk * d], &slots[tk * n]);
     Ciphertext cx(r.ctx, 2, T), real(r.ctx, 2, T), zero(r.ctx, 2, T), cy(r.ctx, 2, T);
     r.encrypt_slots(slots, real, zero);
-    gated("PackedTransformerBlock::apply", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { blk.apply(cx, cy, s); });
+    r.gate.gated("PackedTransformerBlock::apply", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { blk.apply(cx, cy, s); });
     const std::vector<uint64_t> got = r.decrypt_slots(cy);
     size_t bad = 0;
     for (size_t tk = 0; tk < T; ++tk) {
         const uint64_t* xt = &x[tk * d];
-        const std::vector<uint64_t> qkv = affine(Wqkv, bqkv.data(), 3 * d, d, xt), o = affine(Wo, bo.data(), d, d, &qkv[2 * d]);
+        const std::vector<uint64_t> qkv = affine(Wqkv, bqkv.data(), 3 * d, d, xt, T_MOD), o = affine(Wo, bo.data(), d, d, &qkv[2 * d], T_MOD);
         std::vector<uint64_t> h1(d), h2(d);
         for (size_t i = 0; i < d; ++i) h1[i] = (xt[i] + o[i]) % T_MOD;
-        const std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, h1.data()), dn = affine(Wd, bd.data(), d, h, u.data());
+        const std::vector<uint64_t> u = affine(Wu, bu.data(), h, d, h1.data(), T_MOD), dn = affine(Wd, bd.data(), d, h, u.data(), T_MOD);
         for (size_t i = 0; i < d; ++i) h2[i] = (h1[i] + dn[i]) % T_MOD;
         for (size_t s = 0; s < n; ++s) {
             const size_t c = (s % row) % pd;
@@ -266,7 +161,7 @@ static void exact_ops(Rig& r) {
         Ciphertext a(ctx2, 2, B), real(ctx2, 2, B), zero(ctx2, 2, B), sq(ctx2, 3, B);
         enc2.encrypt_exact(cx.data(), T_MOD, real);
         enc2.encrypt_exact(zeros.data(), T_MOD, zero);
-        gated("ExactMultiplier::multiply", {late(a, zero, real)}, {out_of(sq)}, [&](Stream* s) { mul.multiply(a, a, sq, s); });
+        r.gate.gated("ExactMultiplier::multiply", {late(a, zero, real)}, {out_of(sq)}, [&](Stream* s) { mul.multiply(a, a, sq, s); });
         dec2.decrypt_exact(sq, T_MOD, dd.data());
         size_t bad = 0;
         for (size_t i = 0; i < B; ++i) {
@@ -285,7 +180,7 @@ static void exact_ops(Rig& r) {
         r.kg.create_public_key(pk);
         Rerandomizer rr(r.ctx, pk, TestSeed{92});
         const unsigned flood = rr.max_flood_bits(T_MOD);
-        gated("Rerandomizer::rerandomize", {late(ct, zero, real)}, {}, [&](Stream* s) { rr.rerandomize(ct, T_MOD, flood, s); });
+        r.gate.gated("Rerandomizer::rerandomize", {late(ct, zero, real)}, {}, [&](Stream* s) { rr.rerandomize(ct, T_MOD, flood, s); });
         r.dec.decrypt_exact(ct, T_MOD, dd.data());
         size_t bad = 0;
         for (size_t i = 0; i < B * n; ++i) bad += dd[i] != (uint64_t)m[i];
@@ -296,7 +191,7 @@ static void exact_ops(Rig& r) {
     {
         const auto bits = CompactCiphertext::recommended_bits(r.p.log2_n, T_MOD);
         CompactCiphertext cc(r.ctx, B, bits.first, bits.second);
-        gated("Evaluator::compact", {late(ct, zero, real)}, {Out{cc.data(), cc.bytes()}}, [&](Stream* s) { r.ev.compact(ct, cc, s); });
+        r.gate.gated("Evaluator::compact", {late(ct, zero, real)}, {Out{cc.data(), cc.bytes()}}, [&](Stream* s) { r.ev.compact(ct, cc, s); });
         r.dec.decrypt_exact(cc, T_MOD, dd.data());
         size_t bad = 0;
         for (size_t i = 0; i < B * n; ++i) bad += dd[i] != (uint64_t)m[i];
@@ -311,7 +206,7 @@ static void exact_ops(Rig& r) {
         HIP(hipMemcpy(d_zero, z.data(), z.size() * 4, hipMemcpyHostToDevice));
         for (bool to_ntt : {false, true}) {
             Plaintext out(r.ctx, B), ref(r.ctx, B);
-            gated(to_ntt ? "BatchEncoder::encode_device (device pointer, transformed)" : "BatchEncoder::encode_device (device pointer)",
+            r.gate.gated(to_ntt ? "BatchEncoder::encode_device (device pointer, transformed)" : "BatchEncoder::encode_device (device pointer)",
                   {Late{d_slots, d_zero, d_real, slots.size() * 4}}, {out_of(out)}, [&](Stream* s) { r.be.encode_device(d_slots, B, out, to_ntt, s); });
             r.be.encode_device(slots.data(), B, ref, to_ntt);                 // from the host pointer, on the null stream: staged and synchronised
             r.ctx.synchronize();
@@ -342,7 +237,7 @@ static void evaluator_methods(Rig& r) {
         {"Evaluator::dyadic_multiply", [&](PolyBuffer& o, Stream* s) { r.ev.dyadic_multiply(a, b, o, s); }},
     };
     for (auto& op : ops) {
-        gated(op.name, ab, {out_of(o2)}, [&](Stream* s) { op.call(o2, s); });
+        r.gate.gated(op.name, ab, {out_of(o2)}, [&](Stream* s) { op.call(o2, s); });
         load_real();
         op.call(ref2, nullptr);
         r.ctx.synchronize();
@@ -353,7 +248,7 @@ static void evaluator_methods(Rig& r) {
         fill(racc, false);
         std::vector<Late> in3 = ab;
         in3.insert(in3.begin(), late(acc, z, racc));
-        gated("Evaluator::dyadic_multiply_add", in3, {}, [&](Stream* s) { r.ev.dyadic_multiply_add(a, b, acc, s); });
+        r.gate.gated("Evaluator::dyadic_multiply_add", in3, {}, [&](Stream* s) { r.ev.dyadic_multiply_add(a, b, acc, s); });
         load_real();
         HIP(hipMemcpy(ref2.data(), racc.data(), ref2.words() * 8, hipMemcpyDeviceToDevice));
         r.ev.dyadic_multiply_add(a, b, ref2);
@@ -361,7 +256,7 @@ static void evaluator_methods(Rig& r) {
         CHECK(words(acc) == words(ref2));
     }
     for (bool fwd : {true, false}) {   // in place; the domain flag is set before every call
-        gated(fwd ? "Evaluator::transform_to_ntt_inplace" : "Evaluator::transform_from_ntt_inplace", {late(a, z, ra)}, {},
+        r.gate.gated(fwd ? "Evaluator::transform_to_ntt_inplace" : "Evaluator::transform_from_ntt_inplace", {late(a, z, ra)}, {},
               [&](Stream* s) { a.set_ntt(!fwd); if (fwd) r.ev.transform_to_ntt_inplace(a, s); else r.ev.transform_from_ntt_inplace(a, s); });
         HIP(hipMemcpy(ref2.data(), ra.data(), ref2.words() * 8, hipMemcpyDeviceToDevice));
         ref2.set_ntt(!fwd);
@@ -370,7 +265,7 @@ static void evaluator_methods(Rig& r) {
         CHECK(words(a) == words(ref2));
         a.set_ntt(false); ref2.set_ntt(false);
     }
-    gated("Evaluator::multiply", ab, {out_of(o3)}, [&](Stream* s) { r.ev.multiply(a, b, o3, s); });
+    r.gate.gated("Evaluator::multiply", ab, {out_of(o3)}, [&](Stream* s) { r.ev.multiply(a, b, o3, s); });
     load_real();
     r.ev.multiply(a, b, ref3);
     r.ctx.synchronize();
@@ -380,7 +275,7 @@ static void evaluator_methods(Rig& r) {
         r.kg.create_relin_keys(rk);
         Ciphertext in3(r.ctx, 3, B), z3(r.ctx, 3, B);
         fill(z3, true);
-        gated("Evaluator::relinearize", {late(in3, z3, ref3)}, {out_of(o2)}, [&](Stream* s) { r.ev.relinearize(in3, rk, o2, s); });
+        r.gate.gated("Evaluator::relinearize", {late(in3, z3, ref3)}, {out_of(o2)}, [&](Stream* s) { r.ev.relinearize(in3, rk, o2, s); });
         r.ev.relinearize(ref3, rk, ref2);
         r.ctx.synchronize();
         CHECK(words(o2) == words(ref2));
@@ -388,7 +283,7 @@ static void evaluator_methods(Rig& r) {
     {
         Context next(r.p.drop_last_limb(), 0);
         Ciphertext lo(next, 2, B), lo_ref(next, 2, B);
-        gated("Evaluator::rescale", {late(a, z, ra)}, {out_of(lo)}, [&](Stream* s) { r.ev.rescale(a, lo, s); });
+        r.gate.gated("Evaluator::rescale", {late(a, z, ra)}, {out_of(lo)}, [&](Stream* s) { r.ev.rescale(a, lo, s); });
         r.ev.rescale(ra, lo_ref);
         r.ctx.synchronize();
         CHECK(words(lo) == words(lo_ref));
@@ -398,12 +293,12 @@ static void evaluator_methods(Rig& r) {
         Plaintext pt(r.ctx, 1, true), W(r.ctx, rows * cols, true);
         fill(pt, false); fill(W, false);
         a.set_ntt(true); ra.set_ntt(true); o2.set_ntt(true); ref2.set_ntt(true);
-        gated("Evaluator::multiply_plain", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.multiply_plain(a, pt, o2, s); });
+        r.gate.gated("Evaluator::multiply_plain", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.multiply_plain(a, pt, o2, s); });
         r.ev.multiply_plain(ra, pt, ref2);
         r.ctx.synchronize();
         CHECK(words(o2) == words(ref2));
         Ciphertext y(r.ctx, 2, rows, true), yref(r.ctx, 2, rows, true);
-        gated("Evaluator::matvec_plain", {late(a, z, ra)}, {out_of(y)}, [&](Stream* s) { r.ev.matvec_plain(W, a, y, s); });
+        r.gate.gated("Evaluator::matvec_plain", {late(a, z, ra)}, {out_of(y)}, [&](Stream* s) { r.ev.matvec_plain(W, a, y, s); });
         r.ev.matvec_plain(W, ra, yref);
         r.ctx.synchronize();
         CHECK(words(y) == words(yref));
@@ -411,19 +306,19 @@ static void evaluator_methods(Rig& r) {
         std::vector<int64_t> w(rows * cols);
         for (auto& v : w) v = (int64_t)rnd(1 << 20) - (1 << 19);
         Ws.set(w.data());
-        gated("Evaluator::matvec_scalar", {late(a, z, ra)}, {out_of(y)}, [&](Stream* s) { r.ev.matvec_scalar(Ws, a, y, s); });
+        r.gate.gated("Evaluator::matvec_scalar", {late(a, z, ra)}, {out_of(y)}, [&](Stream* s) { r.ev.matvec_scalar(Ws, a, y, s); });
         r.ev.matvec_scalar(Ws, ra, yref);
         r.ctx.synchronize();
         CHECK(words(y) == words(yref));
         Plaintext W1(r.ctx, rows, true);                                       // cols = 1, n_rhs = 3: x is [1][3]
         fill(W1, false);
         Ciphertext ym(r.ctx, 2, rows * B, true), ymref(r.ctx, 2, rows * B, true);
-        gated("Evaluator::matvec_plain_multi", {late(a, z, ra)}, {out_of(ym)}, [&](Stream* s) { r.ev.matvec_plain_multi(W1, a, ym, B, s); });
+        r.gate.gated("Evaluator::matvec_plain_multi", {late(a, z, ra)}, {out_of(ym)}, [&](Stream* s) { r.ev.matvec_plain_multi(W1, a, ym, B, s); });
         r.ev.matvec_plain_multi(W1, ra, ymref, B);
         r.ctx.synchronize();
         CHECK(words(ym) == words(ymref));
         Ciphertext one(r.ctx, 2, 1, true), one_ref(r.ctx, 2, 1, true);
-        gated("Evaluator::reduce_sum", {late(a, z, ra)}, {out_of(one)}, [&](Stream* s) { r.ev.reduce_sum(a, one, s); });
+        r.gate.gated("Evaluator::reduce_sum", {late(a, z, ra)}, {out_of(one)}, [&](Stream* s) { r.ev.reduce_sum(a, one, s); });
         r.ev.reduce_sum(ra, one_ref);
         r.ctx.synchronize();
         CHECK(words(one) == words(one_ref));
@@ -434,11 +329,11 @@ static void evaluator_methods(Rig& r) {
         std::vector<int64_t> c(n);
         for (auto& v : c) v = (int64_t)rnd(T_MOD);
         pb.set_coefficients(c.data());
-        gated("Evaluator::add_plain_exact", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.add_plain_exact(a, pb, o2, s); });
+        r.gate.gated("Evaluator::add_plain_exact", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.add_plain_exact(a, pb, o2, s); });
         r.ev.add_plain_exact(ra, pb, ref2);
         r.ctx.synchronize();
         CHECK(words(o2) == words(ref2));
-        gated("Evaluator::sub_plain_exact", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.sub_plain_exact(a, pb, o2, s); });
+        r.gate.gated("Evaluator::sub_plain_exact", {late(a, z, ra)}, {out_of(o2)}, [&](Stream* s) { r.ev.sub_plain_exact(a, pb, o2, s); });
         r.ev.sub_plain_exact(ra, pb, ref2);
         r.ctx.synchronize();
         CHECK(words(o2) == words(ref2));
@@ -463,17 +358,17 @@ static void synchronising_methods(Rig& r) {
     };
     GaloisKeys gk(r.ctx, g);
     r.kg.create_galois_keys(gk);
-    gated("Evaluator::apply_galois", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.ev.apply_galois(cx, gk, cy, s); }, /*enqueue_only=*/false);
+    r.gate.gated("Evaluator::apply_galois", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.ev.apply_galois(cx, gk, cy, s); }, /*enqueue_only=*/false);
     CHECK(rotated_ok(cy));
     r.hks.add_galois_element(g);
-    gated("HybridKeySwitcher::apply_galois", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois(cx, g, cy, s); }, false);
+    r.gate.gated("HybridKeySwitcher::apply_galois", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois(cx, g, cy, s); }, false);
     CHECK(rotated_ok(cy));
     // the rotations that only enqueue (their first call packs and caches the keys, which synchronises: that is the warm-up)
-    gated("HybridKeySwitcher::apply_galois_many", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_many(cx, std::vector<uint32_t>(B, g), cy, 0, s); });
+    r.gate.gated("HybridKeySwitcher::apply_galois_many", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_many(cx, std::vector<uint32_t>(B, g), cy, 0, s); });
     CHECK(rotated_ok(cy));
-    gated("HybridKeySwitcher::apply_galois_grouped", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_grouped(cx, 0, std::vector<uint32_t>(1, g), B, cy, 0, s); });
+    r.gate.gated("HybridKeySwitcher::apply_galois_grouped", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_grouped(cx, 0, std::vector<uint32_t>(1, g), B, cy, 0, s); });
     CHECK(rotated_ok(cy));
-    gated("HybridKeySwitcher::apply_galois_hoisted", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_hoisted(cx, 0, B, std::vector<uint32_t>(1, g), cy, 0, s); });
+    r.gate.gated("HybridKeySwitcher::apply_galois_hoisted", {late(cx, zero, real)}, {out_of(cy)}, [&](Stream* s) { r.hks.apply_galois_hoisted(cx, 0, B, std::vector<uint32_t>(1, g), cy, 0, s); });
     CHECK(rotated_ok(cy));
     {   // relinearisation of a product: decrypts to the slot-wise square
         FheParams p2 = r.p;
@@ -493,7 +388,7 @@ static void synchronising_methods(Rig& r) {
         mul.multiply(a, a, sq);
         mul.multiply(z2, z2, sq0);
         ctx2.synchronize();
-        gated("HybridKeySwitcher::relinearize", {late(in3, sq0, sq)}, {out_of(out)}, [&](Stream* s) { hks2.relinearize(in3, out, s); }, false);
+        r.gate.gated("HybridKeySwitcher::relinearize", {late(in3, sq0, sq)}, {out_of(out)}, [&](Stream* s) { hks2.relinearize(in3, out, s); }, false);
         std::vector<uint64_t> dd(B * n), got(n);
         dec2.decrypt_exact(out, T_MOD, dd.data());
         size_t bad = 0;
@@ -506,11 +401,11 @@ static void synchronising_methods(Rig& r) {
 }
 
 int main(int argc, char** argv) {
-    if (argc > 1) G = std::atof(argv[1]);
+    const double G = argc > 1 ? std::atof(argv[1]) : 0.040;
     if (!(G >= 0.010 && G <= 0.1)) { std::printf("G = %g s is outside [0.010, 0.1]\n", G); return 2; }
     try {
-        Rig r;
-        if (stream_gate_stream_create(&S) != 0 || !S) { std::printf("no non-blocking stream\n"); return 2; }
+        Rig r(G);
+        if (!r.gate.ok()) { std::printf("no non-blocking stream\n"); return 2; }
         evaluator_methods(r);
         packed_linear(r);
         packed_select(r);
@@ -518,16 +413,10 @@ int main(int argc, char** argv) {
         exact_ops(r);
         synchronising_methods(r);
         r.ctx.synchronize();
-        stream_gate_stream_destroy(S);
+        std::printf("%d gated facade calls; G = %.1f ms; slowest t_enqueue %.3f ms (%s)\n", r.gate.gated_calls, G * 1e3, r.gate.slowest * 1e3, r.gate.slowest_what.c_str());
     } catch (const std::exception& e) {
         std::printf("exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%d gated facade calls; G = %.1f ms; slowest t_enqueue %.3f ms (%s)\n", gated_calls, G * 1e3, slowest * 1e3, slowest_what.c_str());
-    if (failures) {
-        std::printf("%d check(s) failed\n", failures);
-        return 1;
-    }
-    std::printf("stream C++ facade OK\n");
-    return 0;
+    return finish("stream C++ facade OK");
 }

@@ -3,18 +3,16 @@
 The kernel must give the host twin's bytes (tests/test_compact_cpu.py holds the host twin to the definition) on every ring degree, limb count and
 limb class, for odd batches, without writing past the records or touching the input.  Through the C++ facade (tests/cpp/test_compact_api.cpp):
 a fresh ciphertext, a biased 768 x 768 PackedLinear at N = 8192 and an activated FFN at N = 16384 decrypt exactly from compact form."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi
 from deeppowers_amd.params import FheParams, ntt_primes
 from test_compact_cpu import WIDTHS, plant_edges, random_words, twin
 from test_seeded_cpu import mixed_params
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0xA5
 
 pytestmark = pytest.mark.gpu
@@ -113,11 +111,8 @@ def test_device_entry_rejects_bad_arguments():
         ctx.close()
 
 
-def test_cpp_compact_facade(tmp_path):
-    exe = str(tmp_path / "test_compact_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_compact_api.cpp"), "-o", exe,
-                           "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_compact_facade():
+    exe = cpp_build.build_program("test_compact_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=1500)
     print(out.stdout)
     assert out.returncode == 0 and "compact C++ facade OK" in out.stdout, out.stdout + out.stderr

@@ -8,18 +8,16 @@ tests/stream_gate.py's gate on a non-blocking stream in tests/test_gpu_stream_co
 process's gate.  Through the C++ facade (tests/cpp/test_complex_encode_api.cpp): ComplexEncoder::encode_device equals encode + lift + upload
 word for word, and a device-encoded operand multiplies, rotates and rescales correctly under encryption."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi
 from deeppowers_amd.params import FheParams, min_primitive_2n_root, ntt_primes
 from complex_encode_ref import special_vectors, twin
 from test_plain_add_cpu import PARAMS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -154,12 +152,8 @@ def test_device_entry_rejects_bad_arguments():
         ctx.close()
 
 
-def test_cpp_complex_encode_facade(tmp_path):
-    exe = str(tmp_path / "test_complex_encode_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "test_complex_encode_api.cpp"), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib",
-                           "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_complex_encode_facade():
+    exe = cpp_build.build_program("test_complex_encode_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     print(out.stdout)
     assert out.returncode == 0 and "complex encode C++ facade OK" in out.stdout, out.stdout + out.stderr

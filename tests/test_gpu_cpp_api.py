@@ -4,18 +4,13 @@ import subprocess
 
 import pytest
 
+import cpp_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_cpp_test():
-    exe = os.path.join(ROOT, "tests", "cpp", "test_fhe_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"])
-    subprocess.check_call([
-        "g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_fhe_api.cpp"),
-        "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L" + os.path.join(ROOT, "oracle"), "-loracle",
-        "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", f"-Wl,-rpath,{os.path.join(ROOT, 'oracle')}", "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return cpp_build.build_program("test_fhe_api", oracle=True)
 
 
 def test_cpp_facade_compiles_and_links():
@@ -30,10 +25,8 @@ def test_cpp_prime_chain_is_the_python_generators(tmp_path):
     src = tmp_path / "chain.cpp"
     src.write_text('#include <cstdio>\n#include <deeppowers/fhe.hpp>\nint main() { auto p = deeppowers::fhe::FheParams::n8192(20);\n'
                    'for (size_t i = 0; i < p.n_limbs(); ++i) std::printf("%llu %llu\\n", (unsigned long long)p.moduli[i], (unsigned long long)p.psi[i]); }\n')
-    lib = os.path.join(ROOT, "deeppowers_amd")
     exe = str(tmp_path / "chain")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    subprocess.check_call(cpp_build.command(src, exe))
     got = [tuple(int(v) for v in l.split()) for l in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()]
     want = ntt_primes(13, 20)
     assert got == list(zip(want.moduli, want.psi))

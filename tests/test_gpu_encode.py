@@ -6,19 +6,17 @@ diagonals of a 768 -> 3072 layer at N = 8192 over six limbs) every word is compa
 output alone.  Through the C++ facade (tests/cpp/test_encode_api.cpp): BatchEncoder::encode_device equals encode + lift + upload word for word
 on the data and the extended context, and device-encoded operands multiply and add correctly under encryption."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi
 from deeppowers_amd.params import FheParams, min_primitive_2n_root, ntt_primes
 from encode_ref import extreme_slot_vectors, largest_t, slot_vectors, t_values, twin, zeta_of
 from test_plain_add_cpu import PARAMS, big_prime_t
 from test_seeded_cpu import SENTINEL
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T_BIG = big_prime_t()
 
 pytestmark = pytest.mark.gpu
@@ -155,12 +153,8 @@ def test_device_entry_rejects_bad_arguments():
         ctx.close()
 
 
-def test_cpp_encode_facade(tmp_path):
-    exe = str(tmp_path / "test_encode_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "test_encode_api.cpp"), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib",
-                           "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_encode_facade():
+    exe = cpp_build.build_program("test_encode_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=1500)
     print(out.stdout)
     assert out.returncode == 0 and "encode C++ facade OK" in out.stdout, out.stdout + out.stderr

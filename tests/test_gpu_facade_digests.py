@@ -16,6 +16,8 @@ import tempfile
 
 import pytest
 
+import cpp_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -29,11 +31,8 @@ def facade_digests(workdir):
     """build tests/cpp/facade_digests.cpp against the tree's libraries, run it, hash what it wrote: name -> SHA-256"""
     from deeppowers_amd.params import ntt_primes
     p = ntt_primes(LOG2_N, LIMBS)
-    exe, outdir, lib = os.path.join(workdir, "facade_digests"), os.path.join(workdir, "out"), os.path.join(ROOT, "deeppowers_amd")
+    exe, outdir = cpp_build.build_program("facade_digests"), os.path.join(workdir, "out")
     os.makedirs(outdir)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "facade_digests.cpp"), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib",
-                           "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
     args = [exe, outdir, str(LOG2_N)] + [str(v) for q, psi in zip(p.moduli, p.psi) for v in (q, psi)]
     out = subprocess.run(args, capture_output=True, text=True, timeout=120)
     print(out.stdout)

@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+import cpp_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -23,10 +25,8 @@ def test_cpp_n32768_chain_is_the_python_generators(tmp_path):
                    '    for (size_t i = 0; i < p.n_limbs(); ++i) std::printf(" %llu %llu", (unsigned long long)p.moduli[i], (unsigned long long)p.psi[i]);\n'
                    '    std::printf("\\n"); }\n'
                    '  for (size_t k : {size_t(0), size_t(15)}) { try { FheParams::n32768(k); std::printf("accepted\\n"); } catch (const Exception&) { std::printf("rejected\\n"); } }\n}\n')
-    lib = os.path.join(ROOT, "deeppowers_amd")
     exe = str(tmp_path / "chain15")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    subprocess.check_call(cpp_build.command(src, exe))
     lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
     chain = ntt_primes(15, 14)
     assert len(lines) == 16 and lines[14:] == ["rejected", "rejected"]

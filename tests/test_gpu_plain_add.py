@@ -4,18 +4,16 @@ The kernel must give the host twin's words (tests/test_plain_add_cpu.py holds th
 class, in place and out of place, with components >= 1 untouched or copied.  Through the C++ facade (tests/cpp/test_affine_api.cpp): decryption
 of ciphertexts plus plaintexts, 3-component products plus plaintexts, biased PackedLinear layers, the biased transformer block and the activated
 FFN with biases."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi
 from deeppowers_amd.params import FheParams, ntt_primes
 from test_plain_add_cpu import PARAMS, T_PRIME_BIG, T_VALUES, random_ct, random_plain, twin
 from test_seeded_cpu import SENTINEL
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -156,11 +154,8 @@ def test_device_entry_rejects_bad_arguments():
         ctx.close()
 
 
-def test_cpp_affine_facade(tmp_path):
-    exe = str(tmp_path / "test_affine_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_affine_api.cpp"), "-o", exe,
-                           "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_affine_facade():
+    exe = cpp_build.build_program("test_affine_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=1500)
     print(out.stdout)
     assert out.returncode == 0 and "affine C++ facade OK" in out.stdout, out.stdout + out.stderr

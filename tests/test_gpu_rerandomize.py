@@ -4,18 +4,16 @@ The sampler must give the host twin's words (tests/test_rerandomize_cpu.py holds
 and limb class, for odd batches, with and without DPFHE_NOISE_ADD, without touching another component or a word past the buffer.
 dpfhe_rerandomize must equal its definition composed from the host twin and the CPU oracle's transforms and products.  Through the C++ facade
 (tests/cpp/test_rerandomize_api.cpp): message kept, c1 replaced, the derived budget, a biased 768 x 768 PackedLinear re-randomised and compacted."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi, wire
 from deeppowers_amd.params import FheParams, ntt_primes
 from test_rerandomize_cpu import CBD21, FLOOD, FLOOD_BITS, TERNARY
 from test_seeded_cpu import SEED, mixed_params
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0x5A5A5A5A5A5A5A5A
 TAIL = 512
 
@@ -238,11 +236,8 @@ def test_device_entries_reject_bad_arguments():
 
 
 # ---- 8: the C++ facade -------------------------------------------------------------------------------------------------------------
-def test_cpp_rerandomize_facade(tmp_path):
-    exe = str(tmp_path / "test_rerandomize_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_rerandomize_api.cpp"), "-o",
-                           exe, "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_rerandomize_facade():
+    exe = cpp_build.build_program("test_rerandomize_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     print(out.stdout)
     assert out.returncode == 0 and "rerandomize C++ facade OK" in out.stdout, out.stdout + out.stderr

@@ -3,19 +3,17 @@
 The kernel must give the host twin's words (tests/test_seeded_cpu.py holds the host twin to a restatement of the definition) on every
 ring degree and limb class, write nothing but its component, and split into item ranges with first_item.  Through the C++ facade
 (tests/cpp/test_seeded_api.cpp): seeded encryption, keys and streams.  Over RPC: seeded operands and keys give the plain request's words."""
-import os
 import subprocess
 
 import grpc
 import numpy as np
 import pytest
 
+import cpp_build
 from deeppowers_amd import _cabi, rpc, wire
 from deeppowers_amd.params import FheParams, ntt_primes
 from test_rlwe_semantics import negacyclic_int, phase, small_params
 from test_seeded_cpu import SEED, SENTINEL, mixed_params, pinned60, primes31
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -109,11 +107,8 @@ def test_device_entry_rejects_bad_arguments():
         ctx.close()
 
 
-def test_cpp_seeded_facade(tmp_path):
-    exe = str(tmp_path / "test_seeded_api")
-    lib = os.path.join(ROOT, "deeppowers_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "test_seeded_api.cpp"), "-o", exe,
-                           "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+def test_cpp_seeded_facade():
+    exe = cpp_build.build_program("test_seeded_api")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "seeded C++ facade OK" in out.stdout, out.stdout + out.stderr
 

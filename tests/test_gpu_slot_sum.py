@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import approx_poly_model as apm
+import cpp_build
 import stream_gate as sg
 
 CASES = [(2, 1), (8, 1), (2048, 1), (8, 4)]
@@ -19,7 +19,7 @@ MAGIC = 0x534C4F5453554D31
 
 
 def build_api_test():
-    return apm._build("test_slot_sum_api", extra=(sg.build_library(),))
+    return cpp_build.build_program("test_slot_sum_api", gate=True)
 
 
 def test_program_links_and_its_cases_have_sums_of_order_one_and_a_tight_bound():

@@ -16,12 +16,12 @@ which the CPU tests pin to Python integers):
   dpfhe_encode_slots        flags 0, PLAIN and NTT at N = 256 and N = 32768 (two kernels that park words in d_out)
   dpfhe_rerandomize         on a `mixed` context, and at N = 16384
 The C++ facade's Stream* arguments: tests/cpp/test_stream_api.cpp, run from here."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 import stream_gate as sg
 import test_gpu_footprint as fp
 import test_gpu_large_ring_pipeline as lr
@@ -31,8 +31,6 @@ from deeppowers_amd.params import ntt_primes
 from test_seeded_cpu import SEED
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 rig = fp.rig
 
 
@@ -282,15 +280,7 @@ def test_rerandomize(rig, gated, name, log2n, flood_bits):
 
 # ---- the C++ facade's Stream* ----------------------------------------------------------------------------------------------------------------------------------
 def build_stream_api_test():
-    exe = os.path.join(ROOT, "tests", "cpp", "test_stream_api")
-    src = os.path.join(ROOT, "tests", "cpp", "test_stream_api.cpp")
-    lib, gate_dir = os.path.join(ROOT, "deeppowers_amd"), os.path.dirname(sg.build_library())
-    deps = [src, sg.LIB, os.path.join(ROOT, "include", "deeppowers", "fhe.hpp"), os.path.join(lib, "libdpfhe_api.so")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", src, "-o", exe,
-                               "-L" + lib, "-ldpfhe_api", "-ldpfhe_hip", "-L" + gate_dir, "-lstream_gate", "-L/opt/rocm/lib", "-lamdhip64",
-                               f"-Wl,-rpath,{lib}", f"-Wl,-rpath,{gate_dir}", "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return cpp_build.build_program("test_stream_api", gate=True)
 
 
 def test_cpp_facade_stream_arguments():
