@@ -43,6 +43,10 @@ SYMBOLS = {
     "dpfhe_relinearize_rescale_pass_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t], C.c_int),
     "dpfhe_lincomb_rescale": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_lincomb_rescale_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t], C.c_int),
+    "dpfhe_relinearize_lincomb_rescale_hybrid": ([C.c_void_p, _U64P, _U64P, _U64P, _U64P, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t, _U64P,
+                                                  C.c_size_t, C.c_void_p], C.c_int),
+    "dpfhe_relinearize_lincomb_rescale_pass_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p, C.c_size_t], C.c_int),
     "dpfhe_rotate_hybrid_batch": ([C.c_void_p, _U64P, _U64P, C.c_size_t, C.POINTER(C.c_uint32), _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_rotate_hybrid_hoisted": ([C.c_void_p, _U64P, _U64P, C.c_size_t, C.POINTER(C.c_uint32), _U64P, _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_rotate_hybrid_grouped": ([C.c_void_p, _U64P, _U64P, C.POINTER(C.c_uint32), C.c_size_t, C.c_size_t, _U64P, _U64P, _U64P, C.c_void_p], C.c_int),

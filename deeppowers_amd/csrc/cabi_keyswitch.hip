@@ -166,7 +166,7 @@ int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_
     if (rblocks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     if (drop_last) {   // ... and by the last data prime in the same pass
         with_ctx_arith(c, [&](auto arith) {
-            hipLaunchKernelGGL((relin_rescale_kernel<decltype(arith)>), dim3((unsigned)(batch * 2 * (Ld - 1) * (size_t)chunks)), dim3(256), 0, s, d_out2, d_work, d_in, c->lc,
+            hipLaunchKernelGGL((relin_rescale_kernel<decltype(arith)>), dim3((unsigned)relin_rescale_grid(batch, Ld, (size_t)n)), dim3(256), 0, s, d_out2, d_work, d_in, c->lc,
                                c->d_rescale, c->d_rescale2, (int)L, n, chunks);
         });
         return check_launch("hybrid rescale-twice launch");
@@ -382,5 +382,88 @@ extern "C" int dpfhe_lincomb_rescale_host(const uint64_t* moduli, uint32_t n_lim
     if (int e = host_rescale_consts(what, moduli, L - 1, rc)) return e;
     if (fold) lincomb_rescale_host<FoldArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
     else lincomb_rescale_host<ShoupArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
+    return DPFHE_SUCCESS;
+}
+
+// ---- a relinearised product + scalar linear combination + rescale in one last pass (fused_rescale.h (c)) ----------------------------------------------------
+// what the device entry and the host twin check alike: the counts, the terms' heights, and that the output overlaps no input
+static int relin_lincomb_args(const char* what, const uint64_t* out, const uint64_t* in3, const uint64_t* const* terms, const uint32_t* term_limbs, size_t n_terms,
+                              const uint64_t* w, size_t batch, size_t Ld, size_t n) {
+    if (n_terms > kRelinLincombMaxTerms) return fail(DPFHE_INVALID_ARGUMENT, what, "0 to 15 terms");
+    if (!out || !in3 || !w || (n_terms && (!terms || !term_limbs))) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    const size_t out_words = batch * 2 * (Ld - 1) * n;
+    if (overlaps(out, out_words, in3, batch * 3 * Ld * n) || overlaps(out, out_words, w, (n_terms + 2) * Ld)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    for (size_t k = 0; k < n_terms; ++k) {
+        if (!terms[k]) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+        if (term_limbs[k] < Ld) return fail(DPFHE_INVALID_ARGUMENT, what, "a term has fewer limbs than the data context");
+        if (overlaps(out, out_words, terms[k], batch * 2 * term_limbs[k] * n)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    }
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_relinearize_lincomb_rescale_hybrid(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t* d_in3, const uint64_t* d_key, uint64_t* d_work,
+                                                        const uint64_t* const* d_terms, const uint32_t* term_limbs, size_t n_terms, const uint64_t* d_w,
+                                                        size_t batch, void* stream) {
+    static const char* what = "dpfhe_relinearize_lincomb_rescale_hybrid";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (int rc = check_extended(c, what)) return rc;
+    if (c->n_limbs < 3) return fail(DPFHE_INVALID_STATE, what, "no data limb left to drop (Ld < 2)");
+    if (batch == 0) return DPFHE_SUCCESS;
+    const size_t L = c->n_limbs, Ld = L - 1, n = (size_t)1 << c->log2n;
+    if (!d_key || !d_work) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    if (int rc = relin_lincomb_args(what, d_out2, d_in3, d_terms, term_limbs, n_terms, d_w, batch, Ld, n)) return rc;
+    bool skew = misaligned(d_out2) || misaligned(d_in3) || misaligned(d_key) || misaligned(d_work) || misaligned(d_w);
+    for (size_t k = 0; k < n_terms; ++k) skew = skew || misaligned(d_terms[k]);
+    if (skew) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    {   // pass 1 writes the work buffer while it reads the input and the key; the last pass reads everything else while it writes the output
+        const size_t out_words = batch * 2 * (Ld - 1) * n, work_words = batch * 2 * L * n, key_words = Ld * 2 * L * n;
+        bool hit = overlaps(d_work, work_words, d_out2, out_words) || overlaps(d_work, work_words, d_in3, batch * 3 * Ld * n) || overlaps(d_work, work_words, d_key, key_words) ||
+                   overlaps(d_work, work_words, d_w, (n_terms + 2) * Ld) || overlaps(d_out2, out_words, d_key, key_words);
+        for (size_t k = 0; k < n_terms; ++k) hit = hit || overlaps(d_work, work_words, d_terms[k], batch * 2 * term_limbs[k] * n);
+        if (hit) return fail(DPFHE_INVALID_ARGUMENT, what, "the output and the work buffer must not overlap each other or any input");
+    }
+    if (!key_products_fit(c, batch, 0, 1) || relin_rescale_grid(batch, Ld, n) > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    DPFHE_ON_DEVICE(c, what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = key_products_hybrid(c, what, 3, d_work, d_in3, d_key, batch, s, 0, 1)) return rc;
+    LincombTerms terms{};
+    for (size_t k = 0; k < n_terms; ++k) { terms.z[k] = d_terms[k]; terms.limbs[k] = term_limbs[k]; }
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((relin_lincomb_rescale_kernel<decltype(arith)>), dim3((unsigned)relin_rescale_grid(batch, Ld, n)), dim3(256), 0, s, d_out2, d_work, d_in3, terms,
+                           d_w, c->lc, c->d_rescale, c->d_rescale2, (int)L, (int)n, chunks_of(n), (int)n_terms);
+    });
+    return check_launch("hybrid relinearise-combine-rescale launch");
+}
+
+extern "C" int dpfhe_relinearize_lincomb_rescale_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp,
+                                                           const uint64_t* in3, const uint64_t* const* terms, const uint32_t* term_limbs, size_t n_terms,
+                                                           const uint64_t* w, size_t batch) {
+    static const char* what = "dpfhe_relinearize_lincomb_rescale_pass_host";
+    if (!moduli || !work_qp) return fail(DPFHE_INVALID_ARGUMENT, what, "null argument");
+    if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
+    if (n_limbs < 3) return fail(DPFHE_INVALID_STATE, what, "no data limb left to drop (Ld < 2)");
+    const size_t n = (size_t)1 << log2_n, L = n_limbs, Ld = L - 1;
+    if (int rc = relin_lincomb_args(what, out, in3, terms, term_limbs, n_terms, w, batch, Ld, n)) return rc;
+    if (overlaps(out, batch * 2 * (Ld - 1) * n, work_qp, batch * 2 * L * n)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
+    for (size_t p = 0; p < 2 * batch; ++p)
+        for (size_t l = 0; l < L; ++l)
+            for (size_t k = 0; k < n; ++k) {
+                bool ok = work_qp[(p * L + l) * n + k] < moduli[l];
+                if (l < Ld) {   // of a term, as of the device entry, only the first Ld limbs are read
+                    ok = ok && in3[(((p >> 1) * 3 + (p & 1)) * Ld + l) * n + k] < moduli[l];
+                    for (size_t t = 0; t < n_terms; ++t) ok = ok && terms[t][(p * term_limbs[t] + l) * n + k] < moduli[l];
+                }
+                if (!ok) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
+            }
+    for (size_t i = 0; i < (n_terms + 2) * Ld; ++i)
+        if (w[i] >= moduli[i % Ld]) return fail(DPFHE_INVALID_ARGUMENT, what, "weights must be canonical residues");
+    std::vector<LimbConst> lc;
+    std::vector<RescaleConst> rcp, rcq;
+    bool fold;
+    host_limb_consts(moduli, n_limbs, lc, fold);
+    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
+    if (int rc = host_rescale_consts(what, moduli, L - 2, rcq)) return rc;
+    if (fold) relin_lincomb_rescale_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, terms, term_limbs, n_terms, w, batch);
+    else relin_lincomb_rescale_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, terms, term_limbs, n_terms, w, batch);
     return DPFHE_SUCCESS;
 }

@@ -234,6 +234,86 @@ void HybridKeySwitcher::multiply_rescale_range(const Ciphertext& a, size_t a_fir
     out.set_ntt(false);
 }
 
+// ---- ScalarWeights ---------------------------------------------------------------------------------------------------------
+class __attribute__((visibility("hidden"))) ScalarWeights::Impl {
+public:
+    const Context* ctx = nullptr;
+    size_t K = 0;
+    uint64_t* d_w = nullptr;   // [K + 2][Ld]
+    ~Impl() { if (d_w) (void)hipFree(d_w); }
+};
+
+ScalarWeights::ScalarWeights(const Context& data_ctx, int64_t product_weight, const std::vector<int64_t>& term_weights, int64_t constant_at_output) : impl_(new Impl) {
+    const FheParams& p = data_ctx.params();
+    const size_t Ld = p.n_limbs(), K = term_weights.size();
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, "ScalarWeights: no data limb left to drop");
+    if (K > 15) throw Exception(ErrorCode::INVALID_ARGUMENT, "ScalarWeights: at most 15 terms");
+    std::vector<int64_t> rows{product_weight};
+    rows.insert(rows.end(), term_weights.begin(), term_weights.end());
+    rows.push_back(constant_at_output);
+    const int64_t lim = (int64_t)1 << 62;
+    for (int64_t v : rows)
+        if (v <= -lim || v >= lim) throw Exception(ErrorCode::INVALID_ARGUMENT, "ScalarWeights: a weight |w| reaches 2^62");
+    std::vector<uint64_t> w(rows.size() * Ld);
+    for (size_t row = 0; row < rows.size(); ++row) {
+        const int64_t v = rows[row];
+        for (size_t l = 0; l < Ld; ++l) {
+            const uint64_t q = p.moduli[l];
+            uint64_t m = (uint64_t)(v < 0 ? -v : v) % q;
+            if (row == K + 1) m = (uint64_t)((u128)m * (p.moduli.back() % q) % q);   // the constant row: constant_at_output * q_last
+            w[row * Ld + l] = (v < 0 && m) ? q - m : m;
+        }
+    }
+    impl_->ctx = &data_ctx;
+    impl_->K = K;
+    impl_->d_w = device_alloc<uint64_t>(data_ctx.device_id(), w.size());
+    hip_check(hipMemcpy(impl_->d_w, w.data(), w.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+}
+ScalarWeights::~ScalarWeights() = default;
+size_t ScalarWeights::terms() const { return impl_->K; }
+const Context& ScalarWeights::context() const { return *impl_->ctx; }
+const uint64_t* ScalarWeights::data() const { return impl_->d_w; }
+
+void HybridKeySwitcher::multiply_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, const ScalarWeights& weights,
+                                                       const std::vector<LincombTerm>& terms, Ciphertext& out, size_t out_first, Stream* s) const {
+    static const char* what = "HybridKeySwitcher::multiply_lincomb_rescale";
+    const FheParams& pe = impl_->ext->params();
+    const FheParams& pd = impl_->data_ctx->params();
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), in_words = 2 * Ld * n;
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, std::string(what) + ": no data limb left to drop");
+    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+        a_first + count > a.batch() || b_first + count > b.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": 2-component coefficient-domain ciphertexts on the data context, ranges inside them");
+    const size_t out_words = 2 * (Ld - 1) * n;
+    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + count > out.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for the range");
+    const FheParams& pw = weights.context().params();
+    if (weights.terms() != terms.size() || pw.log2_n != pd.log2_n || pw.moduli != pd.moduli || weights.context().device_id() != impl_->data_ctx->device_id())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": weights built on the data context, one per term");
+    const uint64_t* ptrs[15] = {};
+    uint32_t limbs[15] = {};
+    for (size_t k = 0; k < terms.size(); ++k) {
+        const Ciphertext* z = terms[k].ct;
+        if (!z) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": null term");
+        const FheParams& pz = z->context().params();
+        const size_t Lz = pz.n_limbs();
+        if (z->is_ntt() || z->size() != 2 || pz.log2_n != pd.log2_n || Lz < Ld || !std::equal(pd.moduli.begin(), pd.moduli.end(), pz.moduli.begin()) ||
+            z->words() != z->batch() * 2 * Lz * n || terms[k].first + count > z->batch() || z->context().device_id() != impl_->data_ctx->device_id())
+            throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": a term is 2 components, coefficient domain, on a context whose first limbs are the data context's, range inside it");
+        ptrs[k] = z->data() + terms[k].first * 2 * Lz * n;
+        limbs[k] = (uint32_t)Lz;
+    }
+    if (count == 0) return;
+    grow_scratch(impl_->scratch_product, count, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
+    grow_scratch(impl_->scratch_work, count, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, count, 0, s),
+          "dpfhe_ct_mul");
+    check(dpfhe_relinearize_lincomb_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                                   impl_->scratch_work->data(), ptrs, limbs, terms.size(), weights.data(), count, s),
+          "dpfhe_relinearize_lincomb_rescale_hybrid");
+    out.set_ntt(false);
+}
+
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
 const Context& HybridKeySwitcher::data_context() const { return *impl_->data_ctx; }
 

@@ -176,6 +176,65 @@ __global__ __launch_bounds__(256) void lincomb_rescale_kernel(u64* out, const u6
               rescale_word<Arith>(lazy_reduce<Arith>(si[1], lc), lazy_reduce<Arith>(sl[1], lcl), lc, rc)};
 }
 
+// The last pass of a relinearised product with a scalar linear combination of K <= 15 other ciphertexts and a constant, rescaled at once (fused_rescale.h (c)):
+//   out[t][c] = round((w_0 t[t][c] + sum_{k<K} w_{1+k} z_k[t][c] + [c = 0] w_{K+1}) / q_{Ld-1}),   t = (c0, c1) + round(work / P)  (never written).
+// work, in3, out, lcs, rcp, rcq as in relin_rescale_kernel; w: [K + 2][Ld]; term k: [batch][2][limbs[k]][N], limbs[k] >= Ld, of which rows `limb` and Ld-1
+// are read in place.  The term pointers and their limb counts travel in the kernel arguments (nothing uploaded per call).  Per (polynomial, kept limb,
+// chunk): the five 16-byte loads of relin_rescale_kernel, 2 K more (four terms in flight) and one store; the weights are workgroup-uniform (scalar loads).
+struct LincombTerms {
+    const u64* z[kRelinLincombMaxTerms];
+    unsigned limbs[kRelinLincombMaxTerms];
+};
+template <class Arith>
+__global__ __launch_bounds__(256) void relin_lincomb_rescale_kernel(u64* out, const u64* __restrict__ work, const u64* __restrict__ in3, const LincombTerms terms,
+                                                                    const u64* __restrict__ w, const LimbConst* lcs, const RescaleConst* rcp,
+                                                                    const RescaleConst* rcq, int n_limbs, int n, int chunks, int n_terms) {
+    const int Ld = n_limbs - 1, Lo = Ld - 1;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, Lo);
+    const int limb = wk.limb;
+    const size_t poly = wk.poly;   // = b * 2 + comp
+    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const RelinRescaleConsts k{lcs[limb], lcs[Lo], rcp[limb], rcp[Lo], rcq[limb]};
+    const u64* wp = work + poly * n_limbs * (size_t)n + w0;
+    const u64* cp = in3 + ((poly >> 1) * 3 + (poly & 1)) * Ld * (size_t)n + w0;
+    const U64x2 wi = *reinterpret_cast<const U64x2*>(wp + (size_t)limb * n);
+    const U64x2 wl = *reinterpret_cast<const U64x2*>(wp + (size_t)Lo * n);
+    const U64x2 wP = *reinterpret_cast<const U64x2*>(wp + (size_t)Ld * n);
+    const U64x2 ci = *reinterpret_cast<const U64x2*>(cp + (size_t)limb * n);
+    const U64x2 cl = *reinterpret_cast<const U64x2*>(cp + (size_t)Lo * n);
+    LazySum si[2] = {{0, 0}, {0, 0}}, sl[2] = {{0, 0}, {0, 0}};
+    const u64* wt = w + Ld;   // the terms' rows
+    auto row = [&](int t, int l) { return terms.z[t] + (poly * terms.limbs[t] + (size_t)l) * n + w0; };
+    int t = 0;
+    for (; t + 4 <= n_terms; t += 4) {
+        U64x2 vi[4], vl[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            vi[u] = *reinterpret_cast<const U64x2*>(row(t + u, limb));
+            vl[u] = *reinterpret_cast<const U64x2*>(row(t + u, Lo));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const u64 a = wt[(t + u) * Ld + limb], b = wt[(t + u) * Ld + Lo];
+            lazy_mac(si[0], a, vi[u].a); lazy_mac(si[1], a, vi[u].b);
+            lazy_mac(sl[0], b, vl[u].a); lazy_mac(sl[1], b, vl[u].b);
+        }
+    }
+    for (; t < n_terms; ++t) {
+        const U64x2 vi = *reinterpret_cast<const U64x2*>(row(t, limb));
+        const U64x2 vl = *reinterpret_cast<const U64x2*>(row(t, Lo));
+        const u64 a = wt[t * Ld + limb], b = wt[t * Ld + Lo];
+        lazy_mac(si[0], a, vi.a); lazy_mac(si[1], a, vi.b);
+        lazy_mac(sl[0], b, vl.a); lazy_mac(sl[1], b, vl.b);
+    }
+    if (!(poly & 1) && w0 == 0) { lazy_add(si[0], wt[n_terms * Ld + limb]); lazy_add(sl[0], wt[n_terms * Ld + Lo]); }
+    const u64 pi = w[limb], pl = w[Lo];
+    *reinterpret_cast<U64x2*>(out + (poly * Lo + limb) * n + w0) =
+        U64x2{relin_lincomb_rescale_word<Arith>(wi.a, wl.a, wP.a, ci.a, cl.a, pi, pl, si[0], sl[0], k),
+              relin_lincomb_rescale_word<Arith>(wi.b, wl.b, wP.b, ci.b, cl.b, pi, pl, si[1], sl[1], k)};
+}
+
 // (the exact base extension / scale-and-round kernels live in kernels_bx.h: one kernel per source-limb count, compiled in their own
 // translation units k_bx_fold.hip / k_bx_shoup.hip)
 

@@ -386,6 +386,39 @@ class Evaluator:
                                                                self._sp(stream)), "dpfhe_relinearize_rescale_hybrid")
         return Ciphertext(out, False)
 
+    def relinearize_lincomb_rescale_hybrid(self, ct3: Ciphertext, key: torch.Tensor, terms, w: torch.Tensor, stream=None) -> Ciphertext:
+        """A relinearised product, a scalar linear combination of other ciphertexts, a constant and the rescale in one call
+        (dpfhe_relinearize_lincomb_rescale_hybrid): round((w[0] t + sum_k w[1 + k] terms[k] + [c0, X^0] w[K + 1]) / q_{L-2}) with t the words of
+        keyswitch_hybrid(ct3, key).  THIS evaluator's context is the extended one; ct3: [batch][3][L-1][N]; terms: 0 to 15 coefficient-domain tensors
+        [batch][2][>= L-1][N] whose first L - 1 limbs are read in place (a term higher up the prime chain needs no copy); w: [K + 2][L-1] residues
+        -> [batch][2][L-2][N]."""
+        import ctypes as C
+        p = self.ctx.params
+        L, Ld, n = p.n_limbs, p.n_limbs - 1, p.n
+        d = ct3.data
+        terms = [t.data if isinstance(t, Ciphertext) else t for t in terms]
+        K = len(terms)
+        if ct3.is_ntt or ct3.size != 3 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "relinearize_lincomb_rescale_hybrid: coefficient-domain [batch][3][L-1][N] ciphertexts on the extended context")
+        if tuple(key.shape) != (Ld, 2, L, n):
+            raise _cabi.DpfheError(2000, "key must be [L-1][2][L][N]")
+        if Ld < 2:
+            raise _cabi.DpfheError(2002, "relinearize_lincomb_rescale_hybrid: no data limb left to drop")
+        batch = d.shape[0]
+        for t in terms:
+            if t.dim() != 4 or t.shape[0] != batch or t.shape[1] != 2 or t.shape[2] < Ld or t.shape[3] != n or t.dtype != torch.int64 or not t.is_contiguous() \
+                    or t.device != d.device:
+                raise _cabi.DpfheError(2000, "relinearize_lincomb_rescale_hybrid: terms are [batch][2][>= L-1][N] int64 on the ciphertext's device")
+        if K > 15 or tuple(w.shape) != (K + 2, Ld) or w.dtype != torch.int64 or not w.is_contiguous() or w.device != d.device:
+            raise _cabi.DpfheError(2000, "relinearize_lincomb_rescale_hybrid: at most 15 terms, w [K + 2][L-1] int64 on the ciphertext's device")
+        out = self._empty((batch, 2, Ld - 1, n), stream)
+        work = self._empty((batch, 2, L, n), stream)
+        ptrs = (C.c_void_p * max(K, 1))(*[t.data_ptr() for t in terms])
+        limbs = (C.c_uint32 * max(K, 1))(*[t.shape[2] for t in terms])
+        _cabi.check(self._lib.dpfhe_relinearize_lincomb_rescale_hybrid(self.ctx.handle, out.data_ptr(), d.data_ptr(), key.data_ptr(), work.data_ptr(), ptrs, limbs, K,
+                                                                       w.data_ptr(), batch, self._sp(stream)), "dpfhe_relinearize_lincomb_rescale_hybrid")
+        return Ciphertext(out, False)
+
     def rotate_hybrid_batch(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> Ciphertext:
         """N3, batched rotations on the extended context: output item i = key-switched sigma_{galois_elts[i]} of input item
         i, or of THE input item when ct holds one.  keys: [len(elts)][L-1][2][L][N] (key i switches sigma_{g_i}(s) -> s)."""

@@ -491,6 +491,32 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// ScalarWeights: the integer weights of HybridKeySwitcher::multiply_lincomb_rescale_range as residue rows on the device ([K + 2][Ld], the d_w of
+// dpfhe_relinearize_lincomb_rescale_hybrid), built once: row 0 the product's weight, rows 1 .. K the terms', row K + 1 the constant
+// constant_at_output * q_last - an exact integer product, as ApproxPolynomial builds its own, so that the rescale gives constant_at_output back exactly in
+// every slot's coefficient 0 (a constant at the OUTPUT's scale).  INVALID_ARGUMENT for more than 15 terms or a |w| >= 2^62; INVALID_STATE for a data_ctx of
+// one limb (nothing to drop).  data_ctx must outlive the object.
+class ScalarWeights {
+public:
+    ScalarWeights(const Context& data_ctx, int64_t product_weight, const std::vector<int64_t>& term_weights, int64_t constant_at_output);
+    ~ScalarWeights();
+    ScalarWeights(const ScalarWeights&) = delete;
+    ScalarWeights& operator=(const ScalarWeights&) = delete;
+    size_t terms() const;                 // K
+    const Context& context() const;       // data_ctx
+    const uint64_t* data() const;         // device, [K + 2][Ld]
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// one addend of multiply_lincomb_rescale_range: items first .. first + count - 1 of ct
+struct LincombTerm {
+    const Ciphertext* ct;
+    size_t first;
+};
+
 // Hybrid key switching with one special prime P (SURVEY.md 8f N1 "base extension"): keys live on the extended
 // context (data moduli + P) and the switching noise drops from ~ L N q sigma to ~ L N q sigma / P.
 class HybridKeySwitcher {
@@ -521,6 +547,15 @@ public:
     // the same on item ranges: out item out_first + i = items a_first + i of a times b_first + i of b, i < count (a and b may be one buffer, also one range)
     void multiply_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, Ciphertext& out_next_level,
                                 size_t out_first, Stream* stream = nullptr) const;
+    // A product, a scalar linear combination and the rescale in one step (the second half of a Newton step, a Horner step): out item out_first + i =
+    //   round((w_0 relinearize(a_i * b_i) + sum_k w_{1+k} z_k,i + constant) / q_last)   at the next level
+    // - Evaluator::multiply on data_ctx into the object's scratch, then dpfhe_relinearize_lincomb_rescale_hybrid: the relinearised product is never written,
+    // and term k = items terms[k].first + i of *terms[k].ct is read in place on ITS context, whose first limbs must be data_ctx's (the same level, or any level
+    // above it on the same prime chain: keeping the first limbs is the level drop; no copy).  The scales are the caller's: the phases summed are
+    // w_0 s_a s_b (a b) and w_{1+k} s_k z_k, and the sum is divided by q_last (ApproxInvSqrt shows one choice).  weights: on data_ctx, weights.terms() == terms.size().
+    // Terms: 2 components, coefficient domain.  The stream contract is multiply_rescale_range's: enqueues only, scratch grown only for a larger batch.
+    void multiply_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, const ScalarWeights& weights,
+                                        const std::vector<LincombTerm>& terms, Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
     // many rotations in one pass (dpfhe_rotate_hybrid_batch): out item out_first + i = sigma_{elts[i]} of in item i, or of THE
     // item of `in` when it holds one.  All elements must have been added; the keys of a given element list are packed
     // back to back once and cached.
@@ -872,6 +907,75 @@ public:
     // only; the scratch (powers, operands) belongs to the object and grows only for a larger T than before; one apply() at a time per object and per key
     // switcher.
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxInvSqrt: slot-wise y ~ 1 / sqrt(v) in the approximate family by K Newton steps  y <- y (3 - v y^2) / 2 = 1.5 y - 0.5 (v y)(y y)  on a guess y_0 the
+// caller supplies (a low-degree ApproxPolynomial of v: a polynomial alone is a poor 1 / sqrt - on a variance range of 10x a cubic is off by 10 % - while two
+// steps take that cubic to 3e-4 and a degree-5 guess to 2e-6).  The division of a LayerNorm by its standard deviation.  Relinearisation keys only.
+//
+// Levels.  2 K key switchers, input level first, each one limb below the last; y_n lives at scale s_n on level 2 n (the data context of levels[2 n]); out_ctx
+//   is level 2 K.  Iteration n, with q_a the last prime of level 2 n and q_b the last prime of level 2 n + 1:
+//   1. a = v y_n and b = y_n y_n on levels[2 n] (HybridKeySwitcher::multiply_rescale_range twice; v is brought to the level by keeping its first limbs, as
+//      ApproxPolynomial::apply does with its powers), both at level 2 n + 1;
+//   2. y_{n+1} = round((-(a (x) b relinearised) + w_n y_n) / q_b) on levels[2 n + 1] in ONE HybridKeySwitcher::multiply_lincomb_rescale_range: the product's
+//      weight is exactly -1, so no rounding of a weight touches the product, and y_n is read where it lives, one limb above that level (no copy).
+// Scales, in exactly these double operations (tests/invsqrt_model.py mirrors them):  s_0 = guess_scale;
+//     s_a = (v_scale * s_n) / (double)q_a;   s_b = (s_n * s_n) / (double)q_a;   top = 2.0 * (s_a * s_b);   w_n = llround(1.5 * (top / s_n));
+//     s_{n+1} = top / (double)q_b.
+//   -(a b) read at scale top is -0.5 v y^3, and w_n y_n is 1.5 y.  s_{n+1} / s_n = 2 v_scale s_n^2 / (q_a^2 q_b): a guess scale off the balance by a factor c
+//   is off by c^3 after one step, c^9 after two - a mismatch grows cubically per step.  balanced_guess_scale(v_scale, q_a, q_b) = sqrt(q_a^2 q_b / (2 v_scale))
+//   makes s_1 = s_0 (for primes of one size every s_n then stays there); consult scale(n) before choosing limbs.  INVALID_ARGUMENT when the contexts do not
+//   form the chain, a scale is not finite and positive, |w_n| >= 2^62, or any s_n, n <= K, lies outside [2^20, 2^62).
+//
+// Error bound.  ApproxPolynomial's notation and tools T1 - T4: u = 2^-53, H = (N + 1) / 2 (T3), per level r: L_r its data limbs, rho_r = max_j q_j / P_r,
+//   K_r = 21 L_r N rho_r (T4).  V = max|v|, Y a bound on every |y_n| (n <= K, of the real iteration and of its float64 evaluation), Bv and By the coefficient
+//   errors of the phases of v and y_0.  The phase of v has slot v_scale v + d_v, |d_v| <= D_v = N Bv (T1; dropping limbs changes nothing); the phase of y_n has
+//   slot s_n y_n + e_n with y_n the REAL iterate of the values encrypted, |e_n| <= E_n, E_0 = N By.  One recurrence per iteration.  The products follow
+//   ApproxPolynomial's D_k rule (slots multiply (T2), the relinearisation adds K_r + H per coefficient after its division by P, the division by q_a divides all
+//   of it and adds H, the scale as a double is off by at most 4 u of itself):
+//     D_a = (v_scale V E_n + s_n Y D_v + D_v E_n + N (K_{2n} + H)) / q_a + N H + 4 u s_a V Y
+//     D_b = (2 s_n Y E_n + E_n^2             + N (K_{2n} + H)) / q_a + N H + 4 u s_b Y^2
+//   The fused step sums  w_n (s_n y_n + e_n) - (s_a v y_n + d_a)(s_b y_n^2 + d_b) = top y_{n+1} + errors: the product of the two phases is off by
+//   s_a V Y D_b + s_b Y^2 D_a + D_a D_b, plus N (K_{2n+1} + H) for its relinearisation, plus |w_n| E_n; w_n = 1.5 top / s_n + r with |r| <= R = 1/2 +
+//   4 u 1.5 top / s_n (llround; the roundings of the double expression) adds R s_n Y, and top as a double stands for 2 s_a s_b up to u top, which adds
+//   u top V Y^3.  The rescale divides all of this by q_b and adds N H; s_{n+1} as a double is off top / q_b by at most 2 u s_{n+1}:
+//     E_{n+1} = (s_a V Y D_b + s_b Y^2 D_a + D_a D_b + N (K_{2n+1} + H) + (1.5 top / s_n + R) E_n + R s_n Y + u top V Y^3) / q_b + N H + 2 u s_{n+1} Y.
+//   pre = E_K / s_K; the client's decode adds u8 N (Y + pre), u8 = 8 log2(N) u; and the float64 iteration the bound is stated against is itself off the real
+//   one by F_K, F_0 = 0, F_{n+1} = 1.5 (1 + V Y^2) F_n + 8 u (1.5 Y + 0.5 V Y^3) (the step's derivative, its five roundings).
+//   error_bound(V, Y, Bv, By) = pre + u8 N (Y + pre) + F_K bounds |decoded slot - Y_K| for every slot and token, Y_K the float64 iteration
+//   y <- 1.5 y - 0.5 (v y)(y y) from the values actually encrypted, PROVIDED no phase wraps.  How far the GUESS is from 1 / sqrt(v) is the caller's and is
+//   not part of it (Newton's own convergence: a relative error e becomes about 1.5 e^2).  Worst case throughout.
+//
+// Exact on a transparent input (c1 = 0: every relinearisation digit is zero): with mu_v and mu_0 the integer polynomials of v and y_0 and (*) the product in
+//   Z[X] / (X^N + 1),  mu_a = round(mu_v (*) mu_n / q_a),  mu_b = round(mu_n (*) mu_n / q_a),  mu_{n+1} = round((w_n mu_n - mu_a (*) mu_b) / q_b),
+//   c0_out = mu_K mod q_l,  c1_out = 0, word for word (tests/invsqrt_model.py states it on Python integers, tests/test_gpu_invsqrt_words.py holds the device to it).
+class ApproxInvSqrt {
+public:
+    // levels: 2 K key switchers (K >= 1), input level first, levels[r] on the context of the input's limbs without the last r (same ring, same device, same
+    // secret); out_ctx: levels.back()'s data context without its last limb.  Everything referenced must outlive the object.
+    ApproxInvSqrt(const std::vector<HybridKeySwitcher*>& levels, const Context& out_ctx, double v_scale, double guess_scale);
+    ~ApproxInvSqrt();
+    ApproxInvSqrt(const ApproxInvSqrt&) = delete;
+    ApproxInvSqrt& operator=(const ApproxInvSqrt&) = delete;
+    size_t iterations() const;           // K
+    size_t depth() const;                // 2 K: the limbs between (v, y_0) and y
+    double scale(size_t n) const;        // s_n, n <= K; scale(K) is the output's
+    int64_t weight(size_t n) const;      // w_n, n < K
+    // the bound derived above: max_abs_v = V, max_abs_y = Y, v_noise_bound = Bv, guess_noise_bound = By
+    double error_bound(double max_abs_v, double max_abs_y, double v_noise_bound, double guess_noise_bound) const;
+    // ... and without a device: data_moduli are the input level's limbs (at least 2 K + 1), special_primes one P per level (2 K)
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, const std::vector<uint64_t>& special_primes, double v_scale,
+                              double guess_scale, double max_abs_v, double max_abs_y, double v_noise_bound, double guess_noise_bound);
+    // sqrt(q_a^2 q_b / (2 v_scale)): the guess scale at which s_1 = s_0 (q_a, q_b: the last primes of levels 0 and 1)
+    static double balanced_guess_scale(double v_scale, uint64_t q_a, uint64_t q_b);
+    // v, y0: T items on levels[0]'s data context (2 components, coefficient domain, scales v_scale and guess_scale); y: T items on out_ctx, scale
+    // scale(K).  Enqueues only; the scratch (v at the lower levels, the products, the iterates) belongs to the object and grows only for a larger T than
+    // before; one apply() at a time per object and per key switcher.
+    void apply(const Ciphertext& v, const Ciphertext& y0, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:
     class Impl;

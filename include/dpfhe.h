@@ -220,6 +220,40 @@ int dpfhe_lincomb_rescale(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_x, 
 int dpfhe_lincomb_rescale_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* x, const uint64_t* w,
                                size_t n_terms, size_t batch);
 
+/* -- a relinearised product, a scalar linear combination and the rescale in one call (the second half of a Newton step y (3 - v y^2) / 2, a Horner or
+ * Paterson-Stockmeyer step p x + c_k z + c_0, a Chebyshev doubling 2 T_k^2 - 1): ctx_ext, d_in3, d_key, d_work and d_out2 ([batch][2][Ld-1][N]) are exactly
+ * dpfhe_relinearize_rescale_hybrid's.  With t = (c0, c1) + round(sum_j [c2]_{q_j} key_j / P) on the Ld data limbs - the words dpfhe_relinearize_hybrid
+ * writes - and K = n_terms, per item, component and coefficient
+ *   s_l   = w[0][l] t_l + sum_{k<K} w[1+k][l] z_k,l + [component 0, coefficient 0] w[K+1][l]   mod q_l,   l < Ld
+ *   out_i = round(s / q_{Ld-1}) mod q_i,   i < Ld - 1        (dpfhe_rescale's rounding)
+ * d_terms: HOST array of K device pointers, term_limbs: HOST array of K limb counts; term k is [batch][2][term_limbs[k]][N], coefficient domain, canonical
+ *   residues, term_limbs[k] >= Ld, and only the first Ld limbs of each of its polynomials are read: a ciphertext that lives higher up the same prime chain is an
+ *   addend as it stands (keeping the first limbs IS the level drop; nothing is copied).  0 <= K <= 15: with the product at most 16 multiply-adds and one
+ *   constant, dpfhe_lincomb_rescale's bound on the 128-bit lazy sum.  Both arrays are read during the call only and may be NULL when K = 0.
+ * d_w: DEVICE array [K + 2][Ld] of canonical residues: dpfhe_lincomb_rescale's rows with the product's weight in front - row 0 the product's, rows 1 .. K the
+ *   terms', row K + 1 the constant (zeros for none).
+ * Identities: with K = 0, w[0] = 1 and a zero constant row the result is the words of dpfhe_relinearize_rescale_hybrid; in general it is the words of
+ *   dpfhe_relinearize_hybrid followed by dpfhe_lincomb_rescale on the data context over [t, z_0, ..., z_{K-1}] (each z_k cut to its first Ld limbs), however the
+ *   sum is taken: all results are canonical residues.
+ * One last pass after the key products: t is never written.  Algorithmic traffic of that pass per item, in rows of N words, every row counted once: it reads
+ *   the sums (2 L), c0 and c1 (2 Ld) and the first Ld limbs of every term (2 K Ld) and writes 2 (Ld - 1):  2 (L + (K + 2) Ld - 1) rows.  The three entries it
+ *   replaces - dpfhe_relinearize_hybrid's last pass, a strided copy of each of the K' terms that are taller or not yet next to t, dpfhe_lincomb_rescale - read
+ *   and write the same rows and on top write and re-read t (4 Ld) and every copied term (4 Ld each):  2 (L + (K + 2) Ld - 1) + 4 (1 + K') Ld rows.  At K = K' = 1,
+ *   Ld = 4, L = 5: 32 rows against 64.
+ * The term pointers travel in the kernel's arguments: nothing is uploaded or allocated per call.  Enqueues only; at log2_n <= 13 it never allocates (above, the
+ * key products take arena scratch as in dpfhe_relinearize_hybrid).  Every log2_n (8 ... 16) and limb class.  DPFHE_INVALID_STATE without a special prime or with
+ * Ld < 2; DPFHE_INVALID_ARGUMENT, before the device is touched, on a null or misaligned (16 bytes) buffer, n_terms > 15, a term_limbs[k] < Ld, d_out2 or d_work
+ * overlapping each other or anything else, or a grid too large for one launch.  batch == 0 returns success.  Read-only buffers may alias each other.
+ * dpfhe_relinearize_lincomb_rescale_pass_host: the host twin of that last pass alone (no device, no context, no alignment rule): moduli, work_qp, in3 and out as
+ *   for dpfhe_relinearize_rescale_pass_host, terms / term_limbs / w as above but in host memory.  Words that are not canonical residues are rejected (of a
+ *   term, the first Ld limbs - the ones that are read). */
+int dpfhe_relinearize_lincomb_rescale_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in3, const uint64_t* d_key, uint64_t* d_work,
+                                             const uint64_t* const* d_terms, const uint32_t* term_limbs, size_t n_terms, const uint64_t* d_w,
+                                             size_t batch, void* stream);
+int dpfhe_relinearize_lincomb_rescale_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp,
+                                                const uint64_t* in3, const uint64_t* const* terms, const uint32_t* term_limbs, size_t n_terms,
+                                                const uint64_t* w, size_t batch);
+
 /* -- N3, batched rotations (the baby / giant steps of a packed matrix-vector product): item i of the output is the
  * hybrid-key-switched sigma_{galois_elts[i]} of input item i (n_in == batch) or of THE input item (n_in == 1).
  * galois_elts: HOST array of `batch` odd elements < 2N.  d_keys: `batch` keys back to back, each [Ld][2][L][N] as for
