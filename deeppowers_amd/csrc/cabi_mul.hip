@@ -1,5 +1,6 @@
 // cabi_mul.hip - the C ABI's ciphertext multiply: dpfhe_ct_mul on the fused kernels of kernels.h (launch.h), composed above N = 8192 over
-// kernels_mul.h, and its traced diagnostic form.  cabi.h lists the other units and states the ABI's conventions.
+// kernels_mul.h, its traced diagnostic form, and dpfhe_ct_mul_sum (sums of products, composed at every ring degree).  cabi.h lists the other units and
+// states the ABI's conventions.
 #include "cabi.h"
 #include "kernels_mul.h"
 
@@ -67,6 +68,91 @@ extern "C" int dpfhe_ct_mul(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2
     }
     if (rc) return fail(DPFHE_INVALID_STATE, "dpfhe_ct_mul", "no kernel geometry for this log2_n");
     return check_launch("ct_mul kernel launch");
+}
+
+// ---- a sum of tensor products (include/dpfhe.h dpfhe_ct_mul_sum): always composed, at every ring degree - batched forward transforms into the stream's arena,
+// tensor3_sum_kernel (kernels_mul.h), three inverse transforms per group.
+
+struct MulSumCall {
+    dpfhe_ctx* c;
+    uint32_t flags;
+    hipStream_t s;
+    size_t terms_total;   // the terms of a group as the CALLER laid them out (strides of d_a2 / d_b2)
+    bool shared, square;
+};
+
+static int mul_sum_kernel_launch(const MulSumCall& k, uint64_t* d_out3, const u64* pa, const u64* pb, size_t groups, size_t terms, bool b_shared, bool accumulate) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n;
+    const size_t grid = mul_sum_grid(groups, L, n);
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((tensor3_sum_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, k.s, d_out3, pa, pb, c->lc, (int)L, (int)n, chunks_of(n), (int)terms,
+                           (int)b_shared, (int)accumulate);
+    });
+    return check_launch("tensor product sum kernel launch");
+}
+
+static int ct_mul_sum_composed(const MulSumCall& k, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t groups) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, poly = L << c->log2n, terms = k.terms_total, item = terms * 2 * poly;   // item: one group's operand
+    const bool out_ntt = (k.flags & DPFHE_OUT_NTT) != 0;
+    if (k.flags & DPFHE_IN_NTT) {   // no scratch: one launch over everything
+        if (int rc = mul_sum_kernel_launch(k, d_out3, d_a2, d_b2, groups, terms, k.shared, false)) return rc;
+        return out_ntt ? DPFHE_SUCCESS : ntt_launch(c, true, d_out3, d_out3, groups * 3 * L, k.s);
+    }
+    // Scratch for the transformed operands: [b, when shared | slice of a | that slice of b, when it has its own and is not a itself]
+    const size_t limit = c->scratch_limit_words.load(std::memory_order_relaxed);
+    const size_t fixed = k.shared ? item : 0, per_group = (k.shared || k.square ? 1 : 2) * item;
+    StreamScratch ws(c, k.s);
+    if (fixed + per_group <= limit) {   // whole groups fit: slices of groups
+        const size_t fit = (limit - fixed) / per_group, per = fit < groups ? fit : groups;
+        if (int rc = ws.alloc(fixed + per * per_group, "dpfhe_ct_mul_sum (scratch for the transformed operands)")) return rc;
+        if (k.shared) if (int rc = ntt_launch(c, false, ws.p, d_b2, terms * 2 * L, k.s)) return rc;   // once for all slices
+        return for_slices(groups, per, [&](size_t g0, size_t m) {
+            u64* ta = ws.p + fixed;
+            u64* tb = k.shared ? ws.p : k.square ? ta : ta + m * item;
+            if (int rc = ntt_launch(c, false, ta, d_a2 + g0 * item, m * terms * 2 * L, k.s)) return rc;
+            if (!k.shared && !k.square) if (int rc = ntt_launch(c, false, tb, d_b2 + g0 * item, m * terms * 2 * L, k.s)) return rc;
+            if (int rc = mul_sum_kernel_launch(k, d_out3 + g0 * 3 * poly, ta, tb, m, terms, k.shared, false)) return rc;
+            return out_ntt ? (int)DPFHE_SUCCESS : ntt_launch(c, true, d_out3 + g0 * 3 * poly, d_out3 + g0 * 3 * poly, m * 3 * L, k.s);
+        });
+    }
+    // one group does not fit: group by group, each cut into ranges of terms that accumulate into its NTT-domain output; the inverse transforms come last
+    const size_t per_term = (k.square ? 2 : 4) * poly, fit = limit / per_term, per = fit == 0 ? 1 : (fit < terms ? fit : terms);
+    if (int rc = ws.alloc(per * per_term, "dpfhe_ct_mul_sum (scratch for a range of transformed terms)")) return rc;
+    for (size_t g = 0; g < groups; ++g) {
+        const u64 *ga = d_a2 + g * item, *gb = d_b2 + (k.shared ? 0 : g * item);
+        u64* go = d_out3 + g * 3 * poly;
+        if (int rc = for_slices(terms, per, [&](size_t t0, size_t m) {
+                u64 *ta = ws.p, *tb = k.square ? ta : ta + m * 2 * poly;
+                if (int rc = ntt_launch(c, false, ta, ga + t0 * 2 * poly, m * 2 * L, k.s)) return rc;
+                if (!k.square) if (int rc = ntt_launch(c, false, tb, gb + t0 * 2 * poly, m * 2 * L, k.s)) return rc;
+                return mul_sum_kernel_launch(k, go, ta, tb, 1, m, false, t0 != 0);
+            })) return rc;
+        if (!out_ntt) if (int rc = ntt_launch(c, true, go, go, 3 * L, k.s)) return rc;
+    }
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_ct_mul_sum(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t groups, size_t terms, size_t b_groups,
+                                uint32_t flags, void* stream) {
+    static const char* what = "dpfhe_ct_mul_sum";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (flags & ~(DPFHE_IN_NTT | DPFHE_OUT_NTT)) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag");
+    if (terms == 0) return fail(DPFHE_INVALID_ARGUMENT, what, "terms must be at least 1");
+    if (groups == 0) return DPFHE_SUCCESS;
+    if (b_groups != 1 && b_groups != groups) return fail(DPFHE_INVALID_ARGUMENT, what, "b_groups must be 1 (shared) or groups");
+    if (!d_out3 || !d_a2 || !d_b2 || misaligned(d_out3) || misaligned(d_a2) || misaligned(d_b2)) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n, poly = L * n;
+    // sizes first (a product that wraps size_t would pass the overlap test): every count below stays under 2^31 residue polynomials
+    if (groups > kMaxGrid || terms > kMaxGrid || groups * terms > kMaxGrid / (2 * L) || mul_sum_grid(groups, L, n) > kMaxGrid || !ntt_grid_fits(c, groups * 3 * L) ||
+        !ntt_grid_fits(c, groups * terms * 2 * L))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "groups * terms too large for one launch");
+    if (overlaps(d_out3, groups * 3 * poly, d_a2, groups * terms * 2 * poly) || overlaps(d_out3, groups * 3 * poly, d_b2, b_groups * terms * 2 * poly))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an operand");
+    DPFHE_ON_DEVICE(c, what);
+    MulSumCall k{c, flags, static_cast<hipStream_t>(stream), terms, b_groups == 1 && groups > 1, d_a2 == d_b2 && b_groups == groups};
+    return ct_mul_sum_composed(k, d_out3, d_a2, d_b2, groups);
 }
 
 // diagnostics: the quad form with per-workgroup timestamps (kernels.h ct_mul_quad_kernel<..., TRACE>); FoldArith contexts at N = 4096

@@ -1,7 +1,7 @@
 // fhe_api.cpp - deeppowers::fhe facade over the C ABI (include/dpfhe.h): parameters, contexts, buffers and their wire formats, the evaluator and the
 // communicator.  Plain C++17 (g++); the only HIP it touches is the runtime API for buffer ownership.  The other roles of the facade, all built into the
 // same libdpfhe_api.so: fhe_keys.cpp (everything that holds or draws secrets), fhe_keyswitch.cpp, fhe_encode.cpp, fhe_packed.cpp (kBabyShiftDefault
-// lives there), fhe_polynomial.cpp, fhe_invsqrt.cpp; fhe_internal.h is what they share.
+// lives there), fhe_polynomial.cpp, fhe_invsqrt.cpp, fhe_product_sum.cpp; fhe_internal.h is what they share.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -506,6 +506,16 @@ void Evaluator::multiply(const Ciphertext& a, const Ciphertext& b, Ciphertext& o
     if (out.size() != 3 || out.batch() != a.batch()) throw Exception(ErrorCode::INVALID_ARGUMENT, "multiply: output must be a 3-component ciphertext of the same batch");
     const uint32_t flags = (a.is_ntt() ? (uint32_t)DPFHE_IN_NTT : 0u) | (out.is_ntt() ? (uint32_t)DPFHE_OUT_NTT : 0u);
     check(dpfhe_ct_mul(impl_->h(), out.data(), a.data(), b.data(), a.batch(), flags, s), "dpfhe_ct_mul");
+}
+void Evaluator::multiply_sum(const Ciphertext& a, const Ciphertext& b, size_t terms, bool b_shared, Ciphertext& out, Stream* s) const {
+    if (a.is_ntt() != b.is_ntt()) throw Exception(ErrorCode::INVALID_STATE, "multiply_sum: operands are in different domains");
+    if (a.size() != 2 || b.size() != 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "multiply_sum: inputs must be 2-component ciphertexts");
+    if (terms == 0 || a.batch() % terms || b.batch() != (b_shared ? terms : a.batch()))
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "multiply_sum: a holds groups * terms items, b as many or, shared, terms items");
+    const size_t groups = a.batch() / terms;
+    if (out.size() != 3 || out.batch() != groups) throw Exception(ErrorCode::INVALID_ARGUMENT, "multiply_sum: output must be a 3-component ciphertext of one item per group");
+    const uint32_t flags = (a.is_ntt() ? (uint32_t)DPFHE_IN_NTT : 0u) | (out.is_ntt() ? (uint32_t)DPFHE_OUT_NTT : 0u);
+    check(dpfhe_ct_mul_sum(impl_->h(), out.data(), a.data(), b.data(), groups, terms, b_shared ? 1 : groups, flags, s), "dpfhe_ct_mul_sum");
 }
 void Evaluator::relinearize(const Ciphertext& in3, const RelinKeys& keys, Ciphertext& out2, Stream* s) const {
     if (in3.is_ntt()) throw Exception(ErrorCode::INVALID_STATE, "relinearize: input must be in the coefficient domain");

@@ -314,6 +314,79 @@ void HybridKeySwitcher::multiply_lincomb_rescale_range(const Ciphertext& a, size
     out.set_ntt(false);
 }
 
+// ---- sums of products: the tensor products summed by dpfhe_ct_mul_sum into the object's scratch, ONE key switch and one rounding per group ----------------
+namespace {
+
+// the operand and output ranges of a product sum; returns the product's word counts through the references
+void check_product_sum(const char* what, const FheParams& pe, const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups,
+                       size_t terms, const Ciphertext& out, size_t out_first, size_t& in_words, size_t& out_words) {
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n();
+    in_words = 2 * Ld * n;
+    out_words = 2 * (Ld - 1) * n;
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, std::string(what) + ": no data limb left to drop");
+    if (terms == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": at least one term");
+    const size_t a_count = groups * terms, b_count = b_shared ? terms : a_count;
+    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+        a_first + a_count > a.batch() || b_first + b_count > b.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": 2-component coefficient-domain ciphertexts on the data context, groups * terms items of a, as many or (shared) terms items of b");
+    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + groups > out.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for one item per group");
+}
+
+}  // namespace
+
+void HybridKeySwitcher::multiply_sum_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups, size_t terms,
+                                                   Ciphertext& out, size_t out_first, Stream* s) const {
+    size_t in_words, out_words;
+    check_product_sum("HybridKeySwitcher::multiply_sum_rescale", impl_->ext->params(), a, a_first, b, b_first, b_shared, groups, terms, out, out_first, in_words, out_words);
+    if (groups == 0) return;
+    grow_scratch(impl_->scratch_product, groups, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
+    grow_scratch(impl_->scratch_work, groups, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul_sum(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, groups, terms,
+                           b_shared ? 1 : groups, 0, s),
+          "dpfhe_ct_mul_sum");
+    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                           impl_->scratch_work->data(), groups, s),
+          "dpfhe_relinearize_rescale_hybrid");
+    out.set_ntt(false);
+}
+
+void HybridKeySwitcher::multiply_sum_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups,
+                                                           size_t terms, const ScalarWeights& weights, const std::vector<LincombTerm>& addends, Ciphertext& out,
+                                                           size_t out_first, Stream* s) const {
+    static const char* what = "HybridKeySwitcher::multiply_sum_lincomb_rescale";
+    size_t in_words, out_words;
+    check_product_sum(what, impl_->ext->params(), a, a_first, b, b_first, b_shared, groups, terms, out, out_first, in_words, out_words);
+    const FheParams& pd = impl_->data_ctx->params();
+    const size_t Ld = pd.n_limbs(), n = pd.n();
+    const FheParams& pw = weights.context().params();
+    if (weights.terms() != addends.size() || pw.log2_n != pd.log2_n || pw.moduli != pd.moduli || weights.context().device_id() != impl_->data_ctx->device_id())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": weights built on the data context, one per addend");
+    const uint64_t* ptrs[15] = {};
+    uint32_t limbs[15] = {};
+    for (size_t k = 0; k < addends.size(); ++k) {   // (multiply_lincomb_rescale_range's rules, one item per group)
+        const Ciphertext* z = addends[k].ct;
+        if (!z) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": null addend");
+        const FheParams& pz = z->context().params();
+        const size_t Lz = pz.n_limbs();
+        if (z->is_ntt() || z->size() != 2 || pz.log2_n != pd.log2_n || Lz < Ld || !std::equal(pd.moduli.begin(), pd.moduli.end(), pz.moduli.begin()) ||
+            z->words() != z->batch() * 2 * Lz * n || addends[k].first + groups > z->batch() || z->context().device_id() != impl_->data_ctx->device_id())
+            throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": an addend is 2 components, coefficient domain, on a context whose first limbs are the data context's, range inside it");
+        ptrs[k] = z->data() + addends[k].first * 2 * Lz * n;
+        limbs[k] = (uint32_t)Lz;
+    }
+    if (groups == 0) return;
+    grow_scratch(impl_->scratch_product, groups, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
+    grow_scratch(impl_->scratch_work, groups, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul_sum(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, groups, terms,
+                           b_shared ? 1 : groups, 0, s),
+          "dpfhe_ct_mul_sum");
+    check(dpfhe_relinearize_lincomb_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                                   impl_->scratch_work->data(), ptrs, limbs, addends.size(), weights.data(), groups, s),
+          "dpfhe_relinearize_lincomb_rescale_hybrid");
+    out.set_ntt(false);
+}
+
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
 const Context& HybridKeySwitcher::data_context() const { return *impl_->data_ctx; }
 

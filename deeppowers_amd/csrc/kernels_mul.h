@@ -1,4 +1,4 @@
-// kernels_mul.h - the multiply at ring degrees above 8192 (device).  Included by cabi_mul.hip only.
+// kernels_mul.h - the multiply at ring degrees above 8192, and sums of products at every ring degree (device).  Included by cabi_mul.hip only.
 //
 // The fused multiply kernels of kernels.h keep whole polynomials in one workgroup's registers and LDS, which stops at
 // N = 8192 (one 1024-thread workgroup at N = 16384 has 128 VGPRs per thread; four polynomials of 16 words per thread do not fit).
@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "modarith.h"
+#include "mul_sum.h"
 #include "workmap.h"
 
 namespace dpfhe {
@@ -34,6 +35,63 @@ __global__ __launch_bounds__(256) void tensor3_kernel(u64* __restrict__ out3, co
     *reinterpret_cast<U64x2*>(out3 + (pair * 3 + 0) * poly + off) = d0;
     *reinterpret_cast<U64x2*>(out3 + (pair * 3 + 1) * poly + off) = d1;
     *reinterpret_cast<U64x2*>(out3 + (pair * 3 + 2) * poly + off) = d2;
+}
+
+// A SUM of tensor products, one pass: out3[g] (+)= sum_{k < terms} a[g][k] (x) b[g][k], NTT domain, canonical in and out (mul_sum.h holds the lane arithmetic
+// and its bounds).  a2: [groups][terms][2][L][N]; b2: the same, or [terms][2][L][N] read by every group (b_shared); out3: [groups][3][L][N].  The tensor
+// product is bilinear, so whatever follows - inverse transforms, key switch, rescale - is paid once per group, not once per term.  `accumulate`: the sums
+// continue from the canonical words already in out3 (a group cut into ranges of terms).  One workgroup per (group, limb, 512-word chunk), 16 bytes per lane.
+// kMulSumDepth terms are loaded before the first of them is used: 16 independent 16-byte loads per lane in flight (a loop that waits on one term's four
+// loads per iteration leaves the memory pipeline idle for most of a round trip).  Traffic per group and limb in rows of N words: 4 terms + 3, or 2 terms + 3
+// and the shared rows once per XCD from HBM (groups of one limb and chunk are `L chunks` ids apart: the shared rows are L2 hits at best, not guaranteed).
+constexpr int kMulSumDepth = 4;
+template <class Arith>
+__global__ __launch_bounds__(256) void tensor3_sum_kernel(u64* __restrict__ out3, const u64* __restrict__ a2, const u64* __restrict__ b2, const LimbConst* lcs,
+                                                          int n_limbs, int n, int chunks, int terms, int b_shared, int accumulate) {
+    typedef MulSumLane<Arith> Lane;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t group = wk.poly;
+    const int w0 = chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const LimbConst lc = lcs[limb];
+    const size_t poly = (size_t)n_limbs * n, off = (size_t)limb * n + w0;
+    const u64* pa = a2 + group * (size_t)terms * 2 * poly + off;
+    const u64* pb = b2 + (b_shared ? 0 : group * (size_t)terms * 2 * poly) + off;
+    u64* po = out3 + group * 3 * poly + off;
+    U64x2 p0{0, 0}, p1{0, 0}, p2{0, 0};
+    if (accumulate) {
+        p0 = *reinterpret_cast<const U64x2*>(po); p1 = *reinterpret_cast<const U64x2*>(po + poly); p2 = *reinterpret_cast<const U64x2*>(po + 2 * poly);
+    }
+    typename Lane::Acc sa = Lane::init(p0.a, p1.a, p2.a, lc), sb = Lane::init(p0.b, p1.b, p2.b, lc);
+    int k = 0;
+    for (; k + kMulSumDepth <= terms; k += kMulSumDepth) {
+        U64x2 a0[kMulSumDepth], a1[kMulSumDepth], b0[kMulSumDepth], b1[kMulSumDepth];
+#pragma unroll
+        for (int u = 0; u < kMulSumDepth; ++u) {
+            const size_t t = (size_t)(k + u) * 2 * poly;
+            a0[u] = *reinterpret_cast<const U64x2*>(pa + t); a1[u] = *reinterpret_cast<const U64x2*>(pa + t + poly);
+            b0[u] = *reinterpret_cast<const U64x2*>(pb + t); b1[u] = *reinterpret_cast<const U64x2*>(pb + t + poly);
+        }
+#pragma unroll
+        for (int u = 0; u < kMulSumDepth; ++u) {
+            Lane::term(sa, a0[u].a, a1[u].a, b0[u].a, b1[u].a, lc);
+            Lane::term(sb, a0[u].b, a1[u].b, b0[u].b, b1[u].b, lc);
+        }
+    }
+    for (; k < terms; ++k) {   // the ragged end: fewer than kMulSumDepth terms
+        const size_t t = (size_t)k * 2 * poly;
+        const U64x2 a0 = *reinterpret_cast<const U64x2*>(pa + t), a1 = *reinterpret_cast<const U64x2*>(pa + t + poly);
+        const U64x2 b0 = *reinterpret_cast<const U64x2*>(pb + t), b1 = *reinterpret_cast<const U64x2*>(pb + t + poly);
+        Lane::term(sa, a0.a, a1.a, b0.a, b1.a, lc);
+        Lane::term(sb, a0.b, a1.b, b0.b, b1.b, lc);
+    }
+    U64x2 d0, d1, d2;
+    Lane::finish(sa, lc, d0.a, d1.a, d2.a);
+    Lane::finish(sb, lc, d0.b, d1.b, d2.b);
+    *reinterpret_cast<U64x2*>(po) = d0;
+    *reinterpret_cast<U64x2*>(po + poly) = d1;
+    *reinterpret_cast<U64x2*>(po + 2 * poly) = d2;
 }
 
 }  // namespace dpfhe

@@ -201,6 +201,9 @@ DPF_HD ChunkWork chunk_work(unsigned id, int chunks, Limbs n_limbs) {
 // the grid of a last pass that drops the last data prime as well (relin_rescale_kernel, relin_lincomb_rescale_kernel): chunk_work over the 2 polynomials of
 // every item and the Ld - 1 kept limbs
 constexpr size_t relin_rescale_grid(size_t batch, size_t n_data_limbs, size_t n) { return batch * 2 * (n_data_limbs - 1) * (size_t)chunks_of(n); }
+// the grid of a sum of tensor products (kernels_mul.h tensor3_sum_kernel): chunk_work with the GROUP in the polynomial's place - a workgroup owns one chunk of one
+// limb of all three output rows of its group
+constexpr size_t mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return groups * n_limbs * (size_t)chunks_of(n); }
 
 // ------------------------------------------------------------------------------------------------
 // The last pass of a rotate-and-add step (kernels_rotate.h rotate_add_pass_kernel): outer = (item, data limb), inner = slice of that residue polynomial's

@@ -319,6 +319,32 @@ class Evaluator:
         _cabi.check(self._lib.dpfhe_ct_mul(self.ctx.handle, out.data_ptr(), a.data.data_ptr(), b.data.data_ptr(), a.batch, flags, self._sp(stream)), "dpfhe_ct_mul")
         return Ciphertext(out, out_ntt)
 
+    def multiply_sum(self, a: Ciphertext, b: Ciphertext, terms: int, b_shared: bool = False, out_ntt: bool | None = None, out: torch.Tensor | None = None,
+                     stream=None) -> Ciphertext:
+        """sum_k a[g][k] (x) b[g][k] -> one 3-component item per group, summed BEFORE any relinearisation (dpfhe_ct_mul_sum: one streaming pass over the
+        transformed operands, three inverse transforms per group).  a: groups * terms items, group-major; b: the same, or with b_shared `terms` items that
+        every group reads.  a and b may be the same ciphertext (a sum of squares).  The words of multiply(out_ntt=True) over the pairs, reduce_sum per group
+        and ntt_inverse."""
+        if a.is_ntt != b.is_ntt:
+            raise _cabi.DpfheError(2002, "operands are in different domains (is_ntt mismatch)")
+        if a.size != 2 or b.size != 2:
+            raise _cabi.DpfheError(2000, "multiply_sum expects 2-component ciphertexts")
+        self._chk(a.data, b.data)
+        terms = int(terms)
+        if terms < 1 or a.batch % terms or b.batch != (terms if b_shared else a.batch):
+            raise _cabi.DpfheError(2000, "multiply_sum: a holds groups * terms items, b as many or, shared, terms items")
+        groups = a.batch // terms
+        out_ntt = a.is_ntt if out_ntt is None else bool(out_ntt)
+        if out is None:
+            out = self._empty((groups, 3, self.ctx.params.n_limbs, self.ctx.params.n), stream)
+        self._chk(out)
+        if out.numel() != groups * 3 * self.ctx.params.words_per_rns_poly():
+            raise _cabi.DpfheError(2000, "multiply_sum: out holds groups items of 3 components")
+        flags = (_cabi.IN_NTT if a.is_ntt else 0) | (_cabi.OUT_NTT if out_ntt else 0)
+        _cabi.check(self._lib.dpfhe_ct_mul_sum(self.ctx.handle, out.data_ptr(), a.data.data_ptr(), b.data.data_ptr(), groups, terms, 1 if b_shared else groups, flags,
+                                               self._sp(stream)), "dpfhe_ct_mul_sum")
+        return Ciphertext(out, out_ntt)
+
     def matvec_scalar(self, w: torch.Tensor, x: Ciphertext, out: torch.Tensor | None = None, stream=None) -> Ciphertext:
         """y_i = sum_j w_ij * x_j with scalar weights w: [rows][cols][L] residues (either domain)."""
         p = self.ctx.params

@@ -266,6 +266,10 @@ public:
     void dyadic_multiply_add(const PolyBuffer& a, const PolyBuffer& b, PolyBuffer& acc, Stream* stream = nullptr) const;
     // A6: the metric op.  out must be a 3-component ciphertext of the same batch; its domain flag selects OUT_NTT.
     void multiply(const Ciphertext& a, const Ciphertext& b, Ciphertext& out, Stream* stream = nullptr) const;
+    // A sum of products before any relinearisation (dpfhe_ct_mul_sum): out item g = sum_{k < terms} a item g * terms + k (x) b item g * terms + k, or, with
+    // b_shared, b item k for every group (b then holds `terms` items).  a: groups * terms items; out: 3 components, `groups` items, its domain flag selects
+    // OUT_NTT as in multiply.  a and b may be the same object (a sum of squares).  The words of multiply per pair summed with add.
+    void multiply_sum(const Ciphertext& a, const Ciphertext& b, size_t terms, bool b_shared, Ciphertext& out, Stream* stream = nullptr) const;
     // N1: 3 -> 2 components, coefficient domain in and out
     void relinearize(const Ciphertext& in3, const RelinKeys& keys, Ciphertext& out2, Stream* stream = nullptr) const;
     // N1, second half: out = round(in / q_last) at the next level; `out` must have been created on a Context of
@@ -556,6 +560,21 @@ public:
     // Terms: 2 components, coefficient domain.  The stream contract is multiply_rescale_range's: enqueues only, scratch grown only for a larger batch.
     void multiply_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, const ScalarWeights& weights,
                                         const std::vector<LincombTerm>& terms, Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
+    // A SUM of products under one key switch and one rounding (attention's sum_j p_ij v_j, an inner product over several ciphertexts): out item out_first + g =
+    //   round(relinearize(sum_{k < terms} a_{g,k} * b_{g,k}) / q_last)   at the next level,   g < groups,
+    // a_{g,k} = item a_first + g * terms + k of a; b_{g,k} = item b_first + g * terms + k of b or, with b_shared, item b_first + k for every group.  The tensor
+    // products are summed by dpfhe_ct_mul_sum into the object's scratch (3 components per GROUP), then dpfhe_relinearize_rescale_hybrid runs over `groups`
+    // items: `terms` times fewer key products, inverse transforms and roundings than `terms` multiply_rescale_range calls and their additions - and NOT their
+    // words (one rounding instead of `terms`).  Word for word Evaluator::multiply per pair, Evaluator::add over the pairs, relinearize, Evaluator::rescale.  All
+    // pairs of a group must share one scale product s_a s_b; the result has scale s_a s_b / q_last.  a and b may be one buffer (a sum of squares when the ranges
+    // coincide).  The stream contract is multiply_rescale_range's.  INVALID_ARGUMENT for terms == 0.
+    void multiply_sum_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups, size_t terms,
+                                    Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
+    // ... and with multiply_lincomb_rescale_range's second half (the giant-step sum of a Paterson-Stockmeyer evaluation plus scalar terms plus a constant):
+    //   round((w_0 relinearize(sum_k a_{g,k} * b_{g,k}) + sum_j w_{1+j} z_j,g + constant) / q_last);   addend j = items addends[j].first + g of *addends[j].ct.
+    void multiply_sum_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups, size_t terms,
+                                            const ScalarWeights& weights, const std::vector<LincombTerm>& addends, Ciphertext& out_next_level, size_t out_first,
+                                            Stream* stream = nullptr) const;
     // many rotations in one pass (dpfhe_rotate_hybrid_batch): out item out_first + i = sigma_{elts[i]} of in item i, or of THE
     // item of `in` when it holds one.  All elements must have been added; the keys of a given element list are packed
     // back to back once and cached.
@@ -976,6 +995,53 @@ public:
     // scale(K).  Enqueues only; the scratch (v at the lower levels, the products, the iterates) belongs to the object and grows only for a larger T than
     // before; one apply() at a time per object and per key switcher.
     void apply(const Ciphertext& v, const Ciphertext& y0, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxProductSum: slot-wise y_g = sum_{k < K} a_{g,k} b_{g,k} in the approximate family, K = terms, under ONE key switch and ONE rescale per group
+// (HybridKeySwitcher::multiply_sum_rescale_range: the tensor product is bilinear, so the K products are summed as 3-component ciphertexts in the NTT domain
+// before anything else happens to them).  The attention mix out_i = sum_j p_ij v_j (a = the weights, each replicated over its ciphertext's slots; b = the
+// values, shared by all queries), a sum of squares or an inner product over several ciphertexts, a giant-step sum.  One level; relinearisation keys only.
+//
+// Scales.  Every a at a_scale, every b at b_scale;  output_scale() = (a_scale * b_scale) / (double)q_last  in exactly these double operations, q_last the
+//   last prime of ks's data context.
+//
+// Error bound.  ApproxPolynomial's notation and tools T1 - T4: u = 2^-53, H = (N + 1) / 2 (T3), Ld the data limbs, rho = max_j q_j / P, Kr = 21 Ld N rho (T4),
+//   q = q_last, S = output_scale().  A = max|a|, B = max|b|, Ba and Bb the coefficient errors of the phases of a and b.  The phase of a_k has slot
+//   a_scale a_k + d_a with |d_a| <= D_a = N Ba (T1), that of b_k  b_scale b_k + d_b, |d_b| <= D_b = N Bb.  Term by term:
+//   - K product-noise terms.  A tensor product multiplies phases, so slots multiply (T2): (a_scale a_k + d_a)(b_scale b_k + d_b) is off a_scale b_scale a_k b_k
+//     by at most a_scale A D_b + b_scale B D_a + D_a D_b, and the K products add up exactly (sums of ciphertexts add phases): K times that.
+//   - one key switch: Kr + H per coefficient after its division by P, N (Kr + H) in a slot (T1) - ONCE, where K separate products pay it K times.
+//   - one rescale: the division by q divides all of the above and adds H per coefficient, N H in a slot - once, not K times.
+//   - S as a double is off the real a_scale b_scale / q by at most 4 u S (two roundings and the conversion of q), which misreads the sum by 4 u S K A B:
+//     E = (K (a_scale A D_b + b_scale B D_a + D_a D_b) + N (Kr + H)) / q + N H + 4 u S K A B;    pre = E / S.
+//   The client's decode adds u8 N (K A B + pre), u8 = 8 log2(N) u; the float64 sum the bound is stated against is off the real one by at most
+//   F = 2 K u K A B (K products and K - 1 additions, (1 + u)^K - 1 <= 2 K u).
+//   error_bound(A, B, Ba, Bb) = pre + u8 N (K A B + pre) + F bounds |decoded slot - sum_k a_k b_k| (the float64 sum of the values encrypted, k ascending) for every
+//   slot and group, PROVIDED no phase wraps (the phase before the rescale is about a_scale b_scale K A B).  Worst case throughout.
+class ApproxProductSum {
+public:
+    // ks: the key switcher of the level the operands live on (at least two data limbs); it must outlive the object.  INVALID_ARGUMENT for terms == 0 or a scale
+    // that is not finite and positive.
+    ApproxProductSum(HybridKeySwitcher& ks, size_t terms, bool b_shared, double a_scale, double b_scale);
+    ~ApproxProductSum();
+    ApproxProductSum(const ApproxProductSum&) = delete;
+    ApproxProductSum& operator=(const ApproxProductSum&) = delete;
+    size_t terms() const;
+    bool b_shared() const;
+    double output_scale() const;   // (a_scale * b_scale) / (double)q_last
+    // the bound derived above: max_abs_a = A, max_abs_b = B, a_noise_bound = Ba, b_noise_bound = Bb
+    double error_bound(double max_abs_a, double max_abs_b, double a_noise_bound, double b_noise_bound) const;
+    // ... and without a device: data_moduli are the operands' limbs (at least 2), special_prime the key switcher's P
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t terms, double a_scale, double b_scale,
+                              double max_abs_a, double max_abs_b, double a_noise_bound, double b_noise_bound);
+    // y: G items on ks's data context without its last limb (2 components), scale output_scale(); a: G * terms items on ks's data context, group-major (2
+    // components, coefficient domain, scale a_scale); b: as many at b_scale or, shared, `terms` items every group reads.  Enqueues only; the scratch is the key
+    // switcher's (multiply_sum_rescale_range); one apply() at a time per key switcher.
+    void apply(const Ciphertext& a, const Ciphertext& b, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:
     class Impl;

@@ -161,6 +161,26 @@ int dpfhe_multiply_plain(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, c
 int dpfhe_ct_mul(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t batch,
                  uint32_t flags, void* stream);
 
+/* -- a SUM of tensor products, one relinearisation later (attention's sum_j p_ij (.) v_j, inner products over several ciphertexts, the giant-step sum of a
+ * Paterson-Stockmeyer evaluation): the tensor product is bilinear, so K products are summed BEFORE the key switch, the inverse transforms and the rounding.
+ *   d_a2: [groups][terms][2][L][N];  d_b2: [b_groups][terms][2][L][N], b_groups = groups, or 1: every group reads the same `terms` items (shared);
+ *   d_out3: [groups][3][L][N],  d_out3[g] = sum_{k < terms} a[g][k] (x) b[g][k]   with (x) dpfhe_ct_mul's (a0 b0, a0 b1 + a1 b0, a1 b1) in R_q.
+ * flags: dpfhe_ct_mul's DPFHE_IN_NTT / DPFHE_OUT_NTT; 0 = coefficient domain in and out.  The words are those of the sum taken mod every q_l, however it is
+ * taken; with terms = 1 they are dpfhe_ct_mul's.  Every log2_n (8 ... 16) and limb class.
+ * Aliasing: the operands are read-only and may alias each other in any way (d_a2 == d_b2 with b_groups == groups is a sum of squares and transforms once);
+ * d_out3 must not overlap either operand.
+ * Always composed: batched forward transforms of the operands into the arena of the caller's stream (see "Conventions" - here at EVERY log2_n; a shared d_b2
+ * is transformed once), one streaming pass, three inverse transforms per group.  Scratch: what the transformed operands take, in slices that honour
+ * dpfhe_ctx_set_scratch_limit - whole groups first; when one group does not fit, that group in ranges of terms that accumulate into d_out3 in the NTT domain,
+ * its inverse transforms after the last range.  With DPFHE_IN_NTT there is no scratch at all (DPFHE_OUT_NTT only skips the inverse transforms, in place).
+ * Enqueues only; allocates only when the stream's arena grows.
+ * Algorithmic traffic of the streaming pass per group and limb, in rows of N words: 4 terms + 3 (2 terms + 3 and the shared 2 terms rows once, when shared),
+ * against 10 terms + 3 for dpfhe_ct_mul(DPFHE_OUT_NTT) over the pairs, dpfhe_reduce_sum and dpfhe_ntt_inv: that composition writes and re-reads 3 terms rows.
+ * DPFHE_INVALID_ARGUMENT, before the device is touched: a null or misaligned (16 bytes) buffer, terms == 0, b_groups not in {1, groups}, an unknown flag, d_out3
+ * overlapping an operand, groups * terms too large for one launch.  groups == 0 returns success. */
+int dpfhe_ct_mul_sum(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t groups, size_t terms, size_t b_groups, uint32_t flags,
+                     void* stream);
+
 /* diagnostics (tools/ctmul_trace.py): the "quad" form of dpfhe_ct_mul(flags = 0) with timestamps - thread 0 of workgroup w (= pair w / L, limb w % L)
  * writes d_trace[12 w .. 12 w + 11]: s_memrealtime (100 MHz) at start / first operand word arrived / forward transforms done / tensor
  * product done / inverse transforms done / stores issued / stores drained, then HW_ID | XCC_ID << 32, then prologue done / first operand's
