@@ -268,6 +268,13 @@ inline bool inverse_mod(uint64_t t, uint64_t q, uint64_t& inv) {
     return true;
 }
 
+// g^-1 mod 2N by Newton iteration (g odd): x <- x (2 - g x)
+inline unsigned galois_inverse(unsigned g, unsigned two_n) {
+    unsigned inv = 1;
+    for (int i = 0; i < 5; ++i) inv *= 2u - g * inv;
+    return inv & (two_n - 1u);
+}
+
 // ---- launches one family borrows from another: arguments validated, device selected by the caller ------------------------------------------------------------
 // batched transform of `items` RNS polynomials over the first `limbs_used` limbs (limbs_used = 0: all)
 int ntt_launch_items(dpfhe_ctx* c, bool inverse, uint64_t* out, const uint64_t* in, size_t items, size_t limbs_used, hipStream_t s);   // cabi_poly.hip

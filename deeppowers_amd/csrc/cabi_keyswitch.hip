@@ -262,20 +262,47 @@ extern "C" int dpfhe_rescale_bsgs(dpfhe_ctx* c, uint64_t* d_out2, const uint64_t
 
 // ------------------------------------------------------------------------------------------------
 // the fused rescales of the approximate family's activations (fused_rescale.h; kernels in kernels_keyswitch.h)
-// what a host twin has no context to take from: every limb's constants and the rescale constants of limbs [0, last) relative to limb `last`
-static void host_limb_consts(const uint64_t* moduli, uint32_t n_limbs, std::vector<LimbConst>& lc, bool& fold) {
-    lc.assign(n_limbs, LimbConst{});
-    fold = true;
-    for (uint32_t l = 0; l < n_limbs; ++l) {
-        lc[l] = limb_const_of_modulus(moduli[l]);
-        fold = fold && fold_eligible(moduli[l]);
+// what a host twin has no context to take from: every limb's constants, which arithmetic they allow, and the rescale constants of the limbs below the
+// last one relative to it (rc_last) and - two_levels - of those below the one before it relative to that (rc_prev)
+struct HostRing {
+    std::vector<LimbConst> lc;
+    std::vector<RescaleConst> rc_last, rc_prev;
+    bool fold = true;
+    int build(const char* what, const uint64_t* moduli, uint32_t n_limbs, bool two_levels) {
+        lc.assign(n_limbs, LimbConst{});
+        for (uint32_t l = 0; l < n_limbs; ++l) {
+            lc[l] = limb_const_of_modulus(moduli[l]);
+            fold = fold && fold_eligible(moduli[l]);
+        }
+        bool coprime = true;
+        auto inv = [&](u64 a, u64 q) { uint64_t r = 0; coprime = inverse_mod(a, q, r) && coprime; return r; };
+        rc_last.assign(n_limbs - 1, RescaleConst{});
+        fill_rescale_consts(rc_last.data(), moduli, n_limbs - 1, inv);
+        if (coprime && two_levels) {
+            rc_prev.assign(n_limbs - 2, RescaleConst{});
+            fill_rescale_consts(rc_prev.data(), moduli, n_limbs - 2, inv);
+        }
+        return coprime ? (int)DPFHE_SUCCESS : fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be pairwise coprime");
     }
+};
+// f(FoldArith{} or ShoupArith{}): the twin runs in the arithmetic a context on these moduli would launch with (cabi.h with_ctx_arith)
+template <class Fn>
+static void with_host_arith(bool fold, Fn f) { fold ? f(FoldArith{}) : f(ShoupArith{}); }
+
+// p: [rows][row_limbs][n], of which the first read_limbs limbs of every row are read: each word below its limb's modulus
+static int canonical_rows(const char* what, const uint64_t* p, size_t rows, size_t row_limbs, size_t read_limbs, const uint64_t* moduli, size_t n,
+                          const char* detail = "words must be canonical residues") {
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t l = 0; l < read_limbs; ++l)
+            for (size_t k = 0; k < n; ++k)
+                if (p[(r * row_limbs + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, detail);
+    return DPFHE_SUCCESS;
 }
-static int host_rescale_consts(const char* what, const uint64_t* moduli, size_t last, std::vector<RescaleConst>& rc) {
-    rc.assign(last, RescaleConst{});
-    bool coprime = true;
-    fill_rescale_consts(rc.data(), moduli, last, [&](u64 a, u64 q) { uint64_t inv = 0; coprime = inverse_mod(a, q, inv) && coprime; return inv; });
-    return coprime ? (int)DPFHE_SUCCESS : fail(DPFHE_INVALID_ARGUMENT, what, "moduli must be pairwise coprime");
+// ... of the product's components 0 and 1 (in3: [batch][3][Ld][n])
+static int canonical_c0_c1(const char* what, const uint64_t* in3, size_t batch, size_t Ld, const uint64_t* moduli, size_t n) {
+    for (size_t b = 0; b < batch; ++b)
+        if (int rc = canonical_rows(what, in3 + b * 3 * Ld * n, 2, Ld, Ld, moduli, n)) return rc;
+    return DPFHE_SUCCESS;
 }
 
 extern "C" int dpfhe_relinearize_rescale_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp,
@@ -287,20 +314,13 @@ extern "C" int dpfhe_relinearize_rescale_pass_host(const uint64_t* moduli, uint3
     const size_t n = (size_t)1 << log2_n, L = n_limbs, Ld = L - 1;
     if (overlaps(out, batch * 2 * (Ld - 1) * n, work_qp, batch * 2 * L * n) || overlaps(out, batch * 2 * (Ld - 1) * n, in3, batch * 3 * Ld * n))
         return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
-    for (size_t p = 0; p < 2 * batch; ++p)
-        for (size_t l = 0; l < L; ++l)
-            for (size_t k = 0; k < n; ++k) {
-                if (work_qp[(p * L + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-                if (l < Ld && in3[(((p >> 1) * 3 + (p & 1)) * Ld + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-            }
-    std::vector<LimbConst> lc;
-    std::vector<RescaleConst> rcp, rcq;
-    bool fold;
-    host_limb_consts(moduli, n_limbs, lc, fold);
-    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
-    if (int rc = host_rescale_consts(what, moduli, L - 2, rcq)) return rc;
-    if (fold) relin_rescale_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
-    else relin_rescale_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, batch);
+    if (int rc = canonical_rows(what, work_qp, 2 * batch, L, L, moduli, n)) return rc;
+    if (int rc = canonical_c0_c1(what, in3, batch, Ld, moduli, n)) return rc;
+    HostRing r;
+    if (int rc = r.build(what, moduli, n_limbs, true)) return rc;
+    with_host_arith(r.fold, [&](auto arith) {
+        relin_rescale_pass_host<decltype(arith)>(n, L, r.lc.data(), r.rc_last.data(), r.rc_prev.data(), out, work_qp, in3, batch);
+    });
     return DPFHE_SUCCESS;
 }
 
@@ -315,22 +335,12 @@ extern "C" int dpfhe_rotate_add_pass_host(const uint64_t* moduli, uint32_t n_lim
     if (!(galois_elt & 1u) || galois_elt >= 2 * n) return fail(DPFHE_INVALID_ARGUMENT, what, "galois_elt must be odd and < 2N");
     if (overlaps(out, batch * 2 * Ld * n, work_qp, batch * 2 * L * n) || overlaps(out, batch * 2 * Ld * n, in2, batch * 2 * Ld * n))
         return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
-    for (size_t p = 0; p < 2 * batch; ++p)
-        for (size_t l = 0; l < L; ++l)
-            for (size_t k = 0; k < n; ++k) {
-                if (work_qp[(p * L + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-                if (l < Ld && in2[(p * Ld + l) * n + k] >= moduli[l]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-            }
-    std::vector<LimbConst> lc;
-    std::vector<RescaleConst> rcp;
-    bool fold;
-    host_limb_consts(moduli, n_limbs, lc, fold);
-    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
-    unsigned g_inv = 1;   // g^-1 mod 2N by Newton iteration (g odd)
-    for (int i = 0; i < 5; ++i) g_inv *= 2u - galois_elt * g_inv;
-    g_inv &= 2u * (unsigned)n - 1u;
-    if (fold) rotate_add_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), out, work_qp, in2, g_inv, batch);
-    else rotate_add_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), out, work_qp, in2, g_inv, batch);
+    if (int rc = canonical_rows(what, work_qp, 2 * batch, L, L, moduli, n)) return rc;
+    if (int rc = canonical_rows(what, in2, 2 * batch, Ld, Ld, moduli, n)) return rc;
+    HostRing r;
+    if (int rc = r.build(what, moduli, n_limbs, false)) return rc;
+    const unsigned g_inv = galois_inverse(galois_elt, 2u * (unsigned)n);
+    with_host_arith(r.fold, [&](auto arith) { rotate_add_pass_host<decltype(arith)>(n, L, r.lc.data(), r.rc_last.data(), out, work_qp, in2, g_inv, batch); });
     return DPFHE_SUCCESS;
 }
 
@@ -370,18 +380,11 @@ extern "C" int dpfhe_lincomb_rescale_host(const uint64_t* moduli, uint32_t n_lim
     if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
     if (int rc = lincomb_args(what, out, x, w, n_terms, batch, n_limbs, log2_n)) return rc;
     const size_t n = (size_t)1 << log2_n, L = n_limbs;
-    for (size_t i = 0; i < n_terms * batch * 2 * L; ++i)
-        for (size_t k = 0; k < n; ++k)
-            if (x[i * n + k] >= moduli[i % L]) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-    for (size_t i = 0; i < (n_terms + 1) * L; ++i)
-        if (w[i] >= moduli[i % L]) return fail(DPFHE_INVALID_ARGUMENT, what, "weights must be canonical residues");
-    std::vector<LimbConst> lc;
-    std::vector<RescaleConst> rc;
-    bool fold;
-    host_limb_consts(moduli, n_limbs, lc, fold);
-    if (int e = host_rescale_consts(what, moduli, L - 1, rc)) return e;
-    if (fold) lincomb_rescale_host<FoldArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
-    else lincomb_rescale_host<ShoupArith>(n, L, lc.data(), rc.data(), out, x, w, n_terms, batch);
+    if (int rc = canonical_rows(what, x, n_terms * batch * 2, L, L, moduli, n)) return rc;
+    if (int rc = canonical_rows(what, w, n_terms + 1, L, L, moduli, 1, "weights must be canonical residues")) return rc;
+    HostRing r;
+    if (int rc = r.build(what, moduli, n_limbs, false)) return rc;
+    with_host_arith(r.fold, [&](auto arith) { lincomb_rescale_host<decltype(arith)>(n, L, r.lc.data(), r.rc_last.data(), out, x, w, n_terms, batch); });
     return DPFHE_SUCCESS;
 }
 
@@ -445,25 +448,15 @@ extern "C" int dpfhe_relinearize_lincomb_rescale_pass_host(const uint64_t* modul
     const size_t n = (size_t)1 << log2_n, L = n_limbs, Ld = L - 1;
     if (int rc = relin_lincomb_args(what, out, in3, terms, term_limbs, n_terms, w, batch, Ld, n)) return rc;
     if (overlaps(out, batch * 2 * (Ld - 1) * n, work_qp, batch * 2 * L * n)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an input");
-    for (size_t p = 0; p < 2 * batch; ++p)
-        for (size_t l = 0; l < L; ++l)
-            for (size_t k = 0; k < n; ++k) {
-                bool ok = work_qp[(p * L + l) * n + k] < moduli[l];
-                if (l < Ld) {   // of a term, as of the device entry, only the first Ld limbs are read
-                    ok = ok && in3[(((p >> 1) * 3 + (p & 1)) * Ld + l) * n + k] < moduli[l];
-                    for (size_t t = 0; t < n_terms; ++t) ok = ok && terms[t][(p * term_limbs[t] + l) * n + k] < moduli[l];
-                }
-                if (!ok) return fail(DPFHE_INVALID_ARGUMENT, what, "words must be canonical residues");
-            }
-    for (size_t i = 0; i < (n_terms + 2) * Ld; ++i)
-        if (w[i] >= moduli[i % Ld]) return fail(DPFHE_INVALID_ARGUMENT, what, "weights must be canonical residues");
-    std::vector<LimbConst> lc;
-    std::vector<RescaleConst> rcp, rcq;
-    bool fold;
-    host_limb_consts(moduli, n_limbs, lc, fold);
-    if (int rc = host_rescale_consts(what, moduli, L - 1, rcp)) return rc;
-    if (int rc = host_rescale_consts(what, moduli, L - 2, rcq)) return rc;
-    if (fold) relin_lincomb_rescale_pass_host<FoldArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, terms, term_limbs, n_terms, w, batch);
-    else relin_lincomb_rescale_pass_host<ShoupArith>(n, L, lc.data(), rcp.data(), rcq.data(), out, work_qp, in3, terms, term_limbs, n_terms, w, batch);
+    if (int rc = canonical_rows(what, work_qp, 2 * batch, L, L, moduli, n)) return rc;
+    if (int rc = canonical_c0_c1(what, in3, batch, Ld, moduli, n)) return rc;
+    for (size_t t = 0; t < n_terms; ++t)   // of a term, as of the device entry, only the first Ld limbs are read
+        if (int rc = canonical_rows(what, terms[t], 2 * batch, term_limbs[t], Ld, moduli, n)) return rc;
+    if (int rc = canonical_rows(what, w, n_terms + 2, Ld, Ld, moduli, 1, "weights must be canonical residues")) return rc;
+    HostRing r;
+    if (int rc = r.build(what, moduli, n_limbs, true)) return rc;
+    with_host_arith(r.fold, [&](auto arith) {
+        relin_lincomb_rescale_pass_host<decltype(arith)>(n, L, r.lc.data(), r.rc_last.data(), r.rc_prev.data(), out, work_qp, in3, terms, term_limbs, n_terms, w, batch);
+    });
     return DPFHE_SUCCESS;
 }

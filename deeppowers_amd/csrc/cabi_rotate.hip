@@ -14,12 +14,6 @@ static void launch_galois_multi(hipStream_t s, unsigned grid, u64* out, const u6
         hipLaunchKernelGGL(galois_multi_kernel<false>, dim3(grid), dim3(256), 0, s, out, in, in_item_stride, lc, n_limbs, n, polys_per_item, inv, in_mod, item0, out_item_stride);
 }
 
-static unsigned galois_inverse(unsigned g, unsigned two_n) {  // g^-1 mod 2N by Newton iteration (g odd): x <- x (2 - g x)
-    unsigned inv = 1;
-    for (int i = 0; i < 5; ++i) inv *= 2u - g * inv;
-    return inv & (two_n - 1u);
-}
-
 // the inverses of `cnt` output items' elements from `first` on, `div` consecutive items sharing an element: what galois_multi_kernel takes
 static GaloisInvs galois_inverses(const uint32_t* galois_elts, size_t first, size_t cnt, size_t div, unsigned two_n) {
     GaloisInvs inv{};

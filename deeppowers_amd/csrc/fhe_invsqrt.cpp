@@ -107,16 +107,11 @@ double ApproxInvSqrt::error_bound(uint32_t log2_n, const std::vector<uint64_t>& 
     if (depth == 0 || (depth & 1)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxInvSqrt::error_bound: two special primes per iteration");
     if (L0 < depth + 1) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxInvSqrt::error_bound: the input level needs 2 K + 1 limbs");
     if (!(V >= 0) || !(Y >= 0) || !(Bv >= 0) || !(By >= 0)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxInvSqrt::error_bound: magnitudes and noise bounds must be non-negative");
-    const double N = std::ldexp(1.0, (int)log2_n), H = (N + 1) / 2, u = std::ldexp(1.0, -53), u8 = 8.0 * log2_n * u;
-    std::vector<uint64_t> drop;
-    std::vector<double> Kr;
-    for (size_t r = 0; r < depth; ++r) {
-        const size_t Lr = L0 - r;
-        uint64_t qmax = 0;
-        for (size_t j = 0; j < Lr; ++j) qmax = std::max(qmax, data_moduli[j]);
-        drop.push_back(data_moduli[Lr - 1]);
-        Kr.push_back(21.0 * (double)Lr * N * ((double)qmax / (double)special_primes[r]));
-    }
+    const BoundUnits bu(log2_n);
+    const double N = bu.N, H = bu.H, u = bu.u, u8 = bu.u8;
+    const LevelLadder ladder = level_ladder(data_moduli, special_primes, N);
+    const std::vector<uint64_t>& drop = ladder.drop;
+    const std::vector<double>& Kr = ladder.K;
     std::vector<double> s;
     const std::vector<StepScales> st = step_scales(drop, v_scale, guess_scale, s);
     const double Dv = N * Bv, Y2 = Y * Y, Y3 = Y2 * Y;
@@ -147,15 +142,12 @@ void ApproxInvSqrt::apply(const Ciphertext& v, const Ciphertext& y0, Ciphertext&
     if (!on_level0(v) || !on_level0(y0) || y.size() != 2 || y.batch() != T || y.words() != T * I.ct_words(2 * K))
         throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxInvSqrt::apply: v and y0 are T 2-component coefficient-domain ciphertexts on the input context, y T on out_ctx");
     if (T == 0) return;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const size_t n_ring = I.ctx[0]->params().n();
     const Ciphertext* yn = &y0;
     for (size_t n = 0; n < K; ++n) {
         const Ciphertext* vn = &v;
         if (n) {   // v at level 2 n: the first limbs of every polynomial (the ciphertext and its scale do not change)
             Ciphertext& vd = grow_scratch(I.v_at[n], T, [&](size_t m) { return new Ciphertext(*I.ctx[2 * n], 2, m); });
-            const size_t src_row = I.ctx[0]->params().n_limbs() * n_ring * 8, dst_row = I.ctx[2 * n]->params().n_limbs() * n_ring * 8;
-            hip_check(hipMemcpy2DAsync(vd.data(), dst_row, v.data(), src_row, dst_row, 2 * T, hipMemcpyDeviceToDevice, hs), "hipMemcpy2DAsync D2D");
+            keep_first_limbs(vd.data(), *I.ctx[2 * n], v.data(), *I.ctx[0], 2 * T, stream);
             vn = &vd;
         }
         Ciphertext& ab = grow_scratch(I.ab[n], 2 * T, [&](size_t m) { return new Ciphertext(*I.ctx[2 * n + 1], 2, m); });

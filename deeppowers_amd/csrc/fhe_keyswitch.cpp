@@ -11,6 +11,22 @@ namespace fhe {
 
 using namespace detail;
 
+namespace {
+
+// One product step, behind the four multiply_*_rescale_range methods: the tensor products of groups x terms pairs summed per group, ONE key switch per group
+// and a last pass that rescales - with `weights`, after combining with their addends and constant.  The single product (`sum` false: terms = 1, b not
+// shared) keeps dpfhe_ct_mul, whose fused kernel dpfhe_ct_mul_sum does not run.  `what` and the wording `sum` picks are the public method's own.
+struct ProductStep {
+    const char* what;
+    bool sum;
+    size_t groups, terms;
+    bool b_shared;
+    const ScalarWeights* weights;                 // null: relinearise and rescale, nothing combined
+    const std::vector<LincombTerm>* addends;      // one per weight
+};
+
+}  // namespace
+
 // ---- HybridKeySwitcher ---------------------------------------------------------------------------------------------------
 class __attribute__((visibility("hidden"))) HybridKeySwitcher::Impl {   // (hidden like the Sampler it holds)
 public:
@@ -67,6 +83,55 @@ public:
     void ensure_digits(size_t polys) { grow_scratch(scratch_digits, polys, [&](size_t b) { return new PolyBuffer(*ext, b, 1, true); }); }
     Sampler rng;
     uint64_t p_special = 0;
+
+    void product_step(const ProductStep& st, const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, Ciphertext& out, size_t out_first, Stream* s) {
+        const std::string what = st.what;
+        const FheParams& pd = data_ctx->params();
+        const size_t Ld = pd.n_limbs(), n = pd.n(), in_words = 2 * Ld * n, out_words = 2 * (Ld - 1) * n, groups = st.groups;
+        if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, what + ": no data limb left to drop");
+        if (st.terms == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": at least one term");
+        const size_t a_count = groups * st.terms, b_count = st.b_shared ? st.terms : a_count;
+        if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+            a_first + a_count > a.batch() || b_first + b_count > b.batch())
+            throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": 2-component coefficient-domain ciphertexts on the data context, " +
+                                                             (st.sum ? "groups * terms items of a, as many or (shared) terms items of b" : "ranges inside them"));
+        if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + groups > out.batch())
+            throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for " +
+                                                             (st.sum ? "one item per group" : "the range"));
+        const uint64_t* ptrs[15] = {};   // the addends where they live, and how many limbs their contexts have (ScalarWeights holds at most 15)
+        uint32_t limbs[15] = {};
+        if (st.weights) {
+            const std::string noun = st.sum ? "addend" : "term", a_noun = st.sum ? "an addend" : "a term";
+            const FheParams& pw = st.weights->context().params();
+            if (st.weights->terms() != st.addends->size() || pw.log2_n != pd.log2_n || pw.moduli != pd.moduli || st.weights->context().device_id() != data_ctx->device_id())
+                throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": weights built on the data context, one per " + noun);
+            for (size_t k = 0; k < st.addends->size(); ++k) {
+                const LincombTerm& t = (*st.addends)[k];
+                if (!t.ct) throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": null " + noun);
+                const FheParams& pz = t.ct->context().params();
+                const size_t Lz = pz.n_limbs();
+                if (t.ct->is_ntt() || t.ct->size() != 2 || pz.log2_n != pd.log2_n || Lz < Ld || !std::equal(pd.moduli.begin(), pd.moduli.end(), pz.moduli.begin()) ||
+                    t.ct->words() != t.ct->batch() * 2 * Lz * n || t.first + groups > t.ct->batch() || t.ct->context().device_id() != data_ctx->device_id())
+                    throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": " + a_noun + " is 2 components, coefficient domain, on a context whose first limbs are the data context's, range inside it");
+                ptrs[k] = t.ct->data() + t.first * 2 * Lz * n;
+                limbs[k] = (uint32_t)Lz;
+            }
+        }
+        if (groups == 0) return;
+        grow_scratch(scratch_product, groups, [&](size_t m) { return new Ciphertext(*data_ctx, 3, m); });
+        grow_scratch(scratch_work, groups, [&](size_t m) { return new PolyBuffer(*ext, m, 2, false); });
+        const uint64_t *pa = a.data() + a_first * in_words, *pb = b.data() + b_first * in_words;
+        if (st.sum) check(dpfhe_ct_mul_sum(handle_of(*data_ctx), scratch_product->data(), pa, pb, groups, st.terms, st.b_shared ? 1 : groups, 0, s), "dpfhe_ct_mul_sum");
+        else check(dpfhe_ct_mul(handle_of(*data_ctx), scratch_product->data(), pa, pb, groups, 0, s), "dpfhe_ct_mul");
+        uint64_t* po = out.data() + out_first * out_words;
+        if (st.weights)
+            check(dpfhe_relinearize_lincomb_rescale_hybrid(handle_of(*ext), po, scratch_product->data(), relin->data(), scratch_work->data(), ptrs, limbs, st.addends->size(),
+                                                           st.weights->data(), groups, s),
+                  "dpfhe_relinearize_lincomb_rescale_hybrid");
+        else
+            check(dpfhe_relinearize_rescale_hybrid(handle_of(*ext), po, scratch_product->data(), relin->data(), scratch_work->data(), groups, s), "dpfhe_relinearize_rescale_hybrid");
+        out.set_ntt(false);
+    }
 
     // target (NTT domain on ext, all limbs) scaled by P limb-wise: P mod q_i for data limbs, 0 for the P limb
     void make_key(const uint64_t* d_target_ntt_ext, PolyBuffer& out) {
@@ -214,24 +279,7 @@ void HybridKeySwitcher::multiply_rescale(const Ciphertext& a, const Ciphertext& 
 
 void HybridKeySwitcher::multiply_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, Ciphertext& out,
                                                size_t out_first, Stream* s) const {
-    const FheParams& pe = impl_->ext->params();
-    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), in_words = 2 * Ld * n;
-    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, "HybridKeySwitcher::multiply_rescale: no data limb left to drop");
-    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
-        a_first + count > a.batch() || b_first + count > b.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: 2-component coefficient-domain ciphertexts on the data context, ranges inside them");
-    const size_t out_words = 2 * (Ld - 1) * n;
-    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + count > out.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: output must live on the next-level context (Ld - 1 limbs), 2 components, with room for the range");
-    if (count == 0) return;
-    grow_scratch(impl_->scratch_product, count, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
-    grow_scratch(impl_->scratch_work, count, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
-    check(dpfhe_ct_mul(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, count, 0, s),
-          "dpfhe_ct_mul");
-    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
-                                           impl_->scratch_work->data(), count, s),
-          "dpfhe_relinearize_rescale_hybrid");
-    out.set_ntt(false);
+    impl_->product_step({"HybridKeySwitcher::multiply_rescale", false, count, 1, false, nullptr, nullptr}, a, a_first, b, b_first, out, out_first, s);
 }
 
 // ---- ScalarWeights ---------------------------------------------------------------------------------------------------------
@@ -254,16 +302,7 @@ ScalarWeights::ScalarWeights(const Context& data_ctx, int64_t product_weight, co
     const int64_t lim = (int64_t)1 << 62;
     for (int64_t v : rows)
         if (v <= -lim || v >= lim) throw Exception(ErrorCode::INVALID_ARGUMENT, "ScalarWeights: a weight |w| reaches 2^62");
-    std::vector<uint64_t> w(rows.size() * Ld);
-    for (size_t row = 0; row < rows.size(); ++row) {
-        const int64_t v = rows[row];
-        for (size_t l = 0; l < Ld; ++l) {
-            const uint64_t q = p.moduli[l];
-            uint64_t m = (uint64_t)(v < 0 ? -v : v) % q;
-            if (row == K + 1) m = (uint64_t)((u128)m * (p.moduli.back() % q) % q);   // the constant row: constant_at_output * q_last
-            w[row * Ld + l] = (v < 0 && m) ? q - m : m;
-        }
-    }
+    const std::vector<uint64_t> w = signed_weight_rows(p, rows, K + 1);   // the constant row: constant_at_output * q_last
     impl_->ctx = &data_ctx;
     impl_->K = K;
     impl_->d_w = device_alloc<uint64_t>(data_ctx.device_id(), w.size());
@@ -276,115 +315,19 @@ const uint64_t* ScalarWeights::data() const { return impl_->d_w; }
 
 void HybridKeySwitcher::multiply_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t count, const ScalarWeights& weights,
                                                        const std::vector<LincombTerm>& terms, Ciphertext& out, size_t out_first, Stream* s) const {
-    static const char* what = "HybridKeySwitcher::multiply_lincomb_rescale";
-    const FheParams& pe = impl_->ext->params();
-    const FheParams& pd = impl_->data_ctx->params();
-    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), in_words = 2 * Ld * n;
-    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, std::string(what) + ": no data limb left to drop");
-    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
-        a_first + count > a.batch() || b_first + count > b.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": 2-component coefficient-domain ciphertexts on the data context, ranges inside them");
-    const size_t out_words = 2 * (Ld - 1) * n;
-    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + count > out.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for the range");
-    const FheParams& pw = weights.context().params();
-    if (weights.terms() != terms.size() || pw.log2_n != pd.log2_n || pw.moduli != pd.moduli || weights.context().device_id() != impl_->data_ctx->device_id())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": weights built on the data context, one per term");
-    const uint64_t* ptrs[15] = {};
-    uint32_t limbs[15] = {};
-    for (size_t k = 0; k < terms.size(); ++k) {
-        const Ciphertext* z = terms[k].ct;
-        if (!z) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": null term");
-        const FheParams& pz = z->context().params();
-        const size_t Lz = pz.n_limbs();
-        if (z->is_ntt() || z->size() != 2 || pz.log2_n != pd.log2_n || Lz < Ld || !std::equal(pd.moduli.begin(), pd.moduli.end(), pz.moduli.begin()) ||
-            z->words() != z->batch() * 2 * Lz * n || terms[k].first + count > z->batch() || z->context().device_id() != impl_->data_ctx->device_id())
-            throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": a term is 2 components, coefficient domain, on a context whose first limbs are the data context's, range inside it");
-        ptrs[k] = z->data() + terms[k].first * 2 * Lz * n;
-        limbs[k] = (uint32_t)Lz;
-    }
-    if (count == 0) return;
-    grow_scratch(impl_->scratch_product, count, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
-    grow_scratch(impl_->scratch_work, count, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
-    check(dpfhe_ct_mul(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, count, 0, s),
-          "dpfhe_ct_mul");
-    check(dpfhe_relinearize_lincomb_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
-                                                   impl_->scratch_work->data(), ptrs, limbs, terms.size(), weights.data(), count, s),
-          "dpfhe_relinearize_lincomb_rescale_hybrid");
-    out.set_ntt(false);
+    impl_->product_step({"HybridKeySwitcher::multiply_lincomb_rescale", false, count, 1, false, &weights, &terms}, a, a_first, b, b_first, out, out_first, s);
 }
 
 // ---- sums of products: the tensor products summed by dpfhe_ct_mul_sum into the object's scratch, ONE key switch and one rounding per group ----------------
-namespace {
-
-// the operand and output ranges of a product sum; returns the product's word counts through the references
-void check_product_sum(const char* what, const FheParams& pe, const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups,
-                       size_t terms, const Ciphertext& out, size_t out_first, size_t& in_words, size_t& out_words) {
-    const size_t Ld = pe.n_limbs() - 1, n = pe.n();
-    in_words = 2 * Ld * n;
-    out_words = 2 * (Ld - 1) * n;
-    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, std::string(what) + ": no data limb left to drop");
-    if (terms == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": at least one term");
-    const size_t a_count = groups * terms, b_count = b_shared ? terms : a_count;
-    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
-        a_first + a_count > a.batch() || b_first + b_count > b.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": 2-component coefficient-domain ciphertexts on the data context, groups * terms items of a, as many or (shared) terms items of b");
-    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + groups > out.batch())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for one item per group");
-}
-
-}  // namespace
-
 void HybridKeySwitcher::multiply_sum_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups, size_t terms,
                                                    Ciphertext& out, size_t out_first, Stream* s) const {
-    size_t in_words, out_words;
-    check_product_sum("HybridKeySwitcher::multiply_sum_rescale", impl_->ext->params(), a, a_first, b, b_first, b_shared, groups, terms, out, out_first, in_words, out_words);
-    if (groups == 0) return;
-    grow_scratch(impl_->scratch_product, groups, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
-    grow_scratch(impl_->scratch_work, groups, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
-    check(dpfhe_ct_mul_sum(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, groups, terms,
-                           b_shared ? 1 : groups, 0, s),
-          "dpfhe_ct_mul_sum");
-    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
-                                           impl_->scratch_work->data(), groups, s),
-          "dpfhe_relinearize_rescale_hybrid");
-    out.set_ntt(false);
+    impl_->product_step({"HybridKeySwitcher::multiply_sum_rescale", true, groups, terms, b_shared, nullptr, nullptr}, a, a_first, b, b_first, out, out_first, s);
 }
 
 void HybridKeySwitcher::multiply_sum_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups,
                                                            size_t terms, const ScalarWeights& weights, const std::vector<LincombTerm>& addends, Ciphertext& out,
                                                            size_t out_first, Stream* s) const {
-    static const char* what = "HybridKeySwitcher::multiply_sum_lincomb_rescale";
-    size_t in_words, out_words;
-    check_product_sum(what, impl_->ext->params(), a, a_first, b, b_first, b_shared, groups, terms, out, out_first, in_words, out_words);
-    const FheParams& pd = impl_->data_ctx->params();
-    const size_t Ld = pd.n_limbs(), n = pd.n();
-    const FheParams& pw = weights.context().params();
-    if (weights.terms() != addends.size() || pw.log2_n != pd.log2_n || pw.moduli != pd.moduli || weights.context().device_id() != impl_->data_ctx->device_id())
-        throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": weights built on the data context, one per addend");
-    const uint64_t* ptrs[15] = {};
-    uint32_t limbs[15] = {};
-    for (size_t k = 0; k < addends.size(); ++k) {   // (multiply_lincomb_rescale_range's rules, one item per group)
-        const Ciphertext* z = addends[k].ct;
-        if (!z) throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": null addend");
-        const FheParams& pz = z->context().params();
-        const size_t Lz = pz.n_limbs();
-        if (z->is_ntt() || z->size() != 2 || pz.log2_n != pd.log2_n || Lz < Ld || !std::equal(pd.moduli.begin(), pd.moduli.end(), pz.moduli.begin()) ||
-            z->words() != z->batch() * 2 * Lz * n || addends[k].first + groups > z->batch() || z->context().device_id() != impl_->data_ctx->device_id())
-            throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": an addend is 2 components, coefficient domain, on a context whose first limbs are the data context's, range inside it");
-        ptrs[k] = z->data() + addends[k].first * 2 * Lz * n;
-        limbs[k] = (uint32_t)Lz;
-    }
-    if (groups == 0) return;
-    grow_scratch(impl_->scratch_product, groups, [&](size_t m) { return new Ciphertext(*impl_->data_ctx, 3, m); });
-    grow_scratch(impl_->scratch_work, groups, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
-    check(dpfhe_ct_mul_sum(handle_of(*impl_->data_ctx), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, groups, terms,
-                           b_shared ? 1 : groups, 0, s),
-          "dpfhe_ct_mul_sum");
-    check(dpfhe_relinearize_lincomb_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
-                                                   impl_->scratch_work->data(), ptrs, limbs, addends.size(), weights.data(), groups, s),
-          "dpfhe_relinearize_lincomb_rescale_hybrid");
-    out.set_ntt(false);
+    impl_->product_step({"HybridKeySwitcher::multiply_sum_lincomb_rescale", true, groups, terms, b_shared, &weights, &addends}, a, a_first, b, b_first, out, out_first, s);
 }
 
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
@@ -457,12 +400,9 @@ const std::vector<uint32_t>& SlotSum::galois_elements() const { return impl_->el
 
 double SlotSum::error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double scale, double max_abs_input,
                             double input_noise_bound) {
-    const double N = std::ldexp(1.0, (int)log2_n), Ld = (double)data_moduli.size(), B = (double)block;
-    uint64_t qmax = 0;
-    for (uint64_t q : data_moduli) qmax = std::max(qmax, q);
-    const double rho = (double)qmax / (double)special_prime;
-    const double u8 = 8.0 * (double)log2_n * std::ldexp(1.0, -53);
-    const double K = 21.0 * Ld * N * rho, H = (N + 1) / 2;
+    const BoundUnits bu(log2_n);
+    const double N = bu.N, H = bu.H, u8 = bu.u8, B = (double)block;
+    const double K = keyswitch_term((double)data_moduli.size(), N, max_modulus(data_moduli, data_moduli.size()), special_prime);
     const double pre = N * (B * input_noise_bound + (B - 1) * (K + H)) / scale;
     return pre + u8 * N * (B * max_abs_input + pre);
 }

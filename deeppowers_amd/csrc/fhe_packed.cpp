@@ -459,10 +459,10 @@ size_t ApproxPackedLinear::row_of_slot(size_t output_ciphertext, size_t slot) co
 double ApproxPackedLinear::error_bound(double max_abs_input, double input_noise_bound) const {
     const Impl& I = *impl_;
     const FheParams& p = I.ctx->params();
-    const double N = (double)p.n(), Ld = (double)p.n_limbs(), two = I.tpc == 2 ? std::sqrt(2.0) : 1.0;
-    const double u8 = 8.0 * (double)p.log2_n * std::ldexp(1.0, -53);
+    const BoundUnits bu(p.log2_n);
+    const double N = bu.N, H = bu.H, u8 = bu.u8, two = I.tpc == 2 ? std::sqrt(2.0) : 1.0;
     const double Dx = I.x_scale, Dw = I.w_scale, Do = output_scale();
-    const double K = 21.0 * Ld * N * I.rho, H = (N + 1) / 2;
+    const double K = keyswitch_term((double)p.n_limbs(), N, I.rho);
     const double X = max_abs_input * two, B = I.b_max * two, n = (double)I.n, n2 = (double)I.n2;
     const double G = N * (0.5 + u8 * Dw * I.w_max);                 // a diagonal's slot, off its weight
     const double S = N * input_noise_bound + N * K;                 // a baby step's slot, off Dx x

@@ -93,17 +93,9 @@ ApproxPolynomial::ApproxPolynomial(const std::vector<HybridKeySwitcher*>& levels
         if (!(std::fabs(v) < std::ldexp(1.0, 62))) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPolynomial: a weight |c_k| reaches 2^62 (lower output_scale or the coefficient)");
         I.c[k] = std::llround(v);
     }
-    const size_t L = ps.n_limbs();
-    std::vector<uint64_t> w((I.d + 1) * L);
-    for (size_t row = 0; row <= I.d; ++row) {
-        const int64_t v = I.c[row < I.d ? row + 1 : 0];
-        for (size_t l = 0; l < L; ++l) {
-            const uint64_t q = ps.moduli[l];
-            uint64_t m = (uint64_t)(v < 0 ? -v : v) % q;
-            if (row == I.d) m = (uint64_t)((unsigned __int128)m * (ps.moduli.back() % q) % q);   // the constant row: c_0 = llround(a_0 S) q*
-            w[row * L + l] = (v < 0 && m) ? q - m : m;
-        }
-    }
+    std::vector<int64_t> rows(I.c.begin() + 1, I.c.end());   // c_1 .. c_d, then the constant row: c_0 = llround(a_0 S) q*
+    rows.push_back(I.c[0]);
+    const std::vector<uint64_t> w = signed_weight_rows(ps, rows, I.d);
     I.d_w = device_alloc<uint64_t>(sum_ctx.device_id(), w.size());
     hip_check(hipMemcpy(I.d_w, w.data(), w.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
     I.lvl.resize(I.rstar + 1); I.op_a.resize(I.rstar + 1); I.op_b.resize(I.rstar + 1);
@@ -127,16 +119,11 @@ double ApproxPolynomial::error_bound(uint32_t log2_n, const std::vector<uint64_t
     check_shape(coeffs, special_primes.size(), input_scale, output_scale);
     const size_t d = coeffs.size() - 1, rstar = special_primes.size(), L0 = data_moduli.size();
     if (L0 < rstar + 2) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPolynomial::error_bound: the input level needs ceil(log2 degree) + 2 limbs");
-    const double N = std::ldexp(1.0, (int)log2_n), H = (N + 1) / 2, u = std::ldexp(1.0, -53), u8 = 8.0 * log2_n * u;
-    std::vector<uint64_t> drop;
-    std::vector<double> K;   // K_r of level r + 1
-    for (size_t r = 0; r < rstar; ++r) {
-        const size_t Lr = L0 - r;
-        uint64_t qmax = 0;
-        for (size_t j = 0; j < Lr; ++j) qmax = std::max(qmax, data_moduli[j]);
-        drop.push_back(data_moduli[Lr - 1]);
-        K.push_back(21.0 * (double)Lr * N * ((double)qmax / (double)special_primes[r]));
-    }
+    const BoundUnits bu(log2_n);
+    const double N = bu.N, H = bu.H, u = bu.u, u8 = bu.u8;
+    const LevelLadder ladder = level_ladder(data_moduli, special_primes, N);
+    const std::vector<uint64_t>& drop = ladder.drop;
+    const std::vector<double>& K = ladder.K;   // K_r of level r + 1
     const std::vector<double> s = power_scales(d, input_scale, drop);
     std::vector<double> D(d + 1, 0.0), Xp(d + 1, 1.0);
     for (size_t k = 1; k <= d; ++k) Xp[k] = Xp[k - 1] * X;
@@ -168,7 +155,6 @@ void ApproxPolynomial::apply(const Ciphertext& x, Ciphertext& y, Stream* stream)
         y.words() != T * 2 * I.out->params().n_limbs() * I.out->params().n())
         throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPolynomial::apply: T 2-component coefficient-domain ciphertexts on the input context in, T on out_ctx out");
     if (T == 0) return;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     grow_scratch(I.terms, d * T, [&](size_t m) { return new Ciphertext(*I.ctx[rstar], 2, m); });
     // where the T items of power k live (its own depth), and a copy of them to `dst` at depth `to` (<= its own limbs: the first limbs of every polynomial)
     auto depth_of = [&](size_t k) { return ceil_log2(k); };
@@ -178,10 +164,7 @@ void ApproxPolynomial::apply(const Ciphertext& x, Ciphertext& y, Stream* stream)
         if (r == rstar) return I.terms->data() + (k - 1) * T * I.ct_words(rstar);
         return I.lvl[r]->data() + (k - I.first_power(r)) * T * I.ct_words(r);
     };
-    auto drop_to = [&](uint64_t* dst, size_t to, size_t k) {
-        const size_t n = I.ctx[0]->params().n(), src_row = I.ctx[depth_of(k)]->params().n_limbs() * n * 8, dst_row = I.ctx[to]->params().n_limbs() * n * 8;
-        hip_check(hipMemcpy2DAsync(dst, dst_row, power(k), src_row, dst_row, 2 * T, hipMemcpyDeviceToDevice, hs), "hipMemcpy2DAsync D2D");
-    };
+    auto drop_to = [&](uint64_t* dst, size_t to, size_t k) { keep_first_limbs(dst, *I.ctx[to], power(k), *I.ctx[depth_of(k)], 2 * T, stream); };
     for (size_t r = 1; r <= rstar; ++r) {
         const size_t first = I.first_power(r), count = I.last_power(r) - first + 1, half = (size_t)1 << (r - 1);
         Ciphertext* out = r == rstar ? I.terms.get() : &grow_scratch(I.lvl[r], count * T, [&](size_t m) { return new Ciphertext(*I.ctx[r], 2, m); });

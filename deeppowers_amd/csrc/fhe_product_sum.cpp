@@ -40,11 +40,9 @@ double ApproxProductSum::error_bound(uint32_t log2_n, const std::vector<uint64_t
                                      double A, double B, double Ba, double Bb) {
     if (data_moduli.size() < 2 || !special_prime || terms == 0) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxProductSum::error_bound: two data limbs, a special prime, one term at least");
     if (!(A >= 0) || !(B >= 0) || !(Ba >= 0) || !(Bb >= 0)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxProductSum::error_bound: magnitudes and noise bounds must be non-negative");
-    const double N = std::ldexp(1.0, (int)log2_n), Ld = (double)data_moduli.size(), K = (double)terms;
-    const double u = std::ldexp(1.0, -53), u8 = 8.0 * (double)log2_n * u, H = (N + 1) / 2;
-    uint64_t qmax = 0;
-    for (uint64_t q : data_moduli) qmax = std::max(qmax, q);
-    const double Kr = 21.0 * Ld * N * ((double)qmax / (double)special_prime), q = (double)data_moduli.back();
+    const BoundUnits bu(log2_n);
+    const double N = bu.N, H = bu.H, u = bu.u, u8 = bu.u8, K = (double)terms;
+    const double Kr = keyswitch_term((double)data_moduli.size(), N, max_modulus(data_moduli, data_moduli.size()), special_prime), q = (double)data_moduli.back();
     const double S = (a_scale * b_scale) / q, Da = N * Ba, Db = N * Bb, Y = K * A * B;
     const double E = (K * (a_scale * A * Db + b_scale * B * Da + Da * Db) + N * (Kr + H)) / q + N * H + 4 * u * S * Y;
     const double pre = E / S, F = 2 * K * u * Y;

@@ -21,7 +21,7 @@
 // All results are canonical residues, so the words do not depend on how a policy reduces: Arith::kFold picks FoldArith's folds, anything else the
 // generic 128-bit Barrett products, as in every other streaming kernel (cabi.h with_ctx_arith).
 //
-// Shared by the device kernels (kernels_keyswitch.h relin_rescale_kernel, lincomb_rescale_kernel, relin_lincomb_rescale_kernel) and the host twins below
+// Shared by the device kernels (kernels_keyswitch.h: every rescale there, plain or fused, is rescale_word) and the host twins below
 // (dpfhe_relinearize_rescale_pass_host, dpfhe_lincomb_rescale_host, dpfhe_relinearize_lincomb_rescale_pass_host): one statement of the arithmetic.  No HIP in here.
 #pragma once
 #include <stddef.h>

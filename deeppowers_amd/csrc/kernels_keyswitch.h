@@ -16,7 +16,7 @@ namespace dpfhe {
 
 // N1 (second half): rescale / modulus switch to the next level, coefficient domain.
 //   out_i = ((in_i + h) - ((in_last + h) mod q_last)) * q_last^-1   (mod q_i),  h = floor(q_last / 2),  i < L-1
-// i.e. round(x / q_last) of the CRT-composed value, limb by limb (no big integers).  HBM-bound.
+// i.e. round(x / q_last) of the CRT-composed value, limb by limb (no big integers): fused_rescale.h rescale_word.  HBM-bound.
 // (RescaleConst: devtables.h)
 
 // `addend` (optional) is the last step of hybrid key switching: polynomial p = 2*b + comp of the rescaled pair gets
@@ -34,19 +34,7 @@ __global__ __launch_bounds__(256) void rescale_kernel(u64* out, const u64* in, c
     const RescaleConst rc = rcs[limb];
     const U64x2 x = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + limb) * n + w0);
     const U64x2 last = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + Lo) * n + w0);
-    U64x2 r;
-    {
-        const u64 t = csub(last.a + rc.h, rc.q_last);             // (in_last + h) mod q_last
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);   // ... mod q_i
-        const u64 d = sub_mod(add_mod(x.a, rc.h_mod, lc.q), tm, lc.q);
-        r.a = Arith::mul_var(d, rc.inv, lc);
-    }
-    {
-        const u64 t = csub(last.b + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        const u64 d = sub_mod(add_mod(x.b, rc.h_mod, lc.q), tm, lc.q);
-        r.b = Arith::mul_var(d, rc.inv, lc);
-    }
+    U64x2 r{rescale_word<Arith>(x.a, last.a, lc, rc), rescale_word<Arith>(x.b, last.b, lc, rc)};
     if (addend && ((add_mask >> (poly & 1)) & 1)) {
         const size_t ap = (poly >> 1) * (size_t)add_in_comps + (poly & 1);
         const U64x2 ad = *reinterpret_cast<const U64x2*>(addend + (ap * Lo + limb) * n + w0);
@@ -75,17 +63,7 @@ __global__ __launch_bounds__(256) void rescale_bsgs_kernel(u64* out, const u64* 
     const RescaleConst rc = rcs[limb];
     const U64x2 x = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + limb) * n + w0);
     const U64x2 last = *reinterpret_cast<const U64x2*>(in + (poly * n_limbs + Lo) * n + w0);
-    U64x2 r;
-    {
-        const u64 t = csub(last.a + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        r.a = Arith::mul_var(sub_mod(add_mod(x.a, rc.h_mod, lc.q), tm, lc.q), rc.inv, lc);
-    }
-    {
-        const u64 t = csub(last.b + rc.h, rc.q_last);
-        const u64 tm = Arith::kFold ? FoldArith::canon(t, lc) : ShoupArith::mul_var(t, 1, lc);
-        r.b = Arith::mul_var(sub_mod(add_mod(x.b, rc.h_mod, lc.q), tm, lc.q), rc.inv, lc);
-    }
+    U64x2 r{rescale_word<Arith>(x.a, last.a, lc, rc), rescale_word<Arith>(x.b, last.b, lc, rc)};
     const size_t terms = (poly & 1) ? (n_add ? 1 : 0) : n_add;
     const u64* ap = addends + (poly * Lo + limb) * n + w0;
     const size_t astride = batch * 2 * Lo * (size_t)n;
