@@ -223,6 +223,15 @@ static int for_slices(size_t total, size_t per, Fn fn) {
         if (int rc = fn(first, total - first < per ? total - first : per)) return rc;
     return DPFHE_SUCCESS;
 }
+// The limbs of a kernel whose per-limb constants are a kernel ARGUMENT (plain add, noise), in launches of at most `max_per_launch`: fill(l0, count) sets
+// limbs [l0, l0 + count) in the arguments, f() launches them (or runs the host twin); stops at the first non-zero result
+template <class Fill, class Fn>
+static int for_limb_groups(uint32_t n_limbs, uint32_t max_per_launch, Fill fill, Fn f) {
+    return for_slices(n_limbs, max_per_launch, [&](size_t l0, size_t count) {
+        fill((uint32_t)l0, (uint32_t)count);
+        return f();
+    });
+}
 inline size_t slice_items(const dpfhe_ctx* c, size_t batch, size_t scratch_words_per_item) {   // 1 GiB of scratch unless dpfhe_ctx_set_scratch_limit said otherwise
     const size_t fit = c->scratch_limit_words.load(std::memory_order_relaxed) / scratch_words_per_item;
     return fit == 0 ? 1 : (fit < batch ? fit : batch);

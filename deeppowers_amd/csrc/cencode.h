@@ -27,11 +27,9 @@ constexpr double kCencClamp = 4611686018427387904.0;   // 2^62
 
 #if defined(__HIPCC__)
 typedef double cenc_f64x2 __attribute__((ext_vector_type(2)));
-typedef u64 cenc_u64x2 __attribute__((ext_vector_type(2)));
 typedef u32 cenc_u32x4 __attribute__((ext_vector_type(4)));
 #else
 struct alignas(16) cenc_f64x2 { double x, y; };
-struct alignas(16) cenc_u64x2 { u64 x, y; };
 struct alignas(16) cenc_u32x4 { u32 x, y, z, w; };
 #endif
 
@@ -148,14 +146,14 @@ DPF_HD void cenc_store_pair(u64* item_out, size_t j, cenc_f64x2 c0, cenc_f64x2 c
     const size_t n = (size_t)1 << tb.log2n, h = n >> 1;
     const int64_t r0 = cenc_round(c0.x), r1 = cenc_round(c1.x), i0 = cenc_round(c0.y), i1 = cenc_round(c1.y);
     if (plain) {
-        *reinterpret_cast<cenc_u64x2*>(item_out + j) = cenc_u64x2{(u64)r0, (u64)r1};
-        *reinterpret_cast<cenc_u64x2*>(item_out + h + j) = cenc_u64x2{(u64)i0, (u64)i1};
+        *reinterpret_cast<u64x2_t*>(item_out + j) = u64x2_t{(u64)r0, (u64)r1};
+        *reinterpret_cast<u64x2_t*>(item_out + h + j) = u64x2_t{(u64)i0, (u64)i1};
         return;
     }
     for (u32 l = 0; l < tb.n_limbs; ++l) {
         const CencLimb lim = tb.limb[l];
-        *reinterpret_cast<cenc_u64x2*>(item_out + l * n + j) = cenc_u64x2{cenc_lift(r0, lim), cenc_lift(r1, lim)};
-        *reinterpret_cast<cenc_u64x2*>(item_out + l * n + h + j) = cenc_u64x2{cenc_lift(i0, lim), cenc_lift(i1, lim)};
+        *reinterpret_cast<u64x2_t*>(item_out + l * n + j) = u64x2_t{cenc_lift(r0, lim), cenc_lift(r1, lim)};
+        *reinterpret_cast<u64x2_t*>(item_out + l * n + h + j) = u64x2_t{cenc_lift(i0, lim), cenc_lift(i1, lim)};
     }
 }
 // the lane's pairs of the chunk: WHOLE the output rows; otherwise the chunk's words parked in row 0 of the item's output, real parts at words j, imaginary

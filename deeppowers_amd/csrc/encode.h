@@ -106,10 +106,8 @@ DPF_HD u64 enc_lift(u32 a, u32 t, u32 half, const EncLimb& l) {
 // ---- the lane's steps of the LDS kernel between two barriers: k_encode.hip runs them on the device, tools/emulate_encode.cpp lane by lane on the CPU.
 // `a` holds the C = 2^log2c words of the chunk that starts at position `base` (the whole vector when C = N); lane `tid` of T.
 #if defined(__HIPCC__)
-typedef u64 enc_u64x2 __attribute__((ext_vector_type(2)));
 typedef u32 enc_u32x4 __attribute__((ext_vector_type(4)));
 #else
-struct alignas(16) enc_u64x2 { u64 x, y; };
 struct alignas(16) enc_u32x4 { u32 x, y, z, w; };
 #endif
 
@@ -142,13 +140,13 @@ DPF_HD void enc_lane_last_pass(u32* a, u32 tid, u32 T, u32 base, u32 log2c, u32 
 // coefficients k, k + 1 (k even) of one item: the plain words, or their residues on every limb row (16-byte stores)
 DPF_HD void enc_store_pair(u64* item_out, size_t k, u32 a0, u32 a1, bool plain, const EncodeTables& tb) {
     if (plain) {
-        *reinterpret_cast<enc_u64x2*>(item_out + k) = enc_u64x2{a0, a1};
+        *reinterpret_cast<u64x2_t*>(item_out + k) = u64x2_t{a0, a1};
         return;
     }
     const size_t n = (size_t)1 << tb.log2n;
     for (u32 l = 0; l < tb.n_limbs; ++l) {
         const EncLimb lim = tb.limb[l];
-        *reinterpret_cast<enc_u64x2*>(item_out + l * n + k) = enc_u64x2{enc_lift(a0, tb.t, tb.half, lim), enc_lift(a1, tb.t, tb.half, lim)};
+        *reinterpret_cast<u64x2_t*>(item_out + l * n + k) = u64x2_t{enc_lift(a0, tb.t, tb.half, lim), enc_lift(a1, tb.t, tb.half, lim)};
     }
 }
 // the lane's pairs of the chunk: WHOLE the output rows, otherwise the chunk's words parked in row 0 of the item's output
@@ -156,7 +154,7 @@ template <bool WHOLE>
 DPF_HD void enc_lane_store(u64* item_out, const u32* a, u32 tid, u32 T, u32 base, u32 C, bool plain, const EncodeTables& tb) {
     for (u32 p = 2 * tid; p < C; p += 2 * T) {
         if (WHOLE) enc_store_pair(item_out, p, a[p], a[p + 1], plain, tb);
-        else *reinterpret_cast<enc_u64x2*>(item_out + base + p) = enc_u64x2{a[p], a[p + 1]};
+        else *reinterpret_cast<u64x2_t*>(item_out + base + p) = u64x2_t{a[p], a[p + 1]};
     }
 }
 // the second kernel of N = 32768 / 65536: the last R = log2 N - log2c levels on the 2^R words 2^log2c apart of columns k, k + 1 (k even), read from row 0
@@ -165,7 +163,7 @@ DPF_HD void enc_lane_tail(u64* item_out, u32 k, u32 log2c, bool plain, const Enc
     u32 x0[1 << R], x1[1 << R];
 #pragma unroll
     for (int c = 0; c < (1 << R); ++c) {
-        const enc_u64x2 w = *reinterpret_cast<const enc_u64x2*>(item_out + k + ((size_t)c << log2c));
+        const u64x2_t w = *reinterpret_cast<const u64x2_t*>(item_out + k + ((size_t)c << log2c));
         x0[c] = (u32)w.x;
         x1[c] = (u32)w.y;
     }

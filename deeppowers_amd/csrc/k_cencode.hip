@@ -21,10 +21,12 @@ constexpr u32 kCencLdsThreads = 512;    // lanes per slot vector (or chunk) of t
 constexpr u32 kCencDynLdsLog = 12;      // complex words in 64 KiB of dynamic LDS
 constexpr u32 kCencMaxLdsLog = 13;      // complex words in the static 128 KiB array
 constexpr u32 kCencChunkLog = 12;       // chunk of the two-kernel form
+// the second kernel's blocks: one lane per pair of columns of a chunk (spelled with % and / in the kernel, as in k_encode.hip)
+constexpr ItemChunkPlan cenc_tail_plan(size_t items) { return ItemChunkMap::plan(items, 1u << (kCencChunkLog - 1), kCencThreads); }
 
-// block b = item * chunks + chunk, chunks = n >> log2c.  WHOLE (log2c == log2 n): the full transform and the output; otherwise the first log2c levels
-// of the chunk, parked in row 0 of the item's output.  STATIC: complex words of a static LDS array (0: dynamic).  The steps between the barriers are
-// cencode.h's cenc_lane_*.
+// A workgroup per chunk of 2^log2c complex words (workmap.h ItemChunkMap, n >> log2c chunks per item).  WHOLE (log2c == log2 n): the full transform and the
+// output; otherwise the first log2c levels of the chunk, parked in row 0 of the item's output.  STATIC: complex words of a static LDS array (0: dynamic).
+// The steps between the barriers are cencode.h's cenc_lane_*.
 template <bool WHOLE, u32 STATIC>
 __global__ __launch_bounds__(kCencLdsThreads) void cencode_lds_kernel(u64* __restrict__ out, const double* __restrict__ slots, const CencodeTables tb, u32 log2c,
                                                                       double scale, u32 real, u32 plain) {
@@ -32,8 +34,8 @@ __global__ __launch_bounds__(kCencLdsThreads) void cencode_lds_kernel(u64* __res
     __shared__ __attribute__((aligned(16))) cenc_f64x2 static_lds[STATIC ? STATIC : 1];
     cenc_f64x2* a = STATIC ? static_lds : dyn_lds;
     const u32 tid = threadIdx.x, T = blockDim.x, log2h = tb.log2n - 1;
-    const u32 C = 1u << log2c, chunk = blockIdx.x & ((1u << (log2h - log2c)) - 1u), base = chunk << log2c;
-    const size_t item = blockIdx.x >> (log2h - log2c);
+    const u32 C = 1u << log2c, chunk = ItemChunkMap::chunk(blockIdx.x, log2h - log2c), base = chunk << log2c;
+    const size_t item = ItemChunkMap::outer(blockIdx.x, log2h - log2c);
     cenc_lane_first_pass(a, slots + (item << (real ? log2h : tb.log2n)), real != 0, tid, T, base, C, tb);
     __syncthreads();
     u32 lg0 = kCencRadixLog;
@@ -49,8 +51,8 @@ __global__ __launch_bounds__(kCencLdsThreads) void cencode_lds_kernel(u64* __res
 // the last R = log2 n - 12 levels: lane j of an item owns columns 2 j, 2 j + 1 of each of the 2^R chunks
 template <int R>
 __global__ __launch_bounds__(kCencThreads) void cencode_tail_kernel(u64* __restrict__ out, const CencodeTables tb, double scale, u32 plain) {
-    constexpr u32 kBlocksPerItem = (1u << (kCencChunkLog - 1)) / kCencThreads;
-    const u32 k = 2 * ((blockIdx.x % kBlocksPerItem) * kCencThreads + threadIdx.x);
+    constexpr u32 kBlocksPerItem = 1u << cenc_tail_plan(1).log2_chunks;
+    const u32 k = 2 * ItemChunkMap::lane(blockIdx.x % kBlocksPerItem, kCencThreads, threadIdx.x);
     const size_t item = blockIdx.x / kBlocksPerItem;
     cenc_lane_tail<R>(out + item * ((plain ? (size_t)1 : (size_t)tb.n_limbs) << tb.log2n), k, kCencChunkLog, scale, plain != 0, tb);
 }
@@ -62,23 +64,22 @@ static int launch_encode_complex(u64* out, const double* slots, size_t items, do
     const bool whole = log2h <= kCencMaxLdsLog;
     const u32 log2c = whole ? log2h : kCencChunkLog;
     const u32 C = 1u << log2c, threads = (C >> kCencRadixLog) < kCencLdsThreads ? (C >> kCencRadixLog) : kCencLdsThreads;
-    const size_t grid = items << (log2h - log2c);
-    if (grid == 0 || grid > 0x7fffffffu || (grid >> (log2h - log2c)) != items) return -1;
+    const ItemChunkPlan lds = ItemChunkMap::fixed(items, threads, log2h - log2c), tail = cenc_tail_plan(items);
+    if (!lds.ok || (!whole && !tail.ok)) return -1;
     const u32 r = real ? 1u : 0u, p = plain ? 1u : 0u;
     if (whole && log2c > kCencDynLdsLog) {
-        hipLaunchKernelGGL((cencode_lds_kernel<true, 1u << kCencMaxLdsLog>), dim3((unsigned)grid), dim3(threads), 0, s, out, slots, tb, log2c, scale, r, p);
+        hipLaunchKernelGGL((cencode_lds_kernel<true, 1u << kCencMaxLdsLog>), dim3((unsigned)lds.grid), dim3(threads), 0, s, out, slots, tb, log2c, scale, r, p);
         return 0;
     }
     if (whole) {
-        hipLaunchKernelGGL((cencode_lds_kernel<true, 0>), dim3((unsigned)grid), dim3(threads), C * sizeof(cenc_f64x2), s, out, slots, tb, log2c, scale, r, p);
+        hipLaunchKernelGGL((cencode_lds_kernel<true, 0>), dim3((unsigned)lds.grid), dim3(threads), C * sizeof(cenc_f64x2), s, out, slots, tb, log2c, scale, r, p);
         return 0;
     }
-    hipLaunchKernelGGL((cencode_lds_kernel<false, 0>), dim3((unsigned)grid), dim3(threads), C * sizeof(cenc_f64x2), s, out, slots, tb, log2c, 0.0, r, p);
-    const size_t tail_grid = items * ((1u << (kCencChunkLog - 1)) / kCencThreads);
+    hipLaunchKernelGGL((cencode_lds_kernel<false, 0>), dim3((unsigned)lds.grid), dim3(threads), C * sizeof(cenc_f64x2), s, out, slots, tb, log2c, 0.0, r, p);
     if (log2h - kCencChunkLog == 2)
-        hipLaunchKernelGGL(cencode_tail_kernel<2>, dim3((unsigned)tail_grid), dim3(kCencThreads), 0, s, out, tb, scale, p);
+        hipLaunchKernelGGL(cencode_tail_kernel<2>, dim3((unsigned)tail.grid), dim3(kCencThreads), 0, s, out, tb, scale, p);
     else
-        hipLaunchKernelGGL(cencode_tail_kernel<3>, dim3((unsigned)tail_grid), dim3(kCencThreads), 0, s, out, tb, scale, p);
+        hipLaunchKernelGGL(cencode_tail_kernel<3>, dim3((unsigned)tail.grid), dim3(kCencThreads), 0, s, out, tb, scale, p);
     return 0;
 }
 
@@ -208,7 +209,7 @@ extern "C" int dpfhe_encode_complex(dpfhe_cencoder* e, uint64_t* d_out, const do
     if (!cencode_scale(scale, c->log2n, scale_over_n)) return fail(DPFHE_INVALID_ARGUMENT, what, "scale must be finite and positive");
     const bool plain = (flags & DPFHE_ENCODE_PLAIN) != 0, real = (flags & DPFHE_ENCODE_REAL) != 0;
     const size_t n = (size_t)1 << c->log2n;
-    if (items > kMaxGrid / n) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");   // (also keeps every size below in range)
+    if (items > kMaxGrid / n) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");   // (tighter than the launcher's ItemChunkPlan: kept, it keeps every size below in range)
     if (overlaps_bytes(d_out, items * (plain ? 1 : c->n_limbs) * n * 8, d_slots, items * (real ? n / 2 : n) * 8))
         return fail(DPFHE_INVALID_ARGUMENT, what, "out and slots overlap");
     if ((flags & DPFHE_ENCODE_NTT) && !ntt_grid_fits(c, items * c->n_limbs)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");

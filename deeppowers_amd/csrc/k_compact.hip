@@ -3,13 +3,11 @@
 // One lane per pair of coefficients: for each component it reads its pair of every limb row (16-byte loads, each row contiguous across the wave),
 // computes the two switched values in registers and parks them in LDS.  After one barrier the block's bit strings are gathered from LDS into
 // 16-byte chunks: the block's 2 T values of component c are 2 T k_c bits = T k_c / 64 chunks (T >= 128 lanes, so every chunk is whole and
-// starts on a 32-byte boundary of the record), and every global store is one full 16-byte contiguous store.
+// starts on a 32-byte boundary of the record), and every global store is one full 16-byte contiguous store.  Blocks and lanes: workmap.h ItemChunkMap.
 #include "cabi.h"
 #include "compact.h"
 
 namespace dpfhe {
-
-typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
 
 constexpr u32 kCompactThreads = 256;
 
@@ -28,16 +26,16 @@ __device__ __forceinline__ void compact_pair(u64* vals, const u64* __restrict__ 
     vals[2 * tid + 1] = compact_value<NL>(x1, C, a);
 }
 
-// block b = (item << log2_chunks) + chunk;  lane t of the chunk owns coefficients 2 j, 2 j + 1, j = chunk * blockDim.x + t
+// lane j of an item owns coefficients 2 j, 2 j + 1
 template <int NL>
 __global__ __launch_bounds__(kCompactThreads) void compact_kernel(uint8_t* __restrict__ out, const u64* __restrict__ in, const CompactArgs a, u32 log2n,
                                                                   u32 log2_chunks) {
     __shared__ u64 vals[2][2 * kCompactThreads];
     const u32 tid = threadIdx.x, T = blockDim.x;
-    const u32 chunk = blockIdx.x & ((1u << log2_chunks) - 1u);
-    const size_t item = blockIdx.x >> log2_chunks;
+    const ItemChunkWork w = ItemChunkMap::decode(blockIdx.x, log2_chunks);
+    const size_t item = w.outer;
     const size_t poly = (size_t)1 << log2n;
-    const size_t k = 2 * ((size_t)chunk * T + tid);
+    const size_t k = 2 * ItemChunkMap::lane<size_t>(w.chunk, T, tid);
     compact_pair<NL, 0>(vals[0], in, a, item, poly, k, tid);
     compact_pair<NL, 1>(vals[1], in, a, item, poly, k, tid);
     __syncthreads();
@@ -55,21 +53,17 @@ __global__ __launch_bounds__(kCompactThreads) void compact_kernel(uint8_t* __res
             else if (p < 64) { lo |= v << p; hi |= v >> (64 - p); }
             else hi |= v << (p - 64);
         }
-        const size_t off = (c ? ((size_t)a.bits[0] << log2n) / 8 : 0) + (size_t)chunk * T * kb / 4 + 16 * (size_t)mm;
+        const size_t off = (c ? ((size_t)a.bits[0] << log2n) / 8 : 0) + (size_t)w.chunk * T * kb / 4 + 16 * (size_t)mm;
         *reinterpret_cast<u64x2_t*>(rec + off) = u64x2_t{lo, hi};
     }
 }
 
 // device: out = the records of in [batch][2][L][N] (log2n >= 8; out and in 16-byte aligned).  0, or -1 if the grid is too large for one launch.
 static int launch_compact(int log2n, uint8_t* out, const u64* in, size_t batch, const CompactArgs& a, hipStream_t s) {
-    const u32 pairs = 1u << (log2n - 1);                       // lanes per residue polynomial (log2n >= 8: at least two waves)
-    const u32 threads = pairs < kCompactThreads ? pairs : kCompactThreads;
-    u32 log2_chunks = 0;
-    while ((threads << log2_chunks) < pairs) ++log2_chunks;
-    const size_t grid = batch << log2_chunks;
-    if (grid == 0 || grid > 0x7fffffffu || (grid >> log2_chunks) != batch) return -1;
+    const ItemChunkPlan p = ItemChunkMap::plan(batch, 1u << (log2n - 1), kCompactThreads);   // (the kernel's LDS array holds kCompactThreads pairs)
+    if (!p.ok) return -1;
     const bool ok = compact_with_limbs(a.n_limbs, [&](auto nl) {
-        hipLaunchKernelGGL(compact_kernel<decltype(nl)::value>, dim3((unsigned)grid), dim3(threads), 0, s, out, in, a, (u32)log2n, log2_chunks);
+        hipLaunchKernelGGL(compact_kernel<decltype(nl)::value>, dim3((unsigned)p.grid), dim3(p.threads), 0, s, out, in, a, (u32)log2n, p.log2_chunks);
     });
     return ok ? 0 : -1;
 }

@@ -20,16 +20,18 @@ constexpr u32 kEncThreads = 256;      // lanes per workgroup of the second kerne
 constexpr u32 kEncLdsThreads = 512;   // lanes per slot vector (or chunk) of the LDS kernel
 constexpr u32 kEncMaxLdsLog = 14;     // 64 KiB of LDS
 constexpr u32 kEncChunkLog = 13;      // chunk of the two-kernel form
+// the second kernel's blocks: a lane per pair of columns of a chunk (in the kernel with % and /: as mask and shift its butterflies change, profiles/r21_item_chunk_map.txt)
+constexpr ItemChunkPlan enc_tail_plan(size_t items) { return ItemChunkMap::plan(items, 1u << (kEncChunkLog - 1), kEncThreads); }
 
-// block b = item * chunks + chunk, chunks = N >> log2c.  WHOLE (log2c == log2 N): the full transform and the output; otherwise the first log2c levels
-// of the chunk, parked in row 0 of the item's output.  The steps between the barriers are encode.h's enc_lane_*.
+// A workgroup per chunk of 2^log2c words (workmap.h ItemChunkMap, N >> log2c chunks per item).  WHOLE (log2c == log2 N): the full transform and the output;
+// otherwise the first log2c levels of the chunk, parked in row 0 of the item's output.  The steps between the barriers are encode.h's enc_lane_*.
 template <bool WHOLE>
 __global__ __launch_bounds__(kEncLdsThreads) void encode_lds_kernel(u64* __restrict__ out, const u32* __restrict__ slots, const EncodeTables tb, u32 log2c,
                                                                     u32 plain) {
     extern __shared__ __attribute__((aligned(16))) u32 a[];
     const u32 tid = threadIdx.x, T = blockDim.x, log2n = tb.log2n;
-    const u32 C = 1u << log2c, chunk = blockIdx.x & ((1u << (log2n - log2c)) - 1u), base = chunk << log2c;
-    const size_t item = blockIdx.x >> (log2n - log2c);
+    const u32 C = 1u << log2c, chunk = ItemChunkMap::chunk(blockIdx.x, log2n - log2c), base = chunk << log2c;
+    const size_t item = ItemChunkMap::outer(blockIdx.x, log2n - log2c);
     enc_lane_first_pass(a, slots + (item << log2n), tid, T, base, C, tb);
     __syncthreads();
     u32 lg0 = kEncRadixLog;
@@ -45,8 +47,8 @@ __global__ __launch_bounds__(kEncLdsThreads) void encode_lds_kernel(u64* __restr
 // the last R = log2 N - 13 levels: lane j of an item owns coefficients 2 j, 2 j + 1 of each of the 2^R chunks
 template <int R>
 __global__ __launch_bounds__(kEncThreads) void encode_tail_kernel(u64* __restrict__ out, const EncodeTables tb, u32 plain) {
-    constexpr u32 kBlocksPerItem = (1u << (kEncChunkLog - 1)) / kEncThreads;
-    const u32 k = 2 * ((blockIdx.x % kBlocksPerItem) * kEncThreads + threadIdx.x);
+    constexpr u32 kBlocksPerItem = 1u << enc_tail_plan(1).log2_chunks;
+    const u32 k = 2 * ItemChunkMap::lane(blockIdx.x % kBlocksPerItem, kEncThreads, threadIdx.x);
     const size_t item = blockIdx.x / kBlocksPerItem;
     enc_lane_tail<R>(out + item * ((plain ? (size_t)1 : (size_t)tb.n_limbs) << tb.log2n), k, kEncChunkLog, plain != 0, tb);
 }
@@ -57,18 +59,17 @@ static int launch_encode_slots(u64* out, const u32* slots, size_t items, bool pl
     const bool whole = log2n <= kEncMaxLdsLog;
     const u32 log2c = whole ? log2n : kEncChunkLog;
     const u32 C = 1u << log2c, threads = (C >> kEncRadixLog) < kEncLdsThreads ? (C >> kEncRadixLog) : kEncLdsThreads;
-    const size_t grid = items << (log2n - log2c);
-    if (grid == 0 || grid > 0x7fffffffu || (grid >> (log2n - log2c)) != items) return -1;
+    const ItemChunkPlan p = ItemChunkMap::fixed(items, threads, log2n - log2c), tail = enc_tail_plan(items);
+    if (!p.ok || (!whole && !tail.ok)) return -1;
     if (whole) {
-        hipLaunchKernelGGL(encode_lds_kernel<true>, dim3((unsigned)grid), dim3(threads), C * sizeof(u32), s, out, slots, tb, log2c, plain ? 1u : 0u);
+        hipLaunchKernelGGL(encode_lds_kernel<true>, dim3((unsigned)p.grid), dim3(threads), C * sizeof(u32), s, out, slots, tb, log2c, plain ? 1u : 0u);
         return 0;
     }
-    hipLaunchKernelGGL(encode_lds_kernel<false>, dim3((unsigned)grid), dim3(threads), C * sizeof(u32), s, out, slots, tb, log2c, plain ? 1u : 0u);
-    const size_t tail_grid = items * ((1u << (kEncChunkLog - 1)) / kEncThreads);
+    hipLaunchKernelGGL(encode_lds_kernel<false>, dim3((unsigned)p.grid), dim3(threads), C * sizeof(u32), s, out, slots, tb, log2c, plain ? 1u : 0u);
     if (log2n - kEncChunkLog == 2)
-        hipLaunchKernelGGL(encode_tail_kernel<2>, dim3((unsigned)tail_grid), dim3(kEncThreads), 0, s, out, tb, plain ? 1u : 0u);
+        hipLaunchKernelGGL(encode_tail_kernel<2>, dim3((unsigned)tail.grid), dim3(kEncThreads), 0, s, out, tb, plain ? 1u : 0u);
     else
-        hipLaunchKernelGGL(encode_tail_kernel<3>, dim3((unsigned)tail_grid), dim3(kEncThreads), 0, s, out, tb, plain ? 1u : 0u);
+        hipLaunchKernelGGL(encode_tail_kernel<3>, dim3((unsigned)tail.grid), dim3(kEncThreads), 0, s, out, tb, plain ? 1u : 0u);
     return 0;
 }
 
@@ -173,7 +174,7 @@ extern "C" int dpfhe_encode_slots(dpfhe_encoder* e, uint64_t* d_out, const uint3
     dpfhe_ctx* c = e->ctx;
     const bool plain = (flags & DPFHE_ENCODE_PLAIN) != 0;
     const size_t n = (size_t)1 << c->log2n;
-    if (items > kMaxGrid / n) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");   // (also keeps every size below in range)
+    if (items > kMaxGrid / n) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");   // (tighter than the launcher's ItemChunkPlan: kept, it keeps every size below in range)
     if (overlaps_bytes(d_out, items * (plain ? 1 : c->n_limbs) * n * 8, d_slots, items * n * 4)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and slots overlap");
     if ((flags & DPFHE_ENCODE_NTT) && !ntt_grid_fits(c, items * c->n_limbs)) return fail(DPFHE_INVALID_ARGUMENT, what, "too many items for one launch");
     DPFHE_ON_DEVICE(c, what);

@@ -1,9 +1,9 @@
 // k_expand.hip - seeded uniform polynomials (expand.h): the device kernel, its launcher, the host twin and the entries of include/dpfhe.h.
 //
 // One lane per ChaCha20 block: a lane produces 4 coefficients (32 contiguous bytes, two 16-byte stores) and consecutive lanes write
-// consecutive blocks, so the stores coalesce without LDS.  A workgroup covers one (item, limb) range of blocks, so the limb's
-// constants are workgroup-uniform scalar loads; the seed's key words are kernel arguments (SGPRs).  No loads from memory besides
-// the LimbConst: the kernel is VALU-bound (20 ChaCha rounds + four exact 128-bit reductions per lane).
+// consecutive blocks, so the stores coalesce without LDS.  A workgroup covers one (item, limb) range of blocks (workmap.h ItemChunkMap: outer =
+// item x limb, N / 4 lanes), so the limb's constants are workgroup-uniform scalar loads; the seed's key words are kernel arguments (SGPRs).  No loads
+// from memory besides the LimbConst: the kernel is VALU-bound (20 ChaCha rounds + four exact 128-bit reductions per lane).
 #include <cstring>
 
 #include "cabi.h"
@@ -11,16 +11,12 @@
 
 namespace dpfhe {
 
-typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-
-// block b = ((item * L + limb) << log2_chunks) + chunk;  lane t of the chunk computes ChaCha block j = chunk * blockDim.x + t
+// lane j of (item, limb) computes ChaCha block j
 __global__ __launch_bounds__(256) void expand_uniform_kernel(u64* __restrict__ buf, const ExpandKey key, const LimbConst* __restrict__ lc, u32 first_item,
                                                              u32 comp, u32 comps, u32 n_limbs, u32 log2n, u32 log2_chunks) {
-    const u32 blk = blockIdx.x;
-    const u32 chunk = blk & ((1u << log2_chunks) - 1u);
-    const u32 item_limb = blk >> log2_chunks;
-    const u32 limb = item_limb % n_limbs, b = item_limb / n_limbs;
-    const u32 j = chunk * blockDim.x + threadIdx.x;
+    const ItemChunkWork w = ItemChunkMap::decode(blockIdx.x, log2_chunks);
+    const u32 limb = w.outer % n_limbs, b = w.outer / n_limbs;
+    const u32 j = ItemChunkMap::lane(w.chunk, blockDim.x, threadIdx.x);
     const u64 q = lc[limb].q, br_hi = lc[limb].br_hi, br_lo = lc[limb].br_lo;
     u64 v[4];
     expand_block(key, j, first_item + b, limb, comp, q, br_hi, br_lo, v);
@@ -32,14 +28,11 @@ __global__ __launch_bounds__(256) void expand_uniform_kernel(u64* __restrict__ b
 // device: component `comp` of items [0, batch) of buf [batch][comps][L][N] = expand(seed, first_item + b, limb, comp); 0, or -1 if the grid is too large
 static int launch_expand_uniform(int log2n, u64* buf, size_t batch, size_t comps, u32 comp, u32 n_limbs, const LimbConst* lc, const ExpandKey& key, u32 first_item,
                           hipStream_t s) {
-    const u32 blocks_per_poly = 1u << (log2n - 2);                  // ChaCha blocks of one residue polynomial (log2n >= 8: at least one wave)
-    const u32 threads = blocks_per_poly < 256u ? blocks_per_poly : 256u;
-    u32 log2_chunks = 0;
-    while ((threads << log2_chunks) < blocks_per_poly) ++log2_chunks;
-    const size_t grid = (batch * n_limbs) << log2_chunks;
-    if (grid == 0 || grid > 0x7fffffffu || batch > 0xffffffffu) return -1;
-    hipLaunchKernelGGL(expand_uniform_kernel, dim3((unsigned)grid), dim3(threads), 0, s, buf, key, lc, first_item, comp, (u32)comps, n_limbs, (u32)log2n,
-                       log2_chunks);
+    // the ChaCha blocks of one residue polynomial (log2n >= 8: at least one wave); batch <= 2^32 (expand_args), so batch * n_limbs cannot wrap
+    const ItemChunkPlan p = ItemChunkMap::plan(batch * n_limbs, 1u << (log2n - 2), 256u);
+    if (!p.ok) return -1;
+    hipLaunchKernelGGL(expand_uniform_kernel, dim3((unsigned)p.grid), dim3(p.threads), 0, s, buf, key, lc, first_item, comp, (u32)comps, n_limbs, (u32)log2n,
+                       p.log2_chunks);
     return 0;
 }
 

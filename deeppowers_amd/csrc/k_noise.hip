@@ -3,9 +3,8 @@
 //
 // One lane per ChaCha20 block: the block gives two adjacent coefficients, and since the key stream does not depend on the limb the lane decodes them
 // once and walks the limbs, writing one 16-byte store per limb row; consecutive lanes write consecutive 16-byte words, so every wave store covers 1 KiB
-// of one row without LDS.  The limb constants and the seed's key words are kernel arguments (scalar loads, SGPRs).  Without `add` the kernel loads
-// nothing from memory; with it, one 16-byte load per store.
-#include <algorithm>
+// of one row without LDS (workmap.h ItemChunkMap: outer = item, N / 2 lanes).  The limb constants and the seed's key words are kernel arguments (scalar
+// loads, SGPRs).  Without `add` the kernel loads nothing from memory; with it, one 16-byte load per store.
 #include <cstring>
 
 #include "cabi.h"
@@ -13,20 +12,16 @@
 
 namespace dpfhe {
 
-typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
-
-// block b = (item << log2_chunks) + chunk;  lane t of the chunk computes ChaCha block j = chunk * blockDim.x + t, coefficients 2 j and 2 j + 1
+// lane j of an item computes ChaCha block j, coefficients 2 j and 2 j + 1
 template <u32 KIND, bool ADD>
 __global__ __launch_bounds__(256) void sample_noise_kernel(u64* __restrict__ buf, const NoiseArgs a, u32 log2_chunks) {
-    const u32 blk = blockIdx.x;
-    const u32 chunk = blk & ((1u << log2_chunks) - 1u);
-    const u32 b = blk >> log2_chunks;
-    const u32 j = chunk * blockDim.x + threadIdx.x;
+    const ItemChunkWork w = ItemChunkMap::decode(blockIdx.x, log2_chunks);
+    const u32 j = ItemChunkMap::lane(w.chunk, blockDim.x, threadIdx.x);
     NoiseCoeff v0, v1;
-    noise_block<KIND>(a, j, a.first_item + b, v0, v1);
+    noise_block<KIND>(a, j, a.first_item + w.outer, v0, v1);
     const bool wide = a.param >= 128;
     const size_t poly = (size_t)1 << a.log2n;
-    u64* p = buf + (((size_t)b * a.comps + a.comp) * a.ctx_limbs + a.l0) * poly + 2 * (size_t)j;
+    u64* p = buf + (((size_t)w.outer * a.comps + a.comp) * a.ctx_limbs + a.l0) * poly + 2 * (size_t)j;
     for (u32 l = 0; l < a.n_limbs; ++l, p += poly) {
         const NoiseLimb c = a.limb[l];
         u64 r0 = noise_residue<KIND>(v0, c, wide), r1 = noise_residue<KIND>(v1, c, wide);
@@ -40,24 +35,20 @@ __global__ __launch_bounds__(256) void sample_noise_kernel(u64* __restrict__ buf
 }
 
 template <u32 KIND>
-static void launch_kind(u64* buf, const NoiseArgs& a, unsigned grid, unsigned threads, u32 log2_chunks, hipStream_t s) {
-    if (a.add) hipLaunchKernelGGL((sample_noise_kernel<KIND, true>), dim3(grid), dim3(threads), 0, s, buf, a, log2_chunks);
-    else hipLaunchKernelGGL((sample_noise_kernel<KIND, false>), dim3(grid), dim3(threads), 0, s, buf, a, log2_chunks);
+static void launch_kind(u64* buf, const NoiseArgs& a, const ItemChunkPlan& p, hipStream_t s) {
+    if (a.add) hipLaunchKernelGGL((sample_noise_kernel<KIND, true>), dim3((unsigned)p.grid), dim3(p.threads), 0, s, buf, a, p.log2_chunks);
+    else hipLaunchKernelGGL((sample_noise_kernel<KIND, false>), dim3((unsigned)p.grid), dim3(p.threads), 0, s, buf, a, p.log2_chunks);
 }
 
 // device: component a.comp of items [0, batch) of buf [batch][comps][ctx_limbs][N], limbs [a.l0, a.l0 + a.n_limbs): = noise, or += noise mod q with a.add;
 // 0, or -1 if the grid is too large
 static int launch_sample_noise(u64* buf, size_t batch, const NoiseArgs& a, hipStream_t s) {
-    const u32 pairs = 1u << (a.log2n - 1);                     // ChaCha blocks of one polynomial (log2n >= 8: at least two waves)
-    const u32 threads = pairs < 256u ? pairs : 256u;
-    u32 log2_chunks = 0;
-    while ((threads << log2_chunks) < pairs) ++log2_chunks;
-    const size_t grid = batch << log2_chunks;
-    if (grid == 0 || grid > 0x7fffffffu || batch > 0xffffffffu || a.n_limbs == 0 || a.n_limbs > kNoiseLimbs) return -1;
+    const ItemChunkPlan p = ItemChunkMap::pairs(batch, a.log2n);   // a ChaCha block per pair
+    if (!p.ok || a.n_limbs == 0 || a.n_limbs > kNoiseLimbs) return -1;
     switch (a.kind) {
-        case kNoiseTernary: launch_kind<kNoiseTernary>(buf, a, (unsigned)grid, threads, log2_chunks, s); break;
-        case kNoiseCbd21: launch_kind<kNoiseCbd21>(buf, a, (unsigned)grid, threads, log2_chunks, s); break;
-        case kNoiseFlood: launch_kind<kNoiseFlood>(buf, a, (unsigned)grid, threads, log2_chunks, s); break;
+        case kNoiseTernary: launch_kind<kNoiseTernary>(buf, a, p, s); break;
+        case kNoiseCbd21: launch_kind<kNoiseCbd21>(buf, a, p, s); break;
+        case kNoiseFlood: launch_kind<kNoiseFlood>(buf, a, p, s); break;
         default: return -1;
     }
     return 0;
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(256) void add_products_kernel(u64* __restrict__ ct,
 // device: ct [batch][2][L][N] += prod [2][batch][L][N] mod q, word by word (the last step of dpfhe_rerandomize); 0, or -1 if the grid is too large
 static int launch_add_products(u64* ct, const u64* prod, size_t batch, u32 n_limbs, int log2n, const LimbConst* lc, hipStream_t s) {
     const size_t grid = batch * 2 * n_limbs;
-    if (grid == 0 || grid > 0x7fffffffu) return -1;
+    if (grid == 0 || grid > kMaxGrid) return -1;
     hipLaunchKernelGGL(add_products_kernel, dim3((unsigned)grid), dim3(256), 0, s, ct, prod, lc, (u32)batch, n_limbs, (u32)log2n);
     return 0;
 }
@@ -131,22 +122,20 @@ static int noise_args(const char* what, const void* out, size_t batch, size_t co
     return DPFHE_SUCCESS;
 }
 
-// the limbs in launches of at most kNoiseLimbs (their constants are a kernel argument)
+// the limbs in launches of at most kNoiseLimbs (for_limb_groups): f() runs with a's limbs and their constants set
 template <class F>
-static int for_noise_groups(NoiseArgs& a, const uint64_t* moduli, uint32_t n_limbs, F f) {
-    for (uint32_t l0 = 0; l0 < n_limbs; l0 += kNoiseLimbs) {
+static int noise_limb_groups(NoiseArgs& a, const uint64_t* moduli, uint32_t n_limbs, F f) {
+    return for_limb_groups(n_limbs, kNoiseLimbs, [&](uint32_t l0, uint32_t count) {
         a.l0 = l0;
-        a.n_limbs = std::min<uint32_t>(kNoiseLimbs, n_limbs - l0);
-        for (uint32_t l = 0; l < a.n_limbs; ++l) a.limb[l] = noise_limb(moduli[l0 + l], a.kind, a.param);
-        if (int rc = f(a)) return rc;
-    }
-    return DPFHE_SUCCESS;
+        a.n_limbs = count;
+        for (uint32_t l = 0; l < count; ++l) a.limb[l] = noise_limb(moduli[l0 + l], a.kind, a.param);
+    }, f);
 }
 
 // arguments validated, device selected by the caller
 static int noise_launch(const char* what, dpfhe_ctx* c, uint64_t* d_out, size_t batch, NoiseArgs& a, hipStream_t s) {
-    return for_noise_groups(a, c->moduli.data(), c->n_limbs, [&](const NoiseArgs& g) {
-        if (launch_sample_noise(d_out, batch, g, s)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    return noise_limb_groups(a, c->moduli.data(), c->n_limbs, [&] {
+        if (launch_sample_noise(d_out, batch, a, s)) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
         return check_launch("sample_noise kernel launch");
     });
 }
@@ -158,7 +147,7 @@ extern "C" int dpfhe_sample_noise(dpfhe_ctx* c, uint64_t* d_out, size_t batch, s
     NoiseArgs a;
     if (int rc = noise_args(what, d_out, batch, comps, comp, kind, param, stream_id, seed, first_item, flags, c->n_limbs, c->log2n, a)) return rc;
     if (misaligned(d_out)) return fail(DPFHE_INVALID_ARGUMENT, what, "misaligned buffer");
-    if ((batch << (c->log2n - 1)) > kMaxGrid * (size_t)256) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (!ItemChunkMap::pairs(batch, c->log2n).ok) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     DPFHE_ON_DEVICE(c, what);
     return noise_launch(what, c, d_out, batch, a, static_cast<hipStream_t>(stream));
 }
@@ -170,8 +159,8 @@ extern "C" int dpfhe_sample_noise_host(const uint64_t* moduli, uint32_t n_limbs,
     if (int rc = check_host_ring(what, moduli, n_limbs, log2_n)) return rc;
     NoiseArgs a;
     if (int rc = noise_args(what, out, batch, comps, comp, kind, param, stream_id, seed, first_item, flags, n_limbs, log2_n, a)) return rc;
-    return for_noise_groups(a, moduli, n_limbs, [&](const NoiseArgs& g) {
-        sample_noise_host(out, batch, g);
+    return noise_limb_groups(a, moduli, n_limbs, [&] {
+        sample_noise_host(out, batch, a);
         return (int)DPFHE_SUCCESS;
     });
 }
@@ -204,7 +193,7 @@ extern "C" int dpfhe_rerandomize(dpfhe_ctx* c, uint64_t* d_ct2, const uint64_t* 
         return fail(DPFHE_INVALID_ARGUMENT, what, "flood_bits must lie in [1, min(250, floor(log2 Q) - 3)]");
     if (batch > ((uint64_t)1 << 32) - first_item) return fail(DPFHE_INVALID_ARGUMENT, what, "first_item + batch must be <= 2^32");
     const size_t poly = (size_t)c->n_limbs << c->log2n, npolys = batch * c->n_limbs;
-    if (!ntt_grid_fits(c, 2 * npolys) || (batch << (c->log2n - 1)) > kMaxGrid * (size_t)256)
+    if (!ntt_grid_fits(c, 2 * npolys) || !ItemChunkMap::pairs(batch, c->log2n).ok)
         return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     if (overlaps(d_work, 3 * batch * poly, d_ct2, 2 * batch * poly) || overlaps(d_work, 3 * batch * poly, d_pk, 2 * poly) ||
         overlaps(d_ct2, 2 * batch * poly, d_pk, 2 * poly))

@@ -2,8 +2,8 @@
 //
 // One lane per pair of coefficients: it reads its two plaintext words (16 bytes; a broadcast plaintext is read from cache), reduces them mod t once
 // and walks the limbs of component 0 with one 16-byte load and store per limb - each limb row is contiguous across the wave.  Out of place, the same
-// lane copies its pair of every other component.  A one-pass stream: 16 bytes of HBM traffic per c0 word in place.
-// Below it, the plaintext addition on residues (dpfhe_add_plain: the approximate family's bias add) in the same shape.
+// lane copies its pair of every other component.  A one-pass stream: 16 bytes of HBM traffic per c0 word in place.  Blocks and lanes: workmap.h
+// ItemChunkMap::pairs.  Below it, the plaintext addition on residues (dpfhe_add_plain: the approximate family's bias add) in the same shape.
 #include <algorithm>
 #include <vector>
 
@@ -12,45 +12,47 @@
 
 namespace dpfhe {
 
-typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
+// out of place, the lane copies its pair (at `base` in row 0 of component 0) of rows [0, n_limbs) of every other component; components are ctx_limbs rows apart
+__device__ __forceinline__ void copy_other_components(u64* out, const u64* in, size_t base, size_t poly, u32 comps, u32 ctx_limbs, u32 n_limbs) {
+    if (out != in)
+        for (u32 j = 1; j < comps; ++j)
+            for (u32 l = 0; l < n_limbs; ++l) {
+                const size_t off = base + ((size_t)j * ctx_limbs + l) * poly;
+                *reinterpret_cast<u64x2_t*>(out + off) = *reinterpret_cast<const u64x2_t*>(in + off);
+            }
+}
+// the same for the host twins: row `row` of component 0, n words
+static void copy_other_components_host(u64* out, const u64* in, size_t row, size_t n, u32 comps, u32 ctx_limbs) {
+    if (out != in)
+        for (u32 j = 1; j < comps; ++j)
+            for (size_t k = 0; k < n; ++k) out[row + j * ctx_limbs * n + k] = in[row + j * ctx_limbs * n + k];
+}
 
-// block b = (item << log2_chunks) + chunk;  lane t of the chunk owns coefficients 2 j, 2 j + 1, j = chunk * blockDim.x + t
-// (out and in may be the same buffer: no __restrict__ on them)
+// lane j of an item owns coefficients 2 j, 2 j + 1  (out and in may be the same buffer: no __restrict__ on them)
 __global__ __launch_bounds__(256) void add_plain_scaled_kernel(u64* out, const u64* in, const u64* __restrict__ plain, const PlainAddArgs a,
                                                                u32 comps, u32 ctx_limbs, u32 log2n, u32 log2_chunks, u32 group) {
-    const u32 blk = blockIdx.x;
-    const u32 chunk = blk & ((1u << log2_chunks) - 1u);
-    const u32 item = blk >> log2_chunks;
-    const size_t k = 2 * ((size_t)chunk * blockDim.x + threadIdx.x);
-    const u64x2_t b = *reinterpret_cast<const u64x2_t*>(plain + ((size_t)(item / group) << log2n) + k);
+    const ItemChunkWork w = ItemChunkMap::decode(blockIdx.x, log2_chunks);
+    const size_t k = 2 * ItemChunkMap::lane<size_t>(w.chunk, blockDim.x, threadIdx.x);
+    const u64x2_t b = *reinterpret_cast<const u64x2_t*>(plain + ((size_t)(w.outer / group) << log2n) + k);
     const u64 y0 = plain_add_residue(b.x, a), y1 = plain_add_residue(b.y, a);
     const bool hi0 = y0 > a.half, hi1 = y1 > a.half;
     const size_t poly = (size_t)1 << log2n;
-    const size_t base = ((size_t)item * comps * ctx_limbs + a.l0) * poly + k;
+    const size_t base = ((size_t)w.outer * comps * ctx_limbs + a.l0) * poly + k;
     for (u32 l = 0; l < a.n_limbs; ++l) {
         const PlainAddLimb c = a.limb[l];
         const u64x2_t x = *reinterpret_cast<const u64x2_t*>(in + base + l * poly);
         *reinterpret_cast<u64x2_t*>(out + base + l * poly) = u64x2_t{plain_add_limb(x.x, y0, c, hi0), plain_add_limb(x.y, y1, c, hi1)};
     }
-    if (out != in)
-        for (u32 j = 1; j < comps; ++j)
-            for (u32 l = 0; l < a.n_limbs; ++l) {
-                const size_t off = base + ((size_t)j * ctx_limbs + l) * poly;
-                *reinterpret_cast<u64x2_t*>(out + off) = *reinterpret_cast<const u64x2_t*>(in + off);
-            }
+    copy_other_components(out, in, base, poly, comps, ctx_limbs, a.n_limbs);
 }
 
 // device: out[i][0][l0 .. l0 + n_limbs) = in[i][0] + round(Q plain[i / group] / t), out[i][k >= 1] = in[i][k] of those limbs when out != in.
 // 0, or -1 if the grid is too large for one launch.
 static int launch_add_plain_scaled(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 ctx_limbs, size_t group, const PlainAddArgs& a,
                             hipStream_t s) {
-    const u32 pairs = 1u << (log2n - 1);                       // lanes per residue polynomial (log2n >= 8: at least two waves)
-    const u32 threads = pairs < 256u ? pairs : 256u;
-    u32 log2_chunks = 0;
-    while ((threads << log2_chunks) < pairs) ++log2_chunks;
-    const size_t grid = batch << log2_chunks;
-    if (grid == 0 || grid > 0x7fffffffu || group == 0 || group > 0xffffffffu) return -1;
-    hipLaunchKernelGGL(add_plain_scaled_kernel, dim3((unsigned)grid), dim3(threads), 0, s, out, in, plain, a, comps, ctx_limbs, (u32)log2n, log2_chunks,
+    const ItemChunkPlan p = ItemChunkMap::pairs(batch, (unsigned)log2n);
+    if (!p.ok || group == 0 || group > 0xffffffffu) return -1;
+    hipLaunchKernelGGL(add_plain_scaled_kernel, dim3((unsigned)p.grid), dim3(p.threads), 0, s, out, in, plain, a, comps, ctx_limbs, (u32)log2n, p.log2_chunks,
                        (u32)group);
     return 0;
 }
@@ -65,51 +67,38 @@ void add_plain_scaled_host(int log2n, u64* out, const u64* in, const u64* plain,
                 const u64 y = plain_add_residue(b[k], a);
                 out[row + k] = plain_add_limb(in[row + k], y, a.limb[l], y > a.half);
             }
-            if (out != in)
-                for (u32 j = 1; j < comps; ++j)
-                    for (size_t k = 0; k < n; ++k) out[row + j * ctx_limbs * n + k] = in[row + j * ctx_limbs * n + k];
+            copy_other_components_host(out, in, row, n, comps, ctx_limbs);
         }
     }
 }
 
 // ---- plaintext addition on residues: c0 +- p mod q_l, the plaintext [plain_items][L][N] canonical words of the ciphertext's own domain -------------
-// The same blocks and lanes as above; q comes from the context's LimbConst (a scalar load: the limb is uniform over the launch's inner loop), the
+// The same map as above; q comes from the context's LimbConst (a scalar load: the limb is uniform over the launch's inner loop), the
 // plaintext row of a limb is read with one 16-byte load per lane like the c0 row.  In place: 24 bytes of traffic per c0 word, 16 of them HBM when
 // the plaintext is broadcast (it then stays in cache).
 __global__ __launch_bounds__(256) void add_plain_kernel(u64* out, const u64* in, const u64* __restrict__ plain, const LimbConst* __restrict__ lc, u32 comps,
                                                         u32 n_limbs, u32 log2n, u32 log2_chunks, u32 group, u32 negate) {
-    const u32 blk = blockIdx.x;
-    const u32 chunk = blk & ((1u << log2_chunks) - 1u);
-    const u32 item = blk >> log2_chunks;
-    const size_t k = 2 * ((size_t)chunk * blockDim.x + threadIdx.x);
+    const ItemChunkWork w = ItemChunkMap::decode(blockIdx.x, log2_chunks);
+    const size_t k = 2 * ItemChunkMap::lane<size_t>(w.chunk, blockDim.x, threadIdx.x);
     const size_t poly = (size_t)1 << log2n;
-    const size_t base = (size_t)item * comps * n_limbs * poly + k;
-    const size_t pbase = (size_t)(item / group) * n_limbs * poly + k;
+    const size_t base = (size_t)w.outer * comps * n_limbs * poly + k;
+    const size_t pbase = (size_t)(w.outer / group) * n_limbs * poly + k;
     for (u32 l = 0; l < n_limbs; ++l) {
         const u64 q = lc[l].q;
         const u64x2_t x = *reinterpret_cast<const u64x2_t*>(in + base + l * poly);
         const u64x2_t p = *reinterpret_cast<const u64x2_t*>(plain + pbase + l * poly);
         *reinterpret_cast<u64x2_t*>(out + base + l * poly) = u64x2_t{add_plain_word(x.x, p.x, q, negate), add_plain_word(x.y, p.y, q, negate)};
     }
-    if (out != in)
-        for (u32 j = 1; j < comps; ++j)
-            for (u32 l = 0; l < n_limbs; ++l) {
-                const size_t off = base + ((size_t)j * n_limbs + l) * poly;
-                *reinterpret_cast<u64x2_t*>(out + off) = *reinterpret_cast<const u64x2_t*>(in + off);
-            }
+    copy_other_components(out, in, base, poly, comps, n_limbs, n_limbs);
 }
 
 // device: out[i][0] = in[i][0] +- plain[i / group] on every limb, out[i][k >= 1] = in[i][k] when out != in; q_l from lc[l].q.
 // 0, or -1 if the grid is too large for one launch.
 static int launch_add_plain(int log2n, u64* out, const u64* in, const u64* plain, size_t batch, u32 comps, u32 n_limbs, size_t group, bool negate,
                      const LimbConst* lc, hipStream_t s) {
-    const u32 pairs = 1u << (log2n - 1);                       // lanes per residue polynomial (log2n >= 8: at least two waves)
-    const u32 threads = pairs < 256u ? pairs : 256u;
-    u32 log2_chunks = 0;
-    while ((threads << log2_chunks) < pairs) ++log2_chunks;
-    const size_t grid = batch << log2_chunks;
-    if (grid == 0 || grid > 0x7fffffffu || group == 0 || group > 0xffffffffu) return -1;
-    hipLaunchKernelGGL(add_plain_kernel, dim3((unsigned)grid), dim3(threads), 0, s, out, in, plain, lc, comps, n_limbs, (u32)log2n, log2_chunks, (u32)group,
+    const ItemChunkPlan p = ItemChunkMap::pairs(batch, (unsigned)log2n);
+    if (!p.ok || group == 0 || group > 0xffffffffu) return -1;
+    hipLaunchKernelGGL(add_plain_kernel, dim3((unsigned)p.grid), dim3(p.threads), 0, s, out, in, plain, lc, comps, n_limbs, (u32)log2n, p.log2_chunks, (u32)group,
                        negate ? 1u : 0u);
     return 0;
 }
@@ -121,9 +110,7 @@ void add_plain_host(int log2n, const u64* moduli, u32 n_limbs, u64* out, const u
             const u64* p = plain + ((i / group) * n_limbs + l) * n;
             const size_t row = (i * comps * n_limbs + l) * n;
             for (size_t k = 0; k < n; ++k) out[row + k] = add_plain_word(in[row + k], p[k], moduli[l], negate);
-            if (out != in)
-                for (u32 j = 1; j < comps; ++j)
-                    for (size_t k = 0; k < n; ++k) out[row + j * n_limbs * n + k] = in[row + j * n_limbs * n + k];
+            copy_other_components_host(out, in, row, n, comps, n_limbs);
         }
 }
 
@@ -155,16 +142,14 @@ static int plain_add_args(const char* what, const uint64_t* out, const uint64_t*
     return DPFHE_SUCCESS;
 }
 
-// the limbs in launches of at most kPlainAddLimbs (their constants are a kernel argument)
+// the limbs in launches of at most kPlainAddLimbs (for_limb_groups): f() runs with a's limbs and their constants set
 template <class F>
-static int for_limb_groups(PlainAddArgs& a, const std::vector<PlainAddLimb>& limbs, F f) {
-    for (uint32_t l0 = 0; l0 < (uint32_t)limbs.size(); l0 += kPlainAddLimbs) {
+static int plain_add_limb_groups(PlainAddArgs& a, const std::vector<PlainAddLimb>& limbs, F f) {
+    return for_limb_groups((uint32_t)limbs.size(), kPlainAddLimbs, [&](uint32_t l0, uint32_t count) {
         a.l0 = l0;
-        a.n_limbs = std::min<uint32_t>(kPlainAddLimbs, (uint32_t)limbs.size() - l0);
-        std::copy(limbs.begin() + l0, limbs.begin() + l0 + a.n_limbs, a.limb);
-        if (int rc = f(a)) return rc;
-    }
-    return DPFHE_SUCCESS;
+        a.n_limbs = count;
+        std::copy(limbs.begin() + l0, limbs.begin() + l0 + count, a.limb);
+    }, f);
 }
 
 extern "C" int dpfhe_add_plain_scaled(dpfhe_ctx* c, uint64_t* d_out, const uint64_t* d_in, const uint64_t* d_plain, size_t batch, size_t comps,
@@ -180,8 +165,8 @@ extern "C" int dpfhe_add_plain_scaled(dpfhe_ctx* c, uint64_t* d_out, const uint6
     if (batch == 0) return DPFHE_SUCCESS;
     DPFHE_ON_DEVICE(c, what);
     const size_t group = batch / plain_items;
-    return for_limb_groups(a, limbs, [&](const PlainAddArgs& g) {
-        if (launch_add_plain_scaled((int)c->log2n, d_out, d_in, d_plain, batch, (u32)comps, c->n_limbs, group, g, static_cast<hipStream_t>(stream)))
+    return plain_add_limb_groups(a, limbs, [&] {
+        if (launch_add_plain_scaled((int)c->log2n, d_out, d_in, d_plain, batch, (u32)comps, c->n_limbs, group, a, static_cast<hipStream_t>(stream)))
             return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
         return check_launch("add_plain_scaled kernel launch");
     });
@@ -201,8 +186,8 @@ extern "C" int dpfhe_add_plain_scaled_host(const uint64_t* moduli, uint32_t n_li
         if (plain[i] >> 32) return fail(DPFHE_INVALID_ARGUMENT, what, "plaintext words must be < 2^32");
     if (batch == 0) return DPFHE_SUCCESS;
     const size_t group = batch / plain_items;
-    return for_limb_groups(a, limbs, [&](const PlainAddArgs& g) {
-        add_plain_scaled_host((int)log2_n, out, in, plain, batch, (u32)comps, n_limbs, group, g);
+    return plain_add_limb_groups(a, limbs, [&] {
+        add_plain_scaled_host((int)log2_n, out, in, plain, batch, (u32)comps, n_limbs, group, a);
         return (int)DPFHE_SUCCESS;
     });
 }
@@ -214,7 +199,7 @@ static int add_plain_args(const char* what, const uint64_t* out, const uint64_t*
     if (!out || !in || !plain) return fail(DPFHE_INVALID_ARGUMENT, what, "null buffer");
     if (comps != 2 && comps != 3) return fail(DPFHE_INVALID_ARGUMENT, what, "ciphertexts have 2 or 3 components");
     if (batch == 0 || plain_items == 0 || batch % plain_items) return fail(DPFHE_INVALID_ARGUMENT, what, "batch must be a positive multiple of plain_items");
-    if (batch > (kMaxGrid >> (log2n > 9 ? log2n - 9 : 0))) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    if (!ItemChunkMap::pairs(batch, log2n).ok) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
     const size_t poly = (size_t)limbs << log2n, words = batch * comps * poly;
     if (out != in && overlaps(out, words, in, words)) return fail(DPFHE_INVALID_ARGUMENT, what, "out and in overlap without being the same buffer");
     if (overlaps(out, words, plain, plain_items * poly)) return fail(DPFHE_INVALID_ARGUMENT, what, "out overlaps the plaintext");

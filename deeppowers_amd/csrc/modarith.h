@@ -29,6 +29,12 @@ namespace dpfhe {
 
 typedef uint64_t u64;
 typedef uint32_t u32;
+// two adjacent words as one 16-byte load or store (a struct with the same layout in the host builds of the encoders' headers)
+#if defined(__HIPCC__)
+typedef u64 u64x2_t __attribute__((ext_vector_type(2)));
+#else
+struct alignas(16) u64x2_t { u64 x, y; };
+#endif
 
 // tools/emulate.cpp defines DPFHE_EMU_CHECK: host-only counters of broken lazy-arithmetic preconditions
 #if defined(DPFHE_EMU_CHECK) && !defined(__HIPCC__)

@@ -232,4 +232,37 @@ struct RotateAddMap {
     static DPF_HD size_t grid(size_t n_polys, unsigned slices) { return xcd_deal::grid(n_polys, slices); }   // n_polys = items x data limbs
 };
 
+// ------------------------------------------------------------------------------------------------
+// Items in chunks (the byte-stream and encoding families: k_expand, k_noise, k_plain_add, k_compact, k_encode, k_cencode .hip): `outer` items (an item, or an
+// (item, limb)) of `lanes` lanes each, a workgroup = one chunk of `threads` lanes.  id = (outer << log2_chunks) + chunk; thread t of the chunk is lane
+// chunk * threads + t of its outer item.  Powers of two throughout: threads << log2_chunks is the lane count exactly, so no id and no thread is dead.
+// `plan` is the launch AND the "too large for one launch" bound of the entries (constexpr: a kernel with constant geometry takes its log2_chunks from it);
+// the encoders' first kernels choose their chunk themselves (a workgroup walks it): `fixed`, and call `chunk` and `outer` where their statements had the two.
+// ------------------------------------------------------------------------------------------------
+struct ItemChunkWork { unsigned outer, chunk; };
+struct ItemChunkPlan { unsigned threads, log2_chunks; size_t grid; bool ok; };   // ok: an item at least, no overflow of the shift, at most 2^31 - 1 workgroups
+struct ItemChunkMap {
+    static DPF_HD unsigned chunk(unsigned id, unsigned log2_chunks) { return id & ((1u << log2_chunks) - 1u); }
+    static DPF_HD unsigned outer(unsigned id, unsigned log2_chunks) { return id >> log2_chunks; }
+    static DPF_HD ItemChunkWork decode(unsigned id, unsigned log2_chunks) {
+        const unsigned c = chunk(id, log2_chunks);
+        return ItemChunkWork{outer(id, log2_chunks), c};
+    }
+    template <class I = unsigned>   // (the index in the type the kernel computes its offsets in)
+    static DPF_HD I lane(unsigned chunk, unsigned threads, unsigned tid) { return (I)chunk * threads + tid; }
+    static constexpr DPF_HD ItemChunkPlan fixed(size_t outer, unsigned threads, unsigned log2_chunks) {
+        ItemChunkPlan p{threads, log2_chunks, outer << log2_chunks, false};
+        p.ok = outer != 0 && (p.grid >> log2_chunks) == outer && p.grid <= (size_t)0x7fffffffu;
+        return p;
+    }
+    static constexpr DPF_HD ItemChunkPlan plan(size_t outer, unsigned lanes_per_outer, unsigned max_threads) {
+        const unsigned threads = lanes_per_outer < max_threads ? lanes_per_outer : max_threads;
+        unsigned log2_chunks = 0;
+        while ((threads << log2_chunks) < lanes_per_outer) ++log2_chunks;
+        return fixed(outer, threads, log2_chunks);
+    }
+    // one lane per pair of coefficients of a residue polynomial (16 bytes of each limb row), at most 256 lanes per workgroup (log2n >= 8: at least two waves)
+    static DPF_HD ItemChunkPlan pairs(size_t items, unsigned log2n) { return plan(items, 1u << (log2n - 1), 256u); }
+};
+
 }  // namespace dpfhe

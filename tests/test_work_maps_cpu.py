@@ -8,6 +8,8 @@ the same header; tools/emulate_workmap.cpp exports both, so every id of every gr
   there).  The workgroups that share an x tile of a matrix-vector product (one slab, one group of right-hand sides, every row tile) are `groups`
   apart by construction (the group is the fastest index): the same id & 7, and their sorted id >> 3 are an arithmetic progression of step `groups`
   inside their slab's block of consecutive id >> 3 - consecutive themselves with one group;
+* items in chunks (expand, noise, plain add, compact, the two encoders): every THREAD of every id is a lane of an item, the lanes cover items x lanes
+  exactly once, and the plan refuses an empty launch, a shift that wraps and a grid above 2^31 - 1;
 * the Galois position maps are the permutations the kernels' comments say they are, in Python integers.
 
 A layout change starts here."""
@@ -43,6 +45,9 @@ def wm(tmp_path_factory):
         ("wm_qp_pair_map", None, [i, u, u, u, I64]),
         ("wm_chunks_of", i, [z]),
         ("wm_chunk_decode", None, [u, i, i, I64]),
+        ("wm_item_chunk_plan", C.c_uint64, [z, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(i)]),
+        ("wm_item_chunk_fixed", C.c_uint64, [z, u, u, C.POINTER(i)]),
+        ("wm_item_chunk_lanes", None, [u, u, u, I64]),
         ("wm_transform_decode", None, [u, i, i, i, ull, I64]),
         ("wm_galois_src_pos", i, [i, u, I64]),
     ):
@@ -236,6 +241,83 @@ def test_chunk_work(wm, L, chunks):
 
 def test_chunks_of(wm):
     assert [wm.wm_chunks_of(n) for n in (256, 512, 1024, 4096, 8192, 65536)] == [1, 1, 2, 8, 16, 128]
+
+
+# ---- items in chunks: the byte-stream and encoding families ----------------------------------------------------------------------------------------------
+def _item_chunk_plan(wm, outer, lanes, max_threads=256):
+    threads, log2_chunks, ok = C.c_uint(0), C.c_uint(0), C.c_int(0)
+    grid = int(wm.wm_item_chunk_plan(outer, lanes, max_threads, C.byref(threads), C.byref(log2_chunks), C.byref(ok)))
+    return threads.value, log2_chunks.value, grid, bool(ok.value)
+
+
+def _item_chunk_fixed(wm, outer, threads, log2_chunks):
+    ok = C.c_int(0)
+    return int(wm.wm_item_chunk_fixed(outer, threads, log2_chunks, C.byref(ok))), bool(ok.value)
+
+
+def _item_chunk_lanes(wm, grid, log2_chunks, threads):
+    """(outer, lane) of every thread of every id of the grid"""
+    out = np.zeros((grid * threads, 2), dtype=np.int64)
+    wm.wm_item_chunk_lanes(grid, log2_chunks, threads, out.ctypes.data_as(I64))
+    return out
+
+
+def _covers_once(rows, outer, lanes):
+    """the rows (outer, lane) are outer x lanes, each pair exactly once (so no id and no thread is dead)"""
+    assert len(rows) == outer * lanes
+    assert (rows >= 0).all() and (rows[:, 0] < outer).all() and (rows[:, 1] < lanes).all()
+    assert np.array_equal(np.sort(rows[:, 0] * lanes + rows[:, 1]), np.arange(outer * lanes))
+
+
+@pytest.mark.parametrize("log2n,outer", list(itertools.product(range(8, 17), (1, 3, 8, 9))))
+def test_item_chunk_layout(wm, log2n, outer):
+    """N / 2 lanes per item (noise, plain add, compact) and N / 4 per (item, limb) (expand), at most 256 per workgroup"""
+    for lanes in ((1 << log2n) // 2, (1 << log2n) // 4):
+        threads, log2_chunks, grid, ok = _item_chunk_plan(wm, outer, lanes)
+        assert ok and threads << log2_chunks == lanes and grid == outer << log2_chunks
+        assert threads == (256 if log2n >= 10 else lanes) and threads in (64, 128, 256)
+        _covers_once(_item_chunk_lanes(wm, grid, log2_chunks, threads), outer, lanes)
+
+
+# (log2 of the transform's length, log2c): the slot encoder's N words with 64 KiB of LDS, the complex encoder's N / 2 complex words with 128 KiB
+ENCODE_WHOLE = [(v, v) for v in range(8, 15)] + [(v, v) for v in range(7, 14)]
+ENCODE_CHUNKED = [(15, 13), (16, 13), (14, 12), (15, 12)]
+
+
+@pytest.mark.parametrize("log2v,log2c", sorted(set(ENCODE_WHOLE)) + ENCODE_CHUNKED)
+def test_encode_chunk_layout(wm, log2v, log2c):
+    """first kernel: a workgroup per chunk of 2^log2c words, its lanes walking the chunk in groups of 8; second kernel (chunked form): a lane per pair of
+    columns of the chunks, 256 per workgroup"""
+    items, C_, R = 3, 1 << log2c, log2v - log2c
+    threads = min(C_ >> 3, 512)
+    grid, ok = _item_chunk_fixed(wm, items, threads, R)
+    assert ok and grid == items << R
+    first = _item_chunk_lanes(wm, grid, R, 1)                       # (item, chunk): thread 0's lane with one thread per chunk is the chunk itself
+    _covers_once(first, items, 1 << R)
+    words = (first[:, :1] << log2v) + (first[:, 1:] << log2c) + np.arange(C_)   # the chunk's words start at base = chunk << log2c
+    assert np.array_equal(np.sort(words.ravel()), np.arange(items << log2v))
+    if R == 0:
+        return
+    t_threads, t_log2_chunks, t_grid, ok = _item_chunk_plan(wm, items, C_ // 2, 256)
+    assert ok and t_threads == 256 and t_grid == items * (C_ // 2 // 256)
+    tail = _item_chunk_lanes(wm, t_grid, t_log2_chunks, t_threads)
+    _covers_once(tail, items, C_ // 2)
+    # lane j reads and writes positions 2 j, 2 j + 1 of each of the 2^R chunks: over the lanes, every position of the vector exactly once
+    pos = np.concatenate([tail[:, :1] * (1 << log2v) + (c << log2c) + 2 * tail[:, 1:] + h for c in range(1 << R) for h in (0, 1)])
+    assert np.array_equal(np.sort(pos.ravel()), np.arange(items << log2v))
+
+
+def test_item_chunk_bounds(wm):
+    """ok = at least one item, no overflow of the shift, at most 2^31 - 1 workgroups"""
+    assert _item_chunk_plan(wm, 2 ** 31 - 1, 256) == (256, 0, 2 ** 31 - 1, True)
+    assert not _item_chunk_plan(wm, 2 ** 31, 256)[3]                # one chunk: the first grid of 2^31
+    assert _item_chunk_plan(wm, 2 ** 29 - 1, 1024) == (256, 2, 2 ** 31 - 4, True)
+    assert not _item_chunk_plan(wm, 2 ** 29, 1024)[3]               # four chunks: the first grid of 2^31
+    threads, log2_chunks, grid, ok = _item_chunk_plan(wm, 2 ** 62 + 1, 1024)
+    assert (log2_chunks, grid, ok) == (2, 4, False)                 # the shift wraps to a grid of 4: refused
+    assert not _item_chunk_plan(wm, 0, 1024)[3]
+    assert _item_chunk_fixed(wm, 2 ** 28 - 1, 512, 3) == (2 ** 31 - 8, True)
+    assert not _item_chunk_fixed(wm, 2 ** 28, 512, 3)[1] and not _item_chunk_fixed(wm, 2 ** 61 + 1, 512, 3)[1] and not _item_chunk_fixed(wm, 0, 512, 3)[1]
 
 
 def test_transform_block(wm):

@@ -101,6 +101,25 @@ void wm_rotate_add_decode(unsigned n_ids, unsigned slices, size_t n_polys, unsig
     }
 }
 
+// items in chunks: the plan -> grid (threads, log2_chunks, ok through the pointers); the same with the chunk count given (the encoders' first kernels);
+// rows (outer, lane), one per THREAD of every id, in id-major order
+u64 wm_item_chunk_plan(size_t outer, unsigned lanes_per_outer, unsigned max_threads, unsigned* threads, unsigned* log2_chunks, int* ok) {
+    const ItemChunkPlan p = ItemChunkMap::plan(outer, lanes_per_outer, max_threads);
+    *threads = p.threads; *log2_chunks = p.log2_chunks; *ok = p.ok;
+    return p.grid;
+}
+u64 wm_item_chunk_fixed(size_t outer, unsigned threads, unsigned log2_chunks, int* ok) {
+    const ItemChunkPlan p = ItemChunkMap::fixed(outer, threads, log2_chunks);
+    *ok = p.ok;
+    return p.grid;
+}
+void wm_item_chunk_lanes(unsigned n_ids, unsigned log2_chunks, unsigned threads, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const ItemChunkWork w = ItemChunkMap::decode(id, log2_chunks);
+        for (unsigned t = 0; t < threads; ++t, out += 2) { out[0] = w.outer; out[1] = ItemChunkMap::lane<size_t>(w.chunk, threads, t); }
+    }
+}
+
 // batched transforms: rows (first word / N, limb, sub-block)
 void wm_transform_decode(unsigned n_ids, int n_sub, int n_limbs, int n_active, unsigned long long active_map, i64* out) {
     const Tables tb{n_sub, n_limbs, n_active, active_map};
