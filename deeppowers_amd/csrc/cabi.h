@@ -31,6 +31,7 @@
 #include "../../include/dpfhe.h"
 #include "devtables.h"
 #include "launch.h"
+#include "scratch_pool.h"
 #include "tables.h"
 #include "workmap.h"
 
@@ -63,6 +64,20 @@ struct DeviceGuard {
 #define DPFHE_ON_DEVICE(ctx, what)                                                                            \
     DeviceGuard _guard((ctx)->device);                                                                         \
     if (_guard.err != hipSuccess) return fail(DPFHE_DEVICE_ERROR, what, hipGetErrorString(_guard.err))
+
+// the device calls of the scratch arenas (scratch_pool.h lists them): whatever allocates, frees or waits runs under a DeviceGuard on the context's
+// device; record runs inside an entry that holds one already (cabi_ctx.hip)
+struct HipScratchBackend {
+    using Stream = hipStream_t;
+    using Event = hipEvent_t;
+    int device;
+    int alloc(size_t words, uint64_t*& p, const char*& detail);
+    void free(uint64_t* p);
+    int new_event(Event& e, const char*& detail);
+    void destroy_event(Event e);
+    void record(Event e, Stream s) { (void)hipEventRecord(e, s); }
+    void wait(Event e);
+};
 
 // half-open byte ranges [a, a + na) and [b, b + nb) intersect
 static inline bool overlaps_bytes(const void* a, size_t na, const void* b, size_t nb) {
@@ -107,12 +122,8 @@ struct dpfhe_ctx {
     DevTables<F64WideArith> cls_f64w{};
     DevTables<ShoupArith> cls_shoup{};
     MixedTables mixed{};                              // the batched transforms' one-launch view (kernels.h ntt_classes_kernel)
-    // scratch of the composed large-ring operations: a pool of this context's own (created on first use) that keeps what it has been
-    // given until the context goes - the default pool hands its memory back at every synchronisation and pays the mapping again
-    struct ScratchArena { hipStream_t stream; u64* p; size_t words; uint64_t last_use; };
-    std::vector<ScratchArena> scratch_arenas;   // one per stream that ran a composed operation (StreamScratch below); at most kMaxScratchArenas, least recently used evicted
-    uint64_t scratch_clock = 0;                 // guarded by scratch_mutex
-    std::mutex scratch_mutex;
+    // scratch of the composed large-ring operations: one arena per stream that ran one, leased through StreamScratch below (policy: scratch_pool.h)
+    ScratchPool<HipScratchBackend> scratch{HipScratchBackend{0}};   // (dpfhe_ctx_create sets the backend's device)
     // which form of the fused multiply dpfhe_ct_mul(flags = 0) launches (launch.h CtMulVariant): the default of the ring degree until
     // dpfhe_ctx_autotune or dpfhe_ctx_set_ct_mul_variant says otherwise.  Both forms give the same words.
     std::atomic<int> ct_mul_variant{0};
@@ -237,24 +248,24 @@ inline size_t slice_items(const dpfhe_ctx* c, size_t batch, size_t scratch_words
     return fit == 0 ? 1 : (fit < batch ? fit : batch);
 }
 
-// Scratch of the composed large-ring operations: one ARENA per (context, stream), a plain hipMalloc made the first time that stream runs a
-// composed operation and grown (hipStreamSynchronize of that stream + hipFree + hipMalloc) only when a larger slice than ever before arrives;
-// kept until dpfhe_ctx_destroy, dpfhe_ctx_release_scratch or eviction.  Work on one stream is ordered, so consecutive calls share their stream's arena without a fence; different
-// streams never share one.  Steady state: no allocation, no synchronisation.
-// (Rounds 2-4 took the scratch from a stream-ordered memory pool - hipMallocFromPoolAsync / hipFreeAsync.  Round 5 found blocks of tens of MiB from
-// that pool giving wrong results and millisecond allocation times in a process without PyTorch - the C++ programs; tools/gpu_r05_f.sh -, while the
-// same calls under PyTorch were exact: the arena has no such dependence on the runtime's allocator state.)
-// The arena is created and grown on the CONTEXT's device whatever the calling thread's current device is (round 6: the advisor's finding - one caller
-// allocated before it took the device guard).  A context keeps at most kMaxScratchArenas arenas: a caller that rotates through a pool of streams evicts
-// the least recently used one (its stream is synchronised first); dpfhe_ctx_release_scratch hands an arena back explicitly (a stream about to be
-// destroyed, a phase that will not run composed operations again).
-static const size_t kMaxScratchArenas = 16;
+// A LEASE of the stream's scratch arena (scratch_pool.h: when arenas are made, grown, evicted and released): alloc() pins the arena's block into `p`, the
+// destructor records the arena's event on the stream and unpins.  So the object lives until the last launch that reads `p` has been enqueued, and ends
+// while the DeviceGuard of its entry is still in scope (declared after it): the event is recorded on the context's device.  Steady state: no allocation,
+// no synchronisation, one hipEventRecord per lease.
+// (Plain hipMalloc blocks, not the stream-ordered memory pool of rounds 2-4: round 5 found blocks of tens of MiB from that pool giving wrong results and
+// millisecond allocation times in a process without PyTorch, while the same calls under PyTorch were exact.)
 struct StreamScratch {
     u64* p = nullptr;
     dpfhe_ctx* c;
     hipStream_t s;
     StreamScratch(dpfhe_ctx* ctx, hipStream_t st) : c(ctx), s(st) {}
-    int alloc(size_t words, const char* what);   // cabi_ctx.hip
+    ~StreamScratch() { if (held) c->scratch.end(lease); }
+    StreamScratch(const StreamScratch&) = delete;
+    StreamScratch& operator=(const StreamScratch&) = delete;
+    int alloc(size_t words, const char* what);   // cabi_ctx.hip; once per object
+private:
+    ScratchPool<HipScratchBackend>::Lease lease;
+    bool held = false;
 };
 
 // the ring of a host twin (no context to take it from): at least one limb, 8 <= log2 N <= 16, odd moduli in [3, 2^60)

@@ -183,7 +183,7 @@ extern "C" int dpfhe_ctx_create(dpfhe_ctx** out, uint32_t log2_n, uint32_t n_lim
 
     dpfhe_ctx* c = new (std::nothrow) dpfhe_ctx;
     if (!c) return fail(DPFHE_OUT_OF_MEMORY, "dpfhe_ctx_create", "host allocation");
-    c->log2n = log2_n; c->n_limbs = n_limbs; c->device = device_id; c->fold = fold; c->p_special = moduli[L - 1];
+    c->log2n = log2_n; c->n_limbs = n_limbs; c->device = c->scratch.backend().device = device_id; c->fold = fold; c->p_special = moduli[L - 1];
     c->moduli.assign(moduli, moduli + L);
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->n_cu = cus; }
 
@@ -252,8 +252,7 @@ extern "C" int dpfhe_ctx_destroy(dpfhe_ctx* c) {
     if (c->class_blob) (void)hipFree(c->class_blob);
     if (c->lazy29_blob) (void)hipFree(c->lazy29_blob);
     if (c->rescale2_blob) (void)hipFree(c->rescale2_blob);
-    for (auto& a : c->scratch_arenas) if (a.p) (void)hipFree(a.p);
-    delete c;
+    delete c;   // (the scratch pool waits for, frees and strips of its event every arena it still has)
     return DPFHE_SUCCESS;
 }
 extern "C" int dpfhe_ctx_set_scratch_limit(dpfhe_ctx* c, size_t mib) {
@@ -274,65 +273,54 @@ static_assert(DPFHE_ARITH_SHOUP == kClassShoup && DPFHE_ARITH_FOLD == kClassFold
               DPFHE_ARITH_F64_WIDE == kClassF64Wide, "dpfhe.h <-> tables.h");
 
 // ------------------------------------------------------------------------------------------------
-// the scratch arenas (cabi.h StreamScratch)
+// the scratch arenas: the device calls of their policy (scratch_pool.h), the lease (cabi.h StreamScratch) and the three entries
+
+// a device call of the backend under a guard on the context's device; a failed guard fails the call
+template <class Fn>
+static hipError_t on_device(int device, Fn fn) {
+    DeviceGuard guard(device);
+    const hipError_t e = guard.err != hipSuccess ? guard.err : fn();
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+int HipScratchBackend::alloc(size_t words, uint64_t*& p, const char*& detail) {
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) { detail = hipGetErrorString(guard.err); return DPFHE_DEVICE_ERROR; }
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), words * sizeof(u64));
+    if (e == hipSuccess) return DPFHE_SUCCESS;
+    (void)hipGetLastError();
+    detail = hipGetErrorString(e);
+    return DPFHE_OUT_OF_MEMORY;
+}
+// The event only says when the work that used the block is over, so that the block can be freed: nobody reads through it what that work wrote.  So no
+// system-scope fence at the record - with one (the default) the cache write-back and invalidation between two back-to-back calls cost 3 to 5 us of device
+// time per call at N = 16384 (profiles/r22_scratch_leases.txt).
+int HipScratchBackend::new_event(Event& ev, const char*& detail) {
+    const hipError_t e = on_device(device, [&] { return hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence); });
+    if (e != hipSuccess) detail = hipGetErrorString(e);
+    return e == hipSuccess ? DPFHE_SUCCESS : DPFHE_DEVICE_ERROR;
+}
+void HipScratchBackend::free(uint64_t* p) { (void)on_device(device, [&] { return hipFree(p); }); }
+void HipScratchBackend::destroy_event(Event ev) { (void)on_device(device, [&] { return hipEventDestroy(ev); }); }
+void HipScratchBackend::wait(Event ev) { (void)on_device(device, [&] { return hipEventSynchronize(ev); }); }
+
 int StreamScratch::alloc(size_t words, const char* what) {
-    std::lock_guard<std::mutex> lock(c->scratch_mutex);
-    dpfhe_ctx::ScratchArena* arena = nullptr;
-    for (auto& a : c->scratch_arenas) if (a.stream == s) arena = &a;
-    if (arena && arena->words >= words) { arena->last_use = ++c->scratch_clock; p = arena->p; return DPFHE_SUCCESS; }
-    DeviceGuard guard(c->device);   // everything below touches the device: the context's, not the caller's current one
-    if (guard.err != hipSuccess) return fail(DPFHE_DEVICE_ERROR, what, hipGetErrorString(guard.err));
-    if (arena && arena->p) {   // growth: the stream's earlier launches may still be using the old block
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(DPFHE_DEVICE_ERROR, what, hipGetErrorString(e));
-        (void)hipFree(arena->p);
-        arena->p = nullptr; arena->words = 0;
-    }
-    if (!arena && c->scratch_arenas.size() >= kMaxScratchArenas) {   // evict the least recently used arena (another stream's: wait for that stream)
-        size_t lru = 0;
-        for (size_t i = 1; i < c->scratch_arenas.size(); ++i) if (c->scratch_arenas[i].last_use < c->scratch_arenas[lru].last_use) lru = i;
-        if (c->scratch_arenas[lru].p) {
-            if (hipStreamSynchronize(c->scratch_arenas[lru].stream) != hipSuccess) (void)hipGetLastError();   // a destroyed stream: hipFree below synchronises the device anyway
-            (void)hipFree(c->scratch_arenas[lru].p);
-        }
-        c->scratch_arenas.erase(c->scratch_arenas.begin() + (long)lru);
-    }
-    const size_t gran = (size_t)1 << 21;                                    // 16 MiB steps
-    const size_t want = (words + gran - 1) / gran * gran;
-    u64* q = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), want * sizeof(u64));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(DPFHE_OUT_OF_MEMORY, what, hipGetErrorString(e)); }
-    if (arena) { arena->p = q; arena->words = want; arena->last_use = ++c->scratch_clock; }
-    else c->scratch_arenas.push_back(dpfhe_ctx::ScratchArena{s, q, want, ++c->scratch_clock});
-    p = q;
+    const char* detail = "";
+    const int rc = c->scratch.acquire(s, words, lease, detail);
+    if (rc) return fail(rc, what, detail);
+    held = true;
+    p = lease.p;
     return DPFHE_SUCCESS;
 }
 
 extern "C" int dpfhe_ctx_release_scratch(dpfhe_ctx* c, void* stream, uint32_t flags) {
     if (!c) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_release_scratch", "null context");
     if (flags & ~(uint32_t)DPFHE_SCRATCH_ALL) return fail(DPFHE_INVALID_ARGUMENT, "dpfhe_ctx_release_scratch", "unknown flag");
-    DPFHE_ON_DEVICE(c, "dpfhe_ctx_release_scratch");
-    std::lock_guard<std::mutex> lock(c->scratch_mutex);
-    int rc = DPFHE_SUCCESS;
-    for (size_t i = 0; i < c->scratch_arenas.size();) {
-        dpfhe_ctx::ScratchArena& a = c->scratch_arenas[i];
-        if (!(flags & DPFHE_SCRATCH_ALL) && a.stream != static_cast<hipStream_t>(stream)) { ++i; continue; }
-        if (a.p) {
-            hipError_t e = hipStreamSynchronize(a.stream);   // the stream's composed operations may still be reading the block
-            if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(DPFHE_DEVICE_ERROR, "dpfhe_ctx_release_scratch", hipGetErrorString(e)); }
-            (void)hipFree(a.p);
-        }
-        c->scratch_arenas.erase(c->scratch_arenas.begin() + (long)i);
-    }
-    return rc;
+    if (c->scratch.release(static_cast<hipStream_t>(stream), (flags & DPFHE_SCRATCH_ALL) != 0))
+        return fail(DPFHE_INVALID_STATE, "dpfhe_ctx_release_scratch", "an arena is in use by a call in progress (it stays)");
+    return DPFHE_SUCCESS;
 }
-extern "C" size_t dpfhe_ctx_scratch_bytes(const dpfhe_ctx* c) {
-    if (!c) return 0;
-    std::lock_guard<std::mutex> lock(const_cast<dpfhe_ctx*>(c)->scratch_mutex);
-    size_t w = 0;
-    for (const auto& a : c->scratch_arenas) w += a.words;
-    return w * sizeof(u64);
-}
+extern "C" size_t dpfhe_ctx_scratch_bytes(const dpfhe_ctx* c) { return c ? c->scratch.bytes() : 0; }
 
 // ------------------------------------------------------------------------------------------------
 extern "C" const char* dpfhe_strerror(int code) {

@@ -28,8 +28,9 @@
  *     BASELINE configuration) they never allocate either: all scratch is caller-provided (d_work / d_digits / ... arguments).  The ONE
  *     exception is spelled out at dpfhe_ctx_create below: at log2_n >= 14 dpfhe_ct_mul, dpfhe_relinearize, dpfhe_switch_key and the two
  *     hybrid entries take their scratch from an arena the context keeps PER STREAM: allocated (hipMalloc) the first time that stream runs such an
- *     operation, grown - after synchronising that stream only - when a larger slice than ever before arrives, kept until dpfhe_ctx_destroy; in steady
- *     state they neither allocate nor synchronise.  dpfhe_ctx_create (uploads the tables: one allocation, one copy, no kernel), dpfhe_ctx_autotune
+ *     operation, grown - after waiting for that arena's own last work only - when a larger slice than ever before arrives, kept until
+ *     dpfhe_ctx_destroy; in steady state they neither allocate nor synchronise (one hipEventRecord per call marks the arena's last work).  An arena in
+ *     use by a call in progress is never released, by eviction or by dpfhe_ctx_release_scratch (see there).  dpfhe_ctx_create (uploads the tables: one allocation, one copy, no kernel), dpfhe_ctx_autotune
  *     (times kernels on caller scratch) and dpfhe_comm_create are set-up calls: they may allocate and synchronise.  After set-up a dpfhe_ctx is immutable: concurrent calls from different host threads on
  *     different streams are allowed.
  *   - digits: wherever a formula below writes [c]_{q_j} (key switching, relinearisation, the hoisted rotations), it means limb j of c taken as it
@@ -83,13 +84,18 @@ int dpfhe_ctx_destroy(dpfhe_ctx* ctx);
  * one slice's scratch stays below `mib` MiB (default 1024).  The library reads NO environment variable. */
 int dpfhe_ctx_set_scratch_limit(dpfhe_ctx* ctx, size_t mib);
 /* The composed operations take their scratch from one ARENA per (context, stream): a device allocation made at that stream's first composed call (<= the
- * scratch limit above, in 16 MiB steps), grown only for a larger slice than ever before (growth synchronises that stream), reused without allocation or
- * synchronisation from then on.  A context keeps at most 16 arenas - the least recently used one is released (after synchronising ITS stream) when a
- * 17th stream arrives - and all of them until dpfhe_ctx_destroy unless told otherwise:
- *   dpfhe_ctx_release_scratch(ctx, stream, 0)                  releases the arena of `stream` (NULL = the default stream), after synchronising it - call it
- *                                                               before destroying a stream that ran composed operations, or when a phase is over;
+ * scratch limit above, in 16 MiB steps), grown only for a larger slice than ever before, reused without allocation or synchronisation from then on.
+ * A composed call holds its stream's arena for as long as it runs on the host, and an arena in use by a call in progress is never released.  Every call
+ * ends by recording an event on its stream; eviction, growth and release wait for the arena's last recorded work - that event - and not for a stream
+ * handle, so a stream may be destroyed before its arena is released.  A context keeps at most 16 arenas - when a 17th stream arrives, the least
+ * recently used arena that is not in use is released - and more than 16 exist only while more than 16 calls are in progress at once (the next new
+ * stream brings the count back).  All of them stay until dpfhe_ctx_destroy unless told otherwise:
+ *   dpfhe_ctx_release_scratch(ctx, stream, 0)                  releases the arena of `stream` (NULL = the default stream) - when a phase is over, or a
+ *                                                               stream that ran composed operations is gone;
  *   dpfhe_ctx_release_scratch(ctx, NULL, DPFHE_SCRATCH_ALL)    releases every arena of the context.
- * dpfhe_ctx_scratch_bytes: device bytes the context's arenas hold right now.  Thread-safe (one mutex per context). */
+ * Both wait on the host for the work recorded on what they release.  An arena in use by a call in progress stays, and the call returns
+ * DPFHE_INVALID_STATE (after releasing the others); a stream without an arena is no error.
+ * dpfhe_ctx_scratch_bytes: device bytes the context's arenas hold right now.  Thread-safe (one mutex per context, not held while waiting or freeing). */
 enum { DPFHE_SCRATCH_ALL = 1 };
 int dpfhe_ctx_release_scratch(dpfhe_ctx* ctx, void* stream, uint32_t flags);
 size_t dpfhe_ctx_scratch_bytes(const dpfhe_ctx* ctx);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #define FACADE_TEST_GATE
+#include "dpfhe.h"
 #include "facade_test.h"
 
 using namespace deeppowers::fhe;
@@ -400,6 +401,31 @@ static void synchronising_methods(Rig& r) {
     }
 }
 
+// ---- a stream destroyed before its scratch arena is released: the release waits for the arena's last recorded work, never for the stream handle -------
+static void destroyed_stream(Rig& r) {
+    const size_t n = r.n, L = r.p.n_limbs(), terms = 2;
+    Ciphertext a(r.ctx, 2, terms), b(r.ctx, 2, terms), sum(r.ctx, 3, 1), ref(r.ctx, 3, 1);
+    for (Ciphertext* ct : {&a, &b}) {
+        std::vector<uint64_t> h(ct->words());
+        for (size_t i = 0; i < h.size(); ++i) h[i] = rnd(r.p.moduli[(i / n) % L]);
+        ct->copy_from_host(h.data());
+    }
+    r.ctx.release_scratch(nullptr, true);
+    CHECK(r.ctx.scratch_bytes() == 0);
+    r.ev.multiply_sum(a, b, terms, false, ref);                           // on the null stream
+    r.ctx.synchronize();
+    void* s = nullptr;
+    CHECK(stream_gate_stream_create(&s) == 0 && s);
+    const size_t before = r.ctx.scratch_bytes();
+    r.ev.multiply_sum(a, b, terms, false, sum, s);                        // composed at every ring degree: an arena for s
+    CHECK(r.ctx.scratch_bytes() > before);
+    HIP(hipStreamSynchronize(static_cast<hipStream_t>(s)));
+    CHECK(stream_gate_stream_destroy(s) == 0);
+    CHECK(dpfhe_ctx_release_scratch(static_cast<dpfhe_ctx*>(r.ctx.handle()), nullptr, DPFHE_SCRATCH_ALL) == DPFHE_SUCCESS);
+    CHECK(dpfhe_ctx_scratch_bytes(static_cast<dpfhe_ctx*>(r.ctx.handle())) == 0);
+    CHECK(words(sum) == words(ref));
+}
+
 int main(int argc, char** argv) {
     const double G = argc > 1 ? std::atof(argv[1]) : 0.040;
     if (!(G >= 0.010 && G <= 0.1)) { std::printf("G = %g s is outside [0.010, 0.1]\n", G); return 2; }
@@ -412,6 +438,7 @@ int main(int argc, char** argv) {
         block(r);
         exact_ops(r);
         synchronising_methods(r);
+        destroyed_stream(r);
         r.ctx.synchronize();
         std::printf("%d gated facade calls; G = %.1f ms; slowest t_enqueue %.3f ms (%s)\n", r.gate.gated_calls, G * 1e3, r.gate.slowest * 1e3, r.gate.slowest_what.c_str());
     } catch (const std::exception& e) {

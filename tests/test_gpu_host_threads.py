@@ -144,3 +144,38 @@ def test_scratch_arenas_are_capped_and_released():
         assert ctx.scratch_bytes == 0
     finally:
         ctx.close()
+
+
+@pytest.mark.gpu
+def test_eviction_waits_for_the_victims_pending_work():
+    """S is held behind the gate of tests/stream_gate.py with one composed multiply enqueued on it; 16 other streams then run one each, and the 16th evicts
+    the arena of S while the work that reads it has not started: the eviction waits for the event recorded at the end of S's call, not for S."""
+    import torch
+    from deeppowers_amd.evaluator import Ciphertext, Context, Evaluator, to_device, to_host
+    from stream_gate import shared_gate
+    p = _large_params()
+    ctx = Context(p, 0)
+    ev = Evaluator(ctx)
+    orc = Oracle.from_params(p)
+    try:
+        gate = shared_gate(ctx.device)
+        L, n = p.n_limbs, p.n
+        hosts = [orc.fill(2, seed).reshape(1, 2, L, n) for seed in (11, 12, 13, 14)]
+        want_s, want = orc.ct_mul(hosts[0], hosts[1], threads=0), orc.ct_mul(hosts[2], hosts[3], threads=0)
+        a_s, b_s, a, b = (Ciphertext(to_device(h, ctx.device)) for h in hosts)
+        others = [torch.cuda.Stream(device=ctx.device) for _ in range(16)]
+        torch.cuda.synchronize()
+        gate.hold()
+        got_s = ev.multiply(a_s, b_s, stream=gate.stream)          # the arena of S: leased, its event recorded behind the gate
+        per = ctx.scratch_bytes
+        assert per > 0
+        for i, s in enumerate(others):
+            got = ev.multiply(a, b, stream=s)                      # the 16th needs a 17th arena: S's is the least recently used
+            s.synchronize()
+            assert np.array_equal(to_host(got.data), want), i
+        assert ctx.scratch_bytes == per * 16
+        gate.stream.synchronize()
+        assert np.array_equal(to_host(got_s.data), want_s)
+        assert ctx.scratch_bytes == per * 16
+    finally:
+        ctx.close()

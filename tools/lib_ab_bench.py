@@ -1,12 +1,16 @@
 """Two builds of libdpfhe_hip.so against each other (tool; profiles/r20_last_pass_refactor.txt): another commit's library and this tree's are loaded into ONE
-process and the same entry runs on the same buffers, alternating round by round, for the streaming kernels of key switching - dpfhe_rescale, dpfhe_rescale_bsgs,
-dpfhe_lincomb_rescale, dpfhe_relinearize_lincomb_rescale_hybrid - on fold and generic primes.  Per shape: median / min / max ms per call of each library, whether
-this tree's median lies inside the other's own min-max range (the noise, measured in the same run), and whether both libraries wrote the same words.
-usage: python tools/lib_ab_bench.py <the other build's libdpfhe_hip.so> [rounds = 9] [reps = 20]"""
+process and the same entry runs on the same buffers, alternating round by round.  Two sets of entries: "streaming" (the default) - the streaming kernels of
+key switching, dpfhe_rescale, dpfhe_rescale_bsgs, dpfhe_lincomb_rescale, dpfhe_relinearize_lincomb_rescale_hybrid, on fold and generic primes; "arenas"
+(profiles/r22_scratch_leases.txt) - the composed dpfhe_ct_mul and dpfhe_relinearize at N = 16384, L = 3, batch 1 and 8, one stream in steady state, which
+lease their stream's scratch arena.  Per shape: median / min / max ms per call of each library by events, and us of host time per call (the enqueue cost: the
+wall time of the calls alone), whether this tree's median lies inside the other's own min-max range (the noise, measured in the same run), and whether both
+libraries wrote the same words.
+usage: python tools/lib_ab_bench.py <the other build's libdpfhe_hip.so> [rounds = 9] [reps = 20] [streaming | arenas]"""
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -17,6 +21,7 @@ from deeppowers_amd.params import ntt_primes  # noqa: E402
 
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 9
 REPS = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+SET = sys.argv[4] if len(sys.argv) > 4 else "streaming"
 
 
 def load(path):
@@ -54,16 +59,19 @@ def alternate(what, shape, calls, outs):
         f()
         f()
     torch.cuda.synchronize()
-    ms = {name: [] for name in calls}
+    ms, host = {name: [] for name in calls}, {name: [] for name in calls}
     for _ in range(ROUNDS):
         for name, f in calls.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
+            t0 = time.perf_counter()
             for _ in range(REPS):
                 f()
+            t1 = time.perf_counter()
             e1.record()
             e1.synchronize()
             ms[name].append(e0.elapsed_time(e1) / REPS)
+            host[name].append((t1 - t0) * 1e6 / REPS)
     row = {"entry": what, **shape, "rounds": ROUNDS, "reps": REPS, "same_words": bool(torch.equal(outs["parent"], outs["new"]))}
     for name, v in ms.items():
         v.sort()
@@ -72,6 +80,12 @@ def alternate(what, shape, calls, outs):
     row["new_over_parent"] = round(nw[len(nw) // 2] / p[len(p) // 2], 4)
     row["new_median_inside_parent_range"] = bool(p[0] <= nw[len(nw) // 2] <= p[-1])
     row["new_median_not_above_parent_max"] = bool(nw[len(nw) // 2] <= p[-1])
+    for name, v in host.items():
+        v.sort()
+        row[name + "_host_us"] = {"median": round(v[len(v) // 2], 2), "min": round(v[0], 2), "max": round(v[-1], 2)}
+    p, nw = host["parent"], host["new"]
+    row["new_minus_parent_host_us"] = round(nw[len(nw) // 2] - p[len(p) // 2], 2)
+    row["new_host_median_inside_parent_range"] = bool(p[0] <= nw[len(nw) // 2] <= p[-1])
     print(json.dumps(row), flush=True)
 
 
@@ -142,8 +156,36 @@ def relin_lincomb(ext, K, batch, tag):
                                                            "fold": LIBS["new"].dpfhe_ctx_uses_fold(keep[-1][0])}, calls, outs)
 
 
+def composed(params, batch, relin):
+    """dpfhe_ct_mul / dpfhe_relinearize above N = 8192: composed, scratch leased from the null stream's arena"""
+    L, n = params.n_limbs, params.n
+    g = torch.Generator(device=DEV).manual_seed(5)
+    x = words(g, params.moduli, (batch, 3 if relin else 2), n)
+    y = words(g, params.moduli, (L, 2) if relin else (batch, 2), n)
+    calls, outs, keep = {}, {}, []
+    for name, lib in LIBS.items():
+        h = ctx_of(lib, params)
+        out = torch.zeros((batch, 2 if relin else 3, L, n), dtype=torch.int64, device=DEV)
+        if relin:
+            calls[name] = lambda lib=lib, h=h, out=out: ok(lib, lib.dpfhe_relinearize(h, out.data_ptr(), x.data_ptr(), y.data_ptr(), batch, None))
+        else:
+            calls[name] = lambda lib=lib, h=h, out=out: ok(lib, lib.dpfhe_ct_mul(h, out.data_ptr(), x.data_ptr(), y.data_ptr(), batch, 0, None))
+        outs[name] = out
+        keep.append(h)
+    for f in calls.values():   # the arenas exist from here on
+        f()
+    torch.cuda.synchronize()
+    alternate("dpfhe_relinearize" if relin else "dpfhe_ct_mul", {"log2_n": params.log2_n, "limbs": L, "batch": batch, "scratch_bytes": LIBS["new"].dpfhe_ctx_scratch_bytes(keep[-1])},
+              calls, outs)
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available(), "a measurement needs the GPU"
+    if SET == "arenas":
+        for batch in (1, 8):
+            for relin in (False, True):
+                composed(ntt_primes(14, 3), batch, relin)
+        sys.exit(0)
     fold13, gen13 = ntt_primes(13, 6), ntt_primes(13, 6, 58)
     for params, tag in ((fold13, "fold"), (gen13, "generic")):
         rescale(params, 128, tag)
