@@ -101,6 +101,15 @@ DPF_HD u64 shl1_add(u64 a, u64 c) {
 #endif
 }
 
+// a + c in one v_lshl_add_u64 for a WAVE-UNIFORM c (a multiple of q built once on the scalar unit).  Written as `a + off * q` hipcc multiplies the low word
+// of q by `off` in a v_mad_u64_u32 and then repairs the high word with a second add.
+DPF_HD u64 add_uniform(u64 a, u64 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(c));   // opaque scalar pair: the add stays one v_lshl_add_u64 (an instruction of its own in inline assembly costs a wait state behind it)
+#endif
+    return a + c;
+}
+
 // x >= m ? x - m : x
 DPF_HD u64 csub(u64 x, u64 m) {
     u64 t = x - m;
@@ -277,7 +286,28 @@ struct FoldArith {
         return R;
     }
     static DPF_HD u64 mul_tw29(u64 y, const Tw& t, const LimbConst& c) { return mul_tw29_add(y, t, c, 0); }
-    // (emulator only) the chain above in exact arithmetic: none of H, L, R leaves 64 bits
+    // The same chain for a WAVE-UNIFORM addend m = k q (a scalar register pair): R == y w (mod q), R < 4.125 * 2^60 + y / 8 + m.  A Gentleman-Sande product
+    // that is the minuend of its next butterfly takes that butterfly's `off q` on board here, where the plan's bounds leave room for it in the sum as well
+    // (ntt_core.h make_gs29_ride).  The multiple enters at y0 a, whose other operands are vector registers: H.lo 2^29 already reads a scalar (2^29), and a
+    // multiply-add reads one scalar operand only.  The sums are those of mul_tw29_add in another order; tw29_fits checks them in exact arithmetic.
+    static DPF_HD u64 mul_tw29_add_uniform(u64 y, const Tw& t, const LimbConst& c, u64 m) {
+        const u32 y0 = (u32)y, y1 = (u32)(y >> 32);
+        const u32 a = (u32)t.w, b = (u32)(t.w >> 32), as = (u32)t.ws, bs = (u32)(t.ws >> 32);
+        DPFHE_EMU_ASSERT(((a | as) >> 29) == 0 && ((b | bs) >> 31) == 0);
+        DPFHE_EMU_ASSERT(m % c.q == 0 && tw29_fits(y0, y1, a, b, as, bs, m, (u32)c.d));
+        const u64 H = mad32(y1, bs, mad32(y0, b, 0));
+        u32 two29 = 1u << 29;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("s_mov_b32 %0, 0x20000000" : "=s"(two29));
+        asm("" : "+s"(m));
+#endif
+        const u64 L = mad32((u32)H, two29, mad32(y1, as, mad32(y0, a, m)));
+        const u64 R = mad32((u32)(H >> 32), 2 * (u32)c.d, L);
+        DPFHE_EMU_ASSERT((unsigned __int128)R % c.q == (unsigned __int128)y * ((u64)a + ((u64)b << 29)) % c.q);   // the multiple of q changed the word, not the residue
+        DPFHE_EMU_NOTE(kSiteFoldMulTw29Add, R, (1ull << 60) - c.d);
+        return R;
+    }
+    // (emulator only) the two chains above in exact arithmetic: none of H, L, R leaves 64 bits
     static DPF_HD bool tw29_fits(u32 y0, u32 y1, u32 a, u32 b, u32 as, u32 bs, u64 addend, u32 d) {
         typedef unsigned __int128 u128;
         const u128 H = (u128)y0 * b + (u128)y1 * bs;

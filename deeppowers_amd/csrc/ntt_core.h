@@ -41,7 +41,15 @@ inline u64 chk_lazy_diff(u64 a, u64 c, u64 s) {  // 2a + c - s must END in [0, 2
     if (v < 0 || (v >> 64)) ++g_emu_overflows;
     return shl1_add(a, c) - s;
 }
+inline u64 chk_add_uniform_sub(u64 a, u64 c, u64 b) {  // a + c must stay below 2^64 and a + c - b in [0, 2^64)
+    __int128 v = (__int128)a + (__int128)c - (__int128)b;
+    if (v < 0 || ((unsigned __int128)a + c) >> 64) ++g_emu_overflows;
+    return add_uniform(a, c) - b;
+}
+inline u64 chk_sub(u64 a, u64 b) { if (a < b) ++g_emu_overflows; return a - b; }
 #else
+DPF_HD u64 chk_add_uniform_sub(u64 a, u64 c, u64 b) { return add_uniform(a, c) - b; }
+DPF_HD u64 chk_sub(u64 a, u64 b) { return a - b; }
 DPF_HD u64 chk_lazy_diff(u64 a, u64 c, u64 s) { return shl1_add(a, c) - s; }
 DPF_HD u64 chk_shl1_add_sub(u64 a, u64 c, u64 s) { return shl1_add(a, c) - s; }
 DPF_HD u64 chk_add(u64 a, u64 b) { return a + b; }
@@ -313,7 +321,8 @@ constexpr CtfPlan<LOGE> make_ctf_plan(int lb_top, int r, int in_bound, int out_c
 // `a` is reduced first (3 instructions) when x' or y' would not fit a word, or when that saves reductions at the phase hand-over.
 // Inverse butterfly: x' = a + b, y' = (a - b + off q) w unreduced; the larger of a, b is reduced first when the sum or the difference would not fit, then
 // the other if it still does not.  The transform's last stage reduces its products (inv_canon's input bound) and divides its sums by N (mul_ninv).
-// Every plan counts its reductions (n_red): the transform's cost is 9 VALU per forward butterfly, 10 per inverse one, plus 3 per reduction.
+// Every plan counts its reductions (n_red): the transform's cost is 9 VALU per forward butterfly, 10 per inverse one (sum 1, difference 3 - off q is a scalar pair
+// added in one v_lshl_add_u64, or rides the previous product's chain: Gs29Ride below -, chain 6), plus 3 per reduction.
 // ------------------------------------------------------------------------------------------------
 constexpr int kLazy29B = 4 * kUnit + kUnit / 8 + 1;
 constexpr int kCtf29Mid = 14 * kUnit;             // forward hand-over cap: above every word the N = 4096 geometry hands over (13 q) - no reduction at an exchange
@@ -397,6 +406,68 @@ constexpr Gs29Plan<LOGE> make_gs29_plan(int lb0, int r, int in_bound, int out_ca
         if (bnd[k] > p.out_bound) p.out_bound = bnd[k];
     }
     return p;
+}
+
+// Where the `+ off q` of an inverse butterfly comes from (derived from a Gs29Plan; every field of the plan keeps its value, no reduction is added or moved).
+// ride[u][kk]: the product that stage u writes to element kk leaves its multiply-add chain with the `off q` of its NEXT butterfly on board
+// (FoldArith::mul_tw29_add_uniform: the chain's addend, free), where kk is that butterfly's minuend and is not reduced in front of it.  The butterfly is then
+// x' = a + b, y' = (a - b) w: its difference costs the subtraction alone, and the multiple travels on in its sum.  Everywhere else the multiple is a scalar
+// register pair added in one v_lshl_add_u64 (chk_add_uniform_sub).
+// The rule: candidates are taken in the order (u, kk) ascending; one stays when the phase, walked with the TRUE bounds under the plan's own reductions and
+// offsets, still has every subtrahend <= off q, every sum inside sum_cap (the last stage's margin included), every difference and product inside a word and
+// every unreduced output inside out_cap (gs29_ride_fits).  At N = 4096: 3 butterflies of the first phase walked, none in the other two (their products are
+// at 5.78 q: two of them and 6 q pass 16 q).
+template <int LOGE>
+struct Gs29Ride {
+    bool ride[LOGE][1 << LOGE];
+    int n_ride;
+};
+template <int LOGE>
+constexpr bool gs29_ride_fits(const Gs29Plan<LOGE>& p, const Gs29Ride<LOGE>& rd, int lb0, int r, int in_bound, int out_cap, bool last, int ninv_shift) {
+    constexpr int E = 1 << LOGE;
+    int bnd[E] = {};
+    bool on_board[E] = {};
+    for (int k = 0; k < E; ++k) bnd[k] = in_bound;
+    for (int u = 0; u < r; ++u) {
+        const int bit = 1 << (lb0 + u);
+        const bool fin = last && u == r - 1;
+        const int sum_cap = fin ? kWord - kUnit / 8 : kWord;
+        for (int k = 0; k < E; ++k) {
+            if (k & bit) continue;
+            const int kk = k | bit;
+            int bx = bnd[k], by = bnd[kk];
+            if (on_board[kk] || (on_board[k] && p.red[u][k])) return false;   // a multiple rides to a minuend that is not reduced on the way
+            if (p.red[u][k]) bx = kRedB;
+            if (p.red[u][kk]) by = kRedB;
+            const int offq = p.off[u][k] * kUnit;
+            const int dl = on_board[k] ? bx : bx + offq;                      // a - b + off q <= a + off q, and bx counts a multiple on board
+            if (by > offq || bx + by > sum_cap || dl > kWord) return false;
+            const bool rides = rd.ride[u][kk];
+            if (rides && (fin || u + 1 >= r || (kk & (bit << 1)))) return false;
+            bnd[k] = fin ? kUnit + ((bx + by) >> ninv_shift) + 2 : bx + by;
+            bnd[kk] = fin ? kRedB : kLazy29B + (dl + 7) / 8 + (rides ? p.off[u + 1][kk] * kUnit : 0);
+            if (bnd[kk] > kWord) return false;
+            on_board[k] = false;
+            on_board[kk] = rides;
+        }
+    }
+    for (int k = 0; k < E; ++k)
+        if (on_board[k] || (!p.red_end[k] && bnd[k] > out_cap)) return false;
+    return true;
+}
+template <int LOGE>
+constexpr Gs29Ride<LOGE> make_gs29_ride(const Gs29Plan<LOGE>& p, int lb0, int r, int in_bound, int out_cap, bool last, int ninv_shift) {
+    constexpr int E = 1 << LOGE;
+    Gs29Ride<LOGE> rd{};
+    for (int u = 0; u + 1 < r; ++u) {
+        const int bit = 1 << (lb0 + u);
+        for (int kk = 0; kk < E; ++kk) {
+            if (!(kk & bit) || (kk & (bit << 1))) continue;
+            rd.ride[u][kk] = true;
+            if (gs29_ride_fits<LOGE>(p, rd, lb0, r, in_bound, out_cap, last, ninv_shift)) ++rd.n_ride; else rd.ride[u][kk] = false;
+        }
+    }
+    return rd;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -836,6 +907,11 @@ struct NttBody {
         constexpr Phase ph = G::phase(P);
         return make_gs29_plan<LOGE>(ph.b - ph.c, ph.r, (P == NPH - 1) ? IN : kGs29Mid, (P == 0) ? 3 * kUnit / 2 : kGs29Mid, P == 0, LOGN);
     }
+    template <int P, int IN>
+    static constexpr Gs29Ride<LOGE> gs29_ride() {   // derived from the plan of the same phase, with the same arguments
+        constexpr Phase ph = G::phase(P);
+        return make_gs29_ride<LOGE>(gs29_plan<P, IN>(), ph.b - ph.c, ph.r, (P == NPH - 1) ? IN : kGs29Mid, (P == 0) ? 3 * kUnit / 2 : kGs29Mid, P == 0, LOGN);
+    }
     // reductions per transform and thread under the lazy plans (E / 2 * LOGN butterflies)
     template <int P = 0> static constexpr int lazy_fwd_reductions() { if constexpr (P < NPH) return ctf29_plan<P>().n_red + lazy_fwd_reductions<P + 1>(); else return 0; }
     template <int IN, int P = 0> static constexpr int lazy_inv_reductions() { if constexpr (P < NPH) return gs29_plan<P, IN>().n_red + lazy_inv_reductions<IN, P + 1>(); else return 0; }
@@ -1036,6 +1112,42 @@ struct NttBody {
         return make_gs_plan<LOGE>(ph.b - ph.c, ph.r, (P == NPH - 1) ? IN : kGsMid, (P == 0) ? kLimit : kGsMid, P == 0, Arith::kFold ? LOGN : 0);
     }
 
+    // One lazy inverse phase under a plan and the table derived from it.  The multiple of q of a difference is a scalar pair added in one instruction, or is
+    // already on board of the minuend (ride: the previous stage's product took it through its chain).  (The emulator also runs this under tables of its own.)
+    template <int P>
+    static DPF_HD void inv_phase_lazy29(u64 (&x)[E], const TwRegs& twr, const Tw& w_last, const LimbConst& lc, const Gs29Plan<LOGE>& plan, const Gs29Ride<LOGE>& ride) {
+        constexpr Phase ph = G::phase(P);
+        const u64 q = lc.q;
+#pragma clang loop unroll(full)
+        for (int u = 0; u < ph.r; ++u) {
+            const int pos = ph.b + u;
+            const int lb = pos - ph.c;
+            const bool last = (pos == LOGN - 1);
+#pragma clang loop unroll(full)
+            for (int k = 0; k < E; ++k) {
+                if (k & (1 << lb)) continue;
+                const int kk = k | (1 << lb);
+                u64 a = x[k], b = x[kk];
+                if (plan.red[u][k]) a = FoldArith::reduce(a, lc);
+                if (plan.red[u][kk]) b = FoldArith::reduce(b, lc);
+                const u64 s = chk_add(a, b);
+                const bool on_board = u > 0 && ride.ride[u > 0 ? u - 1 : 0][k];
+                const u64 dlt = on_board ? chk_sub(a, b) : chk_add_uniform_sub(a, (u64)plan.off[u][k] * q, b);
+                if (last) {  // the sums are divided by N exactly, the products reduced: what inv_canon takes
+                    x[k] = FoldArith::mul_ninv(s, lc, LOGN);
+                    x[kk] = FoldArith::reduce(FoldArith::mul_tw29(dlt, w_last, lc), lc);
+                } else {
+                    x[k] = s;
+                    const Tw& w = twr[u][k >> (lb + 1)];
+                    // unreduced: < 4.125 * 2^60 + dlt / 8 (+ the next butterfly's off q)
+                    x[kk] = ride.ride[u][kk] ? FoldArith::mul_tw29_add_uniform(dlt, w, lc, (u64)plan.off[u + 1 < ph.r ? u + 1 : u][kk] * q) : FoldArith::mul_tw29(dlt, w, lc);
+                }
+            }
+        }
+#pragma clang loop unroll(full)
+        for (int k = 0; k < E; ++k)
+            if (plan.red_end[k]) x[k] = FoldArith::reduce(x[k], lc);
+    }
     template <int P, int IN>
     static DPF_HD void inv_phase_r(u64 (&x)[E], const TwRegs& twr, const Tw& w_last, const Tw& w_ninv, const LimbConst& lc_in) {
         constexpr Phase ph = G::phase(P);
@@ -1073,33 +1185,8 @@ struct NttBody {
                 if (plan.red_end[k]) x[k] = Arith::b(Arith::reduce(Arith::f(x[k]), q, qi));
         } else if constexpr (LAZY29) {
             constexpr Gs29Plan<LOGE> plan = gs29_plan<P, IN>();
-            const u64 q = lc.q;
-#pragma clang loop unroll(full)
-            for (int u = 0; u < ph.r; ++u) {
-                const int pos = ph.b + u;
-                const int lb = pos - ph.c;
-                const bool last = (pos == LOGN - 1);
-#pragma clang loop unroll(full)
-                for (int k = 0; k < E; ++k) {
-                    if (k & (1 << lb)) continue;
-                    const int kk = k | (1 << lb);
-                    u64 a = x[k], b = x[kk];
-                    if (plan.red[u][k]) a = FoldArith::reduce(a, lc);
-                    if (plan.red[u][kk]) b = FoldArith::reduce(b, lc);
-                    const u64 s = chk_add(a, b);
-                    const u64 dlt = chk_sub_add(a, b, (u64)plan.off[u][k] * q);
-                    if (last) {  // the sums are divided by N exactly, the products reduced: what inv_canon takes
-                        x[k] = FoldArith::mul_ninv(s, lc, LOGN);
-                        x[kk] = FoldArith::reduce(FoldArith::mul_tw29(dlt, w_last, lc), lc);
-                    } else {
-                        x[k] = s;
-                        x[kk] = FoldArith::mul_tw29(dlt, twr[u][k >> (lb + 1)], lc);   // unreduced: < 4.125 * 2^60 + dlt / 8
-                    }
-                }
-            }
-#pragma clang loop unroll(full)
-            for (int k = 0; k < E; ++k)
-                if (plan.red_end[k]) x[k] = FoldArith::reduce(x[k], lc);
+            constexpr Gs29Ride<LOGE> ride = gs29_ride<P, IN>();
+            inv_phase_lazy29<P>(x, twr, w_last, lc, plan, ride);
         } else {
             constexpr GsPlan<LOGE> plan = gs_plan<P, IN>();
             const u64 q = lc.q, two_q = 2 * lc.q;

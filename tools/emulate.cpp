@@ -595,6 +595,58 @@ extern "C" int emu_lazy29_plan(int inverse, int phase, int in_bound, int* flags,
     }
     return 0;
 }
+// FoldArith::mul_tw29_add_uniform with the multiple k q on board: the UNREDUCED word (its assertions check the chain and the residue in 128-bit arithmetic)
+extern "C" u64 emu_fold_tw29_uniform(u64 d, u64 y, u64 w, u64 k) {
+    LimbConst lc{};
+    lc.q = (1ull << 60) - d; lc.d = d;
+    return FoldArith::mul_tw29_add_uniform(y, h_tw_fold29(w, lc.q), lc, k * lc.q);
+}
+// Where the inverse butterflies' multiples of q come from (ntt_core.h Gs29Ride, derived from the plan of the same phase and input bound): ride[u][kk] in
+// flags[u * 16 + kk]; returns the number of products that carry their next butterfly's multiple, or -2000.
+extern "C" int emu_gs29_ride(int phase, int in_bound, int* flags) {
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, true, true> B;
+    if (phase < 0 || phase >= B::NPH) return -2000;
+    const Phase ph = B::G::phase(phase);
+    const int cap = phase == 0 ? 3 * kUnit / 2 : kGs29Mid;
+    const Gs29Plan<4> p = make_gs29_plan<4>(ph.b - ph.c, ph.r, in_bound, cap, phase == 0, 12);
+    const Gs29Ride<4> rd = make_gs29_ride<4>(p, ph.b - ph.c, ph.r, in_bound, cap, phase == 0, 12);
+    for (int u = 0; u < 4; ++u) for (int k = 0; k < 16; ++k) flags[u * 16 + k] = rd.ride[u][k];
+    return rd.n_ride;
+}
+// the tables the shipped body compiles in, phase by phase: ride[phase][u][kk] in flags[phase * 64 + u * 16 + kk]; returns their total per transform and thread
+extern "C" int emu_gs29_ride_shipped(int* flags) {
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, true, true> BI;
+    constexpr int IN = BI::kProdInvIn;
+    const Gs29Ride<4> rd[3] = {BI::gs29_ride<0, IN>(), BI::gs29_ride<1, IN>(), BI::gs29_ride<2, IN>()};
+    int n = 0;
+    for (int p = 0; p < 3; ++p) { n += rd[p].n_ride; for (int u = 0; u < 4; ++u) for (int k = 0; k < 16; ++k) flags[p * 64 + u * 16 + k] = rd[p].ride[u][k]; }
+    return n;
+}
+// One thread's lazy inverse phase (NttBody::inv_phase_lazy29, the code the kernel runs) on the caller's 16 words and twiddles, under the shipped plan of
+// that phase and either its shipped derived table (ride_flags == nullptr) or the caller's - a multiple folded where the bounds have no room must trip the
+// armed assertions.  w[u * 8 + j]: the twiddle (a residue below q) of stage u, butterfly group j; w_last: the last stage's.  q = 2^60 - d, any fold modulus.
+template <int P>
+static void emu_gs29_phase_p(u64 q, const int* ride_flags, const u64* w, u64 w_last, u64 (&x)[16]) {
+    typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, true, true> BI;
+    constexpr int IN = BI::kProdInvIn;
+    const Gs29Plan<4> plan = BI::gs29_plan<P, IN>();
+    Gs29Ride<4> rd = BI::gs29_ride<P, IN>();
+    if (ride_flags) for (int u = 0; u < 4; ++u) for (int k = 0; k < 16; ++k) rd.ride[u][k] = ride_flags[u * 16 + k] != 0;
+    LimbConst lc{};
+    lc.q = q; lc.d = (1ull << 60) - q;
+    typename BI::TwRegs twr;
+    for (int u = 0; u < 4; ++u) for (int j = 0; j < 8; ++j) twr[u][j] = h_tw_fold29(w[u * 8 + j], q);
+    BI::inv_phase_lazy29<P>(x, twr, h_tw_fold29(w_last, q), lc, plan, rd);
+}
+extern "C" int emu_gs29_phase(int phase, u64 q, const int* ride_flags, const u64* w, u64 w_last, u64* x16) {
+    if (!fold_eligible(q) || !(q & 1)) return 2000;
+    u64(&x)[16] = *reinterpret_cast<u64(*)[16]>(x16);
+    if (phase == 0) emu_gs29_phase_p<0>(q, ride_flags, w, w_last, x);
+    else if (phase == 1) emu_gs29_phase_p<1>(q, ride_flags, w, w_last, x);
+    else if (phase == 2) emu_gs29_phase_p<2>(q, ride_flags, w, w_last, x);
+    else return 2000;
+    return 0;
+}
 // what the shipped body compiles in: reductions per transform and thread, forward and inverse, and the hand-over bounds the phases were planned with
 extern "C" void emu_lazy29_totals(int* out) {
     typedef NttBody<FoldArith, 12, kLoge, 0, kUnit, false, true> B;
