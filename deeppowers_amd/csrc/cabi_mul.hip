@@ -1,6 +1,6 @@
 // cabi_mul.hip - the C ABI's ciphertext multiply: dpfhe_ct_mul on the fused kernels of kernels.h (launch.h), composed above N = 8192 over
-// kernels_mul.h, its traced diagnostic form, and dpfhe_ct_mul_sum (sums of products, composed at every ring degree).  cabi.h lists the other units and
-// states the ABI's conventions.
+// kernels_mul.h, its traced diagnostic form, dpfhe_ct_mul_sum (sums of products) and dpfhe_ct_mul_complement (products with a shared complement factor), both
+// composed at every ring degree.  cabi.h lists the other units and states the ABI's conventions.
 #include "cabi.h"
 #include "kernels_mul.h"
 
@@ -153,6 +153,95 @@ extern "C" int dpfhe_ct_mul_sum(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* 
     DPFHE_ON_DEVICE(c, what);
     MulSumCall k{c, flags, static_cast<hipStream_t>(stream), terms, b_groups == 1 && groups > 1, d_a2 == d_b2 && b_groups == groups};
     return ct_mul_sum_composed(k, d_out3, d_a2, d_b2, groups);
+}
+
+// ---- products with a shared complement factor (include/dpfhe.h dpfhe_ct_mul_complement): always composed, at every ring degree - batched forward transforms of
+// b and a into the stream's arena, tensor3_complement_kernel (kernels_mul.h), three inverse transforms per output item.  At N <= 8192 a fused form would have
+// to hold the factor's transform in the workgroup across terms + 1 products; the composed form reuses the batched transforms as they are.
+
+struct MulComplementCall {
+    dpfhe_ctx* c;
+    uint32_t flags;
+    hipStream_t s;
+    const u64* d_kappa;
+};
+
+// `groups` groups of `terms` items: a and out3 are the first group's; out_self null for no self product
+static int mul_complement_kernel_launch(const MulComplementCall& k, u64* d_out3, u64* d_out_self, const u64* pa, const u64* pb, size_t groups, size_t terms) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n;
+    const size_t grid = mul_complement_grid(groups, L, n);
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((tensor3_complement_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, k.s, d_out3, d_out_self, terms ? pa : pb, pb, k.d_kappa, c->lc, (int)L, (int)n,
+                           chunks_of(n), (int)terms);
+    });
+    return check_launch("complement product kernel launch");
+}
+
+static int ct_mul_complement_composed(const MulComplementCall& k, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t groups, size_t terms, bool with_self) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, poly = L << c->log2n;
+    const bool out_ntt = (k.flags & DPFHE_OUT_NTT) != 0;
+    u64* d_self = with_self ? d_out3 + groups * terms * 3 * poly : nullptr;
+    auto inverse = [&](u64* p, size_t items) { return out_ntt || items == 0 ? (int)DPFHE_SUCCESS : ntt_launch(c, true, p, p, items * 3 * L, k.s); };
+    if (k.flags & DPFHE_IN_NTT) {   // no scratch: one launch over everything
+        if (int rc = mul_complement_kernel_launch(k, d_out3, d_self, d_a2, d_b2, groups, terms)) return rc;
+        return inverse(d_out3, groups * (terms + (with_self ? 1 : 0)));
+    }
+    // Scratch for the transformed operands: [slice of b | that slice's a]
+    const size_t limit = c->scratch_limit_words.load(std::memory_order_relaxed), item = 2 * poly, per_group = (terms + 1) * item;
+    StreamScratch ws(c, k.s);
+    if (per_group <= limit) {   // whole groups fit: slices of groups
+        const size_t fit = limit / per_group, per = fit < groups ? fit : groups;
+        if (int rc = ws.alloc(per * per_group, "dpfhe_ct_mul_complement (scratch for the transformed operands)")) return rc;
+        return for_slices(groups, per, [&](size_t g0, size_t m) {
+            u64 *tb = ws.p, *ta = ws.p + m * item;
+            u64* go = d_out3 + g0 * terms * 3 * poly;
+            if (int rc = ntt_launch(c, false, tb, d_b2 + g0 * item, m * 2 * L, k.s)) return rc;
+            if (terms) if (int rc = ntt_launch(c, false, ta, d_a2 + g0 * terms * item, m * terms * 2 * L, k.s)) return rc;
+            if (int rc = mul_complement_kernel_launch(k, go, with_self ? d_self + g0 * 3 * poly : nullptr, ta, tb, m, terms)) return rc;
+            if (int rc = inverse(go, m * terms)) return rc;
+            return with_self ? inverse(d_self + g0 * 3 * poly, m) : (int)DPFHE_SUCCESS;
+        });
+    }
+    // one group does not fit: group by group, b[g]'s transform kept across ranges of that group's numerators; the self product goes with the first range
+    const size_t fit = limit > item ? (limit - item) / item : 0, per = fit == 0 ? 1 : (fit < terms ? fit : terms);
+    if (int rc = ws.alloc((1 + per) * item, "dpfhe_ct_mul_complement (scratch for a range of transformed items)")) return rc;
+    for (size_t g = 0; g < groups; ++g) {
+        u64 *tb = ws.p, *ta = ws.p + item;
+        if (int rc = ntt_launch(c, false, tb, d_b2 + g * item, 2 * L, k.s)) return rc;
+        if (terms == 0) if (int rc = mul_complement_kernel_launch(k, d_out3, d_self + g * 3 * poly, tb, tb, 1, 0)) return rc;   // (with_self: the entry checked)
+        if (int rc = for_slices(terms, per, [&](size_t t0, size_t m) {
+                u64* go = d_out3 + (g * terms + t0) * 3 * poly;
+                if (int rc = ntt_launch(c, false, ta, d_a2 + (g * terms + t0) * item, m * 2 * L, k.s)) return rc;
+                if (int rc = mul_complement_kernel_launch(k, go, with_self && t0 == 0 ? d_self + g * 3 * poly : nullptr, ta, tb, 1, m)) return rc;
+                return inverse(go, m);
+            })) return rc;
+        if (with_self) if (int rc = inverse(d_self + g * 3 * poly, 1)) return rc;
+    }
+    return DPFHE_SUCCESS;
+}
+
+extern "C" int dpfhe_ct_mul_complement(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, const uint64_t* d_kappa, size_t groups, size_t terms,
+                                       int with_self, uint32_t flags, void* stream) {
+    static const char* what = "dpfhe_ct_mul_complement";
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (flags & ~(DPFHE_IN_NTT | DPFHE_OUT_NTT)) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag");
+    if (terms == 0 && !with_self) return fail(DPFHE_INVALID_ARGUMENT, what, "terms must be at least 1 when there is no self product");
+    if (groups == 0) return DPFHE_SUCCESS;
+    if (!d_out3 || !d_b2 || !d_kappa || (terms && !d_a2) || misaligned(d_out3) || misaligned(d_a2) || misaligned(d_b2) || misaligned(d_kappa))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n, poly = L * n;
+    // sizes first (a product that wraps size_t would pass the overlap test): every count below stays under 2^31 residue polynomials
+    if (groups > kMaxGrid || terms > kMaxGrid || groups * (terms + 1) > kMaxGrid / (3 * L) || mul_complement_grid(groups, L, n) > kMaxGrid ||
+        !ntt_grid_fits(c, groups * (terms + 1) * 3 * L))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "groups * (terms + 1) too large for one launch");
+    const size_t out_words = groups * (terms + (with_self ? 1 : 0)) * 3 * poly;
+    if ((terms && overlaps(d_out3, out_words, d_a2, groups * terms * 2 * poly)) || overlaps(d_out3, out_words, d_b2, groups * 2 * poly) || overlaps(d_out3, out_words, d_kappa, L))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an operand");
+    DPFHE_ON_DEVICE(c, what);
+    MulComplementCall k{c, flags, static_cast<hipStream_t>(stream), d_kappa};
+    return ct_mul_complement_composed(k, d_out3, d_a2, d_b2, groups, terms, with_self != 0);
 }
 
 // diagnostics: the quad form with per-workgroup timestamps (kernels.h ct_mul_quad_kernel<..., TRACE>); FoldArith contexts at N = 4096

@@ -1,7 +1,7 @@
 // fhe_api.cpp - deeppowers::fhe facade over the C ABI (include/dpfhe.h): parameters, contexts, buffers and their wire formats, the evaluator and the
 // communicator.  Plain C++17 (g++); the only HIP it touches is the runtime API for buffer ownership.  The other roles of the facade, all built into the
 // same libdpfhe_api.so: fhe_keys.cpp (everything that holds or draws secrets), fhe_keyswitch.cpp, fhe_encode.cpp, fhe_packed.cpp (kBabyShiftDefault
-// lives there), fhe_polynomial.cpp, fhe_invsqrt.cpp, fhe_product_sum.cpp; fhe_internal.h is what they share.
+// lives there), fhe_polynomial.cpp, fhe_invsqrt.cpp, fhe_product_sum.cpp, fhe_divide.cpp; fhe_internal.h is what they share.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -330,6 +330,56 @@ void HybridKeySwitcher::multiply_sum_lincomb_rescale_range(const Ciphertext& a, 
     impl_->product_step({"HybridKeySwitcher::multiply_sum_lincomb_rescale", true, groups, terms, b_shared, &weights, &addends}, a, a_first, b, b_first, out, out_first, s);
 }
 
+// ---- products with a shared complement factor: dpfhe_ct_mul_complement into the object's scratch, one key switch and one rounding per product ----------------
+class __attribute__((visibility("hidden"))) ComplementConstant::Impl {
+public:
+    const Context* ctx = nullptr;
+    int64_t kappa = 0;
+    uint64_t* d_kappa = nullptr;   // [Ld]
+    ~Impl() { if (d_kappa) (void)hipFree(d_kappa); }
+};
+
+ComplementConstant::ComplementConstant(const Context& data_ctx, int64_t kappa) : impl_(new Impl) {
+    if (kappa < 0 || kappa >= ((int64_t)1 << 62)) throw Exception(ErrorCode::INVALID_ARGUMENT, "ComplementConstant: kappa in [0, 2^62)");
+    const std::vector<uint64_t> w = signed_weight_rows(data_ctx.params(), {kappa}, 1);   // (no constant row: kappa lives at the INPUT's scale)
+    impl_->ctx = &data_ctx;
+    impl_->kappa = kappa;
+    impl_->d_kappa = device_alloc<uint64_t>(data_ctx.device_id(), w.size());
+    hip_check(hipMemcpy(impl_->d_kappa, w.data(), w.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "hipMemcpy H2D");
+}
+ComplementConstant::~ComplementConstant() = default;
+int64_t ComplementConstant::value() const { return impl_->kappa; }
+const Context& ComplementConstant::context() const { return *impl_->ctx; }
+const uint64_t* ComplementConstant::data() const { return impl_->d_kappa; }
+
+void HybridKeySwitcher::multiply_complement_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t groups, size_t terms,
+                                                          bool with_self, const ComplementConstant& kappa, Ciphertext& out, size_t out_first, Stream* s) const {
+    const std::string what = "HybridKeySwitcher::multiply_complement_rescale";
+    const Context& data = *impl_->data_ctx;
+    const FheParams& pd = data.params();
+    const size_t Ld = pd.n_limbs(), n = pd.n(), in_words = 2 * Ld * n, out_words = 2 * (Ld - 1) * n, items = groups * (terms + (with_self ? 1 : 0));
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, what + ": no data limb left to drop");
+    if (terms == 0 && !with_self) throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": at least one term, or the self product");
+    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+        a_first + groups * terms > a.batch() || b_first + groups > b.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": 2-component coefficient-domain ciphertexts on the data context, groups * terms items of a and groups items of b");
+    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + items > out.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for groups * terms (+ groups) items");
+    const FheParams& pk = kappa.context().params();
+    if (pk.log2_n != pd.log2_n || pk.moduli != pd.moduli || kappa.context().device_id() != data.device_id())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": kappa built on the data context");
+    if (groups == 0) return;
+    grow_scratch(impl_->scratch_product, items, [&](size_t m) { return new Ciphertext(data, 3, m); });
+    grow_scratch(impl_->scratch_work, items, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul_complement(handle_of(data), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, kappa.data(), groups,
+                                  terms, with_self ? 1 : 0, 0, s),
+          "dpfhe_ct_mul_complement");
+    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                           impl_->scratch_work->data(), items, s),
+          "dpfhe_relinearize_rescale_hybrid");
+    out.set_ntt(false);
+}
+
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
 const Context& HybridKeySwitcher::data_context() const { return *impl_->data_ctx; }
 

@@ -1,4 +1,4 @@
-// kernels_mul.h - the multiply at ring degrees above 8192, and sums of products at every ring degree (device).  Included by cabi_mul.hip only.
+// kernels_mul.h - the multiply at ring degrees above 8192, and sums of products and complement products at every ring degree (device).  Included by cabi_mul.hip only.
 //
 // The fused multiply kernels of kernels.h keep whole polynomials in one workgroup's registers and LDS, which stops at
 // N = 8192 (one 1024-thread workgroup at N = 16384 has 128 VGPRs per thread; four polynomials of 16 words per thread do not fit).
@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "modarith.h"
+#include "mul_complement.h"
 #include "mul_sum.h"
 #include "workmap.h"
 
@@ -92,6 +93,58 @@ __global__ __launch_bounds__(256) void tensor3_sum_kernel(u64* __restrict__ out3
     *reinterpret_cast<U64x2*>(po) = d0;
     *reinterpret_cast<U64x2*>(po + poly) = d1;
     *reinterpret_cast<U64x2*>(po + 2 * poly) = d2;
+}
+
+// Products that share a COMPLEMENT factor, one pass (Goldschmidt's n_j <- n_j F, D <- D F with F = 2 - D): per group g
+//   f = (kappa_l - b0, -b1),   out3[g * terms + k] = a[g][k] (x) f  (k < terms),   out_self[g] = b[g] (x) f  (when out_self is not null),
+// NTT domain, canonical in and out (mul_complement.h holds the lane arithmetic).  a2: [groups][terms][2][L][N]; b2: [groups][2][L][N]; kappa: [L] canonical
+// residues; out3: [groups * terms][3][L][N]; out_self: [groups][3][L][N] or null.  The factor is never written and never transformed: the lane forms it ONCE
+// per group from b's two words and walks the group's items, kMulSumDepth items' loads (8 x 16 bytes per lane) in flight before the first is used, three
+// 16-byte stores per item; the self product takes its operand from the registers b already sits in.  One workgroup per (group, limb, 512-word chunk): the
+// grid is mul_complement_grid (workmap.h).  Traffic per group and limb in rows of N words: 2 terms + 2 read, 3 (terms + self) written.
+template <class Arith>
+__global__ __launch_bounds__(256) void tensor3_complement_kernel(u64* __restrict__ out3, u64* __restrict__ out_self, const u64* __restrict__ a2,
+                                                                 const u64* __restrict__ b2, const u64* __restrict__ kappa, const LimbConst* lcs, int n_limbs, int n,
+                                                                 int chunks, int terms) {
+    typedef MulComplementLane<Arith> Lane;
+    const ChunkWork wk = chunk_work(blockIdx.x, chunks, n_limbs);
+    const int chunk = wk.chunk, limb = wk.limb;
+    const size_t group = wk.poly;
+    const int w0 = chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const LimbConst lc = lcs[limb];
+    const u64 kap = kappa[limb];
+    const size_t poly = (size_t)n_limbs * n, off = (size_t)limb * n + w0;
+    const u64* pb = b2 + group * 2 * poly + off;
+    const u64* pa = a2 + group * (size_t)terms * 2 * poly + off;
+    u64* po = out3 + group * (size_t)terms * 3 * poly + off;
+    const U64x2 b0 = *reinterpret_cast<const U64x2*>(pb), b1 = *reinterpret_cast<const U64x2*>(pb + poly);
+    const typename Lane::Factor fa = Lane::factor(b0.a, b1.a, kap, lc), fb = Lane::factor(b0.b, b1.b, kap, lc);
+    auto product = [&](u64* o, const U64x2& x0, const U64x2& x1) {
+        U64x2 d0, d1, d2;
+        Lane::item(x0.a, x1.a, fa, lc, d0.a, d1.a, d2.a);
+        Lane::item(x0.b, x1.b, fb, lc, d0.b, d1.b, d2.b);
+        *reinterpret_cast<U64x2*>(o) = d0;
+        *reinterpret_cast<U64x2*>(o + poly) = d1;
+        *reinterpret_cast<U64x2*>(o + 2 * poly) = d2;
+    };
+    int k = 0;
+    for (; k + kMulSumDepth <= terms; k += kMulSumDepth) {
+        U64x2 x0[kMulSumDepth], x1[kMulSumDepth];
+#pragma unroll
+        for (int u = 0; u < kMulSumDepth; ++u) {
+            const size_t t = (size_t)(k + u) * 2 * poly;
+            x0[u] = *reinterpret_cast<const U64x2*>(pa + t); x1[u] = *reinterpret_cast<const U64x2*>(pa + t + poly);
+        }
+#pragma unroll
+        for (int u = 0; u < kMulSumDepth; ++u) product(po + (size_t)(k + u) * 3 * poly, x0[u], x1[u]);
+    }
+    for (; k < terms; ++k) {   // the ragged end: fewer than kMulSumDepth items
+        const size_t t = (size_t)k * 2 * poly;
+        const U64x2 x0 = *reinterpret_cast<const U64x2*>(pa + t), x1 = *reinterpret_cast<const U64x2*>(pa + t + poly);
+        product(po + (size_t)k * 3 * poly, x0, x1);
+    }
+    if (out_self) product(out_self + group * 3 * poly + off, b0, b1);
 }
 
 }  // namespace dpfhe

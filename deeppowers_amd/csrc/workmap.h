@@ -204,6 +204,9 @@ constexpr size_t relin_rescale_grid(size_t batch, size_t n_data_limbs, size_t n)
 // the grid of a sum of tensor products (kernels_mul.h tensor3_sum_kernel): chunk_work with the GROUP in the polynomial's place - a workgroup owns one chunk of one
 // limb of all three output rows of its group
 constexpr size_t mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return groups * n_limbs * (size_t)chunks_of(n); }
+// the grid of the complement products (kernels_mul.h tensor3_complement_kernel): the same map - a workgroup owns one chunk of one limb of its group's factor and of
+// all three rows of every product of the group, however many items the group has and whether the self product is among them
+constexpr size_t mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return groups * n_limbs * (size_t)chunks_of(n); }
 
 // ------------------------------------------------------------------------------------------------
 // The last pass of a rotate-and-add step (kernels_rotate.h rotate_add_pass_kernel): outer = (item, data limb), inner = slice of that residue polynomial's

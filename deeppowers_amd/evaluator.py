@@ -345,6 +345,38 @@ class Evaluator:
                                                self._sp(stream)), "dpfhe_ct_mul_sum")
         return Ciphertext(out, out_ntt)
 
+    def multiply_complement(self, a: Ciphertext | None, b: Ciphertext, kappa: torch.Tensor, terms: int, with_self: bool = True, out_ntt: bool | None = None,
+                            out: torch.Tensor | None = None, stream=None) -> Ciphertext:
+        """Every item of a group times the group's complement factor F_g = kappa X^0 - b[g] (dpfhe_ct_mul_complement: a Goldschmidt step's products; F is
+        never written and never transformed).  a: groups * terms items, group-major (None when terms is 0); b: groups items; kappa: [L] int64 canonical
+        residues on the device, word l = kappa mod q_l.  Returns groups * terms items of 3 components, then, with_self, the groups products b[g] (x) F_g.  The
+        words of negate, kappa added to coefficient 0 of component 0, and multiply of each item with that factor."""
+        p = self.ctx.params
+        terms = int(terms)
+        if b.size != 2 or (terms and (a is None or a.size != 2)):
+            raise _cabi.DpfheError(2000, "multiply_complement expects 2-component ciphertexts")
+        if terms and a.is_ntt != b.is_ntt:
+            raise _cabi.DpfheError(2002, "operands are in different domains (is_ntt mismatch)")
+        self._chk(b.data)
+        groups = b.batch
+        if terms < 0 or (terms == 0 and not with_self) or (terms and a.batch != groups * terms):
+            raise _cabi.DpfheError(2000, "multiply_complement: b holds groups items, a groups * terms; no terms needs with_self")
+        if terms:
+            self._chk(a.data)
+        if kappa.dtype != torch.int64 or not kappa.is_contiguous() or kappa.device != b.data.device or tuple(kappa.shape) != (p.n_limbs,):
+            raise _cabi.DpfheError(2000, "multiply_complement: kappa is a contiguous int64 [L] tensor on the operands' device")
+        out_ntt = b.is_ntt if out_ntt is None else bool(out_ntt)
+        items = groups * (terms + (1 if with_self else 0))
+        if out is None:
+            out = self._empty((items, 3, p.n_limbs, p.n), stream)
+        self._chk(out)
+        if out.numel() != items * 3 * p.words_per_rns_poly():
+            raise _cabi.DpfheError(2000, "multiply_complement: out holds groups * (terms + with_self) items of 3 components")
+        flags = (_cabi.IN_NTT if b.is_ntt else 0) | (_cabi.OUT_NTT if out_ntt else 0)
+        _cabi.check(self._lib.dpfhe_ct_mul_complement(self.ctx.handle, out.data_ptr(), a.data.data_ptr() if terms else None, b.data.data_ptr(), kappa.data_ptr(),
+                                                      groups, terms, 1 if with_self else 0, flags, self._sp(stream)), "dpfhe_ct_mul_complement")
+        return Ciphertext(out, out_ntt)
+
     def matvec_scalar(self, w: torch.Tensor, x: Ciphertext, out: torch.Tensor | None = None, stream=None) -> Ciphertext:
         """y_i = sum_j w_ij * x_j with scalar weights w: [rows][cols][L] residues (either domain)."""
         p = self.ctx.params

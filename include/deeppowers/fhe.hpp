@@ -515,6 +515,25 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// ComplementConstant: the constant kappa of HybridKeySwitcher::multiply_complement_rescale_range as residues on the device ([Ld], word l = kappa mod q_l: the
+// d_kappa of dpfhe_ct_mul_complement), uploaded once at construction.  kappa is the integer the factor kappa X^0 - b complements b to: at b's scale sigma
+// the encoding of the constant kappa / sigma in every slot (Goldschmidt's 2 is kappa = llround(2 sigma)).  INVALID_ARGUMENT for kappa < 0 or kappa >= 2^62.
+// data_ctx must outlive the object.
+class ComplementConstant {
+public:
+    ComplementConstant(const Context& data_ctx, int64_t kappa);
+    ~ComplementConstant();
+    ComplementConstant(const ComplementConstant&) = delete;
+    ComplementConstant& operator=(const ComplementConstant&) = delete;
+    int64_t value() const;                // kappa
+    const Context& context() const;       // data_ctx
+    const uint64_t* data() const;         // device, [Ld]
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
 // one addend of multiply_lincomb_rescale_range: items first .. first + count - 1 of ct
 struct LincombTerm {
     const Ciphertext* ct;
@@ -575,6 +594,18 @@ public:
     void multiply_sum_lincomb_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, bool b_shared, size_t groups, size_t terms,
                                             const ScalarWeights& weights, const std::vector<LincombTerm>& addends, Ciphertext& out_next_level, size_t out_first,
                                             Stream* stream = nullptr) const;
+    // Products that share a COMPLEMENT factor, at the next level (one Goldschmidt division step n_j <- n_j F, D <- D F with F = 2 - D): with
+    // F_g = kappa X^0 - b_g, b_g = item b_first + g of b, and a_{g,k} = item a_first + g * terms + k of a,
+    //   out item out_first + g * terms + k      = round(relinearize(a_{g,k} * F_g) / q_last),   g < groups, k < terms,
+    //   out item out_first + groups * terms + g = round(relinearize(b_g * F_g) / q_last)        when with_self:
+    // the numerators group-major, then the denominators - the next step's two item ranges.  dpfhe_ct_mul_complement writes the groups * terms (+ groups) tensor
+    // products into the object's scratch - F is never written and never transformed - then dpfhe_relinearize_rescale_hybrid runs over all of them.  Word for
+    // word Evaluator::negate on b_g, Evaluator::add_plain of the constant polynomial kappa X^0, and multiply_rescale_range against that factor copied out per
+    // item.  At scales s_a of a and sigma of b, with kappa = llround(c sigma), the results have scales s_a sigma / q_last and sigma^2 / q_last and hold
+    // a (c - b) and b (c - b).  a and b may be one buffer; terms may be 0 with with_self (the denominators alone).  kappa: on data_ctx.  The stream contract is
+    // multiply_rescale_range's.  INVALID_ARGUMENT for terms == 0 without with_self, ranges outside their buffers, a kappa of another context.
+    void multiply_complement_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t groups, size_t terms, bool with_self,
+                                           const ComplementConstant& kappa, Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
     // many rotations in one pass (dpfhe_rotate_hybrid_batch): out item out_first + i = sigma_{elts[i]} of in item i, or of THE
     // item of `in` when it holds one.  All elements must have been added; the keys of a given element list are packed
     // back to back once and cached.
@@ -995,6 +1026,80 @@ public:
     // scale(K).  Enqueues only; the scratch (v at the lower levels, the products, the iterates) belongs to the object and grows only for a larger T than
     // before; one apply() at a time per object and per key switcher.
     void apply(const Ciphertext& v, const Ciphertext& y0, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxDivide: slot-wise y_{g,j} ~ n_{g,j} / D_g in the approximate family for G groups of T numerators that share a denominator (a softmax's e_j / sum e),
+// by K Goldschmidt steps
+//     F = 2 - D;    n_j <- n_j F  (j < T);    D <- D F
+// on a denominator the caller has brought near 1: D_K = 1 - (1 - D_0)^(2^K) and n_K = (n_0 / D_0) D_K, so K steps leave the relative residual (1 - D_0)^(2^K).
+// A constant first guess c ~ 1 / d costs no level - it is a reinterpretation of the scale, s_d d = (s_d / c)(c d): encrypt d at scale s_d and pass
+// den_scale = s_d / c.  For d in [lo, hi], guess(lo, hi) = 2 / (lo + hi) puts c d in [1 - rho, 1 + rho], rho = (hi - lo) / (hi + lo), and residual(lo, hi, K) =
+// rho^(2^K).  Relinearisation keys only.
+//
+// Levels.  K key switchers, input level first, each one limb below the last: ONE level per step.  Step n runs on levels[n] in one
+//   HybridKeySwitcher::multiply_complement_rescale_range: all T + 1 products of a group share the factor F = kappa_n X^0 - D, which is never written and never
+//   transformed; its output - the G T numerators, then the G denominators - is the next step's input as it stands.  The last step runs without the self product.
+// Scales, in exactly these double operations (tests/divide_model.py mirrors them):  sigma_0 = den_scale, nu_0 = num_scale; per step n, q_n the prime level n drops:
+//     kappa_n = llround(2.0 * sigma_n);    sigma_{n+1} = (sigma_n * sigma_n) / (double)q_n;    nu_{n+1} = (nu_n * sigma_n) / (double)q_n.
+//   kappa_n read at scale sigma_n is the constant 2.  sigma_{n+1} / q = (sigma_n / q)^2: a mismatch sigma_0 / q = 1 + delta grows like (1 + delta)^(2^n), so
+//   den_scale belongs within about a percent of the primes (consult den_scale(n) before choosing limbs); the numerators' scale is free.  INVALID_ARGUMENT when
+//   the contexts do not form the chain, a scale is not finite and positive, a kappa_n >= 2^62, or any sigma_n or nu_n, n <= K, lies outside [2^20, 2^62).
+//
+// Error bound.  ApproxPolynomial's notation and tools T1 - T4: u = 2^-53, H = (N + 1) / 2 (T3), per level n: L_n its data limbs, rho_n = max_j q_j / P_n,
+//   K_n = 21 L_n N rho_n (T4).  Dm a bound on every D_n and X a bound on every |n_{j,n}| (n <= K, of the real iteration and of its float64 evaluation);
+//   every D_n lies in [0, Dm] with Dm <= 2 - the iteration's own requirement, it converges for D_0 in (0, 2) only - so that |F_n| = |2 - D_n| <= Fm = 2
+//   (error_bound: INVALID_ARGUMENT for Dm > 2); Bd and Bn the coefficient errors of the phases of D_0 and of the numerators.  The phase of D_n has slot
+//   sigma_n D_n + e_n with D_n the REAL iterate of the values encrypted, |e_n| <= E_n, E_0 = N Bd (T1); the phase of a numerator has slot nu_n n_n + g_n,
+//   |g_n| <= G_n, G_0 = N Bn.  The constant kappa_n X^0 is kappa_n in every slot, exactly, and |kappa_n - 2 sigma_n| <= 1/2 (llround; the doubling is exact):
+//   the factor's phase has slot sigma_n F_n + f_n with |f_n| <= E_n + 1/2.  One recurrence per step for each track, by ApproxPolynomial's D_k rule (slots
+//   multiply (T2), the relinearisation adds K_n + H per coefficient after its division by P, the division by q_n divides all of it and adds H, a scale as a
+//   double is off by at most 4 u of itself: two roundings and the conversion of q_n):
+//     E_{n+1} = (sigma_n (Dm (E_n + 1/2) + Fm E_n) + E_n (E_n + 1/2) + N (K_n + H)) / q_n + N H + 4 u sigma_{n+1} Dm
+//     G_{n+1} = (nu_n X (E_n + 1/2) + sigma_n Fm G_n + G_n (E_n + 1/2) + N (K_n + H)) / q_n + N H + 4 u nu_{n+1} X
+//   (the last step needs no E_K).  pre = G_K / nu_K; the client's decode adds u8 N (X + pre), u8 = 8 log2(N) u; and the float64 iteration the bound is stated
+//   against is itself off the real one by Phi_K:  with Psi_n the distance of the float64 D_n, Psi_0 = Phi_0 = 0,
+//     Psi_{n+1} = (Fm + Dm) Psi_n + 4 u Dm Fm;    Phi_{n+1} = Fm Phi_n + X Psi_n + 4 u X Fm
+//   (each step's derivative; its roundings - one for F, one per product - with a factor 2 of slack for the second-order terms).
+//   error_bound(Dm, X, Bd, Bn) = pre + u8 N (X + pre) + Phi_K bounds |decoded slot - n_K| for every slot, numerator and group, n_K the float64 iteration
+//   F = 2.0 - D; n = n * F; D = D * F from the values actually encrypted (D_0 = c d, the denominator as read at den_scale), PROVIDED no phase wraps: the phases
+//   before a rescale are about nu_n sigma_n X Fm and sigma_n^2 Dm Fm, and a quotient near 1 at a scale near the primes needs TWO limbs on out_ctx (one limb
+//   holds |phase| < q / 2 only, and nu_K |y| plus its noise comes within a factor two of that).  How far K steps are from the true quotient is Goldschmidt's
+//   own closed form above - |n / D| residual - and is not part of the bound.  Worst case throughout.
+//
+// Exact on a transparent input (c1 = 0: every relinearisation digit is zero): with mu_D and mu_j the integer polynomials of D and the numerators and (*) the
+//   product in Z[X] / (X^N + 1),
+//     mu_F = kappa_n X^0 - mu_D (kappa_n on coefficient 0),    mu_j' = round(mu_j (*) mu_F / q_n),    mu_D' = round(mu_D (*) mu_F / q_n),
+//   c0_out = mu_j after K steps mod q_l,  c1_out = 0, word for word (tests/divide_model.py states it on Python integers, tests/test_gpu_divide_words.py holds
+//   the device to it).
+class ApproxDivide {
+public:
+    // levels: K key switchers (K >= 1), input level first, levels[r] on the context of the input's limbs without the last r (same ring, same device, same
+    // secret); out_ctx: levels.back()'s data context without its last limb.  Everything referenced must outlive the object.
+    ApproxDivide(const std::vector<HybridKeySwitcher*>& levels, const Context& out_ctx, double num_scale, double den_scale);
+    ~ApproxDivide();
+    ApproxDivide(const ApproxDivide&) = delete;
+    ApproxDivide& operator=(const ApproxDivide&) = delete;
+    size_t iterations() const;            // K
+    size_t depth() const;                 // K: the limbs between (n, D) and y
+    double den_scale(size_t n) const;     // sigma_n, n <= K
+    double num_scale(size_t n) const;     // nu_n, n <= K; num_scale(K) is the output's
+    int64_t kappa(size_t n) const;        // kappa_n, n < K
+    // 2 / (lo + hi): the constant guess for denominators in [lo, hi], 0 < lo <= hi;  ((hi - lo) / (hi + lo))^(2^K): what K steps leave of it
+    static double guess(double lo, double hi);
+    static double residual(double lo, double hi, size_t K);
+    // the bound derived above: max_abs_den = Dm, max_abs_quotient = X, den_noise_bound = Bd, num_noise_bound = Bn
+    double error_bound(double max_abs_den, double max_abs_quotient, double den_noise_bound, double num_noise_bound) const;
+    // ... and without a device: data_moduli are the input level's limbs (at least K + 1), special_primes one P per level (K)
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, const std::vector<uint64_t>& special_primes, double num_scale,
+                              double den_scale, double max_abs_den, double max_abs_quotient, double den_noise_bound, double num_noise_bound);
+    // num: G T items, group-major, and den: G items (G >= 1, T >= 1), on levels[0]'s data context (2 components, coefficient domain, scales num_scale and
+    // den_scale); y: G T items on out_ctx, scale num_scale(K).  Enqueues only; the scratch (the iterates of every level) belongs to the object and grows only
+    // for a larger batch than before; one apply() at a time per object and per key switcher.
+    void apply(const Ciphertext& num, const Ciphertext& den, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:
     class Impl;

@@ -187,6 +187,27 @@ int dpfhe_ct_mul(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const u
 int dpfhe_ct_mul_sum(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t groups, size_t terms, size_t b_groups, uint32_t flags,
                      void* stream);
 
+/* -- products that share a COMPLEMENT factor (a Goldschmidt division step n_j <- n_j F, D <- D F with F = 2 - D, at D's scale): per group g the factor is
+ *   F_g = kappa X^0 - b[g] = (kappa - b0, -b1)      - dpfhe_negate on b[g], kappa added to coefficient 0 of component 0 -
+ * and every item of the group is multiplied by it; F is never written and never transformed (the transform of kappa X^0 is kappa in every word).
+ *   d_a2: [groups][terms][2][L][N];  d_b2: [groups][2][L][N];  d_kappa: [L] canonical residues ON THE DEVICE, word l = kappa mod q_l (dpfhe_lincomb_rescale's d_w convention);
+ *   d_out3: [groups * terms + (with_self ? groups : 0)][3][L][N]:  d_out3[g * terms + k] = a[g][k] (x) F_g for k < terms, group-major, then, with_self != 0,
+ *   d_out3[groups * terms + g] = b[g] (x) F_g, with (x) dpfhe_ct_mul's (x0 y0, x0 y1 + x1 y0, x1 y1) in R_q.  A relinearisation + rescale over the whole buffer
+ *   leaves the next step's numerators and denominators as two contiguous item ranges.
+ * flags: dpfhe_ct_mul_sum's.  0 = coefficient domain in and out: the words of dpfhe_negate on b[g], kappa added to coefficient 0 of component 0, and dpfhe_ct_mul
+ * of each item with that factor.  In the NTT domain the constant is kappa in every word.  Every log2_n (8 ... 16) and limb class.
+ * Aliasing: the operands are read-only and may alias each other in any way; d_out3 must overlap none of d_a2, d_b2, d_kappa.
+ * Always composed: batched forward transforms of b and a into the arena of the caller's stream (see "Conventions" - here at EVERY log2_n), one streaming
+ * pass, three inverse transforms per output item.  Scratch: what the transformed operands take, in slices of whole groups that honour
+ * dpfhe_ctx_set_scratch_limit; when one group does not fit, that group's numerators in ranges, b[g]'s transform kept across the ranges.  With DPFHE_IN_NTT
+ * there is no scratch at all (DPFHE_OUT_NTT only skips the inverse transforms, in place).  Enqueues only; allocates only when the stream's arena grows.
+ * Algorithmic traffic of the streaming pass per group and limb, in rows of N words: 2 terms + 2 read, 3 (terms + with_self) written - against 4 (terms + with_self)
+ * read for dpfhe_ct_mul over the items and a factor copied out per item, after two passes that write the factor.  d_a2 is not read when terms == 0 (it may be NULL).
+ * DPFHE_INVALID_ARGUMENT, before the device is touched: a null or misaligned (16 bytes) buffer, terms == 0 without with_self, an unknown flag, d_out3
+ * overlapping an operand or d_kappa, groups * (terms + 1) too large for one launch.  groups == 0 returns success. */
+int dpfhe_ct_mul_complement(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, const uint64_t* d_kappa, size_t groups, size_t terms,
+                            int with_self, uint32_t flags, void* stream);
+
 /* diagnostics (tools/ctmul_trace.py): the "quad" form of dpfhe_ct_mul(flags = 0) with timestamps - thread 0 of workgroup w (= pair w / L, limb w % L)
  * writes d_trace[12 w .. 12 w + 11]: s_memrealtime (100 MHz) at start / first operand word arrived / forward transforms done / tensor
  * product done / inverse transforms done / stores issued / stores drained, then HW_ID | XCC_ID << 32, then prologue done / first operand's

@@ -88,6 +88,8 @@ void wm_chunk_decode(unsigned n_ids, int chunks, int n_limbs, i64* out) {
 u64 wm_relin_rescale_grid(size_t batch, size_t n_data_limbs, size_t n) { return relin_rescale_grid(batch, n_data_limbs, n); }
 // a sum of tensor products: the grid; ids decode through wm_chunk_decode over all limbs, the group in the polynomial's place
 u64 wm_mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return mul_sum_grid(groups, n_limbs, n); }
+// products with a shared complement factor: the grid; ids decode through wm_chunk_decode over all limbs, the group in the polynomial's place
+u64 wm_mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return mul_complement_grid(groups, n_limbs, n); }
 
 // last pass of a rotate-and-add step: rows (item, limb, slice, live)
 unsigned wm_rotate_add_slices(size_t n) { return RotateAddMap::slices(n); }
