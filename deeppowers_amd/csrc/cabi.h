@@ -288,12 +288,7 @@ inline bool inverse_mod(uint64_t t, uint64_t q, uint64_t& inv) {
     return true;
 }
 
-// g^-1 mod 2N by Newton iteration (g odd): x <- x (2 - g x)
-inline unsigned galois_inverse(unsigned g, unsigned two_n) {
-    unsigned inv = 1;
-    for (int i = 0; i < 5; ++i) inv *= 2u - g * inv;
-    return inv & (two_n - 1u);
-}
+// (g^-1 mod 2N for the coefficient-domain rotations: workmap.h galois_inverse)
 
 // ---- launches one family borrows from another: arguments validated, device selected by the caller ------------------------------------------------------------
 // batched transform of `items` RNS polynomials over the first `limbs_used` limbs (limbs_used = 0: all)

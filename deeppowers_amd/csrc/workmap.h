@@ -123,6 +123,16 @@ struct MatvecMap {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The coefficient-domain rotations gather word k of sigma_g(a) from position k g^-1 mod 2N (kernels_rotate.h): their launchers invert the element here.
+// g^-1 mod 2N by Newton iteration (g odd): x <- x (2 - g x) doubles the correct low bits, 1 -> 32 in five steps.  Host only.
+// ------------------------------------------------------------------------------------------------
+inline unsigned galois_inverse(unsigned g, unsigned two_n) {
+    unsigned inv = 1;
+    for (int i = 0; i < 5; ++i) inv *= 2u - g * inv;
+    return inv & (two_n - 1u);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Baby steps of the double-hoisted products (kernels_rotate.h hoisted_qp_stream_kernel, hoisted_qp_upfront_kernel): a workgroup is 256 threads x
 // `pairs` 16-byte pairs = one segment of one (rotation, limb, token).  outer = combo = (limb, SOURCE segment), inner = (rotation group, rotation in
 // the group, token): XCD combo % 8 gets, one block of kQpRotGroup rotations x n_items tokens at a time, all workgroups of one combo - every key

@@ -21,6 +21,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from galois_elements import edge_elements
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = C.POINTER(C.c_int64)
 ROT_MAJOR = 0x80000000
@@ -191,8 +193,10 @@ def _src_pos(g, p, log2n):
 
 
 def _galois_elts(log2n):
+    """3, 5, 2N - 1, 3^7, then the rest of galois_elements.edge_elements (the whole group and the other maps: tests/test_galois_elements_cpu.py)"""
     two_n = 2 << log2n
-    return (3, 5, two_n - 1, pow(3, 7, two_n))
+    first = (3, 5, two_n - 1, pow(3, 7, two_n))
+    return first + tuple(g for g in edge_elements(log2n) if g not in first)
 
 
 @pytest.mark.parametrize("log2n,pairs", list(itertools.product((8, 10, 13), (1, 2))))

@@ -431,6 +431,69 @@ extern "C" int emu_ctx_ntt_inv_galois(int log2n, int n_limbs, const u64* moduli,
     if (form == kFormGeneric || !c.fold) return run(ShoupArith{});
     return run(FoldArith{});
 }
+// ---- the Galois gather alone: which word does every output position read? ------------------------------------------------------------------------------
+// The kernels' own gather_plan / stage_load / stage_write / gather_read on the words in[i] = first + i of one N-word block, wave by wave as above (the
+// kernel stages from its FIRST lane's region), with no transform behind them: out[p] = the word position p receives.  -7: a wave's staged range leaves
+// [0, N) of the block, its lanes disagree on the shift, or an LDS address leaves the workgroup's rows.
+template <class B>
+static int emu_gather_block(unsigned g, unsigned h, u64 first, long long* out) {
+    constexpr int N = B::G::N, T = B::T, E = B::E;
+    static_assert(B::kLdsIO, "the kernels' gather path");
+    std::vector<u64> in((size_t)N), lds(B::G::lds_words(), 0xDEADBEEFDEADBEEFull);
+    for (int i = 0; i < N; ++i) in[(size_t)i] = first + (u64)i;
+    std::vector<unsigned> addr((size_t)64 * E);
+    auto A = [&](int lane) -> unsigned(&)[E] { return *reinterpret_cast<unsigned(*)[E]>(&addr[(size_t)lane * E]); };
+    for (int w = T / 64 - 1; w >= 0; --w) {
+        long shift0 = 0;
+        for (int tid = w * 64; tid < (w + 1) * 64; ++tid) {
+            const long shift = B::gather_plan(tid, g, h, A(tid & 63));
+            if (tid == w * 64) shift0 = shift;
+            const long lo = (long)w * 64 * E + shift;
+            if (shift != shift0 || lo < 0 || lo + 64 * E > N) return -7;
+            for (int k = 0; k < E; ++k) if (A(tid & 63)[k] >= (unsigned)B::G::lds_words()) return -7;
+            u64 v[E];
+            B::stage_load(tid, v, in.data() + shift0);
+            B::stage_write(tid, v, lds.data());
+        }
+        for (int tid = w * 64; tid < (w + 1) * 64; ++tid) {
+            u64 x[E];
+            B::gather_read(x, lds.data(), A(tid & 63));
+            for (int k = 0; k < E; ++k) out[(size_t)tid * E + k] = (long long)x[k];
+        }
+    }
+    return 0;
+}
+// kernels.h ntt_inv_galois_kernel's gather at N = 1024 ... 16384: h = (g - 1) / 2.  out[p], p < N: the source position.  -1: no such kernel.
+extern "C" int emu_gather_map(int log2n, unsigned g, long long* out) {
+    const unsigned h = (g - 1u) >> 1;
+    switch (log2n) {
+        case 10: return emu_gather_block<NttBody<FoldArith, 10, kLoge>>(g, h, 0, out);
+        case 11: return emu_gather_block<NttBody<FoldArith, 11, kLoge>>(g, h, 0, out);
+        case 12: return emu_gather_block<NttBody<FoldArith, 12, kLoge>>(g, h, 0, out);
+        case 13: return emu_gather_block<NttBody<FoldArith, 13, kLoge>>(g, h, 0, out);
+        case 14: return emu_gather_block<NttBody<FoldArith, 14, kLoge>>(g, h, 0, out);
+        default: return -1;
+    }
+}
+// kernels.h ntt_inv_galois_sub_kernel's gather at N = 32768, 65536: sub-block b reads sub-block blocks[b] (galois_sub_block) with that block's h.
+// out[b N2 + k] = blocks[b] N2 + the index read inside it.
+template <int LOG_N1>
+static int emu_gather_split(unsigned g, long long* out, long long* blocks) {
+    typedef NttBody<FoldArith, kSplitLog2N2, 4> B;
+    for (unsigned b = 0; b < (1u << LOG_N1); ++b) {
+        const GaloisSub gs = galois_sub_block<LOG_N1>(g, b, kSplitLog2N2);
+        blocks[b] = (long long)gs.block;
+        if (gs.block >= (1u << LOG_N1)) return -7;
+        if (int rc = emu_gather_block<B>(g, gs.h, (u64)gs.block * B::G::N, out + (size_t)b * B::G::N)) return rc;
+    }
+    return 0;
+}
+extern "C" int emu_gather_map_split(int log2n, unsigned g, long long* out, long long* blocks) {
+    if (log2n == 15) return emu_gather_split<3>(g, out, blocks);
+    if (log2n == 16) return emu_gather_split<4>(g, out, blocks);
+    return -1;
+}
+
 // The bytes dpfhe_ctx_create would upload: which = 0 the context-wide blob, 1 the class blob, 2 the lazy-multiply blob (log2 N = 12 with a fold limb).  Returns the size (0: the context has no class blob), or
 // -2000 for parameters a context rejects; copies the bytes when out holds at least that many, and the LimbClass per limb into limb_cls (n_limbs <= 16).
 extern "C" long emu_ctx_blob(int log2n, int n_limbs, const u64* moduli, const u64* psi, int which, unsigned char* out, size_t cap, unsigned char* limb_cls) {

@@ -12,6 +12,9 @@ struct Tables {   // what the limb helpers of devtables.h read of a DevTables
     int n_sub, n_limbs, n_active;
     unsigned long long active_map;
 };
+template <int LOGN> void src_pos_all(unsigned g, i64* out) {
+    for (unsigned p = 0; p < (1u << LOGN); ++p) out[p] = galois_src_pos<LOGN>(g, p);
+}
 }  // namespace
 
 extern "C" {
@@ -133,12 +136,24 @@ void wm_transform_decode(unsigned n_ids, int n_sub, int n_limbs, int n_active, u
 
 // Galois source positions of all N output positions; 0, or -1 for a ring degree not compiled here
 int wm_galois_src_pos(int log2n, unsigned g, i64* out) {
-    for (unsigned p = 0; p < (1u << log2n); ++p) {
-        if (log2n == 8) out[p] = galois_src_pos<8>(g, p);
-        else if (log2n == 10) out[p] = galois_src_pos<10>(g, p);
-        else return -1;
+    switch (log2n) {
+        case 8: src_pos_all<8>(g, out); return 0;
+        case 9: src_pos_all<9>(g, out); return 0;
+        case 10: src_pos_all<10>(g, out); return 0;
+        case 11: src_pos_all<11>(g, out); return 0;
+        case 12: src_pos_all<12>(g, out); return 0;
+        case 13: src_pos_all<13>(g, out); return 0;
+        case 14: src_pos_all<14>(g, out); return 0;
+        case 15: src_pos_all<15>(g, out); return 0;
+        case 16: src_pos_all<16>(g, out); return 0;
+        default: return -1;
     }
-    return 0;
+}
+
+// g^-1 mod 2N as the launchers of the coefficient-domain rotations take it; for every odd g < two_n at once: out[(g - 1) / 2]
+unsigned wm_galois_inverse(unsigned g, unsigned two_n) { return galois_inverse(g, two_n); }
+void wm_galois_inverse_all(unsigned two_n, i64* out) {
+    for (unsigned g = 1; g < two_n; g += 2) out[g >> 1] = galois_inverse(g, two_n);
 }
 
 }  // extern "C"
