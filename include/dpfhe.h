@@ -22,6 +22,11 @@
  *   - All data buffers are DEVICE pointers owned by the caller, 16-byte aligned, holding little-endian
  *     u64 words that are canonical residues in [0, q_limb).  Layout: [batch][component][limb][N], contiguous.
  *     "n_rns_polys" counts RNS polynomials (L limbs x N words each); a 2-component ciphertext is 2 of them.
+ *   - sizes: every count (batch, n_rns_polys, rows, items, groups, n_words) is a size_t.  A batch is limited by the launch grid of its entry (2^31 - 1
+ *     workgroups: "too large for one launch"; first_item + batch <= 2^32 for the seeded samplers) and by nothing else - never by its bytes.  Buffers beyond
+ *     4 GiB are supported and tested for every batched entry, buffers beyond 2^32 words (32 GiB) for the flat-indexed ones; the table at the head of
+ *     tests/test_gpu_wide_batch.py says which pointer of which entry crosses which line (three calls whose buffers cannot all pass 4 GiB within the
+ *     test's memory cap hold their smallest buffer past 2 GiB only).
  *   - forward NTT: natural order in, BIT-REVERSED order out, ahat[k] = sum_j a[j] psi^((2 brv(k)+1) j);
  *     inverse NTT: bit-reversed in, natural out, including N^-1.  Outputs are canonical.
  *   - `stream` is a hipStream_t (NULL = the null stream).  Compute calls only enqueue work and never synchronise.  At log2_n <= 13 (every
