@@ -38,6 +38,7 @@ SYMBOLS = {
     "dpfhe_ct_mul": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_ct_mul_sum": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_ct_mul_complement": ([C.c_void_p, _U64P, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32, C.c_void_p], C.c_int),
+    "dpfhe_ct_mul_outer": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p], C.c_int),
     "dpfhe_relinearize": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_relinearize_hybrid": ([C.c_void_p, _U64P, _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_switch_key_hybrid": ([C.c_void_p, _U64P, _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),
@@ -104,6 +105,7 @@ SYMBOLS = {
 }
 
 IN_NTT, OUT_NTT = 1, 2
+OUTER_CAUSAL = 4                  # dpfhe_ct_mul_outer: pairs (i, j <= i) only
 ENCODE_PLAIN, ENCODE_NTT = 1, 2   # dpfhe_encode_slots flags
 ENCODE_REAL = 4                   # dpfhe_encode_complex: real slots
 NOISE_TERNARY, NOISE_CBD21, NOISE_FLOOD = 0, 1, 2   # dpfhe_sample_noise kinds

@@ -2,7 +2,7 @@
 // arithmetic policies and limb classes, and the few launch functions one family borrows from another.  The units of include/dpfhe.h:
 //   cabi_ctx.hip        contexts, their tables, the fused multiply's tuner, the scratch arenas, dpfhe_strerror / dpfhe_last_error
 //   cabi_poly.hip       transforms, coefficient-wise operations, copy                                  (kernels_poly.h)
-//   cabi_mul.hip        ciphertext multiply, its traced form, sums of products                         (kernels_mul.h, mul_sum.h)
+//   cabi_mul.hip        ciphertext multiply, its traced form, sums of products, all-pairs products     (kernels_mul.h, mul_sum.h, mul_outer.h)
 //   cabi_keyswitch.hip  key switching (RNS-digit and hybrid keys), rescales, host twins of the fused rescales  (kernels_keyswitch.h)
 //   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations, the rotate-and-add ladder (kernels_rotate.h, rotate_add.h)
 //   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)

@@ -1,6 +1,6 @@
 // cabi_mul.hip - the C ABI's ciphertext multiply: dpfhe_ct_mul on the fused kernels of kernels.h (launch.h), composed above N = 8192 over
-// kernels_mul.h, its traced diagnostic form, dpfhe_ct_mul_sum (sums of products) and dpfhe_ct_mul_complement (products with a shared complement factor), both
-// composed at every ring degree.  cabi.h lists the other units and states the ABI's conventions.
+// kernels_mul.h, its traced diagnostic form, dpfhe_ct_mul_sum (sums of products), dpfhe_ct_mul_complement (products with a shared complement factor) and
+// dpfhe_ct_mul_outer (all pairs of two operand lists), all three composed at every ring degree.  cabi.h lists the other units and states the ABI's conventions.
 #include "cabi.h"
 #include "kernels_mul.h"
 
@@ -242,6 +242,94 @@ extern "C" int dpfhe_ct_mul_complement(dpfhe_ctx* c, uint64_t* d_out3, const uin
     DPFHE_ON_DEVICE(c, what);
     MulComplementCall k{c, flags, static_cast<hipStream_t>(stream), d_kappa};
     return ct_mul_complement_composed(k, d_out3, d_a2, d_b2, groups, terms, with_self != 0);
+}
+
+// ---- all pairs of two operand lists (include/dpfhe.h dpfhe_ct_mul_outer): always composed, at every ring degree - batched forward transforms of a and of b into
+// the stream's arena (each operand transformed ONCE, not once per pair), tensor3_outer_kernel (kernels_mul.h), three inverse transforms per pair in place.
+
+struct MulOuterCall {
+    dpfhe_ctx* c;
+    uint32_t flags;
+    hipStream_t s;
+    size_t b_total;   // the keys of the whole call: the row length of the full form's output
+    bool causal;
+};
+
+// the scratch plan, in ITEMS of 2 L N words (the header states it): the operands' ranges per launch
+struct MulOuterPlan { size_t a_per, b_per; bool shared; };   // shared: one transform serves both operands (a squaring that fits whole)
+static MulOuterPlan mul_outer_plan(size_t fit, size_t A, size_t B, bool square) {
+    if ((square ? A : A + B) <= fit) return MulOuterPlan{A, B, square};
+    if (A + 1 <= fit) return MulOuterPlan{A, fit - A < B ? fit - A : B, false};   // a whole, b in ranges
+    // a in ranges of whole tiles on half of what fits (one tile at least), b in ranges on the rest (half a tile of keys at least)
+    const size_t tile = (size_t)kMulOuterTile;
+    size_t a_per = fit / 2 / tile * tile;
+    if (a_per < tile) a_per = tile;
+    size_t b_per = fit > a_per ? fit - a_per : 0;
+    if (b_per < tile / 2) b_per = tile / 2;
+    return MulOuterPlan{a_per < A ? a_per : A, b_per < B ? b_per : B, false};
+}
+
+// pa, pb: the transformed rows of the ranges [a_off, a_off + a_count) and [b_off, b_off + b_count); d_out3: the whole output
+static int mul_outer_kernel_launch(const MulOuterCall& k, u64* d_out3, const u64* pa, const u64* pb, size_t a_count, size_t b_count, size_t a_off, size_t b_off) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n;
+    const size_t grid = MulOuterMap::grid(a_count, L, n);   // (<= the whole call's, which the entry checked)
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((tensor3_outer_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, k.s, d_out3, pa, pb, c->lc, (int)L, (int)n, chunks_of(n),
+                           (unsigned)MulOuterMap::tiles(a_count), a_count, b_count, a_off, b_off, k.b_total, (int)k.causal);
+    });
+    return check_launch("outer tensor product kernel launch");
+}
+
+static int ct_mul_outer_composed(const MulOuterCall& k, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t A, size_t B) {
+    dpfhe_ctx* c = k.c;
+    const size_t L = c->n_limbs, poly = L << c->log2n, item = 2 * poly;
+    const size_t pairs = k.causal ? A * (A + 1) / 2 : A * B;
+    auto inverse = [&]() { return (k.flags & DPFHE_OUT_NTT) ? (int)DPFHE_SUCCESS : ntt_launch(c, true, d_out3, d_out3, pairs * 3 * L, k.s); };
+    if (k.flags & DPFHE_IN_NTT) {   // no scratch: one launch over everything
+        if (int rc = mul_outer_kernel_launch(k, d_out3, d_a2, d_b2, A, B, 0, 0)) return rc;
+        return inverse();
+    }
+    // Scratch for the transformed operands: [range of a | range of b]; the products of different ranges are independent - nothing accumulates
+    const MulOuterPlan pl = mul_outer_plan(c->scratch_limit_words.load(std::memory_order_relaxed) / item, A, B, d_a2 == d_b2 && A == B);
+    StreamScratch ws(c, k.s);
+    if (int rc = ws.alloc((pl.a_per + (pl.shared ? 0 : pl.b_per)) * item, "dpfhe_ct_mul_outer (scratch for the transformed operands)")) return rc;
+    u64 *ta = ws.p, *tb = pl.shared ? ws.p : ws.p + pl.a_per * item;
+    if (int rc = for_slices(A, pl.a_per, [&](size_t a0, size_t am) {
+            if (int rc = ntt_launch(c, false, ta, d_a2 + a0 * item, am * 2 * L, k.s)) return rc;
+            // under the causal flag the blocks wholly above the diagonal are empty: the keys past the range's last query are neither transformed nor walked
+            const size_t b_end = k.causal && a0 + am < B ? a0 + am : B;
+            return for_slices(b_end, pl.b_per, [&](size_t b0, size_t bm) {
+                if (!pl.shared) if (int rc = ntt_launch(c, false, tb, d_b2 + b0 * item, bm * 2 * L, k.s)) return rc;
+                return mul_outer_kernel_launch(k, d_out3, ta, tb, am, bm, a0, b0);
+            });
+        })) return rc;
+    return inverse();
+}
+
+extern "C" int dpfhe_ct_mul_outer(dpfhe_ctx* c, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t a_items, size_t b_items, uint32_t flags, void* stream) {
+    static const char* what = "dpfhe_ct_mul_outer";
+    // what the arguments alone decide comes before the context is looked at: a caller without a device learns of it too (tests/test_mul_outer_cabi_cpu.py)
+    if (flags & ~(DPFHE_IN_NTT | DPFHE_OUT_NTT | DPFHE_OUTER_CAUSAL)) return fail(DPFHE_INVALID_ARGUMENT, what, "unknown flag");
+    const bool causal = (flags & DPFHE_OUTER_CAUSAL) != 0;
+    if (causal && a_items != b_items) return fail(DPFHE_INVALID_ARGUMENT, what, "the causal form needs a_items == b_items");
+    if (a_items > kMaxGrid || b_items > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "a_items * b_items too large for one launch");
+    const bool nothing = a_items == 0 || b_items == 0;
+    if (!nothing && (!d_out3 || !d_a2 || !d_b2 || misaligned(d_out3) || misaligned(d_a2) || misaligned(d_b2)))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer");
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (nothing) return DPFHE_SUCCESS;
+    const size_t L = c->n_limbs, n = (size_t)1 << c->log2n, poly = L * n;
+    // sizes first (a product that wraps size_t would pass the overlap test): every count below stays under 2^31 residue polynomials
+    if (a_items * b_items > kMaxGrid / (3 * L) || MulOuterMap::grid(a_items, L, n) > kMaxGrid ||
+        !ntt_grid_fits(c, a_items * b_items * 3 * L) || !ntt_grid_fits(c, a_items * 2 * L) || !ntt_grid_fits(c, b_items * 2 * L))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "a_items * b_items too large for one launch");
+    const size_t out_words = (causal ? a_items * (a_items + 1) / 2 : a_items * b_items) * 3 * poly;
+    if (overlaps(d_out3, out_words, d_a2, a_items * 2 * poly) || overlaps(d_out3, out_words, d_b2, b_items * 2 * poly))
+        return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps an operand");
+    DPFHE_ON_DEVICE(c, what);
+    MulOuterCall k{c, flags, static_cast<hipStream_t>(stream), b_items, causal};
+    return ct_mul_outer_composed(k, d_out3, d_a2, d_b2, a_items, b_items);
 }
 
 // diagnostics: the quad form with per-workgroup timestamps (kernels.h ct_mul_quad_kernel<..., TRACE>); FoldArith contexts at N = 4096

@@ -380,6 +380,33 @@ void HybridKeySwitcher::multiply_complement_rescale_range(const Ciphertext& a, s
     out.set_ntt(false);
 }
 
+// ---- all pairs of two item ranges: dpfhe_ct_mul_outer into the object's scratch, one key switch and one rounding per pair ----------------------------------
+void HybridKeySwitcher::multiply_outer_rescale_range(const Ciphertext& a, size_t a_first, size_t a_count, const Ciphertext& b, size_t b_first, size_t b_count, bool causal,
+                                                     Ciphertext& out, size_t out_first, Stream* s) const {
+    const std::string what = "HybridKeySwitcher::multiply_outer_rescale";
+    const Context& data = *impl_->data_ctx;
+    const FheParams& pd = data.params();
+    const size_t Ld = pd.n_limbs(), n = pd.n(), in_words = 2 * Ld * n, out_words = 2 * (Ld - 1) * n;
+    if (Ld < 2) throw Exception(ErrorCode::INVALID_STATE, what + ": no data limb left to drop");
+    if (causal && a_count != b_count) throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": the causal form pairs item i of a with items j <= i of b: as many of each");
+    if (a.is_ntt() || b.is_ntt() || a.size() != 2 || b.size() != 2 || a.words() != a.batch() * in_words || b.words() != b.batch() * in_words ||
+        a_first + a_count > a.batch() || b_first + b_count > b.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": 2-component coefficient-domain ciphertexts on the data context, a_count items of a and b_count items of b");
+    const size_t pairs = causal ? a_count * (a_count + 1) / 2 : a_count * b_count;
+    if (out.size() != 2 || out.words() != out.batch() * out_words || out_first + pairs > out.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, what + ": output must live on the next-level context (Ld - 1 limbs), 2 components, with room for one item per pair");
+    if (pairs == 0) return;
+    grow_scratch(impl_->scratch_product, pairs, [&](size_t m) { return new Ciphertext(data, 3, m); });
+    grow_scratch(impl_->scratch_work, pairs, [&](size_t m) { return new PolyBuffer(*impl_->ext, m, 2, false); });
+    check(dpfhe_ct_mul_outer(handle_of(data), impl_->scratch_product->data(), a.data() + a_first * in_words, b.data() + b_first * in_words, a_count, b_count,
+                             causal ? DPFHE_OUTER_CAUSAL : 0, s),
+          "dpfhe_ct_mul_outer");
+    check(dpfhe_relinearize_rescale_hybrid(handle_of(*impl_->ext), out.data() + out_first * out_words, impl_->scratch_product->data(), impl_->relin->data(),
+                                           impl_->scratch_work->data(), pairs, s),
+          "dpfhe_relinearize_rescale_hybrid");
+    out.set_ntt(false);
+}
+
 const Context& HybridKeySwitcher::extended_context() const { return *impl_->ext; }
 const Context& HybridKeySwitcher::data_context() const { return *impl_->data_ctx; }
 

@@ -1,4 +1,5 @@
-// kernels_mul.h - the multiply at ring degrees above 8192, and sums of products and complement products at every ring degree (device).  Included by cabi_mul.hip only.
+// kernels_mul.h - the multiply at ring degrees above 8192, and sums of products, complement products and all-pairs (outer) products at every ring degree (device).
+// Included by cabi_mul.hip only.
 //
 // The fused multiply kernels of kernels.h keep whole polynomials in one workgroup's registers and LDS, which stops at
 // N = 8192 (one 1024-thread workgroup at N = 16384 has 128 VGPRs per thread; four polynomials of 16 words per thread do not fit).
@@ -10,6 +11,7 @@
 
 #include "modarith.h"
 #include "mul_complement.h"
+#include "mul_outer.h"
 #include "mul_sum.h"
 #include "workmap.h"
 
@@ -145,6 +147,77 @@ __global__ __launch_bounds__(256) void tensor3_complement_kernel(u64* __restrict
         product(po + (size_t)k * 3 * poly, x0, x1);
     }
     if (out_self) product(out_self + group * 3 * poly + off, b0, b1);
+}
+
+// ALL PAIRS of a_count resident operands (queries) and b_count streamed ones (keys), one pass: the tensor product a[i] (x) b[j] of every pair, NTT domain,
+// canonical in and out (mul_outer.h holds the lane arithmetic).  a2: [a_count][2][L][N]; b2: [b_count][2][L][N]; out3: the WHOLE output of the call, pair
+// (gi, gj) = (a_off + i, b_off + j) at item gi * b_total + gj, or under `causal` pair (gi, gj <= gi) at item gi (gi + 1) / 2 + gj (workmap.h MulOuterMap::item:
+// a_off, b_off place a launch over ranges of the operands inside the whole; every index is size_t).  A workgroup owns one 512-word chunk of one limb of a TILE
+// of kMulOuterTile queries (MulOuterMap::decode: the tiles of a (limb, chunk) share one XCD): the tile is loaded once and prepared in registers, then the
+// workgroup walks the keys, kMulOuterDepth keys' loads (8 x 16 bytes per lane) in flight before the first is used, three 16-byte stores per product.  A ragged
+// last tile skips its missing rows; the ragged end of the key loop runs key by key; under `causal` a tile walks the keys up to its last row's and skips the
+// pairs above the diagonal (all three predicates are uniform over the workgroup).  Traffic per limb in rows of N words: 2 a_count + 2 b_count ceil(a_count /
+// tile) read - the re-reads L2 hits -, 3 per pair written.
+constexpr int kMulOuterDepth = 4;   // keys whose loads are in flight before the first is used (its own constant: the block of keys below is written out)
+template <class Arith>
+__global__ __launch_bounds__(256) void tensor3_outer_kernel(u64* __restrict__ out3, const u64* __restrict__ a2, const u64* __restrict__ b2, const LimbConst* lcs, int n_limbs,
+                                                            int n, int chunks, unsigned tiles, size_t a_count, size_t b_count, size_t a_off, size_t b_off, size_t b_total,
+                                                            int causal) {
+    typedef MulOuterLane<Arith> Lane;
+    const MulOuterWork wk = MulOuterMap::decode(blockIdx.x, tiles, (unsigned)n_limbs, (unsigned)chunks);
+    if (!wk.live) return;
+    const int w0 = wk.chunk * 512 + threadIdx.x * 2;
+    if (w0 >= n) return;
+    const size_t r0 = wk.tile * kMulOuterTile;
+    const size_t keys = MulOuterMap::keys(r0, a_count, b_count, a_off, b_off, causal != 0);
+    if (keys == 0) return;   // a tile wholly above the diagonal
+    const int rows = a_count - r0 < (size_t)kMulOuterTile ? (int)(a_count - r0) : kMulOuterTile;
+    const LimbConst lc = lcs[wk.limb];
+    const size_t poly = (size_t)n_limbs * n, off = (size_t)wk.limb * n + w0;
+    const u64* pb = b2 + off;
+    typename Lane::Prepared qa[kMulOuterTile], qb[kMulOuterTile];   // the tile: the lane's first and second word of every row
+#pragma unroll
+    for (int t = 0; t < kMulOuterTile; ++t) {
+        const u64* pa = a2 + (r0 + (t < rows ? t : 0)) * 2 * poly + off;   // a missing row re-reads the first: no load out of bounds, no product, no store
+        const U64x2 a0 = *reinterpret_cast<const U64x2*>(pa), a1 = *reinterpret_cast<const U64x2*>(pa + poly);
+        qa[t] = Lane::prepare(a0.a, a1.a, lc);
+        qb[t] = Lane::prepare(a0.b, a1.b, lc);
+    }
+    // key j against every row of the tile (always inlined: a call would take the key buffers and the tile through memory)
+    auto products = [&](size_t j, const U64x2& b0, const U64x2& b1) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < kMulOuterTile; ++t) {
+            if (t >= rows || !MulOuterMap::writes(r0 + t, j, a_off, b_off, causal != 0)) continue;
+            U64x2 d0, d1, d2;
+            Lane::product(qa[t], b0.a, b1.a, lc, d0.a, d1.a, d2.a);
+            Lane::product(qb[t], b0.b, b1.b, lc, d0.b, d1.b, d2.b);
+            u64* o = out3 + MulOuterMap::item(r0 + t, j, a_off, b_off, b_total, causal != 0) * 3 * poly + off;
+            *reinterpret_cast<U64x2*>(o) = d0;
+            *reinterpret_cast<U64x2*>(o + poly) = d1;
+            *reinterpret_cast<U64x2*>(o + 2 * poly) = d2;
+        }
+    };
+    size_t j = 0;
+    for (; j + kMulOuterDepth <= keys; j += kMulOuterDepth) {
+        U64x2 b0[kMulOuterDepth], b1[kMulOuterDepth];
+#pragma unroll
+        for (int u = 0; u < kMulOuterDepth; ++u) {
+            const size_t t = (j + u) * 2 * poly;
+            b0[u] = *reinterpret_cast<const U64x2*>(pb + t); b1[u] = *reinterpret_cast<const U64x2*>(pb + t + poly);
+        }
+        // written out: 4 keys x 4 rows x 2 words of products are past the size up to which hipcc unrolls a loop on request, and a loop left rolled
+        // keeps b0 / b1 in scratch memory
+        static_assert(kMulOuterDepth == 4, "the products of a block of keys are written out");
+        products(j, b0[0], b1[0]);
+        products(j + 1, b0[1], b1[1]);
+        products(j + 2, b0[2], b1[2]);
+        products(j + 3, b0[3], b1[3]);
+    }
+    for (; j < keys; ++j) {   // the ragged end: fewer than kMulOuterDepth keys
+        const size_t t = j * 2 * poly;
+        const U64x2 b0 = *reinterpret_cast<const U64x2*>(pb + t), b1 = *reinterpret_cast<const U64x2*>(pb + t + poly);
+        products(j, b0, b1);
+    }
 }
 
 }  // namespace dpfhe

@@ -219,6 +219,44 @@ constexpr size_t mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return 
 constexpr size_t mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return groups * n_limbs * (size_t)chunks_of(n); }
 
 // ------------------------------------------------------------------------------------------------
+// All pairs of A resident operands and B streamed ones (kernels_mul.h tensor3_outer_kernel): outer = slab = (limb, 512-word chunk), inner = tile of
+// kMulOuterTile resident operands.  A workgroup keeps its tile's chunk in registers and walks the streamed operands' chunk; the `tiles` workgroups of a slab read
+// the SAME streamed rows, so they share ONE XCD, consecutive in its order: the rows come from HBM once and are L2 hits for the other tiles.  Ids of a last,
+// partly filled round of slabs are dead.  A tile may be ragged (rows past a_count), and under the causal flag a tile walks the streamed operands up to its
+// last row's only: `keys` and `writes` are that predicate, once, for the kernel, the launcher's callers and the enumeration on the CPU.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMulOuterTile = 4;
+struct MulOuterWork {
+    int limb, chunk;
+    size_t tile;
+    bool live;
+};
+struct MulOuterMap {
+    static DPF_HD size_t tiles(size_t a_count) { return (a_count + kMulOuterTile - 1) / kMulOuterTile; }
+    static DPF_HD MulOuterWork decode(unsigned id, unsigned tiles, unsigned n_limbs, unsigned chunks) {
+        const XcdSlot s = xcd_deal::decode(id, tiles);
+        if (s.outer >= n_limbs * chunks) return MulOuterWork{0, 0, 0, false};
+        return MulOuterWork{(int)(s.outer / chunks), (int)(s.outer % chunks), (size_t)s.inner, true};
+    }
+    static DPF_HD size_t grid(size_t a_count, size_t n_limbs, size_t n) { return xcd_deal::grid(n_limbs * (size_t)chunks_of(n), tiles(a_count)); }
+    // the streamed operands a tile whose first row is local row r0 walks: all b_count, or under the causal flag those with b_off + j <= the GLOBAL index of the
+    // tile's last row (a_off, b_off: where the launch's ranges start among all operands; a block above the diagonal walks none)
+    static DPF_HD size_t keys(size_t r0, size_t a_count, size_t b_count, size_t a_off, size_t b_off, bool causal) {
+        if (!causal) return b_count;
+        const size_t rows = a_count - r0 < (size_t)kMulOuterTile ? a_count - r0 : (size_t)kMulOuterTile, last = a_off + r0 + rows - 1;
+        if (last < b_off) return 0;
+        return last - b_off + 1 < b_count ? last - b_off + 1 : b_count;
+    }
+    // whether the pair (local row i, local streamed j) is written
+    static DPF_HD bool writes(size_t i, size_t j, size_t a_off, size_t b_off, bool causal) { return !causal || b_off + j <= a_off + i; }
+    // ... and where: item i B + j of the full form (b_total = B streamed operands in all), item i (i + 1) / 2 + j of the causal one, in GLOBAL indices
+    static DPF_HD size_t item(size_t i, size_t j, size_t a_off, size_t b_off, size_t b_total, bool causal) {
+        const size_t gi = a_off + i, gj = b_off + j;
+        return causal ? gi * (gi + 1) / 2 + gj : gi * b_total + gj;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // The last pass of a rotate-and-add step (kernels_rotate.h rotate_add_pass_kernel): outer = (item, data limb), inner = slice of that residue polynomial's
 // chunks.  A workgroup writes its slice of BOTH components; component 0 gathers sigma_g(c0) from anywhere in the polynomial, so the `slices`
 // workgroups of a polynomial share ONE XCD: staged (the polynomial fits 64 KiB of LDS, N <= 8192) each of them reads all of c0 - from HBM once, L2 hits

@@ -377,6 +377,32 @@ class Evaluator:
                                                       groups, terms, 1 if with_self else 0, flags, self._sp(stream)), "dpfhe_ct_mul_complement")
         return Ciphertext(out, out_ntt)
 
+    def multiply_outer(self, a: Ciphertext, b: Ciphertext, causal: bool = False, out_ntt: bool | None = None, out: torch.Tensor | None = None,
+                       stream=None) -> Ciphertext:
+        """a[i] (x) b[j] for ALL pairs (dpfhe_ct_mul_outer: attention's scores - every operand transformed once, one streaming pass with a tile of a's items
+        in registers).  a: A items, b: B items; returns A * B items of 3 components, pair (i, j) at i * B + j, or with `causal` (A == B) the A (A + 1) / 2
+        pairs j <= i, pair (i, j) at i (i + 1) / 2 + j.  a and b may be the same ciphertext.  The words of multiply on the pair lists."""
+        p = self.ctx.params
+        if a.is_ntt != b.is_ntt:
+            raise _cabi.DpfheError(2002, "operands are in different domains (is_ntt mismatch)")
+        if a.size != 2 or b.size != 2:
+            raise _cabi.DpfheError(2000, "multiply_outer expects 2-component ciphertexts")
+        self._chk(a.data, b.data)
+        A, B = a.batch, b.batch
+        if causal and A != B:
+            raise _cabi.DpfheError(2000, "multiply_outer: the causal form pairs every item of a with the items of b up to its own index: as many of each")
+        pairs = A * (A + 1) // 2 if causal else A * B
+        out_ntt = a.is_ntt if out_ntt is None else bool(out_ntt)
+        if out is None:
+            out = self._empty((pairs, 3, p.n_limbs, p.n), stream)
+        self._chk(out)
+        if out.numel() != pairs * 3 * p.words_per_rns_poly():
+            raise _cabi.DpfheError(2000, "multiply_outer: out holds one item of 3 components per pair")
+        flags = (_cabi.IN_NTT if a.is_ntt else 0) | (_cabi.OUT_NTT if out_ntt else 0) | (_cabi.OUTER_CAUSAL if causal else 0)
+        _cabi.check(self._lib.dpfhe_ct_mul_outer(self.ctx.handle, out.data_ptr(), a.data.data_ptr(), b.data.data_ptr(), A, B, flags, self._sp(stream)),
+                    "dpfhe_ct_mul_outer")
+        return Ciphertext(out, out_ntt)
+
     def matvec_scalar(self, w: torch.Tensor, x: Ciphertext, out: torch.Tensor | None = None, stream=None) -> Ciphertext:
         """y_i = sum_j w_ij * x_j with scalar weights w: [rows][cols][L] residues (either domain)."""
         p = self.ctx.params

@@ -606,6 +606,16 @@ public:
     // multiply_rescale_range's.  INVALID_ARGUMENT for terms == 0 without with_self, ranges outside their buffers, a kappa of another context.
     void multiply_complement_rescale_range(const Ciphertext& a, size_t a_first, const Ciphertext& b, size_t b_first, size_t groups, size_t terms, bool with_self,
                                            const ComplementConstant& kappa, Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
+    // ALL PAIRS of two item ranges at the next level (attention's scores before their slot sum: every query against every key): with a_i = item a_first + i of
+    // a (i < a_count) and b_j = item b_first + j of b (j < b_count),
+    //   out item out_first + i * b_count + j     = round(relinearize(a_i * b_j) / q_last)                       (every pair), or, with `causal` (a_count == b_count),
+    //   out item out_first + i (i + 1) / 2 + j   = the same for j <= i only                                      (a_count (a_count + 1) / 2 items).
+    // dpfhe_ct_mul_outer writes the tensor products into the object's scratch - every operand transformed once, a tile of queries kept in registers while the
+    // keys stream past - then dpfhe_relinearize_rescale_hybrid runs over all pairs.  Word for word multiply_rescale_range on the two pair lists copied out item
+    // by item.  At scales s_a, s_b every result has scale s_a s_b / q_last.  a and b may be one buffer, also one range.  The stream contract is
+    // multiply_rescale_range's.  INVALID_ARGUMENT for causal with a_count != b_count and for ranges outside their buffers; a count of 0 is a no-op.
+    void multiply_outer_rescale_range(const Ciphertext& a, size_t a_first, size_t a_count, const Ciphertext& b, size_t b_first, size_t b_count, bool causal,
+                                      Ciphertext& out_next_level, size_t out_first, Stream* stream = nullptr) const;
     // many rotations in one pass (dpfhe_rotate_hybrid_batch): out item out_first + i = sigma_{elts[i]} of in item i, or of THE
     // item of `in` when it holds one.  All elements must have been added; the keys of a given element list are packed
     // back to back once and cached.
@@ -1147,6 +1157,58 @@ public:
     // components, coefficient domain, scale a_scale); b: as many at b_scale or, shared, `terms` items every group reads.  Enqueues only; the scratch is the key
     // switcher's (multiply_sum_rescale_range); one apply() at a time per key switcher.
     void apply(const Ciphertext& a, const Ciphertext& b, Ciphertext& y, Stream* stream = nullptr) const;
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// ApproxAttentionScores: the first step of an attention head under encryption, s_ij = post_factor <q_i, k_j>, from T encrypted queries and T encrypted keys: ONE
+// all-pairs product step (HybridKeySwitcher::multiply_outer_rescale_range: every operand transformed once, one key switch and one rescale per pair), then ONE
+// rotate_add_range over all pairs with SlotSum's elements for (block, stride).  The ladder runs AFTER the rescale, on one limb fewer, so it takes the key
+// switcher of the next level (a HybridKeySwitcher is bound to one level: ks_next.data_context() is ks.data_context() without its last limb).
+//
+// Packings (both: the vector has period block * stride in the slots, so after the ladder every slot holds the total of its residue class modulo stride):
+//   one head           the d <= block values of the head in slots 0 .. d - 1 of every period `block`, zeros above d, stride = 1.  The ladder adds the block
+//                      slots i, i + 1, ..., i + block - 1 (cyclically inside the period): EVERY slot of pair (i, j) holds sum_d q_i[d] k_j[d].
+//   heads interleaved  value `dim` of head `head` in slot dim * stride + head, stride >= the head count (slots head >= heads hold zeros), block = d_head
+//                      (GPT-2 small: block 64, stride 16, period 1024).  The ladder adds slots i + e stride, e < block: slot dim * stride + head holds head's
+//                      score for every dim - one product and one log2(block)-step ladder give all heads' scores, each replicated over its own head's slots,
+//                      the layout a slot-wise mix with v packed the same way needs.
+// Output.  Full: T * T items, pair (i, j) at i * T + j; causal: T (T + 1) / 2 items, pair (i, j <= i) at i (i + 1) / 2 + j.
+// Scales.  S = (q_scale * k_scale) / (double)q_last is the scale the sums live at;  output_scale() = S / post_factor  in exactly these double operations.  A
+//   client that decodes at output_scale() reads post_factor * sum: the factor 1 / sqrt(d_head) (post_factor = 1 / 8 for GPT-2) is folded into the scale and
+//   costs no level, as ApproxDivide folds its constant guess.
+// Error bound.  A = max|q|, B = max|k| over the slots, Bq, Bk the coefficient errors of the input phases.  The product step is ApproxProductSum at one term:
+//   its error_bound(A, B, Bq, Bk) = e1 bounds every slot of a product in units of the values, so S e1 bounds the slot error of its phase, and a coefficient is
+//   an average of slots (T1 read backwards: c_k = (2 / N) Re sum_j z_j zeta^(-j k)), so Bin = S e1 bounds the coefficient error that enters the ladder.
+//   SlotSum's bound on the next level's limbs, at scale S, with X = A B and that Bin, bounds |decoded slot at scale S - the sum|; reading at output_scale()
+//   multiplies values and errors by post_factor, and output_scale() as a double is off S / post_factor by at most 4 u relative:
+//   error_bound(A, B, Bq, Bk) = post_factor (SlotSum::error_bound(S, A B, S e1) + 4 u block A B) bounds |decoded slot - post_factor sum_d q_i[d] k_j[d]| (the
+//   float64 sum over the class's block slots, ascending) for every slot and pair, provided no phase wraps (the phase is about S block A B).
+// Integer model on transparent inputs (c1 = 0, c0 the residues of a known integer polynomial): the product is (a0 b0, 0, 0), every key-switch digit is zero, the
+//   division by P is exact, and the words of a pair are round(a0 b0 / q_last) in R followed by the ladder's sums of automorphisms acc <- acc + sigma_g(acc).
+class ApproxAttentionScores {
+public:
+    // ks: the level of q and k (at least two data limbs: the product step drops one); ks_next: the level below it.  Adds SlotSum's
+    // elements to ks_next.  Both must outlive the object.  INVALID_ARGUMENT for tokens == 0, a bad (block, stride), scales or a post_factor that are not finite and
+    // positive, or a ks_next that is not ks's next level.
+    ApproxAttentionScores(HybridKeySwitcher& ks, HybridKeySwitcher& ks_next, size_t tokens, size_t block, size_t stride, bool causal, double q_scale, double k_scale,
+                          double post_factor);
+    ~ApproxAttentionScores();
+    ApproxAttentionScores(const ApproxAttentionScores&) = delete;
+    ApproxAttentionScores& operator=(const ApproxAttentionScores&) = delete;
+    size_t tokens() const;
+    size_t pairs() const;          // tokens^2, or tokens (tokens + 1) / 2 when causal
+    bool causal() const;
+    double output_scale() const;   // (q_scale * k_scale) / (double)q_last / post_factor
+    double error_bound(double max_abs_q, double max_abs_k, double q_noise_bound, double k_noise_bound) const;
+    // ... and without a device: data_moduli are the limbs of q and k (at least 2), special_prime the key switchers' P
+    static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double q_scale, double k_scale,
+                              double post_factor, double max_abs_q, double max_abs_k, double q_noise_bound, double k_noise_bound);
+    // q, k: `tokens` items each on ks's data context (2 components, coefficient domain); scores: pairs() items on ks_next's data context.  Enqueues only after
+    // the first call (the ladder's keys are packed then); the product's pairs live in scratch the object owns; one apply() at a time per key switcher.
+    void apply(const Ciphertext& q, const Ciphertext& k, Ciphertext& scores, Stream* stream = nullptr) const;
 
 private:
     class Impl;

@@ -213,6 +213,34 @@ int dpfhe_ct_mul_sum(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, con
 int dpfhe_ct_mul_complement(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, const uint64_t* d_kappa, size_t groups, size_t terms,
                             int with_self, uint32_t flags, void* stream);
 
+/* -- ALL PAIRS of two lists of ciphertexts, the OUTER product (attention's scores s_ij = <q_i, k_j>: T queries against T keys are T^2 tensor products of 2 T
+ * distinct operands): every operand is transformed ONCE, and one streaming pass keeps a tile of 4 queries in registers while the keys stream past.
+ *   d_a2: [a_items][2][L][N] (queries);  d_b2: [b_items][2][L][N] (keys);  (x) is dpfhe_ct_mul's (a0 b0, a0 b1 + a1 b0, a1 b1) in R_q;
+ *   full form:    d_out3: [a_items * b_items][3][L][N],          d_out3[i * b_items + j] = a[i] (x) b[j];
+ *   causal form:  d_out3: [a_items (a_items + 1) / 2][3][L][N],  d_out3[i (i + 1) / 2 + j] = a[i] (x) b[j] for j <= i  (DPFHE_OUTER_CAUSAL; a_items == b_items).
+ * flags: dpfhe_ct_mul_sum's DPFHE_IN_NTT / DPFHE_OUT_NTT, and DPFHE_OUTER_CAUSAL.  With flags 0 (coefficient domain in and out) the words are those of
+ * dpfhe_ct_mul on the two pair lists a[i], b[j] copied out pair by pair.  Every log2_n (8 ... 16) and limb class.
+ * Aliasing: the operands are read-only and may alias each other in any way (d_a2 == d_b2 with a_items == b_items is every product of a list with itself and,
+ * when the list fits the scratch limit, transforms once); d_out3 must not overlap either operand.
+ * Always composed: batched forward transforms of a and of b into the arena of the caller's stream (see "Conventions" - here at EVERY log2_n), one streaming
+ * launch, three inverse transforms per pair, in place.  Scratch, in items of 2 L N words, with fit = the limit of dpfhe_ctx_set_scratch_limit in such items:
+ *   a_items + b_items (a_items when d_a2 == d_b2 and a_items == b_items) when that is <= fit: one launch;
+ *   otherwise a_items + min(b_items, fit - a_items) when a_items + 1 <= fit: a whole, b in ranges of keys, one launch per range;
+ *   otherwise min(a_items, ta) + min(b_items, max(2, fit - ta)) with ta = max(4, fit / 2 rounded down to a multiple of 4): a in ranges of whole tiles of 4
+ *   queries, b in ranges of keys, one launch per pair of ranges - 6 items at least, whatever the limit.
+ * How the limit is treated: it is honoured whenever it holds 6 items (one tile of 4 queries and 2 keys: the smallest ranges the entry works in); a limit below
+ * that is EXCEEDED, to exactly 6 items (min(a_items, 4) + min(b_items, 2) for fewer), as the other composed entries exceed a limit below one item.
+ * The products of different ranges are independent (nothing accumulates); under DPFHE_OUTER_CAUSAL the blocks wholly above the diagonal are skipped, keys
+ * and all.  With DPFHE_IN_NTT there is no scratch at all (DPFHE_OUT_NTT only skips the inverse transforms, in place).  Enqueues only; allocates only when
+ * the stream's arena grows.
+ * Algorithmic traffic of the streaming pass per limb, in rows of N words: 2 a_items + 2 b_items ceil(a_items / 4) read, 3 per pair written - against 4 per pair
+ * read for dpfhe_ct_mul over pair lists, after the copies that build them (4 rows read and written per pair).
+ * DPFHE_INVALID_ARGUMENT, before the device is touched: an unknown flag, DPFHE_OUTER_CAUSAL with a_items != b_items, a null or misaligned (16 bytes) buffer,
+ * d_out3 overlapping an operand, a_items * b_items too large for one launch.  The rejections that the arguments alone decide come before the context is
+ * looked at.  a_items == 0 or b_items == 0 returns success. */
+enum { DPFHE_OUTER_CAUSAL = 4u };
+int dpfhe_ct_mul_outer(dpfhe_ctx* ctx, uint64_t* d_out3, const uint64_t* d_a2, const uint64_t* d_b2, size_t a_items, size_t b_items, uint32_t flags, void* stream);
+
 /* diagnostics (tools/ctmul_trace.py): the "quad" form of dpfhe_ct_mul(flags = 0) with timestamps - thread 0 of workgroup w (= pair w / L, limb w % L)
  * writes d_trace[12 w .. 12 w + 11]: s_memrealtime (100 MHz) at start / first operand word arrived / forward transforms done / tensor
  * product done / inverse transforms done / stores issued / stores drained, then HW_ID | XCC_ID << 32, then prologue done / first operand's

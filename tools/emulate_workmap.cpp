@@ -94,6 +94,34 @@ u64 wm_mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return mul_sum_gr
 // products with a shared complement factor: the grid; ids decode through wm_chunk_decode over all limbs, the group in the polynomial's place
 u64 wm_mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return mul_complement_grid(groups, n_limbs, n); }
 
+// all pairs of resident and streamed operands: the grid of a launch over a_count resident ones, and per id the row (limb, chunk, tile, live, keys walked,
+// rows of the tile); wm_mul_outer_pairs lists what ONE id writes, as the kernel's loops do: rows (output item, local row i, local key j), returns their number
+int wm_mul_outer_tile() { return kMulOuterTile; }
+u64 wm_mul_outer_grid(size_t a_count, size_t n_limbs, size_t n) { return MulOuterMap::grid(a_count, n_limbs, n); }
+void wm_mul_outer_decode(unsigned n_ids, unsigned n_limbs, unsigned chunks, size_t a_count, size_t b_count, size_t a_off, size_t b_off, int causal, i64* out) {
+    const unsigned tiles = (unsigned)MulOuterMap::tiles(a_count);
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const MulOuterWork w = MulOuterMap::decode(id, tiles, n_limbs, chunks);
+        i64* o = out + 6 * (size_t)id;
+        const size_t r0 = w.tile * kMulOuterTile;
+        o[0] = w.limb; o[1] = w.chunk; o[2] = (i64)w.tile; o[3] = w.live;
+        o[4] = w.live ? (i64)MulOuterMap::keys(r0, a_count, b_count, a_off, b_off, causal != 0) : 0;
+        o[5] = w.live ? (i64)(a_count - r0 < (size_t)kMulOuterTile ? a_count - r0 : (size_t)kMulOuterTile) : 0;
+    }
+}
+size_t wm_mul_outer_pairs(size_t tile, size_t a_count, size_t b_count, size_t a_off, size_t b_off, size_t b_total, int causal, i64* out) {
+    const size_t r0 = tile * kMulOuterTile, keys = MulOuterMap::keys(r0, a_count, b_count, a_off, b_off, causal != 0);
+    const size_t rows = a_count - r0 < (size_t)kMulOuterTile ? a_count - r0 : (size_t)kMulOuterTile;
+    size_t m = 0;
+    for (size_t j = 0; j < keys; ++j)
+        for (size_t t = 0; t < rows; ++t) {
+            if (!MulOuterMap::writes(r0 + t, j, a_off, b_off, causal != 0)) continue;
+            out[3 * m] = (i64)MulOuterMap::item(r0 + t, j, a_off, b_off, b_total, causal != 0); out[3 * m + 1] = (i64)(r0 + t); out[3 * m + 2] = (i64)j;
+            ++m;
+        }
+    return m;
+}
+
 // last pass of a rotate-and-add step: rows (item, limb, slice, live)
 unsigned wm_rotate_add_slices(size_t n) { return RotateAddMap::slices(n); }
 int wm_rotate_add_staged(size_t n) { return RotateAddMap::staged(n); }
