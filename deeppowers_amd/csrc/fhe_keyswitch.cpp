@@ -271,6 +271,24 @@ void HybridKeySwitcher::rotate_add_range(const Ciphertext& in2, size_t in_first,
     out2.set_ntt(false);
 }
 
+void HybridKeySwitcher::rotate_sum_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& elts, Ciphertext& out2, size_t out_first,
+                                         Stream* s) const {
+    if (count == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t Ld = pe.n_limbs() - 1, n = pe.n(), ct_words = 2 * Ld * n;
+    if (elts.empty() || elts.size() > 64 || in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in2.words() != in2.batch() * ct_words ||
+        out2.words() != out2.batch() * ct_words || in_first + count > in2.batch() || out_first + count > out2.batch())
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::rotate_sum_range: 1 .. 64 elements, count coefficient-domain items of the data context in and out");
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    impl_->ensure_digits(count * Ld);
+    grow_scratch(impl_->scratch_in_ntt, count, [&](size_t b) { return new Ciphertext(*impl_->data_ctx, 2, b, true); });
+    grow_scratch(impl_->scratch_work, count, [&](size_t b) { return new PolyBuffer(*impl_->ext, b, 2, false); });   // the items' sums over Q P
+    check(dpfhe_rotate_sum_hoisted(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words, count, elts.data(), keys->data(),
+                                   elts.size(), impl_->scratch_in_ntt->data(), impl_->scratch_digits->data(), impl_->scratch_work->data(), s),
+          "dpfhe_rotate_sum_hoisted");
+    out2.set_ntt(false);
+}
+
 void HybridKeySwitcher::multiply_rescale(const Ciphertext& a, const Ciphertext& b, Ciphertext& out_next_level, Stream* s) const {
     if (b.batch() != a.batch() || out_next_level.batch() != a.batch())
         throw Exception(ErrorCode::INVALID_ARGUMENT, "HybridKeySwitcher::multiply_rescale: operands and output of one batch");
@@ -448,50 +466,88 @@ void HybridKeySwitcher::switch_key_qp(const Ciphertext& in2, size_t in_first, co
 class __attribute__((visibility("hidden"))) SlotSum::Impl {
 public:
     HybridKeySwitcher* ks = nullptr;
-    size_t block = 0, stride = 0;
-    std::vector<uint32_t> elts;
+    size_t block = 0, stride = 0, radix = 2;
+    std::vector<uint32_t> elts;                  // every element, in the order it is used
+    std::vector<std::vector<uint32_t>> stages;   // radix > 2: the elements of each hoisted stage (empty for the ladder)
+    mutable std::unique_ptr<Ciphertext> pong;    // radix > 2, more than one stage: the ping-pong partner of the output
 };
 
-SlotSum::SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride) : impl_(new Impl) {
+// the radices of the stages: 2^p while at least p bits of log2(block) remain, then the remainder
+static std::vector<size_t> slot_sum_radices(size_t block, size_t radix) {
+    std::vector<size_t> rho;
+    for (size_t left = block; left > 1; left /= rho.back()) rho.push_back(left >= radix ? radix : left);
+    return rho;
+}
+
+SlotSum::SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride, size_t radix) : impl_(new Impl) {
     const FheParams& p = ks.data_context().params();
     const size_t n = p.n();
     auto pow2 = [](size_t v) { return v && !(v & (v - 1)); };
     if (!pow2(block) || !pow2(stride) || block < 2 || stride > n / 2 || block > n / 2 / stride)
         throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum: block and stride must be powers of two with block >= 2 and block * stride <= N / 2");
+    if (!pow2(radix) || radix < 2 || radix > 64) throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum: radix must be a power of two in [2, 64]");
     impl_->ks = &ks;
     impl_->block = block;
     impl_->stride = stride;
-    uint64_t g = 3;   // 3^stride mod 2N by `log2(stride)` squarings, then one squaring per step
+    impl_->radix = radix;
+    uint64_t g = 3;   // 3^stride mod 2N by `log2(stride)` squarings
     for (size_t v = stride; v > 1; v >>= 1) g = g * g % (2 * n);
-    for (size_t b = block; b > 1; b >>= 1) {
-        impl_->elts.push_back((uint32_t)g);
-        ks.add_galois_element((uint32_t)g);
-        g = g * g % (2 * n);
+    if (radix == 2) {   // the ladder: one squaring per step
+        for (size_t b = block; b > 1; b >>= 1) {
+            impl_->elts.push_back((uint32_t)g);
+            ks.add_galois_element((uint32_t)g);
+            g = g * g % (2 * n);
+        }
+        return;
+    }
+    for (size_t rho : slot_sum_radices(block, radix)) {   // g = 3^(stride w_s): the stage's elements are g^k, k = 1 .. rho - 1, the next stage's g is g^rho
+        std::vector<uint32_t> st;
+        uint64_t e = g;
+        for (size_t k = 1; k < rho; ++k, e = e * g % (2 * n)) {
+            st.push_back((uint32_t)e);
+            impl_->elts.push_back((uint32_t)e);
+            ks.add_galois_element((uint32_t)e);
+        }
+        impl_->stages.push_back(st);
+        g = e;
     }
 }
 SlotSum::~SlotSum() = default;
 size_t SlotSum::block() const { return impl_->block; }
 size_t SlotSum::stride() const { return impl_->stride; }
-size_t SlotSum::steps() const { return impl_->elts.size(); }
+size_t SlotSum::radix() const { return impl_->radix; }
+size_t SlotSum::steps() const { return impl_->radix == 2 ? impl_->elts.size() : impl_->stages.size(); }
 const std::vector<uint32_t>& SlotSum::galois_elements() const { return impl_->elts; }
 
 double SlotSum::error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double scale, double max_abs_input,
-                            double input_noise_bound) {
+                            double input_noise_bound, size_t radix) {
     const BoundUnits bu(log2_n);
     const double N = bu.N, H = bu.H, u8 = bu.u8, B = (double)block;
     const double K = keyswitch_term((double)data_moduli.size(), N, max_modulus(data_moduli, data_moduli.size()), special_prime);
-    const double pre = N * (B * input_noise_bound + (B - 1) * (K + H)) / scale;
+    double roundings = 0, after = 1;   // sum_s prod_{u > s} rho_u, from the last stage back
+    const std::vector<size_t> rho = slot_sum_radices(block, radix);
+    for (size_t s = rho.size(); s-- > 0; after *= (double)rho[s]) roundings += after;
+    // (radix 2: roundings = block - 1 and the ladder's own expression, kept to the bit)
+    const double pre = N * (B * input_noise_bound + (radix == 2 ? (B - 1) * (K + H) : (B - 1) * K + roundings * H)) / scale;
     return pre + u8 * N * (B * max_abs_input + pre);
 }
 double SlotSum::error_bound(double scale, double max_abs_input, double input_noise_bound) const {
     const FheParams& pe = impl_->ks->extended_context().params();
     return error_bound(pe.log2_n, std::vector<uint64_t>(pe.moduli.begin(), pe.moduli.end() - 1), pe.moduli.back(), impl_->block, scale, max_abs_input,
-                       input_noise_bound);
+                       input_noise_bound, impl_->radix);
 }
 
 void SlotSum::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
     if (x.batch() == 0 || y.batch() != x.batch()) throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum::apply: T items in, T items out");
-    impl_->ks->rotate_add_range(x, 0, x.batch(), impl_->elts, y, 0, s);
+    if (impl_->radix == 2) return impl_->ks->rotate_add_range(x, 0, x.batch(), impl_->elts, y, 0, s);
+    const size_t S = impl_->stages.size(), T = x.batch();
+    if (S > 1) grow_scratch(impl_->pong, T, [&](size_t b) { return new Ciphertext(impl_->ks->data_context(), 2, b); });
+    const Ciphertext* cur = &x;
+    for (size_t i = 0; i < S; ++i) {   // the stages ping-pong so that the last one lands in y
+        Ciphertext* dst = ((S - 1 - i) & 1) ? impl_->pong.get() : &y;
+        impl_->ks->rotate_sum_range(*cur, 0, T, impl_->stages[i], *dst, 0, s);
+        cur = dst;
+    }
 }
 
 }  // namespace fhe

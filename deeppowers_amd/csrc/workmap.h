@@ -195,6 +195,44 @@ struct QpMap {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The SUM of the baby steps of an item (kernels_rotate_sum.h hoisted_qp_sum_kernel): output-stationary.  A workgroup is 256 threads x one 16-byte pair =
+// one OUTPUT segment of 512 words of one limb, for a tile of up to kQpSumTile items, whose accumulators it keeps over all rotations.  outer = combo =
+// (limb, output segment), inner = item tile: the tiles of a combo share ONE XCD, consecutive in its order, so a key segment comes from HBM once for all
+// items.  Nothing on the source side is dealt: per rotation a thread derives its source pair from its output pair (`source`, the second half of
+// QpMap::pair_map: out -> cf -> src, swap), and the digit segment it lands in is re-read by the workgroups of the R output segments that need it.
+// ------------------------------------------------------------------------------------------------
+constexpr int kQpSumTile = 4;
+struct QpSumWork {
+    int limb;
+    unsigned oseg, tile;
+    bool live;
+};
+struct QpSumPlan { unsigned tiles; size_t grid; };
+struct QpSumMap {
+    static DPF_HD QpGeo geo(int log2n) { return QpMap::geo(log2n, 1); }
+    static DPF_HD QpSumPlan plan(int log2n, size_t n_limbs, size_t n_items) {
+        const size_t tiles = (n_items + kQpSumTile - 1) / kQpSumTile;
+        return QpSumPlan{(unsigned)tiles, xcd_deal::grid(n_limbs * geo(log2n).nseg, tiles)};
+    }
+    static DPF_HD size_t grid(int log2n, size_t n_limbs, size_t n_items) { return plan(log2n, n_limbs, n_items).grid; }
+    static DPF_HD QpSumWork decode(unsigned id, const QpGeo& g, unsigned n_limbs, unsigned tiles) {
+        const XcdSlot s = xcd_deal::decode(id, tiles);
+        if (s.outer >= n_limbs * g.nseg) return QpSumWork{0, 0, 0, false};
+        return QpSumWork{(int)(s.outer % n_limbs), s.outer / n_limbs, s.inner, true};
+    }
+    // the pair `lane` of output segment oseg, and where rotation g gathers it from: p.ok as in QpMap::pair_map (rings below one segment)
+    static DPF_HD QpPair source(unsigned g, unsigned oseg, unsigned lane, const QpGeo& geo) {
+        QpPair p;
+        p.out = oseg * geo.seg_pairs + lane;
+        p.ok = p.out < geo.half;
+        const unsigned cf = (g * (2u * QpMap::brv(p.out, geo.n1) + 1u)) & (2u * geo.n - 1u);
+        p.swap = cf >= geo.n;
+        p.src = QpMap::brv(((cf & (geo.n - 1u)) - 1u) >> 1, geo.n1);
+        return p;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // The streaming kernels take their work in 512-word chunks of a residue polynomial: 256 threads x one 16-byte pair (the `chunks` argument of each;
 // a thread owns words chunk * 512 + 2 tid and the next).  Rings below N = 512 have one partial chunk, whose upper threads idle.
 // id = (poly * n_limbs + limb) * chunks + chunk.

@@ -584,6 +584,28 @@ class Evaluator:
                                                       acc.data_ptr() if acc is not None else None, k, T, self._sp(stream)), "dpfhe_rotate_add_hybrid")
         return Ciphertext(out, False)
 
+    def rotate_sum_hoisted(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> Ciphertext:
+        """N3, hoisted slot sums: every item plus the sum of its rotations by galois_elts (1 .. 64 of them) under ONE digit lift - ct_t + round(INTT(S_t) / P),
+        S_t the sum over Q P of the rotations' blocks of rotate_hoisted_qp, accumulated in registers (dpfhe_rotate_sum_hoisted).  keys: [len(elts)][L-1][2][L][N].
+        A radix-2^p stage of a slot sum is one call with the elements 3^(w k), k = 1 .. 2^p - 1."""
+        p = self.ctx.params
+        L, Ld, n = p.n_limbs, p.n_limbs - 1, p.n
+        d = ct.data
+        k = len(galois_elts)
+        if ct.is_ntt or ct.size != 2 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "rotate_sum_hoisted: coefficient-domain [T][2][L-1][N] ciphertexts on the extended context")
+        if k == 0 or tuple(keys.shape) != (k, Ld, 2, L, n) or keys.dtype != torch.int64 or not keys.is_contiguous():
+            raise _cabi.DpfheError(2000, "keys must be [k][L-1][2][L][N], k >= 1")
+        T = d.shape[0]
+        out = self._empty((T, 2, Ld, n), stream)
+        in_ntt = self._empty((T, 2, Ld, n), stream)
+        digits = self._empty((T, Ld, L, n), stream)
+        sum_qp = self._empty((T, 2, L, n), stream)
+        elts = (C.c_uint32 * k)(*[int(g) for g in galois_elts])
+        _cabi.check(self._lib.dpfhe_rotate_sum_hoisted(self.ctx.handle, out.data_ptr(), d.data_ptr(), T, elts, keys.data_ptr(), k, in_ntt.data_ptr(),
+                                                       digits.data_ptr(), sum_qp.data_ptr(), self._sp(stream)), "dpfhe_rotate_sum_hoisted")
+        return Ciphertext(out, False)
+
     def device_copy(self, dst: torch.Tensor, src: torch.Tensor, stream=None) -> torch.Tensor:
         """Plain device-to-device copy through the library's streaming access shape (dpfhe_copy): the practical HBM ceiling."""
         if dst.numel() != src.numel() or dst.dtype != torch.int64 or src.dtype != torch.int64 or not dst.is_contiguous() or not src.is_contiguous():

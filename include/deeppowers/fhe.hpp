@@ -643,6 +643,13 @@ public:
     void rotate_add_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& galois_elts, Ciphertext& out2, size_t out_first,
                           Stream* stream = nullptr) const;
 
+    // A hoisted slot-sum stage (dpfhe_rotate_sum_hoisted): out item out_first + i = in item in_first + i plus the sum of its rotations by galois_elts (1 .. 64 of
+    // them, all added before), under ONE digit lift: the rotated key products are summed over Q P in registers, one inverse transform and one division by P per
+    // item.  With one element: the words of apply_galois_hoisted followed by Evaluator::add.  Ranges, aliasing and the stream contract as rotate_add_range:
+    // enqueues only after the first call with a given element list; the scratch (transformed inputs, digits, the sums over Q P) is the object's own.
+    void rotate_sum_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& galois_elts, Ciphertext& out2, size_t out_first,
+                          Stream* stream = nullptr) const;
+
     // ---- division by P deferred ("double hoisting"; include/dpfhe.h "N3, round 3") -------------------------------------
     // The context of the data moduli + the special prime: buffers holding terms over Q P live on it.
     const Context& extended_context() const;
@@ -742,25 +749,36 @@ private:
 //   coefficients obey max|c_k| <= D (block X + pre) and the client's decode adds u8 N (block X + pre).
 //   error_bound(D, X, Bin) = pre + u8 N (block X + pre): a bound on |decoded slot - the sum| for every slot and token, provided the phase does not wrap.
 //   (Worst case throughout, like the layers' bounds: key-switch errors add like a random walk, not in absolute value.)
+//
+// Radix.  radix = 2 is the ladder above, untouched: same elements, same words, same key order.  radix = 2^p > 2 runs HOISTED stages: stage s has radix
+//   rho_s = 2^p while at least p bits of log2(block) remain, then the remainder; weight w_s = prod_{u<s} rho_u; it is ONE HybridKeySwitcher::rotate_sum_range
+//   with the elements 3^(stride w_s k), k = 1 .. rho_s - 1: acc <- sum_{k < rho_s} rot(acc, stride w_s k) under one digit lift.  Every slot ends up holding
+//   the same sum; the keys number sum_s (rho_s - 1) instead of log2(block).  A stage adds the running sum to rho - 1 key-switched rotations of it and rounds
+//   ONCE, so an error e becomes rho e + (rho - 1) K + H; with f = e + K this is f -> rho f + H, and after all stages
+//     e = block (Bin + K) - K + H sum_s prod_{u>s} rho_u      (radix 2: the sum is block - 1, the ladder's bound; otherwise smaller)
+//   takes the place of block Bin + (block - 1) (K + H) in `pre`; the rest of the bound is unchanged.
 class SlotSum {
 public:
     // block, stride: powers of two, block >= 2, block * stride <= N/2 (INVALID_ARGUMENT otherwise).  Adds the elements 3^(stride 2^e) mod 2N, e < log2(block),
-    // to `ks` in ascending order of e; `ks` must outlive the object.
-    SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride = 1);
+    // to `ks` in ascending order of e; `ks` must outlive the object.  radix: a power of two in [2, 64] (INVALID_ARGUMENT otherwise); above 2 it adds the stages'
+    // elements instead, stage by stage, k ascending.
+    SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride = 1, size_t radix = 2);
     ~SlotSum();
     SlotSum(const SlotSum&) = delete;
     SlotSum& operator=(const SlotSum&) = delete;
     size_t block() const;
     size_t stride() const;
-    size_t steps() const;                                    // log2(block): key switches per item
-    const std::vector<uint32_t>& galois_elements() const;    // the ladder's elements, in the order they are applied
+    size_t radix() const;
+    size_t steps() const;                                    // radix 2: log2(block), key switches per item; above: the number of stages (digit lifts per item)
+    const std::vector<uint32_t>& galois_elements() const;    // every element, in the order it is used (radix 2: the ladder's)
     // the bound derived above (the approximate family): scale = D, max_abs_input = X, input_noise_bound = Bin
     double error_bound(double scale, double max_abs_input, double input_noise_bound) const;
     // ... and without a device: data_moduli are the limbs of ks.data_context(), special_prime its P
     static double error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_moduli, uint64_t special_prime, size_t block, double scale, double max_abs_input,
-                              double input_noise_bound);
+                              double input_noise_bound, size_t radix = 2);
     // x: T items on ks.data_context() (2 components, coefficient domain); y: T items on the same context, another buffer.  Level and scale do not change.
-    // The stream contract of HybridKeySwitcher::rotate_add_range: enqueues only after the first call; one apply() at a time per key switcher.
+    // The stream contract of HybridKeySwitcher::rotate_add_range: enqueues only after the first call; one apply() at a time per key switcher.  With more than
+    // one hoisted stage the object owns the ping-pong partner of y.
     void apply(const Ciphertext& x, Ciphertext& y, Stream* stream = nullptr) const;
 
 private:

@@ -383,6 +383,22 @@ int dpfhe_rotate_add_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t
 int dpfhe_rotate_add_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_t log2_n, uint64_t* out, const uint64_t* work_qp, const uint64_t* in2,
                                uint32_t galois_elt, size_t batch);
 
+/* -- N3, HOISTED slot sums: every item plus the sum of n_rot rotations of it, under ONE digit lift:
+ *   d_out2 item t = ct_t + round(INTT(S_t) / P),   S_t = sum_{r < n_rot} block 1 + r of dpfhe_rotate_hoisted_qp (below) for item t, mod q_l over Q P
+ * - word for word dpfhe_rotate_hoisted_qp, dpfhe_reduce_sum over its blocks 0 .. n_rot on ctx_ext, dpfhe_ntt_inv and dpfhe_rescale_bsgs with no addend
+ * (block 0 = P ct is an exact multiple of P: it enters as the addend of the division instead).  n_rot == 1 gives the words of dpfhe_rotate_hybrid_hoisted
+ * followed by dpfhe_add.  d_in2, d_out2: [n_items][2][Ld][N], coefficient domain, canonical; galois_elts: HOST array of n_rot odd elements < 2N; d_keys:
+ * n_rot keys back to back as for dpfhe_rotate_hybrid_hoisted.  The R rotated key products of an item are summed in registers (one workgroup per output
+ * segment, limb and tile of 4 items): no Q P block per rotation is written - per item and limb R (Ld + 1) gathered rows, 2 written; keys once per tile.
+ * A radix-2^p stage of a slot sum is one call with 2^p - 1 elements: one digit lift where the ladder (dpfhe_rotate_add_hybrid) pays p.
+ * Scratch, exactly: d_in_ntt n_items * 2 * Ld * N words; d_digits n_items * Ld * L * N words; d_sum_qp n_items * 2 * L * N words.  No buffer overlaps
+ * another, the input or the keys.  Enqueues only, every log2_n (8 ... 16) and limb class; never allocates at log2_n <= 13, above that the composed transforms
+ * lease arena scratch exactly as in dpfhe_rotate_hoisted_qp.  DPFHE_INVALID_STATE on a context without a special prime; DPFHE_INVALID_ARGUMENT, before the
+ * device is touched, on n_rot outside [1, 64] (a sum is one launch: its accumulators are never re-read), an even element or one >= 2N, a null or misaligned
+ * buffer, overlapping buffers, or a grid too large for one launch.  n_items == 0 returns success. */
+int dpfhe_rotate_sum_hoisted(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
+                             size_t n_rot, uint64_t* d_in_ntt, uint64_t* d_digits, uint64_t* d_sum_qp, void* stream);
+
 /* -- N3, round 3: baby-step / giant-step sums with the division by P DEFERRED ("double hoisting", Bossuat-Mouchet-Troncoso-Pastoriza-
  * Hubaux 2021).  A rotated term is kept in the NTT domain over the extended basis Q P as  P sigma_g(ct) + key-switching noise;
  * plaintext products and sums are taken there, and one inverse transform + divide-by-P is paid per SUM, not per rotation.

@@ -77,6 +77,30 @@ void wm_qp_pair_map(int log2n, unsigned pairs, unsigned g, unsigned sseg, i64* o
     }
 }
 
+// the sum of the baby steps: rows (limb, output segment, item tile, live); the out-to-source map of one (g, output segment): rows (out, src, swap, ok) per lane
+int wm_qp_sum_tile() { return kQpSumTile; }
+u64 wm_qp_sum_grid(int log2n, size_t n_limbs, size_t n_items, unsigned* tiles) {
+    const QpSumPlan p = QpSumMap::plan(log2n, n_limbs, n_items);
+    *tiles = p.tiles;
+    return p.grid;
+}
+void wm_qp_sum_decode(unsigned n_ids, int log2n, unsigned n_limbs, unsigned tiles, i64* out) {
+    const QpGeo geo = QpSumMap::geo(log2n);
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const QpSumWork w = QpSumMap::decode(id, geo, n_limbs, tiles);
+        i64* o = out + 4 * (size_t)id;
+        o[0] = w.limb; o[1] = w.oseg; o[2] = w.tile; o[3] = w.live;
+    }
+}
+void wm_qp_sum_source(int log2n, unsigned g, unsigned oseg, i64* out) {
+    const QpGeo geo = QpSumMap::geo(log2n);
+    for (unsigned lane = 0; lane < geo.seg_pairs; ++lane) {
+        const QpPair p = QpSumMap::source(g, oseg, lane, geo);
+        i64* o = out + 4 * (size_t)lane;
+        o[0] = p.out; o[1] = p.src; o[2] = p.swap; o[3] = p.ok;
+    }
+}
+
 // streaming kernels: rows (chunk, limb, polynomial)
 int wm_chunks_of(size_t n) { return chunks_of(n); }
 void wm_chunk_decode(unsigned n_ids, int chunks, int n_limbs, i64* out) {
