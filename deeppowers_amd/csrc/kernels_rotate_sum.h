@@ -5,6 +5,7 @@
 
 #include "launch.h"
 #include "modarith.h"
+#include "rotate_sum.h"
 #include "stream_access.h"
 #include "workmap.h"
 
@@ -19,7 +20,9 @@ namespace dpfhe {
 //   - the terms of a rotation are j = 0 .. Ld - 1 (digit j x key (r, j)) and, on the data limbs, j = Ld (c0 x P: no key);
 //   - a key pair (e0, e1) of (r, j) is loaded once and split once for the whole tile; a digit word's split serves both key components;
 //   - the loads of term u + 1 are issued before term u multiplies (the last term re-requests itself: cache hits instead of a branch);
-//   - fold limbs: Dot30 columns, one dot30_fold per kDot30Period terms counted ACROSS rotations; other classes: mul_var + add_mod per term.
+//   - fold limbs: Dot30 columns, one dot30_fold per kDot30Period terms counted ACROSS rotations; other classes: mul_var + add_mod per term.  That
+//     arithmetic - accumulators, a term's products, the period, the final words - is rotate_sum.h QpSumLane, which tools/emulate_rotate_sum.cpp runs on the
+//     CPU; this kernel keeps the loads, the map, the prefetch and the stores.
 // Traffic per item: R (Ld + 1) digit / input rows gathered (each digit segment by R different workgroups: L2 and the Infinity Cache are asked to absorb
 // that), R 2 Ld key rows per TILE, 2 rows written - per limb.
 struct QpSumElts { unsigned v[kMaxGaloisBatch]; };
@@ -72,28 +75,11 @@ __global__ __launch_bounds__(256) void hoisted_qp_sum_kernel(u64* __restrict__ o
     bool sw = pm.swap;
     request(x, e0, e1, 0u, 0, pm.src);
 
-    // what differs between the arithmetic classes: the accumulators, one term's products, the final words
-    typedef FoldArith::Dot30 Dot;
-    typedef FoldArith::Half30 Half;
-    Dot s0[TI][2], s1[TI][2];      // fold: lazy columns ...
-    u64 r0[TI][2], r1[TI][2];      // ... and the folded running words; generic: the canonical running sums
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) { s0[i][h] = Dot{0, 0, 0}; s1[i][h] = Dot{0, 0, 0}; r0[i][h] = 0; r1[i][h] = 0; }
-    int terms = 0;
-    auto fold_all = [&]() {
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                r0[i][h] = FoldArith::dot30_fold(s0[i][h], r0[i][h], lc); s0[i][h] = Dot{0, 0, 0};
-                r1[i][h] = FoldArith::dot30_fold(s1[i][h], r1[i][h], lc); s1[i][h] = Dot{0, 0, 0};
-            }
-        terms = 0;
-    };
-    const u64 pmod = Arith::kFold ? FoldArith::canon(p_special, lc) : ShoupArith::mul_var(p_special, 1, lc);
-    auto accw = [&](u64 acc, u64 a, u64 b) -> u64 { return add_mod(acc, ShoupArith::mul_var(a, b, lc), lc.q); };
+    // what differs between the arithmetic classes - the accumulators, one term's products, the fold period, the final words - is the lane's (rotate_sum.h)
+    typedef QpSumLane<Arith> Lane;
+    Lane lane;
+    lane.clear();
+    const u64 pmod = Lane::p_operand(p_special, lc);
 
 #pragma unroll 1
     for (unsigned u = 0; u < total; ++u) {
@@ -115,41 +101,30 @@ __global__ __launch_bounds__(256) void hoisted_qp_sum_kernel(u64* __restrict__ o
         for (int i = 0; i < TI; ++i) xn[i] = x[i];
         request(xn, e0n, e1n, rn, jn, pn.src);
 
-        if constexpr (Arith::kFold) {
-            // all operands are canonical residues (< 2^60), which is what split30 needs
-            if (terms == FoldArith::kDot30Period) fold_all();   // workgroup-uniform
-            ++terms;
+        lane.begin_term(lc);   // (fold: the period's fold, workgroup-uniform)
+        if constexpr (Arith::kFold) {   // the kind of term outside the rows: a key pair is split once for the tile
             if (j < Ld) {
-                const Half k0a = FoldArith::split30(e0.a), k0b = FoldArith::split30(e0.b), k1a = FoldArith::split30(e1.a), k1b = FoldArith::split30(e1.b);
+                const typename Lane::Key k = Lane::split_key(e0.a, e0.b, e1.a, e1.b);
 #pragma unroll
                 for (int i = 0; i < TI; ++i) {
                     if ((unsigned)i >= rows) continue;
-                    const Half xa = FoldArith::split30(sw ? x[i].b : x[i].a), xb = FoldArith::split30(sw ? x[i].a : x[i].b);
-                    FoldArith::dot30_mac(s0[i][0], xa, k0a);
-                    FoldArith::dot30_mac(s0[i][1], xb, k0b);
-                    FoldArith::dot30_mac(s1[i][0], xa, k1a);
-                    FoldArith::dot30_mac(s1[i][1], xb, k1b);
+                    lane.digit_term(i, sw ? x[i].b : x[i].a, sw ? x[i].a : x[i].b, k, lc);
                 }
             } else {
-                const Half hp = FoldArith::split30(pmod);
+                const typename Lane::PTerm hp = Lane::split_p(pmod);
 #pragma unroll
                 for (int i = 0; i < TI; ++i) {
                     if ((unsigned)i >= rows) continue;
-                    FoldArith::dot30_mac(s0[i][0], FoldArith::split30(sw ? x[i].b : x[i].a), hp);
-                    FoldArith::dot30_mac(s0[i][1], FoldArith::split30(sw ? x[i].a : x[i].b), hp);
+                    lane.p_term(i, sw ? x[i].b : x[i].a, sw ? x[i].a : x[i].b, hp, lc);
                 }
             }
-        } else {
+        } else {                        // nothing to split: the rows outside (fewer registers live across the branch)
 #pragma unroll
             for (int i = 0; i < TI; ++i) {
                 if ((unsigned)i >= rows) continue;
                 const u64 xa = sw ? x[i].b : x[i].a, xb = sw ? x[i].a : x[i].b;
-                if (j < Ld) {
-                    r0[i][0] = accw(r0[i][0], xa, e0.a); r0[i][1] = accw(r0[i][1], xb, e0.b);
-                    r1[i][0] = accw(r1[i][0], xa, e1.a); r1[i][1] = accw(r1[i][1], xb, e1.b);
-                } else {
-                    r0[i][0] = accw(r0[i][0], xa, pmod); r0[i][1] = accw(r0[i][1], xb, pmod);
-                }
+                if (j < Ld) lane.digit_term(i, xa, xb, Lane::split_key(e0.a, e0.b, e1.a, e1.b), lc);
+                else lane.p_term(i, xa, xb, Lane::split_p(pmod), lc);
             }
         }
 #pragma unroll
@@ -158,20 +133,14 @@ __global__ __launch_bounds__(256) void hoisted_qp_sum_kernel(u64* __restrict__ o
         r = rn; j = jn; pm = pn; sw = pn.swap;
     }
     if (!ok) return;
-    if constexpr (Arith::kFold) {
-        fold_all();
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { r0[i][h] = FoldArith::canon_small(r0[i][h], lc); r1[i][h] = FoldArith::canon_small(r1[i][h], lc); }
-    }
+    lane.finish(lc);
     // written once, read by the inverse transform's launch: around the caches the keys and digits live in
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
         if ((unsigned)i >= rows) continue;
         U64x2* o0 = reinterpret_cast<U64x2*>(out + (((size_t)(t0 + i) * 2 + 0) * L + limb) * N) + mo;
-        st_vec<true>(o0, U64x2{r0[i][0], r0[i][1]});
-        st_vec<true>(o0 + row, U64x2{r1[i][0], r1[i][1]});
+        st_vec<true>(o0, U64x2{lane.r0[i][0], lane.r0[i][1]});
+        st_vec<true>(o0 + row, U64x2{lane.r1[i][0], lane.r1[i][1]});
     }
 }
 

@@ -390,6 +390,63 @@ def hoisted_inputs(orc, data, elts, tokens, seed, per_limb=False):
     return (cts, np.ascontiguousarray(np.stack([k for k, _ in made]))), sum(m for _, m in made)
 
 
+def edge_sums():
+    """NEXT [9][9]: the index in target_set of T_i + T_s where that sum is in T again, else -1.  With q = 2 h + 1 an element of T is a h + b (a in {0, 1},
+    b in -2 .. 2) and 2 h = -1, so the table is the same for every prime (above 16, where the nine elements are distinct)"""
+    rep = [(0, 0), (0, 1), (0, 2), (0, -2), (0, -1), (1, -1), (1, 0), (1, 1), (1, 2)]
+    nxt = np.full((N_TARGETS, N_TARGETS), -1, np.int64)
+    for i, (a, b) in enumerate(rep):
+        for s, (c, d) in enumerate(rep):
+            e = (a + c, b + d) if a + c < 2 else (0, b + d - 1)
+            if e in rep:
+                nxt[i, s] = rep.index(e)
+    return nxt
+
+
+def rotate_sum_inputs(orc, data, elts, tokens, seed, per_limb=False):
+    """cts [tokens][2][L-1][N] and one key per Galois element [R][L-1][2][L][N] for the hoisted slot SUM (dpfhe_rotate_sum_hoisted), targeted at token 0.
+    With x_{r,j} the digits as rotation r multiplies them (digit_transforms with galois_elt) and P perm_r(c0) the term that shares component 0's sum on the
+    data limbs (block 1 + r of rotate_hoisted_qp under a zero key), word by word:
+      every digit product x_{r,j} key_{r,j,c} but the last digit's is in T;
+      every per-rotation sum (block 1 + r: the key products and the P term) is in T;
+      the running total after each rotation is in T - a walk through T that only takes steps which are in T themselves (edge_sums);
+      the last digit of each rotation carries (the target for the running total) - (everything before it: the total so far, the P term, the other digits).
+    Where a digit's transform holds a 0 no key word reaches a non-zero target: those (rotation, digit, component, word) places are counted; the next
+    rotation's last digit aims from the total as it stands, so a missed word costs that rotation's sum and total only.  -> ((cts, keys), n_untargeted)"""
+    L, n, Ld, R = orc.L, orc.n, data.L, len(elts)
+    cts = data.fill(tokens * 2, seed).reshape(tokens, 2, Ld, n)
+    p_terms = orc.rotate_hoisted_qp(cts[0], elts, np.zeros((R, Ld, 2, L, n), np.uint64), threads=0)[1:]
+    table, nxt = _limb_table(orc, target_set), edge_sums()
+    limb = np.arange(L)[None, :, None]
+    k = np.arange(n)[None, None, :]
+    spread = k + 2 * limb + 5 * np.arange(2)[:, None, None] + seed
+    pace = 4 + k // N_TARGETS                                    # another sequence of steps for every run of nine words: the walks do not move in lockstep
+    state = np.zeros((2, L, n), np.int64)                       # the running total's place in T: it starts on 0
+    running = constant(orc, (2,), lambda q: 0)
+    keys, miss = [], np.zeros(L, np.int64)
+    for r, g in enumerate(elts):
+        x = digit_transforms(orc, cts[0, 1], g)
+        xc = np.ascontiguousarray(np.broadcast_to(x[:, None], (Ld, 2, L, n)))
+        step = np.full(state.shape, -1, np.int64)                # this rotation's sum: the first of nine candidates whose total stays in T (0 always does)
+        for d in range(N_TARGETS):
+            cand = (spread + pace * r + d) % N_TARGETS
+            step = np.where((step < 0) & (nxt[state, cand] >= 0), cand, step)
+        state = nxt[state, step]
+        total = np.ascontiguousarray(table[limb, state])
+        tgt = np.ascontiguousarray(targets(orc, (Ld, 2), seed + 1 + r))
+        fallback = orc.fill(Ld * 2, seed + 1 + r).reshape(Ld, 2, L, n)
+        key, zero = key_for_targets(orc, x, tgt, fallback)
+        rest = add(orc, running, np.ascontiguousarray(p_terms[r]))
+        for j in range(Ld - 1):
+            rest = add(orc, rest, mul(orc, np.ascontiguousarray(key[j]), xc[j]))
+        tgt[Ld - 1] = sub(orc, total, rest)
+        key[Ld - 1] = key_for_targets(orc, x[Ld - 1:], tgt[Ld - 1:], fallback[Ld - 1:])[0][0]
+        running = add(orc, rest, mul(orc, np.ascontiguousarray(key[Ld - 1]), xc[Ld - 1]))
+        keys.append(key)
+        miss += (zero[:, None] & (tgt != 0)).sum(axis=(0, 1, 3))
+    return (cts, np.ascontiguousarray(np.stack(keys))), (miss if per_limb else int(miss.sum()))
+
+
 # ---- rescale --------------------------------------------------------------------------------------------------------------------------------------------------------
 def rescale_inputs(orc, lead, seed):
     """x [*lead][L][N] with x_i = R q_last + x_last (mod q_i) on the limbs below the last: (x_i - x_last) q_last^-1 = R in T.  The rounding adds

@@ -5,7 +5,8 @@
   - oracle.c's relinearize, keyswitch_hybrid (2 and 3 components), switch_key_qp and rotate_hoisted_qp equal their definitions in Python integers
     (tests/test_packed_stage_edges_cpu.py: direct evaluation of the transform, the lift as the residue in [0, q_j), the division by P on the integer the
     residues represent) at N = 256 with 8, 14 and 17 limbs - the oracle reduces after every product, so nothing in it depends on the digit count, and
-    this shows it;
+    this shows it; and so does the reference of the hoisted slot sums (tests/test_gpu_rotate_sum.py reference, composed of those parts) equal
+    out = ct + round(INTT(S) / P) for 1, 3 and 9 rotations;
   - the adversarial keys of class_edges.adversarial_key do what they claim, on the oracle alone, at 14, 17 and 40 limbs: x e = q - 1 in Python integers
     for every word with x != 0, at most 1 word in 1000 with x = 0, and the closed form - relinearize returns (c0, c1) with coefficient 0 shifted by -L,
     switch_key_qp the constant -Ld in every word, keyswitch_hybrid (c0, c1) unchanged (the sum is Q P - Ld, which divided by P rounds to Q = 0)."""
@@ -146,6 +147,39 @@ def test_rotate_hoisted_qp_is_its_definition_at_every_digit_count(chain):
     for t in range(2):
         got = orc.rotate_hoisted_qp(cts[t], elts, keys, threads=0)
         assert same(got, rotate_hoisted_qp_definition(ints(cts[t]), elts, ints(keys), p)), (Ld, t)
+
+
+def rotate_sum_definition(ct, elts, keys, p):
+    """include/dpfhe.h dpfhe_rotate_sum_hoisted for one item: out = ct + round(INTT(S) / P), S the sum mod q_l of blocks 1 .. R of
+    dpfhe_rotate_hoisted_qp; ct [2][Ld][N], keys [R][Ld][2][L][N] -> [2][Ld][N]"""
+    return rotate_sum_closed(ct, rotate_hoisted_qp_definition(ct, elts, keys, p)[1:], p)
+
+
+def rotate_sum_closed(ct, blocks, p):
+    """the same from the rotations' blocks [R][2][L][N]"""
+    S = blocks.sum(axis=0) % np.array(p.moduli, object)[:, None]
+    t = np.stack([np.stack([intt(S[c, i], q, psi) for i, (q, psi) in enumerate(zip(p.moduli, p.psi))]) for c in range(2)])
+    return (divide_by_last(t, p.moduli) + ct) % np.array(p.moduli[:-1], object)[:, None]
+
+
+def test_rotate_sum_reference_is_its_definition_at_every_digit_count(chain):
+    """test_gpu_rotate_sum.reference - what every device test of the hoisted slot sums is held to, composed of oracle parts - against the definition in
+    Python integers, for 1, 3 and 9 rotations (the definition's blocks are taken once: the sums of 1 and 3 rotations are over a prefix of the nine)"""
+    from types import SimpleNamespace
+
+    from test_gpu_rotate_sum import reference
+    p, orc, data = chain
+    L, Ld = p.n_limbs, p.n_limbs - 1
+    r = SimpleNamespace(p=p, orc=orc, L=L, n=N, qcol=np.array(p.moduli, np.uint64)[:, None])
+    elts = [3, pow(3, -1, 2 * N), 5, N + 1, 2 * N - 1, 2 * N - 3, pow(3, 77, 2 * N), 1, pow(3, N // 4, 2 * N)]
+    keys = words(orc, (9, Ld, 2), 70)                   # stripes in rotation 0's key, q - 1 everywhere in rotation 1's
+    ct = words(data, (2, 2), 71)[:1]                    # the striped item
+    blocks = rotate_hoisted_qp_definition(ints(ct[0]), elts, ints(keys), p)[1:]
+    for R in (1, 3, 9):
+        got = reference(r, ct, elts[:R], keys[:R])
+        assert got.shape == (1, 2, Ld, N) and same(got[0], rotate_sum_closed(ints(ct[0]), blocks[:R], p)), (Ld, R)
+        if R == 1:                                      # the definition as it is written, blocks and all
+            assert same(got[0], rotate_sum_definition(ints(ct[0]), elts[:1], ints(keys[:1]), p))
 
 
 # ---- the adversarial keys, on the oracle alone -------------------------------------------------------------------------------------------------------------------

@@ -8,13 +8,17 @@ rungs (class_edges.LADDER) stand on both sides of every rule that reads the digi
   launch_relin                 relin_shared_kernel for fold, 1024 <= N <= 4096, 4..7 digits; relin_kernel otherwise (and kLdsKeys key tiles at N = 8192)
   launch_hoisted_ks            hoisted_ks2_kernel (merged) for fold, Ld <= 7 and rotations x L x tokens >= 512; the split kernel otherwise
   dpfhe_rotate_hoisted_qp      hoisted_qp_upfront_kernel<LD> for Ld 1..6, hoisted_qp_stream_kernel from 7; Dot30 column sums folded every 8 terms
+  dpfhe_rotate_sum_hoisted     hoisted_qp_sum_kernel: J = Ld + 1 terms per rotation (Ld on the special limb), Dot30 columns folded every 8 terms counted
+                               ACROSS the rotations - J = 8 / 9 is a period equal to / one past a rotation; item tiles of 4
   per-limb classes             L <= 16 (16 nibbles of active_map); 17 limbs run on the context-wide policy
 
 Every comparison is a whole buffer, word for word, against the oracle (threads=0), which reduces after every product whatever the digit count and is
 held to Python integers at 8, 14 and 17 limbs by tests/test_digit_ladder_cpu.py.  Inputs are Rig.words - stripes in item 0, q - 1 in every word of
 item 1, ciphertexts and keys - and, on the fold rungs, ADVERSARIAL keys (class_edges.adversarial_key): random words would never fill a lazy sum
 (17 random products are about 8.5 q, a word holds 16 q), and q - 1 in the inputs does not either, the products being taken in the NTT domain; these
-keys make every lazily added product of item 0 the word q - 1, so the schedule runs at the worst case it was designed for.  One case = one entry on
+keys make every lazily added product of item 0 the word q - 1, so the schedule runs at the worst case it was designed for.  The sum kernel's Dot30 columns
+depend on the 30-bit HALVES of the operands, not on the remainder: saturated_rotate_sum_hoisted plants constants whose halves are the largest a canonical
+word has (tests/rotate_sum_ref.py, where eight such terms are shown to fill a column and nine to wrap it).  One case = one entry on
 one rung; a rung's context and keys are built once and shared by its cases."""
 from concurrent.futures import ThreadPoolExecutor
 
@@ -28,10 +32,26 @@ pytestmark = pytest.mark.gpu
 
 ENTRIES_RNS = ("relinearize", "apply_galois")                                      # L digits
 ENTRIES_P = ("keyswitch_hybrid", "rotate_hybrid_batch", "rotate_hybrid_grouped", "rotate_hybrid_hoisted", "switch_key_qp_1x3", "switch_key_qp_9x2",
-             "rotate_hoisted_qp")                                                   # L - 1 digits
-ENTRIES_FOLD = ("adversarial_relinearize", "adversarial_switch_key_qp", "adversarial_keyswitch_hybrid")
-CASES = [(rung, e) for rung in LADDER
-         for e in ENTRIES_RNS + (ENTRIES_P if rung[2] >= 2 else ()) + (ENTRIES_FOLD[:1 if rung[2] < 2 else 3] if rung[0] == "fold" else ())]
+             "rotate_hoisted_qp", "rotate_sum_hoisted")                             # L - 1 digits
+ENTRIES_FOLD = ("adversarial_relinearize", "adversarial_switch_key_qp", "adversarial_keyswitch_hybrid", "adversarial_rotate_sum_hoisted")
+SATURATED_L = (2, 8, 9, 10, 17)                                                    # fold, N = 256: the rungs of saturated_rotate_sum_hoisted
+
+
+def is_heavy(rung):
+    """LadderRig.heavy, from the rung alone"""
+    return rung[2] * rung[2] * (1 << rung[1]) > (1 << 23)
+
+
+def fold_entries(rung):
+    kind, log2n, L = rung
+    if kind != "fold":
+        return ()
+    if L < 2:
+        return ENTRIES_FOLD[:1]
+    return (ENTRIES_FOLD[:3 if is_heavy(rung) else 4]) + (("saturated_rotate_sum_hoisted",) if log2n == 8 and L in SATURATED_L else ())
+
+
+CASES = [(rung, e) for rung in LADDER for e in ENTRIES_RNS + (ENTRIES_P if rung[2] >= 2 else ()) + fold_entries(rung)]
 IDS = [f"{k}_n{1 << ln}_l{L}-{e}" for (k, ln, L), e in CASES]
 
 
@@ -52,6 +72,7 @@ class LadderRig(Rig):
         # the one rung on which a key alone is 200 MB (N = 8192, 40 limbs): the smallest batches that still reach every form - one or two rotations, one item
         # per key
         self.heavy = L * L * self.n > (1 << 23)
+        assert self.heavy == is_heavy((kind, log2n, L))
         self.max_keys = 16 if kind == "fold" and L in (8, 9) else 9
         self._made = {}
 
@@ -223,6 +244,32 @@ def rotate_hoisted_qp(r):
     assert np.array_equal(closed, rescale_bsgs_reference(orc, r.data, orc.ntt_inv(want[k], threads=0), cts[None]))
 
 
+def rotate_sum_shapes(r, kind):
+    """(rotations, items): 9 x 3 - a tile with 3 live rows, 9 (Ld + 1) terms - everywhere but on the heavy rung (2 x 1); on the fold N = 256 rungs with 8 and
+    9 limbs - 8 and 9 terms per rotation - also the cap of 64 rotations on 7 items (tiles of 4 and 3)"""
+    if r.heavy:
+        return [(2, 1)]
+    return [(9, 3)] + ([(64, 7)] if kind == "fold" and r.n == 256 and r.L in (8, 9) else [])
+
+
+def rotate_sum_hoisted(r, kind):
+    from deeppowers_amd.evaluator import Ciphertext
+    from test_gpu_rotate_sum import reference
+    for k, T in rotate_sum_shapes(r, kind):
+        elts = elements(r.n, k)
+        assert len(set(elts)) == k
+        if k <= r.max_keys:
+            keys, dks = r.rotation_keys(k)
+            keys = np.stack(keys)
+        else:                                              # keys of its own: stripes in key 0, q - 1 in every word of key 1
+            keys = r.words(r.orc, (k, r.L - 1, 2), 980)
+            dks = r.dev(keys)
+        cts = r.words(r.data, (max(T, 2), 2), 981 + k)[:T]
+        got = host(r.ev.rotate_sum_hoisted(Ciphertext(r.dev(cts)), elts, dks).data)
+        want = reference(r, cts, elts, keys)
+        assert np.array_equal(got, want), (k, T, np.argwhere(got != want)[:4])
+
+
 # ---- adversarial keys (fold rungs) ---------------------------------------------------------------------------------------------------------------------------
 def checked_adversarial_key(orc, digits, seed):
     """class_edges.adversarial_key with its own claims asserted: x e = q - 1 wherever x != 0 (by the oracle's modular multiply, itself held to Python
@@ -301,8 +348,70 @@ def adversarial_keyswitch_hybrid(r):
         assert np.array_equal(host(got.data), want), comps
 
 
+def adversarial_rotate_sum_hoisted(r):
+    """nine rotations: the key of rotation g is solved against item 0's digits as THAT rotation multiplies them (lifted, then rotated), every target q - 1,
+    and item 0's c0 is the constant -(P^-1) mod q_l, so that P NTT(c0) is q_l - 1 in every word under every permutation: every term the sum kernel adds for
+    item 0 - key products and the P c0 term that shares component 0's columns - is the largest canonical word"""
+    from deeppowers_amd.evaluator import Ciphertext
+    import remainder_edges as re_
+    from test_gpu_rotate_sum import reference
+    orc, data, Ld, n, P = r.orc, r.data, r.L - 1, r.n, r.p.moduli[-1]
+    elts = elements(n, 9)
+    cts = r.words(data, (r.batch, 2), 990)
+    cts[0, 0] = 0
+    cts[0, 0, :, 0] = [(-pow(P, -1, q)) % q for q in data.moduli]
+    qcol = r.qcol
+    keys = []
+    for i, g in enumerate(elts):
+        x = re_.digit_transforms(orc, cts[0, 1], galois_elt=g)
+        rnd = orc.fill(Ld, 991 + i)
+        key, zero = re_.key_for_targets(orc, x, re_.constant(orc, (Ld, 2), lambda q: q - 1), np.stack([rnd, rnd], axis=1))
+        for c in range(2):
+            prod = orc.dyadic("mul", x, np.ascontiguousarray(key[:, c]), threads=0)
+            assert bool(((prod == qcol - np.uint64(1)) | (x == 0)).all()), (g, c)
+        assert int(zero.sum()) * 1000 <= x.size, (g, int(zero.sum()), x.size)
+        keys.append(key)
+    keys = np.stack(keys)
+    pc0 = data.dyadic("mul", data.ntt_fwd(cts[0, 0][None].copy(), threads=0), re_.constant(data, (1,), lambda q: P), threads=0)
+    assert np.array_equal(pc0[0], np.broadcast_to(qcol[:Ld] - np.uint64(1), (Ld, n)))
+    got = host(r.ev.rotate_sum_hoisted(Ciphertext(r.dev(cts)), elts, r.dev(keys)).data)
+    want = reference(r, cts, elts, keys)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4]
+
+
+def saturated_rotate_sum_hoisted(r):
+    """nine rotations of two items whose every digit word is one constant v - min q - 1 (item 0) and lowmax = 2^60 - 2^30 - 1 (item 1), the words with the
+    largest high and low 30-bit halves -: c1 is the constant polynomial v on every limb, its lift is v mod q_l = v and the transform of a constant is that
+    constant in every word, under every permutation.  Keys: q_l - 1 in every word for the odd rotations, lowmax for the even ones; c0: the constant lowmax.
+    Every Dot30 column of the sum kernel then runs as full as canonical words can make it (tests/test_emulated_rotate_sum.py)"""
+    from deeppowers_amd.evaluator import Ciphertext
+    import remainder_edges as re_
+    import rotate_sum_ref as rs
+    from test_gpu_rotate_sum import reference
+    orc, data, L, Ld, n = r.orc, r.data, r.L, r.L - 1, r.n
+    low = rs.lowmax(min(r.p.moduli))
+    assert low == (1 << 60) - (1 << 30) - 1
+    values = (min(r.p.moduli) - 1, low)
+    elts = elements(n, 9)
+    cts = np.zeros((2, 2, Ld, n), np.uint64)
+    cts[:, 0, :, 0] = low
+    for t, v in enumerate(values):
+        cts[t, 1, :, 0] = v
+    keys = np.empty((9, Ld, 2, L, n), np.uint64)
+    keys[0::2] = low
+    keys[1::2] = r.qcol - np.uint64(1)
+    for t, v in enumerate(values):                         # the digit words the device multiplies, by the oracle's own lift, automorphism and transform
+        for g in elts:
+            assert bool((re_.digit_transforms(orc, cts[t, 1], galois_elt=g) == np.uint64(v)).all()), (t, g)
+    assert bool((data.ntt_fwd(np.ascontiguousarray(cts[:, 0]), threads=0) == np.uint64(low)).all())
+    got = host(r.ev.rotate_sum_hoisted(Ciphertext(r.dev(cts)), elts, r.dev(keys)).data)
+    want = reference(r, cts, elts, keys)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4]
+
+
 RUN = {f.__name__: f for f in (relinearize, apply_galois, keyswitch_hybrid, rotate_hybrid_batch, rotate_hybrid_grouped, switch_key_qp_1x3, switch_key_qp_9x2,
-                              rotate_hoisted_qp, adversarial_relinearize, adversarial_switch_key_qp, adversarial_keyswitch_hybrid)}
+                              rotate_hoisted_qp, adversarial_relinearize, adversarial_switch_key_qp, adversarial_keyswitch_hybrid,
+                              adversarial_rotate_sum_hoisted, saturated_rotate_sum_hoisted)}
 
 
 @pytest.mark.parametrize("rung,entry", CASES, ids=IDS)
@@ -310,5 +419,7 @@ def test_key_switching_along_the_digit_count(rung_rig, rung, entry):
     r = rung_rig(rung)
     if entry == "rotate_hybrid_hoisted":
         rotate_hybrid_hoisted(r, rung[0])
+    elif entry == "rotate_sum_hoisted":
+        rotate_sum_hoisted(r, rung[0])
     else:
         RUN[entry](r)

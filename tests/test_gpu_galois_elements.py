@@ -16,6 +16,8 @@ at the rings where a kernel takes another path:
     2 tokens                     (stream form)
   dpfhe_rotate_add_hybrid        N = 256: eight ladders of 32 steps, every        N = 8192, 16384: one single-step call per element
     2 items                      element once as a step
+  dpfhe_rotate_sum_hoisted       N = 256 at L = 3 and L = 9: sixteen sums of 16   N = 1024 mixed classes; N = 8192; N = 16384 (composed transforms): sums of
+    2 items                      elements, every element once as a term           at most 64 elements; g = 1 and a repeated element in one sum
 
 The elements of a case always go in ONE call where the entry takes a list, so the launch groups of 64 elements are crossed (edge_elements has 67 at
 N = 8192).  Keys are orc.fill words; one ciphertext component is q - 1 in every word; inputs are distinct per item up to N = 4096 and three base inputs cycled
@@ -210,6 +212,59 @@ def test_rotate_hoisted_qp(rig, kind, ln, L, which):
         want = orc.rotate_hoisted_qp(cts[t], elts, keys, threads=0)
         assert np.array_equal(got[0, t], want[0]), (t, "identity block")
         assert wrong(got[1:, t], want[1:], elts) == [], t
+
+
+# ---- dpfhe_rotate_sum_hoisted ----------------------------------------------------------------------------------------------------------------------------------
+def sum_call(r, cts, elts, seed):
+    """one call of the entry against test_gpu_rotate_sum.reference -> True when every word agrees"""
+    from deeppowers_amd.evaluator import Ciphertext, to_host
+    from test_gpu_rotate_sum import reference
+    keys, dkeys = rotation_keys(r, len(elts), seed)
+    got = to_host(r.ev.rotate_sum_hoisted(Ciphertext(r.dev(cts)), elts, dkeys).data)
+    return np.array_equal(got, reference(r, cts, elts, keys))
+
+
+@pytest.mark.parametrize("L", (3, 9))
+def test_rotate_sum_over_the_whole_group(rig, L):
+    """N = 256, 2 items: sixteen calls, call j sums the rotations by the elements 2 (16 i + j) + 1 - every call mixes both halves of the group, and a failure
+    names a call of 16 elements"""
+    r = rig("fold", 8, L)
+    every = ge.all_elements(8)
+    cts, _ = inputs(r.data, 2, 2, 2000 + L)
+    run, bad = [], []
+    for j in range(16):
+        elts = every[j::16]
+        run += elts
+        if not sum_call(r, cts, elts, 2010 + j):
+            bad.append(elts)
+    assert sorted(run) == every
+    assert bad == []
+
+
+SUM_CASES = [("mixed", 10, 4), ("fold", 13, 3), ("fold", 14, 2)]
+
+
+@pytest.mark.parametrize("kind,ln,L", SUM_CASES, ids=[f"{kind}-n{1 << ln}-l{L}" for kind, ln, L in SUM_CASES])
+def test_rotate_sum_edge_elements(rig, kind, ln, L):
+    """the edge elements in calls of at most 64 (the entry's cap): N = 1024 on the mixed classes, N = 8192, N = 16384 (composed transforms)"""
+    r = rig(kind, ln, L)
+    assert r.L == L
+    elts = ge.edge_elements(ln)
+    cts, _ = inputs(r.data, 2, 2, 2100 + ln)
+    size = -(-len(elts) // -(-len(elts) // 64))                                            # the fewest calls, of even sizes: 49; 34 + 33; 37 + 36
+    calls = [elts[i:i + size] for i in range(0, len(elts), size)]
+    assert [g for c in calls for g in c] == elts and all(8 <= len(c) <= 64 for c in calls)
+    bad = [c for i, c in enumerate(calls) if not sum_call(r, cts, c, 2110 + ln + i)]
+    assert bad == []
+
+
+def test_rotate_sum_takes_the_identity_and_repeated_elements(rig):
+    """check_galois_elts (cabi.h) asks for odd elements below 2N and nothing else: g = 1 (the identity's map: every pair its own source) and an element named
+    twice, with two different keys, are summed like any other"""
+    r = rig("fold", 8, 3)
+    cts, _ = inputs(r.data, 3, 2, 2200)
+    assert sum_call(r, cts, [1], 2201)
+    assert sum_call(r, cts, [5, 1, 5, 2 * r.n - 1, 1, 5, 3, 3], 2202)
 
 
 # ---- dpfhe_rotate_add_hybrid -----------------------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,10 @@ relin_shared_kernel) and 13 (the dual form, the halves transforms, the LDS key t
 quarters form at 14 - are out of scope here: their stage structure differs from the builders' radix-2 model.
 
 A case that could not target its words must not pass quietly: every case asserts its builder's n_untargeted - exactly 0 for the dyadic, tensor,
-transform and rescale builders, at most 1 % of the key's words for key material (the digits' transforms can hold zeros)."""
+transform and rescale builders, at most 1 % of the key's words for key material (the digits' transforms can hold zeros).
+
+The hoisted slot sums (dpfhe_rotate_sum_hoisted) have a builder of their own, rotate_sum_inputs: besides the digit products, every rotation's sum and the
+running total ACROSS rotations - the P perm(c0) term that shares component 0's sum included - are in T."""
 import numpy as np
 import pytest
 
@@ -201,3 +204,20 @@ def test_key_switching_at_the_remainder_edges(rig, kind, log2n):
     got = host(r.ev.rotate_hybrid_hoisted(Ciphertext(r.dev(cts)), list(elts), r.dev(keys)).data).reshape(len(elts), T, 2, L - 1, n)
     for t in range(T):
         assert np.array_equal(got[:, t], orc.rotate_hoisted(cts[t], elts, keys, threads=0)), t
+
+
+@pytest.mark.parametrize("kind,log2n", KEY_CONTEXTS, ids=ids(KEY_CONTEXTS))
+def test_rotate_sum_at_the_remainder_edges(rig, kind, log2n):
+    """rotate_sum_hoisted over (3, 3^9, 2N - 1) under keys solved against item 0's digits and its P perm(c0) terms: every digit product but a rotation's last
+    in T, every rotation's sum in T, the running total after each rotation in T - what add_mod takes after mul_var on the generic arm and what dot30_fold
+    and canon_small return on the fold arm (tests/test_remainder_edges_cpu.py holds the builder to these claims and the emulated lane to all nine targets)"""
+    from deeppowers_amd.evaluator import Ciphertext
+    from test_gpu_rotate_sum import reference
+    r = rig(kind, log2n)
+    data = Oracle(log2n, r.p.moduli[:-1], r.p.psi[:-1])
+    elts = list(re_.rotation_elements(r.n))
+    (cts, keys), miss = re_.rotate_sum_inputs(r.orc, data, elts, 2, 730)
+    under_cap(miss, keys)
+    got = host(r.ev.rotate_sum_hoisted(Ciphertext(r.dev(cts)), elts, r.dev(keys)).data)
+    want = reference(r, cts, elts, keys)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4]

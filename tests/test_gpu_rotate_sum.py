@@ -13,9 +13,10 @@ from deeppowers_amd.params import FheParams
 pytestmark = pytest.mark.gpu
 rig = fp.rig
 
-# a ring below one segment (one item; a tile + a remainder tile; the cap); several segments per class, 9 (Ld + 1) terms; P of another class; composed transforms
-SHAPES = ([("fold", 8, (1, 1)), ("fold", 8, (7, 5)), ("fold", 8, (64, 2))] + [(k, 12, (9, 4)) for k in CLASSES + ("mixed",)]
-          + [("f64_under_fold", 12, (3, 2)), ("fold", 14, (3, 2)), ("fold", 15, (3, 2))])
+# a ring below one segment (one item; a tile + a remainder tile; a tile with 3 live rows; the cap); several segments per class, 9 (Ld + 1) terms; the mixture
+# with a tile of 4 and one of 3; P of another class; composed transforms
+SHAPES = ([("fold", 8, (1, 1)), ("fold", 8, (7, 5)), ("fold", 8, (3, 3)), ("fold", 8, (64, 2))] + [(k, 12, (9, 4)) for k in CLASSES + ("mixed",)]
+          + [("mixed", 12, (9, 7)), ("f64_under_fold", 12, (3, 2)), ("fold", 14, (3, 2)), ("fold", 15, (3, 2))])
 FOOTPRINT = [("fold", 8), ("f64_under_fold", 12), ("fold", 14)]
 
 

@@ -45,6 +45,9 @@ Entry -> cases (a batched entry of include/dpfhe.h that is in neither list is a 
                                                      (all four past B32 take 11 x 4 GiB)
   dpfhe_rotate_hybrid_batch                       A: rotate_hybrid_batch, one input: d_keys and d_work cross B32, d_rotated and d_out2 cross B31 (all four past B32
                                                      take 24.4 GiB, over the cap)
+  dpfhe_rotate_sum_hoisted                        A: rotate_sum_hoisted-fold at N = 4096 with three data limbs, three rotations, the ITEMS tiled (period 3 against the
+                                                     kernel's tile of 4): d_digits and d_sum_qp cross B32, d_in2, d_in_ntt and d_out2 cross B31.  The three are of one
+                                                     size (2 Ld N words per item), so d_in_ntt past B32 puts all five there: at least 24 GiB at any limb count, over the cap
   dpfhe_ntt_inv_galois                            A: ntt_inv_galois apart and in place, one element per item tiled with the same odd period
   dpfhe_add_plain / dpfhe_add_plain_scaled        A: add_plain*-broadcast (out of place) and -one-to-one (in place: the plaintexts cross too)
   dpfhe_compact / dpfhe_encode_slots / dpfhe_encode_complex   A: compact, encode_slots, encode_complex (each with and without the forward transform)
@@ -909,6 +912,28 @@ def _rotate_batch(r, pl, call):
     k = pl.batch
     i, pk, w, t, o = call.shared("in2", ct), call.inp("keys", keys), call.scratch("work", 2 * L * n), call.scratch("rotated", 2 * Ld * n), call.out("out2", want)
     call.run("dpfhe_rotate_hybrid_batch", lib.dpfhe_rotate_hybrid_batch(h, o, i, 1, u32([elts3[j % P] for j in range(k)]), pk, w, t, k, None))
+
+
+def rotate_sum_shape(L, n):
+    Ld, log2n = L - 1, n.bit_length() - 1
+    return {"items": {"digits": Ld * L * n, "sum_qp": 2 * L * n}, "low_items": {"in2": 2 * Ld * n, "in_ntt": 2 * Ld * n, "out2": 2 * Ld * n},
+            "writable": ("digits", "sum_qp", "in_ntt", "out2"), "extra": P * Ld * 2 * L * n * 8,
+            "limits": [("items", lambda b: b, 0xFFFFFFFF), ("lift workgroups", lambda b: b * Ld * L * chunks_of(n), K_MAX_GRID),
+                       ("sum workgroups", lambda b: -(-b // 4) * L * chunks_of(n), K_MAX_GRID), ("widest transform grid", lambda b: ntt_widest(log2n, b * Ld * L), K_MAX_GRID)]}
+
+
+@case("rotate_sum_hoisted-fold", "A", "fold", 12, rotate_sum_shape)
+def _rotate_sum(r, pl, call):
+    """three rotations of every item, the items tiled.  hoisted_qp_sum_kernel forms its own offsets into d_digits, d_in_ntt, d_sum_qp and the keys: d_digits
+    (12 N words per item) and d_sum_qp (8 N) cross B32, d_in_ntt with d_in2 and d_out2 (6 N each) crosses B31 - all five past B32 take 24 GiB and more"""
+    import test_gpu_rotate_sum as rs
+    lib, h, L, n = r.ctx._lib, r.ctx.handle, r.L, r.n
+    Ld, data = L - 1, data_oracle(r)
+    elts3, keys = hoisted_keys(r, 370)
+    cts = r.words(data, (P, 2), 372)
+    i, k, o = call.inp("in2", cts), call.shared("keys", keys), call.out("out2", rs.reference(r, cts, elts3, keys))
+    a, d, s = call.scratch("in_ntt", 2 * Ld * n), call.scratch("digits", Ld * L * n), call.scratch("sum_qp", 2 * L * n)
+    call.run("dpfhe_rotate_sum_hoisted", lib.dpfhe_rotate_sum_hoisted(h, o, i, pl.batch, u32(elts3), k, P, a, d, s, None))
 
 
 def relin_lincomb_shape(L, n):

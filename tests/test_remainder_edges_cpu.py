@@ -1,4 +1,5 @@
-"""CPU: the remainder-edge stimulus (tests/remainder_edges.py) against Python integers, and the emulated kernels (tools/emulate.cpp) on it.
+"""CPU: the remainder-edge stimulus (tests/remainder_edges.py) against Python integers, and the emulated kernels (tools/emulate.cpp; for the hoisted slot
+sums tools/emulate_rotate_sum.cpp) on it.
 
 The suite's other inputs pin the OPERANDS of a modular product (random words, q - 1 / 0 / q // 2 stripes); these pin its REMAINDER to
 T(q) = {0, 1, 2, q - 2, q - 1, h - 1, h, h + 1, h + 2}: where a conditional subtract after a floor quotient, the sign fix after a nearest-integer quotient
@@ -230,6 +231,120 @@ def test_targeted_keys_put_every_product_and_the_sum_over_the_digits_on_the_edge
     assert miss == 0 and all(in_t([int(a) * int(b) % q for a, b in zip(ints(x[1, l]), ints(one[0, c, l]))], q) for l, q in enumerate(orc.moduli) for c in range(2))
 
 
+def test_edge_sums_is_addition_inside_t(orc):
+    nxt = re_.edge_sums()
+    for q in orc.moduli:
+        t = re_.target_set(q)
+        assert len(set(t)) == 9
+        for i in range(9):
+            for s in range(9):
+                v = (t[i] + t[s]) % q
+                assert int(nxt[i, s]) == (t.index(v) if v in t else -1), (q, i, s)
+    assert (nxt[:, 0] == np.arange(9)).all() and (nxt[0] == np.arange(9)).all()       # a step of 0 is always open; from 0 every step is
+
+
+SUM_ELTS = [3, pow(3, -1, 2 * N), 5, N + 1, 2 * N - 1, 2 * N - 3, pow(3, 77, 2 * N), 1, pow(3, N // 4, 2 * N)]
+
+
+def rotate_sum_columns(o, data, cts, elts, keys):
+    """what the sum kernel multiplies, per rotation: x [R][Ld][L][N] (the digits, lifted, rotated, transformed) and c [R][Ld][N] (perm_r(NTT(c0)))"""
+    x = np.stack([re_.digit_transforms(o, cts[0, 1], g) for g in elts])
+    c = np.stack([data.ntt_fwd(data.apply_galois(cts[0, :1], g), threads=0)[0] for g in elts])
+    return x, c
+
+
+def test_rotate_sum_inputs_put_products_rotation_sums_and_running_totals_on_the_edges(orc):
+    """nine rotations of seven digits, Python integers: every digit product but the last digit's, every rotation's block (key products + P perm(c0)) and the
+    running total after every rotation are in T wherever no digit word is 0; the blocks are those of the oracle's rotate_hoisted_qp; the P term is restated
+    from the transform's definition"""
+    L, Ld, R = orc.L, orc.L - 1, len(SUM_ELTS)
+    data = Oracle(LN, orc.moduli[:-1], orc.psi[:-1])
+    P = orc.moduli[-1]
+    (cts, keys), miss = re_.rotate_sum_inputs(orc, data, SUM_ELTS, 2, 17)
+    assert cts.shape == (2, 2, Ld, N) and keys.shape == (R, Ld, 2, L, N)
+    x, c = rotate_sum_columns(orc, data, cts, SUM_ELTS, keys)
+    blocks = orc.rotate_hoisted_qp(cts[0], SUM_ELTS, keys, threads=0)[1:]
+    for l, (q, psi) in enumerate(zip(orc.moduli[:-1], orc.psi[:-1])):       # the P term's operand, restated for two rotations
+        for r in (0, 4):
+            rot = [0] * N
+            for k, v in enumerate(ints(cts[0, 0, l])):
+                idx = k * SUM_ELTS[r] % (2 * N)
+                rot[idx % N] = v if idx < N else (q - v) % q
+            assert ints(c[r, l]) == po.ntt_forward(rot, q, psi)
+    n_zero = int((x == 0).sum())
+    for l, q in enumerate(orc.moduli):
+        t = set(re_.target_set(q))
+        clean = [True] * N                                                   # no digit word of this limb was 0 up to this rotation
+        for comp in range(2):
+            total, seen_total, seen_sum, seen_prod = [0] * N, set(), set(), set()
+            clean = [True] * N
+            for r in range(R):
+                prods = [[int(x[r, j, l, k]) * int(keys[r, j, comp, l, k]) % q for k in range(N)] for j in range(Ld)]
+                pterm = [P * int(v) % q for v in c[r, l]] if comp == 0 and l < Ld else [0] * N
+                block = [(sum(col) + p) % q for col, p in zip(zip(*prods), pterm)]
+                assert block == ints(blocks[r, comp, l])
+                was_clean = list(clean)
+                clean = [ok and all(int(x[r, j, l, k]) for j in range(Ld)) for k, ok in enumerate(clean)]
+                total = [(a + b) % q for a, b in zip(total, block)]
+                for k in range(N):
+                    assert all(prods[j][k] in t for j in range(Ld - 1)), (l, comp, r, k)
+                    if int(x[r, Ld - 1, l, k]):
+                        assert total[k] in t, (l, comp, r, k)                  # the last digit re-aims the total whatever was missed before
+                    if clean[k]:
+                        assert block[k] in t and total[k] in t, (l, comp, r, k)
+                seen_total |= set(total) & t
+                seen_sum |= set(block) & t
+                seen_prod |= {v for j in range(Ld - 1) for v in prods[j]} & t
+            assert len(seen_total) == len(seen_sum) == len(seen_prod) == 9, (l, comp)
+    assert miss <= 2 * n_zero and n_zero * 100 <= x.size
+
+
+@pytest.fixture(scope="module")
+def sum_emu(tmp_path_factory):
+    from test_emulated_rotate_sum import build_emulator
+    return build_emulator(tmp_path_factory.mktemp("emu_rotate_sum"))
+
+
+@pytest.mark.parametrize("kind,sites", [("fold", ("fold.dot30_fold", "fold.canon_small")), ("shoup", ("shoup.mul_var",))])
+def test_emulated_sum_lane_sees_all_nine_targets(sum_emu, kind, sites):
+    """tools/emulate_rotate_sum.cpp (csrc/rotate_sum.h QpSumLane, assertions armed) over every word pair of every limb of the rotate_sum_inputs of an
+    N = 256 context, both tokens in one tile: the words equal the sum of the oracle's blocks, no precondition fires, and the primitives that take the
+    running sum - dot30_fold and canon_small on the fold lane, mul_var on the generic one - have each returned all nine targets"""
+    from test_emulated_mul_sum import CLASSES as EMU_CLASS
+    p = class_edges.edge_moduli(kind, LN)
+    o = Oracle.from_params(p)
+    data = Oracle(LN, p.moduli[:-1], p.psi[:-1])
+    L, Ld, R = o.L, o.L - 1, len(SUM_ELTS)
+    (cts, keys), _ = re_.rotate_sum_inputs(o, data, SUM_ELTS, 2, 23)
+    x = np.stack([np.stack([re_.digit_transforms(o, cts[t, 1], g) for g in SUM_ELTS]) for t in range(2)])                       # [2][R][Ld][L][N]
+    c = np.stack([np.stack([data.ntt_fwd(data.apply_galois(cts[t, :1], g), threads=0)[0] for g in SUM_ELTS]) for t in range(2)])   # [2][R][Ld][N]
+    want = np.stack([o.rotate_hoisted_qp(cts[t], SUM_ELTS, keys, threads=0)[1:].astype(object).sum(axis=0) % np.array(o.moduli, object)[:, None] for t in range(2)])
+    before = sum_emu.emu_rotate_sum_overflows()
+    sum_emu.emu_rotate_sum_notes_reset()
+    for l, q in enumerate(o.moduli):
+        has_p = l < Ld
+        J = Ld + 1 if has_p else Ld
+        xs = np.zeros((R, J, 2, N), np.uint64)                       # [rotation][term][row][word]
+        xs[:, :Ld] = x[:, :, :, l].transpose(1, 2, 0, 3)
+        if has_p:
+            xs[:, Ld] = c[:, :, l].transpose(1, 0, 2)
+        ks = np.zeros((R, J, 2, N), np.uint64)                       # [rotation][term][component][word]
+        ks[:, :Ld] = keys[:, :, :, l]
+        for m in range(N // 2):
+            xa = np.ascontiguousarray(xs[..., 2 * m: 2 * m + 2]).reshape(-1)                                   # [R J][rows][2]
+            ka = np.ascontiguousarray(ks[..., 2 * m: 2 * m + 2]).reshape(-1)                                   # [R J][e0.a, e0.b, e1.a, e1.b]
+            out = np.zeros(8, np.uint64)
+            assert sum_emu.emu_rotate_sum(EMU_CLASS[kind], q, p.moduli[-1], R, J, int(has_p), 2, p64(xa), p64(ka), p64(out)) == 0
+            got = out.reshape(2, 2, 2)                                # [row][component][half]
+            assert [int(v) for v in got.ravel()] == [int(want[t, comp, l, 2 * m + h]) for t in range(2) for comp in range(2) for h in range(2)], (l, m)
+    assert sum_emu.emu_rotate_sum_overflows() == before
+    buf = (C.c_uint * 64)()
+    assert sum_emu.emu_rotate_sum_notes_get(buf, 64) == len(SITE_NAMES)
+    for s in sites:
+        mask = buf[SITE_NAMES.index(s)]
+        assert mask & REACHED and mask & ALL_NINE == ALL_NINE, f"{kind}: {s} returned only the targets {mask & ALL_NINE:09b} of (0, 1, 2, q-2, q-1, h-1, h, h+1, h+2)"
+
+
 def test_adversarial_key_is_the_all_q_minus_1_case_with_unchanged_words(orc):
     digits = orc.fill(1, 41)[0][: orc.L - 1].copy()
     key, x, n_zero = class_edges.adversarial_key(orc, digits, 42)
@@ -294,8 +409,9 @@ ALL_NINE, REACHED = 0x1FF, 1 << 31
 #   an inverse transform multiplies the difference leg (mul_tw, mulmod); N^-1 is mul_ninv's exact division on FoldArith, a twiddle product otherwise.
 #   the generic fused multiply takes its dyadic products with Arith::mul_var (FoldScaledArith's through mul60); the lazy one with prod_tw + mul_ptw_add on
 #   the fold core and with mulmod on the f64 classes.
-# Primitives no emulated kernel calls - FoldArith::mul60_full, FoldArith::mul_var, FoldArith::dot30_fold (the key-switching and streaming kernels, which
-# run on the GPU only: tests/test_gpu_remainder_edges.py) - have a site but no row here.
+# Primitives no emulated kernel of tools/emulate.cpp calls - FoldArith::mul60_full, FoldArith::mul_var, FoldArith::dot30_fold (the key-switching and
+# streaming kernels, which run on the GPU only: tests/test_gpu_remainder_edges.py) - have a site but no row here; dot30_fold is reached through the sum
+# lane's own emulator (test_emulated_sum_lane_sees_all_nine_targets).
 TRANSFORM_SITES = {
     ("shoup", 0): ("shoup.mul_tw",), ("shoup", 1): ("shoup.mul_tw",),
     ("fold", 0): ("fold.mul_tw_add", "fold.reduce", "fold.canon_small"), ("fold", 1): ("fold.mul_tw", "fold.reduce", "fold.mul_ninv", "fold.canon_small"),
@@ -539,3 +655,20 @@ def test_targeted_keys_of_the_gpu_cases_stay_under_the_untargeted_cap(kind, log2
     for name, (_, miss), words_per_limb in checks:
         assert miss.shape == (p.n_limbs,) and all(int(m) * 100 <= words_per_limb for m in miss), (name, [int(m) for m in miss], words_per_limb)
         print(f"{kind} N={n} {name}: untargeted per limb {[int(m) for m in miss]} of {words_per_limb}")
+
+
+SUM_CAP_CONTEXTS = [(k, ln) for ln in (8, 12) for k in class_edges.CLASSES + ("mixed",)] + [("bench", 12)]
+
+
+@pytest.mark.parametrize("kind,log2n", SUM_CAP_CONTEXTS, ids=[f"{k}_n{1 << ln}" for k, ln in SUM_CAP_CONTEXTS])
+def test_rotate_sum_keys_stay_under_the_untargeted_cap(kind, log2n):
+    """rotate_sum_inputs with the elements, tokens and seed of tests/test_gpu_remainder_edges.py, at N = 256 and 4096 and for every kind: at most 1 % of the
+    key's words untargeted, limb by limb"""
+    p = edge_params(kind, log2n)
+    o = Oracle.from_params(p)
+    data = Oracle(log2n, p.moduli[:-1], p.psi[:-1])
+    n = 1 << log2n
+    ((cts, keys), miss), words_per_limb = re_.rotate_sum_inputs(o, data, re_.rotation_elements(n), 2, 730, per_limb=True), 3 * (p.n_limbs - 1) * 2 * n
+    assert keys.size == words_per_limb * p.n_limbs
+    assert miss.shape == (p.n_limbs,) and all(int(m) * 100 <= words_per_limb for m in miss), ([int(m) for m in miss], words_per_limb)
+    print(f"{kind} N={n} rotate_sum: untargeted per limb {[int(m) for m in miss]} of {words_per_limb}")

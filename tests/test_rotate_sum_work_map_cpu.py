@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from galois_elements import edge_elements, src_pos
+from galois_elements import all_elements, edge_elements, src_pos
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = C.POINTER(C.c_int64)
@@ -42,10 +42,13 @@ def test_layout(wm, log2n, L, items):
 
 @pytest.mark.parametrize("log2n", [8, 10, 13, 16])
 def test_source_of_an_output_pair(wm, log2n):
-    """output pair m gathers source pair src, swapped iff word 2 m comes from an odd position: every pair at N = 256, 1024, three output segments above"""
+    """output pair m gathers source pair src, swapped iff word 2 m comes from an odd position: every pair under EVERY element of the group at N = 256, 1024;
+    the edge elements on three output segments above"""
     half, nseg = 1 << (log2n - 1), max(1, (1 << (log2n - 1)) // 256)
     rows = np.zeros((256, 4), np.int64)
-    for g in edge_elements(log2n):
+    elts = all_elements(log2n) if log2n <= 10 else edge_elements(log2n)
+    assert set(edge_elements(log2n)) <= set(elts)
+    for g in elts:
         for oseg in (range(nseg) if log2n <= 10 else (0, nseg // 3, nseg - 1)):
             wm.wm_qp_sum_source(log2n, g, oseg, rows.ctypes.data_as(I64))
             for lane, (out, src, swap, ok) in enumerate(rows.tolist()):

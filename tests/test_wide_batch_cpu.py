@@ -191,6 +191,23 @@ def test_every_gpu_case_is_within_its_limits_and_its_cap():
     assert {c.tier for c in cases} == {"A", "B"}
 
 
+def test_the_slot_sum_case_crosses_the_lines_it_names():
+    """rotate_sum_hoisted-fold at the real lines: d_digits and d_sum_qp end past B32, the three buffers of 2 Ld N words per item past B31 and short of B32 -
+    and with those three asked past B32 as well the plan refuses the case, at this limb count and at two limbs"""
+    import test_gpu_wide_batch as g
+    c = next(c for c in _gpu_cases() if c.id == "rotate_sum_hoisted-fold")
+    pl = c.plan()
+    b31, b32 = wb.REAL.words["B31"], wb.REAL.words["B32"]
+    assert pl.batch == b32 // pl.items["sum_qp"] + 2 and pl.batch % 4 == 2            # (the last tile has two live rows)
+    assert set(pl.items) == {"digits", "sum_qp"} and all(pl.batch * w >= b32 + 2 * w for w in pl.items.values())
+    assert set(pl.low_items) == {"in2", "in_ntt", "out2"} and all(b31 + 2 * w <= pl.batch * w < b32 for w in pl.low_items.values())
+    assert pl.peak <= wb.CAP["A"]
+    for L in (4, 2):
+        s = g.rotate_sum_shape(L, 4096)
+        with pytest.raises(AssertionError, match="exceeds the cap"):
+            wb.plan({**s["items"], **s["low_items"]}, "A", period=g.P, writable=s["writable"], extra_bytes=s["extra"], limits=s["limits"])
+
+
 def test_the_peaks_of_the_tier_b_cases_are_pinned():
     """a tier B case skips only when mem_get_info reports less than its peak + 8 GiB free: these are the peaks, in bytes"""
     import test_gpu_wide_batch as g
