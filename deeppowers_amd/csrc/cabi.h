@@ -6,6 +6,7 @@
 //   cabi_keyswitch.hip  key switching (RNS-digit and hybrid keys), rescales, host twins of the fused rescales  (kernels_keyswitch.h)
 //   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations, the rotate-and-add ladder (kernels_rotate.h, rotate_add.h)
 //   cabi_rotate_sum.hip hoisted slot sums: R rotations of an item summed under one digit lift          (kernels_rotate_sum.h)
+//   cabi_rotate_matvec.hip  the baby steps of a packed layer times their diagonals, one pass       (rotate_matvec.h)
 //   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)
 //   cabi_bx.hip         base extension, scale-and-round                                                (base_ext.h; kernels in k_bx_*.hip)
 //   cabi_comm.hip       the RCCL communicator

@@ -446,6 +446,26 @@ void HybridKeySwitcher::rotate_hoisted_qp(const Ciphertext& in2, size_t in_first
     out_qp.set_ntt(true);
 }
 
+void HybridKeySwitcher::rotate_matvec_hoisted_qp(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& elts, const Plaintext& W, size_t rows,
+                                                 PolyBuffer& out_qp, size_t out_first, Stream* s) const {
+    const size_t k = elts.size();
+    if (n_items == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), Ld = L - 1, n = pe.n();
+    if (k == 0 || k > 64 || rows == 0 || in2.is_ntt() || in2.size() != 2 || out_qp.size() != 2 || in_first + n_items > in2.batch() ||
+        out_first + rows * n_items > out_qp.batch() || out_qp.words() != out_qp.batch() * 2 * L * n || !W.is_ntt() || W.words() != rows * (k + 1) * L * n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT,
+                        "HybridKeySwitcher::rotate_matvec_hoisted_qp: 1 .. 64 elements, n_items coefficient-domain inputs, rows * (1 + elements) NTT-domain polynomials "
+                        "of W and rows * n_items items out, both on the extended context");
+    const PolyBuffer* keys = impl_->packed_keys(elts, s);
+    impl_->ensure_digits(n_items * Ld);
+    grow_scratch(impl_->scratch_in_ntt, n_items, [&](size_t b) { return new Ciphertext(*impl_->data_ctx, 2, b, true); });
+    check(dpfhe_rotate_matvec_hoisted_qp(handle_of(*impl_->ext), out_qp.data() + out_first * 2 * L * n, W.data(), in2.data() + in_first * 2 * Ld * n, n_items, elts.data(),
+                                         keys->data(), k, rows, impl_->scratch_in_ntt->data(), impl_->scratch_digits->data(), s),
+          "dpfhe_rotate_matvec_hoisted_qp");
+    out_qp.set_ntt(true);
+}
+
 void HybridKeySwitcher::switch_key_qp(const Ciphertext& in2, size_t in_first, const std::vector<uint32_t>& elts, size_t group, PolyBuffer& out_qp,
                                       size_t out_first, Stream* s) const {
     const size_t k = elts.size(), batch = k * group;

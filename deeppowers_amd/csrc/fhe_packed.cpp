@@ -33,6 +33,7 @@ struct PackedCore {
     size_t passes = 0;   // output ciphertexts
     bool replicate = false;   // one block: every window computes it (the output is again a periodic vector)
     size_t n1 = 0, n2 = 0;
+    bool fused = false;   // the baby steps and their diagonal products in one call (dpfhe_rotate_matvec_hoisted_qp): babies_qp is never allocated
     std::unique_ptr<Plaintext> diag;   // [passes][n2][n1] pre-rotated diagonals, NTT domain
     std::vector<uint32_t> baby_elts, giant_elts, fold_elts;
     // per-layer scratch, reused by every apply() (one caller at a time).  Terms over Q P live on the key switcher's extended context.
@@ -80,6 +81,8 @@ struct PackedCore {
     }
     // after the diagonals: the inner sums' elements
     void finish_plan() {
+        if (fused && (n1 < 2 || n1 > 65))
+            throw Exception(ErrorCode::INVALID_ARGUMENT, "packed layer: the fused baby steps take 1 .. 64 rotations in one launch (baby_steps() in [2, 65])");
         for (size_t pass = 0; pass < passes; ++pass) {
             inner_elts.push_back(1u);
             inner_elts.insert(inner_elts.end(), giant_elts.begin(), giant_elts.end());
@@ -89,7 +92,7 @@ struct PackedCore {
     void ensure_tokens(size_t T) {
         if (T <= tokens) return;
         const Context& ext = ks->extended_context();
-        babies_qp.reset(new PolyBuffer(ext, n1 * T, 2, true));                      // [n1][T]: P rot_j(x_t) + key-switching terms, NTT domain
+        if (!fused) babies_qp.reset(new PolyBuffer(ext, n1 * T, 2, true));                      // [n1][T]: P rot_j(x_t) + key-switching terms, NTT domain
         inner_qp.reset(new PolyBuffer(ext, passes * n2 * T, 2, true));              // [passes * n2][T]
         rot.reset(new Ciphertext(*ctx, 2, passes * n2 * T));                        // the inner sums, rotated by their giant step, divided by P
         if (n2 > 1) {
@@ -129,9 +132,11 @@ struct PackedCore {
         // Layout of every intermediate: [rotation or diagonal index][token][component] - the token index sits where the plaintext
         // matvec sees "more components", so keys and diagonals are read once for all tokens.
         // baby steps: P rot_j(x_t) + key-switching term, j < n1, all tokens, ONE hoisted pass; they stay in the NTT domain over Q P
-        ks->rotate_hoisted_qp(x, 0, T, baby_elts, *babies_qp, 0, s);
+        // (fused: both stages in one pass - the same words, no Q P block per baby step written)
+        if (fused) ks->rotate_matvec_hoisted_qp(x, 0, T, baby_elts, *diag, passes * n2, *inner_qp, 0, s);
+        else ks->rotate_hoisted_qp(x, 0, T, baby_elts, *babies_qp, 0, s);
         // inner sums of all giant steps of all output ciphertexts of all tokens: ONE matrix-vector product over the pre-rotated diagonals
-        check(dpfhe_matvec_plain_multi(he, inner_qp->data(), diag->data(), babies_qp->data(), passes * n2, n1, T, s), "dpfhe_matvec_plain_multi");
+        if (!fused) check(dpfhe_matvec_plain_multi(he, inner_qp->data(), diag->data(), babies_qp->data(), passes * n2, n1, T, s), "dpfhe_matvec_plain_multi");
         // back to the coefficient domain, the giant step's automorphism applied by the transform's loads; then the ONE division by P
         // the baby steps and the plaintext products share
         check(dpfhe_ntt_inv_galois(he, inner_qp->data(), inner_qp->data(), T * 2, inner_elts.data(), passes * n2, s), "dpfhe_ntt_inv_galois");
@@ -179,7 +184,7 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
     : PackedLinear(ctx, enc, ks, W, out_dim, in_dim, tokens_per_ciphertext, nullptr) {}
 
 PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim, size_t tokens_per_ciphertext,
-                           const uint64_t* bias)
+                           const uint64_t* bias, bool fuse_baby_steps)
     : impl_(new Impl) {
     const FheParams& p = ctx.params();
     const size_t N = p.n(), L = p.n_limbs();
@@ -188,6 +193,7 @@ PackedLinear::PackedLinear(const Context& ctx, const BatchEncoder& enc, HybridKe
     if (enc.slot_count() != N) throw Exception(ErrorCode::INVALID_ARGUMENT, "PackedLinear: encoder and context disagree on N");
     Impl& I = *impl_;
     I.enc = &enc;
+    I.fused = fuse_baby_steps;
     const uint64_t t = enc.plain_modulus();
     // (the weights are looked at only after the keys exist, as before: a refused matrix leaves the key switcher with the layer's elements)
     I.plan("PackedLinear", ctx, ks, out_dim, in_dim, 2, tokens_per_ciphertext, [&](int s) { return enc.galois_element(s); });
@@ -333,7 +339,7 @@ public:
 };
 
 ApproxPackedLinear::ApproxPackedLinear(const Context& ctx, const Context& next_ctx, const ComplexEncoder& enc, HybridKeySwitcher& ks, const double* W, size_t out_dim,
-                                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext, const double* bias)
+                                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext, const double* bias, bool fuse_baby_steps)
     : impl_(new Impl) {
     const FheParams& p = ctx.params();
     const size_t N = p.n(), L = p.n_limbs(), row = N / 2;
@@ -346,6 +352,7 @@ ApproxPackedLinear::ApproxPackedLinear(const Context& ctx, const Context& next_c
     if (next_ctx.params().log2_n != pn.log2_n || next_ctx.params().moduli != pn.moduli || next_ctx.params().psi != pn.psi || next_ctx.device_id() != ctx.device_id())
         throw Exception(ErrorCode::INVALID_ARGUMENT, "ApproxPackedLinear: next_ctx must be a context on data_ctx.params().drop_last_limb(), on the same device");
     Impl& I = *impl_;
+    I.fused = fuse_baby_steps;
     I.next = &next_ctx; I.enc = &enc; I.w_scale = weight_scale; I.x_scale = input_scale; I.q_last = (double)p.moduli.back();
     const double out_scale = input_scale * weight_scale / I.q_last, clamp = std::ldexp(1.0, 62);
     for (size_t R = 0; R < out_dim; ++R) {

@@ -233,6 +233,34 @@ struct QpSumMap {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The baby steps WEIGHTED by their diagonals (rotate_matvec.h hoisted_qp_matvec_kernel): output-stationary like the sum above.  A workgroup is 256 threads x one
+// 16-byte pair = one OUTPUT segment of one limb of ONE item, both components, for a tile of up to kRotMatvecRows rows of W: each rotated key product is formed
+// once per workgroup and multiplied into the tile's row accumulators.  outer = combo = (limb, output segment), inner = (row tile, item), item fastest: all
+// workgroups of a combo share ONE XCD, consecutive in its order - the items of a row tile read the same W segments, and every workgroup of the combo the same
+// key segments, from L2.  The source side is QpSumMap::source.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRotMatvecRows = 6;   // (8 rows: 256 VGPRs + 40 AGPRs at one wave per SIMD; 6: 238 at two - rotate_matvec.h)
+constexpr size_t kRotMatvecMaxRows = 65536;   // rows of W one call takes
+struct RotMatvecWork {
+    int limb;
+    unsigned oseg, item, row_tile;
+    bool live;
+};
+struct RotMatvecPlan { unsigned row_tiles; size_t grid; };
+struct RotMatvecMap {
+    static DPF_HD QpGeo geo(int log2n) { return QpMap::geo(log2n, 1); }
+    static DPF_HD RotMatvecPlan plan(int log2n, size_t n_limbs, size_t n_items, size_t rows) {
+        const size_t row_tiles = (rows + kRotMatvecRows - 1) / kRotMatvecRows;
+        return RotMatvecPlan{(unsigned)row_tiles, xcd_deal::grid(n_limbs * geo(log2n).nseg, row_tiles * n_items)};
+    }
+    static DPF_HD RotMatvecWork decode(unsigned id, const QpGeo& g, unsigned n_limbs, unsigned n_items, unsigned row_tiles) {
+        const XcdSlot s = xcd_deal::decode(id, row_tiles * n_items);
+        if (s.outer >= n_limbs * g.nseg) return RotMatvecWork{0, 0, 0, 0, false};
+        return RotMatvecWork{(int)(s.outer % n_limbs), s.outer / n_limbs, s.inner % n_items, s.inner / n_items, true};
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // The streaming kernels take their work in 512-word chunks of a residue polynomial: 256 threads x one 16-byte pair (the `chunks` argument of each;
 // a thread owns words chunk * 512 + 2 tid and the next).  Rings below N = 512 have one partial chunk, whose upper threads idle.
 // id = (poly * n_limbs + limb) * chunks + chunk.

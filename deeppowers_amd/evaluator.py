@@ -606,6 +606,29 @@ class Evaluator:
                                                        digits.data_ptr(), sum_qp.data_ptr(), self._sp(stream)), "dpfhe_rotate_sum_hoisted")
         return Ciphertext(out, False)
 
+    def rotate_matvec_hoisted_qp(self, W: torch.Tensor, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> torch.Tensor:
+        """The first two stages of a packed layer in one call (dpfhe_rotate_matvec_hoisted_qp): [T][2][L-1][N] coefficient-domain inputs on the extended
+        context and W [rows][1 + k][L][N] (NTT, column 0 for the un-rotated input) -> [rows][T][2][L][N], NTT domain over Q P: the words of
+        matvec_plain_multi(W, rotate_hoisted_qp(ct, elts, keys), T), with no Q P block per rotation in between.  k = len(elts) in [1, 64]."""
+        p = self.ctx.params
+        L, Ld, n = p.n_limbs, p.n_limbs - 1, p.n
+        d = ct.data
+        k = len(galois_elts)
+        if ct.is_ntt or ct.size != 2 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "rotate_matvec_hoisted_qp: coefficient-domain [T][2][L-1][N] ciphertexts on the extended context")
+        if k == 0 or tuple(keys.shape) != (k, Ld, 2, L, n) or keys.dtype != torch.int64 or not keys.is_contiguous():
+            raise _cabi.DpfheError(2000, "keys must be [k][L-1][2][L][N], k >= 1")
+        if W.dim() != 4 or W.shape[0] == 0 or tuple(W.shape[1:]) != (k + 1, L, n) or W.dtype != torch.int64 or not W.is_contiguous():
+            raise _cabi.DpfheError(2000, "W must be [rows][1 + k][L][N], rows >= 1")
+        T, rows = d.shape[0], W.shape[0]
+        out = self._empty((rows, T, 2, L, n), stream)
+        in_ntt = self._empty((T, 2, Ld, n), stream)
+        digits = self._empty((T, Ld, L, n), stream)
+        elts = (C.c_uint32 * k)(*[int(g) for g in galois_elts])
+        _cabi.check(self._lib.dpfhe_rotate_matvec_hoisted_qp(self.ctx.handle, out.data_ptr(), W.data_ptr(), d.data_ptr(), T, elts, keys.data_ptr(), k, rows,
+                                                             in_ntt.data_ptr(), digits.data_ptr(), self._sp(stream)), "dpfhe_rotate_matvec_hoisted_qp")
+        return out
+
     def device_copy(self, dst: torch.Tensor, src: torch.Tensor, stream=None) -> torch.Tensor:
         """Plain device-to-device copy through the library's streaming access shape (dpfhe_copy): the practical HBM ceiling."""
         if dst.numel() != src.numel() or dst.dtype != torch.int64 or src.dtype != torch.int64 or not dst.is_contiguous() or not src.is_contiguous():

@@ -3,7 +3,9 @@
 // Z_65537 by the diagonal method with baby-step / giant-step rotations (deeppowers::fhe::PackedLinear).
 // The layer shapes are the reference's matmul sites (/root/reference/src/core/execution/models/gpt_model.cpp:793 QKV 768 -> 2304,
 // :848 FFN 768 -> 3072 -> 768, :883 logits 768 -> 50257; hidden_size 768, vocab 50257 at execution/model.hpp:47-50).
-//   usage: encrypted_gpt2_linear [layer = all | square | qkv | ffn_up | ffn_down | lm_head | <out>x<in>] [reps = 2] [json | text] [tokens = 1] [log2_n = 13 | 14 | 15] [tokens_per_ciphertext = 1 | 2]
+//   usage: encrypted_gpt2_linear [layer = all | square | qkv | ffn_up | ffn_down | lm_head | <out>x<in>] [reps = 2] [json | text] [tokens = 1] [log2_n = 13 | 14 | 15] [tokens_per_ciphertext = 1 | 2] [fused]
+// fused: a SECOND layer is built with PackedLinear's fuse_baby_steps on (the baby steps and their diagonal products in one call), applied to the same
+// ciphertexts and timed the same way; its output words must equal the first layer's (json: fused_words_equal, fused_ms_per_token).
 // tokens_per_ciphertext = 2 (round 6): the two slot rows of a ciphertext carry two tokens (PackedLinear's two-token packing) - the same kernels on half the ciphertexts.
 // WHAT THIS IS: single dense layers (matrix x encrypted vector over Z_65537), nothing else of the model.  SECURITY: at the default N = 8192 the 360-bit modulus
 // under key switching is beyond the 218 bits of 128-bit security at that ring (Homomorphic Encryption Standard): a performance shape (BASELINE configs[4]).
@@ -36,6 +38,7 @@ int main(int argc, char** argv) {
     const size_t tpc = argc > 6 ? (size_t)std::atol(argv[6]) : 1;
     if ((tpc != 1 && tpc != 2) || T % tpc) { std::fprintf(stderr, "tokens_per_ciphertext must be 1 or 2 and divide the token count\n"); return 1; }
     const size_t C = T / tpc;   // ciphertexts per application
+    const bool fused = argc > 7 && !std::strcmp(argv[7], "fused");
     std::vector<Shape> shapes;
     const Shape known[] = {{"square", 768, 768}, {"qkv", 2304, 768}, {"ffn_up", 3072, 768}, {"ffn_down", 768, 3072}, {"lm_head", 50257, 768}};
     for (const Shape& k : known)
@@ -92,6 +95,23 @@ int main(int argc, char** argv) {
             const double apply_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3 / reps / (double)T;
             dec.decrypt_exact(cy, t, dm.data());
             size_t bad = 0;
+            double fused_ms = 0;
+            bool fused_equal = true;
+            if (fused) {   // the same keys (one key switcher), the same input: every output word must be the same
+                PackedLinear flayer(ctx, be, hks, W.data(), sh.out, sh.in, tpc, nullptr, true);
+                Ciphertext fy(ctx, 2, outs * C);
+                flayer.apply(cx, fy);
+                ctx.synchronize();
+                t0 = std::chrono::steady_clock::now();
+                for (int i = 0; i < reps; ++i) flayer.apply(cx, fy);
+                ctx.synchronize();
+                fused_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3 / reps / (double)T;
+                std::vector<uint64_t> a(cy.words()), b(fy.words());
+                cy.copy_to_host(a.data());
+                fy.copy_to_host(b.data());
+                fused_equal = a == b;
+                if (!fused_equal) bad += 1;
+            }
             for (size_t c = 0; c < C; ++c) {
                 for (size_t o = 0; o < outs; ++o) be.decode(dm.data() + (o * C + c) * n, got.data() + o * n);
                 if (tpc == 1) {
@@ -104,9 +124,9 @@ int main(int argc, char** argv) {
             }
             if (json)
                 std::printf("{\"layer\": \"%s\", \"out_dim\": %zu, \"in_dim\": %zu, \"log2_n\": %d, \"data_limbs\": %zu, \"plain_modulus\": %llu, \"baby_steps\": %zu, "
-                            "\"giant_steps\": %zu, \"output_ciphertexts\": %zu, \"key_switches\": %zu, \"tokens_per_apply\": %zu, \"tokens_per_ciphertext\": %zu, \"setup_s\": %.2f, \"encode_s\": %.3f, \"ms_per_token\": %.3f, \"correct\": %s}\n",
+                            "\"giant_steps\": %zu, \"output_ciphertexts\": %zu, \"key_switches\": %zu, \"tokens_per_apply\": %zu, \"tokens_per_ciphertext\": %zu, \"setup_s\": %.2f, \"encode_s\": %.3f, \"ms_per_token\": %.3f, \"fused_ms_per_token\": %.3f, \"fused_words_equal\": %s, \"correct\": %s}\n",
                             sh.name, sh.out, sh.in, log2n, p.n_limbs(), (unsigned long long)t, layer.baby_steps(), layer.giant_steps(), outs, layer.key_switches_per_apply(), T, tpc,
-                            setup_s, layer.encode_seconds(), apply_ms, bad ? "false" : "true");
+                            setup_s, layer.encode_seconds(), apply_ms, fused_ms, !fused ? "null" : fused_equal ? "true" : "false", bad ? "false" : "true");
             else
                 std::printf("%-8s %5zu <- %4zu: period %zu, %zu baby x %zu giant steps, %zu output ciphertext(s), %zu key switches, %zu token(s) per apply; setup %.2f s, apply %.3f ms per token: %s\n",
                             sh.name, sh.out, sh.in, layer.input_period(), layer.baby_steps(), layer.giant_steps(), outs, layer.key_switches_per_apply(), T, setup_s, apply_ms,

@@ -659,6 +659,11 @@ public:
     // `out_qp`: 2-component buffer on extended_context().
     void rotate_hoisted_qp(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& galois_elts, PolyBuffer& out_qp,
                            size_t out_first, Stream* stream = nullptr) const;
+    // rotate_hoisted_qp and the plaintext matrix-vector product over its blocks in ONE pass (dpfhe_rotate_matvec_hoisted_qp): W holds rows * (1 + elts.size())
+    // polynomials on extended_context() in the NTT domain, row-major, column 0 for the un-rotated input; out_qp item out_first + i * n_items + t =
+    // W[i][0] (.) P ct_t + sum_r W[i][1 + r] (.) (block r + 1 of rotate_hoisted_qp for item t) - the same words, no block per rotation written.  1 .. 64 elements.
+    void rotate_matvec_hoisted_qp(const Ciphertext& in2, size_t in_first, size_t n_items, const std::vector<uint32_t>& galois_elts, const Plaintext& W, size_t rows,
+                                  PolyBuffer& out_qp, size_t out_first, Stream* stream = nullptr) const;
     // elts.size() * group items (in2 items in_first ...), item i with the key of elts[i / group]: out_qp item out_first + i = the key
     // inner product of item i's c1 alone, NTT domain over Q P (dpfhe_switch_key_qp); the caller sums such terms, transforms back
     // once and finishes with dpfhe_rescale_bsgs.  The items must already carry the automorphism (coefficient domain).
@@ -817,8 +822,11 @@ public:
     PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t d);
     // y = W x + bias: `bias` holds out_dim values < t (null: exactly the constructor above).  Every slot that holds output row R gets bias[R] (0 where no
     // row is), encoded once per output ciphertext and kept on the device; apply() ends with one exact plaintext addition on its stream.
+    // fuse_baby_steps (default off): the first two stages of apply() - the hoisted baby steps and the product with the diagonals - become ONE call,
+    // HybridKeySwitcher::rotate_matvec_hoisted_qp: the same words, no Q P block per baby step written or re-read.  It needs baby_steps() in [2, 65]
+    // (INVALID_ARGUMENT otherwise).  Slower than the two calls at the shapes measured so far (README.md), hence opt-in.
     PackedLinear(const Context& data_ctx, const BatchEncoder& enc, HybridKeySwitcher& ks, const uint64_t* W, size_t out_dim, size_t in_dim,
-                 size_t tokens_per_ciphertext, const uint64_t* bias);
+                 size_t tokens_per_ciphertext, const uint64_t* bias, bool fuse_baby_steps = false);
     bool has_bias() const;
     double encode_seconds() const;   // wall time the constructor spent building and encoding the diagonals and the bias (the rest of it generates keys)
     ~PackedLinear();
@@ -894,7 +902,8 @@ public:
     // bound to any context of the ring degree.  tokens_per_ciphertext = 2: token A in the real parts, token B in the imaginary parts of the slots - the
     // diagonals are real, so W (x_A + i x_B) = W x_A + i W x_B with the same kernels at half the cost per token; the bias slots are b (1 + i).
     ApproxPackedLinear(const Context& data_ctx, const Context& next_ctx, const ComplexEncoder& enc, HybridKeySwitcher& ks, const double* W, size_t out_dim,
-                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext = 1, const double* bias = nullptr);
+                       size_t in_dim, double weight_scale, double input_scale, size_t tokens_per_ciphertext = 1, const double* bias = nullptr,
+                       bool fuse_baby_steps = false);   // (fuse_baby_steps: as PackedLinear's)
     ~ApproxPackedLinear();
     ApproxPackedLinear(const ApproxPackedLinear&) = delete;
     ApproxPackedLinear& operator=(const ApproxPackedLinear&) = delete;

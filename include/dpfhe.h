@@ -425,6 +425,21 @@ int dpfhe_rotate_sum_hoisted(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_
  *   dpfhe_switch_key_qp). */
 int dpfhe_rotate_hoisted_qp(dpfhe_ctx* ctx_ext, uint64_t* d_out_qp, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts,
                             const uint64_t* d_keys, uint64_t* d_in_ntt, uint64_t* d_digits, size_t batch, void* stream);
+/* dpfhe_rotate_matvec_hoisted_qp: the first TWO stages of a packed layer in one call - the baby steps multiplied by their pre-rotated diagonals and summed:
+ *   d_y_qp [rows][n_items][2][L][N], NTT domain, canonical:  y[i][t] = d_W[i][0] (.) (P c0_t, P c1_t) + sum_{r < batch} d_W[i][1 + r] (.) block 1 + r of item t
+ * - word for word  dpfhe_rotate_hoisted_qp(ctx_ext, blocks, d_in2, n_items, galois_elts, d_keys, d_in_ntt, d_digits, batch, stream)  followed by
+ * dpfhe_matvec_plain_multi(ctx_ext, d_y_qp, d_W, blocks, rows, 1 + batch, n_items, stream), but the blocks buffer is never allocated, written or read.
+ * d_W: [rows][1 + batch][L][N] plaintext polynomials over Q P, NTT domain (column 0 multiplies block 0); d_in2, galois_elts (a HOST array), d_keys, d_in_ntt
+ * and d_digits exactly as for dpfhe_rotate_hoisted_qp, the scratch sizes exactly that entry's.  batch in [1, 64] and rows in [1, 65536]: one launch, the
+ * row accumulators are never re-read.  One workgroup per output segment, limb, item and tile of 6 rows keeps the tile's accumulators in registers; a rotated
+ * key product is formed once per tile of rows, so rows above 6 recompute it rows / 6 times inside the launch (csrc/rotate_matvec.h gives the arithmetic).
+ * No written buffer (d_y_qp, d_in_ntt, d_digits) overlaps any other buffer.  Enqueues only, every log2_n (8 ... 16) and limb class; never allocates at
+ * log2_n <= 13, above that the composed transforms lease arena scratch exactly as in dpfhe_rotate_hoisted_qp.  DPFHE_INVALID_STATE on a context without a
+ * special prime; DPFHE_INVALID_ARGUMENT, before the device is touched, on batch or rows outside their range, an even element or one >= 2N, a null or
+ * misaligned buffer, overlapping buffers, or a grid too large for one launch.  n_items == 0 returns success. */
+int dpfhe_rotate_matvec_hoisted_qp(dpfhe_ctx* ctx_ext, uint64_t* d_y_qp, const uint64_t* d_W, const uint64_t* d_in2, size_t n_items,
+                                   const uint32_t* galois_elts, const uint64_t* d_keys, size_t batch, size_t rows, uint64_t* d_in_ntt, uint64_t* d_digits,
+                                   void* stream);
 int dpfhe_ntt_inv_galois(dpfhe_ctx* ctx, uint64_t* d_out, const uint64_t* d_in, size_t rns_polys_per_elt, const uint32_t* galois_elts, size_t n_elts,
                          void* stream);
 int dpfhe_switch_key_qp(dpfhe_ctx* ctx_ext, uint64_t* d_out_qp, const uint64_t* d_in2, const uint64_t* d_keys, size_t n_keys, size_t group, void* stream);

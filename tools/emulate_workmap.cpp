@@ -101,6 +101,22 @@ void wm_qp_sum_source(int log2n, unsigned g, unsigned oseg, i64* out) {
     }
 }
 
+// the baby steps weighted by their diagonals: rows (limb, output segment, item, row tile, live); the source side is wm_qp_sum_source
+int wm_rot_matvec_rows() { return kRotMatvecRows; }
+u64 wm_rot_matvec_grid(int log2n, size_t n_limbs, size_t n_items, size_t rows, unsigned* row_tiles) {
+    const RotMatvecPlan p = RotMatvecMap::plan(log2n, n_limbs, n_items, rows);
+    *row_tiles = p.row_tiles;
+    return p.grid;
+}
+void wm_rot_matvec_decode(unsigned n_ids, int log2n, unsigned n_limbs, unsigned n_items, unsigned row_tiles, i64* out) {
+    const QpGeo geo = RotMatvecMap::geo(log2n);
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const RotMatvecWork w = RotMatvecMap::decode(id, geo, n_limbs, n_items, row_tiles);
+        i64* o = out + 5 * (size_t)id;
+        o[0] = w.limb; o[1] = w.oseg; o[2] = w.item; o[3] = w.row_tile; o[4] = w.live;
+    }
+}
+
 // streaming kernels: rows (chunk, limb, polynomial)
 int wm_chunks_of(size_t n) { return chunks_of(n); }
 void wm_chunk_decode(unsigned n_ids, int chunks, int n_limbs, i64* out) {
