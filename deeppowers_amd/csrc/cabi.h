@@ -7,6 +7,7 @@
 //   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations, the rotate-and-add ladder (kernels_rotate.h, rotate_add.h)
 //   cabi_rotate_sum.hip hoisted slot sums: R rotations of an item summed under one digit lift          (kernels_rotate_sum.h)
 //   cabi_rotate_matvec.hip  the baby steps of a packed layer times their diagonals, one pass       (rotate_matvec.h)
+//   cabi_keyswitch_grouped.hip  hybrid key switching with grouped digits and several special primes  (keyswitch_grouped.h)
 //   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)
 //   cabi_bx.hip         base extension, scale-and-round                                                (base_ext.h; kernels in k_bx_*.hip)
 //   cabi_comm.hip       the RCCL communicator
@@ -38,6 +39,7 @@
 #include "workmap.h"
 
 using namespace dpfhe;   // (an internal header: every unit that includes it is the library's own)
+namespace dpfhe { struct BaseExtArgs; }   // base_ext.h
 
 int fail(int code, const char* what, const char* detail);   // sets dpfhe_last_error() to "what: detail" and returns code (cabi_ctx.hip)
 #define HIP_TRY(expr)                                                                  \
@@ -131,6 +133,10 @@ struct dpfhe_ctx {
     std::atomic<int> ct_mul_variant{0};
     dpfhe_tune_info tune{};           // guarded by tune_mutex (the launch path reads ct_mul_variant only)
     mutable std::mutex tune_mutex;
+    // dpfhe_switch_key_grouped: per number of special primes (1 .. 10) the device table of its digit groups and of its division by P (keyswitch_grouped.h), made at
+    // the first call with that number (a call with batch == 0 is the warm-up) and kept for the context's life (cabi_keyswitch_grouped.hip grouped_table)
+    std::atomic<void*> grouped_tabs[11] = {};
+    std::mutex grouped_mutex;
     std::atomic<size_t> scratch_limit_words{(size_t)1024 << 17};   // slice size of the composed large-ring operations (dpfhe_ctx_set_scratch_limit; read on the compute path)
 };
 
@@ -300,6 +306,12 @@ inline int ntt_launch(dpfhe_ctx* c, bool inverse, uint64_t* out, const uint64_t*
 }
 // dyadic_kernel<op> over `npolys` residue polynomials (DyOp; b_period as in kernels_poly.h); -1: no such op                                  // cabi_poly.hip
 int launch_dyadic(const dpfhe_ctx* c, int op, u64* out, const u64* a, const u64* b, size_t npolys, hipStream_t s, int b_period);
+// key_inner_product_kernel over `grid` (item, limb, chunk) workgroups: acc [items][2][L][N] = sum_{j < n_digits} digits [items][n_digits][L][N] (.) key_j, the key
+// of item i at keys + ((item0 + i) / key_group) * key_stride (cabi_keyswitch.hip; NTT domain, canonical)
+void launch_key_inner_product(const dpfhe_ctx* c, size_t grid, hipStream_t s, u64* acc, const u64* digits, const u64* keys, int n_digits, int chunks, size_t key_stride = 0,
+                              unsigned key_group = 1, unsigned item0 = 0);
+// the argument block of dpfhe_base_extend (mode 0) / dpfhe_scale_round (mode 1) for one pair of limb ranges, ranges validated by the caller (cabi_bx.hip)
+int fill_base_ext_args(const dpfhe_ctx* c, int mode, uint32_t src0, uint32_t ns, uint32_t dst0, uint32_t nd, uint64_t multiplier, BaseExtArgs& a, const char* what);
 // what the rotations borrow from key switching (cabi_keyswitch.hip, which describes each at its definition): the division by P, the digit lift, and the
 // hybrid key switch itself with every check of its entries (`what` names the caller in its reports)
 void launch_rescale(const dpfhe_ctx* c, size_t blocks, hipStream_t s, u64* out, const u64* in, const u64* add, int add_comps, int add_mask);

@@ -2,27 +2,12 @@
 #include "base_ext.h"
 #include "cabi.h"
 
-// exact base extension / scale-and-round between limb ranges of one context (kernels_bx.h base_extend_kernel)
-static int base_extend_common(dpfhe_ctx* c, int mode, uint64_t* d_out, size_t out_stride_limbs, const uint64_t* d_in, size_t in_stride_limbs, uint32_t src0, uint32_t ns,
-                              uint32_t dst0, uint32_t nd, uint64_t multiplier, size_t n_polys, void* stream, const char* what) {
-    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
-    if (n_polys == 0) return DPFHE_SUCCESS;
-    const uint32_t L = c->n_limbs;
-    if (ns == 0 || ns > (uint32_t)kBxMaxSrc || nd == 0 || nd > (uint32_t)kBxMaxDst || src0 > L || ns > L - src0 || dst0 > L || nd > L - dst0)   /* no 32-bit wrap-around */
-        return fail(DPFHE_INVALID_ARGUMENT, what, "1..10 source limbs and 1..20 destination limbs inside the context");
-    if (mode == 1 && !(dst0 >= src0 + ns || dst0 + nd <= src0)) return fail(DPFHE_INVALID_ARGUMENT, what, "the dropped limbs and the kept limbs must be disjoint");
-    if (!d_out || !d_in || misaligned(d_out) || misaligned(d_in) || out_stride_limbs < nd || in_stride_limbs < ns) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer, or an item stride shorter than its limbs");
-    const size_t n = (size_t)1 << c->log2n;
-    const int chunks = chunks_of(n);
-    if (n_polys * (size_t)chunks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
-    {   // mode 1: d_in points at the first dropped limb of item 0 inside a [n_polys][L][N] buffer that starts src0 limbs earlier
-        const uint64_t* in_lo = mode == 1 ? d_in - (size_t)src0 * n : d_in;
-        const size_t in_words = mode == 1 ? n_polys * (size_t)L * n : ((n_polys - 1) * in_stride_limbs + ns) * n;
-        if (overlaps(d_out, ((n_polys - 1) * out_stride_limbs + nd) * n, in_lo, in_words)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps the input");
-    }
-    // host constants (a handful of modular inverses; moduli read back from the context's limb constants would need a copy - they are kept on the host)
+// the argument block of one (source range, destination range) of a context: host constants (a handful of modular inverses).  Ranges validated by the caller
+// (dpfhe_switch_key_grouped, cabi_keyswitch_grouped.hip, builds its digit groups' blocks with it as well).
+int fill_base_ext_args(const dpfhe_ctx* c, int mode, uint32_t src0, uint32_t ns, uint32_t dst0, uint32_t nd, uint64_t multiplier, BaseExtArgs& a, const char* what) {
+    // (moduli read back from the context's limb constants would need a copy - they are kept on the host)
     const std::vector<uint64_t>& q = c->moduli;
-    BaseExtArgs a{};
+    a = BaseExtArgs{};
     a.n_src = (int)ns; a.n_dst = (int)nd;
     for (uint32_t i = 0; i < ns; ++i) a.src_limb[i] = (int)(src0 + i);
     for (uint32_t j = 0; j < nd; ++j) a.dst_limb[j] = (int)(dst0 + j);
@@ -51,6 +36,29 @@ static int base_extend_common(dpfhe_ctx* c, int mode, uint64_t* d_out, size_t ou
         }
     }
     for (uint32_t i = 0; i < ns; ++i) a.mul_src[i] = multiplier % q[src0 + i];
+    return DPFHE_SUCCESS;
+}
+
+// exact base extension / scale-and-round between limb ranges of one context (kernels_bx.h base_extend_kernel)
+static int base_extend_common(dpfhe_ctx* c, int mode, uint64_t* d_out, size_t out_stride_limbs, const uint64_t* d_in, size_t in_stride_limbs, uint32_t src0, uint32_t ns,
+                              uint32_t dst0, uint32_t nd, uint64_t multiplier, size_t n_polys, void* stream, const char* what) {
+    if (!c) return fail(DPFHE_INVALID_ARGUMENT, what, "null context");
+    if (n_polys == 0) return DPFHE_SUCCESS;
+    const uint32_t L = c->n_limbs;
+    if (ns == 0 || ns > (uint32_t)kBxMaxSrc || nd == 0 || nd > (uint32_t)kBxMaxDst || src0 > L || ns > L - src0 || dst0 > L || nd > L - dst0)   /* no 32-bit wrap-around */
+        return fail(DPFHE_INVALID_ARGUMENT, what, "1..10 source limbs and 1..20 destination limbs inside the context");
+    if (mode == 1 && !(dst0 >= src0 + ns || dst0 + nd <= src0)) return fail(DPFHE_INVALID_ARGUMENT, what, "the dropped limbs and the kept limbs must be disjoint");
+    if (!d_out || !d_in || misaligned(d_out) || misaligned(d_in) || out_stride_limbs < nd || in_stride_limbs < ns) return fail(DPFHE_INVALID_ARGUMENT, what, "null or misaligned buffer, or an item stride shorter than its limbs");
+    const size_t n = (size_t)1 << c->log2n;
+    const int chunks = chunks_of(n);
+    if (n_polys * (size_t)chunks > kMaxGrid) return fail(DPFHE_INVALID_ARGUMENT, what, "batch too large for one launch");
+    {   // mode 1: d_in points at the first dropped limb of item 0 inside a [n_polys][L][N] buffer that starts src0 limbs earlier
+        const uint64_t* in_lo = mode == 1 ? d_in - (size_t)src0 * n : d_in;
+        const size_t in_words = mode == 1 ? n_polys * (size_t)L * n : ((n_polys - 1) * in_stride_limbs + ns) * n;
+        if (overlaps(d_out, ((n_polys - 1) * out_stride_limbs + nd) * n, in_lo, in_words)) return fail(DPFHE_INVALID_ARGUMENT, what, "output overlaps the input");
+    }
+    BaseExtArgs a{};
+    if (int rc = fill_base_ext_args(c, mode, src0, ns, dst0, nd, multiplier, a, what)) return rc;
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(n_polys * (size_t)chunks);

@@ -252,6 +252,7 @@ extern "C" int dpfhe_ctx_destroy(dpfhe_ctx* c) {
     if (c->class_blob) (void)hipFree(c->class_blob);
     if (c->lazy29_blob) (void)hipFree(c->lazy29_blob);
     if (c->rescale2_blob) (void)hipFree(c->rescale2_blob);
+    for (auto& t : c->grouped_tabs) if (void* p = t.load()) (void)hipFree(p);
     delete c;   // (the scratch pool waits for, frees and strips of its event every arena it still has)
     return DPFHE_SUCCESS;
 }

@@ -16,6 +16,15 @@ static int relin_launch(const dpfhe_ctx* c, int mode, u64* out, const u64* in, c
     return with_policy(c, [&](const auto& tb) { return launch_relin((int)c->log2n, mode, out, in, evk, key_stride, key_group, blocks, tb, s); });
 }
 
+// the key inner product of the composed forms below and of dpfhe_switch_key_grouped (cabi.h): the digit count is the launch's, L, Ld or the number of digit groups
+void launch_key_inner_product(const dpfhe_ctx* c, size_t grid, hipStream_t s, u64* acc, const u64* digits, const u64* keys, int n_digits, int chunks, size_t key_stride,
+                              unsigned key_group, unsigned item0) {
+    with_ctx_arith(c, [&](auto arith) {
+        hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3((unsigned)grid), dim3(256), 0, s, acc, digits, keys, c->lc, n_digits, (int)c->n_limbs,
+                           1 << c->log2n, chunks, key_stride, key_group, item0);
+    });
+}
+
 // ---- ring degrees above 8192: the fused kernels stop there (kernels_keyswitch.h); the same operations composed from the batched transforms
 // and one-pass streaming kernels.  Their scratch comes from per-stream arenas (cabi.h StreamScratch).
 
@@ -34,7 +43,7 @@ static int key_switch_composed_slice(dpfhe_ctx* c, uint64_t* d_out2, const uint6
     if (int rc = check_launch("digit lift kernel launch")) return rc;
     if (int rc = ntt_launch(c, false, ws.p, ws.p, batch * L * L, s)) return rc;
     const unsigned grid = (unsigned)(batch * L * (size_t)chunks);
-    with_ctx_arith(c, [&](auto arith) { hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3(grid), dim3(256), 0, s, d_out2, ws.p, d_evk, c->lc, (int)L, (int)L, (int)n, chunks); });
+    launch_key_inner_product(c, grid, s, d_out2, ws.p, d_evk, (int)L, chunks);
     if (int rc = check_launch("key inner product kernel launch")) return rc;
     if (int rc = ntt_launch(c, true, d_out2, d_out2, batch * 2 * L, s)) return rc;
     hipLaunchKernelGGL(add_back_kernel, dim3(2 * grid), dim3(256), 0, s, d_out2, d_in, in_comps, add_mask, c->lc, (int)L, (int)n, chunks);
@@ -132,9 +141,7 @@ static int key_products_composed(dpfhe_ctx* c, uint64_t* d_out_qp, const uint64_
         if (int rc = ntt_launch(c, false, ws.p, ws.p, m * Ld * L, s)) return rc;
         const unsigned grid = (unsigned)(m * L * (size_t)ch);
         u64* o = d_out_qp + i0 * 2 * L * n;
-        with_ctx_arith(c, [&](auto arith) {
-            hipLaunchKernelGGL((key_inner_product_kernel<decltype(arith)>), dim3(grid), dim3(256), 0, s, o, ws.p, d_keys, c->lc, (int)Ld, (int)L, n, ch, key_stride, key_group, (unsigned)i0);
-        });
+        launch_key_inner_product(c, grid, s, o, ws.p, d_keys, (int)Ld, ch, key_stride, key_group, (unsigned)i0);
         return check_launch("key inner product kernel launch");
     });
 }

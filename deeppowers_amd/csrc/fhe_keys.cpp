@@ -216,6 +216,50 @@ void KeyGenerator::create_relin_keys(RelinKeys& out) { impl_->switch_key(impl_->
 void KeyGenerator::create_relin_keys_seeded(RelinKeys& out, Seed& seed_out) { impl_->switch_key(impl_->sk->ntt_squared(), out, &seed_out); }
 void KeyGenerator::create_galois_keys(GaloisKeys& out) { impl_->galois_key(out, nullptr); }
 void KeyGenerator::create_galois_keys_seeded(GaloisKeys& out, Seed& seed_out) { impl_->galois_key(out, &seed_out); }
+// Grouped hybrid keys: the RLWE samples of make_switch_key, the target scaled by P and placed on the limbs of digit group d
+void KeyGenerator::make_grouped_key(const uint64_t* d_target_ntt, uint32_t n_special, PolyBuffer& out) {
+    const Context& ctx = *impl_->ctx;
+    const FheParams& p = ctx.params();
+    const size_t n = p.n(), L = p.n_limbs(), poly = L * n;
+    if (n_special == 0 || n_special >= L) throw Exception(ErrorCode::INVALID_ARGUMENT, "make_grouped_key: n_special must be in [1, L)");
+    const size_t Ld = L - n_special, groups = (Ld + n_special - 1) / n_special;
+    if (!d_target_ntt || out.batch() != groups || out.size() != 2 || out.words() != groups * 2 * poly)
+        throw Exception(ErrorCode::INVALID_ARGUMENT, "make_grouped_key: target on this context, key [ceil(Ld / n_special)][2][L][N]");
+    dpfhe_ctx* h = handle_of(ctx);
+    std::vector<uint64_t> host(poly);
+    hip_check(hipMemcpy(host.data(), d_target_ntt, poly * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    for (size_t l = 0; l < L; ++l) {   // P T limb-wise: P mod q_l on the data limbs, 0 on the special ones
+        const uint64_t q = p.moduli[l];
+        uint64_t f = l < Ld ? 1 : 0;
+        for (size_t k = Ld; k < L && l < Ld; ++k) f = (uint64_t)((unsigned __int128)f * (p.moduli[k] % q) % q);
+        for (size_t k = 0; k < n; ++k) host[l * n + k] = (uint64_t)((unsigned __int128)host[l * n + k] * f % q);
+    }
+    PolyBuffer scaled(ctx, 1, 1, true), e(ctx, 1, 1, false), t(ctx, 1, 1, true);
+    scaled.copy_from_host(host.data());
+    for (size_t d = 0; d < groups; ++d) {   // draw order as make_switch_key: all of a_d (limb-major), then the N errors
+        uint64_t* b = out.data() + (d * 2 + 0) * poly;
+        uint64_t* a = out.data() + (d * 2 + 1) * poly;
+        sample_uniform(impl_->rng, p, host.data());
+        upload(a, host);
+        sample_error(impl_->rng, p, host.data());
+        e.copy_from_host(host.data());
+        check(dpfhe_ntt_fwd(h, e.data(), 1, nullptr), "dpfhe_ntt_fwd");
+        check(dpfhe_dyadic_mul(h, t.data(), a, impl_->sk->ntt(), 1, nullptr), "dpfhe_dyadic_mul");
+        check(dpfhe_sub(h, b, e.data(), t.data(), 1, nullptr), "dpfhe_sub");                    // e_d - a_d s
+        check(dpfhe_add(h, t.data(), b, scaled.data(), 1, nullptr), "dpfhe_add");               // ... + P T, kept on the group's limbs only
+        const size_t l0 = d * n_special, count = std::min<size_t>(n_special, Ld - l0);
+        hip_check(hipMemcpyAsync(b + l0 * n, t.data() + l0 * n, count * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, nullptr), "hipMemcpyAsync");
+        ctx.synchronize();
+    }
+    out.set_ntt(true);
+}
+void KeyGenerator::make_grouped_galois_key(uint32_t galois_elt, uint32_t n_special, PolyBuffer& out) {
+    const size_t n = impl_->ctx->params().n();
+    if (!(galois_elt & 1u) || galois_elt >= 2 * n) throw Exception(ErrorCode::INVALID_ARGUMENT, "make_grouped_galois_key: element must be odd and < 2N");
+    PolyBuffer target = galois_target_ntt(*impl_->ctx, impl_->sk->coefficients(), galois_elt);
+    make_grouped_key(target.data(), n_special, out);
+}
+
 void KeyGenerator::create_public_key(PublicKey& out) { make_public_key(*impl_->ctx, *impl_->sk, impl_->rng, out, nullptr); }
 void KeyGenerator::create_public_key_seeded(PublicKey& out, Seed& seed_out) { make_public_key(*impl_->ctx, *impl_->sk, impl_->rng, out, &seed_out); }
 

@@ -1,5 +1,5 @@
-// fhe_keyswitch.cpp - the facade's hybrid key switcher (one special prime P): relinearisation and Galois keys on the extended context Q P and the
-// rotations built on them.  Part of libdpfhe_api.so (fhe_api.cpp names the other units); its keys are made by fhe_keys.cpp's make_switch_key.
+// fhe_keyswitch.cpp - the facade's hybrid key switchers: HybridKeySwitcher (one special prime P: relinearisation and Galois keys on the extended context Q P and
+// the rotations built on them) and, at the end, GroupedKeySwitcher (several special primes, grouped digits).  Part of libdpfhe_api.so (fhe_api.cpp names the other units); its keys are made by fhe_keys.cpp's make_switch_key.
 #include <algorithm>
 #include <cmath>
 
@@ -568,6 +568,65 @@ void SlotSum::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
         impl_->ks->rotate_sum_range(*cur, 0, T, impl_->stages[i], *dst, 0, s);
         cur = dst;
     }
+}
+
+// ---- GroupedKeySwitcher ---------------------------------------------------------------------------------------------------
+class __attribute__((visibility("hidden"))) GroupedKeySwitcher::Impl {
+public:
+    const Context* ext = nullptr;
+    const PolyBuffer* relin = nullptr;
+    uint32_t alpha = 0;
+    size_t Ld = 0, groups = 0;
+    std::unique_ptr<PolyBuffer> digits, work;   // [batch * groups][1][L][N] and [batch][2][L][N]
+    void run(const char* what, const Ciphertext& in, uint32_t comps, const PolyBuffer& key, Ciphertext& out2, Stream* s) {
+        const FheParams& pe = ext->params();
+        const size_t L = pe.n_limbs(), n = pe.n(), batch = in.batch();
+        if (in.is_ntt() || in.size() != comps || out2.size() != 2 || out2.batch() != batch || in.words() != batch * comps * Ld * n || out2.words() != batch * 2 * Ld * n ||
+            key.batch() != groups || key.size() != 2 || key.words() != groups * 2 * L * n)
+            throw Exception(ErrorCode::INVALID_ARGUMENT, std::string(what) + ": coefficient-domain ciphertexts on the data limbs, key [groups][2][L][N] on the extended context");
+        if (batch == 0) return;
+        grow_scratch(digits, batch * groups, [&](size_t b) { return new PolyBuffer(*ext, b, 1, true); });
+        grow_scratch(work, batch, [&](size_t b) { return new PolyBuffer(*ext, b, 2, false); });
+        check(dpfhe_switch_key_grouped(handle_of(*ext), out2.data(), in.data(), comps, alpha, key.data(), digits->data(), work->data(), batch, s), "dpfhe_switch_key_grouped");
+        out2.set_ntt(false);
+    }
+};
+
+GroupedKeySwitcher::GroupedKeySwitcher(const Context& ext_ctx, uint32_t n_special) : impl_(new Impl) {
+    const size_t L = ext_ctx.params().n_limbs();
+    if (n_special == 0 || n_special >= L) throw Exception(ErrorCode::INVALID_ARGUMENT, "GroupedKeySwitcher: n_special must be in [1, L)");
+    impl_->ext = &ext_ctx;
+    impl_->alpha = n_special;
+    impl_->Ld = L - n_special;
+    impl_->groups = (impl_->Ld + n_special - 1) / n_special;
+    // the warm-up call: checks P >= D_max and makes the context's digit-group tables, so that no later call uploads anything
+    check(dpfhe_switch_key_grouped(handle_of(ext_ctx), nullptr, nullptr, 3, n_special, nullptr, nullptr, nullptr, 0, nullptr), "dpfhe_switch_key_grouped (warm-up)");
+}
+GroupedKeySwitcher::~GroupedKeySwitcher() = default;
+size_t GroupedKeySwitcher::groups() const { return impl_->groups; }
+void GroupedKeySwitcher::set_relin_key(const PolyBuffer& key) { impl_->relin = &key; }
+
+double GroupedKeySwitcher::noise_bound() const {
+    const FheParams& p = impl_->ext->params();
+    long double ratio = 0;   // D_max / P: each group's product over P, factor by factor (a short group divides by the special primes it has no partner for)
+    for (size_t d = 0; d < impl_->groups; ++d) {
+        long double r = 1;
+        for (size_t k = 0; k < impl_->alpha; ++k) {
+            const size_t l = d * impl_->alpha + k;
+            r *= (l < impl_->Ld ? (long double)p.moduli[l] : 1.0L) / (long double)p.moduli[impl_->Ld + k];
+        }
+        ratio = std::max(ratio, r);
+    }
+    const double N = (double)p.n();
+    return (double)(impl_->groups * N * ratio * 21.0L / 2.0L) * (1.0 + std::ldexp(1.0, -40)) + (N + 1) / 2;
+}
+
+void GroupedKeySwitcher::relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* s) {
+    if (!impl_->relin) throw Exception(ErrorCode::INVALID_STATE, "GroupedKeySwitcher::relinearize: no key (set_relin_key first)");
+    impl_->run("GroupedKeySwitcher::relinearize", in3, 3, *impl_->relin, out2, s);
+}
+void GroupedKeySwitcher::switch_key(const Ciphertext& in2, const PolyBuffer& key, Ciphertext& out2, Stream* s) {
+    impl_->run("GroupedKeySwitcher::switch_key", in2, 2, key, out2, s);
 }
 
 }  // namespace fhe

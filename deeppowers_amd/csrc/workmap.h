@@ -285,6 +285,38 @@ constexpr size_t mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return 
 constexpr size_t mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return groups * n_limbs * (size_t)chunks_of(n); }
 
 // ------------------------------------------------------------------------------------------------
+// Key switching with grouped digits (keyswitch_grouped.h): both kernels own whole COLUMNS of coefficient pairs, so neither map has a limb in it.
+//   lift     digit_group_lift_kernel: id = (item * groups + group) * chunks + chunk - a workgroup reads the group's rows of its chunk once and writes all L rows;
+//   moddown  grouped_moddown_kernel:  id = (item * 2 + component) * chunks + chunk - a workgroup reads the special rows of its chunk once and walks the data limbs.
+// Every id is live (a ring below one chunk idles its upper threads).  `plan` is the launch and the entry's "too large for one launch" bound; it refuses a
+// shape without work or without a data limb left.
+// ------------------------------------------------------------------------------------------------
+struct GroupedKsPlan { unsigned groups; size_t lift_grid, moddown_grid; bool ok; };
+struct GroupLiftWork { size_t item; int group, chunk; };
+struct GroupedModdownWork { size_t item; int comp, chunk; };
+struct GroupedKsMap {
+    static DPF_HD GroupedKsPlan plan(size_t batch, unsigned n_limbs, unsigned n_special, size_t n) {
+        GroupedKsPlan p{0, 0, 0, false};
+        if (batch == 0 || n_special == 0 || n_special >= n_limbs || n == 0) return p;
+        const size_t chunks = (size_t)chunks_of(n), cap = 0x7fffffffu;
+        p.groups = (n_limbs - n_special + n_special - 1) / n_special;
+        if (batch > cap / ((size_t)p.groups * chunks) || batch > cap / (2 * chunks)) return p;
+        p.lift_grid = batch * p.groups * chunks;
+        p.moddown_grid = batch * 2 * chunks;
+        p.ok = true;
+        return p;
+    }
+    static DPF_HD GroupLiftWork lift(unsigned id, unsigned groups, int chunks) {
+        const ChunkWork w = chunk_work(id, chunks, groups);
+        return GroupLiftWork{w.poly, w.limb, w.chunk};
+    }
+    static DPF_HD GroupedModdownWork moddown(unsigned id, int chunks) {
+        const ChunkWork w = chunk_work(id, chunks, 2u);
+        return GroupedModdownWork{w.poly, w.limb, w.chunk};
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // All pairs of A resident operands and B streamed ones (kernels_mul.h tensor3_outer_kernel): outer = slab = (limb, 512-word chunk), inner = tile of
 // kMulOuterTile resident operands.  A workgroup keeps its tile's chunk in registers and walks the streamed operands' chunk; the `tiles` workgroups of a slab read
 // the SAME streamed rows, so they share ONE XCD, consecutive in its order: the rows come from HBM once and are L2 hits for the other tiles.  Ids of a last,

@@ -451,6 +451,30 @@ class Evaluator:
         _cabi.check(fn(self.ctx.handle, out.data_ptr(), d.data_ptr(), key.data_ptr(), work.data_ptr(), batch, self._sp(stream)), "dpfhe_*_hybrid")
         return Ciphertext(out, False)
 
+    def switch_key_grouped(self, ct: Ciphertext, keys: torch.Tensor, n_special: int, stream=None) -> Ciphertext:
+        """Hybrid key switching with grouped digits (dpfhe_switch_key_grouped): THIS evaluator's context is the extended one whose last n_special limbs are
+        the special primes; `ct` ([batch][2|3][Ld][N], coefficient domain) lives on the first Ld = L - n_special limbs.  keys: [ceil(Ld / n_special)][2][L][N],
+        NTT domain, key_d = (-(a_d s) + e_d + P G_d T, a_d).  3 components: relinearisation; 2: the key switch after an automorphism."""
+        p = self.ctx.params
+        L, n = p.n_limbs, p.n
+        if not 0 < n_special < L:
+            raise _cabi.DpfheError(2000, "switch_key_grouped: n_special must leave a data limb")
+        Ld = L - n_special
+        groups = -(-Ld // n_special)
+        d = ct.data
+        if ct.is_ntt or ct.size not in (2, 3) or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "switch_key_grouped: coefficient-domain [batch][2|3][L-n_special][N] ciphertexts on the extended context")
+        if tuple(keys.shape) != (groups, 2, L, n):
+            raise _cabi.DpfheError(2000, "keys must be [ceil((L-n_special)/n_special)][2][L][N]")
+        self._chk(keys)
+        batch = d.shape[0]
+        out = self._empty((batch, 2, Ld, n), stream)
+        digits = self._empty((batch, groups, L, n), stream)
+        work = self._empty((batch, 2, L, n), stream)
+        _cabi.check(self._lib.dpfhe_switch_key_grouped(self.ctx.handle, out.data_ptr(), d.data_ptr(), ct.size, n_special, keys.data_ptr(), digits.data_ptr(),
+                                                       work.data_ptr(), batch, self._sp(stream)), "dpfhe_switch_key_grouped")
+        return Ciphertext(out, False)
+
     def relinearize_rescale_hybrid(self, ct3: Ciphertext, key: torch.Tensor, stream=None) -> Ciphertext:
         """A relinearised product at the next level (dpfhe_relinearize_rescale_hybrid): the words of rescale(keyswitch_hybrid(ct3, key)) with one
         rounding pass.  THIS evaluator's context is the extended one; ct3: [batch][3][L-1][N], key as for keyswitch_hybrid -> [batch][2][L-2][N]."""

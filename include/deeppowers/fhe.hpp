@@ -410,6 +410,12 @@ public:
     void create_relin_keys_seeded(RelinKeys& out, Seed& seed_out);
     void create_galois_keys_seeded(GaloisKeys& out, Seed& seed_out);
     void create_public_key_seeded(PublicKey& out, Seed& seed_out);
+    // Grouped hybrid keys (GroupedKeySwitcher below): this generator's context is the EXTENDED one, its last n_special limbs the special primes (product P).
+    // out: [ceil(Ld / n_special)][2][L][N], NTT domain, key_d = (-(a_d s) + e_d + P G_d T, a_d), G_d = 1 modulo the limbs of digit group d and 0 modulo every
+    // other data limb.  d_target_ntt: T on this context, NTT domain, all L limbs - secret_key().ntt_squared() for relinearisation; the Galois form takes
+    // T = sigma_g(s).  INVALID_ARGUMENT for n_special == 0 or >= L or an `out` of another shape.
+    void make_grouped_key(const uint64_t* d_target_ntt, uint32_t n_special, PolyBuffer& out);
+    void make_grouped_galois_key(uint32_t galois_elt, uint32_t n_special, PolyBuffer& out);
 
 private:
     class Impl;
@@ -671,6 +677,38 @@ public:
                        size_t out_first, Stream* stream = nullptr) const;
     // One HybridKeySwitcher serves ONE stream at a time: its scratch buffers and its cache of packed keys are shared by every call
     // (and by every PackedLinear built on it); calls on different streams must be ordered by the caller.
+
+private:
+    class Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// GroupedKeySwitcher: hybrid key switching with alpha = n_special special primes and alpha data limbs per digit (dpfhe_switch_key_grouped).  ext_ctx has
+// L = Ld + alpha limbs, the last alpha special (product P); ciphertexts live on a context of its first Ld limbs.  Digit group d covers the data limbs
+// [d alpha, min((d + 1) alpha, Ld)), beta = ceil(Ld / alpha) groups of product D_d; the digit is the centred x_d in (-D_d / 2, D_d / 2], x_d = c mod D_d.
+// Rows: a switch lifts and transforms beta (Ld + alpha) rows per item and streams a key of beta 2 (Ld + alpha) rows, where HybridKeySwitcher's one prime and
+// one limb per digit take Ld (Ld + 1) and Ld 2 (Ld + 1): 48 against 156 at Ld = 12, alpha = 4.
+// Noise: sum_d x_d key_d = (sum_d x_d e_d) + P c T over Q P (sum_d x_d G_d = c modulo Q), so after the division by P the result is the switched ciphertext
+// plus E / P + rounding, E = sum_d x_d e_d.  A coefficient of x_d e_d is a sum of N products with |x_d| <= D_d / 2 and |e_d| <= B, so
+//   |E| / P <= beta N D_max B / (2 P),  D_max = max_d D_d,
+// about beta N D_max sigma / P for errors of deviation sigma (B = 2 sigma); KeyGenerator's centred-binomial errors have B = 21 (sigma = 3.24).  The rounding adds
+// r0 + r1 s with |r| <= 1 / 2 per coefficient: at most (N + 1) / 2 under a ternary s.  noise_bound() is the sum of the two at B = 21, per coefficient of the
+// phase.  P < D_max is refused (INVALID_STATE): the division would not tame E.
+// The object holds the scratch (digits beta L N and work 2 L N words per item, grown only for a larger batch than ever before); the digit-group tables live on
+// ext_ctx, made once by the constructor's warm-up call, so relinearize and switch_key only enqueue on `stream`.  ext_ctx and the keys must outlive the object.
+class GroupedKeySwitcher {
+public:
+    GroupedKeySwitcher(const Context& ext_ctx, uint32_t n_special);
+    ~GroupedKeySwitcher();
+    GroupedKeySwitcher(const GroupedKeySwitcher&) = delete;
+    GroupedKeySwitcher& operator=(const GroupedKeySwitcher&) = delete;
+    size_t groups() const;                         // beta
+    double noise_bound() const;
+    void set_relin_key(const PolyBuffer& key);     // KeyGenerator::make_grouped_key(secret_key().ntt_squared(), n_special, key); kept by pointer
+    // 3 -> 2 components, coefficient domain, on the data limbs: (c0, c1) + round(sum_d x_d(c2) key_d / P).  INVALID_STATE before set_relin_key.
+    void relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* stream = nullptr);
+    // (c0, 0) + round(sum_d x_d(c1) key_d / P): the key switch after an automorphism, key from make_grouped_galois_key
+    void switch_key(const Ciphertext& in2, const PolyBuffer& key, Ciphertext& out2, Stream* stream = nullptr);
 
 private:
     class Impl;

@@ -270,6 +270,30 @@ int dpfhe_relinearize_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_
 int dpfhe_switch_key_hybrid(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, const uint64_t* d_key, uint64_t* d_work,
                             size_t batch, void* stream);
 
+/* -- hybrid key switching with GROUPED digits and SEVERAL special primes: ctx_ext has L = Ld + n_special limbs, the last n_special (alpha) of them special, product
+ * P; data live on the first Ld limbs.  Digit group d covers the data limbs [d alpha, min((d + 1) alpha, Ld)), beta = ceil(Ld / alpha) groups, the last one
+ * possibly short; D_d is the product of the group's limbs.  With c = component in_components - 1 of d_in [batch][in_components][Ld][N] (coefficient domain,
+ * canonical), the digit of group d is, per coefficient, the CENTRED integer x_d in (-D_d / 2, D_d / 2] with x_d = c mod D_d - the representative
+ * dpfhe_base_extend reconstructs.  d_key: [beta][2][L][N], NTT domain, key_d = (-(a_d s) + e_d + P G_d T, a_d) with G_d = 1 modulo the limbs of group d and 0
+ * modulo every other data limb.  Result (coefficient domain, Ld limbs):
+ *   d_out2 [batch][2][Ld][N] = (c0, c1 or 0) + round(INTT(sum_d NTT(x_d mod every limb) (.) key_d) / P)
+ * - the addend is (c0, c1) for in_components = 3 (relinearisation) and (c0, 0) for 2 (after an automorphism); round is dpfhe_scale_round's with multiplier 1,
+ * dropping the special limbs (P is odd: the centred remainder has no tie).  A switch lifts and transforms beta (Ld + alpha) rows per item and streams a key
+ * of beta 2 (Ld + alpha) rows, where the one-prime form above takes Ld (Ld + 1) and Ld 2 (Ld + 1): 48 against 156 rows at Ld = 12, alpha = 4.
+ * Noise: the division leaves about beta N D_max sigma / P (D_max the largest D_d, sigma the key noise's deviation) plus the rounding's (N + 1) / 2.
+ * NOT word-identical to dpfhe_switch_key_hybrid at alpha = 1, whose digits are read in [0, q_j).  Word for word this composition: dpfhe_base_extend per group
+ * (the group's limbs onto all L) -> dpfhe_ntt_fwd -> dpfhe_dyadic_mul / _mul_add over the groups -> dpfhe_ntt_inv -> dpfhe_scale_round(drop the special limbs,
+ * keep the data limbs, multiplier 1) -> dpfhe_add; that is 3 beta + 5 launches against 5 + the transforms' here, and every digit row is read once.
+ * Scratch: d_digits batch * beta * L * N words, d_work batch * 2 * L * N words, exactly.  The three written buffers overlap nothing.  Enqueues only, every
+ * log2_n (8 ... 16), once the context has its table for this n_special ((beta + 1) x 3 KiB, uploaded synchronously by the first call that needs it): a call
+ * with batch == 0 is the WARM-UP - it checks n_special, in_components and P >= max_d D_d, makes the table and touches no buffer - so a caller that captures
+ * a stream or counts on enqueue-only calls warms up first (the C++ GroupedKeySwitcher does in its constructor).  Later calls allocate nothing beyond what the
+ * composed transforms lease above log2_n = 13.  Generic arithmetic in its two own kernels (csrc/keyswitch_grouped.h), the context's classes in the transforms.
+ * DPFHE_INVALID_ARGUMENT, before the device is touched: n_special 0, above 10 or >= L; in_components not 2 or 3; L above 20 (dpfhe_base_extend's limit); a null
+ * or misaligned (16 bytes) buffer; overlapping buffers; a grid too large for one launch.  DPFHE_INVALID_STATE: P < max_d D_d. */
+int dpfhe_switch_key_grouped(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in, uint32_t in_components, uint32_t n_special, const uint64_t* d_key,
+                             uint64_t* d_digits, uint64_t* d_work, size_t batch, void* stream);
+
 /* -- a relinearised product at the next level in one call (the approximate family's ciphertext x ciphertext step): dpfhe_relinearize_hybrid and the
  * dpfhe_rescale that follows it, with ONE rounding pass instead of two.  ctx_ext, d_in3, d_key, d_work (batch * 2 * L * N words) and the overlap rules are
  * dpfhe_relinearize_hybrid's; d_out2 is [batch][2][Ld-1][N], coefficient domain, on the data context's first Ld - 1 limbs:

@@ -134,6 +134,26 @@ u64 wm_mul_sum_grid(size_t groups, size_t n_limbs, size_t n) { return mul_sum_gr
 // products with a shared complement factor: the grid; ids decode through wm_chunk_decode over all limbs, the group in the polynomial's place
 u64 wm_mul_complement_grid(size_t groups, size_t n_limbs, size_t n) { return mul_complement_grid(groups, n_limbs, n); }
 
+// key switching with grouped digits: the plan -> the lift's grid (groups, the last pass's grid and ok through the pointers); the lift's rows
+// (item, group, chunk) and the last pass's rows (item, component, chunk)
+u64 wm_grouped_ks_plan(size_t batch, unsigned n_limbs, unsigned n_special, size_t n, unsigned* groups, u64* moddown_grid, int* ok) {
+    const GroupedKsPlan p = GroupedKsMap::plan(batch, n_limbs, n_special, n);
+    *groups = p.groups; *moddown_grid = p.moddown_grid; *ok = p.ok;
+    return p.lift_grid;
+}
+void wm_grouped_lift_decode(unsigned n_ids, unsigned groups, int chunks, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const GroupLiftWork w = GroupedKsMap::lift(id, groups, chunks);
+        out[3 * id] = (i64)w.item; out[3 * id + 1] = w.group; out[3 * id + 2] = w.chunk;
+    }
+}
+void wm_grouped_moddown_decode(unsigned n_ids, int chunks, i64* out) {
+    for (unsigned id = 0; id < n_ids; ++id) {
+        const GroupedModdownWork w = GroupedKsMap::moddown(id, chunks);
+        out[3 * id] = (i64)w.item; out[3 * id + 1] = w.comp; out[3 * id + 2] = w.chunk;
+    }
+}
+
 // all pairs of resident and streamed operands: the grid of a launch over a_count resident ones, and per id the row (limb, chunk, tile, live, keys walked,
 // rows of the tile); wm_mul_outer_pairs lists what ONE id writes, as the kernel's loops do: rows (output item, local row i, local key j), returns their number
 int wm_mul_outer_tile() { return kMulOuterTile; }
