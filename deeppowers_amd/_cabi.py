@@ -56,6 +56,8 @@ SYMBOLS = {
     "dpfhe_rotate_add_hybrid": ([C.c_void_p, _U64P, _U64P, C.POINTER(C.c_uint32), _U64P, _U64P, _U64P, C.c_size_t, C.c_size_t, C.c_void_p], C.c_int),
     "dpfhe_rotate_add_pass_host": ([C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t], C.c_int),
     "dpfhe_rotate_sum_hoisted": ([C.c_void_p, _U64P, _U64P, C.c_size_t, C.POINTER(C.c_uint32), _U64P, C.c_size_t, _U64P, _U64P, _U64P, C.c_void_p], C.c_int),
+    "dpfhe_rotate_sum_hoisted_grouped": ([C.c_void_p, _U64P, _U64P, C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32), _U64P, C.c_size_t, _U64P, _U64P, _U64P,
+                                          C.c_void_p], C.c_int),
     "dpfhe_rotate_matvec_hoisted_qp": ([C.c_void_p, _U64P, _U64P, _U64P, C.c_size_t, C.POINTER(C.c_uint32), _U64P, C.c_size_t, C.c_size_t, _U64P, _U64P,
                                         C.c_void_p], C.c_int),
     "dpfhe_switch_key_grouped": ([C.c_void_p, _U64P, _U64P, C.c_uint32, C.c_uint32, _U64P, _U64P, _U64P, C.c_size_t, C.c_void_p], C.c_int),

@@ -5,7 +5,7 @@
 //   cabi_mul.hip        ciphertext multiply, its traced form, sums of products, all-pairs products     (kernels_mul.h, mul_sum.h, mul_outer.h)
 //   cabi_keyswitch.hip  key switching (RNS-digit and hybrid keys), rescales, host twins of the fused rescales  (kernels_keyswitch.h)
 //   cabi_rotate.hip     Galois automorphisms, batched and hoisted rotations, the rotate-and-add ladder (kernels_rotate.h, rotate_add.h)
-//   cabi_rotate_sum.hip hoisted slot sums: R rotations of an item summed under one digit lift          (kernels_rotate_sum.h)
+//   cabi_rotate_sum.hip hoisted slot sums: R rotations of an item summed under one digit lift, one-prime and grouped-digit keys  (kernels_rotate_sum.h)
 //   cabi_rotate_matvec.hip  the baby steps of a packed layer times their diagonals, one pass       (rotate_matvec.h)
 //   cabi_keyswitch_grouped.hip  hybrid key switching with grouped digits and several special primes  (keyswitch_grouped.h)
 //   cabi_linalg.hip     matrix-vector products, shard-local sums                                       (kernels_linalg.h)
@@ -322,3 +322,9 @@ int key_switch_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_
 bool key_products_fit(const dpfhe_ctx* c, size_t batch, size_t key_stride, unsigned key_group);
 int key_products_hybrid(dpfhe_ctx* c, const char* what, int in_comps, uint64_t* d_work, const uint64_t* d_in, const uint64_t* d_key, size_t batch, hipStream_t s,
                         size_t key_stride, unsigned key_group);
+// what the hoisted slot sums on grouped digits borrow from grouped key switching (cabi_keyswitch_grouped.hip): the device table of (context, alpha) - made once,
+// synchronously, with the verdict P >= max_d D_d; later calls return at once - and its two kernels: lift = digit_group_lift_kernel (out = the digits, a = the
+// input whose component in_comps - 1 is lifted; b and add_mask unused), otherwise grouped_moddown_kernel (out = round(a / P) + the components of b in add_mask)
+int grouped_table(dpfhe_ctx* c, uint32_t alpha, unsigned groups, const char* what);
+void launch_grouped(uint32_t alpha, bool lift, const GroupedKsPlan& plan, hipStream_t s, u64* out, const u64* a, const u64* b, int in_comps, int add_mask,
+                    const BaseExtArgs* tabs, const dpfhe_ctx* c, int n_data, int chunks);

@@ -27,8 +27,8 @@ static bool less_than(const std::vector<uint64_t>& a, const std::vector<uint64_t
 // The device table of (context, alpha): BaseExtArgs[groups + 1] - block d: digit group d onto all L limbs; the last block: the special limbs onto the data limbs,
 // with P^-1 (dpfhe_scale_round's constants at multiplier 1).  Made ONCE per (context, alpha), by the first call that gets this far - a call with batch == 0 is
 // the warm-up that does nothing else: the verdict P >= max_d D_d, the constants (host only, before the device is touched), then one synchronous upload under
-// a guard of its own.  Every later call reads the pointer and nothing else.
-static int grouped_table(dpfhe_ctx* c, uint32_t alpha, unsigned groups, const char* what) {
+// a guard of its own.  Every later call reads the pointer and nothing else.  (cabi.h: dpfhe_rotate_sum_hoisted_grouped shares the table.)
+int grouped_table(dpfhe_ctx* c, uint32_t alpha, unsigned groups, const char* what) {
     std::lock_guard<std::mutex> lock(c->grouped_mutex);
     if (c->grouped_tabs[alpha].load(std::memory_order_relaxed)) return DPFHE_SUCCESS;
     const uint32_t L = c->n_limbs, Ld = L - alpha;
@@ -49,20 +49,20 @@ static int grouped_table(dpfhe_ctx* c, uint32_t alpha, unsigned groups, const ch
 }
 
 template <int NS>
-static void launch_grouped_kernels(bool lift, const GroupedKsPlan& plan, hipStream_t s, u64* out, const u64* a, const u64* b, int in_comps, const BaseExtArgs* tabs,
-                                   const dpfhe_ctx* c, int n_data, int chunks) {
+static void launch_grouped_kernels(bool lift, const GroupedKsPlan& plan, hipStream_t s, u64* out, const u64* a, const u64* b, int in_comps, int add_mask,
+                                   const BaseExtArgs* tabs, const dpfhe_ctx* c, int n_data, int chunks) {
     const int L = (int)c->n_limbs, n = 1 << c->log2n;
     if (lift)
         hipLaunchKernelGGL((digit_group_lift_kernel<NS>), dim3((unsigned)plan.lift_grid), dim3(256), 0, s, out, a, in_comps, tabs, c->lc, n_data, L, plan.groups, n, chunks);
     else
-        hipLaunchKernelGGL((grouped_moddown_kernel<NS>), dim3((unsigned)plan.moddown_grid), dim3(256), 0, s, out, a, b, in_comps, tabs + plan.groups, c->lc, n_data, L, n,
+        hipLaunchKernelGGL((grouped_moddown_kernel<NS>), dim3((unsigned)plan.moddown_grid), dim3(256), 0, s, out, a, b, in_comps, add_mask, tabs + plan.groups, c->lc, n_data, L, n,
                            chunks);
 }
 // one kernel pair per number of special primes (the digit arrays are indexed at compile time)
-static void launch_grouped(uint32_t alpha, bool lift, const GroupedKsPlan& plan, hipStream_t s, u64* out, const u64* a, const u64* b, int in_comps, const BaseExtArgs* tabs,
-                           const dpfhe_ctx* c, int n_data, int chunks) {
+void launch_grouped(uint32_t alpha, bool lift, const GroupedKsPlan& plan, hipStream_t s, u64* out, const u64* a, const u64* b, int in_comps, int add_mask,
+                    const BaseExtArgs* tabs, const dpfhe_ctx* c, int n_data, int chunks) {
     static_assert(kGroupedMaxSpecial == 10, "one case per number of special primes below");
-#define GROUPED_CASE(NS) case NS: launch_grouped_kernels<NS>(lift, plan, s, out, a, b, in_comps, tabs, c, n_data, chunks); break;
+#define GROUPED_CASE(NS) case NS: launch_grouped_kernels<NS>(lift, plan, s, out, a, b, in_comps, add_mask, tabs, c, n_data, chunks); break;
     switch (alpha) { GROUPED_CASE(1) GROUPED_CASE(2) GROUPED_CASE(3) GROUPED_CASE(4) GROUPED_CASE(5) GROUPED_CASE(6) GROUPED_CASE(7) GROUPED_CASE(8) GROUPED_CASE(9)
                      GROUPED_CASE(10) default: break; }
 #undef GROUPED_CASE
@@ -99,7 +99,7 @@ extern "C" int dpfhe_switch_key_grouped(dpfhe_ctx* c, uint64_t* d_out2, const ui
     DPFHE_ON_DEVICE(c, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // 1. the centred digit of every group on every limb of Q P;  2. their transforms
-    launch_grouped(alpha, true, plan, s, d_digits, d_in, nullptr, (int)in_components, tabs, c, (int)Ld, chunks);
+    launch_grouped(alpha, true, plan, s, d_digits, d_in, nullptr, (int)in_components, 0, tabs, c, (int)Ld, chunks);
     if (int rc = check_launch("digit group lift kernel launch")) return rc;
     if (int rc = ntt_launch_items(c, false, d_digits, d_digits, batch * groups, 0, s)) return rc;
     // 3. sum_d digit_d (.) key_d over Q P;  4. back to coefficients
@@ -107,6 +107,6 @@ extern "C" int dpfhe_switch_key_grouped(dpfhe_ctx* c, uint64_t* d_out2, const ui
     if (int rc = check_launch("key inner product kernel launch")) return rc;
     if (int rc = ntt_launch_items(c, true, d_work, d_work, batch * 2, 0, s)) return rc;
     // 5. divide by P with rounding, add (c0, c1 or 0)
-    launch_grouped(alpha, false, plan, s, d_out2, d_work, d_in, (int)in_components, tabs, c, (int)Ld, chunks);
+    launch_grouped(alpha, false, plan, s, d_out2, d_work, d_in, (int)in_components, in_components == 3 ? 3 : 1, tabs, c, (int)Ld, chunks);
     return check_launch("grouped division launch");
 }

@@ -486,6 +486,8 @@ void HybridKeySwitcher::switch_key_qp(const Ciphertext& in2, size_t in_first, co
 class __attribute__((visibility("hidden"))) SlotSum::Impl {
 public:
     HybridKeySwitcher* ks = nullptr;
+    GroupedKeySwitcher* gks = nullptr;           // the grouped-digit form: every stage through gks->rotate_sum_range with the stage's own keys
+    std::vector<std::unique_ptr<PolyBuffer>> stage_keys;
     size_t block = 0, stride = 0, radix = 2;
     std::vector<uint32_t> elts;                  // every element, in the order it is used
     std::vector<std::vector<uint32_t>> stages;   // radix > 2: the elements of each hoisted stage (empty for the ladder)
@@ -499,13 +501,44 @@ static std::vector<size_t> slot_sum_radices(size_t block, size_t radix) {
     return rho;
 }
 
-SlotSum::SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride, size_t radix) : impl_(new Impl) {
-    const FheParams& p = ks.data_context().params();
-    const size_t n = p.n();
+static void check_slot_sum_shape(size_t n, size_t block, size_t stride, size_t radix) {
     auto pow2 = [](size_t v) { return v && !(v & (v - 1)); };
     if (!pow2(block) || !pow2(stride) || block < 2 || stride > n / 2 || block > n / 2 / stride)
         throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum: block and stride must be powers of two with block >= 2 and block * stride <= N / 2");
     if (!pow2(radix) || radix < 2 || radix > 64) throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum: radix must be a power of two in [2, 64]");
+}
+
+SlotSum::SlotSum(GroupedKeySwitcher& ks, KeyGenerator& keygen, size_t block, size_t stride, size_t radix) : impl_(new Impl) {
+    const Context& ext = ks.extended_context();
+    const size_t n = ext.params().n(), key_words = ks.groups() * 2 * ext.params().n_limbs() * n;
+    check_slot_sum_shape(n, block, stride, radix);
+    impl_->gks = &ks;
+    impl_->block = block;
+    impl_->stride = stride;
+    impl_->radix = radix;
+    uint64_t g = 3;   // 3^stride mod 2N, then stage by stage as below: g^k, k = 1 .. rho - 1, the next stage's g is g^rho
+    for (size_t v = stride; v > 1; v >>= 1) g = g * g % (2 * n);
+    PolyBuffer one(ext, ks.groups(), 2, true);
+    for (size_t rho : slot_sum_radices(block, radix)) {
+        std::vector<uint32_t> st;
+        uint64_t e = g;
+        for (size_t k = 1; k < rho; ++k, e = e * g % (2 * n)) st.push_back((uint32_t)e);
+        std::unique_ptr<PolyBuffer> keys(new PolyBuffer(ext, st.size() * ks.groups(), 2, true));
+        for (size_t r = 0; r < st.size(); ++r) {
+            keygen.make_grouped_galois_key(st[r], ks.n_special(), one);
+            hip_check(hipMemcpy(keys->data() + r * key_words, one.data(), key_words * sizeof(uint64_t), hipMemcpyDeviceToDevice), "hipMemcpy D2D");
+        }
+        impl_->elts.insert(impl_->elts.end(), st.begin(), st.end());
+        impl_->stages.push_back(st);
+        impl_->stage_keys.push_back(std::move(keys));
+        g = e;
+    }
+}
+
+SlotSum::SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride, size_t radix) : impl_(new Impl) {
+    const FheParams& p = ks.data_context().params();
+    const size_t n = p.n();
+    check_slot_sum_shape(n, block, stride, radix);
     impl_->ks = &ks;
     impl_->block = block;
     impl_->stride = stride;
@@ -552,6 +585,15 @@ double SlotSum::error_bound(uint32_t log2_n, const std::vector<uint64_t>& data_m
     return pre + u8 * N * (B * max_abs_input + pre);
 }
 double SlotSum::error_bound(double scale, double max_abs_input, double input_noise_bound) const {
+    if (impl_->gks) {   // the header's derivation with noise_bound() = K_g + H in K + H's place
+        const BoundUnits bu(impl_->gks->extended_context().params().log2_n);
+        const double N = bu.N, H = bu.H, B = (double)impl_->block, KH = impl_->gks->noise_bound();
+        double roundings = 0, after = 1;
+        const std::vector<size_t> rho = slot_sum_radices(impl_->block, impl_->radix);
+        for (size_t s = rho.size(); s-- > 0; after *= (double)rho[s]) roundings += after;
+        const double pre = N * (B * input_noise_bound + (impl_->radix == 2 ? (B - 1) * KH : (B - 1) * (KH - H) + roundings * H)) / scale;
+        return pre + bu.u8 * N * (B * max_abs_input + pre);
+    }
     const FheParams& pe = impl_->ks->extended_context().params();
     return error_bound(pe.log2_n, std::vector<uint64_t>(pe.moduli.begin(), pe.moduli.end() - 1), pe.moduli.back(), impl_->block, scale, max_abs_input,
                        input_noise_bound, impl_->radix);
@@ -559,13 +601,14 @@ double SlotSum::error_bound(double scale, double max_abs_input, double input_noi
 
 void SlotSum::apply(const Ciphertext& x, Ciphertext& y, Stream* s) const {
     if (x.batch() == 0 || y.batch() != x.batch()) throw Exception(ErrorCode::INVALID_ARGUMENT, "SlotSum::apply: T items in, T items out");
-    if (impl_->radix == 2) return impl_->ks->rotate_add_range(x, 0, x.batch(), impl_->elts, y, 0, s);
+    if (!impl_->gks && impl_->radix == 2) return impl_->ks->rotate_add_range(x, 0, x.batch(), impl_->elts, y, 0, s);
     const size_t S = impl_->stages.size(), T = x.batch();
-    if (S > 1) grow_scratch(impl_->pong, T, [&](size_t b) { return new Ciphertext(impl_->ks->data_context(), 2, b); });
+    if (S > 1) grow_scratch(impl_->pong, T, [&](size_t b) { return new Ciphertext(impl_->gks ? x.context() : impl_->ks->data_context(), 2, b); });
     const Ciphertext* cur = &x;
     for (size_t i = 0; i < S; ++i) {   // the stages ping-pong so that the last one lands in y
         Ciphertext* dst = ((S - 1 - i) & 1) ? impl_->pong.get() : &y;
-        impl_->ks->rotate_sum_range(*cur, 0, T, impl_->stages[i], *dst, 0, s);
+        if (impl_->gks) impl_->gks->rotate_sum_range(*cur, 0, T, impl_->stages[i], *impl_->stage_keys[i], *dst, 0, s);
+        else impl_->ks->rotate_sum_range(*cur, 0, T, impl_->stages[i], *dst, 0, s);
         cur = dst;
     }
 }
@@ -578,6 +621,7 @@ public:
     uint32_t alpha = 0;
     size_t Ld = 0, groups = 0;
     std::unique_ptr<PolyBuffer> digits, work;   // [batch * groups][1][L][N] and [batch][2][L][N]
+    std::unique_ptr<Ciphertext> in_ntt;         // rotate_sum_range: the items' transforms on the data limbs
     void run(const char* what, const Ciphertext& in, uint32_t comps, const PolyBuffer& key, Ciphertext& out2, Stream* s) {
         const FheParams& pe = ext->params();
         const size_t L = pe.n_limbs(), n = pe.n(), batch = in.batch();
@@ -605,6 +649,8 @@ GroupedKeySwitcher::GroupedKeySwitcher(const Context& ext_ctx, uint32_t n_specia
 GroupedKeySwitcher::~GroupedKeySwitcher() = default;
 size_t GroupedKeySwitcher::groups() const { return impl_->groups; }
 void GroupedKeySwitcher::set_relin_key(const PolyBuffer& key) { impl_->relin = &key; }
+const Context& GroupedKeySwitcher::extended_context() const { return *impl_->ext; }
+uint32_t GroupedKeySwitcher::n_special() const { return impl_->alpha; }
 
 double GroupedKeySwitcher::noise_bound() const {
     const FheParams& p = impl_->ext->params();
@@ -627,6 +673,25 @@ void GroupedKeySwitcher::relinearize(const Ciphertext& in3, Ciphertext& out2, St
 }
 void GroupedKeySwitcher::switch_key(const Ciphertext& in2, const PolyBuffer& key, Ciphertext& out2, Stream* s) {
     impl_->run("GroupedKeySwitcher::switch_key", in2, 2, key, out2, s);
+}
+
+void GroupedKeySwitcher::rotate_sum_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& elts, const PolyBuffer& keys, Ciphertext& out2,
+                                          size_t out_first, Stream* s) {
+    if (count == 0) return;
+    const FheParams& pe = impl_->ext->params();
+    const size_t L = pe.n_limbs(), n = pe.n(), Ld = impl_->Ld, G = impl_->groups, ct_words = 2 * Ld * n;
+    if (elts.empty() || elts.size() > 64 || in2.is_ntt() || in2.size() != 2 || out2.size() != 2 || in2.words() != in2.batch() * ct_words ||
+        out2.words() != out2.batch() * ct_words || in_first + count > in2.batch() || out_first + count > out2.batch() || keys.size() != 2 ||
+        keys.words() != elts.size() * G * 2 * L * n)
+        throw Exception(ErrorCode::INVALID_ARGUMENT,
+                        "GroupedKeySwitcher::rotate_sum_range: 1 .. 64 elements with one key [groups][2][L][N] each, count coefficient-domain items of the data limbs in and out");
+    grow_scratch(impl_->in_ntt, count, [&](size_t b) { return new Ciphertext(in2.context(), 2, b, true); });
+    grow_scratch(impl_->digits, count * G, [&](size_t b) { return new PolyBuffer(*impl_->ext, b, 1, true); });
+    grow_scratch(impl_->work, count, [&](size_t b) { return new PolyBuffer(*impl_->ext, b, 2, false); });   // the items' sums over Q P
+    check(dpfhe_rotate_sum_hoisted_grouped(handle_of(*impl_->ext), out2.data() + out_first * ct_words, in2.data() + in_first * ct_words, count, impl_->alpha, elts.data(),
+                                           keys.data(), elts.size(), impl_->in_ntt->data(), impl_->digits->data(), impl_->work->data(), s),
+          "dpfhe_rotate_sum_hoisted_grouped");
+    out2.set_ntt(false);
 }
 
 }  // namespace fhe

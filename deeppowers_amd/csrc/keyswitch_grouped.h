@@ -95,12 +95,12 @@ __global__ __launch_bounds__(256) void digit_group_lift_kernel(u64* __restrict__
     }
 }
 
-// out [batch][2][n_data][N] <- round(work / P) + addend: work [batch][2][L][N] over Q P (coefficient domain), the addend components 0 and - in_comps == 3 - 1 of
-// in [batch][in_comps][n_data][N].  a: the division's block (the NS = alpha special limbs as sources, the data limbs as destinations, Q_inv = P^-1).
+// out [batch][2][n_data][N] <- round(work / P) + addend: work [batch][2][L][N] over Q P (coefficient domain), the addend the components of add_mask (bit c:
+// component c; 1 after an automorphism, 3 for a relinearisation and for the hoisted slot sums, whose input has two components) of in [batch][in_comps][n_data][N].  a: the division's block (the NS = alpha special limbs as sources, the data limbs as destinations, Q_inv = P^-1).
 // round(X / P) = (X - r) / P with r the centred remainder: dpfhe_scale_round with multiplier 1.
 template <int NS>
 __global__ __launch_bounds__(256) void grouped_moddown_kernel(u64* __restrict__ out, const u64* __restrict__ work, const u64* __restrict__ in, int in_comps,
-                                                              const BaseExtArgs* __restrict__ tab, const LimbConst* __restrict__ lcs, int n_data, int n_limbs, int n,
+                                                              int add_mask, const BaseExtArgs* __restrict__ tab, const LimbConst* __restrict__ lcs, int n_data, int n_limbs, int n,
                                                               int chunks) {
     const GroupedModdownWork wk = GroupedKsMap::moddown(blockIdx.x, chunks);
     const int w0 = wk.chunk * 512 + threadIdx.x * 2;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void grouped_moddown_kernel(u64* __restrict__ 
         va[k] = x.a; vb[k] = x.b;
     }
     const bool na = grouped_digits<NS>(va, a, lcs, NS), nb = grouped_digits<NS>(vb, a, lcs, NS);
-    const bool add = wk.comp == 0 || in_comps == 3;
+    const bool add = (add_mask >> wk.comp) & 1;
     const u64* cp = in + (wk.item * in_comps + wk.comp) * (size_t)n_data * n + w0;
     u64* op = out + (wk.item * 2 + wk.comp) * (size_t)n_data * n + w0;
 #pragma unroll 1

@@ -630,6 +630,33 @@ class Evaluator:
                                                        digits.data_ptr(), sum_qp.data_ptr(), self._sp(stream)), "dpfhe_rotate_sum_hoisted")
         return Ciphertext(out, False)
 
+    def rotate_sum_hoisted_grouped(self, ct: Ciphertext, galois_elts, keys: torch.Tensor, n_special: int, stream=None) -> Ciphertext:
+        """rotate_sum_hoisted on grouped-digit keys (dpfhe_rotate_sum_hoisted_grouped): THIS evaluator's context is the extended one whose last n_special limbs
+        are the special primes; `ct` ([T][2][Ld][N], coefficient domain) lives on the first Ld = L - n_special limbs.  keys: [len(elts)][beta][2][L][N] with
+        beta = ceil(Ld / n_special), each the layout of switch_key_grouped's key for its element.  ct_t + round(INTT(S_t) / P), P the special primes' product."""
+        p = self.ctx.params
+        L, n = p.n_limbs, p.n
+        if not 0 < n_special < L:
+            raise _cabi.DpfheError(2000, "rotate_sum_hoisted_grouped: n_special must leave a data limb")
+        Ld = L - n_special
+        groups = -(-Ld // n_special)
+        d = ct.data
+        k = len(galois_elts)
+        if ct.is_ntt or ct.size != 2 or d.dim() != 4 or d.shape[-2] != Ld or d.shape[-1] != n or d.dtype != torch.int64 or not d.is_contiguous():
+            raise _cabi.DpfheError(2000, "rotate_sum_hoisted_grouped: coefficient-domain [T][2][L-n_special][N] ciphertexts on the extended context")
+        if k == 0 or tuple(keys.shape) != (k, groups, 2, L, n) or keys.dtype != torch.int64 or not keys.is_contiguous():
+            raise _cabi.DpfheError(2000, "keys must be [k][ceil((L-n_special)/n_special)][2][L][N], k >= 1")
+        T = d.shape[0]
+        out = self._empty((T, 2, Ld, n), stream)
+        in_ntt = self._empty((T, 2, Ld, n), stream)
+        digits = self._empty((T, groups, L, n), stream)
+        sum_qp = self._empty((T, 2, L, n), stream)
+        elts = (C.c_uint32 * k)(*[int(g) for g in galois_elts])
+        _cabi.check(self._lib.dpfhe_rotate_sum_hoisted_grouped(self.ctx.handle, out.data_ptr(), d.data_ptr(), T, n_special, elts, keys.data_ptr(), k,
+                                                               in_ntt.data_ptr(), digits.data_ptr(), sum_qp.data_ptr(), self._sp(stream)),
+                    "dpfhe_rotate_sum_hoisted_grouped")
+        return Ciphertext(out, False)
+
     def rotate_matvec_hoisted_qp(self, W: torch.Tensor, ct: Ciphertext, galois_elts, keys: torch.Tensor, stream=None) -> torch.Tensor:
         """The first two stages of a packed layer in one call (dpfhe_rotate_matvec_hoisted_qp): [T][2][L-1][N] coefficient-domain inputs on the extended
         context and W [rows][1 + k][L][N] (NTT, column 0 for the un-rotated input) -> [rows][T][2][L][N], NTT domain over Q P: the words of

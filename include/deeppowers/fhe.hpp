@@ -709,6 +709,15 @@ public:
     void relinearize(const Ciphertext& in3, Ciphertext& out2, Stream* stream = nullptr);
     // (c0, 0) + round(sum_d x_d(c1) key_d / P): the key switch after an automorphism, key from make_grouped_galois_key
     void switch_key(const Ciphertext& in2, const PolyBuffer& key, Ciphertext& out2, Stream* stream = nullptr);
+    // A hoisted slot-sum stage on grouped-digit keys (dpfhe_rotate_sum_hoisted_grouped): out item out_first + i = in item in_first + i plus the sum of its
+    // rotations by galois_elts (1 .. 64), under ONE lift of the beta group digits.  keys: galois_elts.size() keys of make_grouped_galois_key back to back, key r
+    // for element r ([n_rot * beta][2][L][N] on ext_ctx).  Ranges, aliasing and the stream contract as HybridKeySwitcher::rotate_sum_range: `in2` and `out2` may
+    // be one buffer when the ranges do not overlap; enqueues only; the scratch (transformed inputs, digits, the sums over Q P) is the object's own, grown only for
+    // a larger count than ever before.  Each rotation adds at most noise_bound() - (N + 1) / 2, the one division's rounding (N + 1) / 2.
+    void rotate_sum_range(const Ciphertext& in2, size_t in_first, size_t count, const std::vector<uint32_t>& galois_elts, const PolyBuffer& keys, Ciphertext& out2,
+                          size_t out_first, Stream* stream = nullptr);
+    const Context& extended_context() const;
+    uint32_t n_special() const;
 
 private:
     class Impl;
@@ -800,12 +809,20 @@ private:
 //   ONCE, so an error e becomes rho e + (rho - 1) K + H; with f = e + K this is f -> rho f + H, and after all stages
 //     e = block (Bin + K) - K + H sum_s prod_{u>s} rho_u      (radix 2: the sum is block - 1, the ladder's bound; otherwise smaller)
 //   takes the place of block Bin + (block - 1) (K + H) in `pre`; the rest of the bound is unchanged.
+//
+// Grouped-digit keys.  The GroupedKeySwitcher form runs EVERY stage, radix 2 included (one element per stage), as one GroupedKeySwitcher::rotate_sum_range.  A
+//   stage is the same recurrence - rho - 1 key-switched rotations, one rounding - with the grouped switch's error per rotation in K's place:
+//   ks.noise_bound() = K_g + H with K_g = beta N D_max 21 / (2 P), so K + H becomes ks.noise_bound() and K becomes ks.noise_bound() - H above
+//   (radix 2: block Bin + (block - 1) ks.noise_bound()).  Nothing else in the bound changes.
 class SlotSum {
 public:
     // block, stride: powers of two, block >= 2, block * stride <= N/2 (INVALID_ARGUMENT otherwise).  Adds the elements 3^(stride 2^e) mod 2N, e < log2(block),
     // to `ks` in ascending order of e; `ks` must outlive the object.  radix: a power of two in [2, 64] (INVALID_ARGUMENT otherwise); above 2 it adds the stages'
     // elements instead, stage by stage, k ascending.
     SlotSum(HybridKeySwitcher& ks, size_t block, size_t stride = 1, size_t radix = 2);
+    // The same sums on grouped-digit keys: the stages' keys are made here, once, with keygen.make_grouped_galois_key (keygen on ks.extended_context()) and kept
+    // by the object, one buffer per stage; every stage is one ks.rotate_sum_range.  Same elements per radix as above (radix 2: one element per stage).
+    SlotSum(GroupedKeySwitcher& ks, KeyGenerator& keygen, size_t block, size_t stride = 1, size_t radix = 2);
     ~SlotSum();
     SlotSum(const SlotSum&) = delete;
     SlotSum& operator=(const SlotSum&) = delete;

@@ -423,6 +423,33 @@ int dpfhe_rotate_add_pass_host(const uint64_t* moduli, uint32_t n_limbs, uint32_
 int dpfhe_rotate_sum_hoisted(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, const uint32_t* galois_elts, const uint64_t* d_keys,
                              size_t n_rot, uint64_t* d_in_ntt, uint64_t* d_digits, uint64_t* d_sum_qp, void* stream);
 
+/* -- N3, hoisted slot sums on GROUPED-digit keys ("grouped" = the digit groups of dpfhe_switch_key_grouped, not the token groups of dpfhe_rotate_hybrid_grouped).
+ * ctx_ext has L = Ld + alpha limbs, the last alpha = n_special of them special, product P; the groups and the centred digits x_d, d < beta = ceil(Ld / alpha),
+ * are exactly dpfhe_switch_key_grouped's.  For item t with ct_t = (c0, c1) of d_in2 [n_items][2][Ld][N] (coefficient domain, canonical), the elements
+ * g_0 .. g_{R-1} of galois_elts (HOST array, R = n_rot, odd, < 2N) and key_r = block r of d_keys, each [beta][2][L][N], NTT domain, the layout of
+ * dpfhe_switch_key_grouped's key for sigma_{g_r} (KeyGenerator::make_grouped_galois_key), n_rot of them back to back:
+ *   S_t.c0 = sum_r ( sum_{d<beta} perm_{g_r}(NTT(x_d(c1) mod every limb)) (.) key_{r,d,0} + P perm_{g_r}(NTT(c0)) )     mod q_l, every limb l of Q P
+ *   S_t.c1 = sum_r   sum_{d<beta} perm_{g_r}(NTT(x_d(c1) mod every limb)) (.) key_{r,d,1}
+ *   d_out2 item t = ct_t + round(INTT(S_t) / P)       both components; round is dpfhe_switch_key_grouped's: the centred remainder modulo the odd P, special limbs dropped
+ * perm_g is the automorphism as a gather in the NTT domain (forward-output order); P perm(c0) is (P mod q_l) * word on a data limb and zero on every special limb.
+ * With n_rot = 1 the words are those of the automorphism sigma_g on ct, dpfhe_switch_key_grouped with in_components = 2 and dpfhe_add of the input, for two
+ * reasons: the centred digit commutes with the automorphism because every D_d is odd (sigma_g permutes coefficients up to sign, and -x_d is the centred digit
+ * of -c: no tie at D_d / 2), so lifting before or after sigma_g gives the same words; and P sigma_g(c0) is an exact multiple of P, so it passes through the
+ * rounded division as sigma_g(c0) exactly, whether it is added over Q P or after the division.
+ * Rows against dpfhe_rotate_sum_hoisted on the same Ld data limbs under one special prime, per item: beta (Ld + alpha) digit rows lifted and transformed against
+ * Ld (Ld + 1); R (beta + 1) key-product terms per output word of a data limb (R beta on a special limb) against R (Ld + 1); keys of beta 2 (Ld + alpha) rows
+ * against Ld 2 (Ld + 1) per rotation.  At Ld = 12, alpha = 4: 48 rows against 156, 4 terms per rotation against 13.
+ * The sum kernel is dpfhe_rotate_sum_hoisted's (one workgroup per output segment, limb and tile of 4 items, sums in registers, each output word stored once).
+ * Scratch, exactly: d_in_ntt n_items * 2 * Ld * N words; d_digits n_items * beta * L * N words; d_sum_qp n_items * 2 * L * N words.  The four written buffers
+ * overlap nothing; the input and the keys may overlap each other.  The device table of (context, n_special) is the one dpfhe_switch_key_grouped makes: the first
+ * call of either entry makes it synchronously, and a call with n_items == 0 (n_special and n_rot valid, buffers not looked at) is the WARM-UP here, as batch == 0
+ * is there.  After it the entry only enqueues on the caller's stream, every log2_n (8 ... 16); it allocates nothing beyond what the composed transforms lease
+ * above log2_n = 13.  Generic arithmetic in the lift and the division, the context-wide arithmetic (fold on an all-fold context) in the sum kernel, the context's
+ * classes in the transforms.  DPFHE_INVALID_ARGUMENT, before the device is touched: n_special 0, above 10 or >= L; L above 20; n_rot outside [1, 64]; an even
+ * element or one >= 2N; a null or misaligned (16 bytes) buffer; overlapping buffers; a grid too large for one launch.  DPFHE_INVALID_STATE: P < max_d D_d. */
+int dpfhe_rotate_sum_hoisted_grouped(dpfhe_ctx* ctx_ext, uint64_t* d_out2, const uint64_t* d_in2, size_t n_items, uint32_t n_special, const uint32_t* galois_elts,
+                                     const uint64_t* d_keys, size_t n_rot, uint64_t* d_in_ntt, uint64_t* d_digits, uint64_t* d_sum_qp, void* stream);
+
 /* -- N3, round 3: baby-step / giant-step sums with the division by P DEFERRED ("double hoisting", Bossuat-Mouchet-Troncoso-Pastoriza-
  * Hubaux 2021).  A rotated term is kept in the NTT domain over the extended basis Q P as  P sigma_g(ct) + key-switching noise;
  * plaintext products and sums are taken there, and one inverse transform + divide-by-P is paid per SUM, not per rotation.
